@@ -12,9 +12,16 @@ result records (96-byte plsvo_pose_record: pose + n_tracked, num_obs_pt, num_obs
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline`, `cpu_baseline` and -- default
-workload, one GPU -- `latency`: the small-batch operating points (1 / 8 / 64 streams resident, what a live camera or
-BASELINE config 4's 8 streams per GPU see) and the C++ drop-in's per-call wall time including the PCIe upload.
+Prints ONE JSON line on rank 0 with the headline figure (`value` frames/s, `ms_per_step`), the `roofline` of the dominant kernel
+and the per-kernel times of the timed steps themselves.  A plain run does nothing else: set up, warm up, time the K steps, write
+the outputs (--dump-outputs DIR), print the line.
+--full adds everything that takes runs or checks of its own: the other launch-order policy (`launch_order.value_other_policy`),
+the accuracy and oracle checks of the timed batch, `cpu_baseline`, per-shard step times (--config 4), the pose all-gather latency
+(N > 1 / --dist-selftest) and -- default workload, one GPU -- `latency`: the small-batch operating points (1 / 8 / 64 streams
+resident, what a live camera or BASELINE config 4's 8 streams per GPU see) and the C++ drop-in's per-call wall time including the
+PCIe upload, `launch_order.moving_inputs`, `host_fed` and `frame_chain`.
+--dump-outputs DIR writes what the last timed step computed, as the fetch calls return it, to DIR/<name>.npy (float64, masks
+float32; a fixed seeded sample of the streams where the whole would pass 64 MB); the inputs depend on the arguments only.
 Other workloads (extra lines for profiles/, the driver's invocation is the default one):
   --config 3   BASELINE configs[2]: 1280x720, 400 points + 150 segments, 5-image pyramid, levels 4..2
   --config 4   BASELINE configs[3]: 64 streams in eight shards of 8 (one shard per GPU at --gpus 8; on fewer GPUs a rank runs its
@@ -498,6 +505,176 @@ def chain_leg(P, torch, dev, stream, streams, cfg, n_streams=4096, steps=10, cpu
         ctx.close()
 
 
+def _host_inputs_chunk(args):
+    """worker of host_inputs: the synthetic streams and pose-optimiser frames of a run of seeds"""
+    seeds, cfg, pose_only = args
+    synth = importlib.import_module("pl-svo_amd").synth
+    W, H = cfg["W"], cfg["H"]
+    streams = [] if pose_only else [synth.make_align_stream(s_, W, H, cfg["pts"], cfg["seg"], max_level=cfg["maxl"]) for s_ in seeds]
+    frames = [synth.make_poseopt_frame(s_, cfg["pose_pts"], cfg["pose_seg"], W, H) for s_ in seeds]
+    return streams, frames
+
+
+def host_inputs(seeds, cfg, pose_only, workers):
+    """(streams, pose frames) of the seeds.  Every stream is drawn from its own seed, so a pool of fresh interpreters (started before
+    this process touches the GPU) returns exactly what one process would; at the default batch it cuts the set-up by a minute."""
+    if workers <= 1 or len(seeds) < 2048:
+        return _host_inputs_chunk((seeds, cfg, pose_only))
+    import multiprocessing as mp
+    step = -(-len(seeds) // (4 * workers))
+    parts = [(seeds[i:i + step], cfg, pose_only) for i in range(0, len(seeds), step)]
+    try:
+        with mp.get_context("spawn").Pool(workers) as pool:
+            done = pool.map(_host_inputs_chunk, parts)
+    except Exception as e:    # no process pool here (no POSIX semaphores, a __main__ the workers cannot import): the same inputs, drawn in this process
+        print(f"bench.py: input pool unavailable ({e}); drawing the inputs in one process", file=sys.stderr)
+        return _host_inputs_chunk((seeds, cfg, pose_only))
+    return [s_ for d in done for s_ in d[0]], [f for d in done for f in d[1]]
+
+
+# One term of the texture sum of synth.render_streams -- acc += amp * sin(kx * a + ky * b + phase) -- as ONE elementwise kernel
+# instead of seven float64 passes over the image batch (the passes made the renderer ~25 s of the default run's set-up).  Same
+# operations in the same order, each rounded on its own (no fma contraction); render_streams_fast checks its first images against
+# synth.render_streams bit for bit and falls back to it on any difference.
+_TEX_TERM_SRC = """
+template <typename T> T tex_term(T acc, T a, T b, T kx, T ky, T ph, T amp) {
+#pragma clang fp contract(off)
+    T arg = kx * a;
+    arg = arg + ky * b;
+    arg = arg + ph;
+    T s = sin(arg);
+    return acc + amp * s;
+}
+"""
+
+
+def _render_fused(synth, torch, streams, dev, tex_term, noise_sigma=2.0, chunk=64):
+    """synth.render_streams(streams, device=dev) (both images, default noise) with the texture loop in tex_term"""
+    B = len(streams)
+    W, H = streams[0].W, streams[0].H
+    out = torch.empty((B, 2, H, W), dtype=torch.uint8, device=dev)
+    fx, fy, cx, cy = streams[0].cam[:4]
+    u = torch.arange(W, dtype=torch.float64, device=dev)
+    v = torch.arange(H, dtype=torch.float64, device=dev)
+    rays = torch.stack([((u - cx) / fx)[None, :].expand(H, W), ((v - cy) / fy)[:, None].expand(H, W),
+                        torch.ones((H, W), dtype=torch.float64, device=dev)], dim=-1)
+    for c0 in range(0, B, chunk):
+        sub = streams[c0:c0 + chunk]
+        b = len(sub)
+        t64 = lambda a: torch.as_tensor(np.stack(a), dtype=torch.float64, device=dev)
+        n = t64([s.plane_n for s in sub])
+        d = t64([np.array(s.plane_d) for s in sub])
+        e1 = t64([s.e1 for s in sub])
+        e2 = t64([s.e2 for s in sub])
+        tex = t64([s.tex for s in sub])
+        tnorm = t64([np.array(s.tex_norm) for s in sub])
+        gen = torch.Generator(device=dev)
+        for which in (0, 1):
+            if which == 0:
+                o = torch.zeros((b, 3), dtype=torch.float64, device=dev)
+                dirs = rays[None].expand(b, H, W, 3)
+            else:
+                R = t64([synth.quat_to_R(s.T_true[:4]) for s in sub])
+                t = t64([s.T_true[4:] for s in sub])
+                o = -torch.einsum("bji,bj->bi", R, t)
+                dirs = torch.einsum("bji,hwj->bhwi", R, rays)
+            nd = torch.einsum("bhwi,bi->bhw", dirs, n)
+            s_ = (d - torch.einsum("bi,bi->b", n, o))[:, None, None] / nd
+            X = o[:, None, None, :] + s_[..., None] * dirs
+            a = torch.einsum("bhwi,bi->bhw", X, e1)
+            bb = torch.einsum("bhwi,bi->bhw", X, e2)
+            acc = torch.zeros_like(a)
+            for k in range(tex.shape[1]):
+                acc = tex_term(acc, a, bb, tex[:, k, 0][:, None, None], tex[:, k, 1][:, None, None], tex[:, k, 2][:, None, None],
+                               tex[:, k, 3][:, None, None])
+            img = 128.0 + 45.0 * acc / tnorm[:, None, None]
+            img = img.clamp(16.0, 240.0)
+            if noise_sigma > 0:
+                gen.manual_seed(int(sub[0].seed) * 2 + which + 977)
+                img = img + noise_sigma * torch.randn(img.shape, dtype=torch.float64, device=dev, generator=gen)
+            out[c0:c0 + b, which] = img.round().clamp(0, 255).to(torch.uint8)
+    return out
+
+
+class StreamRenderer:
+    """synth.render_streams for the timed batch's staging: the fused texture term on a GPU once its first call has reproduced
+    synth.render_streams bit for bit, synth.render_streams itself otherwise (CPU dry run, no kernel compiler, any difference)"""
+
+    def __init__(self, synth, torch, dev):
+        self.synth, self.torch, self.dev, self.fn, self.checked = synth, torch, dev, None, False
+        if dev.type == "cuda":
+            try:
+                self.fn = torch.cuda.jiterator._create_jit_fn(_TEX_TERM_SRC)
+            except Exception as e:
+                print(f"bench.py: fused texture term unavailable ({str(e)[:120]}); rendering with synth.render_streams", file=sys.stderr)
+
+    def __call__(self, streams):
+        if self.fn is None:
+            return self.synth.render_streams(streams, device=self.dev)
+        try:
+            out = _render_fused(self.synth, self.torch, streams, self.dev, self.fn)
+        except Exception as e:
+            print(f"bench.py: fused texture term failed ({str(e)[:120]}); rendering with synth.render_streams", file=sys.stderr)
+            self.fn = None
+            return self.synth.render_streams(streams, device=self.dev)
+        if not self.checked:
+            ref = self.synth.render_streams(streams, device=self.dev)
+            self.checked = True
+            if not self.torch.equal(out, ref):
+                print("bench.py: fused texture term differs from synth.render_streams; rendering with synth.render_streams", file=sys.stderr)
+                self.fn = None
+                return ref
+        return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, align_res, pose_res, seeds):
+    """What the timed path's last step computed, as plsvo_align_fetch / plsvo_poseopt_fetch hand it to a caller, one DIR/<name>.npy per
+    field: per-stream records in float64, per-feature masks in float32 (padded with -1 to the longest list).  Records are kept for every
+    stream and masks for up to 8192 while that fits in DUMP_LIMIT_BYTES; beyond that a fixed, seeded sample of the streams is written,
+    whose stream seeds are stored beside it (`*_seed.npy`)."""
+    os.makedirs(out_dir, exist_ok=True)
+    seeds = np.asarray(seeds, dtype=np.float64)
+    rec, mask = {}, {}
+    if align_res:
+        rec["align_T_cur_from_ref"] = [r.T for r in align_res]
+        rec["align_H"] = [r.H.reshape(-1) for r in align_res]
+        for k in ("n_meas", "n_tracked", "chi2", "status"):
+            rec["align_" + k] = [getattr(r, k) for r in align_res]
+        rec["align_iters_per_level"] = [r.iters_per_level for r in align_res]
+        mask["align_seg_alive"] = [r.seg_alive for r in align_res]
+    rec["poseopt_T_f_w"] = [r.T for r in pose_res]
+    rec["poseopt_cov"] = [r.cov.reshape(-1) for r in pose_res]
+    for k in ("estimated_scale", "error_init", "error_final", "num_obs_pt", "num_obs_ls", "iters", "iters_ref", "status"):
+        rec["poseopt_" + k] = [getattr(r, k) for r in pose_res]
+    mask["poseopt_pt_keep"] = [r.pt_keep for r in pose_res]
+    mask["poseopt_seg_keep"] = [r.seg_keep for r in pose_res]
+    n = len(seeds)
+    rec = {k: np.asarray(v, dtype=np.float64) for k, v in rec.items()}
+    mask_w = {k: max([len(m) for m in v] + [1]) for k, v in mask.items()}
+    rec_b = sum(a.nbytes for a in rec.values()) // max(n, 1) + 8
+    mask_b = sum(4 * w for w in mask_w.values()) + 8
+    n_rec = min(n, (DUMP_LIMIT_BYTES // 2) // rec_b)
+    n_mask = min(n, 8192, (DUMP_LIMIT_BYTES - n_rec * rec_b) // mask_b)
+
+    def sample(k, tag):
+        if k >= n:
+            return np.arange(n)
+        idx = np.sort(np.random.default_rng(20240601).choice(n, k, replace=False))
+        np.save(os.path.join(out_dir, f"{tag}_seed.npy"), seeds[idx])
+        return idx
+    ri, mi = sample(n_rec, "records"), sample(n_mask, "masks")
+    for k, a in rec.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a[ri])
+    for k, v in mask.items():
+        a = np.full((len(mi), mask_w[k]), -1.0, dtype=np.float32)
+        for j, i in enumerate(mi):
+            a[j, :len(v[i])] = v[i]
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -510,6 +687,9 @@ def main():
     ap.add_argument("--no-latency", action="store_true", help="skip the small-batch / per-call latency leg")
     ap.add_argument("--dist-selftest", action="store_true", help="run the N>1 code path (process group, RCCL communicator, pose copy + "
                     "plsvo_gather_poses every step) with a single rank: what a 1-GPU box can exercise of it")
+    ap.add_argument("--full", action="store_true", help="also run every leg and check beyond the headline figure (other launch order, "
+                    "CPU baseline, latency, moving inputs, host-fed, frame chain, oracle / accuracy checks, per-shard and gather times)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy")
     args = ap.parse_args()
     cfg = CONFIGS[args.config]
     pose_only = args.config == 5
@@ -520,10 +700,24 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    P = importlib.import_module("pl-svo_amd")
+    capi, synth, abi, D = P.capi, P.synth, P.abi, P.dist
+    B = args.batch if args.batch > 0 else cfg["batch"]
+    W, H = cfg["W"], cfg["H"]
+    # shards: blocks of B streams with their own context.  Normally one per rank; BASELINE configs[3] fixes eight of them, so with
+    # fewer than eight ranks a rank owns several and runs them back to back.
+    shards_total = cfg.get("shards", world)
+    if shards_total % world:
+        raise SystemExit(f"--config {args.config} has {shards_total} shards: --gpus must divide it")
+    local_shards = shards_total // world
+    # the host-side inputs of every local shard, drawn before this process touches the GPU (1234 + global stream index)
+    shard_seeds = [D.rank_seeds(rank * local_shards + v, shards_total, B) for v in range(local_shards)]
+    workers = max(1, min(16, host_cores()) // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1"))))
+    shard_inputs = [host_inputs(sd, cfg, pose_only, workers) for sd in shard_seeds]
     # DRY RUN (tests/test_emu_parity.py only): PLSVO_BENCH_DRY_RUN=1 together with a host emulation build of the library runs this very
     # script on the CPU -- same staging, same calls, same JSON assembly, tiny batch -- so that a mistake in it shows up in the CPU suite
     # and not at the end of a round.  Its line says what it is; without the emulated library the variable has no effect.
-    dry = os.environ.get("PLSVO_BENCH_DRY_RUN") == "1" and hasattr(importlib.import_module("pl-svo_amd").capi.lib(), "plsvo_emu_build")
+    dry = os.environ.get("PLSVO_BENCH_DRY_RUN") == "1" and hasattr(capi.lib(), "plsvo_emu_build")
     if dry:
         global _DRY
         _DRY = True
@@ -548,18 +742,8 @@ def main():
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
     dev = torch.device("cpu") if dry else torch.device("cuda", local_rank)
 
-    P = importlib.import_module("pl-svo_amd")
-    capi, synth, abi, D = P.capi, P.synth, P.abi, P.dist
     if hasattr(capi.lib(), "plsvo_emu_build") and not dry:   # tests/host/build_emu.sh: the device sources on a CPU wave emulator -- a test vehicle, never a measurement
         raise SystemExit("bench.py: PLSVO_HIP_LIB names a host emulation build of the library; the benchmark runs the gfx950 library only")
-    B = args.batch if args.batch > 0 else cfg["batch"]
-    W, H = cfg["W"], cfg["H"]
-    # shards: blocks of B streams with their own context.  Normally one per rank; BASELINE configs[3] fixes eight of them, so with
-    # fewer than eight ranks a rank owns several and runs them back to back.
-    shards_total = cfg.get("shards", world)
-    if shards_total % world:
-        raise SystemExit(f"--config {args.config} has {shards_total} shards: --gpus must divide it")
-    local_shards = shards_total // world
 
     # ONE stream for everything: the library enqueues on it (plsvo_hip_create_on_stream), it is torch's current stream while the
     # benchmark runs, so torch.cuda.synchronize and the RCCL all-gather (plsvo_gather_poses, same stream) are ordered after the
@@ -568,25 +752,27 @@ def main():
     stream = torch.cuda.Stream(dev)
     with torch.cuda.stream(stream):
         shard = []      # per local shard: dict(ctx, streams, align_jobs, pose_frames, pose_jobs)
+        render = StreamRenderer(synth, torch, dev)                            # = synth.render_streams(sub, device=dev)
         for v in range(local_shards):
             c = capi.Context(local_rank, stream=stream.cuda_stream)
             c.set_launch_order_refresh(align=order_refresh, poseopt=order_refresh)
-            seeds = D.rank_seeds(rank * local_shards + v, shards_total, B)          # 1234 + global stream index
-            streams, align_jobs = [], []
+            streams, pose_frames = shard_inputs[v]
+            align_jobs, pose_jobs = [], []
             if not pose_only:
-                streams = [synth.make_align_stream(s_, W, H, cfg["pts"], cfg["seg"], max_level=cfg["maxl"]) for s_ in seeds]
                 c.config_pyramids(2 * B, W, H, cfg["pyr"])
                 chunk = 256 if W <= 640 else 64
                 for c0 in range(0, B, chunk):
                     sub = streams[c0:c0 + chunk]
-                    imgs = synth.render_streams(sub, device=dev)                      # [b, 2, H, W] u8 in HBM
+                    imgs = render(sub)                                                # [b, 2, H, W] u8 in HBM
                     c.build_pyramids_dev(2 * c0, 2 * len(sub), imgs.data_ptr(), W, W * H, 0)   # device half-sampler
+                    # the chunk's job descriptors are built while the GPU renders it
+                    align_jobs += [P.align_job_from_stream(s_, cfg["maxl"], cfg["minl"], ref_slot=2 * i, cur_slot=2 * i + 1) for i, s_ in enumerate(sub, c0)]
+                    pose_jobs += [P.poseopt_job_from_frame(f) for f in pose_frames[c0:c0 + chunk]]
                     c.synchronize()
                     del imgs
-                align_jobs = [P.align_job_from_stream(s_, cfg["maxl"], cfg["minl"], ref_slot=2 * i, cur_slot=2 * i + 1) for i, s_ in enumerate(streams)]
                 c.align_stage(align_jobs)      # features + job descriptors -> HBM; the timed region only launches kernels
-            pose_frames = [synth.make_poseopt_frame(s_, cfg["pose_pts"], cfg["pose_seg"], W, H) for s_ in seeds]
-            pose_jobs = [P.poseopt_job_from_frame(f) for f in pose_frames]
+            else:
+                pose_jobs = [P.poseopt_job_from_frame(f) for f in pose_frames]
             c.poseopt_stage(pose_jobs)
             c.synchronize()
             shard.append(dict(ctx=c, streams=streams, align_jobs=align_jobs, pose_frames=pose_frames, pose_jobs=pose_jobs))
@@ -621,8 +807,12 @@ def main():
                                                   gather=gather if (use_dist and not dry) else None, force_gather=args.dist_selftest)
         for sh in shard:
             sh["ctx"].set_profiling(False)
+        if args.dump_outputs:
+            align_out = [] if pose_only else [r for sh in shard for r in sh["ctx"].align_fetch()]
+            dump_outputs(args.dump_outputs if rank == 0 else os.path.join(args.dump_outputs, f"rank{rank}"), align_out,
+                         [r for sh in shard for r in sh["ctx"].poseopt_fetch()], [s_ for sd in shard_seeds for s_ in sd])
         other_policy = None
-        if world == 1 and not use_dist:
+        if args.full and world == 1 and not use_dist:
             # the same K steps under the OTHER launch-order policy (same protocol, one process: no barrier needed), reported beside `value`
             for sh in shard:
                 sh["ctx"].set_launch_order_refresh(align=not order_refresh, poseopt=not order_refresh)
@@ -639,7 +829,7 @@ def main():
             step_local()                        # the resident results / work counters read below are those of the line's own policy
             torch.cuda.synchronize(dev)
         gather_us = None
-        if comm is not None:
+        if comm is not None and args.full:
             # latency of the pose all-gather alone (plsvo_gather_poses = ncclAllGather on the library's stream): a baseline for the
             # first multi-GPU run to compare with.  8 records = BASELINE configs[3]'s per-GPU shard, n_local = this run's.
             torch.cuda.synchronize(dev)
@@ -655,6 +845,7 @@ def main():
                 torch.cuda.synchronize(dev)
                 gather_us[str(nrec)] = round((time.perf_counter() - t0) / 200 * 1e6, 2)
                 del outb
+        if comm is not None:
             torch.cuda.synchronize(dev)
             P.rccl.comm_destroy(comm)
 
@@ -666,8 +857,8 @@ def main():
                 lvl_ms += a_ms; lvl_launches += a_n
             p_ms, p_n = sh["ctx"].kernel_time(abi.K_POSEOPT)
             pose_ms += p_ms; pose_launches += p_n
-        res = [] if pose_only else ctx.align_fetch()
-        pres = ctx.poseopt_fetch()
+        res = [] if (pose_only or not args.full) else ctx.align_fetch()
+        pres = ctx.poseopt_fetch() if args.full else []
         result = None
         if rank == 0:
             frames = world * n_local * args.steps
@@ -768,7 +959,7 @@ def main():
                 result["config"]["library"] = os.path.basename(os.environ["PLSVO_HIP_LIB"])
                 if hasattr(capi.lib(), "plsvo_hip_build_flags"):
                     result["config"]["build_flags"] = (capi.lib().plsvo_hip_build_flags() or b"").decode().strip()
-            if local_shards > 1:
+            if local_shards > 1 and args.full:
                 # every shard alone: K steps, then a host synchronisation (what one GPU of the 8-GPU deployment would do per step)
                 per = []
                 for sh in shard:
@@ -784,7 +975,7 @@ def main():
                                        "frames_per_s_of_one_shard": round(B / float(np.mean(per)), 1),
                                        "note": f"{local_shards} shards of {B} streams run back to back on this GPU; with one shard per GPU the step "
                                                "time of the job is the slowest shard's (plus the pose all-gather): that run is the driver's --gpus 8"}
-            if not pose_only and hasattr(ctx.L, "plsvo_align_chi2_ties"):
+            if args.full and not pose_only and hasattr(ctx.L, "plsvo_align_chi2_ties"):
                 gn_it = gn_ties = gn_un = 0
                 for sh in shard:
                     a_, b_, c_ = sh["ctx"].align_chi2_ties()
@@ -792,12 +983,12 @@ def main():
                 result["chi2_ties"] = {"gn_iterations_per_step": int(gn_it), "decided_on_exact_float_sums": int(gn_ties), "near_ties_without_terms": int(gn_un),
                                        "what": "iterations whose `new_chi2 > chi2_` decision was taken on the reference's sequential float sums "
                                                "(the two values closer than the sums' own rounding noise)"}
-            if not pose_only:
+            if args.full and not pose_only:
                 errs = np.array([synth.se3_log_angle_dist(r.T, s.T_true) for r, s in zip(res[:64], streams[:64])])
                 result["accuracy_vs_truth"] = {"median_rot_rad": float(np.median(errs[:, 0])), "median_trans_m": float(np.median(errs[:, 1]))}
             # ---- CPU baseline: the oracle on a bounded sample of the same streams, on this box's host cores ----
             single_fps = None
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 from oracle import binding as ob
                 ob.build()
                 n_s = min(B, 64)
@@ -856,7 +1047,7 @@ def main():
                 result["speedup_vs_cpu_all_cores"] = round(value / (doneN / tcN), 1)
                 result["speedup_vs_cpu_1core"] = round(value / single_fps, 1)
             # ---- small batches and the drop-in's per-call latency (default workload, one GPU) ----
-            if world == 1 and args.config == 2 and not args.no_latency:
+            if args.full and world == 1 and args.config == 2 and not args.no_latency:
                 try:
                     result["latency"] = latency_leg(P, ctx, align_jobs, pose_jobs, streams, pose_frames, cfg, single_fps)
                     cb = result.get("cpu_baseline")
@@ -864,7 +1055,7 @@ def main():
                         result["latency"]["B8_vs_cpu_all_cores"] = round(result["latency"]["B8"]["frames_per_s"] / cb["value"], 2)
                 except Exception as e:   # an auxiliary leg never takes the headline line down
                     result["latency"] = {"error": str(e)[:300]}
-            if world == 1 and args.config == 2 and not args.no_latency and not args.dist_selftest:
+            if args.full and world == 1 and args.config == 2 and not args.no_latency and not args.dist_selftest:
                 try:
                     result["launch_order"]["moving_inputs"] = moving_leg(P, torch, dev, stream, streams, cfg, **({"n_streams": 8, "n_images": 2} if dry else {}))
                 except Exception as e:   # never take the headline line down

@@ -1,5 +1,6 @@
 """Host logic of bench.py that decides what the bench line may claim (no GPU): the hash that ties the offline counter traffic
-(profiles/hbm_traffic*.json) to the kernel sources it was measured on, and the synthetic moving-sequence inputs of the launch-order leg."""
+(profiles/hbm_traffic*.json) to the kernel sources it was measured on, the synthetic moving-sequence inputs of the launch-order leg,
+and the inputs and output files of a run (--dump-outputs)."""
 import importlib
 import json
 import os
@@ -72,3 +73,48 @@ def test_moving_sequence_inputs():
     assert np.array_equal(pair[0, 0].numpy(), ref[0].numpy()) and np.array_equal(pair[0, 1].numpy(), cur[0].numpy())
     other = sy.render_views([st], [ind[0]], noise_sigma=0.0)
     assert not np.array_equal(other[0].numpy(), cur[0].numpy())
+
+
+def test_host_inputs_from_a_pool_equal_the_serial_ones():
+    """bench.py draws the streams of a large batch in a pool of fresh interpreters: every field must be what one process draws"""
+    seeds = P.dist.rank_seeds(0, 1, 2048)
+    for c in (2, 5):
+        cfg = bench.CONFIGS[c]
+        a = bench.host_inputs(seeds, cfg, c == 5, 1)
+        b = bench.host_inputs(seeds, cfg, c == 5, 2)
+        assert [len(x) for x in a] == [len(x) for x in b] == [0 if c == 5 else 2048, 2048]
+        for la, lb in zip(a, b):
+            for x, y in zip(la, lb):
+                assert x.__dict__.keys() == y.__dict__.keys()
+                for k, v in x.__dict__.items():
+                    w = y.__dict__[k]
+                    if isinstance(v, np.ndarray):
+                        assert v.dtype == w.dtype and v.tobytes() == w.tobytes(), (c, x.seed, k)
+                    else:
+                        assert v == w, (c, x.seed, k)
+
+
+def test_dump_outputs_stays_under_its_limit_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: float32 / float64 files only, at most 64 MB, and where the whole would not fit the same seeded sample every time"""
+    from types import SimpleNamespace as NS
+    n = 50000
+    rng = np.random.default_rng(3)
+    ar = [NS(T=rng.normal(size=7), H=np.zeros((6, 6)), n_meas=i, n_tracked=3, chi2=0.5, status=0, iters_per_level=[1, 2, 3, 0, 0, 0, 0, 0],
+             seg_alive=np.ones(80, np.uint8)) for i in range(n)]
+    pr = [NS(T=rng.normal(size=7), cov=np.eye(6), estimated_scale=1.0, error_init=2.0, error_final=1.0, num_obs_pt=200, num_obs_ls=80,
+             iters=10, iters_ref=0, status=0, pt_keep=np.ones(200 - i % 3, np.uint8), seg_keep=np.zeros(80, np.uint8)) for i in range(n)]
+    seeds = list(range(1234, 1234 + n))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), ar, pr, seeds)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) and "align_T_cur_from_ref.npy" in files and "poseopt_pt_keep.npy" in files
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), f
+    rec_seed = np.load(tmp_path / "a" / "records_seed.npy")
+    T = np.load(tmp_path / "a" / "align_T_cur_from_ref.npy")
+    assert 0 < len(rec_seed) < n and T.shape == (len(rec_seed), 7)
+    assert np.array_equal(T, np.stack([ar[int(s) - 1234].T for s in rec_seed]))
+    keep = np.load(tmp_path / "a" / "poseopt_pt_keep.npy")
+    assert keep.shape == (8192, 200) and set(np.unique(keep)) <= {-1.0, 1.0}

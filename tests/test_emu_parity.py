@@ -100,9 +100,9 @@ print("ok")
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout[-1500:] + out.stderr[-3000:]
 
 
-@pytest.mark.parametrize("argv", [["--batch", "8", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.4"],
-                                  ["--config", "5", "--batch", "6", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0.4"],
-                                  ["--config", "4", "--batch", "2", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"]], ids=["config2", "config5", "config4-shards"])
+@pytest.mark.parametrize("argv", [["--batch", "8", "--steps", "2", "--warmup", "1", "--full", "--cpu-seconds", "0.4"],
+                                  ["--config", "5", "--batch", "6", "--steps", "2", "--warmup", "1", "--full", "--cpu-seconds", "0.4"],
+                                  ["--config", "4", "--batch", "2", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline"]], ids=["config2", "config5", "config4-shards"])
 def test_bench_script_dry_run(emu_lib, argv):
     """bench.py itself -- staging, the timed control flow, the work counters, the roofline and CPU-baseline blocks, the JSON line --
     executed end to end on the CPU: PLSVO_BENCH_DRY_RUN=1 is honoured only together with the emulated library and the line says so.
@@ -139,6 +139,34 @@ def test_bench_script_dry_run(emu_lib, argv):
     if "--no-cpu-baseline" not in argv:
         cb = d["cpu_baseline"]
         assert cb["value"] > 0 and cb["cores"] >= 1 and cb["kind"] == "port" and cb["sample"]
+
+
+def test_bench_script_plain_run_is_lean_and_dumps_the_same_outputs_twice(emu_lib, tmp_path):
+    """A plain bench.py run (no --full): the headline fields and nothing measured or checked beside them, --steps timed steps, and
+    --dump-outputs writes the last timed step's results -- float32 / float64 only -- identically in two runs with the same arguments."""
+    import json
+    import numpy as np
+    env = emu_env(emu_lib)
+    env["PLSVO_BENCH_DRY_RUN"] = "1"
+    lines = []
+    for d in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "4", "--steps", "3", "--warmup", "1", "--dump-outputs",
+                              str(tmp_path / d)], env=env, capture_output=True, text=True, cwd=ROOT)
+        assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
+        lines += [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 2
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["roofline"]["launches"] == 3
+    for k in ("cpu_baseline", "latency", "host_fed", "frame_chain", "accuracy_vs_truth", "chi2_ties", "per_shard"):
+        assert k not in d, k
+    assert d["launch_order"]["value_other_policy"] is None and "moving_inputs" not in d["launch_order"]
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) and "align_T_cur_from_ref.npy" in files and "poseopt_T_f_w.npy" in files
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and x.shape[0] == 4 and np.array_equal(x, y, equal_nan=True), f
 
 
 @pytest.mark.parametrize("argv", [["--batch", "3", "--steps", "2", "--warmup", "1"], ["--config", "4", "--batch", "1", "--steps", "1", "--warmup", "0"]],

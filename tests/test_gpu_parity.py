@@ -1337,7 +1337,7 @@ def test_bench_distributed_branch_with_one_rank():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "4", "--steps", "3", "--warmup", "1", "--dist-selftest",
-                        "--no-cpu-baseline", "--no-latency"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
+                        "--full", "--no-cpu-baseline", "--no-latency"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)

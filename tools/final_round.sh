@@ -23,12 +23,12 @@ python $R/tools/hbm_traffic.py $O/pmc_c3_FETCH_SIZE.csv $O/pmc_c3_WRITE_SIZE.csv
        $R/profiles/r03_calib_FETCH_SIZE.csv $R/profiles/r03_calib_WRITE_SIZE.csv $R/profiles/r03_calib_known_bytes.json > $O/hbm_traffic_c3.log 2>&1; tail -c 200 $O/hbm_traffic_c3.log; echo
 cp $O/hbm_traffic_config3.json $R/profiles/hbm_traffic_config3.json
 rm -rf /tmp/kt
-timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/kt -- python $R/bench.py > $O/bench_stdout.txt 2> $O/bench_default.err
+timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/kt -- python $R/bench.py --full > $O/bench_stdout.txt 2> $O/bench_default.err
 grep '^{"metric"' $O/bench_stdout.txt | tail -1 > $O/bench_default.json; cut -c1-260 $O/bench_default.json
 DB=$(find /tmp/kt -name "*results.db" | paste -sd, -)
-python $R/tools/rocpd_summary.py "$DB" $O/kernel_trace_stats.csv "python bench.py (default: 32768 streams, 20 steps + 3 warm-up; MI355X); same run as bench_default.json"
+python $R/tools/rocpd_summary.py "$DB" $O/kernel_trace_stats.csv "python bench.py --full (default: 32768 streams, 20 steps + 3 warm-up; MI355X); same run as bench_default.json"
 cd $R
-timeout 600 python bench.py --config 3 > $O/bench_config3.json 2> $O/bench_config3.err; cut -c1-200 $O/bench_config3.json
-timeout 300 python bench.py --config 4 > $O/bench_config4.json 2> $O/bench_config4.err; cut -c1-200 $O/bench_config4.json
-timeout 300 python bench.py --config 5 > $O/bench_config5.json 2> $O/bench_config5.err; cut -c1-200 $O/bench_config5.json
+timeout 600 python bench.py --config 3 --full > $O/bench_config3.json 2> $O/bench_config3.err; cut -c1-200 $O/bench_config3.json
+timeout 300 python bench.py --config 4 --full > $O/bench_config4.json 2> $O/bench_config4.err; cut -c1-200 $O/bench_config4.json
+timeout 300 python bench.py --config 5 --full > $O/bench_config5.json 2> $O/bench_config5.err; cut -c1-200 $O/bench_config5.json
 head -9 $O/kernel_trace_stats.csv | tail -4

@@ -11,16 +11,16 @@ O=$R/gpurun_out/$TAG
 mkdir -p $O
 export TMPDIR=/tmp
 cd $R
-timeout 600 python bench.py --config 4 > $O/bench_config4.json 2> $O/bench_config4.err; cut -c1-200 $O/bench_config4.json
-timeout 600 python bench.py --config 5 > $O/bench_config5.json 2> $O/bench_config5.err; cut -c1-200 $O/bench_config5.json
+timeout 600 python bench.py --config 4 --full > $O/bench_config4.json 2> $O/bench_config4.err; cut -c1-200 $O/bench_config4.json
+timeout 600 python bench.py --config 5 --full > $O/bench_config5.json 2> $O/bench_config5.err; cut -c1-200 $O/bench_config5.json
 # default bench line + kernel trace of that same run
 cd /tmp
 rm -rf /tmp/kt
-timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/kt -- python $R/bench.py > $O/bench_stdout.txt 2> $O/bench_default.err
+timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/kt -- python $R/bench.py --full > $O/bench_stdout.txt 2> $O/bench_default.err
 grep '^{"metric"' $O/bench_stdout.txt | tail -1 > $O/bench_default.json
 cut -c1-300 $O/bench_default.json
 DB=$(find /tmp/kt -name "*results.db" | paste -sd, -)
-python $R/tools/rocpd_summary.py "$DB" $O/kernel_trace_stats.csv "python bench.py (default: 32768 streams, 20 steps + 3 warm-up; MI355X); same run as bench_default.json"
+python $R/tools/rocpd_summary.py "$DB" $O/kernel_trace_stats.csv "python bench.py --full (default: 32768 streams, 20 steps + 3 warm-up; MI355X); same run as bench_default.json"
 for C in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/cal_$C
   timeout 300 rocprofv3 --kernel-trace --pmc $C -d /tmp/cal_$C -- $R/tools/pmc_calib > $O/calib_$C.log 2>&1
@@ -44,5 +44,5 @@ done
 # config 3's own line, now that its traffic figure exists next to it
 cd $R
 mkdir -p profiles; cp $O/hbm_traffic.json profiles/hbm_traffic.json; cp $O/hbm_traffic_config3.json profiles/hbm_traffic_config3.json
-timeout 900 python bench.py --config 3 > $O/bench_config3.json 2> $O/bench_config3.err; cut -c1-300 $O/bench_config3.json
+timeout 900 python bench.py --config 3 --full > $O/bench_config3.json 2> $O/bench_config3.err; cut -c1-300 $O/bench_config3.json
 head -8 $O/kernel_trace_stats.csv

@@ -120,6 +120,41 @@ int plsvo_hip_copy_slots(plsvo_ctx* ctx, int dst_first, int src_first, int n);
 int plsvo_hip_download_level(plsvo_ctx* ctx, int slot, int level, uint8_t* out);
 
 /* ------------------------------------------------------------------------------------------ */
+/* rectification of raw distorted frames into pyramid slots                                   */
+/* replaces vk::PinholeCamera::undistortImage ([ext] vikit, an OpenCV initUndistortRectifyMap  */
+/* + remap) and the vertical flip before it (app/run_pipeline.cpp:397-411), followed by        */
+/* frame_utils::createImgPyramid (DESIGN.md "Rectification")                                  */
+/* ------------------------------------------------------------------------------------------ */
+
+/* radial-tangential pinhole camera: vk::PinholeCamera(w, h, fx, fy, cx, cy, d0, d1, d2, d3, d4),
+ * d = { k1, k2, p1, p2, k3 }.  fx..cy and d are rounded to float first, as vikit stores them.
+ * |d[0]| <= 1e-7 is vikit's identity branch: the frame is copied, whatever d[1..4] hold. */
+typedef struct plsvo_pinhole_radtan {
+  plsvo_pinhole cam;
+  double d[5];
+} plsvo_pinhole_radtan;
+
+#define PLSVO_MAX_RECTIFY_MAPS 8   /* rectification maps one ctx holds (one per camera of a rig) */
+
+/* Host-only helper (no device needed): the map OpenCV's initUndistortRectifyMap(K, D, I, K, size, CV_16SC2) builds for the camera,
+ * in OpenCV's form: xy = width*height pairs (x, y) of the top-left source tap, frac = width*height entries (fy & 31) * 32 + (fx & 31).
+ * This is the map of the parameters as given: the identity branch (|d[0]| <= 1e-7) is applied by the device calls, not here.
+ * PLSVO_E_INVALID (nothing written) for non-finite parameters or a size outside 1 .. 2046 in either direction. */
+int plsvo_rectify_map(const plsvo_pinhole_radtan* cam, int16_t* xy, uint16_t* frac);
+/* Build the camera's map once, pack it for the device and upload it: *map_id receives its handle (0 .. PLSVO_MAX_RECTIFY_MAPS-1).
+ * flip_vertical != 0: the raw frame is flipped vertically before the remap (run_pipeline does this for a negative fy).  The camera size
+ * must equal the level-0 size of plsvo_hip_config_pyramids (which must have been called); a re-configuration keeps the maps. */
+int plsvo_hip_config_rectify(plsvo_ctx* ctx, const plsvo_pinhole_radtan* cam, int flip_vertical, int* map_id);
+/* Rectify one raw host frame (stride_bytes per row) into level 0 of `slot` and build levels 1.. with the half-sampler (rounding as
+ * plsvo_hip_build_pyramid).  One PCIe copy of the raw frame; the tiled mirror is refreshed eagerly. */
+int plsvo_hip_rectify_build_pyramid(plsvo_ctx* ctx, int map_id, int slot, const uint8_t* raw, int stride_bytes, int rounding);
+/* Same, raw frames already in HBM: frame i at d_raw + i*image_pitch_bytes -> slot first_slot + i, i < n.
+ * Every error (unknown map, camera size != configured pyramid, slot range out of bounds, stride < width) is PLSVO_E_INVALID and
+ * writes nothing. */
+int plsvo_hip_rectify_build_pyramids_dev(plsvo_ctx* ctx, int map_id, int first_slot, int n, const void* d_raw,
+                                         int stride_bytes, size_t image_pitch_bytes, int rounding);
+
+/* ------------------------------------------------------------------------------------------ */
 /* sparse image alignment                                                                      */
 /* replaces plsvo::SparseImgAlign::run   (include/plsvo/sparse_img_align.h:64-66,              */
 /*                                        src/sparse_img_align.cpp:54-95; call sites           */

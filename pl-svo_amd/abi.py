@@ -28,6 +28,16 @@ class Pinhole(C.Structure):
                 ("width", C.c_int32), ("height", C.c_int32)]
 
 
+class PinholeRadtan(C.Structure):
+    """plsvo_pinhole_radtan: vk::PinholeCamera(w, h, fx, fy, cx, cy, d0..d4), d = (k1, k2, p1, p2, k3)"""
+    _fields_ = [("cam", Pinhole), ("d", C.c_double * 5)]
+
+
+def pinhole_radtan(width, height, fx, fy, cx, cy, d):
+    d = list(d) + [0.0] * (5 - len(d))
+    return PinholeRadtan(Pinhole(fx, fy, cx, cy, int(width), int(height)), (C.c_double * 5)(*[float(v) for v in d[:5]]))
+
+
 class AlignIn(C.Structure):
     _fields_ = [("ref_slot", C.c_int32), ("cur_slot", C.c_int32), ("cam", Pinhole),
                 ("max_level", C.c_int32), ("min_level", C.c_int32), ("n_iter", C.c_int32),

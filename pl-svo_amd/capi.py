@@ -19,6 +19,7 @@ SYMBOLS = [
     "plsvo_hip_create", "plsvo_hip_create_on_stream", "plsvo_hip_set_option", "plsvo_align_slot_layout", "plsvo_hip_destroy", "plsvo_hip_last_error", "plsvo_hip_stream", "plsvo_hip_synchronize",
     "plsvo_hip_config_pyramids", "plsvo_hip_upload_pyramid", "plsvo_hip_build_pyramid", "plsvo_hip_build_pyramids_dev",
     "plsvo_hip_download_level", "plsvo_hip_copy_slots",
+    "plsvo_rectify_map", "plsvo_hip_config_rectify", "plsvo_hip_rectify_build_pyramid", "plsvo_hip_rectify_build_pyramids_dev",
     "plsvo_sparse_align", "plsvo_sparse_align_batch", "plsvo_align_stage", "plsvo_align_run", "plsvo_align_fetch",
     "plsvo_align_set_trace", "plsvo_align_fetch_trace", "plsvo_align_poses_dev", "plsvo_align_copy_poses", "plsvo_align_work", "plsvo_align_work_points", "plsvo_align_chi2_ties", "plsvo_align_launch_order",
     "plsvo_pose_optimize", "plsvo_pose_optimize_batch", "plsvo_poseopt_stage", "plsvo_poseopt_run", "plsvo_poseopt_fetch",
@@ -29,6 +30,17 @@ SYMBOLS = [
     "plsvo_hip_set_profiling", "plsvo_hip_kernel_time", "plsvo_hip_reset_profiling",
     "plsvo_hip_version", "plsvo_hip_build_flags", "plsvo_hip_device_info",
 ]
+
+
+def rectify_map(cam):
+    """plsvo_rectify_map (host only, no device): OpenCV's CV_16SC2 map of the camera -> (xy int16 [h, w, 2], frac uint16 [h, w])"""
+    w, h = cam.cam.width, cam.cam.height
+    xy = np.zeros((max(h, 0), max(w, 0), 2), dtype=np.int16)
+    fr = np.zeros((max(h, 0), max(w, 0)), dtype=np.uint16)
+    rc = lib().plsvo_rectify_map(C.byref(cam), xy.ctypes.data_as(C.POINTER(C.c_int16)), fr.ctypes.data_as(C.POINTER(C.c_uint16)))
+    if rc != 0:
+        raise PlsvoError(rc, "rectify_map: bad camera (non-finite or zero focal length, size outside 1..2046)")
+    return xy, fr
 
 
 class PlsvoError(RuntimeError):
@@ -69,6 +81,10 @@ def lib():
         "plsvo_hip_build_pyramids_dev": (C.c_int, [ctxp, C.c_int, C.c_int, vp, C.c_int, C.c_size_t, C.c_int]),
         "plsvo_hip_download_level": (C.c_int, [ctxp, C.c_int, C.c_int, abi.c_u8_p]),
         "plsvo_hip_copy_slots": (C.c_int, [ctxp, C.c_int, C.c_int, C.c_int]),
+        "plsvo_rectify_map": (C.c_int, [C.POINTER(abi.PinholeRadtan), C.POINTER(C.c_int16), C.POINTER(C.c_uint16)]),
+        "plsvo_hip_config_rectify": (C.c_int, [ctxp, C.POINTER(abi.PinholeRadtan), C.c_int, C.POINTER(C.c_int)]),
+        "plsvo_hip_rectify_build_pyramid": (C.c_int, [ctxp, C.c_int, C.c_int, abi.c_u8_p, C.c_int, C.c_int]),
+        "plsvo_hip_rectify_build_pyramids_dev": (C.c_int, [ctxp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_size_t, C.c_int]),
         "plsvo_sparse_align": (C.c_int, [ctxp, C.POINTER(abi.AlignIn), C.POINTER(abi.AlignOut)]),
         "plsvo_sparse_align_batch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.AlignIn), C.POINTER(abi.AlignOut)]),
         "plsvo_align_stage": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.AlignIn)]),
@@ -235,6 +251,24 @@ class Context:
 
     def download_pyramid(self, slot):
         return [self.download_level(slot, l) for l in range(self.n_levels)]
+
+    # ---- rectification of raw distorted frames ----
+    def config_rectify(self, cam, flip_vertical=False):
+        """plsvo_hip_config_rectify: cam is an abi.PinholeRadtan (abi.pinhole_radtan(..)); returns the map id"""
+        mid = C.c_int(-1)
+        self._chk(self.L.plsvo_hip_config_rectify(self.h, C.byref(cam), 1 if flip_vertical else 0, C.byref(mid)))
+        return mid.value
+
+    def rectify_build_pyramid(self, map_id, slot, raw, rounding=0):
+        raw = np.asarray(raw, dtype=np.uint8)
+        if raw.ndim != 2 or raw.strides[1] != 1:
+            raw = np.ascontiguousarray(raw)
+        self._chk(self.L.plsvo_hip_rectify_build_pyramid(self.h, int(map_id), int(slot), raw.ctypes.data_as(abi.c_u8_p), raw.strides[0],
+                                                         int(rounding)))
+
+    def rectify_build_pyramids_dev(self, map_id, first_slot, n, d_ptr, stride_bytes, image_pitch_bytes, rounding=0):
+        self._chk(self.L.plsvo_hip_rectify_build_pyramids_dev(self.h, int(map_id), int(first_slot), int(n), C.c_void_p(d_ptr),
+                                                              int(stride_bytes), int(image_pitch_bytes), int(rounding)))
 
     # ---- sparse image alignment ----
     def align_set_trace(self, max_records):

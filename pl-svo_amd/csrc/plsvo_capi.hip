@@ -39,6 +39,8 @@ hipError_t launch_pack_pose_records(const AlignStateDev* ast, const PoseStateDev
 hipError_t launch_chain_active(const ChainBatchDev& b, hipStream_t stream);
 hipError_t launch_chain_select(const ChainBatchDev& b, hipStream_t stream);
 hipError_t launch_tile_level(const uint8_t* src, size_t src_pitch, int w, int h, uint8_t* dst, size_t dst_pitch, int n_slots, hipStream_t stream);
+hipError_t launch_rectify(const uint8_t* raw, size_t raw_pitch, int stride, int flip, const uint32_t* map, int w, int h, uint8_t* dst,
+                          size_t dst_pitch, int n_slots, hipStream_t stream);
 }  // namespace plsvo_hip
 
 using namespace plsvo_hip;
@@ -95,6 +97,10 @@ struct plsvo_ctx {
   DevBuf pyr_slab;
   PyrDesc pyr{};
   DevBuf pyr_upload;  // staging for level-0 uploads
+  // rectification maps (plsvo_hip_config_rectify): packed words of pyramid_kernels.hip::rectify_kernel, one map per camera
+  struct RectifyMap { DevBuf map; int w = 0, h = 0; bool identity = false, flip = false; };
+  RectifyMap rect[PLSVO_MAX_RECTIFY_MAPS];
+  int rect_n = 0;
 
   // alignment batch
   int a_n = 0;
@@ -282,6 +288,7 @@ extern "C" void plsvo_hip_destroy(plsvo_ctx* c) {
                      &c->p_d_log, &c->p_d_poses, &c->s_d_in, &c->s_d_out, &c->ch_d_blob, &c->ch_d_work, &c->ch_d_po, &c->ch_d_state,
                      &c->ch_d_ptkeep, &c->ch_d_segkeep, &c->ch_d_s32, &c->ch_d_s64, &c->ch_d_poses, &c->rec_d };
   for (DevBuf* b : bufs) b->release();
+  for (auto& r : c->rect) r.map.release();
   for (int k = 0; k < 2; ++k) { if (c->pinned[k]) (void)hipHostFree(c->pinned[k]); if (c->pinned_done[k]) (void)hipEventDestroy(c->pinned_done[k]); }
   for (int k = 0; k < 2; ++k) { if (c->pyr_pinned[k]) (void)hipHostFree(c->pyr_pinned[k]); if (c->pyr_pinned_done[k]) (void)hipEventDestroy(c->pyr_pinned_done[k]); }
   if (c->dl_pinned) (void)hipHostFree(c->dl_pinned);
@@ -529,6 +536,159 @@ extern "C" int plsvo_hip_download_level(plsvo_ctx* c, int slot, int level, uint8
   HIP_TRY(c, hipMemcpyAsync(out, src, (size_t)c->pyr.w[level] * c->pyr.h[level], hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return PLSVO_OK;
+}
+
+// ---- rectification of raw distorted frames ------------------------------------------------------
+// vk::PinholeCamera::undistortImage ([ext] vikit): cv::remap(raw, out, map1, map2, INTER_LINEAR) through the map the camera's
+// constructor builds with cv::initUndistortRectifyMap(K, D, I, K, size, CV_16SC2); K and D are cv::Mat_<float>.  OpenCV 3.x, scalar
+// path, restated operation for operation (DESIGN.md "Rectification"); tests/np_rectify.py is the independent NumPy restatement.
+static int cv_round(double v) {   // cvRound = _mm_cvtsd_si32: half to even, 0x80000000 when the result does not fit
+  if (!(v >= -2147483648.5 && v < 2147483647.5)) return INT32_MIN;
+  return (int)std::nearbyint(v);
+}
+
+static bool rectify_cam_ok(const plsvo_pinhole_radtan* cam) {
+  if (!cam || cam->cam.width < 1 || cam->cam.height < 1 || cam->cam.width > 2046 || cam->cam.height > 2046) return false;   // 11-bit x0 + 1, y0 + 1
+  const double p[4] = { cam->cam.fx, cam->cam.fy, cam->cam.cx, cam->cam.cy };
+  for (double v : p) if (!std::isfinite(v) || !std::isfinite((float)v)) return false;
+  for (double v : cam->d) if (!std::isfinite(v) || !std::isfinite((float)v)) return false;
+  return (float)cam->cam.fx != 0.f && (float)cam->cam.fy != 0.f;   // (a singular K: OpenCV's invert fails)
+}
+
+static void rectify_map_build(const plsvo_pinhole_radtan* cam, int16_t* xy, uint16_t* frac) {
+#pragma clang fp contract(off)
+  const int W = cam->cam.width, H = cam->cam.height;
+  // cameraMatrix = newCameraMatrix = K (float -> double), R = I: iR = (K * I).inv(DECOMP_LU) -- for 3x3 the closed form of
+  // cv::invert (adjugate times 1/det3)
+  double A[9] = { (double)(float)cam->cam.fx, 0., (double)(float)cam->cam.cx, 0., (double)(float)cam->cam.fy, (double)(float)cam->cam.cy, 0., 0., 1. };
+  double Ar[9];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) Ar[i * 3 + j] = A[i * 3 + 0] * (j == 0 ? 1. : 0.) + A[i * 3 + 1] * (j == 1 ? 1. : 0.) + A[i * 3 + 2] * (j == 2 ? 1. : 0.);
+#define M(i, j) Ar[(i) * 3 + (j)]
+  double d = M(0, 0) * (M(1, 1) * M(2, 2) - M(1, 2) * M(2, 1)) - M(0, 1) * (M(1, 0) * M(2, 2) - M(1, 2) * M(2, 0)) +
+             M(0, 2) * (M(1, 0) * M(2, 1) - M(1, 1) * M(2, 0));
+  d = 1. / d;
+  double ir[9];
+  ir[0] = (M(1, 1) * M(2, 2) - M(1, 2) * M(2, 1)) * d;
+  ir[1] = (M(0, 2) * M(2, 1) - M(0, 1) * M(2, 2)) * d;
+  ir[2] = (M(0, 1) * M(1, 2) - M(0, 2) * M(1, 1)) * d;
+  ir[3] = (M(1, 2) * M(2, 0) - M(1, 0) * M(2, 2)) * d;
+  ir[4] = (M(0, 0) * M(2, 2) - M(0, 2) * M(2, 0)) * d;
+  ir[5] = (M(0, 2) * M(1, 0) - M(0, 0) * M(1, 2)) * d;
+  ir[6] = (M(1, 0) * M(2, 1) - M(1, 1) * M(2, 0)) * d;
+  ir[7] = (M(0, 1) * M(2, 0) - M(0, 0) * M(2, 1)) * d;
+  ir[8] = (M(0, 0) * M(1, 1) - M(0, 1) * M(1, 0)) * d;
+#undef M
+  const double u0 = A[2], v0 = A[5], fx = A[0], fy = A[4];
+  const double k1 = (double)(float)cam->d[0], k2 = (double)(float)cam->d[1], p1 = (double)(float)cam->d[2], p2 = (double)(float)cam->d[3],
+               k3 = (double)(float)cam->d[4], k4 = 0., k5 = 0., k6 = 0.;
+  for (int i = 0; i < H; ++i) {
+    int16_t* m1 = xy + (size_t)i * W * 2;
+    uint16_t* m2 = frac + (size_t)i * W;
+    double _x = i * ir[1] + ir[2], _y = i * ir[4] + ir[5], _w = i * ir[7] + ir[8];
+    for (int j = 0; j < W; ++j, _x += ir[0], _y += ir[3], _w += ir[6]) {
+      const double w = 1. / _w, x = _x * w, y = _y * w;
+      const double x2 = x * x, y2 = y * y;
+      const double r2 = x2 + y2, _2xy = 2 * x * y;
+      const double kr = (1 + ((k3 * r2 + k2) * r2 + k1) * r2) / (1 + ((k6 * r2 + k5) * r2 + k4) * r2);
+      const double xd = x * kr + p1 * _2xy + p2 * (r2 + 2 * x2);
+      const double yd = y * kr + p1 * (r2 + 2 * y2) + p2 * _2xy;
+      const double u = fx * xd + u0, v = fy * yd + v0;   // (tilt matrix = I, invProj = 1)
+      const int iu = cv_round(u * 32), iv = cv_round(v * 32);
+      m1[j * 2] = (int16_t)(iu >> 5);
+      m1[j * 2 + 1] = (int16_t)(iv >> 5);
+      m2[j] = (uint16_t)((iv & 31) * 32 + (iu & 31));
+    }
+  }
+}
+
+extern "C" int plsvo_rectify_map(const plsvo_pinhole_radtan* cam, int16_t* xy, uint16_t* frac) {
+  if (!rectify_cam_ok(cam) || !xy || !frac) return PLSVO_E_INVALID;
+  rectify_map_build(cam, xy, frac);
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_hip_config_rectify(plsvo_ctx* c, const plsvo_pinhole_radtan* cam, int flip_vertical, int* map_id) {
+  CTX_CHECK(c);
+  if (!map_id || !rectify_cam_ok(cam)) return fail(c, PLSVO_E_INVALID, "config_rectify: bad camera (non-finite or zero focal length, size outside 1..2046)");
+  if (!c->pyr.base) return fail(c, PLSVO_E_STATE, "config_rectify: pyramids not configured");
+  if (cam->cam.width != c->pyr.w[0] || cam->cam.height != c->pyr.h[0]) return fail(c, PLSVO_E_INVALID, "config_rectify: camera size does not match the configured pyramid");
+  if (c->rect_n >= PLSVO_MAX_RECTIFY_MAPS) return fail(c, PLSVO_E_CAPACITY, "config_rectify: every rectification map of the context is in use");
+  const int W = cam->cam.width, H = cam->cam.height, qw = (W + 3) >> 2;
+  const bool identity = !(std::fabs(cam->d[0]) > 0.0000001);   // vikit: distortion_ = fabs(d0) > 0.0000001
+  std::vector<int16_t> xy((size_t)W * H * 2);
+  std::vector<uint16_t> fr((size_t)W * H);
+  if (identity) {   // undistortImage copies; only the flipped copy goes through the remap kernel (an identity map: a copy, bit for bit)
+    for (int i = 0; i < H; ++i)
+      for (int j = 0; j < W; ++j) { xy[((size_t)i * W + j) * 2] = (int16_t)j; xy[((size_t)i * W + j) * 2 + 1] = (int16_t)i; fr[(size_t)i * W + j] = 0; }
+  } else {
+    rectify_map_build(cam, xy.data(), fr.data());
+  }
+  // pack: rows padded to 4 words (padding = a pixel whose taps are all outside)
+  std::vector<uint32_t> packed((size_t)qw * 4 * H, (uint32_t)(W + 1) << 10);
+  for (int i = 0; i < H; ++i)
+    for (int j = 0; j < W; ++j) {
+      const size_t k = (size_t)i * W + j;
+      const int x0 = xy[k * 2], y0 = xy[k * 2 + 1];
+      uint32_t word = (uint32_t)(W + 1) << 10;   // every tap outside the raw frame: 0
+      if (x0 >= -1 && x0 < W && y0 >= -1 && y0 < H) word = (uint32_t)fr[k] | ((uint32_t)(x0 + 1) << 10) | ((uint32_t)(y0 + 1) << 21);
+      packed[(size_t)i * qw * 4 + j] = word;
+    }
+  HIP_TRY(c, hipSetDevice(c->device));
+  plsvo_ctx::RectifyMap& r = c->rect[c->rect_n];
+  HIP_TRY(c, r.map.ensure(packed.size() * sizeof(uint32_t)));
+  HIP_TRY(c, hipMemcpyAsync(r.map.p, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the packed words live on this call's stack)
+  r.w = W; r.h = H; r.identity = identity; r.flip = flip_vertical != 0;
+  *map_id = c->rect_n++;
+  return PLSVO_OK;
+}
+
+// checks shared by the two rectifying builders: every failure is PLSVO_E_INVALID and nothing has been enqueued
+static int rectify_check(plsvo_ctx* c, int map_id, int first_slot, int n, int stride_bytes, const char* what) {
+  if (!c->pyr.base) return fail(c, PLSVO_E_STATE, std::string(what) + ": pyramids not configured");
+  if (map_id < 0 || map_id >= c->rect_n) return fail(c, PLSVO_E_INVALID, std::string(what) + ": unknown rectification map");
+  const plsvo_ctx::RectifyMap& r = c->rect[map_id];
+  if (r.w != c->pyr.w[0] || r.h != c->pyr.h[0]) return fail(c, PLSVO_E_INVALID, std::string(what) + ": camera size does not match the configured pyramid");
+  if (n <= 0 || first_slot < 0 || first_slot > c->pyr.n_slots - n) return fail(c, PLSVO_E_INVALID, std::string(what) + ": slot range out of bounds");
+  if (stride_bytes < r.w || (long long)stride_bytes * r.h > INT32_MAX) return fail(c, PLSVO_E_INVALID, std::string(what) + ": bad row stride");
+  return PLSVO_OK;
+}
+
+// raw frames (device) -> level 0 of slots [first_slot, first_slot + n), then levels 1.. and the tiled mirror
+static int rectify_levels(plsvo_ctx* c, int map_id, int first_slot, int n, const uint8_t* d_raw, int stride_bytes, size_t image_pitch_bytes,
+                          int rounding) {
+  const plsvo_ctx::RectifyMap& r = c->rect[map_id];
+  uint8_t* base = c->pyr_slab.as<uint8_t>() + (size_t)first_slot * c->pyr.slot_bytes;
+  if (r.identity && !r.flip) {   // vikit's identity branch: the existing level-0 copy
+    HIP_TRY(c, launch_copy_level0(d_raw, image_pitch_bytes, r.w, r.h, stride_bytes, base + c->pyr.off[0], c->pyr.slot_bytes, n, c->stream));
+  } else {
+    HIP_TRY(c, launch_rectify(d_raw, image_pitch_bytes, stride_bytes, r.flip ? 1 : 0, r.map.as<uint32_t>(), r.w, r.h, base + c->pyr.off[0],
+                              c->pyr.slot_bytes, n, c->stream));
+  }
+  return build_levels(c, first_slot, n, rounding);
+}
+
+extern "C" int plsvo_hip_rectify_build_pyramid(plsvo_ctx* c, int map_id, int slot, const uint8_t* raw, int stride_bytes, int rounding) {
+  CTX_CHECK(c);
+  if (!raw) return fail(c, PLSVO_E_INVALID, "rectify_build_pyramid: bad arguments");
+  int rc = rectify_check(c, map_id, slot, 1, stride_bytes, "rectify_build_pyramid"); if (rc) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const int W = c->pyr.w[0], H = c->pyr.h[0];
+  HIP_TRY(c, c->pyr_upload.ensure((size_t)W * H));
+  HIP_TRY(c, hipMemcpy2DAsync(c->pyr_upload.p, (size_t)W, raw, (size_t)stride_bytes, (size_t)W, (size_t)H, hipMemcpyHostToDevice, c->stream));
+  rc = rectify_levels(c, map_id, slot, 1, c->pyr_upload.as<uint8_t>(), W, (size_t)W * H, rounding); if (rc) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_hip_rectify_build_pyramids_dev(plsvo_ctx* c, int map_id, int first_slot, int n, const void* d_raw, int stride_bytes,
+                                                    size_t image_pitch_bytes, int rounding) {
+  CTX_CHECK(c);
+  if (!d_raw) return fail(c, PLSVO_E_INVALID, "rectify_build_pyramids_dev: bad arguments");
+  int rc = rectify_check(c, map_id, first_slot, n, stride_bytes, "rectify_build_pyramids_dev"); if (rc) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  return rectify_levels(c, map_id, first_slot, n, reinterpret_cast<const uint8_t*>(d_raw), stride_bytes, image_pitch_bytes, rounding);
 }
 
 // ---- alignment -----------------------------------------------------------------------------------

@@ -4,6 +4,8 @@
 // 4 bytes, fully coalesced; one launch handles one level of a whole batch of slots.
 //   rounding 0: vikit's SSE2 path  avg(avg(a,c), avg(b,d)) with rounding averages (x+y+1)>>1
 //   rounding 1: vikit's scalar path (a+b+c+d)/4 truncating
+// Also the rectification of raw distorted frames into level 0 (vk::PinholeCamera::undistortImage, app/run_pipeline.cpp:397-411):
+// a byte gather through a packed map shared by every slot (DESIGN.md "Rectification").
 #include <hip/hip_runtime.h>
 
 #include "plsvo_dev.hpp"
@@ -90,6 +92,70 @@ __global__ __launch_bounds__(256) void tile_level_kernel(const uint8_t* src, siz
     }
   }
   *reinterpret_cast<uint4*>(d) = v;
+}
+
+// ---- rectification of raw distorted frames (vk::PinholeCamera::undistortImage = OpenCV remap INTER_LINEAR, BORDER_CONSTANT 0) ----
+// One map word per output pixel, shared by every slot (built and packed on the host, plsvo_capi.hip):
+//   bits 0..9 = (fy & 31) * 32 + (fx & 31), the fixed-point fraction; bits 10..20 = x0 + 1; bits 21..31 = y0 + 1
+// (x0, y0) = the top-left source tap.  A tap outside the raw frame reads 0; a pixel with every tap outside is stored as x0 = w.
+// Map rows are padded to a multiple of 4 words, so every lane loads its 4 words as one 16-byte load.
+__device__ __forceinline__ uint32_t rectify_px(const uint8_t* src, int row_step, int w, int h, int y_first, int y_sign, uint32_t m) {
+  const int tx = (int)(m & 31u), ty = (int)((m >> 5) & 31u);
+  const int x0 = (int)((m >> 10) & 2047u) - 1, y0 = (int)(m >> 21) - 1;
+  // initInterTab2D's fixed-point weights (INTER_REMAP_COEF_SCALE = 32768); entry (0, 0) saturates to 32767 and OpenCV's fix-up adds the
+  // missing 1 to the last tap
+  int w00 = (32 - ty) * (32 - tx) * 32, w01 = (32 - ty) * tx * 32, w10 = ty * (32 - tx) * 32, w11 = ty * tx * 32;
+  if ((m & 1023u) == 0u) { w00 = 32767; w11 = 1; }
+  const uint8_t* r0 = src + (ptrdiff_t)(y_first + y_sign * y0) * row_step;   // raw row of tap row y0 (flipped: h - 1 - y0)
+  const uint8_t* r1 = r0 + (ptrdiff_t)y_sign * row_step;
+  int v00 = 0, v01 = 0, v10 = 0, v11 = 0;
+  if ((unsigned)x0 < (unsigned)(w - 1) && (unsigned)y0 < (unsigned)(h - 1)) {
+    v00 = r0[x0]; v01 = r0[x0 + 1]; v10 = r1[x0]; v11 = r1[x0 + 1];
+  } else {
+    const bool xa = (unsigned)x0 < (unsigned)w, xb = (unsigned)(x0 + 1) < (unsigned)w;
+    const bool ya = (unsigned)y0 < (unsigned)h, yb = (unsigned)(y0 + 1) < (unsigned)h;
+    if (ya && xa) v00 = r0[x0];
+    if (ya && xb) v01 = r0[x0 + 1];
+    if (yb && xa) v10 = r1[x0];
+    if (yb && xb) v11 = r1[x0 + 1];
+  }
+  const int s = (v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + (1 << 14)) >> 15;
+  return (uint32_t)(s > 255 ? 255 : s);
+}
+
+// grid: (ceil(qw * h / 256), n_slots), qw = ceil(w / 4), like the other pyramid kernels: the workgroups in flight walk one frame after the
+// other (the shared map is re-read per slot from L2 / MALL).  Each lane writes 4 output pixels of one row (one 32-bit store when the row
+// allows it).
+// raw frame of slot s at raw + s * raw_pitch, rows stride apart; flip: raw row h - 1 - y is read as row y.
+__global__ __launch_bounds__(256) void rectify_kernel(const uint8_t* raw, size_t raw_pitch, int stride, int flip, const uint32_t* map,
+                                                      int w, int h, uint8_t* dst, size_t dst_pitch) {
+  const int qw = (w + 3) >> 2;
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= qw * h) return;
+  const int y = idx / qw, q = idx - y * qw;
+  const uint4 m = *reinterpret_cast<const uint4*>(map + (size_t)idx * 4);
+  const uint8_t* src = raw + (size_t)blockIdx.y * raw_pitch;
+  const int y_first = flip ? h - 1 : 0, y_sign = flip ? -1 : 1;
+  const uint32_t p0 = rectify_px(src, stride, w, h, y_first, y_sign, m.x);
+  const uint32_t p1 = rectify_px(src, stride, w, h, y_first, y_sign, m.y);
+  const uint32_t p2 = rectify_px(src, stride, w, h, y_first, y_sign, m.z);
+  const uint32_t p3 = rectify_px(src, stride, w, h, y_first, y_sign, m.w);
+  uint8_t* o = dst + (size_t)blockIdx.y * dst_pitch + (size_t)y * w + 4 * q;
+  if (4 * q + 4 <= w && (reinterpret_cast<uintptr_t>(o) & 3) == 0) {
+    *reinterpret_cast<uint32_t*>(o) = p0 | (p1 << 8) | (p2 << 16) | (p3 << 24);
+  } else {
+    const uint32_t p[4] = { p0, p1, p2, p3 };
+    for (int k = 0; k < 4 && 4 * q + k < w; ++k) o[k] = (uint8_t)p[k];
+  }
+}
+
+hipError_t launch_rectify(const uint8_t* raw, size_t raw_pitch, int stride, int flip, const uint32_t* map, int w, int h, uint8_t* dst,
+                          size_t dst_pitch, int n_slots, hipStream_t stream) {
+  const int work = ((w + 3) >> 2) * h;
+  if (work <= 0 || n_slots <= 0) return hipSuccess;
+  hipLaunchKernelGGL(rectify_kernel, dim3((work + 255) / 256, n_slots), dim3(256), 0, stream, raw, raw_pitch, stride, flip, map, w, h,
+                     dst, dst_pitch);
+  return hipGetLastError();
 }
 
 hipError_t launch_tile_level(const uint8_t* src, size_t src_pitch, int w, int h, uint8_t* dst, size_t dst_pitch, int n_slots, hipStream_t stream) {

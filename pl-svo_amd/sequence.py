@@ -20,7 +20,7 @@ With mapping=True two more steps run per frame, again as processFrame / the dept
 starting from a map that knows only part of the landmarks (with noisy positions) and holds the rest as seeds that turn
 into landmarks when they converge.
 
-`backend` is duck-typed: load_frames(list of level-0 images), sparse_align(job), reproject(job), match_direct(job),
+`backend` is duck-typed: load_frames(list of level-0 images; HipBackend also takes raw frames with rectify=), sparse_align(job), reproject(job), match_direct(job),
 pose_optimize(job), and for mapping structure_optimize(job), update_seeds(job).  The product backend is HipBackend (C ABI on the GPU, no fallback); tests pass an oracle-backed one
 to check the whole chain end to end."""
 import copy
@@ -31,14 +31,24 @@ from . import abi, synth
 
 
 class HipBackend:
-    def __init__(self, ctx, n_levels=4):
-        self.ctx, self.n_levels = ctx, n_levels
+    def __init__(self, ctx, n_levels=4, rectify=None):
+        self.ctx, self.n_levels, self.rectify = ctx, n_levels, rectify
 
-    def load_frames(self, images):
+    def load_frames(self, images, rectify=None):
+        """images: level-0 frames, already rectified -- or, with rectify = an abi.PinholeRadtan (or (camera, flip_vertical)), the raw
+        frames of that camera, rectified on the device into their pyramid slots (plsvo_hip_rectify_build_pyramid).  rectify=None falls
+        back to the one given to the constructor."""
         h, w = images[0].shape
         self.ctx.config_pyramids(len(images), w, h, self.n_levels)
+        rectify = rectify if rectify is not None else self.rectify
+        if rectify is None:
+            for k, img in enumerate(images):
+                self.ctx.build_pyramid(k, img, 0)
+            return
+        cam, flip = rectify if isinstance(rectify, tuple) else (rectify, False)
+        mid = self.ctx.config_rectify(cam, flip_vertical=flip)
         for k, img in enumerate(images):
-            self.ctx.build_pyramid(k, img, 0)
+            self.ctx.rectify_build_pyramid(mid, k, img, 0)
 
     def sparse_align(self, job):
         return self.ctx.sparse_align(job)

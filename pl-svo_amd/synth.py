@@ -475,3 +475,31 @@ def apply_seed_update(pt, seg, res):
         pt[k] = res["pt_" + k].copy()
     for k in ("a", "b", "mu_s", "mu_e", "sigma2_s", "sigma2_e"):
         seg[k] = res["seg_" + k].copy()
+
+
+def distort_image(img, cam, fill=0):
+    """A raw frame of a radial-tangential camera whose rectification approximates `img` (tools/run_sequence.py --distortion): every raw
+    pixel samples `img` bilinearly at the undistorted point it images, found by fixed-point iteration of the inverse of the model.
+    cam: dict(fx, fy, cx, cy, d=[k1, k2, p1, p2(, k3)]).  Only a plausible input, not part of the rectification contract."""
+    img = np.asarray(img, dtype=np.float64)
+    H, W = img.shape
+    fx, fy, cx, cy = (float(cam[k]) for k in ("fx", "fy", "cx", "cy"))
+    k1, k2, p1, p2, k3 = (list(cam["d"]) + [0.0] * 5)[:5]
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
+    xd, yd = (xx - cx) / fx, (yy - cy) / fy
+    x, y = xd.copy(), yd.copy()
+    for _ in range(20):
+        r2 = x * x + y * y
+        kr = 1 + ((k3 * r2 + k2) * r2 + k1) * r2
+        dx = 2 * p1 * x * y + p2 * (r2 + 2 * x * x)
+        dy = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
+        x, y = (xd - dx) / kr, (yd - dy) / kr
+    u, v = fx * x + cx, fy * y + cy
+    u0, v0 = np.floor(u), np.floor(v)
+    a, b = u - u0, v - v0
+    out = np.zeros((H, W), dtype=np.float64)
+    for dy_, dx_, wgt in ((0, 0, (1 - a) * (1 - b)), (0, 1, a * (1 - b)), (1, 0, (1 - a) * b), (1, 1, a * b)):
+        ys, xs = v0.astype(np.int64) + dy_, u0.astype(np.int64) + dx_
+        inside = (ys >= 0) & (ys < H) & (xs >= 0) & (xs < W)
+        out += wgt * np.where(inside, img[np.clip(ys, 0, H - 1), np.clip(xs, 0, W - 1)], fill)
+    return np.clip(np.rint(out), 0, 255).astype(np.uint8)

@@ -155,6 +155,50 @@ int plsvo_hip_rectify_build_pyramids_dev(plsvo_ctx* ctx, int map_id, int first_s
                                          int stride_bytes, size_t image_pitch_bytes, int rounding);
 
 /* ------------------------------------------------------------------------------------------ */
+/* FAST corners per grid cell from pyramid slots                                              */
+/* replaces plsvo::feature_detection::FastDetector::detect (src/feature_detection.cpp:53-104), */
+/* called by DepthFilter::initializeSeeds (src/depth_filter.cpp:161-165) and the bootstrap     */
+/* (src/initialization.cpp:135-137): fast_corner_detect_10, fast_corner_score_10 and           */
+/* fast_nonmax_3x3 ([ext] fast) per level, vk::shiTomasiScore ([ext] vikit) of the survivors,  */
+/* the best corner of every grid cell (DESIGN.md "Corner detection")                          */
+/* ------------------------------------------------------------------------------------------ */
+
+/* one feature: px in level-0 pixels = (x_L << level, y_L << level), score = its Shi-Tomasi score (feature_detection.cpp:93) */
+typedef struct plsvo_corner { int32_t x, y; float score; int32_t level; } plsvo_corner;
+
+typedef struct plsvo_detect_params {
+  int32_t cell_size;            /* Config::gridSize() (25) */
+  int32_t n_levels;             /* Config::nPyrLevels() (3); <= the configured levels */
+  int32_t fast_threshold;       /* 20 (feature_detection.cpp:67), 1..254 */
+  int32_t reserved0;
+  double  detection_threshold;  /* Config::triangMinCornerScore() (20.0): >= 0, finite, exactly representable as float */
+} plsvo_detect_params;
+
+/* Host only, no ctx: the grid of AbstractDetector (include/plsvo/feature_detection.h:97,110-112), cols = ceil(width / cell_size),
+ * rows = ceil(height / cell_size).  PLSVO_E_INVALID (nothing written) for a size or cell below 1 or a NULL output. */
+int plsvo_detect_grid(int width, int height, int cell_size, int* cols, int* rows);
+/* Host only, no ctx: the cell index FastDetector::setGridOccpuancy / setExistingFeatures mark for a feature at level-0 pixel
+ * (px_x, px_y) (src/feature_detection.cpp:106-121): (int)(px_y / cell_size) * cols + (int)(px_x / cell_size).
+ * PLSVO_E_INVALID for cols or cell_size below 1 and for a pixel that is negative or not finite. */
+int plsvo_detect_cell(int cols, int cell_size, double px_x, double px_y);
+/* FastDetector::detect for slots [first_slot, first_slot + n): with cells = cols * rows of plsvo_detect_grid for the configured
+ * level-0 size, slot i reads occupancy[i * cells .. ) (non-zero = the cell already holds a feature; NULL = no cell does) and writes
+ * its features to corners[i * cells .. ) in cell-index order, the first counts[i] of them valid.  Host buffers; synchronous.
+ * PLSVO_E_STATE when the pyramids are not configured; PLSVO_E_INVALID for a slot range out of bounds, n_levels outside 1 .. the
+ * configured levels, cell_size < 1, a level smaller than 7 x 7, a level-0 width or height above 8191, fast_threshold outside 1..254,
+ * a detection_threshold that is negative, not finite or not a float, or a NULL params / corners / counts.  An error writes nothing. */
+int plsvo_hip_detect_fast(plsvo_ctx* ctx, int first_slot, int n, const plsvo_detect_params* params, const uint8_t* occupancy,
+                          plsvo_corner* corners, int32_t* counts);
+/* Same with device buffers (d_occupancy may be NULL); enqueued on the ctx stream, nothing is waited for: a detection can follow
+ * plsvo_hip_rectify_build_pyramids_dev / plsvo_hip_build_pyramids_dev without a host round trip. */
+int plsvo_hip_detect_fast_dev(plsvo_ctx* ctx, int first_slot, int n, const plsvo_detect_params* params, const uint8_t* d_occupancy,
+                              plsvo_corner* d_corners, int32_t* d_counts);
+/* Diagnostic: the stages of one level of one slot before the grid, as the three fast:: calls leave them
+ * (src/feature_detection.cpp:63-82): score[y * W_L + x] = fast_corner_score_10 of a corner, 0 = not a corner;
+ * survives[..] = 1 where fast_nonmax_3x3 keeps it.  Host buffers of W_L * H_L bytes each; synchronous. */
+int plsvo_hip_detect_stages(plsvo_ctx* ctx, int slot, int level, int fast_threshold, uint8_t* score, uint8_t* survives);
+
+/* ------------------------------------------------------------------------------------------ */
 /* sparse image alignment                                                                      */
 /* replaces plsvo::SparseImgAlign::run   (include/plsvo/sparse_img_align.h:64-66,              */
 /*                                        src/sparse_img_align.cpp:54-95; call sites           */

@@ -38,6 +38,24 @@ def pinhole_radtan(width, height, fx, fy, cx, cy, d):
     return PinholeRadtan(Pinhole(fx, fy, cx, cy, int(width), int(height)), (C.c_double * 5)(*[float(v) for v in d[:5]]))
 
 
+class Corner(C.Structure):
+    """plsvo_corner: one detected feature, px in level-0 pixels"""
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("score", C.c_float), ("level", C.c_int32)]
+
+
+CORNER_DTYPE = np.dtype([("x", np.int32), ("y", np.int32), ("score", np.float32), ("level", np.int32)])
+
+
+class DetectParams(C.Structure):
+    """plsvo_detect_params (defaults: Config::gridSize, nPyrLevels, the FAST threshold of feature_detection.cpp:67, triangMinCornerScore)"""
+    _fields_ = [("cell_size", C.c_int32), ("n_levels", C.c_int32), ("fast_threshold", C.c_int32), ("reserved0", C.c_int32),
+                ("detection_threshold", C.c_double)]
+
+
+def detect_params(cell_size=25, n_levels=3, fast_threshold=20, detection_threshold=20.0):
+    return DetectParams(int(cell_size), int(n_levels), int(fast_threshold), 0, float(detection_threshold))
+
+
 class AlignIn(C.Structure):
     _fields_ = [("ref_slot", C.c_int32), ("cur_slot", C.c_int32), ("cam", Pinhole),
                 ("max_level", C.c_int32), ("min_level", C.c_int32), ("n_iter", C.c_int32),

@@ -20,6 +20,7 @@ SYMBOLS = [
     "plsvo_hip_config_pyramids", "plsvo_hip_upload_pyramid", "plsvo_hip_build_pyramid", "plsvo_hip_build_pyramids_dev",
     "plsvo_hip_download_level", "plsvo_hip_copy_slots",
     "plsvo_rectify_map", "plsvo_hip_config_rectify", "plsvo_hip_rectify_build_pyramid", "plsvo_hip_rectify_build_pyramids_dev",
+    "plsvo_detect_grid", "plsvo_detect_cell", "plsvo_hip_detect_fast", "plsvo_hip_detect_fast_dev", "plsvo_hip_detect_stages",
     "plsvo_sparse_align", "plsvo_sparse_align_batch", "plsvo_align_stage", "plsvo_align_run", "plsvo_align_fetch",
     "plsvo_align_set_trace", "plsvo_align_fetch_trace", "plsvo_align_poses_dev", "plsvo_align_copy_poses", "plsvo_align_work", "plsvo_align_work_points", "plsvo_align_chi2_ties", "plsvo_align_launch_order",
     "plsvo_pose_optimize", "plsvo_pose_optimize_batch", "plsvo_poseopt_stage", "plsvo_poseopt_run", "plsvo_poseopt_fetch",
@@ -41,6 +42,23 @@ def rectify_map(cam):
     if rc != 0:
         raise PlsvoError(rc, "rectify_map: bad camera (non-finite or zero focal length, size outside 1..2046)")
     return xy, fr
+
+
+def detect_grid(width, height, cell_size):
+    """plsvo_detect_grid (host only): (cols, rows) of the detector's grid"""
+    cols, rows = C.c_int(0), C.c_int(0)
+    rc = lib().plsvo_detect_grid(int(width), int(height), int(cell_size), C.byref(cols), C.byref(rows))
+    if rc != 0:
+        raise PlsvoError(rc, "detect_grid: width, height and cell_size must be >= 1")
+    return cols.value, rows.value
+
+
+def detect_cell(cols, cell_size, px_x, px_y):
+    """plsvo_detect_cell (host only): the grid cell setGridOccpuancy marks for a feature at level-0 pixel (px_x, px_y)"""
+    k = lib().plsvo_detect_cell(int(cols), int(cell_size), float(px_x), float(px_y))
+    if k < 0:
+        raise PlsvoError(k, "detect_cell: cols and cell_size must be >= 1, the pixel finite and not negative")
+    return k
 
 
 class PlsvoError(RuntimeError):
@@ -85,6 +103,11 @@ def lib():
         "plsvo_hip_config_rectify": (C.c_int, [ctxp, C.POINTER(abi.PinholeRadtan), C.c_int, C.POINTER(C.c_int)]),
         "plsvo_hip_rectify_build_pyramid": (C.c_int, [ctxp, C.c_int, C.c_int, abi.c_u8_p, C.c_int, C.c_int]),
         "plsvo_hip_rectify_build_pyramids_dev": (C.c_int, [ctxp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_size_t, C.c_int]),
+        "plsvo_detect_grid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "plsvo_detect_cell": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double]),
+        "plsvo_hip_detect_fast": (C.c_int, [ctxp, C.c_int, C.c_int, C.POINTER(abi.DetectParams), abi.c_u8_p, C.POINTER(abi.Corner), abi.c_i32_p]),
+        "plsvo_hip_detect_fast_dev": (C.c_int, [ctxp, C.c_int, C.c_int, C.POINTER(abi.DetectParams), vp, vp, vp]),
+        "plsvo_hip_detect_stages": (C.c_int, [ctxp, C.c_int, C.c_int, C.c_int, abi.c_u8_p, abi.c_u8_p]),
         "plsvo_sparse_align": (C.c_int, [ctxp, C.POINTER(abi.AlignIn), C.POINTER(abi.AlignOut)]),
         "plsvo_sparse_align_batch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.AlignIn), C.POINTER(abi.AlignOut)]),
         "plsvo_align_stage": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.AlignIn)]),
@@ -269,6 +292,38 @@ class Context:
     def rectify_build_pyramids_dev(self, map_id, first_slot, n, d_ptr, stride_bytes, image_pitch_bytes, rounding=0):
         self._chk(self.L.plsvo_hip_rectify_build_pyramids_dev(self.h, int(map_id), int(first_slot), int(n), C.c_void_p(d_ptr),
                                                               int(stride_bytes), int(image_pitch_bytes), int(rounding)))
+
+    # ---- FAST corners per grid cell ----
+    def detect_fast(self, first_slot, n, cell_size=25, n_levels=3, fast_threshold=20, detection_threshold=20.0, occupancy=None):
+        """plsvo_hip_detect_fast: FastDetector::detect for n slots.  occupancy: None or n x cells bytes (non-zero = occupied).
+        Returns one structured array (abi.CORNER_DTYPE) per slot, in cell-index order."""
+        cols, rows = detect_grid(self.width, self.height, cell_size)
+        cells = cols * rows
+        pr = abi.detect_params(cell_size, n_levels, fast_threshold, detection_threshold)
+        occ = None
+        if occupancy is not None:
+            occ = np.ascontiguousarray(np.asarray(occupancy).reshape(int(n), cells) != 0, dtype=np.uint8)
+        out = np.zeros((max(int(n), 1), cells), dtype=abi.CORNER_DTYPE)
+        counts = np.zeros(max(int(n), 1), dtype=np.int32)
+        self._chk(self.L.plsvo_hip_detect_fast(self.h, int(first_slot), int(n), C.byref(pr), None if occ is None else occ.ctypes.data_as(abi.c_u8_p),
+                                               out.ctypes.data_as(C.POINTER(abi.Corner)), counts.ctypes.data_as(abi.c_i32_p)))
+        return [out[i, :counts[i]].copy() for i in range(int(n))]
+
+    def detect_fast_dev(self, first_slot, n, d_corners, d_counts, cell_size=25, n_levels=3, fast_threshold=20, detection_threshold=20.0,
+                        d_occupancy=None):
+        """plsvo_hip_detect_fast_dev: the same into device buffers (n x cells plsvo_corner of 16 bytes, n int32); enqueued only"""
+        pr = abi.detect_params(cell_size, n_levels, fast_threshold, detection_threshold)
+        self._chk(self.L.plsvo_hip_detect_fast_dev(self.h, int(first_slot), int(n), C.byref(pr), C.c_void_p(d_occupancy), C.c_void_p(d_corners),
+                                                   C.c_void_p(d_counts)))
+
+    def detect_stages(self, slot, level, fast_threshold=20):
+        """plsvo_hip_detect_stages: (score map, survivor map) of one level, uint8 [H_L, W_L]; score 0 = not a corner"""
+        w, h = self.width >> level, self.height >> level
+        score = np.zeros((max(h, 0), max(w, 0)), dtype=np.uint8)
+        surv = np.zeros_like(score)
+        self._chk(self.L.plsvo_hip_detect_stages(self.h, int(slot), int(level), int(fast_threshold), score.ctypes.data_as(abi.c_u8_p),
+                                                 surv.ctypes.data_as(abi.c_u8_p)))
+        return score, surv
 
     # ---- sparse image alignment ----
     def align_set_trace(self, max_records):

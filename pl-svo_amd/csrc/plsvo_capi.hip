@@ -41,6 +41,9 @@ hipError_t launch_chain_select(const ChainBatchDev& b, hipStream_t stream);
 hipError_t launch_tile_level(const uint8_t* src, size_t src_pitch, int w, int h, uint8_t* dst, size_t dst_pitch, int n_slots, hipStream_t stream);
 hipError_t launch_rectify(const uint8_t* raw, size_t raw_pitch, int stride, int flip, const uint32_t* map, int w, int h, uint8_t* dst,
                           size_t dst_pitch, int n_slots, hipStream_t stream);
+hipError_t launch_detect_fast(const DetectLaunch& a, int n_slots, hipStream_t stream);
+hipError_t launch_detect_stages(const DetectLaunch& a, hipStream_t stream);
+hipError_t launch_detect_compact(unsigned long long* keys, int n_cells, plsvo_corner* corners, int32_t* counts, int n_slots, hipStream_t stream);
 }  // namespace plsvo_hip
 
 using namespace plsvo_hip;
@@ -101,6 +104,8 @@ struct plsvo_ctx {
   struct RectifyMap { DevBuf map; int w = 0, h = 0; bool identity = false, flip = false; };
   RectifyMap rect[PLSVO_MAX_RECTIFY_MAPS];
   int rect_n = 0;
+  // corner detection (plsvo_hip_detect_fast*): one 64-bit key per (slot, cell), 0 between calls (detect_device.hpp); staging of the host form
+  DevBuf det_keys, det_occ, det_corners, det_counts, det_stage;
 
   // alignment batch
   int a_n = 0;
@@ -289,6 +294,7 @@ extern "C" void plsvo_hip_destroy(plsvo_ctx* c) {
                      &c->ch_d_ptkeep, &c->ch_d_segkeep, &c->ch_d_s32, &c->ch_d_s64, &c->ch_d_poses, &c->rec_d };
   for (DevBuf* b : bufs) b->release();
   for (auto& r : c->rect) r.map.release();
+  c->det_keys.release(); c->det_occ.release(); c->det_corners.release(); c->det_counts.release(); c->det_stage.release();
   for (int k = 0; k < 2; ++k) { if (c->pinned[k]) (void)hipHostFree(c->pinned[k]); if (c->pinned_done[k]) (void)hipEventDestroy(c->pinned_done[k]); }
   for (int k = 0; k < 2; ++k) { if (c->pyr_pinned[k]) (void)hipHostFree(c->pyr_pinned[k]); if (c->pyr_pinned_done[k]) (void)hipEventDestroy(c->pyr_pinned_done[k]); }
   if (c->dl_pinned) (void)hipHostFree(c->dl_pinned);
@@ -689,6 +695,132 @@ extern "C" int plsvo_hip_rectify_build_pyramids_dev(plsvo_ctx* c, int map_id, in
   int rc = rectify_check(c, map_id, first_slot, n, stride_bytes, "rectify_build_pyramids_dev"); if (rc) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   return rectify_levels(c, map_id, first_slot, n, reinterpret_cast<const uint8_t*>(d_raw), stride_bytes, image_pitch_bytes, rounding);
+}
+
+// ---- FAST corners per grid cell ------------------------------------------------------------------
+// feature_detection::FastDetector::detect (src/feature_detection.cpp:53-104); kernels and key format: detect_device.hpp
+extern "C" int plsvo_detect_grid(int width, int height, int cell_size, int* cols, int* rows) {
+  if (width < 1 || height < 1 || cell_size < 1 || !cols || !rows) return PLSVO_E_INVALID;
+  *cols = (int)(((long long)width + cell_size - 1) / cell_size);    // ceil(static_cast<double>(img_width) / cell_size), feature_detection.h:110-111
+  *rows = (int)(((long long)height + cell_size - 1) / cell_size);
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_detect_cell(int cols, int cell_size, double px_x, double px_y) {
+  if (cols < 1 || cell_size < 1 || !std::isfinite(px_x) || !std::isfinite(px_y) || px_x < 0.0 || px_y < 0.0) return PLSVO_E_INVALID;
+  const double cx = px_x / cell_size, cy = px_y / cell_size;
+  if (cx >= 2147483647.0 || cy * cols + cx >= 2147483647.0) return PLSVO_E_INVALID;
+  return static_cast<int>(cy) * cols + static_cast<int>(cx);
+}
+
+// the levels [level_lo, level_hi] of the configured pyramid as one launch
+static void detect_fill_levels(const plsvo_ctx* c, int level_lo, int level_hi, DetectLaunch* a) {
+  a->n_lv = 0; a->tile_begin[0] = 0;
+  for (int l = level_lo; l <= level_hi; ++l) {
+    const int e = a->n_lv++;
+    a->level[e] = l; a->w[e] = c->pyr.w[l]; a->h[e] = c->pyr.h[l]; a->off[e] = c->pyr.off[l];
+    a->tile_begin[e + 1] = a->tile_begin[e] + detect_tiles(a->w[e], a->h[e], &a->tiles_x[e]);
+  }
+}
+
+// checks shared by the detect entry points: nothing has been enqueued or written when one fails
+static int detect_check(plsvo_ctx* c, int first_slot, int n, const plsvo_detect_params* p, const void* corners, const void* counts, const char* what,
+                        int* cols, int* rows) {
+  if (!c->pyr.base) return fail(c, PLSVO_E_STATE, std::string(what) + ": pyramids not configured");
+  if (!p || !corners || !counts) return fail(c, PLSVO_E_INVALID, std::string(what) + ": NULL params, corners or counts");
+  if (n <= 0 || first_slot < 0 || first_slot > c->pyr.n_slots - n) return fail(c, PLSVO_E_INVALID, std::string(what) + ": slot range out of bounds");
+  if (p->n_levels < 1 || p->n_levels > c->pyr.n_levels) return fail(c, PLSVO_E_INVALID, std::string(what) + ": n_levels outside the configured pyramid");
+  if (p->cell_size < 1) return fail(c, PLSVO_E_INVALID, std::string(what) + ": cell_size < 1");
+  if (c->pyr.w[0] > 8191 || c->pyr.h[0] > 8191) return fail(c, PLSVO_E_INVALID, std::string(what) + ": image wider or higher than 8191 (13 bits per coordinate of a cell key)");
+  if (c->pyr.w[p->n_levels - 1] < 7 || c->pyr.h[p->n_levels - 1] < 7) return fail(c, PLSVO_E_INVALID, std::string(what) + ": a level smaller than 7 x 7");
+  if (p->fast_threshold < 1 || p->fast_threshold > 254) return fail(c, PLSVO_E_INVALID, std::string(what) + ": fast_threshold outside 1..254");
+  const double t = p->detection_threshold;
+  if (!std::isfinite(t) || t < 0.0 || (double)(float)t != t) return fail(c, PLSVO_E_INVALID, std::string(what) + ": detection_threshold negative, not finite or not a float");
+  if (plsvo_detect_grid(c->pyr.w[0], c->pyr.h[0], p->cell_size, cols, rows) != PLSVO_OK || (long long)*cols * *rows * n > INT32_MAX)
+    return fail(c, PLSVO_E_INVALID, std::string(what) + ": grid too large");
+  return PLSVO_OK;
+}
+
+static int detect_enqueue(plsvo_ctx* c, int first_slot, int n, const plsvo_detect_params* p, int cells, int cols, const uint8_t* d_occ,
+                          plsvo_corner* d_corners, int32_t* d_counts) {
+  const size_t key_bytes = (size_t)n * cells * sizeof(unsigned long long);
+  if (key_bytes > c->det_keys.cap) {   // a new buffer starts armed; every compaction leaves it armed
+    HIP_TRY(c, c->det_keys.ensure(key_bytes));
+    HIP_TRY(c, hipMemsetAsync(c->det_keys.p, 0, c->det_keys.cap, c->stream));
+  }
+  DetectLaunch a{};
+  a.pyr = c->pyr_slab.as<uint8_t>() + (size_t)first_slot * c->pyr.slot_bytes;
+  a.slot_bytes = c->pyr.slot_bytes;
+  detect_fill_levels(c, 0, p->n_levels - 1, &a);
+  a.fast_b = p->fast_threshold; a.thr = (float)p->detection_threshold;
+  a.cell = p->cell_size; a.cols = cols; a.n_cells = cells;
+  a.occupancy = d_occ; a.keys = c->det_keys.as<unsigned long long>();
+  HIP_TRY(c, launch_detect_fast(a, n, c->stream));
+  HIP_TRY(c, launch_detect_compact(a.keys, cells, d_corners, d_counts, n, c->stream));
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_hip_detect_fast_dev(plsvo_ctx* c, int first_slot, int n, const plsvo_detect_params* params, const uint8_t* d_occupancy,
+                                         plsvo_corner* d_corners, int32_t* d_counts) {
+  CTX_CHECK(c);
+  int cols = 0, rows = 0;
+  int rc = detect_check(c, first_slot, n, params, d_corners, d_counts, "detect_fast_dev", &cols, &rows); if (rc) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  return detect_enqueue(c, first_slot, n, params, cols * rows, cols, d_occupancy, d_corners, d_counts);
+}
+
+extern "C" int plsvo_hip_detect_fast(plsvo_ctx* c, int first_slot, int n, const plsvo_detect_params* params, const uint8_t* occupancy,
+                                     plsvo_corner* corners, int32_t* counts) {
+  CTX_CHECK(c);
+  int cols = 0, rows = 0;
+  int rc = detect_check(c, first_slot, n, params, corners, counts, "detect_fast", &cols, &rows); if (rc) return rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const int cells = cols * rows;
+  const size_t total = (size_t)n * cells;
+  HIP_TRY(c, c->det_corners.ensure(total * sizeof(plsvo_corner)));
+  HIP_TRY(c, c->det_counts.ensure((size_t)n * sizeof(int32_t)));
+  if (occupancy) {
+    HIP_TRY(c, c->det_occ.ensure(total));
+    HIP_TRY(c, hipMemcpyAsync(c->det_occ.p, occupancy, total, hipMemcpyHostToDevice, c->stream));
+  }
+  rc = detect_enqueue(c, first_slot, n, params, cells, cols, occupancy ? c->det_occ.as<uint8_t>() : nullptr, c->det_corners.as<plsvo_corner>(),
+                      c->det_counts.as<int32_t>());
+  if (rc) return rc;
+  // the records come back through a host copy of the device buffer: only the valid ones of every slot reach the caller's array
+  std::vector<int32_t> cnt((size_t)n);
+  HIP_TRY(c, hipMemcpyAsync(cnt.data(), c->det_counts.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (int i = 0; i < n; ++i) {
+    if (cnt[(size_t)i] < 0 || cnt[(size_t)i] > cells) return fail(c, PLSVO_E_HIP, "detect_fast: corrupt count");
+    if (cnt[(size_t)i] > 0)
+      HIP_TRY(c, hipMemcpyAsync(corners + (size_t)i * cells, c->det_corners.as<plsvo_corner>() + (size_t)i * cells, (size_t)cnt[(size_t)i] * sizeof(plsvo_corner),
+                                hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  memcpy(counts, cnt.data(), (size_t)n * sizeof(int32_t));
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_hip_detect_stages(plsvo_ctx* c, int slot, int level, int fast_threshold, uint8_t* score, uint8_t* survives) {
+  CTX_CHECK(c);
+  if (!c->pyr.base) return fail(c, PLSVO_E_STATE, "detect_stages: pyramids not configured");
+  if (!score || !survives || slot < 0 || slot >= c->pyr.n_slots || level < 0 || level >= c->pyr.n_levels || fast_threshold < 1 || fast_threshold > 254 ||
+      c->pyr.w[0] > 8191 || c->pyr.h[0] > 8191)
+    return fail(c, PLSVO_E_INVALID, "detect_stages: bad arguments");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t px = (size_t)c->pyr.w[level] * c->pyr.h[level];
+  HIP_TRY(c, c->det_stage.ensure(2 * px));
+  DetectLaunch a{};
+  a.pyr = c->pyr_slab.as<uint8_t>() + (size_t)slot * c->pyr.slot_bytes;
+  a.slot_bytes = c->pyr.slot_bytes;
+  detect_fill_levels(c, level, level, &a);
+  a.fast_b = fast_threshold; a.cell = 1; a.cols = 1; a.n_cells = 1;
+  a.stage_score = c->det_stage.as<uint8_t>(); a.stage_survives = a.stage_score + px;
+  HIP_TRY(c, launch_detect_stages(a, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(score, a.stage_score, px, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(survives, a.stage_survives, px, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return PLSVO_OK;
 }
 
 // ---- alignment -----------------------------------------------------------------------------------

@@ -249,4 +249,34 @@ struct ReprojBatchDev {
   double* px; int* cell;
 };
 
+// corner detection (detect_device.hpp, include/plsvo_hip.h plsvo_hip_detect_fast): tile geometry and the launch record
+constexpr int kDetTileW = 64, kDetTileH = 32;          // pixels of a tile that one workgroup decides
+constexpr int kDetImgX0 = 8, kDetImgY0 = 5;            // LDS image origin = tile origin - (8, 5): a halo of 5 (Shi-Tomasi: x - 5 .. x + 4), 8 keeps rows dword-aligned
+constexpr int kDetImgW = kDetTileW + 16, kDetImgH = kDetTileH + 10;   // 80 x 42 bytes
+constexpr int kDetScoreW = 68, kDetScoreH = kDetTileH + 2;            // scores of the tile + a ring of 1 (66 x 34, rows padded to 68)
+constexpr int kDetCellCap = 128;                       // cells of one tile reduced in LDS (640 x 480, cell 25: at most 12 x 6 at level 2)
+constexpr int kDetThreads = 256;
+
+struct DetectLaunch {
+  const uint8_t* pyr;                 // first slot of the call
+  unsigned long long slot_bytes;
+  int n_lv;                           // levels of this launch; entry i is pyramid level level[i]
+  int level[PLSVO_MAX_LEVELS], w[PLSVO_MAX_LEVELS], h[PLSVO_MAX_LEVELS], tiles_x[PLSVO_MAX_LEVELS];
+  unsigned int off[PLSVO_MAX_LEVELS];
+  int tile_begin[PLSVO_MAX_LEVELS + 1];   // blockIdx.x in [tile_begin[i], tile_begin[i + 1]) works on entry i
+  int fast_b;                         // FAST threshold b
+  float thr;                          // (float)detection_threshold: a candidate must score above it
+  int cell, cols, n_cells;
+  const uint8_t* occupancy;           // n_cells per slot, or null
+  unsigned long long* keys;           // n_cells per slot
+  uint8_t* stage_score;               // detect_stages only: W_L * H_L each (one slot, one level)
+  uint8_t* stage_survives;
+};
+
+inline int detect_tiles(int w, int h, int* tiles_x) {
+  *tiles_x = (w + kDetTileW - 1) / kDetTileW;
+  return *tiles_x * ((h + kDetTileH - 1) / kDetTileH);
+}
+
+
 }  // namespace plsvo_hip

@@ -6,9 +6,11 @@
 //   rounding 1: vikit's scalar path (a+b+c+d)/4 truncating
 // Also the rectification of raw distorted frames into level 0 (vk::PinholeCamera::undistortImage, app/run_pipeline.cpp:397-411):
 // a byte gather through a packed map shared by every slot (DESIGN.md "Rectification").
+// And the corner detector that reads the slots (feature_detection::FastDetector::detect, src/feature_detection.cpp:53-104): detect_device.hpp.
 #include <hip/hip_runtime.h>
 
 #include "plsvo_dev.hpp"
+#include "detect_device.hpp"
 
 namespace plsvo_hip {
 
@@ -155,6 +157,27 @@ hipError_t launch_rectify(const uint8_t* raw, size_t raw_pitch, int stride, int 
   if (work <= 0 || n_slots <= 0) return hipSuccess;
   hipLaunchKernelGGL(rectify_kernel, dim3((work + 255) / 256, n_slots), dim3(256), 0, stream, raw, raw_pitch, stride, flip, map, w, h,
                      dst, dst_pitch);
+  return hipGetLastError();
+}
+
+// FAST corners per grid cell (detect_device.hpp): keys of n_slots slots, then (launch_detect_compact) records + counts
+hipError_t launch_detect_fast(const DetectLaunch& a, int n_slots, hipStream_t stream) {
+  const int tiles = a.tile_begin[a.n_lv];
+  if (tiles <= 0 || n_slots <= 0) return hipSuccess;
+  hipLaunchKernelGGL(detect_fast_kernel<false>, dim3(tiles, n_slots), dim3(kDetThreads), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_detect_stages(const DetectLaunch& a, hipStream_t stream) {
+  const int tiles = a.tile_begin[a.n_lv];
+  if (tiles <= 0) return hipSuccess;
+  hipLaunchKernelGGL(detect_fast_kernel<true>, dim3(tiles, 1), dim3(kDetThreads), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_detect_compact(unsigned long long* keys, int n_cells, plsvo_corner* corners, int32_t* counts, int n_slots, hipStream_t stream) {
+  if (n_cells <= 0 || n_slots <= 0) return hipSuccess;
+  hipLaunchKernelGGL(detect_compact_kernel, dim3(n_slots), dim3(kDetThreads), 0, stream, keys, n_cells, corners, counts);
   return hipGetLastError();
 }
 

@@ -21,6 +21,7 @@
 // reference's own failure paths (run() returns 0; optimizeGaussNewton leaves its outputs untouched).
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -782,6 +783,103 @@ bool updateSeeds(const FrameT& frame, PointSeedList& pt_seeds, LineSeedList& seg
 }
 
 }  // namespace depth_filter
+}  // namespace plsvo
+
+namespace plsvo_hip_adapter {
+// How FastDetector::detect creates a feature: the reference's `new PointFeat(frame, Vector2d(x, y), level)` (src/feature_detection.cpp:100),
+// whose constructor sets f = frame->cam_->cam2world(px).  The default fills the members a PointFeat look-alike has (frame, px, f, level) with
+// the unit bearing vector of the undistorted pinhole model; a PL-SVO build specialises it with the one-line constructor call.
+template <class PointFeatT>
+struct point_feat_traits {
+  template <class FrameT>
+  static PointFeatT* create(FrameT* frame, const plsvo_pinhole& cam, double x, double y, int level) {
+    PointFeatT* ft = new PointFeatT();
+    ft->frame = frame; ft->px[0] = x; ft->px[1] = y; ft->level = level;
+    const double vx = (x - cam.cx) / cam.fx, vy = (y - cam.cy) / cam.fy;
+    const double n = std::sqrt(vx * vx + vy * vy + 1.0);
+    ft->f[0] = vx / n; ft->f[1] = vy / n; ft->f[2] = 1.0 / n;
+    return ft;
+  }
+};
+}  // namespace plsvo_hip_adapter
+
+namespace plsvo {
+namespace feature_detection {
+
+/// Drop-in for feature_detection::FastDetector (include/plsvo/feature_detection.h:60-131, src/feature_detection.cpp:45-121), the
+/// detector DepthFilter::initializeSeeds (src/depth_filter.cpp:161-165) and the bootstrap (src/initialization.cpp:135-137) call:
+///
+///     feature_detection::FastDetector detector(img_width, img_height, Config::gridSize(), Config::nPyrLevels());
+///     detector.setExistingFeatures(frame->pt_fts_);
+///     detector.detect(frame.get(), frame->img_pyr_, Config::triangMinCornerScore(), new_features);
+///
+/// detect() runs on the frame's pyramid slot on the device (uploaded on first sight, like the direct matcher's frames): `img_pyr` must
+/// be frame->img_pyr_, as it is at both call sites.  Duck-typed: Frame::cam_ / img_pyr_ / id_ / T_f_w_, PointFeat::px.
+class FastDetector {
+ public:
+  FastDetector(int img_width, int img_height, int cell_size, int n_pyr_levels)
+      : cell_size_(cell_size), n_pyr_levels_(n_pyr_levels), grid_n_cols_(0), grid_n_rows_(0), ok_(true) {
+    if (plsvo_detect_grid(img_width, img_height, cell_size, &grid_n_cols_, &grid_n_rows_) != PLSVO_OK) { grid_n_cols_ = grid_n_rows_ = 0; ok_ = false; }
+    grid_occupancy_.assign((size_t)grid_n_cols_ * grid_n_rows_, 0);
+  }
+
+  /// appends one feature per free grid cell whose best corner scores above detection_threshold, in cell order, and resets the grid;
+  /// on a device failure nothing is appended and ok() is false
+  template <class FrameT, class ImgPyr, class PointFeatT>
+  void detect(FrameT* frame, const ImgPyr& img_pyr, double detection_threshold, std::list<PointFeatT*>& fts) {
+    using namespace plsvo_hip_adapter;
+    (void)img_pyr;
+    ok_ = false;
+    FrameRegistry reg;
+    const int idx = reg.index(frame);
+    Context& c = default_context();
+    if (!reg.valid() || grid_occupancy_.empty()) { resetGrid(); return; }
+    plsvo_detect_params p;
+    p.cell_size = cell_size_; p.n_levels = n_pyr_levels_; p.fast_threshold = 20; p.reserved0 = 0; p.detection_threshold = detection_threshold;
+    std::vector<plsvo_corner> corners(grid_occupancy_.size());
+    int32_t count = 0;
+    // the library sizes a slot's records by the grid of the configured pyramid: the detector must have been made for the frame's size
+    int cols = 0, rows = 0;
+    if (plsvo_detect_grid(c.width, c.height, cell_size_, &cols, &rows) != PLSVO_OK || cols != grid_n_cols_ || rows != grid_n_rows_) {
+      std::fprintf(stderr, "[plsvo_hip] FastDetector was constructed for another image size than the frame's\n");
+      resetGrid();
+      return;
+    }
+    if (plsvo_hip_detect_fast(c.ctx, reg.frame_slot[(size_t)idx], 1, &p, grid_occupancy_.data(), corners.data(), &count) != PLSVO_OK) {
+      std::fprintf(stderr, "[plsvo_hip] detect_fast failed: %s\n", c.ctx ? plsvo_hip_last_error(c.ctx) : "no context");
+      resetGrid();
+      return;
+    }
+    for (int32_t i = 0; i < count; ++i)
+      fts.push_back(point_feat_traits<PointFeatT>::create(frame, reg.cam, (double)corners[(size_t)i].x, (double)corners[(size_t)i].y, corners[(size_t)i].level));
+    ok_ = true;
+    resetGrid();
+  }
+
+  /// flag the grid cells of the features the frame already has (src/feature_detection.cpp:106-113)
+  template <class PointFeatT>
+  void setExistingFeatures(const std::list<PointFeatT*>& fts) {
+    for (typename std::list<PointFeatT*>::const_iterator it = fts.begin(); it != fts.end(); ++it) setGridOccpuancy(**it);
+  }
+  /// flag one feature's cell (src/feature_detection.cpp:115-121; the reference's spelling)
+  template <class PointFeatT>
+  void setGridOccpuancy(const PointFeatT& ft) {
+    const int k = plsvo_detect_cell(grid_n_cols_, cell_size_, ft.px[0], ft.px[1]);
+    if (k >= 0 && (size_t)k < grid_occupancy_.size()) grid_occupancy_[(size_t)k] = 1;
+    else std::fprintf(stderr, "[plsvo_hip] FastDetector: feature outside the grid ignored\n");   // (the reference's .at() throws)
+  }
+  void resetGrid() { std::fill(grid_occupancy_.begin(), grid_occupancy_.end(), (uint8_t)0); }
+  bool ok() const { return ok_; }
+  int grid_n_cols() const { return grid_n_cols_; }
+  int grid_n_rows() const { return grid_n_rows_; }
+
+ private:
+  int cell_size_, n_pyr_levels_, grid_n_cols_, grid_n_rows_;
+  bool ok_;
+  std::vector<uint8_t> grid_occupancy_;
+};
+
+}  // namespace feature_detection
 }  // namespace plsvo
 
 namespace svo = plsvo;  // BASELINE.json spells the upstream name svo::SparseImgAlign

@@ -73,6 +73,10 @@ class HipBackend:
     def update_seeds(self, job):
         return self.ctx.update_seeds(job)
 
+    def detect_corners(self, slot, occupancy=None, cell_size=25, n_levels=3, detection_threshold=20.0):
+        """FastDetector::detect on the frame in `slot` (plsvo_hip_detect_fast): abi.CORNER_DTYPE records in cell order"""
+        return self.ctx.detect_fast(slot, 1, cell_size, n_levels, 20, detection_threshold, None if occupancy is None else occupancy[None])[0]
+
 
 class HipChainBackend(HipBackend):
     """The same product backend with steps 1-4 of a frame -- alignment, reprojection, matching, pose optimisation -- as ONE resident
@@ -116,13 +120,42 @@ def _bearing(cam, px):
     return r / np.linalg.norm(r, axis=1, keepdims=True)
 
 
+def seeds_from_corners(corners, cam, depth_mean, depth_min):
+    """Point seeds for detected corners (abi.CORNER_DTYPE records), as DepthFilter::initializeSeeds creates them
+    (src/depth_filter.cpp:161-172): a feature `new PointFeat(frame, px, level)` -- f = cam2world(px), type CORNER, grad (1, 0) -- in a
+    PointSeed(ftr, depth_mean, depth_min) (src/depth_filter.cpp:53-61: float arguments, a = b = 10, mu = 1.0 / depth_mean,
+    z_range = 1.0 / depth_min, sigma2 = z_range * z_range / 36, all stored as float).  -> the point half of plsvo_seeds_in without the
+    frame indices: a dict for abi.SeedsJob's `pt` once `ref_frame` / `cur_frame` are added."""
+    f32 = np.float32
+    n = len(corners)
+    px = np.stack([corners["x"].astype(np.float64), corners["y"].astype(np.float64)], axis=1) if n else np.zeros((0, 2))
+    z_range = f32(1.0 / float(f32(depth_min)))
+    return dict(px=px, f=_bearing(cam, px) if n else np.zeros((0, 3)), level=corners["level"].astype(np.int32), type=np.zeros(n, np.uint8),
+                grad=np.tile(np.array([1.0, 0.0]), (n, 1)), a=np.full(n, 10, f32), b=np.full(n, 10, f32),
+                mu=np.full(n, f32(1.0 / float(f32(depth_mean))), f32), z_range=np.full(n, z_range, f32),
+                sigma2=np.full(n, f32(z_range * z_range) / f32(36), f32))
+
+
+def _occupancy(px, w, h, cell):
+    """FastDetector::setExistingFeatures: the grid cells of the features a frame already has"""
+    cols, rows = -(-w // cell), -(-h // cell)
+    occ = np.zeros(cols * rows, np.uint8)
+    inside = (px[:, 0] >= 0) & (px[:, 0] < w) & (px[:, 1] >= 0) & (px[:, 1] < h)
+    occ[(px[inside, 1] / cell).astype(np.int64) * cols + (px[inside, 0] / cell).astype(np.int64)] = 1
+    return occ
+
+
 def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_thresh=2.0, mapping=False, known_frac=0.6,
-                 pos_noise=0.005, map_seed=0, kf_every=5):
+                 pos_noise=0.005, map_seed=0, kf_every=5, detect=False, detect_cell_size=25):
     """-> list of per-frame dicts (pose T_f_w, cov, counts).  Frame 0 is the keyframe with the true pose.
     mapping=True: only `known_frac` of the point landmarks start in the map (positions off by `pos_noise` x depth along
     their viewing ray), the others are depth-filter seeds; the seed update runs every frame; every `kf_every`-th frame
     plays the keyframe: its matches become observations of their landmarks (Feature3D::obs_ grows at keyframes only, as
-    in the reference) and the 20 least recently refined landmarks with >= 2 observations are structure-optimised."""
+    in the reference) and the 20 least recently refined landmarks with >= 2 observations are structure-optimised.
+    detect=True (with mapping, a backend with detect_corners): every keyframe, frame 0 included, also runs the corner detector on its
+    own pyramid slot with the cells of the features it tracks marked occupied (DepthFilter::initializeSeeds), and the corners become
+    point seeds (seeds_from_corners) that the following frames update next to the map's own; the records gain n_image_seeds /
+    n_image_seeds_converged.  These seeds come from the image alone and are not added to the map, whose landmarks carry the truth."""
     cam = seq["cam"]
     backend.load_frames(seq["images"])
     n_pts, n_seg = len(seq["pt_pos"]), len(seq["seg_spos"])
@@ -144,6 +177,17 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
         obs = {int(i): [(0, seq["pt_f0"][i])] for i in range(n_pts)}     # Feature3D::obs_: (frame, unit bearing)
         last_optim = np.zeros(n_pts, np.int64)
         poses_est = [kf_T.copy()]
+        detect = detect and hasattr(backend, "detect_corners")
+        img_seeds, img_converged = None, 0
+        w_img, h_img = int(cam[4]), int(cam[5])
+
+        def new_image_seeds(frame, feature_px):
+            corners = backend.detect_corners(frame, _occupancy(feature_px, w_img, h_img, detect_cell_size), detect_cell_size, n_pyr_levels)
+            sd = seeds_from_corners(corners, cam, dmean, dmin)
+            sd["ref_frame"] = np.full(len(corners), frame, np.int32)
+            return sd
+        if detect:
+            img_seeds = new_image_seeds(0, seq["pt_px0"][known])
     # features of the previous frame that still carry a landmark: index into the map + pixel position
     k0 = np.nonzero(known)[0]
     prev = dict(pt_idx=k0, pt_px=seq["pt_px0"][k0].copy(), seg_idx=np.arange(n_seg), seg_spx=seq["seg_spx0"].copy(),
@@ -252,6 +296,22 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
                 seeds = dict(idx=si_[keep_s], a=sr["pt_a"][keep_s], b=sr["pt_b"][keep_s], mu=sr["pt_mu"][keep_s], z_range=seeds["z_range"][keep_s],
                              sigma2=sr["pt_sigma2"][keep_s])
                 rec["n_seed_converged"] = int(conv.sum())
+            if detect:
+                # ---- 7. the seeds that came from the image: updated with this frame; a keyframe adds those of its own free cells ----
+                ni = len(img_seeds["px"])
+                if ni:
+                    sr = backend.update_seeds(abi.SeedsJob(cam, np.stack(poses_est), np.arange(len(poses_est), dtype=np.int32),
+                                                           dict(img_seeds, cur_frame=np.full(ni, k, np.int32)), None, n_pyr_levels=n_pyr_levels))
+                    stt = sr["pt_status"]
+                    img_converged += int((stt == abi.SEED_CONVERGED).sum())
+                    keep_s = ~((stt == abi.SEED_CONVERGED) | (stt == abi.SEED_NAN))
+                    img_seeds = {key: v[keep_s] for key, v in img_seeds.items()}
+                    for key in ("a", "b", "mu", "sigma2"):
+                        img_seeds[key] = sr["pt_" + key][keep_s]
+                if is_kf:
+                    fresh = new_image_seeds(k, px_new[kept])
+                    img_seeds = {key: np.concatenate([img_seeds[key], fresh[key]]) for key in img_seeds}
+                rec.update(n_image_seeds=len(img_seeds["px"]), n_image_seeds_converged=img_converged)
             rec.update(n_known=int(known.sum()), n_seeds=len(seeds["idx"]),
                        landmark_err=float(np.median(np.linalg.norm(P3[known] - seq["pt_pos"][known], axis=1))))
         out.append(rec)

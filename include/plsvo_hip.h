@@ -79,6 +79,11 @@ void plsvo_hip_destroy(plsvo_ctx* ctx);
  * on it.  The environment switches PLSVO_ALIGN_NO_REORDER / PLSVO_POSEOPT_NO_REORDER set the initial value to 0. */
 #define PLSVO_OPT_ALIGN_REORDER 4
 #define PLSVO_OPT_POSEOPT_REORDER 5
+/* Tail split of the large-batch alignment launch (one wave per frame, at least four rounds of resident workgroups, at least two pyramid
+ * levels): 1 (default) = the frames at the end of the launch order run as two workgroups of the same launch, their coarse levels first
+ * of all and their finest level last of all, so that the launch does not end on whole long frames; 0 = one workgroup per frame
+ * throughout.  Scheduling only -- every result is bit-identical.  The environment switch PLSVO_ALIGN_TAIL_SPLIT=0 sets the initial value to 0. */
+#define PLSVO_OPT_ALIGN_TAIL_SPLIT 6
 int plsvo_hip_set_option(plsvo_ctx* ctx, int option, int value);
 const char* plsvo_hip_last_error(const plsvo_ctx* ctx);   /* ctx may be NULL: last create error */
 void* plsvo_hip_stream(plsvo_ctx* ctx);                   /* the hipStream_t all work is enqueued on */
@@ -304,6 +309,9 @@ int plsvo_align_work(plsvo_ctx* ctx, uint64_t* patch_levels, uint64_t* patch_ite
    patch-iterations that run measured, longest first (align_kernels.hip::align_reorder_kernel).  Scheduling only: a job's results do not
    depend on its place in the launch.  Tests and measurements. */
 int plsvo_align_launch_order(plsvo_ctx* ctx, int n, int32_t* order);
+/* How many frames at the end of that order the LAST plsvo_align_run ran as two workgroups (PLSVO_OPT_ALIGN_TAIL_SPLIT): 0 when the
+   launch was not split.  Tests and measurements. */
+int plsvo_align_tail_frames(plsvo_ctx* ctx, int* tail_frames);
 /* of patch_iters, the evaluations of POINT patches that also wrote their 64 B of per-pixel chi2 terms to HBM (see plsvo_align_chi2_ties) */
 int plsvo_align_work_points(plsvo_ctx* ctx, uint64_t* point_patch_iters);
 

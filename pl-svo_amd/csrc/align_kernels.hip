@@ -40,6 +40,7 @@
 // fma contraction (__fmul_rn/__fadd_rn); geometry and all accumulators in double.
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <type_traits>
 
 #include "plsvo_dev.hpp"
@@ -344,7 +345,21 @@ __global__ __launch_bounds__(T, kMinWavesPerSimd) void align_fused_kernel(AlignB
   // deals consecutive blocks to the eight XCDs in turn, so the pair shares an L2 (a speed bonus, never a correctness condition).
   const bool pair = T >= kQuadMinThreads && b.pair != 0;
   const int rank = pair ? (int)((blockIdx.x >> 3) & 1u) : 0;
-  const int wg_index = pair ? (int)((blockIdx.x >> 4) * 8u + (blockIdx.x & 7u)) : (int)blockIdx.x;
+  int wg_index = pair ? (int)((blockIdx.x >> 4) * 8u + (blockIdx.x & 7u)) : (int)blockIdx.x;
+  // TAIL SPLIT (b.tail_n = S > 0, this shape only; grid = n_jobs + S).  Frames cost 10 .. 30 iterations and nothing known beforehand says
+  // which, so in an arbitrary order the launch ends on a few long frames with most of the chip idle.  The S frames that
+  // START LAST are therefore cut in two: blocks [0, S) run their levels above the finest first of all ("coarse part"), blocks
+  // [S, n) are the other frames, whole, and blocks [n, n + S) run the finest level of the S frames last of all ("fine part") -- the tail of
+  // the launch is then made of single levels, not of whole frames.  The frame's state crosses from one workgroup to the other in HBM
+  // (AlignStateDev, seg_alive: what the per-level debug launches carry across kernel boundaries) behind a per-frame flag
+  // (plsvo_wave.hpp::tail_publish / tail_wait); the hardware starts workgroups in blockIdx order, so a fine part starts a launch-length
+  // after its coarse part, but it does not rely on that: it polls the flag, bounded.  Results per frame are bit-identical to one workgroup's.
+  constexpr bool kTail = T == 64;
+  int part = 0;   // 0 = the whole frame, 1 = coarse part, 2 = fine part (workgroup-uniform)
+  if (kTail && b.tail_n > 0) {
+    if (wg_index < b.tail_n) { part = 1; wg_index += b.n_jobs - b.tail_n; }
+    else { if (wg_index >= b.n_jobs) part = 2; wg_index -= b.tail_n; }
+  }
   if (wg_index >= b.n_jobs) return;
   const bool lead = rank == 0;                    // the workgroup that publishes the frame's state, pose and trace
   const bool own_pts = !pair || rank == 0, own_segs = !pair || rank == 1;
@@ -359,7 +374,7 @@ __global__ __launch_bounds__(T, kMinWavesPerSimd) void align_fused_kernel(AlignB
   double* s_red = reinterpret_cast<double*>(smem);                       // ROWS * 32: row partials
   double* s_pose = s_red + ROWS * 32;                                    // 0..8 R, 9..11 t, 12..18 model, 19..25 old model, 26 chi2_, 27 #evals, 28/29/31 work counters, 30 n_meas_ of the previous iteration
   double* s_tot = s_pose + 32;                                           // block totals of the last iteration: 21 H, 6 Jres, chi2, n_meas, evals
-  int* s_ctl = reinterpret_cast<int*>(s_tot + 32);                       // 0 break, 1 stop, 2 iterations done, 3 error, 5 #patches of the level
+  int* s_ctl = reinterpret_cast<int*>(s_tot + 32);                       // 0 break, 1 stop, 2 iterations done, 3 error, 5 #patches of the level, 11 part of a split frame (0 whole, 1 coarse, 2 fine), 12 its flag word
   int2* s_meta = reinterpret_cast<int2*>(s_ctl + 32);                    // cap: x = feature (>= 0 point, < 0 segment -1-x, SLOT_HOLE), y = first slot | N << 20
   float* s_abs = reinterpret_cast<float*>(s_meta + cap);                 // cap: sum |res| of the slot's 16 pixels, -1 = sample not in the image
   int* s_dead = reinterpret_cast<int*>(s_abs + cap);                     // scap: per segment, 0 = alive, k + 1 = culled at iteration k of this level
@@ -374,13 +389,39 @@ __global__ __launch_bounds__(T, kMinWavesPerSimd) void align_fused_kernel(AlignB
   __shared__ unsigned long long s_tlast;
   if (tid == 0) { for (int k = 0; k < 8; ++k) s_time[k] = 0; s_tlast = __builtin_amdgcn_s_memtime(); }
 #endif
-  const int lv_first = min(job.max_level, level_hi), lv_last = max(job.min_level, level_lo);
+  int lv_first = min(job.max_level, level_hi), lv_last = max(job.min_level, level_lo);
   const bool nothing = job.skip || lv_first < lv_last;
+  if (part == 1) lv_last += 1;          // (a frame with ONE level: its coarse part initialises, runs no level and hands the initial state on)
+  else if (part == 2) lv_first = lv_last;
+  if (part == 2) do_init = 0;
+  unsigned* const tail_flag = kTail && part ? b.tail_flag + (wg_index - (b.n_jobs - b.tail_n)) : nullptr;
+  if (part == 2 && !nothing) {
+    // the coarse part's state: wait for its flag (every exit of a coarse part publishes it), then what it left decides as the one loop would
+    // have: a layout error ends the frame, a solver stop goes on into the level (one iteration that rolls back)
+    if (!tail_wait(tail_flag)) { if (tid == 0) st->error = 2; return; }
+    if (handoff_load_i32(&st->error)) return;
+    if (lane < 8) {   // model, old model and chi2 go to LDS from eight lanes (AlignStateDev: T[7], chi2)
+      const double v = handoff_load_f64(&st->T[lane]);
+      if (lane < 7) { s_pose[12 + lane] = v; s_pose[19 + lane] = v; } else s_pose[26] = v;
+    }
+    if (lane == 8) s_ctl[1] = handoff_load_i32(&st->stop);
+  }
   if (do_init && own_segs) {
     // solver reset() ([ext] vk::NLLSSolver::reset) and the working copy of the segment flags
     for (int s = tid; s < job.n_seg; s += T)
-      b.seg_alive[job.seg_off + s] = b.seg_alive_in ? (b.seg_alive_in[job.seg_off + s] != 0) : 1;
+      ((kTail && part == 1) ? b.seg_alive_tail : b.seg_alive)[job.seg_off + s] = b.seg_alive_in ? (b.seg_alive_in[job.seg_off + s] != 0) : 1;
   }
+  if (kTail && tid == 0) {   // (read back at the exits: nothing of the split stays live across the levels)
+    s_ctl[11] = part; s_ctl[12] = wg_index - (b.n_jobs - b.tail_n);
+    for (int k = 0; k < PLSVO_MAX_LEVELS; ++k) s_ctl[16 + k] = 0;   // a coarse part's iterations per level
+  }
+  // A coarse part must leave NO byte of the frame's state or segment flags dirty in its XCD's L2: the fine part, on another XCD, writes the
+  // same bytes later, and at the end of the launch the two caches' write-backs land in either order.  So it works on a copy of the segment
+  // flags, skips the initialising stores, keeps its iteration counts in LDS, and at its end writes the whole state and the flags with
+  // agent-scope (write-through) stores.
+  // (the pointer is chosen where it is used -- four places, none of them hot -- from the part kept in LDS: a pointer held across the levels
+  //  tips the pixel block into scratch)
+  auto seg_flags = [&]() -> uint8_t* { return (kTail && s_ctl[11] == 1) ? b.seg_alive_tail : b.seg_alive; };
   if (tid == 0) {
     // (the seven pose values are requested together and go to LDS from registers: written to the state and read back one by one, each
     //  of the fourteen accesses waited for the one before -- a lone frame pays a microsecond per dependent first touch)
@@ -388,7 +429,7 @@ __global__ __launch_bounds__(T, kMinWavesPerSimd) void align_fused_kernel(AlignB
     if (do_init) {
 #pragma unroll
       for (int k = 0; k < 7; ++k) T_in[k] = b.T0[7 * job_id + k];
-      if (lead) {
+      if (lead && !(kTail && part == 1 && !nothing)) {
 #pragma unroll
       for (int k = 0; k < 7; ++k) st->T[k] = T_in[k];
       st->chi2 = 1e10; st->n_meas = 0; st->stop = 0; st->log_count = 0; st->error = 0;
@@ -399,21 +440,24 @@ __global__ __launch_bounds__(T, kMinWavesPerSimd) void align_fused_kernel(AlignB
       if (nothing && b.poses) for (int k = 0; k < 7; ++k) b.poses[7 * job_id + k] = T_in[k];
       if (nothing && b.work_key) b.work_key[job_id] = 0;   // a job without work sorts last in the next launch's order
       }
-    } else if (!nothing) {   // per-level debug launches: the state crosses launches in HBM
+    } else if (!nothing && part != 2) {   // per-level debug launches: the state crosses launches in HBM
 #pragma unroll
       for (int k = 0; k < 7; ++k) T_in[k] = st->T[k];
       chi_in = st->chi2; stop_in = st->stop;
     }
     if (!nothing) {
+      if (part != 2) {   // (the fine part of a split frame has put its model, chi2 and stop there already)
 #pragma unroll
       for (int k = 0; k < 7; ++k) { s_pose[12 + k] = T_in[k]; s_pose[19 + k] = T_in[k]; }
-      s_pose[26] = chi_in; s_pose[28] = 0.0; s_pose[29] = 0.0; s_pose[31] = 0.0;
+      s_pose[26] = chi_in; s_ctl[1] = stop_in;
+      }
+      s_pose[28] = 0.0; s_pose[29] = 0.0; s_pose[31] = 0.0;
       for (int k = 0; k < 32; ++k) s_tot[k] = 0.0;
-      s_ctl[1] = stop_in; s_ctl[3] = 0; s_ctl[6] = 0; s_ctl[9] = 0;
+      s_ctl[3] = 0; s_ctl[6] = 0; s_ctl[9] = 0;
       s_ctl[10] = 0;
     }
   }
-  if (nothing) return;
+  if (nothing) { if (kTail && part == 1) tail_publish(tail_flag); return; }   // (nothing to hand over: the fine part of such a job does not wait either)
   block_sync<T>();   // seg_alive / state of this job initialised (same workgroup: visible after the barrier)
   if (b.chi_lds_pts > 0) {   // LDS planes: the slots between the last point and the next multiple of 4 are read by the exact sums: +0
     const int tail0 = job.n_pts * 16, tail1 = ((job.n_pts + 3) & ~3) * 16;
@@ -445,6 +489,7 @@ __global__ __launch_bounds__(T, kMinWavesPerSimd) void align_fused_kernel(AlignB
     for (int l = 0; l < PLSVO_MAX_LEVELS; ++l) if (l == level) { n_slots = job.n_slots[l]; long_lines = ((job.long_mask >> l) & 1) != 0; }
     if (n_slots > cap || n_slots > job.patch_cap) {  // host layout inconsistent with the launch: flag and bail out (uniform)
       if (tid == 0 && lead) { st->error = 1; if (b.work_key) b.work_key[job_id] = 0; }
+      if (kTail && s_ctl[11] == 1) { if (tid == 0) handoff_store(&st->error, 1); tail_publish(b.tail_flag + s_ctl[12]); }   // (the fine part reads the error, ends, and writes nothing)
       return;
     }
     const int slot_lo = (pair && rank == 1) ? min(line0, n_slots) : 0, slot_hi = (pair && rank == 0) ? min(line0, n_slots) : n_slots;
@@ -494,7 +539,7 @@ __global__ __launch_bounds__(T, kMinWavesPerSimd) void align_fused_kernel(AlignB
           for (int c = 0; c < 3; ++c) { g_p[c] = b.seg_p[3 * s + c]; g_q[c] = b.seg_q[3 * s + c]; }
         }
         const int code = b.seg_slot[(size_t)(level - b.slot_level0) * b.slot_stride + s];
-        if (code >= 0 && b.seg_alive[s]) {
+        if (code >= 0 && seg_flags()[s]) {
           const int p0 = code & 0xfffff, N = code >> 20;
           // :316-332: 2-D step on the level image, 3-D step between the end points, both accumulated
           const double sx = kQuad ? g_s[0] : b.seg_spx[2 * s], sy = kQuad ? g_s[1] : b.seg_spx[2 * s + 1];
@@ -717,7 +762,7 @@ __global__ __launch_bounds__(T, kMinWavesPerSimd) void align_fused_kernel(AlignB
                 }
               } else if (p == first) {
                 s_dead[-1 - meta.x] = iter + 1;                                    // :687-688 it->feat3D = NULL
-                b.seg_alive[job.seg_off + (-1 - meta.x)] = 0;
+                seg_flags()[job.seg_off + (-1 - meta.x)] = 0;
               }
             }
           }
@@ -1039,7 +1084,7 @@ __global__ __launch_bounds__(T, kMinWavesPerSimd) void align_fused_kernel(AlignB
                 }
               } else if (p == first) {
                 s_dead[-1 - meta.x] = iter + 1;                                    // :687-688 it->feat3D = NULL
-                b.seg_alive[job.seg_off + (-1 - meta.x)] = 0;
+                seg_flags()[job.seg_off + (-1 - meta.x)] = 0;
               }
             }
           }
@@ -1213,25 +1258,67 @@ __global__ __launch_bounds__(T, kMinWavesPerSimd) void align_fused_kernel(AlignB
     }
 
     if (tid == 0) {   // work counters stay in LDS until the end of the launch (a global read-modify-write here would stall every level)
-      if (lead) st->iters[level] = s_ctl[2];
+      if (kTail && s_ctl[11] == 1) s_ctl[16 + level] = s_ctl[2];
+      else if (lead) st->iters[level] = s_ctl[2];
       s_pose[28] += pair ? s_tot[31] : (double)s_ctl[5];   // (two workgroups per frame: value 31 of the exchanged totals = both patch counts)
       s_pose[29] += s_pose[27];
+      // old_model_ = model_ at the top of every level's optimize() ([ext] NLLSSolver::optimizeGaussNewton: `old_model = model`; the first
+      // level's is set with the model above): a solve that fails at iteration 0 of a level keeps the model the level above ended on,
+      // whichever workgroup or launch ran that level
+      for (int k = 0; k < 7; ++k) s_pose[19 + k] = s_pose[12 + k];
     }
   }  // levels
 
   block_sync<T>();
+  const int part_end = kTail ? s_ctl[11] : 0;
+  if (part_end == 1) {
+    // coarse part of a split frame: the frame's state as the one loop would hold it here, assembled in LDS (s_red is free) and sent out
+    // write-through, a word per lane; H, n_meas and the pose copy are the fine part's
+    constexpr int kWords = (int)(sizeof(AlignStateDev) / sizeof(unsigned long long));
+    static_assert(sizeof(AlignStateDev) % sizeof(unsigned long long) == 0 && kWords <= 64 && sizeof(AlignStateDev) <= ROWS * 32 * sizeof(double), "one word per lane, in s_red");
+    unsigned long long* const img = reinterpret_cast<unsigned long long*>(s_red);
+    if (tid < kWords) img[tid] = 0ull;
+    block_sync<T>();
+    if (tid == 0) {
+      AlignStateDev* const im = reinterpret_cast<AlignStateDev*>(s_red);
+      for (int k = 0; k < 7; ++k) im->T[k] = s_pose[12 + k];
+      im->chi2 = s_pose[26]; im->stop = s_ctl[1]; im->error = s_ctl[3];
+      for (int k = 0; k < PLSVO_MAX_LEVELS; ++k) im->iters[k] = s_ctl[16 + k];
+      im->patch_levels = (unsigned long long)(s_pose[28] + 0.5); im->patch_iters = (unsigned long long)(s_pose[29] + 0.5);
+      im->patch_iters_pt = (unsigned long long)(s_pose[31] + 0.5);
+      im->chi2_ties = s_ctl[6]; im->chi2_unarmed = s_ctl[9];
+#ifdef PLSVO_TIMING
+      for (int k = 0; k < 8; ++k) im->phase_ticks[k] = s_time[k];
+#endif
+      if (b.work_key) handoff_store(&b.work_key[job_id], (int)fmin(s_pose[29] + 0.5, 2147483647.0));
+    }
+    block_sync<T>();
+    if (tid < kWords) handoff_store(reinterpret_cast<unsigned long long*>(st) + tid, img[tid]);
+    for (int sg = tid; sg < job.n_seg; sg += T) handoff_store(&b.seg_alive[job.seg_off + sg], b.seg_alive_tail[job.seg_off + sg]);
+    tail_publish(b.tail_flag + s_ctl[12]);
+    return;
+  }
   if (tid == 0 && lead) {
     for (int k = 0; k < 7; ++k) st->T[k] = s_pose[12 + k];
     if (b.poses) for (int k = 0; k < 7; ++k) b.poses[7 * job_id + k] = s_pose[12 + k];
     st->chi2 = s_pose[26];
-    st->patch_levels += (unsigned long long)(s_pose[28] + 0.5);
-    st->patch_iters += (unsigned long long)(s_pose[29] + 0.5);
-    if (b.work_key) b.work_key[job_id] = (int)fmin(s_pose[29] + 0.5, 2147483647.0);   // what this frame cost: the next launch's sort key
-    st->patch_iters_pt += (unsigned long long)(s_pose[31] + 0.5);
+    // (work counters add up over the launches / the two workgroups of a frame; a fine part reads the coarse part's with agent-scope loads)
+    unsigned long long w_lv = 0, w_it = 0, w_pt = 0; int w_ties = 0, w_unarmed = 0; double w_key = 0.0;
+    if (part_end == 2) {
+      w_lv = handoff_load_u64(&st->patch_levels); w_it = handoff_load_u64(&st->patch_iters); w_pt = handoff_load_u64(&st->patch_iters_pt);
+      w_ties = handoff_load_i32(&st->chi2_ties); w_unarmed = handoff_load_i32(&st->chi2_unarmed);
+      if (b.work_key) w_key = (double)handoff_load_i32(&b.work_key[job_id]);   // the key is the cost of the WHOLE frame
+    } else {
+      w_lv = st->patch_levels; w_it = st->patch_iters; w_pt = st->patch_iters_pt; w_ties = st->chi2_ties; w_unarmed = st->chi2_unarmed;
+    }
+    st->patch_levels = w_lv + (unsigned long long)(s_pose[28] + 0.5);
+    st->patch_iters = w_it + (unsigned long long)(s_pose[29] + 0.5);
+    if (b.work_key) b.work_key[job_id] = (int)fmin(w_key + s_pose[29] + 0.5, 2147483647.0);   // what this frame cost: the next launch's sort key
+    st->patch_iters_pt = w_pt + (unsigned long long)(s_pose[31] + 0.5);
     st->stop = s_ctl[1];
     if (s_ctl[3]) st->error = s_ctl[3];
-    st->chi2_ties += s_ctl[6];
-    st->chi2_unarmed += s_ctl[9];
+    st->chi2_ties = w_ties + s_ctl[6];
+    st->chi2_unarmed = w_unarmed + s_ctl[9];
     st->n_meas = (unsigned long long)(s_tot[28] + 0.5);
     for (int i = 0; i < 6; ++i) for (int jj = 0; jj < 6; ++jj) st->H[i * 6 + jj] = s_tot[sym6_index(i, jj)];
 #ifdef PLSVO_TIMING
@@ -1245,6 +1332,11 @@ __global__ __launch_bounds__(T, kMinWavesPerSimd) void align_fused_kernel(AlignB
 size_t align_level_lds_bytes(int threads, int cap, int scap, int chi_lds_pts) { return align_lds_used(threads, cap, scap, chi_lds_pts); }
 
 }  // namespace plsvo_hip
+#ifdef PLSVO_WAVE_EMU
+// host emulation build only (tests): the value the coarse part of a split frame publishes; anything but 1 makes every fine part's bounded
+// poll give up -- the time-out branch, which nothing may provoke on a GPU
+extern "C" void plsvo_emu_set_tail_flag_value(unsigned v) { plsvo_hip::wave_emu_tail_flag_value() = v; }
+#endif
 extern "C" const char* plsvo_hip_build_flags(void) { return ""; }   // no compile-time experiment switch is left in this build
 namespace plsvo_hip {
 
@@ -1253,7 +1345,7 @@ static hipError_t launch_fused_T(const AlignBatchDev& b, int cap, int scap, int 
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(align_fused_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   // one workgroup per frame, or (b.pair) two: blocks q and q + 8 of every group of 16
-  const unsigned grid = (T >= kQuadMinThreads && b.pair) ? (unsigned)((b.n_jobs + 7) / 8) * 16u : (unsigned)b.n_jobs;
+  const unsigned grid = (T >= kQuadMinThreads && b.pair) ? (unsigned)((b.n_jobs + 7) / 8) * 16u : (unsigned)(b.n_jobs + (T == 64 ? b.tail_n : 0));   // (tail split: a second workgroup for the last tail_n frames)
 #ifdef PLSVO_WAVE_EMU
   wave_emu::pair_stride() = (T >= kQuadMinThreads && b.pair) ? 8 : 0;   // the emulator runs the two workgroups of a frame on two OS threads
 #endif
@@ -1272,6 +1364,10 @@ static hipError_t launch_fused_T(const AlignBatchDev& b, int cap, int scap, int 
 // batch by the patch-iterations of its LAST launch (written by every frame's workgroup as it ends; counting sort over 1024 bins, longest first) into the order
 // the NEXT launch of the same batch uses.  A tracker's streams change slowly from frame to frame, a benchmark's not at all.  The results of a
 // job do not depend on where it sits in the launch (tests: batch == single, bit for bit), so this is scheduling only.  One workgroup.
+// The sort needs a previous launch on (nearly) the same inputs.  What needs no knowledge of the cost is the TAIL SPLIT inside
+// align_fused_kernel<64> (b.tail_n): the last two rounds' worth of the order -- this kernel's or the stage call's -- run as a coarse and a
+// fine workgroup of the same launch, so the launch ends on single levels whatever the frames cost (measured: 13.02 -> 12.71 ms in the
+// staged order at 32768 frames).  The key a split frame writes is the cost of both its parts, so this sort sees whole frames either way.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void align_reorder_kernel(const int* work_key, int n, int* order_out, int shift) {
   __shared__ int s_hist[1024];

@@ -128,6 +128,13 @@ struct plsvo_ctx {
   const int* a_stage_order = nullptr;          // the staged batch's own order (most patches first), inside a_d_blob
   bool a_one_shot = false, p_one_shot = false;   // set around the run of a one-shot batch call: its launch order is never consumed
   int env_align_reorder_min = 0;            //   PLSVO_ALIGN_REORDER_MIN: smallest batch that is re-ordered (tests; default 16 frames per CU)
+  // tail split of the one-wave-per-frame alignment launch (align_kernels.hip): PLSVO_OPT_ALIGN_TAIL_SPLIT, and for tests and measurements
+  // PLSVO_ALIGN_TAIL_MIN (smallest batch that is split; default four times the resident workgroups), PLSVO_ALIGN_TAIL_K (tail set in
+  // multiples of the resident workgroups; default 2), PLSVO_ALIGN_TAIL_FRAMES (the tail set itself, in frames)
+  bool opt_align_tail_split = true;
+  int env_align_tail_min = 0, env_align_tail_k = 0, env_align_tail_frames = 0;
+  DevBuf a_d_tailflag;                      //   one flag word per tail frame, zeroed before every launch
+  DevBuf a_d_alive_tail;                    //   the coarse parts' working copy of the segment flags
   DevBuf a_d_xbuf;                          // two workgroups per frame: their exchange granules (2 KB per frame, zeroed once)
   unsigned int x_launch = 0;                // launches that used it (tags = launch << 10 | exchange: never repeated)
   bool env_align_no_pair = false;
@@ -274,6 +281,10 @@ static int create_ctx(int device_id, void* stream, bool use_given_stream, plsvo_
   c->env_align_no_pair = env_flag("PLSVO_ALIGN_NO_PAIR");   // (A/B: one workgroup per frame also for small batches)
   c->env_align_no_reorder = env_flag("PLSVO_ALIGN_NO_REORDER");   // (A/B: keep the stage call's patch-count order for every launch)
   if (const char* s = getenv("PLSVO_ALIGN_REORDER_MIN")) c->env_align_reorder_min = atoi(s);
+  if (const char* s = getenv("PLSVO_ALIGN_TAIL_SPLIT")) c->opt_align_tail_split = atoi(s) != 0;
+  if (const char* s = getenv("PLSVO_ALIGN_TAIL_MIN")) c->env_align_tail_min = atoi(s);
+  if (const char* s = getenv("PLSVO_ALIGN_TAIL_K")) c->env_align_tail_k = atoi(s);
+  if (const char* s = getenv("PLSVO_ALIGN_TAIL_FRAMES")) c->env_align_tail_frames = atoi(s);
   c->env_poseopt_no_reorder = env_flag("PLSVO_POSEOPT_NO_REORDER");
   if (const char* s = getenv("PLSVO_POSEOPT_REORDER_MIN")) c->env_poseopt_reorder_min = atoi(s);
   c->env_host_timing = getenv("PLSVO_HOST_TIMING") != nullptr;
@@ -287,7 +298,7 @@ extern "C" void plsvo_hip_destroy(plsvo_ctx* c) {
   (void)hipStreamSynchronize(c->stream);
   prof_collect(c);
   for (auto& ep : c->ev_pool) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
-  c->a_d_xbuf.release(); c->a_d_order[0].release(); c->a_d_order[1].release(); c->a_d_workkey.release(); c->p_d_workkey.release(); c->p_d_order[0].release(); c->p_d_order[1].release();
+  c->a_d_tailflag.release(); c->a_d_alive_tail.release(); c->a_d_xbuf.release(); c->a_d_order[0].release(); c->a_d_order[1].release(); c->a_d_workkey.release(); c->p_d_workkey.release(); c->p_d_order[0].release(); c->p_d_order[1].release();
   DevBuf* bufs[] = { &c->pyr_slab, &c->pyr_tiled, &c->pyr_upload, &c->a_d_blob, &c->a_d_state, &c->a_d_alive, &c->a_d_pxyz, &c->a_d_puv, &c->a_d_cref,
                      &c->a_d_chi, &c->a_d_log, &c->a_d_poses, &c->p_d_blob, &c->p_d_state, &c->p_d_ptkeep, &c->p_d_segkeep, &c->p_d_s32, &c->p_d_s64,
                      &c->p_d_log, &c->p_d_poses, &c->s_d_in, &c->s_d_out, &c->ch_d_blob, &c->ch_d_work, &c->ch_d_po, &c->ch_d_state,
@@ -328,6 +339,11 @@ extern "C" int plsvo_hip_set_option(plsvo_ctx* c, int option, int value) {
     } else {
       c->env_poseopt_no_reorder = value == 0;
     }
+    return PLSVO_OK;
+  }
+  if (option == PLSVO_OPT_ALIGN_TAIL_SPLIT) {
+    if (value != 0 && value != 1) return fail(c, PLSVO_E_INVALID, "set_option: the alignment's tail split is 0 (one workgroup per frame throughout) or 1 (the frames that start last run as a coarse and a fine part)");
+    c->opt_align_tail_split = value != 0;
     return PLSVO_OK;
   }
   return fail(c, PLSVO_E_INVALID, "set_option: unknown option");
@@ -1080,7 +1096,7 @@ extern "C" int plsvo_align_stage(plsvo_ctx* c, int n, const plsvo_align_in* in) 
   b.log = c->a_trace_cap > 0 ? c->a_d_log.as<plsvo_align_iterlog>() : nullptr;
   b.log_cap = c->a_trace_cap;
   b.n_jobs = n;
-  b.pair = 0; b.xseq0 = 0; b.xbuf = nullptr; b.work_key = nullptr;   // (plsvo_align_run decides)
+  b.pair = 0; b.xseq0 = 0; b.xbuf = nullptr; b.work_key = nullptr; b.tail_n = 0; b.reserved_tail = 0; b.tail_flag = nullptr; b.seg_alive_tail = nullptr;   // (plsvo_align_run decides)
   b.order = reinterpret_cast<const int*>(base + o_order);
   c->a_stage_order = b.order;
   c->a_jobs.swap(jobs);
@@ -1139,6 +1155,7 @@ struct RoctxRange {
 };
 }  // namespace
 
+constexpr int kAlignTailRounds = 2;   // tail set of the split, in rounds of resident workgroups (measured: DESIGN.md 3.1)
 extern "C" int plsvo_align_run(plsvo_ctx* c) {
   CTX_CHECK(c);
   RoctxRange range("sparse_img_align");
@@ -1205,6 +1222,27 @@ extern "C" int plsvo_align_run(plsvo_ctx* c) {
     }
     c->a_b.work_key = c->a_d_workkey.as<int>();
   }
+  // TAIL SPLIT: a launch of many rounds of resident workgroups ends on whichever long frames started last (~5 % of it: nothing known
+  // before a frame runs predicts its cost).  The frames at the end of the launch order -- two rounds' worth -- therefore run as two
+  // workgroups of the same launch, their coarse levels first and their finest level last (align_kernels.hip), so that the launch ends on
+  // single levels.  Scheduling only: every result is bit-identical.  One wave per frame, at least two levels, at least four rounds; a
+  // traced batch (plsvo_align_set_trace: its records count up in the frame's state iteration by iteration) keeps one workgroup per frame.
+  c->a_b.tail_n = 0; c->a_b.tail_flag = nullptr; c->a_b.seg_alive_tail = nullptr;
+  if (c->opt_align_tail_split && threads == 64 && have_levels && c->a_gmax > c->a_gmin && !pair && !per_level && c->a_trace_cap == 0) {
+    const int resident = cus_run * 512 / threads;
+    const int min_n = c->env_align_tail_min > 0 ? c->env_align_tail_min : 4 * resident;
+    const int want = c->env_align_tail_frames > 0 ? c->env_align_tail_frames : (c->env_align_tail_k > 0 ? c->env_align_tail_k : kAlignTailRounds) * resident;
+    if (c->a_n >= min_n) {
+      const int tail_n = std::min(c->a_n, want);
+      // flags are re-armed by a memset ahead of every launch (a 16-byte multiple from the allocation's start): no tag to keep in step
+      // with the launch count, and a launch that was cut short leaves nothing behind
+      const size_t fbytes = (((size_t)tail_n * sizeof(unsigned int)) + 15) & ~(size_t)15;
+      HIP_TRY(c, c->a_d_tailflag.ensure(fbytes));
+      HIP_TRY(c, hipMemsetAsync(c->a_d_tailflag.p, 0, fbytes, c->stream));
+      HIP_TRY(c, c->a_d_alive_tail.ensure((size_t)std::max(c->a_total_seg, 1)));
+      c->a_b.tail_n = tail_n; c->a_b.tail_flag = c->a_d_tailflag.as<unsigned int>(); c->a_b.seg_alive_tail = c->a_d_alive_tail.as<uint8_t>();
+    }
+  }
   if (!per_level || !have_levels) {
     EventPair ep{}; prof_begin(c, PLSVO_K_ALIGN_LEVEL, &ep);
     HIP_TRY(c, launch_align_levels(c->a_b, cap, scap, have_levels ? c->a_gmax : 0, have_levels ? c->a_gmin : 0, 1, threads, lds, c->stream));
@@ -1258,6 +1296,9 @@ extern "C" int plsvo_align_fetch(plsvo_ctx* c, int n, plsvo_align_out* out) {
       memcpy(alive_out, alive + c->a_jobs[(size_t)j].seg_off, (size_t)c->a_jobs[(size_t)j].n_seg);
     if (s.error) dev_err = s.error;
   }
+  // 1: a job's slot layout does not fit the launch; 2: a workgroup waited in vain for another one's data (the partner of a two-workgroup
+  // frame, or the coarse part of a split frame) -- nothing a capacity would have prevented
+  if (dev_err == 2) return fail(c, PLSVO_E_HIP, "align: a workgroup timed out waiting for the workgroup it shares a frame with (device-side hand-off, code 2)");
   if (dev_err) return fail(c, PLSVO_E_CAPACITY, "align: device-side capacity check failed (code " + std::to_string(dev_err) + ")");
   return PLSVO_OK;
 }
@@ -1378,6 +1419,14 @@ extern "C" int plsvo_align_launch_order(plsvo_ctx* c, int n, int32_t* order) {
   if (!c->a_b.order) { for (int j = 0; j < n; ++j) order[j] = j; return PLSVO_OK; }
   HIP_TRY(c, hipMemcpyAsync(order, c->a_b.order, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_align_tail_frames(plsvo_ctx* c, int* tail_frames) {
+  CTX_CHECK(c);
+  if (!c->a_staged) return fail(c, PLSVO_E_STATE, "align_tail_frames: no staged batch");
+  if (!tail_frames) return fail(c, PLSVO_E_INVALID, "align_tail_frames: NULL output");
+  *tail_frames = c->a_b.tail_n;
   return PLSVO_OK;
 }
 

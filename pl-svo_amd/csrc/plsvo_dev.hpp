@@ -134,6 +134,14 @@ struct AlignBatchDev {
   int pair;                    // 0 = one workgroup per frame, 1 = two
   unsigned int xseq0;          // first sequence number of this launch's exchanges (launch number << 10: never repeats in the buffer's life)
   unsigned long long* xbuf;    // 2 (parity) x 2 (rank) x 64 granules per frame
+  // TAIL SPLIT (one wave per frame, batches of many rounds): the last tail_n entries of the launch order run as TWO workgroups of the
+  // same launch -- the coarse levels first of all, the finest level last of all -- and hand the frame's state over through
+  // AlignStateDev / seg_alive and one flag word each (align_kernels.hip::align_fused_kernel).  0 = every frame is one workgroup.
+  int tail_n;
+  int reserved_tail;
+  unsigned int* tail_flag;     // tail_n words, zeroed before every launch; 1 = the coarse part of tail frame t has published its state
+  uint8_t* seg_alive_tail;     // a coarse part's working copy of the segment flags (layout of seg_alive): it never stores into seg_alive or the
+                               // state with ordinary stores, so no dirty byte of its L2 can land on what the fine part writes later
 };
 
 struct PoseJobDev {

@@ -368,6 +368,72 @@ __device__ __forceinline__ double pair_allgather32(unsigned long long* xb, int r
   return __hiloint2double((int)hi, (int)lo);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Hand-off of a frame's state from one workgroup to another workgroup of the SAME launch (align_kernels.hip, tail split): the producer
+// writes every handed-off value with handoff_store_* -- agent-scope relaxed stores (sc1: write-through, visible to every XCD; what the pair
+// exchange above ships its granules with), so no release fence is needed: an agent-scope release writes the whole L2's dirty lines back,
+// measured 0.08 ms per 2048 publishes on a 13 ms launch -- then tail_publish: the wave's own wait for those stores and ONE lane's
+// agent-scope store of the flag word.  The consumer polls that one word with relaxed agent-scope loads (never served from its CU's
+// L1), BOUNDED like the pair exchange above, then takes ONE agent-scope acquire (drops the CU's stale lines) and reads.  Values at a
+// wave-uniform address are read with handoff_load_* -- agent-scope loads, which the compiler keeps off the scalar cache the acquire
+// does not cover.  One wave per workgroup on both sides.  The flag words are zeroed before every launch.
+// ------------------------------------------------------------------------------------------------
+#ifdef PLSVO_WAVE_EMU
+constexpr unsigned kTailPollMax = 1u << 10;   // (the emulator runs workgroups in blockIdx order: a flag is either there or never comes)
+inline unsigned& wave_emu_tail_flag_value() { static unsigned v = 1u; return v; }   // test hook: what a coarse part publishes (1 = the protocol's value)
+#else
+constexpr unsigned kTailPollMax = kPairPollMax;
+#endif
+__device__ __forceinline__ unsigned long long handoff_load_u64(const void* p) {
+#ifdef PLSVO_WAVE_EMU
+  return __atomic_load_n(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_ACQUIRE);
+#else
+  return __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#endif
+}
+__device__ __forceinline__ double handoff_load_f64(const double* p) { return __longlong_as_double((long long)handoff_load_u64(p)); }
+__device__ __forceinline__ int handoff_load_i32(const void* p) {
+#ifdef PLSVO_WAVE_EMU
+  return __atomic_load_n(reinterpret_cast<const int*>(p), __ATOMIC_ACQUIRE);
+#else
+  return __hip_atomic_load(reinterpret_cast<const int*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#endif
+}
+template <typename V>
+__device__ __forceinline__ void handoff_store(V* p, V v) {
+#ifdef PLSVO_WAVE_EMU
+  __atomic_store_n(p, v, __ATOMIC_RELEASE);
+#else
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#endif
+}
+__device__ __forceinline__ void handoff_store_f64(double* p, double v) { handoff_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v)); }
+// called by the whole (single) wave of the producer, after its last handoff_store_* of the handed-off state
+__device__ __forceinline__ void tail_publish(unsigned* flag) {
+#ifdef PLSVO_WAVE_EMU
+  if ((threadIdx.x & 63) == 0) __atomic_store_n(flag, wave_emu_tail_flag_value(), __ATOMIC_RELEASE);
+#else
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every lane's write-through stores have been acknowledged
+  if ((threadIdx.x & 63) == 0) __hip_atomic_store(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#endif
+}
+// called by the whole (single) wave of the consumer; false = the flag never came (the caller flags the frame and ends)
+__device__ __forceinline__ bool tail_wait(const unsigned* flag) {
+  for (unsigned polls = 0;; ++polls) {
+    if ((unsigned)handoff_load_i32(flag) == 1u) break;
+    if (polls >= kTailPollMax) return false;
+#ifdef PLSVO_WAVE_EMU
+    wave_emu_yield_thread();
+#else
+    __builtin_amdgcn_s_sleep(8);
+#endif
+  }
+#ifndef PLSVO_WAVE_EMU
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+#endif
+  return true;
+}
+
 __device__ __forceinline__ Quat quat_normalized_fast(const Quat& a) {
   const double inv = fast_rcp(fast_sqrt(a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w));
   Quat r = { a.x * inv, a.y * inv, a.z * inv, a.w * inv };

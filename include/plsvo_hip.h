@@ -84,6 +84,14 @@ void plsvo_hip_destroy(plsvo_ctx* ctx);
  * of all and their finest level last of all, so that the launch does not end on whole long frames; 0 = one workgroup per frame
  * throughout.  Scheduling only -- every result is bit-identical.  The environment switch PLSVO_ALIGN_TAIL_SPLIT=0 sets the initial value to 0. */
 #define PLSVO_OPT_ALIGN_TAIL_SPLIT 6
+/* Row refill of the large-batch pose-optimiser launch (a 16-lane row per frame, more than two frames per resident row, no refinement
+ * loop -- every n_iter_ref <= 0 --, no iteration trace): 1 (default) = the launch runs as three kernels, and the rows of the middle one
+ * -- the Gauss-Newton loop, persistent -- take their next frame from a queue as soon as their frame stops; 0 = one kernel, the four
+ * frames of a wave iterate until the last of them stops.  Scheduling only -- every result is bit-identical.  The environment switch
+ * PLSVO_POSEOPT_REFILL=0 sets the initial value to 0; for tests and measurements PLSVO_POSEOPT_REFILL_MIN is the smallest batch (in
+ * frames) that takes the three kernels and PLSVO_POSEOPT_REFILL_WAVES the number of workgroups of the persistent one (read once, at
+ * plsvo_hip_create). */
+#define PLSVO_OPT_POSEOPT_REFILL 7
 int plsvo_hip_set_option(plsvo_ctx* ctx, int option, int value);
 const char* plsvo_hip_last_error(const plsvo_ctx* ctx);   /* ctx may be NULL: last create error */
 void* plsvo_hip_stream(plsvo_ctx* ctx);                   /* the hipStream_t all work is enqueued on */
@@ -384,6 +392,10 @@ const double* plsvo_poseopt_poses_dev(plsvo_ctx* ctx);
 int plsvo_poseopt_copy_poses(plsvo_ctx* ctx, double* d_dst);
 /* feature-iterations of the last run: points (24 B each) and lines (40 B each), SURVEY 8d */
 int plsvo_poseopt_work(plsvo_ctx* ctx, uint64_t* pt_iters, uint64_t* seg_iters);
+/* How many frames the LAST pose-optimiser launch of the context -- plsvo_poseopt_run, or the pose stage of plsvo_chain_run -- ran
+   through the row-refill path (PLSVO_OPT_POSEOPT_REFILL): the whole batch, or 0 when it ran as one kernel (the chain's always does:
+   its jobs are written on the device).  Tests and measurements. */
+int plsvo_poseopt_refill_frames(plsvo_ctx* ctx, int* refill_frames);
 
 /* ------------------------------------------------------------------------------------------ */
 /* structure optimisation (hot-path contract row (f) "next" #3)                                */

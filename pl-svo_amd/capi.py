@@ -24,7 +24,7 @@ SYMBOLS = [
     "plsvo_sparse_align", "plsvo_sparse_align_batch", "plsvo_align_stage", "plsvo_align_run", "plsvo_align_fetch",
     "plsvo_align_set_trace", "plsvo_align_fetch_trace", "plsvo_align_poses_dev", "plsvo_align_copy_poses", "plsvo_align_work", "plsvo_align_work_points", "plsvo_align_chi2_ties", "plsvo_align_launch_order", "plsvo_align_tail_frames",
     "plsvo_pose_optimize", "plsvo_pose_optimize_batch", "plsvo_poseopt_stage", "plsvo_poseopt_run", "plsvo_poseopt_fetch",
-    "plsvo_poseopt_set_trace", "plsvo_poseopt_fetch_trace", "plsvo_poseopt_poses_dev", "plsvo_poseopt_copy_poses", "plsvo_poseopt_work",
+    "plsvo_poseopt_set_trace", "plsvo_poseopt_fetch_trace", "plsvo_poseopt_poses_dev", "plsvo_poseopt_copy_poses", "plsvo_poseopt_work", "plsvo_poseopt_refill_frames",
     "plsvo_structure_optimize", "plsvo_match_direct", "plsvo_reproject", "plsvo_trajectory_record", "plsvo_update_seeds",
     "plsvo_chain_stage", "plsvo_chain_run", "plsvo_chain_fetch", "plsvo_frame_step_batch", "plsvo_chain_poses_dev",
     "plsvo_pack_pose_records", "plsvo_fetch_pose_records", "plsvo_gather_poses",
@@ -123,6 +123,7 @@ def lib():
         "plsvo_align_work_points": (C.c_int, [ctxp, C.POINTER(C.c_uint64)]),
         "plsvo_align_launch_order": (C.c_int, [ctxp, C.c_int, C.POINTER(C.c_int32)]),
         "plsvo_align_tail_frames": (C.c_int, [ctxp, C.POINTER(C.c_int)]),
+        "plsvo_poseopt_refill_frames": (C.c_int, [ctxp, C.POINTER(C.c_int)]),
         "plsvo_pose_optimize": (C.c_int, [ctxp, C.POINTER(abi.PoseOptIn), C.POINTER(abi.PoseOptOut)]),
         "plsvo_pose_optimize_batch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.PoseOptIn), C.POINTER(abi.PoseOptOut)]),
         "plsvo_poseopt_stage": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.PoseOptIn)]),
@@ -204,6 +205,12 @@ class Context:
         """large-batch alignment launch: True (default) = the frames that start last run as a coarse and a fine workgroup of the same launch,
         False = one workgroup per frame throughout (PLSVO_OPT_ALIGN_TAIL_SPLIT); scheduling only, results bit-identical"""
         self._chk(self.L.plsvo_hip_set_option(self.h, 6, 1 if on else 0))
+
+    def set_poseopt_refill(self, on):
+        """large-batch pose optimiser (row shape): True (default) = three launches, the rows of the Gauss-Newton kernel take their next
+        frame from a queue, False = one launch, the four frames of a wave in lock step (PLSVO_OPT_POSEOPT_REFILL); scheduling only,
+        results bit-identical"""
+        self._chk(self.L.plsvo_hip_set_option(self.h, 7, 1 if on else 0))
 
     def close(self):
         if getattr(self, "h", None):
@@ -385,6 +392,12 @@ class Context:
         out = np.zeros(n, dtype=np.int32)
         self._chk(self.L.plsvo_align_launch_order(self.h, n, out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out
+
+    def poseopt_refill_frames(self):
+        """plsvo_poseopt_refill_frames: frames the last pose-optimiser launch ran through the row-refill path (0 = one launch)"""
+        n = C.c_int(0)
+        self._chk(self.L.plsvo_poseopt_refill_frames(self.h, C.byref(n)))
+        return n.value
 
     def align_tail_frames(self):
         """plsvo_align_tail_frames: frames of the last align_run that ran as a coarse and a fine workgroup (0 = launch not split)"""

@@ -18,6 +18,7 @@
 #include "../../include/plsvo_hip.h"
 #include "plsvo_dev.hpp"
 #include "plsvo_math.hpp"
+#include "poseopt_refill.hpp"
 
 namespace plsvo_hip {
 // kernels (align_kernels.hip, poseopt_kernels.hip, pyramid_kernels.hip)
@@ -153,6 +154,14 @@ struct plsvo_ctx {
   int p_order_next = 0, p_key_shift = 0;
   bool env_poseopt_no_reorder = false;
   int env_poseopt_reorder_min = 0;          //   PLSVO_POSEOPT_REORDER_MIN (tests)
+  // row refill of the row shape's Gauss-Newton loop (poseopt_kernels.hip: three launches): PLSVO_OPT_POSEOPT_REFILL, and for tests and
+  // measurements PLSVO_POSEOPT_REFILL_MIN (smallest batch that takes it, in frames; default: more than two frames per resident row) and
+  // PLSVO_POSEOPT_REFILL_WAVES (workgroups of the persistent kernel; default: the resident ones)
+  bool opt_poseopt_refill = true;
+  int env_poseopt_refill_min = 0, env_poseopt_refill_waves = 0;
+  bool p_any_ref = false;                   //   a job of the staged batch has a refinement loop (n_iter_ref > 0): pose_opt_rows_kernel
+  int p_refill_frames = 0;                  //   frames the last pose-optimiser launch ran through the three launches
+  DevBuf p_d_carry, p_d_refill_next;        //   PoseRefillCarry per job; the queue's counter
 
   // resident frame step (plsvo_chain_*): candidates, glue state, pose-optimiser input written on the device
   bool ch_staged = false;
@@ -287,6 +296,9 @@ static int create_ctx(int device_id, void* stream, bool use_given_stream, plsvo_
   if (const char* s = getenv("PLSVO_ALIGN_TAIL_FRAMES")) c->env_align_tail_frames = atoi(s);
   c->env_poseopt_no_reorder = env_flag("PLSVO_POSEOPT_NO_REORDER");
   if (const char* s = getenv("PLSVO_POSEOPT_REORDER_MIN")) c->env_poseopt_reorder_min = atoi(s);
+  if (const char* s = getenv("PLSVO_POSEOPT_REFILL")) c->opt_poseopt_refill = atoi(s) != 0;
+  if (const char* s = getenv("PLSVO_POSEOPT_REFILL_MIN")) c->env_poseopt_refill_min = atoi(s);
+  if (const char* s = getenv("PLSVO_POSEOPT_REFILL_WAVES")) c->env_poseopt_refill_waves = atoi(s);
   c->env_host_timing = getenv("PLSVO_HOST_TIMING") != nullptr;
   *out = c;
   return PLSVO_OK;
@@ -299,6 +311,7 @@ extern "C" void plsvo_hip_destroy(plsvo_ctx* c) {
   prof_collect(c);
   for (auto& ep : c->ev_pool) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
   c->a_d_tailflag.release(); c->a_d_alive_tail.release(); c->a_d_xbuf.release(); c->a_d_order[0].release(); c->a_d_order[1].release(); c->a_d_workkey.release(); c->p_d_workkey.release(); c->p_d_order[0].release(); c->p_d_order[1].release();
+  c->p_d_carry.release(); c->p_d_refill_next.release();
   DevBuf* bufs[] = { &c->pyr_slab, &c->pyr_tiled, &c->pyr_upload, &c->a_d_blob, &c->a_d_state, &c->a_d_alive, &c->a_d_pxyz, &c->a_d_puv, &c->a_d_cref,
                      &c->a_d_chi, &c->a_d_log, &c->a_d_poses, &c->p_d_blob, &c->p_d_state, &c->p_d_ptkeep, &c->p_d_segkeep, &c->p_d_s32, &c->p_d_s64,
                      &c->p_d_log, &c->p_d_poses, &c->s_d_in, &c->s_d_out, &c->ch_d_blob, &c->ch_d_work, &c->ch_d_po, &c->ch_d_state,
@@ -344,6 +357,11 @@ extern "C" int plsvo_hip_set_option(plsvo_ctx* c, int option, int value) {
   if (option == PLSVO_OPT_ALIGN_TAIL_SPLIT) {
     if (value != 0 && value != 1) return fail(c, PLSVO_E_INVALID, "set_option: the alignment's tail split is 0 (one workgroup per frame throughout) or 1 (the frames that start last run as a coarse and a fine part)");
     c->opt_align_tail_split = value != 0;
+    return PLSVO_OK;
+  }
+  if (option == PLSVO_OPT_POSEOPT_REFILL) {
+    if (value != 0 && value != 1) return fail(c, PLSVO_E_INVALID, "set_option: the pose optimiser's row refill is 0 (four frames of a wave in lock step) or 1 (rows take their next frame from a queue)");
+    c->opt_poseopt_refill = value != 0;
     return PLSVO_OK;
   }
   return fail(c, PLSVO_E_INVALID, "set_option: unknown option");
@@ -1504,6 +1522,8 @@ extern "C" int plsvo_poseopt_stage(plsvo_ctx* c, int n, const plsvo_poseopt_in* 
     c->p_key_shift = 0;
     while ((key_max >> c->p_key_shift) > 1023) ++c->p_key_shift;
   }
+  c->p_any_ref = false;
+  for (int j = 0; j < n; ++j) c->p_any_ref = c->p_any_ref || jobs[j].n_iter_ref > 0;
   c->p_jobs.swap(jobs);
   c->p_n = n; c->p_total_pt = (int)npt; c->p_total_seg = (int)nsg;
   c->p_staged = true; c->p_run_seq = 0;
@@ -1537,8 +1557,30 @@ extern "C" int plsvo_poseopt_run(plsvo_ctx* c) {
     }
     c->p_b.work_key = c->p_d_workkey.as<int>();
   } else c->p_b.order = nullptr;
+  // ROW REFILL: the four frames of a row-shape wave iterate until the last of them stops, and iteration counts are bimodal -- in the
+  // stage order almost every wave runs all ten.  With more than two frames per resident row the launch is cut at the Gauss-Newton
+  // loop's borders and the rows of a persistent kernel take their next frame from a queue (poseopt_kernels.hip).  Scheduling only: every
+  // result is bit-identical.  At two frames per row the launch still ends on a ten-iteration frame that started second.  The crossover,
+  // measured on MI355X (8192 resident rows, 200 + 80 features, one launch -> three; profiles/poseopt_refill_ab.md): 16384 frames 0.890 ->
+  // 0.887 ms, 24576 frames 1.325 -> 1.271, 32768 frames 1.751 -> 1.575, 65536 frames 3.385 -> 2.914; 550 features x 16384 frames 1.684 -> 1.712.
+  // A batch with a refinement loop or an iteration trace keeps pose_opt_rows_kernel.
+  const int resident_wgs = cus * 512 / 64;
+  const int refill_min = c->env_poseopt_refill_min > 0 ? c->env_poseopt_refill_min : 2 * 4 * resident_wgs + 1;
+  const bool refill = c->opt_poseopt_refill && threads == 16 && !c->p_b.log && !c->p_any_ref && pose_opt_refill_built() && c->p_n >= refill_min;
+  c->p_refill_frames = 0;
   EventPair ep{}; prof_begin(c, PLSVO_K_POSEOPT, &ep);
-  HIP_TRY(c, launch_pose_opt(c->p_b, c->p_d_poses.as<double>(), threads, c->stream));
+  if (refill) {
+    const int wgs = (c->p_n + 3) / 4;
+    const int gn_grid = std::max(1, std::min(wgs, c->env_poseopt_refill_waves > 0 ? c->env_poseopt_refill_waves : resident_wgs));
+    HIP_TRY(c, c->p_d_carry.ensure((size_t)c->p_n * sizeof(PoseRefillCarry)));
+    HIP_TRY(c, c->p_d_refill_next.ensure(16));
+    HIP_TRY(c, hipMemsetAsync(c->p_d_refill_next.p, 0, 16, c->stream));   // the queue is re-armed ahead of every launch
+    const PoseRefillDev q{ c->p_d_carry.as<PoseRefillCarry>(), c->p_d_refill_next.as<int>() };
+    HIP_TRY(c, launch_pose_opt_refill(c->p_b, q, c->p_d_poses.as<double>(), gn_grid, c->stream));
+    c->p_refill_frames = c->p_n;
+  } else {
+    HIP_TRY(c, launch_pose_opt(c->p_b, c->p_d_poses.as<double>(), threads, c->stream));
+  }
   c->p_run_seq = ++c->run_seq;
   prof_end(c, PLSVO_K_POSEOPT, &ep);
   if (reorder) {
@@ -1578,6 +1620,13 @@ extern "C" int plsvo_poseopt_fetch(plsvo_ctx* c, int n, plsvo_poseopt_out* out) 
     if (pko && J.n_pts > 0) memcpy(pko, pk + J.pt_off, (size_t)J.n_pts);
     if (sko && J.n_seg > 0) memcpy(sko, sk + J.seg_off, (size_t)J.n_seg);
   }
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_poseopt_refill_frames(plsvo_ctx* c, int* refill_frames) {
+  CTX_CHECK(c);
+  if (!refill_frames) return fail(c, PLSVO_E_INVALID, "poseopt_refill_frames: NULL output");
+  *refill_frames = c->p_refill_frames;
   return PLSVO_OK;
 }
 
@@ -1972,6 +2021,7 @@ extern "C" int plsvo_chain_run(plsvo_ctx* c) {
   const int cus = c->cu_count > 0 ? c->cu_count : 256;
   int threads = c->ch_n <= 2 * cus ? 256 : ((long)c->ch_b.n_cand <= 580l * c->ch_n ? 16 : 64);   // (selected features <= candidates; see plsvo_poseopt_run)
   if (c->env_poseopt_threads) threads = c->env_poseopt_threads;
+  c->p_refill_frames = 0;   // (the chain's jobs are written on the device: the host cannot see whether one has a refinement loop -- pose_opt_rows_kernel)
   EventPair ep{}; prof_begin(c, PLSVO_K_POSEOPT, &ep);
   HIP_TRY(c, launch_pose_opt(c->ch_pose, c->ch_d_poses.as<double>(), threads, c->stream));
   prof_end(c, PLSVO_K_POSEOPT, &ep);

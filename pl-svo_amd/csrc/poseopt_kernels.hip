@@ -20,6 +20,7 @@
 #include "plsvo_dev.hpp"
 #include "plsvo_math.hpp"
 #include "plsvo_wave.hpp"
+#include "poseopt_refill.hpp"
 
 // Waves per SIMD.  The wave-per-frame shape (64 threads) is capped at 168 VGPRs = THREE waves per SIMD: its feature loops stay spill-free
 // (the 58 spilled registers are touched ~20 times per Gauss-Newton iteration, around the solve) and the f64 division chains of a third
@@ -832,6 +833,271 @@ __global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_opt_rows_kernel(Pos
     st->pt_iters = (unsigned long long)(L.pose[27] + 0.5); st->seg_iters = (unsigned long long)(L.pose[28] + 0.5);
     if (b.work_key) b.work_key[job_id] = (int)fmin(L.pose[27] + L.pose[28] + 0.5, 2147483647.0);
   }
+}
+
+// ================================================================================================================================
+// The row shape as THREE launches: rows of the Gauss-Newton loop are refilled from a queue of frames.
+//
+// The four frames of a pose_opt_rows_kernel wave iterate until the LAST of them stops, and iteration counts are bimodal (4-6, or all
+// ten): in an arbitrary launch order almost every wave runs ten.  Rows share a program counter, so a row cannot start its next frame's
+// scale pass while its neighbours iterate -- the kernel is therefore cut at the loop's borders:
+//   * pose_refill_prologue_kernel: everything up to the two MAD scales, four frames per wave in lock step (uniform work);
+//   * pose_refill_gn_kernel: persistent.  A row without a running frame takes the next launch slot from one device counter, loads that
+//     frame's carry (PoseRefillCarry) into its PoseRowLds and joins the loop at ITS iteration 0; when the frame stops the row writes the
+//     carry back.  A row either gets a slot or is done: nothing polls, nothing waits for another workgroup;
+//   * pose_refill_epilogue_kernel: covariance, cull, medians and the final writes, four frames per wave in lock step.
+// Per frame the arithmetic, the sums and their order are pose_opt_rows_kernel's: every output is bit-identical.  Batches with a
+// refinement loop (n_iter_ref > 0), an iteration trace or a -DPLSVO_TIMING build keep pose_opt_rows_kernel (plsvo_capi.hip decides).
+// ================================================================================================================================
+// quat_to_matrix (plsvo_math.hpp) with its contractions WRITTEN OUT.  Every entry of R is a sum of two products, and which of the two
+// hipcc fuses into the fma depends on the code around the call (the use counts of the products when the sum is visited): inside
+// pose_opt_rows_kernel it is the first one in all three places, inside a kernel that holds the Gauss-Newton loop alone it came out
+// as the second for five of the nine entries -- R a last bit off, and with it every later iteration.  The refill kernels must match
+// pose_opt_rows_kernel bit for bit (tests/test_gpu_poseopt_refill.py holds the two together), so they do not leave the choice open.
+#ifdef PLSVO_WAVE_EMU   // (the host emulation build contracts nothing anywhere)
+__device__ __forceinline__ void quat_to_matrix_rows(const Quat& q, double* R) { quat_to_matrix(q, R); }
+#else
+__device__ __forceinline__ void quat_to_matrix_rows(const Quat& q, double* R) {
+#pragma clang fp contract(off)
+  const double tx = 2.0 * q.x, ty = 2.0 * q.y, tz = 2.0 * q.z;
+  const double twx = tx * q.w, twy = ty * q.w, twz = tz * q.w;
+  const double tyy = ty * q.y, tzz = tz * q.z;
+  R[0] = 1.0 - fma(q.y, ty, tzz); R[1] = fma(q.x, ty, -twz);      R[2] = fma(q.x, tz, twy);
+  R[3] = fma(q.x, ty, twz);       R[4] = 1.0 - fma(q.x, tx, tzz); R[5] = fma(q.y, tz, -twx);
+  R[6] = fma(q.x, tz, -twy);      R[7] = fma(q.y, tz, twx);       R[8] = 1.0 - fma(q.x, tx, tyy);
+}
+#endif
+
+__global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_refill_prologue_kernel(PoseBatchDev b, PoseRefillDev q, double* poses) {
+  __shared__ __align__(16) PoseRowLds s_rows[4];
+  const int lane = threadIdx.x & 63, row = lane >> 4, rl = lane & 15;
+  const int job_raw = blockIdx.x * 4 + row;
+  const bool row_valid = job_raw < b.n_jobs;
+  const int job_id = row_valid ? job_raw : b.n_jobs - 1;   // (index order: the work of a frame is uniform here)
+  const PoseJobDev job = b.jobs[job_id];
+  PoseStateDev* st = b.state + job_id;
+  PoseRowLds& L = s_rows[row];
+  const int np = job.n_pts, ns = job.n_seg, nf = np + ns;
+  const size_t fbase = (size_t)job.pt_off + (size_t)job.seg_off;   // scratch layout: see pose_opt_rows_kernel
+  float* errs = b.scratch_f32 + fbase;
+  double* vec = b.scratch_f64 + 5 * fbase;
+
+  if (row_valid && rl == 0) {
+    SE3d m = se3_load(job.T0);
+    se3_store(m, L.pose + 12); se3_store(m, L.pose + 19); L.pose[26] = 0.0; L.pose[27] = 0.0; L.pose[28] = 0.0;
+    L.pose[29] = 0.0; L.pose[30] = 0.0; L.pose[31] = 0.0;
+    quat_to_matrix_rows(m.q, L.pose); L.pose[9] = m.t[0]; L.pose[10] = m.t[1]; L.pose[11] = m.t[2];
+    st->log_count = 0; st->status = 0; st->iters = 0; st->iters_ref = 0; st->pt_iters = 0; st->seg_iters = 0;
+    st->num_obs_pt = 0; st->num_obs_ls = 0; st->estimated_scale = 0; st->error_init = 0; st->error_final = 0;
+    for (int k = 0; k < 36; ++k) st->cov[k] = 0.0;
+    for (int k = 0; k < 7; ++k) st->T[k] = job.T0[k];
+    for (int k = 0; k < 8; ++k) st->phase_ticks[k] = 0;
+    if (nf == 0) { st->status = 1; if (poses) for (int k = 0; k < 7; ++k) poses[7 * job_id + k] = job.T0[k]; }   // errors.empty() :88-89
+    if (b.work_key) b.work_key[job_id] = 0;
+  }
+  const bool row_on = row_valid && nf > 0;
+  if (row_on) {
+    for (int i = rl; i < np; i += 16) b.pt_keep[job.pt_off + i] = 1;
+    for (int s = rl; s < ns; s += 16) b.seg_keep[job.seg_off + s] = 1;
+  }
+  wave_lds_fence();
+
+  // ---- scale pass :57-95 ----
+  if (row_on) {
+    double P[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) P[k] = L.pose[k];
+    for (int f = rl; f < nf; f += 16) errs[f] = popt_scale_error(b, job, f, P, vec + 3 * nf);
+  }
+  wave_lds_fence();
+  double scale_pt = 1.0, scale_ls = 1.0;
+  {
+    const uint32_t m_pt = row_radix_select<32, uint32_t>([&](int i) { return (uint32_t)__float_as_uint(errs[i]); }, np, np / 2, row_on && np > 0, L.hist, L.sel);
+    const uint32_t m_ls = row_radix_select<32, uint32_t>([&](int i) { return (uint32_t)__float_as_uint(errs[np + i]); }, ns, ns / 2, row_on && ns > 0, L.hist, L.sel);
+    if (np > 0) scale_pt = (double)__fmul_rn(1.48f, __uint_as_float(m_pt));
+    if (ns > 0) scale_ls = (double)__fmul_rn(1.48f, __uint_as_float(m_ls));
+  }
+  if (row_on && job.n_iter <= 0) for (int f = rl; f < nf; f += 16) vec[f] = __longlong_as_double(0x7ff0000000000000LL);
+
+  if (row_valid) {
+    PoseRefillCarry& c = q.carry[job_id];
+    *reinterpret_cast<double2*>(c.pose + 2 * rl) = *reinterpret_cast<const double2*>(L.pose + 2 * rl);
+    *reinterpret_cast<double2*>(c.tot + 2 * rl) = make_double2(0.0, 0.0);
+    if (rl == 0) { c.scale_pt = scale_pt; c.scale_ls = scale_ls; c.iters = 0; }
+  }
+}
+
+__global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_refill_gn_kernel(PoseBatchDev b, PoseRefillDev q) {
+  __shared__ __align__(16) PoseRowLds s_rows[4];
+  const int lane = threadIdx.x & 63, row = lane >> 4, rl = lane & 15;
+  PoseRowLds& L = s_rows[row];
+  // per row, in plain lane registers: the frame, its iteration index, what of its job the feature pass reads
+  PoseJobDev job;
+  job.n_pts = 0; job.n_seg = 0; job.pt_off = 0; job.seg_off = 0; job.n_iter = 0; job.ldlt_flavour = 320;
+  int job_id = 0, nf = 0, iter = 0;
+  double scale_pt = 1.0, scale_ls = 1.0;
+  double* vec = b.scratch_f64;
+  bool running = false, want = true;
+  for (;;) {
+    // ---- refill: a row without a frame takes the next launch slot; frames without iterations to run are passed over ----
+    while (__any(want)) {
+      if (want && rl == 0) L.sel[6] = atomicAdd(q.next, 1);
+      wave_lds_fence();
+      if (want) {
+        const int slot = L.sel[6];
+        if (slot >= b.n_jobs) {
+          want = false;
+        } else {
+          job_id = b.order ? b.order[slot] : slot;
+          const PoseJobDev* J = b.jobs + job_id;
+          job.n_pts = J->n_pts; job.n_seg = J->n_seg; job.pt_off = J->pt_off; job.seg_off = J->seg_off; job.n_iter = J->n_iter; job.ldlt_flavour = J->ldlt_flavour;
+          nf = job.n_pts + job.n_seg;
+          if (nf > 0 && job.n_iter > 0) {
+            const PoseRefillCarry& c = q.carry[job_id];
+            *reinterpret_cast<double2*>(L.pose + 2 * rl) = *reinterpret_cast<const double2*>(c.pose + 2 * rl);
+            if (rl == 0) { L.ctl[0] = 0; L.ctl[1] = 0; }
+            scale_pt = c.scale_pt; scale_ls = c.scale_ls;
+            vec = b.scratch_f64 + 5 * ((size_t)job.pt_off + (size_t)job.seg_off);
+            iter = 0; running = true; want = false;
+          }
+        }
+      }
+      wave_lds_fence();
+    }
+    if (!__any(running)) break;
+
+    // ---- one Gauss-Newton iteration of every running row (rows_gn_loop's body with the iteration index per row) ----
+    double acc[32];
+#pragma unroll
+    for (int k = 0; k < 32; ++k) acc[k] = 0.0;
+    if (running) {
+      double P[12];
+#pragma unroll
+      for (int k = 0; k < 12; ++k) P[k] = L.pose[k];
+      for (int f = rl; f < nf; f += 16) popt_accumulate_feature(b, job, f, P, scale_pt, scale_ls, iter == 0, vec, vec + 3 * nf, acc);
+    }
+    double out2[2];
+    row_reduce_scatter32(acc, out2);
+    if (running) *reinterpret_cast<double2*>(L.tot + row_reduce_scatter32_index(lane)) = make_double2(out2[0], out2[1]);
+    wave_lds_fence();
+    if (running && rl == 0) {
+      double dT[6];
+      lane_solve6(L.tot, L.x, dT, job.ldlt_flavour);                          // A.ldlt().solve(b) :170
+      const double new_chi2 = L.tot[27];
+      L.pose[27] += L.tot[28]; L.pose[28] += L.tot[29];
+      L.ctl[1] += 1;
+      SE3d model = se3_load(L.pose + 12);
+      int brk = 0;
+      if ((iter > 0 && new_chi2 > L.pose[26]) || isnan(dT[0])) {              // :173-180
+        model = se3_load(L.pose + 19); brk = 1;
+      } else {
+        const SE3d Tn = se3_mul_dev(se3_exp_dev(dT), model);                   // :183 left update
+        se3_store(model, L.pose + 19);
+        model = Tn; L.pose[26] = new_chi2;
+        if (norm_max6(dT) <= 0.0000000001) brk = 1;                            // EPS, global.h:99
+      }
+      if (iter + 1 >= job.n_iter) brk = 1;
+      se3_store(model, L.pose + 12);
+      quat_to_matrix_rows(model.q, L.pose); L.pose[9] = model.t[0]; L.pose[10] = model.t[1]; L.pose[11] = model.t[2];
+      L.ctl[0] = brk;
+    }
+    wave_lds_fence();
+    if (running) {
+      ++iter;
+      if (L.ctl[0]) {   // the frame has stopped: its carry goes back, the row is free
+        PoseRefillCarry& c = q.carry[job_id];
+        *reinterpret_cast<double2*>(c.pose + 2 * rl) = *reinterpret_cast<const double2*>(L.pose + 2 * rl);
+        *reinterpret_cast<double2*>(c.tot + 2 * rl) = *reinterpret_cast<const double2*>(L.tot + 2 * rl);
+        if (rl == 0) c.iters = L.ctl[1];
+        running = false; want = true;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_refill_epilogue_kernel(PoseBatchDev b, PoseRefillDev q, double* poses) {
+  __shared__ __align__(16) PoseRowLds s_rows[4];
+  const int lane = threadIdx.x & 63, row = lane >> 4, rl = lane & 15;
+  const int job_raw = blockIdx.x * 4 + row;
+  const bool row_valid = job_raw < b.n_jobs;
+  const int job_id = row_valid ? job_raw : b.n_jobs - 1;
+  const PoseJobDev job = b.jobs[job_id];
+  PoseStateDev* st = b.state + job_id;
+  PoseRowLds& L = s_rows[row];
+  const int np = job.n_pts, ns = job.n_seg, nf = np + ns;
+  const size_t fbase = (size_t)job.pt_off + (size_t)job.seg_off;
+  double* vec = b.scratch_f64 + 5 * fbase;
+  const bool row_on = row_valid && nf > 0;
+  const PoseRefillCarry& c = q.carry[job_id];
+  *reinterpret_cast<double2*>(L.pose + 2 * rl) = *reinterpret_cast<const double2*>(c.pose + 2 * rl);
+  *reinterpret_cast<double2*>(L.tot + 2 * rl) = *reinterpret_cast<const double2*>(c.tot + 2 * rl);
+  const double scale_pt = c.scale_pt, scale_ls = c.scale_ls;
+  const int iters = c.iters;
+  wave_lds_fence();
+
+  // ---- covariance :197-199 (from the last assembled A, even if that iteration was rolled back) ----
+  if (row_on) {
+    const double f2 = job.fx * job.fx;
+    for (int t = rl; t < 36; t += 16) L.lu[t] = L.tot[sym6_index(t / 6, t % 6)] * f2;
+  }
+  wave_lds_fence();
+  if (row_on && rl == 0) lu6_lds(L.lu, L.perm);
+  wave_lds_fence();
+  if (row_on && rl < 6) inv6_column_lds(L.lu, L.perm, rl, st->cov);
+
+  // ---- cull :201-242 ----
+  const double thr_pt = job.reproj_thresh / job.fx;
+  const double thr_ls = thr_pt * scale_ls / scale_pt;
+  int del_pt = 0, del_ls = 0;
+  if (row_on) {
+    double P[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) P[k] = L.pose[k];
+    for (int f = rl; f < nf; f += 16) {
+      int deleted;
+      vec[2 * nf + f] = popt_cull_feature(b, job, f, P, thr_pt, thr_ls, vec + 3 * nf, deleted);
+      del_pt += deleted == 1; del_ls += deleted == 2;
+      vec[nf + f] = __longlong_as_double(0x7ff0000000000000LL);  // (the refinement's init entries: no batch with a refinement loop comes here)
+    }
+  }
+  const int n_del_pt = row_sum_i32(del_pt), n_del_ls = row_sum_i32(del_ls);
+  wave_lds_fence();   // keep flags and vec visible to the row
+
+  // ---- medians :244-249 ----
+  const int n_init = job.n_iter > 0 ? nf : 0;
+  const unsigned long long mi = row_radix_select<64, unsigned long long>([&](int i) { return (unsigned long long)__double_as_longlong(vec[i]); },
+                                                                         nf, n_init / 2, row_on && n_init > 0, L.hist, L.sel);
+  const unsigned long long mf = row_radix_select<64, unsigned long long>([&](int i) { return (unsigned long long)__double_as_longlong(vec[2 * nf + i]); },
+                                                                         nf, nf / 2, row_on, L.hist, L.sel);
+  if (row_on && rl == 0) {
+    for (int k = 0; k < 7; ++k) st->T[k] = L.pose[12 + k];
+    if (poses) for (int k = 0; k < 7; ++k) poses[7 * job_id + k] = L.pose[12 + k];
+    st->error_init = n_init > 0 ? sqrt(__longlong_as_double((long long)mi)) * job.fx : 0.0;
+    st->error_final = sqrt(__longlong_as_double((long long)mf)) * job.fx;
+    st->estimated_scale = scale_pt * job.fx;
+    st->num_obs_pt = (unsigned long long)(np - n_del_pt);
+    st->num_obs_ls = (unsigned long long)(ns - n_del_ls);
+    st->iters = iters; st->iters_ref = 0;
+    st->pt_iters = (unsigned long long)(L.pose[27] + 0.5); st->seg_iters = (unsigned long long)(L.pose[28] + 0.5);
+    if (b.work_key) b.work_key[job_id] = (int)fmin(L.pose[27] + L.pose[28] + 0.5, 2147483647.0);
+  }
+}
+
+bool pose_opt_refill_built() {
+#ifdef PLSVO_TIMING
+  return false;
+#else
+  return true;
+#endif
+}
+
+hipError_t launch_pose_opt_refill(const PoseBatchDev& b, const PoseRefillDev& q, double* d_poses, int gn_grid, hipStream_t stream) {
+  const int wgs = (b.n_jobs + 3) / 4;
+  if (gn_grid < 1 || gn_grid > wgs) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(pose_refill_prologue_kernel, dim3(wgs), dim3(64), 0, stream, b, q, d_poses);
+  hipLaunchKernelGGL(pose_refill_gn_kernel, dim3(gn_grid), dim3(64), 0, stream, b, q);
+  hipLaunchKernelGGL(pose_refill_epilogue_kernel, dim3(wgs), dim3(64), 0, stream, b, q, d_poses);
+  return hipGetLastError();
 }
 
 hipError_t launch_pose_opt(const PoseBatchDev& b, double* d_poses, int threads, hipStream_t stream) {

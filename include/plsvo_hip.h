@@ -498,6 +498,20 @@ typedef struct plsvo_match_out {    /* caller buffers; any of them may be NULL *
 
 int plsvo_match_direct(plsvo_ctx* ctx, const plsvo_match_in* in, plsvo_match_out* out);
 
+/* Diagnostic view of the matcher's affine warp (tests; like plsvo_hip_detect_stages for the detector): the production kernel of
+ * plsvo_match_direct, instantiated to stop after warp::warpAffine and to write what it holds at that point.  Same inputs, same
+ * argument checks (px_cur and align_max_iter are checked, not used). */
+typedef struct plsvo_match_warp_out { /* caller buffers; any of them may be NULL */
+  double* A;                        /* 4*n    warp::getWarpMatrixAffine's A_cur_ref, row-major {a00, a01, a10, a11}; 0 when rejected */
+  int32_t* search_level;            /* n      warp::getBestSearchLevel (-1 when rejected by the border check before the warp) */
+  uint8_t* warped;                  /* n      1 when warpAffine wrote the patch (0: rejected, or the inverse of A is NaN) */
+  uint8_t* patch;                   /* 100*n  patch_with_border_, rows 0..9 x columns 0..9; all 0 when not warped */
+  uint8_t* staged;                  /* n      bit g set: patch rows 2g, 2g+1 took their taps from the window staged in LDS
+                                              (pl-svo_amd/csrc/match_device.hpp::warp_affine_lds); other groups read the image */
+} plsvo_match_warp_out;
+
+int plsvo_match_warp_patches(plsvo_ctx* ctx, const plsvo_match_in* in, plsvo_match_warp_out* out);
+
 /* Reprojector::reproject(frame, Point*) / (frame, LineSeg*) (src/reprojector.cpp:389-423): the projection of map
  * landmarks into a frame that produces the candidates (and their initial px_cur) for plsvo_match_direct.
  *   px[i]   = frame->w2c(pos[i]) = world2cam(T_f_w * pos[i])                      (include/plsvo/frame.h:113)

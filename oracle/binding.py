@@ -54,6 +54,8 @@ def lib():
         L.plsvo_oracle_structure_optimize.argtypes = [C.POINTER(abi.StructOptIn), C.POINTER(abi.StructOptOut)]
         L.plsvo_oracle_match_direct.restype = C.c_int
         L.plsvo_oracle_match_direct.argtypes = [C.POINTER(abi.MatchIn), C.POINTER(OraclePyr), C.POINTER(abi.MatchOut)]
+        L.plsvo_oracle_match_warp_patches.restype = C.c_int
+        L.plsvo_oracle_match_warp_patches.argtypes = [C.POINTER(abi.MatchIn), C.POINTER(OraclePyr), C.POINTER(abi.MatchWarpOut)]
         L.plsvo_oracle_reproject.restype = C.c_int
         L.plsvo_oracle_reproject.argtypes = [C.POINTER(abi.ReprojectIn), C.POINTER(abi.ReprojectOut)]
         L.plsvo_oracle_trajectory_record.restype = C.c_int
@@ -178,6 +180,21 @@ def match_direct(job, frame_levels):
     rc = lib().plsvo_oracle_match_direct(C.byref(job.c), pyrs, C.byref(out))
     if rc != 0:
         raise RuntimeError(f"oracle match_direct failed rc={rc}")
+    return job.trim(bufs)
+
+
+def match_warp_patches(job, frame_levels):
+    """the oracle's side of plsvo_match_warp_patches: dict of A, search_level, warped, patch (no `staged`: that is the device's own)"""
+    pyrs = (OraclePyr * len(frame_levels))()
+    keep = []
+    for k, levels in enumerate(frame_levels):
+        p, kk = make_pyr(levels)
+        pyrs[k] = p
+        keep.append(kk)
+    out, bufs = job.make_warp_out(("A", "search_level", "warped", "patch"))
+    rc = lib().plsvo_oracle_match_warp_patches(C.byref(job.c), pyrs, C.byref(out))
+    if rc != 0:
+        raise RuntimeError(f"oracle match_warp_patches failed rc={rc}")
     return job.trim(bufs)
 
 

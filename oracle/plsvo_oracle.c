@@ -1214,53 +1214,82 @@ static int align_1d(const uint8_t* cur_img, int cols, int rows, int cur_step, co
   return converged;
 }
 
+/* Matcher::findMatchDirect up to and including warp::warpAffine for candidate i (matcher.cpp:165-184): the border check of the
+ * reference observation, A_cur_ref, the search level and patch_with_border_.  Returns -1 when the observation is rejected by the
+ * border check (A and *search_level are not written), 0 when the inverse of A is NaN (no patch), 1 when the patch was written.
+ * Shared by plsvo_oracle_match_direct and plsvo_oracle_match_warp_patches. */
+static int match_warp_candidate(const plsvo_match_in* in, const plsvo_oracle_pyr* frames, int i, double A[4], int* search_level,
+                                uint8_t patch_with_border[M_STEP * M_STEP]) {
+  const int halfpatch_size_ = 4;
+  const int rf = in->ref_frame[i], cf = in->cur_frame[i], level = in->ref_level[i];
+  const double* rpx = in->ref_px + 2 * i;
+  /* :168-170  px.cast<int>() / (1<<level): truncation, then integer division */
+  if (!cam_is_in_frame(&in->cam, (int)rpx[0] / (1 << level), (int)rpx[1] / (1 << level), halfpatch_size_ + 2, level)) return -1;
+  const se3_t T_ref = se3_load(in->frame_T + 7 * rf), T_cur = se3_load(in->frame_T + 7 * cf);
+  const se3_t T_ref_inv = se3_inv(&T_ref);
+  const se3_t T_cur_ref = se3_mul(&T_cur, &T_ref_inv);
+  /* Frame::pos() = T_f_w_.inverse().translation() (frame.h:106); depth = |pos_ref - pos| */
+  const double d[3] = { T_ref_inv.t[0] - in->pos[3 * i], T_ref_inv.t[1] - in->pos[3 * i + 1], T_ref_inv.t[2] - in->pos[3 * i + 2] };
+  const double depth_ref = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+  warp_matrix_affine(&in->cam, rpx, in->ref_f + 3 * i, depth_ref, &T_cur_ref, level, A);
+  *search_level = best_search_level(A, in->n_pyr_levels - 1);
+  const plsvo_oracle_pyr* rp = &frames[rf];
+  return warp_affine(A, rp->img[level], rp->width[level], rp->height[level], rp->stride[level], rpx, level, *search_level,
+                     halfpatch_size_ + 1, patch_with_border) ? 1 : 0;
+}
+
 /* Matcher::findMatchDirect for one candidate: a point (matcher.cpp:159-207) or one end point of a line
  * segment (:209-230 + :253-274).  The closest-view observation has been chosen by the caller (:165, :239). */
 int plsvo_oracle_match_direct(const plsvo_match_in* in, const plsvo_oracle_pyr* frames, plsvo_match_out* out) {
   if (!in || !out || in->n < 0 || in->n_frames <= 0 || !frames) return PLSVO_E_INVALID;
-  const int halfpatch_size_ = 4;
   for (int i = 0; i < in->n; ++i) {
-    const int rf = in->ref_frame[i], cf = in->cur_frame[i], level = in->ref_level[i];
+    const int cf = in->cur_frame[i];
     double px_cur[2] = { in->px_cur[2 * i], in->px_cur[2 * i + 1] };
     int found = 0, search_level = -1, iters = 0;
-    const double* rpx = in->ref_px + 2 * i;
-    /* :168-170  px.cast<int>() / (1<<level): truncation, then integer division */
-    if (cam_is_in_frame(&in->cam, (int)rpx[0] / (1 << level), (int)rpx[1] / (1 << level), halfpatch_size_ + 2, level)) {
-      const se3_t T_ref = se3_load(in->frame_T + 7 * rf), T_cur = se3_load(in->frame_T + 7 * cf);
-      const se3_t T_ref_inv = se3_inv(&T_ref);
-      const se3_t T_cur_ref = se3_mul(&T_cur, &T_ref_inv);
-      /* Frame::pos() = T_f_w_.inverse().translation() (frame.h:106); depth = |pos_ref - pos| */
-      const double d[3] = { T_ref_inv.t[0] - in->pos[3 * i], T_ref_inv.t[1] - in->pos[3 * i + 1], T_ref_inv.t[2] - in->pos[3 * i + 2] };
-      const double depth_ref = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-      double A[4];
-      warp_matrix_affine(&in->cam, rpx, in->ref_f + 3 * i, depth_ref, &T_cur_ref, level, A);
-      search_level = best_search_level(A, in->n_pyr_levels - 1);
-      uint8_t patch_with_border[M_STEP * M_STEP], patch[M_AREA];
-      const plsvo_oracle_pyr* rp = &frames[rf];
+    double A[4];
+    uint8_t patch_with_border[M_STEP * M_STEP], patch[M_AREA];
+    if (match_warp_candidate(in, frames, i, A, &search_level, patch_with_border) == 1) {
       const plsvo_oracle_pyr* cp = &frames[cf];
-      if (warp_affine(A, rp->img[level], rp->width[level], rp->height[level], rp->stride[level], rpx, level, search_level,
-                      halfpatch_size_ + 1, patch_with_border)) {
-        for (int y = 1; y < M_PATCH + 1; ++y)          /* createPatchFromPatchWithBorder :148-157 */
-          for (int x = 0; x < M_PATCH; ++x) patch[(y - 1) * M_PATCH + x] = patch_with_border[y * M_STEP + 1 + x];
-        double px_scaled[2] = { px_cur[0] / (1 << search_level), px_cur[1] / (1 << search_level) };
-        if (in->ref_type[i] == PLSVO_FTR_EDGELET) {
-          double dc[2] = { A[0] * in->ref_grad[2 * i] + A[1] * in->ref_grad[2 * i + 1], A[2] * in->ref_grad[2 * i] + A[3] * in->ref_grad[2 * i + 1] };
-          const double nrm = sqrt(dc[0] * dc[0] + dc[1] * dc[1]);
-          dc[0] /= nrm; dc[1] /= nrm;
-          const float dir[2] = { (float)dc[0], (float)dc[1] };
-          found = align_1d(cp->img[search_level], cp->width[search_level], cp->height[search_level], cp->stride[search_level], dir,
-                           patch_with_border, patch, in->align_max_iter, px_scaled, &iters);
-        } else {
-          found = align_2d(cp->img[search_level], cp->width[search_level], cp->height[search_level], cp->stride[search_level],
-                           patch_with_border, patch, in->align_max_iter, px_scaled, &iters);
-        }
-        px_cur[0] = px_scaled[0] * (1 << search_level); px_cur[1] = px_scaled[1] * (1 << search_level);
+      for (int y = 1; y < M_PATCH + 1; ++y)          /* createPatchFromPatchWithBorder :148-157 */
+        for (int x = 0; x < M_PATCH; ++x) patch[(y - 1) * M_PATCH + x] = patch_with_border[y * M_STEP + 1 + x];
+      double px_scaled[2] = { px_cur[0] / (1 << search_level), px_cur[1] / (1 << search_level) };
+      if (in->ref_type[i] == PLSVO_FTR_EDGELET) {
+        double dc[2] = { A[0] * in->ref_grad[2 * i] + A[1] * in->ref_grad[2 * i + 1], A[2] * in->ref_grad[2 * i] + A[3] * in->ref_grad[2 * i + 1] };
+        const double nrm = sqrt(dc[0] * dc[0] + dc[1] * dc[1]);
+        dc[0] /= nrm; dc[1] /= nrm;
+        const float dir[2] = { (float)dc[0], (float)dc[1] };
+        found = align_1d(cp->img[search_level], cp->width[search_level], cp->height[search_level], cp->stride[search_level], dir,
+                         patch_with_border, patch, in->align_max_iter, px_scaled, &iters);
+      } else {
+        found = align_2d(cp->img[search_level], cp->width[search_level], cp->height[search_level], cp->stride[search_level],
+                         patch_with_border, patch, in->align_max_iter, px_scaled, &iters);
       }
+      px_cur[0] = px_scaled[0] * (1 << search_level); px_cur[1] = px_scaled[1] * (1 << search_level);
     }
     if (out->px_cur) { out->px_cur[2 * i] = px_cur[0]; out->px_cur[2 * i + 1] = px_cur[1]; }
     if (out->found) out->found[i] = (uint8_t)found;
     if (out->search_level) out->search_level[i] = search_level;
     if (out->n_iter) out->n_iter[i] = iters;
+  }
+  return PLSVO_OK;
+}
+
+/* what plsvo_match_warp_patches (include/plsvo_hip.h) reports, from the same code as above; out->staged is the device's own and is
+ * not written */
+int plsvo_oracle_match_warp_patches(const plsvo_match_in* in, const plsvo_oracle_pyr* frames, plsvo_match_warp_out* out) {
+  if (!in || !out || in->n < 0 || in->n_frames <= 0 || !frames) return PLSVO_E_INVALID;
+  for (int i = 0; i < in->n; ++i) {
+    double A[4] = { 0, 0, 0, 0 };
+    int search_level = -1;
+    uint8_t patch_with_border[M_STEP * M_STEP];
+    const int warped = match_warp_candidate(in, frames, i, A, &search_level, patch_with_border) == 1;
+    if (out->A) for (int k = 0; k < 4; ++k) out->A[4 * i + k] = A[k];
+    if (out->search_level) out->search_level[i] = search_level;
+    if (out->warped) out->warped[i] = (uint8_t)warped;
+    if (out->patch) {
+      if (warped) memcpy(out->patch + (size_t)i * M_STEP * M_STEP, patch_with_border, M_STEP * M_STEP);
+      else memset(out->patch + (size_t)i * M_STEP * M_STEP, 0, M_STEP * M_STEP);
+    }
   }
   return PLSVO_OK;
 }

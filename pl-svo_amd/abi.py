@@ -123,6 +123,10 @@ class MatchOut(C.Structure):
     _fields_ = [("px_cur", c_double_p), ("found", c_u8_p), ("search_level", c_i32_p), ("n_iter", c_i32_p)]
 
 
+class MatchWarpOut(C.Structure):
+    _fields_ = [("A", c_double_p), ("search_level", c_i32_p), ("warped", c_u8_p), ("patch", c_u8_p), ("staged", c_u8_p)]
+
+
 class ReprojectIn(C.Structure):
     _fields_ = [("cam", Pinhole), ("n_frames", C.c_int32), ("n", C.c_int32), ("cell_size", C.c_int32), ("grid_n_cols", C.c_int32),
                 ("boundary", C.c_int32), ("reserved0", C.c_int32), ("frame_T", c_double_p), ("frame", c_i32_p), ("pos", c_double_p)]
@@ -375,6 +379,20 @@ class MatchJob:
 
     def trim(self, bufs):
         return {k: v[:self.n].copy() for k, v in bufs.items()}
+
+    def make_warp_out(self, fields=("A", "search_level", "warped", "patch", "staged")):
+        """buffers of plsvo_match_warp_patches (only `fields`; the others are passed as NULL), pre-filled with a pattern the call
+        must overwrite"""
+        o = MatchWarpOut()
+        m = max(self.n, 1)
+        shapes = dict(A=((m, 4), np.float64), search_level=((m,), np.int32), warped=((m,), np.uint8), patch=((m, 10, 10), np.uint8),
+                      staged=((m,), np.uint8))
+        bufs = {}
+        for k in fields:
+            shape, dt = shapes[k]
+            bufs[k] = np.frombuffer(b"\xa5" * (int(np.prod(shape)) * np.dtype(dt).itemsize), dtype=dt).reshape(shape).copy()
+            setattr(o, k, bufs[k].ctypes.data_as(dict(MatchWarpOut._fields_)[k]))
+        return o, bufs
 
 
 class ReprojectJob:

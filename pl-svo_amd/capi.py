@@ -25,7 +25,7 @@ SYMBOLS = [
     "plsvo_align_set_trace", "plsvo_align_fetch_trace", "plsvo_align_poses_dev", "plsvo_align_copy_poses", "plsvo_align_work", "plsvo_align_work_points", "plsvo_align_chi2_ties", "plsvo_align_launch_order", "plsvo_align_tail_frames",
     "plsvo_pose_optimize", "plsvo_pose_optimize_batch", "plsvo_poseopt_stage", "plsvo_poseopt_run", "plsvo_poseopt_fetch",
     "plsvo_poseopt_set_trace", "plsvo_poseopt_fetch_trace", "plsvo_poseopt_poses_dev", "plsvo_poseopt_copy_poses", "plsvo_poseopt_work", "plsvo_poseopt_refill_frames",
-    "plsvo_structure_optimize", "plsvo_match_direct", "plsvo_reproject", "plsvo_trajectory_record", "plsvo_update_seeds",
+    "plsvo_structure_optimize", "plsvo_match_direct", "plsvo_match_warp_patches", "plsvo_reproject", "plsvo_trajectory_record", "plsvo_update_seeds",
     "plsvo_chain_stage", "plsvo_chain_run", "plsvo_chain_fetch", "plsvo_frame_step_batch", "plsvo_chain_poses_dev",
     "plsvo_pack_pose_records", "plsvo_fetch_pose_records", "plsvo_gather_poses",
     "plsvo_hip_set_profiling", "plsvo_hip_kernel_time", "plsvo_hip_reset_profiling",
@@ -135,6 +135,7 @@ def lib():
         "plsvo_poseopt_work": (C.c_int, [ctxp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "plsvo_structure_optimize": (C.c_int, [ctxp, C.POINTER(abi.StructOptIn), C.POINTER(abi.StructOptOut)]),
         "plsvo_match_direct": (C.c_int, [ctxp, C.POINTER(abi.MatchIn), C.POINTER(abi.MatchOut)]),
+        "plsvo_match_warp_patches": (C.c_int, [ctxp, C.POINTER(abi.MatchIn), C.POINTER(abi.MatchWarpOut)]),
         "plsvo_reproject": (C.c_int, [ctxp, C.POINTER(abi.ReprojectIn), C.POINTER(abi.ReprojectOut)]),
         "plsvo_update_seeds": (C.c_int, [ctxp, C.POINTER(abi.SeedsIn), C.POINTER(abi.SeedsOut)]),
         "plsvo_trajectory_record": (C.c_int, [abi.c_double_p, abi.c_double_p, abi.c_double_p]),
@@ -534,6 +535,13 @@ class Context:
     def match_direct(self, job):
         out, bufs = job.make_out()
         self._chk(self.L.plsvo_match_direct(self.h, C.byref(job.c), C.byref(out)))
+        return job.trim(bufs)
+
+    def match_warp_patches(self, job, fields=("A", "search_level", "warped", "patch", "staged")):
+        """plsvo_match_warp_patches: the matcher's kernel stopped after the affine warp -> dict of A [n, 4], search_level [n], warped [n],
+        patch [n, 10, 10] and staged [n] (bit g: patch rows 2g, 2g+1 read the LDS window); only `fields` are asked for"""
+        out, bufs = job.make_warp_out(fields)
+        self._chk(self.L.plsvo_match_warp_patches(self.h, C.byref(job.c), C.byref(out)))
         return job.trim(bufs)
 
     def reproject(self, job):

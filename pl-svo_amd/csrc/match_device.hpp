@@ -122,8 +122,11 @@ constexpr int SRC_WORDS = 5;
 // (Round 5 staged the box of the WHOLE patch, 14 rows: 280 B of LDS per lane capped the kernel at six one-wave workgroups per CU, and a
 //  candidate is a chain of dependent float additions -- the reference's sequential sums -- that wants many waves per SIMD, not few.  Five
 //  groups of <= 6 rows re-read ~40 % more image rows from L1 / L2 and take 120 B per lane: ten workgroups per CU.)
+// `staged_mask` (optional, diagnostics): bit g is set when group g took its taps from the window.  tests/test_match_warp.py pins the rule
+// above (which group is staged, at its limits of 19 bytes and 6 rows) and the bytes of all three paths against the oracle.
 __device__ __forceinline__ bool warp_affine_lds(const double* A, const uint8_t* img_ref, int rcols, int rrows, double rpx0, double rpx1,
-                                                int level, int search_level, uint32_t* my, uint32_t* src = nullptr) {
+                                                int level, int search_level, uint32_t* my, uint32_t* src = nullptr,
+                                                uint32_t* staged_mask = nullptr) {
   const double det = A[0] * A[3] - A[2] * A[1];
   const double invdet = 1.0 / det;
   const float a00 = (float)(A[3] * invdet), a01 = (float)(-A[1] * invdet);
@@ -171,6 +174,7 @@ __device__ __forceinline__ bool warp_affine_lds(const double* A, const uint8_t* 
         }
       }
     }
+    if (staged_mask && staged) *staged_mask |= 1u << (y0 / SRC_GROUP);
     auto tap = [&](int lr, int lc) -> float {   // byte (row rmin + lr, column cbase + lc) of the staged window
       return (float)src_b[((lr * SRC_WORDS + (lc >> 2)) * MT) * 4 + (lc & 3)];
     };

@@ -32,6 +32,9 @@ namespace plsvo_hip {
 
 #pragma clang fp contract(off)
 
+// DIAG (plsvo_match_warp_patches): the same body up to and including the warp, then A, the patch and the mask of staged groups are written
+// out instead of aligning.  match_direct_kernel<false> is the product's kernel.
+template <bool DIAG>
 __global__ void __launch_bounds__(MT) match_direct_kernel(const MatchBatchDev b) {
   __shared__ uint32_t s_patch[PB_ROWS * PB_WORDS * MT];   // patch_with_border_, word-major / lane-minor
   __shared__ uint32_t s_src[SRC_ROWS * SRC_WORDS * MT];   // the keyframe-image window a warp reads, staged once (match_device.hpp::warp_affine_lds)
@@ -58,7 +61,23 @@ __global__ void __launch_bounds__(MT) match_direct_kernel(const MatchBatchDev b)
     warp_matrix_affine(cam, rpx0, rpx1, b.ref_f + 3 * i, depth_ref, T_cur_ref, level, A);
     search_level = best_search_level(A, b.n_pyr_levels - 1);
     const uint8_t* img_ref = b.pyr_base + (unsigned long long)b.frame_slot[rf] * b.slot_bytes + pyr_level_offset(b.width, b.height, level);
-    if (warp_affine_lds(A, img_ref, b.width >> level, b.height >> level, rpx0, rpx1, level, search_level, my, s_src + lane)) {
+    uint32_t staged_mask = 0u;
+    const bool warped = warp_affine_lds(A, img_ref, b.width >> level, b.height >> level, rpx0, rpx1, level, search_level, my, s_src + lane,
+                                        DIAG ? &staged_mask : nullptr);
+    if (DIAG) {   // (the buffers were zeroed by the host: a candidate that does not get here reports A = 0, warped = 0, patch = 0, staged = 0)
+      if (b.diag_A) for (int k = 0; k < 4; ++k) b.diag_A[4 * i + k] = A[k];
+      if (b.diag_warped) b.diag_warped[i] = warped ? 1 : 0;
+      if (b.diag_staged) b.diag_staged[i] = warped ? (uint8_t)staged_mask : (uint8_t)0;
+      if (b.diag_patch && warped) {
+        uint8_t* o = b.diag_patch + (size_t)i * (PB_ROWS * PB_STEP);
+        for (int y = 0; y < PB_ROWS; ++y) {
+          const uint32_t w0 = PBW(my, y, 0), w1 = PBW(my, y, 1), w2 = PBW(my, y, 2);
+#pragma unroll
+          for (int x = 0; x < PB_STEP; ++x) o[y * PB_STEP + x] = (uint8_t)row_byte(w0, w1, w2, x);
+        }
+      }
+    }
+    if (!DIAG && warped) {
       const int cols = b.width >> search_level, rows = b.height >> search_level;
       const uint8_t* cur_img = b.pyr_base + (unsigned long long)b.frame_slot[cf] * b.slot_bytes + pyr_level_offset(b.width, b.height, search_level);
       const double scale = (double)(1 << search_level);
@@ -174,7 +193,14 @@ hipError_t launch_reproject(const ReprojBatchDev& b, hipStream_t stream) {
 hipError_t launch_match_direct(const MatchBatchDev& b, hipStream_t stream) {
   if (b.n <= 0) return hipSuccess;
   const int blocks = (b.n + MT - 1) / MT;
-  hipLaunchKernelGGL(match_direct_kernel, dim3(blocks), dim3(MT), 0, stream, b);
+  hipLaunchKernelGGL(match_direct_kernel<false>, dim3(blocks), dim3(MT), 0, stream, b);
+  return hipGetLastError();
+}
+
+hipError_t launch_match_warp_patches(const MatchBatchDev& b, hipStream_t stream) {
+  if (b.n <= 0) return hipSuccess;
+  const int blocks = (b.n + MT - 1) / MT;
+  hipLaunchKernelGGL(match_direct_kernel<true>, dim3(blocks), dim3(MT), 0, stream, b);
   return hipGetLastError();
 }
 

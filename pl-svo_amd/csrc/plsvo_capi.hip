@@ -29,6 +29,7 @@ hipError_t launch_align_levels(const AlignBatchDev& b, int cap, int scap, int le
 hipError_t launch_pose_opt(const PoseBatchDev& b, double* d_poses, int threads, hipStream_t stream);
 hipError_t launch_structopt(const StructBatchDev& s, hipStream_t stream);
 hipError_t launch_match_direct(const MatchBatchDev& b, hipStream_t stream);
+hipError_t launch_match_warp_patches(const MatchBatchDev& b, hipStream_t stream);
 hipError_t launch_reproject(const ReprojBatchDev& b, hipStream_t stream);
 hipError_t launch_update_seeds(const SeedsBatchDev& b, hipStream_t stream);
 hipError_t launch_halfsample(const uint8_t* src, size_t src_pitch, int in_w, int in_h, int in_stride, uint8_t* dst,
@@ -1754,9 +1755,11 @@ extern "C" int plsvo_structure_optimize(plsvo_ctx* c, const plsvo_structopt_in* 
 }
 
 // ---- direct feature matching -------------------------------------------------------------------------
-extern "C" int plsvo_match_direct(plsvo_ctx* c, const plsvo_match_in* in, plsvo_match_out* out) {
+constexpr size_t kWarpPatchBytes = 100;   // patch_with_border_: 10 x 10 (match_device.hpp PB_ROWS x PB_STEP)
+// one staging, launch and read-back path for plsvo_match_direct (wout == nullptr) and its diagnostic view plsvo_match_warp_patches (out == nullptr)
+static int match_run(plsvo_ctx* c, const plsvo_match_in* in, plsvo_match_out* out, plsvo_match_warp_out* wout) {
   CTX_CHECK(c);
-  if (!in || !out || in->n < 0 || in->n_frames < 0 || in->n_pyr_levels < 1 || in->align_max_iter < 0)
+  if (!in || (!out && !wout) || in->n < 0 || in->n_frames < 0 || in->n_pyr_levels < 1 || in->align_max_iter < 0)
     return fail(c, PLSVO_E_INVALID, "match_direct: bad arguments");
   const int n = in->n, nf = in->n_frames;
   if (n == 0) return PLSVO_OK;
@@ -1791,7 +1794,9 @@ extern "C" int plsvo_match_direct(plsvo_ctx* c, const plsvo_match_in* in, plsvo_
   HIP_TRY(c, hipMemcpyAsync(din + dbytes, iv.data(), iv.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipMemcpyAsync(din + dbytes + ibytes, in->ref_type, bbytes, hipMemcpyHostToDevice, c->stream));
   const size_t out_d = (size_t)n * 2 * sizeof(double), out_i = (size_t)n * 2 * sizeof(int), out_b = (size_t)n;
-  HIP_TRY(c, c->s_d_out.ensure(out_d + out_i + out_b + 16));
+  // the diagnostic view appends: A (4 doubles), then warped, staged, patch (100 bytes) per candidate
+  const size_t o_dA = (out_d + out_i + out_b + 15) / 16 * 16, diag_A = (size_t)n * 4 * sizeof(double), diag_b = (size_t)n * (2 + kWarpPatchBytes);
+  HIP_TRY(c, c->s_d_out.ensure((wout ? o_dA + diag_A + diag_b : out_d + out_i + out_b) + 16));
   char* dout = reinterpret_cast<char*>(c->s_d_out.p);
   const double* dd = reinterpret_cast<const double*>(din);
   const int* di = reinterpret_cast<const int*>(din + dbytes);
@@ -1805,6 +1810,22 @@ extern "C" int plsvo_match_direct(plsvo_ctx* c, const plsvo_match_in* in, plsvo_
   b.px_out = reinterpret_cast<double*>(dout);
   b.search_level = reinterpret_cast<int*>(dout + out_d); b.n_iter = b.search_level + n;
   b.found = reinterpret_cast<uint8_t*>(dout + out_d + out_i);
+  if (wout) {
+    HIP_TRY(c, hipMemsetAsync(dout + o_dA, 0, diag_A + diag_b, c->stream));
+    b.diag_A = reinterpret_cast<double*>(dout + o_dA);
+    b.diag_warped = reinterpret_cast<uint8_t*>(dout + o_dA + diag_A); b.diag_staged = b.diag_warped + n; b.diag_patch = b.diag_staged + n;
+    HIP_TRY(c, launch_match_warp_patches(b, c->stream));
+    std::vector<char> h(o_dA + diag_A + diag_b);
+    HIP_TRY(c, hipMemcpyAsync(h.data(), dout, h.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const char* hb = h.data() + o_dA + diag_A;
+    if (wout->A) memcpy(wout->A, h.data() + o_dA, diag_A);
+    if (wout->search_level) memcpy(wout->search_level, h.data() + out_d, (size_t)n * sizeof(int));
+    if (wout->warped) memcpy(wout->warped, hb, (size_t)n);
+    if (wout->staged) memcpy(wout->staged, hb + n, (size_t)n);
+    if (wout->patch) memcpy(wout->patch, hb + 2 * (size_t)n, (size_t)n * kWarpPatchBytes);
+    return PLSVO_OK;
+  }
   {
     EventPair ep{}; prof_begin(c, PLSVO_K_MATCH, &ep);
     HIP_TRY(c, launch_match_direct(b, c->stream));
@@ -1818,6 +1839,18 @@ extern "C" int plsvo_match_direct(plsvo_ctx* c, const plsvo_match_in* in, plsvo_
   if (out->n_iter) memcpy(out->n_iter, h.data() + out_d + (size_t)n * sizeof(int), (size_t)n * sizeof(int));
   if (out->found) memcpy(out->found, h.data() + out_d + out_i, out_b);
   return PLSVO_OK;
+}
+
+extern "C" int plsvo_match_direct(plsvo_ctx* c, const plsvo_match_in* in, plsvo_match_out* out) {
+  CTX_CHECK(c);
+  if (!out) return fail(c, PLSVO_E_INVALID, "match_direct: bad arguments");
+  return match_run(c, in, out, nullptr);
+}
+
+extern "C" int plsvo_match_warp_patches(plsvo_ctx* c, const plsvo_match_in* in, plsvo_match_warp_out* out) {
+  CTX_CHECK(c);
+  if (!out) return fail(c, PLSVO_E_INVALID, "match_warp_patches: bad arguments");
+  return match_run(c, in, nullptr, out);
 }
 
 // ---- reprojection of landmarks (candidates for the direct matcher) ------------------------------------

@@ -203,6 +203,8 @@ struct MatchBatchDev {
   const double* pos; const double* px_cur;
   double* px_out; uint8_t* found; int* search_level; int* n_iter;
   const uint8_t* active;            // optional (resident frame step): candidates with 0 are reported "not found" without any work
+  // plsvo_match_warp_patches only (match_direct_kernel<true>; the <false> instantiation never reads them): any may be null
+  double* diag_A; uint8_t* diag_warped; uint8_t* diag_patch; uint8_t* diag_staged;
 };
 
 // depth-filter seeds (include/plsvo_hip.h plsvo_seeds_in / plsvo_seeds_out), one lane per seed

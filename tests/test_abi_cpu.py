@@ -37,7 +37,8 @@ def test_ctypes_structs_match_the_c_header(P, tmp_path):
                "plsvo_align_iterlog": P.abi.AlignIterLog, "plsvo_poseopt_in": P.abi.PoseOptIn,
                "plsvo_poseopt_out": P.abi.PoseOptOut, "plsvo_poseopt_iterlog": P.abi.PoseOptIterLog,
                "plsvo_structopt_in": P.abi.StructOptIn, "plsvo_structopt_out": P.abi.StructOptOut,
-               "plsvo_match_in": P.abi.MatchIn, "plsvo_match_out": P.abi.MatchOut, "plsvo_reproject_in": P.abi.ReprojectIn,
+               "plsvo_match_in": P.abi.MatchIn, "plsvo_match_out": P.abi.MatchOut, "plsvo_match_warp_out": P.abi.MatchWarpOut,
+               "plsvo_reproject_in": P.abi.ReprojectIn,
                "plsvo_reproject_out": P.abi.ReprojectOut, "plsvo_seeds_in": P.abi.SeedsIn, "plsvo_seeds_out": P.abi.SeedsOut,
                "plsvo_chain_in": P.abi.ChainIn, "plsvo_chain_params": P.abi.ChainParams, "plsvo_chain_out": P.abi.ChainOut,
                "plsvo_pose_record": P.abi.PoseRecord}

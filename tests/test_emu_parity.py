@@ -50,7 +50,7 @@ def test_gpu_parity_suite_passes_on_the_emulated_library(emu_lib):
     tail = out.stdout[-3000:] + out.stderr[-1000:]
     assert out.returncode == 0, tail
     last = [l for l in out.stdout.splitlines() if " passed" in l][-1]
-    assert " failed" not in last and int(last.split(" passed")[0].split()[-1]) >= 87, tail
+    assert " failed" not in last and int(last.split(" passed")[0].split()[-1]) >= 128, tail
 
 
 def test_cpp_adapter_on_the_emulated_library(emu_lib):

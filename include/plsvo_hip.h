@@ -92,6 +92,12 @@ void plsvo_hip_destroy(plsvo_ctx* ctx);
  * frames) that takes the three kernels and PLSVO_POSEOPT_REFILL_WAVES the number of workgroups of the persistent one (read once, at
  * plsvo_hip_create). */
 #define PLSVO_OPT_POSEOPT_REFILL 7
+/* Medians of the pose optimiser's row kernels (the two MAD scales, error_init, error_final; a 16-lane row per frame): 1 (default) =
+ * every lane fetches its values once into registers, the first digit starts at the highest bit in which the row's minimum and maximum
+ * differ, and the last (at most 16) candidates are finished by rank; 0 = the radix select that walks every digit over memory.  A wave
+ * with a row of more than 320 values takes the latter either way.  An order statistic has one value: every result is bit-identical.
+ * The environment switch PLSVO_POSEOPT_SELECT=0 sets the initial value to 0. */
+#define PLSVO_OPT_POSEOPT_SELECT 8
 int plsvo_hip_set_option(plsvo_ctx* ctx, int option, int value);
 const char* plsvo_hip_last_error(const plsvo_ctx* ctx);   /* ctx may be NULL: last create error */
 void* plsvo_hip_stream(plsvo_ctx* ctx);                   /* the hipStream_t all work is enqueued on */
@@ -396,6 +402,27 @@ int plsvo_poseopt_work(plsvo_ctx* ctx, uint64_t* pt_iters, uint64_t* seg_iters);
    through the row-refill path (PLSVO_OPT_POSEOPT_REFILL): the whole batch, or 0 when it ran as one kernel (the chain's always does:
    its jobs are written on the device).  Tests and measurements. */
 int plsvo_poseopt_refill_frames(plsvo_ctx* ctx, int* refill_frames);
+/* For tests: the select of the row kernels' medians -- the very device function, four rows per 64-thread workgroup -- on rows of
+ * unsigned patterns.  selected: n_rows patterns of `bits` bits (the k-th smallest of each row, 0-based; 0 for an inactive or empty row);
+ * path: n_rows words of PLSVO_ROW_SELECT_* bits, the route a row took (0 for an inactive row).  Rows of one workgroup (4 consecutive
+ * rows) share the route when one of them is above the cap.  Follows PLSVO_OPT_POSEOPT_SELECT. */
+#define PLSVO_ROW_SELECT_CAP 320          /* values per row the register route holds */
+#define PLSVO_ROW_SELECT_EQUAL 1          /* minimum == maximum */
+#define PLSVO_ROW_SELECT_RANK 2           /* finished by rank among at most 16 candidates */
+#define PLSVO_ROW_SELECT_EXTRA_PASS 4     /* more than one histogram pass */
+#define PLSVO_ROW_SELECT_FALLBACK 8       /* the radix select over memory */
+#define PLSVO_ROW_SELECT_DIGITS 16        /* every bit decided by histogram passes */
+typedef struct {
+  int32_t bits;                 /* 32 or 64 */
+  int32_t n_rows;
+  const void* patterns;         /* n_patterns values of uint32_t / uint64_t */
+  int64_t n_patterns;
+  const int64_t* row_off;       /* per row: index of its first pattern */
+  const int32_t* row_n;
+  const int32_t* row_k;         /* 0 <= k < n for an active row */
+  const uint8_t* row_active;
+} plsvo_row_select_in;
+int plsvo_poseopt_row_select(plsvo_ctx* ctx, const plsvo_row_select_in* in, void* selected, int32_t* path);
 
 /* ------------------------------------------------------------------------------------------ */
 /* structure optimisation (hot-path contract row (f) "next" #3)                                */

@@ -127,6 +127,11 @@ class MatchWarpOut(C.Structure):
     _fields_ = [("A", c_double_p), ("search_level", c_i32_p), ("warped", c_u8_p), ("patch", c_u8_p), ("staged", c_u8_p)]
 
 
+class RowSelectIn(C.Structure):
+    _fields_ = [("bits", C.c_int32), ("n_rows", C.c_int32), ("patterns", C.c_void_p), ("n_patterns", C.c_int64),
+                ("row_off", C.POINTER(C.c_int64)), ("row_n", c_i32_p), ("row_k", c_i32_p), ("row_active", c_u8_p)]
+
+
 class ReprojectIn(C.Structure):
     _fields_ = [("cam", Pinhole), ("n_frames", C.c_int32), ("n", C.c_int32), ("cell_size", C.c_int32), ("grid_n_cols", C.c_int32),
                 ("boundary", C.c_int32), ("reserved0", C.c_int32), ("frame_T", c_double_p), ("frame", c_i32_p), ("pos", c_double_p)]

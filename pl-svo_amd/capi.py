@@ -24,7 +24,7 @@ SYMBOLS = [
     "plsvo_sparse_align", "plsvo_sparse_align_batch", "plsvo_align_stage", "plsvo_align_run", "plsvo_align_fetch",
     "plsvo_align_set_trace", "plsvo_align_fetch_trace", "plsvo_align_poses_dev", "plsvo_align_copy_poses", "plsvo_align_work", "plsvo_align_work_points", "plsvo_align_chi2_ties", "plsvo_align_launch_order", "plsvo_align_tail_frames",
     "plsvo_pose_optimize", "plsvo_pose_optimize_batch", "plsvo_poseopt_stage", "plsvo_poseopt_run", "plsvo_poseopt_fetch",
-    "plsvo_poseopt_set_trace", "plsvo_poseopt_fetch_trace", "plsvo_poseopt_poses_dev", "plsvo_poseopt_copy_poses", "plsvo_poseopt_work", "plsvo_poseopt_refill_frames",
+    "plsvo_poseopt_set_trace", "plsvo_poseopt_fetch_trace", "plsvo_poseopt_poses_dev", "plsvo_poseopt_copy_poses", "plsvo_poseopt_work", "plsvo_poseopt_refill_frames", "plsvo_poseopt_row_select",
     "plsvo_structure_optimize", "plsvo_match_direct", "plsvo_match_warp_patches", "plsvo_reproject", "plsvo_trajectory_record", "plsvo_update_seeds",
     "plsvo_chain_stage", "plsvo_chain_run", "plsvo_chain_fetch", "plsvo_frame_step_batch", "plsvo_chain_poses_dev",
     "plsvo_pack_pose_records", "plsvo_fetch_pose_records", "plsvo_gather_poses",
@@ -124,6 +124,7 @@ def lib():
         "plsvo_align_launch_order": (C.c_int, [ctxp, C.c_int, C.POINTER(C.c_int32)]),
         "plsvo_align_tail_frames": (C.c_int, [ctxp, C.POINTER(C.c_int)]),
         "plsvo_poseopt_refill_frames": (C.c_int, [ctxp, C.POINTER(C.c_int)]),
+        "plsvo_poseopt_row_select": (C.c_int, [ctxp, C.POINTER(abi.RowSelectIn), vp, abi.c_i32_p]),
         "plsvo_pose_optimize": (C.c_int, [ctxp, C.POINTER(abi.PoseOptIn), C.POINTER(abi.PoseOptOut)]),
         "plsvo_pose_optimize_batch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.PoseOptIn), C.POINTER(abi.PoseOptOut)]),
         "plsvo_poseopt_stage": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.PoseOptIn)]),
@@ -212,6 +213,11 @@ class Context:
         frame from a queue, False = one launch, the four frames of a wave in lock step (PLSVO_OPT_POSEOPT_REFILL); scheduling only,
         results bit-identical"""
         self._chk(self.L.plsvo_hip_set_option(self.h, 7, 1 if on else 0))
+
+    def set_poseopt_select(self, on):
+        """medians of the pose optimiser's row kernels: True (default) = values once into registers, first digit at the highest bit that
+        differs, rank finish; False = the radix select over memory, every digit (PLSVO_OPT_POSEOPT_SELECT); results bit-identical"""
+        self._chk(self.L.plsvo_hip_set_option(self.h, 8, 1 if on else 0))
 
     def close(self):
         if getattr(self, "h", None):
@@ -393,6 +399,24 @@ class Context:
         out = np.zeros(n, dtype=np.int32)
         self._chk(self.L.plsvo_align_launch_order(self.h, n, out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out
+
+    def poseopt_row_select(self, patterns, row_off, row_n, row_k, row_active):
+        """plsvo_poseopt_row_select: the row kernels' median select on rows of uint32 / uint64 patterns (concatenated in `patterns`; per
+        row its offset, n, k and active flag) -> (selected [n_rows] of the patterns' dtype, path [n_rows] int32 of PLSVO_ROW_SELECT_* bits)"""
+        patterns = np.ascontiguousarray(patterns)
+        if patterns.dtype not in (np.dtype(np.uint32), np.dtype(np.uint64)):
+            raise ValueError("poseopt_row_select: patterns are uint32 or uint64")
+        off = np.ascontiguousarray(row_off, np.int64); n = np.ascontiguousarray(row_n, np.int32)
+        k = np.ascontiguousarray(row_k, np.int32); act = np.ascontiguousarray(row_active, np.uint8)
+        nr = len(n)
+        if not (len(off) == len(k) == len(act) == nr):
+            raise ValueError("poseopt_row_select: per-row arrays differ in length")
+        sel = np.zeros(nr, patterns.dtype); path = np.zeros(nr, np.int32)
+        a = abi.RowSelectIn(patterns.dtype.itemsize * 8, nr, patterns.ctypes.data_as(C.c_void_p), patterns.size,
+                            off.ctypes.data_as(C.POINTER(C.c_int64)), n.ctypes.data_as(abi.c_i32_p), k.ctypes.data_as(abi.c_i32_p),
+                            act.ctypes.data_as(abi.c_u8_p))
+        self._chk(self.L.plsvo_poseopt_row_select(self.h, C.byref(a), sel.ctypes.data_as(C.c_void_p), path.ctypes.data_as(abi.c_i32_p)))
+        return sel, path
 
     def poseopt_refill_frames(self):
         """plsvo_poseopt_refill_frames: frames the last pose-optimiser launch ran through the row-refill path (0 = one launch)"""

@@ -19,6 +19,7 @@
 #include "plsvo_dev.hpp"
 #include "plsvo_math.hpp"
 #include "poseopt_refill.hpp"
+#include "poseopt_select.hpp"
 
 namespace plsvo_hip {
 // kernels (align_kernels.hip, poseopt_kernels.hip, pyramid_kernels.hip)
@@ -26,7 +27,7 @@ size_t align_level_lds_bytes(int threads, int cap, int scap, int chi_lds_pts);
 hipError_t launch_align_reorder(const int* work_key, int n, int* order_out, int shift, hipStream_t stream);   // (the pose optimiser's batches use it too)
 hipError_t launch_align_levels(const AlignBatchDev& b, int cap, int scap, int level_hi, int level_lo, int do_init, int threads, size_t lds,
                                hipStream_t stream);
-hipError_t launch_pose_opt(const PoseBatchDev& b, double* d_poses, int threads, hipStream_t stream);
+hipError_t launch_pose_opt(const PoseBatchDev& b, double* d_poses, int threads, int select, hipStream_t stream);
 hipError_t launch_structopt(const StructBatchDev& s, hipStream_t stream);
 hipError_t launch_match_direct(const MatchBatchDev& b, hipStream_t stream);
 hipError_t launch_match_warp_patches(const MatchBatchDev& b, hipStream_t stream);
@@ -160,6 +161,8 @@ struct plsvo_ctx {
   // PLSVO_POSEOPT_REFILL_WAVES (workgroups of the persistent kernel; default: the resident ones)
   bool opt_poseopt_refill = true;
   int env_poseopt_refill_min = 0, env_poseopt_refill_waves = 0;
+  // medians of the row kernels (poseopt_select.hpp): values once into registers, rank finish -- PLSVO_OPT_POSEOPT_SELECT; false = row_radix_select everywhere
+  bool opt_poseopt_select = true;
   bool p_any_ref = false;                   //   a job of the staged batch has a refinement loop (n_iter_ref > 0): pose_opt_rows_kernel
   int p_refill_frames = 0;                  //   frames the last pose-optimiser launch ran through the three launches
   DevBuf p_d_carry, p_d_refill_next;        //   PoseRefillCarry per job; the queue's counter
@@ -298,6 +301,7 @@ static int create_ctx(int device_id, void* stream, bool use_given_stream, plsvo_
   c->env_poseopt_no_reorder = env_flag("PLSVO_POSEOPT_NO_REORDER");
   if (const char* s = getenv("PLSVO_POSEOPT_REORDER_MIN")) c->env_poseopt_reorder_min = atoi(s);
   if (const char* s = getenv("PLSVO_POSEOPT_REFILL")) c->opt_poseopt_refill = atoi(s) != 0;
+  if (const char* s = getenv("PLSVO_POSEOPT_SELECT")) c->opt_poseopt_select = atoi(s) != 0;
   if (const char* s = getenv("PLSVO_POSEOPT_REFILL_MIN")) c->env_poseopt_refill_min = atoi(s);
   if (const char* s = getenv("PLSVO_POSEOPT_REFILL_WAVES")) c->env_poseopt_refill_waves = atoi(s);
   c->env_host_timing = getenv("PLSVO_HOST_TIMING") != nullptr;
@@ -363,6 +367,11 @@ extern "C" int plsvo_hip_set_option(plsvo_ctx* c, int option, int value) {
   if (option == PLSVO_OPT_POSEOPT_REFILL) {
     if (value != 0 && value != 1) return fail(c, PLSVO_E_INVALID, "set_option: the pose optimiser's row refill is 0 (four frames of a wave in lock step) or 1 (rows take their next frame from a queue)");
     c->opt_poseopt_refill = value != 0;
+    return PLSVO_OK;
+  }
+  if (option == PLSVO_OPT_POSEOPT_SELECT) {
+    if (value != 0 && value != 1) return fail(c, PLSVO_E_INVALID, "set_option: the row kernels' median select is 0 (radix select over memory, every digit) or 1 (values in registers, rank finish)");
+    c->opt_poseopt_select = value != 0;
     return PLSVO_OK;
   }
   return fail(c, PLSVO_E_INVALID, "set_option: unknown option");
@@ -1577,10 +1586,10 @@ extern "C" int plsvo_poseopt_run(plsvo_ctx* c) {
     HIP_TRY(c, c->p_d_refill_next.ensure(16));
     HIP_TRY(c, hipMemsetAsync(c->p_d_refill_next.p, 0, 16, c->stream));   // the queue is re-armed ahead of every launch
     const PoseRefillDev q{ c->p_d_carry.as<PoseRefillCarry>(), c->p_d_refill_next.as<int>() };
-    HIP_TRY(c, launch_pose_opt_refill(c->p_b, q, c->p_d_poses.as<double>(), gn_grid, c->stream));
+    HIP_TRY(c, launch_pose_opt_refill(c->p_b, q, c->p_d_poses.as<double>(), gn_grid, c->opt_poseopt_select ? 1 : 0, c->stream));
     c->p_refill_frames = c->p_n;
   } else {
-    HIP_TRY(c, launch_pose_opt(c->p_b, c->p_d_poses.as<double>(), threads, c->stream));
+    HIP_TRY(c, launch_pose_opt(c->p_b, c->p_d_poses.as<double>(), threads, c->opt_poseopt_select ? 1 : 0, c->stream));
   }
   c->p_run_seq = ++c->run_seq;
   prof_end(c, PLSVO_K_POSEOPT, &ep);
@@ -1628,6 +1637,51 @@ extern "C" int plsvo_poseopt_refill_frames(plsvo_ctx* c, int* refill_frames) {
   CTX_CHECK(c);
   if (!refill_frames) return fail(c, PLSVO_E_INVALID, "poseopt_refill_frames: NULL output");
   *refill_frames = c->p_refill_frames;
+  return PLSVO_OK;
+}
+
+// the row kernels' select on rows of patterns (tests): staged in one blob, one launch, read back
+extern "C" int plsvo_poseopt_row_select(plsvo_ctx* c, const plsvo_row_select_in* in, void* selected, int32_t* path) {
+  CTX_CHECK(c);
+  if (!in || !selected || !path || in->n_rows < 0 || in->n_patterns < 0 || (in->bits != 32 && in->bits != 64))
+    return fail(c, PLSVO_E_INVALID, "poseopt_row_select: bad arguments");
+  const int nr = in->n_rows;
+  if (nr == 0) return PLSVO_OK;
+  if (!in->row_off || !in->row_n || !in->row_k || !in->row_active || (in->n_patterns > 0 && !in->patterns))
+    return fail(c, PLSVO_E_INVALID, "poseopt_row_select: null input array");
+  for (int r = 0; r < nr; ++r) {
+    const long long o = in->row_off[r]; const int n = in->row_n[r];
+    if (n < 0 || o < 0 || o + (long long)n > in->n_patterns) return fail(c, PLSVO_E_INVALID, "poseopt_row_select: a row lies outside the patterns");
+    if (in->row_active[r] && n > 0 && (in->row_k[r] < 0 || in->row_k[r] >= n)) return fail(c, PLSVO_E_INVALID, "poseopt_row_select: k outside [0, n)");
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t width = (size_t)in->bits / 8;
+  auto up16 = [](size_t v) { return (v + 15) / 16 * 16; };
+  const size_t o_off = up16((size_t)in->n_patterns * width), o_n = o_off + up16((size_t)nr * sizeof(long long)), o_k = o_n + up16((size_t)nr * sizeof(int));
+  const size_t o_act = o_k + up16((size_t)nr * sizeof(int)), in_bytes = o_act + up16((size_t)nr);
+  std::vector<uint8_t> h(in_bytes, 0);
+  if (in->n_patterns > 0) memcpy(h.data(), in->patterns, (size_t)in->n_patterns * width);
+  memcpy(h.data() + o_off, in->row_off, (size_t)nr * sizeof(long long));
+  memcpy(h.data() + o_n, in->row_n, (size_t)nr * sizeof(int));
+  memcpy(h.data() + o_k, in->row_k, (size_t)nr * sizeof(int));
+  memcpy(h.data() + o_act, in->row_active, (size_t)nr);
+  const size_t o_path = up16((size_t)nr * width), out_bytes = o_path + (size_t)nr * sizeof(int);
+  HIP_TRY(c, c->s_d_in.ensure(in_bytes + 16));
+  HIP_TRY(c, c->s_d_out.ensure(out_bytes + 16));
+  char* din = reinterpret_cast<char*>(c->s_d_in.p); char* dout = reinterpret_cast<char*>(c->s_d_out.p);
+  HIP_TRY(c, hipMemcpyAsync(din, h.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemsetAsync(dout, 0, out_bytes, c->stream));
+  RowSelectDev t{};
+  t.patterns = din; t.row_off = reinterpret_cast<const long long*>(din + o_off); t.row_n = reinterpret_cast<const int*>(din + o_n);
+  t.row_k = reinterpret_cast<const int*>(din + o_k); t.row_active = reinterpret_cast<const uint8_t*>(din + o_act);
+  t.selected = dout; t.path = reinterpret_cast<int*>(dout + o_path);
+  t.n_rows = nr; t.bits = in->bits; t.select = c->opt_poseopt_select ? 1 : 0;
+  HIP_TRY(c, launch_pose_row_select(t, c->stream));
+  std::vector<uint8_t> ho(out_bytes);
+  HIP_TRY(c, hipMemcpyAsync(ho.data(), dout, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  memcpy(selected, ho.data(), (size_t)nr * width);
+  memcpy(path, ho.data() + o_path, (size_t)nr * sizeof(int));
   return PLSVO_OK;
 }
 
@@ -2056,7 +2110,7 @@ extern "C" int plsvo_chain_run(plsvo_ctx* c) {
   if (c->env_poseopt_threads) threads = c->env_poseopt_threads;
   c->p_refill_frames = 0;   // (the chain's jobs are written on the device: the host cannot see whether one has a refinement loop -- pose_opt_rows_kernel)
   EventPair ep{}; prof_begin(c, PLSVO_K_POSEOPT, &ep);
-  HIP_TRY(c, launch_pose_opt(c->ch_pose, c->ch_d_poses.as<double>(), threads, c->stream));
+  HIP_TRY(c, launch_pose_opt(c->ch_pose, c->ch_d_poses.as<double>(), threads, c->opt_poseopt_select ? 1 : 0, c->stream));
   prof_end(c, PLSVO_K_POSEOPT, &ep);
   c->ch_run_seq = ++c->run_seq;
   return PLSVO_OK;

@@ -21,6 +21,7 @@
 #include "plsvo_math.hpp"
 #include "plsvo_wave.hpp"
 #include "poseopt_refill.hpp"
+#include "poseopt_select.hpp"
 
 // Waves per SIMD.  The wave-per-frame shape (64 threads) is capped at 168 VGPRs = THREE waves per SIMD: its feature loops stay spill-free
 // (the 58 spilled registers are touched ~20 times per Gauss-Newton iteration, around the solve) and the f64 division chains of a third
@@ -516,7 +517,8 @@ __global__ __launch_bounds__(PO_T) PLSVO_PO_OCC(PO_T) void pose_opt_kernel(PoseB
 //   * solve + update: lane 0 of every row solves its frame's 6x6 system serially in registers (lane_solve6: Eigen's pivot order is the
 //     original diagonal sorted once, so the matrix is gathered from LDS already permuted and eliminated with static indices -- nothing
 //     indexed at run time, no scratch) and applies the update: four frames per instruction stream instead of one;
-//   * medians: radix select per row over a 256-bin LDS histogram per frame, bins scanned with row-level DPP shifts.
+//   * medians: per row, from the values held in the lanes' registers (row_select_regs, poseopt_select.hpp: minimum / maximum, histogram
+//     passes over a 256-bin LDS histogram per frame, rank finish); rows above its cap: radix select over memory (row_radix_select).
 // Rows of a wave run in lock step: a loop runs to the largest trip count of its four frames (same feature counts in practice; the
 // Gauss-Newton loops differ by an iteration or two).
 // ================================================================================================================================
@@ -599,6 +601,140 @@ __device__ __forceinline__ U row_radix_select(GET get, int n, int k, bool active
     wave_lds_fence();   // sel is rewritten by the next pass
   }
   return done ? result : prefix;
+}
+
+// ---- the row select from registers (poseopt_select.hpp: what it is for, the paths) -----------------------------------------------------
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_mov_bits(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true); }
+template <int CTRL>
+__device__ __forceinline__ unsigned long long dpp_mov_bits(unsigned long long v) {
+  const uint32_t lo = dpp_mov_bits<CTRL>((uint32_t)v), hi = dpp_mov_bits<CTRL>((uint32_t)(v >> 32));
+  return ((unsigned long long)hi << 32) | (unsigned long long)lo;
+}
+// minimum / maximum / bitwise OR over the 16 lanes of a row, result in every lane of the row
+template <typename U>
+__device__ __forceinline__ void row_min_max_bits(U& mn, U& mx) {
+  U a, c;
+  a = dpp_mov_bits<DPP_QUAD_XOR1>(mn); c = dpp_mov_bits<DPP_QUAD_XOR1>(mx); mn = a < mn ? a : mn; mx = c > mx ? c : mx;
+  a = dpp_mov_bits<DPP_QUAD_XOR2>(mn); c = dpp_mov_bits<DPP_QUAD_XOR2>(mx); mn = a < mn ? a : mn; mx = c > mx ? c : mx;
+  a = dpp_mov_bits<DPP_ROW_HALF_MIRROR>(mn); c = dpp_mov_bits<DPP_ROW_HALF_MIRROR>(mx); mn = a < mn ? a : mn; mx = c > mx ? c : mx;
+  a = dpp_mov_bits<DPP_ROW_MIRROR>(mn); c = dpp_mov_bits<DPP_ROW_MIRROR>(mx); mn = a < mn ? a : mn; mx = c > mx ? c : mx;
+}
+template <typename U>
+__device__ __forceinline__ U row_or_bits(U v) {
+  v |= dpp_mov_bits<DPP_QUAD_XOR1>(v); v |= dpp_mov_bits<DPP_QUAD_XOR2>(v);
+  v |= dpp_mov_bits<DPP_ROW_HALF_MIRROR>(v); v |= dpp_mov_bits<DPP_ROW_MIRROR>(v);
+  return v;
+}
+__device__ __forceinline__ uint32_t po_bits(float x) { return (uint32_t)__float_as_uint(x); }
+__device__ __forceinline__ unsigned long long po_bits(double x) { return (unsigned long long)__double_as_longlong(x); }
+__device__ __forceinline__ uint32_t po_bits(uint32_t x) { return x; }
+__device__ __forceinline__ unsigned long long po_bits(unsigned long long x) { return x; }
+
+// k-th smallest (0-based) of n <= kRowSelectCap unsigned patterns of BITS bits by the 16 lanes of ONE ROW, the values in registers: lane rl
+// holds elements rl, rl + 16, ... in v[0], v[1], ... (entries at or past n are never looked at).  Every row of the wave calls it
+// together.  `hist`: the row's 256 histogram words (the first 32 double as the candidates' staging).  `path`: kRowSelect* bits.
+template <int BITS, typename U>
+__device__ __forceinline__ U row_select_regs(const U (&v)[kRowSelectChunks], int n, int k, bool active, int* hist, int& path) {
+  static_assert(PO_RADIX_BITS == 8 && kRowSelectCap < 1024, "16 lanes x 16 bins; bin, count and rank share one word");
+  const int rl = threadIdx.x & 15;
+  constexpr U ONES = ~(U)0;
+  U mn = ONES, mx = 0;
+#pragma unroll
+  for (int c = 0; c < kRowSelectChunks; ++c) if (rl + 16 * c < n) { mn = v[c] < mn ? v[c] : mn; mx = v[c] > mx ? v[c] : mx; }
+  row_min_max_bits(mn, mx);
+  U result = 0;
+  bool done = !active;
+  path = 0;
+  if (active && mn == mx) { result = mn; done = true; path = kRowSelectEqual; }   // (identical values: also n == 1)
+  // the bits above the highest bit in which minimum and maximum differ are common to every value: the first digit starts there
+  const U diff = mn ^ mx;
+  const int hb = diff ? 63 - __builtin_clzll((unsigned long long)diff) : 0;
+  U mask = hb + 1 >= BITS ? (U)0 : (U)(ONES << (hb + 1));
+  U prefix = mn & mask;
+  int shift = hb >= 7 ? hb - 7 : 0;
+  int passes = 0, cnt = 0;
+  while (__any(!done)) {
+#pragma unroll
+    for (int j = 0; j < 16; j += 4) *reinterpret_cast<uint4*>(hist + rl * 16 + j) = make_uint4(0u, 0u, 0u, 0u);
+    wave_lds_fence();
+    if (!done) {
+#pragma unroll
+      for (int c = 0; c < kRowSelectChunks; ++c)
+        if (rl + 16 * c < n && (v[c] & mask) == prefix) atomicAdd(&hist[(int)(((v[c] & ~mask) >> shift) & (U)255)], 1);
+    }
+    wave_lds_fence();
+    int loc[16], local = 0;
+#pragma unroll
+    for (int j = 0; j < 16; j += 4) {
+      const uint4 h4 = *reinterpret_cast<const uint4*>(hist + rl * 16 + j);
+      loc[j] = (int)h4.x; loc[j + 1] = (int)h4.y; loc[j + 2] = (int)h4.z; loc[j + 3] = (int)h4.w;
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j) local += loc[j];
+    int cum = row_scan_incl_i32(local) - local;
+    int pack = 0;   // the lane that owns the bin of rank k: bin << 20 | its count << 10 | the rank inside it
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      if (!done && k >= cum && k < cum + loc[j]) pack = ((rl * 16 + j) << 20) | (loc[j] << 10) | (k - cum);
+      cum += loc[j];
+    }
+    pack = row_sum_i32(pack);
+    bool rank = false;
+    if (!done) {
+      ++passes;
+      prefix |= (U)(unsigned)(pack >> 20) << shift;
+      mask |= (U)255 << shift;
+      cnt = (pack >> 10) & 1023; k = pack & 1023;
+      if (shift == 0) { result = prefix; done = true; path = kRowSelectDigits | (passes > 1 ? kRowSelectExtraPass : 0); }   // every bit is decided
+      else if (cnt <= 16) rank = true;
+      else shift = shift >= 8 ? shift - 8 : 0;   // (heavy duplicates, or a crowded bin: another digit)
+    }
+    if (__any(rank)) {
+      // at most 16 values are left: one per lane through LDS, every lane counts how many are below / not above its own, and the lane
+      // with less <= k < leq holds the answer (equal values: several lanes, the same pattern)
+      // (the candidates are staged in the row's first histogram words, which the rest of the pass reads and writes as int / uint4: what
+      //  orders the two views is the wave_lds_fence() in front of the bin reads above, the one between these stores and the reads of
+      //  cand[], and the one behind them, ahead of the next pass's zeroing -- keep all three when editing)
+      U* const cand = reinterpret_cast<U*>(hist);
+      int mine = 0;
+#pragma unroll
+      for (int c = 0; c < kRowSelectChunks; ++c) mine += (rank && rl + 16 * c < n && (v[c] & mask) == prefix) ? 1 : 0;
+      int off = row_scan_incl_i32(mine) - mine;
+      if (rank) {
+#pragma unroll
+        for (int c = 0; c < kRowSelectChunks; ++c) if (rl + 16 * c < n && (v[c] & mask) == prefix) cand[off++] = v[c];
+      }
+      wave_lds_fence();
+      const bool holds = rank && rl < cnt;
+      const U me = holds ? cand[rl] : ONES;
+      int less = 0, leq = 0;
+      if (rank) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) if (j < cnt) { const U o = cand[j]; less += o < me ? 1 : 0; leq += o <= me ? 1 : 0; }
+      }
+      const U r = row_or_bits((holds && less <= k && k < leq) ? me : (U)0);
+      if (rank) { result = r; done = true; path = kRowSelectRank | (passes > 1 ? kRowSelectExtraPass : 0); }
+      wave_lds_fence();   // the histogram words are zeroed again by the next pass
+    }
+  }
+  return result;
+}
+
+// The select of the row kernels' four call sites: p[0..n) are the row's values (float / double / their patterns).  use_regs (wave-uniform)
+// and no active row of the wave above the cap: every lane fetches its values ONCE, all loads issued before the first wait, and
+// row_select_regs finishes from registers; otherwise the whole wave takes row_radix_select (rows share a program counter).
+template <int BITS, typename U, typename T>
+__device__ __forceinline__ U row_select(const T* p, int n, int k, bool active, bool use_regs, int* hist, int* sel, int& path) {
+  if (use_regs && !__any(active && n > kRowSelectCap)) {
+    const int rl = threadIdx.x & 15;
+    U v[kRowSelectChunks];
+#pragma unroll
+    for (int c = 0; c < kRowSelectChunks; ++c) { v[c] = ~(U)0; if (active && rl + 16 * c < n) v[c] = po_bits(p[rl + 16 * c]); }
+    return row_select_regs<BITS, U>(v, n, k, active, hist, path);
+  }
+  path = active ? kRowSelectFallback : 0;
+  return row_radix_select<BITS, U>([&](int i) { return (U)po_bits(p[i]); }, n, k, active, hist, sel);
 }
 
 // H x = rhs for a symmetric 6x6 H by ONE LANE: the arithmetic of wave_solve6_core (Gauss-Jordan in the pivot order of Eigen's LDLT, the
@@ -721,7 +857,7 @@ __device__ __forceinline__ void rows_gn_loop(const PoseBatchDev& b, const PoseJo
   }
 }
 
-__global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_opt_rows_kernel(PoseBatchDev b, double* poses) {
+__global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_opt_rows_kernel(PoseBatchDev b, double* poses, int select) {
   __shared__ __align__(16) PoseRowLds s_rows[4];
   const int lane = threadIdx.x & 63, row = lane >> 4, rl = lane & 15;
   const int job_raw = blockIdx.x * 4 + row;
@@ -772,8 +908,9 @@ __global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_opt_rows_kernel(Pos
   // MAD scale = 1.48f * median (float).  Zero points: the reference is undefined (:70); we define 1.0.
   double scale_pt = 1.0, scale_ls = 1.0;
   {
-    const uint32_t m_pt = row_radix_select<32, uint32_t>([&](int i) { return (uint32_t)__float_as_uint(errs[i]); }, np, np / 2, row_on && np > 0, L.hist, L.sel);
-    const uint32_t m_ls = row_radix_select<32, uint32_t>([&](int i) { return (uint32_t)__float_as_uint(errs[np + i]); }, ns, ns / 2, row_on && ns > 0, L.hist, L.sel);
+    int path;
+    const uint32_t m_pt = row_select<32, uint32_t>(errs, np, np / 2, row_on && np > 0, select != 0, L.hist, L.sel, path);
+    const uint32_t m_ls = row_select<32, uint32_t>(errs + np, ns, ns / 2, row_on && ns > 0, select != 0, L.hist, L.sel, path);
     if (np > 0) scale_pt = (double)__fmul_rn(1.48f, __uint_as_float(m_pt));
     if (ns > 0) scale_ls = (double)__fmul_rn(1.48f, __uint_as_float(m_ls));
   }
@@ -817,10 +954,9 @@ __global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_opt_rows_kernel(Pos
   wave_lds_fence();
 
   // ---- medians :244-249 ----
-  const unsigned long long mi = row_radix_select<64, unsigned long long>([&](int i) { return (unsigned long long)__double_as_longlong(vec[i]); },
-                                                                         (job.n_iter_ref > 0) ? 2 * nf : nf, n_init / 2, row_on && n_init > 0, L.hist, L.sel);   // unwritten refinement entries hold +inf and sort last
-  const unsigned long long mf = row_radix_select<64, unsigned long long>([&](int i) { return (unsigned long long)__double_as_longlong(vec[2 * nf + i]); },
-                                                                         nf, nf / 2, row_on, L.hist, L.sel);
+  int path;
+  const unsigned long long mi = row_select<64, unsigned long long>(vec, (job.n_iter_ref > 0) ? 2 * nf : nf, n_init / 2, row_on && n_init > 0, select != 0, L.hist, L.sel, path);   // unwritten refinement entries hold +inf and sort last
+  const unsigned long long mf = row_select<64, unsigned long long>(vec + 2 * nf, nf, nf / 2, row_on, select != 0, L.hist, L.sel, path);
   if (row_on && rl == 0) {
     for (int k = 0; k < 7; ++k) st->T[k] = L.pose[12 + k];
     if (poses) for (int k = 0; k < 7; ++k) poses[7 * job_id + k] = L.pose[12 + k];
@@ -868,7 +1004,7 @@ __device__ __forceinline__ void quat_to_matrix_rows(const Quat& q, double* R) {
 }
 #endif
 
-__global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_refill_prologue_kernel(PoseBatchDev b, PoseRefillDev q, double* poses) {
+__global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_refill_prologue_kernel(PoseBatchDev b, PoseRefillDev q, double* poses, int select) {
   __shared__ __align__(16) PoseRowLds s_rows[4];
   const int lane = threadIdx.x & 63, row = lane >> 4, rl = lane & 15;
   const int job_raw = blockIdx.x * 4 + row;
@@ -912,8 +1048,9 @@ __global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_refill_prologue_ker
   wave_lds_fence();
   double scale_pt = 1.0, scale_ls = 1.0;
   {
-    const uint32_t m_pt = row_radix_select<32, uint32_t>([&](int i) { return (uint32_t)__float_as_uint(errs[i]); }, np, np / 2, row_on && np > 0, L.hist, L.sel);
-    const uint32_t m_ls = row_radix_select<32, uint32_t>([&](int i) { return (uint32_t)__float_as_uint(errs[np + i]); }, ns, ns / 2, row_on && ns > 0, L.hist, L.sel);
+    int path;
+    const uint32_t m_pt = row_select<32, uint32_t>(errs, np, np / 2, row_on && np > 0, select != 0, L.hist, L.sel, path);
+    const uint32_t m_ls = row_select<32, uint32_t>(errs + np, ns, ns / 2, row_on && ns > 0, select != 0, L.hist, L.sel, path);
     if (np > 0) scale_pt = (double)__fmul_rn(1.48f, __uint_as_float(m_pt));
     if (ns > 0) scale_ls = (double)__fmul_rn(1.48f, __uint_as_float(m_ls));
   }
@@ -1015,7 +1152,7 @@ __global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_refill_gn_kernel(Po
   }
 }
 
-__global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_refill_epilogue_kernel(PoseBatchDev b, PoseRefillDev q, double* poses) {
+__global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_refill_epilogue_kernel(PoseBatchDev b, PoseRefillDev q, double* poses, int select) {
   __shared__ __align__(16) PoseRowLds s_rows[4];
   const int lane = threadIdx.x & 63, row = lane >> 4, rl = lane & 15;
   const int job_raw = blockIdx.x * 4 + row;
@@ -1065,10 +1202,9 @@ __global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_refill_epilogue_ker
 
   // ---- medians :244-249 ----
   const int n_init = job.n_iter > 0 ? nf : 0;
-  const unsigned long long mi = row_radix_select<64, unsigned long long>([&](int i) { return (unsigned long long)__double_as_longlong(vec[i]); },
-                                                                         nf, n_init / 2, row_on && n_init > 0, L.hist, L.sel);
-  const unsigned long long mf = row_radix_select<64, unsigned long long>([&](int i) { return (unsigned long long)__double_as_longlong(vec[2 * nf + i]); },
-                                                                         nf, nf / 2, row_on, L.hist, L.sel);
+  int path;
+  const unsigned long long mi = row_select<64, unsigned long long>(vec, nf, n_init / 2, row_on && n_init > 0, select != 0, L.hist, L.sel, path);
+  const unsigned long long mf = row_select<64, unsigned long long>(vec + 2 * nf, nf, nf / 2, row_on, select != 0, L.hist, L.sel, path);
   if (row_on && rl == 0) {
     for (int k = 0; k < 7; ++k) st->T[k] = L.pose[12 + k];
     if (poses) for (int k = 0; k < 7; ++k) poses[7 * job_id + k] = L.pose[12 + k];
@@ -1091,18 +1227,44 @@ bool pose_opt_refill_built() {
 #endif
 }
 
-hipError_t launch_pose_opt_refill(const PoseBatchDev& b, const PoseRefillDev& q, double* d_poses, int gn_grid, hipStream_t stream) {
+hipError_t launch_pose_opt_refill(const PoseBatchDev& b, const PoseRefillDev& q, double* d_poses, int gn_grid, int select, hipStream_t stream) {
   const int wgs = (b.n_jobs + 3) / 4;
   if (gn_grid < 1 || gn_grid > wgs) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(pose_refill_prologue_kernel, dim3(wgs), dim3(64), 0, stream, b, q, d_poses);
+  hipLaunchKernelGGL(pose_refill_prologue_kernel, dim3(wgs), dim3(64), 0, stream, b, q, d_poses, select);
   hipLaunchKernelGGL(pose_refill_gn_kernel, dim3(gn_grid), dim3(64), 0, stream, b, q);
-  hipLaunchKernelGGL(pose_refill_epilogue_kernel, dim3(wgs), dim3(64), 0, stream, b, q, d_poses);
+  hipLaunchKernelGGL(pose_refill_epilogue_kernel, dim3(wgs), dim3(64), 0, stream, b, q, d_poses, select);
   return hipGetLastError();
 }
 
-hipError_t launch_pose_opt(const PoseBatchDev& b, double* d_poses, int threads, hipStream_t stream) {
+// plsvo_poseopt_row_select (tests): row_select -- the function of the three row kernels above -- on rows of patterns, four rows per workgroup
+struct RowSelectLds { int hist[PO_BINS]; int sel[8]; };
+template <int BITS, typename U>
+__global__ __launch_bounds__(64) void pose_row_select_kernel(RowSelectDev t) {
+  __shared__ __align__(16) RowSelectLds s_rows[4];
+  const int lane = threadIdx.x & 63, rl = lane & 15;
+  const int row_raw = blockIdx.x * 4 + (lane >> 4);
+  const bool valid = row_raw < t.n_rows;
+  const int row = valid ? row_raw : t.n_rows - 1;
+  const int n = t.row_n[row];
+  RowSelectLds& L = s_rows[lane >> 4];
+  int path;
+  const U r = row_select<BITS, U>(reinterpret_cast<const U*>(t.patterns) + t.row_off[row], n, t.row_k[row], valid && t.row_active[row] != 0 && n > 0,
+                                  t.select != 0, L.hist, L.sel, path);
+  if (valid && rl == 0) { reinterpret_cast<U*>(t.selected)[row] = r; t.path[row] = path; }
+}
+
+hipError_t launch_pose_row_select(const RowSelectDev& t, hipStream_t stream) {
+  if (t.n_rows < 1) return hipErrorInvalidValue;
+  const dim3 grid((t.n_rows + 3) / 4);
+  if (t.bits == 32) hipLaunchKernelGGL((pose_row_select_kernel<32, uint32_t>), grid, dim3(64), 0, stream, t);
+  else if (t.bits == 64) hipLaunchKernelGGL((pose_row_select_kernel<64, unsigned long long>), grid, dim3(64), 0, stream, t);
+  else return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+hipError_t launch_pose_opt(const PoseBatchDev& b, double* d_poses, int threads, int select, hipStream_t stream) {
   switch (threads) {
-    case 16: hipLaunchKernelGGL(pose_opt_rows_kernel, dim3((b.n_jobs + 3) / 4), dim3(64), 0, stream, b, d_poses); break;   // a 16-lane row per frame
+    case 16: hipLaunchKernelGGL(pose_opt_rows_kernel, dim3((b.n_jobs + 3) / 4), dim3(64), 0, stream, b, d_poses, select); break;   // a 16-lane row per frame
     case 64: hipLaunchKernelGGL((pose_opt_kernel<64>), dim3(b.n_jobs), dim3(64), 0, stream, b, d_poses); break;
     case 256: hipLaunchKernelGGL((pose_opt_kernel<256>), dim3(b.n_jobs), dim3(256), 0, stream, b, d_poses); break;
     case 512: hipLaunchKernelGGL((pose_opt_kernel<512>), dim3(b.n_jobs), dim3(512), 0, stream, b, d_poses); break;

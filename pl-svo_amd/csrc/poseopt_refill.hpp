@@ -22,7 +22,8 @@ struct PoseRefillDev {
 
 // false in a -DPLSVO_TIMING build (the three kernels carry no phase ticks)
 bool pose_opt_refill_built();
-// prologue (4 frames per workgroup), Gauss-Newton kernel (gn_grid persistent workgroups), epilogue, back to back on `stream`
-hipError_t launch_pose_opt_refill(const PoseBatchDev& b, const PoseRefillDev& q, double* d_poses, int gn_grid, hipStream_t stream);
+// prologue (4 frames per workgroup), Gauss-Newton kernel (gn_grid persistent workgroups), epilogue, back to back on `stream`;
+// select: 1 = the medians of prologue and epilogue finish from registers (poseopt_select.hpp), 0 = row_radix_select everywhere
+hipError_t launch_pose_opt_refill(const PoseBatchDev& b, const PoseRefillDev& q, double* d_poses, int gn_grid, int select, hipStream_t stream);
 
 }  // namespace plsvo_hip

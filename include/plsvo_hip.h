@@ -637,6 +637,83 @@ int plsvo_chain_fetch(plsvo_ctx* ctx, int n, plsvo_chain_out* out);
 int plsvo_frame_step_batch(plsvo_ctx* ctx, int n, const plsvo_chain_in* in, const plsvo_chain_params* params, plsvo_chain_out* out);
 const double* plsvo_chain_poses_dev(plsvo_ctx* ctx);   /* n*7 doubles: the optimised T_f_w of the staged streams, on the device */
 
+/* ------------------------------------------------------------------------------------------ */
+/* keyframe stage: what FrameHandlerMono::processFrame decides between "pose optimised" and    */
+/* "detect corners, start seeds" (src/frame_handler_mono.cpp:351-358, :396) and the head of    */
+/* Reprojector::reprojectMap (src/reprojector.cpp:147-163), for a batch of independent streams */
+/* (one wave per stream).  Synchronous; host arrays unless named d_.           */
+/* ------------------------------------------------------------------------------------------ */
+
+/* Map::getCloseKeyframes (src/map.cpp:158-179) followed by the sort and the cut of reprojectMap (:147-163).
+ * The keyframe table of a stream: kf_T = Frame::T_f_w_ of every keyframe, keypt_pos = key_pts_[k]->feat3D->pos_ (world) of its five
+ * key points, keypt_valid = 0 where key_pts_[k] is NULL.  A keyframe is close when one valid key point passes Frame::isVisible
+ * (src/frame.cpp:156-165) in the frame with pose T_f_w; its distance is |T_f_w.translation() - kf.T_f_w.translation()| -- the
+ * translations of the poses, not the camera centres, as in the reference. */
+typedef struct plsvo_close_kf_in {
+  plsvo_pinhole cam;                /* frame->cam_ */
+  double T_f_w[7];                  /* the new frame's pose after alignment */
+  int32_t n_kf;                     /* keyframes in the table */
+  int32_t max_n_kfs;                /* Reprojector::Options::max_n_kfs (10) */
+  const double* kf_T;               /* 7*n_kf */
+  const double* keypt_pos;          /* 15*n_kf */
+  const uint8_t* keypt_valid;       /* 5*n_kf */
+} plsvo_close_kf_in;
+
+typedef struct plsvo_close_kf_out {
+  int32_t n_close;                  /* keyframes with an overlapping field of view */
+  int32_t n_overlap;                /* min(n_close, max_n_kfs): the first n_overlap entries are the reference's overlap_kfs */
+  int32_t* close_idx;               /* caller buffers of n_kf entries or NULL: the first n_close filled, ascending by distance, */
+  double* close_dist;               /*   equal distances in table order (std::list::sort is stable) */
+} plsvo_close_kf_out;
+
+/* n streams.  PLSVO_E_INVALID (nothing written) for n < 0, a NULL in / out with n > 0, a negative n_kf or max_n_kfs, or a NULL table
+ * array with n_kf > 0.  Finite inputs are a precondition. */
+int plsvo_close_keyframes(plsvo_ctx* ctx, int n, const plsvo_close_kf_in* in, plsvo_close_kf_out* out);
+
+/* One stream's frame after pose optimisation:
+ *   frame_utils::getSceneDepth (src/frame.cpp:182-217) -> has_depth, depth_mean (vk::getMedian: the element of rank m/2), depth_min
+ *   FrameHandlerMono::needNewKf (src/frame_handler_mono.cpp:475-499) over the overlap keyframes -> need_new_kf, blocking, delta_t/r
+ *   Frame::setKeyPoints / checkKeyPoints (src/frame.cpp:87-141) -> key_pts
+ *   Map::getFurthestKeyframe(new_frame->pos()) (src/map.cpp:201-214) -> furthest_kf
+ * Features: pt_px = Feature::px, pt_pos = feat3D->pos_, pt_alive = 0 where feat3D is NULL (NULL array = all alive); segments alike. */
+typedef struct plsvo_kf_decide_in {
+  plsvo_pinhole cam;                /* only width and height are read (cu = width/2, cv = height/2) */
+  double T_new_w[7];                /* new_frame_->T_f_w_ after pose optimisation */
+  const double* d_T_new;            /* NULL, or a DEVICE pointer to 7 doubles read instead of T_new_w (plsvo_chain_poses_dev(ctx) + 7*i) */
+  double T_last_w[7];               /* last_frame_->T_f_w_: the PREVIOUS frame's pose, which needNewKf measures from */
+  double kfselect_mindist_t;        /* Config::kfSelectMinDistT() (0.06, src/config.cpp:112) */
+  double kfselect_mindist_r;        /* Config::kfSelectMinDistR() (3.0 degrees of 3.1416, src/config.cpp:113) */
+  int32_t n_pt, n_seg;
+  int32_t n_kf, n_overlap;
+  const double* pt_px;              /* 2*n_pt */
+  const double* pt_pos;             /* 3*n_pt */
+  const uint8_t* pt_alive;          /* n_pt or NULL */
+  const double* seg_spos;           /* 3*n_seg */
+  const double* seg_epos;           /* 3*n_seg */
+  const uint8_t* seg_alive;         /* n_seg or NULL */
+  const double* kf_T;               /* 7*n_kf: the keyframe table of plsvo_close_kf_in */
+  const int32_t* overlap_idx;       /* n_overlap indices into it, in order (plsvo_close_kf_out.close_idx) */
+  int32_t key_pts_prev[5];          /* key_pts_ on entry: indices into the points, -1 = NULL */
+  int32_t reserved0;
+} plsvo_kf_decide_in;
+
+typedef struct plsvo_kf_decide_out {
+  double depth_mean;                /* 0 when has_depth == 0 (the reference leaves its argument untouched) */
+  double depth_min;                 /* DBL_MAX when has_depth == 0; of zeros of both signs the negative one */
+  int32_t has_depth;                /* getSceneDepth's return value */
+  int32_t n_depth;                  /* depth_vec.size(): alive points + 2 * alive segments */
+  int32_t need_new_kf;              /* needNewKf's return value */
+  int32_t blocking;                 /* position in overlap_idx of the first keyframe closer than both thresholds, -1 = none */
+  int32_t key_pts[5];               /* key_pts_ on exit (indices, -1 = NULL) */
+  int32_t furthest_kf;              /* index into the table, -1 when no keyframe is further than 0 */
+  double* delta_t;                  /* caller buffers of n_overlap entries or NULL: |log(T_last^-1 * T_kf)[0:3]| and */
+  double* delta_r;                  /*   |log(..)[3:6]| * 180.0 / 3.1416 of EVERY overlap keyframe (diagnostic) */
+} plsvo_kf_decide_out;
+
+/* n streams.  PLSVO_E_INVALID (nothing written) for n < 0, a NULL in / out with n > 0, a negative count, a NULL array with a
+ * non-zero count (the alive arrays excepted), an overlap index outside the table or a key_pts_prev entry outside -1 .. n_pt-1. */
+int plsvo_keyframe_decide(plsvo_ctx* ctx, int n, const plsvo_kf_decide_in* in, plsvo_kf_decide_out* out);
+
 /* TUM-style trajectory record of a frame (app/run_pipeline.cpp:425-451): the camera pose in the world,
  * T_f_w^-1, as tx ty tz qx qy qz qw.  Returns 1 and fills out7 when the reference would write the line, 0 when
  * it skips the frame (a covariance entry outside (1e-16, 1e16), or an exactly-identity pose).  Host-only helper:
@@ -763,7 +840,8 @@ int plsvo_gather_poses(plsvo_ctx* ctx, void* rccl_comm, const plsvo_pose_record*
 #define PLSVO_K_STRUCTOPT     4
 #define PLSVO_K_MATCH         5
 #define PLSVO_K_SEEDS         6
-#define PLSVO_K_COUNT         7
+#define PLSVO_K_KEYFRAME      7   /* plsvo_close_keyframes / plsvo_keyframe_decide: the launch alone, without packing and copies */
+#define PLSVO_K_COUNT         8
 int plsvo_hip_set_profiling(plsvo_ctx* ctx, int enable);
 /* accumulated GPU time and launch count of kernel family k since the last reset (synchronises) */
 int plsvo_hip_kernel_time(plsvo_ctx* ctx, int k, double* total_ms, int64_t* launches);

@@ -18,7 +18,7 @@ c_i32_p = C.POINTER(C.c_int32)
 OK, E_INVALID, E_NODEVICE, E_HIP, E_CAPACITY, E_STATE, E_RCCL = 0, -1, -2, -3, -4, -5, -6
 
 # kernel families for plsvo_hip_kernel_time
-K_ALIGN_INIT, K_ALIGN_LEVEL, K_POSEOPT, K_HALFSAMPLE, K_STRUCTOPT, K_MATCH, K_SEEDS, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7
+K_ALIGN_INIT, K_ALIGN_LEVEL, K_POSEOPT, K_HALFSAMPLE, K_STRUCTOPT, K_MATCH, K_SEEDS, K_KEYFRAME, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8
 SEED_NOT_VISIBLE, SEED_NO_MATCH, SEED_UPDATED, SEED_CONVERGED, SEED_NAN = 0, 1, 2, 3, 4
 FTR_CORNER, FTR_EDGELET = 0, 1
 
@@ -157,6 +157,34 @@ class ChainParams(C.Structure):
 class ChainOut(C.Structure):
     _fields_ = [("align", AlignOut), ("pose", PoseOptOut), ("n_sel_pt", C.c_int32), ("n_sel_seg", C.c_int32),
                 ("found", c_u8_p), ("px", c_double_p), ("search_level", c_i32_p), ("sel_pt", c_i32_p), ("sel_seg", c_i32_p)]
+
+
+class CloseKfIn(C.Structure):
+    """plsvo_close_kf_in"""
+    _fields_ = [("cam", Pinhole), ("T_f_w", C.c_double * 7), ("n_kf", C.c_int32), ("max_n_kfs", C.c_int32),
+                ("kf_T", c_double_p), ("keypt_pos", c_double_p), ("keypt_valid", c_u8_p)]
+
+
+class CloseKfOut(C.Structure):
+    """plsvo_close_kf_out"""
+    _fields_ = [("n_close", C.c_int32), ("n_overlap", C.c_int32), ("close_idx", c_i32_p), ("close_dist", c_double_p)]
+
+
+class KfDecideIn(C.Structure):
+    """plsvo_kf_decide_in"""
+    _fields_ = [("cam", Pinhole), ("T_new_w", C.c_double * 7), ("d_T_new", C.c_void_p), ("T_last_w", C.c_double * 7),
+                ("kfselect_mindist_t", C.c_double), ("kfselect_mindist_r", C.c_double),
+                ("n_pt", C.c_int32), ("n_seg", C.c_int32), ("n_kf", C.c_int32), ("n_overlap", C.c_int32),
+                ("pt_px", c_double_p), ("pt_pos", c_double_p), ("pt_alive", c_u8_p), ("seg_spos", c_double_p), ("seg_epos", c_double_p),
+                ("seg_alive", c_u8_p), ("kf_T", c_double_p), ("overlap_idx", c_i32_p), ("key_pts_prev", C.c_int32 * 5),
+                ("reserved0", C.c_int32)]
+
+
+class KfDecideOut(C.Structure):
+    """plsvo_kf_decide_out"""
+    _fields_ = [("depth_mean", C.c_double), ("depth_min", C.c_double), ("has_depth", C.c_int32), ("n_depth", C.c_int32),
+                ("need_new_kf", C.c_int32), ("blocking", C.c_int32), ("key_pts", C.c_int32 * 5), ("furthest_kf", C.c_int32),
+                ("delta_t", c_double_p), ("delta_r", c_double_p)]
 
 
 class PoseRecord(C.Structure):
@@ -424,6 +452,60 @@ class ReprojectJob:
 
     def trim(self, bufs):
         return {k: v[:self.n].copy() for k, v in bufs.items()}
+
+
+class CloseKeyframesJob:
+    """One stream of plsvo_close_keyframes: the new frame's pose and the stream's keyframe table; owns the buffers.
+    keypt_pos [n_kf, 5, 3] world positions of the keyframes' key points, keypt_valid [n_kf, 5] (0 = key_pts_[k] is NULL)."""
+
+    def __init__(self, cam, T_f_w, kf_T, keypt_pos, keypt_valid, max_n_kfs=10):
+        self.kf_T = _f64(kf_T).reshape(-1, 7)
+        self.n_kf = self.kf_T.shape[0]
+        self.keypt_pos = _f64(keypt_pos, 15 * self.n_kf).reshape(-1, 5, 3)
+        self.keypt_valid = np.ascontiguousarray(np.asarray(keypt_valid).reshape(-1, 5) != 0, dtype=np.uint8)
+        if self.keypt_valid.shape[0] != self.n_kf:
+            raise ValueError("keypt_valid: five flags per keyframe")
+        c = CloseKfIn()
+        c.cam = cam if isinstance(cam, Pinhole) else Pinhole(*cam)
+        c.T_f_w = (C.c_double * 7)(*_f64(T_f_w, 7))
+        c.n_kf, c.max_n_kfs = self.n_kf, int(max_n_kfs)
+        c.kf_T, c.keypt_pos, c.keypt_valid = _ptr(self.kf_T, c_double_p), _ptr(self.keypt_pos, c_double_p), _ptr(self.keypt_valid, c_u8_p)
+        self.c = c
+
+
+class KeyframeDecideJob:
+    """One stream of plsvo_keyframe_decide: the frame's poses and features, the keyframe table and the overlap list; owns the buffers.
+    pt_alive / seg_alive: None = every feature has its landmark.  key_pts_prev: five point indices, -1 = none."""
+
+    def __init__(self, cam, T_new_w, T_last_w, pt_px, pt_pos, pt_alive=None, seg_spos=(), seg_epos=(), seg_alive=None, kf_T=(), overlap_idx=(),
+                 key_pts_prev=(-1, -1, -1, -1, -1), mindist_t=0.06, mindist_r=3.0):
+        self.pt_px = _f64(pt_px).reshape(-1, 2)
+        self.n_pt = self.pt_px.shape[0]
+        self.pt_pos = _f64(pt_pos, 3 * self.n_pt).reshape(-1, 3)
+        self.seg_spos = _f64(seg_spos).reshape(-1, 3)
+        self.n_seg = self.seg_spos.shape[0]
+        self.seg_epos = _f64(seg_epos, 3 * self.n_seg).reshape(-1, 3)
+        self.pt_alive = None if pt_alive is None else np.ascontiguousarray(np.asarray(pt_alive).reshape(-1) != 0, dtype=np.uint8)
+        self.seg_alive = None if seg_alive is None else np.ascontiguousarray(np.asarray(seg_alive).reshape(-1) != 0, dtype=np.uint8)
+        if (self.pt_alive is not None and self.pt_alive.size != self.n_pt) or (self.seg_alive is not None and self.seg_alive.size != self.n_seg):
+            raise ValueError("alive flags: one per feature")
+        self.kf_T = _f64(kf_T).reshape(-1, 7)
+        self.overlap_idx = np.ascontiguousarray(overlap_idx, dtype=np.int32).reshape(-1)
+        self.n_overlap = self.overlap_idx.size
+        c = KfDecideIn()
+        c.cam = cam if isinstance(cam, Pinhole) else Pinhole(*cam)
+        c.T_new_w = (C.c_double * 7)(*_f64(T_new_w, 7))
+        c.T_last_w = (C.c_double * 7)(*_f64(T_last_w, 7))
+        c.d_T_new = None
+        c.kfselect_mindist_t, c.kfselect_mindist_r = float(mindist_t), float(mindist_r)
+        c.n_pt, c.n_seg, c.n_kf, c.n_overlap = self.n_pt, self.n_seg, self.kf_T.shape[0], self.n_overlap
+        c.pt_px, c.pt_pos = _ptr(self.pt_px, c_double_p), _ptr(self.pt_pos, c_double_p)
+        c.pt_alive = C.cast(None, c_u8_p) if self.pt_alive is None else _ptr(self.pt_alive, c_u8_p)
+        c.seg_spos, c.seg_epos = _ptr(self.seg_spos, c_double_p), _ptr(self.seg_epos, c_double_p)
+        c.seg_alive = C.cast(None, c_u8_p) if self.seg_alive is None else _ptr(self.seg_alive, c_u8_p)
+        c.kf_T, c.overlap_idx = _ptr(self.kf_T, c_double_p), _ptr(self.overlap_idx, c_i32_p)
+        c.key_pts_prev = (C.c_int32 * 5)(*[int(v) for v in key_pts_prev])
+        self.c = c
 
 
 class SeedsJob:

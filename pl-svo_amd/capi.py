@@ -26,6 +26,7 @@ SYMBOLS = [
     "plsvo_pose_optimize", "plsvo_pose_optimize_batch", "plsvo_poseopt_stage", "plsvo_poseopt_run", "plsvo_poseopt_fetch",
     "plsvo_poseopt_set_trace", "plsvo_poseopt_fetch_trace", "plsvo_poseopt_poses_dev", "plsvo_poseopt_copy_poses", "plsvo_poseopt_work", "plsvo_poseopt_refill_frames", "plsvo_poseopt_row_select",
     "plsvo_structure_optimize", "plsvo_match_direct", "plsvo_match_warp_patches", "plsvo_reproject", "plsvo_trajectory_record", "plsvo_update_seeds",
+    "plsvo_close_keyframes", "plsvo_keyframe_decide",
     "plsvo_chain_stage", "plsvo_chain_run", "plsvo_chain_fetch", "plsvo_frame_step_batch", "plsvo_chain_poses_dev",
     "plsvo_pack_pose_records", "plsvo_fetch_pose_records", "plsvo_gather_poses",
     "plsvo_hip_set_profiling", "plsvo_hip_kernel_time", "plsvo_hip_reset_profiling",
@@ -138,6 +139,8 @@ def lib():
         "plsvo_match_direct": (C.c_int, [ctxp, C.POINTER(abi.MatchIn), C.POINTER(abi.MatchOut)]),
         "plsvo_match_warp_patches": (C.c_int, [ctxp, C.POINTER(abi.MatchIn), C.POINTER(abi.MatchWarpOut)]),
         "plsvo_reproject": (C.c_int, [ctxp, C.POINTER(abi.ReprojectIn), C.POINTER(abi.ReprojectOut)]),
+        "plsvo_close_keyframes": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CloseKfIn), C.POINTER(abi.CloseKfOut)]),
+        "plsvo_keyframe_decide": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.KfDecideIn), C.POINTER(abi.KfDecideOut)]),
         "plsvo_update_seeds": (C.c_int, [ctxp, C.POINTER(abi.SeedsIn), C.POINTER(abi.SeedsOut)]),
         "plsvo_trajectory_record": (C.c_int, [abi.c_double_p, abi.c_double_p, abi.c_double_p]),
         "plsvo_chain_stage": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.ChainIn), C.POINTER(abi.ChainParams)]),
@@ -548,6 +551,39 @@ class Context:
 
     def chain_poses_dev(self):
         return self.L.plsvo_chain_poses_dev(self.h)
+
+    # ---- keyframe stage ----
+    def close_keyframes(self, jobs):
+        """plsvo_close_keyframes: per stream (abi.CloseKeyframesJob) a dict of n_close, n_overlap, close_idx [n_close] (ascending by
+        distance, equal distances in table order) and close_dist [n_close]; the first n_overlap entries are the overlap keyframes"""
+        n = len(jobs)
+        ins = (abi.CloseKfIn * max(n, 1))(*[j.c for j in jobs])
+        outs = (abi.CloseKfOut * max(n, 1))()
+        bufs = [(np.full(max(j.n_kf, 1), -1, np.int32), np.zeros(max(j.n_kf, 1))) for j in jobs]
+        for o, (bi, bd) in zip(outs, bufs):
+            o.close_idx, o.close_dist = bi.ctypes.data_as(abi.c_i32_p), bd.ctypes.data_as(abi.c_double_p)
+        self._chk(self.L.plsvo_close_keyframes(self.h, n, ins, outs))
+        return [dict(n_close=int(o.n_close), n_overlap=int(o.n_overlap), close_idx=bi[:o.n_close].copy(), close_dist=bd[:o.n_close].copy())
+                for o, (bi, bd) in zip(outs[:n], bufs)]
+
+    def keyframe_decide(self, jobs, poses_dev=None):
+        """plsvo_keyframe_decide: per stream (abi.KeyframeDecideJob) a dict of has_depth, n_depth, depth_mean, depth_min, need_new_kf,
+        blocking, delta_t / delta_r [n_overlap], key_pts [5] and furthest_kf.  poses_dev: a device pointer to len(jobs) * 7 doubles
+        (e.g. chain_poses_dev()) whose i-th pose is read instead of job i's T_new_w"""
+        n = len(jobs)
+        ins = (abi.KfDecideIn * max(n, 1))(*[j.c for j in jobs])
+        if poses_dev is not None:
+            for i in range(n):
+                ins[i].d_T_new = int(poses_dev) + 56 * i
+        outs = (abi.KfDecideOut * max(n, 1))()
+        bufs = [(np.zeros(max(j.n_overlap, 1)), np.zeros(max(j.n_overlap, 1))) for j in jobs]
+        for o, (bt, br) in zip(outs, bufs):
+            o.delta_t, o.delta_r = bt.ctypes.data_as(abi.c_double_p), br.ctypes.data_as(abi.c_double_p)
+        self._chk(self.L.plsvo_keyframe_decide(self.h, n, ins, outs))
+        return [dict(has_depth=int(o.has_depth), n_depth=int(o.n_depth), depth_mean=float(o.depth_mean), depth_min=float(o.depth_min),
+                     need_new_kf=int(o.need_new_kf), blocking=int(o.blocking), delta_t=bt[:j.n_overlap].copy(), delta_r=br[:j.n_overlap].copy(),
+                     key_pts=np.array(list(o.key_pts), np.int32), furthest_kf=int(o.furthest_kf))
+                for o, j, (bt, br) in zip(outs[:n], jobs, bufs)]
 
     # ---- structure optimisation ----
     def structure_optimize(self, job):

@@ -33,6 +33,8 @@ hipError_t launch_match_direct(const MatchBatchDev& b, hipStream_t stream);
 hipError_t launch_match_warp_patches(const MatchBatchDev& b, hipStream_t stream);
 hipError_t launch_reproject(const ReprojBatchDev& b, hipStream_t stream);
 hipError_t launch_update_seeds(const SeedsBatchDev& b, hipStream_t stream);
+hipError_t launch_close_keyframes(const CloseKfBatchDev& b, hipStream_t stream);     // keyframe_device.hpp, in seeds_kernels.hip
+hipError_t launch_keyframe_decide(const KfDecideBatchDev& b, hipStream_t stream);
 hipError_t launch_halfsample(const uint8_t* src, size_t src_pitch, int in_w, int in_h, int in_stride, uint8_t* dst,
                              size_t dst_pitch, int n_slots, int rounding, hipStream_t stream);
 hipError_t launch_copy_level0(const uint8_t* src, size_t src_pitch, int w, int h, int stride, uint8_t* dst, size_t dst_pitch,
@@ -82,6 +84,13 @@ struct Blob {
     if (!v.empty()) memcpy(host.data() + off, v.data(), v.size() * sizeof(T));
     return off;
   }
+  // a section of n elements to be filled in place: take the pointers (at<T>) only after the LAST reserve / add, which may move the blob
+  template <typename T> size_t reserve(size_t n) {
+    const size_t off = (host.size() + 255) & ~(size_t)255;
+    host.resize(off + std::max(n * sizeof(T), (size_t)16));
+    return off;
+  }
+  template <typename T> T* at(size_t off) { return reinterpret_cast<T*>(host.data() + off); }
 };
 
 }  // namespace
@@ -1953,6 +1962,166 @@ struct Carver {
   template <typename T> size_t take(size_t n) { const size_t o = (off + 255) & ~(size_t)255; off = o + std::max(n, (size_t)1) * sizeof(T); return o; }
 };
 }  // namespace
+
+// ---- keyframe stage: close keyframes, scene depth, new-keyframe test, key points (keyframe_device.hpp) --------------------
+extern "C" int plsvo_close_keyframes(plsvo_ctx* c, int n, const plsvo_close_kf_in* in, plsvo_close_kf_out* out) {
+  CTX_CHECK(c);
+  if (n < 0 || (n > 0 && (!in || !out))) return fail(c, PLSVO_E_INVALID, "close_keyframes: bad arguments");
+  if (n == 0) return PLSVO_OK;
+  size_t total = 0;
+  for (int i = 0; i < n; ++i) {
+    if (in[i].n_kf < 0 || in[i].max_n_kfs < 0) return fail(c, PLSVO_E_INVALID, "close_keyframes: negative count");
+    if (in[i].n_kf > 0 && (!in[i].kf_T || !in[i].keypt_pos || !in[i].keypt_valid)) return fail(c, PLSVO_E_INVALID, "close_keyframes: null table array");
+    total += (size_t)in[i].n_kf;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  // the streams' tables are packed straight into the blob that travels (one pass over the caller's arrays)
+  Blob blob;
+  blob.host.reserve((size_t)n * sizeof(CloseKfJobDev) + total * (22 * sizeof(double) + 5) + 4 * 512);
+  const size_t o_jobs = blob.reserve<CloseKfJobDev>((size_t)n), o_T = blob.reserve<double>(total * 7), o_kp = blob.reserve<double>(total * 15),
+               o_kv = blob.reserve<uint8_t>(total * 5);
+  CloseKfJobDev* jobs = blob.at<CloseKfJobDev>(o_jobs);
+  double* kf_T = blob.at<double>(o_T); double* kp = blob.at<double>(o_kp); uint8_t* kv = blob.at<uint8_t>(o_kv);
+  size_t off = 0;
+  for (int i = 0; i < n; ++i) {
+    CloseKfJobDev& J = jobs[(size_t)i];
+    memcpy(J.T, in[i].T_f_w, sizeof(J.T));
+    J.fx = in[i].cam.fx; J.fy = in[i].cam.fy; J.cx = in[i].cam.cx; J.cy = in[i].cam.cy; J.width = in[i].cam.width; J.height = in[i].cam.height;
+    J.n_kf = in[i].n_kf; J.max_n_kfs = in[i].max_n_kfs; J.kf_off = (long long)off;
+    const size_t k = (size_t)in[i].n_kf;
+    if (k) {
+      memcpy(kf_T + off * 7, in[i].kf_T, k * 7 * sizeof(double));
+      memcpy(kp + off * 15, in[i].keypt_pos, k * 15 * sizeof(double));
+      memcpy(kv + off * 5, in[i].keypt_valid, k * 5);
+    }
+    off += k;
+  }
+  int rc;
+  if ((rc = upload_blob(c, c->s_d_in, blob))) return rc;
+  Carver cv;
+  const size_t o_tmp = cv.take<double>(total), o_idx = cv.take<int>(total), o_dist = cv.take<double>(total), o_cnt = cv.take<int>((size_t)n * 2);
+  HIP_TRY(c, c->s_d_out.ensure(cv.off + 256));
+  char* din = reinterpret_cast<char*>(c->s_d_in.p); char* dout = reinterpret_cast<char*>(c->s_d_out.p);
+  CloseKfBatchDev b{};
+  b.jobs = reinterpret_cast<const CloseKfJobDev*>(din + o_jobs); b.n_jobs = n;
+  b.kf_T = reinterpret_cast<const double*>(din + o_T); b.keypt_pos = reinterpret_cast<const double*>(din + o_kp);
+  b.keypt_valid = reinterpret_cast<const uint8_t*>(din + o_kv);
+  b.tmp_dist = reinterpret_cast<double*>(dout + o_tmp); b.close_idx = reinterpret_cast<int*>(dout + o_idx);
+  b.close_dist = reinterpret_cast<double*>(dout + o_dist); b.counts = reinterpret_cast<int*>(dout + o_cnt);
+  {
+    EventPair ep{}; prof_begin(c, PLSVO_K_KEYFRAME, &ep);
+    HIP_TRY(c, launch_close_keyframes(b, c->stream));
+    prof_end(c, PLSVO_K_KEYFRAME, &ep);
+  }
+  std::vector<char> h(cv.off);
+  HIP_TRY(c, hipMemcpyAsync(h.data(), dout, h.size(), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const int* h_idx = reinterpret_cast<const int*>(h.data() + o_idx); const double* h_dist = reinterpret_cast<const double*>(h.data() + o_dist);
+  const int* h_cnt = reinterpret_cast<const int*>(h.data() + o_cnt);
+  for (int i = 0; i < n; ++i) {
+    const size_t at = (size_t)blob.at<CloseKfJobDev>(o_jobs)[(size_t)i].kf_off;
+    const int nc = h_cnt[2 * i];
+    out[i].n_close = nc; out[i].n_overlap = h_cnt[2 * i + 1];
+    if (out[i].close_idx && nc > 0) memcpy(out[i].close_idx, h_idx + at, (size_t)nc * sizeof(int));
+    if (out[i].close_dist && nc > 0) memcpy(out[i].close_dist, h_dist + at, (size_t)nc * sizeof(double));
+  }
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_keyframe_decide(plsvo_ctx* c, int n, const plsvo_kf_decide_in* in, plsvo_kf_decide_out* out) {
+  CTX_CHECK(c);
+  if (n < 0 || (n > 0 && (!in || !out))) return fail(c, PLSVO_E_INVALID, "keyframe_decide: bad arguments");
+  if (n == 0) return PLSVO_OK;
+  size_t t_pt = 0, t_seg = 0, t_kf = 0, t_ov = 0;
+  for (int i = 0; i < n; ++i) {
+    const plsvo_kf_decide_in& I = in[i];
+    if (I.n_pt < 0 || I.n_seg < 0 || I.n_kf < 0 || I.n_overlap < 0) return fail(c, PLSVO_E_INVALID, "keyframe_decide: negative count");
+    if ((I.n_pt > 0 && (!I.pt_px || !I.pt_pos)) || (I.n_seg > 0 && (!I.seg_spos || !I.seg_epos)) || (I.n_kf > 0 && !I.kf_T) ||
+        (I.n_overlap > 0 && !I.overlap_idx))
+      return fail(c, PLSVO_E_INVALID, "keyframe_decide: null array with a non-zero count");
+    for (int k = 0; k < I.n_overlap; ++k)
+      if (I.overlap_idx[k] < 0 || I.overlap_idx[k] >= I.n_kf) return fail(c, PLSVO_E_INVALID, "keyframe_decide: overlap index outside the keyframe table");
+    for (int k = 0; k < 5; ++k)
+      if (I.key_pts_prev[k] < -1 || I.key_pts_prev[k] >= I.n_pt) return fail(c, PLSVO_E_INVALID, "keyframe_decide: key_pts_prev outside the points");
+    t_pt += (size_t)I.n_pt; t_seg += (size_t)I.n_seg; t_kf += (size_t)I.n_kf; t_ov += (size_t)I.n_overlap;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  // the streams' lists are packed straight into the blob that travels (one pass over the caller's arrays)
+  Blob blob;
+  blob.host.reserve((size_t)n * sizeof(KfDecideJobDev) + t_pt * (5 * sizeof(double) + 1) + t_seg * (6 * sizeof(double) + 1) + t_kf * 7 * sizeof(double) +
+                    t_ov * sizeof(int) + 9 * 512);
+  const size_t b_jobs = blob.reserve<KfDecideJobDev>((size_t)n), b_px = blob.reserve<double>(t_pt * 2), b_pos = blob.reserve<double>(t_pt * 3),
+               b_pa = blob.reserve<uint8_t>(t_pt), b_sp = blob.reserve<double>(t_seg * 3), b_ep = blob.reserve<double>(t_seg * 3),
+               b_sa = blob.reserve<uint8_t>(t_seg), b_kf = blob.reserve<double>(t_kf * 7), b_ov = blob.reserve<int>(t_ov);
+  KfDecideJobDev* jobs = blob.at<KfDecideJobDev>(b_jobs);
+  double* pt_px = blob.at<double>(b_px); double* pt_pos = blob.at<double>(b_pos); uint8_t* pa = blob.at<uint8_t>(b_pa);
+  double* sp = blob.at<double>(b_sp); double* ep = blob.at<double>(b_ep); uint8_t* sa = blob.at<uint8_t>(b_sa);
+  double* kf_T = blob.at<double>(b_kf); int* ov = blob.at<int>(b_ov);
+  size_t o_pt = 0, o_seg = 0, o_kf = 0, o_ov = 0, o_depth = 0;
+  for (int i = 0; i < n; ++i) {
+    const plsvo_kf_decide_in& I = in[i];
+    KfDecideJobDev& J = jobs[(size_t)i];
+    memcpy(J.T_new, I.T_new_w, sizeof(J.T_new)); memcpy(J.T_last, I.T_last_w, sizeof(J.T_last));
+    J.d_T_new = I.d_T_new; J.min_t = I.kfselect_mindist_t; J.min_r = I.kfselect_mindist_r;
+    J.width = I.cam.width; J.height = I.cam.height;
+    J.n_pt = I.n_pt; J.n_seg = I.n_seg; J.n_kf = I.n_kf; J.n_ov = I.n_overlap;
+    J.pt_off = (long long)o_pt; J.seg_off = (long long)o_seg; J.kf_off = (long long)o_kf; J.ov_off = (long long)o_ov; J.depth_off = (long long)o_depth;
+    for (int k = 0; k < 5; ++k) J.key_prev[k] = I.key_pts_prev[k];
+    J.reserved0 = 0;
+    const size_t np = (size_t)I.n_pt, ns = (size_t)I.n_seg, nk = (size_t)I.n_kf, no = (size_t)I.n_overlap;
+    if (np) {
+      memcpy(pt_px + o_pt * 2, I.pt_px, np * 2 * sizeof(double)); memcpy(pt_pos + o_pt * 3, I.pt_pos, np * 3 * sizeof(double));
+      if (I.pt_alive) for (size_t k = 0; k < np; ++k) pa[o_pt + k] = I.pt_alive[k] ? 1 : 0;
+      else memset(pa + o_pt, 1, np);
+    }
+    if (ns) {
+      memcpy(sp + o_seg * 3, I.seg_spos, ns * 3 * sizeof(double)); memcpy(ep + o_seg * 3, I.seg_epos, ns * 3 * sizeof(double));
+      if (I.seg_alive) for (size_t k = 0; k < ns; ++k) sa[o_seg + k] = I.seg_alive[k] ? 1 : 0;
+      else memset(sa + o_seg, 1, ns);
+    }
+    if (nk) memcpy(kf_T + o_kf * 7, I.kf_T, nk * 7 * sizeof(double));
+    if (no) memcpy(ov + o_ov, I.overlap_idx, no * sizeof(int));
+    o_pt += np; o_seg += ns; o_kf += nk; o_ov += no; o_depth += np + 2 * ns;
+  }
+  int rc;
+  if ((rc = upload_blob(c, c->s_d_in, blob))) return rc;
+  Carver cv;   // results first (what travels back), the depth rows behind them
+  const size_t r_out = cv.take<KfDecideOutDev>((size_t)n), r_dt = cv.take<double>(t_ov), r_dr = cv.take<double>(t_ov);
+  const size_t fetch_bytes = cv.off;
+  const size_t r_keys = cv.take<unsigned long long>(o_depth);
+  HIP_TRY(c, c->s_d_out.ensure(cv.off + 256));
+  char* din = reinterpret_cast<char*>(c->s_d_in.p); char* dout = reinterpret_cast<char*>(c->s_d_out.p);
+  KfDecideBatchDev b{};
+  b.jobs = reinterpret_cast<const KfDecideJobDev*>(din + b_jobs); b.out = reinterpret_cast<KfDecideOutDev*>(dout + r_out); b.n_jobs = n;
+  b.pt_px = reinterpret_cast<const double*>(din + b_px); b.pt_pos = reinterpret_cast<const double*>(din + b_pos);
+  b.pt_alive = reinterpret_cast<const uint8_t*>(din + b_pa);
+  b.seg_spos = reinterpret_cast<const double*>(din + b_sp); b.seg_epos = reinterpret_cast<const double*>(din + b_ep);
+  b.seg_alive = reinterpret_cast<const uint8_t*>(din + b_sa);
+  b.kf_T = reinterpret_cast<const double*>(din + b_kf); b.overlap_idx = reinterpret_cast<const int*>(din + b_ov);
+  b.depth_keys = reinterpret_cast<unsigned long long*>(dout + r_keys);
+  b.delta_t = reinterpret_cast<double*>(dout + r_dt); b.delta_r = reinterpret_cast<double*>(dout + r_dr);
+  {
+    EventPair ep{}; prof_begin(c, PLSVO_K_KEYFRAME, &ep);
+    HIP_TRY(c, launch_keyframe_decide(b, c->stream));
+    prof_end(c, PLSVO_K_KEYFRAME, &ep);
+  }
+  std::vector<char> h(fetch_bytes);
+  HIP_TRY(c, hipMemcpyAsync(h.data(), dout, h.size(), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const KfDecideOutDev* ho = reinterpret_cast<const KfDecideOutDev*>(h.data() + r_out);
+  const double* h_dt = reinterpret_cast<const double*>(h.data() + r_dt); const double* h_dr = reinterpret_cast<const double*>(h.data() + r_dr);
+  for (int i = 0; i < n; ++i) {
+    const KfDecideOutDev& o = ho[i];
+    plsvo_kf_decide_out& O = out[i];
+    O.depth_mean = o.depth_mean; O.depth_min = o.depth_min; O.has_depth = o.has_depth; O.n_depth = o.n_depth;
+    O.need_new_kf = o.need_new_kf; O.blocking = o.blocking; O.furthest_kf = o.furthest_kf;
+    for (int k = 0; k < 5; ++k) O.key_pts[k] = o.key_pts[k];
+    const size_t at = (size_t)blob.at<KfDecideJobDev>(b_jobs)[(size_t)i].ov_off, no = (size_t)in[i].n_overlap;
+    if (O.delta_t && no) memcpy(O.delta_t, h_dt + at, no * sizeof(double));
+    if (O.delta_r && no) memcpy(O.delta_r, h_dr + at, no * sizeof(double));
+  }
+  return PLSVO_OK;
+}
 
 extern "C" int plsvo_chain_stage(plsvo_ctx* c, int n, const plsvo_chain_in* in, const plsvo_chain_params* pr) {
   CTX_CHECK(c);

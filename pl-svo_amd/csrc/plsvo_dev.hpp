@@ -259,6 +259,45 @@ struct ReprojBatchDev {
   double* px; int* cell;
 };
 
+// keyframe stage (keyframe_device.hpp, include/plsvo_hip.h plsvo_close_keyframes / plsvo_keyframe_decide): one wave per stream; the
+// streams' tables and feature lists are concatenated, a job holds its offsets (in entries, not bytes)
+struct CloseKfJobDev {
+  double T[7];
+  double fx, fy, cx, cy;
+  int width, height;
+  int n_kf, max_n_kfs;
+  long long kf_off;                 // first keyframe of the stream in kf_T / keypt_* / tmp_dist / close_*
+};
+struct CloseKfBatchDev {
+  const CloseKfJobDev* jobs; int n_jobs;
+  const double* kf_T; const double* keypt_pos; const uint8_t* keypt_valid;
+  double* tmp_dist;                 // per keyframe: its distance, -1 = not close
+  int* close_idx; double* close_dist;
+  int* counts;                      // 2 per job: n_close, n_overlap
+};
+struct KfDecideJobDev {
+  double T_new[7], T_last[7];
+  const double* d_T_new;            // device pointer read instead of T_new, or null
+  double min_t, min_r;
+  int width, height;
+  int n_pt, n_seg, n_kf, n_ov;
+  long long pt_off, seg_off, kf_off, ov_off, depth_off;
+  int key_prev[5]; int reserved0;
+};
+struct KfDecideOutDev {
+  double depth_mean, depth_min;
+  int has_depth, n_depth, need_new_kf, blocking;
+  int key_pts[5]; int furthest_kf;
+};
+struct KfDecideBatchDev {
+  const KfDecideJobDev* jobs; KfDecideOutDev* out; int n_jobs;
+  const double* pt_px; const double* pt_pos; const uint8_t* pt_alive;
+  const double* seg_spos; const double* seg_epos; const uint8_t* seg_alive;
+  const double* kf_T; const int* overlap_idx;
+  unsigned long long* depth_keys;   // n_pt + 2 * n_seg per job from depth_off: the order-preserving keys of the depths (all ones = dead)
+  double* delta_t; double* delta_r; // per overlap entry
+};
+
 // corner detection (detect_device.hpp, include/plsvo_hip.h plsvo_hip_detect_fast): tile geometry and the launch record
 constexpr int kDetTileW = 64, kDetTileH = 32;          // pixels of a tile that one workgroup decides
 constexpr int kDetImgX0 = 8, kDetImgY0 = 5;            // LDS image origin = tile origin - (8, 5): a halo of 5 (Shi-Tomasi: x - 5 .. x + 4), 8 keeps rows dword-aligned

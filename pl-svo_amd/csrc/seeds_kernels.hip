@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "match_device.hpp"
+#include "keyframe_device.hpp"   // the keyframe stage's kernels live in this translation unit for its -ffp-contract=off
 
 namespace plsvo_hip {
 
@@ -382,6 +383,18 @@ hipError_t launch_update_seeds(const SeedsBatchDev& b, hipStream_t stream) {
   const int n = b.n_pt + b.n_seg;
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(update_seeds_kernel, dim3((n + MT - 1) / MT), dim3(MT), 0, stream, b);
+  return hipGetLastError();
+}
+
+// keyframe stage (keyframe_device.hpp): one wave per stream, four streams per workgroup
+hipError_t launch_close_keyframes(const CloseKfBatchDev& b, hipStream_t stream) {
+  if (b.n_jobs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(close_keyframes_kernel, dim3((b.n_jobs + kKfWaves - 1) / kKfWaves), dim3(64 * kKfWaves), 0, stream, b);
+  return hipGetLastError();
+}
+hipError_t launch_keyframe_decide(const KfDecideBatchDev& b, hipStream_t stream) {
+  if (b.n_jobs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(keyframe_decide_kernel, dim3((b.n_jobs + kKfWaves - 1) / kKfWaves), dim3(64 * kKfWaves), 0, stream, b);
   return hipGetLastError();
 }
 

@@ -127,7 +127,8 @@ struct Context {
     *victim = lru;
     return -1;
   }
-  bool ensure(int w, int h, int n_levels) {
+  /// the context alone, for the calls that read no image (the keyframe stage)
+  bool ensure_ctx() {
     if (!ctx) {
       const char* dev = std::getenv("PLSVO_DEVICE");
       if (plsvo_hip_create(dev ? std::atoi(dev) : 0, nullptr, &ctx) != PLSVO_OK) {
@@ -136,6 +137,10 @@ struct Context {
         return false;
       }
     }
+    return true;
+  }
+  bool ensure(int w, int h, int n_levels) {
+    if (!ensure_ctx()) return false;
     if (w != width || h != height || n_levels > levels) {   // n_levels is a minimum: fewer levels never reconfigure
       const int n_cache = cache_slots();
       if (plsvo_hip_config_pyramids(ctx, 2 + n_cache, w, h, n_levels) != PLSVO_OK) {
@@ -880,6 +885,158 @@ class FastDetector {
 };
 
 }  // namespace feature_detection
+}  // namespace plsvo
+
+namespace plsvo_hip_adapter {
+// One stream of plsvo_keyframe_decide flattened from a frame: Feature::px, feat3D->pos_ / spos_ / epos_ and the alive flags
+// (feat3D != NULL), in list order, so that the indices the call returns address pt_fts_.
+struct KeyframeInput {
+  plsvo_kf_decide_in in;
+  std::vector<double> pt_px, pt_pos, seg_spos, seg_epos, kf_T;
+  std::vector<uint8_t> pt_alive, seg_alive;
+  std::vector<int32_t> overlap;
+  template <class FrameT>
+  explicit KeyframeInput(const FrameT& frame) {
+    in = plsvo_kf_decide_in();
+    typedef typename std::remove_reference<decltype(*frame.cam_)>::type Cam;
+    in.cam = camera_traits<Cam>::get(*frame.cam_);
+    typedef typename std::decay<decltype(frame.T_f_w_)>::type SE3T;
+    se3_traits<SE3T>::get(frame.T_f_w_, in.T_new_w);
+    se3_traits<SE3T>::get(frame.T_f_w_, in.T_last_w);
+    for (auto it = frame.pt_fts_.begin(); it != frame.pt_fts_.end(); ++it) {
+      double p[3] = {0, 0, 0};
+      if ((*it)->feat3D) copy3((*it)->feat3D->pos_, p);
+      pt_px.push_back((*it)->px[0]); pt_px.push_back((*it)->px[1]);
+      pt_pos.insert(pt_pos.end(), p, p + 3);
+      pt_alive.push_back((*it)->feat3D ? 1 : 0);
+    }
+    for (auto it = frame.seg_fts_.begin(); it != frame.seg_fts_.end(); ++it) {
+      double a[3] = {0, 0, 0}, b[3] = {0, 0, 0};
+      if ((*it)->feat3D) { copy3((*it)->feat3D->spos_, a); copy3((*it)->feat3D->epos_, b); }
+      seg_spos.insert(seg_spos.end(), a, a + 3); seg_epos.insert(seg_epos.end(), b, b + 3);
+      seg_alive.push_back((*it)->feat3D ? 1 : 0);
+    }
+    for (int k = 0; k < 5; ++k) in.key_pts_prev[k] = -1;
+    in.kfselect_mindist_t = 0.06; in.kfselect_mindist_r = 3.0;
+  }
+  /// points the struct at the vectors (call after the last push_back) and runs the batch of one
+  bool run(plsvo_kf_decide_out* out) {
+    in.n_pt = (int32_t)pt_alive.size(); in.n_seg = (int32_t)seg_alive.size();
+    in.n_kf = (int32_t)(kf_T.size() / 7); in.n_overlap = (int32_t)overlap.size();
+    in.pt_px = pt_px.data(); in.pt_pos = pt_pos.data(); in.pt_alive = pt_alive.data();
+    in.seg_spos = seg_spos.data(); in.seg_epos = seg_epos.data(); in.seg_alive = seg_alive.data();
+    in.kf_T = kf_T.data(); in.overlap_idx = overlap.data();
+    Context& c = default_context();
+    if (!c.ensure_ctx()) return false;
+    if (plsvo_keyframe_decide(c.ctx, 1, &in, out) != PLSVO_OK) {
+      std::fprintf(stderr, "[plsvo_hip] keyframe_decide failed: %s\n", plsvo_hip_last_error(c.ctx));
+      return false;
+    }
+    return true;
+  }
+};
+}  // namespace plsvo_hip_adapter
+
+namespace plsvo {
+namespace frame_utils {
+/// Drop-in for frame_utils::getSceneDepth (src/frame.cpp:182-217): the median (rank m / 2) and the minimum of the depths of the frame's
+/// landmarks.  false, depth_min = DBL_MAX and depth_mean untouched when the frame observes none -- or when the device call fails.
+template <class FrameT>
+inline bool getSceneDepth(const FrameT& frame, double& depth_mean, double& depth_min) {
+  plsvo_hip_adapter::KeyframeInput k(frame);
+  plsvo_kf_decide_out out = plsvo_kf_decide_out();
+  depth_min = 1.7976931348623157e308;
+  if (!k.run(&out) || !out.has_depth) return false;
+  depth_mean = out.depth_mean; depth_min = out.depth_min;
+  return true;
+}
+}  // namespace frame_utils
+
+namespace keyframe {
+/// Map::getCloseKeyframes (src/map.cpp:158-179) with the sort of Reprojector::reprojectMap (src/reprojector.cpp:155-157) already
+/// applied: `close_kfs` receives (keyframe, distance) of every keyframe that has a key point visible in `frame`, ascending by distance.
+/// `keyframes`: a container of frame pointers (Map::keyframes_); a key point contributes when key_pts_[k] and its feat3D are set.
+template <class FramePtrT, class KeyframeList>
+inline bool getCloseKeyframes(const FramePtrT& frame, const KeyframeList& keyframes, std::list<std::pair<FramePtrT, double> >& close_kfs) {
+  using namespace plsvo_hip_adapter;
+  plsvo_close_kf_in in = plsvo_close_kf_in();
+  typedef typename std::remove_reference<decltype(*frame->cam_)>::type Cam;
+  typedef typename std::decay<decltype(frame->T_f_w_)>::type SE3T;
+  in.cam = camera_traits<Cam>::get(*frame->cam_);
+  se3_traits<SE3T>::get(frame->T_f_w_, in.T_f_w);
+  std::vector<double> kf_T, kp;
+  std::vector<uint8_t> kv;
+  std::vector<FramePtrT> table;
+  for (auto it = keyframes.begin(); it != keyframes.end(); ++it) {
+    double T[7];
+    se3_traits<SE3T>::get((*it)->T_f_w_, T);
+    kf_T.insert(kf_T.end(), T, T + 7);
+    for (int k = 0; k < 5; ++k) {
+      double p[3] = {0, 0, 0};
+      const bool valid = (*it)->key_pts_[(size_t)k] != nullptr && (*it)->key_pts_[(size_t)k]->feat3D != nullptr;
+      if (valid) copy3((*it)->key_pts_[(size_t)k]->feat3D->pos_, p);
+      kp.insert(kp.end(), p, p + 3);
+      kv.push_back(valid ? 1 : 0);
+    }
+    table.push_back(*it);
+  }
+  in.n_kf = (int32_t)table.size(); in.max_n_kfs = in.n_kf;
+  in.kf_T = kf_T.data(); in.keypt_pos = kp.data(); in.keypt_valid = kv.data();
+  std::vector<int32_t> idx(table.size() + 1);
+  std::vector<double> dist(table.size() + 1);
+  plsvo_close_kf_out out = plsvo_close_kf_out();
+  out.close_idx = idx.data(); out.close_dist = dist.data();
+  Context& c = default_context();
+  if (!c.ensure_ctx()) return false;
+  if (plsvo_close_keyframes(c.ctx, 1, &in, &out) != PLSVO_OK) {
+    std::fprintf(stderr, "[plsvo_hip] close_keyframes failed: %s\n", plsvo_hip_last_error(c.ctx));
+    return false;
+  }
+  for (int32_t i = 0; i < out.n_close; ++i) close_kfs.push_back(std::make_pair(table[(size_t)idx[(size_t)i]], dist[(size_t)i]));
+  return true;
+}
+
+/// FrameHandlerMono::needNewKf (src/frame_handler_mono.cpp:475-499): false when one of the overlap keyframes (a container of
+/// (keyframe, distance) pairs, overlap_kfs_) is closer to `last_frame` than both thresholds (Config::kfSelectMinDistT / R).  A device
+/// failure returns true, like an empty list.
+template <class FramePtrT, class OverlapList>
+inline bool needNewKf(const FramePtrT& last_frame, const OverlapList& overlap_kfs, double min_t, double min_r) {
+  using namespace plsvo_hip_adapter;
+  typedef typename std::decay<decltype(last_frame->T_f_w_)>::type SE3T;
+  KeyframeInput k(*last_frame);
+  k.pt_px.clear(); k.pt_pos.clear(); k.pt_alive.clear(); k.seg_spos.clear(); k.seg_epos.clear(); k.seg_alive.clear();   // poses only
+  for (auto it = overlap_kfs.begin(); it != overlap_kfs.end(); ++it) {
+    double T[7];
+    se3_traits<SE3T>::get(it->first->T_f_w_, T);
+    k.overlap.push_back((int32_t)(k.kf_T.size() / 7));
+    k.kf_T.insert(k.kf_T.end(), T, T + 7);
+  }
+  k.in.kfselect_mindist_t = min_t; k.in.kfselect_mindist_r = min_r;
+  plsvo_kf_decide_out out = plsvo_kf_decide_out();
+  if (!k.run(&out)) return true;
+  return out.need_new_kf != 0;
+}
+
+/// Frame::setKeyPoints (src/frame.cpp:87-95): drops the key points that lost their landmark and lets every feature with a landmark
+/// challenge the five holders; mutates frame.key_pts_ (five PointFeat pointers).  Untouched on a device failure (false).
+template <class FrameT>
+inline bool setKeyPoints(FrameT& frame) {
+  using namespace plsvo_hip_adapter;
+  KeyframeInput k(frame);
+  typedef typename std::decay<decltype(*frame.pt_fts_.begin())>::type FeatPtr;
+  std::vector<FeatPtr> fts(frame.pt_fts_.begin(), frame.pt_fts_.end());
+  for (int s = 0; s < 5; ++s) {
+    k.in.key_pts_prev[s] = -1;
+    for (size_t i = 0; i < fts.size() && frame.key_pts_[(size_t)s] != nullptr; ++i)
+      if (fts[i] == frame.key_pts_[(size_t)s]) { k.in.key_pts_prev[s] = (int32_t)i; break; }
+    // (a holder that is not in pt_fts_ any more cannot be addressed: it is dropped like one without a landmark)
+  }
+  plsvo_kf_decide_out out = plsvo_kf_decide_out();
+  if (!k.run(&out)) return false;
+  for (int s = 0; s < 5; ++s) frame.key_pts_[(size_t)s] = out.key_pts[s] >= 0 ? fts[(size_t)out.key_pts[s]] : nullptr;
+  return true;
+}
+}  // namespace keyframe
 }  // namespace plsvo
 
 namespace svo = plsvo;  // BASELINE.json spells the upstream name svo::SparseImgAlign

@@ -55,6 +55,7 @@ struct Frame {
   std::vector<Image> img_pyr_;
   std::list<PointFeat*> pt_fts_;
   std::list<LineFeat*> seg_fts_;
+  std::vector<PointFeat*> key_pts_ = std::vector<PointFeat*>(5, nullptr);   // Frame::key_pts_ (include/plsvo/frame.h:66)
 };
 // depth-filter seeds (include/plsvo/depth_filter.h:47-101)
 struct PointSeed { int batch_id = 0, id = 0; PointFeat* ftr = nullptr; float a = 10, b = 10, mu = 0, z_range = 0, sigma2 = 0; };

@@ -9,8 +9,8 @@
 
 on a synthetic sequence with a known map (a textured plane carrying point and line-segment landmarks, observed in
 keyframe 0).  It exists to exercise the entry points chained the way the reference chains them and to emit trajectory
-files in the reference harness's format; it is not a VO system: no feature detection, depth filter,
-keyframe selection or map maintenance.
+files in the reference harness's format; it is not a VO system: the map is given, and its maintenance (candidate
+lists, keyframe removal) is not part of it.
 
 With mapping=True two more steps run per frame, again as processFrame / the depth-filter thread order them:
 
@@ -20,8 +20,17 @@ With mapping=True two more steps run per frame, again as processFrame / the dept
 starting from a map that knows only part of the landmarks (with noisy positions) and holds the rest as seeds that turn
 into landmarks when they converge.
 
+With kf_select=True (and mapping) the keyframe stage of processFrame runs on the device too (:351-358, :396):
+
+    keyframes that overlap the aligned frame, before matching           plsvo_close_keyframes      (reprojector.cpp:147-163)
+    scene depth, new-keyframe test, the frame's five key points          plsvo_keyframe_decide
+
+A frame then plays the keyframe when needNewKf says so -- measured, like the reference, from the PREVIOUS frame's pose -- instead of
+every kf_every-th; the keyframe table (pose and the landmark positions of the five key points) grows with it, and the seeds of a
+keyframe's corners start from depth_mean * 2.0 and 0.1 * depth_min of that call (:391).
+
 `backend` is duck-typed: load_frames(list of level-0 images; HipBackend also takes raw frames with rectify=), sparse_align(job), reproject(job), match_direct(job),
-pose_optimize(job), and for mapping structure_optimize(job), update_seeds(job).  The product backend is HipBackend (C ABI on the GPU, no fallback); tests pass an oracle-backed one
+pose_optimize(job), for mapping structure_optimize(job), update_seeds(job), and for kf_select close_keyframes(job), keyframe_decide(job).  The product backend is HipBackend (C ABI on the GPU, no fallback); tests pass an oracle-backed one
 to check the whole chain end to end."""
 import copy
 
@@ -72,6 +81,12 @@ class HipBackend:
 
     def update_seeds(self, job):
         return self.ctx.update_seeds(job)
+
+    def close_keyframes(self, job):
+        return self.ctx.close_keyframes([job])[0]
+
+    def keyframe_decide(self, job):
+        return self.ctx.keyframe_decide([job])[0]
 
     def detect_corners(self, slot, occupancy=None, cell_size=25, n_levels=3, detection_threshold=20.0):
         """FastDetector::detect on the frame in `slot` (plsvo_hip_detect_fast): abi.CORNER_DTYPE records in cell order"""
@@ -146,7 +161,8 @@ def _occupancy(px, w, h, cell):
 
 
 def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_thresh=2.0, mapping=False, known_frac=0.6,
-                 pos_noise=0.005, map_seed=0, kf_every=5, detect=False, detect_cell_size=25):
+                 pos_noise=0.005, map_seed=0, kf_every=5, detect=False, detect_cell_size=25, kf_select=False, kfselect_mindist_t=0.06,
+                 kfselect_mindist_r=3.0, max_n_kfs=10):
     """-> list of per-frame dicts (pose T_f_w, cov, counts).  Frame 0 is the keyframe with the true pose.
     mapping=True: only `known_frac` of the point landmarks start in the map (positions off by `pos_noise` x depth along
     their viewing ray), the others are depth-filter seeds; the seed update runs every frame; every `kf_every`-th frame
@@ -155,7 +171,9 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
     detect=True (with mapping, a backend with detect_corners): every keyframe, frame 0 included, also runs the corner detector on its
     own pyramid slot with the cells of the features it tracks marked occupied (DepthFilter::initializeSeeds), and the corners become
     point seeds (seeds_from_corners) that the following frames update next to the map's own; the records gain n_image_seeds /
-    n_image_seeds_converged.  These seeds come from the image alone and are not added to the map, whose landmarks carry the truth."""
+    n_image_seeds_converged.  These seeds come from the image alone and are not added to the map, whose landmarks carry the truth.
+    kf_select=True (with mapping, a backend with close_keyframes / keyframe_decide): the keyframe stage decides which frames play the
+    keyframe (module docstring); the records gain is_kf, n_overlap, depth_mean."""
     cam = seq["cam"]
     backend.load_frames(seq["images"])
     n_pts, n_seg = len(seq["pt_pos"]), len(seq["seg_spos"])
@@ -181,9 +199,29 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
         img_seeds, img_converged = None, 0
         w_img, h_img = int(cam[4]), int(cam[5])
 
+        kf_select = kf_select and hasattr(backend, "keyframe_decide")
+        z3 = np.zeros((0, 3))
+
+        def decide(T_new, T_last, px, pos, sp, ep, overlap):
+            return backend.keyframe_decide(abi.KeyframeDecideJob(cam, T_new, T_last, px, pos, None, sp, ep, None, np.stack(kfs["T"]), overlap,
+                                                                 (-1,) * 5, kfselect_mindist_t, kfselect_mindist_r))
+
+        def add_keyframe(T, key_pts, pos):
+            """the keyframe table row: the pose and the landmark positions of the five key points (key_pts index `pos`, -1 = none)"""
+            kfs["T"].append(np.asarray(T, float).copy())
+            kfs["pos"].append(np.array([pos[i] if i >= 0 else np.zeros(3) for i in key_pts]))
+            kfs["valid"].append(np.array([i >= 0 for i in key_pts], np.uint8))
+        kfs = dict(T=[kf_T.copy()], pos=[], valid=[])
+        seed_depth = (dmean, dmin)
+        if kf_select:      # frame 0 is a keyframe: its key points come from the same call (no overlap keyframes: nothing else is looked at)
+            kfs["T"] = []
+            d0_ = backend.keyframe_decide(abi.KeyframeDecideJob(cam, kf_T, kf_T, seq["pt_px0"][known], P3[known], None, z3, z3, None, np.zeros((0, 7)), (),
+                                                                (-1,) * 5, kfselect_mindist_t, kfselect_mindist_r))
+            add_keyframe(kf_T, d0_["key_pts"], P3[known])
+
         def new_image_seeds(frame, feature_px):
             corners = backend.detect_corners(frame, _occupancy(feature_px, w_img, h_img, detect_cell_size), detect_cell_size, n_pyr_levels)
-            sd = seeds_from_corners(corners, cam, dmean, dmin)
+            sd = seeds_from_corners(corners, cam, *seed_depth)
             sd["ref_frame"] = np.full(len(corners), frame, np.int32)
             return sd
         if detect:
@@ -193,6 +231,7 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
     prev = dict(pt_idx=k0, pt_px=seq["pt_px0"][k0].copy(), seg_idx=np.arange(n_seg), seg_spx=seq["seg_spx0"].copy(),
                 seg_epx=seq["seg_epx0"].copy())
     out = [dict(T=T_prev.copy(), cov=np.full((6, 6), 1e-9), n_align=0, n_matched_pt=int(known.sum()), n_matched_seg=n_seg)]
+    kf_select = mapping and kf_select
     for k in range(1, len(seq["images"])):
         # ---- 1. sparse image alignment, previous frame -> frame k (processFrame :266-274) ----
         ref_pos = synth.se3_inv(T_prev)[4:]
@@ -251,6 +290,12 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
                                 seq["seg_spos"][seg_i], seq["seg_epos"][seg_i], level[n_pts + seg_i])
             pr = backend.pose_optimize(pj)
         n_ties = backend.align_ties() if hasattr(backend, "align_ties") else None
+        if kf_select:
+            # ---- the keyframes that overlap the aligned frame (the head of reprojectMap: it runs before the matching, which here takes
+            #      its candidates from keyframe 0 either way, so the call's place in this function does not matter) ----
+            close = backend.close_keyframes(abi.CloseKeyframesJob(cam, synth.se3_mul(ar.T, T_prev), np.stack(kfs["T"]), np.stack(kfs["pos"]),
+                                                                  np.stack(kfs["valid"]), max_n_kfs))
+        T_last = T_prev
         T_k = pr.T.copy()
         pt_keep, seg_keep = pr.pt_keep.astype(bool), pr.seg_keep.astype(bool)
         prev = dict(pt_idx=pt_i[pt_keep], pt_px=px_new[pt_i[pt_keep]], seg_idx=seg_i[seg_keep],
@@ -264,6 +309,16 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
             poses_est.append(T_k.copy())
             kept = pt_i[pt_keep]
             is_kf = (k % kf_every) == 0
+            if kf_select:
+                # ---- scene depth, needNewKf against the overlap keyframes from the previous frame's pose, the frame's key points ----
+                skept = seg_i[seg_keep]
+                dec = decide(T_k, T_last, px_new[kept], P3[kept], seq["seg_spos"][skept], seq["seg_epos"][skept], close["close_idx"][:close["n_overlap"]])
+                is_kf = bool(dec["need_new_kf"])
+                rec.update(is_kf=is_kf, n_overlap=close["n_overlap"], depth_mean=dec["depth_mean"])
+                if is_kf:
+                    add_keyframe(T_k, dec["key_pts"], P3[kept])
+                    if dec["has_depth"]:
+                        seed_depth = (dec["depth_mean"] * 2.0, 0.1 * dec["depth_min"])
             if is_kf:
                 for i, brg in zip(kept, _bearing(cam, px_new[kept])):
                     obs[int(i)].append((k, brg))

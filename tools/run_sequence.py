@@ -7,7 +7,9 @@ coefficients (synth.distort_image) and rectified on the device into its pyramid 
 run_pipeline.cpp undistorts each raw frame before addImage.
 With --detect (off by default; needs mapping) every keyframe also runs the corner detector on its pyramid slot (plsvo_hip_detect_fast)
 and the corners become depth-filter seeds (sequence.seeds_from_corners) that the following frames update: seeds that come from the image.
-usage: python tools/run_sequence.py [--distortion k1,k2,p1,p2[,k3]] [--detect] [out.txt] [n_frames] [seed] [mapping 0|1]"""
+With --kf-select (off by default; needs mapping) the keyframe stage runs on the device (plsvo_close_keyframes, plsvo_keyframe_decide): a
+frame plays the keyframe when FrameHandlerMono::needNewKf says so instead of every fifth, and the JSON line lists the keyframe frames.
+usage: python tools/run_sequence.py [--distortion k1,k2,p1,p2[,k3]] [--detect] [--kf-select] [out.txt] [n_frames] [seed] [mapping 0|1]"""
 import importlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -25,6 +27,9 @@ if "--distortion" in argv:
 detect = "--detect" in argv
 if detect:
     argv.remove("--detect")
+kf_select = "--kf-select" in argv
+if kf_select:
+    argv.remove("--kf-select")
 sys.argv = sys.argv[:1] + argv
 
 out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "gpurun_out", "trajectory.txt")
@@ -39,12 +44,14 @@ if distortion is not None:
     fx, fy, cx, cy, w, h = seq["cam"]
     seq = dict(seq, images=[P.synth.distort_image(img, dict(fx=fx, fy=fy, cx=cx, cy=cy, d=distortion)) for img in seq["images"]])
     rectify = P.abi.pinhole_radtan(w, h, fx, fy, cx, cy, distortion)
-res = seqm.run_sequence(seqm.HipBackend(ctx, rectify=rectify), seq, mapping=mapping, detect=detect)
+res = seqm.run_sequence(seqm.HipBackend(ctx, rectify=rectify), seq, mapping=mapping, detect=detect, kf_select=kf_select)
 n = P.trajectory.write_trajectory(out, ["%.6f" % (0.05 * k) for k in range(n_frames)], [r["T"] for r in res], [r["cov"] for r in res])
 err = seqm.pose_errors(res, seq)
 print(json.dumps({"frames": n_frames, "lines_written": n, "trajectory": out, "max_rot_err_rad": max(e[0] for e in err),
                   "max_trans_err_m": max(e[1] for e in err), "matched_points_last": res[-1]["n_matched_pt"], "matched_segments_last": res[-1]["n_matched_seg"],
                   "mapping": mapping, "distortion": distortion, "landmarks_first_last": [res[1].get("n_known"), res[-1].get("n_known")],
                   "seeds_first_last": [res[1].get("n_seeds"), res[-1].get("n_seeds")],
-                  **({"image_seeds_last": res[-1].get("n_image_seeds"), "image_seeds_converged": res[-1].get("n_image_seeds_converged")} if detect else {})}))
+                  **({"image_seeds_last": res[-1].get("n_image_seeds"), "image_seeds_converged": res[-1].get("n_image_seeds_converged")} if detect else {}),
+                  **({"keyframes": [k for k, r in enumerate(res) if r.get("is_kf")], "overlap_last": res[-1].get("n_overlap"),
+                      "depth_mean_last": res[-1].get("depth_mean")} if kf_select else {})}))
 ctx.close()

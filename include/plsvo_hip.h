@@ -714,6 +714,156 @@ typedef struct plsvo_kf_decide_out {
  * non-zero count (the alive arrays excepted), an overlap index outside the table or a key_pts_prev entry outside -1 .. n_pt-1. */
 int plsvo_keyframe_decide(plsvo_ctx* ctx, int n, const plsvo_kf_decide_in* in, plsvo_kf_decide_out* out);
 
+/* ------------------------------------------------------------------------------------------ */
+/* map candidates: what Reprojector::reprojectMap builds between "close keyframes sorted" and   */
+/* "match one candidate per cell" (src/reprojector.cpp:157-183) -- the visits of the overlap    */
+/* keyframes' features with setKfCandidates (:92-109), setMapCandidates (:111-133), reproject   */
+/* (:389-423) -- together with the closest-view observation the matcher picks first             */
+/* (Point::getCloseViewObs / LineSeg::getCloseViewObs, src/feature3D.cpp:80-125, called at      */
+/* src/matcher.cpp:165, :239) and the order cell.sort(pointQualityComparator) leaves in every   */
+/* cell (:219-276), for a batch of independent streams (one wave per stream).   */
+/* The map tables are staged once and stay on the device; a frame costs a pose and an overlap   */
+/* list; the result is handed to the direct matcher without leaving the device.                 */
+/* ------------------------------------------------------------------------------------------ */
+
+#define PLSVO_LM_DELETED   0        /* Point::TYPE_DELETED < TYPE_CANDIDATE < TYPE_UNKNOWN < TYPE_GOOD (include/plsvo/feature3D.h:55-59), */
+#define PLSVO_LM_CANDIDATE 1        /* and the same four of LineSeg */
+#define PLSVO_LM_UNKNOWN   2
+#define PLSVO_LM_GOOD      3
+
+/* One stream's map tables (they change at keyframes only; a keyframe restages them).
+ *   kf_T, kf_slot      7*n_kf, n_kf    Frame::T_f_w_ and the pyramid slot of every keyframe
+ *   kf_pt_off          n_kf+1          CSR: keyframe k's pt_fts_ are entries [kf_pt_off[k], kf_pt_off[k+1]) of kf_pt_lm, in list order
+ *   kf_pt_lm                           the point landmark of every feature (index < n_pt), -1 where feat3D == NULL
+ *   kf_seg_off, kf_seg_lm              the same for seg_fts_ and the segment landmarks
+ *   pt_pos, pt_type    3*n_pt, n_pt    Point::pos_, Point::type_ (PLSVO_LM_*)
+ *   pt_obs_off         n_pt+1          CSR: Point::obs_ in list order (the reference pushes at the front; the list as it stands)
+ *   pt_obs_kf ..                       per observation: index of Feature::frame in the keyframe table, px (2), f (3), level,
+ *                                      type (PLSVO_FTR_*), PointFeat::grad (2; the array may be NULL without edgelets)
+ *   seg_spos, seg_epos, seg_type       LineSeg::spos_, epos_, type_
+ *   seg_obs_*                          LineFeat: frame, spx (2), epx (2), sf (3), ef (3), level
+ *   pt_cand, seg_cand                  map_.point_candidates_ / map_.segment_candidates_ as landmark indices in list order
+ * Preconditions: finite values, and no landmark at a camera centre it is seen from or at the new frame's (Eigen normalises a
+ * zero vector to NaN; a finite non-zero direction is required). */
+typedef struct plsvo_cand_map {
+  int32_t n_kf;
+  int32_t n_pt, n_seg;              /* landmarks */
+  int32_t n_pt_cand, n_seg_cand;    /* entries of the map's candidate lists */
+  int32_t reserved0;
+  const double* kf_T;
+  const int32_t* kf_slot;
+  const int32_t* kf_pt_off;
+  const int32_t* kf_pt_lm;
+  const int32_t* kf_seg_off;
+  const int32_t* kf_seg_lm;
+  const double* pt_pos;
+  const int32_t* pt_type;
+  const int32_t* pt_obs_off;
+  const int32_t* pt_obs_kf;
+  const double* pt_obs_px;
+  const double* pt_obs_f;
+  const int32_t* pt_obs_level;
+  const uint8_t* pt_obs_type;
+  const double* pt_obs_grad;
+  const double* seg_spos;
+  const double* seg_epos;
+  const int32_t* seg_type;
+  const int32_t* seg_obs_off;
+  const int32_t* seg_obs_kf;
+  const double* seg_obs_spx;
+  const double* seg_obs_epx;
+  const double* seg_obs_sf;
+  const double* seg_obs_ef;
+  const int32_t* seg_obs_level;
+  const int32_t* pt_cand;
+  const int32_t* seg_cand;
+} plsvo_cand_map;
+
+typedef struct plsvo_cand_params {  /* one set for the batch */
+  plsvo_pinhole cam;
+  int32_t cell_size;                /* Config::gridSize(): the points' grid (reprojector.cpp:57-66) */
+  int32_t seg_cell_size;            /* Config::gridSizeSegs(): the segments' grid (:68-79) */
+  int32_t boundary;                 /* 8 (:393) */
+  int32_t n_pyr_levels;             /* Config::nPyrLevels() (matcher) */
+  int32_t align_max_iter;           /* Matcher::Options::align_max_iter (10) */
+  int32_t reserved0;
+} plsvo_cand_params;
+
+/* One stream's new frame. */
+typedef struct plsvo_cand_frame {
+  double T_f_w[7];                  /* the frame's T_f_w_ after alignment */
+  const double* d_T_f_w;            /* NULL, or a DEVICE pointer to 7 doubles read instead (as plsvo_kf_decide_in::d_T_new) */
+  int32_t cur_slot;                 /* its pyramid slot */
+  int32_t n_overlap;
+  const int32_t* overlap_idx;       /* n_overlap indices into the keyframe table, in order (plsvo_close_kf_out.close_idx) */
+} plsvo_cand_frame;
+
+/* Results of one stream.  A landmark is FILED when its visit won (the first visit of a landmark in the order overlap rank, then
+ * point features, then segment features of that keyframe; points and segments are separate landmark spaces) and its projection
+ * is what plsvo_reproject accepts (both end points for a segment); the map's candidates follow in list order without the
+ * first-visit test.  Filed landmarks come out in stable descending order of type_, within a type in filing order.
+ * Caller buffers, any may be NULL; capacity n_pt + n_pt_cand points, n_seg + n_seg_cand segments, of which the first n_filed_*
+ * are written. */
+typedef struct plsvo_cand_out {
+  int32_t n_filed_pt, n_filed_seg;
+  int32_t* pt_lm;                   /* landmark index */
+  double* pt_px;                    /* 2: the projection */
+  int32_t* pt_cell;                 /* its grid cell */
+  int32_t* pt_obs;                  /* position in the landmark's observation list of getCloseViewObs' choice; -1 for an empty list */
+  uint8_t* pt_has_view;             /* getCloseViewObs' return value (0 for an empty list) */
+  uint8_t* pt_active;               /* has_view and not TYPE_DELETED: refine() would call the matcher */
+  int32_t* seg_lm;
+  double* seg_px;                   /* 4: projected start point, end point */
+  int32_t* seg_cell;                /* 2 */
+  int32_t* seg_obs;
+  uint8_t* seg_has_view;
+  uint8_t* seg_active;
+  int32_t* kf_count;                /* n_overlap: overlap_kfs[r].second (a segment counts once) */
+  uint8_t* pt_cand_failed;          /* n_pt_cand: 1 where reproject() failed (n_failed_reproj_ += 3 and the deletion stay with the caller) */
+  uint8_t* seg_cand_failed;         /* n_seg_cand */
+} plsvo_cand_out;
+
+/* The matcher's result for one stream's filed landmarks: n_filed_pt points, then the start points of the n_filed_seg segments,
+ * then their end points, each in output order.  An entry with active == 0 reports found 0, its projection and search level -1.
+ * Caller buffers of n_pt + n_pt_cand + 2 * (n_seg + n_seg_cand) entries, any may be NULL. */
+typedef struct plsvo_cand_match_out {
+  uint8_t* found;
+  double* px;                       /* 2 */
+  int32_t* search_level;
+} plsvo_cand_match_out;
+
+/* The candidate arrays on the device, in the layout of plsvo_match_in, for a later stage of a resident chain: stream s owns entries
+ * [m_off[s], m_off[s] + cap) with cap = n_pt + n_pt_cand + 2 * (n_seg + n_seg_cand), of which the first n_filed_pt + 2 * n_filed_seg
+ * are candidates ([points | start points | end points]) and the rest have active == 0; counts holds n_filed_pt, n_filed_seg per
+ * stream.  Frame indices are global: stream s owns frames [f_off[s], f_off[s] + n_kf] -- its keyframes, then the new frame.
+ * Valid from plsvo_candidates_run until the next plsvo_candidates_stage. */
+typedef struct plsvo_cand_dev {
+  int64_t n_entries, n_frames;
+  const int64_t* m_off;             /* HOST arrays of n streams, owned by the context */
+  const int64_t* f_off;
+  const int32_t* d_counts;
+  const double* d_frame_T; const int32_t* d_frame_slot;
+  const int32_t* d_cur_frame; const int32_t* d_ref_frame;
+  const double* d_ref_px; const double* d_ref_f; const int32_t* d_ref_level; const uint8_t* d_ref_type; const double* d_ref_grad;
+  const double* d_pos; const double* d_px_cur; const uint8_t* d_active;
+  const uint8_t* d_found; const double* d_px_out; const int32_t* d_search_level;   /* written by plsvo_candidates_match */
+} plsvo_cand_dev;
+
+/* stage: n streams' tables travel once.  run: enqueue only -- the frames' records travel, the first-visit words are re-armed, one
+ * launch.  fetch: synchronises.  match: enqueue only -- Matcher::findMatchDirect (plsvo_match_direct's kernel, unchanged) on the
+ * resident candidates; match_fetch synchronises.
+ * PLSVO_E_INVALID (nothing written) for n < 0, NULL arguments with n > 0, a negative count, a NULL array with a non-zero count
+ * (pt_obs_grad excepted), CSR offsets that do not start at 0 or decrease, a landmark, keyframe, candidate or overlap index out of
+ * range, a type outside PLSVO_LM_* / PLSVO_FTR_*, a negative level or slot, non-positive cell sizes; run / fetch with another n
+ * than staged.  PLSVO_E_STATE for run without stage, fetch without run, match_fetch without match, match without pyramids;
+ * PLSVO_E_CAPACITY for a slot or level outside the configured pyramids at match. */
+int plsvo_candidates_stage(plsvo_ctx* ctx, int n, const plsvo_cand_map* maps, const plsvo_cand_params* params);
+int plsvo_candidates_run(plsvo_ctx* ctx, int n, const plsvo_cand_frame* frames);
+int plsvo_candidates_fetch(plsvo_ctx* ctx, int n, plsvo_cand_out* out);
+int plsvo_candidates_match(plsvo_ctx* ctx);
+int plsvo_candidates_match_fetch(plsvo_ctx* ctx, int n, plsvo_cand_match_out* out);
+int plsvo_candidates_dev(plsvo_ctx* ctx, plsvo_cand_dev* out);
+
 /* TUM-style trajectory record of a frame (app/run_pipeline.cpp:425-451): the camera pose in the world,
  * T_f_w^-1, as tx ty tz qx qy qz qw.  Returns 1 and fills out7 when the reference would write the line, 0 when
  * it skips the frame (a covariance entry outside (1e-16, 1e16), or an exactly-identity pose).  Host-only helper:
@@ -841,7 +991,8 @@ int plsvo_gather_poses(plsvo_ctx* ctx, void* rccl_comm, const plsvo_pose_record*
 #define PLSVO_K_MATCH         5
 #define PLSVO_K_SEEDS         6
 #define PLSVO_K_KEYFRAME      7   /* plsvo_close_keyframes / plsvo_keyframe_decide: the launch alone, without packing and copies */
-#define PLSVO_K_COUNT         8
+#define PLSVO_K_CANDIDATES    8   /* plsvo_candidates_run: the re-arm and the launch alone (the resident match counts under PLSVO_K_MATCH) */
+#define PLSVO_K_COUNT         9
 int plsvo_hip_set_profiling(plsvo_ctx* ctx, int enable);
 /* accumulated GPU time and launch count of kernel family k since the last reset (synchronises) */
 int plsvo_hip_kernel_time(plsvo_ctx* ctx, int k, double* total_ms, int64_t* launches);

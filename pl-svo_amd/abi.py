@@ -18,9 +18,10 @@ c_i32_p = C.POINTER(C.c_int32)
 OK, E_INVALID, E_NODEVICE, E_HIP, E_CAPACITY, E_STATE, E_RCCL = 0, -1, -2, -3, -4, -5, -6
 
 # kernel families for plsvo_hip_kernel_time
-K_ALIGN_INIT, K_ALIGN_LEVEL, K_POSEOPT, K_HALFSAMPLE, K_STRUCTOPT, K_MATCH, K_SEEDS, K_KEYFRAME, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8
+K_ALIGN_INIT, K_ALIGN_LEVEL, K_POSEOPT, K_HALFSAMPLE, K_STRUCTOPT, K_MATCH, K_SEEDS, K_KEYFRAME, K_CANDIDATES, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 SEED_NOT_VISIBLE, SEED_NO_MATCH, SEED_UPDATED, SEED_CONVERGED, SEED_NAN = 0, 1, 2, 3, 4
 FTR_CORNER, FTR_EDGELET = 0, 1
+LM_DELETED, LM_CANDIDATE, LM_UNKNOWN, LM_GOOD = 0, 1, 2, 3
 
 
 class Pinhole(C.Structure):
@@ -185,6 +186,50 @@ class KfDecideOut(C.Structure):
     _fields_ = [("depth_mean", C.c_double), ("depth_min", C.c_double), ("has_depth", C.c_int32), ("n_depth", C.c_int32),
                 ("need_new_kf", C.c_int32), ("blocking", C.c_int32), ("key_pts", C.c_int32 * 5), ("furthest_kf", C.c_int32),
                 ("delta_t", c_double_p), ("delta_r", c_double_p)]
+
+
+_CAND_MAP_I32 = ("kf_slot", "kf_pt_off", "kf_pt_lm", "kf_seg_off", "kf_seg_lm", "pt_type", "pt_obs_off", "pt_obs_kf", "pt_obs_level", "seg_type", "seg_obs_off",
+                 "seg_obs_kf", "seg_obs_level", "pt_cand", "seg_cand")
+_CAND_MAP_U8 = ("pt_obs_type",)
+_CAND_MAP_ORDER = ("kf_T", "kf_slot", "kf_pt_off", "kf_pt_lm", "kf_seg_off", "kf_seg_lm", "pt_pos", "pt_type", "pt_obs_off", "pt_obs_kf", "pt_obs_px", "pt_obs_f",
+                   "pt_obs_level", "pt_obs_type", "pt_obs_grad", "seg_spos", "seg_epos", "seg_type", "seg_obs_off", "seg_obs_kf", "seg_obs_spx", "seg_obs_epx",
+                   "seg_obs_sf", "seg_obs_ef", "seg_obs_level", "pt_cand", "seg_cand")
+
+
+class CandMap(C.Structure):
+    """plsvo_cand_map"""
+    _fields_ = [("n_kf", C.c_int32), ("n_pt", C.c_int32), ("n_seg", C.c_int32), ("n_pt_cand", C.c_int32), ("n_seg_cand", C.c_int32), ("reserved0", C.c_int32)] + \
+               [(f, c_i32_p if f in _CAND_MAP_I32 else c_u8_p if f in _CAND_MAP_U8 else c_double_p) for f in _CAND_MAP_ORDER]
+
+
+class CandParams(C.Structure):
+    """plsvo_cand_params"""
+    _fields_ = [("cam", Pinhole), ("cell_size", C.c_int32), ("seg_cell_size", C.c_int32), ("boundary", C.c_int32), ("n_pyr_levels", C.c_int32),
+                ("align_max_iter", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class CandFrame(C.Structure):
+    """plsvo_cand_frame"""
+    _fields_ = [("T_f_w", C.c_double * 7), ("d_T_f_w", C.c_void_p), ("cur_slot", C.c_int32), ("n_overlap", C.c_int32), ("overlap_idx", c_i32_p)]
+
+
+class CandOut(C.Structure):
+    """plsvo_cand_out"""
+    _fields_ = [("n_filed_pt", C.c_int32), ("n_filed_seg", C.c_int32), ("pt_lm", c_i32_p), ("pt_px", c_double_p), ("pt_cell", c_i32_p), ("pt_obs", c_i32_p),
+                ("pt_has_view", c_u8_p), ("pt_active", c_u8_p), ("seg_lm", c_i32_p), ("seg_px", c_double_p), ("seg_cell", c_i32_p), ("seg_obs", c_i32_p),
+                ("seg_has_view", c_u8_p), ("seg_active", c_u8_p), ("kf_count", c_i32_p), ("pt_cand_failed", c_u8_p), ("seg_cand_failed", c_u8_p)]
+
+
+class CandMatchOut(C.Structure):
+    """plsvo_cand_match_out"""
+    _fields_ = [("found", c_u8_p), ("px", c_double_p), ("search_level", c_i32_p)]
+
+
+class CandDev(C.Structure):
+    """plsvo_cand_dev"""
+    _fields_ = [("n_entries", C.c_int64), ("n_frames", C.c_int64), ("m_off", C.POINTER(C.c_int64)), ("f_off", C.POINTER(C.c_int64))] + \
+               [(f, C.c_void_p) for f in ("d_counts", "d_frame_T", "d_frame_slot", "d_cur_frame", "d_ref_frame", "d_ref_px", "d_ref_f", "d_ref_level", "d_ref_type",
+                                          "d_ref_grad", "d_pos", "d_px_cur", "d_active", "d_found", "d_px_out", "d_search_level")]
 
 
 class PoseRecord(C.Structure):
@@ -505,6 +550,54 @@ class KeyframeDecideJob:
         c.seg_alive = C.cast(None, c_u8_p) if self.seg_alive is None else _ptr(self.seg_alive, c_u8_p)
         c.kf_T, c.overlap_idx = _ptr(self.kf_T, c_double_p), _ptr(self.overlap_idx, c_i32_p)
         c.key_pts_prev = (C.c_int32 * 5)(*[int(v) for v in key_pts_prev])
+        self.c = c
+
+
+class CandidateMapJob:
+    """One stream's map tables for plsvo_candidates_stage; owns the buffers.  `tables`: arrays named like the plsvo_cand_map fields
+    (CSR offsets relative to the stream; a missing array is empty, pt_obs_grad may be None)."""
+    _WIDTH = dict(kf_T=7, pt_pos=3, pt_obs_px=2, pt_obs_f=3, pt_obs_grad=2, seg_spos=3, seg_epos=3, seg_obs_spx=2, seg_obs_epx=2, seg_obs_sf=3, seg_obs_ef=3)
+
+    def __init__(self, **tables):
+        unknown = set(tables) - set(_CAND_MAP_ORDER)
+        if unknown:
+            raise ValueError(f"unknown tables {sorted(unknown)}")
+        c = CandMap()
+        self.t = {}
+        for f in _CAND_MAP_ORDER:
+            v = tables.get(f)
+            if f in _CAND_MAP_I32:
+                a, typ = np.ascontiguousarray(() if v is None else v, dtype=np.int32).reshape(-1), c_i32_p
+            elif f in _CAND_MAP_U8:
+                a, typ = np.ascontiguousarray(() if v is None else v, dtype=np.uint8).reshape(-1), c_u8_p
+            else:
+                a, typ = _f64(() if v is None else v).reshape(-1, self._WIDTH[f]), c_double_p
+            self.t[f] = a
+            setattr(c, f, _ptr(a, typ))
+        t = self.t
+        self.n_kf, self.n_pt, self.n_seg = t["kf_T"].shape[0], t["pt_pos"].shape[0], t["seg_spos"].shape[0]
+        self.n_pt_cand, self.n_seg_cand = t["pt_cand"].size, t["seg_cand"].size
+        for f, k in (("kf_pt_off", self.n_kf), ("kf_seg_off", self.n_kf), ("pt_obs_off", self.n_pt), ("seg_obs_off", self.n_seg)):
+            if t[f].size == 0:                             # no lists: offsets of k empty ones
+                t[f] = np.zeros(k + 1, np.int32)
+                setattr(c, f, _ptr(t[f], c_i32_p))
+            elif t[f].size != k + 1:
+                raise ValueError(f"{f}: {k + 1} offsets expected")
+        c.n_kf, c.n_pt, c.n_seg, c.n_pt_cand, c.n_seg_cand = self.n_kf, self.n_pt, self.n_seg, self.n_pt_cand, self.n_seg_cand
+        self.cap_pt, self.cap_seg = self.n_pt + self.n_pt_cand, self.n_seg + self.n_seg_cand
+        self.c = c
+
+
+class CandidateFrameJob:
+    """One stream's new frame for plsvo_candidates_run: pose, pyramid slot, overlap list; owns the buffers."""
+
+    def __init__(self, T_f_w, overlap_idx=(), cur_slot=0):
+        self.overlap_idx = np.ascontiguousarray(overlap_idx, dtype=np.int32).reshape(-1)
+        self.n_overlap = self.overlap_idx.size
+        c = CandFrame()
+        c.T_f_w = (C.c_double * 7)(*_f64(T_f_w, 7))
+        c.d_T_f_w = None
+        c.cur_slot, c.n_overlap, c.overlap_idx = int(cur_slot), self.n_overlap, _ptr(self.overlap_idx, c_i32_p)
         self.c = c
 
 

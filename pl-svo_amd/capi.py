@@ -27,6 +27,7 @@ SYMBOLS = [
     "plsvo_poseopt_set_trace", "plsvo_poseopt_fetch_trace", "plsvo_poseopt_poses_dev", "plsvo_poseopt_copy_poses", "plsvo_poseopt_work", "plsvo_poseopt_refill_frames", "plsvo_poseopt_row_select",
     "plsvo_structure_optimize", "plsvo_match_direct", "plsvo_match_warp_patches", "plsvo_reproject", "plsvo_trajectory_record", "plsvo_update_seeds",
     "plsvo_close_keyframes", "plsvo_keyframe_decide",
+    "plsvo_candidates_stage", "plsvo_candidates_run", "plsvo_candidates_fetch", "plsvo_candidates_match", "plsvo_candidates_match_fetch", "plsvo_candidates_dev",
     "plsvo_chain_stage", "plsvo_chain_run", "plsvo_chain_fetch", "plsvo_frame_step_batch", "plsvo_chain_poses_dev",
     "plsvo_pack_pose_records", "plsvo_fetch_pose_records", "plsvo_gather_poses",
     "plsvo_hip_set_profiling", "plsvo_hip_kernel_time", "plsvo_hip_reset_profiling",
@@ -141,6 +142,12 @@ def lib():
         "plsvo_reproject": (C.c_int, [ctxp, C.POINTER(abi.ReprojectIn), C.POINTER(abi.ReprojectOut)]),
         "plsvo_close_keyframes": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CloseKfIn), C.POINTER(abi.CloseKfOut)]),
         "plsvo_keyframe_decide": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.KfDecideIn), C.POINTER(abi.KfDecideOut)]),
+        "plsvo_candidates_stage": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandMap), C.POINTER(abi.CandParams)]),
+        "plsvo_candidates_run": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandFrame)]),
+        "plsvo_candidates_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandOut)]),
+        "plsvo_candidates_match": (C.c_int, [ctxp]),
+        "plsvo_candidates_match_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandMatchOut)]),
+        "plsvo_candidates_dev": (C.c_int, [ctxp, C.POINTER(abi.CandDev)]),
         "plsvo_update_seeds": (C.c_int, [ctxp, C.POINTER(abi.SeedsIn), C.POINTER(abi.SeedsOut)]),
         "plsvo_trajectory_record": (C.c_int, [abi.c_double_p, abi.c_double_p, abi.c_double_p]),
         "plsvo_chain_stage": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.ChainIn), C.POINTER(abi.ChainParams)]),
@@ -584,6 +591,88 @@ class Context:
                      need_new_kf=int(o.need_new_kf), blocking=int(o.blocking), delta_t=bt[:j.n_overlap].copy(), delta_r=br[:j.n_overlap].copy(),
                      key_pts=np.array(list(o.key_pts), np.int32), furthest_kf=int(o.furthest_kf))
                 for o, j, (bt, br) in zip(outs[:n], jobs, bufs)]
+
+    # ---- map candidates ----
+    def candidates_stage(self, maps, cam, cell_size=30, seg_cell_size=40, boundary=8, n_pyr_levels=3, align_max_iter=10):
+        """plsvo_candidates_stage: the streams' map tables (abi.CandidateMapJob) travel once and stay on the device"""
+        n = len(maps)
+        arr = (abi.CandMap * max(n, 1))(*[m.c for m in maps])
+        pr = abi.CandParams()
+        pr.cam = cam if isinstance(cam, abi.Pinhole) else abi.Pinhole(*cam)
+        pr.cell_size, pr.seg_cell_size, pr.boundary, pr.n_pyr_levels, pr.align_max_iter = cell_size, seg_cell_size, boundary, n_pyr_levels, align_max_iter
+        self._chk(self.L.plsvo_candidates_stage(self.h, n, arr, C.byref(pr)))
+        self._cand_maps = list(maps)
+
+    def candidates_run(self, frames, poses_dev=None):
+        """plsvo_candidates_run (enqueue only): one abi.CandidateFrameJob per staged stream.  poses_dev: a device pointer to
+        len(frames) * 7 doubles whose i-th pose is read instead of frame i's T_f_w, or a list of one device pointer per frame"""
+        n = len(frames)
+        arr = (abi.CandFrame * max(n, 1))(*[f.c for f in frames])
+        if poses_dev is not None:
+            for i in range(n):
+                arr[i].d_T_f_w = int(poses_dev[i]) if isinstance(poses_dev, (list, tuple)) else int(poses_dev) + 56 * i
+        self._chk(self.L.plsvo_candidates_run(self.h, n, arr))
+        self._cand_frames = list(frames)
+
+    def candidates_fetch(self):
+        """plsvo_candidates_fetch: per stream a dict of n_filed_pt / n_filed_seg, the filed points (pt_lm, pt_px [n, 2], pt_cell, pt_obs,
+        pt_has_view, pt_active) and segments (seg_px [n, 4], seg_cell [n, 2]) in output order, kf_count [n_overlap] and the failure
+        flags of the map's candidates"""
+        maps, frames = self._cand_maps, self._cand_frames
+        n = len(maps)
+        outs = (abi.CandOut * max(n, 1))()
+        bufs = []
+        for o, m, f in zip(outs, maps, frames):
+            cp, cs = max(m.cap_pt, 1), max(m.cap_seg, 1)
+            b = dict(pt_lm=np.full(cp, -9, np.int32), pt_px=np.zeros((cp, 2)), pt_cell=np.full(cp, -9, np.int32), pt_obs=np.full(cp, -9, np.int32),
+                     pt_has_view=np.full(cp, 9, np.uint8), pt_active=np.full(cp, 9, np.uint8),
+                     seg_lm=np.full(cs, -9, np.int32), seg_px=np.zeros((cs, 4)), seg_cell=np.full((cs, 2), -9, np.int32), seg_obs=np.full(cs, -9, np.int32),
+                     seg_has_view=np.full(cs, 9, np.uint8), seg_active=np.full(cs, 9, np.uint8),
+                     kf_count=np.full(max(f.n_overlap, 1), -9, np.int32), pt_cand_failed=np.full(max(m.n_pt_cand, 1), 9, np.uint8),
+                     seg_cand_failed=np.full(max(m.n_seg_cand, 1), 9, np.uint8))
+            for k, v in b.items():
+                setattr(o, k, v.ctypes.data_as(abi.c_double_p if v.dtype == np.float64 else abi.c_u8_p if v.dtype == np.uint8 else abi.c_i32_p))
+            bufs.append(b)
+        self._chk(self.L.plsvo_candidates_fetch(self.h, n, outs))
+        res = []
+        for o, m, f, b in zip(outs[:n], maps, frames, bufs):
+            r = dict(n_filed_pt=int(o.n_filed_pt), n_filed_seg=int(o.n_filed_seg))
+            for k, v in b.items():
+                cut = o.n_filed_pt if k.startswith("pt_") else o.n_filed_seg
+                if k == "kf_count":
+                    cut = f.n_overlap
+                elif k == "pt_cand_failed":
+                    cut = m.n_pt_cand
+                elif k == "seg_cand_failed":
+                    cut = m.n_seg_cand
+                r[k] = v[:cut].copy()
+            res.append(r)
+        return res
+
+    def candidates_match(self):
+        """plsvo_candidates_match (enqueue only): the direct matcher on the candidates that are on the device"""
+        self._chk(self.L.plsvo_candidates_match(self.h))
+
+    def candidates_match_fetch(self, counts):
+        """plsvo_candidates_match_fetch: per stream found / px [k, 2] / search_level of its k = n_filed_pt + 2 * n_filed_seg entries
+        (points, start points, end points).  counts: the (n_filed_pt, n_filed_seg) of candidates_fetch()"""
+        maps = self._cand_maps
+        n = len(maps)
+        outs = (abi.CandMatchOut * max(n, 1))()
+        bufs = []
+        for o, m in zip(outs, maps):
+            cap = max(m.cap_pt + 2 * m.cap_seg, 1)
+            b = dict(found=np.full(cap, 9, np.uint8), px=np.zeros((cap, 2)), search_level=np.full(cap, -9, np.int32))
+            o.found, o.px, o.search_level = b["found"].ctypes.data_as(abi.c_u8_p), b["px"].ctypes.data_as(abi.c_double_p), b["search_level"].ctypes.data_as(abi.c_i32_p)
+            bufs.append(b)
+        self._chk(self.L.plsvo_candidates_match_fetch(self.h, n, outs))
+        return [{k: v[:npt + 2 * nseg].copy() for k, v in b.items()} for b, (npt, nseg) in zip(bufs, counts)]
+
+    def candidates_dev(self):
+        """plsvo_candidates_dev: the device pointers of the candidate arrays (abi.CandDev)"""
+        d = abi.CandDev()
+        self._chk(self.L.plsvo_candidates_dev(self.h, C.byref(d)))
+        return d
 
     # ---- structure optimisation ----
     def structure_optimize(self, job):

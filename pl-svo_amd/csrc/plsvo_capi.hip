@@ -35,6 +35,7 @@ hipError_t launch_reproject(const ReprojBatchDev& b, hipStream_t stream);
 hipError_t launch_update_seeds(const SeedsBatchDev& b, hipStream_t stream);
 hipError_t launch_close_keyframes(const CloseKfBatchDev& b, hipStream_t stream);     // keyframe_device.hpp, in seeds_kernels.hip
 hipError_t launch_keyframe_decide(const KfDecideBatchDev& b, hipStream_t stream);
+hipError_t launch_map_candidates(const CandBatchDev& b, hipStream_t stream);         // candidates_device.hpp, in seeds_kernels.hip
 hipError_t launch_halfsample(const uint8_t* src, size_t src_pitch, int in_w, int in_h, int in_stride, uint8_t* dst,
                              size_t dst_pitch, int n_slots, int rounding, hipStream_t stream);
 hipError_t launch_copy_level0(const uint8_t* src, size_t src_pitch, int w, int h, int stride, uint8_t* dst, size_t dst_pitch,
@@ -187,6 +188,19 @@ struct plsvo_ctx {
   PoseBatchDev ch_pose{};
   DevBuf ch_d_state, ch_d_ptkeep, ch_d_segkeep, ch_d_s32, ch_d_s64, ch_d_poses;
   DevBuf rec_d;   // plsvo_fetch_pose_records
+  // map candidates (plsvo_candidates_*): the staged tables (cd_d_blob), results / scratch / the matcher's arrays (cd_d_work), a run's frames
+  bool cd_staged = false, cd_ran = false, cd_matched = false;
+  int cd_n = 0, cd_max_level = 0;
+  std::vector<CandMapDev> cd_maps;
+  std::vector<int> cd_kf_slot, cd_cur_slot;
+  std::vector<int64_t> cd_m_off, cd_f_off;
+  std::vector<long long> cd_ov_off;         // per stream of the last run: where its overlap list starts (n + 1 entries)
+  std::vector<size_t> cd_off;               // sections of the fetched part of cd_d_work
+  size_t cd_fetch_bytes = 0, cd_vis_off = 0, cd_vis_bytes = 0, cd_total_m = 0, cd_total_f = 0;
+  plsvo_cand_params cd_params{};
+  DevBuf cd_d_blob, cd_d_work, cd_d_run, cd_d_kfcount;
+  CandBatchDev cd_b{};
+  MatchBatchDev cd_match{};
   unsigned long long run_seq = 0, a_run_seq = 0, p_run_seq = 0, ch_run_seq = 0;   // which resident batch ran last, 0 = not since it was staged (plsvo_pack_pose_records)
 
   // structure optimisation (one-shot batches)
@@ -326,6 +340,7 @@ extern "C" void plsvo_hip_destroy(plsvo_ctx* c) {
   for (auto& ep : c->ev_pool) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
   c->a_d_tailflag.release(); c->a_d_alive_tail.release(); c->a_d_xbuf.release(); c->a_d_order[0].release(); c->a_d_order[1].release(); c->a_d_workkey.release(); c->p_d_workkey.release(); c->p_d_order[0].release(); c->p_d_order[1].release();
   c->p_d_carry.release(); c->p_d_refill_next.release();
+  c->cd_d_blob.release(); c->cd_d_work.release(); c->cd_d_run.release(); c->cd_d_kfcount.release();
   DevBuf* bufs[] = { &c->pyr_slab, &c->pyr_tiled, &c->pyr_upload, &c->a_d_blob, &c->a_d_state, &c->a_d_alive, &c->a_d_pxyz, &c->a_d_puv, &c->a_d_cref,
                      &c->a_d_chi, &c->a_d_log, &c->a_d_poses, &c->p_d_blob, &c->p_d_state, &c->p_d_ptkeep, &c->p_d_segkeep, &c->p_d_s32, &c->p_d_s64,
                      &c->p_d_log, &c->p_d_poses, &c->s_d_in, &c->s_d_out, &c->ch_d_blob, &c->ch_d_work, &c->ch_d_po, &c->ch_d_state,
@@ -2347,6 +2362,321 @@ extern "C" int plsvo_frame_step_batch(plsvo_ctx* c, int n, const plsvo_chain_in*
   int rc = plsvo_chain_stage(c, n, in, params); if (rc) return rc;
   rc = plsvo_chain_run(c); if (rc) return rc;
   return plsvo_chain_fetch(c, n, out);
+}
+
+// ---- map candidates: overlap keyframes' features, first visit, closest view, quality order (candidates_device.hpp) ---------
+namespace {
+struct CandTotals { size_t kf = 0, kfpt = 0, kfseg = 0, pt = 0, seg = 0, ptobs = 0, segobs = 0, ptc = 0, segc = 0, opt = 0, oseg = 0, m = 0, f = 0, vis = 0; };
+// CSR offsets of k lists over `total` entries: start at 0, never decrease; the last one is the length
+static bool cand_csr_ok(const int32_t* off, int k) {
+  if (off[0] != 0) return false;
+  for (int i = 0; i < k; ++i) if (off[i + 1] < off[i]) return false;
+  return true;
+}
+static bool cand_idx_ok(const int32_t* v, size_t n, int lo, int hi) {   // lo <= v < hi
+  for (size_t i = 0; i < n; ++i) if (v[i] < lo || v[i] >= hi) return false;
+  return true;
+}
+}  // namespace
+
+extern "C" int plsvo_candidates_stage(plsvo_ctx* c, int n, const plsvo_cand_map* maps, const plsvo_cand_params* pr) {
+  CTX_CHECK(c);
+  if (n < 0 || !pr || (n > 0 && !maps)) return fail(c, PLSVO_E_INVALID, "candidates_stage: bad arguments");
+  if (pr->cell_size <= 0 || pr->seg_cell_size <= 0 || pr->boundary < 0 || pr->n_pyr_levels < 1 || pr->align_max_iter < 0 || pr->cam.width <= 0 || pr->cam.height <= 0)
+    return fail(c, PLSVO_E_INVALID, "candidates_stage: bad parameters");
+  CandTotals t;
+  int max_level = 0;
+  std::vector<CandMapDev> md((size_t)n);
+  for (int s = 0; s < n; ++s) {
+    const plsvo_cand_map& I = maps[s];
+    if (I.n_kf < 0 || I.n_pt < 0 || I.n_seg < 0 || I.n_pt_cand < 0 || I.n_seg_cand < 0) return fail(c, PLSVO_E_INVALID, "candidates_stage: negative count");
+    if (I.n_kf > 0 && (!I.kf_T || !I.kf_slot || !I.kf_pt_off || !I.kf_seg_off)) return fail(c, PLSVO_E_INVALID, "candidates_stage: null keyframe table");
+    if (I.n_pt > 0 && (!I.pt_pos || !I.pt_type || !I.pt_obs_off)) return fail(c, PLSVO_E_INVALID, "candidates_stage: null point table");
+    if (I.n_seg > 0 && (!I.seg_spos || !I.seg_epos || !I.seg_type || !I.seg_obs_off)) return fail(c, PLSVO_E_INVALID, "candidates_stage: null segment table");
+    if ((I.n_pt_cand > 0 && !I.pt_cand) || (I.n_seg_cand > 0 && !I.seg_cand)) return fail(c, PLSVO_E_INVALID, "candidates_stage: null candidate list");
+    if (I.n_kf > 0 && (!cand_csr_ok(I.kf_pt_off, I.n_kf) || !cand_csr_ok(I.kf_seg_off, I.n_kf))) return fail(c, PLSVO_E_INVALID, "candidates_stage: bad feature list offsets");
+    if ((I.n_pt > 0 && !cand_csr_ok(I.pt_obs_off, I.n_pt)) || (I.n_seg > 0 && !cand_csr_ok(I.seg_obs_off, I.n_seg)))
+      return fail(c, PLSVO_E_INVALID, "candidates_stage: bad observation list offsets");
+    const size_t kfpt = I.n_kf ? (size_t)I.kf_pt_off[I.n_kf] : 0, kfseg = I.n_kf ? (size_t)I.kf_seg_off[I.n_kf] : 0;
+    const size_t ptobs = I.n_pt ? (size_t)I.pt_obs_off[I.n_pt] : 0, segobs = I.n_seg ? (size_t)I.seg_obs_off[I.n_seg] : 0;
+    if ((kfpt && !I.kf_pt_lm) || (kfseg && !I.kf_seg_lm)) return fail(c, PLSVO_E_INVALID, "candidates_stage: null feature list");
+    if (ptobs && (!I.pt_obs_kf || !I.pt_obs_px || !I.pt_obs_f || !I.pt_obs_level || !I.pt_obs_type)) return fail(c, PLSVO_E_INVALID, "candidates_stage: null point observations");
+    if (segobs && (!I.seg_obs_kf || !I.seg_obs_spx || !I.seg_obs_epx || !I.seg_obs_sf || !I.seg_obs_ef || !I.seg_obs_level))
+      return fail(c, PLSVO_E_INVALID, "candidates_stage: null segment observations");
+    if (!cand_idx_ok(I.kf_pt_lm, kfpt, -1, I.n_pt) || !cand_idx_ok(I.kf_seg_lm, kfseg, -1, I.n_seg)) return fail(c, PLSVO_E_INVALID, "candidates_stage: landmark index out of range");
+    if (!cand_idx_ok(I.pt_cand, (size_t)I.n_pt_cand, 0, I.n_pt) || !cand_idx_ok(I.seg_cand, (size_t)I.n_seg_cand, 0, I.n_seg))
+      return fail(c, PLSVO_E_INVALID, "candidates_stage: candidate index out of range");
+    if (!cand_idx_ok(I.pt_obs_kf, ptobs, 0, I.n_kf) || !cand_idx_ok(I.seg_obs_kf, segobs, 0, I.n_kf)) return fail(c, PLSVO_E_INVALID, "candidates_stage: observation keyframe out of range");
+    if (!cand_idx_ok(I.pt_type, (size_t)I.n_pt, PLSVO_LM_DELETED, PLSVO_LM_GOOD + 1) || !cand_idx_ok(I.seg_type, (size_t)I.n_seg, PLSVO_LM_DELETED, PLSVO_LM_GOOD + 1))
+      return fail(c, PLSVO_E_INVALID, "candidates_stage: unknown landmark type");
+    if (!cand_idx_ok(I.kf_slot, (size_t)I.n_kf, 0, INT32_MAX)) return fail(c, PLSVO_E_INVALID, "candidates_stage: negative pyramid slot");
+    if (!cand_idx_ok(I.pt_obs_level, ptobs, 0, PLSVO_MAX_LEVELS) || !cand_idx_ok(I.seg_obs_level, segobs, 0, PLSVO_MAX_LEVELS))
+      return fail(c, PLSVO_E_INVALID, "candidates_stage: observation level out of range");
+    bool edgelet = false;
+    for (size_t k = 0; k < ptobs; ++k) {
+      if (I.pt_obs_type[k] == PLSVO_FTR_EDGELET) edgelet = true;
+      else if (I.pt_obs_type[k] != PLSVO_FTR_CORNER) return fail(c, PLSVO_E_INVALID, "candidates_stage: unknown feature type");
+      max_level = std::max(max_level, (int)I.pt_obs_level[k]);
+    }
+    if (edgelet && !I.pt_obs_grad) return fail(c, PLSVO_E_INVALID, "candidates_stage: edgelets without pt_obs_grad");
+    for (size_t k = 0; k < segobs; ++k) max_level = std::max(max_level, (int)I.seg_obs_level[k]);
+    CandMapDev& M = md[(size_t)s];
+    M.n_kf = I.n_kf; M.n_pt = I.n_pt; M.n_seg = I.n_seg; M.n_pt_cand = I.n_pt_cand; M.n_seg_cand = I.n_seg_cand;
+    M.cap_pt = I.n_pt + I.n_pt_cand; M.cap_seg = I.n_seg + I.n_seg_cand; M.stream = s;
+    M.kf_off = (long long)t.kf; M.kfpt_off = (long long)t.kfpt; M.kfseg_off = (long long)t.kfseg; M.pt_off = (long long)t.pt; M.seg_off = (long long)t.seg;
+    M.ptobs_off = (long long)t.ptobs; M.segobs_off = (long long)t.segobs; M.ptc_off = (long long)t.ptc; M.segc_off = (long long)t.segc;
+    M.opt_off = (long long)t.opt; M.oseg_off = (long long)t.oseg; M.m_off = (long long)t.m; M.f_off = (long long)t.f;
+    M.vis_pt_off = (long long)t.vis; t.vis += ((size_t)I.n_pt + 63) & ~(size_t)63;
+    M.vis_seg_off = (long long)t.vis; t.vis += ((size_t)I.n_seg + 63) & ~(size_t)63;
+    t.kf += (size_t)I.n_kf; t.kfpt += kfpt; t.kfseg += kfseg; t.pt += (size_t)I.n_pt; t.seg += (size_t)I.n_seg; t.ptobs += ptobs; t.segobs += segobs;
+    t.ptc += (size_t)I.n_pt_cand; t.segc += (size_t)I.n_seg_cand; t.opt += (size_t)M.cap_pt; t.oseg += (size_t)M.cap_seg;
+    t.m += (size_t)M.cap_pt + 2 * (size_t)M.cap_seg; t.f += (size_t)I.n_kf + 1;
+  }
+  if (t.m > (size_t)INT32_MAX || t.f > (size_t)INT32_MAX || t.vis > (size_t)INT32_MAX) return fail(c, PLSVO_E_CAPACITY, "candidates_stage: batch too large");
+  c->cd_staged = false; c->cd_ran = false; c->cd_matched = false;
+  if (n == 0) { c->cd_n = 0; c->cd_staged = true; c->cd_maps.clear(); c->cd_m_off.clear(); c->cd_f_off.clear(); c->cd_params = *pr; return PLSVO_OK; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t N = (size_t)n;
+  Blob blob;
+  const size_t b_maps = blob.add(md);
+  const size_t b_kfT = blob.reserve<double>(t.kf * 7), b_kfpo = blob.reserve<int>(t.kf + N), b_kfpl = blob.reserve<int>(t.kfpt), b_kfso = blob.reserve<int>(t.kf + N),
+               b_kfsl = blob.reserve<int>(t.kfseg);
+  const size_t b_ppos = blob.reserve<double>(t.pt * 3), b_ptype = blob.reserve<int>(t.pt), b_pobo = blob.reserve<int>(t.pt + N), b_pokf = blob.reserve<int>(t.ptobs),
+               b_popx = blob.reserve<double>(t.ptobs * 2), b_pof = blob.reserve<double>(t.ptobs * 3), b_polv = blob.reserve<int>(t.ptobs),
+               b_poty = blob.reserve<uint8_t>(t.ptobs), b_pogr = blob.reserve<double>(t.ptobs * 2);
+  const size_t b_sspos = blob.reserve<double>(t.seg * 3), b_sepos = blob.reserve<double>(t.seg * 3), b_stype = blob.reserve<int>(t.seg), b_sobo = blob.reserve<int>(t.seg + N),
+               b_sokf = blob.reserve<int>(t.segobs), b_sospx = blob.reserve<double>(t.segobs * 2), b_soepx = blob.reserve<double>(t.segobs * 2),
+               b_sosf = blob.reserve<double>(t.segobs * 3), b_soef = blob.reserve<double>(t.segobs * 3), b_solv = blob.reserve<int>(t.segobs);
+  const size_t b_ptc = blob.reserve<int>(t.ptc), b_segc = blob.reserve<int>(t.segc), b_fT = blob.reserve<double>(t.f * 7), b_fslot = blob.reserve<int>(t.f);
+  auto put = [&](size_t sec, size_t at, const void* src, size_t count, size_t elem) {
+    if (count) { if (src) memcpy(blob.host.data() + sec + at * elem, src, count * elem); else memset(blob.host.data() + sec + at * elem, 0, count * elem); }
+  };
+  c->cd_kf_slot.assign(t.kf, 0);
+  c->cd_m_off.resize(N); c->cd_f_off.resize(N);
+  for (int s = 0; s < n; ++s) {
+    const plsvo_cand_map& I = maps[s];
+    const CandMapDev& M = md[(size_t)s];
+    const size_t nk = (size_t)I.n_kf, np = (size_t)I.n_pt, ns = (size_t)I.n_seg;
+    const size_t kfpt = nk ? (size_t)I.kf_pt_off[nk] : 0, kfseg = nk ? (size_t)I.kf_seg_off[nk] : 0, ptobs = np ? (size_t)I.pt_obs_off[np] : 0, segobs = ns ? (size_t)I.seg_obs_off[ns] : 0;
+    const size_t S = (size_t)s;
+    put(b_kfT, (size_t)M.kf_off * 7, I.kf_T, nk * 7, sizeof(double));
+    put(b_kfpo, (size_t)M.kf_off + S, nk ? I.kf_pt_off : nullptr, nk + 1, sizeof(int));
+    put(b_kfso, (size_t)M.kf_off + S, nk ? I.kf_seg_off : nullptr, nk + 1, sizeof(int));
+    put(b_kfpl, (size_t)M.kfpt_off, I.kf_pt_lm, kfpt, sizeof(int)); put(b_kfsl, (size_t)M.kfseg_off, I.kf_seg_lm, kfseg, sizeof(int));
+    put(b_ppos, (size_t)M.pt_off * 3, I.pt_pos, np * 3, sizeof(double)); put(b_ptype, (size_t)M.pt_off, I.pt_type, np, sizeof(int));
+    put(b_pobo, (size_t)M.pt_off + S, np ? I.pt_obs_off : nullptr, np + 1, sizeof(int));
+    put(b_pokf, (size_t)M.ptobs_off, I.pt_obs_kf, ptobs, sizeof(int)); put(b_popx, (size_t)M.ptobs_off * 2, I.pt_obs_px, ptobs * 2, sizeof(double));
+    put(b_pof, (size_t)M.ptobs_off * 3, I.pt_obs_f, ptobs * 3, sizeof(double)); put(b_polv, (size_t)M.ptobs_off, I.pt_obs_level, ptobs, sizeof(int));
+    put(b_poty, (size_t)M.ptobs_off, I.pt_obs_type, ptobs, 1); put(b_pogr, (size_t)M.ptobs_off * 2, I.pt_obs_grad, ptobs * 2, sizeof(double));
+    put(b_sspos, (size_t)M.seg_off * 3, I.seg_spos, ns * 3, sizeof(double)); put(b_sepos, (size_t)M.seg_off * 3, I.seg_epos, ns * 3, sizeof(double));
+    put(b_stype, (size_t)M.seg_off, I.seg_type, ns, sizeof(int)); put(b_sobo, (size_t)M.seg_off + S, ns ? I.seg_obs_off : nullptr, ns + 1, sizeof(int));
+    put(b_sokf, (size_t)M.segobs_off, I.seg_obs_kf, segobs, sizeof(int));
+    put(b_sospx, (size_t)M.segobs_off * 2, I.seg_obs_spx, segobs * 2, sizeof(double)); put(b_soepx, (size_t)M.segobs_off * 2, I.seg_obs_epx, segobs * 2, sizeof(double));
+    put(b_sosf, (size_t)M.segobs_off * 3, I.seg_obs_sf, segobs * 3, sizeof(double)); put(b_soef, (size_t)M.segobs_off * 3, I.seg_obs_ef, segobs * 3, sizeof(double));
+    put(b_solv, (size_t)M.segobs_off, I.seg_obs_level, segobs, sizeof(int));
+    put(b_ptc, (size_t)M.ptc_off, I.pt_cand, (size_t)I.n_pt_cand, sizeof(int)); put(b_segc, (size_t)M.segc_off, I.seg_cand, (size_t)I.n_seg_cand, sizeof(int));
+    // the matcher's frame table: the keyframes; the new frame's entry (identity until a run writes it)
+    put(b_fT, (size_t)M.f_off * 7, I.kf_T, nk * 7, sizeof(double)); put(b_fslot, (size_t)M.f_off, I.kf_slot, nk, sizeof(int));
+    const double ident[7] = { 0, 0, 0, 1, 0, 0, 0 };
+    put(b_fT, ((size_t)M.f_off + nk) * 7, ident, 7, sizeof(double)); put(b_fslot, (size_t)M.f_off + nk, nullptr, 1, sizeof(int));
+    if (nk) memcpy(c->cd_kf_slot.data() + M.kf_off, I.kf_slot, nk * sizeof(int));
+    c->cd_m_off[S] = M.m_off; c->cd_f_off[S] = M.f_off;
+  }
+  int rc;
+  if ((rc = upload_blob(c, c->cd_d_blob, blob))) return rc;
+  // device work: results first (what a fetch brings back), then scratch, then the matcher's arrays and its results
+  Carver cv;
+  const size_t w_cnt = cv.take<int>(N * 2), w_plm = cv.take<int>(t.opt), w_ppx = cv.take<double>(t.opt * 2), w_pcell = cv.take<int>(t.opt), w_pobs = cv.take<int>(t.opt),
+               w_pview = cv.take<uint8_t>(t.opt), w_pact = cv.take<uint8_t>(t.opt), w_slm = cv.take<int>(t.oseg), w_spx = cv.take<double>(t.oseg * 4),
+               w_scell = cv.take<int>(t.oseg * 2), w_sobs = cv.take<int>(t.oseg), w_sview = cv.take<uint8_t>(t.oseg), w_sact = cv.take<uint8_t>(t.oseg),
+               w_pfail = cv.take<uint8_t>(t.ptc), w_sfail = cv.take<uint8_t>(t.segc);
+  c->cd_fetch_bytes = cv.off;
+  const size_t w_vis = cv.take<unsigned int>(t.vis), w_kfpos = cv.take<double>(t.kf * 3), w_tplm = cv.take<int>(t.opt), w_tppx = cv.take<double>(t.opt * 2),
+               w_tpcell = cv.take<int>(t.opt), w_tslm = cv.take<int>(t.oseg), w_tspx = cv.take<double>(t.oseg * 4), w_tscell = cv.take<int>(t.oseg * 2);
+  const size_t w_mcf = cv.take<int>(t.m), w_mrf = cv.take<int>(t.m), w_mrpx = cv.take<double>(t.m * 2), w_mrf3 = cv.take<double>(t.m * 3), w_mlv = cv.take<int>(t.m),
+               w_mty = cv.take<uint8_t>(t.m), w_mgr = cv.take<double>(t.m * 2), w_mpos = cv.take<double>(t.m * 3), w_mpx = cv.take<double>(t.m * 2), w_mact = cv.take<uint8_t>(t.m);
+  const size_t w_opx = cv.take<double>(t.m * 2), w_olev = cv.take<int>(t.m), w_oit = cv.take<int>(t.m), w_ofound = cv.take<uint8_t>(t.m);
+  HIP_TRY(c, c->cd_d_work.ensure(cv.off + 256));
+  char* din = reinterpret_cast<char*>(c->cd_d_blob.p); char* dw = reinterpret_cast<char*>(c->cd_d_work.p);
+  auto D = [&](size_t o) { return reinterpret_cast<double*>(din + o); };
+  auto Iv = [&](size_t o) { return reinterpret_cast<int*>(din + o); };
+  auto WD = [&](size_t o) { return reinterpret_cast<double*>(dw + o); };
+  auto WI = [&](size_t o) { return reinterpret_cast<int*>(dw + o); };
+  auto WB = [&](size_t o) { return reinterpret_cast<uint8_t*>(dw + o); };
+  CandBatchDev b{};
+  b.maps = reinterpret_cast<const CandMapDev*>(din + b_maps); b.n_jobs = n;
+  b.fx = pr->cam.fx; b.fy = pr->cam.fy; b.cx = pr->cam.cx; b.cy = pr->cam.cy; b.cam_width = pr->cam.width; b.cam_height = pr->cam.height;
+  b.cell_size = pr->cell_size; b.grid_n_cols = (pr->cam.width + pr->cell_size - 1) / pr->cell_size;
+  b.seg_cell_size = pr->seg_cell_size; b.seg_grid_n_cols = (pr->cam.width + pr->seg_cell_size - 1) / pr->seg_cell_size; b.boundary = pr->boundary;
+  b.kf_T = D(b_kfT); b.kf_pt_off = Iv(b_kfpo); b.kf_pt_lm = Iv(b_kfpl); b.kf_seg_off = Iv(b_kfso); b.kf_seg_lm = Iv(b_kfsl);
+  b.pt_pos = D(b_ppos); b.pt_type = Iv(b_ptype); b.pt_obs_off = Iv(b_pobo); b.pt_obs_kf = Iv(b_pokf); b.pt_obs_px = D(b_popx); b.pt_obs_f = D(b_pof);
+  b.pt_obs_level = Iv(b_polv); b.pt_obs_type = reinterpret_cast<const uint8_t*>(din + b_poty); b.pt_obs_grad = D(b_pogr);
+  b.seg_spos = D(b_sspos); b.seg_epos = D(b_sepos); b.seg_type = Iv(b_stype); b.seg_obs_off = Iv(b_sobo); b.seg_obs_kf = Iv(b_sokf);
+  b.seg_obs_spx = D(b_sospx); b.seg_obs_epx = D(b_soepx); b.seg_obs_sf = D(b_sosf); b.seg_obs_ef = D(b_soef); b.seg_obs_level = Iv(b_solv);
+  b.pt_cand = Iv(b_ptc); b.seg_cand = Iv(b_segc);
+  b.visit = reinterpret_cast<unsigned int*>(dw + w_vis); b.kf_pos = WD(w_kfpos);
+  b.t_pt_lm = WI(w_tplm); b.t_pt_px = WD(w_tppx); b.t_pt_cell = WI(w_tpcell); b.t_seg_lm = WI(w_tslm); b.t_seg_px = WD(w_tspx); b.t_seg_cell = WI(w_tscell);
+  b.counts = WI(w_cnt);
+  b.o_pt_lm = WI(w_plm); b.o_pt_px = WD(w_ppx); b.o_pt_cell = WI(w_pcell); b.o_pt_obs = WI(w_pobs); b.o_pt_view = WB(w_pview); b.o_pt_active = WB(w_pact);
+  b.o_seg_lm = WI(w_slm); b.o_seg_px = WD(w_spx); b.o_seg_cell = WI(w_scell); b.o_seg_obs = WI(w_sobs); b.o_seg_view = WB(w_sview); b.o_seg_active = WB(w_sact);
+  b.pt_cand_failed = WB(w_pfail); b.seg_cand_failed = WB(w_sfail);
+  b.frame_T = D(b_fT); b.frame_slot = Iv(b_fslot);
+  b.m_cur_frame = WI(w_mcf); b.m_ref_frame = WI(w_mrf); b.m_ref_px = WD(w_mrpx); b.m_ref_f = WD(w_mrf3); b.m_ref_level = WI(w_mlv); b.m_ref_type = WB(w_mty);
+  b.m_ref_grad = WD(w_mgr); b.m_pos = WD(w_mpos); b.m_px_cur = WD(w_mpx); b.m_active = WB(w_mact);
+  c->cd_b = b;
+  MatchBatchDev mb{};
+  mb.fx = b.fx; mb.fy = b.fy; mb.cx = b.cx; mb.cy = b.cy; mb.cam_width = b.cam_width; mb.cam_height = b.cam_height;
+  mb.n = (int)t.m; mb.n_pyr_levels = pr->n_pyr_levels; mb.align_max_iter = pr->align_max_iter;
+  mb.frame_T = b.frame_T; mb.frame_slot = b.frame_slot; mb.cur_frame = b.m_cur_frame; mb.ref_frame = b.m_ref_frame;
+  mb.ref_px = b.m_ref_px; mb.ref_f = b.m_ref_f; mb.ref_level = b.m_ref_level; mb.ref_type = b.m_ref_type; mb.ref_grad = b.m_ref_grad;
+  mb.pos = b.m_pos; mb.px_cur = b.m_px_cur; mb.active = b.m_active;
+  mb.px_out = WD(w_opx); mb.search_level = WI(w_olev); mb.n_iter = WI(w_oit); mb.found = WB(w_ofound);
+  c->cd_match = mb;
+  c->cd_off = { w_cnt, w_plm, w_ppx, w_pcell, w_pobs, w_pview, w_pact, w_slm, w_spx, w_scell, w_sobs, w_sview, w_sact, w_pfail, w_sfail };
+  c->cd_vis_off = w_vis; c->cd_vis_bytes = t.vis * sizeof(unsigned int);
+  c->cd_maps = std::move(md); c->cd_params = *pr; c->cd_n = n; c->cd_total_m = t.m; c->cd_total_f = t.f; c->cd_max_level = max_level;
+  c->cd_staged = true;
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_run(plsvo_ctx* c, int n, const plsvo_cand_frame* fr) {
+  CTX_CHECK(c);
+  if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_run: no staged map tables");
+  if (n != c->cd_n || (n > 0 && !fr)) return fail(c, PLSVO_E_INVALID, "candidates_run: n does not match the staged batch");
+  size_t t_ov = 0;
+  for (int s = 0; s < n; ++s) {
+    if (fr[s].n_overlap < 0 || fr[s].cur_slot < 0) return fail(c, PLSVO_E_INVALID, "candidates_run: negative count or slot");
+    if (fr[s].n_overlap > 0 && !fr[s].overlap_idx) return fail(c, PLSVO_E_INVALID, "candidates_run: null overlap list");
+    if (!cand_idx_ok(fr[s].overlap_idx, (size_t)fr[s].n_overlap, 0, c->cd_maps[(size_t)s].n_kf)) return fail(c, PLSVO_E_INVALID, "candidates_run: overlap index outside the keyframe table");
+    t_ov += (size_t)fr[s].n_overlap;
+  }
+  c->cd_ran = false; c->cd_matched = false;
+  c->cd_ov_off.assign((size_t)n + 1, 0);
+  if (n == 0) { c->cd_ran = true; return PLSVO_OK; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  Blob blob;
+  const size_t b_jobs = blob.reserve<CandJobDev>((size_t)n), b_ov = blob.reserve<int>(t_ov);
+  CandJobDev* jobs = blob.at<CandJobDev>(b_jobs); int* ov = blob.at<int>(b_ov);
+  c->cd_cur_slot.resize((size_t)n);
+  size_t o = 0;
+  for (int s = 0; s < n; ++s) {
+    CandJobDev& J = jobs[s];
+    memcpy(J.T, fr[s].T_f_w, sizeof(J.T)); J.d_T = fr[s].d_T_f_w; J.cur_slot = fr[s].cur_slot; J.n_ov = fr[s].n_overlap; J.ov_off = (long long)o;
+    if (J.n_ov) memcpy(ov + o, fr[s].overlap_idx, (size_t)J.n_ov * sizeof(int));
+    c->cd_cur_slot[(size_t)s] = fr[s].cur_slot; c->cd_ov_off[(size_t)s] = (long long)o;
+    o += (size_t)J.n_ov;
+  }
+  c->cd_ov_off[(size_t)n] = (long long)o;
+  int rc;
+  if ((rc = upload_blob(c, c->cd_d_run, blob))) return rc;
+  HIP_TRY(c, c->cd_d_kfcount.ensure(std::max(t_ov, (size_t)1) * sizeof(int)));
+  CandBatchDev b = c->cd_b;
+  const char* dr = reinterpret_cast<const char*>(c->cd_d_run.p);
+  b.jobs = reinterpret_cast<const CandJobDev*>(dr + b_jobs); b.overlap_idx = reinterpret_cast<const int*>(dr + b_ov); b.kf_count = c->cd_d_kfcount.as<int>();
+  {
+    EventPair ep{}; prof_begin(c, PLSVO_K_CANDIDATES, &ep);
+    // the first-visit words are all ones ahead of EVERY launch: a run must not see the visits of the one before
+    hipError_t rearm_then_launch = hipSuccess;
+    if (c->cd_vis_bytes) rearm_then_launch = hipMemsetAsync(reinterpret_cast<char*>(c->cd_d_work.p) + c->cd_vis_off, 0xff, c->cd_vis_bytes, c->stream);
+    if (rearm_then_launch == hipSuccess) rearm_then_launch = launch_map_candidates(b, c->stream);
+    prof_end(c, PLSVO_K_CANDIDATES, &ep);            // ahead of the error return: the event pair goes back to the pool either way
+    HIP_TRY(c, rearm_then_launch);
+  }
+  c->cd_ran = true;
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_fetch(plsvo_ctx* c, int n, plsvo_cand_out* out) {
+  CTX_CHECK(c);
+  if (!c->cd_staged || !c->cd_ran) return fail(c, PLSVO_E_STATE, "candidates_fetch: no run to fetch");
+  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_fetch: n does not match the staged batch");
+  if (n == 0) return PLSVO_OK;
+  std::vector<char> h(c->cd_fetch_bytes);
+  const size_t t_ov = (size_t)c->cd_ov_off[(size_t)n];
+  std::vector<int> kfc(std::max(t_ov, (size_t)1));
+  HIP_TRY(c, hipMemcpyAsync(h.data(), c->cd_d_work.p, h.size(), hipMemcpyDeviceToHost, c->stream));
+  if (t_ov) HIP_TRY(c, hipMemcpyAsync(kfc.data(), c->cd_d_kfcount.p, t_ov * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const size_t* W = c->cd_off.data();
+  const int* cnt = reinterpret_cast<const int*>(h.data() + W[0]);
+  auto cp = [&](void* dst, size_t sec, size_t at, size_t count, size_t elem) { if (dst && count) memcpy(dst, h.data() + sec + at * elem, count * elem); };
+  for (int s = 0; s < n; ++s) {
+    const CandMapDev& M = c->cd_maps[(size_t)s];
+    plsvo_cand_out& O = out[s];
+    const size_t np = (size_t)cnt[2 * s], ns = (size_t)cnt[2 * s + 1], po = (size_t)M.opt_off, so = (size_t)M.oseg_off;
+    O.n_filed_pt = (int32_t)np; O.n_filed_seg = (int32_t)ns;
+    cp(O.pt_lm, W[1], po, np, sizeof(int)); cp(O.pt_px, W[2], po * 2, np * 2, sizeof(double)); cp(O.pt_cell, W[3], po, np, sizeof(int));
+    cp(O.pt_obs, W[4], po, np, sizeof(int)); cp(O.pt_has_view, W[5], po, np, 1); cp(O.pt_active, W[6], po, np, 1);
+    cp(O.seg_lm, W[7], so, ns, sizeof(int)); cp(O.seg_px, W[8], so * 4, ns * 4, sizeof(double)); cp(O.seg_cell, W[9], so * 2, ns * 2, sizeof(int));
+    cp(O.seg_obs, W[10], so, ns, sizeof(int)); cp(O.seg_has_view, W[11], so, ns, 1); cp(O.seg_active, W[12], so, ns, 1);
+    cp(O.pt_cand_failed, W[13], (size_t)M.ptc_off, (size_t)M.n_pt_cand, 1); cp(O.seg_cand_failed, W[14], (size_t)M.segc_off, (size_t)M.n_seg_cand, 1);
+    const size_t a = (size_t)c->cd_ov_off[(size_t)s], e = (size_t)c->cd_ov_off[(size_t)s + 1];
+    if (O.kf_count && e > a) memcpy(O.kf_count, kfc.data() + a, (e - a) * sizeof(int));
+  }
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_match(plsvo_ctx* c) {
+  CTX_CHECK(c);
+  if (!c->cd_staged || !c->cd_ran) return fail(c, PLSVO_E_STATE, "candidates_match: no candidates on the device");
+  if (c->cd_n == 0 || c->cd_total_m == 0) { c->cd_matched = true; return PLSVO_OK; }
+  if (!c->pyr.base) return fail(c, PLSVO_E_STATE, "candidates_match: pyramids not configured");
+  const plsvo_cand_params& pr = c->cd_params;
+  if (pr.n_pyr_levels > c->pyr.n_levels) return fail(c, PLSVO_E_INVALID, "candidates_match: n_pyr_levels exceeds the configured pyramid");
+  if (pr.cam.width != c->pyr.w[0] || pr.cam.height != c->pyr.h[0]) return fail(c, PLSVO_E_INVALID, "candidates_match: camera size does not match the configured pyramid");
+  if (c->cd_max_level >= c->pyr.n_levels) return fail(c, PLSVO_E_CAPACITY, "candidates_match: observation level outside the configured pyramid");
+  for (int v : c->cd_kf_slot) if (v >= c->pyr.n_slots) return fail(c, PLSVO_E_CAPACITY, "candidates_match: pyramid slot out of range");
+  for (int v : c->cd_cur_slot) if (v >= c->pyr.n_slots) return fail(c, PLSVO_E_CAPACITY, "candidates_match: pyramid slot out of range");
+  HIP_TRY(c, hipSetDevice(c->device));
+  MatchBatchDev mb = c->cd_match;
+  mb.pyr_base = c->pyr.base; mb.slot_bytes = c->pyr.slot_bytes; mb.width = c->pyr.w[0]; mb.height = c->pyr.h[0];
+  {
+    EventPair ep{}; prof_begin(c, PLSVO_K_MATCH, &ep);
+    const hipError_t launched = launch_match_direct(mb, c->stream);
+    prof_end(c, PLSVO_K_MATCH, &ep);                 // ahead of the error return, as in plsvo_candidates_run
+    HIP_TRY(c, launched);
+  }
+  c->cd_matched = true;
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_match_fetch(plsvo_ctx* c, int n, plsvo_cand_match_out* out) {
+  CTX_CHECK(c);
+  if (!c->cd_staged || !c->cd_ran || !c->cd_matched) return fail(c, PLSVO_E_STATE, "candidates_match_fetch: no match to fetch");
+  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_match_fetch: n does not match the staged batch");
+  if (n == 0 || c->cd_total_m == 0) return PLSVO_OK;
+  const size_t NM = c->cd_total_m;
+  std::vector<int> cnt((size_t)n * 2), lev(NM);
+  std::vector<double> px(NM * 2);
+  std::vector<uint8_t> found(NM);
+  const MatchBatchDev& mb = c->cd_match;
+  HIP_TRY(c, hipMemcpyAsync(cnt.data(), c->cd_b.counts, cnt.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(px.data(), mb.px_out, NM * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(lev.data(), mb.search_level, NM * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(found.data(), mb.found, NM, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (int s = 0; s < n; ++s) {
+    const size_t at = (size_t)c->cd_maps[(size_t)s].m_off, k = (size_t)cnt[2 * s] + 2 * (size_t)cnt[2 * s + 1];
+    if (!k) continue;
+    if (out[s].found) memcpy(out[s].found, found.data() + at, k);
+    if (out[s].px) memcpy(out[s].px, px.data() + 2 * at, k * 2 * sizeof(double));
+    if (out[s].search_level) memcpy(out[s].search_level, lev.data() + at, k * sizeof(int));
+  }
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_dev(plsvo_ctx* c, plsvo_cand_dev* o) {
+  CTX_CHECK(c);
+  if (!o) return fail(c, PLSVO_E_INVALID, "candidates_dev: bad arguments");
+  if (!c->cd_staged || !c->cd_ran || c->cd_n == 0) return fail(c, PLSVO_E_STATE, "candidates_dev: no candidates on the device");
+  const CandBatchDev& b = c->cd_b; const MatchBatchDev& mb = c->cd_match;
+  o->n_entries = (int64_t)c->cd_total_m; o->n_frames = (int64_t)c->cd_total_f;
+  o->m_off = c->cd_m_off.data(); o->f_off = c->cd_f_off.data();
+  o->d_counts = b.counts; o->d_frame_T = b.frame_T; o->d_frame_slot = b.frame_slot; o->d_cur_frame = b.m_cur_frame; o->d_ref_frame = b.m_ref_frame;
+  o->d_ref_px = b.m_ref_px; o->d_ref_f = b.m_ref_f; o->d_ref_level = b.m_ref_level; o->d_ref_type = b.m_ref_type; o->d_ref_grad = b.m_ref_grad;
+  o->d_pos = b.m_pos; o->d_px_cur = b.m_px_cur; o->d_active = b.m_active;
+  o->d_found = mb.found; o->d_px_out = mb.px_out; o->d_search_level = mb.search_level;
+  return PLSVO_OK;
 }
 
 // ---- trajectory record (host only; app/run_pipeline.cpp:425-451) ---------------------------------------

@@ -298,6 +298,57 @@ struct KfDecideBatchDev {
   double* delta_t; double* delta_r; // per overlap entry
 };
 
+// map candidates (candidates_device.hpp, include/plsvo_hip.h plsvo_candidates_*): one wave per stream.  The streams' map tables are
+// concatenated and stay resident; a stream's record holds its counts and offsets (in entries, not bytes).  CSR offset arrays keep the
+// caller's stream-relative values: kf_pt_off of stream s has n_kf + 1 entries from kf_off + s, pt_obs_off n_pt + 1 from pt_off + s.
+struct CandMapDev {
+  int n_kf, n_pt, n_seg, n_pt_cand, n_seg_cand;
+  int cap_pt, cap_seg;              // n_pt + n_pt_cand, n_seg + n_seg_cand: the most that can be filed
+  int stream;                       // s
+  long long kf_off;                 // keyframes: kf_T, kf_pos
+  long long kfpt_off, kfseg_off;    // the keyframes' feature lists
+  long long pt_off, seg_off;        // landmarks
+  long long ptobs_off, segobs_off;  // observations
+  long long ptc_off, segc_off;      // the map's candidate lists (and their failure flags)
+  long long opt_off, oseg_off;      // filed landmarks: scratch in filing order, results in output order (capacity rows)
+  long long m_off;                  // the matcher's candidates: cap_pt + 2 * cap_seg entries
+  long long f_off;                  // the matcher's frame table: n_kf keyframes, then the new frame
+  long long vis_pt_off, vis_seg_off;// first-visit words, rows padded to 64 words
+};
+struct CandJobDev {                 // one stream's frame (plsvo_candidates_run)
+  double T[7];
+  const double* d_T;                // device pointer read instead of T, or null
+  int cur_slot, n_ov;
+  long long ov_off;                 // overlap list and the counts per overlap keyframe
+};
+struct CandBatchDev {
+  const CandMapDev* maps; const CandJobDev* jobs; int n_jobs;
+  double fx, fy, cx, cy; int cam_width, cam_height;
+  int cell_size, grid_n_cols, seg_cell_size, seg_grid_n_cols, boundary;
+  // staged tables
+  const double* kf_T; const int* kf_pt_off; const int* kf_pt_lm; const int* kf_seg_off; const int* kf_seg_lm;
+  const double* pt_pos; const int* pt_type; const int* pt_obs_off;
+  const int* pt_obs_kf; const double* pt_obs_px; const double* pt_obs_f; const int* pt_obs_level; const uint8_t* pt_obs_type; const double* pt_obs_grad;
+  const double* seg_spos; const double* seg_epos; const int* seg_type; const int* seg_obs_off;
+  const int* seg_obs_kf; const double* seg_obs_spx; const double* seg_obs_epx; const double* seg_obs_sf; const double* seg_obs_ef; const int* seg_obs_level;
+  const int* pt_cand; const int* seg_cand;
+  const int* overlap_idx;           // per run
+  // scratch
+  unsigned int* visit;              // all ones before EVERY launch: the lowest visit index of a landmark (atomicMin)
+  double* kf_pos;                   // 3 per keyframe: Frame::pos()
+  int* t_pt_lm; double* t_pt_px; int* t_pt_cell;        // filed points in filing order
+  int* t_seg_lm; double* t_seg_px; int* t_seg_cell;     // filed segments: 4 doubles, 2 cells
+  // results
+  int* counts;                      // 2 per job: n_filed_pt, n_filed_seg
+  int* o_pt_lm; double* o_pt_px; int* o_pt_cell; int* o_pt_obs; uint8_t* o_pt_view; uint8_t* o_pt_active;
+  int* o_seg_lm; double* o_seg_px; int* o_seg_cell; int* o_seg_obs; uint8_t* o_seg_view; uint8_t* o_seg_active;
+  int* kf_count; uint8_t* pt_cand_failed; uint8_t* seg_cand_failed;
+  // what MatchBatchDev reads
+  double* frame_T; int* frame_slot;
+  int* m_cur_frame; int* m_ref_frame; double* m_ref_px; double* m_ref_f; int* m_ref_level; uint8_t* m_ref_type; double* m_ref_grad;
+  double* m_pos; double* m_px_cur; uint8_t* m_active;
+};
+
 // corner detection (detect_device.hpp, include/plsvo_hip.h plsvo_hip_detect_fast): tile geometry and the launch record
 constexpr int kDetTileW = 64, kDetTileH = 32;          // pixels of a tile that one workgroup decides
 constexpr int kDetImgX0 = 8, kDetImgY0 = 5;            // LDS image origin = tile origin - (8, 5): a halo of 5 (Shi-Tomasi: x - 5 .. x + 4), 8 keeps rows dword-aligned

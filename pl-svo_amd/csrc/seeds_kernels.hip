@@ -22,6 +22,7 @@
 
 #include "match_device.hpp"
 #include "keyframe_device.hpp"   // the keyframe stage's kernels live in this translation unit for its -ffp-contract=off
+#include "candidates_device.hpp" // and the map candidates' kernel
 
 namespace plsvo_hip {
 
@@ -395,6 +396,12 @@ hipError_t launch_close_keyframes(const CloseKfBatchDev& b, hipStream_t stream) 
 hipError_t launch_keyframe_decide(const KfDecideBatchDev& b, hipStream_t stream) {
   if (b.n_jobs <= 0) return hipSuccess;
   hipLaunchKernelGGL(keyframe_decide_kernel, dim3((b.n_jobs + kKfWaves - 1) / kKfWaves), dim3(64 * kKfWaves), 0, stream, b);
+  return hipGetLastError();
+}
+// map candidates (candidates_device.hpp): one wave per stream, four streams per workgroup
+hipError_t launch_map_candidates(const CandBatchDev& b, hipStream_t stream) {
+  if (b.n_jobs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_candidates_kernel, dim3((b.n_jobs + kCandWaves - 1) / kCandWaves), dim3(64 * kCandWaves), 0, stream, b);
   return hipGetLastError();
 }
 

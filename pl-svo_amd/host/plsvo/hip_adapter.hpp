@@ -28,6 +28,7 @@
 #include <cstdlib>
 #include <list>
 #include <type_traits>
+#include <unordered_map>
 #include <utility>
 #include <vector>
 
@@ -1037,6 +1038,163 @@ inline bool setKeyPoints(FrameT& frame) {
   return true;
 }
 }  // namespace keyframe
+}  // namespace plsvo
+
+namespace plsvo {
+namespace reprojector {
+/// One filed landmark of mapCandidates: what Reprojector::reproject files in a cell (the landmark and its projection) together with
+/// what Matcher::findMatchDirect looks up first, the closest-view observation.  Feat3D = Point or LineSeg, FeatT = its feature type.
+template <class Feat3D, class FeatT>
+struct MapCandidate {
+  Feat3D* feat3D = nullptr;
+  double px[4] = {0, 0, 0, 0};      ///< a point's projection in px[0..1]; a segment's start point in px[0..1], end point in px[2..3]
+  int cell[2] = {-1, -1};           ///< a segment has two
+  FeatT* ref_ftr = nullptr;         ///< getCloseViewObs' choice (nullptr for an empty obs_)
+  bool has_view = false;            ///< getCloseViewObs' return value
+  bool active = false;              ///< has_view and not TYPE_DELETED: refine() would call the matcher
+};
+
+/// The candidate set of Reprojector::reprojectMap (src/reprojector.cpp:157-183) in one device call (plsvo_candidates_*): the features
+/// of `overlap_kfs` (a container of (keyframe, count) pairs, as reprojectMap fills it) are visited in order, every landmark once,
+/// projected into `frame`; the map's candidates (containers of Point* / LineSeg*: the .first of map_.point_candidates_.candidates_)
+/// follow.  `keyframes` is Map::keyframes_: every frame an observation of a visited landmark sits in must be in it.
+/// Written back, exactly what the reference has mutated at that point: last_projected_kf_id_ = frame->id_ of every visited landmark,
+/// overlap_kfs[r].second.  n_failed_reproj_ and the deletion of failed map candidates stay with the caller: pt_cand_failed /
+/// seg_cand_failed (optional) receive one flag per candidate.  The filed landmarks arrive in stable descending order of type_ --
+/// a cell's entries in that order are the cell after cell.sort(qualityComparator).
+template <class FramePtrT, class KeyframeList, class OverlapList, class PointCandList, class SegCandList, class PointT, class PointFeatT, class SegT,
+          class SegFeatT>
+inline bool mapCandidates(const FramePtrT& frame, const KeyframeList& keyframes, OverlapList& overlap_kfs, const PointCandList& point_candidates,
+                          const SegCandList& segment_candidates, int cell_size, int seg_cell_size, std::vector<MapCandidate<PointT, PointFeatT> >& points,
+                          std::vector<MapCandidate<SegT, SegFeatT> >& segments, std::vector<uint8_t>* pt_cand_failed = nullptr,
+                          std::vector<uint8_t>* seg_cand_failed = nullptr) {
+  using namespace plsvo_hip_adapter;
+  typedef typename std::remove_reference<decltype(*frame->cam_)>::type Cam;
+  typedef typename std::decay<decltype(frame->T_f_w_)>::type SE3T;
+  // one walk over the lists: the keyframe table, the feature lists as landmark indices, the landmarks in order of first sight
+  std::vector<double> kf_T;
+  std::vector<int32_t> kf_slot, kf_pt_off(1, 0), kf_pt_lm, kf_seg_off(1, 0), kf_seg_lm;
+  std::unordered_map<const void*, int32_t> kf_ptr, pt_ptr, seg_ptr;
+  std::vector<PointT*> pts;
+  std::vector<SegT*> segs;
+  auto index_of = [](const std::unordered_map<const void*, int32_t>& tab, const void* p) { auto it = tab.find(p); return it == tab.end() ? (int32_t)-1 : it->second; };
+  auto pt_index = [&](PointT* p) { int32_t i = index_of(pt_ptr, p); if (i < 0) { i = (int32_t)pts.size(); pts.push_back(p); pt_ptr[p] = i; } return i; };
+  auto seg_index = [&](SegT* p) { int32_t i = index_of(seg_ptr, p); if (i < 0) { i = (int32_t)segs.size(); segs.push_back(p); seg_ptr[p] = i; } return i; };
+  for (auto it = keyframes.begin(); it != keyframes.end(); ++it) {
+    double T[7];
+    se3_traits<SE3T>::get((*it)->T_f_w_, T);
+    kf_T.insert(kf_T.end(), T, T + 7);
+    kf_slot.push_back(0);
+    { const int32_t k = (int32_t)kf_ptr.size(); kf_ptr[&**it] = k; }
+    for (auto f = (*it)->pt_fts_.begin(); f != (*it)->pt_fts_.end(); ++f) kf_pt_lm.push_back((*f)->feat3D ? pt_index((*f)->feat3D) : -1);
+    for (auto f = (*it)->seg_fts_.begin(); f != (*it)->seg_fts_.end(); ++f) kf_seg_lm.push_back((*f)->feat3D ? seg_index((*f)->feat3D) : -1);
+    kf_pt_off.push_back((int32_t)kf_pt_lm.size()); kf_seg_off.push_back((int32_t)kf_seg_lm.size());
+  }
+  std::vector<int32_t> pt_cand, seg_cand, overlap;
+  for (auto it = point_candidates.begin(); it != point_candidates.end(); ++it) pt_cand.push_back(pt_index(*it));
+  for (auto it = segment_candidates.begin(); it != segment_candidates.end(); ++it) seg_cand.push_back(seg_index(*it));
+  for (auto it = overlap_kfs.begin(); it != overlap_kfs.end(); ++it) {
+    const int32_t k = index_of(kf_ptr, &*it->first);
+    if (k < 0) { std::fprintf(stderr, "[plsvo_hip] mapCandidates: an overlap keyframe is not in the keyframe list\n"); return false; }
+    overlap.push_back(k);
+  }
+  // the landmarks' tables and observation lists, in list order
+  std::vector<double> pt_pos, po_px, po_f, po_grad, s_pos, e_pos, so_spx, so_epx, so_sf, so_ef;
+  std::vector<int32_t> pt_type, po_off(1, 0), po_kf, po_level, seg_type, so_off(1, 0), so_kf, so_level;
+  std::vector<uint8_t> po_type;
+  std::vector<PointFeatT*> po_ftr;
+  std::vector<SegFeatT*> so_ftr;
+  auto push = [](std::vector<double>& v, const double* p, int n) { v.insert(v.end(), p, p + n); };
+  for (size_t i = 0; i < pts.size(); ++i) {
+    double p[3]; copy3(pts[i]->pos_, p); push(pt_pos, p, 3);
+    pt_type.push_back((int32_t)pts[i]->type_);
+    for (auto o = pts[i]->obs_.begin(); o != pts[i]->obs_.end(); ++o) {
+      const int32_t k = index_of(kf_ptr, (*o)->frame);
+      if (k < 0) { std::fprintf(stderr, "[plsvo_hip] mapCandidates: an observation's frame is not in the keyframe list\n"); return false; }
+      double f[3]; copy3((*o)->f, f);
+      const double px[2] = { (*o)->px[0], (*o)->px[1] }, g[2] = { (*o)->grad[0], (*o)->grad[1] };
+      po_kf.push_back(k); push(po_px, px, 2); push(po_f, f, 3); push(po_grad, g, 2); po_level.push_back((*o)->level);
+      po_type.push_back((int)(*o)->type == 1 ? PLSVO_FTR_EDGELET : PLSVO_FTR_CORNER);
+      po_ftr.push_back(*o);
+    }
+    po_off.push_back((int32_t)po_kf.size());
+  }
+  for (size_t i = 0; i < segs.size(); ++i) {
+    double p[3]; copy3(segs[i]->spos_, p); push(s_pos, p, 3); copy3(segs[i]->epos_, p); push(e_pos, p, 3);
+    seg_type.push_back((int32_t)segs[i]->type_);
+    for (auto o = segs[i]->obs_.begin(); o != segs[i]->obs_.end(); ++o) {
+      const int32_t k = index_of(kf_ptr, (*o)->frame);
+      if (k < 0) { std::fprintf(stderr, "[plsvo_hip] mapCandidates: an observation's frame is not in the keyframe list\n"); return false; }
+      double sf[3], ef[3]; copy3((*o)->sf, sf); copy3((*o)->ef, ef);
+      const double spx[2] = { (*o)->spx[0], (*o)->spx[1] }, epx[2] = { (*o)->epx[0], (*o)->epx[1] };
+      so_kf.push_back(k); push(so_spx, spx, 2); push(so_epx, epx, 2); push(so_sf, sf, 3); push(so_ef, ef, 3); so_level.push_back((*o)->level);
+      so_ftr.push_back(*o);
+    }
+    so_off.push_back((int32_t)so_kf.size());
+  }
+  plsvo_cand_map m = plsvo_cand_map();
+  m.n_kf = (int32_t)kf_ptr.size(); m.n_pt = (int32_t)pts.size(); m.n_seg = (int32_t)segs.size();
+  m.n_pt_cand = (int32_t)pt_cand.size(); m.n_seg_cand = (int32_t)seg_cand.size();
+  m.kf_T = kf_T.data(); m.kf_slot = kf_slot.data(); m.kf_pt_off = kf_pt_off.data(); m.kf_pt_lm = kf_pt_lm.data(); m.kf_seg_off = kf_seg_off.data();
+  m.kf_seg_lm = kf_seg_lm.data(); m.pt_pos = pt_pos.data(); m.pt_type = pt_type.data(); m.pt_obs_off = po_off.data(); m.pt_obs_kf = po_kf.data();
+  m.pt_obs_px = po_px.data(); m.pt_obs_f = po_f.data(); m.pt_obs_level = po_level.data(); m.pt_obs_type = po_type.data(); m.pt_obs_grad = po_grad.data();
+  m.seg_spos = s_pos.data(); m.seg_epos = e_pos.data(); m.seg_type = seg_type.data(); m.seg_obs_off = so_off.data(); m.seg_obs_kf = so_kf.data();
+  m.seg_obs_spx = so_spx.data(); m.seg_obs_epx = so_epx.data(); m.seg_obs_sf = so_sf.data(); m.seg_obs_ef = so_ef.data(); m.seg_obs_level = so_level.data();
+  m.pt_cand = pt_cand.data(); m.seg_cand = seg_cand.data();
+  plsvo_cand_params pr = plsvo_cand_params();
+  pr.cam = camera_traits<Cam>::get(*frame->cam_);
+  pr.cell_size = cell_size; pr.seg_cell_size = seg_cell_size; pr.boundary = 8; pr.n_pyr_levels = 1; pr.align_max_iter = 10;
+  plsvo_cand_frame fr = plsvo_cand_frame();
+  se3_traits<SE3T>::get(frame->T_f_w_, fr.T_f_w);
+  fr.n_overlap = (int32_t)overlap.size(); fr.overlap_idx = overlap.data();
+  const size_t cap_pt = pts.size() + pt_cand.size() + 1, cap_seg = segs.size() + seg_cand.size() + 1;
+  std::vector<int32_t> o_plm(cap_pt), o_pcell(cap_pt), o_pobs(cap_pt), o_slm(cap_seg), o_scell(2 * cap_seg), o_sobs(cap_seg), o_cnt(overlap.size() + 1);
+  std::vector<double> o_ppx(2 * cap_pt), o_spx(4 * cap_seg);
+  std::vector<uint8_t> o_pview(cap_pt), o_pact(cap_pt), o_sview(cap_seg), o_sact(cap_seg), o_pfail(pt_cand.size() + 1), o_sfail(seg_cand.size() + 1);
+  plsvo_cand_out out = plsvo_cand_out();
+  out.pt_lm = o_plm.data(); out.pt_px = o_ppx.data(); out.pt_cell = o_pcell.data(); out.pt_obs = o_pobs.data(); out.pt_has_view = o_pview.data();
+  out.pt_active = o_pact.data(); out.seg_lm = o_slm.data(); out.seg_px = o_spx.data(); out.seg_cell = o_scell.data(); out.seg_obs = o_sobs.data();
+  out.seg_has_view = o_sview.data(); out.seg_active = o_sact.data(); out.kf_count = o_cnt.data(); out.pt_cand_failed = o_pfail.data();
+  out.seg_cand_failed = o_sfail.data();
+  Context& c = default_context();
+  if (!c.ensure_ctx()) return false;
+  if (plsvo_candidates_stage(c.ctx, 1, &m, &pr) != PLSVO_OK || plsvo_candidates_run(c.ctx, 1, &fr) != PLSVO_OK || plsvo_candidates_fetch(c.ctx, 1, &out) != PLSVO_OK) {
+    std::fprintf(stderr, "[plsvo_hip] mapCandidates failed: %s\n", plsvo_hip_last_error(c.ctx));
+    return false;
+  }
+  // the reference's mutations up to this point
+  {
+    size_t r = 0;
+    for (auto it = overlap_kfs.begin(); it != overlap_kfs.end(); ++it, ++r) {
+      it->second = (typename std::decay<decltype(it->second)>::type)o_cnt[r];
+      for (auto f = it->first->pt_fts_.begin(); f != it->first->pt_fts_.end(); ++f) if ((*f)->feat3D) (*f)->feat3D->last_projected_kf_id_ = frame->id_;
+      for (auto f = it->first->seg_fts_.begin(); f != it->first->seg_fts_.end(); ++f) if ((*f)->feat3D) (*f)->feat3D->last_projected_kf_id_ = frame->id_;
+    }
+  }
+  points.clear(); segments.clear();
+  for (int32_t i = 0; i < out.n_filed_pt; ++i) {
+    MapCandidate<PointT, PointFeatT> mc;
+    const size_t lm = (size_t)o_plm[(size_t)i];
+    mc.feat3D = pts[lm]; mc.px[0] = o_ppx[2 * (size_t)i]; mc.px[1] = o_ppx[2 * (size_t)i + 1]; mc.cell[0] = o_pcell[(size_t)i];
+    mc.ref_ftr = o_pobs[(size_t)i] >= 0 ? po_ftr[(size_t)(po_off[lm] + o_pobs[(size_t)i])] : nullptr;
+    mc.has_view = o_pview[(size_t)i] != 0; mc.active = o_pact[(size_t)i] != 0;
+    points.push_back(mc);
+  }
+  for (int32_t i = 0; i < out.n_filed_seg; ++i) {
+    MapCandidate<SegT, SegFeatT> mc;
+    const size_t lm = (size_t)o_slm[(size_t)i];
+    mc.feat3D = segs[lm];
+    for (int k = 0; k < 4; ++k) mc.px[k] = o_spx[4 * (size_t)i + (size_t)k];
+    mc.cell[0] = o_scell[2 * (size_t)i]; mc.cell[1] = o_scell[2 * (size_t)i + 1];
+    mc.ref_ftr = o_sobs[(size_t)i] >= 0 ? so_ftr[(size_t)(so_off[lm] + o_sobs[(size_t)i])] : nullptr;
+    mc.has_view = o_sview[(size_t)i] != 0; mc.active = o_sact[(size_t)i] != 0;
+    segments.push_back(mc);
+  }
+  if (pt_cand_failed) pt_cand_failed->assign(o_pfail.begin(), o_pfail.begin() + (long)pt_cand.size());
+  if (seg_cand_failed) seg_cand_failed->assign(o_sfail.begin(), o_sfail.begin() + (long)seg_cand.size());
+  return true;
+}
+}  // namespace reprojector
 }  // namespace plsvo
 
 namespace svo = plsvo;  // BASELINE.json spells the upstream name svo::SparseImgAlign

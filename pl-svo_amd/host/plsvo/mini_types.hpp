@@ -42,8 +42,10 @@ struct Camera {  // vk::PinholeCamera look-alike (no distortion)
 struct Frame;
 struct PointFeat;
 struct LineFeat;
-struct Point { Vec3 pos_; std::list<PointFeat*> obs_; };              // Feature3D<PointFeat>::obs_
-struct LineSeg { Vec3 spos_, epos_; std::list<LineFeat*> obs_; };     // Feature3D<LineFeat>::obs_
+// Feature3D<FeatureT> (include/plsvo/feature3D.h:55-59, :98-150): the quality enum, obs_, and the mark Reprojector::setKfCandidates leaves
+enum Feature3DType { TYPE_DELETED, TYPE_CANDIDATE, TYPE_UNKNOWN, TYPE_GOOD };
+struct Point { Vec3 pos_; std::list<PointFeat*> obs_; int type_ = TYPE_UNKNOWN; int last_projected_kf_id_ = -1; };
+struct LineSeg { Vec3 spos_, epos_; std::list<LineFeat*> obs_; int type_ = TYPE_UNKNOWN; int last_projected_kf_id_ = -1; };
 struct Feature { Frame* frame = nullptr; Vec2 px; Vec3 f; int level = 0; };
 struct PointFeat : Feature { enum FeatureType { CORNER, EDGELET }; FeatureType type = CORNER; Vec2 grad; Point* feat3D = nullptr; };
 struct LineFeat : Feature { Vec2 spx, epx, grad; Vec3 sf, ef, line; LineSeg* feat3D = nullptr; double length = 0; };

@@ -29,6 +29,13 @@ A frame then plays the keyframe when needNewKf says so -- measured, like the ref
 every kf_every-th; the keyframe table (pose and the landmark positions of the five key points) grows with it, and the seeds of a
 keyframe's corners start from depth_mean * 2.0 and 0.1 * depth_min of that call (:391).
 
+With map_candidates=True (a per-call backend with map_candidates) steps 2 and 3 take their candidates and reference observations from the
+map-candidate stage (plsvo_candidates_*) instead of keyframe 0: the harness keeps the map tables the stage needs -- the
+keyframes' feature lists, every landmark's observation list with px / f / level, newest first -- restages them when they change (a frame
+becomes a keyframe, a seed converges into the map's candidate list), and hands each frame its pose and its overlap list: the one of
+plsvo_close_keyframes with kf_select, otherwise every keyframe in table order.  The matches reach the pose optimiser in landmark-index
+order, as without it.
+
 `backend` is duck-typed: load_frames(list of level-0 images; HipBackend also takes raw frames with rectify=), sparse_align(job), reproject(job), match_direct(job),
 pose_optimize(job), for mapping structure_optimize(job), update_seeds(job), and for kf_select close_keyframes(job), keyframe_decide(job).  The product backend is HipBackend (C ABI on the GPU, no fallback); tests pass an oracle-backed one
 to check the whole chain end to end."""
@@ -87,6 +94,16 @@ class HipBackend:
 
     def keyframe_decide(self, job):
         return self.ctx.keyframe_decide([job])[0]
+
+    def map_candidates(self, map_job, frame_job, cam, n_pyr_levels, cell_size=30, seg_cell_size=30):
+        """the map-candidate stage and the resident match for one stream: map_job (abi.CandidateMapJob) = the tables to (re)stage, None =
+        they have not changed since the last call.  -> (the stage's result, the matcher's) as capi.Context returns them"""
+        if map_job is not None:
+            self.ctx.candidates_stage([map_job], cam, cell_size, seg_cell_size, 8, n_pyr_levels, 10)
+        self.ctx.candidates_run([frame_job])
+        r = self.ctx.candidates_fetch()[0]
+        self.ctx.candidates_match()
+        return r, self.ctx.candidates_match_fetch([(r["n_filed_pt"], r["n_filed_seg"])])[0]
 
     def detect_corners(self, slot, occupancy=None, cell_size=25, n_levels=3, detection_threshold=20.0):
         """FastDetector::detect on the frame in `slot` (plsvo_hip_detect_fast): abi.CORNER_DTYPE records in cell order"""
@@ -160,9 +177,28 @@ def _occupancy(px, w, h, cell):
     return occ
 
 
+def candidate_map_job(cm):
+    """the harness's map tables (lists, as tests/np_candidates.py reads them) flattened into the CSR arrays of plsvo_cand_map"""
+    def csr(lists):
+        off = np.zeros(len(lists) + 1, np.int32)
+        off[1:] = np.cumsum([len(l) for l in lists])
+        return off
+    po = [o for l in cm["pt_obs"] for o in l]
+    so = [o for l in cm["seg_obs"] for o in l]
+    col = lambda obs, f: [o[f] for o in obs]
+    return abi.CandidateMapJob(
+        kf_T=cm["kf_T"], kf_slot=cm["kf_slot"], kf_pt_off=csr(cm["kf_pt"]), kf_pt_lm=[v for l in cm["kf_pt"] for v in l],
+        kf_seg_off=csr(cm["kf_seg"]), kf_seg_lm=[v for l in cm["kf_seg"] for v in l],
+        pt_pos=cm["pt_pos"], pt_type=cm["pt_type"], pt_obs_off=csr(cm["pt_obs"]), pt_obs_kf=col(po, "kf"), pt_obs_px=col(po, "px"), pt_obs_f=col(po, "f"),
+        pt_obs_level=col(po, "level"), pt_obs_type=col(po, "type"), pt_obs_grad=col(po, "grad"),
+        seg_spos=cm["seg_spos"], seg_epos=cm["seg_epos"], seg_type=cm["seg_type"], seg_obs_off=csr(cm["seg_obs"]), seg_obs_kf=col(so, "kf"),
+        seg_obs_spx=col(so, "spx"), seg_obs_epx=col(so, "epx"), seg_obs_sf=col(so, "sf"), seg_obs_ef=col(so, "ef"), seg_obs_level=col(so, "level"),
+        pt_cand=cm["pt_cand"], seg_cand=cm["seg_cand"])
+
+
 def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_thresh=2.0, mapping=False, known_frac=0.6,
                  pos_noise=0.005, map_seed=0, kf_every=5, detect=False, detect_cell_size=25, kf_select=False, kfselect_mindist_t=0.06,
-                 kfselect_mindist_r=3.0, max_n_kfs=10):
+                 kfselect_mindist_r=3.0, max_n_kfs=10, map_candidates=False, record_candidates=False):
     """-> list of per-frame dicts (pose T_f_w, cov, counts).  Frame 0 is the keyframe with the true pose.
     mapping=True: only `known_frac` of the point landmarks start in the map (positions off by `pos_noise` x depth along
     their viewing ray), the others are depth-filter seeds; the seed update runs every frame; every `kf_every`-th frame
@@ -173,8 +209,14 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
     point seeds (seeds_from_corners) that the following frames update next to the map's own; the records gain n_image_seeds /
     n_image_seeds_converged.  These seeds come from the image alone and are not added to the map, whose landmarks carry the truth.
     kf_select=True (with mapping, a backend with close_keyframes / keyframe_decide): the keyframe stage decides which frames play the
-    keyframe (module docstring); the records gain is_kf, n_overlap, depth_mean."""
+    keyframe (module docstring); the records gain is_kf, n_overlap, depth_mean.
+    map_candidates=True (a backend with map_candidates, not the resident chain): candidates and reference observations come from the
+    map-candidate stage (module docstring); the records gain n_filed_pt / n_filed_seg and ref_kf_hist, how many of the filed landmarks
+    took their reference observation from each keyframe of the table.  record_candidates=True also keeps each frame's stage inputs and
+    result in rec["candidates"] (tests)."""
     cam = seq["cam"]
+    if map_candidates and (hasattr(backend, "frame_step") or not hasattr(backend, "map_candidates")):
+        raise ValueError("map_candidates needs a per-call backend with map_candidates()")
     backend.load_frames(seq["images"])
     n_pts, n_seg = len(seq["pt_pos"]), len(seq["seg_spos"])
     T_prev = seq["poses_true"][0].copy()
@@ -232,6 +274,16 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
                 seg_epx=seq["seg_epx0"].copy())
     out = [dict(T=T_prev.copy(), cov=np.full((6, 6), 1e-9), n_align=0, n_matched_pt=int(known.sum()), n_matched_seg=n_seg)]
     kf_select = mapping and kf_select
+    f3 = lambda v: [float(x) for x in v]             # plain floats for the map tables below and in the keyframe branch of the loop
+    if map_candidates:
+        # the map tables of the stage: keyframe 0 with the features of the landmarks it starts with, one observation each (newest first later)
+        cm = dict(kf_T=[f3(kf_T)], kf_slot=[0], kf_pt=[[int(i) for i in k0]], kf_seg=[list(range(n_seg))],
+                  pt_pos=None, pt_type=[abi.LM_UNKNOWN] * n_pts,
+                  pt_obs=[[dict(kf=0, px=f3(seq["pt_px0"][i]), f=f3(seq["pt_f0"][i]), level=0, type=abi.FTR_CORNER, grad=[0.0, 0.0])] if known[i] else [] for i in range(n_pts)],
+                  seg_spos=[f3(v) for v in seq["seg_spos"]], seg_epos=[f3(v) for v in seq["seg_epos"]], seg_type=[abi.LM_UNKNOWN] * n_seg,
+                  seg_obs=[[dict(kf=0, spx=f3(seq["seg_spx0"][i]), epx=f3(seq["seg_epx0"][i]), sf=f3(seq["seg_sf0"][i]), ef=f3(seq["seg_ef0"][i]), level=0)]
+                           for i in range(n_seg)], pt_cand=[], seg_cand=[])
+        cm_dirty = True
     for k in range(1, len(seq["images"])):
         # ---- 1. sparse image alignment, previous frame -> frame k (processFrame :266-274) ----
         ref_pos = synth.se3_inv(T_prev)[4:]
@@ -258,27 +310,61 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
         else:
             ar = backend.sparse_align(job)
             T_k = synth.se3_mul(ar.T, T_prev)                                                    # :92
-            # ---- 2. reprojection of the whole map (Reprojector::reprojectMap) ----
-            rp = backend.reproject(abi.ReprojectJob(cam, np.stack([kf_T, T_k]), np.ones(len(pos_all), np.int32), pos_all, cell_size=30))
-            vis = rp["cell"] >= 0
-            vis[:n_pts] &= known                     # seeds are not in the map yet
-            seg_vis = vis[n_pts:n_pts + n_seg] & vis[n_pts + n_seg:]
-            vis[n_pts:n_pts + n_seg] = seg_vis
-            vis[n_pts + n_seg:] = seg_vis
-            idx = np.nonzero(vis)[0]
-            # ---- 3. direct matching against the keyframe-0 observations (Matcher::findMatchDirect) ----
-            ref_px = np.concatenate([seq["pt_px0"], seq["seg_spx0"], seq["seg_epx0"]])[idx]
-            ref_f = np.concatenate([seq["pt_f0"], seq["seg_sf0"], seq["seg_ef0"]])[idx]
-            m = len(idx)
-            mj = abi.MatchJob(cam, np.stack([kf_T, T_k]), np.array([0, k], np.int32), np.ones(m, np.int32), np.zeros(m, np.int32), ref_px, ref_f,
-                              np.zeros(m, np.int32), np.zeros(m, np.uint8), np.zeros((m, 2)), pos_all[idx], rp["px"][idx], n_pyr_levels, 10)
-            mr = backend.match_direct(mj)
-            found = np.zeros(len(pos_all), bool)
-            found[idx] = mr["found"].astype(bool)
-            px_new = rp["px"].copy()
-            px_new[idx] = mr["px_cur"]
-            level = np.zeros(len(pos_all), np.int32)
-            level[idx] = np.maximum(mr["search_level"], 0)
+            close = None
+            if map_candidates:
+                # ---- 2 + 3 from the map-candidate stage: overlap keyframes' features, first visit wins, closest-view observation,
+                #      quality order, matched on the device (reprojectMap :157-183, getCloseViewObs, findMatchDirect) ----
+                if kf_select:
+                    close = backend.close_keyframes(abi.CloseKeyframesJob(cam, T_k, np.stack(kfs["T"]), np.stack(kfs["pos"]), np.stack(kfs["valid"]), max_n_kfs))
+                    overlap = [int(v) for v in close["close_idx"][:close["n_overlap"]]]
+                else:
+                    overlap = list(range(len(cm["kf_T"])))
+                map_job = None
+                if cm_dirty:
+                    cm["pt_pos"] = [[float(x) for x in v] for v in P3]
+                    map_job = candidate_map_job(cm)
+                    cm_dirty = False
+                cr, mr = backend.map_candidates(map_job, abi.CandidateFrameJob(T_k, overlap, cur_slot=k), cam, n_pyr_levels)
+                npf, nsf = cr["n_filed_pt"], cr["n_filed_seg"]
+                found = np.zeros(len(pos_all), bool)
+                px_new = np.zeros((len(pos_all), 2))
+                level = np.zeros(len(pos_all), np.int32)
+                at = np.concatenate([cr["pt_lm"], n_pts + cr["seg_lm"], n_pts + n_seg + cr["seg_lm"]]).astype(np.int64)
+                found[at] = mr["found"].astype(bool)
+                px_new[at] = mr["px"]
+                level[at] = np.maximum(mr["search_level"], 0)
+                hist = np.zeros(len(cm["kf_T"]), np.int64)
+                for lm, o in zip(cr["pt_lm"], cr["pt_obs"]):
+                    if o >= 0:
+                        hist[cm["pt_obs"][lm][o]["kf"]] += 1
+                for lm, o in zip(cr["seg_lm"], cr["seg_obs"]):
+                    if o >= 0:
+                        hist[cm["seg_obs"][lm][o]["kf"]] += 1
+                cand_rec = dict(n_filed_pt=npf, n_filed_seg=nsf, ref_kf_hist=[int(v) for v in hist])
+                if record_candidates:
+                    cand_rec["candidates"] = dict(stream=copy.deepcopy(cm), T=[float(v) for v in T_k], overlap=list(overlap), out=cr, match=mr)
+            else:
+                # ---- 2. reprojection of the whole map (Reprojector::reprojectMap) ----
+                rp = backend.reproject(abi.ReprojectJob(cam, np.stack([kf_T, T_k]), np.ones(len(pos_all), np.int32), pos_all, cell_size=30))
+                vis = rp["cell"] >= 0
+                vis[:n_pts] &= known                     # seeds are not in the map yet
+                seg_vis = vis[n_pts:n_pts + n_seg] & vis[n_pts + n_seg:]
+                vis[n_pts:n_pts + n_seg] = seg_vis
+                vis[n_pts + n_seg:] = seg_vis
+                idx = np.nonzero(vis)[0]
+                # ---- 3. direct matching against the keyframe-0 observations (Matcher::findMatchDirect) ----
+                ref_px = np.concatenate([seq["pt_px0"], seq["seg_spx0"], seq["seg_epx0"]])[idx]
+                ref_f = np.concatenate([seq["pt_f0"], seq["seg_sf0"], seq["seg_ef0"]])[idx]
+                m = len(idx)
+                mj = abi.MatchJob(cam, np.stack([kf_T, T_k]), np.array([0, k], np.int32), np.ones(m, np.int32), np.zeros(m, np.int32), ref_px, ref_f,
+                                  np.zeros(m, np.int32), np.zeros(m, np.uint8), np.zeros((m, 2)), pos_all[idx], rp["px"][idx], n_pyr_levels, 10)
+                mr = backend.match_direct(mj)
+                found = np.zeros(len(pos_all), bool)
+                found[idx] = mr["found"].astype(bool)
+                px_new = rp["px"].copy()
+                px_new[idx] = mr["px_cur"]
+                level = np.zeros(len(pos_all), np.int32)
+                level[idx] = np.maximum(mr["search_level"], 0)
             pt_ok = found[:n_pts]
             seg_ok = found[n_pts:n_pts + n_seg] & found[n_pts + n_seg:]
             # ---- 4. motion-only pose optimisation on the matches (processFrame :327-329) ----
@@ -290,9 +376,9 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
                                 seq["seg_spos"][seg_i], seq["seg_epos"][seg_i], level[n_pts + seg_i])
             pr = backend.pose_optimize(pj)
         n_ties = backend.align_ties() if hasattr(backend, "align_ties") else None
-        if kf_select:
-            # ---- the keyframes that overlap the aligned frame (the head of reprojectMap: it runs before the matching, which here takes
-            #      its candidates from keyframe 0 either way, so the call's place in this function does not matter) ----
+        if kf_select and not map_candidates:
+            # ---- the keyframes that overlap the aligned frame (the head of reprojectMap: it runs before the matching, which without
+            #      map_candidates takes its candidates from keyframe 0 either way, so the call's place here does not matter) ----
             close = backend.close_keyframes(abi.CloseKeyframesJob(cam, synth.se3_mul(ar.T, T_prev), np.stack(kfs["T"]), np.stack(kfs["pos"]),
                                                                   np.stack(kfs["valid"]), max_n_kfs))
         T_last = T_prev
@@ -305,6 +391,8 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
                    n_kept_pt=int(pt_keep.sum()), n_kept_seg=int(seg_keep.sum()))
         if n_ties is not None:
             rec["align_ties"] = n_ties
+        if map_candidates:
+            rec.update(cand_rec)
         if mapping:
             poses_est.append(T_k.copy())
             kept = pt_i[pt_keep]
@@ -322,6 +410,23 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
             if is_kf:
                 for i, brg in zip(kept, _bearing(cam, px_new[kept])):
                     obs[int(i)].append((k, brg))
+                if map_candidates:
+                    # the frame joins the keyframe table: its features, and an observation at the FRONT of every landmark's list
+                    # (Feature3D::addFrameRef pushes at the front, include/plsvo/feature3D.h:204); a candidate it matched leaves the
+                    # map's candidate list for the keyframe's features
+                    skept_ = seg_i[seg_keep]
+                    kf_id = len(cm["kf_T"])
+                    cm["kf_T"].append(f3(T_k)); cm["kf_slot"].append(k)
+                    cm["kf_pt"].append([int(i) for i in kept]); cm["kf_seg"].append([int(i) for i in skept_])
+                    for i, brg in zip(kept, _bearing(cam, px_new[kept])):
+                        cm["pt_obs"][int(i)].insert(0, dict(kf=kf_id, px=f3(px_new[i]), f=f3(brg), level=int(level[i]), type=abi.FTR_CORNER, grad=[0.0, 0.0]))
+                        cm["pt_type"][int(i)] = abi.LM_UNKNOWN
+                    for i, sb, eb in zip(skept_, _bearing(cam, px_new[n_pts + skept_]), _bearing(cam, px_new[n_pts + n_seg + skept_])):
+                        cm["seg_obs"][int(i)].insert(0, dict(kf=kf_id, spx=f3(px_new[n_pts + i]), epx=f3(px_new[n_pts + n_seg + i]), sf=f3(sb), ef=f3(eb),
+                                                             level=int(level[n_pts + i])))
+                    matched = set(int(v) for v in kept)
+                    cm["pt_cand"] = [i for i in cm["pt_cand"] if i not in matched]
+                    cm_dirty = True
             # ---- 5. structure optimisation (FrameHandlerBase::optimizeStructure: the 20 least recently refined, :202-237) ----
             cand = np.array([i for i in kept if len(obs[int(i)]) >= 2], np.int64)
             if len(cand) and is_kf:
@@ -336,6 +441,8 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
                 so = backend.structure_optimize(abi.StructOptJob(np.stack(poses_est), P3[sel], off, ofr, np.array(of_), z3, z3, np.zeros(1, np.int32), zi, z3, z3, 5, 5))
                 P3[sel] = so["pt_pos"]
                 last_optim[sel] = k
+                if map_candidates:
+                    cm_dirty = True
             # ---- 6. depth-filter update of the seeds with this frame (DepthFilter::updateSeeds) ----
             ns = len(seeds["idx"])
             if ns:
@@ -347,6 +454,14 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
                 conv = stt == abi.SEED_CONVERGED
                 P3[si_[conv]] = sr["pt_xyz_world"][conv]
                 known[si_[conv]] = True
+                if map_candidates and conv.any():
+                    # a converged seed becomes a candidate of the map (map_.point_candidates_), observed in the keyframe it was started in
+                    for i in si_[conv]:
+                        cm["pt_obs"][int(i)] = [dict(kf=0, px=[float(x) for x in seq["pt_px0"][i]], f=[float(x) for x in seq["pt_f0"][i]], level=0,
+                                                     type=abi.FTR_CORNER, grad=[0.0, 0.0])]
+                        cm["pt_type"][int(i)] = abi.LM_CANDIDATE
+                        cm["pt_cand"].append(int(i))
+                    cm_dirty = True
                 keep_s = ~(conv | (stt == abi.SEED_NAN))
                 seeds = dict(idx=si_[keep_s], a=sr["pt_a"][keep_s], b=sr["pt_b"][keep_s], mu=sr["pt_mu"][keep_s], z_range=seeds["z_range"][keep_s],
                              sigma2=sr["pt_sigma2"][keep_s])

@@ -731,7 +731,7 @@ int plsvo_keyframe_decide(plsvo_ctx* ctx, int n, const plsvo_kf_decide_in* in, p
 #define PLSVO_LM_UNKNOWN   2
 #define PLSVO_LM_GOOD      3
 
-/* One stream's map tables (they change at keyframes only; a keyframe restages them).
+/* One stream's map tables (a keyframe restages them; between keyframes plsvo_candidates_select changes types and lists in place).
  *   kf_T, kf_slot      7*n_kf, n_kf    Frame::T_f_w_ and the pyramid slot of every keyframe
  *   kf_pt_off          n_kf+1          CSR: keyframe k's pt_fts_ are entries [kf_pt_off[k], kf_pt_off[k+1]) of kf_pt_lm, in list order
  *   kf_pt_lm                           the point landmark of every feature (index < n_pt), -1 where feat3D == NULL
@@ -864,6 +864,89 @@ int plsvo_candidates_match(plsvo_ctx* ctx);
 int plsvo_candidates_match_fetch(plsvo_ctx* ctx, int n, plsvo_cand_match_out* out);
 int plsvo_candidates_dev(plsvo_ctx* ctx, plsvo_cand_dev* out);
 
+/* ------------------------------------------------------------------------------------------ */
+/* cell selection of the map candidates: the second half of Reprojector::reprojectMap           */
+/* (src/reprojector.cpp:185-216) with refineBestCandidate (:236-276) and refine (:278-387), the  */
+/* failures of setMapCandidates (:116-131) and the deletions they lead to (src/map.cpp:116-139,  */
+/* :311-324, :403-416), in place on the resident tables of plsvo_candidates_stage (one wave per  */
+/* stream).  Candidates, match, selection and pose optimisation of a frame are   */
+/* one enqueue sequence; the tables stay what the reference's map would be from keyframe to      */
+/* keyframe.                                                                                    */
+/* Preconditions (unchecked): a landmark occurs at most once in a candidate list, and a landmark */
+/* in a candidate list is referenced by no keyframe feature -- a point is then filed at most     */
+/* once per frame.  The observation lists of a deleted landmark are left as staged (the          */
+/* reference clears them; a deleted landmark is never matched).                                  */
+/* ------------------------------------------------------------------------------------------ */
+
+#define PLSVO_LM_EVENT_PROMOTED 1   /* TYPE_UNKNOWN -> TYPE_GOOD by the last selection (:306-307, :367-369) */
+#define PLSVO_LM_EVENT_DELETED  2   /* -> TYPE_DELETED by the last selection (safeDelete*, deleteCandidate*) */
+
+typedef struct plsvo_cand_select_params {   /* one set for the batch; the grids are those of the staged plsvo_cand_params */
+  int32_t max_fts;                  /* Config::maxFts(): the visit stops after the match that makes n_matches_ exceed it (:195) */
+  int32_t max_fts_segs;             /* Config::maxFtsSegs() (:205) */
+  int32_t poseopt_n_iter;           /* 10 (src/config.cpp:103) */
+  int32_t reserved0;
+  const int32_t* cell_order;        /* ceil(width / cell_size) * ceil(height / cell_size) cell indices (Grid::cell_order, :63-66); NULL = 0,1,2,.. */
+  const int32_t* seg_cell_order;    /* the same for the segments' grid (:76-79) */
+  double reproj_thresh;             /* 2.0 (src/config.cpp:102) */
+} plsvo_cand_select_params;
+
+/* Point::n_failed_reproj_ / n_succeeded_reproj_ and LineSeg's (include/plsvo/feature3D.h), per landmark of one stream.  A NULL array
+ * leaves those counters as they are.  They are zero after plsvo_candidates_stage. */
+typedef struct plsvo_cand_quality_in {
+  const int32_t* pt_n_failed; const int32_t* pt_n_succeeded;       /* n_pt */
+  const int32_t* seg_n_failed; const int32_t* seg_n_succeeded;     /* n_seg */
+} plsvo_cand_quality_in;
+
+/* The quality state of one stream as it now stands.  Caller buffers, any may be NULL: n_pt / n_seg entries, the candidate lists
+ * n_pt_cand / n_seg_cand of the STAGED counts, of which the first n_pt_cand / n_seg_cand reported here are written (an erased
+ * candidate closes the list up).  *_event: PLSVO_LM_EVENT_* of the last plsvo_candidates_select, 0 before the first. */
+typedef struct plsvo_cand_quality_out {
+  int32_t n_pt_cand, n_seg_cand;
+  int32_t* pt_n_failed; int32_t* pt_n_succeeded; int32_t* pt_type; uint8_t* pt_event;
+  int32_t* seg_n_failed; int32_t* seg_n_succeeded; int32_t* seg_type; uint8_t* seg_event;
+  int32_t* pt_cand; int32_t* seg_cand;
+} plsvo_cand_quality_out;
+
+/* The features the new frame received, in the order refine() adds them (:311-312, :373-374).  Caller buffers, any may be NULL:
+ * capacity n_filed_pt points and 2 * n_filed_seg segments (a segment that wins both of its cells is a feature twice). */
+typedef struct plsvo_cand_select_out {
+  int32_t n_matches;                /* Reprojector::n_matches_: point features */
+  int32_t n_ls_matches;             /* n_ls_matches_: segment features */
+  int32_t n_trials;                 /* n_trials_, points and segments */
+  int32_t reserved0;
+  int32_t* pt_lm;                   /* landmark index */
+  double* pt_px;                    /* 2: the refined pixel */
+  int32_t* pt_level;                /* Matcher::search_level_ */
+  uint8_t* pt_type;                 /* PLSVO_FTR_EDGELET when the reference observation is one (:319-327) */
+  double* pt_grad;                  /* 2: normalize(A_cur_ref * ref grad) for an edgelet, (1, 0) otherwise (src/feature.cpp:56) */
+  int32_t* seg_lm;
+  double* seg_px;                   /* 4: refined start point, end point */
+  int32_t* seg_level;               /* the END point's search level (src/matcher.cpp:264, :373) */
+} plsvo_cand_select_out;
+
+/* set_quality / fetch_quality: synchronous; valid from plsvo_candidates_stage on.
+ * select: enqueue only -- the re-arm of the launch's scratch and one launch; PLSVO_E_STATE without a preceding plsvo_candidates_match
+ * (or plsvo_candidates_set_match) on the last plsvo_candidates_run, or when that run was selected already.  It changes the resident tables: types, counters, the keyframes'
+ * feature lists (-1 where safeDelete* cut the landmark loose) and the candidate lists, so the next plsvo_candidates_run sees the map the
+ * reference would see.  select_fetch synchronises.
+ * pose_optimize: enqueue only -- pose_optimizer::optimizeGaussNewton (plsvo_pose_optimize's kernels, unchanged) on the features the
+ * selection wrote on the device, starting from the pose the candidate stage projected with; pose_fetch synchronises, its keep masks are in
+ * selection order.  poses_dev: n*7 doubles, the optimised T_f_w, on the device (as plsvo_chain_poses_dev).
+ * PLSVO_E_INVALID (nothing written) for another n than staged, NULL arguments with n > 0, negative max_fts / max_fts_segs /
+ * poseopt_n_iter, a cell order that is not a permutation of its grid, a negative counter. */
+int plsvo_candidates_set_quality(plsvo_ctx* ctx, int n, const plsvo_cand_quality_in* in);
+int plsvo_candidates_fetch_quality(plsvo_ctx* ctx, int n, plsvo_cand_quality_out* out);
+int plsvo_candidates_select(plsvo_ctx* ctx, const plsvo_cand_select_params* params);
+int plsvo_candidates_select_fetch(plsvo_ctx* ctx, int n, plsvo_cand_select_out* out);
+int plsvo_candidates_pose_optimize(plsvo_ctx* ctx);
+int plsvo_candidates_pose_fetch(plsvo_ctx* ctx, int n, plsvo_poseopt_out* out);
+const double* plsvo_candidates_poses_dev(plsvo_ctx* ctx);
+/* Diagnostic (tests; like plsvo_hip_detect_stages for the detector): overwrites the resident match output of the last
+ * plsvo_candidates_run with the caller's -- per stream n_filed_pt + 2 * n_filed_seg entries in the layout of plsvo_cand_match_out, all
+ * three arrays required -- so that the selection can be driven with constructed match results.  Synchronous. */
+int plsvo_candidates_set_match(plsvo_ctx* ctx, int n, const plsvo_cand_match_out* in);
+
 /* TUM-style trajectory record of a frame (app/run_pipeline.cpp:425-451): the camera pose in the world,
  * T_f_w^-1, as tx ty tz qx qy qz qw.  Returns 1 and fills out7 when the reference would write the line, 0 when
  * it skips the frame (a covariance entry outside (1e-16, 1e16), or an exactly-identity pose).  Host-only helper:
@@ -992,7 +1075,8 @@ int plsvo_gather_poses(plsvo_ctx* ctx, void* rccl_comm, const plsvo_pose_record*
 #define PLSVO_K_SEEDS         6
 #define PLSVO_K_KEYFRAME      7   /* plsvo_close_keyframes / plsvo_keyframe_decide: the launch alone, without packing and copies */
 #define PLSVO_K_CANDIDATES    8   /* plsvo_candidates_run: the re-arm and the launch alone (the resident match counts under PLSVO_K_MATCH) */
-#define PLSVO_K_COUNT         9
+#define PLSVO_K_SELECT        9   /* plsvo_candidates_select: the re-arm and the launch alone */
+#define PLSVO_K_COUNT         10
 int plsvo_hip_set_profiling(plsvo_ctx* ctx, int enable);
 /* accumulated GPU time and launch count of kernel family k since the last reset (synchronises) */
 int plsvo_hip_kernel_time(plsvo_ctx* ctx, int k, double* total_ms, int64_t* launches);

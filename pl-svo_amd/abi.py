@@ -18,7 +18,7 @@ c_i32_p = C.POINTER(C.c_int32)
 OK, E_INVALID, E_NODEVICE, E_HIP, E_CAPACITY, E_STATE, E_RCCL = 0, -1, -2, -3, -4, -5, -6
 
 # kernel families for plsvo_hip_kernel_time
-K_ALIGN_INIT, K_ALIGN_LEVEL, K_POSEOPT, K_HALFSAMPLE, K_STRUCTOPT, K_MATCH, K_SEEDS, K_KEYFRAME, K_CANDIDATES, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
+K_ALIGN_INIT, K_ALIGN_LEVEL, K_POSEOPT, K_HALFSAMPLE, K_STRUCTOPT, K_MATCH, K_SEEDS, K_KEYFRAME, K_CANDIDATES, K_SELECT, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 SEED_NOT_VISIBLE, SEED_NO_MATCH, SEED_UPDATED, SEED_CONVERGED, SEED_NAN = 0, 1, 2, 3, 4
 FTR_CORNER, FTR_EDGELET = 0, 1
 LM_DELETED, LM_CANDIDATE, LM_UNKNOWN, LM_GOOD = 0, 1, 2, 3
@@ -223,6 +223,32 @@ class CandOut(C.Structure):
 class CandMatchOut(C.Structure):
     """plsvo_cand_match_out"""
     _fields_ = [("found", c_u8_p), ("px", c_double_p), ("search_level", c_i32_p)]
+
+
+class CandSelectParams(C.Structure):
+    """plsvo_cand_select_params"""
+    _fields_ = [("max_fts", C.c_int32), ("max_fts_segs", C.c_int32), ("poseopt_n_iter", C.c_int32), ("reserved0", C.c_int32),
+                ("cell_order", c_i32_p), ("seg_cell_order", c_i32_p), ("reproj_thresh", C.c_double)]
+
+
+class CandQualityIn(C.Structure):
+    """plsvo_cand_quality_in"""
+    _fields_ = [("pt_n_failed", c_i32_p), ("pt_n_succeeded", c_i32_p), ("seg_n_failed", c_i32_p), ("seg_n_succeeded", c_i32_p)]
+
+
+class CandQualityOut(C.Structure):
+    """plsvo_cand_quality_out"""
+    _fields_ = [("n_pt_cand", C.c_int32), ("n_seg_cand", C.c_int32), ("pt_n_failed", c_i32_p), ("pt_n_succeeded", c_i32_p), ("pt_type", c_i32_p), ("pt_event", c_u8_p),
+                ("seg_n_failed", c_i32_p), ("seg_n_succeeded", c_i32_p), ("seg_type", c_i32_p), ("seg_event", c_u8_p), ("pt_cand", c_i32_p), ("seg_cand", c_i32_p)]
+
+
+class CandSelectOut(C.Structure):
+    """plsvo_cand_select_out"""
+    _fields_ = [("n_matches", C.c_int32), ("n_ls_matches", C.c_int32), ("n_trials", C.c_int32), ("reserved0", C.c_int32), ("pt_lm", c_i32_p), ("pt_px", c_double_p),
+                ("pt_level", c_i32_p), ("pt_type", c_u8_p), ("pt_grad", c_double_p), ("seg_lm", c_i32_p), ("seg_px", c_double_p), ("seg_level", c_i32_p)]
+
+
+LM_EVENT_PROMOTED, LM_EVENT_DELETED = 1, 2
 
 
 class CandDev(C.Structure):

@@ -28,6 +28,8 @@ SYMBOLS = [
     "plsvo_structure_optimize", "plsvo_match_direct", "plsvo_match_warp_patches", "plsvo_reproject", "plsvo_trajectory_record", "plsvo_update_seeds",
     "plsvo_close_keyframes", "plsvo_keyframe_decide",
     "plsvo_candidates_stage", "plsvo_candidates_run", "plsvo_candidates_fetch", "plsvo_candidates_match", "plsvo_candidates_match_fetch", "plsvo_candidates_dev",
+    "plsvo_candidates_set_quality", "plsvo_candidates_fetch_quality", "plsvo_candidates_select", "plsvo_candidates_select_fetch", "plsvo_candidates_pose_optimize",
+    "plsvo_candidates_pose_fetch", "plsvo_candidates_poses_dev", "plsvo_candidates_set_match",
     "plsvo_chain_stage", "plsvo_chain_run", "plsvo_chain_fetch", "plsvo_frame_step_batch", "plsvo_chain_poses_dev",
     "plsvo_pack_pose_records", "plsvo_fetch_pose_records", "plsvo_gather_poses",
     "plsvo_hip_set_profiling", "plsvo_hip_kernel_time", "plsvo_hip_reset_profiling",
@@ -148,6 +150,14 @@ def lib():
         "plsvo_candidates_match": (C.c_int, [ctxp]),
         "plsvo_candidates_match_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandMatchOut)]),
         "plsvo_candidates_dev": (C.c_int, [ctxp, C.POINTER(abi.CandDev)]),
+        "plsvo_candidates_set_quality": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandQualityIn)]),
+        "plsvo_candidates_fetch_quality": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandQualityOut)]),
+        "plsvo_candidates_select": (C.c_int, [ctxp, C.POINTER(abi.CandSelectParams)]),
+        "plsvo_candidates_select_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandSelectOut)]),
+        "plsvo_candidates_pose_optimize": (C.c_int, [ctxp]),
+        "plsvo_candidates_pose_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.PoseOptOut)]),
+        "plsvo_candidates_poses_dev": (vp, [ctxp]),
+        "plsvo_candidates_set_match": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandMatchOut)]),
         "plsvo_update_seeds": (C.c_int, [ctxp, C.POINTER(abi.SeedsIn), C.POINTER(abi.SeedsOut)]),
         "plsvo_trajectory_record": (C.c_int, [abi.c_double_p, abi.c_double_p, abi.c_double_p]),
         "plsvo_chain_stage": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.ChainIn), C.POINTER(abi.ChainParams)]),
@@ -673,6 +683,112 @@ class Context:
         d = abi.CandDev()
         self._chk(self.L.plsvo_candidates_dev(self.h, C.byref(d)))
         return d
+
+    # ---- cell selection of the map candidates ----
+    @staticmethod
+    def _ptr(v):
+        return v.ctypes.data_as(abi.c_double_p if v.dtype == np.float64 else abi.c_u8_p if v.dtype == np.uint8 else abi.c_i32_p)
+
+    def candidates_set_quality(self, quality):
+        """plsvo_candidates_set_quality: per staged stream a dict with any of pt_n_failed, pt_n_succeeded, seg_n_failed, seg_n_succeeded
+        (a missing one leaves those counters as they are)"""
+        n = len(quality)
+        arr = (abi.CandQualityIn * max(n, 1))()
+        keep = []
+        for a, q in zip(arr, quality):
+            for f in ("pt_n_failed", "pt_n_succeeded", "seg_n_failed", "seg_n_succeeded"):
+                if q.get(f) is not None:
+                    v = np.ascontiguousarray(q[f], dtype=np.int32)
+                    keep.append(v)
+                    setattr(a, f, v.ctypes.data_as(abi.c_i32_p))
+        self._chk(self.L.plsvo_candidates_set_quality(self.h, n, arr))
+
+    def candidates_fetch_quality(self):
+        """plsvo_candidates_fetch_quality: per stream a dict of the counters, the types, the event flags of the last selection
+        (abi.LM_EVENT_*) and the candidate lists as they now stand"""
+        maps = self._cand_maps
+        n = len(maps)
+        outs = (abi.CandQualityOut * max(n, 1))()
+        bufs = []
+        for o, m in zip(outs, maps):
+            b = dict(pt_n_failed=np.full(max(m.n_pt, 1), -9, np.int32), pt_n_succeeded=np.full(max(m.n_pt, 1), -9, np.int32), pt_type=np.full(max(m.n_pt, 1), -9, np.int32),
+                     pt_event=np.full(max(m.n_pt, 1), 9, np.uint8), seg_n_failed=np.full(max(m.n_seg, 1), -9, np.int32), seg_n_succeeded=np.full(max(m.n_seg, 1), -9, np.int32),
+                     seg_type=np.full(max(m.n_seg, 1), -9, np.int32), seg_event=np.full(max(m.n_seg, 1), 9, np.uint8),
+                     pt_cand=np.full(max(m.n_pt_cand, 1), -9, np.int32), seg_cand=np.full(max(m.n_seg_cand, 1), -9, np.int32))
+            for k, v in b.items():
+                setattr(o, k, self._ptr(v))
+            bufs.append(b)
+        self._chk(self.L.plsvo_candidates_fetch_quality(self.h, n, outs))
+        res = []
+        for o, m, b in zip(outs[:n], maps, bufs):
+            cut = lambda k: o.n_pt_cand if k == "pt_cand" else o.n_seg_cand if k == "seg_cand" else m.n_pt if k.startswith("pt_") else m.n_seg
+            res.append({k: v[:cut(k)].copy() for k, v in b.items()})
+        return res
+
+    def candidates_set_match(self, match):
+        """plsvo_candidates_set_match (diagnostic): per stream a dict of found / px [k, 2] / search_level that replaces the resident
+        match output of the last run"""
+        n = len(match)
+        arr = (abi.CandMatchOut * max(n, 1))()
+        keep = []
+        for a, m in zip(arr, match):
+            b = (np.ascontiguousarray(m["found"], dtype=np.uint8).reshape(-1), np.ascontiguousarray(m["px"], dtype=np.float64).reshape(-1, 2),
+                 np.ascontiguousarray(m["search_level"], dtype=np.int32).reshape(-1))
+            b = tuple(v if v.size else np.zeros(2, v.dtype) for v in b)
+            keep.append(b)
+            a.found, a.px, a.search_level = self._ptr(b[0]), self._ptr(b[1]), self._ptr(b[2])
+        self._chk(self.L.plsvo_candidates_set_match(self.h, n, arr))
+
+    def candidates_select(self, max_fts=120, max_fts_segs=100, cell_order=None, seg_cell_order=None, poseopt_n_iter=10, reproj_thresh=2.0):
+        """plsvo_candidates_select (enqueue only): one candidate per cell, landmark quality, the new frame's features and the pose
+        optimiser's input, in place on the resident tables"""
+        pr = abi.CandSelectParams()
+        pr.max_fts, pr.max_fts_segs, pr.poseopt_n_iter, pr.reproj_thresh = int(max_fts), int(max_fts_segs), int(poseopt_n_iter), float(reproj_thresh)
+        keep = [None if o is None else np.ascontiguousarray(o, dtype=np.int32) for o in (cell_order, seg_cell_order)]
+        pr.cell_order = C.cast(None, abi.c_i32_p) if keep[0] is None else keep[0].ctypes.data_as(abi.c_i32_p)
+        pr.seg_cell_order = C.cast(None, abi.c_i32_p) if keep[1] is None else keep[1].ctypes.data_as(abi.c_i32_p)
+        self._chk(self.L.plsvo_candidates_select(self.h, C.byref(pr)))
+
+    def candidates_select_fetch(self):
+        """plsvo_candidates_select_fetch: per stream a dict of n_matches, n_ls_matches, n_trials and the new frame's features in the order
+        refine() adds them (pt_lm, pt_px [n, 2], pt_level, pt_type, pt_grad [n, 2], seg_lm, seg_px [n, 4], seg_level)"""
+        maps = self._cand_maps
+        n = len(maps)
+        outs = (abi.CandSelectOut * max(n, 1))()
+        bufs = []
+        for o, m in zip(outs, maps):
+            cp, cs = max(m.cap_pt, 1), max(2 * m.cap_seg, 1)
+            b = dict(pt_lm=np.full(cp, -9, np.int32), pt_px=np.zeros((cp, 2)), pt_level=np.full(cp, -9, np.int32), pt_type=np.full(cp, 9, np.uint8), pt_grad=np.zeros((cp, 2)),
+                     seg_lm=np.full(cs, -9, np.int32), seg_px=np.zeros((cs, 4)), seg_level=np.full(cs, -9, np.int32))
+            for k, v in b.items():
+                setattr(o, k, self._ptr(v))
+            bufs.append(b)
+        self._chk(self.L.plsvo_candidates_select_fetch(self.h, n, outs))
+        res = []
+        for o, b in zip(outs[:n], bufs):
+            r = dict(n_matches=int(o.n_matches), n_ls_matches=int(o.n_ls_matches), n_trials=int(o.n_trials))
+            r.update({k: v[:(o.n_matches if k.startswith("pt_") else o.n_ls_matches)].copy() for k, v in b.items()})
+            res.append(r)
+        return res
+
+    def candidates_pose_optimize(self):
+        """plsvo_candidates_pose_optimize (enqueue only): the pose optimiser on the features the selection wrote on the device"""
+        self._chk(self.L.plsvo_candidates_pose_optimize(self.h))
+
+    def candidates_pose_fetch(self, counts):
+        """plsvo_candidates_pose_fetch: an abi.PoseOptResult per stream, keep masks in selection order.  counts: the (n_matches,
+        n_ls_matches) of candidates_select_fetch()"""
+        n = len(counts)
+        outs = (abi.PoseOptOut * max(n, 1))()
+        pk = [np.zeros(max(a, 1), np.uint8) for a, _ in counts]
+        sk = [np.zeros(max(b, 1), np.uint8) for _, b in counts]
+        for o, a, b in zip(outs, pk, sk):
+            o.pt_keep, o.seg_keep = a.ctypes.data_as(abi.c_u8_p), b.ctypes.data_as(abi.c_u8_p)
+        self._chk(self.L.plsvo_candidates_pose_fetch(self.h, n, outs))
+        return [abi.PoseOptResult(o, a[:c[0]].copy(), b[:c[1]].copy()) for o, a, b, c in zip(outs[:n], pk, sk, counts)]
+
+    def candidates_poses_dev(self):
+        return self.L.plsvo_candidates_poses_dev(self.h)
 
     # ---- structure optimisation ----
     def structure_optimize(self, job):

@@ -36,6 +36,7 @@ hipError_t launch_update_seeds(const SeedsBatchDev& b, hipStream_t stream);
 hipError_t launch_close_keyframes(const CloseKfBatchDev& b, hipStream_t stream);     // keyframe_device.hpp, in seeds_kernels.hip
 hipError_t launch_keyframe_decide(const KfDecideBatchDev& b, hipStream_t stream);
 hipError_t launch_map_candidates(const CandBatchDev& b, hipStream_t stream);         // candidates_device.hpp, in seeds_kernels.hip
+hipError_t launch_map_select(const SelectBatchDev& b, hipStream_t stream);            // select_device.hpp, in seeds_kernels.hip
 hipError_t launch_halfsample(const uint8_t* src, size_t src_pitch, int in_w, int in_h, int in_stride, uint8_t* dst,
                              size_t dst_pitch, int n_slots, int rounding, hipStream_t stream);
 hipError_t launch_copy_level0(const uint8_t* src, size_t src_pitch, int w, int h, int stride, uint8_t* dst, size_t dst_pitch,
@@ -201,6 +202,15 @@ struct plsvo_ctx {
   DevBuf cd_d_blob, cd_d_work, cd_d_run, cd_d_kfcount;
   CandBatchDev cd_b{};
   MatchBatchDev cd_match{};
+  // their cell selection (plsvo_candidates_select ..): the resident landmark quality (cs_d_q: counters, then the event bytes), the
+  // launch's scratch, the features and the pose optimiser's input (cs_d_work), the visit orders of the two grids (cs_d_order)
+  bool cs_selected = false, cs_posed = false;
+  size_t cd_t_pt = 0, cd_t_seg = 0, cd_t_ptc = 0, cd_t_segc = 0, cd_t_opt = 0, cd_t_oseg = 0;
+  size_t cs_ev_off = 0, cs_win_bytes = 0;
+  std::vector<int> cs_order;                // what cs_d_order holds: order, positions, for the points' grid and the segments'
+  DevBuf cs_d_q, cs_d_work, cs_d_order, cs_d_state, cs_d_ptkeep, cs_d_segkeep, cs_d_s32, cs_d_s64, cs_d_poses;
+  SelectBatchDev cs_b{};
+  PoseBatchDev cs_pose{};
   unsigned long long run_seq = 0, a_run_seq = 0, p_run_seq = 0, ch_run_seq = 0;   // which resident batch ran last, 0 = not since it was staged (plsvo_pack_pose_records)
 
   // structure optimisation (one-shot batches)
@@ -341,6 +351,7 @@ extern "C" void plsvo_hip_destroy(plsvo_ctx* c) {
   c->a_d_tailflag.release(); c->a_d_alive_tail.release(); c->a_d_xbuf.release(); c->a_d_order[0].release(); c->a_d_order[1].release(); c->a_d_workkey.release(); c->p_d_workkey.release(); c->p_d_order[0].release(); c->p_d_order[1].release();
   c->p_d_carry.release(); c->p_d_refill_next.release();
   c->cd_d_blob.release(); c->cd_d_work.release(); c->cd_d_run.release(); c->cd_d_kfcount.release();
+  for (DevBuf* b : { &c->cs_d_q, &c->cs_d_work, &c->cs_d_order, &c->cs_d_state, &c->cs_d_ptkeep, &c->cs_d_segkeep, &c->cs_d_s32, &c->cs_d_s64, &c->cs_d_poses }) b->release();
   DevBuf* bufs[] = { &c->pyr_slab, &c->pyr_tiled, &c->pyr_upload, &c->a_d_blob, &c->a_d_state, &c->a_d_alive, &c->a_d_pxyz, &c->a_d_puv, &c->a_d_cref,
                      &c->a_d_chi, &c->a_d_log, &c->a_d_poses, &c->p_d_blob, &c->p_d_state, &c->p_d_ptkeep, &c->p_d_segkeep, &c->p_d_s32, &c->p_d_s64,
                      &c->p_d_log, &c->p_d_poses, &c->s_d_in, &c->s_d_out, &c->ch_d_blob, &c->ch_d_work, &c->ch_d_po, &c->ch_d_state,
@@ -1169,6 +1180,14 @@ extern "C" int plsvo_align_stage(plsvo_ctx* c, int n, const plsvo_align_in* in) 
 // Environment overrides (experiments only, read once at plsvo_hip_create): PLSVO_ALIGN_THREADS, PLSVO_ALIGN_PER_LEVEL, PLSVO_ALIGN_LDS_PAD,
 // PLSVO_ALIGN_NO_PAIR, PLSVO_ALIGN_NO_REORDER / PLSVO_POSEOPT_NO_REORDER (launch order of a re-run staged batch), PLSVO_ALIGN_REORDER_MIN /
 // PLSVO_POSEOPT_REORDER_MIN (its threshold, tests).  A switch set to "0" is off.
+// Threads per frame of a pose-optimiser launch over n frames with `feats` features in all (the crossover is measured below, in
+// plsvo_poseopt_run): shared by plsvo_poseopt_run, plsvo_chain_run and plsvo_candidates_pose_optimize
+static int pose_opt_threads(const plsvo_ctx* c, int n, long feats) {
+  const int cus = c->cu_count > 0 ? c->cu_count : 256;
+  const int threads = n <= 2 * cus ? 256 : (feats <= 580l * n ? 16 : 64);
+  return c->env_poseopt_threads ? c->env_poseopt_threads : threads;
+}
+
 static void pick_align_config(const plsvo_ctx* c, int n_jobs, int cap, int scap, int max_pts, int* threads, size_t* lds, int* chi_lds_pts) {
   const int cus = c->cu_count > 0 ? c->cu_count : 256;
   int t = 64;                            // >= 64 frames per CU: one wave per frame, no workgroup barrier at all
@@ -1577,8 +1596,7 @@ extern "C" int plsvo_poseopt_run(plsvo_ctx* c) {
   // one frame is then ~2x shorter).  PLSVO_POSEOPT_THREADS / PLSVO_OPT_POSEOPT_THREADS override (tests and measurements).
   const int cus = c->cu_count > 0 ? c->cu_count : 256;
   const long feats = (long)c->p_total_pt + (long)c->p_total_seg;
-  int threads = c->p_n <= 2 * cus ? 256 : (feats <= 580l * c->p_n ? 16 : 64);
-  if (c->env_poseopt_threads) threads = c->env_poseopt_threads;
+  const int threads = pose_opt_threads(c, c->p_n, feats);
   // batches larger than the resident waves: this launch records what every frame cost, the next one takes them most-expensive first (see
   // plsvo_align_run; for the rows kernel the sort also puts frames that stop together into the same wave)
   const bool reorder = threads != 256 && !c->env_poseopt_no_reorder && !c->p_one_shot &&
@@ -2289,9 +2307,7 @@ extern "C" int plsvo_chain_run(plsvo_ctx* c) {
     HIP_TRY(c, launch_match_direct(c->ch_match, c->stream));
     HIP_TRY(c, launch_chain_select(c->ch_b, c->stream));
     prof_end(c, PLSVO_K_MATCH, &ep); }
-  const int cus = c->cu_count > 0 ? c->cu_count : 256;
-  int threads = c->ch_n <= 2 * cus ? 256 : ((long)c->ch_b.n_cand <= 580l * c->ch_n ? 16 : 64);   // (selected features <= candidates; see plsvo_poseopt_run)
-  if (c->env_poseopt_threads) threads = c->env_poseopt_threads;
+  const int threads = pose_opt_threads(c, c->ch_n, (long)c->ch_b.n_cand);   // (selected features <= candidates)
   c->p_refill_frames = 0;   // (the chain's jobs are written on the device: the host cannot see whether one has a refinement loop -- pose_opt_rows_kernel)
   EventPair ep{}; prof_begin(c, PLSVO_K_POSEOPT, &ep);
   HIP_TRY(c, launch_pose_opt(c->ch_pose, c->ch_d_poses.as<double>(), threads, c->opt_poseopt_select ? 1 : 0, c->stream));
@@ -2433,7 +2449,7 @@ extern "C" int plsvo_candidates_stage(plsvo_ctx* c, int n, const plsvo_cand_map*
     t.m += (size_t)M.cap_pt + 2 * (size_t)M.cap_seg; t.f += (size_t)I.n_kf + 1;
   }
   if (t.m > (size_t)INT32_MAX || t.f > (size_t)INT32_MAX || t.vis > (size_t)INT32_MAX) return fail(c, PLSVO_E_CAPACITY, "candidates_stage: batch too large");
-  c->cd_staged = false; c->cd_ran = false; c->cd_matched = false;
+  c->cd_staged = false; c->cd_ran = false; c->cd_matched = false; c->cs_selected = false; c->cs_posed = false;
   if (n == 0) { c->cd_n = 0; c->cd_staged = true; c->cd_maps.clear(); c->cd_m_off.clear(); c->cd_f_off.clear(); c->cd_params = *pr; return PLSVO_OK; }
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t N = (size_t)n;
@@ -2535,6 +2551,15 @@ extern "C" int plsvo_candidates_stage(plsvo_ctx* c, int n, const plsvo_cand_map*
   c->cd_off = { w_cnt, w_plm, w_ppx, w_pcell, w_pobs, w_pview, w_pact, w_slm, w_spx, w_scell, w_sobs, w_sview, w_sact, w_pfail, w_sfail };
   c->cd_vis_off = w_vis; c->cd_vis_bytes = t.vis * sizeof(unsigned int);
   c->cd_maps = std::move(md); c->cd_params = *pr; c->cd_n = n; c->cd_total_m = t.m; c->cd_total_f = t.f; c->cd_max_level = max_level;
+  // the landmark quality the selection maintains: n_failed_reproj_, n_succeeded_reproj_ of points and segments, then their event bytes -- zero
+  {
+    Carver q;
+    q.take<int>(t.pt); q.take<int>(t.pt); q.take<int>(t.seg); q.take<int>(t.seg);
+    c->cs_ev_off = q.take<uint8_t>(t.pt); q.take<uint8_t>(t.seg);
+    HIP_TRY(c, c->cs_d_q.ensure(q.off + 256));
+    HIP_TRY(c, hipMemsetAsync(c->cs_d_q.p, 0, q.off, c->stream));
+  }
+  c->cd_t_pt = t.pt; c->cd_t_seg = t.seg; c->cd_t_ptc = t.ptc; c->cd_t_segc = t.segc; c->cd_t_opt = t.opt; c->cd_t_oseg = t.oseg;
   c->cd_staged = true;
   return PLSVO_OK;
 }
@@ -2550,7 +2575,7 @@ extern "C" int plsvo_candidates_run(plsvo_ctx* c, int n, const plsvo_cand_frame*
     if (!cand_idx_ok(fr[s].overlap_idx, (size_t)fr[s].n_overlap, 0, c->cd_maps[(size_t)s].n_kf)) return fail(c, PLSVO_E_INVALID, "candidates_run: overlap index outside the keyframe table");
     t_ov += (size_t)fr[s].n_overlap;
   }
-  c->cd_ran = false; c->cd_matched = false;
+  c->cd_ran = false; c->cd_matched = false; c->cs_selected = false; c->cs_posed = false;
   c->cd_ov_off.assign((size_t)n + 1, 0);
   if (n == 0) { c->cd_ran = true; return PLSVO_OK; }
   HIP_TRY(c, hipSetDevice(c->device));
@@ -2676,6 +2701,269 @@ extern "C" int plsvo_candidates_dev(plsvo_ctx* c, plsvo_cand_dev* o) {
   o->d_ref_px = b.m_ref_px; o->d_ref_f = b.m_ref_f; o->d_ref_level = b.m_ref_level; o->d_ref_type = b.m_ref_type; o->d_ref_grad = b.m_ref_grad;
   o->d_pos = b.m_pos; o->d_px_cur = b.m_px_cur; o->d_active = b.m_active;
   o->d_found = mb.found; o->d_px_out = mb.px_out; o->d_search_level = mb.search_level;
+  return PLSVO_OK;
+}
+
+// ---- cell selection of the map candidates: one per cell, landmark quality, features, pose-optimiser input (select_device.hpp) ---------
+namespace {
+// the sections of cs_d_q, as plsvo_candidates_stage carved them
+struct QualitySections { size_t pt_nf, pt_ns, seg_nf, seg_ns, pt_ev, seg_ev, end; };
+static QualitySections quality_sections(const plsvo_ctx* c) {
+  Carver q; QualitySections s;
+  s.pt_nf = q.take<int>(c->cd_t_pt); s.pt_ns = q.take<int>(c->cd_t_pt); s.seg_nf = q.take<int>(c->cd_t_seg); s.seg_ns = q.take<int>(c->cd_t_seg);
+  s.pt_ev = q.take<uint8_t>(c->cd_t_pt); s.seg_ev = q.take<uint8_t>(c->cd_t_seg); s.end = q.off;
+  return s;
+}
+// order (visit position -> cell) and its inverse, appended to v; false when `order` is no permutation of 0 .. n-1
+static bool append_cell_order(std::vector<int>& v, const int32_t* order, int n) {
+  const size_t at = v.size();
+  v.resize(at + 2 * (size_t)n, -1);
+  for (int k = 0; k < n; ++k) {
+    const int cell = order ? order[k] : k;
+    if (cell < 0 || cell >= n || v[at + (size_t)n + (size_t)cell] != -1) return false;
+    v[at + (size_t)k] = cell; v[at + (size_t)n + (size_t)cell] = k;
+  }
+  return true;
+}
+}  // namespace
+
+extern "C" int plsvo_candidates_set_quality(plsvo_ctx* c, int n, const plsvo_cand_quality_in* in) {
+  CTX_CHECK(c);
+  if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_set_quality: no staged map tables");
+  if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_set_quality: n does not match the staged batch");
+  for (int s = 0; s < n; ++s) {
+    const CandMapDev& M = c->cd_maps[(size_t)s];
+    const int32_t* arr[4] = { in[s].pt_n_failed, in[s].pt_n_succeeded, in[s].seg_n_failed, in[s].seg_n_succeeded };
+    for (int a = 0; a < 4; ++a) if (arr[a] && !cand_idx_ok(arr[a], (size_t)(a < 2 ? M.n_pt : M.n_seg), 0, INT32_MAX)) return fail(c, PLSVO_E_INVALID, "candidates_set_quality: negative counter");
+  }
+  if (n == 0) return PLSVO_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const QualitySections q = quality_sections(c);
+  const size_t sec[4] = { q.pt_nf, q.pt_ns, q.seg_nf, q.seg_ns };
+  char* d = reinterpret_cast<char*>(c->cs_d_q.p);
+  for (int s = 0; s < n; ++s) {
+    const CandMapDev& M = c->cd_maps[(size_t)s];
+    const int32_t* arr[4] = { in[s].pt_n_failed, in[s].pt_n_succeeded, in[s].seg_n_failed, in[s].seg_n_succeeded };
+    for (int a = 0; a < 4; ++a) {
+      const size_t cnt = (size_t)(a < 2 ? M.n_pt : M.n_seg), at = (size_t)(a < 2 ? M.pt_off : M.seg_off);
+      if (arr[a] && cnt) HIP_TRY(c, hipMemcpyAsync(d + sec[a] + at * sizeof(int), arr[a], cnt * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    }
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));      // the caller's arrays are free again
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_fetch_quality(plsvo_ctx* c, int n, plsvo_cand_quality_out* out) {
+  CTX_CHECK(c);
+  if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_fetch_quality: no staged map tables");
+  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_fetch_quality: n does not match the staged batch");
+  if (n == 0) return PLSVO_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const QualitySections q = quality_sections(c);
+  const CandBatchDev& b = c->cd_b;
+  std::vector<char> hq(q.end);
+  std::vector<CandMapDev> maps((size_t)n);
+  std::vector<int> ptype(std::max(c->cd_t_pt, (size_t)1)), stype(std::max(c->cd_t_seg, (size_t)1)), ptc(std::max(c->cd_t_ptc, (size_t)1)), segc(std::max(c->cd_t_segc, (size_t)1));
+  HIP_TRY(c, hipMemcpyAsync(hq.data(), c->cs_d_q.p, q.end, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(maps.data(), b.maps, (size_t)n * sizeof(CandMapDev), hipMemcpyDeviceToHost, c->stream));
+  if (c->cd_t_pt) HIP_TRY(c, hipMemcpyAsync(ptype.data(), b.pt_type, c->cd_t_pt * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (c->cd_t_seg) HIP_TRY(c, hipMemcpyAsync(stype.data(), b.seg_type, c->cd_t_seg * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (c->cd_t_ptc) HIP_TRY(c, hipMemcpyAsync(ptc.data(), b.pt_cand, c->cd_t_ptc * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  if (c->cd_t_segc) HIP_TRY(c, hipMemcpyAsync(segc.data(), b.seg_cand, c->cd_t_segc * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  auto cp = [&](void* dst, const void* src, size_t at, size_t count, size_t elem) { if (dst && count) memcpy(dst, reinterpret_cast<const char*>(src) + at * elem, count * elem); };
+  for (int s = 0; s < n; ++s) {
+    const CandMapDev& M = maps[(size_t)s];
+    plsvo_cand_quality_out& O = out[s];
+    const size_t np = (size_t)M.n_pt, ns = (size_t)M.n_seg, po = (size_t)M.pt_off, so = (size_t)M.seg_off;
+    O.n_pt_cand = M.n_pt_cand; O.n_seg_cand = M.n_seg_cand;
+    cp(O.pt_n_failed, hq.data() + q.pt_nf, po, np, sizeof(int)); cp(O.pt_n_succeeded, hq.data() + q.pt_ns, po, np, sizeof(int));
+    cp(O.seg_n_failed, hq.data() + q.seg_nf, so, ns, sizeof(int)); cp(O.seg_n_succeeded, hq.data() + q.seg_ns, so, ns, sizeof(int));
+    cp(O.pt_type, ptype.data(), po, np, sizeof(int)); cp(O.seg_type, stype.data(), so, ns, sizeof(int));
+    if (O.pt_event) for (size_t k = 0; k < np; ++k) O.pt_event[k] = (uint8_t)(hq[q.pt_ev + po + k] & (PLSVO_LM_EVENT_PROMOTED | PLSVO_LM_EVENT_DELETED));
+    if (O.seg_event) for (size_t k = 0; k < ns; ++k) O.seg_event[k] = (uint8_t)(hq[q.seg_ev + so + k] & (PLSVO_LM_EVENT_PROMOTED | PLSVO_LM_EVENT_DELETED));
+    cp(O.pt_cand, ptc.data(), (size_t)M.ptc_off, (size_t)M.n_pt_cand, sizeof(int)); cp(O.seg_cand, segc.data(), (size_t)M.segc_off, (size_t)M.n_seg_cand, sizeof(int));
+  }
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_set_match(plsvo_ctx* c, int n, const plsvo_cand_match_out* in) {
+  CTX_CHECK(c);
+  if (!c->cd_staged || !c->cd_ran) return fail(c, PLSVO_E_STATE, "candidates_set_match: no candidates on the device");
+  if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_set_match: n does not match the staged batch");
+  for (int s = 0; s < n; ++s) if (!in[s].found || !in[s].px || !in[s].search_level) return fail(c, PLSVO_E_INVALID, "candidates_set_match: null array");
+  if (n == 0 || c->cd_total_m == 0) { c->cd_matched = true; return PLSVO_OK; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  std::vector<int> cnt((size_t)n * 2);
+  HIP_TRY(c, hipMemcpyAsync(cnt.data(), c->cd_b.counts, cnt.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const MatchBatchDev& mb = c->cd_match;
+  for (int s = 0; s < n; ++s) {
+    const size_t at = (size_t)c->cd_maps[(size_t)s].m_off, k = (size_t)cnt[2 * s] + 2 * (size_t)cnt[2 * s + 1];
+    if (!k) continue;
+    HIP_TRY(c, hipMemcpyAsync(mb.found + at, in[s].found, k, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(mb.px_out + 2 * at, in[s].px, k * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(mb.search_level + at, in[s].search_level, k * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->cd_matched = true;
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_select(plsvo_ctx* c, const plsvo_cand_select_params* sp) {
+  CTX_CHECK(c);
+  if (!sp) return fail(c, PLSVO_E_INVALID, "candidates_select: bad arguments");
+  if (!c->cd_staged || !c->cd_ran || !c->cd_matched) return fail(c, PLSVO_E_STATE, "candidates_select: no match on the device");
+  if (c->cs_selected) return fail(c, PLSVO_E_STATE, "candidates_select: this run's candidates were selected already (the tables have moved on)");
+  if (sp->max_fts < 0 || sp->max_fts_segs < 0 || sp->poseopt_n_iter < 0)
+    return fail(c, PLSVO_E_INVALID, "candidates_select: bad parameters");
+  const plsvo_cand_params& pr = c->cd_params;
+  const int n = c->cd_n;
+  const int n_cells = c->cd_b.grid_n_cols * ((pr.cam.height + pr.cell_size - 1) / pr.cell_size);
+  const int seg_n_cells = c->cd_b.seg_grid_n_cols * ((pr.cam.height + pr.seg_cell_size - 1) / pr.seg_cell_size);
+  std::vector<int> order;
+  order.reserve(2 * ((size_t)n_cells + (size_t)seg_n_cells));
+  if (!append_cell_order(order, sp->cell_order, n_cells) || !append_cell_order(order, sp->seg_cell_order, seg_n_cells))
+    return fail(c, PLSVO_E_INVALID, "candidates_select: a cell order is not a permutation of its grid");
+  if (n == 0) { c->cs_selected = true; return PLSVO_OK; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (order != c->cs_order || !c->cs_d_order.p) {   // the visit orders travel when they change (the reference shuffles them once)
+    Blob blob; blob.add(order);
+    int rc;
+    if ((rc = upload_blob(c, c->cs_d_order, blob))) return rc;
+    c->cs_order = order;
+  }
+  const size_t N = (size_t)n, np = c->cd_t_opt, ns = 2 * c->cd_t_oseg;
+  Carver w;
+  const size_t w_win = w.take<unsigned int>(N * (size_t)n_cells), w_sc = w.take<int>(N * 3), w_plm = w.take<int>(np), w_ppx = w.take<double>(np * 2), w_plev = w.take<int>(np),
+               w_pty = w.take<uint8_t>(np), w_pgr = w.take<double>(np * 2), w_slm = w.take<int>(ns), w_spx = w.take<double>(ns * 4), w_slev = w.take<int>(ns),
+               w_jobs = w.take<PoseJobDev>(N), w_ptf = w.take<double>(np * 3), w_ptpos = w.take<double>(np * 3), w_ptlev = w.take<int>(np), w_line = w.take<double>(ns * 3),
+               w_spos = w.take<double>(ns * 3), w_epos = w.take<double>(ns * 3), w_seglev = w.take<int>(ns);
+  HIP_TRY(c, c->cs_d_work.ensure(w.off + 256));
+  const QualitySections q = quality_sections(c);
+  char* dq = reinterpret_cast<char*>(c->cs_d_q.p); char* dw = reinterpret_cast<char*>(c->cs_d_work.p);
+  const int* dord = c->cs_d_order.as<int>();
+  auto WD = [&](size_t o) { return reinterpret_cast<double*>(dw + o); };
+  auto WI = [&](size_t o) { return reinterpret_cast<int*>(dw + o); };
+  SelectBatchDev b{};
+  b.c = c->cd_b;
+  b.found = c->cd_match.found; b.px_out = c->cd_match.px_out; b.search_level = c->cd_match.search_level;
+  b.n_cells = n_cells; b.seg_n_cells = seg_n_cells; b.max_fts = sp->max_fts; b.max_fts_segs = sp->max_fts_segs; b.n_pyr_levels = pr.n_pyr_levels;
+  b.cell_order = dord; b.cell_pos = dord + n_cells; b.seg_cell_order = dord + 2 * n_cells; b.seg_cell_pos = dord + 2 * n_cells + seg_n_cells;
+  b.pt_nfail = reinterpret_cast<int*>(dq + q.pt_nf); b.pt_nsucc = reinterpret_cast<int*>(dq + q.pt_ns);
+  b.seg_nfail = reinterpret_cast<int*>(dq + q.seg_nf); b.seg_nsucc = reinterpret_cast<int*>(dq + q.seg_ns);
+  b.pt_event = reinterpret_cast<uint8_t*>(dq + q.pt_ev); b.seg_event = reinterpret_cast<uint8_t*>(dq + q.seg_ev);
+  b.cell_win = reinterpret_cast<unsigned int*>(dw + w_win);
+  b.f_pt_lm = WI(w_plm); b.f_pt_px = WD(w_ppx); b.f_pt_level = WI(w_plev); b.f_pt_type = reinterpret_cast<uint8_t*>(dw + w_pty); b.f_pt_grad = WD(w_pgr);
+  b.f_seg_lm = WI(w_slm); b.f_seg_px = WD(w_spx); b.f_seg_level = WI(w_slev); b.scalars = WI(w_sc);
+  b.po_jobs = reinterpret_cast<PoseJobDev*>(dw + w_jobs); b.pt_f = WD(w_ptf); b.pt_pos = WD(w_ptpos); b.pt_level = WI(w_ptlev);
+  b.seg_line = WD(w_line); b.seg_spos = WD(w_spos); b.seg_epos = WD(w_epos); b.seg_level = WI(w_seglev);
+  b.reproj_thresh = sp->reproj_thresh; b.po_n_iter = sp->poseopt_n_iter; b.ldlt_flavour = c->ldlt_flavour;
+  c->cs_b = b;
+  c->cs_win_bytes = N * (size_t)n_cells * sizeof(unsigned int);
+  {
+    EventPair ep{}; prof_begin(c, PLSVO_K_SELECT, &ep);
+    // ahead of EVERY launch: the event bytes are zero, the cells' winner words all ones
+    hipError_t rearm_then_launch = hipMemsetAsync(dq + q.pt_ev, 0, q.end - q.pt_ev, c->stream);
+    if (rearm_then_launch == hipSuccess) rearm_then_launch = hipMemsetAsync(b.cell_win, 0xff, c->cs_win_bytes, c->stream);
+    if (rearm_then_launch == hipSuccess) rearm_then_launch = launch_map_select(b, c->stream);
+    prof_end(c, PLSVO_K_SELECT, &ep);                // ahead of the error return, as in plsvo_candidates_run
+    HIP_TRY(c, rearm_then_launch);
+  }
+  c->cs_selected = true;
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_select_fetch(plsvo_ctx* c, int n, plsvo_cand_select_out* out) {
+  CTX_CHECK(c);
+  if (!c->cd_staged || !c->cs_selected) return fail(c, PLSVO_E_STATE, "candidates_select_fetch: no selection to fetch");
+  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_select_fetch: n does not match the staged batch");
+  if (n == 0) return PLSVO_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const SelectBatchDev& b = c->cs_b;
+  // the features lie between the scalars and the pose optimiser's jobs: one copy
+  const char* lo = reinterpret_cast<const char*>(b.scalars); const char* hi = reinterpret_cast<const char*>(b.po_jobs);
+  std::vector<char> h((size_t)(hi - lo));
+  HIP_TRY(c, hipMemcpyAsync(h.data(), lo, h.size(), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  auto H = [&](const void* dev) { return h.data() + (reinterpret_cast<const char*>(dev) - lo); };
+  auto cp = [&](void* dst, const void* dev, size_t at, size_t count, size_t elem) { if (dst && count) memcpy(dst, H(dev) + at * elem, count * elem); };
+  const int* sc = reinterpret_cast<const int*>(H(b.scalars));
+  for (int s = 0; s < n; ++s) {
+    const CandMapDev& M = c->cd_maps[(size_t)s];
+    plsvo_cand_select_out& O = out[s];
+    O.n_matches = sc[3 * s]; O.n_ls_matches = sc[3 * s + 1]; O.n_trials = sc[3 * s + 2]; O.reserved0 = 0;
+    const size_t np = (size_t)O.n_matches, ns = (size_t)O.n_ls_matches, po = (size_t)M.opt_off, so = 2 * (size_t)M.oseg_off;
+    cp(O.pt_lm, b.f_pt_lm, po, np, sizeof(int)); cp(O.pt_px, b.f_pt_px, po * 2, np * 2, sizeof(double)); cp(O.pt_level, b.f_pt_level, po, np, sizeof(int));
+    cp(O.pt_type, b.f_pt_type, po, np, 1); cp(O.pt_grad, b.f_pt_grad, po * 2, np * 2, sizeof(double));
+    cp(O.seg_lm, b.f_seg_lm, so, ns, sizeof(int)); cp(O.seg_px, b.f_seg_px, so * 4, ns * 4, sizeof(double)); cp(O.seg_level, b.f_seg_level, so, ns, sizeof(int));
+  }
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_pose_optimize(plsvo_ctx* c) {
+  CTX_CHECK(c);
+  if (!c->cd_staged || !c->cs_selected) return fail(c, PLSVO_E_STATE, "candidates_pose_optimize: no selection on the device");
+  const int n = c->cd_n;
+  c->cs_posed = false;
+  if (n == 0) { c->cs_posed = true; return PLSVO_OK; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t np = std::max(c->cd_t_opt, (size_t)1), ns = std::max(2 * c->cd_t_oseg, (size_t)1), nft = np + ns;
+  HIP_TRY(c, c->cs_d_ptkeep.ensure(np));
+  HIP_TRY(c, c->cs_d_segkeep.ensure(ns));
+  HIP_TRY(c, c->cs_d_s32.ensure(nft * sizeof(float)));
+  HIP_TRY(c, c->cs_d_s64.ensure(nft * 5 * sizeof(double)));
+  HIP_TRY(c, c->cs_d_state.ensure((size_t)n * sizeof(PoseStateDev)));
+  HIP_TRY(c, c->cs_d_poses.ensure((size_t)n * 7 * sizeof(double)));
+  const SelectBatchDev& b = c->cs_b;
+  PoseBatchDev& q = c->cs_pose;
+  q = PoseBatchDev{};
+  q.jobs = b.po_jobs; q.state = c->cs_d_state.as<PoseStateDev>();
+  q.pt_f = b.pt_f; q.pt_pos = b.pt_pos; q.pt_level = b.pt_level; q.seg_line = b.seg_line; q.seg_spos = b.seg_spos; q.seg_epos = b.seg_epos; q.seg_level = b.seg_level;
+  q.pt_keep = c->cs_d_ptkeep.as<uint8_t>(); q.seg_keep = c->cs_d_segkeep.as<uint8_t>();
+  q.scratch_f32 = c->cs_d_s32.as<float>(); q.scratch_f64 = c->cs_d_s64.as<double>();
+  q.log = nullptr; q.log_cap = 0; q.n_jobs = n;
+  const int threads = pose_opt_threads(c, n, (long)nft);   // (selected features <= filed landmarks)
+  c->p_refill_frames = 0;                           // (jobs written on the device, as in plsvo_chain_run)
+  EventPair ep{}; prof_begin(c, PLSVO_K_POSEOPT, &ep);
+  const hipError_t launched = launch_pose_opt(q, c->cs_d_poses.as<double>(), threads, c->opt_poseopt_select ? 1 : 0, c->stream);
+  prof_end(c, PLSVO_K_POSEOPT, &ep);
+  HIP_TRY(c, launched);
+  c->cs_posed = true;
+  return PLSVO_OK;
+}
+
+extern "C" const double* plsvo_candidates_poses_dev(plsvo_ctx* c) { return (c && c->cd_staged && c->cs_posed) ? c->cs_d_poses.as<double>() : nullptr; }
+
+extern "C" int plsvo_candidates_pose_fetch(plsvo_ctx* c, int n, plsvo_poseopt_out* out) {
+  CTX_CHECK(c);
+  if (!c->cd_staged || !c->cs_selected || !c->cs_posed) return fail(c, PLSVO_E_STATE, "candidates_pose_fetch: no pose optimisation to fetch");
+  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_pose_fetch: n does not match the staged batch");
+  if (n == 0) return PLSVO_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t NP = std::max(c->cd_t_opt, (size_t)1), NS = std::max(2 * c->cd_t_oseg, (size_t)1);
+  std::vector<PoseStateDev> st((size_t)n);
+  std::vector<PoseJobDev> jobs((size_t)n);
+  std::vector<uint8_t> pk(NP), sk(NS);
+  HIP_TRY(c, hipMemcpyAsync(st.data(), c->cs_d_state.p, (size_t)n * sizeof(PoseStateDev), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(jobs.data(), c->cs_b.po_jobs, (size_t)n * sizeof(PoseJobDev), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(pk.data(), c->cs_d_ptkeep.p, NP, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(sk.data(), c->cs_d_segkeep.p, NS, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (int j = 0; j < n; ++j) {
+    const PoseStateDev& s = st[(size_t)j]; const PoseJobDev& J = jobs[(size_t)j];
+    plsvo_poseopt_out& o = out[j];
+    uint8_t* pko = o.pt_keep; uint8_t* sko = o.seg_keep;
+    memset(&o, 0, sizeof(o));
+    o.pt_keep = pko; o.seg_keep = sko;
+    for (int k = 0; k < 7; ++k) o.T_f_w[k] = s.T[k];
+    for (int k = 0; k < 36; ++k) o.cov[k] = s.cov[k];
+    o.estimated_scale = s.estimated_scale; o.error_init = s.error_init; o.error_final = s.error_final;
+    o.num_obs_pt = s.num_obs_pt; o.num_obs_ls = s.num_obs_ls;
+    o.iters = s.iters; o.iters_ref = s.iters_ref; o.status = s.status;
+    if (pko && J.n_pts > 0) memcpy(pko, pk.data() + J.pt_off, (size_t)J.n_pts);
+    if (sko && J.n_seg > 0) memcpy(sko, sk.data() + J.seg_off, (size_t)J.n_seg);
+  }
   return PLSVO_OK;
 }
 

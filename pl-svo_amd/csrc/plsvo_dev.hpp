@@ -349,6 +349,28 @@ struct CandBatchDev {
   double* m_pos; double* m_px_cur; uint8_t* m_active;
 };
 
+// cell selection of the map candidates (select_device.hpp, include/plsvo_hip.h plsvo_candidates_select): one wave per stream, on the
+// arrays the candidate stage (c) and the resident match left on the device.  Per-landmark arrays follow pt_off / seg_off, feature rows
+// opt_off (points, at most one per filed point) and 2 * oseg_off (segments, at most two per filed segment).
+struct SelectBatchDev {
+  CandBatchDev c;
+  const uint8_t* found; const double* px_out; const int* search_level;   // the resident match (MatchBatchDev), entries from m_off
+  int n_cells, seg_n_cells, max_fts, max_fts_segs, n_pyr_levels;
+  const int* cell_order; const int* cell_pos;             // visit position -> cell and its inverse (n_cells entries each)
+  const int* seg_cell_order; const int* seg_cell_pos;
+  // resident landmark quality
+  int* pt_nfail; int* pt_nsucc; int* seg_nfail; int* seg_nsucc;
+  uint8_t* pt_event; uint8_t* seg_event;                  // zero before EVERY launch: kSel* bits
+  unsigned int* cell_win;                                 // n_cells words per stream, all ones before EVERY launch: the cell's first success
+  // the new frame's features, in the order refine() adds them
+  int* f_pt_lm; double* f_pt_px; int* f_pt_level; uint8_t* f_pt_type; double* f_pt_grad;
+  int* f_seg_lm; double* f_seg_px; int* f_seg_level;
+  int* scalars;                                           // 3 per stream: n_matches, n_ls_matches, n_trials
+  // pose-optimiser input (PoseBatchDev reads these)
+  PoseJobDev* po_jobs; double* pt_f; double* pt_pos; int* pt_level; double* seg_line; double* seg_spos; double* seg_epos; int* seg_level;
+  double reproj_thresh; int po_n_iter, ldlt_flavour;
+};
+
 // corner detection (detect_device.hpp, include/plsvo_hip.h plsvo_hip_detect_fast): tile geometry and the launch record
 constexpr int kDetTileW = 64, kDetTileH = 32;          // pixels of a tile that one workgroup decides
 constexpr int kDetImgX0 = 8, kDetImgY0 = 5;            // LDS image origin = tile origin - (8, 5): a halo of 5 (Shi-Tomasi: x - 5 .. x + 4), 8 keeps rows dword-aligned

@@ -23,6 +23,7 @@
 #include "match_device.hpp"
 #include "keyframe_device.hpp"   // the keyframe stage's kernels live in this translation unit for its -ffp-contract=off
 #include "candidates_device.hpp" // and the map candidates' kernel
+#include "select_device.hpp"     // and their cell selection
 
 namespace plsvo_hip {
 
@@ -402,6 +403,12 @@ hipError_t launch_keyframe_decide(const KfDecideBatchDev& b, hipStream_t stream)
 hipError_t launch_map_candidates(const CandBatchDev& b, hipStream_t stream) {
   if (b.n_jobs <= 0) return hipSuccess;
   hipLaunchKernelGGL(map_candidates_kernel, dim3((b.n_jobs + kCandWaves - 1) / kCandWaves), dim3(64 * kCandWaves), 0, stream, b);
+  return hipGetLastError();
+}
+// their cell selection (select_device.hpp): the same shape
+hipError_t launch_map_select(const SelectBatchDev& b, hipStream_t stream) {
+  if (b.c.n_jobs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_select_kernel, dim3((b.c.n_jobs + kSelWaves - 1) / kSelWaves), dim3(64 * kSelWaves), 0, stream, b);
   return hipGetLastError();
 }
 

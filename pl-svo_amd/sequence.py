@@ -36,6 +36,13 @@ becomes a keyframe, a seed converges into the map's candidate list), and hands e
 plsvo_close_keyframes with kf_select, otherwise every keyframe in table order.  The matches reach the pose optimiser in landmark-index
 order, as without it.
 
+With cell_select=True on top of it (a backend with map_select) the second half of Reprojector::reprojectMap runs on the device as well
+(plsvo_candidates_select): one candidate per grid cell in place of every found match, the landmark quality
+(n_failed_reproj_ / n_succeeded_reproj_, promotions, deletions) kept resident from frame to frame, and the pose optimiser fed on the
+device.  The harness follows the types, the candidate lists and the deletions in its own tables from fetch_quality, restages only when
+the map changes at a keyframe (or a seed converges), and carries the counters over a restage with fetch_quality / set_quality.  The
+features reach the pose optimiser in selection order; a segment that won both of its cells is a feature twice.
+
 `backend` is duck-typed: load_frames(list of level-0 images; HipBackend also takes raw frames with rectify=), sparse_align(job), reproject(job), match_direct(job),
 pose_optimize(job), for mapping structure_optimize(job), update_seeds(job), and for kf_select close_keyframes(job), keyframe_decide(job).  The product backend is HipBackend (C ABI on the GPU, no fallback); tests pass an oracle-backed one
 to check the whole chain end to end."""
@@ -104,6 +111,26 @@ class HipBackend:
         r = self.ctx.candidates_fetch()[0]
         self.ctx.candidates_match()
         return r, self.ctx.candidates_match_fetch([(r["n_filed_pt"], r["n_filed_seg"])])[0]
+
+    def map_select(self, map_job, frame_job, cam, n_pyr_levels, select, carry=None, cell_size=30, seg_cell_size=30):
+        """the map part of a frame as one enqueue sequence on the resident tables: candidates, match, cell selection, pose optimisation
+        (plsvo_candidates_run .. plsvo_candidates_pose_optimize).  map_job as in map_candidates; carry: the counters to put back after a
+        restage (a candidates_fetch_quality() record), select: the keyword arguments of capi.Context.candidates_select.
+        -> (the stage's result, the matcher's, the selection, the pose optimiser's result, the quality state after the frame)"""
+        if map_job is not None:
+            self.ctx.candidates_stage([map_job], cam, cell_size, seg_cell_size, 8, n_pyr_levels, 10)
+            if carry is not None:
+                self.ctx.candidates_set_quality([dict(pt_n_failed=carry["pt_n_failed"], pt_n_succeeded=carry["pt_n_succeeded"],
+                                                      seg_n_failed=carry["seg_n_failed"], seg_n_succeeded=carry["seg_n_succeeded"])])
+        self.ctx.candidates_run([frame_job])
+        self.ctx.candidates_match()
+        self.ctx.candidates_select(**select)
+        self.ctx.candidates_pose_optimize()
+        r = self.ctx.candidates_fetch()[0]
+        mr = self.ctx.candidates_match_fetch([(r["n_filed_pt"], r["n_filed_seg"])])[0]
+        sel = self.ctx.candidates_select_fetch()[0]
+        pr = self.ctx.candidates_pose_fetch([(sel["n_matches"], sel["n_ls_matches"])])[0]
+        return r, mr, sel, pr, self.ctx.candidates_fetch_quality()[0]
 
     def detect_corners(self, slot, occupancy=None, cell_size=25, n_levels=3, detection_threshold=20.0):
         """FastDetector::detect on the frame in `slot` (plsvo_hip_detect_fast): abi.CORNER_DTYPE records in cell order"""
@@ -198,7 +225,7 @@ def candidate_map_job(cm):
 
 def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_thresh=2.0, mapping=False, known_frac=0.6,
                  pos_noise=0.005, map_seed=0, kf_every=5, detect=False, detect_cell_size=25, kf_select=False, kfselect_mindist_t=0.06,
-                 kfselect_mindist_r=3.0, max_n_kfs=10, map_candidates=False, record_candidates=False):
+                 kfselect_mindist_r=3.0, max_n_kfs=10, map_candidates=False, record_candidates=False, cell_select=False, select_params=None):
     """-> list of per-frame dicts (pose T_f_w, cov, counts).  Frame 0 is the keyframe with the true pose.
     mapping=True: only `known_frac` of the point landmarks start in the map (positions off by `pos_noise` x depth along
     their viewing ray), the others are depth-filter seeds; the seed update runs every frame; every `kf_every`-th frame
@@ -213,10 +240,16 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
     map_candidates=True (a backend with map_candidates, not the resident chain): candidates and reference observations come from the
     map-candidate stage (module docstring); the records gain n_filed_pt / n_filed_seg and ref_kf_hist, how many of the filed landmarks
     took their reference observation from each keyframe of the table.  record_candidates=True also keeps each frame's stage inputs and
-    result in rec["candidates"] (tests)."""
+    result in rec["candidates"] (tests).
+    cell_select=True (with map_candidates, a backend with map_select): the cell selection and the resident pose optimiser take the place
+    of "every found match" and the per-call pose optimiser (module docstring); select_params: keyword arguments of
+    capi.Context.candidates_select (default: max_fts 120, max_fts_segs 100, cells in index order).  The records gain n_trials and
+    n_promoted / n_deleted; rec["candidates"] gains the selection and the quality state before and after the frame."""
     cam = seq["cam"]
-    if map_candidates and (hasattr(backend, "frame_step") or not hasattr(backend, "map_candidates")):
-        raise ValueError("map_candidates needs a per-call backend with map_candidates()")
+    if cell_select and not (map_candidates and hasattr(backend, "map_select")):
+        raise ValueError("cell_select needs map_candidates and a backend with map_select()")
+    if map_candidates and (hasattr(backend, "frame_step") or not hasattr(backend, "map_select" if cell_select else "map_candidates")):
+        raise ValueError("cell_select needs a per-call backend with map_select()" if cell_select else "map_candidates needs a per-call backend with map_candidates()")
     backend.load_frames(seq["images"])
     n_pts, n_seg = len(seq["pt_pos"]), len(seq["seg_spos"])
     T_prev = seq["poses_true"][0].copy()
@@ -284,6 +317,9 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
                   seg_obs=[[dict(kf=0, spx=f3(seq["seg_spx0"][i]), epx=f3(seq["seg_epx0"][i]), sf=f3(seq["seg_sf0"][i]), ef=f3(seq["seg_ef0"][i]), level=0)]
                            for i in range(n_seg)], pt_cand=[], seg_cand=[])
         cm_dirty = True
+        quality = None                                 # cell_select: the quality state after the last frame (None: nothing staged yet)
+        select_kw = dict(max_fts=120, max_fts_segs=100, cell_order=None, seg_cell_order=None, reproj_thresh=reproj_thresh)
+        select_kw.update(select_params or {})
     for k in range(1, len(seq["images"])):
         # ---- 1. sparse image alignment, previous frame -> frame k (processFrame :266-274) ----
         ref_pos = synth.se3_inv(T_prev)[4:]
@@ -324,7 +360,12 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
                     cm["pt_pos"] = [[float(x) for x in v] for v in P3]
                     map_job = candidate_map_job(cm)
                     cm_dirty = False
-                cr, mr = backend.map_candidates(map_job, abi.CandidateFrameJob(T_k, overlap, cur_slot=k), cam, n_pyr_levels)
+                if cell_select:
+                    cm_before = copy.deepcopy(cm) if record_candidates else None
+                    cr, mr, sel, pr_sel, q_after = backend.map_select(map_job, abi.CandidateFrameJob(T_k, overlap, cur_slot=k), cam, n_pyr_levels, select_kw,
+                                                                      carry=quality if map_job is not None else None)
+                else:
+                    cr, mr = backend.map_candidates(map_job, abi.CandidateFrameJob(T_k, overlap, cur_slot=k), cam, n_pyr_levels)
                 npf, nsf = cr["n_filed_pt"], cr["n_filed_seg"]
                 found = np.zeros(len(pos_all), bool)
                 px_new = np.zeros((len(pos_all), 2))
@@ -342,7 +383,21 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
                         hist[cm["seg_obs"][lm][o]["kf"]] += 1
                 cand_rec = dict(n_filed_pt=npf, n_filed_seg=nsf, ref_kf_hist=[int(v) for v in hist])
                 if record_candidates:
-                    cand_rec["candidates"] = dict(stream=copy.deepcopy(cm), T=[float(v) for v in T_k], overlap=list(overlap), out=cr, match=mr)
+                    cand_rec["candidates"] = dict(stream=cm_before if cell_select else copy.deepcopy(cm), T=[float(v) for v in T_k], overlap=list(overlap), out=cr, match=mr)
+                if cell_select:
+                    # the tables follow the device: types, candidate lists, and the keyframe features of the landmarks safeDelete* cut loose
+                    for name in ("pt", "seg"):
+                        for lm in np.nonzero(q_after[name + "_event"] & abi.LM_EVENT_DELETED)[0]:
+                            if cm[name + "_type"][int(lm)] == abi.LM_UNKNOWN:
+                                cm["kf_" + name] = [[-1 if v == lm else v for v in fts] for fts in cm["kf_" + name]]
+                        cm[name + "_type"] = [int(v) for v in q_after[name + "_type"]]
+                        cm[name + "_cand"] = [int(v) for v in q_after[name + "_cand"]]
+                    ev = np.concatenate([q_after["pt_event"], q_after["seg_event"]])
+                    cand_rec.update(n_trials=sel["n_trials"], n_promoted=int((ev & abi.LM_EVENT_PROMOTED).astype(bool).sum()),
+                                    n_deleted=int((ev & abi.LM_EVENT_DELETED).astype(bool).sum()))
+                    if record_candidates:
+                        cand_rec["candidates"].update(select=sel, quality_before=quality, quality=q_after, select_params=dict(select_kw))
+                    quality = q_after
             else:
                 # ---- 2. reprojection of the whole map (Reprojector::reprojectMap) ----
                 rp = backend.reproject(abi.ReprojectJob(cam, np.stack([kf_T, T_k]), np.ones(len(pos_all), np.int32), pos_all, cell_size=30))
@@ -367,6 +422,13 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
                 level[idx] = np.maximum(mr["search_level"], 0)
             pt_ok = found[:n_pts]
             seg_ok = found[n_pts:n_pts + n_seg] & found[n_pts + n_seg:]
+            if cell_select:
+                # ---- 4. on the device: the selected features in selection order, the resident pose optimiser's result ----
+                pt_i, seg_i = sel["pt_lm"].astype(np.int64), sel["seg_lm"].astype(np.int64)
+                pt_ok = np.zeros(n_pts, bool); pt_ok[pt_i] = True
+                seg_ok = np.zeros(n_seg, bool); seg_ok[seg_i] = True
+                pr = pr_sel
+        if not hasattr(backend, "frame_step") and not cell_select:
             # ---- 4. motion-only pose optimisation on the matches (processFrame :327-329) ----
             pt_i, seg_i = np.nonzero(pt_ok)[0], np.nonzero(seg_ok)[0]
             sf, ef = _bearing(cam, px_new[n_pts + seg_i]), _bearing(cam, px_new[n_pts + n_seg + seg_i])
@@ -420,7 +482,8 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
                     cm["kf_pt"].append([int(i) for i in kept]); cm["kf_seg"].append([int(i) for i in skept_])
                     for i, brg in zip(kept, _bearing(cam, px_new[kept])):
                         cm["pt_obs"][int(i)].insert(0, dict(kf=kf_id, px=f3(px_new[i]), f=f3(brg), level=int(level[i]), type=abi.FTR_CORNER, grad=[0.0, 0.0]))
-                        cm["pt_type"][int(i)] = abi.LM_UNKNOWN
+                        if not cell_select or cm["pt_type"][int(i)] == abi.LM_CANDIDATE:      # (a candidate that joins a keyframe: TYPE_UNKNOWN)
+                            cm["pt_type"][int(i)] = abi.LM_UNKNOWN
                     for i, sb, eb in zip(skept_, _bearing(cam, px_new[n_pts + skept_]), _bearing(cam, px_new[n_pts + n_seg + skept_])):
                         cm["seg_obs"][int(i)].insert(0, dict(kf=kf_id, spx=f3(px_new[n_pts + i]), epx=f3(px_new[n_pts + n_seg + i]), sf=f3(sb), ef=f3(eb),
                                                              level=int(level[n_pts + i])))

@@ -836,7 +836,7 @@ typedef struct plsvo_cand_match_out {
  * [m_off[s], m_off[s] + cap) with cap = n_pt + n_pt_cand + 2 * (n_seg + n_seg_cand), of which the first n_filed_pt + 2 * n_filed_seg
  * are candidates ([points | start points | end points]) and the rest have active == 0; counts holds n_filed_pt, n_filed_seg per
  * stream.  Frame indices are global: stream s owns frames [f_off[s], f_off[s] + n_kf] -- its keyframes, then the new frame.
- * Valid from plsvo_candidates_run until the next plsvo_candidates_stage. */
+ * Valid from plsvo_candidates_run until the next stage or insertion (plsvo_candidates_stage, plsvo_candidates_insert_keyframe). */
 typedef struct plsvo_cand_dev {
   int64_t n_entries, n_frames;
   const int64_t* m_off;             /* HOST arrays of n streams, owned by the context */
@@ -900,7 +900,8 @@ typedef struct plsvo_cand_quality_in {
 
 /* The quality state of one stream as it now stands.  Caller buffers, any may be NULL: n_pt / n_seg entries, the candidate lists
  * n_pt_cand / n_seg_cand of the STAGED counts, of which the first n_pt_cand / n_seg_cand reported here are written (an erased
- * candidate closes the list up).  *_event: PLSVO_LM_EVENT_* of the last plsvo_candidates_select, 0 before the first. */
+ * candidate closes the list up).  *_event: PLSVO_LM_EVENT_* of the last plsvo_candidates_select, 0 before the first; a keyframe
+ * insertion behind that selection ORs its own bits in (PLSVO_LM_EVENT_JOINED, PLSVO_LM_EVENT_DELETED). */
 typedef struct plsvo_cand_quality_out {
   int32_t n_pt_cand, n_seg_cand;
   int32_t* pt_n_failed; int32_t* pt_n_succeeded; int32_t* pt_type; uint8_t* pt_event;
@@ -946,6 +947,130 @@ const double* plsvo_candidates_poses_dev(plsvo_ctx* ctx);
  * plsvo_candidates_run with the caller's -- per stream n_filed_pt + 2 * n_filed_seg entries in the layout of plsvo_cand_match_out, all
  * three arrays required -- so that the selection can be driven with constructed match results.  Synchronous. */
 int plsvo_candidates_set_match(plsvo_ctx* ctx, int n, const plsvo_cand_match_out* in);
+
+/* ------------------------------------------------------------------------------------------ */
+/* keyframe insertion: the frame of the last plsvo_candidates_run becomes a keyframe of the     */
+/* resident tables, in place (one wave per stream).  It replaces, in this       */
+/* order: the landmark a rejected feature loses (src/pose_optimizer.cpp:218, :239); addFrameRef  */
+/* of every feature of the new frame, pushed at the FRONT of the landmark's list                */
+/* (src/frame_handler_mono.cpp:358-369, include/plsvo/feature3D.h:202-206);                      */
+/* MapPointCandidates::addCandidatePointToFrame and its segment twin (src/map.cpp:292-309,       */
+/* :384-401): a candidate the new frame observes becomes TYPE_UNKNOWN with n_failed_reproj_ 0,   */
+/* its original feature -- the LAST observation -- is appended to the feature list of that       */
+/* observation's keyframe, the entry leaves the candidate list; Map::safeDeleteFrame with        */
+/* removePtFrameRef / removeLsFrameRef (:53-114), safeDeletePoint / safeDeleteSegment (:116-139) */
+/* and removeFrameCandidates (:326-340) when a keyframe is removed; Map::addKeyframe (:153-156). */
+/* Keyframe identities are table indices: removing a keyframe closes the table up (every         */
+/* *_obs_kf above remove_kf drops by one) and the new keyframe is the LAST row.                  */
+/* Map::getFurthestKeyframe and the test map_.size() >= maxNKfs stay with the caller             */
+/* (plsvo_keyframe_decide reports furthest_kf).                                                  */
+/* Pinned where the reference leaves the result open:                                            */
+/*  - a feature of the new frame whose landmark is TYPE_DELETED when the frame becomes a         */
+/*    keyframe (a segment that won its first cell and was deleted by its failure in the second)  */
+/*    has no landmark; the reference keeps a feature that points at a trashed landmark;          */
+/*  - segment candidates of the removed keyframe are deleted and erased like point candidates;   */
+/*    the reference (src/map.cpp:73) calls removeFrameCandidates for points only and leaves a    */
+/*    segment candidate that observes a freed frame;                                             */
+/*  - Frame::key_pts_ (removeKeyPoint) are not in these tables: the deleted landmarks are        */
+/*    reported as events and the removed keyframe is the caller's own argument;                  */
+/*  - the observation list of a landmark deleted HERE is emptied (the reference clears it); a    */
+/*    landmark deleted earlier keeps its list, less the observations in the removed keyframe.    */
+/* Preconditions (unchecked) as for the selection, and: a landmark in a candidate list has       */
+/* exactly one observation; every feature of a keyframe that holds a landmark has an observation */
+/* of that landmark in that keyframe.                                                            */
+/* ------------------------------------------------------------------------------------------ */
+
+#define PLSVO_LM_EVENT_JOINED   4   /* a candidate whose original feature joined its keyframe (TYPE_CANDIDATE -> TYPE_UNKNOWN) by the last insertion */
+
+/* Room per stream beyond what is staged, added by the NEXT and every later plsvo_candidates_stage to each stream's sizes: the
+ * per-stream offsets are then laid out by capacity instead of by count (the matcher's frame table and kf_pos too), so a stream's
+ * rows never move.  NULL or all zeros: the tight layout -- every result, offset and byte is what it is without this call. */
+typedef struct plsvo_cand_reserve {
+  int32_t extra_kf;                 /* keyframes */
+  int32_t extra_kf_pt, extra_kf_seg;   /* entries of the keyframes' feature lists */
+  int32_t extra_pt_obs, extra_seg_obs; /* observations */
+  int32_t reserved0;
+} plsvo_cand_reserve;
+
+#define PLSVO_INSERT_POSE_HOST     0   /* T_f_w */
+#define PLSVO_INSERT_POSE_DEV      1   /* d_T_f_w: a DEVICE pointer to 7 doubles */
+#define PLSVO_INSERT_POSE_RESIDENT 2   /* the optimised pose of plsvo_candidates_pose_optimize, on the device */
+
+/* One stream's insertion: about 100 bytes. */
+typedef struct plsvo_cand_insert {
+  int32_t is_kf;                    /* 0: this stream is not touched at all */
+  int32_t remove_kf;                /* -1, or the table index of the keyframe Map::safeDeleteFrame removes */
+  int32_t kf_slot;                  /* the new keyframe's pyramid slot */
+  int32_t pose_source;              /* PLSVO_INSERT_POSE_* */
+  double T_f_w[7];
+  const double* d_T_f_w;
+  const uint8_t* pt_keep;           /* HOST keep masks in selection order (n_matches / n_ls_matches entries), or NULL: the resident */
+  const uint8_t* seg_keep;          /* masks of plsvo_candidates_pose_optimize */
+} plsvo_cand_insert;
+
+/* What an insertion did to one stream (zeros for a stream with is_kf == 0, except n_kf and the sizes, which are reported as they stand). */
+typedef struct plsvo_cand_insert_out {
+  int32_t n_kf;                     /* keyframes in the table now */
+  int32_t new_kf;                   /* the new keyframe's index (n_kf - 1), -1 for a stream that did not insert */
+  int32_t n_kf_pt, n_kf_seg;        /* used sizes: entries of the keyframes' feature lists */
+  int32_t n_pt_obs, n_seg_obs;      /* observations */
+  int32_t n_pt_cand, n_seg_cand;    /* the candidate lists */
+  int32_t n_joined_pt, n_joined_seg;     /* candidates that joined */
+  int32_t n_deleted_pt, n_deleted_seg;   /* landmarks deleted by the insertion */
+} plsvo_cand_insert_out;
+
+/* The resident tables of one stream as they now stand, in plsvo_cand_map's layout.  Caller buffers, any may be NULL, of the stream's
+ * CAPACITY as plsvo_candidates_capacity reports it (staged sizes plus the reserve in force at stage time; kf_T / kf_slot one row per
+ * keyframe of capacity, offsets one more than their lists; landmark arrays n_pt / n_seg, candidate lists their staged counts); the
+ * counts are reported.  The library cannot see the buffers' sizes: smaller ones are overrun. */
+typedef struct plsvo_cand_map_out {
+  int32_t n_kf, n_pt, n_seg, n_pt_cand, n_seg_cand;
+  int32_t n_kf_pt, n_kf_seg, n_pt_obs, n_seg_obs;
+  int32_t reserved0;
+  double* kf_T; int32_t* kf_slot; int32_t* kf_pt_off; int32_t* kf_pt_lm; int32_t* kf_seg_off; int32_t* kf_seg_lm;
+  double* pt_pos; int32_t* pt_type; int32_t* pt_obs_off; int32_t* pt_obs_kf; double* pt_obs_px; double* pt_obs_f; int32_t* pt_obs_level; uint8_t* pt_obs_type; double* pt_obs_grad;
+  double* seg_spos; double* seg_epos; int32_t* seg_type; int32_t* seg_obs_off; int32_t* seg_obs_kf; double* seg_obs_spx; double* seg_obs_epx; double* seg_obs_sf; double* seg_obs_ef;
+  int32_t* seg_obs_level;
+  int32_t* pt_cand; int32_t* seg_cand;
+} plsvo_cand_map_out;
+
+/* Landmark positions the caller has moved (FrameHandlerBase::optimizeStructure, src/frame_handler_mono.cpp:340): Point::pos_ of
+ * n_pt listed points, LineSeg::spos_ / epos_ of n_seg listed segments.  A landmark listed twice in one call ends with either of its
+ * positions (one thread writes each entry, unordered): list a landmark once. */
+typedef struct plsvo_cand_positions {
+  int32_t n_pt, n_seg;
+  const int32_t* pt_idx; const double* pt_pos;                           /* n_pt, 3*n_pt */
+  const int32_t* seg_idx; const double* seg_spos; const double* seg_epos; /* n_seg, 3*n_seg each */
+} plsvo_cand_positions;
+
+/* reserve: host only; PLSVO_E_INVALID for a negative field.
+ * insert_keyframe: SYNCHRONISES -- the caller has just waited for the keyframe decision.  A planning launch writes scratch only and a
+ * few integers per stream come back; capacity is decided before anything is changed: if any inserting stream's new sizes (keyframes,
+ * features per kind, observations per kind) exceed its room the call returns PLSVO_E_CAPACITY and EVERY stream's tables are what they
+ * were.  Then one launch changes the tables of the inserting streams; nothing but the per-stream records (and host keep masks) crosses
+ * the bus.  Afterwards the next plsvo_candidates_run / _match / _select / _pose_optimize work on the new tables; overlap indices are
+ * validated against the new keyframe count.  The insertion ORs PLSVO_LM_EVENT_JOINED / PLSVO_LM_EVENT_DELETED into the event bytes
+ * plsvo_candidates_fetch_quality reports; it does not clear the selection's bits.
+ * PLSVO_E_STATE: no selection on the last run; NULL masks or PLSVO_INSERT_POSE_RESIDENT without a resident pose optimisation; a second
+ * insertion on the same run.  PLSVO_E_INVALID (nothing written): another n than staged, NULL in with n > 0, remove_kf outside the
+ * table, a negative slot, an unknown pose source, PLSVO_INSERT_POSE_DEV without a pointer.
+ * After an insertion the run it closed is over: plsvo_candidates_match / _set_match / _select / _pose_optimize / _dev return PLSVO_E_STATE
+ * until the next plsvo_candidates_run (their inputs index the tables as they were); the run's fetches (plsvo_candidates_fetch,
+ * _match_fetch, _select_fetch, _pose_fetch, _poses_dev) still return its results, whose observation and keyframe indices refer to the
+ * tables BEFORE the insertion.
+ * capacity: per stream the room its rows were laid out with at stage time (staged sizes plus the reserve in force THEN; a later
+ * plsvo_candidates_reserve does not change it), in the fields of plsvo_cand_reserve: keyframes, feature entries per kind, observations per
+ * kind.  These are the buffer sizes plsvo_candidates_fetch_map needs.
+ * insert_fetch: what the last insertion did; PLSVO_E_STATE before the first one since the tables were staged.
+ * fetch_map: synchronous, valid from plsvo_candidates_stage on.
+ * set_positions: a host-fed scatter into the resident landmark tables, enqueue-only after the copy of the lists; PLSVO_E_INVALID
+ * (nothing written) for an index outside the stream's landmarks, a negative count or a NULL array with a non-zero count. */
+int plsvo_candidates_reserve(plsvo_ctx* ctx, const plsvo_cand_reserve* reserve);
+int plsvo_candidates_insert_keyframe(plsvo_ctx* ctx, int n, const plsvo_cand_insert* in);
+int plsvo_candidates_capacity(plsvo_ctx* ctx, int n, plsvo_cand_reserve* out);
+int plsvo_candidates_insert_fetch(plsvo_ctx* ctx, int n, plsvo_cand_insert_out* out);
+int plsvo_candidates_fetch_map(plsvo_ctx* ctx, int n, plsvo_cand_map_out* out);
+int plsvo_candidates_set_positions(plsvo_ctx* ctx, int n, const plsvo_cand_positions* in);
 
 /* TUM-style trajectory record of a frame (app/run_pipeline.cpp:425-451): the camera pose in the world,
  * T_f_w^-1, as tx ty tz qx qy qz qw.  Returns 1 and fills out7 when the reference would write the line, 0 when
@@ -1076,7 +1201,8 @@ int plsvo_gather_poses(plsvo_ctx* ctx, void* rccl_comm, const plsvo_pose_record*
 #define PLSVO_K_KEYFRAME      7   /* plsvo_close_keyframes / plsvo_keyframe_decide: the launch alone, without packing and copies */
 #define PLSVO_K_CANDIDATES    8   /* plsvo_candidates_run: the re-arm and the launch alone (the resident match counts under PLSVO_K_MATCH) */
 #define PLSVO_K_SELECT        9   /* plsvo_candidates_select: the re-arm and the launch alone */
-#define PLSVO_K_COUNT         10
+#define PLSVO_K_INSERT        10  /* plsvo_candidates_insert_keyframe: the launch that changes the tables (the planning launch is timed by the caller's clock) */
+#define PLSVO_K_COUNT         11
 int plsvo_hip_set_profiling(plsvo_ctx* ctx, int enable);
 /* accumulated GPU time and launch count of kernel family k since the last reset (synchronises) */
 int plsvo_hip_kernel_time(plsvo_ctx* ctx, int k, double* total_ms, int64_t* launches);

@@ -18,7 +18,7 @@ c_i32_p = C.POINTER(C.c_int32)
 OK, E_INVALID, E_NODEVICE, E_HIP, E_CAPACITY, E_STATE, E_RCCL = 0, -1, -2, -3, -4, -5, -6
 
 # kernel families for plsvo_hip_kernel_time
-K_ALIGN_INIT, K_ALIGN_LEVEL, K_POSEOPT, K_HALFSAMPLE, K_STRUCTOPT, K_MATCH, K_SEEDS, K_KEYFRAME, K_CANDIDATES, K_SELECT, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
+K_ALIGN_INIT, K_ALIGN_LEVEL, K_POSEOPT, K_HALFSAMPLE, K_STRUCTOPT, K_MATCH, K_SEEDS, K_KEYFRAME, K_CANDIDATES, K_SELECT, K_INSERT, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
 SEED_NOT_VISIBLE, SEED_NO_MATCH, SEED_UPDATED, SEED_CONVERGED, SEED_NAN = 0, 1, 2, 3, 4
 FTR_CORNER, FTR_EDGELET = 0, 1
 LM_DELETED, LM_CANDIDATE, LM_UNKNOWN, LM_GOOD = 0, 1, 2, 3
@@ -249,6 +249,38 @@ class CandSelectOut(C.Structure):
 
 
 LM_EVENT_PROMOTED, LM_EVENT_DELETED = 1, 2
+LM_EVENT_JOINED = 4
+INSERT_POSE_HOST, INSERT_POSE_DEV, INSERT_POSE_RESIDENT = 0, 1, 2
+
+
+class CandReserve(C.Structure):
+    """plsvo_cand_reserve"""
+    _fields_ = [("extra_kf", C.c_int32), ("extra_kf_pt", C.c_int32), ("extra_kf_seg", C.c_int32), ("extra_pt_obs", C.c_int32), ("extra_seg_obs", C.c_int32),
+                ("reserved0", C.c_int32)]
+
+
+class CandInsert(C.Structure):
+    """plsvo_cand_insert"""
+    _fields_ = [("is_kf", C.c_int32), ("remove_kf", C.c_int32), ("kf_slot", C.c_int32), ("pose_source", C.c_int32), ("T_f_w", C.c_double * 7), ("d_T_f_w", C.c_void_p),
+                ("pt_keep", c_u8_p), ("seg_keep", c_u8_p)]
+
+
+class CandInsertOut(C.Structure):
+    """plsvo_cand_insert_out"""
+    _fields_ = [(f, C.c_int32) for f in ("n_kf", "new_kf", "n_kf_pt", "n_kf_seg", "n_pt_obs", "n_seg_obs", "n_pt_cand", "n_seg_cand", "n_joined_pt", "n_joined_seg",
+                                         "n_deleted_pt", "n_deleted_seg")]
+
+
+class CandMapOut(C.Structure):
+    """plsvo_cand_map_out"""
+    _fields_ = [(f, C.c_int32) for f in ("n_kf", "n_pt", "n_seg", "n_pt_cand", "n_seg_cand", "n_kf_pt", "n_kf_seg", "n_pt_obs", "n_seg_obs", "reserved0")] + \
+               [(f, c_i32_p if f in _CAND_MAP_I32 else c_u8_p if f in _CAND_MAP_U8 else c_double_p) for f in _CAND_MAP_ORDER]
+
+
+class CandPositions(C.Structure):
+    """plsvo_cand_positions"""
+    _fields_ = [("n_pt", C.c_int32), ("n_seg", C.c_int32), ("pt_idx", c_i32_p), ("pt_pos", c_double_p), ("seg_idx", c_i32_p), ("seg_spos", c_double_p),
+                ("seg_epos", c_double_p)]
 
 
 class CandDev(C.Structure):

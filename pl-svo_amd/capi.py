@@ -30,6 +30,7 @@ SYMBOLS = [
     "plsvo_candidates_stage", "plsvo_candidates_run", "plsvo_candidates_fetch", "plsvo_candidates_match", "plsvo_candidates_match_fetch", "plsvo_candidates_dev",
     "plsvo_candidates_set_quality", "plsvo_candidates_fetch_quality", "plsvo_candidates_select", "plsvo_candidates_select_fetch", "plsvo_candidates_pose_optimize",
     "plsvo_candidates_pose_fetch", "plsvo_candidates_poses_dev", "plsvo_candidates_set_match",
+    "plsvo_candidates_reserve", "plsvo_candidates_capacity", "plsvo_candidates_insert_keyframe", "plsvo_candidates_insert_fetch", "plsvo_candidates_fetch_map", "plsvo_candidates_set_positions",
     "plsvo_chain_stage", "plsvo_chain_run", "plsvo_chain_fetch", "plsvo_frame_step_batch", "plsvo_chain_poses_dev",
     "plsvo_pack_pose_records", "plsvo_fetch_pose_records", "plsvo_gather_poses",
     "plsvo_hip_set_profiling", "plsvo_hip_kernel_time", "plsvo_hip_reset_profiling",
@@ -158,6 +159,12 @@ def lib():
         "plsvo_candidates_pose_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.PoseOptOut)]),
         "plsvo_candidates_poses_dev": (vp, [ctxp]),
         "plsvo_candidates_set_match": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandMatchOut)]),
+        "plsvo_candidates_reserve": (C.c_int, [ctxp, C.POINTER(abi.CandReserve)]),
+        "plsvo_candidates_capacity": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandReserve)]),
+        "plsvo_candidates_insert_keyframe": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandInsert)]),
+        "plsvo_candidates_insert_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandInsertOut)]),
+        "plsvo_candidates_fetch_map": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandMapOut)]),
+        "plsvo_candidates_set_positions": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandPositions)]),
         "plsvo_update_seeds": (C.c_int, [ctxp, C.POINTER(abi.SeedsIn), C.POINTER(abi.SeedsOut)]),
         "plsvo_trajectory_record": (C.c_int, [abi.c_double_p, abi.c_double_p, abi.c_double_p]),
         "plsvo_chain_stage": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.ChainIn), C.POINTER(abi.ChainParams)]),
@@ -789,6 +796,110 @@ class Context:
 
     def candidates_poses_dev(self):
         return self.L.plsvo_candidates_poses_dev(self.h)
+
+    # ---- keyframe insertion into the resident map tables ----
+    def candidates_reserve(self, extra_kf=0, extra_kf_pt=0, extra_kf_seg=0, extra_pt_obs=0, extra_seg_obs=0):
+        """plsvo_candidates_reserve: room per stream that the NEXT and every later candidates_stage adds to the staged sizes"""
+        r = abi.CandReserve(int(extra_kf), int(extra_kf_pt), int(extra_kf_seg), int(extra_pt_obs), int(extra_seg_obs), 0)
+        self._chk(self.L.plsvo_candidates_reserve(self.h, C.byref(r)))
+
+    def candidates_capacity(self):
+        """plsvo_candidates_capacity: per staged stream a dict of the room its rows were laid out with (kf, kf_pt, kf_seg, pt_obs, seg_obs)"""
+        n = len(self._cand_maps)
+        outs = (abi.CandReserve * max(n, 1))()
+        self._chk(self.L.plsvo_candidates_capacity(self.h, n, outs))
+        return [dict(kf=o.extra_kf, kf_pt=o.extra_kf_pt, kf_seg=o.extra_kf_seg, pt_obs=o.extra_pt_obs, seg_obs=o.extra_seg_obs) for o in outs[:n]]
+
+    def candidates_insert_keyframe(self, inserts):
+        """plsvo_candidates_insert_keyframe (synchronises): per staged stream None (not touched) or a dict of remove_kf (-1: none), kf_slot,
+        T_f_w (7 doubles), or poses_dev (a device pointer), or neither (the resident optimised pose), and optionally pt_keep / seg_keep
+        (host masks in selection order; missing: the resident pose optimiser's)"""
+        n = len(inserts)
+        arr = (abi.CandInsert * max(n, 1))()
+        keep = []
+        for a, i in zip(arr, inserts):
+            if i is None:
+                continue
+            a.is_kf, a.remove_kf, a.kf_slot = 1, int(i.get("remove_kf", -1)), int(i.get("kf_slot", 0))
+            if i.get("T_f_w") is not None:
+                a.pose_source, a.T_f_w = abi.INSERT_POSE_HOST, (C.c_double * 7)(*[float(v) for v in i["T_f_w"]])
+            elif i.get("poses_dev") is not None:
+                a.pose_source, a.d_T_f_w = abi.INSERT_POSE_DEV, int(i["poses_dev"])
+            else:
+                a.pose_source = abi.INSERT_POSE_RESIDENT
+            for f in ("pt_keep", "seg_keep"):
+                if i.get(f) is not None:
+                    v = np.ascontiguousarray(i[f], dtype=np.uint8).reshape(-1)
+                    v = v if v.size else np.zeros(1, np.uint8)
+                    keep.append(v)
+                    setattr(a, f, v.ctypes.data_as(abi.c_u8_p))
+        self._chk(self.L.plsvo_candidates_insert_keyframe(self.h, n, arr))
+
+    def candidates_insert_fetch(self):
+        """plsvo_candidates_insert_fetch: per stream a dict of what the last insertion did (abi.CandInsertOut's fields)"""
+        n = len(self._cand_maps)
+        outs = (abi.CandInsertOut * max(n, 1))()
+        self._chk(self.L.plsvo_candidates_insert_fetch(self.h, n, outs))
+        return [{f: int(getattr(o, f)) for f, _ in abi.CandInsertOut._fields_} for o in outs[:n]]
+
+    def candidates_fetch_map(self, streams=None):
+        """plsvo_candidates_fetch_map: per stream a dict of the resident tables as they now stand, arrays named and shaped like
+        abi.CandidateMapJob's tables (CSR offsets relative to the stream).  The buffers have the capacity the library reports
+        (plsvo_candidates_capacity: the layout of the last stage).  streams: the indices to fetch (default all); the others come back as
+        None and cost no buffer"""
+        maps = self._cand_maps
+        n = len(maps)
+        caps = self.candidates_capacity()
+        wanted = set(range(n)) if streams is None else set(int(s) for s in streams)
+        outs = (abi.CandMapOut * max(n, 1))()
+        bufs = []
+        width = abi.CandidateMapJob._WIDTH
+        for k, (o, m, cap) in enumerate(zip(outs, maps, caps)):
+            if k not in wanted:
+                bufs.append(None)
+                continue
+            rows = dict(kf_T=cap["kf"], kf_slot=cap["kf"], kf_pt_off=cap["kf"] + 1, kf_seg_off=cap["kf"] + 1, kf_pt_lm=cap["kf_pt"], kf_seg_lm=cap["kf_seg"],
+                        pt_pos=m.n_pt, pt_type=m.n_pt, pt_obs_off=m.n_pt + 1, seg_spos=m.n_seg, seg_epos=m.n_seg, seg_type=m.n_seg, seg_obs_off=m.n_seg + 1,
+                        pt_cand=m.n_pt_cand, seg_cand=m.n_seg_cand)
+            b = {}
+            for f in abi._CAND_MAP_ORDER:
+                rows_n = rows[f] if f in rows else cap["pt_obs"] if f.startswith("pt_obs") else cap["seg_obs"]
+                dt = np.int32 if f in abi._CAND_MAP_I32 else np.uint8 if f in abi._CAND_MAP_U8 else np.float64
+                b[f] = np.zeros((max(rows_n, 1), width[f]) if f in width else max(rows_n, 1), dt)
+                setattr(o, f, self._ptr(b[f]))
+            bufs.append(b)
+        self._chk(self.L.plsvo_candidates_fetch_map(self.h, n, outs))
+        res = []
+        for o, b in zip(outs[:n], bufs):
+            if b is None:
+                res.append(None)
+                continue
+            cut = dict(kf_T=o.n_kf, kf_slot=o.n_kf, kf_pt_off=o.n_kf + 1, kf_seg_off=o.n_kf + 1, kf_pt_lm=o.n_kf_pt, kf_seg_lm=o.n_kf_seg, pt_pos=o.n_pt, pt_type=o.n_pt,
+                       pt_obs_off=o.n_pt + 1, seg_spos=o.n_seg, seg_epos=o.n_seg, seg_type=o.n_seg, seg_obs_off=o.n_seg + 1, pt_cand=o.n_pt_cand, seg_cand=o.n_seg_cand)
+            res.append({f: v[:(cut[f] if f in cut else o.n_pt_obs if f.startswith("pt_obs") else o.n_seg_obs)].copy() for f, v in b.items()})
+        return res
+
+    def candidates_set_positions(self, moved):
+        """plsvo_candidates_set_positions (enqueue only after the copy): per staged stream None or a dict of pt_idx / pt_pos [k, 3] and
+        seg_idx / seg_spos / seg_epos [k, 3]"""
+        n = len(moved)
+        arr = (abi.CandPositions * max(n, 1))()
+        keep = []
+        for a, m in zip(arr, moved):
+            if not m:
+                continue
+            for idx, fields in (("pt_idx", ("pt_pos",)), ("seg_idx", ("seg_spos", "seg_epos"))):
+                if m.get(idx) is None or len(m[idx]) == 0:
+                    continue
+                i = np.ascontiguousarray(m[idx], dtype=np.int32).reshape(-1)
+                keep.append(i)
+                setattr(a, idx, i.ctypes.data_as(abi.c_i32_p))
+                setattr(a, "n_pt" if idx == "pt_idx" else "n_seg", i.size)
+                for f in fields:
+                    v = np.ascontiguousarray(m[f], dtype=np.float64).reshape(-1, 3)
+                    keep.append(v)
+                    setattr(a, f, v.ctypes.data_as(abi.c_double_p))
+        self._chk(self.L.plsvo_candidates_set_positions(self.h, n, arr))
 
     # ---- structure optimisation ----
     def structure_optimize(self, job):

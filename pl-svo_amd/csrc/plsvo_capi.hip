@@ -37,6 +37,9 @@ hipError_t launch_close_keyframes(const CloseKfBatchDev& b, hipStream_t stream);
 hipError_t launch_keyframe_decide(const KfDecideBatchDev& b, hipStream_t stream);
 hipError_t launch_map_candidates(const CandBatchDev& b, hipStream_t stream);         // candidates_device.hpp, in seeds_kernels.hip
 hipError_t launch_map_select(const SelectBatchDev& b, hipStream_t stream);            // select_device.hpp, in seeds_kernels.hip
+hipError_t launch_map_insert_plan(const InsertBatchDev& b, hipStream_t stream);       // insert_device.hpp, in seeds_kernels.hip
+hipError_t launch_map_insert(const InsertBatchDev& b, hipStream_t stream);
+hipError_t launch_map_set_positions(const PositionsBatchDev& b, hipStream_t stream);
 hipError_t launch_halfsample(const uint8_t* src, size_t src_pitch, int in_w, int in_h, int in_stride, uint8_t* dst,
                              size_t dst_pitch, int n_slots, int rounding, hipStream_t stream);
 hipError_t launch_copy_level0(const uint8_t* src, size_t src_pitch, int w, int h, int stride, uint8_t* dst, size_t dst_pitch,
@@ -211,6 +214,15 @@ struct plsvo_ctx {
   DevBuf cs_d_q, cs_d_work, cs_d_order, cs_d_state, cs_d_ptkeep, cs_d_segkeep, cs_d_s32, cs_d_s64, cs_d_poses;
   SelectBatchDev cs_b{};
   PoseBatchDev cs_pose{};
+  // keyframe insertion (plsvo_candidates_insert_keyframe ..): the room plsvo_candidates_reserve asks for (ci_reserve: the next stage's),
+  // per stream its capacities (ci_cap: keyframes, features per kind, observations per kind) and used sizes (ci_used: the last four),
+  // the capacity totals, the last insertion's report; scratch and staging rows (ci_d_work), a call's records and host masks (ci_d_in)
+  plsvo_cand_reserve ci_reserve{};
+  std::vector<int> ci_cap, ci_used;
+  size_t ci_t_kf = 0, ci_t_kfpt = 0, ci_t_kfseg = 0, ci_t_ptobs = 0, ci_t_segobs = 0, cd_blob_bytes = 0;
+  bool ci_inserted = false, ci_have_out = false;
+  std::vector<InsertPlanDev> ci_last;
+  DevBuf ci_d_work, ci_d_in, ci_d_plan, ci_d_pos;
   unsigned long long run_seq = 0, a_run_seq = 0, p_run_seq = 0, ch_run_seq = 0;   // which resident batch ran last, 0 = not since it was staged (plsvo_pack_pose_records)
 
   // structure optimisation (one-shot batches)
@@ -351,6 +363,7 @@ extern "C" void plsvo_hip_destroy(plsvo_ctx* c) {
   c->a_d_tailflag.release(); c->a_d_alive_tail.release(); c->a_d_xbuf.release(); c->a_d_order[0].release(); c->a_d_order[1].release(); c->a_d_workkey.release(); c->p_d_workkey.release(); c->p_d_order[0].release(); c->p_d_order[1].release();
   c->p_d_carry.release(); c->p_d_refill_next.release();
   c->cd_d_blob.release(); c->cd_d_work.release(); c->cd_d_run.release(); c->cd_d_kfcount.release();
+  for (DevBuf* b : { &c->ci_d_work, &c->ci_d_in, &c->ci_d_plan, &c->ci_d_pos }) b->release();
   for (DevBuf* b : { &c->cs_d_q, &c->cs_d_work, &c->cs_d_order, &c->cs_d_state, &c->cs_d_ptkeep, &c->cs_d_segkeep, &c->cs_d_s32, &c->cs_d_s64, &c->cs_d_poses }) b->release();
   DevBuf* bufs[] = { &c->pyr_slab, &c->pyr_tiled, &c->pyr_upload, &c->a_d_blob, &c->a_d_state, &c->a_d_alive, &c->a_d_pxyz, &c->a_d_puv, &c->a_d_cref,
                      &c->a_d_chi, &c->a_d_log, &c->a_d_poses, &c->p_d_blob, &c->p_d_state, &c->p_d_ptkeep, &c->p_d_segkeep, &c->p_d_s32, &c->p_d_s64,
@@ -2403,6 +2416,8 @@ extern "C" int plsvo_candidates_stage(plsvo_ctx* c, int n, const plsvo_cand_map*
   CandTotals t;
   int max_level = 0;
   std::vector<CandMapDev> md((size_t)n);
+  const plsvo_cand_reserve R = c->ci_reserve;       // room beyond the staged sizes: the offsets below are laid out by capacity
+  std::vector<int> cap((size_t)n * 5), used((size_t)n * 4);
   for (int s = 0; s < n; ++s) {
     const plsvo_cand_map& I = maps[s];
     if (I.n_kf < 0 || I.n_pt < 0 || I.n_seg < 0 || I.n_pt_cand < 0 || I.n_seg_cand < 0) return fail(c, PLSVO_E_INVALID, "candidates_stage: negative count");
@@ -2444,12 +2459,19 @@ extern "C" int plsvo_candidates_stage(plsvo_ctx* c, int n, const plsvo_cand_map*
     M.opt_off = (long long)t.opt; M.oseg_off = (long long)t.oseg; M.m_off = (long long)t.m; M.f_off = (long long)t.f;
     M.vis_pt_off = (long long)t.vis; t.vis += ((size_t)I.n_pt + 63) & ~(size_t)63;
     M.vis_seg_off = (long long)t.vis; t.vis += ((size_t)I.n_seg + 63) & ~(size_t)63;
-    t.kf += (size_t)I.n_kf; t.kfpt += kfpt; t.kfseg += kfseg; t.pt += (size_t)I.n_pt; t.seg += (size_t)I.n_seg; t.ptobs += ptobs; t.segobs += segobs;
+    if (kfpt + (size_t)R.extra_kf_pt > (size_t)INT32_MAX || kfseg + (size_t)R.extra_kf_seg > (size_t)INT32_MAX || ptobs + (size_t)R.extra_pt_obs > (size_t)INT32_MAX ||
+        segobs + (size_t)R.extra_seg_obs > (size_t)INT32_MAX || (size_t)I.n_kf + (size_t)R.extra_kf > (size_t)INT32_MAX) return fail(c, PLSVO_E_CAPACITY, "candidates_stage: stream too large");
+    int* cp = cap.data() + 5 * (size_t)s; int* us = used.data() + 4 * (size_t)s;
+    cp[0] = I.n_kf + R.extra_kf; cp[1] = (int)kfpt + R.extra_kf_pt; cp[2] = (int)kfseg + R.extra_kf_seg; cp[3] = (int)ptobs + R.extra_pt_obs; cp[4] = (int)segobs + R.extra_seg_obs;
+    us[0] = (int)kfpt; us[1] = (int)kfseg; us[2] = (int)ptobs; us[3] = (int)segobs;
+    t.kf += (size_t)cp[0]; t.kfpt += (size_t)cp[1]; t.kfseg += (size_t)cp[2]; t.pt += (size_t)I.n_pt; t.seg += (size_t)I.n_seg; t.ptobs += (size_t)cp[3]; t.segobs += (size_t)cp[4];
     t.ptc += (size_t)I.n_pt_cand; t.segc += (size_t)I.n_seg_cand; t.opt += (size_t)M.cap_pt; t.oseg += (size_t)M.cap_seg;
-    t.m += (size_t)M.cap_pt + 2 * (size_t)M.cap_seg; t.f += (size_t)I.n_kf + 1;
+    t.m += (size_t)M.cap_pt + 2 * (size_t)M.cap_seg; t.f += (size_t)cp[0] + 1;
   }
   if (t.m > (size_t)INT32_MAX || t.f > (size_t)INT32_MAX || t.vis > (size_t)INT32_MAX) return fail(c, PLSVO_E_CAPACITY, "candidates_stage: batch too large");
-  c->cd_staged = false; c->cd_ran = false; c->cd_matched = false; c->cs_selected = false; c->cs_posed = false;
+  c->cd_staged = false; c->cd_ran = false; c->cd_matched = false; c->cs_selected = false; c->cs_posed = false; c->ci_inserted = false; c->ci_have_out = false;
+  c->ci_cap = std::move(cap); c->ci_used = std::move(used);
+  c->ci_t_kf = t.kf; c->ci_t_kfpt = t.kfpt; c->ci_t_kfseg = t.kfseg; c->ci_t_ptobs = t.ptobs; c->ci_t_segobs = t.segobs;
   if (n == 0) { c->cd_n = 0; c->cd_staged = true; c->cd_maps.clear(); c->cd_m_off.clear(); c->cd_f_off.clear(); c->cd_params = *pr; return PLSVO_OK; }
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t N = (size_t)n;
@@ -2500,6 +2522,7 @@ extern "C" int plsvo_candidates_stage(plsvo_ctx* c, int n, const plsvo_cand_map*
   }
   int rc;
   if ((rc = upload_blob(c, c->cd_d_blob, blob))) return rc;
+  c->cd_blob_bytes = blob.host.size();
   // device work: results first (what a fetch brings back), then scratch, then the matcher's arrays and its results
   Carver cv;
   const size_t w_cnt = cv.take<int>(N * 2), w_plm = cv.take<int>(t.opt), w_ppx = cv.take<double>(t.opt * 2), w_pcell = cv.take<int>(t.opt), w_pobs = cv.take<int>(t.opt),
@@ -2575,7 +2598,7 @@ extern "C" int plsvo_candidates_run(plsvo_ctx* c, int n, const plsvo_cand_frame*
     if (!cand_idx_ok(fr[s].overlap_idx, (size_t)fr[s].n_overlap, 0, c->cd_maps[(size_t)s].n_kf)) return fail(c, PLSVO_E_INVALID, "candidates_run: overlap index outside the keyframe table");
     t_ov += (size_t)fr[s].n_overlap;
   }
-  c->cd_ran = false; c->cd_matched = false; c->cs_selected = false; c->cs_posed = false;
+  c->cd_ran = false; c->cd_matched = false; c->cs_selected = false; c->cs_posed = false; c->ci_inserted = false;
   c->cd_ov_off.assign((size_t)n + 1, 0);
   if (n == 0) { c->cd_ran = true; return PLSVO_OK; }
   HIP_TRY(c, hipSetDevice(c->device));
@@ -2644,6 +2667,7 @@ extern "C" int plsvo_candidates_fetch(plsvo_ctx* c, int n, plsvo_cand_out* out) 
 extern "C" int plsvo_candidates_match(plsvo_ctx* c) {
   CTX_CHECK(c);
   if (!c->cd_staged || !c->cd_ran) return fail(c, PLSVO_E_STATE, "candidates_match: no candidates on the device");
+  if (c->ci_inserted) return fail(c, PLSVO_E_STATE, "candidates_match: this run's frame was inserted (the tables have moved on); run again");
   if (c->cd_n == 0 || c->cd_total_m == 0) { c->cd_matched = true; return PLSVO_OK; }
   if (!c->pyr.base) return fail(c, PLSVO_E_STATE, "candidates_match: pyramids not configured");
   const plsvo_cand_params& pr = c->cd_params;
@@ -2693,7 +2717,7 @@ extern "C" int plsvo_candidates_match_fetch(plsvo_ctx* c, int n, plsvo_cand_matc
 extern "C" int plsvo_candidates_dev(plsvo_ctx* c, plsvo_cand_dev* o) {
   CTX_CHECK(c);
   if (!o) return fail(c, PLSVO_E_INVALID, "candidates_dev: bad arguments");
-  if (!c->cd_staged || !c->cd_ran || c->cd_n == 0) return fail(c, PLSVO_E_STATE, "candidates_dev: no candidates on the device");
+  if (!c->cd_staged || !c->cd_ran || c->cd_n == 0 || c->ci_inserted) return fail(c, PLSVO_E_STATE, "candidates_dev: no candidates on the device");
   const CandBatchDev& b = c->cd_b; const MatchBatchDev& mb = c->cd_match;
   o->n_entries = (int64_t)c->cd_total_m; o->n_frames = (int64_t)c->cd_total_f;
   o->m_off = c->cd_m_off.data(); o->f_off = c->cd_f_off.data();
@@ -2706,6 +2730,7 @@ extern "C" int plsvo_candidates_dev(plsvo_ctx* c, plsvo_cand_dev* o) {
 
 // ---- cell selection of the map candidates: one per cell, landmark quality, features, pose-optimiser input (select_device.hpp) ---------
 namespace {
+constexpr int kInsJoinedBit = 32;                  // insert_device.hpp's kInsJoined
 // the sections of cs_d_q, as plsvo_candidates_stage carved them
 struct QualitySections { size_t pt_nf, pt_ns, seg_nf, seg_ns, pt_ev, seg_ev, end; };
 static QualitySections quality_sections(const plsvo_ctx* c) {
@@ -2780,8 +2805,10 @@ extern "C" int plsvo_candidates_fetch_quality(plsvo_ctx* c, int n, plsvo_cand_qu
     cp(O.pt_n_failed, hq.data() + q.pt_nf, po, np, sizeof(int)); cp(O.pt_n_succeeded, hq.data() + q.pt_ns, po, np, sizeof(int));
     cp(O.seg_n_failed, hq.data() + q.seg_nf, so, ns, sizeof(int)); cp(O.seg_n_succeeded, hq.data() + q.seg_ns, so, ns, sizeof(int));
     cp(O.pt_type, ptype.data(), po, np, sizeof(int)); cp(O.seg_type, stype.data(), so, ns, sizeof(int));
-    if (O.pt_event) for (size_t k = 0; k < np; ++k) O.pt_event[k] = (uint8_t)(hq[q.pt_ev + po + k] & (PLSVO_LM_EVENT_PROMOTED | PLSVO_LM_EVENT_DELETED));
-    if (O.seg_event) for (size_t k = 0; k < ns; ++k) O.seg_event[k] = (uint8_t)(hq[q.seg_ev + so + k] & (PLSVO_LM_EVENT_PROMOTED | PLSVO_LM_EVENT_DELETED));
+    // (the insertion's bit sits above the selection's internal ones)
+    auto public_event = [](char ev) { return (uint8_t)((ev & (PLSVO_LM_EVENT_PROMOTED | PLSVO_LM_EVENT_DELETED)) | ((ev & kInsJoinedBit) ? PLSVO_LM_EVENT_JOINED : 0)); };
+    if (O.pt_event) for (size_t k = 0; k < np; ++k) O.pt_event[k] = public_event(hq[q.pt_ev + po + k]);
+    if (O.seg_event) for (size_t k = 0; k < ns; ++k) O.seg_event[k] = public_event(hq[q.seg_ev + so + k]);
     cp(O.pt_cand, ptc.data(), (size_t)M.ptc_off, (size_t)M.n_pt_cand, sizeof(int)); cp(O.seg_cand, segc.data(), (size_t)M.segc_off, (size_t)M.n_seg_cand, sizeof(int));
   }
   return PLSVO_OK;
@@ -2790,6 +2817,7 @@ extern "C" int plsvo_candidates_fetch_quality(plsvo_ctx* c, int n, plsvo_cand_qu
 extern "C" int plsvo_candidates_set_match(plsvo_ctx* c, int n, const plsvo_cand_match_out* in) {
   CTX_CHECK(c);
   if (!c->cd_staged || !c->cd_ran) return fail(c, PLSVO_E_STATE, "candidates_set_match: no candidates on the device");
+  if (c->ci_inserted) return fail(c, PLSVO_E_STATE, "candidates_set_match: this run's frame was inserted (the tables have moved on); run again");
   if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_set_match: n does not match the staged batch");
   for (int s = 0; s < n; ++s) if (!in[s].found || !in[s].px || !in[s].search_level) return fail(c, PLSVO_E_INVALID, "candidates_set_match: null array");
   if (n == 0 || c->cd_total_m == 0) { c->cd_matched = true; return PLSVO_OK; }
@@ -2904,6 +2932,7 @@ extern "C" int plsvo_candidates_select_fetch(plsvo_ctx* c, int n, plsvo_cand_sel
 extern "C" int plsvo_candidates_pose_optimize(plsvo_ctx* c) {
   CTX_CHECK(c);
   if (!c->cd_staged || !c->cs_selected) return fail(c, PLSVO_E_STATE, "candidates_pose_optimize: no selection on the device");
+  if (c->ci_inserted) return fail(c, PLSVO_E_STATE, "candidates_pose_optimize: this run's frame was inserted (the tables have moved on); run again");
   const int n = c->cd_n;
   c->cs_posed = false;
   if (n == 0) { c->cs_posed = true; return PLSVO_OK; }
@@ -2964,6 +2993,238 @@ extern "C" int plsvo_candidates_pose_fetch(plsvo_ctx* c, int n, plsvo_poseopt_ou
     if (pko && J.n_pts > 0) memcpy(pko, pk.data() + J.pt_off, (size_t)J.n_pts);
     if (sko && J.n_seg > 0) memcpy(sko, sk.data() + J.seg_off, (size_t)J.n_seg);
   }
+  return PLSVO_OK;
+}
+
+// ---- keyframe insertion into the resident map tables (insert_device.hpp) ---------------------------------------------
+extern "C" int plsvo_candidates_reserve(plsvo_ctx* c, const plsvo_cand_reserve* r) {
+  CTX_CHECK(c);
+  if (r && (r->extra_kf < 0 || r->extra_kf_pt < 0 || r->extra_kf_seg < 0 || r->extra_pt_obs < 0 || r->extra_seg_obs < 0)) return fail(c, PLSVO_E_INVALID, "candidates_reserve: negative room");
+  c->ci_reserve = r ? *r : plsvo_cand_reserve{};
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_insert_keyframe(plsvo_ctx* c, int n, const plsvo_cand_insert* in) {
+  CTX_CHECK(c);
+  if (!c->cd_staged || !c->cd_ran || !c->cs_selected) return fail(c, PLSVO_E_STATE, "candidates_insert_keyframe: no selection on the last run");
+  if (c->ci_inserted) return fail(c, PLSVO_E_STATE, "candidates_insert_keyframe: this run's frame was inserted already");
+  if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_insert_keyframe: n does not match the staged batch");
+  bool any = false, host_masks = false;
+  for (int s = 0; s < n; ++s) {
+    const plsvo_cand_insert& I = in[s];
+    if (!I.is_kf) continue;
+    any = true;
+    if (I.remove_kf < -1 || I.remove_kf >= c->cd_maps[(size_t)s].n_kf) return fail(c, PLSVO_E_INVALID, "candidates_insert_keyframe: remove_kf outside the keyframe table");
+    if (I.kf_slot < 0) return fail(c, PLSVO_E_INVALID, "candidates_insert_keyframe: negative pyramid slot");
+    if (I.pose_source < PLSVO_INSERT_POSE_HOST || I.pose_source > PLSVO_INSERT_POSE_RESIDENT || (I.pose_source == PLSVO_INSERT_POSE_DEV && !I.d_T_f_w))
+      return fail(c, PLSVO_E_INVALID, "candidates_insert_keyframe: bad pose source");
+    if (I.pt_keep || I.seg_keep) host_masks = true;
+  }
+  for (int s = 0; s < n; ++s)
+    if (in[s].is_kf && (!in[s].pt_keep || !in[s].seg_keep || in[s].pose_source == PLSVO_INSERT_POSE_RESIDENT) && !c->cs_posed)
+      return fail(c, PLSVO_E_STATE, "candidates_insert_keyframe: no resident pose optimisation for the masks or the pose");
+  for (int s = 0; s < n; ++s)                       // the keyframe count needs no launch
+    if (in[s].is_kf && c->cd_maps[(size_t)s].n_kf + 1 - (in[s].remove_kf >= 0 ? 1 : 0) > c->ci_cap[5 * (size_t)s])
+      return fail(c, PLSVO_E_CAPACITY, "candidates_insert_keyframe: no room for another keyframe (plsvo_candidates_reserve)");
+  const size_t N = (size_t)n;
+  c->ci_last.assign(N, InsertPlanDev{});
+  for (int s = 0; s < n; ++s) {
+    InsertPlanDev& O = c->ci_last[(size_t)s]; const CandMapDev& M = c->cd_maps[(size_t)s]; const int* us = c->ci_used.data() + 4 * (size_t)s;
+    O.n_kf = M.n_kf; O.new_kf = -1; O.n_kf_pt = us[0]; O.n_kf_seg = us[1]; O.n_pt_obs = us[2]; O.n_seg_obs = us[3]; O.n_pt_cand = M.n_pt_cand; O.n_seg_cand = M.n_seg_cand;
+  }
+  if (!any) { c->ci_have_out = true; return PLSVO_OK; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  // -- the records and the caller's masks, laid out like the resident masks (feature rows from opt_off / 2 * oseg_off)
+  std::vector<int> sc(N * 3);
+  if (host_masks) {
+    HIP_TRY(c, hipMemcpyAsync(sc.data(), c->cs_b.scalars, sc.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  Blob blob;
+  const size_t b_jobs = blob.reserve<InsertJobDev>(N);
+  const size_t b_pk = host_masks ? blob.reserve<uint8_t>(c->cd_t_opt) : 0, b_sk = host_masks ? blob.reserve<uint8_t>(2 * c->cd_t_oseg) : 0;
+  HIP_TRY(c, c->ci_d_in.ensure(std::max(blob.host.size(), (size_t)256)));
+  HIP_TRY(c, c->ci_d_plan.ensure(N * sizeof(InsertPlanDev)));
+  const uint8_t* din = c->ci_d_in.as<uint8_t>();
+  InsertJobDev* jobs = blob.at<InsertJobDev>(b_jobs);
+  for (int s = 0; s < n; ++s) {
+    const plsvo_cand_insert& I = in[s]; const CandMapDev& M = c->cd_maps[(size_t)s];
+    InsertJobDev& J = jobs[s];
+    memset(&J, 0, sizeof(J));
+    J.is_kf = I.is_kf ? 1 : 0; J.remove_kf = I.remove_kf; J.kf_slot = I.kf_slot;
+    if (!J.is_kf) continue;
+    memcpy(J.T, I.T_f_w, sizeof(J.T));
+    J.d_T = I.pose_source == PLSVO_INSERT_POSE_DEV ? I.d_T_f_w : I.pose_source == PLSVO_INSERT_POSE_RESIDENT ? c->cs_d_poses.as<double>() + 7 * (size_t)s : nullptr;
+    J.pt_keep = c->cs_d_ptkeep.as<uint8_t>(); J.seg_keep = c->cs_d_segkeep.as<uint8_t>();
+    if (I.pt_keep) { J.pt_keep = din + b_pk; if (sc[3 * (size_t)s] > 0) memcpy(blob.at<uint8_t>(b_pk) + M.opt_off, I.pt_keep, (size_t)sc[3 * (size_t)s]); }
+    if (I.seg_keep) { J.seg_keep = din + b_sk; if (sc[3 * (size_t)s + 1] > 0) memcpy(blob.at<uint8_t>(b_sk) + 2 * M.oseg_off, I.seg_keep, (size_t)sc[3 * (size_t)s + 1]); }
+  }
+  int rc;
+  if ((rc = upload_blob(c, c->ci_d_in, blob))) return rc;
+  // -- scratch per landmark, per candidate entry and per new feature; staging rows of the arrays that shift
+  Carver w;
+  InsertBatchDev b{};
+  size_t o_k[2][17];
+  for (int k = 0; k < 2; ++k) {
+    const size_t lm = k ? c->cd_t_seg : c->cd_t_pt, cnd = k ? c->cd_t_segc : c->cd_t_ptc, ftr = k ? 2 * c->cd_t_oseg : c->cd_t_opt;
+    const size_t kfl = k ? c->ci_t_kfseg : c->ci_t_kfpt, obs = k ? c->ci_t_segobs : c->ci_t_ptobs;
+    size_t* o = o_k[k];
+    o[0] = w.take<unsigned int>(lm); o[1] = w.take<unsigned int>(lm); o[2] = w.take<int>(lm); o[3] = w.take<int>(lm); o[4] = w.take<int>(lm);
+    o[5] = w.take<int>(cnd); o[6] = w.take<int>(ftr); o[7] = w.take<int>(c->ci_t_kf + N); o[8] = w.take<int>(kfl); o[9] = w.take<int>(lm + N);
+    o[10] = w.take<int>(obs); o[11] = w.take<int>(obs); o[12] = w.take<double>(obs * 2); o[13] = w.take<double>(obs * (k ? 2 : 3)); o[14] = w.take<double>(obs * (k ? 3 : 2));
+    o[15] = w.take<double>(k ? obs * 3 : 1); o[16] = w.take<uint8_t>(k ? 1 : obs);
+  }
+  HIP_TRY(c, c->ci_d_work.ensure(w.off + 256));
+  char* dw = reinterpret_cast<char*>(c->ci_d_work.p);
+  for (int k = 0; k < 2; ++k) {
+    InsertKindDev& K = k ? b.seg : b.pt; const size_t* o = o_k[k];
+    K.f0 = reinterpret_cast<unsigned int*>(dw + o[0]); K.f1 = reinterpret_cast<unsigned int*>(dw + o[1]);
+    K.cnt = reinterpret_cast<int*>(dw + o[2]); K.len = reinterpret_cast<int*>(dw + o[3]); K.erase = reinterpret_cast<int*>(dw + o[4]);
+    K.cand_kf = reinterpret_cast<int*>(dw + o[5]); K.new_lm = reinterpret_cast<int*>(dw + o[6]); K.kf_off2 = reinterpret_cast<int*>(dw + o[7]);
+    K.kf_lm2 = reinterpret_cast<int*>(dw + o[8]); K.obs_off2 = reinterpret_cast<int*>(dw + o[9]); K.obs_kf2 = reinterpret_cast<int*>(dw + o[10]);
+    K.obs_level2 = reinterpret_cast<int*>(dw + o[11]); K.obs_a2 = reinterpret_cast<double*>(dw + o[12]); K.obs_b2 = reinterpret_cast<double*>(dw + o[13]);
+    K.obs_c2 = reinterpret_cast<double*>(dw + o[14]); K.obs_d2 = reinterpret_cast<double*>(dw + o[15]); K.obs_type2 = reinterpret_cast<uint8_t*>(dw + o[16]);
+  }
+  b.s = c->cs_b;
+  b.jobs = reinterpret_cast<const InsertJobDev*>(din + b_jobs); b.plan = c->ci_d_plan.as<InsertPlanDev>();
+  // -- the plan: decisions and counts in scratch; capacity is decided before anything is changed
+  HIP_TRY(c, launch_map_insert_plan(b, c->stream));
+  std::vector<InsertPlanDev> plan(N);
+  HIP_TRY(c, hipMemcpyAsync(plan.data(), b.plan, N * sizeof(InsertPlanDev), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (int s = 0; s < n; ++s) {
+    if (!in[s].is_kf) continue;
+    const InsertPlanDev& P = plan[(size_t)s]; const int* cp = c->ci_cap.data() + 5 * (size_t)s;
+    if (P.n_kf > cp[0] || P.n_kf_pt > cp[1] || P.n_kf_seg > cp[2] || P.n_pt_obs > cp[3] || P.n_seg_obs > cp[4])
+      return fail(c, PLSVO_E_CAPACITY, "candidates_insert_keyframe: a stream's new sizes exceed its room (plsvo_candidates_reserve); nothing was changed");
+  }
+  {
+    EventPair ep{}; prof_begin(c, PLSVO_K_INSERT, &ep);
+    const hipError_t launched = launch_map_insert(b, c->stream);
+    prof_end(c, PLSVO_K_INSERT, &ep);                // ahead of the error return, as in plsvo_candidates_run
+    HIP_TRY(c, launched);
+  }
+  // -- the host mirrors describe the new tables
+  for (int s = 0; s < n; ++s) {
+    if (!in[s].is_kf) { c->ci_last[(size_t)s] = plan[(size_t)s]; continue; }
+    const InsertPlanDev& P = plan[(size_t)s];
+    CandMapDev& M = c->cd_maps[(size_t)s];
+    int* slot = c->cd_kf_slot.data() + M.kf_off;
+    if (in[s].remove_kf >= 0) for (int k = in[s].remove_kf; k + 1 < M.n_kf; ++k) slot[k] = slot[k + 1];
+    slot[P.new_kf] = in[s].kf_slot;
+    for (int k = P.n_kf; k < c->ci_cap[5 * (size_t)s]; ++k) slot[k] = 0;
+    M.n_kf = P.n_kf; M.n_pt_cand = P.n_pt_cand; M.n_seg_cand = P.n_seg_cand;
+    int* us = c->ci_used.data() + 4 * (size_t)s;
+    us[0] = P.n_kf_pt; us[1] = P.n_kf_seg; us[2] = P.n_pt_obs; us[3] = P.n_seg_obs;
+    c->ci_last[(size_t)s] = P;
+  }
+  c->cd_max_level = std::max(c->cd_max_level, c->cd_params.n_pyr_levels - 1);   // the new observations' levels are the matcher's search levels
+  c->ci_inserted = true; c->ci_have_out = true;
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_capacity(plsvo_ctx* c, int n, plsvo_cand_reserve* out) {
+  CTX_CHECK(c);
+  if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_capacity: no staged map tables");
+  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_capacity: n does not match the staged batch");
+  for (int s = 0; s < n; ++s) {
+    const int* cp = c->ci_cap.data() + 5 * (size_t)s;
+    out[s].extra_kf = cp[0]; out[s].extra_kf_pt = cp[1]; out[s].extra_kf_seg = cp[2]; out[s].extra_pt_obs = cp[3]; out[s].extra_seg_obs = cp[4]; out[s].reserved0 = 0;
+  }
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_insert_fetch(plsvo_ctx* c, int n, plsvo_cand_insert_out* out) {
+  CTX_CHECK(c);
+  if (!c->cd_staged || !c->ci_have_out) return fail(c, PLSVO_E_STATE, "candidates_insert_fetch: no insertion since the tables were staged");
+  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_insert_fetch: n does not match the staged batch");
+  for (int s = 0; s < n; ++s) {
+    const InsertPlanDev& P = c->ci_last[(size_t)s]; plsvo_cand_insert_out& O = out[s];
+    O.n_kf = P.n_kf; O.new_kf = P.new_kf; O.n_kf_pt = P.n_kf_pt; O.n_kf_seg = P.n_kf_seg; O.n_pt_obs = P.n_pt_obs; O.n_seg_obs = P.n_seg_obs;
+    O.n_pt_cand = P.n_pt_cand; O.n_seg_cand = P.n_seg_cand; O.n_joined_pt = P.n_joined_pt; O.n_joined_seg = P.n_joined_seg;
+    O.n_deleted_pt = P.n_deleted_pt; O.n_deleted_seg = P.n_deleted_seg;
+  }
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_fetch_map(plsvo_ctx* c, int n, plsvo_cand_map_out* out) {
+  CTX_CHECK(c);
+  if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_fetch_map: no staged map tables");
+  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_fetch_map: n does not match the staged batch");
+  if (n == 0) return PLSVO_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  std::vector<char> h(c->cd_blob_bytes);           // the tables are one allocation: one copy
+  HIP_TRY(c, hipMemcpyAsync(h.data(), c->cd_d_blob.p, h.size(), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const CandBatchDev& b = c->cd_b;
+  const char* base = reinterpret_cast<const char*>(c->cd_d_blob.p);
+  auto H = [&](const void* dev) { return h.data() + (reinterpret_cast<const char*>(dev) - base); };
+  auto cp = [&](void* dst, const void* dev, size_t at, size_t count, size_t elem) { if (dst && count) memcpy(dst, H(dev) + at * elem, count * elem); };
+  const CandMapDev* maps = reinterpret_cast<const CandMapDev*>(H(b.maps));
+  for (int s = 0; s < n; ++s) {
+    const CandMapDev& M = maps[s];
+    plsvo_cand_map_out& O = out[s];
+    const size_t nk = (size_t)M.n_kf, np = (size_t)M.n_pt, ns = (size_t)M.n_seg, S = (size_t)s;
+    const int* kpo = reinterpret_cast<const int*>(H(b.kf_pt_off)) + M.kf_off + s; const int* kso = reinterpret_cast<const int*>(H(b.kf_seg_off)) + M.kf_off + s;
+    const int* poo = reinterpret_cast<const int*>(H(b.pt_obs_off)) + M.pt_off + s; const int* soo = reinterpret_cast<const int*>(H(b.seg_obs_off)) + M.seg_off + s;
+    const size_t kfpt = (size_t)kpo[nk], kfseg = (size_t)kso[nk], ptobs = (size_t)poo[np], segobs = (size_t)soo[ns];
+    O.n_kf = M.n_kf; O.n_pt = M.n_pt; O.n_seg = M.n_seg; O.n_pt_cand = M.n_pt_cand; O.n_seg_cand = M.n_seg_cand;
+    O.n_kf_pt = (int32_t)kfpt; O.n_kf_seg = (int32_t)kfseg; O.n_pt_obs = (int32_t)ptobs; O.n_seg_obs = (int32_t)segobs; O.reserved0 = 0;
+    cp(O.kf_T, b.kf_T, (size_t)M.kf_off * 7, nk * 7, sizeof(double)); cp(O.kf_slot, b.frame_slot, (size_t)M.f_off, nk, sizeof(int));
+    cp(O.kf_pt_off, b.kf_pt_off, (size_t)M.kf_off + S, nk + 1, sizeof(int)); cp(O.kf_seg_off, b.kf_seg_off, (size_t)M.kf_off + S, nk + 1, sizeof(int));
+    cp(O.kf_pt_lm, b.kf_pt_lm, (size_t)M.kfpt_off, kfpt, sizeof(int)); cp(O.kf_seg_lm, b.kf_seg_lm, (size_t)M.kfseg_off, kfseg, sizeof(int));
+    cp(O.pt_pos, b.pt_pos, (size_t)M.pt_off * 3, np * 3, sizeof(double)); cp(O.pt_type, b.pt_type, (size_t)M.pt_off, np, sizeof(int));
+    cp(O.pt_obs_off, b.pt_obs_off, (size_t)M.pt_off + S, np + 1, sizeof(int)); cp(O.pt_obs_kf, b.pt_obs_kf, (size_t)M.ptobs_off, ptobs, sizeof(int));
+    cp(O.pt_obs_px, b.pt_obs_px, (size_t)M.ptobs_off * 2, ptobs * 2, sizeof(double)); cp(O.pt_obs_f, b.pt_obs_f, (size_t)M.ptobs_off * 3, ptobs * 3, sizeof(double));
+    cp(O.pt_obs_level, b.pt_obs_level, (size_t)M.ptobs_off, ptobs, sizeof(int)); cp(O.pt_obs_type, b.pt_obs_type, (size_t)M.ptobs_off, ptobs, 1);
+    cp(O.pt_obs_grad, b.pt_obs_grad, (size_t)M.ptobs_off * 2, ptobs * 2, sizeof(double));
+    cp(O.seg_spos, b.seg_spos, (size_t)M.seg_off * 3, ns * 3, sizeof(double)); cp(O.seg_epos, b.seg_epos, (size_t)M.seg_off * 3, ns * 3, sizeof(double));
+    cp(O.seg_type, b.seg_type, (size_t)M.seg_off, ns, sizeof(int)); cp(O.seg_obs_off, b.seg_obs_off, (size_t)M.seg_off + S, ns + 1, sizeof(int));
+    cp(O.seg_obs_kf, b.seg_obs_kf, (size_t)M.segobs_off, segobs, sizeof(int));
+    cp(O.seg_obs_spx, b.seg_obs_spx, (size_t)M.segobs_off * 2, segobs * 2, sizeof(double)); cp(O.seg_obs_epx, b.seg_obs_epx, (size_t)M.segobs_off * 2, segobs * 2, sizeof(double));
+    cp(O.seg_obs_sf, b.seg_obs_sf, (size_t)M.segobs_off * 3, segobs * 3, sizeof(double)); cp(O.seg_obs_ef, b.seg_obs_ef, (size_t)M.segobs_off * 3, segobs * 3, sizeof(double));
+    cp(O.seg_obs_level, b.seg_obs_level, (size_t)M.segobs_off, segobs, sizeof(int));
+    cp(O.pt_cand, b.pt_cand, (size_t)M.ptc_off, (size_t)M.n_pt_cand, sizeof(int)); cp(O.seg_cand, b.seg_cand, (size_t)M.segc_off, (size_t)M.n_seg_cand, sizeof(int));
+  }
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_set_positions(plsvo_ctx* c, int n, const plsvo_cand_positions* in) {
+  CTX_CHECK(c);
+  if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_set_positions: no staged map tables");
+  if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_set_positions: n does not match the staged batch");
+  size_t t_pt = 0, t_seg = 0;
+  for (int s = 0; s < n; ++s) {
+    const plsvo_cand_positions& I = in[s]; const CandMapDev& M = c->cd_maps[(size_t)s];
+    if (I.n_pt < 0 || I.n_seg < 0) return fail(c, PLSVO_E_INVALID, "candidates_set_positions: negative count");
+    if ((I.n_pt > 0 && (!I.pt_idx || !I.pt_pos)) || (I.n_seg > 0 && (!I.seg_idx || !I.seg_spos || !I.seg_epos))) return fail(c, PLSVO_E_INVALID, "candidates_set_positions: null array");
+    if (!cand_idx_ok(I.pt_idx, (size_t)I.n_pt, 0, M.n_pt) || !cand_idx_ok(I.seg_idx, (size_t)I.n_seg, 0, M.n_seg)) return fail(c, PLSVO_E_INVALID, "candidates_set_positions: landmark index out of range");
+    t_pt += (size_t)I.n_pt; t_seg += (size_t)I.n_seg;
+  }
+  if (t_pt + t_seg == 0) return PLSVO_OK;
+  if (t_pt > (size_t)INT32_MAX || t_seg > (size_t)INT32_MAX) return fail(c, PLSVO_E_CAPACITY, "candidates_set_positions: batch too large");
+  HIP_TRY(c, hipSetDevice(c->device));
+  Blob blob;
+  const size_t b_pi = blob.reserve<long long>(t_pt), b_pp = blob.reserve<double>(t_pt * 3), b_si = blob.reserve<long long>(t_seg), b_ss = blob.reserve<double>(t_seg * 3),
+               b_se = blob.reserve<double>(t_seg * 3);
+  size_t ap = 0, as = 0;
+  for (int s = 0; s < n; ++s) {
+    const plsvo_cand_positions& I = in[s]; const CandMapDev& M = c->cd_maps[(size_t)s];
+    for (int k = 0; k < I.n_pt; ++k) blob.at<long long>(b_pi)[ap + (size_t)k] = M.pt_off + I.pt_idx[k];
+    if (I.n_pt) memcpy(blob.at<double>(b_pp) + 3 * ap, I.pt_pos, (size_t)I.n_pt * 3 * sizeof(double));
+    for (int k = 0; k < I.n_seg; ++k) blob.at<long long>(b_si)[as + (size_t)k] = M.seg_off + I.seg_idx[k];
+    if (I.n_seg) { memcpy(blob.at<double>(b_ss) + 3 * as, I.seg_spos, (size_t)I.n_seg * 3 * sizeof(double)); memcpy(blob.at<double>(b_se) + 3 * as, I.seg_epos, (size_t)I.n_seg * 3 * sizeof(double)); }
+    ap += (size_t)I.n_pt; as += (size_t)I.n_seg;
+  }
+  int rc;
+  if ((rc = upload_blob(c, c->ci_d_pos, blob))) return rc;
+  const char* d = reinterpret_cast<const char*>(c->ci_d_pos.p);
+  PositionsBatchDev p{};
+  p.n_pt = (int)t_pt; p.n_seg = (int)t_seg;
+  p.pt_at = reinterpret_cast<const long long*>(d + b_pi); p.pt_src = reinterpret_cast<const double*>(d + b_pp);
+  p.seg_at = reinterpret_cast<const long long*>(d + b_si); p.seg_ssrc = reinterpret_cast<const double*>(d + b_ss); p.seg_esrc = reinterpret_cast<const double*>(d + b_se);
+  p.pt_pos = const_cast<double*>(c->cd_b.pt_pos); p.seg_spos = const_cast<double*>(c->cd_b.seg_spos); p.seg_epos = const_cast<double*>(c->cd_b.seg_epos);
+  HIP_TRY(c, launch_map_set_positions(p, c->stream));
   return PLSVO_OK;
 }
 

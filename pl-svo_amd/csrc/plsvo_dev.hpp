@@ -371,6 +371,38 @@ struct SelectBatchDev {
   double reproj_thresh; int po_n_iter, ldlt_flavour;
 };
 
+// keyframe insertion into the resident map tables (insert_device.hpp, include/plsvo_hip.h plsvo_candidates_insert_keyframe): one wave
+// per stream, two launches -- the plan decides and counts in scratch only, the commit builds the new lists in a staging copy of the
+// stream's rows and copies them back.  A stream's rows are laid out by capacity (plsvo_candidates_reserve), so they never move.
+struct InsertJobDev {               // one stream's record, about 100 bytes
+  double T[7];                      // the new keyframe's T_f_w
+  const double* d_T;                // device pointer read instead of T, or null
+  const uint8_t* pt_keep; const uint8_t* seg_keep;   // the pose optimiser's keep masks in selection order (device)
+  int is_kf, remove_kf, kf_slot, reserved0;
+};
+struct InsertPlanDev {              // what the plan finds: the stream's sizes after the insertion
+  int n_kf, new_kf, n_kf_pt, n_kf_seg, n_pt_obs, n_seg_obs, n_pt_cand, n_seg_cand, n_joined_pt, n_joined_seg, n_deleted_pt, n_deleted_seg;
+};
+struct InsertKindDev {              // one kind of landmark: scratch per landmark (pt_off / seg_off), per candidate entry, per new feature; staging
+  unsigned int* f0; unsigned int* f1;   // lowest feature index of the new frame that holds the landmark (all ones: none); highest + 1
+  int* cnt;                         // features of the removed keyframe that hold it; bit 16 up: a candidate of the removed keyframe
+  int* len; int* erase;             // the new observation list's length; observations in the removed keyframe to erase, -1 = deleted here
+  int* cand_kf;                     // per candidate entry: the keyframe its original feature joins, -1 = stays, -2 = deleted with the removed keyframe
+  int* new_lm;                      // the new frame's feature list
+  int* kf_off2; int* kf_lm2; int* obs_off2; int* obs_kf2; int* obs_level2;
+  double* obs_a2; double* obs_b2; double* obs_c2; double* obs_d2; uint8_t* obs_type2;   // points: px, f, grad; segments: spx, epx, sf, ef
+};
+struct InsertBatchDev {
+  SelectBatchDev s;
+  const InsertJobDev* jobs; InsertPlanDev* plan;
+  InsertKindDev pt, seg;
+};
+struct PositionsBatchDev {          // plsvo_candidates_set_positions: moved landmarks scattered into the resident tables (global landmark rows)
+  int n_pt, n_seg;
+  const long long* pt_at; const double* pt_src; const long long* seg_at; const double* seg_ssrc; const double* seg_esrc;
+  double* pt_pos; double* seg_spos; double* seg_epos;
+};
+
 // corner detection (detect_device.hpp, include/plsvo_hip.h plsvo_hip_detect_fast): tile geometry and the launch record
 constexpr int kDetTileW = 64, kDetTileH = 32;          // pixels of a tile that one workgroup decides
 constexpr int kDetImgX0 = 8, kDetImgY0 = 5;            // LDS image origin = tile origin - (8, 5): a halo of 5 (Shi-Tomasi: x - 5 .. x + 4), 8 keeps rows dword-aligned

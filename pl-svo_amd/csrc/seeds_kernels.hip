@@ -24,6 +24,7 @@
 #include "keyframe_device.hpp"   // the keyframe stage's kernels live in this translation unit for its -ffp-contract=off
 #include "candidates_device.hpp" // and the map candidates' kernel
 #include "select_device.hpp"     // and their cell selection
+#include "insert_device.hpp"     // and the keyframe insertion into the resident tables
 
 namespace plsvo_hip {
 
@@ -409,6 +410,22 @@ hipError_t launch_map_candidates(const CandBatchDev& b, hipStream_t stream) {
 hipError_t launch_map_select(const SelectBatchDev& b, hipStream_t stream) {
   if (b.c.n_jobs <= 0) return hipSuccess;
   hipLaunchKernelGGL(map_select_kernel, dim3((b.c.n_jobs + kSelWaves - 1) / kSelWaves), dim3(64 * kSelWaves), 0, stream, b);
+  return hipGetLastError();
+}
+// keyframe insertion (insert_device.hpp): the same shape; the plan writes scratch only, the commit changes the tables
+hipError_t launch_map_insert_plan(const InsertBatchDev& b, hipStream_t stream) {
+  if (b.s.c.n_jobs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_insert_plan_kernel, dim3((b.s.c.n_jobs + kInsWaves - 1) / kInsWaves), dim3(64 * kInsWaves), 0, stream, b);
+  return hipGetLastError();
+}
+hipError_t launch_map_set_positions(const PositionsBatchDev& b, hipStream_t stream) {
+  if (b.n_pt + b.n_seg <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_set_positions_kernel, dim3((b.n_pt + b.n_seg + 255) / 256), dim3(256), 0, stream, b);
+  return hipGetLastError();
+}
+hipError_t launch_map_insert(const InsertBatchDev& b, hipStream_t stream) {
+  if (b.s.c.n_jobs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_insert_kernel, dim3((b.s.c.n_jobs + kInsWaves - 1) / kInsWaves), dim3(64 * kInsWaves), 0, stream, b);
   return hipGetLastError();
 }
 

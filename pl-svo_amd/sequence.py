@@ -40,7 +40,10 @@ With cell_select=True on top of it (a backend with map_select) the second half o
 (plsvo_candidates_select): one candidate per grid cell in place of every found match, the landmark quality
 (n_failed_reproj_ / n_succeeded_reproj_, promotions, deletions) kept resident from frame to frame, and the pose optimiser fed on the
 device.  The harness follows the types, the candidate lists and the deletions in its own tables from fetch_quality, restages only when
-the map changes at a keyframe (or a seed converges), and carries the counters over a restage with fetch_quality / set_quality.  The
+the map changes at a keyframe (or a seed converges), and carries the counters over a restage with fetch_quality / set_quality.  With
+kf_insert=True on top of that (a backend with map_insert) a keyframe no longer restages: the frame joins the resident tables on the device
+(plsvo_candidates_insert_keyframe), the harness takes its own tables from the backend's fetch, moved landmarks go through
+map_set_positions, and only a seed that converges into a NEW candidate stages again.  The
 features reach the pose optimiser in selection order; a segment that won both of its cells is a feature twice.
 
 `backend` is duck-typed: load_frames(list of level-0 images; HipBackend also takes raw frames with rectify=), sparse_align(job), reproject(job), match_direct(job),
@@ -131,6 +134,21 @@ class HipBackend:
         sel = self.ctx.candidates_select_fetch()[0]
         pr = self.ctx.candidates_pose_fetch([(sel["n_matches"], sel["n_ls_matches"])])[0]
         return r, mr, sel, pr, self.ctx.candidates_fetch_quality()[0]
+
+    def map_reserve(self, **room):
+        """room per stream for the insertions to come (plsvo_candidates_reserve; no arguments: the tight layout again)"""
+        self.ctx.candidates_reserve(**room)
+
+    def map_insert(self, remove_kf, kf_slot):
+        """the frame of the last map_select becomes a keyframe of the resident tables (plsvo_candidates_insert_keyframe), with the pose and
+        the keep masks the resident pose optimiser left on the device; remove_kf: -1 or the row Map::safeDeleteFrame takes out.
+        -> (the tables as they now stand: capi.Context.candidates_fetch_map's record, the quality state, what the insertion did)"""
+        self.ctx.candidates_insert_keyframe([dict(remove_kf=remove_kf, kf_slot=kf_slot)])
+        return self.ctx.candidates_fetch_map()[0], self.ctx.candidates_fetch_quality()[0], self.ctx.candidates_insert_fetch()[0]
+
+    def map_set_positions(self, pt_idx, pt_pos):
+        """moved point landmarks into the resident tables (plsvo_candidates_set_positions)"""
+        self.ctx.candidates_set_positions([dict(pt_idx=pt_idx, pt_pos=pt_pos)])
 
     def detect_corners(self, slot, occupancy=None, cell_size=25, n_levels=3, detection_threshold=20.0):
         """FastDetector::detect on the frame in `slot` (plsvo_hip_detect_fast): abi.CORNER_DTYPE records in cell order"""
@@ -223,9 +241,25 @@ def candidate_map_job(cm):
         pt_cand=cm["pt_cand"], seg_cand=cm["seg_cand"])
 
 
+def candidate_map_tables(t):
+    """the inverse of candidate_map_job: the CSR arrays of plsvo_cand_map (capi.Context.candidates_fetch_map's record) as the harness's
+    lists"""
+    f3 = lambda a: [[float(x) for x in v] for v in a]
+    cut = lambda v, off: [[int(x) for x in v[off[k]:off[k + 1]]] for k in range(len(off) - 1)]
+    po, so = t["pt_obs_off"], t["seg_obs_off"]
+    pt_obs = [[dict(kf=int(t["pt_obs_kf"][o]), px=[float(x) for x in t["pt_obs_px"][o]], f=[float(x) for x in t["pt_obs_f"][o]], level=int(t["pt_obs_level"][o]),
+                    type=int(t["pt_obs_type"][o]), grad=[float(x) for x in t["pt_obs_grad"][o]]) for o in range(po[k], po[k + 1])] for k in range(len(po) - 1)]
+    seg_obs = [[dict(kf=int(t["seg_obs_kf"][o]), spx=[float(x) for x in t["seg_obs_spx"][o]], epx=[float(x) for x in t["seg_obs_epx"][o]],
+                     sf=[float(x) for x in t["seg_obs_sf"][o]], ef=[float(x) for x in t["seg_obs_ef"][o]], level=int(t["seg_obs_level"][o])) for o in range(so[k], so[k + 1])]
+               for k in range(len(so) - 1)]
+    return dict(kf_T=f3(t["kf_T"]), kf_slot=[int(v) for v in t["kf_slot"]], kf_pt=cut(t["kf_pt_lm"], t["kf_pt_off"]), kf_seg=cut(t["kf_seg_lm"], t["kf_seg_off"]),
+                pt_pos=f3(t["pt_pos"]), pt_type=[int(v) for v in t["pt_type"]], pt_obs=pt_obs, seg_spos=f3(t["seg_spos"]), seg_epos=f3(t["seg_epos"]),
+                seg_type=[int(v) for v in t["seg_type"]], seg_obs=seg_obs, pt_cand=[int(v) for v in t["pt_cand"]], seg_cand=[int(v) for v in t["seg_cand"]])
+
+
 def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_thresh=2.0, mapping=False, known_frac=0.6,
                  pos_noise=0.005, map_seed=0, kf_every=5, detect=False, detect_cell_size=25, kf_select=False, kfselect_mindist_t=0.06,
-                 kfselect_mindist_r=3.0, max_n_kfs=10, map_candidates=False, record_candidates=False, cell_select=False, select_params=None):
+                 kfselect_mindist_r=3.0, max_n_kfs=10, map_candidates=False, record_candidates=False, cell_select=False, select_params=None, kf_insert=False):
     """-> list of per-frame dicts (pose T_f_w, cov, counts).  Frame 0 is the keyframe with the true pose.
     mapping=True: only `known_frac` of the point landmarks start in the map (positions off by `pos_noise` x depth along
     their viewing ray), the others are depth-filter seeds; the seed update runs every frame; every `kf_every`-th frame
@@ -244,7 +278,31 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
     cell_select=True (with map_candidates, a backend with map_select): the cell selection and the resident pose optimiser take the place
     of "every found match" and the per-call pose optimiser (module docstring); select_params: keyword arguments of
     capi.Context.candidates_select (default: max_fts 120, max_fts_segs 100, cells in index order).  The records gain n_trials and
-    n_promoted / n_deleted; rec["candidates"] gains the selection and the quality state before and after the frame."""
+    n_promoted / n_deleted; rec["candidates"] gains the selection and the quality state before and after the frame.
+    kf_insert=True (with cell_select, a backend with map_insert): a keyframe is inserted into the resident tables on the device
+    (plsvo_candidates_insert_keyframe) with the resident pose and keep masks; when the table holds max_n_kfs keyframes the
+    one keyframe_decide names as the furthest is removed in the same call (kf_select; the first row when it names none).  The harness
+    brings its own tables up to date from the backend's fetch, sends structure-optimised positions with map_set_positions, and stages
+    only at the start and when a seed converges into a NEW candidate -- observed in frame 0's keyframe, whose row the harness follows through
+    the removals; a seed that converges after that keyframe was removed stays outside the map's tables (n_seed_candidates counts the
+    others).  The keyframe records gain n_joined / n_deleted_kf / remove_kf, and
+    with record_candidates rec["insert"]: the tables and the quality before, the selection, the masks, the pose, and all three after."""
+    params = dict(locals())                            # (first statement: exactly the arguments)
+    if kf_insert and not (cell_select and mapping and hasattr(backend, "map_insert")):
+        raise ValueError("kf_insert needs mapping, cell_select and a backend with map_insert()")
+    if not kf_insert:
+        return _run_sequence(**params)
+    # room for every keyframe the sequence can add (a joined candidate adds a feature, every feature an observation)
+    n_fr, n_lm = len(seq["images"]), len(seq["pt_pos"]) + 2 * len(seq["seg_spos"])
+    backend.map_reserve(extra_kf=n_fr, extra_kf_pt=n_fr * n_lm, extra_kf_seg=n_fr * n_lm, extra_pt_obs=n_fr * n_lm, extra_seg_obs=n_fr * n_lm)
+    try:
+        return _run_sequence(**params)
+    finally:
+        backend.map_reserve()                          # the tight layout again for whoever stages next on this backend
+
+
+def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thresh, mapping, known_frac, pos_noise, map_seed, kf_every, detect, detect_cell_size, kf_select,
+                  kfselect_mindist_t, kfselect_mindist_r, max_n_kfs, map_candidates, record_candidates, cell_select, select_params, kf_insert):
     cam = seq["cam"]
     if cell_select and not (map_candidates and hasattr(backend, "map_select")):
         raise ValueError("cell_select needs map_candidates and a backend with map_select()")
@@ -317,6 +375,7 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
                   seg_obs=[[dict(kf=0, spx=f3(seq["seg_spx0"][i]), epx=f3(seq["seg_epx0"][i]), sf=f3(seq["seg_sf0"][i]), ef=f3(seq["seg_ef0"][i]), level=0)]
                            for i in range(n_seg)], pt_cand=[], seg_cand=[])
         cm_dirty = True
+        seed_kf = 0                                    # the row of frame 0, where every seed was started (None once kf_insert removed it)
         quality = None                                 # cell_select: the quality state after the last frame (None: nothing staged yet)
         select_kw = dict(max_fts=120, max_fts_segs=100, cell_order=None, seg_cell_order=None, reproj_thresh=reproj_thresh)
         select_kw.update(select_params or {})
@@ -472,7 +531,23 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
             if is_kf:
                 for i, brg in zip(kept, _bearing(cam, px_new[kept])):
                     obs[int(i)].append((k, brg))
-                if map_candidates:
+                if kf_insert:
+                    # the frame joins the RESIDENT tables on the device; the harness's own follow the backend's fetch
+                    remove = -1
+                    if kf_select and len(cm["kf_T"]) >= max_n_kfs:
+                        remove = max(int(dec["furthest_kf"]), 0)
+                        for key in kfs:
+                            del kfs[key][remove]
+                        if seed_kf is not None:                       # the table closes up: frame 0's row moves, or is gone
+                            seed_kf = None if remove == seed_kf else seed_kf - (remove < seed_kf)
+                    before = (copy.deepcopy(cm), quality) if record_candidates else None
+                    tables, quality, ins = backend.map_insert(remove, k)
+                    cm = candidate_map_tables(tables)
+                    rec.update(n_joined=ins["n_joined_pt"] + ins["n_joined_seg"], n_deleted_kf=ins["n_deleted_pt"] + ins["n_deleted_seg"], remove_kf=remove)
+                    if record_candidates:
+                        rec["insert"] = dict(stream=before[0], quality_before=before[1], select=sel, pt_keep=pr.pt_keep.copy(), seg_keep=pr.seg_keep.copy(), T=[float(v) for v in T_k],
+                                             slot=k, remove_kf=remove, tables=tables, quality=quality, report=ins)
+                elif map_candidates:
                     # the frame joins the keyframe table: its features, and an observation at the FRONT of every landmark's list
                     # (Feature3D::addFrameRef pushes at the front, include/plsvo/feature3D.h:204); a candidate it matched leaves the
                     # map's candidate list for the keyframe's features
@@ -504,7 +579,11 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
                 so = backend.structure_optimize(abi.StructOptJob(np.stack(poses_est), P3[sel], off, ofr, np.array(of_), z3, z3, np.zeros(1, np.int32), zi, z3, z3, 5, 5))
                 P3[sel] = so["pt_pos"]
                 last_optim[sel] = k
-                if map_candidates:
+                if kf_insert:
+                    backend.map_set_positions(sel.astype(np.int32), P3[sel])
+                    for i in sel:
+                        cm["pt_pos"][int(i)] = [float(x) for x in P3[i]]
+                elif map_candidates:
                     cm_dirty = True
             # ---- 6. depth-filter update of the seeds with this frame (DepthFilter::updateSeeds) ----
             ns = len(seeds["idx"])
@@ -517,10 +596,12 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
                 conv = stt == abi.SEED_CONVERGED
                 P3[si_[conv]] = sr["pt_xyz_world"][conv]
                 known[si_[conv]] = True
-                if map_candidates and conv.any():
+                if map_candidates and conv.any() and seed_kf is not None:
                     # a converged seed becomes a candidate of the map (map_.point_candidates_), observed in the keyframe it was started in
+                    # (frame 0; once that keyframe has left the table the seed's only observation is gone with it, as
+                    # removeFrameCandidates would delete it: the landmark stays outside the map's tables)
                     for i in si_[conv]:
-                        cm["pt_obs"][int(i)] = [dict(kf=0, px=[float(x) for x in seq["pt_px0"][i]], f=[float(x) for x in seq["pt_f0"][i]], level=0,
+                        cm["pt_obs"][int(i)] = [dict(kf=seed_kf, px=[float(x) for x in seq["pt_px0"][i]], f=[float(x) for x in seq["pt_f0"][i]], level=0,
                                                      type=abi.FTR_CORNER, grad=[0.0, 0.0])]
                         cm["pt_type"][int(i)] = abi.LM_CANDIDATE
                         cm["pt_cand"].append(int(i))
@@ -529,6 +610,8 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
                 seeds = dict(idx=si_[keep_s], a=sr["pt_a"][keep_s], b=sr["pt_b"][keep_s], mu=sr["pt_mu"][keep_s], z_range=seeds["z_range"][keep_s],
                              sigma2=sr["pt_sigma2"][keep_s])
                 rec["n_seed_converged"] = int(conv.sum())
+                if kf_insert:
+                    rec["n_seed_candidates"] = int(conv.sum()) if seed_kf is not None else 0
             if detect:
                 # ---- 7. the seeds that came from the image: updated with this frame; a keyframe adds those of its own free cells ----
                 ni = len(img_seeds["px"])

@@ -803,7 +803,8 @@ typedef struct plsvo_cand_frame {
  * is what plsvo_reproject accepts (both end points for a segment); the map's candidates follow in list order without the
  * first-visit test.  Filed landmarks come out in stable descending order of type_, within a type in filing order.
  * Caller buffers, any may be NULL; capacity n_pt + n_pt_cand points, n_seg + n_seg_cand segments, of which the first n_filed_*
- * are written. */
+ * are written (with a landmark reserve -- plsvo_candidates_reserve_landmarks -- the counts of CAPACITY: landmark rows as
+ * plsvo_candidates_lm_capacity reports them plus the staged candidate count plus the same room). */
 typedef struct plsvo_cand_out {
   int32_t n_filed_pt, n_filed_seg;
   int32_t* pt_lm;                   /* landmark index */
@@ -900,7 +901,8 @@ typedef struct plsvo_cand_quality_in {
 
 /* The quality state of one stream as it now stands.  Caller buffers, any may be NULL: n_pt / n_seg entries, the candidate lists
  * n_pt_cand / n_seg_cand of the STAGED counts, of which the first n_pt_cand / n_seg_cand reported here are written (an erased
- * candidate closes the list up).  *_event: PLSVO_LM_EVENT_* of the last plsvo_candidates_select, 0 before the first; a keyframe
+ * candidate closes the list up).  With a landmark reserve size them from plsvo_candidates_lm_capacity: plsvo_candidates_add
+ * lengthens the landmark arrays and the lists.  *_event: PLSVO_LM_EVENT_* of the last plsvo_candidates_select, 0 before the first; a keyframe
  * insertion behind that selection ORs its own bits in (PLSVO_LM_EVENT_JOINED, PLSVO_LM_EVENT_DELETED). */
 typedef struct plsvo_cand_quality_out {
   int32_t n_pt_cand, n_seg_cand;
@@ -1021,7 +1023,8 @@ typedef struct plsvo_cand_insert_out {
 
 /* The resident tables of one stream as they now stand, in plsvo_cand_map's layout.  Caller buffers, any may be NULL, of the stream's
  * CAPACITY as plsvo_candidates_capacity reports it (staged sizes plus the reserve in force at stage time; kf_T / kf_slot one row per
- * keyframe of capacity, offsets one more than their lists; landmark arrays n_pt / n_seg, candidate lists their staged counts); the
+ * keyframe of capacity, offsets one more than their lists; landmark arrays n_pt / n_seg, candidate lists their staged counts -- with a
+ * landmark reserve the rows plsvo_candidates_lm_capacity reports, the lists their staged counts plus the same room); the
  * counts are reported.  The library cannot see the buffers' sizes: smaller ones are overrun. */
 typedef struct plsvo_cand_map_out {
   int32_t n_kf, n_pt, n_seg, n_pt_cand, n_seg_cand;
@@ -1071,6 +1074,85 @@ int plsvo_candidates_capacity(plsvo_ctx* ctx, int n, plsvo_cand_reserve* out);
 int plsvo_candidates_insert_fetch(plsvo_ctx* ctx, int n, plsvo_cand_insert_out* out);
 int plsvo_candidates_fetch_map(plsvo_ctx* ctx, int n, plsvo_cand_map_out* out);
 int plsvo_candidates_set_positions(plsvo_ctx* ctx, int n, const plsvo_cand_positions* in);
+
+/* ------------------------------------------------------------------------------------------ */
+/* new map candidates: a depth-filter seed that converged becomes a landmark of the resident    */
+/* tables, in place (one wave per stream).  It replaces what                    */
+/* DepthFilter::updatePointSeeds / updateLineSeeds do with a converged seed                     */
+/* (src/depth_filter.cpp:334-355, :439-462): `new Point(xyz_world, ftr)` /                      */
+/* `new LineSeg(xyz_world_s, xyz_world_e, ftr)`, whose constructors (src/point.cpp:41-55,       */
+/* :198-212) push the seed's feature as the landmark's ONE observation and set both             */
+/* reprojection counters to 0, and the callbacks MapPointCandidates::newCandidatePoint /        */
+/* MapSegmentCandidates::newCandidateSegment (src/map.cpp:285-290, :377-382, bound at           */
+/* src/frame_handler_mono.cpp:88-95): type_ = TYPE_CANDIDATE and a push_back onto the map's     */
+/* candidate list.  The seed's feature is not in its keyframe's feature list until the          */
+/* candidate joins (addCandidatePointToFrame) -- what the resident tables assume of a candidate. */
+/* Within a kind, input order = landmark index order = candidate-list order; points and         */
+/* segments are separate landmark spaces.  The callbacks' depth_sigma2 arguments are unused by  */
+/* the reference and are not part of this interface.  The landmark's position is an INPUT: the  */
+/* pt_xyz_world / seg_xyz_world_s / _e plsvo_update_seeds reports, passed through unchanged.    */
+/* Landmark rows are never reclaimed: a landmark deleted later keeps its row, and a restage     */
+/* (plsvo_candidates_stage) is the only compaction.                                             */
+/* ------------------------------------------------------------------------------------------ */
+
+#define PLSVO_LM_EVENT_NEW      8   /* a landmark appended by plsvo_candidates_add since the last selection */
+
+/* Landmark rows per stream beyond what is staged, added by the NEXT and every later plsvo_candidates_stage: with room here a stream's
+ * landmark rows and every per-landmark array, its candidate lists (staged count + extra), its filed / matcher rows
+ * ((n_pt + extra_pt) + (n_pt_cand + extra_pt), likewise for segments) and its first-visit rows are laid out by capacity.  Each new
+ * landmark also needs one observation entry: plsvo_cand_reserve's extra_pt_obs / extra_seg_obs; the two reserves combine.  NULL or
+ * all zeros: every result, offset and byte is what it is without this call. */
+typedef struct plsvo_cand_lm_reserve {
+  int32_t extra_pt, extra_seg;
+} plsvo_cand_lm_reserve;
+
+/* One stream's new candidate landmarks: about 100 bytes per point and 200 per segment travel. */
+typedef struct plsvo_cand_new {
+  int32_t n_pt, n_seg;
+  const double* pt_pos;             /* 3: Point::pos_ */
+  const int32_t* pt_obs_kf;         /* the keyframe (table index as it stands now) of the seed's feature */
+  const double* pt_obs_px;          /* 2 */
+  const double* pt_obs_f;           /* 3 */
+  const int32_t* pt_obs_level;
+  const uint8_t* pt_obs_type;       /* PLSVO_FTR_* */
+  const double* pt_obs_grad;        /* 2; may be NULL without edgelets (zeros are stored) */
+  const double* seg_spos;           /* 3: LineSeg::spos_ */
+  const double* seg_epos;           /* 3 */
+  const int32_t* seg_obs_kf;
+  const double* seg_obs_spx;        /* 2 */
+  const double* seg_obs_epx;        /* 2 */
+  const double* seg_obs_sf;         /* 3 */
+  const double* seg_obs_ef;         /* 3 */
+  const int32_t* seg_obs_level;
+} plsvo_cand_new;
+
+/* What the last plsvo_candidates_add did to one stream, and its sizes as they stand. */
+typedef struct plsvo_cand_add_out {
+  int32_t first_pt, first_seg;      /* index of the first new landmark per kind, -1 for none */
+  int32_t n_added_pt, n_added_seg;
+  int32_t n_pt, n_seg, n_pt_cand, n_seg_cand, n_pt_obs, n_seg_obs;
+} plsvo_cand_add_out;
+
+/* reserve_landmarks: host only; PLSVO_E_INVALID for a negative field.
+ * lm_capacity: per stream the landmark rows its layout was made with at stage time (staged counts plus the reserve in force THEN), in
+ * the fields of plsvo_cand_lm_reserve; its candidate lists hold the staged count plus the same room.  These are the sizes the
+ * per-landmark buffers of plsvo_candidates_fetch_map, _fetch_quality and _set_quality need (set_quality reads, fetch_quality writes the
+ * landmarks as they stand now).  PLSVO_E_STATE before a stage.
+ * add: enqueue-only after the copy of the records.  Every check runs on the host before anything is written to any stream's tables:
+ * PLSVO_E_INVALID for another n than staged, NULL in with n > 0, a negative count, a NULL array with a non-zero count (pt_obs_grad
+ * excepted), an observation keyframe outside [0, n_kf) of the stream's table as it stands now, a level outside
+ * [0, PLSVO_MAX_LEVELS), an unknown feature type, an edgelet without pt_obs_grad; PLSVO_E_CAPACITY when any stream lacks landmark rows
+ * or observation entries of either kind (capacity is decided from the host's mirrors: no planning launch, no read-back);
+ * PLSVO_E_STATE before a stage.  The new event bytes are PLSVO_LM_EVENT_NEW until the next selection clears them.
+ * An add ends the open run as an insertion does: plsvo_candidates_match / _set_match / _select / _pose_optimize / _dev and
+ * plsvo_candidates_insert_keyframe return PLSVO_E_STATE until the next plsvo_candidates_run; the run's fetches keep returning its
+ * results (they index landmarks below the old counts, which have not moved).  An add after an insertion on the same run and several
+ * adds in a row are legal.
+ * add_fetch: synchronises; PLSVO_E_STATE before the first add since the tables were staged. */
+int plsvo_candidates_reserve_landmarks(plsvo_ctx* ctx, const plsvo_cand_lm_reserve* reserve);
+int plsvo_candidates_lm_capacity(plsvo_ctx* ctx, int n, plsvo_cand_lm_reserve* out);
+int plsvo_candidates_add(plsvo_ctx* ctx, int n, const plsvo_cand_new* in);
+int plsvo_candidates_add_fetch(plsvo_ctx* ctx, int n, plsvo_cand_add_out* out);
 
 /* TUM-style trajectory record of a frame (app/run_pipeline.cpp:425-451): the camera pose in the world,
  * T_f_w^-1, as tx ty tz qx qy qz qw.  Returns 1 and fills out7 when the reference would write the line, 0 when
@@ -1202,7 +1284,8 @@ int plsvo_gather_poses(plsvo_ctx* ctx, void* rccl_comm, const plsvo_pose_record*
 #define PLSVO_K_CANDIDATES    8   /* plsvo_candidates_run: the re-arm and the launch alone (the resident match counts under PLSVO_K_MATCH) */
 #define PLSVO_K_SELECT        9   /* plsvo_candidates_select: the re-arm and the launch alone */
 #define PLSVO_K_INSERT        10  /* plsvo_candidates_insert_keyframe: the launch that changes the tables (the planning launch is timed by the caller's clock) */
-#define PLSVO_K_COUNT         11
+#define PLSVO_K_NEWCAND       11  /* plsvo_candidates_add: the launch alone */
+#define PLSVO_K_COUNT         12
 int plsvo_hip_set_profiling(plsvo_ctx* ctx, int enable);
 /* accumulated GPU time and launch count of kernel family k since the last reset (synchronises) */
 int plsvo_hip_kernel_time(plsvo_ctx* ctx, int k, double* total_ms, int64_t* launches);

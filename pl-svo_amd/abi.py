@@ -18,7 +18,7 @@ c_i32_p = C.POINTER(C.c_int32)
 OK, E_INVALID, E_NODEVICE, E_HIP, E_CAPACITY, E_STATE, E_RCCL = 0, -1, -2, -3, -4, -5, -6
 
 # kernel families for plsvo_hip_kernel_time
-K_ALIGN_INIT, K_ALIGN_LEVEL, K_POSEOPT, K_HALFSAMPLE, K_STRUCTOPT, K_MATCH, K_SEEDS, K_KEYFRAME, K_CANDIDATES, K_SELECT, K_INSERT, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
+K_ALIGN_INIT, K_ALIGN_LEVEL, K_POSEOPT, K_HALFSAMPLE, K_STRUCTOPT, K_MATCH, K_SEEDS, K_KEYFRAME, K_CANDIDATES, K_SELECT, K_INSERT, K_NEWCAND, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12
 SEED_NOT_VISIBLE, SEED_NO_MATCH, SEED_UPDATED, SEED_CONVERGED, SEED_NAN = 0, 1, 2, 3, 4
 FTR_CORNER, FTR_EDGELET = 0, 1
 LM_DELETED, LM_CANDIDATE, LM_UNKNOWN, LM_GOOD = 0, 1, 2, 3
@@ -281,6 +281,39 @@ class CandPositions(C.Structure):
     """plsvo_cand_positions"""
     _fields_ = [("n_pt", C.c_int32), ("n_seg", C.c_int32), ("pt_idx", c_i32_p), ("pt_pos", c_double_p), ("seg_idx", c_i32_p), ("seg_spos", c_double_p),
                 ("seg_epos", c_double_p)]
+
+
+LM_EVENT_NEW = 8
+
+
+class CandLmReserve(C.Structure):
+    """plsvo_cand_lm_reserve"""
+    _fields_ = [("extra_pt", C.c_int32), ("extra_seg", C.c_int32)]
+
+
+_CAND_NEW_I32 = ("pt_obs_kf", "pt_obs_level", "seg_obs_kf", "seg_obs_level")
+_CAND_NEW_U8 = ("pt_obs_type",)
+_CAND_NEW_ORDER = ("pt_pos", "pt_obs_kf", "pt_obs_px", "pt_obs_f", "pt_obs_level", "pt_obs_type", "pt_obs_grad", "seg_spos", "seg_epos", "seg_obs_kf", "seg_obs_spx",
+                   "seg_obs_epx", "seg_obs_sf", "seg_obs_ef", "seg_obs_level")
+_CAND_NEW_WIDTH = dict(pt_pos=3, pt_obs_px=2, pt_obs_f=3, pt_obs_grad=2, seg_spos=3, seg_epos=3, seg_obs_spx=2, seg_obs_epx=2, seg_obs_sf=3, seg_obs_ef=3)
+
+
+class CandNew(C.Structure):
+    """plsvo_cand_new"""
+    _fields_ = [("n_pt", C.c_int32), ("n_seg", C.c_int32)] + \
+               [(f, c_i32_p if f in _CAND_NEW_I32 else c_u8_p if f in _CAND_NEW_U8 else c_double_p) for f in _CAND_NEW_ORDER]
+
+
+class CandNewBatch:
+    """The records of one plsvo_candidates_add call as ctypes (capi.Context.candidates_add_records); owns the buffers."""
+
+    def __init__(self, n, arr, keep, counts):
+        self.n, self.arr, self.keep, self.counts = n, arr, keep, counts
+
+
+class CandAddOut(C.Structure):
+    """plsvo_cand_add_out"""
+    _fields_ = [(f, C.c_int32) for f in ("first_pt", "first_seg", "n_added_pt", "n_added_seg", "n_pt", "n_seg", "n_pt_cand", "n_seg_cand", "n_pt_obs", "n_seg_obs")]
 
 
 class CandDev(C.Structure):

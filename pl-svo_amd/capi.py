@@ -31,6 +31,7 @@ SYMBOLS = [
     "plsvo_candidates_set_quality", "plsvo_candidates_fetch_quality", "plsvo_candidates_select", "plsvo_candidates_select_fetch", "plsvo_candidates_pose_optimize",
     "plsvo_candidates_pose_fetch", "plsvo_candidates_poses_dev", "plsvo_candidates_set_match",
     "plsvo_candidates_reserve", "plsvo_candidates_capacity", "plsvo_candidates_insert_keyframe", "plsvo_candidates_insert_fetch", "plsvo_candidates_fetch_map", "plsvo_candidates_set_positions",
+    "plsvo_candidates_reserve_landmarks", "plsvo_candidates_lm_capacity", "plsvo_candidates_add", "plsvo_candidates_add_fetch",
     "plsvo_chain_stage", "plsvo_chain_run", "plsvo_chain_fetch", "plsvo_frame_step_batch", "plsvo_chain_poses_dev",
     "plsvo_pack_pose_records", "plsvo_fetch_pose_records", "plsvo_gather_poses",
     "plsvo_hip_set_profiling", "plsvo_hip_kernel_time", "plsvo_hip_reset_profiling",
@@ -165,6 +166,10 @@ def lib():
         "plsvo_candidates_insert_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandInsertOut)]),
         "plsvo_candidates_fetch_map": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandMapOut)]),
         "plsvo_candidates_set_positions": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandPositions)]),
+        "plsvo_candidates_reserve_landmarks": (C.c_int, [ctxp, C.POINTER(abi.CandLmReserve)]),
+        "plsvo_candidates_lm_capacity": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandLmReserve)]),
+        "plsvo_candidates_add": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandNew)]),
+        "plsvo_candidates_add_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandAddOut)]),
         "plsvo_update_seeds": (C.c_int, [ctxp, C.POINTER(abi.SeedsIn), C.POINTER(abi.SeedsOut)]),
         "plsvo_trajectory_record": (C.c_int, [abi.c_double_p, abi.c_double_p, abi.c_double_p]),
         "plsvo_chain_stage": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.ChainIn), C.POINTER(abi.ChainParams)]),
@@ -619,6 +624,13 @@ class Context:
         pr.cell_size, pr.seg_cell_size, pr.boundary, pr.n_pyr_levels, pr.align_max_iter = cell_size, seg_cell_size, boundary, n_pyr_levels, align_max_iter
         self._chk(self.L.plsvo_candidates_stage(self.h, n, arr, C.byref(pr)))
         self._cand_maps = list(maps)
+        # the rows the library laid every stream out with (buffers are sized from these), and the counts as they stand: an add moves them
+        lm = self.candidates_lm_capacity()
+        self._cand_cap = [dict(pt=c["pt"], seg=c["seg"], pt_cand=m.n_pt_cand + c["pt"] - m.n_pt, seg_cand=m.n_seg_cand + c["seg"] - m.n_seg) for c, m in zip(lm, maps)]
+        for c in self._cand_cap:
+            c.update(filed_pt=c["pt"] + c["pt_cand"], filed_seg=c["seg"] + c["seg_cand"])
+        self._cand_now = [dict(pt=m.n_pt, seg=m.n_seg, pt_cand=m.n_pt_cand, seg_cand=m.n_seg_cand) for m in maps]
+        self._cand_at_run = [dict(c) for c in self._cand_now]
 
     def candidates_run(self, frames, poses_dev=None):
         """plsvo_candidates_run (enqueue only): one abi.CandidateFrameJob per staged stream.  poses_dev: a device pointer to
@@ -630,6 +642,7 @@ class Context:
                 arr[i].d_T_f_w = int(poses_dev[i]) if isinstance(poses_dev, (list, tuple)) else int(poses_dev) + 56 * i
         self._chk(self.L.plsvo_candidates_run(self.h, n, arr))
         self._cand_frames = list(frames)
+        self._cand_at_run = [dict(c) for c in self._cand_now]
 
     def candidates_fetch(self):
         """plsvo_candidates_fetch: per stream a dict of n_filed_pt / n_filed_seg, the filed points (pt_lm, pt_px [n, 2], pt_cell, pt_obs,
@@ -639,29 +652,29 @@ class Context:
         n = len(maps)
         outs = (abi.CandOut * max(n, 1))()
         bufs = []
-        for o, m, f in zip(outs, maps, frames):
-            cp, cs = max(m.cap_pt, 1), max(m.cap_seg, 1)
+        for o, m, f, cap in zip(outs, maps, frames, self._cand_cap):
+            cp, cs = max(cap["filed_pt"], 1), max(cap["filed_seg"], 1)
             b = dict(pt_lm=np.full(cp, -9, np.int32), pt_px=np.zeros((cp, 2)), pt_cell=np.full(cp, -9, np.int32), pt_obs=np.full(cp, -9, np.int32),
                      pt_has_view=np.full(cp, 9, np.uint8), pt_active=np.full(cp, 9, np.uint8),
                      seg_lm=np.full(cs, -9, np.int32), seg_px=np.zeros((cs, 4)), seg_cell=np.full((cs, 2), -9, np.int32), seg_obs=np.full(cs, -9, np.int32),
                      seg_has_view=np.full(cs, 9, np.uint8), seg_active=np.full(cs, 9, np.uint8),
-                     kf_count=np.full(max(f.n_overlap, 1), -9, np.int32), pt_cand_failed=np.full(max(m.n_pt_cand, 1), 9, np.uint8),
-                     seg_cand_failed=np.full(max(m.n_seg_cand, 1), 9, np.uint8))
+                     kf_count=np.full(max(f.n_overlap, 1), -9, np.int32), pt_cand_failed=np.full(max(cap["pt_cand"], 1), 9, np.uint8),
+                     seg_cand_failed=np.full(max(cap["seg_cand"], 1), 9, np.uint8))
             for k, v in b.items():
                 setattr(o, k, v.ctypes.data_as(abi.c_double_p if v.dtype == np.float64 else abi.c_u8_p if v.dtype == np.uint8 else abi.c_i32_p))
             bufs.append(b)
         self._chk(self.L.plsvo_candidates_fetch(self.h, n, outs))
         res = []
-        for o, m, f, b in zip(outs[:n], maps, frames, bufs):
+        for o, m, f, b in zip(outs[:n], self._cand_at_run, frames, bufs):   # (the candidate lists as long as the run can have seen them)
             r = dict(n_filed_pt=int(o.n_filed_pt), n_filed_seg=int(o.n_filed_seg))
             for k, v in b.items():
                 cut = o.n_filed_pt if k.startswith("pt_") else o.n_filed_seg
                 if k == "kf_count":
                     cut = f.n_overlap
                 elif k == "pt_cand_failed":
-                    cut = m.n_pt_cand
+                    cut = m["pt_cand"]
                 elif k == "seg_cand_failed":
-                    cut = m.n_seg_cand
+                    cut = m["seg_cand"]
                 r[k] = v[:cut].copy()
             res.append(r)
         return res
@@ -677,8 +690,8 @@ class Context:
         n = len(maps)
         outs = (abi.CandMatchOut * max(n, 1))()
         bufs = []
-        for o, m in zip(outs, maps):
-            cap = max(m.cap_pt + 2 * m.cap_seg, 1)
+        for o, m in zip(outs, self._cand_cap):
+            cap = max(m["filed_pt"] + 2 * m["filed_seg"], 1)
             b = dict(found=np.full(cap, 9, np.uint8), px=np.zeros((cap, 2)), search_level=np.full(cap, -9, np.int32))
             o.found, o.px, o.search_level = b["found"].ctypes.data_as(abi.c_u8_p), b["px"].ctypes.data_as(abi.c_double_p), b["search_level"].ctypes.data_as(abi.c_i32_p)
             bufs.append(b)
@@ -717,18 +730,19 @@ class Context:
         n = len(maps)
         outs = (abi.CandQualityOut * max(n, 1))()
         bufs = []
-        for o, m in zip(outs, maps):
-            b = dict(pt_n_failed=np.full(max(m.n_pt, 1), -9, np.int32), pt_n_succeeded=np.full(max(m.n_pt, 1), -9, np.int32), pt_type=np.full(max(m.n_pt, 1), -9, np.int32),
-                     pt_event=np.full(max(m.n_pt, 1), 9, np.uint8), seg_n_failed=np.full(max(m.n_seg, 1), -9, np.int32), seg_n_succeeded=np.full(max(m.n_seg, 1), -9, np.int32),
-                     seg_type=np.full(max(m.n_seg, 1), -9, np.int32), seg_event=np.full(max(m.n_seg, 1), 9, np.uint8),
-                     pt_cand=np.full(max(m.n_pt_cand, 1), -9, np.int32), seg_cand=np.full(max(m.n_seg_cand, 1), -9, np.int32))
+        for o, m in zip(outs, self._cand_cap):
+            npt, nsg = max(m["pt"], 1), max(m["seg"], 1)
+            b = dict(pt_n_failed=np.full(npt, -9, np.int32), pt_n_succeeded=np.full(npt, -9, np.int32), pt_type=np.full(npt, -9, np.int32),
+                     pt_event=np.full(npt, 9, np.uint8), seg_n_failed=np.full(nsg, -9, np.int32), seg_n_succeeded=np.full(nsg, -9, np.int32),
+                     seg_type=np.full(nsg, -9, np.int32), seg_event=np.full(nsg, 9, np.uint8),
+                     pt_cand=np.full(max(m["pt_cand"], 1), -9, np.int32), seg_cand=np.full(max(m["seg_cand"], 1), -9, np.int32))
             for k, v in b.items():
                 setattr(o, k, self._ptr(v))
             bufs.append(b)
         self._chk(self.L.plsvo_candidates_fetch_quality(self.h, n, outs))
         res = []
-        for o, m, b in zip(outs[:n], maps, bufs):
-            cut = lambda k: o.n_pt_cand if k == "pt_cand" else o.n_seg_cand if k == "seg_cand" else m.n_pt if k.startswith("pt_") else m.n_seg
+        for o, m, b in zip(outs[:n], self._cand_now, bufs):
+            cut = lambda k: o.n_pt_cand if k == "pt_cand" else o.n_seg_cand if k == "seg_cand" else m["pt"] if k.startswith("pt_") else m["seg"]
             res.append({k: v[:cut(k)].copy() for k, v in b.items()})
         return res
 
@@ -763,8 +777,8 @@ class Context:
         n = len(maps)
         outs = (abi.CandSelectOut * max(n, 1))()
         bufs = []
-        for o, m in zip(outs, maps):
-            cp, cs = max(m.cap_pt, 1), max(2 * m.cap_seg, 1)
+        for o, m in zip(outs, self._cand_cap):
+            cp, cs = max(m["filed_pt"], 1), max(2 * m["filed_seg"], 1)
             b = dict(pt_lm=np.full(cp, -9, np.int32), pt_px=np.zeros((cp, 2)), pt_level=np.full(cp, -9, np.int32), pt_type=np.full(cp, 9, np.uint8), pt_grad=np.zeros((cp, 2)),
                      seg_lm=np.full(cs, -9, np.int32), seg_px=np.zeros((cs, 4)), seg_level=np.full(cs, -9, np.int32))
             for k, v in b.items():
@@ -850,17 +864,18 @@ class Context:
         maps = self._cand_maps
         n = len(maps)
         caps = self.candidates_capacity()
+        lms = self._cand_cap
         wanted = set(range(n)) if streams is None else set(int(s) for s in streams)
         outs = (abi.CandMapOut * max(n, 1))()
         bufs = []
         width = abi.CandidateMapJob._WIDTH
-        for k, (o, m, cap) in enumerate(zip(outs, maps, caps)):
+        for k, (o, m, cap) in enumerate(zip(outs, lms, caps)):
             if k not in wanted:
                 bufs.append(None)
                 continue
             rows = dict(kf_T=cap["kf"], kf_slot=cap["kf"], kf_pt_off=cap["kf"] + 1, kf_seg_off=cap["kf"] + 1, kf_pt_lm=cap["kf_pt"], kf_seg_lm=cap["kf_seg"],
-                        pt_pos=m.n_pt, pt_type=m.n_pt, pt_obs_off=m.n_pt + 1, seg_spos=m.n_seg, seg_epos=m.n_seg, seg_type=m.n_seg, seg_obs_off=m.n_seg + 1,
-                        pt_cand=m.n_pt_cand, seg_cand=m.n_seg_cand)
+                        pt_pos=m["pt"], pt_type=m["pt"], pt_obs_off=m["pt"] + 1, seg_spos=m["seg"], seg_epos=m["seg"], seg_type=m["seg"], seg_obs_off=m["seg"] + 1,
+                        pt_cand=m["pt_cand"], seg_cand=m["seg_cand"])
             b = {}
             for f in abi._CAND_MAP_ORDER:
                 rows_n = rows[f] if f in rows else cap["pt_obs"] if f.startswith("pt_obs") else cap["seg_obs"]
@@ -878,6 +893,65 @@ class Context:
                        pt_obs_off=o.n_pt + 1, seg_spos=o.n_seg, seg_epos=o.n_seg, seg_type=o.n_seg, seg_obs_off=o.n_seg + 1, pt_cand=o.n_pt_cand, seg_cand=o.n_seg_cand)
             res.append({f: v[:(cut[f] if f in cut else o.n_pt_obs if f.startswith("pt_obs") else o.n_seg_obs)].copy() for f, v in b.items()})
         return res
+
+    # ---- new candidate landmarks appended to the resident map tables ----
+    def candidates_reserve_landmarks(self, extra_pt=0, extra_seg=0):
+        """plsvo_candidates_reserve_landmarks: landmark rows per stream that the NEXT and every later candidates_stage adds to the staged
+        counts (each new landmark also needs one observation entry of candidates_reserve)"""
+        r = abi.CandLmReserve(int(extra_pt), int(extra_seg))
+        self._chk(self.L.plsvo_candidates_reserve_landmarks(self.h, C.byref(r)))
+
+    def candidates_lm_capacity(self):
+        """plsvo_candidates_lm_capacity: per staged stream a dict of the landmark rows its layout was made with (pt, seg)"""
+        n = len(self._cand_maps)
+        outs = (abi.CandLmReserve * max(n, 1))()
+        self._chk(self.L.plsvo_candidates_lm_capacity(self.h, n, outs))
+        return [dict(pt=o.extra_pt, seg=o.extra_seg) for o in outs[:n]]
+
+    def candidates_add_records(self, new):
+        """the records of candidates_add packed once into plsvo_cand_new structs (abi.CandNewBatch, which owns the buffers): per staged
+        stream None or a dict of arrays named like plsvo_cand_new's (pt_pos [k, 3], pt_obs_kf, pt_obs_px [k, 2], pt_obs_f [k, 3],
+        pt_obs_level, pt_obs_type, optionally pt_obs_grad [k, 2]; seg_spos, seg_epos, seg_obs_kf, seg_obs_spx, seg_obs_epx, seg_obs_sf,
+        seg_obs_ef, seg_obs_level); the counts are the lengths of pt_pos / seg_spos"""
+        n = len(new)
+        arr = (abi.CandNew * max(n, 1))()
+        keep, counts = [], []
+        for a, d in zip(arr, new):
+            d = d or {}
+            a.n_pt = 0 if d.get("pt_pos") is None else len(d["pt_pos"])
+            a.n_seg = 0 if d.get("seg_spos") is None else len(d["seg_spos"])
+            counts.append((a.n_pt, a.n_seg))
+            for f in abi._CAND_NEW_ORDER:
+                k = a.n_pt if f.startswith("pt_") else a.n_seg
+                if d.get(f) is None or k == 0:
+                    continue
+                if f in abi._CAND_NEW_I32:
+                    v = np.ascontiguousarray(d[f], dtype=np.int32).reshape(-1)
+                elif f in abi._CAND_NEW_U8:
+                    v = np.ascontiguousarray(d[f], dtype=np.uint8).reshape(-1)
+                else:
+                    v = np.ascontiguousarray(d[f], dtype=np.float64).reshape(-1, abi._CAND_NEW_WIDTH[f])
+                if len(v) != k:
+                    raise ValueError(f"{f}: {k} rows expected")
+                keep.append(v)
+                setattr(a, f, self._ptr(v))
+        return abi.CandNewBatch(n, arr, keep, counts)
+
+    def candidates_add(self, new):
+        """plsvo_candidates_add (enqueue only after the copy): the list candidates_add_records takes, or what it returned (a caller that
+        adds the same shape often, or times the call, packs once)"""
+        batch = new if isinstance(new, abi.CandNewBatch) else self.candidates_add_records(new)
+        self._chk(self.L.plsvo_candidates_add(self.h, batch.n, batch.arr))
+        for now, (k_pt, k_seg) in zip(self._cand_now, batch.counts):
+            now["pt"] += k_pt; now["seg"] += k_seg; now["pt_cand"] += k_pt; now["seg_cand"] += k_seg
+
+    def candidates_add_fetch(self):
+        """plsvo_candidates_add_fetch (synchronises): per stream a dict of what the last add did and the sizes as they stand
+        (abi.CandAddOut's fields)"""
+        n = len(self._cand_maps)
+        outs = (abi.CandAddOut * max(n, 1))()
+        self._chk(self.L.plsvo_candidates_add_fetch(self.h, n, outs))
+        return [{f: int(getattr(o, f)) for f, _ in abi.CandAddOut._fields_} for o in outs[:n]]
 
     def candidates_set_positions(self, moved):
         """plsvo_candidates_set_positions (enqueue only after the copy): per staged stream None or a dict of pt_idx / pt_pos [k, 3] and

@@ -40,6 +40,7 @@ hipError_t launch_map_select(const SelectBatchDev& b, hipStream_t stream);      
 hipError_t launch_map_insert_plan(const InsertBatchDev& b, hipStream_t stream);       // insert_device.hpp, in seeds_kernels.hip
 hipError_t launch_map_insert(const InsertBatchDev& b, hipStream_t stream);
 hipError_t launch_map_set_positions(const PositionsBatchDev& b, hipStream_t stream);
+hipError_t launch_map_add_candidates(const NewCandBatchDev& b, hipStream_t stream);   // newcand_device.hpp, in seeds_kernels.hip
 hipError_t launch_halfsample(const uint8_t* src, size_t src_pitch, int in_w, int in_h, int in_stride, uint8_t* dst,
                              size_t dst_pitch, int n_slots, int rounding, hipStream_t stream);
 hipError_t launch_copy_level0(const uint8_t* src, size_t src_pitch, int w, int h, int stride, uint8_t* dst, size_t dst_pitch,
@@ -223,6 +224,14 @@ struct plsvo_ctx {
   bool ci_inserted = false, ci_have_out = false;
   std::vector<InsertPlanDev> ci_last;
   DevBuf ci_d_work, ci_d_in, ci_d_plan, ci_d_pos;
+  // new candidate landmarks (plsvo_candidates_add ..): the landmark room plsvo_candidates_reserve_landmarks asks for (cn_reserve: the next
+  // stage's), per stream the rows its layout was made with (cn_cap: point rows, segment rows, point candidates, segment candidates), the
+  // candidate counts a run's fetch reports (cd_fetch_cand: an add does not move them), whether an add closed the open run, the last report
+  plsvo_cand_lm_reserve cn_reserve{};
+  std::vector<int> cn_cap, cd_fetch_cand;
+  bool cn_closed = false, cn_have_out = false;
+  std::vector<plsvo_cand_add_out> cn_last;
+  DevBuf cn_d_in;
   unsigned long long run_seq = 0, a_run_seq = 0, p_run_seq = 0, ch_run_seq = 0;   // which resident batch ran last, 0 = not since it was staged (plsvo_pack_pose_records)
 
   // structure optimisation (one-shot batches)
@@ -363,7 +372,7 @@ extern "C" void plsvo_hip_destroy(plsvo_ctx* c) {
   c->a_d_tailflag.release(); c->a_d_alive_tail.release(); c->a_d_xbuf.release(); c->a_d_order[0].release(); c->a_d_order[1].release(); c->a_d_workkey.release(); c->p_d_workkey.release(); c->p_d_order[0].release(); c->p_d_order[1].release();
   c->p_d_carry.release(); c->p_d_refill_next.release();
   c->cd_d_blob.release(); c->cd_d_work.release(); c->cd_d_run.release(); c->cd_d_kfcount.release();
-  for (DevBuf* b : { &c->ci_d_work, &c->ci_d_in, &c->ci_d_plan, &c->ci_d_pos }) b->release();
+  for (DevBuf* b : { &c->ci_d_work, &c->ci_d_in, &c->ci_d_plan, &c->ci_d_pos, &c->cn_d_in }) b->release();
   for (DevBuf* b : { &c->cs_d_q, &c->cs_d_work, &c->cs_d_order, &c->cs_d_state, &c->cs_d_ptkeep, &c->cs_d_segkeep, &c->cs_d_s32, &c->cs_d_s64, &c->cs_d_poses }) b->release();
   DevBuf* bufs[] = { &c->pyr_slab, &c->pyr_tiled, &c->pyr_upload, &c->a_d_blob, &c->a_d_state, &c->a_d_alive, &c->a_d_pxyz, &c->a_d_puv, &c->a_d_cref,
                      &c->a_d_chi, &c->a_d_log, &c->a_d_poses, &c->p_d_blob, &c->p_d_state, &c->p_d_ptkeep, &c->p_d_segkeep, &c->p_d_s32, &c->p_d_s64,
@@ -2417,7 +2426,8 @@ extern "C" int plsvo_candidates_stage(plsvo_ctx* c, int n, const plsvo_cand_map*
   int max_level = 0;
   std::vector<CandMapDev> md((size_t)n);
   const plsvo_cand_reserve R = c->ci_reserve;       // room beyond the staged sizes: the offsets below are laid out by capacity
-  std::vector<int> cap((size_t)n * 5), used((size_t)n * 4);
+  const plsvo_cand_lm_reserve L = c->cn_reserve;    // landmark rows beyond the staged counts: the per-landmark rows, the candidate lists, the filed rows follow
+  std::vector<int> cap((size_t)n * 5), used((size_t)n * 4), lmcap((size_t)n * 4), fetch_cand((size_t)n * 2);
   for (int s = 0; s < n; ++s) {
     const plsvo_cand_map& I = maps[s];
     if (I.n_kf < 0 || I.n_pt < 0 || I.n_seg < 0 || I.n_pt_cand < 0 || I.n_seg_cand < 0) return fail(c, PLSVO_E_INVALID, "candidates_stage: negative count");
@@ -2453,24 +2463,30 @@ extern "C" int plsvo_candidates_stage(plsvo_ctx* c, int n, const plsvo_cand_map*
     for (size_t k = 0; k < segobs; ++k) max_level = std::max(max_level, (int)I.seg_obs_level[k]);
     CandMapDev& M = md[(size_t)s];
     M.n_kf = I.n_kf; M.n_pt = I.n_pt; M.n_seg = I.n_seg; M.n_pt_cand = I.n_pt_cand; M.n_seg_cand = I.n_seg_cand;
-    M.cap_pt = I.n_pt + I.n_pt_cand; M.cap_seg = I.n_seg + I.n_seg_cand; M.stream = s;
+    if ((size_t)I.n_pt + (size_t)I.n_pt_cand + 2 * (size_t)L.extra_pt > (size_t)INT32_MAX || (size_t)I.n_seg + (size_t)I.n_seg_cand + 2 * (size_t)L.extra_seg > (size_t)INT32_MAX)
+      return fail(c, PLSVO_E_CAPACITY, "candidates_stage: stream too large");
+    int* lc = lmcap.data() + 4 * (size_t)s;
+    lc[0] = I.n_pt + L.extra_pt; lc[1] = I.n_seg + L.extra_seg; lc[2] = I.n_pt_cand + L.extra_pt; lc[3] = I.n_seg_cand + L.extra_seg;
+    fetch_cand[2 * (size_t)s] = I.n_pt_cand; fetch_cand[2 * (size_t)s + 1] = I.n_seg_cand;
+    M.cap_pt = lc[0] + lc[2]; M.cap_seg = lc[1] + lc[3]; M.stream = s;   // (what the candidate kernel switches off behind the filed entries: the rows as laid out)
     M.kf_off = (long long)t.kf; M.kfpt_off = (long long)t.kfpt; M.kfseg_off = (long long)t.kfseg; M.pt_off = (long long)t.pt; M.seg_off = (long long)t.seg;
     M.ptobs_off = (long long)t.ptobs; M.segobs_off = (long long)t.segobs; M.ptc_off = (long long)t.ptc; M.segc_off = (long long)t.segc;
     M.opt_off = (long long)t.opt; M.oseg_off = (long long)t.oseg; M.m_off = (long long)t.m; M.f_off = (long long)t.f;
-    M.vis_pt_off = (long long)t.vis; t.vis += ((size_t)I.n_pt + 63) & ~(size_t)63;
-    M.vis_seg_off = (long long)t.vis; t.vis += ((size_t)I.n_seg + 63) & ~(size_t)63;
+    M.vis_pt_off = (long long)t.vis; t.vis += ((size_t)lc[0] + 63) & ~(size_t)63;
+    M.vis_seg_off = (long long)t.vis; t.vis += ((size_t)lc[1] + 63) & ~(size_t)63;
     if (kfpt + (size_t)R.extra_kf_pt > (size_t)INT32_MAX || kfseg + (size_t)R.extra_kf_seg > (size_t)INT32_MAX || ptobs + (size_t)R.extra_pt_obs > (size_t)INT32_MAX ||
         segobs + (size_t)R.extra_seg_obs > (size_t)INT32_MAX || (size_t)I.n_kf + (size_t)R.extra_kf > (size_t)INT32_MAX) return fail(c, PLSVO_E_CAPACITY, "candidates_stage: stream too large");
     int* cp = cap.data() + 5 * (size_t)s; int* us = used.data() + 4 * (size_t)s;
     cp[0] = I.n_kf + R.extra_kf; cp[1] = (int)kfpt + R.extra_kf_pt; cp[2] = (int)kfseg + R.extra_kf_seg; cp[3] = (int)ptobs + R.extra_pt_obs; cp[4] = (int)segobs + R.extra_seg_obs;
     us[0] = (int)kfpt; us[1] = (int)kfseg; us[2] = (int)ptobs; us[3] = (int)segobs;
-    t.kf += (size_t)cp[0]; t.kfpt += (size_t)cp[1]; t.kfseg += (size_t)cp[2]; t.pt += (size_t)I.n_pt; t.seg += (size_t)I.n_seg; t.ptobs += (size_t)cp[3]; t.segobs += (size_t)cp[4];
-    t.ptc += (size_t)I.n_pt_cand; t.segc += (size_t)I.n_seg_cand; t.opt += (size_t)M.cap_pt; t.oseg += (size_t)M.cap_seg;
+    t.kf += (size_t)cp[0]; t.kfpt += (size_t)cp[1]; t.kfseg += (size_t)cp[2]; t.pt += (size_t)lc[0]; t.seg += (size_t)lc[1]; t.ptobs += (size_t)cp[3]; t.segobs += (size_t)cp[4];
+    t.ptc += (size_t)lc[2]; t.segc += (size_t)lc[3]; t.opt += (size_t)M.cap_pt; t.oseg += (size_t)M.cap_seg;
     t.m += (size_t)M.cap_pt + 2 * (size_t)M.cap_seg; t.f += (size_t)cp[0] + 1;
   }
   if (t.m > (size_t)INT32_MAX || t.f > (size_t)INT32_MAX || t.vis > (size_t)INT32_MAX) return fail(c, PLSVO_E_CAPACITY, "candidates_stage: batch too large");
   c->cd_staged = false; c->cd_ran = false; c->cd_matched = false; c->cs_selected = false; c->cs_posed = false; c->ci_inserted = false; c->ci_have_out = false;
-  c->ci_cap = std::move(cap); c->ci_used = std::move(used);
+  c->cn_closed = false; c->cn_have_out = false;
+  c->ci_cap = std::move(cap); c->ci_used = std::move(used); c->cn_cap = std::move(lmcap); c->cd_fetch_cand = std::move(fetch_cand);
   c->ci_t_kf = t.kf; c->ci_t_kfpt = t.kfpt; c->ci_t_kfseg = t.kfseg; c->ci_t_ptobs = t.ptobs; c->ci_t_segobs = t.segobs;
   if (n == 0) { c->cd_n = 0; c->cd_staged = true; c->cd_maps.clear(); c->cd_m_off.clear(); c->cd_f_off.clear(); c->cd_params = *pr; return PLSVO_OK; }
   HIP_TRY(c, hipSetDevice(c->device));
@@ -2598,7 +2614,8 @@ extern "C" int plsvo_candidates_run(plsvo_ctx* c, int n, const plsvo_cand_frame*
     if (!cand_idx_ok(fr[s].overlap_idx, (size_t)fr[s].n_overlap, 0, c->cd_maps[(size_t)s].n_kf)) return fail(c, PLSVO_E_INVALID, "candidates_run: overlap index outside the keyframe table");
     t_ov += (size_t)fr[s].n_overlap;
   }
-  c->cd_ran = false; c->cd_matched = false; c->cs_selected = false; c->cs_posed = false; c->ci_inserted = false;
+  c->cd_ran = false; c->cd_matched = false; c->cs_selected = false; c->cs_posed = false; c->ci_inserted = false; c->cn_closed = false;
+  for (int s = 0; s < n; ++s) { c->cd_fetch_cand[2 * (size_t)s] = c->cd_maps[(size_t)s].n_pt_cand; c->cd_fetch_cand[2 * (size_t)s + 1] = c->cd_maps[(size_t)s].n_seg_cand; }
   c->cd_ov_off.assign((size_t)n + 1, 0);
   if (n == 0) { c->cd_ran = true; return PLSVO_OK; }
   HIP_TRY(c, hipSetDevice(c->device));
@@ -2657,7 +2674,7 @@ extern "C" int plsvo_candidates_fetch(plsvo_ctx* c, int n, plsvo_cand_out* out) 
     cp(O.pt_obs, W[4], po, np, sizeof(int)); cp(O.pt_has_view, W[5], po, np, 1); cp(O.pt_active, W[6], po, np, 1);
     cp(O.seg_lm, W[7], so, ns, sizeof(int)); cp(O.seg_px, W[8], so * 4, ns * 4, sizeof(double)); cp(O.seg_cell, W[9], so * 2, ns * 2, sizeof(int));
     cp(O.seg_obs, W[10], so, ns, sizeof(int)); cp(O.seg_has_view, W[11], so, ns, 1); cp(O.seg_active, W[12], so, ns, 1);
-    cp(O.pt_cand_failed, W[13], (size_t)M.ptc_off, (size_t)M.n_pt_cand, 1); cp(O.seg_cand_failed, W[14], (size_t)M.segc_off, (size_t)M.n_seg_cand, 1);
+    cp(O.pt_cand_failed, W[13], (size_t)M.ptc_off, (size_t)c->cd_fetch_cand[2 * (size_t)s], 1); cp(O.seg_cand_failed, W[14], (size_t)M.segc_off, (size_t)c->cd_fetch_cand[2 * (size_t)s + 1], 1);
     const size_t a = (size_t)c->cd_ov_off[(size_t)s], e = (size_t)c->cd_ov_off[(size_t)s + 1];
     if (O.kf_count && e > a) memcpy(O.kf_count, kfc.data() + a, (e - a) * sizeof(int));
   }
@@ -2668,6 +2685,7 @@ extern "C" int plsvo_candidates_match(plsvo_ctx* c) {
   CTX_CHECK(c);
   if (!c->cd_staged || !c->cd_ran) return fail(c, PLSVO_E_STATE, "candidates_match: no candidates on the device");
   if (c->ci_inserted) return fail(c, PLSVO_E_STATE, "candidates_match: this run's frame was inserted (the tables have moved on); run again");
+  if (c->cn_closed) return fail(c, PLSVO_E_STATE, "candidates_match: landmarks were added behind this run (the tables have moved on); run again");
   if (c->cd_n == 0 || c->cd_total_m == 0) { c->cd_matched = true; return PLSVO_OK; }
   if (!c->pyr.base) return fail(c, PLSVO_E_STATE, "candidates_match: pyramids not configured");
   const plsvo_cand_params& pr = c->cd_params;
@@ -2717,7 +2735,7 @@ extern "C" int plsvo_candidates_match_fetch(plsvo_ctx* c, int n, plsvo_cand_matc
 extern "C" int plsvo_candidates_dev(plsvo_ctx* c, plsvo_cand_dev* o) {
   CTX_CHECK(c);
   if (!o) return fail(c, PLSVO_E_INVALID, "candidates_dev: bad arguments");
-  if (!c->cd_staged || !c->cd_ran || c->cd_n == 0 || c->ci_inserted) return fail(c, PLSVO_E_STATE, "candidates_dev: no candidates on the device");
+  if (!c->cd_staged || !c->cd_ran || c->cd_n == 0 || c->ci_inserted || c->cn_closed) return fail(c, PLSVO_E_STATE, "candidates_dev: no candidates on the device");
   const CandBatchDev& b = c->cd_b; const MatchBatchDev& mb = c->cd_match;
   o->n_entries = (int64_t)c->cd_total_m; o->n_frames = (int64_t)c->cd_total_f;
   o->m_off = c->cd_m_off.data(); o->f_off = c->cd_f_off.data();
@@ -2731,6 +2749,7 @@ extern "C" int plsvo_candidates_dev(plsvo_ctx* c, plsvo_cand_dev* o) {
 // ---- cell selection of the map candidates: one per cell, landmark quality, features, pose-optimiser input (select_device.hpp) ---------
 namespace {
 constexpr int kInsJoinedBit = 32;                  // insert_device.hpp's kInsJoined
+constexpr int kNewCandBit = 64;                    // newcand_device.hpp's kNewCand
 // the sections of cs_d_q, as plsvo_candidates_stage carved them
 struct QualitySections { size_t pt_nf, pt_ns, seg_nf, seg_ns, pt_ev, seg_ev, end; };
 static QualitySections quality_sections(const plsvo_ctx* c) {
@@ -2806,7 +2825,8 @@ extern "C" int plsvo_candidates_fetch_quality(plsvo_ctx* c, int n, plsvo_cand_qu
     cp(O.seg_n_failed, hq.data() + q.seg_nf, so, ns, sizeof(int)); cp(O.seg_n_succeeded, hq.data() + q.seg_ns, so, ns, sizeof(int));
     cp(O.pt_type, ptype.data(), po, np, sizeof(int)); cp(O.seg_type, stype.data(), so, ns, sizeof(int));
     // (the insertion's bit sits above the selection's internal ones)
-    auto public_event = [](char ev) { return (uint8_t)((ev & (PLSVO_LM_EVENT_PROMOTED | PLSVO_LM_EVENT_DELETED)) | ((ev & kInsJoinedBit) ? PLSVO_LM_EVENT_JOINED : 0)); };
+    auto public_event = [](char ev) { return (uint8_t)((ev & (PLSVO_LM_EVENT_PROMOTED | PLSVO_LM_EVENT_DELETED)) | ((ev & kInsJoinedBit) ? PLSVO_LM_EVENT_JOINED : 0) |
+                                                    ((ev & kNewCandBit) ? PLSVO_LM_EVENT_NEW : 0)); };
     if (O.pt_event) for (size_t k = 0; k < np; ++k) O.pt_event[k] = public_event(hq[q.pt_ev + po + k]);
     if (O.seg_event) for (size_t k = 0; k < ns; ++k) O.seg_event[k] = public_event(hq[q.seg_ev + so + k]);
     cp(O.pt_cand, ptc.data(), (size_t)M.ptc_off, (size_t)M.n_pt_cand, sizeof(int)); cp(O.seg_cand, segc.data(), (size_t)M.segc_off, (size_t)M.n_seg_cand, sizeof(int));
@@ -2818,6 +2838,7 @@ extern "C" int plsvo_candidates_set_match(plsvo_ctx* c, int n, const plsvo_cand_
   CTX_CHECK(c);
   if (!c->cd_staged || !c->cd_ran) return fail(c, PLSVO_E_STATE, "candidates_set_match: no candidates on the device");
   if (c->ci_inserted) return fail(c, PLSVO_E_STATE, "candidates_set_match: this run's frame was inserted (the tables have moved on); run again");
+  if (c->cn_closed) return fail(c, PLSVO_E_STATE, "candidates_set_match: landmarks were added behind this run (the tables have moved on); run again");
   if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_set_match: n does not match the staged batch");
   for (int s = 0; s < n; ++s) if (!in[s].found || !in[s].px || !in[s].search_level) return fail(c, PLSVO_E_INVALID, "candidates_set_match: null array");
   if (n == 0 || c->cd_total_m == 0) { c->cd_matched = true; return PLSVO_OK; }
@@ -2843,6 +2864,7 @@ extern "C" int plsvo_candidates_select(plsvo_ctx* c, const plsvo_cand_select_par
   if (!sp) return fail(c, PLSVO_E_INVALID, "candidates_select: bad arguments");
   if (!c->cd_staged || !c->cd_ran || !c->cd_matched) return fail(c, PLSVO_E_STATE, "candidates_select: no match on the device");
   if (c->cs_selected) return fail(c, PLSVO_E_STATE, "candidates_select: this run's candidates were selected already (the tables have moved on)");
+  if (c->cn_closed) return fail(c, PLSVO_E_STATE, "candidates_select: landmarks were added behind this run (the tables have moved on); run again");
   if (sp->max_fts < 0 || sp->max_fts_segs < 0 || sp->poseopt_n_iter < 0)
     return fail(c, PLSVO_E_INVALID, "candidates_select: bad parameters");
   const plsvo_cand_params& pr = c->cd_params;
@@ -2933,6 +2955,7 @@ extern "C" int plsvo_candidates_pose_optimize(plsvo_ctx* c) {
   CTX_CHECK(c);
   if (!c->cd_staged || !c->cs_selected) return fail(c, PLSVO_E_STATE, "candidates_pose_optimize: no selection on the device");
   if (c->ci_inserted) return fail(c, PLSVO_E_STATE, "candidates_pose_optimize: this run's frame was inserted (the tables have moved on); run again");
+  if (c->cn_closed) return fail(c, PLSVO_E_STATE, "candidates_pose_optimize: landmarks were added behind this run (the tables have moved on); run again");
   const int n = c->cd_n;
   c->cs_posed = false;
   if (n == 0) { c->cs_posed = true; return PLSVO_OK; }
@@ -3008,6 +3031,7 @@ extern "C" int plsvo_candidates_insert_keyframe(plsvo_ctx* c, int n, const plsvo
   CTX_CHECK(c);
   if (!c->cd_staged || !c->cd_ran || !c->cs_selected) return fail(c, PLSVO_E_STATE, "candidates_insert_keyframe: no selection on the last run");
   if (c->ci_inserted) return fail(c, PLSVO_E_STATE, "candidates_insert_keyframe: this run's frame was inserted already");
+  if (c->cn_closed) return fail(c, PLSVO_E_STATE, "candidates_insert_keyframe: landmarks were added behind this run (the tables have moved on); run again");
   if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_insert_keyframe: n does not match the staged batch");
   bool any = false, host_masks = false;
   for (int s = 0; s < n; ++s) {
@@ -3114,6 +3138,7 @@ extern "C" int plsvo_candidates_insert_keyframe(plsvo_ctx* c, int n, const plsvo
     slot[P.new_kf] = in[s].kf_slot;
     for (int k = P.n_kf; k < c->ci_cap[5 * (size_t)s]; ++k) slot[k] = 0;
     M.n_kf = P.n_kf; M.n_pt_cand = P.n_pt_cand; M.n_seg_cand = P.n_seg_cand;
+    c->cd_fetch_cand[2 * (size_t)s] = P.n_pt_cand; c->cd_fetch_cand[2 * (size_t)s + 1] = P.n_seg_cand;
     int* us = c->ci_used.data() + 4 * (size_t)s;
     us[0] = P.n_kf_pt; us[1] = P.n_kf_seg; us[2] = P.n_pt_obs; us[3] = P.n_seg_obs;
     c->ci_last[(size_t)s] = P;
@@ -3225,6 +3250,138 @@ extern "C" int plsvo_candidates_set_positions(plsvo_ctx* c, int n, const plsvo_c
   p.seg_at = reinterpret_cast<const long long*>(d + b_si); p.seg_ssrc = reinterpret_cast<const double*>(d + b_ss); p.seg_esrc = reinterpret_cast<const double*>(d + b_se);
   p.pt_pos = const_cast<double*>(c->cd_b.pt_pos); p.seg_spos = const_cast<double*>(c->cd_b.seg_spos); p.seg_epos = const_cast<double*>(c->cd_b.seg_epos);
   HIP_TRY(c, launch_map_set_positions(p, c->stream));
+  return PLSVO_OK;
+}
+
+// ---- new candidate landmarks appended to the resident map tables (newcand_device.hpp) -----------------------------------
+extern "C" int plsvo_candidates_reserve_landmarks(plsvo_ctx* c, const plsvo_cand_lm_reserve* r) {
+  CTX_CHECK(c);
+  if (r && (r->extra_pt < 0 || r->extra_seg < 0)) return fail(c, PLSVO_E_INVALID, "candidates_reserve_landmarks: negative room");
+  c->cn_reserve = r ? *r : plsvo_cand_lm_reserve{};
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_lm_capacity(plsvo_ctx* c, int n, plsvo_cand_lm_reserve* out) {
+  CTX_CHECK(c);
+  if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_lm_capacity: no staged map tables");
+  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_lm_capacity: n does not match the staged batch");
+  for (int s = 0; s < n; ++s) { out[s].extra_pt = c->cn_cap[4 * (size_t)s]; out[s].extra_seg = c->cn_cap[4 * (size_t)s + 1]; }
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_add(plsvo_ctx* c, int n, const plsvo_cand_new* in) {
+  CTX_CHECK(c);
+  if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_add: no staged map tables");
+  if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_add: n does not match the staged batch");
+  // -- every check before anything is written: arguments, then room (from the host's mirrors: landmark count, used observation entries)
+  size_t t_pt = 0, t_seg = 0;
+  int max_level = c->cd_max_level;
+  for (int s = 0; s < n; ++s) {
+    const plsvo_cand_new& I = in[s]; const CandMapDev& M = c->cd_maps[(size_t)s];
+    if (I.n_pt < 0 || I.n_seg < 0) return fail(c, PLSVO_E_INVALID, "candidates_add: negative count");
+    if (I.n_pt > 0 && (!I.pt_pos || !I.pt_obs_kf || !I.pt_obs_px || !I.pt_obs_f || !I.pt_obs_level || !I.pt_obs_type)) return fail(c, PLSVO_E_INVALID, "candidates_add: null point array");
+    if (I.n_seg > 0 && (!I.seg_spos || !I.seg_epos || !I.seg_obs_kf || !I.seg_obs_spx || !I.seg_obs_epx || !I.seg_obs_sf || !I.seg_obs_ef || !I.seg_obs_level))
+      return fail(c, PLSVO_E_INVALID, "candidates_add: null segment array");
+    if (!cand_idx_ok(I.pt_obs_kf, (size_t)I.n_pt, 0, M.n_kf) || !cand_idx_ok(I.seg_obs_kf, (size_t)I.n_seg, 0, M.n_kf)) return fail(c, PLSVO_E_INVALID, "candidates_add: observation keyframe outside the keyframe table");
+    if (!cand_idx_ok(I.pt_obs_level, (size_t)I.n_pt, 0, PLSVO_MAX_LEVELS) || !cand_idx_ok(I.seg_obs_level, (size_t)I.n_seg, 0, PLSVO_MAX_LEVELS))
+      return fail(c, PLSVO_E_INVALID, "candidates_add: observation level out of range");
+    for (int k = 0; k < I.n_pt; ++k) {
+      if (I.pt_obs_type[k] == PLSVO_FTR_EDGELET) { if (!I.pt_obs_grad) return fail(c, PLSVO_E_INVALID, "candidates_add: edgelets without pt_obs_grad"); }
+      else if (I.pt_obs_type[k] != PLSVO_FTR_CORNER) return fail(c, PLSVO_E_INVALID, "candidates_add: unknown feature type");
+      max_level = std::max(max_level, (int)I.pt_obs_level[k]);
+    }
+    for (int k = 0; k < I.n_seg; ++k) max_level = std::max(max_level, (int)I.seg_obs_level[k]);
+    t_pt += (size_t)I.n_pt; t_seg += (size_t)I.n_seg;
+  }
+  for (int s = 0; s < n; ++s) {
+    const plsvo_cand_new& I = in[s]; const CandMapDev& M = c->cd_maps[(size_t)s];
+    const int* lc = c->cn_cap.data() + 4 * (size_t)s; const int* cp = c->ci_cap.data() + 5 * (size_t)s; const int* us = c->ci_used.data() + 4 * (size_t)s;
+    if ((long long)M.n_pt + I.n_pt > lc[0] || (long long)M.n_seg + I.n_seg > lc[1])
+      return fail(c, PLSVO_E_CAPACITY, "candidates_add: a stream lacks landmark rows (plsvo_candidates_reserve_landmarks); nothing was changed");
+    if ((long long)us[2] + I.n_pt > cp[3] || (long long)us[3] + I.n_seg > cp[4])
+      return fail(c, PLSVO_E_CAPACITY, "candidates_add: a stream lacks observation entries (plsvo_candidates_reserve); nothing was changed");
+  }
+  const size_t N = (size_t)n;
+  c->cn_last.assign(N, plsvo_cand_add_out{});
+  for (int s = 0; s < n; ++s) {
+    const plsvo_cand_new& I = in[s]; const CandMapDev& M = c->cd_maps[(size_t)s];
+    plsvo_cand_add_out& O = c->cn_last[(size_t)s];
+    O.first_pt = I.n_pt ? M.n_pt : -1; O.first_seg = I.n_seg ? M.n_seg : -1; O.n_added_pt = I.n_pt; O.n_added_seg = I.n_seg;
+  }
+  c->cn_closed = true; c->cn_have_out = true;       // (an add of nothing ends the run too: the rule does not depend on the counts)
+  if (t_pt + t_seg == 0) return PLSVO_OK;
+  if (t_pt > (size_t)INT32_MAX || t_seg > (size_t)INT32_MAX) return fail(c, PLSVO_E_CAPACITY, "candidates_add: batch too large");
+  HIP_TRY(c, hipSetDevice(c->device));
+  Blob blob;
+  const size_t b_jobs = blob.reserve<NewCandJobDev>(N);
+  const size_t b_ppos = blob.reserve<double>(t_pt * 3), b_pkf = blob.reserve<int>(t_pt), b_ppx = blob.reserve<double>(t_pt * 2), b_pf = blob.reserve<double>(t_pt * 3),
+               b_plv = blob.reserve<int>(t_pt), b_pty = blob.reserve<uint8_t>(t_pt), b_pgr = blob.reserve<double>(t_pt * 2);
+  const size_t b_ss = blob.reserve<double>(t_seg * 3), b_se = blob.reserve<double>(t_seg * 3), b_skf = blob.reserve<int>(t_seg), b_sspx = blob.reserve<double>(t_seg * 2),
+               b_sepx = blob.reserve<double>(t_seg * 2), b_ssf = blob.reserve<double>(t_seg * 3), b_sef = blob.reserve<double>(t_seg * 3), b_slv = blob.reserve<int>(t_seg);
+  auto put = [&](size_t sec, size_t at, const void* src, size_t count, size_t elem) {
+    if (count) { if (src) memcpy(blob.host.data() + sec + at * elem, src, count * elem); else memset(blob.host.data() + sec + at * elem, 0, count * elem); }
+  };
+  size_t ap = 0, as = 0;
+  for (int s = 0; s < n; ++s) {
+    const plsvo_cand_new& I = in[s];
+    NewCandJobDev& J = blob.at<NewCandJobDev>(b_jobs)[s];
+    J.n_pt = I.n_pt; J.n_seg = I.n_seg; J.pt_at = (long long)ap; J.seg_at = (long long)as;
+    const size_t np = (size_t)I.n_pt, ns = (size_t)I.n_seg;
+    put(b_ppos, ap * 3, I.pt_pos, np * 3, sizeof(double)); put(b_pkf, ap, I.pt_obs_kf, np, sizeof(int)); put(b_ppx, ap * 2, I.pt_obs_px, np * 2, sizeof(double));
+    put(b_pf, ap * 3, I.pt_obs_f, np * 3, sizeof(double)); put(b_plv, ap, I.pt_obs_level, np, sizeof(int)); put(b_pty, ap, I.pt_obs_type, np, 1);
+    put(b_pgr, ap * 2, I.pt_obs_grad, np * 2, sizeof(double));
+    put(b_ss, as * 3, I.seg_spos, ns * 3, sizeof(double)); put(b_se, as * 3, I.seg_epos, ns * 3, sizeof(double)); put(b_skf, as, I.seg_obs_kf, ns, sizeof(int));
+    put(b_sspx, as * 2, I.seg_obs_spx, ns * 2, sizeof(double)); put(b_sepx, as * 2, I.seg_obs_epx, ns * 2, sizeof(double));
+    put(b_ssf, as * 3, I.seg_obs_sf, ns * 3, sizeof(double)); put(b_sef, as * 3, I.seg_obs_ef, ns * 3, sizeof(double)); put(b_slv, as, I.seg_obs_level, ns, sizeof(int));
+    ap += np; as += ns;
+  }
+  int rc;
+  if ((rc = upload_blob(c, c->cn_d_in, blob))) return rc;
+  const char* d = reinterpret_cast<const char*>(c->cn_d_in.p);
+  const QualitySections q = quality_sections(c);
+  char* dq = reinterpret_cast<char*>(c->cs_d_q.p);
+  auto D = [&](size_t o) { return reinterpret_cast<const double*>(d + o); };
+  auto Iv = [&](size_t o) { return reinterpret_cast<const int*>(d + o); };
+  NewCandBatchDev b{};
+  b.c = c->cd_b;
+  b.pt_nfail = reinterpret_cast<int*>(dq + q.pt_nf); b.pt_nsucc = reinterpret_cast<int*>(dq + q.pt_ns);
+  b.seg_nfail = reinterpret_cast<int*>(dq + q.seg_nf); b.seg_nsucc = reinterpret_cast<int*>(dq + q.seg_ns);
+  b.pt_event = reinterpret_cast<uint8_t*>(dq + q.pt_ev); b.seg_event = reinterpret_cast<uint8_t*>(dq + q.seg_ev);
+  b.jobs = reinterpret_cast<const NewCandJobDev*>(d + b_jobs);
+  b.pt_pos = D(b_ppos); b.pt_obs_kf = Iv(b_pkf); b.pt_obs_px = D(b_ppx); b.pt_obs_f = D(b_pf); b.pt_obs_level = Iv(b_plv);
+  b.pt_obs_type = reinterpret_cast<const uint8_t*>(d + b_pty); b.pt_obs_grad = D(b_pgr);
+  b.seg_spos = D(b_ss); b.seg_epos = D(b_se); b.seg_obs_kf = Iv(b_skf); b.seg_obs_spx = D(b_sspx); b.seg_obs_epx = D(b_sepx); b.seg_obs_sf = D(b_ssf);
+  b.seg_obs_ef = D(b_sef); b.seg_obs_level = Iv(b_slv);
+  {
+    EventPair ep{}; prof_begin(c, PLSVO_K_NEWCAND, &ep);
+    const hipError_t launched = launch_map_add_candidates(b, c->stream);
+    prof_end(c, PLSVO_K_NEWCAND, &ep);               // ahead of the error return, as in plsvo_candidates_run
+    HIP_TRY(c, launched);
+  }
+  // -- the host mirrors describe the new tables (the candidate counts are upper bounds: the selection shortens the lists on the device)
+  for (int s = 0; s < n; ++s) {
+    CandMapDev& M = c->cd_maps[(size_t)s]; int* us = c->ci_used.data() + 4 * (size_t)s;
+    M.n_pt += in[s].n_pt; M.n_seg += in[s].n_seg; M.n_pt_cand += in[s].n_pt; M.n_seg_cand += in[s].n_seg;
+    us[2] += in[s].n_pt; us[3] += in[s].n_seg;
+  }
+  c->cd_max_level = max_level;
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_add_fetch(plsvo_ctx* c, int n, plsvo_cand_add_out* out) {
+  CTX_CHECK(c);
+  if (!c->cd_staged || !c->cn_have_out) return fail(c, PLSVO_E_STATE, "candidates_add_fetch: no add since the tables were staged");
+  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_add_fetch: n does not match the staged batch");
+  if (n == 0) return PLSVO_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  std::vector<CandMapDev> maps((size_t)n);         // the candidate counts as they stand are the device's
+  HIP_TRY(c, hipMemcpyAsync(maps.data(), c->cd_b.maps, (size_t)n * sizeof(CandMapDev), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (int s = 0; s < n; ++s) {
+    const CandMapDev& M = maps[(size_t)s]; const int* us = c->ci_used.data() + 4 * (size_t)s;
+    out[s] = c->cn_last[(size_t)s];
+    out[s].n_pt = M.n_pt; out[s].n_seg = M.n_seg; out[s].n_pt_cand = M.n_pt_cand; out[s].n_seg_cand = M.n_seg_cand; out[s].n_pt_obs = us[2]; out[s].n_seg_obs = us[3];
+  }
   return PLSVO_OK;
 }
 

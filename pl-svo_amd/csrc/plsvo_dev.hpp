@@ -303,7 +303,7 @@ struct KfDecideBatchDev {
 // caller's stream-relative values: kf_pt_off of stream s has n_kf + 1 entries from kf_off + s, pt_obs_off n_pt + 1 from pt_off + s.
 struct CandMapDev {
   int n_kf, n_pt, n_seg, n_pt_cand, n_seg_cand;
-  int cap_pt, cap_seg;              // n_pt + n_pt_cand, n_seg + n_seg_cand: the most that can be filed
+  int cap_pt, cap_seg;              // the stream's filed rows as laid out: landmark rows + candidate entries of CAPACITY (the counts without a landmark reserve)
   int stream;                       // s
   long long kf_off;                 // keyframes: kf_T, kf_pos
   long long kfpt_off, kfseg_off;    // the keyframes' feature lists
@@ -396,6 +396,23 @@ struct InsertBatchDev {
   SelectBatchDev s;
   const InsertJobDev* jobs; InsertPlanDev* plan;
   InsertKindDev pt, seg;
+};
+// new candidate landmarks appended to the resident map tables (newcand_device.hpp, include/plsvo_hip.h plsvo_candidates_add): one wave
+// per stream.  The records of all streams are concatenated per kind; a stream's begin at pt_at / seg_at.  Its landmark rows, candidate
+// list and observation entries have room behind their used part (plsvo_candidates_reserve_landmarks, plsvo_candidates_reserve); the
+// host has checked that room against its mirrors before the launch.
+struct NewCandJobDev {
+  int n_pt, n_seg;
+  long long pt_at, seg_at;
+};
+struct NewCandBatchDev {
+  CandBatchDev c;
+  int* pt_nfail; int* pt_nsucc; int* seg_nfail; int* seg_nsucc; uint8_t* pt_event; uint8_t* seg_event;   // the resident landmark quality
+  const NewCandJobDev* jobs;
+  const double* pt_pos; const int* pt_obs_kf; const double* pt_obs_px; const double* pt_obs_f; const int* pt_obs_level; const uint8_t* pt_obs_type;
+  const double* pt_obs_grad;        // always present (zeros where the caller gave none)
+  const double* seg_spos; const double* seg_epos; const int* seg_obs_kf; const double* seg_obs_spx; const double* seg_obs_epx; const double* seg_obs_sf;
+  const double* seg_obs_ef; const int* seg_obs_level;
 };
 struct PositionsBatchDev {          // plsvo_candidates_set_positions: moved landmarks scattered into the resident tables (global landmark rows)
   int n_pt, n_seg;

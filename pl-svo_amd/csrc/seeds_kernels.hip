@@ -25,6 +25,7 @@
 #include "candidates_device.hpp" // and the map candidates' kernel
 #include "select_device.hpp"     // and their cell selection
 #include "insert_device.hpp"     // and the keyframe insertion into the resident tables
+#include "newcand_device.hpp"    // and the new candidate landmarks appended to them
 
 namespace plsvo_hip {
 
@@ -426,6 +427,12 @@ hipError_t launch_map_set_positions(const PositionsBatchDev& b, hipStream_t stre
 hipError_t launch_map_insert(const InsertBatchDev& b, hipStream_t stream) {
   if (b.s.c.n_jobs <= 0) return hipSuccess;
   hipLaunchKernelGGL(map_insert_kernel, dim3((b.s.c.n_jobs + kInsWaves - 1) / kInsWaves), dim3(64 * kInsWaves), 0, stream, b);
+  return hipGetLastError();
+}
+// new candidate landmarks (newcand_device.hpp): the same shape
+hipError_t launch_map_add_candidates(const NewCandBatchDev& b, hipStream_t stream) {
+  if (b.c.n_jobs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_add_candidates_kernel, dim3((b.c.n_jobs + kNewWaves - 1) / kNewWaves), dim3(64 * kNewWaves), 0, stream, b);
   return hipGetLastError();
 }
 

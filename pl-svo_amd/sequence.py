@@ -43,7 +43,10 @@ device.  The harness follows the types, the candidate lists and the deletions in
 the map changes at a keyframe (or a seed converges), and carries the counters over a restage with fetch_quality / set_quality.  With
 kf_insert=True on top of that (a backend with map_insert) a keyframe no longer restages: the frame joins the resident tables on the device
 (plsvo_candidates_insert_keyframe), the harness takes its own tables from the backend's fetch, moved landmarks go through
-map_set_positions, and only a seed that converges into a NEW candidate stages again.  The
+map_set_positions, and only a seed that converges into a NEW candidate stages again.  With seed_candidates=True on top of that (a
+backend with map_add_candidates) that last restage goes too: the converged seed is appended to the resident tables on the device
+(plsvo_candidates_add) as a new landmark row with one observation and an entry at the back of the candidate list, and the
+stage is called once, at the first frame.  The
 features reach the pose optimiser in selection order; a segment that won both of its cells is a feature twice.
 
 `backend` is duck-typed: load_frames(list of level-0 images; HipBackend also takes raw frames with rectify=), sparse_align(job), reproject(job), match_direct(job),
@@ -149,6 +152,16 @@ class HipBackend:
     def map_set_positions(self, pt_idx, pt_pos):
         """moved point landmarks into the resident tables (plsvo_candidates_set_positions)"""
         self.ctx.candidates_set_positions([dict(pt_idx=pt_idx, pt_pos=pt_pos)])
+
+    def map_reserve_landmarks(self, **room):
+        """landmark rows per stream for the candidates to come (plsvo_candidates_reserve_landmarks; no arguments: today's layout again)"""
+        self.ctx.candidates_reserve_landmarks(**room)
+
+    def map_add_candidates(self, new):
+        """converged seeds become candidate landmarks of the resident tables (plsvo_candidates_add); new: the arrays of plsvo_cand_new as
+        capi.Context.candidates_add takes them.  -> (what the add did: capi.Context.candidates_add_fetch's record, the quality state)"""
+        self.ctx.candidates_add([new])
+        return self.ctx.candidates_add_fetch()[0], self.ctx.candidates_fetch_quality()[0]
 
     def detect_corners(self, slot, occupancy=None, cell_size=25, n_levels=3, detection_threshold=20.0):
         """FastDetector::detect on the frame in `slot` (plsvo_hip_detect_fast): abi.CORNER_DTYPE records in cell order"""
@@ -259,7 +272,8 @@ def candidate_map_tables(t):
 
 def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_thresh=2.0, mapping=False, known_frac=0.6,
                  pos_noise=0.005, map_seed=0, kf_every=5, detect=False, detect_cell_size=25, kf_select=False, kfselect_mindist_t=0.06,
-                 kfselect_mindist_r=3.0, max_n_kfs=10, map_candidates=False, record_candidates=False, cell_select=False, select_params=None, kf_insert=False):
+                 kfselect_mindist_r=3.0, max_n_kfs=10, map_candidates=False, record_candidates=False, cell_select=False, select_params=None, kf_insert=False,
+                 seed_candidates=False):
     """-> list of per-frame dicts (pose T_f_w, cov, counts).  Frame 0 is the keyframe with the true pose.
     mapping=True: only `known_frac` of the point landmarks start in the map (positions off by `pos_noise` x depth along
     their viewing ray), the others are depth-filter seeds; the seed update runs every frame; every `kf_every`-th frame
@@ -286,8 +300,16 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
     only at the start and when a seed converges into a NEW candidate -- observed in frame 0's keyframe, whose row the harness follows through
     the removals; a seed that converges after that keyframe was removed stays outside the map's tables (n_seed_candidates counts the
     others).  The keyframe records gain n_joined / n_deleted_kf / remove_kf, and
-    with record_candidates rec["insert"]: the tables and the quality before, the selection, the masks, the pose, and all three after."""
+    with record_candidates rec["insert"]: the tables and the quality before, the selection, the masks, the pose, and all three after.
+    seed_candidates=True (with kf_insert, a backend with map_add_candidates): a converged seed whose keyframe is still in the table is
+    appended to the resident tables on the device (plsvo_candidates_add) instead of marking the tables for a restage; the
+    harness appends the same row to its own tables.  The seed's table row is then a NEW one behind the staged rows, no longer its landmark
+    index: the harness keeps the row of every landmark and the landmark of every row, and translates wherever the backend speaks in rows
+    (filed and selected landmarks, moved positions).  With record_candidates rec["add"] holds the tables and the quality before, the new
+    records, the tables and the quality after, and the backend's report."""
     params = dict(locals())                            # (first statement: exactly the arguments)
+    if seed_candidates and not (kf_insert and hasattr(backend, "map_add_candidates")):
+        raise ValueError("seed_candidates needs kf_insert and a backend with map_add_candidates()")
     if kf_insert and not (cell_select and mapping and hasattr(backend, "map_insert")):
         raise ValueError("kf_insert needs mapping, cell_select and a backend with map_insert()")
     if not kf_insert:
@@ -295,14 +317,18 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
     # room for every keyframe the sequence can add (a joined candidate adds a feature, every feature an observation)
     n_fr, n_lm = len(seq["images"]), len(seq["pt_pos"]) + 2 * len(seq["seg_spos"])
     backend.map_reserve(extra_kf=n_fr, extra_kf_pt=n_fr * n_lm, extra_kf_seg=n_fr * n_lm, extra_pt_obs=n_fr * n_lm, extra_seg_obs=n_fr * n_lm)
+    if seed_candidates:                                # a landmark row per seed that can converge (its observation fits the room above)
+        backend.map_reserve_landmarks(extra_pt=len(seq["pt_pos"]), extra_seg=0)
     try:
         return _run_sequence(**params)
     finally:
         backend.map_reserve()                          # the tight layout again for whoever stages next on this backend
+        if seed_candidates:
+            backend.map_reserve_landmarks()
 
 
 def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thresh, mapping, known_frac, pos_noise, map_seed, kf_every, detect, detect_cell_size, kf_select,
-                  kfselect_mindist_t, kfselect_mindist_r, max_n_kfs, map_candidates, record_candidates, cell_select, select_params, kf_insert):
+                  kfselect_mindist_t, kfselect_mindist_r, max_n_kfs, map_candidates, record_candidates, cell_select, select_params, kf_insert, seed_candidates):
     cam = seq["cam"]
     if cell_select and not (map_candidates and hasattr(backend, "map_select")):
         raise ValueError("cell_select needs map_candidates and a backend with map_select()")
@@ -376,6 +402,10 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                            for i in range(n_seg)], pt_cand=[], seg_cand=[])
         cm_dirty = True
         seed_kf = 0                                    # the row of frame 0, where every seed was started (None once kf_insert removed it)
+        # point rows of the tables <-> landmarks (indices of P3 / px_new): the identity until seed_candidates appends a converged seed as a
+        # NEW row (its own row stays behind, empty and in no list); segment rows are segment indices throughout
+        row_lm = list(range(n_pts))
+        lm_row = np.arange(n_pts, dtype=np.int64)
         quality = None                                 # cell_select: the quality state after the last frame (None: nothing staged yet)
         select_kw = dict(max_fts=120, max_fts_segs=100, cell_order=None, seg_cell_order=None, reproj_thresh=reproj_thresh)
         select_kw.update(select_params or {})
@@ -416,7 +446,7 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                     overlap = list(range(len(cm["kf_T"])))
                 map_job = None
                 if cm_dirty:
-                    cm["pt_pos"] = [[float(x) for x in v] for v in P3]
+                    cm["pt_pos"] = [[float(x) for x in P3[i]] for i in row_lm]
                     map_job = candidate_map_job(cm)
                     cm_dirty = False
                 if cell_select:
@@ -429,7 +459,7 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                 found = np.zeros(len(pos_all), bool)
                 px_new = np.zeros((len(pos_all), 2))
                 level = np.zeros(len(pos_all), np.int32)
-                at = np.concatenate([cr["pt_lm"], n_pts + cr["seg_lm"], n_pts + n_seg + cr["seg_lm"]]).astype(np.int64)
+                at = np.concatenate([np.asarray(row_lm, np.int64)[cr["pt_lm"]], n_pts + cr["seg_lm"], n_pts + n_seg + cr["seg_lm"]]).astype(np.int64)
                 found[at] = mr["found"].astype(bool)
                 px_new[at] = mr["px"]
                 level[at] = np.maximum(mr["search_level"], 0)
@@ -483,7 +513,7 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
             seg_ok = found[n_pts:n_pts + n_seg] & found[n_pts + n_seg:]
             if cell_select:
                 # ---- 4. on the device: the selected features in selection order, the resident pose optimiser's result ----
-                pt_i, seg_i = sel["pt_lm"].astype(np.int64), sel["seg_lm"].astype(np.int64)
+                pt_i, seg_i = np.asarray(row_lm, np.int64)[sel["pt_lm"]], sel["seg_lm"].astype(np.int64)
                 pt_ok = np.zeros(n_pts, bool); pt_ok[pt_i] = True
                 seg_ok = np.zeros(n_seg, bool); seg_ok[seg_i] = True
                 pr = pr_sel
@@ -580,9 +610,9 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                 P3[sel] = so["pt_pos"]
                 last_optim[sel] = k
                 if kf_insert:
-                    backend.map_set_positions(sel.astype(np.int32), P3[sel])
+                    backend.map_set_positions(lm_row[sel].astype(np.int32), P3[sel])
                     for i in sel:
-                        cm["pt_pos"][int(i)] = [float(x) for x in P3[i]]
+                        cm["pt_pos"][int(lm_row[i])] = [float(x) for x in P3[i]]
                 elif map_candidates:
                     cm_dirty = True
             # ---- 6. depth-filter update of the seeds with this frame (DepthFilter::updateSeeds) ----
@@ -596,7 +626,26 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                 conv = stt == abi.SEED_CONVERGED
                 P3[si_[conv]] = sr["pt_xyz_world"][conv]
                 known[si_[conv]] = True
-                if map_candidates and conv.any() and seed_kf is not None:
+                if seed_candidates and conv.any() and seed_kf is not None:
+                    # the converged seeds join the RESIDENT tables on the device as new landmark rows (newCandidatePoint); the harness
+                    # appends the same rows to its own
+                    ci = [int(i) for i in si_[conv]]
+                    new = dict(pt_pos=sr["pt_xyz_world"][conv], pt_obs_kf=np.full(len(ci), seed_kf, np.int32), pt_obs_px=seq["pt_px0"][ci], pt_obs_f=seq["pt_f0"][ci],
+                               pt_obs_level=np.zeros(len(ci), np.int32), pt_obs_type=np.full(len(ci), abi.FTR_CORNER, np.uint8), pt_obs_grad=np.zeros((len(ci), 2)))
+                    before = (copy.deepcopy(cm), quality) if record_candidates else None
+                    report, quality = backend.map_add_candidates(new)
+                    for j, i in enumerate(ci):
+                        row = len(cm["pt_pos"])
+                        assert row == report["first_pt"] + j
+                        cm["pt_pos"].append([float(x) for x in P3[i]])
+                        cm["pt_type"].append(abi.LM_CANDIDATE)
+                        cm["pt_obs"].append([dict(kf=seed_kf, px=[float(x) for x in seq["pt_px0"][i]], f=[float(x) for x in seq["pt_f0"][i]], level=0,
+                                                  type=abi.FTR_CORNER, grad=[0.0, 0.0])])
+                        cm["pt_cand"].append(row)
+                        row_lm.append(i); lm_row[i] = row
+                    if record_candidates:
+                        rec["add"] = dict(stream=before[0], quality_before=before[1], new=new, tables=copy.deepcopy(cm), quality=quality, report=report)
+                elif map_candidates and conv.any() and seed_kf is not None:
                     # a converged seed becomes a candidate of the map (map_.point_candidates_), observed in the keyframe it was started in
                     # (frame 0; once that keyframe has left the table the seed's only observation is gone with it, as
                     # removeFrameCandidates would delete it: the landmark stays outside the map's tables)

@@ -11,7 +11,7 @@ With --kf-select (off by default; needs mapping) the keyframe stage runs on the 
 frame plays the keyframe when FrameHandlerMono::needNewKf says so instead of every fifth, and the JSON line lists the keyframe frames.
 With --map-candidates (off by default) reprojection and matching take their candidates from the map-candidate stage (plsvo_candidates_*):
 the overlap keyframes' features, one visit per landmark, the closest-view observation as the reference patch.
-usage: python tools/run_sequence.py [--distortion k1,k2,p1,p2[,k3]] [--detect] [--kf-select] [--map-candidates] [--cell-select] [--kf-insert] [out.txt] [n_frames] [seed] [mapping 0|1]"""
+usage: python tools/run_sequence.py [--distortion k1,k2,p1,p2[,k3]] [--detect] [--kf-select] [--map-candidates] [--cell-select] [--kf-insert] [--seed-candidates] [out.txt] [n_frames] [seed] [mapping 0|1]"""
 import importlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -42,6 +42,9 @@ if cell_select:
 kf_insert = "--kf-insert" in argv                  # with --cell-select and mapping: keyframes are inserted into the resident tables, not staged anew
 if kf_insert:
     argv.remove("--kf-insert")
+seed_candidates = "--seed-candidates" in argv      # with --kf-insert: a converged seed is appended to the resident tables (plsvo_candidates_add), not staged
+if seed_candidates:
+    argv.remove("--seed-candidates")
 sys.argv = sys.argv[:1] + argv
 
 out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "gpurun_out", "trajectory.txt")
@@ -56,7 +59,8 @@ if distortion is not None:
     fx, fy, cx, cy, w, h = seq["cam"]
     seq = dict(seq, images=[P.synth.distort_image(img, dict(fx=fx, fy=fy, cx=cx, cy=cy, d=distortion)) for img in seq["images"]])
     rectify = P.abi.pinhole_radtan(w, h, fx, fy, cx, cy, distortion)
-res = seqm.run_sequence(seqm.HipBackend(ctx, rectify=rectify), seq, mapping=mapping, detect=detect, kf_select=kf_select, map_candidates=map_candidates, cell_select=cell_select, kf_insert=kf_insert)
+res = seqm.run_sequence(seqm.HipBackend(ctx, rectify=rectify), seq, mapping=mapping, detect=detect, kf_select=kf_select, map_candidates=map_candidates, cell_select=cell_select, kf_insert=kf_insert,
+                        seed_candidates=seed_candidates)
 n = P.trajectory.write_trajectory(out, ["%.6f" % (0.05 * k) for k in range(n_frames)], [r["T"] for r in res], [r["cov"] for r in res])
 err = seqm.pose_errors(res, seq)
 print(json.dumps({"frames": n_frames, "lines_written": n, "trajectory": out, "max_rot_err_rad": max(e[0] for e in err),
@@ -65,5 +69,7 @@ print(json.dumps({"frames": n_frames, "lines_written": n, "trajectory": out, "ma
                   "seeds_first_last": [res[1].get("n_seeds"), res[-1].get("n_seeds")],
                   **({"image_seeds_last": res[-1].get("n_image_seeds"), "image_seeds_converged": res[-1].get("n_image_seeds_converged")} if detect else {}),
                   **({"keyframes": [k for k, r in enumerate(res) if r.get("is_kf")], "overlap_last": res[-1].get("n_overlap"),
-                      "depth_mean_last": res[-1].get("depth_mean")} if kf_select else {})}))
+                      "depth_mean_last": res[-1].get("depth_mean")} if kf_select else {}),
+                  **({"seed_candidates_per_frame": [r.get("n_seed_candidates", 0) for r in res[1:]],
+                      "seed_candidates_mean": sum(r.get("n_seed_candidates", 0) for r in res[1:]) / max(len(res) - 1, 1)} if seed_candidates else {})}))
 ctx.close()

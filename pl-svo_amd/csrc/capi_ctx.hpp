@@ -1,0 +1,300 @@
+// capi_ctx.hpp -- what the translation units of the C ABI (plsvo_capi.hip, capi_candidates.hip) share: the kernels' launch functions, the
+// device buffer / staging helpers, the context, the error macros.  Internal: no part of include/plsvo_hip.h, hidden from the dynamic symbol table.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/plsvo_hip.h"
+#include "plsvo_dev.hpp"
+
+#define PLSVO_LOCAL __attribute__((visibility("hidden")))
+
+namespace plsvo_hip {
+// kernels (align_kernels.hip, poseopt_kernels.hip, pyramid_kernels.hip)
+size_t align_level_lds_bytes(int threads, int cap, int scap, int chi_lds_pts);
+hipError_t launch_align_reorder(const int* work_key, int n, int* order_out, int shift, hipStream_t stream);   // (the pose optimiser's batches use it too)
+hipError_t launch_align_levels(const AlignBatchDev& b, int cap, int scap, int level_hi, int level_lo, int do_init, int threads, size_t lds,
+                               hipStream_t stream);
+hipError_t launch_pose_opt(const PoseBatchDev& b, double* d_poses, int threads, int select, hipStream_t stream);
+hipError_t launch_structopt(const StructBatchDev& s, hipStream_t stream);
+hipError_t launch_match_direct(const MatchBatchDev& b, hipStream_t stream);
+hipError_t launch_match_warp_patches(const MatchBatchDev& b, hipStream_t stream);
+hipError_t launch_reproject(const ReprojBatchDev& b, hipStream_t stream);
+hipError_t launch_update_seeds(const SeedsBatchDev& b, hipStream_t stream);
+hipError_t launch_close_keyframes(const CloseKfBatchDev& b, hipStream_t stream);     // keyframe_device.hpp, in seeds_kernels.hip
+hipError_t launch_keyframe_decide(const KfDecideBatchDev& b, hipStream_t stream);
+hipError_t launch_map_candidates(const CandBatchDev& b, hipStream_t stream);         // candidates_device.hpp, in seeds_kernels.hip
+hipError_t launch_map_select(const SelectBatchDev& b, hipStream_t stream);            // select_device.hpp, in seeds_kernels.hip
+hipError_t launch_map_insert_plan(const InsertBatchDev& b, hipStream_t stream);       // insert_device.hpp, in seeds_kernels.hip
+hipError_t launch_map_insert(const InsertBatchDev& b, hipStream_t stream);
+hipError_t launch_map_set_positions(const PositionsBatchDev& b, hipStream_t stream);
+hipError_t launch_map_add_candidates(const NewCandBatchDev& b, hipStream_t stream);   // newcand_device.hpp, in seeds_kernels.hip
+hipError_t launch_halfsample(const uint8_t* src, size_t src_pitch, int in_w, int in_h, int in_stride, uint8_t* dst,
+                             size_t dst_pitch, int n_slots, int rounding, hipStream_t stream);
+hipError_t launch_copy_level0(const uint8_t* src, size_t src_pitch, int w, int h, int stride, uint8_t* dst, size_t dst_pitch,
+                              int n_slots, hipStream_t stream);
+hipError_t launch_chain_pose(const ChainBatchDev& b, hipStream_t stream);
+hipError_t launch_pack_pose_records(const AlignStateDev* ast, const PoseStateDev* pst, int n, plsvo_pose_record* dst, hipStream_t stream);
+hipError_t launch_chain_active(const ChainBatchDev& b, hipStream_t stream);
+hipError_t launch_chain_select(const ChainBatchDev& b, hipStream_t stream);
+hipError_t launch_tile_level(const uint8_t* src, size_t src_pitch, int w, int h, uint8_t* dst, size_t dst_pitch, int n_slots, hipStream_t stream);
+hipError_t launch_rectify(const uint8_t* raw, size_t raw_pitch, int stride, int flip, const uint32_t* map, int w, int h, uint8_t* dst,
+                          size_t dst_pitch, int n_slots, hipStream_t stream);
+hipError_t launch_detect_fast(const DetectLaunch& a, int n_slots, hipStream_t stream);
+hipError_t launch_detect_stages(const DetectLaunch& a, hipStream_t stream);
+hipError_t launch_detect_compact(unsigned long long* keys, int n_cells, plsvo_corner* corners, int32_t* counts, int n_slots, hipStream_t stream);
+}  // namespace plsvo_hip
+
+using namespace plsvo_hip;
+
+struct PLSVO_LOCAL DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  hipError_t ensure(size_t bytes) {
+    if (bytes <= cap) return hipSuccess;
+    if (p) { hipError_t e = hipFree(p); p = nullptr; cap = 0; if (e != hipSuccess) return e; }
+    size_t want = std::max(bytes, (size_t)256);
+    hipError_t e = hipMalloc(&p, want);
+    if (e == hipSuccess) cap = want;
+    return e;
+  }
+  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+  template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+struct PLSVO_LOCAL EventPair { hipEvent_t a, b; };
+
+// All input arrays of a staged batch travel as ONE host-to-device copy: sections of a single blob, each 256-byte aligned.
+// (A single-frame call used to pay a dozen small pageable copies; small blobs go through a pinned staging buffer.)
+struct PLSVO_LOCAL Blob {
+  std::vector<uint8_t> host;
+  template <typename T> size_t add(const std::vector<T>& v) {
+    const size_t off = (host.size() + 255) & ~(size_t)255;
+    host.resize(off + std::max(v.size() * sizeof(T), (size_t)16));
+    if (!v.empty()) memcpy(host.data() + off, v.data(), v.size() * sizeof(T));
+    return off;
+  }
+  // a section of n elements to be filled in place: take the pointers (at<T>) only after the LAST reserve / add, which may move the blob
+  template <typename T> size_t reserve(size_t n) {
+    const size_t off = (host.size() + 255) & ~(size_t)255;
+    host.resize(off + std::max(n * sizeof(T), (size_t)16));
+    return off;
+  }
+  template <typename T> T* at(size_t off) { return reinterpret_cast<T*>(host.data() + off); }
+};
+
+// carve typed arrays out of one device allocation (256-byte aligned sections)
+struct PLSVO_LOCAL Carver {
+  size_t off = 0;
+  template <typename T> size_t take(size_t n) { const size_t o = (off + 255) & ~(size_t)255; off = o + std::max(n, (size_t)1) * sizeof(T); return o; }
+};
+
+struct PLSVO_LOCAL CandStreamHost {      // map candidates: one stream's host mirror of the resident tables' sizes
+  int cap_kf, cap_kf_pt, cap_kf_seg, cap_pt_obs, cap_seg_obs;   // capacities the layout was made with: keyframes, features per kind, observations per kind
+  int n_kf_pt, n_kf_seg, n_pt_obs, n_seg_obs;                   // used sizes of the last four
+  int rows_pt, rows_seg, rows_pt_cand, rows_seg_cand;           // landmark rows and candidate-list rows the layout was made with
+  int fetch_pt_cand, fetch_seg_cand;                            // candidate counts a run's fetch reports (an add does not move them)
+};
+struct PLSVO_LOCAL CandFetchSections {   // ... and where each fetched array starts in cd_d_work, in carve order
+  size_t counts, pt_lm, pt_px, pt_cell, pt_obs, pt_view, pt_active, seg_lm, seg_px, seg_cell, seg_obs, seg_view, seg_active, pt_cand_failed, seg_cand_failed;
+};
+
+// The pose optimiser's device work set, one per caller of launch_pose_opt: the staged batch (p_w), the frame step (ch_w), the map candidates (cs_w)
+struct PLSVO_LOCAL PoseWork {
+  DevBuf state, ptkeep, segkeep, s32, s64, poses;
+  int ensure(plsvo_ctx* c, size_t n_jobs, size_t n_pt, size_t n_seg);   // room for a batch of n_jobs frames over n_pt points and n_seg segments
+  void bind(PoseBatchDev& b) const {
+    b.state = state.as<PoseStateDev>(); b.pt_keep = ptkeep.as<uint8_t>(); b.seg_keep = segkeep.as<uint8_t>();
+    b.scratch_f32 = s32.as<float>(); b.scratch_f64 = s64.as<double>();
+  }
+  template <typename B> void bind_resident(PoseBatchDev& q, const B& b, int n) const {   // jobs and features written on the device: ChainBatchDev, SelectBatchDev
+    q = PoseBatchDev{}; bind(q); q.jobs = b.po_jobs; q.n_jobs = n;
+    q.pt_f = b.pt_f; q.pt_pos = b.pt_pos; q.pt_level = b.pt_level; q.seg_line = b.seg_line; q.seg_spos = b.seg_spos; q.seg_epos = b.seg_epos; q.seg_level = b.seg_level;
+  }
+  void release() { for (DevBuf* b : { &state, &ptkeep, &segkeep, &s32, &s64, &poses }) b->release(); }
+};
+
+struct plsvo_ctx {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  std::string err;
+  int cu_count = 0;
+  size_t lds_per_block = 65536;
+  // experiment switches, read from the environment ONCE, at plsvo_hip_create (never on a launch path)
+  int env_align_threads = 0, env_align_lds_pad = 0, env_poseopt_threads = 0;
+  bool env_align_per_level = false, env_align_no_lpt = false, env_host_timing = false;
+  int ldlt_flavour = 320;   // plsvo_hip_set_option(PLSVO_OPT_LDLT_FLAVOUR)
+
+  // pyramids (row-major slab: half-sampler, matcher, depth filter, download) and their tiled mirror (alignment kernel)
+  DevBuf pyr_tiled;
+  DevBuf pyr_slab;
+  PyrDesc pyr{};
+  DevBuf pyr_upload;  // staging for level-0 uploads
+  // rectification maps (plsvo_hip_config_rectify): packed words of pyramid_kernels.hip::rectify_kernel, one map per camera
+  struct RectifyMap { DevBuf map; int w = 0, h = 0; bool identity = false, flip = false; };
+  RectifyMap rect[PLSVO_MAX_RECTIFY_MAPS];
+  int rect_n = 0;
+  // corner detection (plsvo_hip_detect_fast*): one 64-bit key per (slot, cell), 0 between calls (detect_device.hpp); staging of the host form
+  DevBuf det_keys, det_occ, det_corners, det_counts, det_stage;
+
+  // alignment batch
+  int a_n = 0;
+  bool a_staged = false;
+  std::vector<AlignJobDev> a_jobs;
+  std::vector<int> a_nseg_off;  // per job seg offset (host copy)
+  int a_total_seg = 0;
+  int a_gmax = -1, a_gmin = 99;
+  int a_cap[PLSVO_MAX_LEVELS]{};
+  int a_scap = 4;   // max segments of one job
+  int a_trace_cap = 0;
+  DevBuf a_d_state, a_d_alive;   // (inputs: a_d_blob)
+  DevBuf a_d_pxyz, a_d_puv, a_d_cref, a_d_chi, a_d_log, a_d_poses;
+  size_t a_patch_total = 0;                 // patch slots of the staged batch (all jobs, all levels' maximum)
+  int a_seg_align = 32;                     // the staged layout's segment alignment (64: two workgroups per frame are possible)
+  DevBuf a_d_workkey;                       // per job: the patch-iterations its last launch evaluated
+  DevBuf a_d_order[2];                      // launch order of a RE-RUN resident batch: sorted on the device by the last launch's measured work
+  int a_order_next = 0;                     //   (align_kernels.hip::align_reorder_kernel); the buffer the next reorder writes
+  bool env_align_no_reorder = false;
+  const int* a_stage_order = nullptr;          // the staged batch's own order (most patches first), inside a_d_blob
+  bool a_one_shot = false, p_one_shot = false;   // set around the run of a one-shot batch call: its launch order is never consumed
+  int env_align_reorder_min = 0;            //   PLSVO_ALIGN_REORDER_MIN: smallest batch that is re-ordered (tests; default 16 frames per CU)
+  // tail split of the one-wave-per-frame alignment launch (align_kernels.hip): PLSVO_OPT_ALIGN_TAIL_SPLIT, and for tests and measurements
+  // PLSVO_ALIGN_TAIL_MIN (smallest batch that is split; default four times the resident workgroups), PLSVO_ALIGN_TAIL_K (tail set in
+  // multiples of the resident workgroups; default 2), PLSVO_ALIGN_TAIL_FRAMES (the tail set itself, in frames)
+  bool opt_align_tail_split = true;
+  int env_align_tail_min = 0, env_align_tail_k = 0, env_align_tail_frames = 0;
+  DevBuf a_d_tailflag;                      //   one flag word per tail frame, zeroed before every launch
+  DevBuf a_d_alive_tail;                    //   the coarse parts' working copy of the segment flags
+  DevBuf a_d_xbuf;                          // two workgroups per frame: their exchange granules (2 KB per frame, zeroed once)
+  unsigned int x_launch = 0;                // launches that used it (tags = launch << 10 | exchange: never repeated)
+  bool env_align_no_pair = false;
+  AlignBatchDev a_b{};
+
+  // pose-opt batch
+  int p_n = 0;
+  bool p_staged = false;
+  std::vector<PoseJobDev> p_jobs;
+  int p_total_pt = 0, p_total_seg = 0;
+  int p_trace_cap = 0;
+  PoseWork p_w;                             // (inputs: p_d_blob)
+  DevBuf p_d_log;
+  PoseBatchDev p_b{};
+  DevBuf p_d_workkey, p_d_order[2];         // as a_d_workkey / a_d_order: the launch order of a re-run staged batch, from its last launch's feature-iterations
+  int p_order_next = 0, p_key_shift = 0;
+  bool env_poseopt_no_reorder = false;
+  int env_poseopt_reorder_min = 0;          //   PLSVO_POSEOPT_REORDER_MIN (tests)
+  // row refill of the row shape's Gauss-Newton loop (poseopt_kernels.hip: three launches): PLSVO_OPT_POSEOPT_REFILL, and for tests and
+  // measurements PLSVO_POSEOPT_REFILL_MIN (smallest batch that takes it, in frames; default: more than two frames per resident row) and
+  // PLSVO_POSEOPT_REFILL_WAVES (workgroups of the persistent kernel; default: the resident ones)
+  bool opt_poseopt_refill = true;
+  int env_poseopt_refill_min = 0, env_poseopt_refill_waves = 0;
+  // medians of the row kernels (poseopt_select.hpp): values once into registers, rank finish -- PLSVO_OPT_POSEOPT_SELECT; false = row_radix_select everywhere
+  bool opt_poseopt_select = true;
+  bool p_any_ref = false;                   //   a job of the staged batch has a refinement loop (n_iter_ref > 0): pose_opt_rows_kernel
+  int p_refill_frames = 0;                  //   frames the last pose-optimiser launch ran through the three launches
+  DevBuf p_d_carry, p_d_refill_next;        //   PoseRefillCarry per job; the queue's counter
+
+  // resident frame step (plsvo_chain_*): candidates, glue state, pose-optimiser input written on the device
+  bool ch_staged = false;
+  int ch_n = 0, ch_ncand = 0, ch_npt_cap = 0, ch_nseg_cap = 0;
+  std::vector<ChainJobDev> ch_jobs;
+  DevBuf ch_d_blob, ch_d_work, ch_d_po;
+  ChainBatchDev ch_b{};
+  MatchBatchDev ch_match{};
+  ReprojBatchDev ch_reproj{};
+  PoseBatchDev ch_pose{};
+  PoseWork ch_w;
+  DevBuf rec_d;   // plsvo_fetch_pose_records
+  // map candidates (plsvo_candidates_*): the staged tables (cd_d_blob), results / scratch / the matcher's arrays (cd_d_work), a run's frames
+  bool cd_staged = false, cd_ran = false, cd_matched = false;
+  int cd_n = 0, cd_max_level = 0;
+  std::vector<CandMapDev> cd_maps;
+  std::vector<int> cd_kf_slot, cd_cur_slot;
+  std::vector<int64_t> cd_m_off, cd_f_off;
+  std::vector<long long> cd_ov_off;         // per stream of the last run: where its overlap list starts (n + 1 entries)
+  CandFetchSections cd_off{};               // sections of the fetched part of cd_d_work
+  size_t cd_fetch_bytes = 0, cd_vis_off = 0, cd_vis_bytes = 0, cd_total_m = 0, cd_total_f = 0;
+  plsvo_cand_params cd_params{};
+  DevBuf cd_d_blob, cd_d_work, cd_d_run, cd_d_kfcount;
+  CandBatchDev cd_b{};
+  MatchBatchDev cd_match{};
+  // their cell selection (plsvo_candidates_select ..): the resident landmark quality (cs_d_q: counters, then the event bytes), the
+  // launch's scratch, the features and the pose optimiser's input (cs_d_work), the visit orders of the two grids (cs_d_order)
+  bool cs_selected = false, cs_posed = false;
+  size_t cd_t_pt = 0, cd_t_seg = 0, cd_t_ptc = 0, cd_t_segc = 0, cd_t_opt = 0, cd_t_oseg = 0;
+  std::vector<int> cs_order;                // what cs_d_order holds: order, positions, for the points' grid and the segments'
+  DevBuf cs_d_q, cs_d_work, cs_d_order;
+  PoseWork cs_w;
+  SelectBatchDev cs_b{};
+  PoseBatchDev cs_pose{};
+  // keyframe insertion (plsvo_candidates_insert_keyframe ..): the room plsvo_candidates_reserve asks for (ci_reserve: the next stage's),
+  // per stream its capacities and used sizes (cd_host), the capacity totals, the last insertion's report; scratch and staging rows
+  // (ci_d_work), a call's records and host masks (ci_d_in)
+  plsvo_cand_reserve ci_reserve{};
+  std::vector<CandStreamHost> cd_host;
+  size_t ci_t_kf = 0, ci_t_kfpt = 0, ci_t_kfseg = 0, ci_t_ptobs = 0, ci_t_segobs = 0, cd_blob_bytes = 0;
+  bool ci_inserted = false, ci_have_out = false;
+  std::vector<InsertPlanDev> ci_last;
+  DevBuf ci_d_work, ci_d_in, ci_d_plan, ci_d_pos;
+  // new candidate landmarks (plsvo_candidates_add ..): the landmark room plsvo_candidates_reserve_landmarks asks for (cn_reserve: the next
+  // stage's), per stream the rows its layout was made with and the candidate counts a run's fetch reports (cd_host), whether an add
+  // closed the open run, the last report
+  plsvo_cand_lm_reserve cn_reserve{};
+  bool cn_closed = false, cn_have_out = false;
+  std::vector<plsvo_cand_add_out> cn_last;
+  DevBuf cn_d_in;
+  unsigned long long run_seq = 0, a_run_seq = 0, p_run_seq = 0, ch_run_seq = 0;   // which resident batch ran last, 0 = not since it was staged (plsvo_pack_pose_records)
+
+  // structure optimisation (one-shot batches)
+  DevBuf s_d_in, s_d_out;
+
+  // staging: one blob per batch type (Blob), pinned bounce buffer for small ones
+  DevBuf a_d_blob, p_d_blob;
+  // pinned bounce buffers of the stage calls: two, used in turn, each guarded by an event recorded behind its last DMA
+  void* pinned[2] = { nullptr, nullptr };
+  size_t pinned_cap[2] = { 0, 0 };
+  hipEvent_t pinned_done[2] = { nullptr, nullptr };
+  int pinned_next = 0;
+  // the same for whole pyramids (plsvo_hip_upload_pyramid packs a frame's levels into one pinned image of its slot: ONE DMA, no wait)
+  void* pyr_pinned[2] = { nullptr, nullptr };
+  size_t pyr_pinned_cap[2] = { 0, 0 };
+  hipEvent_t pyr_pinned_done[2] = { nullptr, nullptr };
+  int pyr_pinned_next = 0;
+  // slots whose TILED mirror is stale: an uploaded pyramid is re-tiled only when a launch that reads the mirror (the one-wave-per-frame
+  // shape of the alignment) is about to use it -- a per-frame caller never pays the four tile launches
+  std::vector<uint8_t> tiled_stale;
+  int tiled_stale_count = 0;
+  // results of a fetch come back through a pinned buffer (device-to-PAGEABLE copies are staged and waited for one by one by the driver)
+  void* dl_pinned = nullptr;
+  size_t dl_pinned_cap = 0;
+
+  // profiling
+  bool profiling = false;
+  std::vector<EventPair> ev[PLSVO_K_COUNT];
+  std::vector<EventPair> ev_pool;
+  double ev_ms[PLSVO_K_COUNT]{};
+  int64_t ev_launches[PLSVO_K_COUNT]{};
+};
+
+#define CTX_CHECK(ctx) do { if (!(ctx)) return PLSVO_E_INVALID; } while (0)
+#define HIP_TRY(ctx, expr)                                                                      \
+  do {                                                                                          \
+    hipError_t e__ = (expr);                                                                    \
+    if (e__ != hipSuccess) {                                                                    \
+      (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e__);                          \
+      return PLSVO_E_HIP;                                                                       \
+    }                                                                                           \
+  } while (0)
+static inline int fail(plsvo_ctx* ctx, int code, const std::string& msg) { ctx->err = msg; return code; }
+
+PLSVO_LOCAL void prof_begin(plsvo_ctx* c, int k, EventPair* ep);   // helpers both units use, defined in plsvo_capi.hip
+PLSVO_LOCAL void prof_end(plsvo_ctx* c, int k, EventPair* ep);
+PLSVO_LOCAL int download_ranges(plsvo_ctx* c, int n_ranges, const void* const* src, const size_t* bytes, std::vector<uint8_t>& fallback, const uint8_t** h);
+PLSVO_LOCAL int upload_blob(plsvo_ctx* c, DevBuf& buf, const Blob& blob);
+PLSVO_LOCAL int pose_opt_threads(const plsvo_ctx* c, int n, long feats);
+PLSVO_LOCAL void pose_state_to_out(const PoseStateDev& s, plsvo_poseopt_out& o);   // everything but the keep masks, whose two pointers it leaves as they are

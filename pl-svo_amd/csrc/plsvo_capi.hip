@@ -2,289 +2,30 @@
 // Host side only: context, HBM buffers, staging of flattened features, kernel launches, result fetch,
 // hipEvent timing, RCCL gather.  All device work is enqueued on the ctx stream; nothing here computes
 // any part of the hot path on the CPU (there is no fallback).
-#include <hip/hip_runtime.h>
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
-#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
 
-#include "../../include/plsvo_hip.h"
-#include "plsvo_dev.hpp"
+#include "capi_ctx.hpp"
 #include "plsvo_math.hpp"
 #include "poseopt_refill.hpp"
 #include "poseopt_select.hpp"
 
-namespace plsvo_hip {
-// kernels (align_kernels.hip, poseopt_kernels.hip, pyramid_kernels.hip)
-size_t align_level_lds_bytes(int threads, int cap, int scap, int chi_lds_pts);
-hipError_t launch_align_reorder(const int* work_key, int n, int* order_out, int shift, hipStream_t stream);   // (the pose optimiser's batches use it too)
-hipError_t launch_align_levels(const AlignBatchDev& b, int cap, int scap, int level_hi, int level_lo, int do_init, int threads, size_t lds,
-                               hipStream_t stream);
-hipError_t launch_pose_opt(const PoseBatchDev& b, double* d_poses, int threads, int select, hipStream_t stream);
-hipError_t launch_structopt(const StructBatchDev& s, hipStream_t stream);
-hipError_t launch_match_direct(const MatchBatchDev& b, hipStream_t stream);
-hipError_t launch_match_warp_patches(const MatchBatchDev& b, hipStream_t stream);
-hipError_t launch_reproject(const ReprojBatchDev& b, hipStream_t stream);
-hipError_t launch_update_seeds(const SeedsBatchDev& b, hipStream_t stream);
-hipError_t launch_close_keyframes(const CloseKfBatchDev& b, hipStream_t stream);     // keyframe_device.hpp, in seeds_kernels.hip
-hipError_t launch_keyframe_decide(const KfDecideBatchDev& b, hipStream_t stream);
-hipError_t launch_map_candidates(const CandBatchDev& b, hipStream_t stream);         // candidates_device.hpp, in seeds_kernels.hip
-hipError_t launch_map_select(const SelectBatchDev& b, hipStream_t stream);            // select_device.hpp, in seeds_kernels.hip
-hipError_t launch_map_insert_plan(const InsertBatchDev& b, hipStream_t stream);       // insert_device.hpp, in seeds_kernels.hip
-hipError_t launch_map_insert(const InsertBatchDev& b, hipStream_t stream);
-hipError_t launch_map_set_positions(const PositionsBatchDev& b, hipStream_t stream);
-hipError_t launch_map_add_candidates(const NewCandBatchDev& b, hipStream_t stream);   // newcand_device.hpp, in seeds_kernels.hip
-hipError_t launch_halfsample(const uint8_t* src, size_t src_pitch, int in_w, int in_h, int in_stride, uint8_t* dst,
-                             size_t dst_pitch, int n_slots, int rounding, hipStream_t stream);
-hipError_t launch_copy_level0(const uint8_t* src, size_t src_pitch, int w, int h, int stride, uint8_t* dst, size_t dst_pitch,
-                              int n_slots, hipStream_t stream);
-hipError_t launch_chain_pose(const ChainBatchDev& b, hipStream_t stream);
-hipError_t launch_pack_pose_records(const AlignStateDev* ast, const PoseStateDev* pst, int n, plsvo_pose_record* dst, hipStream_t stream);
-hipError_t launch_chain_active(const ChainBatchDev& b, hipStream_t stream);
-hipError_t launch_chain_select(const ChainBatchDev& b, hipStream_t stream);
-hipError_t launch_tile_level(const uint8_t* src, size_t src_pitch, int w, int h, uint8_t* dst, size_t dst_pitch, int n_slots, hipStream_t stream);
-hipError_t launch_rectify(const uint8_t* raw, size_t raw_pitch, int stride, int flip, const uint32_t* map, int w, int h, uint8_t* dst,
-                          size_t dst_pitch, int n_slots, hipStream_t stream);
-hipError_t launch_detect_fast(const DetectLaunch& a, int n_slots, hipStream_t stream);
-hipError_t launch_detect_stages(const DetectLaunch& a, hipStream_t stream);
-hipError_t launch_detect_compact(unsigned long long* keys, int n_cells, plsvo_corner* corners, int32_t* counts, int n_slots, hipStream_t stream);
-}  // namespace plsvo_hip
-
-using namespace plsvo_hip;
-
 static thread_local std::string g_create_error;
 
-namespace {
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) { hipError_t e = hipFree(p); p = nullptr; cap = 0; if (e != hipSuccess) return e; }
-    size_t want = std::max(bytes, (size_t)256);
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-  template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
-};
-
-struct EventPair { hipEvent_t a, b; };
-
-// All input arrays of a staged batch travel as ONE host-to-device copy: sections of a single blob, each 256-byte aligned.
-// (A single-frame call used to pay a dozen small pageable copies; small blobs go through a pinned staging buffer.)
-struct Blob {
-  std::vector<uint8_t> host;
-  template <typename T> size_t add(const std::vector<T>& v) {
-    const size_t off = (host.size() + 255) & ~(size_t)255;
-    host.resize(off + std::max(v.size() * sizeof(T), (size_t)16));
-    if (!v.empty()) memcpy(host.data() + off, v.data(), v.size() * sizeof(T));
-    return off;
-  }
-  // a section of n elements to be filled in place: take the pointers (at<T>) only after the LAST reserve / add, which may move the blob
-  template <typename T> size_t reserve(size_t n) {
-    const size_t off = (host.size() + 255) & ~(size_t)255;
-    host.resize(off + std::max(n * sizeof(T), (size_t)16));
-    return off;
-  }
-  template <typename T> T* at(size_t off) { return reinterpret_cast<T*>(host.data() + off); }
-};
-
-}  // namespace
-
-struct plsvo_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  std::string err;
-  int cu_count = 0;
-  size_t lds_per_block = 65536;
-  // experiment switches, read from the environment ONCE, at plsvo_hip_create (never on a launch path)
-  int env_align_threads = 0, env_align_lds_pad = 0, env_poseopt_threads = 0;
-  bool env_align_per_level = false, env_align_no_lpt = false, env_host_timing = false;
-  int ldlt_flavour = 320;   // plsvo_hip_set_option(PLSVO_OPT_LDLT_FLAVOUR)
-
-  // pyramids (row-major slab: half-sampler, matcher, depth filter, download) and their tiled mirror (alignment kernel)
-  DevBuf pyr_tiled;
-  DevBuf pyr_slab;
-  PyrDesc pyr{};
-  DevBuf pyr_upload;  // staging for level-0 uploads
-  // rectification maps (plsvo_hip_config_rectify): packed words of pyramid_kernels.hip::rectify_kernel, one map per camera
-  struct RectifyMap { DevBuf map; int w = 0, h = 0; bool identity = false, flip = false; };
-  RectifyMap rect[PLSVO_MAX_RECTIFY_MAPS];
-  int rect_n = 0;
-  // corner detection (plsvo_hip_detect_fast*): one 64-bit key per (slot, cell), 0 between calls (detect_device.hpp); staging of the host form
-  DevBuf det_keys, det_occ, det_corners, det_counts, det_stage;
-
-  // alignment batch
-  int a_n = 0;
-  bool a_staged = false;
-  std::vector<AlignJobDev> a_jobs;
-  std::vector<int> a_nseg_off;  // per job seg offset (host copy)
-  int a_total_seg = 0;
-  int a_gmax = -1, a_gmin = 99;
-  int a_cap[PLSVO_MAX_LEVELS]{};
-  int a_scap = 4;   // max segments of one job
-  int a_trace_cap = 0;
-  DevBuf a_d_state, a_d_alive;   // (inputs: a_d_blob)
-  DevBuf a_d_pxyz, a_d_puv, a_d_cref, a_d_chi, a_d_log, a_d_poses;
-  size_t a_patch_total = 0;                 // patch slots of the staged batch (all jobs, all levels' maximum)
-  int a_seg_align = 32;                     // the staged layout's segment alignment (64: two workgroups per frame are possible)
-  DevBuf a_d_workkey;                       // per job: the patch-iterations its last launch evaluated
-  DevBuf a_d_order[2];                      // launch order of a RE-RUN resident batch: sorted on the device by the last launch's measured work
-  int a_order_next = 0;                     //   (align_kernels.hip::align_reorder_kernel); the buffer the next reorder writes
-  bool env_align_no_reorder = false;
-  const int* a_stage_order = nullptr;          // the staged batch's own order (most patches first), inside a_d_blob
-  bool a_one_shot = false, p_one_shot = false;   // set around the run of a one-shot batch call: its launch order is never consumed
-  int env_align_reorder_min = 0;            //   PLSVO_ALIGN_REORDER_MIN: smallest batch that is re-ordered (tests; default 16 frames per CU)
-  // tail split of the one-wave-per-frame alignment launch (align_kernels.hip): PLSVO_OPT_ALIGN_TAIL_SPLIT, and for tests and measurements
-  // PLSVO_ALIGN_TAIL_MIN (smallest batch that is split; default four times the resident workgroups), PLSVO_ALIGN_TAIL_K (tail set in
-  // multiples of the resident workgroups; default 2), PLSVO_ALIGN_TAIL_FRAMES (the tail set itself, in frames)
-  bool opt_align_tail_split = true;
-  int env_align_tail_min = 0, env_align_tail_k = 0, env_align_tail_frames = 0;
-  DevBuf a_d_tailflag;                      //   one flag word per tail frame, zeroed before every launch
-  DevBuf a_d_alive_tail;                    //   the coarse parts' working copy of the segment flags
-  DevBuf a_d_xbuf;                          // two workgroups per frame: their exchange granules (2 KB per frame, zeroed once)
-  unsigned int x_launch = 0;                // launches that used it (tags = launch << 10 | exchange: never repeated)
-  bool env_align_no_pair = false;
-  AlignBatchDev a_b{};
-
-  // pose-opt batch
-  int p_n = 0;
-  bool p_staged = false;
-  std::vector<PoseJobDev> p_jobs;
-  int p_total_pt = 0, p_total_seg = 0;
-  int p_trace_cap = 0;
-  DevBuf p_d_state, p_d_ptkeep, p_d_segkeep;   // (inputs: p_d_blob)
-  DevBuf p_d_s32, p_d_s64, p_d_log, p_d_poses;
-  PoseBatchDev p_b{};
-  DevBuf p_d_workkey, p_d_order[2];         // as a_d_workkey / a_d_order: the launch order of a re-run staged batch, from its last launch's feature-iterations
-  int p_order_next = 0, p_key_shift = 0;
-  bool env_poseopt_no_reorder = false;
-  int env_poseopt_reorder_min = 0;          //   PLSVO_POSEOPT_REORDER_MIN (tests)
-  // row refill of the row shape's Gauss-Newton loop (poseopt_kernels.hip: three launches): PLSVO_OPT_POSEOPT_REFILL, and for tests and
-  // measurements PLSVO_POSEOPT_REFILL_MIN (smallest batch that takes it, in frames; default: more than two frames per resident row) and
-  // PLSVO_POSEOPT_REFILL_WAVES (workgroups of the persistent kernel; default: the resident ones)
-  bool opt_poseopt_refill = true;
-  int env_poseopt_refill_min = 0, env_poseopt_refill_waves = 0;
-  // medians of the row kernels (poseopt_select.hpp): values once into registers, rank finish -- PLSVO_OPT_POSEOPT_SELECT; false = row_radix_select everywhere
-  bool opt_poseopt_select = true;
-  bool p_any_ref = false;                   //   a job of the staged batch has a refinement loop (n_iter_ref > 0): pose_opt_rows_kernel
-  int p_refill_frames = 0;                  //   frames the last pose-optimiser launch ran through the three launches
-  DevBuf p_d_carry, p_d_refill_next;        //   PoseRefillCarry per job; the queue's counter
-
-  // resident frame step (plsvo_chain_*): candidates, glue state, pose-optimiser input written on the device
-  bool ch_staged = false;
-  int ch_n = 0, ch_ncand = 0, ch_npt_cap = 0, ch_nseg_cap = 0;
-  std::vector<ChainJobDev> ch_jobs;
-  DevBuf ch_d_blob, ch_d_work, ch_d_po;
-  ChainBatchDev ch_b{};
-  MatchBatchDev ch_match{};
-  ReprojBatchDev ch_reproj{};
-  PoseBatchDev ch_pose{};
-  DevBuf ch_d_state, ch_d_ptkeep, ch_d_segkeep, ch_d_s32, ch_d_s64, ch_d_poses;
-  DevBuf rec_d;   // plsvo_fetch_pose_records
-  // map candidates (plsvo_candidates_*): the staged tables (cd_d_blob), results / scratch / the matcher's arrays (cd_d_work), a run's frames
-  bool cd_staged = false, cd_ran = false, cd_matched = false;
-  int cd_n = 0, cd_max_level = 0;
-  std::vector<CandMapDev> cd_maps;
-  std::vector<int> cd_kf_slot, cd_cur_slot;
-  std::vector<int64_t> cd_m_off, cd_f_off;
-  std::vector<long long> cd_ov_off;         // per stream of the last run: where its overlap list starts (n + 1 entries)
-  std::vector<size_t> cd_off;               // sections of the fetched part of cd_d_work
-  size_t cd_fetch_bytes = 0, cd_vis_off = 0, cd_vis_bytes = 0, cd_total_m = 0, cd_total_f = 0;
-  plsvo_cand_params cd_params{};
-  DevBuf cd_d_blob, cd_d_work, cd_d_run, cd_d_kfcount;
-  CandBatchDev cd_b{};
-  MatchBatchDev cd_match{};
-  // their cell selection (plsvo_candidates_select ..): the resident landmark quality (cs_d_q: counters, then the event bytes), the
-  // launch's scratch, the features and the pose optimiser's input (cs_d_work), the visit orders of the two grids (cs_d_order)
-  bool cs_selected = false, cs_posed = false;
-  size_t cd_t_pt = 0, cd_t_seg = 0, cd_t_ptc = 0, cd_t_segc = 0, cd_t_opt = 0, cd_t_oseg = 0;
-  size_t cs_ev_off = 0, cs_win_bytes = 0;
-  std::vector<int> cs_order;                // what cs_d_order holds: order, positions, for the points' grid and the segments'
-  DevBuf cs_d_q, cs_d_work, cs_d_order, cs_d_state, cs_d_ptkeep, cs_d_segkeep, cs_d_s32, cs_d_s64, cs_d_poses;
-  SelectBatchDev cs_b{};
-  PoseBatchDev cs_pose{};
-  // keyframe insertion (plsvo_candidates_insert_keyframe ..): the room plsvo_candidates_reserve asks for (ci_reserve: the next stage's),
-  // per stream its capacities (ci_cap: keyframes, features per kind, observations per kind) and used sizes (ci_used: the last four),
-  // the capacity totals, the last insertion's report; scratch and staging rows (ci_d_work), a call's records and host masks (ci_d_in)
-  plsvo_cand_reserve ci_reserve{};
-  std::vector<int> ci_cap, ci_used;
-  size_t ci_t_kf = 0, ci_t_kfpt = 0, ci_t_kfseg = 0, ci_t_ptobs = 0, ci_t_segobs = 0, cd_blob_bytes = 0;
-  bool ci_inserted = false, ci_have_out = false;
-  std::vector<InsertPlanDev> ci_last;
-  DevBuf ci_d_work, ci_d_in, ci_d_plan, ci_d_pos;
-  // new candidate landmarks (plsvo_candidates_add ..): the landmark room plsvo_candidates_reserve_landmarks asks for (cn_reserve: the next
-  // stage's), per stream the rows its layout was made with (cn_cap: point rows, segment rows, point candidates, segment candidates), the
-  // candidate counts a run's fetch reports (cd_fetch_cand: an add does not move them), whether an add closed the open run, the last report
-  plsvo_cand_lm_reserve cn_reserve{};
-  std::vector<int> cn_cap, cd_fetch_cand;
-  bool cn_closed = false, cn_have_out = false;
-  std::vector<plsvo_cand_add_out> cn_last;
-  DevBuf cn_d_in;
-  unsigned long long run_seq = 0, a_run_seq = 0, p_run_seq = 0, ch_run_seq = 0;   // which resident batch ran last, 0 = not since it was staged (plsvo_pack_pose_records)
-
-  // structure optimisation (one-shot batches)
-  DevBuf s_d_in, s_d_out;
-
-  // staging: one blob per batch type (Blob), pinned bounce buffer for small ones
-  DevBuf a_d_blob, p_d_blob;
-  // pinned bounce buffers of the stage calls: two, used in turn, each guarded by an event recorded behind its last DMA
-  void* pinned[2] = { nullptr, nullptr };
-  size_t pinned_cap[2] = { 0, 0 };
-  hipEvent_t pinned_done[2] = { nullptr, nullptr };
-  int pinned_next = 0;
-  // the same for whole pyramids (plsvo_hip_upload_pyramid packs a frame's levels into one pinned image of its slot: ONE DMA, no wait)
-  void* pyr_pinned[2] = { nullptr, nullptr };
-  size_t pyr_pinned_cap[2] = { 0, 0 };
-  hipEvent_t pyr_pinned_done[2] = { nullptr, nullptr };
-  int pyr_pinned_next = 0;
-  // slots whose TILED mirror is stale: an uploaded pyramid is re-tiled only when a launch that reads the mirror (the one-wave-per-frame
-  // shape of the alignment) is about to use it -- a per-frame caller never pays the four tile launches
-  std::vector<uint8_t> tiled_stale;
-  int tiled_stale_count = 0;
-  // results of a fetch come back through a pinned buffer (device-to-PAGEABLE copies are staged and waited for one by one by the driver)
-  void* dl_pinned = nullptr;
-  size_t dl_pinned_cap = 0;
-
-  // profiling
-  bool profiling = false;
-  std::vector<EventPair> ev[PLSVO_K_COUNT];
-  std::vector<EventPair> ev_pool;
-  double ev_ms[PLSVO_K_COUNT]{};
-  int64_t ev_launches[PLSVO_K_COUNT]{};
-};
-
-#define CTX_CHECK(ctx) do { if (!(ctx)) return PLSVO_E_INVALID; } while (0)
-#define HIP_TRY(ctx, expr)                                                                      \
-  do {                                                                                          \
-    hipError_t e__ = (expr);                                                                    \
-    if (e__ != hipSuccess) {                                                                    \
-      (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e__);                          \
-      return PLSVO_E_HIP;                                                                       \
-    }                                                                                           \
-  } while (0)
-static int fail(plsvo_ctx* ctx, int code, const std::string& msg) { ctx->err = msg; return code; }
-
 // ---- profiling helpers ----------------------------------------------------------------------
-static void prof_begin(plsvo_ctx* c, int k, EventPair* ep) {
+void prof_begin(plsvo_ctx* c, int k, EventPair* ep) {
   if (!c->profiling) return;
   if (!c->ev_pool.empty()) { *ep = c->ev_pool.back(); c->ev_pool.pop_back(); }
   else { (void)hipEventCreate(&ep->a); (void)hipEventCreate(&ep->b); }
   (void)hipEventRecord(ep->a, c->stream);
   (void)k;
 }
-static void prof_end(plsvo_ctx* c, int k, EventPair* ep) {
+void prof_end(plsvo_ctx* c, int k, EventPair* ep) {
   if (!c->profiling) return;
   (void)hipEventRecord(ep->b, c->stream);
   c->ev[k].push_back(*ep);
@@ -371,14 +112,11 @@ extern "C" void plsvo_hip_destroy(plsvo_ctx* c) {
   for (auto& ep : c->ev_pool) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
   c->a_d_tailflag.release(); c->a_d_alive_tail.release(); c->a_d_xbuf.release(); c->a_d_order[0].release(); c->a_d_order[1].release(); c->a_d_workkey.release(); c->p_d_workkey.release(); c->p_d_order[0].release(); c->p_d_order[1].release();
   c->p_d_carry.release(); c->p_d_refill_next.release();
-  c->cd_d_blob.release(); c->cd_d_work.release(); c->cd_d_run.release(); c->cd_d_kfcount.release();
-  for (DevBuf* b : { &c->ci_d_work, &c->ci_d_in, &c->ci_d_plan, &c->ci_d_pos, &c->cn_d_in }) b->release();
-  for (DevBuf* b : { &c->cs_d_q, &c->cs_d_work, &c->cs_d_order, &c->cs_d_state, &c->cs_d_ptkeep, &c->cs_d_segkeep, &c->cs_d_s32, &c->cs_d_s64, &c->cs_d_poses }) b->release();
-  DevBuf* bufs[] = { &c->pyr_slab, &c->pyr_tiled, &c->pyr_upload, &c->a_d_blob, &c->a_d_state, &c->a_d_alive, &c->a_d_pxyz, &c->a_d_puv, &c->a_d_cref,
-                     &c->a_d_chi, &c->a_d_log, &c->a_d_poses, &c->p_d_blob, &c->p_d_state, &c->p_d_ptkeep, &c->p_d_segkeep, &c->p_d_s32, &c->p_d_s64,
-                     &c->p_d_log, &c->p_d_poses, &c->s_d_in, &c->s_d_out, &c->ch_d_blob, &c->ch_d_work, &c->ch_d_po, &c->ch_d_state,
-                     &c->ch_d_ptkeep, &c->ch_d_segkeep, &c->ch_d_s32, &c->ch_d_s64, &c->ch_d_poses, &c->rec_d };
-  for (DevBuf* b : bufs) b->release();
+  for (DevBuf* b : { &c->cd_d_blob, &c->cd_d_work, &c->cd_d_run, &c->cd_d_kfcount, &c->ci_d_work, &c->ci_d_in, &c->ci_d_plan, &c->ci_d_pos, &c->cn_d_in, &c->cs_d_q,
+                     &c->cs_d_work, &c->cs_d_order, &c->pyr_slab, &c->pyr_tiled, &c->pyr_upload, &c->a_d_blob, &c->a_d_state, &c->a_d_alive, &c->a_d_pxyz, &c->a_d_puv,
+                     &c->a_d_cref, &c->a_d_chi, &c->a_d_log, &c->a_d_poses, &c->p_d_blob, &c->p_d_log, &c->s_d_in, &c->s_d_out, &c->ch_d_blob, &c->ch_d_work,
+                     &c->ch_d_po, &c->rec_d }) b->release();
+  c->p_w.release(); c->ch_w.release(); c->cs_w.release();
   for (auto& r : c->rect) r.map.release();
   c->det_keys.release(); c->det_occ.release(); c->det_corners.release(); c->det_counts.release(); c->det_stage.release();
   for (int k = 0; k < 2; ++k) { if (c->pinned[k]) (void)hipHostFree(c->pinned[k]); if (c->pinned_done[k]) (void)hipEventDestroy(c->pinned_done[k]); }
@@ -1007,7 +745,7 @@ extern "C" int plsvo_align_slot_layout(const plsvo_align_in* in, int level, int3
 // range k's bytes: inside the pinned buffer (valid until the next fetch) or inside `fallback`.
 // (`fallback` is sized HERE whenever the pinned path is not taken -- too large, or no pinned memory to be had -- so the decision and the
 //  storage can never disagree: ADVICE r05)
-static int download_ranges(plsvo_ctx* c, int n_ranges, const void* const* src, const size_t* bytes, std::vector<uint8_t>& fallback, const uint8_t** h) {
+int download_ranges(plsvo_ctx* c, int n_ranges, const void* const* src, const size_t* bytes, std::vector<uint8_t>& fallback, const uint8_t** h) {
   size_t total = 0, off[3] = { 0, 0, 0 };
   for (int k = 0; k < n_ranges; ++k) { off[k] = total; total += (bytes[k] + 63) & ~(size_t)63; }
   bool pinned = total <= ((size_t)4 << 20);
@@ -1029,7 +767,7 @@ static int download_ranges(plsvo_ctx* c, int n_ranges, const void* const* src, c
 }
 
 static const size_t kPinnedMax = (size_t)8 << 20;   // blobs up to 8 MB (hundreds of frames) bounce through pinned memory
-static int upload_blob(plsvo_ctx* c, DevBuf& buf, const Blob& blob) {
+int upload_blob(plsvo_ctx* c, DevBuf& buf, const Blob& blob) {
   const size_t bytes = std::max(blob.host.size(), (size_t)256);
   HIP_TRY(c, buf.ensure(bytes));
   if (blob.host.empty()) return PLSVO_OK;
@@ -1204,7 +942,7 @@ extern "C" int plsvo_align_stage(plsvo_ctx* c, int n, const plsvo_align_in* in) 
 // PLSVO_POSEOPT_REORDER_MIN (its threshold, tests).  A switch set to "0" is off.
 // Threads per frame of a pose-optimiser launch over n frames with `feats` features in all (the crossover is measured below, in
 // plsvo_poseopt_run): shared by plsvo_poseopt_run, plsvo_chain_run and plsvo_candidates_pose_optimize
-static int pose_opt_threads(const plsvo_ctx* c, int n, long feats) {
+int pose_opt_threads(const plsvo_ctx* c, int n, long feats) {
   const int cus = c->cu_count > 0 ? c->cu_count : 256;
   const int threads = n <= 2 * cus ? 256 : (feats <= 580l * n ? 16 : 64);
   return c->env_poseopt_threads ? c->env_poseopt_threads : threads;
@@ -1463,7 +1201,7 @@ extern "C" int plsvo_poseopt_phase_ticks(plsvo_ctx* c, unsigned long long* out8)
   CTX_CHECK(c);
   if (!c->p_staged || !out8) return fail(c, PLSVO_E_STATE, "phase_ticks: no staged batch");
   std::vector<PoseStateDev> st((size_t)c->p_n);
-  HIP_TRY(c, hipMemcpyAsync(st.data(), c->p_d_state.p, (size_t)c->p_n * sizeof(PoseStateDev), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(st.data(), c->p_w.state.p, (size_t)c->p_n * sizeof(PoseStateDev), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   for (int k = 0; k < 8; ++k) { out8[k] = 0; for (auto& s : st) out8[k] += s.phase_ticks[k]; }
   return PLSVO_OK;
@@ -1539,6 +1277,30 @@ extern "C" int plsvo_align_chi2_ties(plsvo_ctx* c, uint64_t* iterations, uint64_
 }
 
 // ---- pose optimisation ---------------------------------------------------------------------------
+// The one sizing of a pose-optimiser work set: each feature count floored at 1, the scratch by the SUM of the two floored counts (the candidates' rule).
+// The staged batch and the frame step sized the scratch by max(n_pt + n_seg, 1), never more than that sum, and the masks as here: no buffer shrinks.
+int PoseWork::ensure(plsvo_ctx* c, size_t n_jobs, size_t n_pt, size_t n_seg) {
+  const size_t np = std::max(n_pt, (size_t)1), ns = std::max(n_seg, (size_t)1), nft = np + ns;
+  HIP_TRY(c, ptkeep.ensure(np));
+  HIP_TRY(c, segkeep.ensure(ns));
+  HIP_TRY(c, s32.ensure(nft * sizeof(float)));
+  HIP_TRY(c, s64.ensure(nft * 5 * sizeof(double)));
+  HIP_TRY(c, state.ensure(n_jobs * sizeof(PoseStateDev)));
+  HIP_TRY(c, poses.ensure(n_jobs * 7 * sizeof(double)));
+  return PLSVO_OK;
+}
+
+void pose_state_to_out(const PoseStateDev& s, plsvo_poseopt_out& o) {
+  uint8_t* const pko = o.pt_keep; uint8_t* const sko = o.seg_keep;   // the caller's buffers: each fetch fills them from its own layout
+  memset(&o, 0, sizeof(o));
+  o.pt_keep = pko; o.seg_keep = sko;
+  for (int k = 0; k < 7; ++k) o.T_f_w[k] = s.T[k];
+  for (int k = 0; k < 36; ++k) o.cov[k] = s.cov[k];
+  o.estimated_scale = s.estimated_scale; o.error_init = s.error_init; o.error_final = s.error_final;
+  o.num_obs_pt = s.num_obs_pt; o.num_obs_ls = s.num_obs_ls;
+  o.iters = s.iters; o.iters_ref = s.iters_ref; o.status = s.status;
+}
+
 extern "C" int plsvo_poseopt_stage(plsvo_ctx* c, int n, const plsvo_poseopt_in* in) {
   CTX_CHECK(c);
   if (n <= 0 || !in) return fail(c, PLSVO_E_INVALID, "poseopt_stage: bad arguments");
@@ -1571,23 +1333,16 @@ extern "C" int plsvo_poseopt_stage(plsvo_ctx* c, int n, const plsvo_poseopt_in* 
   const size_t o_jobs = blob.add(jobs), o_f = blob.add(f), o_pos = blob.add(pos), o_plev = blob.add(plev), o_line = blob.add(line),
                o_spos = blob.add(spos), o_epos = blob.add(epos), o_slev = blob.add(slev);
   if ((rc = upload_blob(c, c->p_d_blob, blob))) return rc;
-  const size_t npt = plev.size(), nsg = slev.size(), nft = std::max(npt + nsg, (size_t)1);
-  HIP_TRY(c, c->p_d_ptkeep.ensure(std::max(npt, (size_t)1)));
-  HIP_TRY(c, c->p_d_segkeep.ensure(std::max(nsg, (size_t)1)));
-  HIP_TRY(c, c->p_d_s32.ensure(nft * sizeof(float)));
-  HIP_TRY(c, c->p_d_s64.ensure(nft * 5 * sizeof(double)));
-  HIP_TRY(c, c->p_d_state.ensure((size_t)n * sizeof(PoseStateDev)));
-  HIP_TRY(c, c->p_d_poses.ensure((size_t)n * 7 * sizeof(double)));
+  const size_t npt = plev.size(), nsg = slev.size();
+  if ((rc = c->p_w.ensure(c, (size_t)n, npt, nsg))) return rc;
   if (c->p_trace_cap > 0) HIP_TRY(c, c->p_d_log.ensure((size_t)n * c->p_trace_cap * sizeof(plsvo_poseopt_iterlog)));
   PoseBatchDev& b = c->p_b;
   uint8_t* const base = c->p_d_blob.as<uint8_t>();
-  b.jobs = reinterpret_cast<const PoseJobDev*>(base + o_jobs); b.state = c->p_d_state.as<PoseStateDev>();
+  b.jobs = reinterpret_cast<const PoseJobDev*>(base + o_jobs); c->p_w.bind(b);
   b.pt_f = reinterpret_cast<const double*>(base + o_f); b.pt_pos = reinterpret_cast<const double*>(base + o_pos);
   b.pt_level = reinterpret_cast<const int*>(base + o_plev);
   b.seg_line = reinterpret_cast<const double*>(base + o_line); b.seg_spos = reinterpret_cast<const double*>(base + o_spos);
   b.seg_epos = reinterpret_cast<const double*>(base + o_epos); b.seg_level = reinterpret_cast<const int*>(base + o_slev);
-  b.pt_keep = c->p_d_ptkeep.as<uint8_t>(); b.seg_keep = c->p_d_segkeep.as<uint8_t>();
-  b.scratch_f32 = c->p_d_s32.as<float>(); b.scratch_f64 = c->p_d_s64.as<double>();
   b.log = c->p_trace_cap > 0 ? c->p_d_log.as<plsvo_poseopt_iterlog>() : nullptr;
   b.log_cap = c->p_trace_cap; b.n_jobs = n;
   b.order = nullptr; b.work_key = nullptr;   // a new batch: no measured work yet (plsvo_poseopt_run)
@@ -1650,10 +1405,10 @@ extern "C" int plsvo_poseopt_run(plsvo_ctx* c) {
     HIP_TRY(c, c->p_d_refill_next.ensure(16));
     HIP_TRY(c, hipMemsetAsync(c->p_d_refill_next.p, 0, 16, c->stream));   // the queue is re-armed ahead of every launch
     const PoseRefillDev q{ c->p_d_carry.as<PoseRefillCarry>(), c->p_d_refill_next.as<int>() };
-    HIP_TRY(c, launch_pose_opt_refill(c->p_b, q, c->p_d_poses.as<double>(), gn_grid, c->opt_poseopt_select ? 1 : 0, c->stream));
+    HIP_TRY(c, launch_pose_opt_refill(c->p_b, q, c->p_w.poses.as<double>(), gn_grid, c->opt_poseopt_select ? 1 : 0, c->stream));
     c->p_refill_frames = c->p_n;
   } else {
-    HIP_TRY(c, launch_pose_opt(c->p_b, c->p_d_poses.as<double>(), threads, c->opt_poseopt_select ? 1 : 0, c->stream));
+    HIP_TRY(c, launch_pose_opt(c->p_b, c->p_w.poses.as<double>(), threads, c->opt_poseopt_select ? 1 : 0, c->stream));
   }
   c->p_run_seq = ++c->run_seq;
   prof_end(c, PLSVO_K_POSEOPT, &ep);
@@ -1674,7 +1429,7 @@ extern "C" int plsvo_poseopt_fetch(plsvo_ctx* c, int n, plsvo_poseopt_out* out) 
   HIP_TRY(c, hipSetDevice(c->device));
   std::vector<uint8_t> big;   // (large batches, or no pinned memory: download_ranges sizes it)
   const size_t rb[3] = { (size_t)n * sizeof(PoseStateDev), (size_t)std::max(c->p_total_pt, 0), (size_t)std::max(c->p_total_seg, 0) };
-  const void* const rs[3] = { c->p_d_state.p, c->p_d_ptkeep.p, c->p_d_segkeep.p };
+  const void* const rs[3] = { c->p_w.state.p, c->p_w.ptkeep.p, c->p_w.segkeep.p };
   const uint8_t* rh[3] = { nullptr, nullptr, nullptr };
   { const int rc_d = download_ranges(c, 3, rs, rb, big, rh); if (rc_d) return rc_d; }
   const PoseStateDev* const st = reinterpret_cast<const PoseStateDev*>(rh[0]);
@@ -1683,16 +1438,9 @@ extern "C" int plsvo_poseopt_fetch(plsvo_ctx* c, int n, plsvo_poseopt_out* out) 
     const PoseStateDev& s = st[(size_t)j];
     const PoseJobDev& J = c->p_jobs[(size_t)j];
     plsvo_poseopt_out& o = out[j];
-    uint8_t* pko = o.pt_keep; uint8_t* sko = o.seg_keep;
-    memset(&o, 0, sizeof(o));
-    o.pt_keep = pko; o.seg_keep = sko;
-    for (int k = 0; k < 7; ++k) o.T_f_w[k] = s.T[k];
-    for (int k = 0; k < 36; ++k) o.cov[k] = s.cov[k];
-    o.estimated_scale = s.estimated_scale; o.error_init = s.error_init; o.error_final = s.error_final;
-    o.num_obs_pt = s.num_obs_pt; o.num_obs_ls = s.num_obs_ls;
-    o.iters = s.iters; o.iters_ref = s.iters_ref; o.status = s.status;
-    if (pko && J.n_pts > 0) memcpy(pko, pk + J.pt_off, (size_t)J.n_pts);
-    if (sko && J.n_seg > 0) memcpy(sko, sk + J.seg_off, (size_t)J.n_seg);
+    pose_state_to_out(s, o);
+    if (o.pt_keep && J.n_pts > 0) memcpy(o.pt_keep, pk + J.pt_off, (size_t)J.n_pts);
+    if (o.seg_keep && J.n_seg > 0) memcpy(o.seg_keep, sk + J.seg_off, (size_t)J.n_seg);
   }
   return PLSVO_OK;
 }
@@ -1775,7 +1523,7 @@ extern "C" int plsvo_poseopt_fetch_trace(plsvo_ctx* c, int job, plsvo_poseopt_it
   if (job < 0 || job >= c->p_n || !out || !n_records) return fail(c, PLSVO_E_INVALID, "fetch_trace: bad arguments");
   HIP_TRY(c, hipSetDevice(c->device));
   PoseStateDev s;
-  HIP_TRY(c, hipMemcpyAsync(&s, c->p_d_state.as<PoseStateDev>() + job, sizeof(s), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&s, c->p_w.state.as<PoseStateDev>() + job, sizeof(s), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   const int nrec = std::min(std::min(s.log_count, c->p_trace_cap), max_records);
   if (nrec > 0) {
@@ -1787,13 +1535,13 @@ extern "C" int plsvo_poseopt_fetch_trace(plsvo_ctx* c, int job, plsvo_poseopt_it
   return PLSVO_OK;
 }
 
-extern "C" const double* plsvo_poseopt_poses_dev(plsvo_ctx* c) { return (c && c->p_staged) ? c->p_d_poses.as<double>() : nullptr; }
+extern "C" const double* plsvo_poseopt_poses_dev(plsvo_ctx* c) { return (c && c->p_staged) ? c->p_w.poses.as<double>() : nullptr; }
 
 extern "C" int plsvo_poseopt_copy_poses(plsvo_ctx* c, double* d_dst) {
   CTX_CHECK(c);
   if (!c->p_staged || !d_dst) return fail(c, PLSVO_E_STATE, "poseopt_copy_poses: no staged batch / null destination");
   HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, hipMemcpyAsync(d_dst, c->p_d_poses.p, (size_t)c->p_n * 7 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(d_dst, c->p_w.poses.p, (size_t)c->p_n * 7 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   return PLSVO_OK;
 }
 
@@ -1802,7 +1550,7 @@ extern "C" int plsvo_poseopt_work(plsvo_ctx* c, uint64_t* pt_iters, uint64_t* se
   if (!c->p_staged) return fail(c, PLSVO_E_STATE, "poseopt_work: no staged batch");
   HIP_TRY(c, hipSetDevice(c->device));
   std::vector<PoseStateDev> st((size_t)c->p_n);
-  HIP_TRY(c, hipMemcpyAsync(st.data(), c->p_d_state.p, (size_t)c->p_n * sizeof(PoseStateDev), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(st.data(), c->p_w.state.p, (size_t)c->p_n * sizeof(PoseStateDev), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   uint64_t a = 0, b2 = 0;
   for (auto& s : st) { a += s.pt_iters; b2 += s.seg_iters; }
@@ -2010,13 +1758,6 @@ extern "C" int plsvo_reproject(plsvo_ctx* c, const plsvo_reproject_in* in, plsvo
 }
 
 // ---- resident frame step ------------------------------------------------------------------------------
-namespace {
-// carve typed arrays out of one device allocation (256-byte aligned sections)
-struct Carver {
-  size_t off = 0;
-  template <typename T> size_t take(size_t n) { const size_t o = (off + 255) & ~(size_t)255; off = o + std::max(n, (size_t)1) * sizeof(T); return o; }
-};
-}  // namespace
 
 // ---- keyframe stage: close keyframes, scene depth, new-keyframe test, key points (keyframe_device.hpp) --------------------
 extern "C" int plsvo_close_keyframes(plsvo_ctx* c, int n, const plsvo_close_kf_in* in, plsvo_close_kf_out* out) {
@@ -2257,13 +1998,7 @@ extern "C" int plsvo_chain_stage(plsvo_ctx* c, int n, const plsvo_chain_in* in, 
                p_ptlev = p.take<int>((size_t)npt_total), p_line = p.take<double>((size_t)nseg_total * 3), p_spos = p.take<double>((size_t)nseg_total * 3),
                p_epos = p.take<double>((size_t)nseg_total * 3), p_slev = p.take<int>((size_t)nseg_total);
   HIP_TRY(c, c->ch_d_po.ensure(p.off + 256));
-  const size_t nft = std::max((size_t)npt_total + (size_t)nseg_total, (size_t)1);
-  HIP_TRY(c, c->ch_d_ptkeep.ensure(std::max((size_t)npt_total, (size_t)1)));
-  HIP_TRY(c, c->ch_d_segkeep.ensure(std::max((size_t)nseg_total, (size_t)1)));
-  HIP_TRY(c, c->ch_d_s32.ensure(nft * sizeof(float)));
-  HIP_TRY(c, c->ch_d_s64.ensure(nft * 5 * sizeof(double)));
-  HIP_TRY(c, c->ch_d_state.ensure((size_t)n * sizeof(PoseStateDev)));
-  HIP_TRY(c, c->ch_d_poses.ensure((size_t)n * 7 * sizeof(double)));
+  if ((rc = c->ch_w.ensure(c, (size_t)n, (size_t)npt_total, (size_t)nseg_total))) return rc;
   uint8_t* const B = c->ch_d_blob.as<uint8_t>();
   uint8_t* const Wk = c->ch_d_work.as<uint8_t>();
   uint8_t* const Po = c->ch_d_po.as<uint8_t>();
@@ -2304,13 +2039,7 @@ extern "C" int plsvo_chain_stage(plsvo_ctx* c, int n, const plsvo_chain_in* in, 
   m.ref_type = B + o_rtype; m.ref_grad = reinterpret_cast<const double*>(B + o_rgrad); m.pos = b.pos; m.px_cur = r.px;
   m.px_out = reinterpret_cast<double*>(Wk + w_mpx); m.found = Wk + w_found; m.search_level = reinterpret_cast<int*>(Wk + w_slevel); m.n_iter = reinterpret_cast<int*>(Wk + w_niter);
   m.active = b.active;
-  PoseBatchDev& q = c->ch_pose;
-  q = PoseBatchDev{};
-  q.jobs = b.po_jobs; q.state = c->ch_d_state.as<PoseStateDev>();
-  q.pt_f = b.pt_f; q.pt_pos = b.pt_pos; q.pt_level = b.pt_level; q.seg_line = b.seg_line; q.seg_spos = b.seg_spos; q.seg_epos = b.seg_epos; q.seg_level = b.seg_level;
-  q.pt_keep = c->ch_d_ptkeep.as<uint8_t>(); q.seg_keep = c->ch_d_segkeep.as<uint8_t>();
-  q.scratch_f32 = c->ch_d_s32.as<float>(); q.scratch_f64 = c->ch_d_s64.as<double>();
-  q.log = nullptr; q.log_cap = 0; q.n_jobs = n;
+  c->ch_w.bind_resident(c->ch_pose, b, n);
   c->ch_jobs.swap(jobs);
   c->ch_n = n; c->ch_ncand = (int)NC; c->ch_npt_cap = npt_total; c->ch_nseg_cap = nseg_total;
   c->ch_staged = true; c->ch_run_seq = 0;
@@ -2332,13 +2061,13 @@ extern "C" int plsvo_chain_run(plsvo_ctx* c) {
   const int threads = pose_opt_threads(c, c->ch_n, (long)c->ch_b.n_cand);   // (selected features <= candidates)
   c->p_refill_frames = 0;   // (the chain's jobs are written on the device: the host cannot see whether one has a refinement loop -- pose_opt_rows_kernel)
   EventPair ep{}; prof_begin(c, PLSVO_K_POSEOPT, &ep);
-  HIP_TRY(c, launch_pose_opt(c->ch_pose, c->ch_d_poses.as<double>(), threads, c->opt_poseopt_select ? 1 : 0, c->stream));
+  HIP_TRY(c, launch_pose_opt(c->ch_pose, c->ch_w.poses.as<double>(), threads, c->opt_poseopt_select ? 1 : 0, c->stream));
   prof_end(c, PLSVO_K_POSEOPT, &ep);
   c->ch_run_seq = ++c->run_seq;
   return PLSVO_OK;
 }
 
-extern "C" const double* plsvo_chain_poses_dev(plsvo_ctx* c) { return (c && c->ch_staged) ? c->ch_d_poses.as<double>() : nullptr; }
+extern "C" const double* plsvo_chain_poses_dev(plsvo_ctx* c) { return (c && c->ch_staged) ? c->ch_w.poses.as<double>() : nullptr; }
 
 extern "C" int plsvo_chain_fetch(plsvo_ctx* c, int n, plsvo_chain_out* out) {
   CTX_CHECK(c);
@@ -2354,7 +2083,7 @@ extern "C" int plsvo_chain_fetch(plsvo_ctx* c, int n, plsvo_chain_out* out) {
   std::vector<double> mpx(std::max(NC * 2, (size_t)1));
   std::vector<int> slev(std::max(NC, (size_t)1)), selp(std::max(NP, (size_t)1)), sels(std::max(NS, (size_t)1)), nsel((size_t)n * 2);
   const ChainBatchDev& b = c->ch_b;
-  HIP_TRY(c, hipMemcpyAsync(st.data(), c->ch_d_state.p, (size_t)n * sizeof(PoseStateDev), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(st.data(), c->ch_w.state.p, (size_t)n * sizeof(PoseStateDev), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(nsel.data(), b.n_sel, (size_t)n * 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   if (NC) {
     HIP_TRY(c, hipMemcpyAsync(found.data(), b.found, NC, hipMemcpyDeviceToHost, c->stream));
@@ -2362,11 +2091,11 @@ extern "C" int plsvo_chain_fetch(plsvo_ctx* c, int n, plsvo_chain_out* out) {
     HIP_TRY(c, hipMemcpyAsync(slev.data(), b.search_level, NC * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   }
   if (NP) {
-    HIP_TRY(c, hipMemcpyAsync(pk.data(), c->ch_d_ptkeep.p, NP, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(pk.data(), c->ch_w.ptkeep.p, NP, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(selp.data(), b.sel_pt, NP * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   }
   if (NS) {
-    HIP_TRY(c, hipMemcpyAsync(sk.data(), c->ch_d_segkeep.p, NS, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(sk.data(), c->ch_w.segkeep.p, NS, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(sels.data(), b.sel_seg, NS * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -2375,18 +2104,11 @@ extern "C" int plsvo_chain_fetch(plsvo_ctx* c, int n, plsvo_chain_out* out) {
     const PoseStateDev& s = st[(size_t)j];
     plsvo_chain_out& o = out[j];
     o.align = ao[(size_t)j];
-    uint8_t* pko = o.pose.pt_keep; uint8_t* sko = o.pose.seg_keep;
-    memset(&o.pose, 0, sizeof(o.pose));
-    o.pose.pt_keep = pko; o.pose.seg_keep = sko;
-    for (int k = 0; k < 7; ++k) o.pose.T_f_w[k] = s.T[k];
-    for (int k = 0; k < 36; ++k) o.pose.cov[k] = s.cov[k];
-    o.pose.estimated_scale = s.estimated_scale; o.pose.error_init = s.error_init; o.pose.error_final = s.error_final;
-    o.pose.num_obs_pt = s.num_obs_pt; o.pose.num_obs_ls = s.num_obs_ls;
-    o.pose.iters = s.iters; o.pose.iters_ref = s.iters_ref; o.pose.status = s.status;
+    pose_state_to_out(s, o.pose);
     o.n_sel_pt = nsel[(size_t)j * 2]; o.n_sel_seg = nsel[(size_t)j * 2 + 1];
     const int nc = J.n_pt + 2 * J.n_seg;
-    if (pko && o.n_sel_pt > 0) memcpy(pko, pk.data() + J.po_pt_off, (size_t)o.n_sel_pt);
-    if (sko && o.n_sel_seg > 0) memcpy(sko, sk.data() + J.po_seg_off, (size_t)o.n_sel_seg);
+    if (o.pose.pt_keep && o.n_sel_pt > 0) memcpy(o.pose.pt_keep, pk.data() + J.po_pt_off, (size_t)o.n_sel_pt);
+    if (o.pose.seg_keep && o.n_sel_seg > 0) memcpy(o.pose.seg_keep, sk.data() + J.po_seg_off, (size_t)o.n_sel_seg);
     if (o.found && nc) memcpy(o.found, found.data() + J.cand_off, (size_t)nc);
     if (o.px && nc) memcpy(o.px, mpx.data() + 2 * (size_t)J.cand_off, (size_t)nc * 2 * sizeof(double));
     if (o.search_level && nc) memcpy(o.search_level, slev.data() + J.cand_off, (size_t)nc * sizeof(int));
@@ -2400,989 +2122,6 @@ extern "C" int plsvo_frame_step_batch(plsvo_ctx* c, int n, const plsvo_chain_in*
   int rc = plsvo_chain_stage(c, n, in, params); if (rc) return rc;
   rc = plsvo_chain_run(c); if (rc) return rc;
   return plsvo_chain_fetch(c, n, out);
-}
-
-// ---- map candidates: overlap keyframes' features, first visit, closest view, quality order (candidates_device.hpp) ---------
-namespace {
-struct CandTotals { size_t kf = 0, kfpt = 0, kfseg = 0, pt = 0, seg = 0, ptobs = 0, segobs = 0, ptc = 0, segc = 0, opt = 0, oseg = 0, m = 0, f = 0, vis = 0; };
-// CSR offsets of k lists over `total` entries: start at 0, never decrease; the last one is the length
-static bool cand_csr_ok(const int32_t* off, int k) {
-  if (off[0] != 0) return false;
-  for (int i = 0; i < k; ++i) if (off[i + 1] < off[i]) return false;
-  return true;
-}
-static bool cand_idx_ok(const int32_t* v, size_t n, int lo, int hi) {   // lo <= v < hi
-  for (size_t i = 0; i < n; ++i) if (v[i] < lo || v[i] >= hi) return false;
-  return true;
-}
-}  // namespace
-
-extern "C" int plsvo_candidates_stage(plsvo_ctx* c, int n, const plsvo_cand_map* maps, const plsvo_cand_params* pr) {
-  CTX_CHECK(c);
-  if (n < 0 || !pr || (n > 0 && !maps)) return fail(c, PLSVO_E_INVALID, "candidates_stage: bad arguments");
-  if (pr->cell_size <= 0 || pr->seg_cell_size <= 0 || pr->boundary < 0 || pr->n_pyr_levels < 1 || pr->align_max_iter < 0 || pr->cam.width <= 0 || pr->cam.height <= 0)
-    return fail(c, PLSVO_E_INVALID, "candidates_stage: bad parameters");
-  CandTotals t;
-  int max_level = 0;
-  std::vector<CandMapDev> md((size_t)n);
-  const plsvo_cand_reserve R = c->ci_reserve;       // room beyond the staged sizes: the offsets below are laid out by capacity
-  const plsvo_cand_lm_reserve L = c->cn_reserve;    // landmark rows beyond the staged counts: the per-landmark rows, the candidate lists, the filed rows follow
-  std::vector<int> cap((size_t)n * 5), used((size_t)n * 4), lmcap((size_t)n * 4), fetch_cand((size_t)n * 2);
-  for (int s = 0; s < n; ++s) {
-    const plsvo_cand_map& I = maps[s];
-    if (I.n_kf < 0 || I.n_pt < 0 || I.n_seg < 0 || I.n_pt_cand < 0 || I.n_seg_cand < 0) return fail(c, PLSVO_E_INVALID, "candidates_stage: negative count");
-    if (I.n_kf > 0 && (!I.kf_T || !I.kf_slot || !I.kf_pt_off || !I.kf_seg_off)) return fail(c, PLSVO_E_INVALID, "candidates_stage: null keyframe table");
-    if (I.n_pt > 0 && (!I.pt_pos || !I.pt_type || !I.pt_obs_off)) return fail(c, PLSVO_E_INVALID, "candidates_stage: null point table");
-    if (I.n_seg > 0 && (!I.seg_spos || !I.seg_epos || !I.seg_type || !I.seg_obs_off)) return fail(c, PLSVO_E_INVALID, "candidates_stage: null segment table");
-    if ((I.n_pt_cand > 0 && !I.pt_cand) || (I.n_seg_cand > 0 && !I.seg_cand)) return fail(c, PLSVO_E_INVALID, "candidates_stage: null candidate list");
-    if (I.n_kf > 0 && (!cand_csr_ok(I.kf_pt_off, I.n_kf) || !cand_csr_ok(I.kf_seg_off, I.n_kf))) return fail(c, PLSVO_E_INVALID, "candidates_stage: bad feature list offsets");
-    if ((I.n_pt > 0 && !cand_csr_ok(I.pt_obs_off, I.n_pt)) || (I.n_seg > 0 && !cand_csr_ok(I.seg_obs_off, I.n_seg)))
-      return fail(c, PLSVO_E_INVALID, "candidates_stage: bad observation list offsets");
-    const size_t kfpt = I.n_kf ? (size_t)I.kf_pt_off[I.n_kf] : 0, kfseg = I.n_kf ? (size_t)I.kf_seg_off[I.n_kf] : 0;
-    const size_t ptobs = I.n_pt ? (size_t)I.pt_obs_off[I.n_pt] : 0, segobs = I.n_seg ? (size_t)I.seg_obs_off[I.n_seg] : 0;
-    if ((kfpt && !I.kf_pt_lm) || (kfseg && !I.kf_seg_lm)) return fail(c, PLSVO_E_INVALID, "candidates_stage: null feature list");
-    if (ptobs && (!I.pt_obs_kf || !I.pt_obs_px || !I.pt_obs_f || !I.pt_obs_level || !I.pt_obs_type)) return fail(c, PLSVO_E_INVALID, "candidates_stage: null point observations");
-    if (segobs && (!I.seg_obs_kf || !I.seg_obs_spx || !I.seg_obs_epx || !I.seg_obs_sf || !I.seg_obs_ef || !I.seg_obs_level))
-      return fail(c, PLSVO_E_INVALID, "candidates_stage: null segment observations");
-    if (!cand_idx_ok(I.kf_pt_lm, kfpt, -1, I.n_pt) || !cand_idx_ok(I.kf_seg_lm, kfseg, -1, I.n_seg)) return fail(c, PLSVO_E_INVALID, "candidates_stage: landmark index out of range");
-    if (!cand_idx_ok(I.pt_cand, (size_t)I.n_pt_cand, 0, I.n_pt) || !cand_idx_ok(I.seg_cand, (size_t)I.n_seg_cand, 0, I.n_seg))
-      return fail(c, PLSVO_E_INVALID, "candidates_stage: candidate index out of range");
-    if (!cand_idx_ok(I.pt_obs_kf, ptobs, 0, I.n_kf) || !cand_idx_ok(I.seg_obs_kf, segobs, 0, I.n_kf)) return fail(c, PLSVO_E_INVALID, "candidates_stage: observation keyframe out of range");
-    if (!cand_idx_ok(I.pt_type, (size_t)I.n_pt, PLSVO_LM_DELETED, PLSVO_LM_GOOD + 1) || !cand_idx_ok(I.seg_type, (size_t)I.n_seg, PLSVO_LM_DELETED, PLSVO_LM_GOOD + 1))
-      return fail(c, PLSVO_E_INVALID, "candidates_stage: unknown landmark type");
-    if (!cand_idx_ok(I.kf_slot, (size_t)I.n_kf, 0, INT32_MAX)) return fail(c, PLSVO_E_INVALID, "candidates_stage: negative pyramid slot");
-    if (!cand_idx_ok(I.pt_obs_level, ptobs, 0, PLSVO_MAX_LEVELS) || !cand_idx_ok(I.seg_obs_level, segobs, 0, PLSVO_MAX_LEVELS))
-      return fail(c, PLSVO_E_INVALID, "candidates_stage: observation level out of range");
-    bool edgelet = false;
-    for (size_t k = 0; k < ptobs; ++k) {
-      if (I.pt_obs_type[k] == PLSVO_FTR_EDGELET) edgelet = true;
-      else if (I.pt_obs_type[k] != PLSVO_FTR_CORNER) return fail(c, PLSVO_E_INVALID, "candidates_stage: unknown feature type");
-      max_level = std::max(max_level, (int)I.pt_obs_level[k]);
-    }
-    if (edgelet && !I.pt_obs_grad) return fail(c, PLSVO_E_INVALID, "candidates_stage: edgelets without pt_obs_grad");
-    for (size_t k = 0; k < segobs; ++k) max_level = std::max(max_level, (int)I.seg_obs_level[k]);
-    CandMapDev& M = md[(size_t)s];
-    M.n_kf = I.n_kf; M.n_pt = I.n_pt; M.n_seg = I.n_seg; M.n_pt_cand = I.n_pt_cand; M.n_seg_cand = I.n_seg_cand;
-    if ((size_t)I.n_pt + (size_t)I.n_pt_cand + 2 * (size_t)L.extra_pt > (size_t)INT32_MAX || (size_t)I.n_seg + (size_t)I.n_seg_cand + 2 * (size_t)L.extra_seg > (size_t)INT32_MAX)
-      return fail(c, PLSVO_E_CAPACITY, "candidates_stage: stream too large");
-    int* lc = lmcap.data() + 4 * (size_t)s;
-    lc[0] = I.n_pt + L.extra_pt; lc[1] = I.n_seg + L.extra_seg; lc[2] = I.n_pt_cand + L.extra_pt; lc[3] = I.n_seg_cand + L.extra_seg;
-    fetch_cand[2 * (size_t)s] = I.n_pt_cand; fetch_cand[2 * (size_t)s + 1] = I.n_seg_cand;
-    M.cap_pt = lc[0] + lc[2]; M.cap_seg = lc[1] + lc[3]; M.stream = s;   // (what the candidate kernel switches off behind the filed entries: the rows as laid out)
-    M.kf_off = (long long)t.kf; M.kfpt_off = (long long)t.kfpt; M.kfseg_off = (long long)t.kfseg; M.pt_off = (long long)t.pt; M.seg_off = (long long)t.seg;
-    M.ptobs_off = (long long)t.ptobs; M.segobs_off = (long long)t.segobs; M.ptc_off = (long long)t.ptc; M.segc_off = (long long)t.segc;
-    M.opt_off = (long long)t.opt; M.oseg_off = (long long)t.oseg; M.m_off = (long long)t.m; M.f_off = (long long)t.f;
-    M.vis_pt_off = (long long)t.vis; t.vis += ((size_t)lc[0] + 63) & ~(size_t)63;
-    M.vis_seg_off = (long long)t.vis; t.vis += ((size_t)lc[1] + 63) & ~(size_t)63;
-    if (kfpt + (size_t)R.extra_kf_pt > (size_t)INT32_MAX || kfseg + (size_t)R.extra_kf_seg > (size_t)INT32_MAX || ptobs + (size_t)R.extra_pt_obs > (size_t)INT32_MAX ||
-        segobs + (size_t)R.extra_seg_obs > (size_t)INT32_MAX || (size_t)I.n_kf + (size_t)R.extra_kf > (size_t)INT32_MAX) return fail(c, PLSVO_E_CAPACITY, "candidates_stage: stream too large");
-    int* cp = cap.data() + 5 * (size_t)s; int* us = used.data() + 4 * (size_t)s;
-    cp[0] = I.n_kf + R.extra_kf; cp[1] = (int)kfpt + R.extra_kf_pt; cp[2] = (int)kfseg + R.extra_kf_seg; cp[3] = (int)ptobs + R.extra_pt_obs; cp[4] = (int)segobs + R.extra_seg_obs;
-    us[0] = (int)kfpt; us[1] = (int)kfseg; us[2] = (int)ptobs; us[3] = (int)segobs;
-    t.kf += (size_t)cp[0]; t.kfpt += (size_t)cp[1]; t.kfseg += (size_t)cp[2]; t.pt += (size_t)lc[0]; t.seg += (size_t)lc[1]; t.ptobs += (size_t)cp[3]; t.segobs += (size_t)cp[4];
-    t.ptc += (size_t)lc[2]; t.segc += (size_t)lc[3]; t.opt += (size_t)M.cap_pt; t.oseg += (size_t)M.cap_seg;
-    t.m += (size_t)M.cap_pt + 2 * (size_t)M.cap_seg; t.f += (size_t)cp[0] + 1;
-  }
-  if (t.m > (size_t)INT32_MAX || t.f > (size_t)INT32_MAX || t.vis > (size_t)INT32_MAX) return fail(c, PLSVO_E_CAPACITY, "candidates_stage: batch too large");
-  c->cd_staged = false; c->cd_ran = false; c->cd_matched = false; c->cs_selected = false; c->cs_posed = false; c->ci_inserted = false; c->ci_have_out = false;
-  c->cn_closed = false; c->cn_have_out = false;
-  c->ci_cap = std::move(cap); c->ci_used = std::move(used); c->cn_cap = std::move(lmcap); c->cd_fetch_cand = std::move(fetch_cand);
-  c->ci_t_kf = t.kf; c->ci_t_kfpt = t.kfpt; c->ci_t_kfseg = t.kfseg; c->ci_t_ptobs = t.ptobs; c->ci_t_segobs = t.segobs;
-  if (n == 0) { c->cd_n = 0; c->cd_staged = true; c->cd_maps.clear(); c->cd_m_off.clear(); c->cd_f_off.clear(); c->cd_params = *pr; return PLSVO_OK; }
-  HIP_TRY(c, hipSetDevice(c->device));
-  const size_t N = (size_t)n;
-  Blob blob;
-  const size_t b_maps = blob.add(md);
-  const size_t b_kfT = blob.reserve<double>(t.kf * 7), b_kfpo = blob.reserve<int>(t.kf + N), b_kfpl = blob.reserve<int>(t.kfpt), b_kfso = blob.reserve<int>(t.kf + N),
-               b_kfsl = blob.reserve<int>(t.kfseg);
-  const size_t b_ppos = blob.reserve<double>(t.pt * 3), b_ptype = blob.reserve<int>(t.pt), b_pobo = blob.reserve<int>(t.pt + N), b_pokf = blob.reserve<int>(t.ptobs),
-               b_popx = blob.reserve<double>(t.ptobs * 2), b_pof = blob.reserve<double>(t.ptobs * 3), b_polv = blob.reserve<int>(t.ptobs),
-               b_poty = blob.reserve<uint8_t>(t.ptobs), b_pogr = blob.reserve<double>(t.ptobs * 2);
-  const size_t b_sspos = blob.reserve<double>(t.seg * 3), b_sepos = blob.reserve<double>(t.seg * 3), b_stype = blob.reserve<int>(t.seg), b_sobo = blob.reserve<int>(t.seg + N),
-               b_sokf = blob.reserve<int>(t.segobs), b_sospx = blob.reserve<double>(t.segobs * 2), b_soepx = blob.reserve<double>(t.segobs * 2),
-               b_sosf = blob.reserve<double>(t.segobs * 3), b_soef = blob.reserve<double>(t.segobs * 3), b_solv = blob.reserve<int>(t.segobs);
-  const size_t b_ptc = blob.reserve<int>(t.ptc), b_segc = blob.reserve<int>(t.segc), b_fT = blob.reserve<double>(t.f * 7), b_fslot = blob.reserve<int>(t.f);
-  auto put = [&](size_t sec, size_t at, const void* src, size_t count, size_t elem) {
-    if (count) { if (src) memcpy(blob.host.data() + sec + at * elem, src, count * elem); else memset(blob.host.data() + sec + at * elem, 0, count * elem); }
-  };
-  c->cd_kf_slot.assign(t.kf, 0);
-  c->cd_m_off.resize(N); c->cd_f_off.resize(N);
-  for (int s = 0; s < n; ++s) {
-    const plsvo_cand_map& I = maps[s];
-    const CandMapDev& M = md[(size_t)s];
-    const size_t nk = (size_t)I.n_kf, np = (size_t)I.n_pt, ns = (size_t)I.n_seg;
-    const size_t kfpt = nk ? (size_t)I.kf_pt_off[nk] : 0, kfseg = nk ? (size_t)I.kf_seg_off[nk] : 0, ptobs = np ? (size_t)I.pt_obs_off[np] : 0, segobs = ns ? (size_t)I.seg_obs_off[ns] : 0;
-    const size_t S = (size_t)s;
-    put(b_kfT, (size_t)M.kf_off * 7, I.kf_T, nk * 7, sizeof(double));
-    put(b_kfpo, (size_t)M.kf_off + S, nk ? I.kf_pt_off : nullptr, nk + 1, sizeof(int));
-    put(b_kfso, (size_t)M.kf_off + S, nk ? I.kf_seg_off : nullptr, nk + 1, sizeof(int));
-    put(b_kfpl, (size_t)M.kfpt_off, I.kf_pt_lm, kfpt, sizeof(int)); put(b_kfsl, (size_t)M.kfseg_off, I.kf_seg_lm, kfseg, sizeof(int));
-    put(b_ppos, (size_t)M.pt_off * 3, I.pt_pos, np * 3, sizeof(double)); put(b_ptype, (size_t)M.pt_off, I.pt_type, np, sizeof(int));
-    put(b_pobo, (size_t)M.pt_off + S, np ? I.pt_obs_off : nullptr, np + 1, sizeof(int));
-    put(b_pokf, (size_t)M.ptobs_off, I.pt_obs_kf, ptobs, sizeof(int)); put(b_popx, (size_t)M.ptobs_off * 2, I.pt_obs_px, ptobs * 2, sizeof(double));
-    put(b_pof, (size_t)M.ptobs_off * 3, I.pt_obs_f, ptobs * 3, sizeof(double)); put(b_polv, (size_t)M.ptobs_off, I.pt_obs_level, ptobs, sizeof(int));
-    put(b_poty, (size_t)M.ptobs_off, I.pt_obs_type, ptobs, 1); put(b_pogr, (size_t)M.ptobs_off * 2, I.pt_obs_grad, ptobs * 2, sizeof(double));
-    put(b_sspos, (size_t)M.seg_off * 3, I.seg_spos, ns * 3, sizeof(double)); put(b_sepos, (size_t)M.seg_off * 3, I.seg_epos, ns * 3, sizeof(double));
-    put(b_stype, (size_t)M.seg_off, I.seg_type, ns, sizeof(int)); put(b_sobo, (size_t)M.seg_off + S, ns ? I.seg_obs_off : nullptr, ns + 1, sizeof(int));
-    put(b_sokf, (size_t)M.segobs_off, I.seg_obs_kf, segobs, sizeof(int));
-    put(b_sospx, (size_t)M.segobs_off * 2, I.seg_obs_spx, segobs * 2, sizeof(double)); put(b_soepx, (size_t)M.segobs_off * 2, I.seg_obs_epx, segobs * 2, sizeof(double));
-    put(b_sosf, (size_t)M.segobs_off * 3, I.seg_obs_sf, segobs * 3, sizeof(double)); put(b_soef, (size_t)M.segobs_off * 3, I.seg_obs_ef, segobs * 3, sizeof(double));
-    put(b_solv, (size_t)M.segobs_off, I.seg_obs_level, segobs, sizeof(int));
-    put(b_ptc, (size_t)M.ptc_off, I.pt_cand, (size_t)I.n_pt_cand, sizeof(int)); put(b_segc, (size_t)M.segc_off, I.seg_cand, (size_t)I.n_seg_cand, sizeof(int));
-    // the matcher's frame table: the keyframes; the new frame's entry (identity until a run writes it)
-    put(b_fT, (size_t)M.f_off * 7, I.kf_T, nk * 7, sizeof(double)); put(b_fslot, (size_t)M.f_off, I.kf_slot, nk, sizeof(int));
-    const double ident[7] = { 0, 0, 0, 1, 0, 0, 0 };
-    put(b_fT, ((size_t)M.f_off + nk) * 7, ident, 7, sizeof(double)); put(b_fslot, (size_t)M.f_off + nk, nullptr, 1, sizeof(int));
-    if (nk) memcpy(c->cd_kf_slot.data() + M.kf_off, I.kf_slot, nk * sizeof(int));
-    c->cd_m_off[S] = M.m_off; c->cd_f_off[S] = M.f_off;
-  }
-  int rc;
-  if ((rc = upload_blob(c, c->cd_d_blob, blob))) return rc;
-  c->cd_blob_bytes = blob.host.size();
-  // device work: results first (what a fetch brings back), then scratch, then the matcher's arrays and its results
-  Carver cv;
-  const size_t w_cnt = cv.take<int>(N * 2), w_plm = cv.take<int>(t.opt), w_ppx = cv.take<double>(t.opt * 2), w_pcell = cv.take<int>(t.opt), w_pobs = cv.take<int>(t.opt),
-               w_pview = cv.take<uint8_t>(t.opt), w_pact = cv.take<uint8_t>(t.opt), w_slm = cv.take<int>(t.oseg), w_spx = cv.take<double>(t.oseg * 4),
-               w_scell = cv.take<int>(t.oseg * 2), w_sobs = cv.take<int>(t.oseg), w_sview = cv.take<uint8_t>(t.oseg), w_sact = cv.take<uint8_t>(t.oseg),
-               w_pfail = cv.take<uint8_t>(t.ptc), w_sfail = cv.take<uint8_t>(t.segc);
-  c->cd_fetch_bytes = cv.off;
-  const size_t w_vis = cv.take<unsigned int>(t.vis), w_kfpos = cv.take<double>(t.kf * 3), w_tplm = cv.take<int>(t.opt), w_tppx = cv.take<double>(t.opt * 2),
-               w_tpcell = cv.take<int>(t.opt), w_tslm = cv.take<int>(t.oseg), w_tspx = cv.take<double>(t.oseg * 4), w_tscell = cv.take<int>(t.oseg * 2);
-  const size_t w_mcf = cv.take<int>(t.m), w_mrf = cv.take<int>(t.m), w_mrpx = cv.take<double>(t.m * 2), w_mrf3 = cv.take<double>(t.m * 3), w_mlv = cv.take<int>(t.m),
-               w_mty = cv.take<uint8_t>(t.m), w_mgr = cv.take<double>(t.m * 2), w_mpos = cv.take<double>(t.m * 3), w_mpx = cv.take<double>(t.m * 2), w_mact = cv.take<uint8_t>(t.m);
-  const size_t w_opx = cv.take<double>(t.m * 2), w_olev = cv.take<int>(t.m), w_oit = cv.take<int>(t.m), w_ofound = cv.take<uint8_t>(t.m);
-  HIP_TRY(c, c->cd_d_work.ensure(cv.off + 256));
-  char* din = reinterpret_cast<char*>(c->cd_d_blob.p); char* dw = reinterpret_cast<char*>(c->cd_d_work.p);
-  auto D = [&](size_t o) { return reinterpret_cast<double*>(din + o); };
-  auto Iv = [&](size_t o) { return reinterpret_cast<int*>(din + o); };
-  auto WD = [&](size_t o) { return reinterpret_cast<double*>(dw + o); };
-  auto WI = [&](size_t o) { return reinterpret_cast<int*>(dw + o); };
-  auto WB = [&](size_t o) { return reinterpret_cast<uint8_t*>(dw + o); };
-  CandBatchDev b{};
-  b.maps = reinterpret_cast<const CandMapDev*>(din + b_maps); b.n_jobs = n;
-  b.fx = pr->cam.fx; b.fy = pr->cam.fy; b.cx = pr->cam.cx; b.cy = pr->cam.cy; b.cam_width = pr->cam.width; b.cam_height = pr->cam.height;
-  b.cell_size = pr->cell_size; b.grid_n_cols = (pr->cam.width + pr->cell_size - 1) / pr->cell_size;
-  b.seg_cell_size = pr->seg_cell_size; b.seg_grid_n_cols = (pr->cam.width + pr->seg_cell_size - 1) / pr->seg_cell_size; b.boundary = pr->boundary;
-  b.kf_T = D(b_kfT); b.kf_pt_off = Iv(b_kfpo); b.kf_pt_lm = Iv(b_kfpl); b.kf_seg_off = Iv(b_kfso); b.kf_seg_lm = Iv(b_kfsl);
-  b.pt_pos = D(b_ppos); b.pt_type = Iv(b_ptype); b.pt_obs_off = Iv(b_pobo); b.pt_obs_kf = Iv(b_pokf); b.pt_obs_px = D(b_popx); b.pt_obs_f = D(b_pof);
-  b.pt_obs_level = Iv(b_polv); b.pt_obs_type = reinterpret_cast<const uint8_t*>(din + b_poty); b.pt_obs_grad = D(b_pogr);
-  b.seg_spos = D(b_sspos); b.seg_epos = D(b_sepos); b.seg_type = Iv(b_stype); b.seg_obs_off = Iv(b_sobo); b.seg_obs_kf = Iv(b_sokf);
-  b.seg_obs_spx = D(b_sospx); b.seg_obs_epx = D(b_soepx); b.seg_obs_sf = D(b_sosf); b.seg_obs_ef = D(b_soef); b.seg_obs_level = Iv(b_solv);
-  b.pt_cand = Iv(b_ptc); b.seg_cand = Iv(b_segc);
-  b.visit = reinterpret_cast<unsigned int*>(dw + w_vis); b.kf_pos = WD(w_kfpos);
-  b.t_pt_lm = WI(w_tplm); b.t_pt_px = WD(w_tppx); b.t_pt_cell = WI(w_tpcell); b.t_seg_lm = WI(w_tslm); b.t_seg_px = WD(w_tspx); b.t_seg_cell = WI(w_tscell);
-  b.counts = WI(w_cnt);
-  b.o_pt_lm = WI(w_plm); b.o_pt_px = WD(w_ppx); b.o_pt_cell = WI(w_pcell); b.o_pt_obs = WI(w_pobs); b.o_pt_view = WB(w_pview); b.o_pt_active = WB(w_pact);
-  b.o_seg_lm = WI(w_slm); b.o_seg_px = WD(w_spx); b.o_seg_cell = WI(w_scell); b.o_seg_obs = WI(w_sobs); b.o_seg_view = WB(w_sview); b.o_seg_active = WB(w_sact);
-  b.pt_cand_failed = WB(w_pfail); b.seg_cand_failed = WB(w_sfail);
-  b.frame_T = D(b_fT); b.frame_slot = Iv(b_fslot);
-  b.m_cur_frame = WI(w_mcf); b.m_ref_frame = WI(w_mrf); b.m_ref_px = WD(w_mrpx); b.m_ref_f = WD(w_mrf3); b.m_ref_level = WI(w_mlv); b.m_ref_type = WB(w_mty);
-  b.m_ref_grad = WD(w_mgr); b.m_pos = WD(w_mpos); b.m_px_cur = WD(w_mpx); b.m_active = WB(w_mact);
-  c->cd_b = b;
-  MatchBatchDev mb{};
-  mb.fx = b.fx; mb.fy = b.fy; mb.cx = b.cx; mb.cy = b.cy; mb.cam_width = b.cam_width; mb.cam_height = b.cam_height;
-  mb.n = (int)t.m; mb.n_pyr_levels = pr->n_pyr_levels; mb.align_max_iter = pr->align_max_iter;
-  mb.frame_T = b.frame_T; mb.frame_slot = b.frame_slot; mb.cur_frame = b.m_cur_frame; mb.ref_frame = b.m_ref_frame;
-  mb.ref_px = b.m_ref_px; mb.ref_f = b.m_ref_f; mb.ref_level = b.m_ref_level; mb.ref_type = b.m_ref_type; mb.ref_grad = b.m_ref_grad;
-  mb.pos = b.m_pos; mb.px_cur = b.m_px_cur; mb.active = b.m_active;
-  mb.px_out = WD(w_opx); mb.search_level = WI(w_olev); mb.n_iter = WI(w_oit); mb.found = WB(w_ofound);
-  c->cd_match = mb;
-  c->cd_off = { w_cnt, w_plm, w_ppx, w_pcell, w_pobs, w_pview, w_pact, w_slm, w_spx, w_scell, w_sobs, w_sview, w_sact, w_pfail, w_sfail };
-  c->cd_vis_off = w_vis; c->cd_vis_bytes = t.vis * sizeof(unsigned int);
-  c->cd_maps = std::move(md); c->cd_params = *pr; c->cd_n = n; c->cd_total_m = t.m; c->cd_total_f = t.f; c->cd_max_level = max_level;
-  // the landmark quality the selection maintains: n_failed_reproj_, n_succeeded_reproj_ of points and segments, then their event bytes -- zero
-  {
-    Carver q;
-    q.take<int>(t.pt); q.take<int>(t.pt); q.take<int>(t.seg); q.take<int>(t.seg);
-    c->cs_ev_off = q.take<uint8_t>(t.pt); q.take<uint8_t>(t.seg);
-    HIP_TRY(c, c->cs_d_q.ensure(q.off + 256));
-    HIP_TRY(c, hipMemsetAsync(c->cs_d_q.p, 0, q.off, c->stream));
-  }
-  c->cd_t_pt = t.pt; c->cd_t_seg = t.seg; c->cd_t_ptc = t.ptc; c->cd_t_segc = t.segc; c->cd_t_opt = t.opt; c->cd_t_oseg = t.oseg;
-  c->cd_staged = true;
-  return PLSVO_OK;
-}
-
-extern "C" int plsvo_candidates_run(plsvo_ctx* c, int n, const plsvo_cand_frame* fr) {
-  CTX_CHECK(c);
-  if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_run: no staged map tables");
-  if (n != c->cd_n || (n > 0 && !fr)) return fail(c, PLSVO_E_INVALID, "candidates_run: n does not match the staged batch");
-  size_t t_ov = 0;
-  for (int s = 0; s < n; ++s) {
-    if (fr[s].n_overlap < 0 || fr[s].cur_slot < 0) return fail(c, PLSVO_E_INVALID, "candidates_run: negative count or slot");
-    if (fr[s].n_overlap > 0 && !fr[s].overlap_idx) return fail(c, PLSVO_E_INVALID, "candidates_run: null overlap list");
-    if (!cand_idx_ok(fr[s].overlap_idx, (size_t)fr[s].n_overlap, 0, c->cd_maps[(size_t)s].n_kf)) return fail(c, PLSVO_E_INVALID, "candidates_run: overlap index outside the keyframe table");
-    t_ov += (size_t)fr[s].n_overlap;
-  }
-  c->cd_ran = false; c->cd_matched = false; c->cs_selected = false; c->cs_posed = false; c->ci_inserted = false; c->cn_closed = false;
-  for (int s = 0; s < n; ++s) { c->cd_fetch_cand[2 * (size_t)s] = c->cd_maps[(size_t)s].n_pt_cand; c->cd_fetch_cand[2 * (size_t)s + 1] = c->cd_maps[(size_t)s].n_seg_cand; }
-  c->cd_ov_off.assign((size_t)n + 1, 0);
-  if (n == 0) { c->cd_ran = true; return PLSVO_OK; }
-  HIP_TRY(c, hipSetDevice(c->device));
-  Blob blob;
-  const size_t b_jobs = blob.reserve<CandJobDev>((size_t)n), b_ov = blob.reserve<int>(t_ov);
-  CandJobDev* jobs = blob.at<CandJobDev>(b_jobs); int* ov = blob.at<int>(b_ov);
-  c->cd_cur_slot.resize((size_t)n);
-  size_t o = 0;
-  for (int s = 0; s < n; ++s) {
-    CandJobDev& J = jobs[s];
-    memcpy(J.T, fr[s].T_f_w, sizeof(J.T)); J.d_T = fr[s].d_T_f_w; J.cur_slot = fr[s].cur_slot; J.n_ov = fr[s].n_overlap; J.ov_off = (long long)o;
-    if (J.n_ov) memcpy(ov + o, fr[s].overlap_idx, (size_t)J.n_ov * sizeof(int));
-    c->cd_cur_slot[(size_t)s] = fr[s].cur_slot; c->cd_ov_off[(size_t)s] = (long long)o;
-    o += (size_t)J.n_ov;
-  }
-  c->cd_ov_off[(size_t)n] = (long long)o;
-  int rc;
-  if ((rc = upload_blob(c, c->cd_d_run, blob))) return rc;
-  HIP_TRY(c, c->cd_d_kfcount.ensure(std::max(t_ov, (size_t)1) * sizeof(int)));
-  CandBatchDev b = c->cd_b;
-  const char* dr = reinterpret_cast<const char*>(c->cd_d_run.p);
-  b.jobs = reinterpret_cast<const CandJobDev*>(dr + b_jobs); b.overlap_idx = reinterpret_cast<const int*>(dr + b_ov); b.kf_count = c->cd_d_kfcount.as<int>();
-  {
-    EventPair ep{}; prof_begin(c, PLSVO_K_CANDIDATES, &ep);
-    // the first-visit words are all ones ahead of EVERY launch: a run must not see the visits of the one before
-    hipError_t rearm_then_launch = hipSuccess;
-    if (c->cd_vis_bytes) rearm_then_launch = hipMemsetAsync(reinterpret_cast<char*>(c->cd_d_work.p) + c->cd_vis_off, 0xff, c->cd_vis_bytes, c->stream);
-    if (rearm_then_launch == hipSuccess) rearm_then_launch = launch_map_candidates(b, c->stream);
-    prof_end(c, PLSVO_K_CANDIDATES, &ep);            // ahead of the error return: the event pair goes back to the pool either way
-    HIP_TRY(c, rearm_then_launch);
-  }
-  c->cd_ran = true;
-  return PLSVO_OK;
-}
-
-extern "C" int plsvo_candidates_fetch(plsvo_ctx* c, int n, plsvo_cand_out* out) {
-  CTX_CHECK(c);
-  if (!c->cd_staged || !c->cd_ran) return fail(c, PLSVO_E_STATE, "candidates_fetch: no run to fetch");
-  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_fetch: n does not match the staged batch");
-  if (n == 0) return PLSVO_OK;
-  std::vector<char> h(c->cd_fetch_bytes);
-  const size_t t_ov = (size_t)c->cd_ov_off[(size_t)n];
-  std::vector<int> kfc(std::max(t_ov, (size_t)1));
-  HIP_TRY(c, hipMemcpyAsync(h.data(), c->cd_d_work.p, h.size(), hipMemcpyDeviceToHost, c->stream));
-  if (t_ov) HIP_TRY(c, hipMemcpyAsync(kfc.data(), c->cd_d_kfcount.p, t_ov * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const size_t* W = c->cd_off.data();
-  const int* cnt = reinterpret_cast<const int*>(h.data() + W[0]);
-  auto cp = [&](void* dst, size_t sec, size_t at, size_t count, size_t elem) { if (dst && count) memcpy(dst, h.data() + sec + at * elem, count * elem); };
-  for (int s = 0; s < n; ++s) {
-    const CandMapDev& M = c->cd_maps[(size_t)s];
-    plsvo_cand_out& O = out[s];
-    const size_t np = (size_t)cnt[2 * s], ns = (size_t)cnt[2 * s + 1], po = (size_t)M.opt_off, so = (size_t)M.oseg_off;
-    O.n_filed_pt = (int32_t)np; O.n_filed_seg = (int32_t)ns;
-    cp(O.pt_lm, W[1], po, np, sizeof(int)); cp(O.pt_px, W[2], po * 2, np * 2, sizeof(double)); cp(O.pt_cell, W[3], po, np, sizeof(int));
-    cp(O.pt_obs, W[4], po, np, sizeof(int)); cp(O.pt_has_view, W[5], po, np, 1); cp(O.pt_active, W[6], po, np, 1);
-    cp(O.seg_lm, W[7], so, ns, sizeof(int)); cp(O.seg_px, W[8], so * 4, ns * 4, sizeof(double)); cp(O.seg_cell, W[9], so * 2, ns * 2, sizeof(int));
-    cp(O.seg_obs, W[10], so, ns, sizeof(int)); cp(O.seg_has_view, W[11], so, ns, 1); cp(O.seg_active, W[12], so, ns, 1);
-    cp(O.pt_cand_failed, W[13], (size_t)M.ptc_off, (size_t)c->cd_fetch_cand[2 * (size_t)s], 1); cp(O.seg_cand_failed, W[14], (size_t)M.segc_off, (size_t)c->cd_fetch_cand[2 * (size_t)s + 1], 1);
-    const size_t a = (size_t)c->cd_ov_off[(size_t)s], e = (size_t)c->cd_ov_off[(size_t)s + 1];
-    if (O.kf_count && e > a) memcpy(O.kf_count, kfc.data() + a, (e - a) * sizeof(int));
-  }
-  return PLSVO_OK;
-}
-
-extern "C" int plsvo_candidates_match(plsvo_ctx* c) {
-  CTX_CHECK(c);
-  if (!c->cd_staged || !c->cd_ran) return fail(c, PLSVO_E_STATE, "candidates_match: no candidates on the device");
-  if (c->ci_inserted) return fail(c, PLSVO_E_STATE, "candidates_match: this run's frame was inserted (the tables have moved on); run again");
-  if (c->cn_closed) return fail(c, PLSVO_E_STATE, "candidates_match: landmarks were added behind this run (the tables have moved on); run again");
-  if (c->cd_n == 0 || c->cd_total_m == 0) { c->cd_matched = true; return PLSVO_OK; }
-  if (!c->pyr.base) return fail(c, PLSVO_E_STATE, "candidates_match: pyramids not configured");
-  const plsvo_cand_params& pr = c->cd_params;
-  if (pr.n_pyr_levels > c->pyr.n_levels) return fail(c, PLSVO_E_INVALID, "candidates_match: n_pyr_levels exceeds the configured pyramid");
-  if (pr.cam.width != c->pyr.w[0] || pr.cam.height != c->pyr.h[0]) return fail(c, PLSVO_E_INVALID, "candidates_match: camera size does not match the configured pyramid");
-  if (c->cd_max_level >= c->pyr.n_levels) return fail(c, PLSVO_E_CAPACITY, "candidates_match: observation level outside the configured pyramid");
-  for (int v : c->cd_kf_slot) if (v >= c->pyr.n_slots) return fail(c, PLSVO_E_CAPACITY, "candidates_match: pyramid slot out of range");
-  for (int v : c->cd_cur_slot) if (v >= c->pyr.n_slots) return fail(c, PLSVO_E_CAPACITY, "candidates_match: pyramid slot out of range");
-  HIP_TRY(c, hipSetDevice(c->device));
-  MatchBatchDev mb = c->cd_match;
-  mb.pyr_base = c->pyr.base; mb.slot_bytes = c->pyr.slot_bytes; mb.width = c->pyr.w[0]; mb.height = c->pyr.h[0];
-  {
-    EventPair ep{}; prof_begin(c, PLSVO_K_MATCH, &ep);
-    const hipError_t launched = launch_match_direct(mb, c->stream);
-    prof_end(c, PLSVO_K_MATCH, &ep);                 // ahead of the error return, as in plsvo_candidates_run
-    HIP_TRY(c, launched);
-  }
-  c->cd_matched = true;
-  return PLSVO_OK;
-}
-
-extern "C" int plsvo_candidates_match_fetch(plsvo_ctx* c, int n, plsvo_cand_match_out* out) {
-  CTX_CHECK(c);
-  if (!c->cd_staged || !c->cd_ran || !c->cd_matched) return fail(c, PLSVO_E_STATE, "candidates_match_fetch: no match to fetch");
-  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_match_fetch: n does not match the staged batch");
-  if (n == 0 || c->cd_total_m == 0) return PLSVO_OK;
-  const size_t NM = c->cd_total_m;
-  std::vector<int> cnt((size_t)n * 2), lev(NM);
-  std::vector<double> px(NM * 2);
-  std::vector<uint8_t> found(NM);
-  const MatchBatchDev& mb = c->cd_match;
-  HIP_TRY(c, hipMemcpyAsync(cnt.data(), c->cd_b.counts, cnt.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(px.data(), mb.px_out, NM * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(lev.data(), mb.search_level, NM * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(found.data(), mb.found, NM, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (int s = 0; s < n; ++s) {
-    const size_t at = (size_t)c->cd_maps[(size_t)s].m_off, k = (size_t)cnt[2 * s] + 2 * (size_t)cnt[2 * s + 1];
-    if (!k) continue;
-    if (out[s].found) memcpy(out[s].found, found.data() + at, k);
-    if (out[s].px) memcpy(out[s].px, px.data() + 2 * at, k * 2 * sizeof(double));
-    if (out[s].search_level) memcpy(out[s].search_level, lev.data() + at, k * sizeof(int));
-  }
-  return PLSVO_OK;
-}
-
-extern "C" int plsvo_candidates_dev(plsvo_ctx* c, plsvo_cand_dev* o) {
-  CTX_CHECK(c);
-  if (!o) return fail(c, PLSVO_E_INVALID, "candidates_dev: bad arguments");
-  if (!c->cd_staged || !c->cd_ran || c->cd_n == 0 || c->ci_inserted || c->cn_closed) return fail(c, PLSVO_E_STATE, "candidates_dev: no candidates on the device");
-  const CandBatchDev& b = c->cd_b; const MatchBatchDev& mb = c->cd_match;
-  o->n_entries = (int64_t)c->cd_total_m; o->n_frames = (int64_t)c->cd_total_f;
-  o->m_off = c->cd_m_off.data(); o->f_off = c->cd_f_off.data();
-  o->d_counts = b.counts; o->d_frame_T = b.frame_T; o->d_frame_slot = b.frame_slot; o->d_cur_frame = b.m_cur_frame; o->d_ref_frame = b.m_ref_frame;
-  o->d_ref_px = b.m_ref_px; o->d_ref_f = b.m_ref_f; o->d_ref_level = b.m_ref_level; o->d_ref_type = b.m_ref_type; o->d_ref_grad = b.m_ref_grad;
-  o->d_pos = b.m_pos; o->d_px_cur = b.m_px_cur; o->d_active = b.m_active;
-  o->d_found = mb.found; o->d_px_out = mb.px_out; o->d_search_level = mb.search_level;
-  return PLSVO_OK;
-}
-
-// ---- cell selection of the map candidates: one per cell, landmark quality, features, pose-optimiser input (select_device.hpp) ---------
-namespace {
-constexpr int kInsJoinedBit = 32;                  // insert_device.hpp's kInsJoined
-constexpr int kNewCandBit = 64;                    // newcand_device.hpp's kNewCand
-// the sections of cs_d_q, as plsvo_candidates_stage carved them
-struct QualitySections { size_t pt_nf, pt_ns, seg_nf, seg_ns, pt_ev, seg_ev, end; };
-static QualitySections quality_sections(const plsvo_ctx* c) {
-  Carver q; QualitySections s;
-  s.pt_nf = q.take<int>(c->cd_t_pt); s.pt_ns = q.take<int>(c->cd_t_pt); s.seg_nf = q.take<int>(c->cd_t_seg); s.seg_ns = q.take<int>(c->cd_t_seg);
-  s.pt_ev = q.take<uint8_t>(c->cd_t_pt); s.seg_ev = q.take<uint8_t>(c->cd_t_seg); s.end = q.off;
-  return s;
-}
-// order (visit position -> cell) and its inverse, appended to v; false when `order` is no permutation of 0 .. n-1
-static bool append_cell_order(std::vector<int>& v, const int32_t* order, int n) {
-  const size_t at = v.size();
-  v.resize(at + 2 * (size_t)n, -1);
-  for (int k = 0; k < n; ++k) {
-    const int cell = order ? order[k] : k;
-    if (cell < 0 || cell >= n || v[at + (size_t)n + (size_t)cell] != -1) return false;
-    v[at + (size_t)k] = cell; v[at + (size_t)n + (size_t)cell] = k;
-  }
-  return true;
-}
-}  // namespace
-
-extern "C" int plsvo_candidates_set_quality(plsvo_ctx* c, int n, const plsvo_cand_quality_in* in) {
-  CTX_CHECK(c);
-  if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_set_quality: no staged map tables");
-  if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_set_quality: n does not match the staged batch");
-  for (int s = 0; s < n; ++s) {
-    const CandMapDev& M = c->cd_maps[(size_t)s];
-    const int32_t* arr[4] = { in[s].pt_n_failed, in[s].pt_n_succeeded, in[s].seg_n_failed, in[s].seg_n_succeeded };
-    for (int a = 0; a < 4; ++a) if (arr[a] && !cand_idx_ok(arr[a], (size_t)(a < 2 ? M.n_pt : M.n_seg), 0, INT32_MAX)) return fail(c, PLSVO_E_INVALID, "candidates_set_quality: negative counter");
-  }
-  if (n == 0) return PLSVO_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  const QualitySections q = quality_sections(c);
-  const size_t sec[4] = { q.pt_nf, q.pt_ns, q.seg_nf, q.seg_ns };
-  char* d = reinterpret_cast<char*>(c->cs_d_q.p);
-  for (int s = 0; s < n; ++s) {
-    const CandMapDev& M = c->cd_maps[(size_t)s];
-    const int32_t* arr[4] = { in[s].pt_n_failed, in[s].pt_n_succeeded, in[s].seg_n_failed, in[s].seg_n_succeeded };
-    for (int a = 0; a < 4; ++a) {
-      const size_t cnt = (size_t)(a < 2 ? M.n_pt : M.n_seg), at = (size_t)(a < 2 ? M.pt_off : M.seg_off);
-      if (arr[a] && cnt) HIP_TRY(c, hipMemcpyAsync(d + sec[a] + at * sizeof(int), arr[a], cnt * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    }
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));      // the caller's arrays are free again
-  return PLSVO_OK;
-}
-
-extern "C" int plsvo_candidates_fetch_quality(plsvo_ctx* c, int n, plsvo_cand_quality_out* out) {
-  CTX_CHECK(c);
-  if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_fetch_quality: no staged map tables");
-  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_fetch_quality: n does not match the staged batch");
-  if (n == 0) return PLSVO_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  const QualitySections q = quality_sections(c);
-  const CandBatchDev& b = c->cd_b;
-  std::vector<char> hq(q.end);
-  std::vector<CandMapDev> maps((size_t)n);
-  std::vector<int> ptype(std::max(c->cd_t_pt, (size_t)1)), stype(std::max(c->cd_t_seg, (size_t)1)), ptc(std::max(c->cd_t_ptc, (size_t)1)), segc(std::max(c->cd_t_segc, (size_t)1));
-  HIP_TRY(c, hipMemcpyAsync(hq.data(), c->cs_d_q.p, q.end, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(maps.data(), b.maps, (size_t)n * sizeof(CandMapDev), hipMemcpyDeviceToHost, c->stream));
-  if (c->cd_t_pt) HIP_TRY(c, hipMemcpyAsync(ptype.data(), b.pt_type, c->cd_t_pt * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (c->cd_t_seg) HIP_TRY(c, hipMemcpyAsync(stype.data(), b.seg_type, c->cd_t_seg * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (c->cd_t_ptc) HIP_TRY(c, hipMemcpyAsync(ptc.data(), b.pt_cand, c->cd_t_ptc * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (c->cd_t_segc) HIP_TRY(c, hipMemcpyAsync(segc.data(), b.seg_cand, c->cd_t_segc * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  auto cp = [&](void* dst, const void* src, size_t at, size_t count, size_t elem) { if (dst && count) memcpy(dst, reinterpret_cast<const char*>(src) + at * elem, count * elem); };
-  for (int s = 0; s < n; ++s) {
-    const CandMapDev& M = maps[(size_t)s];
-    plsvo_cand_quality_out& O = out[s];
-    const size_t np = (size_t)M.n_pt, ns = (size_t)M.n_seg, po = (size_t)M.pt_off, so = (size_t)M.seg_off;
-    O.n_pt_cand = M.n_pt_cand; O.n_seg_cand = M.n_seg_cand;
-    cp(O.pt_n_failed, hq.data() + q.pt_nf, po, np, sizeof(int)); cp(O.pt_n_succeeded, hq.data() + q.pt_ns, po, np, sizeof(int));
-    cp(O.seg_n_failed, hq.data() + q.seg_nf, so, ns, sizeof(int)); cp(O.seg_n_succeeded, hq.data() + q.seg_ns, so, ns, sizeof(int));
-    cp(O.pt_type, ptype.data(), po, np, sizeof(int)); cp(O.seg_type, stype.data(), so, ns, sizeof(int));
-    // (the insertion's bit sits above the selection's internal ones)
-    auto public_event = [](char ev) { return (uint8_t)((ev & (PLSVO_LM_EVENT_PROMOTED | PLSVO_LM_EVENT_DELETED)) | ((ev & kInsJoinedBit) ? PLSVO_LM_EVENT_JOINED : 0) |
-                                                    ((ev & kNewCandBit) ? PLSVO_LM_EVENT_NEW : 0)); };
-    if (O.pt_event) for (size_t k = 0; k < np; ++k) O.pt_event[k] = public_event(hq[q.pt_ev + po + k]);
-    if (O.seg_event) for (size_t k = 0; k < ns; ++k) O.seg_event[k] = public_event(hq[q.seg_ev + so + k]);
-    cp(O.pt_cand, ptc.data(), (size_t)M.ptc_off, (size_t)M.n_pt_cand, sizeof(int)); cp(O.seg_cand, segc.data(), (size_t)M.segc_off, (size_t)M.n_seg_cand, sizeof(int));
-  }
-  return PLSVO_OK;
-}
-
-extern "C" int plsvo_candidates_set_match(plsvo_ctx* c, int n, const plsvo_cand_match_out* in) {
-  CTX_CHECK(c);
-  if (!c->cd_staged || !c->cd_ran) return fail(c, PLSVO_E_STATE, "candidates_set_match: no candidates on the device");
-  if (c->ci_inserted) return fail(c, PLSVO_E_STATE, "candidates_set_match: this run's frame was inserted (the tables have moved on); run again");
-  if (c->cn_closed) return fail(c, PLSVO_E_STATE, "candidates_set_match: landmarks were added behind this run (the tables have moved on); run again");
-  if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_set_match: n does not match the staged batch");
-  for (int s = 0; s < n; ++s) if (!in[s].found || !in[s].px || !in[s].search_level) return fail(c, PLSVO_E_INVALID, "candidates_set_match: null array");
-  if (n == 0 || c->cd_total_m == 0) { c->cd_matched = true; return PLSVO_OK; }
-  HIP_TRY(c, hipSetDevice(c->device));
-  std::vector<int> cnt((size_t)n * 2);
-  HIP_TRY(c, hipMemcpyAsync(cnt.data(), c->cd_b.counts, cnt.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const MatchBatchDev& mb = c->cd_match;
-  for (int s = 0; s < n; ++s) {
-    const size_t at = (size_t)c->cd_maps[(size_t)s].m_off, k = (size_t)cnt[2 * s] + 2 * (size_t)cnt[2 * s + 1];
-    if (!k) continue;
-    HIP_TRY(c, hipMemcpyAsync(mb.found + at, in[s].found, k, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(mb.px_out + 2 * at, in[s].px, k * 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(mb.search_level + at, in[s].search_level, k * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->cd_matched = true;
-  return PLSVO_OK;
-}
-
-extern "C" int plsvo_candidates_select(plsvo_ctx* c, const plsvo_cand_select_params* sp) {
-  CTX_CHECK(c);
-  if (!sp) return fail(c, PLSVO_E_INVALID, "candidates_select: bad arguments");
-  if (!c->cd_staged || !c->cd_ran || !c->cd_matched) return fail(c, PLSVO_E_STATE, "candidates_select: no match on the device");
-  if (c->cs_selected) return fail(c, PLSVO_E_STATE, "candidates_select: this run's candidates were selected already (the tables have moved on)");
-  if (c->cn_closed) return fail(c, PLSVO_E_STATE, "candidates_select: landmarks were added behind this run (the tables have moved on); run again");
-  if (sp->max_fts < 0 || sp->max_fts_segs < 0 || sp->poseopt_n_iter < 0)
-    return fail(c, PLSVO_E_INVALID, "candidates_select: bad parameters");
-  const plsvo_cand_params& pr = c->cd_params;
-  const int n = c->cd_n;
-  const int n_cells = c->cd_b.grid_n_cols * ((pr.cam.height + pr.cell_size - 1) / pr.cell_size);
-  const int seg_n_cells = c->cd_b.seg_grid_n_cols * ((pr.cam.height + pr.seg_cell_size - 1) / pr.seg_cell_size);
-  std::vector<int> order;
-  order.reserve(2 * ((size_t)n_cells + (size_t)seg_n_cells));
-  if (!append_cell_order(order, sp->cell_order, n_cells) || !append_cell_order(order, sp->seg_cell_order, seg_n_cells))
-    return fail(c, PLSVO_E_INVALID, "candidates_select: a cell order is not a permutation of its grid");
-  if (n == 0) { c->cs_selected = true; return PLSVO_OK; }
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (order != c->cs_order || !c->cs_d_order.p) {   // the visit orders travel when they change (the reference shuffles them once)
-    Blob blob; blob.add(order);
-    int rc;
-    if ((rc = upload_blob(c, c->cs_d_order, blob))) return rc;
-    c->cs_order = order;
-  }
-  const size_t N = (size_t)n, np = c->cd_t_opt, ns = 2 * c->cd_t_oseg;
-  Carver w;
-  const size_t w_win = w.take<unsigned int>(N * (size_t)n_cells), w_sc = w.take<int>(N * 3), w_plm = w.take<int>(np), w_ppx = w.take<double>(np * 2), w_plev = w.take<int>(np),
-               w_pty = w.take<uint8_t>(np), w_pgr = w.take<double>(np * 2), w_slm = w.take<int>(ns), w_spx = w.take<double>(ns * 4), w_slev = w.take<int>(ns),
-               w_jobs = w.take<PoseJobDev>(N), w_ptf = w.take<double>(np * 3), w_ptpos = w.take<double>(np * 3), w_ptlev = w.take<int>(np), w_line = w.take<double>(ns * 3),
-               w_spos = w.take<double>(ns * 3), w_epos = w.take<double>(ns * 3), w_seglev = w.take<int>(ns);
-  HIP_TRY(c, c->cs_d_work.ensure(w.off + 256));
-  const QualitySections q = quality_sections(c);
-  char* dq = reinterpret_cast<char*>(c->cs_d_q.p); char* dw = reinterpret_cast<char*>(c->cs_d_work.p);
-  const int* dord = c->cs_d_order.as<int>();
-  auto WD = [&](size_t o) { return reinterpret_cast<double*>(dw + o); };
-  auto WI = [&](size_t o) { return reinterpret_cast<int*>(dw + o); };
-  SelectBatchDev b{};
-  b.c = c->cd_b;
-  b.found = c->cd_match.found; b.px_out = c->cd_match.px_out; b.search_level = c->cd_match.search_level;
-  b.n_cells = n_cells; b.seg_n_cells = seg_n_cells; b.max_fts = sp->max_fts; b.max_fts_segs = sp->max_fts_segs; b.n_pyr_levels = pr.n_pyr_levels;
-  b.cell_order = dord; b.cell_pos = dord + n_cells; b.seg_cell_order = dord + 2 * n_cells; b.seg_cell_pos = dord + 2 * n_cells + seg_n_cells;
-  b.pt_nfail = reinterpret_cast<int*>(dq + q.pt_nf); b.pt_nsucc = reinterpret_cast<int*>(dq + q.pt_ns);
-  b.seg_nfail = reinterpret_cast<int*>(dq + q.seg_nf); b.seg_nsucc = reinterpret_cast<int*>(dq + q.seg_ns);
-  b.pt_event = reinterpret_cast<uint8_t*>(dq + q.pt_ev); b.seg_event = reinterpret_cast<uint8_t*>(dq + q.seg_ev);
-  b.cell_win = reinterpret_cast<unsigned int*>(dw + w_win);
-  b.f_pt_lm = WI(w_plm); b.f_pt_px = WD(w_ppx); b.f_pt_level = WI(w_plev); b.f_pt_type = reinterpret_cast<uint8_t*>(dw + w_pty); b.f_pt_grad = WD(w_pgr);
-  b.f_seg_lm = WI(w_slm); b.f_seg_px = WD(w_spx); b.f_seg_level = WI(w_slev); b.scalars = WI(w_sc);
-  b.po_jobs = reinterpret_cast<PoseJobDev*>(dw + w_jobs); b.pt_f = WD(w_ptf); b.pt_pos = WD(w_ptpos); b.pt_level = WI(w_ptlev);
-  b.seg_line = WD(w_line); b.seg_spos = WD(w_spos); b.seg_epos = WD(w_epos); b.seg_level = WI(w_seglev);
-  b.reproj_thresh = sp->reproj_thresh; b.po_n_iter = sp->poseopt_n_iter; b.ldlt_flavour = c->ldlt_flavour;
-  c->cs_b = b;
-  c->cs_win_bytes = N * (size_t)n_cells * sizeof(unsigned int);
-  {
-    EventPair ep{}; prof_begin(c, PLSVO_K_SELECT, &ep);
-    // ahead of EVERY launch: the event bytes are zero, the cells' winner words all ones
-    hipError_t rearm_then_launch = hipMemsetAsync(dq + q.pt_ev, 0, q.end - q.pt_ev, c->stream);
-    if (rearm_then_launch == hipSuccess) rearm_then_launch = hipMemsetAsync(b.cell_win, 0xff, c->cs_win_bytes, c->stream);
-    if (rearm_then_launch == hipSuccess) rearm_then_launch = launch_map_select(b, c->stream);
-    prof_end(c, PLSVO_K_SELECT, &ep);                // ahead of the error return, as in plsvo_candidates_run
-    HIP_TRY(c, rearm_then_launch);
-  }
-  c->cs_selected = true;
-  return PLSVO_OK;
-}
-
-extern "C" int plsvo_candidates_select_fetch(plsvo_ctx* c, int n, plsvo_cand_select_out* out) {
-  CTX_CHECK(c);
-  if (!c->cd_staged || !c->cs_selected) return fail(c, PLSVO_E_STATE, "candidates_select_fetch: no selection to fetch");
-  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_select_fetch: n does not match the staged batch");
-  if (n == 0) return PLSVO_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  const SelectBatchDev& b = c->cs_b;
-  // the features lie between the scalars and the pose optimiser's jobs: one copy
-  const char* lo = reinterpret_cast<const char*>(b.scalars); const char* hi = reinterpret_cast<const char*>(b.po_jobs);
-  std::vector<char> h((size_t)(hi - lo));
-  HIP_TRY(c, hipMemcpyAsync(h.data(), lo, h.size(), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  auto H = [&](const void* dev) { return h.data() + (reinterpret_cast<const char*>(dev) - lo); };
-  auto cp = [&](void* dst, const void* dev, size_t at, size_t count, size_t elem) { if (dst && count) memcpy(dst, H(dev) + at * elem, count * elem); };
-  const int* sc = reinterpret_cast<const int*>(H(b.scalars));
-  for (int s = 0; s < n; ++s) {
-    const CandMapDev& M = c->cd_maps[(size_t)s];
-    plsvo_cand_select_out& O = out[s];
-    O.n_matches = sc[3 * s]; O.n_ls_matches = sc[3 * s + 1]; O.n_trials = sc[3 * s + 2]; O.reserved0 = 0;
-    const size_t np = (size_t)O.n_matches, ns = (size_t)O.n_ls_matches, po = (size_t)M.opt_off, so = 2 * (size_t)M.oseg_off;
-    cp(O.pt_lm, b.f_pt_lm, po, np, sizeof(int)); cp(O.pt_px, b.f_pt_px, po * 2, np * 2, sizeof(double)); cp(O.pt_level, b.f_pt_level, po, np, sizeof(int));
-    cp(O.pt_type, b.f_pt_type, po, np, 1); cp(O.pt_grad, b.f_pt_grad, po * 2, np * 2, sizeof(double));
-    cp(O.seg_lm, b.f_seg_lm, so, ns, sizeof(int)); cp(O.seg_px, b.f_seg_px, so * 4, ns * 4, sizeof(double)); cp(O.seg_level, b.f_seg_level, so, ns, sizeof(int));
-  }
-  return PLSVO_OK;
-}
-
-extern "C" int plsvo_candidates_pose_optimize(plsvo_ctx* c) {
-  CTX_CHECK(c);
-  if (!c->cd_staged || !c->cs_selected) return fail(c, PLSVO_E_STATE, "candidates_pose_optimize: no selection on the device");
-  if (c->ci_inserted) return fail(c, PLSVO_E_STATE, "candidates_pose_optimize: this run's frame was inserted (the tables have moved on); run again");
-  if (c->cn_closed) return fail(c, PLSVO_E_STATE, "candidates_pose_optimize: landmarks were added behind this run (the tables have moved on); run again");
-  const int n = c->cd_n;
-  c->cs_posed = false;
-  if (n == 0) { c->cs_posed = true; return PLSVO_OK; }
-  HIP_TRY(c, hipSetDevice(c->device));
-  const size_t np = std::max(c->cd_t_opt, (size_t)1), ns = std::max(2 * c->cd_t_oseg, (size_t)1), nft = np + ns;
-  HIP_TRY(c, c->cs_d_ptkeep.ensure(np));
-  HIP_TRY(c, c->cs_d_segkeep.ensure(ns));
-  HIP_TRY(c, c->cs_d_s32.ensure(nft * sizeof(float)));
-  HIP_TRY(c, c->cs_d_s64.ensure(nft * 5 * sizeof(double)));
-  HIP_TRY(c, c->cs_d_state.ensure((size_t)n * sizeof(PoseStateDev)));
-  HIP_TRY(c, c->cs_d_poses.ensure((size_t)n * 7 * sizeof(double)));
-  const SelectBatchDev& b = c->cs_b;
-  PoseBatchDev& q = c->cs_pose;
-  q = PoseBatchDev{};
-  q.jobs = b.po_jobs; q.state = c->cs_d_state.as<PoseStateDev>();
-  q.pt_f = b.pt_f; q.pt_pos = b.pt_pos; q.pt_level = b.pt_level; q.seg_line = b.seg_line; q.seg_spos = b.seg_spos; q.seg_epos = b.seg_epos; q.seg_level = b.seg_level;
-  q.pt_keep = c->cs_d_ptkeep.as<uint8_t>(); q.seg_keep = c->cs_d_segkeep.as<uint8_t>();
-  q.scratch_f32 = c->cs_d_s32.as<float>(); q.scratch_f64 = c->cs_d_s64.as<double>();
-  q.log = nullptr; q.log_cap = 0; q.n_jobs = n;
-  const int threads = pose_opt_threads(c, n, (long)nft);   // (selected features <= filed landmarks)
-  c->p_refill_frames = 0;                           // (jobs written on the device, as in plsvo_chain_run)
-  EventPair ep{}; prof_begin(c, PLSVO_K_POSEOPT, &ep);
-  const hipError_t launched = launch_pose_opt(q, c->cs_d_poses.as<double>(), threads, c->opt_poseopt_select ? 1 : 0, c->stream);
-  prof_end(c, PLSVO_K_POSEOPT, &ep);
-  HIP_TRY(c, launched);
-  c->cs_posed = true;
-  return PLSVO_OK;
-}
-
-extern "C" const double* plsvo_candidates_poses_dev(plsvo_ctx* c) { return (c && c->cd_staged && c->cs_posed) ? c->cs_d_poses.as<double>() : nullptr; }
-
-extern "C" int plsvo_candidates_pose_fetch(plsvo_ctx* c, int n, plsvo_poseopt_out* out) {
-  CTX_CHECK(c);
-  if (!c->cd_staged || !c->cs_selected || !c->cs_posed) return fail(c, PLSVO_E_STATE, "candidates_pose_fetch: no pose optimisation to fetch");
-  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_pose_fetch: n does not match the staged batch");
-  if (n == 0) return PLSVO_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  const size_t NP = std::max(c->cd_t_opt, (size_t)1), NS = std::max(2 * c->cd_t_oseg, (size_t)1);
-  std::vector<PoseStateDev> st((size_t)n);
-  std::vector<PoseJobDev> jobs((size_t)n);
-  std::vector<uint8_t> pk(NP), sk(NS);
-  HIP_TRY(c, hipMemcpyAsync(st.data(), c->cs_d_state.p, (size_t)n * sizeof(PoseStateDev), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(jobs.data(), c->cs_b.po_jobs, (size_t)n * sizeof(PoseJobDev), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(pk.data(), c->cs_d_ptkeep.p, NP, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(sk.data(), c->cs_d_segkeep.p, NS, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (int j = 0; j < n; ++j) {
-    const PoseStateDev& s = st[(size_t)j]; const PoseJobDev& J = jobs[(size_t)j];
-    plsvo_poseopt_out& o = out[j];
-    uint8_t* pko = o.pt_keep; uint8_t* sko = o.seg_keep;
-    memset(&o, 0, sizeof(o));
-    o.pt_keep = pko; o.seg_keep = sko;
-    for (int k = 0; k < 7; ++k) o.T_f_w[k] = s.T[k];
-    for (int k = 0; k < 36; ++k) o.cov[k] = s.cov[k];
-    o.estimated_scale = s.estimated_scale; o.error_init = s.error_init; o.error_final = s.error_final;
-    o.num_obs_pt = s.num_obs_pt; o.num_obs_ls = s.num_obs_ls;
-    o.iters = s.iters; o.iters_ref = s.iters_ref; o.status = s.status;
-    if (pko && J.n_pts > 0) memcpy(pko, pk.data() + J.pt_off, (size_t)J.n_pts);
-    if (sko && J.n_seg > 0) memcpy(sko, sk.data() + J.seg_off, (size_t)J.n_seg);
-  }
-  return PLSVO_OK;
-}
-
-// ---- keyframe insertion into the resident map tables (insert_device.hpp) ---------------------------------------------
-extern "C" int plsvo_candidates_reserve(plsvo_ctx* c, const plsvo_cand_reserve* r) {
-  CTX_CHECK(c);
-  if (r && (r->extra_kf < 0 || r->extra_kf_pt < 0 || r->extra_kf_seg < 0 || r->extra_pt_obs < 0 || r->extra_seg_obs < 0)) return fail(c, PLSVO_E_INVALID, "candidates_reserve: negative room");
-  c->ci_reserve = r ? *r : plsvo_cand_reserve{};
-  return PLSVO_OK;
-}
-
-extern "C" int plsvo_candidates_insert_keyframe(plsvo_ctx* c, int n, const plsvo_cand_insert* in) {
-  CTX_CHECK(c);
-  if (!c->cd_staged || !c->cd_ran || !c->cs_selected) return fail(c, PLSVO_E_STATE, "candidates_insert_keyframe: no selection on the last run");
-  if (c->ci_inserted) return fail(c, PLSVO_E_STATE, "candidates_insert_keyframe: this run's frame was inserted already");
-  if (c->cn_closed) return fail(c, PLSVO_E_STATE, "candidates_insert_keyframe: landmarks were added behind this run (the tables have moved on); run again");
-  if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_insert_keyframe: n does not match the staged batch");
-  bool any = false, host_masks = false;
-  for (int s = 0; s < n; ++s) {
-    const plsvo_cand_insert& I = in[s];
-    if (!I.is_kf) continue;
-    any = true;
-    if (I.remove_kf < -1 || I.remove_kf >= c->cd_maps[(size_t)s].n_kf) return fail(c, PLSVO_E_INVALID, "candidates_insert_keyframe: remove_kf outside the keyframe table");
-    if (I.kf_slot < 0) return fail(c, PLSVO_E_INVALID, "candidates_insert_keyframe: negative pyramid slot");
-    if (I.pose_source < PLSVO_INSERT_POSE_HOST || I.pose_source > PLSVO_INSERT_POSE_RESIDENT || (I.pose_source == PLSVO_INSERT_POSE_DEV && !I.d_T_f_w))
-      return fail(c, PLSVO_E_INVALID, "candidates_insert_keyframe: bad pose source");
-    if (I.pt_keep || I.seg_keep) host_masks = true;
-  }
-  for (int s = 0; s < n; ++s)
-    if (in[s].is_kf && (!in[s].pt_keep || !in[s].seg_keep || in[s].pose_source == PLSVO_INSERT_POSE_RESIDENT) && !c->cs_posed)
-      return fail(c, PLSVO_E_STATE, "candidates_insert_keyframe: no resident pose optimisation for the masks or the pose");
-  for (int s = 0; s < n; ++s)                       // the keyframe count needs no launch
-    if (in[s].is_kf && c->cd_maps[(size_t)s].n_kf + 1 - (in[s].remove_kf >= 0 ? 1 : 0) > c->ci_cap[5 * (size_t)s])
-      return fail(c, PLSVO_E_CAPACITY, "candidates_insert_keyframe: no room for another keyframe (plsvo_candidates_reserve)");
-  const size_t N = (size_t)n;
-  c->ci_last.assign(N, InsertPlanDev{});
-  for (int s = 0; s < n; ++s) {
-    InsertPlanDev& O = c->ci_last[(size_t)s]; const CandMapDev& M = c->cd_maps[(size_t)s]; const int* us = c->ci_used.data() + 4 * (size_t)s;
-    O.n_kf = M.n_kf; O.new_kf = -1; O.n_kf_pt = us[0]; O.n_kf_seg = us[1]; O.n_pt_obs = us[2]; O.n_seg_obs = us[3]; O.n_pt_cand = M.n_pt_cand; O.n_seg_cand = M.n_seg_cand;
-  }
-  if (!any) { c->ci_have_out = true; return PLSVO_OK; }
-  HIP_TRY(c, hipSetDevice(c->device));
-  // -- the records and the caller's masks, laid out like the resident masks (feature rows from opt_off / 2 * oseg_off)
-  std::vector<int> sc(N * 3);
-  if (host_masks) {
-    HIP_TRY(c, hipMemcpyAsync(sc.data(), c->cs_b.scalars, sc.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  Blob blob;
-  const size_t b_jobs = blob.reserve<InsertJobDev>(N);
-  const size_t b_pk = host_masks ? blob.reserve<uint8_t>(c->cd_t_opt) : 0, b_sk = host_masks ? blob.reserve<uint8_t>(2 * c->cd_t_oseg) : 0;
-  HIP_TRY(c, c->ci_d_in.ensure(std::max(blob.host.size(), (size_t)256)));
-  HIP_TRY(c, c->ci_d_plan.ensure(N * sizeof(InsertPlanDev)));
-  const uint8_t* din = c->ci_d_in.as<uint8_t>();
-  InsertJobDev* jobs = blob.at<InsertJobDev>(b_jobs);
-  for (int s = 0; s < n; ++s) {
-    const plsvo_cand_insert& I = in[s]; const CandMapDev& M = c->cd_maps[(size_t)s];
-    InsertJobDev& J = jobs[s];
-    memset(&J, 0, sizeof(J));
-    J.is_kf = I.is_kf ? 1 : 0; J.remove_kf = I.remove_kf; J.kf_slot = I.kf_slot;
-    if (!J.is_kf) continue;
-    memcpy(J.T, I.T_f_w, sizeof(J.T));
-    J.d_T = I.pose_source == PLSVO_INSERT_POSE_DEV ? I.d_T_f_w : I.pose_source == PLSVO_INSERT_POSE_RESIDENT ? c->cs_d_poses.as<double>() + 7 * (size_t)s : nullptr;
-    J.pt_keep = c->cs_d_ptkeep.as<uint8_t>(); J.seg_keep = c->cs_d_segkeep.as<uint8_t>();
-    if (I.pt_keep) { J.pt_keep = din + b_pk; if (sc[3 * (size_t)s] > 0) memcpy(blob.at<uint8_t>(b_pk) + M.opt_off, I.pt_keep, (size_t)sc[3 * (size_t)s]); }
-    if (I.seg_keep) { J.seg_keep = din + b_sk; if (sc[3 * (size_t)s + 1] > 0) memcpy(blob.at<uint8_t>(b_sk) + 2 * M.oseg_off, I.seg_keep, (size_t)sc[3 * (size_t)s + 1]); }
-  }
-  int rc;
-  if ((rc = upload_blob(c, c->ci_d_in, blob))) return rc;
-  // -- scratch per landmark, per candidate entry and per new feature; staging rows of the arrays that shift
-  Carver w;
-  InsertBatchDev b{};
-  size_t o_k[2][17];
-  for (int k = 0; k < 2; ++k) {
-    const size_t lm = k ? c->cd_t_seg : c->cd_t_pt, cnd = k ? c->cd_t_segc : c->cd_t_ptc, ftr = k ? 2 * c->cd_t_oseg : c->cd_t_opt;
-    const size_t kfl = k ? c->ci_t_kfseg : c->ci_t_kfpt, obs = k ? c->ci_t_segobs : c->ci_t_ptobs;
-    size_t* o = o_k[k];
-    o[0] = w.take<unsigned int>(lm); o[1] = w.take<unsigned int>(lm); o[2] = w.take<int>(lm); o[3] = w.take<int>(lm); o[4] = w.take<int>(lm);
-    o[5] = w.take<int>(cnd); o[6] = w.take<int>(ftr); o[7] = w.take<int>(c->ci_t_kf + N); o[8] = w.take<int>(kfl); o[9] = w.take<int>(lm + N);
-    o[10] = w.take<int>(obs); o[11] = w.take<int>(obs); o[12] = w.take<double>(obs * 2); o[13] = w.take<double>(obs * (k ? 2 : 3)); o[14] = w.take<double>(obs * (k ? 3 : 2));
-    o[15] = w.take<double>(k ? obs * 3 : 1); o[16] = w.take<uint8_t>(k ? 1 : obs);
-  }
-  HIP_TRY(c, c->ci_d_work.ensure(w.off + 256));
-  char* dw = reinterpret_cast<char*>(c->ci_d_work.p);
-  for (int k = 0; k < 2; ++k) {
-    InsertKindDev& K = k ? b.seg : b.pt; const size_t* o = o_k[k];
-    K.f0 = reinterpret_cast<unsigned int*>(dw + o[0]); K.f1 = reinterpret_cast<unsigned int*>(dw + o[1]);
-    K.cnt = reinterpret_cast<int*>(dw + o[2]); K.len = reinterpret_cast<int*>(dw + o[3]); K.erase = reinterpret_cast<int*>(dw + o[4]);
-    K.cand_kf = reinterpret_cast<int*>(dw + o[5]); K.new_lm = reinterpret_cast<int*>(dw + o[6]); K.kf_off2 = reinterpret_cast<int*>(dw + o[7]);
-    K.kf_lm2 = reinterpret_cast<int*>(dw + o[8]); K.obs_off2 = reinterpret_cast<int*>(dw + o[9]); K.obs_kf2 = reinterpret_cast<int*>(dw + o[10]);
-    K.obs_level2 = reinterpret_cast<int*>(dw + o[11]); K.obs_a2 = reinterpret_cast<double*>(dw + o[12]); K.obs_b2 = reinterpret_cast<double*>(dw + o[13]);
-    K.obs_c2 = reinterpret_cast<double*>(dw + o[14]); K.obs_d2 = reinterpret_cast<double*>(dw + o[15]); K.obs_type2 = reinterpret_cast<uint8_t*>(dw + o[16]);
-  }
-  b.s = c->cs_b;
-  b.jobs = reinterpret_cast<const InsertJobDev*>(din + b_jobs); b.plan = c->ci_d_plan.as<InsertPlanDev>();
-  // -- the plan: decisions and counts in scratch; capacity is decided before anything is changed
-  HIP_TRY(c, launch_map_insert_plan(b, c->stream));
-  std::vector<InsertPlanDev> plan(N);
-  HIP_TRY(c, hipMemcpyAsync(plan.data(), b.plan, N * sizeof(InsertPlanDev), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (int s = 0; s < n; ++s) {
-    if (!in[s].is_kf) continue;
-    const InsertPlanDev& P = plan[(size_t)s]; const int* cp = c->ci_cap.data() + 5 * (size_t)s;
-    if (P.n_kf > cp[0] || P.n_kf_pt > cp[1] || P.n_kf_seg > cp[2] || P.n_pt_obs > cp[3] || P.n_seg_obs > cp[4])
-      return fail(c, PLSVO_E_CAPACITY, "candidates_insert_keyframe: a stream's new sizes exceed its room (plsvo_candidates_reserve); nothing was changed");
-  }
-  {
-    EventPair ep{}; prof_begin(c, PLSVO_K_INSERT, &ep);
-    const hipError_t launched = launch_map_insert(b, c->stream);
-    prof_end(c, PLSVO_K_INSERT, &ep);                // ahead of the error return, as in plsvo_candidates_run
-    HIP_TRY(c, launched);
-  }
-  // -- the host mirrors describe the new tables
-  for (int s = 0; s < n; ++s) {
-    if (!in[s].is_kf) { c->ci_last[(size_t)s] = plan[(size_t)s]; continue; }
-    const InsertPlanDev& P = plan[(size_t)s];
-    CandMapDev& M = c->cd_maps[(size_t)s];
-    int* slot = c->cd_kf_slot.data() + M.kf_off;
-    if (in[s].remove_kf >= 0) for (int k = in[s].remove_kf; k + 1 < M.n_kf; ++k) slot[k] = slot[k + 1];
-    slot[P.new_kf] = in[s].kf_slot;
-    for (int k = P.n_kf; k < c->ci_cap[5 * (size_t)s]; ++k) slot[k] = 0;
-    M.n_kf = P.n_kf; M.n_pt_cand = P.n_pt_cand; M.n_seg_cand = P.n_seg_cand;
-    c->cd_fetch_cand[2 * (size_t)s] = P.n_pt_cand; c->cd_fetch_cand[2 * (size_t)s + 1] = P.n_seg_cand;
-    int* us = c->ci_used.data() + 4 * (size_t)s;
-    us[0] = P.n_kf_pt; us[1] = P.n_kf_seg; us[2] = P.n_pt_obs; us[3] = P.n_seg_obs;
-    c->ci_last[(size_t)s] = P;
-  }
-  c->cd_max_level = std::max(c->cd_max_level, c->cd_params.n_pyr_levels - 1);   // the new observations' levels are the matcher's search levels
-  c->ci_inserted = true; c->ci_have_out = true;
-  return PLSVO_OK;
-}
-
-extern "C" int plsvo_candidates_capacity(plsvo_ctx* c, int n, plsvo_cand_reserve* out) {
-  CTX_CHECK(c);
-  if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_capacity: no staged map tables");
-  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_capacity: n does not match the staged batch");
-  for (int s = 0; s < n; ++s) {
-    const int* cp = c->ci_cap.data() + 5 * (size_t)s;
-    out[s].extra_kf = cp[0]; out[s].extra_kf_pt = cp[1]; out[s].extra_kf_seg = cp[2]; out[s].extra_pt_obs = cp[3]; out[s].extra_seg_obs = cp[4]; out[s].reserved0 = 0;
-  }
-  return PLSVO_OK;
-}
-
-extern "C" int plsvo_candidates_insert_fetch(plsvo_ctx* c, int n, plsvo_cand_insert_out* out) {
-  CTX_CHECK(c);
-  if (!c->cd_staged || !c->ci_have_out) return fail(c, PLSVO_E_STATE, "candidates_insert_fetch: no insertion since the tables were staged");
-  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_insert_fetch: n does not match the staged batch");
-  for (int s = 0; s < n; ++s) {
-    const InsertPlanDev& P = c->ci_last[(size_t)s]; plsvo_cand_insert_out& O = out[s];
-    O.n_kf = P.n_kf; O.new_kf = P.new_kf; O.n_kf_pt = P.n_kf_pt; O.n_kf_seg = P.n_kf_seg; O.n_pt_obs = P.n_pt_obs; O.n_seg_obs = P.n_seg_obs;
-    O.n_pt_cand = P.n_pt_cand; O.n_seg_cand = P.n_seg_cand; O.n_joined_pt = P.n_joined_pt; O.n_joined_seg = P.n_joined_seg;
-    O.n_deleted_pt = P.n_deleted_pt; O.n_deleted_seg = P.n_deleted_seg;
-  }
-  return PLSVO_OK;
-}
-
-extern "C" int plsvo_candidates_fetch_map(plsvo_ctx* c, int n, plsvo_cand_map_out* out) {
-  CTX_CHECK(c);
-  if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_fetch_map: no staged map tables");
-  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_fetch_map: n does not match the staged batch");
-  if (n == 0) return PLSVO_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  std::vector<char> h(c->cd_blob_bytes);           // the tables are one allocation: one copy
-  HIP_TRY(c, hipMemcpyAsync(h.data(), c->cd_d_blob.p, h.size(), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const CandBatchDev& b = c->cd_b;
-  const char* base = reinterpret_cast<const char*>(c->cd_d_blob.p);
-  auto H = [&](const void* dev) { return h.data() + (reinterpret_cast<const char*>(dev) - base); };
-  auto cp = [&](void* dst, const void* dev, size_t at, size_t count, size_t elem) { if (dst && count) memcpy(dst, H(dev) + at * elem, count * elem); };
-  const CandMapDev* maps = reinterpret_cast<const CandMapDev*>(H(b.maps));
-  for (int s = 0; s < n; ++s) {
-    const CandMapDev& M = maps[s];
-    plsvo_cand_map_out& O = out[s];
-    const size_t nk = (size_t)M.n_kf, np = (size_t)M.n_pt, ns = (size_t)M.n_seg, S = (size_t)s;
-    const int* kpo = reinterpret_cast<const int*>(H(b.kf_pt_off)) + M.kf_off + s; const int* kso = reinterpret_cast<const int*>(H(b.kf_seg_off)) + M.kf_off + s;
-    const int* poo = reinterpret_cast<const int*>(H(b.pt_obs_off)) + M.pt_off + s; const int* soo = reinterpret_cast<const int*>(H(b.seg_obs_off)) + M.seg_off + s;
-    const size_t kfpt = (size_t)kpo[nk], kfseg = (size_t)kso[nk], ptobs = (size_t)poo[np], segobs = (size_t)soo[ns];
-    O.n_kf = M.n_kf; O.n_pt = M.n_pt; O.n_seg = M.n_seg; O.n_pt_cand = M.n_pt_cand; O.n_seg_cand = M.n_seg_cand;
-    O.n_kf_pt = (int32_t)kfpt; O.n_kf_seg = (int32_t)kfseg; O.n_pt_obs = (int32_t)ptobs; O.n_seg_obs = (int32_t)segobs; O.reserved0 = 0;
-    cp(O.kf_T, b.kf_T, (size_t)M.kf_off * 7, nk * 7, sizeof(double)); cp(O.kf_slot, b.frame_slot, (size_t)M.f_off, nk, sizeof(int));
-    cp(O.kf_pt_off, b.kf_pt_off, (size_t)M.kf_off + S, nk + 1, sizeof(int)); cp(O.kf_seg_off, b.kf_seg_off, (size_t)M.kf_off + S, nk + 1, sizeof(int));
-    cp(O.kf_pt_lm, b.kf_pt_lm, (size_t)M.kfpt_off, kfpt, sizeof(int)); cp(O.kf_seg_lm, b.kf_seg_lm, (size_t)M.kfseg_off, kfseg, sizeof(int));
-    cp(O.pt_pos, b.pt_pos, (size_t)M.pt_off * 3, np * 3, sizeof(double)); cp(O.pt_type, b.pt_type, (size_t)M.pt_off, np, sizeof(int));
-    cp(O.pt_obs_off, b.pt_obs_off, (size_t)M.pt_off + S, np + 1, sizeof(int)); cp(O.pt_obs_kf, b.pt_obs_kf, (size_t)M.ptobs_off, ptobs, sizeof(int));
-    cp(O.pt_obs_px, b.pt_obs_px, (size_t)M.ptobs_off * 2, ptobs * 2, sizeof(double)); cp(O.pt_obs_f, b.pt_obs_f, (size_t)M.ptobs_off * 3, ptobs * 3, sizeof(double));
-    cp(O.pt_obs_level, b.pt_obs_level, (size_t)M.ptobs_off, ptobs, sizeof(int)); cp(O.pt_obs_type, b.pt_obs_type, (size_t)M.ptobs_off, ptobs, 1);
-    cp(O.pt_obs_grad, b.pt_obs_grad, (size_t)M.ptobs_off * 2, ptobs * 2, sizeof(double));
-    cp(O.seg_spos, b.seg_spos, (size_t)M.seg_off * 3, ns * 3, sizeof(double)); cp(O.seg_epos, b.seg_epos, (size_t)M.seg_off * 3, ns * 3, sizeof(double));
-    cp(O.seg_type, b.seg_type, (size_t)M.seg_off, ns, sizeof(int)); cp(O.seg_obs_off, b.seg_obs_off, (size_t)M.seg_off + S, ns + 1, sizeof(int));
-    cp(O.seg_obs_kf, b.seg_obs_kf, (size_t)M.segobs_off, segobs, sizeof(int));
-    cp(O.seg_obs_spx, b.seg_obs_spx, (size_t)M.segobs_off * 2, segobs * 2, sizeof(double)); cp(O.seg_obs_epx, b.seg_obs_epx, (size_t)M.segobs_off * 2, segobs * 2, sizeof(double));
-    cp(O.seg_obs_sf, b.seg_obs_sf, (size_t)M.segobs_off * 3, segobs * 3, sizeof(double)); cp(O.seg_obs_ef, b.seg_obs_ef, (size_t)M.segobs_off * 3, segobs * 3, sizeof(double));
-    cp(O.seg_obs_level, b.seg_obs_level, (size_t)M.segobs_off, segobs, sizeof(int));
-    cp(O.pt_cand, b.pt_cand, (size_t)M.ptc_off, (size_t)M.n_pt_cand, sizeof(int)); cp(O.seg_cand, b.seg_cand, (size_t)M.segc_off, (size_t)M.n_seg_cand, sizeof(int));
-  }
-  return PLSVO_OK;
-}
-
-extern "C" int plsvo_candidates_set_positions(plsvo_ctx* c, int n, const plsvo_cand_positions* in) {
-  CTX_CHECK(c);
-  if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_set_positions: no staged map tables");
-  if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_set_positions: n does not match the staged batch");
-  size_t t_pt = 0, t_seg = 0;
-  for (int s = 0; s < n; ++s) {
-    const plsvo_cand_positions& I = in[s]; const CandMapDev& M = c->cd_maps[(size_t)s];
-    if (I.n_pt < 0 || I.n_seg < 0) return fail(c, PLSVO_E_INVALID, "candidates_set_positions: negative count");
-    if ((I.n_pt > 0 && (!I.pt_idx || !I.pt_pos)) || (I.n_seg > 0 && (!I.seg_idx || !I.seg_spos || !I.seg_epos))) return fail(c, PLSVO_E_INVALID, "candidates_set_positions: null array");
-    if (!cand_idx_ok(I.pt_idx, (size_t)I.n_pt, 0, M.n_pt) || !cand_idx_ok(I.seg_idx, (size_t)I.n_seg, 0, M.n_seg)) return fail(c, PLSVO_E_INVALID, "candidates_set_positions: landmark index out of range");
-    t_pt += (size_t)I.n_pt; t_seg += (size_t)I.n_seg;
-  }
-  if (t_pt + t_seg == 0) return PLSVO_OK;
-  if (t_pt > (size_t)INT32_MAX || t_seg > (size_t)INT32_MAX) return fail(c, PLSVO_E_CAPACITY, "candidates_set_positions: batch too large");
-  HIP_TRY(c, hipSetDevice(c->device));
-  Blob blob;
-  const size_t b_pi = blob.reserve<long long>(t_pt), b_pp = blob.reserve<double>(t_pt * 3), b_si = blob.reserve<long long>(t_seg), b_ss = blob.reserve<double>(t_seg * 3),
-               b_se = blob.reserve<double>(t_seg * 3);
-  size_t ap = 0, as = 0;
-  for (int s = 0; s < n; ++s) {
-    const plsvo_cand_positions& I = in[s]; const CandMapDev& M = c->cd_maps[(size_t)s];
-    for (int k = 0; k < I.n_pt; ++k) blob.at<long long>(b_pi)[ap + (size_t)k] = M.pt_off + I.pt_idx[k];
-    if (I.n_pt) memcpy(blob.at<double>(b_pp) + 3 * ap, I.pt_pos, (size_t)I.n_pt * 3 * sizeof(double));
-    for (int k = 0; k < I.n_seg; ++k) blob.at<long long>(b_si)[as + (size_t)k] = M.seg_off + I.seg_idx[k];
-    if (I.n_seg) { memcpy(blob.at<double>(b_ss) + 3 * as, I.seg_spos, (size_t)I.n_seg * 3 * sizeof(double)); memcpy(blob.at<double>(b_se) + 3 * as, I.seg_epos, (size_t)I.n_seg * 3 * sizeof(double)); }
-    ap += (size_t)I.n_pt; as += (size_t)I.n_seg;
-  }
-  int rc;
-  if ((rc = upload_blob(c, c->ci_d_pos, blob))) return rc;
-  const char* d = reinterpret_cast<const char*>(c->ci_d_pos.p);
-  PositionsBatchDev p{};
-  p.n_pt = (int)t_pt; p.n_seg = (int)t_seg;
-  p.pt_at = reinterpret_cast<const long long*>(d + b_pi); p.pt_src = reinterpret_cast<const double*>(d + b_pp);
-  p.seg_at = reinterpret_cast<const long long*>(d + b_si); p.seg_ssrc = reinterpret_cast<const double*>(d + b_ss); p.seg_esrc = reinterpret_cast<const double*>(d + b_se);
-  p.pt_pos = const_cast<double*>(c->cd_b.pt_pos); p.seg_spos = const_cast<double*>(c->cd_b.seg_spos); p.seg_epos = const_cast<double*>(c->cd_b.seg_epos);
-  HIP_TRY(c, launch_map_set_positions(p, c->stream));
-  return PLSVO_OK;
-}
-
-// ---- new candidate landmarks appended to the resident map tables (newcand_device.hpp) -----------------------------------
-extern "C" int plsvo_candidates_reserve_landmarks(plsvo_ctx* c, const plsvo_cand_lm_reserve* r) {
-  CTX_CHECK(c);
-  if (r && (r->extra_pt < 0 || r->extra_seg < 0)) return fail(c, PLSVO_E_INVALID, "candidates_reserve_landmarks: negative room");
-  c->cn_reserve = r ? *r : plsvo_cand_lm_reserve{};
-  return PLSVO_OK;
-}
-
-extern "C" int plsvo_candidates_lm_capacity(plsvo_ctx* c, int n, plsvo_cand_lm_reserve* out) {
-  CTX_CHECK(c);
-  if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_lm_capacity: no staged map tables");
-  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_lm_capacity: n does not match the staged batch");
-  for (int s = 0; s < n; ++s) { out[s].extra_pt = c->cn_cap[4 * (size_t)s]; out[s].extra_seg = c->cn_cap[4 * (size_t)s + 1]; }
-  return PLSVO_OK;
-}
-
-extern "C" int plsvo_candidates_add(plsvo_ctx* c, int n, const plsvo_cand_new* in) {
-  CTX_CHECK(c);
-  if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_add: no staged map tables");
-  if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_add: n does not match the staged batch");
-  // -- every check before anything is written: arguments, then room (from the host's mirrors: landmark count, used observation entries)
-  size_t t_pt = 0, t_seg = 0;
-  int max_level = c->cd_max_level;
-  for (int s = 0; s < n; ++s) {
-    const plsvo_cand_new& I = in[s]; const CandMapDev& M = c->cd_maps[(size_t)s];
-    if (I.n_pt < 0 || I.n_seg < 0) return fail(c, PLSVO_E_INVALID, "candidates_add: negative count");
-    if (I.n_pt > 0 && (!I.pt_pos || !I.pt_obs_kf || !I.pt_obs_px || !I.pt_obs_f || !I.pt_obs_level || !I.pt_obs_type)) return fail(c, PLSVO_E_INVALID, "candidates_add: null point array");
-    if (I.n_seg > 0 && (!I.seg_spos || !I.seg_epos || !I.seg_obs_kf || !I.seg_obs_spx || !I.seg_obs_epx || !I.seg_obs_sf || !I.seg_obs_ef || !I.seg_obs_level))
-      return fail(c, PLSVO_E_INVALID, "candidates_add: null segment array");
-    if (!cand_idx_ok(I.pt_obs_kf, (size_t)I.n_pt, 0, M.n_kf) || !cand_idx_ok(I.seg_obs_kf, (size_t)I.n_seg, 0, M.n_kf)) return fail(c, PLSVO_E_INVALID, "candidates_add: observation keyframe outside the keyframe table");
-    if (!cand_idx_ok(I.pt_obs_level, (size_t)I.n_pt, 0, PLSVO_MAX_LEVELS) || !cand_idx_ok(I.seg_obs_level, (size_t)I.n_seg, 0, PLSVO_MAX_LEVELS))
-      return fail(c, PLSVO_E_INVALID, "candidates_add: observation level out of range");
-    for (int k = 0; k < I.n_pt; ++k) {
-      if (I.pt_obs_type[k] == PLSVO_FTR_EDGELET) { if (!I.pt_obs_grad) return fail(c, PLSVO_E_INVALID, "candidates_add: edgelets without pt_obs_grad"); }
-      else if (I.pt_obs_type[k] != PLSVO_FTR_CORNER) return fail(c, PLSVO_E_INVALID, "candidates_add: unknown feature type");
-      max_level = std::max(max_level, (int)I.pt_obs_level[k]);
-    }
-    for (int k = 0; k < I.n_seg; ++k) max_level = std::max(max_level, (int)I.seg_obs_level[k]);
-    t_pt += (size_t)I.n_pt; t_seg += (size_t)I.n_seg;
-  }
-  for (int s = 0; s < n; ++s) {
-    const plsvo_cand_new& I = in[s]; const CandMapDev& M = c->cd_maps[(size_t)s];
-    const int* lc = c->cn_cap.data() + 4 * (size_t)s; const int* cp = c->ci_cap.data() + 5 * (size_t)s; const int* us = c->ci_used.data() + 4 * (size_t)s;
-    if ((long long)M.n_pt + I.n_pt > lc[0] || (long long)M.n_seg + I.n_seg > lc[1])
-      return fail(c, PLSVO_E_CAPACITY, "candidates_add: a stream lacks landmark rows (plsvo_candidates_reserve_landmarks); nothing was changed");
-    if ((long long)us[2] + I.n_pt > cp[3] || (long long)us[3] + I.n_seg > cp[4])
-      return fail(c, PLSVO_E_CAPACITY, "candidates_add: a stream lacks observation entries (plsvo_candidates_reserve); nothing was changed");
-  }
-  const size_t N = (size_t)n;
-  c->cn_last.assign(N, plsvo_cand_add_out{});
-  for (int s = 0; s < n; ++s) {
-    const plsvo_cand_new& I = in[s]; const CandMapDev& M = c->cd_maps[(size_t)s];
-    plsvo_cand_add_out& O = c->cn_last[(size_t)s];
-    O.first_pt = I.n_pt ? M.n_pt : -1; O.first_seg = I.n_seg ? M.n_seg : -1; O.n_added_pt = I.n_pt; O.n_added_seg = I.n_seg;
-  }
-  c->cn_closed = true; c->cn_have_out = true;       // (an add of nothing ends the run too: the rule does not depend on the counts)
-  if (t_pt + t_seg == 0) return PLSVO_OK;
-  if (t_pt > (size_t)INT32_MAX || t_seg > (size_t)INT32_MAX) return fail(c, PLSVO_E_CAPACITY, "candidates_add: batch too large");
-  HIP_TRY(c, hipSetDevice(c->device));
-  Blob blob;
-  const size_t b_jobs = blob.reserve<NewCandJobDev>(N);
-  const size_t b_ppos = blob.reserve<double>(t_pt * 3), b_pkf = blob.reserve<int>(t_pt), b_ppx = blob.reserve<double>(t_pt * 2), b_pf = blob.reserve<double>(t_pt * 3),
-               b_plv = blob.reserve<int>(t_pt), b_pty = blob.reserve<uint8_t>(t_pt), b_pgr = blob.reserve<double>(t_pt * 2);
-  const size_t b_ss = blob.reserve<double>(t_seg * 3), b_se = blob.reserve<double>(t_seg * 3), b_skf = blob.reserve<int>(t_seg), b_sspx = blob.reserve<double>(t_seg * 2),
-               b_sepx = blob.reserve<double>(t_seg * 2), b_ssf = blob.reserve<double>(t_seg * 3), b_sef = blob.reserve<double>(t_seg * 3), b_slv = blob.reserve<int>(t_seg);
-  auto put = [&](size_t sec, size_t at, const void* src, size_t count, size_t elem) {
-    if (count) { if (src) memcpy(blob.host.data() + sec + at * elem, src, count * elem); else memset(blob.host.data() + sec + at * elem, 0, count * elem); }
-  };
-  size_t ap = 0, as = 0;
-  for (int s = 0; s < n; ++s) {
-    const plsvo_cand_new& I = in[s];
-    NewCandJobDev& J = blob.at<NewCandJobDev>(b_jobs)[s];
-    J.n_pt = I.n_pt; J.n_seg = I.n_seg; J.pt_at = (long long)ap; J.seg_at = (long long)as;
-    const size_t np = (size_t)I.n_pt, ns = (size_t)I.n_seg;
-    put(b_ppos, ap * 3, I.pt_pos, np * 3, sizeof(double)); put(b_pkf, ap, I.pt_obs_kf, np, sizeof(int)); put(b_ppx, ap * 2, I.pt_obs_px, np * 2, sizeof(double));
-    put(b_pf, ap * 3, I.pt_obs_f, np * 3, sizeof(double)); put(b_plv, ap, I.pt_obs_level, np, sizeof(int)); put(b_pty, ap, I.pt_obs_type, np, 1);
-    put(b_pgr, ap * 2, I.pt_obs_grad, np * 2, sizeof(double));
-    put(b_ss, as * 3, I.seg_spos, ns * 3, sizeof(double)); put(b_se, as * 3, I.seg_epos, ns * 3, sizeof(double)); put(b_skf, as, I.seg_obs_kf, ns, sizeof(int));
-    put(b_sspx, as * 2, I.seg_obs_spx, ns * 2, sizeof(double)); put(b_sepx, as * 2, I.seg_obs_epx, ns * 2, sizeof(double));
-    put(b_ssf, as * 3, I.seg_obs_sf, ns * 3, sizeof(double)); put(b_sef, as * 3, I.seg_obs_ef, ns * 3, sizeof(double)); put(b_slv, as, I.seg_obs_level, ns, sizeof(int));
-    ap += np; as += ns;
-  }
-  int rc;
-  if ((rc = upload_blob(c, c->cn_d_in, blob))) return rc;
-  const char* d = reinterpret_cast<const char*>(c->cn_d_in.p);
-  const QualitySections q = quality_sections(c);
-  char* dq = reinterpret_cast<char*>(c->cs_d_q.p);
-  auto D = [&](size_t o) { return reinterpret_cast<const double*>(d + o); };
-  auto Iv = [&](size_t o) { return reinterpret_cast<const int*>(d + o); };
-  NewCandBatchDev b{};
-  b.c = c->cd_b;
-  b.pt_nfail = reinterpret_cast<int*>(dq + q.pt_nf); b.pt_nsucc = reinterpret_cast<int*>(dq + q.pt_ns);
-  b.seg_nfail = reinterpret_cast<int*>(dq + q.seg_nf); b.seg_nsucc = reinterpret_cast<int*>(dq + q.seg_ns);
-  b.pt_event = reinterpret_cast<uint8_t*>(dq + q.pt_ev); b.seg_event = reinterpret_cast<uint8_t*>(dq + q.seg_ev);
-  b.jobs = reinterpret_cast<const NewCandJobDev*>(d + b_jobs);
-  b.pt_pos = D(b_ppos); b.pt_obs_kf = Iv(b_pkf); b.pt_obs_px = D(b_ppx); b.pt_obs_f = D(b_pf); b.pt_obs_level = Iv(b_plv);
-  b.pt_obs_type = reinterpret_cast<const uint8_t*>(d + b_pty); b.pt_obs_grad = D(b_pgr);
-  b.seg_spos = D(b_ss); b.seg_epos = D(b_se); b.seg_obs_kf = Iv(b_skf); b.seg_obs_spx = D(b_sspx); b.seg_obs_epx = D(b_sepx); b.seg_obs_sf = D(b_ssf);
-  b.seg_obs_ef = D(b_sef); b.seg_obs_level = Iv(b_slv);
-  {
-    EventPair ep{}; prof_begin(c, PLSVO_K_NEWCAND, &ep);
-    const hipError_t launched = launch_map_add_candidates(b, c->stream);
-    prof_end(c, PLSVO_K_NEWCAND, &ep);               // ahead of the error return, as in plsvo_candidates_run
-    HIP_TRY(c, launched);
-  }
-  // -- the host mirrors describe the new tables (the candidate counts are upper bounds: the selection shortens the lists on the device)
-  for (int s = 0; s < n; ++s) {
-    CandMapDev& M = c->cd_maps[(size_t)s]; int* us = c->ci_used.data() + 4 * (size_t)s;
-    M.n_pt += in[s].n_pt; M.n_seg += in[s].n_seg; M.n_pt_cand += in[s].n_pt; M.n_seg_cand += in[s].n_seg;
-    us[2] += in[s].n_pt; us[3] += in[s].n_seg;
-  }
-  c->cd_max_level = max_level;
-  return PLSVO_OK;
-}
-
-extern "C" int plsvo_candidates_add_fetch(plsvo_ctx* c, int n, plsvo_cand_add_out* out) {
-  CTX_CHECK(c);
-  if (!c->cd_staged || !c->cn_have_out) return fail(c, PLSVO_E_STATE, "candidates_add_fetch: no add since the tables were staged");
-  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_add_fetch: n does not match the staged batch");
-  if (n == 0) return PLSVO_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  std::vector<CandMapDev> maps((size_t)n);         // the candidate counts as they stand are the device's
-  HIP_TRY(c, hipMemcpyAsync(maps.data(), c->cd_b.maps, (size_t)n * sizeof(CandMapDev), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (int s = 0; s < n; ++s) {
-    const CandMapDev& M = maps[(size_t)s]; const int* us = c->ci_used.data() + 4 * (size_t)s;
-    out[s] = c->cn_last[(size_t)s];
-    out[s].n_pt = M.n_pt; out[s].n_seg = M.n_seg; out[s].n_pt_cand = M.n_pt_cand; out[s].n_seg_cand = M.n_seg_cand; out[s].n_pt_obs = us[2]; out[s].n_seg_obs = us[3];
-  }
-  return PLSVO_OK;
 }
 
 // ---- trajectory record (host only; app/run_pipeline.cpp:425-451) ---------------------------------------
@@ -3513,14 +2252,14 @@ RecordSource pick_record_source(plsvo_ctx* c) {
   RecordSource r;
   if (c->ch_staged && c->a_staged && c->a_n == c->ch_n) {   // the resident frame step: its own pose-optimisation state
     if (c->ch_run_seq == 0) { r.why_not = "pack_pose_records: the staged frame step has not run"; return r; }
-    r.ast = c->a_d_state.as<AlignStateDev>(); r.pst = c->ch_d_state.as<PoseStateDev>(); r.n = c->ch_n;
+    r.ast = c->a_d_state.as<AlignStateDev>(); r.pst = c->ch_w.state.as<PoseStateDev>(); r.n = c->ch_n;
     return r;
   }
   // both batches when they describe the same streams (same size); otherwise the one that ran last
   const bool use_a = c->a_staged && c->a_run_seq > 0, use_p = c->p_staged && c->p_run_seq > 0;
   const bool both = use_a && use_p && c->a_n == c->p_n;
   if (use_a && (both || !use_p || c->a_run_seq > c->p_run_seq)) { r.ast = c->a_d_state.as<AlignStateDev>(); r.n = c->a_n; }
-  if (use_p && (both || !use_a || c->p_run_seq > c->a_run_seq)) { r.pst = c->p_d_state.as<PoseStateDev>(); r.n = c->p_n; }
+  if (use_p && (both || !use_a || c->p_run_seq > c->a_run_seq)) { r.pst = c->p_w.state.as<PoseStateDev>(); r.n = c->p_n; }
   if (!r.ast && !r.pst) r.why_not = "pack_pose_records: no staged batch has run";
   return r;
 }

@@ -98,6 +98,11 @@ void plsvo_hip_destroy(plsvo_ctx* ctx);
  * with a row of more than 320 values takes the latter either way.  An order statistic has one value: every result is bit-identical.
  * The environment switch PLSVO_POSEOPT_SELECT=0 sets the initial value to 0. */
 #define PLSVO_OPT_POSEOPT_SELECT 8
+/* 6x6 solve of the alignment's Gauss-Newton iteration, every launch shape: 1 (default) = six distinct, non-NaN |diagonals| fix Eigen's
+ * pivot order before the first elimination step, so the order is sorted once and the six steps run without a pivot search; exact ties
+ * and NaN diagonals take the search; 0 = the search in every step.  Same arithmetic in the same order: every result is bit-identical.
+ * The environment switch PLSVO_ALIGN_STATIC_SOLVE=0 sets the initial value to 0. */
+#define PLSVO_OPT_ALIGN_STATIC_SOLVE 9
 int plsvo_hip_set_option(plsvo_ctx* ctx, int option, int value);
 const char* plsvo_hip_last_error(const plsvo_ctx* ctx);   /* ctx may be NULL: last create error */
 void* plsvo_hip_stream(plsvo_ctx* ctx);                   /* the hipStream_t all work is enqueued on */

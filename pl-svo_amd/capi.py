@@ -251,6 +251,11 @@ class Context:
         differs, rank finish; False = the radix select over memory, every digit (PLSVO_OPT_POSEOPT_SELECT); results bit-identical"""
         self._chk(self.L.plsvo_hip_set_option(self.h, 8, 1 if on else 0))
 
+    def set_align_static_solve(self, on):
+        """6x6 solve of the alignment: True (default) = pivot order sorted once from the diagonals, exact ties and NaN diagonals take the
+        search; False = the pivot search in every elimination step (PLSVO_OPT_ALIGN_STATIC_SOLVE); results bit-identical"""
+        self._chk(self.L.plsvo_hip_set_option(self.h, 9, 1 if on else 0))
+
     def close(self):
         if getattr(self, "h", None):
             self.L.plsvo_hip_destroy(self.h)

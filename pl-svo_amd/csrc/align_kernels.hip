@@ -1146,9 +1146,9 @@ __global__ __launch_bounds__(T, kMinWavesPerSimd) void align_fused_kernel(AlignB
         if (lane < 32 && !terms_only) s_tot[lane] = tot;   // (0..26 the system, 27..30 chi2 / n_meas / work counters: a terms-only re-run reads them back)
         TICK(3);
         double x[6];
-        // (static pivot order in the latency shapes only: the throughput shapes sit at 255-256 registers without scratch, and the few
-        //  values the shorter solve keeps live across the iteration tip them into spilling -- there the solve is 2 % of a launch)
-        wave_solve6_reg(tot, x, job.ldlt_flavour, kQuad);                      // solve() :699
+        // (static pivot order in every shape, wave-uniform switch b.static_solve: the values the shorter solve keeps live across the
+        //  iteration fit the throughput shapes' registers since this unit is built without SLP packing -- Makefile)
+        wave_solve6_reg(tot, x, job.ldlt_flavour, b.static_solve != 0);        // solve() :699
         TICK(4);
         const double chi_sum = readlane_f64(tot, 27), nm_d = readlane_f64(tot, 28), ev_d = readlane_f64(tot, 29), ev_pt = readlane_f64(tot, 30);
         const unsigned long long nm = (unsigned long long)(nm_d + 0.5);

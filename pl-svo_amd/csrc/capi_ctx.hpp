@@ -195,6 +195,8 @@ struct plsvo_ctx {
   int env_poseopt_refill_min = 0, env_poseopt_refill_waves = 0;
   // medians of the row kernels (poseopt_select.hpp): values once into registers, rank finish -- PLSVO_OPT_POSEOPT_SELECT; false = row_radix_select everywhere
   bool opt_poseopt_select = true;
+  // 6x6 solve of the alignment (plsvo_wave.hpp::wave_solve6_core): pivot order sorted once, no per-step search -- PLSVO_OPT_ALIGN_STATIC_SOLVE; false = the search in every step
+  bool opt_align_static_solve = true;
   bool p_any_ref = false;                   //   a job of the staged batch has a refinement loop (n_iter_ref > 0): pose_opt_rows_kernel
   int p_refill_frames = 0;                  //   frames the last pose-optimiser launch ran through the three launches
   DevBuf p_d_carry, p_d_refill_next;        //   PoseRefillCarry per job; the queue's counter

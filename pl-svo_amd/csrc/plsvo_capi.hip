@@ -97,6 +97,7 @@ static int create_ctx(int device_id, void* stream, bool use_given_stream, plsvo_
   if (const char* s = getenv("PLSVO_POSEOPT_REORDER_MIN")) c->env_poseopt_reorder_min = atoi(s);
   if (const char* s = getenv("PLSVO_POSEOPT_REFILL")) c->opt_poseopt_refill = atoi(s) != 0;
   if (const char* s = getenv("PLSVO_POSEOPT_SELECT")) c->opt_poseopt_select = atoi(s) != 0;
+  if (const char* s = getenv("PLSVO_ALIGN_STATIC_SOLVE")) c->opt_align_static_solve = atoi(s) != 0;
   if (const char* s = getenv("PLSVO_POSEOPT_REFILL_MIN")) c->env_poseopt_refill_min = atoi(s);
   if (const char* s = getenv("PLSVO_POSEOPT_REFILL_WAVES")) c->env_poseopt_refill_waves = atoi(s);
   c->env_host_timing = getenv("PLSVO_HOST_TIMING") != nullptr;
@@ -167,6 +168,11 @@ extern "C" int plsvo_hip_set_option(plsvo_ctx* c, int option, int value) {
   if (option == PLSVO_OPT_POSEOPT_SELECT) {
     if (value != 0 && value != 1) return fail(c, PLSVO_E_INVALID, "set_option: the row kernels' median select is 0 (radix select over memory, every digit) or 1 (values in registers, rank finish)");
     c->opt_poseopt_select = value != 0;
+    return PLSVO_OK;
+  }
+  if (option == PLSVO_OPT_ALIGN_STATIC_SOLVE) {
+    if (value != 0 && value != 1) return fail(c, PLSVO_E_INVALID, "set_option: the alignment's static-order solve is 0 (pivot search in every elimination step) or 1 (pivot order sorted once, search on ties and NaN only)");
+    c->opt_align_static_solve = value != 0;
     return PLSVO_OK;
   }
   return fail(c, PLSVO_E_INVALID, "set_option: unknown option");
@@ -919,7 +925,7 @@ extern "C" int plsvo_align_stage(plsvo_ctx* c, int n, const plsvo_align_in* in) 
   b.log = c->a_trace_cap > 0 ? c->a_d_log.as<plsvo_align_iterlog>() : nullptr;
   b.log_cap = c->a_trace_cap;
   b.n_jobs = n;
-  b.pair = 0; b.xseq0 = 0; b.xbuf = nullptr; b.work_key = nullptr; b.tail_n = 0; b.reserved_tail = 0; b.tail_flag = nullptr; b.seg_alive_tail = nullptr;   // (plsvo_align_run decides)
+  b.pair = 0; b.xseq0 = 0; b.xbuf = nullptr; b.work_key = nullptr; b.tail_n = 0; b.static_solve = 1; b.tail_flag = nullptr; b.seg_alive_tail = nullptr;   // (plsvo_align_run decides)
   b.order = reinterpret_cast<const int*>(base + o_order);
   c->a_stage_order = b.order;
   c->a_jobs.swap(jobs);
@@ -1023,6 +1029,7 @@ extern "C" int plsvo_align_run(plsvo_ctx* c) {
   const bool pair = threads >= kQuadMinThreads && chi_lds_pts > 0 && c->a_seg_align == 64 && 2 * c->a_n <= cus_run && !c->env_align_no_pair &&
                     !c->env_align_per_level && have_levels && max_exchanges < 1024;
   c->a_b.pair = pair ? 1 : 0;
+  c->a_b.static_solve = c->opt_align_static_solve ? 1 : 0;
   if (pair) {
     const size_t xbytes = (size_t)c->a_n * 256 * sizeof(unsigned long long);
     if (c->a_d_xbuf.cap < xbytes) {

@@ -138,7 +138,8 @@ struct AlignBatchDev {
   // same launch -- the coarse levels first of all, the finest level last of all -- and hand the frame's state over through
   // AlignStateDev / seg_alive and one flag word each (align_kernels.hip::align_fused_kernel).  0 = every frame is one workgroup.
   int tail_n;
-  int reserved_tail;
+  int static_solve;            // wave-uniform: 1 = the 6x6 solve takes the static pivot order when the diagonals allow it (plsvo_wave.hpp::wave_solve6_core),
+                               //               0 = always the per-step pivot search (PLSVO_OPT_ALIGN_STATIC_SOLVE); bit-identical results
   unsigned int* tail_flag;     // tail_n words, zeroed before every launch; 1 = the coarse part of tail frame t has published its state
   uint8_t* seg_alive_tail;     // a coarse part's working copy of the segment flags (layout of seg_alive): it never stores into seg_alive or the
                                // state with ordinary stores, so no dirty byte of its L2 can land on what the fine part writes later

@@ -1173,8 +1173,9 @@ int plsvo_trajectory_record(const double T_f_w[7], const double cov[36], double 
 /* findEpipolarMatchDirectSegmentEndpoint (:422-586), depthFromTriangulation (:133-146),       */
 /* [ext] vk::patch_score::ZMSSD<4>, DepthFilter::computeTau (src/depth_filter.cpp:568-584),    */
 /* updatePointSeed (:489-512), updateLineSeed (:514-566).                                      */
-/* The seed lists, the batch-age test (:289-292), the converged-seed callbacks and the         */
-/* detector's grid occupancy stay on the host; this call maps seed state -> seed state.        */
+/* This call maps seed state -> seed state for lists the caller keeps: the batch-age test      */
+/* (:289-292), the erasing and the converged-seed callbacks are the caller's.  plsvo_seeds_*   */
+/* below keep the lists on the device.  The detector's grid occupancy stays on the host.       */
 /* ------------------------------------------------------------------------------------------ */
 
 #define PLSVO_SEED_NOT_VISIBLE 0    /* behind the camera or outside the image: unchanged (:296-304) */
@@ -1238,6 +1239,128 @@ typedef struct plsvo_seeds_out {     /* caller buffers; any of them may be NULL 
 int plsvo_update_seeds(plsvo_ctx* ctx, const plsvo_seeds_in* in, plsvo_seeds_out* out);
 
 /* ------------------------------------------------------------------------------------------ */
+/* depth-filter seed lists resident on the device: the list half of           */
+/* DepthFilter -- initializeSeeds (src/depth_filter.cpp:177-191), removeKeyframe (:199-216),   */
+/* and in updatePointSeeds / updateLineSeeds (:270-365, :367-471) the age test (:289-292), the */
+/* erasing of converged and NaN seeds and the converged-seed callbacks (:334-360, :439-467).   */
+/* The per-seed body is plsvo_update_seeds', bit for bit; a converged seed becomes a candidate */
+/* landmark of the resident map tables exactly as plsvo_candidates_add writes one, without     */
+/* leaving the device.  The seed tables belong to the staged candidate tables of the same ctx: */
+/* ref_kf indexes the stream's resident keyframe table as it stands.                           */
+/* Departures from the reference, on purpose: Seed::batch_counter (one static for both kinds   */
+/* and every filter, :44) is one counter PER STREAM; removeKeyframe erases only the POINT      */
+/* seeds of the keyframe and leaves line seeds pointing at a frame that may be gone -- here    */
+/* the line seeds of a removed keyframe are erased too.                                        */
+/* ------------------------------------------------------------------------------------------ */
+
+#define PLSVO_SEED_AGED        5    /* batch_counter - batch_id > max_n_kfs: erased without an update (:289-292); resident lists only */
+#define PLSVO_SEEDS_NO_ROOM    1    /* plsvo_seed_report.no_room */
+
+/* Rows per stream and kind beyond the staged list lengths, for the NEXT and every later plsvo_seeds_stage. */
+typedef struct plsvo_seed_reserve {
+  int32_t extra_pt, extra_seg;
+} plsvo_seed_reserve;
+
+/* plsvo_seeds_in's parameters, and DepthFilter::Options::max_n_kfs */
+typedef struct plsvo_seed_params {
+  plsvo_pinhole cam;
+  int32_t n_pyr_levels, align_max_iter, max_epi_search_steps, edgelet_filtering;
+  double edgelet_max_angle, px_noise, convergence_sigma2_thresh;
+  int32_t max_n_kfs, reserved0;
+} plsvo_seed_params;
+
+/* One stream's lists, in list order (input of the stage; caller buffers of plsvo_seeds_fetch_lists, each with room for the stream's
+ * capacity rows, any of them NULL).  The float fields are plsvo_seeds_in's; spx / epx are LineFeat's end points in pixels, which ride
+ * along for the landmark's observation only. */
+typedef struct plsvo_seed_list {
+  int32_t n_pt, n_seg, batch_counter, reserved0;
+  int32_t* pt_ref_kf; int32_t* pt_batch_id;
+  double* pt_px; double* pt_f; int32_t* pt_level; uint8_t* pt_type;
+  double* pt_grad;                  /* 2 per seed; may be NULL at the stage without edgelets (zeros are stored) */
+  float* pt_a; float* pt_b; float* pt_mu; float* pt_z_range; float* pt_sigma2;
+  int32_t* seg_ref_kf; int32_t* seg_batch_id;
+  double* seg_px; double* seg_f; double* seg_sf; double* seg_ef; double* seg_spx; double* seg_epx; int32_t* seg_level;
+  float* seg_a; float* seg_b; float* seg_mu_s; float* seg_mu_e; float* seg_z_range_s; float* seg_z_range_e; float* seg_sigma2_s; float* seg_sigma2_e;
+} plsvo_seed_list;
+
+/* One stream's frame of an update.  pose_source: PLSVO_INSERT_POSE_* (RESIDENT: the optimised pose of plsvo_candidates_pose_optimize). */
+typedef struct plsvo_seed_frame {
+  int32_t active, cur_slot, pose_source, reserved0;
+  double T_f_w[7];
+  const double* d_T_f_w;
+} plsvo_seed_frame;
+
+/* What the last update did to one stream and its sizes as they stand.  pt / seg: rows per PLSVO_SEED_* status. */
+typedef struct plsvo_seed_report {
+  int32_t pt[6], seg[6];
+  int32_t first_pt, first_seg;      /* index of the first new landmark per kind, -1 for none */
+  int32_t n_pt_seeds, n_seg_seeds;  /* list lengths */
+  int32_t n_pt, n_seg, n_pt_cand, n_seg_cand, n_pt_obs, n_seg_obs;   /* the map tables */
+  int32_t no_room;                  /* PLSVO_SEEDS_NO_ROOM: the update of this stream was dropped as a whole */
+  int32_t batch_counter;
+} plsvo_seed_report;
+
+/* One stream's keyframe event, applied in this order: removeKeyframe(removed_kf), ++batch_counter if new_batch, the new seeds
+ * appended with ref_kf = new_kf (an index of the keyframe table as it stands NOW, after the insertion that closed it up). */
+typedef struct plsvo_seed_kf {
+  int32_t removed_kf;               /* -1: none */
+  int32_t new_batch, new_kf, n_pt, n_seg, reserved0;
+  double depth_mean, depth_min;     /* initializeSeeds' arguments, used as floats like the Seed constructor's (:53-74) */
+  const double* pt_px; const double* pt_f; const int32_t* pt_level; const uint8_t* pt_type; const double* pt_grad;
+  const double* seg_px; const double* seg_f; const double* seg_sf; const double* seg_ef; const double* seg_spx; const double* seg_epx; const int32_t* seg_level;
+} plsvo_seed_kf;
+
+/* The shadow rows of one stream: what the update launch leaves per seed, in the list order before that update.  Input of the
+ * diagnostic plsvo_seeds_commit_rows (status, parameters and xyz_world; n_pt / n_seg must be the list lengths), caller buffers of
+ * plsvo_seeds_fetch_rows (any of them NULL; n_pt / n_seg are written). */
+typedef struct plsvo_seed_rows {
+  int32_t n_pt, n_seg, active, reserved0;
+  int32_t* pt_status; float* pt_a; float* pt_b; float* pt_mu; float* pt_sigma2; double* pt_xyz_world; double* pt_px_cur; double* pt_depth;
+  int32_t* seg_status; float* seg_a; float* seg_b; float* seg_mu_s; float* seg_mu_e; float* seg_sigma2_s; float* seg_sigma2_e;
+  double* seg_xyz_world_s; double* seg_xyz_world_e; double* seg_depth_s; double* seg_depth_e;
+} plsvo_seed_rows;
+
+/* Every check of every call runs on the host before anything is written; every call needs n == the staged n.
+ * reserve: host only; PLSVO_E_INVALID for a negative field.  capacity: the rows per kind a stream's lists may hold (fields of
+ *   plsvo_seed_reserve): the staged length plus the reserve in force at the stage.
+ * stage: the lists with their batch ids and the stream's batch counter.  PLSVO_E_STATE without staged candidate tables of the same n
+ *   or without pyramids; PLSVO_E_INVALID for a negative count, a NULL array with a non-zero count (pt_grad excepted), a ref_kf outside
+ *   the stream's keyframe table, a level outside the pyramid, an unknown feature type, an edgelet without pt_grad under edgelet
+ *   filtering, parameters plsvo_update_seeds refuses.  A later plsvo_candidates_stage drops the seed tables (the caller restages both):
+ *   every seed call returns PLSVO_E_STATE until plsvo_seeds_stage is called again.
+ * update: enqueue only -- the update launch (one lane per row, plsvo_update_seeds' body; the reference keyframe's pose and slot come
+ *   from the resident keyframe table), then the commit launch (one wave per stream): aged, converged and NaN rows are erased, the
+ *   list closes up in order, every converged row is appended to the map tables as plsvo_candidates_add would append it, in list
+ *   order.  A stream whose map tables lack room for ALL its converged rows (landmark rows, observation entries, candidate lists) is
+ *   reported PLSVO_SEEDS_NO_ROOM and neither its seed tables nor its map tables change; the other streams are not affected.  The
+ *   caller restages with room and repeats the update.  It ends the open run as plsvo_candidates_add does and is legal behind an
+ *   insertion.  PLSVO_E_INVALID for an unknown pose source, PLSVO_INSERT_POSE_DEV without a pointer, a negative slot or one outside
+ *   the pyramids; PLSVO_E_STATE for PLSVO_INSERT_POSE_RESIDENT without a resident pose optimisation, and behind an unfetched update.
+ * update_fetch: synchronises, returns the reports and refreshes the host's mirrors of the candidate tables (landmark counts, used
+ *   observation entries, candidate counts), which plsvo_candidates_add, the insertion and the sizes of fetch_map / fetch_quality /
+ *   set_quality depend on.  Between an update and this fetch every plsvo_candidates_* call that reads or moves the tables, and
+ *   plsvo_seeds_keyframe / _fetch_lists / _fetch_rows / _commit_rows, return PLSVO_E_STATE; the fetches of the closed run keep working.
+ * keyframe: enqueue only after the copy of the new seeds.  PLSVO_E_CAPACITY (nothing written) when a list would outgrow its rows,
+ *   decided from the mirrored list lengths, which are exact after an update fetch and upper bounds after a keyframe event with a
+ *   removal; PLSVO_E_INVALID for removed_kf outside [-1, n_kf] (the table as it stood before the insertion closed it up held at most
+ *   one keyframe more), new_kf outside the table with new seeds, a level outside the pyramid, an unknown type, a non-positive depth,
+ *   a NULL array with a non-zero count (pt_grad excepted without edgelets).
+ * fetch_lists / fetch_rows: synchronise.  fetch_rows returns the last fetched update's rows (for setGridOccpuancy, :327-331,
+ *   :432-436, and for tests); PLSVO_E_STATE before one.
+ * commit_rows: a DIAGNOSTIC, synchronous, modelled on plsvo_candidates_set_match: uploads caller-made shadow rows in place of the
+ *   update launch and runs the commit launch; plsvo_seeds_update_fetch follows it as it follows an update.  The row counts are checked
+ *   against the mirrored list lengths: behind a keyframe event with a removal, plsvo_seeds_fetch_lists makes them exact first. */
+int plsvo_seeds_reserve(plsvo_ctx* ctx, const plsvo_seed_reserve* reserve);
+int plsvo_seeds_capacity(plsvo_ctx* ctx, int n, plsvo_seed_reserve* out);
+int plsvo_seeds_stage(plsvo_ctx* ctx, int n, const plsvo_seed_params* params, const plsvo_seed_list* lists);
+int plsvo_seeds_update(plsvo_ctx* ctx, int n, const plsvo_seed_frame* frames);
+int plsvo_seeds_update_fetch(plsvo_ctx* ctx, int n, plsvo_seed_report* out);
+int plsvo_seeds_keyframe(plsvo_ctx* ctx, int n, const plsvo_seed_kf* in);
+int plsvo_seeds_fetch_lists(plsvo_ctx* ctx, int n, plsvo_seed_list* out);
+int plsvo_seeds_fetch_rows(plsvo_ctx* ctx, int n, plsvo_seed_rows* out);
+int plsvo_seeds_commit_rows(plsvo_ctx* ctx, int n, const plsvo_seed_rows* rows);
+
+/* ------------------------------------------------------------------------------------------ */
 /* multi-GPU: gather of per-stream pose records (new; the reference is single-process)         */
 /* ------------------------------------------------------------------------------------------ */
 
@@ -1261,7 +1384,8 @@ typedef struct plsvo_pose_record {
 } plsvo_pose_record;
 
 /* Writes one record per stream of the resident batch into device memory (d_dst: n records), enqueued on the ctx stream after the
- * launches that produce them: the resident frame step (plsvo_chain_stage) if one is staged, else the staged alignment and
+ * launches that produce them: the resident frame step (plsvo_chain_stage) if one is staged and no staged pose-optimisation batch has
+ * run since it was staged and last ran, else the staged alignment and
  * pose-optimisation batches that have run -- both when they have the same number of jobs (one job of each per stream), otherwise the
  * one that ran last.  *n_out (may be NULL) receives the record count. */
 int plsvo_pack_pose_records(plsvo_ctx* ctx, plsvo_pose_record* d_dst, int* n_out);
@@ -1284,12 +1408,12 @@ int plsvo_gather_poses(plsvo_ctx* ctx, void* rccl_comm, const plsvo_pose_record*
 #define PLSVO_K_HALFSAMPLE    3
 #define PLSVO_K_STRUCTOPT     4
 #define PLSVO_K_MATCH         5
-#define PLSVO_K_SEEDS         6
+#define PLSVO_K_SEEDS         6   /* plsvo_update_seeds and the update launch of plsvo_seeds_update */
 #define PLSVO_K_KEYFRAME      7   /* plsvo_close_keyframes / plsvo_keyframe_decide: the launch alone, without packing and copies */
 #define PLSVO_K_CANDIDATES    8   /* plsvo_candidates_run: the re-arm and the launch alone (the resident match counts under PLSVO_K_MATCH) */
 #define PLSVO_K_SELECT        9   /* plsvo_candidates_select: the re-arm and the launch alone */
 #define PLSVO_K_INSERT        10  /* plsvo_candidates_insert_keyframe: the launch that changes the tables (the planning launch is timed by the caller's clock) */
-#define PLSVO_K_NEWCAND       11  /* plsvo_candidates_add: the launch alone */
+#define PLSVO_K_NEWCAND       11  /* plsvo_candidates_add: the launch alone; the commit launch of plsvo_seeds_update, plsvo_seeds_keyframe's */
 #define PLSVO_K_COUNT         12
 int plsvo_hip_set_profiling(plsvo_ctx* ctx, int enable);
 /* accumulated GPU time and launch count of kernel family k since the last reset (synchronises) */

@@ -316,6 +316,62 @@ class CandAddOut(C.Structure):
     _fields_ = [(f, C.c_int32) for f in ("first_pt", "first_seg", "n_added_pt", "n_added_seg", "n_pt", "n_seg", "n_pt_cand", "n_seg_cand", "n_pt_obs", "n_seg_obs")]
 
 
+SEED_NOT_VISIBLE, SEED_NO_MATCH, SEED_UPDATED, SEED_CONVERGED, SEED_NAN, SEED_AGED = 0, 1, 2, 3, 4, 5
+SEEDS_NO_ROOM = 1
+_c_float_p = C.POINTER(C.c_float)
+_SEED_CT = dict(i=(c_i32_p, np.int32), b=(c_u8_p, np.uint8), d=(c_double_p, np.float64), f=(_c_float_p, np.float32))
+# (field, element type, width) of the resident seed lists' structs, in the C order
+_SEED_LIST_FIELDS = (("pt_ref_kf", "i", 1), ("pt_batch_id", "i", 1), ("pt_px", "d", 2), ("pt_f", "d", 3), ("pt_level", "i", 1), ("pt_type", "b", 1), ("pt_grad", "d", 2),
+                     ("pt_a", "f", 1), ("pt_b", "f", 1), ("pt_mu", "f", 1), ("pt_z_range", "f", 1), ("pt_sigma2", "f", 1),
+                     ("seg_ref_kf", "i", 1), ("seg_batch_id", "i", 1), ("seg_px", "d", 2), ("seg_f", "d", 3), ("seg_sf", "d", 3), ("seg_ef", "d", 3), ("seg_spx", "d", 2),
+                     ("seg_epx", "d", 2), ("seg_level", "i", 1), ("seg_a", "f", 1), ("seg_b", "f", 1), ("seg_mu_s", "f", 1), ("seg_mu_e", "f", 1), ("seg_z_range_s", "f", 1),
+                     ("seg_z_range_e", "f", 1), ("seg_sigma2_s", "f", 1), ("seg_sigma2_e", "f", 1))
+_SEED_KF_FIELDS = (("pt_px", "d", 2), ("pt_f", "d", 3), ("pt_level", "i", 1), ("pt_type", "b", 1), ("pt_grad", "d", 2),
+                   ("seg_px", "d", 2), ("seg_f", "d", 3), ("seg_sf", "d", 3), ("seg_ef", "d", 3), ("seg_spx", "d", 2), ("seg_epx", "d", 2), ("seg_level", "i", 1))
+_SEED_ROWS_FIELDS = (("pt_status", "i", 1), ("pt_a", "f", 1), ("pt_b", "f", 1), ("pt_mu", "f", 1), ("pt_sigma2", "f", 1), ("pt_xyz_world", "d", 3), ("pt_px_cur", "d", 2),
+                     ("pt_depth", "d", 1), ("seg_status", "i", 1), ("seg_a", "f", 1), ("seg_b", "f", 1), ("seg_mu_s", "f", 1), ("seg_mu_e", "f", 1), ("seg_sigma2_s", "f", 1),
+                     ("seg_sigma2_e", "f", 1), ("seg_xyz_world_s", "d", 3), ("seg_xyz_world_e", "d", 3), ("seg_depth_s", "d", 1), ("seg_depth_e", "d", 1))
+
+
+class SeedReserve(C.Structure):
+    """plsvo_seed_reserve"""
+    _fields_ = [("extra_pt", C.c_int32), ("extra_seg", C.c_int32)]
+
+
+class SeedParams(C.Structure):
+    """plsvo_seed_params"""
+    _fields_ = [("cam", Pinhole), ("n_pyr_levels", C.c_int32), ("align_max_iter", C.c_int32), ("max_epi_search_steps", C.c_int32), ("edgelet_filtering", C.c_int32),
+                ("edgelet_max_angle", C.c_double), ("px_noise", C.c_double), ("convergence_sigma2_thresh", C.c_double), ("max_n_kfs", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class SeedList(C.Structure):
+    """plsvo_seed_list"""
+    _fields_ = [(f, C.c_int32) for f in ("n_pt", "n_seg", "batch_counter", "reserved0")] + [(f, _SEED_CT[t][0]) for f, t, _ in _SEED_LIST_FIELDS]
+
+
+class SeedFrame(C.Structure):
+    """plsvo_seed_frame"""
+    _fields_ = [(f, C.c_int32) for f in ("active", "cur_slot", "pose_source", "reserved0")] + [("T_f_w", C.c_double * 7), ("d_T_f_w", C.c_void_p)]
+
+
+class SeedReport(C.Structure):
+    """plsvo_seed_report"""
+    _fields_ = [("pt", C.c_int32 * 6), ("seg", C.c_int32 * 6)] + \
+               [(f, C.c_int32) for f in ("first_pt", "first_seg", "n_pt_seeds", "n_seg_seeds", "n_pt", "n_seg", "n_pt_cand", "n_seg_cand", "n_pt_obs", "n_seg_obs", "no_room",
+                                         "batch_counter")]
+
+
+class SeedKf(C.Structure):
+    """plsvo_seed_kf"""
+    _fields_ = [(f, C.c_int32) for f in ("removed_kf", "new_batch", "new_kf", "n_pt", "n_seg", "reserved0")] + [("depth_mean", C.c_double), ("depth_min", C.c_double)] + \
+               [(f, _SEED_CT[t][0]) for f, t, _ in _SEED_KF_FIELDS]
+
+
+class SeedRows(C.Structure):
+    """plsvo_seed_rows"""
+    _fields_ = [(f, C.c_int32) for f in ("n_pt", "n_seg", "active", "reserved0")] + [(f, _SEED_CT[t][0]) for f, t, _ in _SEED_ROWS_FIELDS]
+
+
 class CandDev(C.Structure):
     """plsvo_cand_dev"""
     _fields_ = [("n_entries", C.c_int64), ("n_frames", C.c_int64), ("m_off", C.POINTER(C.c_int64)), ("f_off", C.POINTER(C.c_int64))] + \

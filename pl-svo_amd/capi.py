@@ -32,6 +32,8 @@ SYMBOLS = [
     "plsvo_candidates_pose_fetch", "plsvo_candidates_poses_dev", "plsvo_candidates_set_match",
     "plsvo_candidates_reserve", "plsvo_candidates_capacity", "plsvo_candidates_insert_keyframe", "plsvo_candidates_insert_fetch", "plsvo_candidates_fetch_map", "plsvo_candidates_set_positions",
     "plsvo_candidates_reserve_landmarks", "plsvo_candidates_lm_capacity", "plsvo_candidates_add", "plsvo_candidates_add_fetch",
+    "plsvo_seeds_reserve", "plsvo_seeds_capacity", "plsvo_seeds_stage", "plsvo_seeds_update", "plsvo_seeds_update_fetch", "plsvo_seeds_keyframe", "plsvo_seeds_fetch_lists",
+    "plsvo_seeds_fetch_rows", "plsvo_seeds_commit_rows",
     "plsvo_chain_stage", "plsvo_chain_run", "plsvo_chain_fetch", "plsvo_frame_step_batch", "plsvo_chain_poses_dev",
     "plsvo_pack_pose_records", "plsvo_fetch_pose_records", "plsvo_gather_poses",
     "plsvo_hip_set_profiling", "plsvo_hip_kernel_time", "plsvo_hip_reset_profiling",
@@ -170,6 +172,15 @@ def lib():
         "plsvo_candidates_lm_capacity": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandLmReserve)]),
         "plsvo_candidates_add": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandNew)]),
         "plsvo_candidates_add_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandAddOut)]),
+        "plsvo_seeds_reserve": (C.c_int, [ctxp, C.POINTER(abi.SeedReserve)]),
+        "plsvo_seeds_capacity": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.SeedReserve)]),
+        "plsvo_seeds_stage": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.SeedParams), C.POINTER(abi.SeedList)]),
+        "plsvo_seeds_update": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.SeedFrame)]),
+        "plsvo_seeds_update_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.SeedReport)]),
+        "plsvo_seeds_keyframe": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.SeedKf)]),
+        "plsvo_seeds_fetch_lists": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.SeedList)]),
+        "plsvo_seeds_fetch_rows": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.SeedRows)]),
+        "plsvo_seeds_commit_rows": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.SeedRows)]),
         "plsvo_update_seeds": (C.c_int, [ctxp, C.POINTER(abi.SeedsIn), C.POINTER(abi.SeedsOut)]),
         "plsvo_trajectory_record": (C.c_int, [abi.c_double_p, abi.c_double_p, abi.c_double_p]),
         "plsvo_chain_stage": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.ChainIn), C.POINTER(abi.ChainParams)]),
@@ -979,6 +990,140 @@ class Context:
                     keep.append(v)
                     setattr(a, f, v.ctypes.data_as(abi.c_double_p))
         self._chk(self.L.plsvo_candidates_set_positions(self.h, n, arr))
+
+    # ---- depth-filter seed lists resident beside the map tables ----
+    @staticmethod
+    def _seed_fill(a, d, fields, counts):
+        """the arrays of dict d into the pointer fields of struct a (fields: abi._SEED_*_FIELDS; counts: rows per kind) -> keep-alive list"""
+        keep = []
+        for f, t, w in fields:
+            k = counts[0] if f.startswith("pt_") else counts[1]
+            if d.get(f) is None or k == 0:
+                continue
+            v = np.ascontiguousarray(d[f], dtype=abi._SEED_CT[t][1]).reshape((-1, w) if w > 1 else -1)
+            if len(v) != k:
+                raise ValueError(f"{f}: {k} rows expected")
+            keep.append(v)
+            setattr(a, f, v.ctypes.data_as(abi._SEED_CT[t][0]))
+        return keep
+
+    @staticmethod
+    def _seed_bufs(a, fields, rows):
+        """caller buffers for the pointer fields of struct a: rows = (point rows, segment rows)"""
+        b = {}
+        for f, t, w in fields:
+            k = max(rows[0] if f.startswith("pt_") else rows[1], 1)
+            b[f] = np.zeros((k, w) if w > 1 else k, abi._SEED_CT[t][1])
+            setattr(a, f, b[f].ctypes.data_as(abi._SEED_CT[t][0]))
+        return b
+
+    def seeds_reserve(self, extra_pt=0, extra_seg=0):
+        """plsvo_seeds_reserve: rows per stream and kind that the NEXT and every later seeds_stage adds to the staged list lengths"""
+        self._chk(self.L.plsvo_seeds_reserve(self.h, C.byref(abi.SeedReserve(int(extra_pt), int(extra_seg)))))
+
+    def seeds_capacity(self):
+        """plsvo_seeds_capacity: per staged stream a dict of the rows its lists may hold (pt, seg)"""
+        n = self._seed_n
+        outs = (abi.SeedReserve * max(n, 1))()
+        self._chk(self.L.plsvo_seeds_capacity(self.h, n, outs))
+        return [dict(pt=o.extra_pt, seg=o.extra_seg) for o in outs[:n]]
+
+    def seeds_stage(self, lists, cam, max_n_kfs=3, n_pyr_levels=3, align_max_iter=10, max_epi_search_steps=1000, edgelet_filtering=1, edgelet_max_angle=0.7, px_noise=1.0,
+                    convergence_sigma2_thresh=200.0):
+        """plsvo_seeds_stage: per staged stream of the candidate tables a dict of arrays named like plsvo_seed_list's (the counts are the
+        lengths of pt_ref_kf / seg_ref_kf) and `batch_counter`"""
+        n = len(lists)
+        arr = (abi.SeedList * max(n, 1))()
+        keep = []
+        for a, d in zip(arr, lists):
+            a.n_pt = 0 if d.get("pt_ref_kf") is None else len(d["pt_ref_kf"])
+            a.n_seg = 0 if d.get("seg_ref_kf") is None else len(d["seg_ref_kf"])
+            a.batch_counter = int(d.get("batch_counter", 0))
+            keep.append(self._seed_fill(a, d, abi._SEED_LIST_FIELDS, (a.n_pt, a.n_seg)))
+        pr = abi.SeedParams()
+        pr.cam = cam if isinstance(cam, abi.Pinhole) else abi.Pinhole(*cam)
+        pr.n_pyr_levels, pr.align_max_iter, pr.max_epi_search_steps, pr.edgelet_filtering = n_pyr_levels, align_max_iter, max_epi_search_steps, edgelet_filtering
+        pr.edgelet_max_angle, pr.px_noise, pr.convergence_sigma2_thresh, pr.max_n_kfs = edgelet_max_angle, px_noise, convergence_sigma2_thresh, max_n_kfs
+        self._chk(self.L.plsvo_seeds_stage(self.h, n, C.byref(pr), arr))
+        self._seed_n = n
+
+    def seeds_update(self, frames):
+        """plsvo_seeds_update (enqueue only): per staged stream None (not active) or a dict of cur_slot and T_f_w (host pose), d_T_f_w (a
+        device pointer) or neither (the resident optimised pose of candidates_pose_optimize)"""
+        n = len(frames)
+        arr = (abi.SeedFrame * max(n, 1))()
+        for a, f in zip(arr, frames):
+            if f is None:
+                continue
+            a.active, a.cur_slot = 1, int(f["cur_slot"])
+            if f.get("T_f_w") is not None:
+                a.pose_source = abi.INSERT_POSE_HOST
+                a.T_f_w = (C.c_double * 7)(*[float(v) for v in f["T_f_w"]])
+            elif f.get("d_T_f_w") is not None:
+                a.pose_source, a.d_T_f_w = abi.INSERT_POSE_DEV, int(f["d_T_f_w"])
+            else:
+                a.pose_source = abi.INSERT_POSE_RESIDENT
+        self._chk(self.L.plsvo_seeds_update(self.h, n, arr))
+
+    def seeds_update_fetch(self):
+        """plsvo_seeds_update_fetch (synchronises): per stream a dict of abi.SeedReport's fields (pt / seg: rows per abi.SEED_* status)"""
+        n = self._seed_n
+        outs = (abi.SeedReport * max(n, 1))()
+        self._chk(self.L.plsvo_seeds_update_fetch(self.h, n, outs))
+        res = [{f: (list(getattr(o, f)) if f in ("pt", "seg") else int(getattr(o, f))) for f, _ in abi.SeedReport._fields_} for o in outs[:n]]
+        for now, r in zip(self._cand_now, res):                       # the candidate tables' sizes as they stand
+            now.update(pt=r["n_pt"], seg=r["n_seg"], pt_cand=r["n_pt_cand"], seg_cand=r["n_seg_cand"])
+        return res
+
+    def seeds_keyframe(self, events):
+        """plsvo_seeds_keyframe (enqueue only after the copy): per staged stream None or a dict of removed_kf (-1), new_batch, new_kf,
+        depth_mean, depth_min and the new seeds' arrays named like plsvo_seed_kf's (the counts are the lengths of pt_px / seg_px)"""
+        n = len(events)
+        arr = (abi.SeedKf * max(n, 1))()
+        keep = []
+        for a, e in zip(arr, events):
+            a.removed_kf = -1
+            if e is None:
+                continue
+            a.removed_kf, a.new_batch, a.new_kf = int(e.get("removed_kf", -1)), int(bool(e.get("new_batch", 0))), int(e.get("new_kf", 0))
+            a.depth_mean, a.depth_min = float(e.get("depth_mean", 0.0)), float(e.get("depth_min", 0.0))
+            a.n_pt = 0 if e.get("pt_px") is None else len(e["pt_px"])
+            a.n_seg = 0 if e.get("seg_px") is None else len(e["seg_px"])
+            keep.append(self._seed_fill(a, e, abi._SEED_KF_FIELDS, (a.n_pt, a.n_seg)))
+        self._chk(self.L.plsvo_seeds_keyframe(self.h, n, arr))
+
+    def seeds_fetch_lists(self):
+        """plsvo_seeds_fetch_lists (synchronises): per stream a dict of the lists as they stand, arrays named like plsvo_seed_list's, and
+        batch_counter"""
+        n = self._seed_n
+        outs = (abi.SeedList * max(n, 1))()
+        bufs = [self._seed_bufs(o, abi._SEED_LIST_FIELDS, (c["pt"], c["seg"])) for o, c in zip(outs, self.seeds_capacity())]
+        self._chk(self.L.plsvo_seeds_fetch_lists(self.h, n, outs))
+        return [dict({f: v[:(o.n_pt if f.startswith("pt_") else o.n_seg)].copy() for f, v in b.items()}, batch_counter=int(o.batch_counter)) for o, b in zip(outs[:n], bufs)]
+
+    def seeds_fetch_rows(self):
+        """plsvo_seeds_fetch_rows (synchronises): per stream a dict of the last update's shadow rows in the list order before it, arrays
+        named like plsvo_seed_rows'"""
+        n = self._seed_n
+        outs = (abi.SeedRows * max(n, 1))()
+        bufs = [self._seed_bufs(o, abi._SEED_ROWS_FIELDS, (c["pt"], c["seg"])) for o, c in zip(outs, self.seeds_capacity())]
+        self._chk(self.L.plsvo_seeds_fetch_rows(self.h, n, outs))
+        return [{f: v[:(o.n_pt if f.startswith("pt_") else o.n_seg)].copy() for f, v in b.items()} for o, b in zip(outs[:n], bufs)]
+
+    def seeds_commit_rows(self, rows):
+        """plsvo_seeds_commit_rows (diagnostic, synchronous): per staged stream None (not active) or a dict of caller-made shadow rows
+        (status, parameters, xyz_world) named like plsvo_seed_rows'; the commit launch runs on them in place of an update's"""
+        n = len(rows)
+        arr = (abi.SeedRows * max(n, 1))()
+        keep = []
+        for a, d in zip(arr, rows):
+            if d is None:
+                continue
+            a.active = 1
+            a.n_pt = 0 if d.get("pt_status") is None else len(d["pt_status"])
+            a.n_seg = 0 if d.get("seg_status") is None else len(d["seg_status"])
+            keep.append(self._seed_fill(a, d, abi._SEED_ROWS_FIELDS, (a.n_pt, a.n_seg)))
+        self._chk(self.L.plsvo_seeds_commit_rows(self.h, n, arr))
 
     # ---- structure optimisation ----
     def structure_optimize(self, job):

@@ -1,4 +1,5 @@
-// capi_candidates.hip -- every plsvo_candidates_* entry point of include/plsvo_hip.h (candidates, cell selection, keyframe insertion, new candidates); host side only
+// capi_candidates.hip -- every plsvo_candidates_* entry point of include/plsvo_hip.h (candidates, cell selection, keyframe insertion, new candidates)
+// and the plsvo_seeds_* ones, whose seed lists hand their converged seeds to the same tables; host side only
 #include "capi_ctx.hpp"
 
 // ---- map candidates: overlap keyframes' features, first visit, closest view, quality order (candidates_device.hpp) ---------
@@ -23,11 +24,15 @@ static QualitySections quality_sections(const plsvo_ctx* c) {
   return s;
 }
 static void cand_reset_run(plsvo_ctx* c) { c->cd_ran = c->cd_matched = c->cs_selected = c->cs_posed = c->ci_inserted = c->cn_closed = false; }   // the steps taken on the last run's results
-static void cand_reset_stage(plsvo_ctx* c) { cand_reset_run(c); c->cd_staged = c->ci_have_out = c->cn_have_out = false; }   // those, the tables, the last insertion's and add's reports
+static void cand_reset_stage(plsvo_ctx* c) { cand_reset_run(c); c->cd_staged = c->ci_have_out = c->cn_have_out = c->sd_staged = c->sd_pending = c->sd_have_report = false; }   // those, the tables, the last insertion's and add's reports
 // PLSVO_OK while the last run's candidates still describe the tables; once an insertion or an add came behind it, the refusal of entry point `who`
 static int cand_run_open(plsvo_ctx* c, const char* who) {
   const char* why = c->ci_inserted ? "this run's frame was inserted" : c->cn_closed ? "landmarks were added behind this run" : nullptr;
   return why ? fail(c, PLSVO_E_STATE, std::string(who) + ": " + why + " (the tables have moved on); run again") : PLSVO_OK;
+}
+// between plsvo_seeds_update and plsvo_seeds_update_fetch the tables' sizes are known to the device alone: the refusal of entry point `who`
+static int cand_seeds_pending(plsvo_ctx* c, const char* who) {
+  return c->sd_pending ? fail(c, PLSVO_E_STATE, std::string(who) + ": a seed update is not fetched yet (plsvo_seeds_update_fetch refreshes the tables' sizes)") : PLSVO_OK;
 }
 }  // namespace
 
@@ -213,6 +218,7 @@ extern "C" int plsvo_candidates_stage(plsvo_ctx* c, int n, const plsvo_cand_map*
 extern "C" int plsvo_candidates_run(plsvo_ctx* c, int n, const plsvo_cand_frame* fr) {
   CTX_CHECK(c);
   if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_run: no staged map tables");
+  if (const int rc = cand_seeds_pending(c, "candidates_run")) return rc;
   if (n != c->cd_n || (n > 0 && !fr)) return fail(c, PLSVO_E_INVALID, "candidates_run: n does not match the staged batch");
   size_t t_ov = 0;
   for (int s = 0; s < n; ++s) {
@@ -291,6 +297,7 @@ extern "C" int plsvo_candidates_fetch(plsvo_ctx* c, int n, plsvo_cand_out* out) 
 extern "C" int plsvo_candidates_match(plsvo_ctx* c) {
   CTX_CHECK(c);
   if (!c->cd_staged || !c->cd_ran) return fail(c, PLSVO_E_STATE, "candidates_match: no candidates on the device");
+  if (const int rc = cand_seeds_pending(c, "candidates_match")) return rc;
   if (const int rc = cand_run_open(c, "candidates_match")) return rc;
   if (c->cd_n == 0 || c->cd_total_m == 0) { c->cd_matched = true; return PLSVO_OK; }
   if (!c->pyr.base) return fail(c, PLSVO_E_STATE, "candidates_match: pyramids not configured");
@@ -342,6 +349,7 @@ extern "C" int plsvo_candidates_dev(plsvo_ctx* c, plsvo_cand_dev* o) {
   CTX_CHECK(c);
   if (!o) return fail(c, PLSVO_E_INVALID, "candidates_dev: bad arguments");
   if (!c->cd_staged || !c->cd_ran || c->cd_n == 0 || c->ci_inserted || c->cn_closed) return fail(c, PLSVO_E_STATE, "candidates_dev: no candidates on the device");
+  if (const int rc = cand_seeds_pending(c, "candidates_dev")) return rc;
   const CandBatchDev& b = c->cd_b; const MatchBatchDev& mb = c->cd_match;
   o->n_entries = (int64_t)c->cd_total_m; o->n_frames = (int64_t)c->cd_total_f;
   o->m_off = c->cd_m_off.data(); o->f_off = c->cd_f_off.data();
@@ -372,6 +380,7 @@ static bool append_cell_order(std::vector<int>& v, const int32_t* order, int n) 
 extern "C" int plsvo_candidates_set_quality(plsvo_ctx* c, int n, const plsvo_cand_quality_in* in) {
   CTX_CHECK(c);
   if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_set_quality: no staged map tables");
+  if (const int rc = cand_seeds_pending(c, "candidates_set_quality")) return rc;
   if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_set_quality: n does not match the staged batch");
   for (int s = 0; s < n; ++s) {
     const CandMapDev& M = c->cd_maps[(size_t)s];
@@ -398,6 +407,7 @@ extern "C" int plsvo_candidates_set_quality(plsvo_ctx* c, int n, const plsvo_can
 extern "C" int plsvo_candidates_fetch_quality(plsvo_ctx* c, int n, plsvo_cand_quality_out* out) {
   CTX_CHECK(c);
   if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_fetch_quality: no staged map tables");
+  if (const int rc = cand_seeds_pending(c, "candidates_fetch_quality")) return rc;
   if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_fetch_quality: n does not match the staged batch");
   if (n == 0) return PLSVO_OK;
   HIP_TRY(c, hipSetDevice(c->device));
@@ -435,6 +445,7 @@ extern "C" int plsvo_candidates_fetch_quality(plsvo_ctx* c, int n, plsvo_cand_qu
 extern "C" int plsvo_candidates_set_match(plsvo_ctx* c, int n, const plsvo_cand_match_out* in) {
   CTX_CHECK(c);
   if (!c->cd_staged || !c->cd_ran) return fail(c, PLSVO_E_STATE, "candidates_set_match: no candidates on the device");
+  if (const int rc = cand_seeds_pending(c, "candidates_set_match")) return rc;
   if (const int rc = cand_run_open(c, "candidates_set_match")) return rc;
   if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_set_match: n does not match the staged batch");
   for (int s = 0; s < n; ++s) if (!in[s].found || !in[s].px || !in[s].search_level) return fail(c, PLSVO_E_INVALID, "candidates_set_match: null array");
@@ -460,6 +471,7 @@ extern "C" int plsvo_candidates_select(plsvo_ctx* c, const plsvo_cand_select_par
   CTX_CHECK(c);
   if (!sp) return fail(c, PLSVO_E_INVALID, "candidates_select: bad arguments");
   if (!c->cd_staged || !c->cd_ran || !c->cd_matched) return fail(c, PLSVO_E_STATE, "candidates_select: no match on the device");
+  if (const int rc = cand_seeds_pending(c, "candidates_select")) return rc;
   if (c->cs_selected) return fail(c, PLSVO_E_STATE, "candidates_select: this run's candidates were selected already (the tables have moved on)");
   if (const int rc = cand_run_open(c, "candidates_select")) return rc;   // (an insertion needs a selection: the line above has spoken for it)
   if (sp->max_fts < 0 || sp->max_fts_segs < 0 || sp->poseopt_n_iter < 0)
@@ -550,6 +562,7 @@ extern "C" int plsvo_candidates_select_fetch(plsvo_ctx* c, int n, plsvo_cand_sel
 extern "C" int plsvo_candidates_pose_optimize(plsvo_ctx* c) {
   CTX_CHECK(c);
   if (!c->cd_staged || !c->cs_selected) return fail(c, PLSVO_E_STATE, "candidates_pose_optimize: no selection on the device");
+  if (const int rc = cand_seeds_pending(c, "candidates_pose_optimize")) return rc;
   if (const int rc = cand_run_open(c, "candidates_pose_optimize")) return rc;
   const int n = c->cd_n;
   c->cs_posed = false;
@@ -606,6 +619,7 @@ extern "C" int plsvo_candidates_reserve(plsvo_ctx* c, const plsvo_cand_reserve* 
 extern "C" int plsvo_candidates_insert_keyframe(plsvo_ctx* c, int n, const plsvo_cand_insert* in) {
   CTX_CHECK(c);
   if (!c->cd_staged || !c->cd_ran || !c->cs_selected) return fail(c, PLSVO_E_STATE, "candidates_insert_keyframe: no selection on the last run");
+  if (const int rc = cand_seeds_pending(c, "candidates_insert_keyframe")) return rc;
   if (c->ci_inserted) return fail(c, PLSVO_E_STATE, "candidates_insert_keyframe: this run's frame was inserted already");
   if (const int rc = cand_run_open(c, "candidates_insert_keyframe")) return rc;
   if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_insert_keyframe: n does not match the staged batch");
@@ -749,6 +763,7 @@ extern "C" int plsvo_candidates_insert_fetch(plsvo_ctx* c, int n, plsvo_cand_ins
 extern "C" int plsvo_candidates_fetch_map(plsvo_ctx* c, int n, plsvo_cand_map_out* out) {
   CTX_CHECK(c);
   if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_fetch_map: no staged map tables");
+  if (const int rc = cand_seeds_pending(c, "candidates_fetch_map")) return rc;
   if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_fetch_map: n does not match the staged batch");
   if (n == 0) return PLSVO_OK;
   HIP_TRY(c, hipSetDevice(c->device));
@@ -791,6 +806,7 @@ extern "C" int plsvo_candidates_fetch_map(plsvo_ctx* c, int n, plsvo_cand_map_ou
 extern "C" int plsvo_candidates_set_positions(plsvo_ctx* c, int n, const plsvo_cand_positions* in) {
   CTX_CHECK(c);
   if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_set_positions: no staged map tables");
+  if (const int rc = cand_seeds_pending(c, "candidates_set_positions")) return rc;
   if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_set_positions: n does not match the staged batch");
   size_t t_pt = 0, t_seg = 0;
   for (int s = 0; s < n; ++s) {
@@ -846,6 +862,7 @@ extern "C" int plsvo_candidates_lm_capacity(plsvo_ctx* c, int n, plsvo_cand_lm_r
 extern "C" int plsvo_candidates_add(plsvo_ctx* c, int n, const plsvo_cand_new* in) {
   CTX_CHECK(c);
   if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_add: no staged map tables");
+  if (const int rc = cand_seeds_pending(c, "candidates_add")) return rc;
   if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_add: n does not match the staged batch");
   // -- every check before anything is written: arguments, then room (from the host's mirrors: landmark count, used observation entries)
   size_t t_pt = 0, t_seg = 0;
@@ -945,6 +962,7 @@ extern "C" int plsvo_candidates_add(plsvo_ctx* c, int n, const plsvo_cand_new* i
 extern "C" int plsvo_candidates_add_fetch(plsvo_ctx* c, int n, plsvo_cand_add_out* out) {
   CTX_CHECK(c);
   if (!c->cd_staged || !c->cn_have_out) return fail(c, PLSVO_E_STATE, "candidates_add_fetch: no add since the tables were staged");
+  if (const int rc = cand_seeds_pending(c, "candidates_add_fetch")) return rc;
   if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_add_fetch: n does not match the staged batch");
   if (n == 0) return PLSVO_OK;
   HIP_TRY(c, hipSetDevice(c->device));
@@ -955,6 +973,404 @@ extern "C" int plsvo_candidates_add_fetch(plsvo_ctx* c, int n, plsvo_cand_add_ou
     const CandMapDev& M = maps[(size_t)s]; const CandStreamHost& H = c->cd_host[(size_t)s];
     out[s] = c->cn_last[(size_t)s];
     out[s].n_pt = M.n_pt; out[s].n_seg = M.n_seg; out[s].n_pt_cand = M.n_pt_cand; out[s].n_seg_cand = M.n_seg_cand; out[s].n_pt_obs = H.n_pt_obs; out[s].n_seg_obs = H.n_seg_obs;
+  }
+  return PLSVO_OK;
+}
+
+// ---- depth-filter seed lists resident beside the map tables (seedlist_device.hpp) -------------------------------------------
+namespace {
+// the sections of sd_d_work: reports, then the shadow rows (SeedsBatchDev's outputs, one per capacity row)
+struct SeedWorkSections { size_t report, p_st, p_a, p_b, p_mu, p_s2, p_xyz, p_px, p_z, s_st, s_a, s_b, s_mus, s_mue, s_s2s, s_s2e, s_xs, s_xe, s_zs, s_ze, end; };
+static SeedWorkSections seed_work_sections(size_t n, size_t tp, size_t ts) {
+  Carver w; SeedWorkSections o;
+  o.report = w.take<SeedReportDev>(n);
+  o.p_st = w.take<int>(tp); o.p_a = w.take<float>(tp); o.p_b = w.take<float>(tp); o.p_mu = w.take<float>(tp); o.p_s2 = w.take<float>(tp);
+  o.p_xyz = w.take<double>(tp * 3); o.p_px = w.take<double>(tp * 2); o.p_z = w.take<double>(tp);
+  o.s_st = w.take<int>(ts); o.s_a = w.take<float>(ts); o.s_b = w.take<float>(ts); o.s_mus = w.take<float>(ts); o.s_mue = w.take<float>(ts);
+  o.s_s2s = w.take<float>(ts); o.s_s2e = w.take<float>(ts); o.s_xs = w.take<double>(ts * 3); o.s_xe = w.take<double>(ts * 3); o.s_zs = w.take<double>(ts); o.s_ze = w.take<double>(ts);
+  o.end = w.off;
+  return o;
+}
+static int seeds_ready(plsvo_ctx* c, int n, const void* arg, const char* who, bool may_be_pending = false) {
+  if (!c->cd_staged || !c->sd_staged) return fail(c, PLSVO_E_STATE, std::string(who) + ": no staged seed tables (a plsvo_candidates_stage drops them: stage both again)");
+  if (!may_be_pending && c->sd_pending) return fail(c, PLSVO_E_STATE, std::string(who) + ": a seed update is not fetched yet (plsvo_seeds_update_fetch)");
+  if (n != c->sd_n || (n > 0 && !arg)) return fail(c, PLSVO_E_INVALID, std::string(who) + ": n does not match the staged batch");
+  return PLSVO_OK;
+}
+static size_t seed_round(size_t rows) { return (rows + 63) & ~(size_t)63; }   // match_device.hpp's MT: a workgroup of the update serves one stream
+// the update's frames travel, then the commit launch; `launch_update`: the per-seed launch in front of it
+static int seeds_enqueue(plsvo_ctx* c, int n, const std::vector<SeedFrameDev>& frames, bool launch_update) {
+  Blob blob;
+  blob.add(frames);
+  if (const int rc = upload_blob(c, c->sd_d_in, blob)) return rc;
+  SeedListBatchDev b = c->sd_b;
+  b.frames = c->sd_d_in.as<SeedFrameDev>();
+  b.s.pyr_base = c->pyr.base; b.s.slot_bytes = c->pyr.slot_bytes; b.s.width = c->pyr.w[0]; b.s.height = c->pyr.h[0];
+  if (launch_update) {
+    EventPair ep{}; prof_begin(c, PLSVO_K_SEEDS, &ep);
+    const hipError_t launched = launch_update_seeds_resident(b, c->stream);
+    prof_end(c, PLSVO_K_SEEDS, &ep);                 // ahead of the error return, as in plsvo_candidates_run
+    HIP_TRY(c, launched);
+  }
+  {
+    EventPair ep{}; prof_begin(c, PLSVO_K_NEWCAND, &ep);
+    const hipError_t launched = launch_seeds_commit(b, c->stream);
+    prof_end(c, PLSVO_K_NEWCAND, &ep);
+    HIP_TRY(c, launched);
+  }
+  c->cd_max_level = std::max(c->cd_max_level, c->sd_max_level);   // a new landmark's observation has its seed's level
+  c->cn_closed = true;                              // the open run is over, as behind plsvo_candidates_add
+  c->sd_pending = true; c->sd_have_report = false;
+  (void)n;
+  return PLSVO_OK;
+}
+}  // namespace
+
+extern "C" int plsvo_seeds_reserve(plsvo_ctx* c, const plsvo_seed_reserve* r) {
+  CTX_CHECK(c);
+  if (r && (r->extra_pt < 0 || r->extra_seg < 0)) return fail(c, PLSVO_E_INVALID, "seeds_reserve: negative room");
+  c->sd_reserve = r ? *r : plsvo_seed_reserve{};
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_seeds_capacity(plsvo_ctx* c, int n, plsvo_seed_reserve* out) {
+  CTX_CHECK(c);
+  if (const int rc = seeds_ready(c, n, out, "seeds_capacity", true)) return rc;
+  for (int s = 0; s < n; ++s) { out[s].extra_pt = c->sd_lim[2 * (size_t)s]; out[s].extra_seg = c->sd_lim[2 * (size_t)s + 1]; }
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_seeds_stage(plsvo_ctx* c, int n, const plsvo_seed_params* pr, const plsvo_seed_list* lists) {
+  CTX_CHECK(c);
+  if (!c->cd_staged || n != c->cd_n) return fail(c, PLSVO_E_STATE, "seeds_stage: no staged candidate tables of the same n");
+  if (c->sd_pending) return fail(c, PLSVO_E_STATE, "seeds_stage: a seed update is not fetched yet (plsvo_seeds_update_fetch)");
+  if (!c->pyr.base) return fail(c, PLSVO_E_STATE, "seeds_stage: pyramids not configured");
+  if (!pr || (n > 0 && !lists)) return fail(c, PLSVO_E_INVALID, "seeds_stage: bad arguments");
+  if (pr->n_pyr_levels < 1 || pr->align_max_iter < 0 || pr->max_epi_search_steps < 0 || pr->max_n_kfs < 0 || pr->n_pyr_levels > c->pyr.n_levels)
+    return fail(c, PLSVO_E_INVALID, "seeds_stage: bad parameters");
+  if (pr->cam.width != c->pyr.w[0] || pr->cam.height != c->pyr.h[0]) return fail(c, PLSVO_E_INVALID, "seeds_stage: camera size does not match the configured pyramid");
+  const plsvo_seed_reserve R = c->sd_reserve;
+  const size_t N = (size_t)n;
+  std::vector<SeedStreamDev> sd(N);
+  std::vector<int> lim(2 * N), blk_pt, blk_seg;
+  size_t tp = 0, ts = 0;
+  int max_level = 0;
+  for (int s = 0; s < n; ++s) {
+    const plsvo_seed_list& I = lists[s]; const CandMapDev& M = c->cd_maps[(size_t)s]; const CandStreamHost& H = c->cd_host[(size_t)s];
+    if (I.n_pt < 0 || I.n_seg < 0) return fail(c, PLSVO_E_INVALID, "seeds_stage: negative count");
+    if (I.n_pt > 0 && (!I.pt_ref_kf || !I.pt_batch_id || !I.pt_px || !I.pt_f || !I.pt_level || !I.pt_type || !I.pt_a || !I.pt_b || !I.pt_mu || !I.pt_z_range || !I.pt_sigma2))
+      return fail(c, PLSVO_E_INVALID, "seeds_stage: null point-seed array");
+    if (I.n_seg > 0 && (!I.seg_ref_kf || !I.seg_batch_id || !I.seg_px || !I.seg_f || !I.seg_sf || !I.seg_ef || !I.seg_spx || !I.seg_epx || !I.seg_level || !I.seg_a || !I.seg_b ||
+                        !I.seg_mu_s || !I.seg_mu_e || !I.seg_z_range_s || !I.seg_z_range_e || !I.seg_sigma2_s || !I.seg_sigma2_e))
+      return fail(c, PLSVO_E_INVALID, "seeds_stage: null line-seed array");
+    if (!cand_idx_ok(I.pt_ref_kf, (size_t)I.n_pt, 0, M.n_kf) || !cand_idx_ok(I.seg_ref_kf, (size_t)I.n_seg, 0, M.n_kf)) return fail(c, PLSVO_E_INVALID, "seeds_stage: ref_kf outside the keyframe table");
+    if (!cand_idx_ok(I.pt_level, (size_t)I.n_pt, 0, c->pyr.n_levels) || !cand_idx_ok(I.seg_level, (size_t)I.n_seg, 0, c->pyr.n_levels))
+      return fail(c, PLSVO_E_INVALID, "seeds_stage: feature level outside the configured pyramid");
+    for (int k = 0; k < I.n_pt; ++k) {
+      if (I.pt_type[k] == PLSVO_FTR_EDGELET) { if (pr->edgelet_filtering && !I.pt_grad) return fail(c, PLSVO_E_INVALID, "seeds_stage: edgelets without pt_grad"); }
+      else if (I.pt_type[k] != PLSVO_FTR_CORNER) return fail(c, PLSVO_E_INVALID, "seeds_stage: unknown feature type");
+      max_level = std::max(max_level, (int)I.pt_level[k]);
+    }
+    for (int k = 0; k < I.n_seg; ++k) max_level = std::max(max_level, (int)I.seg_level[k]);
+    if ((size_t)I.n_pt + (size_t)R.extra_pt > (size_t)INT32_MAX - 64 || (size_t)I.n_seg + (size_t)R.extra_seg > (size_t)INT32_MAX - 64) return fail(c, PLSVO_E_CAPACITY, "seeds_stage: stream too large");
+    SeedStreamDev& S = sd[(size_t)s];
+    S = SeedStreamDev{};
+    S.n_pt = I.n_pt; S.n_seg = I.n_seg; S.batch_counter = I.batch_counter;
+    lim[2 * (size_t)s] = I.n_pt + R.extra_pt; lim[2 * (size_t)s + 1] = I.n_seg + R.extra_seg;
+    S.cap_pt = (int)seed_round((size_t)lim[2 * (size_t)s]); S.cap_seg = (int)seed_round((size_t)lim[2 * (size_t)s + 1]);
+    S.rows_pt = H.rows_pt; S.rows_seg = H.rows_seg; S.rows_pt_cand = H.rows_pt_cand; S.rows_seg_cand = H.rows_seg_cand; S.cap_pt_obs = H.cap_pt_obs; S.cap_seg_obs = H.cap_seg_obs;
+    S.pt_off = (long long)tp; S.seg_off = (long long)ts;
+    for (int k = 0; k < S.cap_pt / 64; ++k) blk_pt.push_back(s);
+    for (int k = 0; k < S.cap_seg / 64; ++k) blk_seg.push_back(s);
+    tp += (size_t)S.cap_pt; ts += (size_t)S.cap_seg;
+  }
+  if (tp / 64 + ts / 64 > (size_t)INT32_MAX) return fail(c, PLSVO_E_CAPACITY, "seeds_stage: batch too large");
+  c->sd_staged = false; c->sd_have_report = false;
+  c->sd_params = *pr; c->sd_n = n; c->sd_host = sd; c->sd_lim = lim; c->sd_max_level = max_level; c->sd_t_pt = tp; c->sd_t_seg = ts;
+  if (n == 0) { c->sd_staged = true; c->sd_b = SeedListBatchDev{}; return PLSVO_OK; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  const int n_blk_pt = (int)blk_pt.size();
+  blk_pt.insert(blk_pt.end(), blk_seg.begin(), blk_seg.end());
+  Blob blob;
+  const size_t b_str = blob.add(sd), b_blk = blob.add(blk_pt);
+  const size_t p_kf = blob.reserve<int>(tp), p_bid = blob.reserve<int>(tp), p_px = blob.reserve<double>(tp * 2), p_f = blob.reserve<double>(tp * 3), p_lv = blob.reserve<int>(tp),
+               p_ty = blob.reserve<uint8_t>(tp), p_gr = blob.reserve<double>(tp * 2), p_a = blob.reserve<float>(tp), p_b = blob.reserve<float>(tp), p_mu = blob.reserve<float>(tp),
+               p_zr = blob.reserve<float>(tp), p_s2 = blob.reserve<float>(tp);
+  const size_t s_kf = blob.reserve<int>(ts), s_bid = blob.reserve<int>(ts), s_px = blob.reserve<double>(ts * 2), s_f = blob.reserve<double>(ts * 3), s_sf = blob.reserve<double>(ts * 3),
+               s_ef = blob.reserve<double>(ts * 3), s_spx = blob.reserve<double>(ts * 2), s_epx = blob.reserve<double>(ts * 2), s_lv = blob.reserve<int>(ts), s_a = blob.reserve<float>(ts),
+               s_b = blob.reserve<float>(ts), s_mus = blob.reserve<float>(ts), s_mue = blob.reserve<float>(ts), s_zrs = blob.reserve<float>(ts), s_zre = blob.reserve<float>(ts),
+               s_s2s = blob.reserve<float>(ts), s_s2e = blob.reserve<float>(ts);
+  auto put = [&](size_t sec, size_t at, const void* src, size_t count, size_t elem) { if (count && src) memcpy(blob.host.data() + sec + at * elem, src, count * elem); };
+  for (int s = 0; s < n; ++s) {
+    const plsvo_seed_list& I = lists[s]; const SeedStreamDev& S = sd[(size_t)s];
+    const size_t np = (size_t)I.n_pt, ns = (size_t)I.n_seg, po = (size_t)S.pt_off, so = (size_t)S.seg_off;
+    put(p_kf, po, I.pt_ref_kf, np, 4); put(p_bid, po, I.pt_batch_id, np, 4); put(p_px, po * 2, I.pt_px, np * 2, 8); put(p_f, po * 3, I.pt_f, np * 3, 8); put(p_lv, po, I.pt_level, np, 4);
+    put(p_ty, po, I.pt_type, np, 1); put(p_gr, po * 2, I.pt_grad, np * 2, 8); put(p_a, po, I.pt_a, np, 4); put(p_b, po, I.pt_b, np, 4); put(p_mu, po, I.pt_mu, np, 4);
+    put(p_zr, po, I.pt_z_range, np, 4); put(p_s2, po, I.pt_sigma2, np, 4);
+    put(s_kf, so, I.seg_ref_kf, ns, 4); put(s_bid, so, I.seg_batch_id, ns, 4); put(s_px, so * 2, I.seg_px, ns * 2, 8); put(s_f, so * 3, I.seg_f, ns * 3, 8); put(s_sf, so * 3, I.seg_sf, ns * 3, 8);
+    put(s_ef, so * 3, I.seg_ef, ns * 3, 8); put(s_spx, so * 2, I.seg_spx, ns * 2, 8); put(s_epx, so * 2, I.seg_epx, ns * 2, 8); put(s_lv, so, I.seg_level, ns, 4);
+    put(s_a, so, I.seg_a, ns, 4); put(s_b, so, I.seg_b, ns, 4); put(s_mus, so, I.seg_mu_s, ns, 4); put(s_mue, so, I.seg_mu_e, ns, 4); put(s_zrs, so, I.seg_z_range_s, ns, 4);
+    put(s_zre, so, I.seg_z_range_e, ns, 4); put(s_s2s, so, I.seg_sigma2_s, ns, 4); put(s_s2e, so, I.seg_sigma2_e, ns, 4);
+  }
+  if (const int rc = upload_blob(c, c->sd_d_tab, blob)) return rc;
+  c->sd_tab_bytes = blob.host.size();
+  const SeedWorkSections W = seed_work_sections(N, tp, ts);
+  HIP_TRY(c, c->sd_d_work.ensure(W.end + 256));
+  HIP_TRY(c, hipMemsetAsync(c->sd_d_work.p, 0, W.end, c->stream));
+  char* d = reinterpret_cast<char*>(c->sd_d_tab.p); char* w = reinterpret_cast<char*>(c->sd_d_work.p);
+  auto D = [&](size_t o) { return reinterpret_cast<double*>(d + o); };
+  auto Iv = [&](size_t o) { return reinterpret_cast<int*>(d + o); };
+  auto Fv = [&](size_t o) { return reinterpret_cast<float*>(d + o); };
+  auto WD = [&](size_t o) { return reinterpret_cast<double*>(w + o); };
+  auto WI = [&](size_t o) { return reinterpret_cast<int*>(w + o); };
+  auto WF = [&](size_t o) { return reinterpret_cast<float*>(w + o); };
+  SeedListBatchDev b{};
+  SeedsBatchDev& q = b.s;
+  q.fx = pr->cam.fx; q.fy = pr->cam.fy; q.cx = pr->cam.cx; q.cy = pr->cam.cy; q.cam_width = pr->cam.width; q.cam_height = pr->cam.height;
+  q.n_pyr_levels = pr->n_pyr_levels; q.align_max_iter = pr->align_max_iter; q.max_epi_search_steps = pr->max_epi_search_steps;
+  q.edgelet_filtering = pr->edgelet_filtering; q.edgelet_max_angle = pr->edgelet_max_angle;
+  q.px_error_angle = std::atan(pr->px_noise / (2.0 * std::fabs(pr->cam.fx))) * 2.0;   // depth_filter.cpp:279-280 (host libm, as in plsvo_update_seeds)
+  q.convergence_sigma2_thresh = pr->convergence_sigma2_thresh;
+  q.n_pt = (int)std::min(tp, (size_t)INT32_MAX); q.n_seg = (int)std::min(ts, (size_t)INT32_MAX);
+  q.frame_T = c->cd_b.frame_T; q.frame_slot = c->cd_b.frame_slot;
+  q.pt_ref_frame = Iv(p_kf); q.pt_px = D(p_px); q.pt_f = D(p_f); q.pt_level = Iv(p_lv); q.pt_type = reinterpret_cast<const uint8_t*>(d + p_ty); q.pt_grad = D(p_gr);
+  q.pt_a = Fv(p_a); q.pt_b = Fv(p_b); q.pt_mu = Fv(p_mu); q.pt_z_range = Fv(p_zr); q.pt_sigma2 = Fv(p_s2);
+  q.seg_ref_frame = Iv(s_kf); q.seg_px = D(s_px); q.seg_f = D(s_f); q.seg_sf = D(s_sf); q.seg_ef = D(s_ef); q.seg_level = Iv(s_lv);
+  q.seg_a = Fv(s_a); q.seg_b = Fv(s_b); q.seg_mu_s = Fv(s_mus); q.seg_mu_e = Fv(s_mue); q.seg_z_range_s = Fv(s_zrs); q.seg_z_range_e = Fv(s_zre);
+  q.seg_sigma2_s = Fv(s_s2s); q.seg_sigma2_e = Fv(s_s2e);
+  q.o_pt_status = WI(W.p_st); q.o_pt_a = WF(W.p_a); q.o_pt_b = WF(W.p_b); q.o_pt_mu = WF(W.p_mu); q.o_pt_sigma2 = WF(W.p_s2); q.o_pt_xyz = WD(W.p_xyz); q.o_pt_px = WD(W.p_px);
+  q.o_pt_depth = WD(W.p_z);
+  q.o_seg_status = WI(W.s_st); q.o_seg_a = WF(W.s_a); q.o_seg_b = WF(W.s_b); q.o_seg_mu_s = WF(W.s_mus); q.o_seg_mu_e = WF(W.s_mue); q.o_seg_sigma2_s = WF(W.s_s2s);
+  q.o_seg_sigma2_e = WF(W.s_s2e); q.o_seg_xyz_s = WD(W.s_xs); q.o_seg_xyz_e = WD(W.s_xe); q.o_seg_depth_s = WD(W.s_zs); q.o_seg_depth_e = WD(W.s_ze);
+  const QualitySections ql = quality_sections(c);
+  char* dq = reinterpret_cast<char*>(c->cs_d_q.p);
+  b.m.c = c->cd_b;
+  b.m.pt_nfail = reinterpret_cast<int*>(dq + ql.pt_nf); b.m.pt_nsucc = reinterpret_cast<int*>(dq + ql.pt_ns); b.m.seg_nfail = reinterpret_cast<int*>(dq + ql.seg_nf);
+  b.m.seg_nsucc = reinterpret_cast<int*>(dq + ql.seg_ns); b.m.pt_event = reinterpret_cast<uint8_t*>(dq + ql.pt_ev); b.m.seg_event = reinterpret_cast<uint8_t*>(dq + ql.seg_ev);
+  b.streams = reinterpret_cast<SeedStreamDev*>(d + b_str); b.report = reinterpret_cast<SeedReportDev*>(w + W.report); b.blk_stream = Iv(b_blk);
+  b.n_blk_pt = n_blk_pt; b.n_blk = (int)blk_pt.size(); b.n_jobs = n; b.max_n_kfs = pr->max_n_kfs;
+  b.pt_batch_id = Iv(p_bid); b.seg_batch_id = Iv(s_bid); b.seg_spx = D(s_spx); b.seg_epx = D(s_epx);
+  c->sd_b = b;
+  c->sd_staged = true;
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_seeds_update(plsvo_ctx* c, int n, const plsvo_seed_frame* fr) {
+  CTX_CHECK(c);
+  if (const int rc = seeds_ready(c, n, fr, "seeds_update")) return rc;
+  if (!c->pyr.base || c->pyr.n_levels < c->sd_params.n_pyr_levels || c->sd_max_level >= c->pyr.n_levels || c->sd_params.cam.width != c->pyr.w[0] || c->sd_params.cam.height != c->pyr.h[0])
+    return fail(c, PLSVO_E_STATE, "seeds_update: the configured pyramids are not those of the stage");
+  for (int s = 0; s < n; ++s) {
+    if (!fr[s].active) continue;
+    if (fr[s].cur_slot < 0 || fr[s].cur_slot >= c->pyr.n_slots) return fail(c, PLSVO_E_INVALID, "seeds_update: pyramid slot out of range");
+    if (fr[s].pose_source < PLSVO_INSERT_POSE_HOST || fr[s].pose_source > PLSVO_INSERT_POSE_RESIDENT || (fr[s].pose_source == PLSVO_INSERT_POSE_DEV && !fr[s].d_T_f_w))
+      return fail(c, PLSVO_E_INVALID, "seeds_update: bad pose source");
+    if (fr[s].pose_source == PLSVO_INSERT_POSE_RESIDENT && !c->cs_posed) return fail(c, PLSVO_E_STATE, "seeds_update: no resident pose optimisation for the pose");
+  }
+  for (int s = 0; s < n; ++s) {
+    if (!fr[s].active || c->sd_host[(size_t)s].n_pt + c->sd_host[(size_t)s].n_seg == 0) continue;
+    const CandMapDev& M = c->cd_maps[(size_t)s];
+    for (int k = 0; k < M.n_kf; ++k) if (c->cd_kf_slot[(size_t)M.kf_off + (size_t)k] >= c->pyr.n_slots) return fail(c, PLSVO_E_CAPACITY, "seeds_update: a keyframe's pyramid slot is out of range");
+  }
+  if (n == 0) return PLSVO_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  std::vector<SeedFrameDev> frames((size_t)n);
+  for (int s = 0; s < n; ++s) {
+    SeedFrameDev& J = frames[(size_t)s];
+    memset(&J, 0, sizeof(J));
+    J.active = fr[s].active ? 1 : 0; J.cur_slot = fr[s].cur_slot;
+    if (!J.active) continue;
+    memcpy(J.T, fr[s].T_f_w, sizeof(J.T));
+    J.d_T = fr[s].pose_source == PLSVO_INSERT_POSE_DEV ? fr[s].d_T_f_w : fr[s].pose_source == PLSVO_INSERT_POSE_RESIDENT ? c->cs_w.poses.as<double>() + 7 * (size_t)s : nullptr;
+  }
+  return seeds_enqueue(c, n, frames, true);
+}
+
+extern "C" int plsvo_seeds_commit_rows(plsvo_ctx* c, int n, const plsvo_seed_rows* rows) {
+  CTX_CHECK(c);
+  if (const int rc = seeds_ready(c, n, rows, "seeds_commit_rows")) return rc;
+  for (int s = 0; s < n; ++s) {
+    const plsvo_seed_rows& I = rows[s]; const SeedStreamDev& S = c->sd_host[(size_t)s];
+    if (!I.active) continue;
+    if (I.n_pt != S.n_pt || I.n_seg != S.n_seg) return fail(c, PLSVO_E_INVALID, "seeds_commit_rows: the row counts are not the list lengths");
+    if (I.n_pt > 0 && (!I.pt_status || !I.pt_a || !I.pt_b || !I.pt_mu || !I.pt_sigma2 || !I.pt_xyz_world)) return fail(c, PLSVO_E_INVALID, "seeds_commit_rows: null point array");
+    if (I.n_seg > 0 && (!I.seg_status || !I.seg_a || !I.seg_b || !I.seg_mu_s || !I.seg_mu_e || !I.seg_sigma2_s || !I.seg_sigma2_e || !I.seg_xyz_world_s || !I.seg_xyz_world_e))
+      return fail(c, PLSVO_E_INVALID, "seeds_commit_rows: null segment array");
+    if (!cand_idx_ok(I.pt_status, (size_t)I.n_pt, 0, PLSVO_SEED_AGED + 1) || !cand_idx_ok(I.seg_status, (size_t)I.n_seg, 0, PLSVO_SEED_AGED + 1)) return fail(c, PLSVO_E_INVALID, "seeds_commit_rows: unknown status");
+  }
+  if (n == 0) return PLSVO_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const SeedsBatchDev& q = c->sd_b.s;
+  std::vector<SeedFrameDev> frames((size_t)n);
+  auto up = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess; };
+  for (int s = 0; s < n; ++s) {
+    const plsvo_seed_rows& I = rows[s]; const SeedStreamDev& S = c->sd_host[(size_t)s];
+    memset(&frames[(size_t)s], 0, sizeof(SeedFrameDev));
+    frames[(size_t)s].active = I.active ? 1 : 0;
+    if (!I.active) continue;
+    const size_t np = (size_t)I.n_pt, ns = (size_t)I.n_seg, po = (size_t)S.pt_off, so = (size_t)S.seg_off;
+    HIP_TRY(c, up(q.o_pt_status + po, I.pt_status, np * 4)); HIP_TRY(c, up(q.o_pt_a + po, I.pt_a, np * 4)); HIP_TRY(c, up(q.o_pt_b + po, I.pt_b, np * 4));
+    HIP_TRY(c, up(q.o_pt_mu + po, I.pt_mu, np * 4)); HIP_TRY(c, up(q.o_pt_sigma2 + po, I.pt_sigma2, np * 4)); HIP_TRY(c, up(q.o_pt_xyz + 3 * po, I.pt_xyz_world, np * 24));
+    HIP_TRY(c, up(q.o_seg_status + so, I.seg_status, ns * 4)); HIP_TRY(c, up(q.o_seg_a + so, I.seg_a, ns * 4)); HIP_TRY(c, up(q.o_seg_b + so, I.seg_b, ns * 4));
+    HIP_TRY(c, up(q.o_seg_mu_s + so, I.seg_mu_s, ns * 4)); HIP_TRY(c, up(q.o_seg_mu_e + so, I.seg_mu_e, ns * 4)); HIP_TRY(c, up(q.o_seg_sigma2_s + so, I.seg_sigma2_s, ns * 4));
+    HIP_TRY(c, up(q.o_seg_sigma2_e + so, I.seg_sigma2_e, ns * 4)); HIP_TRY(c, up(q.o_seg_xyz_s + 3 * so, I.seg_xyz_world_s, ns * 24)); HIP_TRY(c, up(q.o_seg_xyz_e + 3 * so, I.seg_xyz_world_e, ns * 24));
+  }
+  if (const int rc = seeds_enqueue(c, n, frames, false)) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));      // the caller's arrays are free again
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_seeds_update_fetch(plsvo_ctx* c, int n, plsvo_seed_report* out) {
+  CTX_CHECK(c);
+  if (const int rc = seeds_ready(c, n, out, "seeds_update_fetch", true)) return rc;
+  if (!c->sd_pending && !c->sd_have_report) return fail(c, PLSVO_E_STATE, "seeds_update_fetch: no update since the seed tables were staged");
+  static_assert(sizeof(SeedReportDev) == sizeof(plsvo_seed_report), "the device's report is the public one");
+  if (c->sd_pending) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->sd_last.resize((size_t)n);
+    if (n > 0) HIP_TRY(c, hipMemcpyAsync(c->sd_last.data(), c->sd_b.report, (size_t)n * sizeof(SeedReportDev), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int s = 0; s < n; ++s) {                   // the host mirrors describe the tables as they stand
+      const SeedReportDev& R = c->sd_last[(size_t)s];
+      CandMapDev& M = c->cd_maps[(size_t)s]; CandStreamHost& H = c->cd_host[(size_t)s]; SeedStreamDev& S = c->sd_host[(size_t)s];
+      M.n_pt = R.n_pt; M.n_seg = R.n_seg; M.n_pt_cand = R.n_pt_cand; M.n_seg_cand = R.n_seg_cand; H.n_pt_obs = R.n_pt_obs; H.n_seg_obs = R.n_seg_obs;
+      S.n_pt = R.n_pt_seeds; S.n_seg = R.n_seg_seeds; S.batch_counter = R.batch_counter;
+    }
+    c->sd_pending = false; c->sd_have_report = true;
+  }
+  if (n > 0) memcpy(out, c->sd_last.data(), (size_t)n * sizeof(plsvo_seed_report));
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_seeds_keyframe(plsvo_ctx* c, int n, const plsvo_seed_kf* in) {
+  CTX_CHECK(c);
+  if (const int rc = seeds_ready(c, n, in, "seeds_keyframe")) return rc;
+  size_t tp = 0, ts = 0;
+  int max_level = c->sd_max_level;
+  bool any = false;
+  for (int s = 0; s < n; ++s) {
+    const plsvo_seed_kf& I = in[s]; const CandMapDev& M = c->cd_maps[(size_t)s];
+    if (I.n_pt < 0 || I.n_seg < 0) return fail(c, PLSVO_E_INVALID, "seeds_keyframe: negative count");
+    if (I.removed_kf < -1 || I.removed_kf > M.n_kf) return fail(c, PLSVO_E_INVALID, "seeds_keyframe: removed_kf outside the keyframe table as it stood");
+    if (I.n_pt + I.n_seg > 0) {
+      if (I.new_kf < 0 || I.new_kf >= M.n_kf) return fail(c, PLSVO_E_INVALID, "seeds_keyframe: new_kf outside the keyframe table");
+      if (!((float)I.depth_mean > 0.0f) || !((float)I.depth_min > 0.0f)) return fail(c, PLSVO_E_INVALID, "seeds_keyframe: depth not positive");
+    }
+    if (I.n_pt > 0 && (!I.pt_px || !I.pt_f || !I.pt_level || !I.pt_type)) return fail(c, PLSVO_E_INVALID, "seeds_keyframe: null point array");
+    if (I.n_seg > 0 && (!I.seg_px || !I.seg_f || !I.seg_sf || !I.seg_ef || !I.seg_spx || !I.seg_epx || !I.seg_level)) return fail(c, PLSVO_E_INVALID, "seeds_keyframe: null segment array");
+    if (!cand_idx_ok(I.pt_level, (size_t)I.n_pt, 0, c->pyr.n_levels) || !cand_idx_ok(I.seg_level, (size_t)I.n_seg, 0, c->pyr.n_levels))
+      return fail(c, PLSVO_E_INVALID, "seeds_keyframe: feature level outside the configured pyramid");
+    for (int k = 0; k < I.n_pt; ++k) {
+      if (I.pt_type[k] == PLSVO_FTR_EDGELET) { if (c->sd_params.edgelet_filtering && !I.pt_grad) return fail(c, PLSVO_E_INVALID, "seeds_keyframe: edgelets without pt_grad"); }
+      else if (I.pt_type[k] != PLSVO_FTR_CORNER) return fail(c, PLSVO_E_INVALID, "seeds_keyframe: unknown feature type");
+      max_level = std::max(max_level, (int)I.pt_level[k]);
+    }
+    for (int k = 0; k < I.n_seg; ++k) max_level = std::max(max_level, (int)I.seg_level[k]);
+    tp += (size_t)I.n_pt; ts += (size_t)I.n_seg;
+    any = any || I.removed_kf >= 0 || I.new_batch || I.n_pt + I.n_seg > 0;
+  }
+  for (int s = 0; s < n; ++s)                       // room, from the mirrored list lengths
+    if ((long long)c->sd_host[(size_t)s].n_pt + in[s].n_pt > c->sd_lim[2 * (size_t)s] || (long long)c->sd_host[(size_t)s].n_seg + in[s].n_seg > c->sd_lim[2 * (size_t)s + 1])
+      return fail(c, PLSVO_E_CAPACITY, "seeds_keyframe: a stream's seed list lacks rows (plsvo_seeds_reserve); nothing was changed");
+  if (!any) return PLSVO_OK;
+  if (tp > (size_t)INT32_MAX || ts > (size_t)INT32_MAX) return fail(c, PLSVO_E_CAPACITY, "seeds_keyframe: batch too large");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t N = (size_t)n;
+  Blob blob;
+  const size_t b_jobs = blob.reserve<SeedKfJobDev>(N);
+  const size_t p_px = blob.reserve<double>(tp * 2), p_f = blob.reserve<double>(tp * 3), p_lv = blob.reserve<int>(tp), p_ty = blob.reserve<uint8_t>(tp), p_gr = blob.reserve<double>(tp * 2);
+  const size_t s_px = blob.reserve<double>(ts * 2), s_f = blob.reserve<double>(ts * 3), s_sf = blob.reserve<double>(ts * 3), s_ef = blob.reserve<double>(ts * 3),
+               s_spx = blob.reserve<double>(ts * 2), s_epx = blob.reserve<double>(ts * 2), s_lv = blob.reserve<int>(ts);
+  auto put = [&](size_t sec, size_t at, const void* src, size_t count, size_t elem) { if (count && src) memcpy(blob.host.data() + sec + at * elem, src, count * elem); };
+  size_t ap = 0, as = 0;
+  for (int s = 0; s < n; ++s) {
+    const plsvo_seed_kf& I = in[s];
+    SeedKfJobDev& J = blob.at<SeedKfJobDev>(b_jobs)[s];
+    memset(&J, 0, sizeof(J));
+    J.removed_kf = I.removed_kf; J.new_batch = I.new_batch ? 1 : 0; J.new_kf = I.new_kf; J.n_pt = I.n_pt; J.n_seg = I.n_seg; J.pt_at = (long long)ap; J.seg_at = (long long)as;
+    if (I.n_pt + I.n_seg > 0) {                     // PointSeed::PointSeed / LineSeed::LineSeed (:53-74): float arguments, float members
+      const float depth_mean = (float)I.depth_mean, depth_min = (float)I.depth_min;
+      const float mu = 1.0 / depth_mean, z_range = 1.0 / depth_min;
+      const float sigma2 = z_range * z_range / 36;
+      J.mu = mu; J.z_range = z_range; J.sigma2 = sigma2;
+    }
+    const size_t np = (size_t)I.n_pt, ns = (size_t)I.n_seg;
+    put(p_px, ap * 2, I.pt_px, np * 2, 8); put(p_f, ap * 3, I.pt_f, np * 3, 8); put(p_lv, ap, I.pt_level, np, 4); put(p_ty, ap, I.pt_type, np, 1); put(p_gr, ap * 2, I.pt_grad, np * 2, 8);
+    put(s_px, as * 2, I.seg_px, ns * 2, 8); put(s_f, as * 3, I.seg_f, ns * 3, 8); put(s_sf, as * 3, I.seg_sf, ns * 3, 8); put(s_ef, as * 3, I.seg_ef, ns * 3, 8);
+    put(s_spx, as * 2, I.seg_spx, ns * 2, 8); put(s_epx, as * 2, I.seg_epx, ns * 2, 8); put(s_lv, as, I.seg_level, ns, 4);
+    ap += np; as += ns;
+  }
+  if (const int rc = upload_blob(c, c->sd_d_in, blob)) return rc;
+  const char* d = reinterpret_cast<const char*>(c->sd_d_in.p);
+  auto D = [&](size_t o) { return reinterpret_cast<const double*>(d + o); };
+  SeedListBatchDev b = c->sd_b;
+  b.kf_jobs = reinterpret_cast<const SeedKfJobDev*>(d + b_jobs);
+  b.k_pt_px = D(p_px); b.k_pt_f = D(p_f); b.k_pt_level = reinterpret_cast<const int*>(d + p_lv); b.k_pt_type = reinterpret_cast<const uint8_t*>(d + p_ty); b.k_pt_grad = D(p_gr);
+  b.k_seg_px = D(s_px); b.k_seg_f = D(s_f); b.k_seg_sf = D(s_sf); b.k_seg_ef = D(s_ef); b.k_seg_spx = D(s_spx); b.k_seg_epx = D(s_epx); b.k_seg_level = reinterpret_cast<const int*>(d + s_lv);
+  {
+    EventPair ep{}; prof_begin(c, PLSVO_K_NEWCAND, &ep);
+    const hipError_t launched = launch_seeds_keyframe(b, c->stream);
+    prof_end(c, PLSVO_K_NEWCAND, &ep);
+    HIP_TRY(c, launched);
+  }
+  for (int s = 0; s < n; ++s) {                     // (with a removal the lengths are upper bounds until the next update fetch)
+    SeedStreamDev& S = c->sd_host[(size_t)s];
+    S.n_pt += in[s].n_pt; S.n_seg += in[s].n_seg; S.batch_counter += in[s].new_batch ? 1 : 0;
+  }
+  c->sd_max_level = max_level;
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_seeds_fetch_lists(plsvo_ctx* c, int n, plsvo_seed_list* out) {
+  CTX_CHECK(c);
+  if (const int rc = seeds_ready(c, n, out, "seeds_fetch_lists")) return rc;
+  if (n == 0) return PLSVO_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  std::vector<char> h(c->sd_tab_bytes);            // the tables are one allocation: one copy
+  HIP_TRY(c, hipMemcpyAsync(h.data(), c->sd_d_tab.p, h.size(), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const SeedListBatchDev& b = c->sd_b; const SeedsBatchDev& q = b.s;
+  const char* base = reinterpret_cast<const char*>(c->sd_d_tab.p);
+  auto cp = [&](void* dst, const void* dev, size_t at, size_t count, size_t elem) { if (dst && count) memcpy(dst, h.data() + (reinterpret_cast<const char*>(dev) - base) + at * elem, count * elem); };
+  const SeedStreamDev* streams = reinterpret_cast<const SeedStreamDev*>(h.data() + (reinterpret_cast<const char*>(b.streams) - base));
+  for (int s = 0; s < n; ++s) {
+    const SeedStreamDev& S = streams[s]; plsvo_seed_list& O = out[s];
+    const size_t np = (size_t)S.n_pt, ns = (size_t)S.n_seg, po = (size_t)S.pt_off, so = (size_t)S.seg_off;
+    O.n_pt = S.n_pt; O.n_seg = S.n_seg; O.batch_counter = S.batch_counter; O.reserved0 = 0;
+    cp(O.pt_ref_kf, q.pt_ref_frame, po, np, 4); cp(O.pt_batch_id, b.pt_batch_id, po, np, 4); cp(O.pt_px, q.pt_px, po * 2, np * 2, 8); cp(O.pt_f, q.pt_f, po * 3, np * 3, 8);
+    cp(O.pt_level, q.pt_level, po, np, 4); cp(O.pt_type, q.pt_type, po, np, 1); cp(O.pt_grad, q.pt_grad, po * 2, np * 2, 8); cp(O.pt_a, q.pt_a, po, np, 4); cp(O.pt_b, q.pt_b, po, np, 4);
+    cp(O.pt_mu, q.pt_mu, po, np, 4); cp(O.pt_z_range, q.pt_z_range, po, np, 4); cp(O.pt_sigma2, q.pt_sigma2, po, np, 4);
+    cp(O.seg_ref_kf, q.seg_ref_frame, so, ns, 4); cp(O.seg_batch_id, b.seg_batch_id, so, ns, 4); cp(O.seg_px, q.seg_px, so * 2, ns * 2, 8); cp(O.seg_f, q.seg_f, so * 3, ns * 3, 8);
+    cp(O.seg_sf, q.seg_sf, so * 3, ns * 3, 8); cp(O.seg_ef, q.seg_ef, so * 3, ns * 3, 8); cp(O.seg_spx, b.seg_spx, so * 2, ns * 2, 8); cp(O.seg_epx, b.seg_epx, so * 2, ns * 2, 8);
+    cp(O.seg_level, q.seg_level, so, ns, 4); cp(O.seg_a, q.seg_a, so, ns, 4); cp(O.seg_b, q.seg_b, so, ns, 4); cp(O.seg_mu_s, q.seg_mu_s, so, ns, 4); cp(O.seg_mu_e, q.seg_mu_e, so, ns, 4);
+    cp(O.seg_z_range_s, q.seg_z_range_s, so, ns, 4); cp(O.seg_z_range_e, q.seg_z_range_e, so, ns, 4); cp(O.seg_sigma2_s, q.seg_sigma2_s, so, ns, 4); cp(O.seg_sigma2_e, q.seg_sigma2_e, so, ns, 4);
+    c->sd_host[(size_t)s].n_pt = S.n_pt; c->sd_host[(size_t)s].n_seg = S.n_seg;   // (exact again behind a keyframe event with a removal)
+  }
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_seeds_fetch_rows(plsvo_ctx* c, int n, plsvo_seed_rows* out) {
+  CTX_CHECK(c);
+  if (const int rc = seeds_ready(c, n, out, "seeds_fetch_rows")) return rc;
+  if (!c->sd_have_report) return fail(c, PLSVO_E_STATE, "seeds_fetch_rows: no fetched update since the seed tables were staged");
+  if (n == 0) return PLSVO_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const SeedWorkSections W = seed_work_sections((size_t)n, c->sd_t_pt, c->sd_t_seg);
+  std::vector<char> h(W.end);
+  HIP_TRY(c, hipMemcpyAsync(h.data(), c->sd_d_work.p, h.size(), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  auto cp = [&](void* dst, size_t sec, size_t at, size_t count, size_t elem) { if (dst && count) memcpy(dst, h.data() + sec + at * elem, count * elem); };
+  for (int s = 0; s < n; ++s) {
+    const SeedReportDev& R = c->sd_last[(size_t)s]; const SeedStreamDev& S = c->sd_host[(size_t)s]; plsvo_seed_rows& O = out[s];
+    size_t np = 0, ns = 0;
+    for (int k = 0; k < 6; ++k) { np += (size_t)R.pt[k]; ns += (size_t)R.seg[k]; }
+    const size_t po = (size_t)S.pt_off, so = (size_t)S.seg_off;
+    O.n_pt = (int32_t)np; O.n_seg = (int32_t)ns; O.active = np + ns > 0; O.reserved0 = 0;
+    cp(O.pt_status, W.p_st, po, np, 4); cp(O.pt_a, W.p_a, po, np, 4); cp(O.pt_b, W.p_b, po, np, 4); cp(O.pt_mu, W.p_mu, po, np, 4); cp(O.pt_sigma2, W.p_s2, po, np, 4);
+    cp(O.pt_xyz_world, W.p_xyz, po * 3, np * 3, 8); cp(O.pt_px_cur, W.p_px, po * 2, np * 2, 8); cp(O.pt_depth, W.p_z, po, np, 8);
+    cp(O.seg_status, W.s_st, so, ns, 4); cp(O.seg_a, W.s_a, so, ns, 4); cp(O.seg_b, W.s_b, so, ns, 4); cp(O.seg_mu_s, W.s_mus, so, ns, 4); cp(O.seg_mu_e, W.s_mue, so, ns, 4);
+    cp(O.seg_sigma2_s, W.s_s2s, so, ns, 4); cp(O.seg_sigma2_e, W.s_s2e, so, ns, 4); cp(O.seg_xyz_world_s, W.s_xs, so * 3, ns * 3, 8); cp(O.seg_xyz_world_e, W.s_xe, so * 3, ns * 3, 8);
+    cp(O.seg_depth_s, W.s_zs, so, ns, 8); cp(O.seg_depth_e, W.s_ze, so, ns, 8);
   }
   return PLSVO_OK;
 }

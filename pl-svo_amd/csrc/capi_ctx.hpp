@@ -33,6 +33,9 @@ hipError_t launch_map_insert_plan(const InsertBatchDev& b, hipStream_t stream); 
 hipError_t launch_map_insert(const InsertBatchDev& b, hipStream_t stream);
 hipError_t launch_map_set_positions(const PositionsBatchDev& b, hipStream_t stream);
 hipError_t launch_map_add_candidates(const NewCandBatchDev& b, hipStream_t stream);   // newcand_device.hpp, in seeds_kernels.hip
+hipError_t launch_update_seeds_resident(const SeedListBatchDev& b, hipStream_t stream);   // seedlist_device.hpp, in seeds_kernels.hip
+hipError_t launch_seeds_commit(const SeedListBatchDev& b, hipStream_t stream);
+hipError_t launch_seeds_keyframe(const SeedListBatchDev& b, hipStream_t stream);
 hipError_t launch_halfsample(const uint8_t* src, size_t src_pitch, int in_w, int in_h, int in_stride, uint8_t* dst,
                              size_t dst_pitch, int n_slots, int rounding, hipStream_t stream);
 hipError_t launch_copy_level0(const uint8_t* src, size_t src_pitch, int w, int h, int stride, uint8_t* dst, size_t dst_pitch,
@@ -250,7 +253,22 @@ struct plsvo_ctx {
   bool cn_closed = false, cn_have_out = false;
   std::vector<plsvo_cand_add_out> cn_last;
   DevBuf cn_d_in;
+  // resident seed lists (plsvo_seeds_*): the room plsvo_seeds_reserve asks for (the next stage's), per stream the host mirror of its
+  // record (sd_host: list lengths, upper bounds between a keyframe event and the next update fetch) and the rows it may fill (sd_lim);
+  // the tables (sd_d_tab: records, workgroup map, rows), shadow rows and reports (sd_d_work), a call's upload (sd_d_in).  A candidate
+  // restage drops them (sd_staged); between an update and its fetch the candidate tables are the device's alone (sd_pending)
+  plsvo_seed_reserve sd_reserve{};
+  bool sd_staged = false, sd_pending = false, sd_have_report = false;
+  int sd_n = 0, sd_max_level = 0;
+  plsvo_seed_params sd_params{};
+  std::vector<SeedStreamDev> sd_host;
+  std::vector<int> sd_lim;                  // 2 per stream: rows a list may hold (staged count + reserve)
+  std::vector<SeedReportDev> sd_last;
+  size_t sd_tab_bytes = 0, sd_t_pt = 0, sd_t_seg = 0;
+  DevBuf sd_d_tab, sd_d_work, sd_d_in;
+  SeedListBatchDev sd_b{};
   unsigned long long run_seq = 0, a_run_seq = 0, p_run_seq = 0, ch_run_seq = 0;   // which resident batch ran last, 0 = not since it was staged (plsvo_pack_pose_records)
+  unsigned long long ch_stage_seq = 0;      // when the frame step was staged, on the same count: a pose-optimisation batch that ran later describes the streams now
 
   // structure optimisation (one-shot batches)
   DevBuf s_d_in, s_d_out;

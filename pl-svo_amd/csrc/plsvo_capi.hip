@@ -113,7 +113,7 @@ extern "C" void plsvo_hip_destroy(plsvo_ctx* c) {
   for (auto& ep : c->ev_pool) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
   c->a_d_tailflag.release(); c->a_d_alive_tail.release(); c->a_d_xbuf.release(); c->a_d_order[0].release(); c->a_d_order[1].release(); c->a_d_workkey.release(); c->p_d_workkey.release(); c->p_d_order[0].release(); c->p_d_order[1].release();
   c->p_d_carry.release(); c->p_d_refill_next.release();
-  for (DevBuf* b : { &c->cd_d_blob, &c->cd_d_work, &c->cd_d_run, &c->cd_d_kfcount, &c->ci_d_work, &c->ci_d_in, &c->ci_d_plan, &c->ci_d_pos, &c->cn_d_in, &c->cs_d_q,
+  for (DevBuf* b : { &c->cd_d_blob, &c->cd_d_work, &c->cd_d_run, &c->cd_d_kfcount, &c->ci_d_work, &c->ci_d_in, &c->ci_d_plan, &c->ci_d_pos, &c->cn_d_in, &c->sd_d_tab, &c->sd_d_work, &c->sd_d_in, &c->cs_d_q,
                      &c->cs_d_work, &c->cs_d_order, &c->pyr_slab, &c->pyr_tiled, &c->pyr_upload, &c->a_d_blob, &c->a_d_state, &c->a_d_alive, &c->a_d_pxyz, &c->a_d_puv,
                      &c->a_d_cref, &c->a_d_chi, &c->a_d_log, &c->a_d_poses, &c->p_d_blob, &c->p_d_log, &c->s_d_in, &c->s_d_out, &c->ch_d_blob, &c->ch_d_work,
                      &c->ch_d_po, &c->rec_d }) b->release();
@@ -2049,7 +2049,7 @@ extern "C" int plsvo_chain_stage(plsvo_ctx* c, int n, const plsvo_chain_in* in, 
   c->ch_w.bind_resident(c->ch_pose, b, n);
   c->ch_jobs.swap(jobs);
   c->ch_n = n; c->ch_ncand = (int)NC; c->ch_npt_cap = npt_total; c->ch_nseg_cap = nseg_total;
-  c->ch_staged = true; c->ch_run_seq = 0;
+  c->ch_staged = true; c->ch_run_seq = 0; c->ch_stage_seq = ++c->run_seq;
   return PLSVO_OK;
 }
 
@@ -2257,7 +2257,10 @@ namespace {
 struct RecordSource { const AlignStateDev* ast = nullptr; const PoseStateDev* pst = nullptr; int n = 0; const char* why_not = nullptr; };
 RecordSource pick_record_source(plsvo_ctx* c) {
   RecordSource r;
-  if (c->ch_staged && c->a_staged && c->a_n == c->ch_n) {   // the resident frame step: its own pose-optimisation state
+  // the resident frame step: its own pose-optimisation state -- unless a staged pose-optimisation batch has run since the step was staged
+  // and last ran (the records then describe that batch: "the one that ran last", as between the two batches below)
+  const bool p_later = c->p_staged && c->p_run_seq > std::max(c->ch_stage_seq, c->ch_run_seq);
+  if (c->ch_staged && c->a_staged && c->a_n == c->ch_n && !p_later) {
     if (c->ch_run_seq == 0) { r.why_not = "pack_pose_records: the staged frame step has not run"; return r; }
     r.ast = c->a_d_state.as<AlignStateDev>(); r.pst = c->ch_w.state.as<PoseStateDev>(); r.n = c->ch_n;
     return r;

@@ -445,6 +445,45 @@ struct DetectLaunch {
   uint8_t* stage_survives;
 };
 
+// depth-filter seed lists resident on the device (seedlist_device.hpp, include/plsvo_hip.h plsvo_seeds_*): flat SoA rows for the whole
+// batch; a stream owns cap_pt / cap_seg rows per kind (multiples of the update kernel's workgroup) from pt_off / seg_off.  The rows are
+// SeedsBatchDev's input arrays (pt_ref_frame holds ref_kf, an index into the stream's resident keyframe table), the shadow rows its
+// outputs; the map tables are the candidate stage's.
+struct SeedStreamDev {
+  int n_pt, n_seg;                  // live rows per kind, in list order
+  int batch_counter;                // Seed::batch_counter, per stream
+  int cap_pt, cap_seg;              // rows as laid out
+  int rows_pt, rows_seg, rows_pt_cand, rows_seg_cand, cap_pt_obs, cap_seg_obs;   // the stream's room in the map tables (CandStreamHost)
+  int reserved0;
+  long long pt_off, seg_off;
+};
+struct SeedFrameDev {               // one stream's frame of an update
+  double T[7];
+  const double* d_T;                // device pointer read instead of T, or null
+  int active, cur_slot;
+};
+struct SeedReportDev {              // plsvo_seed_report, field for field
+  int pt[6], seg[6];                // rows per PLSVO_SEED_* status
+  int first_pt, first_seg, n_pt_seeds, n_seg_seeds, n_pt, n_seg, n_pt_cand, n_seg_cand, n_pt_obs, n_seg_obs, no_room, batch_counter;
+};
+struct SeedKfJobDev {               // one stream's keyframe event
+  int removed_kf, new_batch, new_kf, n_pt, n_seg, reserved0;
+  float mu, z_range, sigma2, reserved1;   // the constructor's values (src/depth_filter.cpp:53-74), computed on the host in float
+  long long pt_at, seg_at;          // the stream's new seeds in the uploaded arrays
+};
+struct SeedListBatchDev {
+  SeedsBatchDev s;                  // rows in, shadow rows out; frame_T / frame_slot: the candidate stage's frame table (rows from f_off)
+  NewCandBatchDev m;                // the map tables and the resident landmark quality (its records are not used)
+  SeedStreamDev* streams; const SeedFrameDev* frames; SeedReportDev* report;
+  const int* blk_stream;            // per workgroup of the update launch: its stream
+  int n_blk_pt, n_blk, n_jobs, max_n_kfs;
+  int* pt_batch_id; int* seg_batch_id; double* seg_spx; double* seg_epx;   // rows SeedsBatchDev does not have
+  // a keyframe event's upload
+  const SeedKfJobDev* kf_jobs;
+  const double* k_pt_px; const double* k_pt_f; const int* k_pt_level; const uint8_t* k_pt_type; const double* k_pt_grad;
+  const double* k_seg_px; const double* k_seg_f; const double* k_seg_sf; const double* k_seg_ef; const double* k_seg_spx; const double* k_seg_epx; const int* k_seg_level;
+};
+
 inline int detect_tiles(int w, int h, int* tiles_x) {
   *tiles_x = (w + kDetTileW - 1) / kDetTileW;
   return *tiles_x * ((h + kDetTileH - 1) / kDetTileH);

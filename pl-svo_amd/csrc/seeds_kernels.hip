@@ -8,7 +8,8 @@
 //   depthFromTriangulation                                   src/matcher.cpp:133-146
 //   DepthFilter::computeTau / updatePointSeed / updateLineSeed   src/depth_filter.cpp:568-584, :489-512, :514-566
 //   [ext] vk::patch_score::ZMSSD<4>, boost::math::pdf(normal_distribution<float>), warp::*, align2D (match_device.hpp)
-// The seed lists, their age test, the converged-seed callbacks and the detector's grid occupancy stay on the host.
+// plsvo_update_seeds maps seed state to seed state for lists kept on the host; plsvo_seeds_* keep the lists, their age test and the
+// converged-seed callbacks on the device (seedlist_device.hpp).  The detector's grid occupancy stays on the host.
 //
 // A seed is an independent problem: project its inverse-depth interval into the new frame, walk the epipolar segment
 // in 0.7-pixel steps scoring an 8x8 warped reference patch by zero-mean SSD (integer), refine the best position with
@@ -26,6 +27,7 @@
 #include "select_device.hpp"     // and their cell selection
 #include "insert_device.hpp"     // and the keyframe insertion into the resident tables
 #include "newcand_device.hpp"    // and the new candidate landmarks appended to them
+#include "seedlist_device.hpp"   // and the seed lists kept resident beside them
 
 namespace plsvo_hip {
 
@@ -65,45 +67,50 @@ __device__ __forceinline__ uint32_t dot4(uint32_t a, uint32_t b, uint32_t c) { r
 // Everything travels by value -- the handful of batch fields it reads (EpiCtx), the bearing, the result (EpiOut): handing the
 // kernel's 500-byte argument struct and three stack arrays over by address cost the kernel a 576-byte scratch frame per lane.
 struct EpiCtx {
-  const uint8_t* pyr_base; unsigned long long slot_bytes; const double* frame_T; const int* frame_slot;
+  const uint8_t* pyr_base; unsigned long long slot_bytes;
   double fx, fy, cx, cy, edgelet_max_angle;
   int width, height, cam_width, cam_height, n_pyr_levels, align_max_iter, max_epi_search_steps, edgelet_filtering;
 };
 struct EpiOut { int ok; double depth, px0, px1; };
+// the two frames of a seed: their poses (7 doubles each) and their pyramid slots
+struct SeedFrames { const double* T_ref; const double* T_cur; int slot_ref, slot_cur; };
 __device__ __forceinline__ EpiCtx epi_ctx(const SeedsBatchDev& s) {
   EpiCtx e;
-  e.pyr_base = s.pyr_base; e.slot_bytes = s.slot_bytes; e.frame_T = s.frame_T; e.frame_slot = s.frame_slot;
+  e.pyr_base = s.pyr_base; e.slot_bytes = s.slot_bytes;
   e.fx = s.fx; e.fy = s.fy; e.cx = s.cx; e.cy = s.cy; e.edgelet_max_angle = s.edgelet_max_angle;
   e.width = s.width; e.height = s.height; e.cam_width = s.cam_width; e.cam_height = s.cam_height; e.n_pyr_levels = s.n_pyr_levels;
   e.align_max_iter = s.align_max_iter; e.max_epi_search_steps = s.max_epi_search_steps; e.edgelet_filtering = s.edgelet_filtering;
   return e;
 }
-__device__ __forceinline__ bool epipolar_search_body(const EpiCtx& b, uint32_t* my, int rf, int cf, double rpx0, double rpx1, const double* f_ref,
+__device__ __forceinline__ bool epipolar_search_body(const EpiCtx& b, uint32_t* my, const SeedFrames& F, double rpx0, double rpx1, const double* f_ref,
                                                      int level, int type, double g0, double g1, double d_estimate, double d_min, double d_max, int seg,
                                                      double* depth, double* px_cur);
 // (an aggregate passed by value travels through the stack as well: the context sits in LDS, written once per workgroup, and the
 //  out-of-line function receives its address)
 typedef const __attribute__((address_space(3))) EpiCtx* EpiCtxLds;
-__device__ __noinline__ EpiOut epipolar_search(EpiCtxLds c, uint32_t* my, int rf, int cf, double rpx0, double rpx1, double f0, double f1, double f2,
-                                               int level, int type, double g0, double g1, double d_estimate, double d_min, double d_max, int seg) {
+__device__ __forceinline__ int epi_lts(int level, int type, int seg) { return level | (type << 8) | (seg << 16); }
+__device__ __noinline__ EpiOut epipolar_search(EpiCtxLds c, uint32_t* my, const double* T_ref_p, const double* T_cur_p, int slot_ref, int slot_cur, double rpx0, double rpx1, double f0, double f1, double f2,
+                                               int level_type_seg, double g0, double g1, double d_estimate, double d_min, double d_max) {
+  // (level, feature type and the end-point flag share one argument: with a pointer per frame the list would outgrow the argument registers)
+  const int level = level_type_seg & 0xff, type = (level_type_seg >> 8) & 0xff, seg = level_type_seg >> 16;
   EpiCtx b;
-  b.pyr_base = c->pyr_base; b.slot_bytes = c->slot_bytes; b.frame_T = c->frame_T; b.frame_slot = c->frame_slot;
+  b.pyr_base = c->pyr_base; b.slot_bytes = c->slot_bytes;
   b.fx = c->fx; b.fy = c->fy; b.cx = c->cx; b.cy = c->cy; b.edgelet_max_angle = c->edgelet_max_angle;
   b.width = c->width; b.height = c->height; b.cam_width = c->cam_width; b.cam_height = c->cam_height; b.n_pyr_levels = c->n_pyr_levels;
   b.align_max_iter = c->align_max_iter; b.max_epi_search_steps = c->max_epi_search_steps; b.edgelet_filtering = c->edgelet_filtering;
   const double f_ref[3] = { f0, f1, f2 };
   double depth = 0.0, px_cur[2] = { 0.0, 0.0 };
   EpiOut o;
-  o.ok = epipolar_search_body(b, my, rf, cf, rpx0, rpx1, f_ref, level, type, g0, g1, d_estimate, d_min, d_max, seg, &depth, px_cur) ? 1 : 0;
+  o.ok = epipolar_search_body(b, my, SeedFrames{T_ref_p, T_cur_p, slot_ref, slot_cur}, rpx0, rpx1, f_ref, level, type, g0, g1, d_estimate, d_min, d_max, seg, &depth, px_cur) ? 1 : 0;
   o.depth = depth; o.px0 = px_cur[0]; o.px1 = px_cur[1];
   return o;
 }
-__device__ __forceinline__ bool epipolar_search_body(const EpiCtx& b, uint32_t* my, int rf, int cf, double rpx0, double rpx1, const double* f_ref,
+__device__ __forceinline__ bool epipolar_search_body(const EpiCtx& b, uint32_t* my, const SeedFrames& F, double rpx0, double rpx1, const double* f_ref,
                                                      int level, int type, double g0, double g1, double d_estimate, double d_min, double d_max, int seg,
                                                      double* depth, double* px_cur) {
   const CamDev cam{b.fx, b.fy, b.cx, b.cy, b.cam_width, b.cam_height};
   px_cur[0] = 0.0; px_cur[1] = 0.0;
-  const SE3d T_ref = se3_load(b.frame_T + 7 * rf), T_cur = se3_load(b.frame_T + 7 * cf);
+  const SE3d T_ref = se3_load(F.T_ref), T_cur = se3_load(F.T_cur);
   const SE3d T_ref_inv = se3_inv(T_ref);
   const SE3d T_cur_ref = se3_mul(T_cur, T_ref_inv);
   if (seg && (d_min != d_min || d_max != d_max)) return false;                                   // :436-440
@@ -127,10 +134,10 @@ __device__ __forceinline__ bool epipolar_search_body(const EpiCtx& b, uint32_t* 
   const double dA0 = pxA0 - pxB0, dA1 = pxA1 - pxB1;
   const double epi_length = sqrt(dA0 * dA0 + dA1 * dA1) / (1 << search_level);
   if (epi_length != epi_length || fabs(epi_length) > 1.7976931348623157e308) return false;
-  const uint8_t* img_ref = b.pyr_base + (unsigned long long)b.frame_slot[rf] * b.slot_bytes + pyr_level_offset(b.width, b.height, level);
+  const uint8_t* img_ref = b.pyr_base + (unsigned long long)F.slot_ref * b.slot_bytes + pyr_level_offset(b.width, b.height, level);
   if (!warp_affine_lds(Aw, img_ref, b.width >> level, b.height >> level, rpx0, rpx1, level, search_level, my)) return false;
   const int cols = b.width >> search_level, rows = b.height >> search_level;
-  const uint8_t* cur_img = b.pyr_base + (unsigned long long)b.frame_slot[cf] * b.slot_bytes + pyr_level_offset(b.width, b.height, search_level);
+  const uint8_t* cur_img = b.pyr_base + (unsigned long long)F.slot_cur * b.slot_bytes + pyr_level_offset(b.width, b.height, search_level);
   const double sc = (double)(1 << search_level);
   int iters = 0;
   if (epi_length < 2.0) {                                                                        // :325-344
@@ -242,27 +249,16 @@ __device__ __forceinline__ bool px_in_image(const CamDev& cam, const double* px)
   return px[0] == px[0] && px[1] == px[1] && fabs(px[0]) < 1e9 && fabs(px[1]) < 1e9 && cam_is_in_frame(cam, (int)px[0], (int)px[1], 0, 0);
 }
 
-__global__ void __launch_bounds__(MT) update_seeds_kernel(const SeedsBatchDev b) {
-  __shared__ uint32_t s_patch[PB_ROWS * PB_WORDS * MT];
-  __shared__ EpiCtx s_epi;
-  const int lane = threadIdx.x;
-  if (lane == 0) s_epi = epi_ctx(b);
-  __syncthreads();
-  const EpiCtxLds epi = (EpiCtxLds)&s_epi;
-  const int gi = blockIdx.x * MT + lane;
-  if (gi >= b.n_pt + b.n_seg) return;
-  uint32_t* my = s_patch + lane;
-  const CamDev cam{b.fx, b.fy, b.cx, b.cy, b.cam_width, b.cam_height};
-  if (gi < b.n_pt) {
-    // ---- DepthFilter::updatePointSeeds, one seed (:295-360) ----
-    const int i = gi;
+// ---- DepthFilter::updatePointSeeds, one seed (:295-360): row i of the inputs -> row o of the outputs ----
+template <typename Row>
+__device__ __forceinline__ void update_point_seed(const SeedsBatchDev& b, const EpiCtxLds epi, uint32_t* my, const CamDev& cam, Row i, Row o, const SeedFrames F) {
+  {
     float a = b.pt_a[i], bb = b.pt_b[i], mu = b.pt_mu[i], sigma2 = b.pt_sigma2[i];
     const float z_range = b.pt_z_range[i];
     int status = PLSVO_SEED_NOT_VISIBLE;
     double xyz_world[3] = { 0, 0, 0 }, z = 0.0, px_cur[2] = { 0, 0 };
-    const int rf = b.pt_ref_frame[i], cf = b.pt_cur_frame[i];
     const double f[3] = { b.pt_f[3 * i], b.pt_f[3 * i + 1], b.pt_f[3 * i + 2] };
-    const SE3d T_ref = se3_load(b.frame_T + 7 * rf), T_cur = se3_load(b.frame_T + 7 * cf);
+    const SE3d T_ref = se3_load(F.T_ref), T_cur = se3_load(F.T_cur);
     const SE3d T_ref_cur = se3_mul(T_ref, se3_inv(T_cur));
     const SE3d T_cur_ref = se3_inv(T_ref_cur);
     const double s = 1.0 / mu;
@@ -276,8 +272,8 @@ __global__ void __launch_bounds__(MT) update_seeds_kernel(const SeedsBatchDev b)
       const float t_ = mu - sqrtf(sigma2);
       const float z_inv_max = t_ > 0.00000001f ? t_ : 0.00000001f;
       const double g0 = b.pt_grad ? b.pt_grad[2 * i] : 0.0, g1 = b.pt_grad ? b.pt_grad[2 * i + 1] : 0.0;
-      const EpiOut eo = epipolar_search(epi, my, rf, cf, b.pt_px[2 * i], b.pt_px[2 * i + 1], f[0], f[1], f[2], b.pt_level[i], b.pt_type[i], g0, g1,
-                                        1.0 / mu, 1.0 / z_inv_min, 1.0 / z_inv_max, 0);
+      const EpiOut eo = epipolar_search(epi, my, F.T_ref, F.T_cur, F.slot_ref, F.slot_cur, b.pt_px[2 * i], b.pt_px[2 * i + 1], f[0], f[1], f[2], epi_lts(b.pt_level[i], b.pt_type[i], 0), g0, g1,
+                                        1.0 / mu, 1.0 / z_inv_min, 1.0 / z_inv_max);
       z = eo.depth; px_cur[0] = eo.px0; px_cur[1] = eo.px1;
       if (!eo.ok) {
         bb += 1.0f;
@@ -305,21 +301,24 @@ __global__ void __launch_bounds__(MT) update_seeds_kernel(const SeedsBatchDev b)
         }
       }
     }
-    b.o_pt_status[i] = status; b.o_pt_a[i] = a; b.o_pt_b[i] = bb; b.o_pt_mu[i] = mu; b.o_pt_sigma2[i] = sigma2;
-    for (int k = 0; k < 3; ++k) b.o_pt_xyz[3 * i + k] = xyz_world[k];
-    b.o_pt_px[2 * i] = px_cur[0]; b.o_pt_px[2 * i + 1] = px_cur[1];
-    b.o_pt_depth[i] = z;
-  } else {
-    // ---- DepthFilter::updateLineSeeds, one seed (:391-467) ----
-    const int i = gi - b.n_pt;
+    b.o_pt_status[o] = status; b.o_pt_a[o] = a; b.o_pt_b[o] = bb; b.o_pt_mu[o] = mu; b.o_pt_sigma2[o] = sigma2;
+    for (int k = 0; k < 3; ++k) b.o_pt_xyz[3 * o + k] = xyz_world[k];
+    b.o_pt_px[2 * o] = px_cur[0]; b.o_pt_px[2 * o + 1] = px_cur[1];
+    b.o_pt_depth[o] = z;
+  }
+}
+
+// ---- DepthFilter::updateLineSeeds, one seed (:391-467) ----
+template <typename Row>
+__device__ __forceinline__ void update_line_seed(const SeedsBatchDev& b, const EpiCtxLds epi, uint32_t* my, const CamDev& cam, Row i, Row o, const SeedFrames F) {
+  {
     float a = b.seg_a[i], bb = b.seg_b[i], mu_s = b.seg_mu_s[i], mu_e = b.seg_mu_e[i], sigma2_s = b.seg_sigma2_s[i], sigma2_e = b.seg_sigma2_e[i];
     const float z_range_s = b.seg_z_range_s[i], z_range_e = b.seg_z_range_e[i];
     int status = PLSVO_SEED_NOT_VISIBLE;
     double xw_s[3] = { 0, 0, 0 }, xw_e[3] = { 0, 0, 0 }, z_s = 0.0, z_e = 0.0, px_cur[2];
-    const int rf = b.seg_ref_frame[i], cf = b.seg_cur_frame[i];
     const double sf[3] = { b.seg_sf[3 * i], b.seg_sf[3 * i + 1], b.seg_sf[3 * i + 2] }, ef[3] = { b.seg_ef[3 * i], b.seg_ef[3 * i + 1], b.seg_ef[3 * i + 2] };
     const double fc[3] = { b.seg_f[3 * i], b.seg_f[3 * i + 1], b.seg_f[3 * i + 2] };
-    const SE3d T_ref = se3_load(b.frame_T + 7 * rf), T_cur = se3_load(b.frame_T + 7 * cf);
+    const SE3d T_ref = se3_load(F.T_ref), T_cur = se3_load(F.T_cur);
     const SE3d T_ref_cur = se3_mul(T_ref, se3_inv(T_cur));
     const SE3d T_cur_ref = se3_inv(T_ref_cur);
     const double ss = 1.0 / mu_s, se = 1.0 / mu_e;
@@ -338,10 +337,10 @@ __global__ void __launch_bounds__(MT) update_seeds_kernel(const SeedsBatchDev b)
       const double px0 = b.seg_px[2 * i], px1 = b.seg_px[2 * i + 1];
       const int level = b.seg_level[i];
       // (the second search runs only when the first one succeeds, like the reference's `||`)
-      const EpiOut es = epipolar_search(epi, my, rf, cf, px0, px1, fc[0], fc[1], fc[2], level, PLSVO_FTR_CORNER, 0.0, 0.0, 1.0 / mu_s, 1.0 / z_inv_min_s, 1.0 / z_inv_max_s, 1);
+      const EpiOut es = epipolar_search(epi, my, F.T_ref, F.T_cur, F.slot_ref, F.slot_cur, px0, px1, fc[0], fc[1], fc[2], epi_lts(level, PLSVO_FTR_CORNER, 1), 0.0, 0.0, 1.0 / mu_s, 1.0 / z_inv_min_s, 1.0 / z_inv_max_s);
       z_s = es.depth;
       EpiOut ee; ee.ok = 0; ee.depth = 0.0; ee.px0 = 0.0; ee.px1 = 0.0;
-      if (es.ok) { ee = epipolar_search(epi, my, rf, cf, px0, px1, fc[0], fc[1], fc[2], level, PLSVO_FTR_CORNER, 0.0, 0.0, 1.0 / mu_e, 1.0 / z_inv_min_e, 1.0 / z_inv_max_e, 1); z_e = ee.depth; }
+      if (es.ok) { ee = epipolar_search(epi, my, F.T_ref, F.T_cur, F.slot_ref, F.slot_cur, px0, px1, fc[0], fc[1], fc[2], epi_lts(level, PLSVO_FTR_CORNER, 1), 0.0, 0.0, 1.0 / mu_e, 1.0 / z_inv_min_e, 1.0 / z_inv_max_e); z_e = ee.depth; }
       if (!es.ok || !ee.ok) {
         bb += 1.0f;
         status = PLSVO_SEED_NO_MATCH;
@@ -376,10 +375,68 @@ __global__ void __launch_bounds__(MT) update_seeds_kernel(const SeedsBatchDev b)
         }
       }
     }
-    b.o_seg_status[i] = status; b.o_seg_a[i] = a; b.o_seg_b[i] = bb; b.o_seg_mu_s[i] = mu_s; b.o_seg_mu_e[i] = mu_e;
-    b.o_seg_sigma2_s[i] = sigma2_s; b.o_seg_sigma2_e[i] = sigma2_e;
-    for (int k = 0; k < 3; ++k) { b.o_seg_xyz_s[3 * i + k] = xw_s[k]; b.o_seg_xyz_e[3 * i + k] = xw_e[k]; }
-    b.o_seg_depth_s[i] = z_s; b.o_seg_depth_e[i] = z_e;
+    b.o_seg_status[o] = status; b.o_seg_a[o] = a; b.o_seg_b[o] = bb; b.o_seg_mu_s[o] = mu_s; b.o_seg_mu_e[o] = mu_e;
+    b.o_seg_sigma2_s[o] = sigma2_s; b.o_seg_sigma2_e[o] = sigma2_e;
+    for (int k = 0; k < 3; ++k) { b.o_seg_xyz_s[3 * o + k] = xw_s[k]; b.o_seg_xyz_e[3 * o + k] = xw_e[k]; }
+    b.o_seg_depth_s[o] = z_s; b.o_seg_depth_e[o] = z_e;
+  }
+}
+
+__global__ void __launch_bounds__(MT) update_seeds_kernel(const SeedsBatchDev b) {
+  __shared__ uint32_t s_patch[PB_ROWS * PB_WORDS * MT];
+  __shared__ EpiCtx s_epi;
+  const int lane = threadIdx.x;
+  if (lane == 0) s_epi = epi_ctx(b);
+  __syncthreads();
+  const EpiCtxLds epi = (EpiCtxLds)&s_epi;
+  const int gi = blockIdx.x * MT + lane;
+  if (gi >= b.n_pt + b.n_seg) return;
+  uint32_t* my = s_patch + lane;
+  const CamDev cam{b.fx, b.fy, b.cx, b.cy, b.cam_width, b.cam_height};
+  if (gi < b.n_pt) {
+    const int i = gi, rf = b.pt_ref_frame[i], cf = b.pt_cur_frame[i];
+    update_point_seed(b, epi, my, cam, i, i, SeedFrames{b.frame_T + 7 * rf, b.frame_T + 7 * cf, b.frame_slot[rf], b.frame_slot[cf]});
+  } else {
+    const int i = gi - b.n_pt, rf = b.seg_ref_frame[i], cf = b.seg_cur_frame[i];
+    update_line_seed(b, epi, my, cam, i, i, SeedFrames{b.frame_T + 7 * rf, b.frame_T + 7 * cf, b.frame_slot[rf], b.frame_slot[cf]});
+  }
+}
+
+// The same bodies on the resident seed rows (seedlist_device.hpp): one lane per capacity row, a workgroup serves one stream.  The reference
+// keyframe's pose and slot come from the stream's rows of the candidate stage's frame table, the new frame's from the stream's record; a
+// seed of a batch older than max_n_kfs keyframes is marked PLSVO_SEED_AGED and not searched (src/depth_filter.cpp:289-292).
+__global__ void __launch_bounds__(MT) update_seeds_resident_kernel(const SeedListBatchDev L) {
+  __shared__ uint32_t s_patch[PB_ROWS * PB_WORDS * MT];
+  __shared__ EpiCtx s_epi;
+  const SeedsBatchDev& b = L.s;
+  const int lane = threadIdx.x;
+  if (lane == 0) s_epi = epi_ctx(b);
+  __syncthreads();
+  const EpiCtxLds epi = (EpiCtxLds)&s_epi;
+  const int blk = blockIdx.x, job = L.blk_stream[blk];
+  const SeedFrameDev& J = L.frames[job];
+  if (!J.active) return;
+  const SeedStreamDev& S = L.streams[job];
+  const CandMapDev& M = L.m.c.maps[job];
+  const bool seg = blk >= L.n_blk_pt;
+  const long long row = (long long)(seg ? blk - L.n_blk_pt : blk) * MT + lane;
+  if (row - (seg ? S.seg_off : S.pt_off) >= (seg ? S.n_seg : S.n_pt)) return;
+  uint32_t* my = s_patch + lane;
+  const CamDev cam{b.fx, b.fy, b.cx, b.cy, b.cam_width, b.cam_height};
+  const int ref_kf = seg ? b.seg_ref_frame[row] : b.pt_ref_frame[row];
+  const bool aged = S.batch_counter - (seg ? L.seg_batch_id[row] : L.pt_batch_id[row]) > L.max_n_kfs;
+  const SeedFrames F{L.m.c.frame_T + 7 * (M.f_off + ref_kf), J.d_T ? J.d_T : J.T, L.m.c.frame_slot[M.f_off + ref_kf], J.cur_slot};
+  if (!seg) {
+    if (!aged) { update_point_seed(b, epi, my, cam, row, row, F); return; }
+    b.o_pt_status[row] = kSeedAged; b.o_pt_a[row] = b.pt_a[row]; b.o_pt_b[row] = b.pt_b[row]; b.o_pt_mu[row] = b.pt_mu[row]; b.o_pt_sigma2[row] = b.pt_sigma2[row];
+    for (int k = 0; k < 3; ++k) b.o_pt_xyz[3 * row + k] = 0.0;
+    b.o_pt_px[2 * row] = 0.0; b.o_pt_px[2 * row + 1] = 0.0; b.o_pt_depth[row] = 0.0;
+  } else {
+    if (!aged) { update_line_seed(b, epi, my, cam, row, row, F); return; }
+    b.o_seg_status[row] = kSeedAged; b.o_seg_a[row] = b.seg_a[row]; b.o_seg_b[row] = b.seg_b[row]; b.o_seg_mu_s[row] = b.seg_mu_s[row]; b.o_seg_mu_e[row] = b.seg_mu_e[row];
+    b.o_seg_sigma2_s[row] = b.seg_sigma2_s[row]; b.o_seg_sigma2_e[row] = b.seg_sigma2_e[row];
+    for (int k = 0; k < 3; ++k) { b.o_seg_xyz_s[3 * row + k] = 0.0; b.o_seg_xyz_e[3 * row + k] = 0.0; }
+    b.o_seg_depth_s[row] = 0.0; b.o_seg_depth_e[row] = 0.0;
   }
 }
 
@@ -390,6 +447,22 @@ hipError_t launch_update_seeds(const SeedsBatchDev& b, hipStream_t stream) {
   return hipGetLastError();
 }
 
+// resident seed lists (seedlist_device.hpp): the update, one workgroup per 64 capacity rows; commit and keyframe event, one wave per stream
+hipError_t launch_update_seeds_resident(const SeedListBatchDev& b, hipStream_t stream) {
+  if (b.n_blk <= 0) return hipSuccess;
+  hipLaunchKernelGGL(update_seeds_resident_kernel, dim3(b.n_blk), dim3(MT), 0, stream, b);
+  return hipGetLastError();
+}
+hipError_t launch_seeds_commit(const SeedListBatchDev& b, hipStream_t stream) {
+  if (b.n_jobs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(seeds_commit_kernel, dim3((b.n_jobs + kSeedWaves - 1) / kSeedWaves), dim3(64 * kSeedWaves), 0, stream, b);
+  return hipGetLastError();
+}
+hipError_t launch_seeds_keyframe(const SeedListBatchDev& b, hipStream_t stream) {
+  if (b.n_jobs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(seeds_keyframe_kernel, dim3((b.n_jobs + kSeedWaves - 1) / kSeedWaves), dim3(64 * kSeedWaves), 0, stream, b);
+  return hipGetLastError();
+}
 // keyframe stage (keyframe_device.hpp): one wave per stream, four streams per workgroup
 hipError_t launch_close_keyframes(const CloseKfBatchDev& b, hipStream_t stream) {
   if (b.n_jobs <= 0) return hipSuccess;

@@ -163,6 +163,29 @@ class HipBackend:
         self.ctx.candidates_add([new])
         return self.ctx.candidates_add_fetch()[0], self.ctx.candidates_fetch_quality()[0]
 
+    def seeds_stage(self, lists, cam, room=None, **params):
+        """the stream's seed lists become a resident table beside the staged map tables (plsvo_seeds_stage); lists: the
+        arrays of plsvo_seed_list and batch_counter as capi.Context.seeds_stage takes them; room: extra_pt / extra_seg rows for the seeds
+        later keyframes start; params: max_n_kfs and the matcher's options"""
+        self.ctx.seeds_reserve(**(room or {}))
+        self.ctx.seeds_stage([lists], cam, **params)
+
+    def seeds_update(self, cur_slot, T_f_w=None):
+        """the resident seeds updated with the frame in cur_slot, aged, erased and handed over to the resident map tables on the device
+        (plsvo_seeds_update .. _update_fetch); T_f_w None: the optimised pose the resident pose optimiser left on the device.
+        -> (the report: capi.Context.seeds_update_fetch's record, the update's rows: capi.Context.seeds_fetch_rows', the quality state)"""
+        self.ctx.seeds_update([dict(cur_slot=cur_slot, T_f_w=T_f_w)])
+        return self.ctx.seeds_update_fetch()[0], self.ctx.seeds_fetch_rows()[0], self.ctx.candidates_fetch_quality()[0]
+
+    def seeds_keyframe(self, **event):
+        """a keyframe event on the resident seed lists (plsvo_seeds_keyframe): removed_kf, new_batch, new_kf, depth_mean, depth_min and the
+        new seeds' arrays"""
+        self.ctx.seeds_keyframe([event])
+
+    def seeds_fetch_lists(self):
+        """the resident seed lists as they stand (plsvo_seeds_fetch_lists)"""
+        return self.ctx.seeds_fetch_lists()[0]
+
     def detect_corners(self, slot, occupancy=None, cell_size=25, n_levels=3, detection_threshold=20.0):
         """FastDetector::detect on the frame in `slot` (plsvo_hip_detect_fast): abi.CORNER_DTYPE records in cell order"""
         return self.ctx.detect_fast(slot, 1, cell_size, n_levels, 20, detection_threshold, None if occupancy is None else occupancy[None])[0]
@@ -273,7 +296,7 @@ def candidate_map_tables(t):
 def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_thresh=2.0, mapping=False, known_frac=0.6,
                  pos_noise=0.005, map_seed=0, kf_every=5, detect=False, detect_cell_size=25, kf_select=False, kfselect_mindist_t=0.06,
                  kfselect_mindist_r=3.0, max_n_kfs=10, map_candidates=False, record_candidates=False, cell_select=False, select_params=None, kf_insert=False,
-                 seed_candidates=False):
+                 seed_candidates=False, seeds_resident=False):
     """-> list of per-frame dicts (pose T_f_w, cov, counts).  Frame 0 is the keyframe with the true pose.
     mapping=True: only `known_frac` of the point landmarks start in the map (positions off by `pos_noise` x depth along
     their viewing ray), the others are depth-filter seeds; the seed update runs every frame; every `kf_every`-th frame
@@ -306,8 +329,16 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
     harness appends the same row to its own tables.  The seed's table row is then a NEW one behind the staged rows, no longer its landmark
     index: the harness keeps the row of every landmark and the landmark of every row, and translates wherever the backend speaks in rows
     (filed and selected landmarks, moved positions).  With record_candidates rec["add"] holds the tables and the quality before, the new
-    records, the tables and the quality after, and the backend's report."""
+    records, the tables and the quality after, and the backend's report.
+    seeds_resident=True (with seed_candidates, a backend with seeds_stage): the map's seeds are staged ONCE, beside the map tables, and are
+    updated, erased and handed over to the resident tables on the device (plsvo_seeds_update): no seed travels per frame and
+    no record comes back, only the report and the update's rows, from which the harness keeps its own tables exactly as it does from an
+    add's report.  A removal at an insertion is passed on (plsvo_seeds_keyframe); when it takes frame 0's keyframe out, the seeds that
+    are left leave the device with it -- their keyframe is no longer in the table -- and the harness goes on following them on the host,
+    outside the map, as it does without this flag.  With the flag off every record is what it is without it."""
     params = dict(locals())                            # (first statement: exactly the arguments)
+    if seeds_resident and not (seed_candidates and hasattr(backend, "seeds_stage")):
+        raise ValueError("seeds_resident needs seed_candidates and a backend with seeds_stage()")
     if seed_candidates and not (kf_insert and hasattr(backend, "map_add_candidates")):
         raise ValueError("seed_candidates needs kf_insert and a backend with map_add_candidates()")
     if kf_insert and not (cell_select and mapping and hasattr(backend, "map_insert")):
@@ -328,8 +359,9 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
 
 
 def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thresh, mapping, known_frac, pos_noise, map_seed, kf_every, detect, detect_cell_size, kf_select,
-                  kfselect_mindist_t, kfselect_mindist_r, max_n_kfs, map_candidates, record_candidates, cell_select, select_params, kf_insert, seed_candidates):
+                  kfselect_mindist_t, kfselect_mindist_r, max_n_kfs, map_candidates, record_candidates, cell_select, select_params, kf_insert, seed_candidates, seeds_resident):
     cam = seq["cam"]
+    seeds_on_device = False                            # seeds_resident: the seed lists are staged and their keyframe is still in the table
     if cell_select and not (map_candidates and hasattr(backend, "map_select")):
         raise ValueError("cell_select needs map_candidates and a backend with map_select()")
     if map_candidates and (hasattr(backend, "frame_step") or not hasattr(backend, "map_select" if cell_select else "map_candidates")):
@@ -453,6 +485,15 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                     cm_before = copy.deepcopy(cm) if record_candidates else None
                     cr, mr, sel, pr_sel, q_after = backend.map_select(map_job, abi.CandidateFrameJob(T_k, overlap, cur_slot=k), cam, n_pyr_levels, select_kw,
                                                                       carry=quality if map_job is not None else None)
+                    if seeds_resident and map_job is not None and mapping and seed_kf is not None:
+                        # the seed lists join the tables that were just staged: every seed was started in frame 0's keyframe, in one batch
+                        # that never ages (the harness keeps its seeds until they converge)
+                        si_ = seeds["idx"]
+                        backend.seeds_stage(dict(batch_counter=0, pt_ref_kf=np.full(len(si_), seed_kf, np.int32), pt_batch_id=np.zeros(len(si_), np.int32), pt_px=seq["pt_px0"][si_],
+                                                 pt_f=seq["pt_f0"][si_], pt_level=np.zeros(len(si_), np.int32), pt_type=np.zeros(len(si_), np.uint8),
+                                                 pt_grad=np.zeros((len(si_), 2)), pt_a=seeds["a"], pt_b=seeds["b"], pt_mu=seeds["mu"], pt_z_range=seeds["z_range"],
+                                                 pt_sigma2=seeds["sigma2"]), cam, max_n_kfs=1 << 30, n_pyr_levels=n_pyr_levels)
+                        seeds_on_device = True
                 else:
                     cr, mr = backend.map_candidates(map_job, abi.CandidateFrameJob(T_k, overlap, cur_slot=k), cam, n_pyr_levels)
                 npf, nsf = cr["n_filed_pt"], cr["n_filed_seg"]
@@ -572,6 +613,9 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                             seed_kf = None if remove == seed_kf else seed_kf - (remove < seed_kf)
                     before = (copy.deepcopy(cm), quality) if record_candidates else None
                     tables, quality, ins = backend.map_insert(remove, k)
+                    if seeds_on_device and remove >= 0:                # removeKeyframe: the seeds' keyframe moves down a row, or leaves with its seeds
+                        backend.seeds_keyframe(removed_kf=remove)
+                        seeds_on_device = seed_kf is not None
                     cm = candidate_map_tables(tables)
                     rec.update(n_joined=ins["n_joined_pt"] + ins["n_joined_seg"], n_deleted_kf=ins["n_deleted_pt"] + ins["n_deleted_seg"], remove_kf=remove)
                     if record_candidates:
@@ -621,7 +665,11 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                 si_ = seeds["idx"]
                 ptd = dict(ref_frame=np.zeros(ns, np.int32), cur_frame=np.ones(ns, np.int32), px=seq["pt_px0"][si_], f=seq["pt_f0"][si_], level=np.zeros(ns, np.int32),
                            a=seeds["a"], b=seeds["b"], mu=seeds["mu"], z_range=seeds["z_range"], sigma2=seeds["sigma2"])
-                sr = backend.update_seeds(abi.SeedsJob(cam, np.stack([kf_T, T_k]), np.array([0, k], np.int32), ptd, None, n_pyr_levels=n_pyr_levels))
+                if seeds_on_device:                               # on the resident lists: the report and the rows come back, no record travels
+                    seed_report, sr, seed_quality = backend.seeds_update(k, T_k)
+                    assert len(sr["pt_status"]) == ns and seed_report["no_room"] == 0
+                else:
+                    sr = backend.update_seeds(abi.SeedsJob(cam, np.stack([kf_T, T_k]), np.array([0, k], np.int32), ptd, None, n_pyr_levels=n_pyr_levels))
                 stt = sr["pt_status"]
                 conv = stt == abi.SEED_CONVERGED
                 P3[si_[conv]] = sr["pt_xyz_world"][conv]
@@ -633,7 +681,12 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                     new = dict(pt_pos=sr["pt_xyz_world"][conv], pt_obs_kf=np.full(len(ci), seed_kf, np.int32), pt_obs_px=seq["pt_px0"][ci], pt_obs_f=seq["pt_f0"][ci],
                                pt_obs_level=np.zeros(len(ci), np.int32), pt_obs_type=np.full(len(ci), abi.FTR_CORNER, np.uint8), pt_obs_grad=np.zeros((len(ci), 2)))
                     before = (copy.deepcopy(cm), quality) if record_candidates else None
-                    report, quality = backend.map_add_candidates(new)
+                    if seeds_on_device:                           # the commit has appended them already: its report stands in for the add's
+                        report = dict(first_pt=seed_report["first_pt"], first_seg=-1, n_added_pt=len(ci), n_added_seg=0, n_pt=seed_report["n_pt"], n_seg=seed_report["n_seg"],
+                                      n_pt_cand=seed_report["n_pt_cand"], n_seg_cand=seed_report["n_seg_cand"], n_pt_obs=seed_report["n_pt_obs"], n_seg_obs=seed_report["n_seg_obs"])
+                        quality = seed_quality
+                    else:
+                        report, quality = backend.map_add_candidates(new)
                     for j, i in enumerate(ci):
                         row = len(cm["pt_pos"])
                         assert row == report["first_pt"] + j

@@ -1361,6 +1361,75 @@ int plsvo_seeds_fetch_rows(plsvo_ctx* ctx, int n, plsvo_seed_rows* out);
 int plsvo_seeds_commit_rows(plsvo_ctx* ctx, int n, const plsvo_seed_rows* rows);
 
 /* ------------------------------------------------------------------------------------------ */
+/* a keyframe's point seeds started on the device from its FAST corners: the  */
+/* creating half of DepthFilter::initializeSeeds (src/depth_filter.cpp:151-191) --             */
+/* FastDetector::setExistingFeatures(frame->pt_fts_) (:161), the grid cells setGridOccpuancy   */
+/* marked during the last update (:327-331), FastDetector::detect (:162-165,                   */
+/* src/feature_detection.cpp:53-104), a PointSeed per new PointFeat (:184-186) -- without the  */
+/* corners, the occupancy grid or the seeds crossing the bus.  Line seeds still travel as in   */
+/* plsvo_seeds_keyframe (there is no device line detector).  Not covered: Frame::key_pts_, the */
+/* C++ adapter; Seed::batch_counter stays per stream (see above).                              */
+/* ------------------------------------------------------------------------------------------ */
+
+#define PLSVO_SEED_OCC_SELECTED 1   /* FastDetector::setExistingFeatures(frame->pt_fts_), src/depth_filter.cpp:161: the point features the last
+                                       plsvo_candidates_select wrote for the stream's new frame -- all n_matches of them, those the pose
+                                       optimiser culled included (the reference leaves a culled feature in pt_fts_) */
+#define PLSVO_SEED_OCC_UPDATED  2   /* setGridOccpuancy(matcher_.px_cur_) of the last fetched update, src/depth_filter.cpp:327-331: px_cur of every
+                                       shadow row with status UPDATED, CONVERGED or NAN (the cell is marked before the convergence and
+                                       NaN tests); rows NOT_VISIBLE, NO_MATCH and AGED mark nothing */
+
+/* One stream's event, applied in this order: removeKeyframe(removed_kf) and ++batch_counter if new_batch, exactly as plsvo_seeds_keyframe;
+ * the detector's grid for the configured level-0 size and params->cell_size (a cell is marked by the caller's byte or by a position of a
+ * chosen source lying in it, cell = plsvo_detect_cell's; a position that is negative, not finite, or at or beyond the image size marks
+ * nothing); FastDetector::detect on the pyramid slot of keyframe new_kf (the stream's resident slot) with that grid; one point seed per
+ * valid cell in cell-index order behind the live rows -- ref_kf = new_kf, batch_id = the counter, px = (x_L << level, y_L << level),
+ * type PLSVO_FTR_CORNER, grad (1, 0) (PointFeat's constructor), f = cam2world(px), a = b = 10 and mu, z_range, sigma2 as
+ * plsvo_seeds_keyframe computes them; then the n_seg uploaded line seeds. */
+typedef struct plsvo_seed_kf_detect {
+  int32_t active;                   /* 0: the stream is not touched at all and costs no launch work */
+  int32_t removed_kf;               /* -1: none */
+  int32_t new_batch, new_kf;
+  int32_t occ_sources;              /* PLSVO_SEED_OCC_* bits */
+  int32_t n_seg;
+  double depth_mean, depth_min;     /* as plsvo_seed_kf's */
+  const uint8_t* d_occupancy;       /* DEVICE, cells bytes (cols * rows of plsvo_detect_grid), non-zero = occupied, OR-ed in; may be NULL */
+  const double* seg_px; const double* seg_f; const double* seg_sf; const double* seg_ef; const double* seg_spx; const double* seg_epx; const int32_t* seg_level;
+} plsvo_seed_kf_detect;
+
+/* What the last event of a stream did; all zero for a stream no event has touched since the stage. */
+typedef struct plsvo_seed_kf_report {
+  int32_t n_new_pt, n_new_seg;      /* seeds appended (0 with no_room) */
+  int32_t n_pt_seeds, n_seg_seeds;  /* list lengths behind the event */
+  int32_t batch_counter;
+  int32_t no_room;                  /* PLSVO_SEEDS_NO_ROOM: nothing of either kind was appended */
+  int32_t n_occupied;               /* cells of the detector's grid that were marked */
+  int32_t reserved0;
+} plsvo_seed_kf_report;
+
+/* keyframe_detect: ENQUEUE ONLY after the copy of the line seeds; the host waits for nothing.  Three launches whose sizes follow the
+ *   ACTIVE streams: the occupancy grids, the detection (the detect_fast kernel through a slot table: the streams' keyframes sit in any
+ *   slots and two streams may share one), the seed start.  The number of new point seeds is known to the device alone, so the point
+ *   rows' room is decided there: when the live point rows (behind the removal) plus the new seeds exceed the rows the stream was laid
+ *   out with (plsvo_seeds_capacity), NOTHING of either kind is appended and the report says PLSVO_SEEDS_NO_ROOM; the removal and the
+ *   counter are applied either way.  The caller restages with room and repeats the event with removed_kf = -1, new_batch = 0: the
+ *   result is then the reference's.  A caller that reserves `cells` point rows beyond its lists (plsvo_seeds_reserve) can never see
+ *   no_room.  The segments' room is decided on the host from the mirrored lengths: PLSVO_E_CAPACITY, nothing written.  The detector's
+ *   keys are left armed in every case: any detection may follow.
+ *   Behind the call the host's mirrored list lengths are upper bounds until plsvo_seeds_keyframe_fetch, plsvo_seeds_fetch_lists or the
+ *   next plsvo_seeds_update_fetch makes them exact: the point list's is old length + cells, capped at the stream's rows; the line
+ *   list's is old length + n_seg, which a stream reported PLSVO_SEEDS_NO_ROOM did not append.
+ *   PLSVO_E_STATE: no staged seed tables, an unfetched update, the pyramids not those of the stage, PLSVO_SEED_OCC_SELECTED without a
+ *   selection on the context, PLSVO_SEED_OCC_UPDATED without a fetched update.  PLSVO_E_INVALID: whatever plsvo_hip_detect_fast_dev
+ *   refuses in its params, n other than the staged n, and for an active stream new_kf outside the keyframe table, a keyframe slot
+ *   outside the pyramids, unknown source bits, a non-positive depth, removed_kf outside [-1, n_kf], a negative n_seg, a NULL segment
+ *   array with n_seg > 0, a segment level outside the pyramid.  Every check runs before anything is written or enqueued.
+ * keyframe_fetch: synchronises, returns every stream's report and makes the mirrored list lengths exact, as plsvo_seeds_fetch_lists
+ *   does.  A pipeline that goes straight on to the next frame's plsvo_seeds_update / _update_fetch needs neither; behind that update
+ *   fetch this call costs a copy and no wait.  PLSVO_E_STATE before the first event since the stage and behind an unfetched update. */
+int plsvo_seeds_keyframe_detect(plsvo_ctx* ctx, int n, const plsvo_detect_params* params, const plsvo_seed_kf_detect* in);
+int plsvo_seeds_keyframe_fetch(plsvo_ctx* ctx, int n, plsvo_seed_kf_report* out);
+
+/* ------------------------------------------------------------------------------------------ */
 /* multi-GPU: gather of per-stream pose records (new; the reference is single-process)         */
 /* ------------------------------------------------------------------------------------------ */
 
@@ -1413,7 +1482,7 @@ int plsvo_gather_poses(plsvo_ctx* ctx, void* rccl_comm, const plsvo_pose_record*
 #define PLSVO_K_CANDIDATES    8   /* plsvo_candidates_run: the re-arm and the launch alone (the resident match counts under PLSVO_K_MATCH) */
 #define PLSVO_K_SELECT        9   /* plsvo_candidates_select: the re-arm and the launch alone */
 #define PLSVO_K_INSERT        10  /* plsvo_candidates_insert_keyframe: the launch that changes the tables (the planning launch is timed by the caller's clock) */
-#define PLSVO_K_NEWCAND       11  /* plsvo_candidates_add: the launch alone; the commit launch of plsvo_seeds_update, plsvo_seeds_keyframe's */
+#define PLSVO_K_NEWCAND       11  /* plsvo_candidates_add: the launch alone; the commit launch of plsvo_seeds_update, plsvo_seeds_keyframe's, the three of plsvo_seeds_keyframe_detect */
 #define PLSVO_K_COUNT         12
 int plsvo_hip_set_profiling(plsvo_ctx* ctx, int enable);
 /* accumulated GPU time and launch count of kernel family k since the last reset (synchronises) */

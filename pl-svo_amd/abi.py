@@ -367,6 +367,21 @@ class SeedKf(C.Structure):
                [(f, _SEED_CT[t][0]) for f, t, _ in _SEED_KF_FIELDS]
 
 
+SEED_OCC_SELECTED, SEED_OCC_UPDATED = 1, 2
+_SEED_KF_DETECT_FIELDS = tuple(f for f in _SEED_KF_FIELDS if f[0].startswith("seg_"))
+
+
+class SeedKfDetect(C.Structure):
+    """plsvo_seed_kf_detect"""
+    _fields_ = [(f, C.c_int32) for f in ("active", "removed_kf", "new_batch", "new_kf", "occ_sources", "n_seg")] + [("depth_mean", C.c_double), ("depth_min", C.c_double)] + \
+               [("d_occupancy", C.c_void_p)] + [(f, _SEED_CT[t][0]) for f, t, _ in _SEED_KF_DETECT_FIELDS]
+
+
+class SeedKfReport(C.Structure):
+    """plsvo_seed_kf_report"""
+    _fields_ = [(f, C.c_int32) for f in ("n_new_pt", "n_new_seg", "n_pt_seeds", "n_seg_seeds", "batch_counter", "no_room", "n_occupied", "reserved0")]
+
+
 class SeedRows(C.Structure):
     """plsvo_seed_rows"""
     _fields_ = [(f, C.c_int32) for f in ("n_pt", "n_seg", "active", "reserved0")] + [(f, _SEED_CT[t][0]) for f, t, _ in _SEED_ROWS_FIELDS]

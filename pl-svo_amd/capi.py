@@ -33,7 +33,7 @@ SYMBOLS = [
     "plsvo_candidates_reserve", "plsvo_candidates_capacity", "plsvo_candidates_insert_keyframe", "plsvo_candidates_insert_fetch", "plsvo_candidates_fetch_map", "plsvo_candidates_set_positions",
     "plsvo_candidates_reserve_landmarks", "plsvo_candidates_lm_capacity", "plsvo_candidates_add", "plsvo_candidates_add_fetch",
     "plsvo_seeds_reserve", "plsvo_seeds_capacity", "plsvo_seeds_stage", "plsvo_seeds_update", "plsvo_seeds_update_fetch", "plsvo_seeds_keyframe", "plsvo_seeds_fetch_lists",
-    "plsvo_seeds_fetch_rows", "plsvo_seeds_commit_rows",
+    "plsvo_seeds_fetch_rows", "plsvo_seeds_commit_rows", "plsvo_seeds_keyframe_detect", "plsvo_seeds_keyframe_fetch",
     "plsvo_chain_stage", "plsvo_chain_run", "plsvo_chain_fetch", "plsvo_frame_step_batch", "plsvo_chain_poses_dev",
     "plsvo_pack_pose_records", "plsvo_fetch_pose_records", "plsvo_gather_poses",
     "plsvo_hip_set_profiling", "plsvo_hip_kernel_time", "plsvo_hip_reset_profiling",
@@ -181,6 +181,8 @@ def lib():
         "plsvo_seeds_fetch_lists": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.SeedList)]),
         "plsvo_seeds_fetch_rows": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.SeedRows)]),
         "plsvo_seeds_commit_rows": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.SeedRows)]),
+        "plsvo_seeds_keyframe_detect": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.DetectParams), C.POINTER(abi.SeedKfDetect)]),
+        "plsvo_seeds_keyframe_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.SeedKfReport)]),
         "plsvo_update_seeds": (C.c_int, [ctxp, C.POINTER(abi.SeedsIn), C.POINTER(abi.SeedsOut)]),
         "plsvo_trajectory_record": (C.c_int, [abi.c_double_p, abi.c_double_p, abi.c_double_p]),
         "plsvo_chain_stage": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.ChainIn), C.POINTER(abi.ChainParams)]),
@@ -1091,6 +1093,36 @@ class Context:
             a.n_seg = 0 if e.get("seg_px") is None else len(e["seg_px"])
             keep.append(self._seed_fill(a, e, abi._SEED_KF_FIELDS, (a.n_pt, a.n_seg)))
         self._chk(self.L.plsvo_seeds_keyframe(self.h, n, arr))
+
+    def seeds_keyframe_detect(self, events, cell_size=25, n_levels=3, fast_threshold=20, detection_threshold=20.0):
+        """plsvo_seeds_keyframe_detect (enqueue only): per staged stream None (not active) or a dict of removed_kf (-1), new_batch, new_kf,
+        depth_mean, depth_min, occ_sources (abi.SEED_OCC_* bits, default both), d_occupancy (a device pointer to `cells` bytes, or None)
+        and the line seeds' arrays named like plsvo_seed_kf_detect's (the count is the length of seg_px).  The keyframe's corners become
+        point seeds of the resident lists without leaving the device"""
+        n = len(events)
+        arr = (abi.SeedKfDetect * max(n, 1))()
+        keep = []
+        for a, e in zip(arr, events):
+            a.removed_kf = -1
+            if e is None:
+                continue
+            a.active = 1
+            a.removed_kf, a.new_batch, a.new_kf = int(e.get("removed_kf", -1)), int(bool(e.get("new_batch", 0))), int(e.get("new_kf", 0))
+            a.depth_mean, a.depth_min = float(e.get("depth_mean", 0.0)), float(e.get("depth_min", 0.0))
+            a.occ_sources = int(e.get("occ_sources", abi.SEED_OCC_SELECTED | abi.SEED_OCC_UPDATED))
+            a.d_occupancy = e.get("d_occupancy") or None
+            a.n_seg = 0 if e.get("seg_px") is None else len(e["seg_px"])
+            keep.append(self._seed_fill(a, e, abi._SEED_KF_DETECT_FIELDS, (0, a.n_seg)))
+        pr = abi.detect_params(cell_size, n_levels, fast_threshold, detection_threshold)
+        self._chk(self.L.plsvo_seeds_keyframe_detect(self.h, n, C.byref(pr), arr))
+
+    def seeds_keyframe_fetch(self):
+        """plsvo_seeds_keyframe_fetch (synchronises): per stream a dict of abi.SeedKfReport's fields -- what the stream's last
+        seeds_keyframe_detect event did"""
+        n = self._seed_n
+        outs = (abi.SeedKfReport * max(n, 1))()
+        self._chk(self.L.plsvo_seeds_keyframe_fetch(self.h, n, outs))
+        return [{f: int(getattr(o, f)) for f, _ in abi.SeedKfReport._fields_} for o in outs[:n]]
 
     def seeds_fetch_lists(self):
         """plsvo_seeds_fetch_lists (synchronises): per stream a dict of the lists as they stand, arrays named like plsvo_seed_list's, and

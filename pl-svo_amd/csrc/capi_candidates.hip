@@ -24,7 +24,7 @@ static QualitySections quality_sections(const plsvo_ctx* c) {
   return s;
 }
 static void cand_reset_run(plsvo_ctx* c) { c->cd_ran = c->cd_matched = c->cs_selected = c->cs_posed = c->ci_inserted = c->cn_closed = false; }   // the steps taken on the last run's results
-static void cand_reset_stage(plsvo_ctx* c) { cand_reset_run(c); c->cd_staged = c->ci_have_out = c->cn_have_out = c->sd_staged = c->sd_pending = c->sd_have_report = false; }   // those, the tables, the last insertion's and add's reports
+static void cand_reset_stage(plsvo_ctx* c) { cand_reset_run(c); c->cd_staged = c->ci_have_out = c->cn_have_out = c->sd_staged = c->sd_pending = c->sd_have_report = c->sk_have_report = false; }   // those, the tables, the last insertion's and add's reports
 // PLSVO_OK while the last run's candidates still describe the tables; once an insertion or an add came behind it, the refusal of entry point `who`
 static int cand_run_open(plsvo_ctx* c, const char* who) {
   const char* why = c->ci_inserted ? "this run's frame was inserted" : c->cn_closed ? "landmarks were added behind this run" : nullptr;
@@ -1085,7 +1085,7 @@ extern "C" int plsvo_seeds_stage(plsvo_ctx* c, int n, const plsvo_seed_params* p
     tp += (size_t)S.cap_pt; ts += (size_t)S.cap_seg;
   }
   if (tp / 64 + ts / 64 > (size_t)INT32_MAX) return fail(c, PLSVO_E_CAPACITY, "seeds_stage: batch too large");
-  c->sd_staged = false; c->sd_have_report = false;
+  c->sd_staged = false; c->sd_have_report = false; c->sk_have_report = false;
   c->sd_params = *pr; c->sd_n = n; c->sd_host = sd; c->sd_lim = lim; c->sd_max_level = max_level; c->sd_t_pt = tp; c->sd_t_seg = ts;
   if (n == 0) { c->sd_staged = true; c->sd_b = SeedListBatchDev{}; return PLSVO_OK; }
   HIP_TRY(c, hipSetDevice(c->device));
@@ -1117,6 +1117,8 @@ extern "C" int plsvo_seeds_stage(plsvo_ctx* c, int n, const plsvo_seed_params* p
   const SeedWorkSections W = seed_work_sections(N, tp, ts);
   HIP_TRY(c, c->sd_d_work.ensure(W.end + 256));
   HIP_TRY(c, hipMemsetAsync(c->sd_d_work.p, 0, W.end, c->stream));
+  HIP_TRY(c, c->sk_d_report.ensure(N * sizeof(SeedStartReportDev)));   // plsvo_seeds_keyframe_detect's reports: all zero until an event touches the stream
+  HIP_TRY(c, hipMemsetAsync(c->sk_d_report.p, 0, N * sizeof(SeedStartReportDev), c->stream));
   char* d = reinterpret_cast<char*>(c->sd_d_tab.p); char* w = reinterpret_cast<char*>(c->sd_d_work.p);
   auto D = [&](size_t o) { return reinterpret_cast<double*>(d + o); };
   auto Iv = [&](size_t o) { return reinterpret_cast<int*>(d + o); };
@@ -1318,6 +1320,130 @@ extern "C" int plsvo_seeds_keyframe(plsvo_ctx* c, int n, const plsvo_seed_kf* in
     S.n_pt += in[s].n_pt; S.n_seg += in[s].n_seg; S.batch_counter += in[s].new_batch ? 1 : 0;
   }
   c->sd_max_level = max_level;
+  return PLSVO_OK;
+}
+
+// DepthFilter::initializeSeeds' creating half (:151-191) on the device: occupancy grids, detection through a slot table, seed start
+extern "C" int plsvo_seeds_keyframe_detect(plsvo_ctx* c, int n, const plsvo_detect_params* p, const plsvo_seed_kf_detect* in) {
+  CTX_CHECK(c);
+  if (const int rc = seeds_ready(c, n, in, "seeds_keyframe_detect")) return rc;
+  if (!c->pyr.base || c->pyr.n_levels < c->sd_params.n_pyr_levels || c->sd_params.cam.width != c->pyr.w[0] || c->sd_params.cam.height != c->pyr.h[0])
+    return fail(c, PLSVO_E_STATE, "seeds_keyframe_detect: the configured pyramids are not those of the stage");
+  if (!p) return fail(c, PLSVO_E_INVALID, "seeds_keyframe_detect: NULL params");
+  int n_act = 0;
+  for (int s = 0; s < n; ++s) n_act += in[s].active ? 1 : 0;
+  int cols = 0, rows = 0;
+  if (const int rc = detect_check_params(c, n_act, p, "seeds_keyframe_detect", &cols, &rows)) return rc;
+  const int cells = cols * rows;
+  size_t ts = 0;
+  int sources = 0, max_level = std::max(c->sd_max_level, p->n_levels - 1);
+  for (int s = 0; s < n; ++s) {
+    const plsvo_seed_kf_detect& I = in[s]; const CandMapDev& M = c->cd_maps[(size_t)s];
+    if (!I.active) continue;
+    if (I.removed_kf < -1 || I.removed_kf > M.n_kf) return fail(c, PLSVO_E_INVALID, "seeds_keyframe_detect: removed_kf outside the keyframe table as it stood");
+    if (I.new_kf < 0 || I.new_kf >= M.n_kf) return fail(c, PLSVO_E_INVALID, "seeds_keyframe_detect: new_kf outside the keyframe table");
+    const int slot = c->cd_kf_slot[(size_t)M.kf_off + (size_t)I.new_kf];
+    if (slot < 0 || slot >= c->pyr.n_slots) return fail(c, PLSVO_E_INVALID, "seeds_keyframe_detect: the keyframe's pyramid slot is out of range");
+    if (I.occ_sources & ~(PLSVO_SEED_OCC_SELECTED | PLSVO_SEED_OCC_UPDATED)) return fail(c, PLSVO_E_INVALID, "seeds_keyframe_detect: unknown occupancy source");
+    if (!((float)I.depth_mean > 0.0f) || !((float)I.depth_min > 0.0f)) return fail(c, PLSVO_E_INVALID, "seeds_keyframe_detect: depth not positive");
+    if (I.n_seg < 0) return fail(c, PLSVO_E_INVALID, "seeds_keyframe_detect: negative count");
+    if (I.n_seg > 0 && (!I.seg_px || !I.seg_f || !I.seg_sf || !I.seg_ef || !I.seg_spx || !I.seg_epx || !I.seg_level)) return fail(c, PLSVO_E_INVALID, "seeds_keyframe_detect: null segment array");
+    if (!cand_idx_ok(I.seg_level, (size_t)I.n_seg, 0, c->pyr.n_levels)) return fail(c, PLSVO_E_INVALID, "seeds_keyframe_detect: feature level outside the configured pyramid");
+    for (int k = 0; k < I.n_seg; ++k) max_level = std::max(max_level, (int)I.seg_level[k]);
+    ts += (size_t)I.n_seg; sources |= I.occ_sources;
+  }
+  if ((sources & PLSVO_SEED_OCC_SELECTED) && !c->cs_selected) return fail(c, PLSVO_E_STATE, "seeds_keyframe_detect: PLSVO_SEED_OCC_SELECTED without a selection (plsvo_candidates_select)");
+  if ((sources & PLSVO_SEED_OCC_UPDATED) && !c->sd_have_report) return fail(c, PLSVO_E_STATE, "seeds_keyframe_detect: PLSVO_SEED_OCC_UPDATED without a fetched update (plsvo_seeds_update_fetch)");
+  for (int s = 0; s < n; ++s)                       // the segments' room, from the mirrored list lengths
+    if (in[s].active && (long long)c->sd_host[(size_t)s].n_seg + in[s].n_seg > c->sd_lim[2 * (size_t)s + 1])
+      return fail(c, PLSVO_E_CAPACITY, "seeds_keyframe_detect: a stream's line-seed list lacks rows (plsvo_seeds_reserve); nothing was changed");
+  if (ts > (size_t)INT32_MAX) return fail(c, PLSVO_E_CAPACITY, "seeds_keyframe_detect: batch too large");
+  if (n_act == 0) return PLSVO_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t A = (size_t)n_act;
+  Blob blob;
+  const size_t b_jobs = blob.reserve<SeedStartJobDev>(A);
+  const size_t s_px = blob.reserve<double>(ts * 2), s_f = blob.reserve<double>(ts * 3), s_sf = blob.reserve<double>(ts * 3), s_ef = blob.reserve<double>(ts * 3),
+               s_spx = blob.reserve<double>(ts * 2), s_epx = blob.reserve<double>(ts * 2), s_lv = blob.reserve<int>(ts);
+  auto put = [&](size_t sec, size_t at, const void* src, size_t count, size_t elem) { if (count && src) memcpy(blob.host.data() + sec + at * elem, src, count * elem); };
+  size_t as = 0;
+  int pos = 0;
+  for (int s = 0; s < n; ++s) {
+    const plsvo_seed_kf_detect& I = in[s];
+    if (!I.active) continue;
+    SeedStartJobDev& J = blob.at<SeedStartJobDev>(b_jobs)[pos++];
+    memset(&J, 0, sizeof(J));
+    J.stream = s; J.removed_kf = I.removed_kf; J.new_batch = I.new_batch ? 1 : 0; J.new_kf = I.new_kf; J.occ_sources = I.occ_sources; J.n_seg = I.n_seg;
+    J.lim_pt = c->sd_lim[2 * (size_t)s]; J.seg_at = (long long)as; J.d_occ = I.d_occupancy;
+    if (I.occ_sources & PLSVO_SEED_OCC_UPDATED) for (int k = 0; k < 6; ++k) J.n_upd_rows += c->sd_last[(size_t)s].pt[k];
+    {                                               // PointSeed::PointSeed / LineSeed::LineSeed (:53-74): float arguments, float members
+      const float depth_mean = (float)I.depth_mean, depth_min = (float)I.depth_min;
+      const float mu = 1.0 / depth_mean, z_range = 1.0 / depth_min;
+      const float sigma2 = z_range * z_range / 36;
+      J.mu = mu; J.z_range = z_range; J.sigma2 = sigma2;
+    }
+    const size_t ns = (size_t)I.n_seg;
+    put(s_px, as * 2, I.seg_px, ns * 2, 8); put(s_f, as * 3, I.seg_f, ns * 3, 8); put(s_sf, as * 3, I.seg_sf, ns * 3, 8); put(s_ef, as * 3, I.seg_ef, ns * 3, 8);
+    put(s_spx, as * 2, I.seg_spx, ns * 2, 8); put(s_epx, as * 2, I.seg_epx, ns * 2, 8); put(s_lv, as, I.seg_level, ns, 4);
+    as += ns;
+  }
+  if (const int rc = upload_blob(c, c->sd_d_in, blob)) return rc;
+  HIP_TRY(c, c->sk_d_occ.ensure(A * (size_t)cells));
+  HIP_TRY(c, c->sk_d_slots.ensure(A * sizeof(int)));
+  const char* d = reinterpret_cast<const char*>(c->sd_d_in.p);
+  auto D = [&](size_t o) { return reinterpret_cast<const double*>(d + o); };
+  SeedStartBatchDev b{};
+  b.l = c->sd_b;
+  b.l.k_seg_px = D(s_px); b.l.k_seg_f = D(s_f); b.l.k_seg_sf = D(s_sf); b.l.k_seg_ef = D(s_ef); b.l.k_seg_spx = D(s_spx); b.l.k_seg_epx = D(s_epx);
+  b.l.k_seg_level = reinterpret_cast<const int*>(d + s_lv);
+  b.jobs = reinterpret_cast<const SeedStartJobDev*>(d + b_jobs); b.n_act = n_act;
+  b.cell = p->cell_size; b.cols = cols; b.n_cells = cells; b.width = c->pyr.w[0]; b.height = c->pyr.h[0];
+  b.f_pt_px = c->cs_b.f_pt_px; b.scalars = c->cs_b.scalars;   // (read under PLSVO_SEED_OCC_SELECTED only)
+  b.occ = c->sk_d_occ.as<uint8_t>(); b.slots = c->sk_d_slots.as<int>(); b.report = c->sk_d_report.as<SeedStartReportDev>();
+  {
+    EventPair ep{}; prof_begin(c, PLSVO_K_NEWCAND, &ep);
+    // the occupancy rows are re-armed ahead of every launch, as the tail split re-arms its flags: the kernel only ever stores a 1
+    hipError_t launched = hipMemsetAsync(b.occ, 0, A * (size_t)cells, c->stream);
+    if (launched == hipSuccess) launched = launch_seeds_occupancy(b, c->stream);
+    int rc = PLSVO_OK;
+    if (launched == hipSuccess) {
+      rc = detect_enqueue_keys(c, 0, b.slots, n_act, p, cells, cols, b.occ);
+      b.keys = c->det_keys.as<unsigned long long>();
+      if (rc == PLSVO_OK) {
+        launched = launch_seeds_start(b, c->stream);
+        // the start launch is what re-arms the keys: if it could not be enqueued behind the detection, a memset arms them in its place
+        if (launched != hipSuccess) (void)hipMemsetAsync(b.keys, 0, A * (size_t)cells * sizeof(unsigned long long), c->stream);
+      }
+    }
+    prof_end(c, PLSVO_K_NEWCAND, &ep);
+    if (rc) return rc;
+    HIP_TRY(c, launched);
+  }
+  for (int s = 0; s < n; ++s) {                     // upper bounds until a fetch: the device alone knows the corners, and with no_room it appends no segment either
+    if (!in[s].active) continue;
+    SeedStreamDev& S = c->sd_host[(size_t)s];
+    S.n_pt = (int)std::min((long long)S.n_pt + cells, (long long)c->sd_lim[2 * (size_t)s]); S.n_seg += in[s].n_seg; S.batch_counter += in[s].new_batch ? 1 : 0;
+  }
+  c->sd_max_level = max_level;
+  c->sk_have_report = true;
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_seeds_keyframe_fetch(plsvo_ctx* c, int n, plsvo_seed_kf_report* out) {
+  CTX_CHECK(c);
+  if (const int rc = seeds_ready(c, n, out, "seeds_keyframe_fetch")) return rc;
+  if (!c->sk_have_report) return fail(c, PLSVO_E_STATE, "seeds_keyframe_fetch: no plsvo_seeds_keyframe_detect since the seed tables were staged");
+  static_assert(sizeof(SeedStartReportDev) == sizeof(plsvo_seed_kf_report) && sizeof(plsvo_seed_kf_report) == 32, "the device's report is the public one");
+  if (n == 0) return PLSVO_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  std::vector<SeedStreamDev> streams((size_t)n);
+  HIP_TRY(c, hipMemcpyAsync(out, c->sk_d_report.p, (size_t)n * sizeof(plsvo_seed_kf_report), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(streams.data(), c->sd_b.streams, (size_t)n * sizeof(SeedStreamDev), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (int s = 0; s < n; ++s) {                     // the mirrors are exact again, as behind plsvo_seeds_fetch_lists
+    SeedStreamDev& S = c->sd_host[(size_t)s];
+    S.n_pt = streams[(size_t)s].n_pt; S.n_seg = streams[(size_t)s].n_seg; S.batch_counter = streams[(size_t)s].batch_counter;
+  }
   return PLSVO_OK;
 }
 

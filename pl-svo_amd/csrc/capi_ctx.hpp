@@ -36,6 +36,8 @@ hipError_t launch_map_add_candidates(const NewCandBatchDev& b, hipStream_t strea
 hipError_t launch_update_seeds_resident(const SeedListBatchDev& b, hipStream_t stream);   // seedlist_device.hpp, in seeds_kernels.hip
 hipError_t launch_seeds_commit(const SeedListBatchDev& b, hipStream_t stream);
 hipError_t launch_seeds_keyframe(const SeedListBatchDev& b, hipStream_t stream);
+hipError_t launch_seeds_occupancy(const SeedStartBatchDev& b, hipStream_t stream);
+hipError_t launch_seeds_start(const SeedStartBatchDev& b, hipStream_t stream);
 hipError_t launch_halfsample(const uint8_t* src, size_t src_pitch, int in_w, int in_h, int in_stride, uint8_t* dst,
                              size_t dst_pitch, int n_slots, int rounding, hipStream_t stream);
 hipError_t launch_copy_level0(const uint8_t* src, size_t src_pitch, int w, int h, int stride, uint8_t* dst, size_t dst_pitch,
@@ -267,6 +269,10 @@ struct plsvo_ctx {
   size_t sd_tab_bytes = 0, sd_t_pt = 0, sd_t_seg = 0;
   DevBuf sd_d_tab, sd_d_work, sd_d_in;
   SeedListBatchDev sd_b{};
+  // seeds started from a keyframe's corners (plsvo_seeds_keyframe_detect): the occupancy rows and the slot table of the active streams
+  // (sk_d_occ, sk_d_slots: per position of the launch), the reports (sk_d_report: per stream, zeroed at plsvo_seeds_stage)
+  bool sk_have_report = false;
+  DevBuf sk_d_occ, sk_d_slots, sk_d_report;
   unsigned long long run_seq = 0, a_run_seq = 0, p_run_seq = 0, ch_run_seq = 0;   // which resident batch ran last, 0 = not since it was staged (plsvo_pack_pose_records)
   unsigned long long ch_stage_seq = 0;      // when the frame step was staged, on the same count: a pose-optimisation batch that ran later describes the streams now
 
@@ -317,4 +323,10 @@ PLSVO_LOCAL void prof_end(plsvo_ctx* c, int k, EventPair* ep);
 PLSVO_LOCAL int download_ranges(plsvo_ctx* c, int n_ranges, const void* const* src, const size_t* bytes, std::vector<uint8_t>& fallback, const uint8_t** h);
 PLSVO_LOCAL int upload_blob(plsvo_ctx* c, DevBuf& buf, const Blob& blob);
 PLSVO_LOCAL int pose_opt_threads(const plsvo_ctx* c, int n, long feats);
+// corner detection, shared by plsvo_hip_detect_fast(_dev) and plsvo_seeds_keyframe_detect (defined in plsvo_capi.hip).  detect_check_params:
+// everything the detect entry points refuse in their params, for n launch positions; the pyramids are configured and p is not NULL.
+// detect_enqueue_keys: the detection launch alone -- position i reads slot first_slot + i, or d_slot_table[i] when a table is given --
+// into the context's armed key rows
+PLSVO_LOCAL int detect_check_params(plsvo_ctx* c, int n, const plsvo_detect_params* p, const char* what, int* cols, int* rows);
+PLSVO_LOCAL int detect_enqueue_keys(plsvo_ctx* c, int first_slot, const int* d_slot_table, int n, const plsvo_detect_params* p, int cells, int cols, const uint8_t* d_occ);
 PLSVO_LOCAL void pose_state_to_out(const PoseStateDev& s, plsvo_poseopt_out& o);   // everything but the keep masks, whose two pointers it leaves as they are

@@ -8,6 +8,7 @@
 //                          lane each, the survivors of the 3 x 3 suppression are listed and get their Shi-Tomasi score one lane each;
 //                          candidates are reduced per cell in LDS, then one global atomic per touched cell
 //   detect_compact_kernel  one workgroup = one slot: cell keys -> plsvo_corner records in cell order + count, keys re-armed
+//                          (seeds_start_kernel, seedlist_device.hpp, reads the keys in its place: seed rows instead of records)
 //
 // A candidate is a 64-bit key: high word = the bits of its (positive) Shi-Tomasi score, low word = ~((L << 26) | (y << 13) | x) in
 // level-L pixels.  max over the keys of a cell = "strictly greater score wins, the earlier one in (level, y, x) order wins a tie":
@@ -91,7 +92,10 @@ __device__ __forceinline__ float det_shi_tomasi(const uint8_t* img, int c) {
 }
 
 // grid: (tiles of all levels of one slot, n_slots).  kStages: write the score and survivor maps of the (single) level instead of keys.
-template <bool kStages>
+// kTable: the slot of launch position blockIdx.y comes from a.slot_table (plsvo_seeds_keyframe_detect: the streams' keyframes sit in any
+// slots).  An instantiation of its own: with the table as a run-time branch in the one kernel, plsvo_hip_detect_fast_dev measured 0.8 - 1.2 %
+// slower than the parent on 4096 slots, outside the parent's run-to-run range; without the table the code is the parent's.
+template <bool kStages, bool kTable = false>
 __global__ __launch_bounds__(kDetThreads) void detect_fast_kernel(DetectLaunch a) {
   __shared__ __align__(16) uint8_t s_img[kDetImgW * kDetImgH + 16];
   __shared__ __align__(16) uint8_t s_score[kDetScoreW * kDetScoreH];
@@ -106,7 +110,8 @@ __global__ __launch_bounds__(kDetThreads) void detect_fast_kernel(DetectLaunch a
   const int tile = (int)blockIdx.x - a.tile_begin[e];
   const int ty = tile / a.tiles_x[e], tx = tile - ty * a.tiles_x[e];
   const int x0 = tx * kDetTileW, y0 = ty * kDetTileH;
-  const uint8_t* lvl = a.pyr + (size_t)blockIdx.y * a.slot_bytes + a.off[e];   // 256-byte aligned, W * H bytes + >= 64 of slack
+  const size_t slot = kTable ? (size_t)a.slot_table[blockIdx.y] : (size_t)blockIdx.y;
+  const uint8_t* lvl = a.pyr + slot * a.slot_bytes + a.off[e];   // 256-byte aligned, W * H bytes + >= 64 of slack
 
   // ---- stage the tile + halo: dword loads of the row-major level.  Row r of the LDS image starts at level byte (y0 - 5 + r) * W + x0 - 8,
   // which is dword-aligned only when W is a multiple of 4: otherwise two dwords are merged.  Bytes left or right of the image row belong

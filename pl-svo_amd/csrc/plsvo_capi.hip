@@ -119,7 +119,7 @@ extern "C" void plsvo_hip_destroy(plsvo_ctx* c) {
                      &c->ch_d_po, &c->rec_d }) b->release();
   c->p_w.release(); c->ch_w.release(); c->cs_w.release();
   for (auto& r : c->rect) r.map.release();
-  c->det_keys.release(); c->det_occ.release(); c->det_corners.release(); c->det_counts.release(); c->det_stage.release();
+  c->det_keys.release(); c->det_occ.release(); c->det_corners.release(); c->det_counts.release(); c->det_stage.release(); c->sk_d_occ.release(); c->sk_d_slots.release(); c->sk_d_report.release();
   for (int k = 0; k < 2; ++k) { if (c->pinned[k]) (void)hipHostFree(c->pinned[k]); if (c->pinned_done[k]) (void)hipEventDestroy(c->pinned_done[k]); }
   for (int k = 0; k < 2; ++k) { if (c->pyr_pinned[k]) (void)hipHostFree(c->pyr_pinned[k]); if (c->pyr_pinned_done[k]) (void)hipEventDestroy(c->pyr_pinned_done[k]); }
   if (c->dl_pinned) (void)hipHostFree(c->dl_pinned);
@@ -568,12 +568,8 @@ static void detect_fill_levels(const plsvo_ctx* c, int level_lo, int level_hi, D
   }
 }
 
-// checks shared by the detect entry points: nothing has been enqueued or written when one fails
-static int detect_check(plsvo_ctx* c, int first_slot, int n, const plsvo_detect_params* p, const void* corners, const void* counts, const char* what,
-                        int* cols, int* rows) {
-  if (!c->pyr.base) return fail(c, PLSVO_E_STATE, std::string(what) + ": pyramids not configured");
-  if (!p || !corners || !counts) return fail(c, PLSVO_E_INVALID, std::string(what) + ": NULL params, corners or counts");
-  if (n <= 0 || first_slot < 0 || first_slot > c->pyr.n_slots - n) return fail(c, PLSVO_E_INVALID, std::string(what) + ": slot range out of bounds");
+// checks shared by the detect entry points (and plsvo_seeds_keyframe_detect, capi_candidates.hip): nothing has been enqueued or written when one fails
+int detect_check_params(plsvo_ctx* c, int n, const plsvo_detect_params* p, const char* what, int* cols, int* rows) {
   if (p->n_levels < 1 || p->n_levels > c->pyr.n_levels) return fail(c, PLSVO_E_INVALID, std::string(what) + ": n_levels outside the configured pyramid");
   if (p->cell_size < 1) return fail(c, PLSVO_E_INVALID, std::string(what) + ": cell_size < 1");
   if (c->pyr.w[0] > 8191 || c->pyr.h[0] > 8191) return fail(c, PLSVO_E_INVALID, std::string(what) + ": image wider or higher than 8191 (13 bits per coordinate of a cell key)");
@@ -581,15 +577,22 @@ static int detect_check(plsvo_ctx* c, int first_slot, int n, const plsvo_detect_
   if (p->fast_threshold < 1 || p->fast_threshold > 254) return fail(c, PLSVO_E_INVALID, std::string(what) + ": fast_threshold outside 1..254");
   const double t = p->detection_threshold;
   if (!std::isfinite(t) || t < 0.0 || (double)(float)t != t) return fail(c, PLSVO_E_INVALID, std::string(what) + ": detection_threshold negative, not finite or not a float");
-  if (plsvo_detect_grid(c->pyr.w[0], c->pyr.h[0], p->cell_size, cols, rows) != PLSVO_OK || (long long)*cols * *rows * n > INT32_MAX)
+  if (plsvo_detect_grid(c->pyr.w[0], c->pyr.h[0], p->cell_size, cols, rows) != PLSVO_OK || (long long)*cols * *rows * std::max(n, 1) > INT32_MAX)
     return fail(c, PLSVO_E_INVALID, std::string(what) + ": grid too large");
   return PLSVO_OK;
 }
 
-static int detect_enqueue(plsvo_ctx* c, int first_slot, int n, const plsvo_detect_params* p, int cells, int cols, const uint8_t* d_occ,
-                          plsvo_corner* d_corners, int32_t* d_counts) {
+static int detect_check(plsvo_ctx* c, int first_slot, int n, const plsvo_detect_params* p, const void* corners, const void* counts, const char* what,
+                        int* cols, int* rows) {
+  if (!c->pyr.base) return fail(c, PLSVO_E_STATE, std::string(what) + ": pyramids not configured");
+  if (!p || !corners || !counts) return fail(c, PLSVO_E_INVALID, std::string(what) + ": NULL params, corners or counts");
+  if (n <= 0 || first_slot < 0 || first_slot > c->pyr.n_slots - n) return fail(c, PLSVO_E_INVALID, std::string(what) + ": slot range out of bounds");
+  return detect_check_params(c, n, p, what, cols, rows);
+}
+
+int detect_enqueue_keys(plsvo_ctx* c, int first_slot, const int* d_slot_table, int n, const plsvo_detect_params* p, int cells, int cols, const uint8_t* d_occ) {
   const size_t key_bytes = (size_t)n * cells * sizeof(unsigned long long);
-  if (key_bytes > c->det_keys.cap) {   // a new buffer starts armed; every compaction leaves it armed
+  if (key_bytes > c->det_keys.cap) {   // a new buffer starts armed; every compaction (and every seed start) leaves it armed
     HIP_TRY(c, c->det_keys.ensure(key_bytes));
     HIP_TRY(c, hipMemsetAsync(c->det_keys.p, 0, c->det_keys.cap, c->stream));
   }
@@ -599,9 +602,15 @@ static int detect_enqueue(plsvo_ctx* c, int first_slot, int n, const plsvo_detec
   detect_fill_levels(c, 0, p->n_levels - 1, &a);
   a.fast_b = p->fast_threshold; a.thr = (float)p->detection_threshold;
   a.cell = p->cell_size; a.cols = cols; a.n_cells = cells;
-  a.occupancy = d_occ; a.keys = c->det_keys.as<unsigned long long>();
+  a.occupancy = d_occ; a.keys = c->det_keys.as<unsigned long long>(); a.slot_table = d_slot_table;
   HIP_TRY(c, launch_detect_fast(a, n, c->stream));
-  HIP_TRY(c, launch_detect_compact(a.keys, cells, d_corners, d_counts, n, c->stream));
+  return PLSVO_OK;
+}
+
+static int detect_enqueue(plsvo_ctx* c, int first_slot, int n, const plsvo_detect_params* p, int cells, int cols, const uint8_t* d_occ,
+                          plsvo_corner* d_corners, int32_t* d_counts) {
+  if (const int rc = detect_enqueue_keys(c, first_slot, nullptr, n, p, cells, cols, d_occ)) return rc;
+  HIP_TRY(c, launch_detect_compact(c->det_keys.as<unsigned long long>(), cells, d_corners, d_counts, n, c->stream));
   return PLSVO_OK;
 }
 

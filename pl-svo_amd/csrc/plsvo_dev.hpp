@@ -430,7 +430,7 @@ constexpr int kDetCellCap = 128;                       // cells of one tile redu
 constexpr int kDetThreads = 256;
 
 struct DetectLaunch {
-  const uint8_t* pyr;                 // first slot of the call
+  const uint8_t* pyr;                 // first slot of the call (slot 0 with a slot table)
   unsigned long long slot_bytes;
   int n_lv;                           // levels of this launch; entry i is pyramid level level[i]
   int level[PLSVO_MAX_LEVELS], w[PLSVO_MAX_LEVELS], h[PLSVO_MAX_LEVELS], tiles_x[PLSVO_MAX_LEVELS];
@@ -443,6 +443,7 @@ struct DetectLaunch {
   unsigned long long* keys;           // n_cells per slot
   uint8_t* stage_score;               // detect_stages only: W_L * H_L each (one slot, one level)
   uint8_t* stage_survives;
+  const int* slot_table;              // detect_fast_kernel<false, true> only: position i of the launch reads slot slot_table[i], not slot i; occupancy and keys stay rows of the POSITION
 };
 
 // depth-filter seed lists resident on the device (seedlist_device.hpp, include/plsvo_hip.h plsvo_seeds_*): flat SoA rows for the whole
@@ -482,6 +483,31 @@ struct SeedListBatchDev {
   const SeedKfJobDev* kf_jobs;
   const double* k_pt_px; const double* k_pt_f; const int* k_pt_level; const uint8_t* k_pt_type; const double* k_pt_grad;
   const double* k_seg_px; const double* k_seg_f; const double* k_seg_sf; const double* k_seg_ef; const double* k_seg_spx; const double* k_seg_epx; const int* k_seg_level;
+};
+
+// a keyframe's point seeds started from its FAST corners (seedlist_device.hpp, include/plsvo_hip.h plsvo_seeds_keyframe_detect): one
+// wave per ACTIVE stream in both launches; position p of the launches serves stream jobs[p].stream, and the occupancy row, the key
+// row and the slot table entry of the detection between them are rows of the position
+struct SeedStartJobDev {
+  int stream, removed_kf, new_batch, new_kf, occ_sources, n_seg;
+  int n_upd_rows;                   // shadow rows of the last fetched update (OCC_UPDATED)
+  int lim_pt;                       // point rows the stream was laid out with
+  float mu, z_range, sigma2, reserved0;   // the constructor's values, as SeedKfJobDev's
+  long long seg_at;                 // the stream's line seeds in the uploaded arrays
+  const uint8_t* d_occ;             // the caller's occupancy bytes, or null
+};
+struct SeedStartReportDev {         // plsvo_seed_kf_report, field for field
+  int n_new_pt, n_new_seg, n_pt_seeds, n_seg_seeds, batch_counter, no_room, n_occupied, reserved0;
+};
+struct SeedStartBatchDev {
+  SeedListBatchDev l;               // the rows, the streams' records, the uploaded line seeds (k_seg_*)
+  const SeedStartJobDev* jobs; int n_act;
+  int cell, cols, n_cells, width, height;
+  const double* f_pt_px; const int* scalars;   // the last selection's features (SelectBatchDev), rows from the stream's opt_off
+  uint8_t* occ;                     // n_cells per position, zero before the occupancy launch
+  int* slots;                       // the detection's slot table, written by the occupancy launch
+  unsigned long long* keys;         // n_cells per position: read, and re-armed, by the start launch
+  SeedStartReportDev* report;       // per STREAM
 };
 
 inline int detect_tiles(int w, int h, int* tiles_x) {

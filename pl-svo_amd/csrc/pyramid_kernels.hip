@@ -164,7 +164,8 @@ hipError_t launch_rectify(const uint8_t* raw, size_t raw_pitch, int stride, int 
 hipError_t launch_detect_fast(const DetectLaunch& a, int n_slots, hipStream_t stream) {
   const int tiles = a.tile_begin[a.n_lv];
   if (tiles <= 0 || n_slots <= 0) return hipSuccess;
-  hipLaunchKernelGGL(detect_fast_kernel<false>, dim3(tiles, n_slots), dim3(kDetThreads), 0, stream, a);
+  if (a.slot_table) hipLaunchKernelGGL((detect_fast_kernel<false, true>), dim3(tiles, n_slots), dim3(kDetThreads), 0, stream, a);
+  else hipLaunchKernelGGL(detect_fast_kernel<false>, dim3(tiles, n_slots), dim3(kDetThreads), 0, stream, a);
   return hipGetLastError();
 }
 

@@ -5,6 +5,7 @@
 //                            (src/depth_filter.cpp:289-292 age, :334-360 / :439-467 converged and NaN seeds erased, the converged ones
 //                            handed to newCandidatePoint / newCandidateSegment, src/map.cpp:285-290, :377-382)
 //   seeds_keyframe_kernel    DepthFilter::initializeSeeds (:177-191) and removeKeyframe (:199-216)
+//   seeds_occupancy_kernel, seeds_start_kernel    initializeSeeds' creating half (:151-191) from the detector's cell keys (below)
 //
 // One WAVE per stream, four per workgroup, no LDS, no atomics, nothing synchronised across waves.  A list is compacted in place, stably,
 // in rounds of 64 rows: every lane loads its row (and its shadow row) into registers, a ballot gives it its rank among the rows that
@@ -189,6 +190,51 @@ __global__ __launch_bounds__(64 * kSeedWaves) void seeds_commit_kernel(const See
   }
 }
 
+// removeKeyframe (:199-216) on one stream's lists, by its wave: the removed keyframe's seeds go, later keyframes move down one row in the
+// table.  n_sp / n_ss: the live rows, in and out
+__device__ __forceinline__ void seed_remove_keyframe(const SeedListBatchDev& b, const SeedStreamDev& S, int removed_kf, int lane, int& n_sp, int& n_ss) {
+  int kept = 0;
+  for (int base = 0; base < n_sp; base += 64) {
+    const int j = base + lane;
+    PtSeedRow Q; Q.ref_kf = removed_kf;
+    if (j < n_sp) Q = pt_seed_load(b, S.pt_off + j);
+    const bool stays = j < n_sp && Q.ref_kf != removed_kf;
+    const unsigned long long mk = __ballot(stays);
+    if (Q.ref_kf > removed_kf) --Q.ref_kf;
+    if (stays) pt_seed_store(b, S.pt_off + kept + seed_rank(mk, lane), Q);
+    kept += __popcll(mk);
+  }
+  n_sp = kept; kept = 0;
+  for (int base = 0; base < n_ss; base += 64) {
+    const int j = base + lane;
+    SegSeedRow Q; Q.ref_kf = removed_kf;
+    if (j < n_ss) Q = seg_seed_load(b, S.seg_off + j);
+    const bool stays = j < n_ss && Q.ref_kf != removed_kf;
+    const unsigned long long mk = __ballot(stays);
+    if (Q.ref_kf > removed_kf) --Q.ref_kf;
+    if (stays) seg_seed_store(b, S.seg_off + kept + seed_rank(mk, lane), Q);
+    kept += __popcll(mk);
+  }
+  n_ss = kept;
+}
+
+// initializeSeeds' line seeds (:187-190): n uploaded segments from row `at` of the k_seg_* arrays, behind the n_ss live rows
+__device__ __forceinline__ void seed_append_segments(const SeedListBatchDev& b, const SeedStreamDev& S, int lane, int n_ss, int n, long long at, int new_kf, int counter,
+                                                     float mu, float z_range, float sigma2) {
+  const SeedsBatchDev& s = b.s;
+  for (int base = 0; base < n; base += 64) {
+    const int j = base + lane;
+    if (j >= n) continue;
+    const long long src = at + j, r = S.seg_off + n_ss + j;
+    seed_mut(s.seg_ref_frame)[r] = new_kf; b.seg_batch_id[r] = counter; seed_mut(s.seg_level)[r] = b.k_seg_level[src];
+    new_copy2(seed_mut(s.seg_px) + 2 * r, b.k_seg_px + 2 * src); new_copy3(seed_mut(s.seg_f) + 3 * r, b.k_seg_f + 3 * src);
+    new_copy3(seed_mut(s.seg_sf) + 3 * r, b.k_seg_sf + 3 * src); new_copy3(seed_mut(s.seg_ef) + 3 * r, b.k_seg_ef + 3 * src);
+    new_copy2(b.seg_spx + 2 * r, b.k_seg_spx + 2 * src); new_copy2(b.seg_epx + 2 * r, b.k_seg_epx + 2 * src);
+    seed_mut(s.seg_a)[r] = 10.0f; seed_mut(s.seg_b)[r] = 10.0f; seed_mut(s.seg_mu_s)[r] = mu; seed_mut(s.seg_mu_e)[r] = mu;
+    seed_mut(s.seg_z_range_s)[r] = z_range; seed_mut(s.seg_z_range_e)[r] = z_range; seed_mut(s.seg_sigma2_s)[r] = sigma2; seed_mut(s.seg_sigma2_e)[r] = sigma2;
+  }
+}
+
 __global__ __launch_bounds__(64 * kSeedWaves) void seeds_keyframe_kernel(const SeedListBatchDev b) {
   const int lane = threadIdx.x & 63;
   const int job = blockIdx.x * kSeedWaves + (int)(threadIdx.x >> 6);
@@ -200,32 +246,7 @@ __global__ __launch_bounds__(64 * kSeedWaves) void seeds_keyframe_kernel(const S
   const int counter = S.batch_counter + (J.new_batch ? 1 : 0);
   const SeedsBatchDev& s = b.s;
 
-  // -- removeKeyframe: the removed keyframe's seeds go, later keyframes move down one row in the table
-  if (J.removed_kf >= 0) {
-    int kept = 0;
-    for (int base = 0; base < n_sp; base += 64) {
-      const int j = base + lane;
-      PtSeedRow Q; Q.ref_kf = J.removed_kf;
-      if (j < n_sp) Q = pt_seed_load(b, S.pt_off + j);
-      const bool stays = j < n_sp && Q.ref_kf != J.removed_kf;
-      const unsigned long long mk = __ballot(stays);
-      if (Q.ref_kf > J.removed_kf) --Q.ref_kf;
-      if (stays) pt_seed_store(b, S.pt_off + kept + seed_rank(mk, lane), Q);
-      kept += __popcll(mk);
-    }
-    n_sp = kept; kept = 0;
-    for (int base = 0; base < n_ss; base += 64) {
-      const int j = base + lane;
-      SegSeedRow Q; Q.ref_kf = J.removed_kf;
-      if (j < n_ss) Q = seg_seed_load(b, S.seg_off + j);
-      const bool stays = j < n_ss && Q.ref_kf != J.removed_kf;
-      const unsigned long long mk = __ballot(stays);
-      if (Q.ref_kf > J.removed_kf) --Q.ref_kf;
-      if (stays) seg_seed_store(b, S.seg_off + kept + seed_rank(mk, lane), Q);
-      kept += __popcll(mk);
-    }
-    n_ss = kept;
-  }
+  if (J.removed_kf >= 0) seed_remove_keyframe(b, S, J.removed_kf, lane, n_sp, n_ss);
 
   // -- initializeSeeds: the new seeds behind the live rows, in the uploaded order (the host has checked the room)
   for (int base = 0; base < J.n_pt; base += 64) {
@@ -237,18 +258,118 @@ __global__ __launch_bounds__(64 * kSeedWaves) void seeds_keyframe_kernel(const S
     new_copy2(seed_mut(s.pt_grad) + 2 * r, b.k_pt_grad + 2 * src);
     seed_mut(s.pt_a)[r] = 10.0f; seed_mut(s.pt_b)[r] = 10.0f; seed_mut(s.pt_mu)[r] = J.mu; seed_mut(s.pt_z_range)[r] = J.z_range; seed_mut(s.pt_sigma2)[r] = J.sigma2;
   }
-  for (int base = 0; base < J.n_seg; base += 64) {
-    const int j = base + lane;
-    if (j >= J.n_seg) continue;
-    const long long src = J.seg_at + j, r = S.seg_off + n_ss + j;
-    seed_mut(s.seg_ref_frame)[r] = J.new_kf; b.seg_batch_id[r] = counter; seed_mut(s.seg_level)[r] = b.k_seg_level[src];
-    new_copy2(seed_mut(s.seg_px) + 2 * r, b.k_seg_px + 2 * src); new_copy3(seed_mut(s.seg_f) + 3 * r, b.k_seg_f + 3 * src);
-    new_copy3(seed_mut(s.seg_sf) + 3 * r, b.k_seg_sf + 3 * src); new_copy3(seed_mut(s.seg_ef) + 3 * r, b.k_seg_ef + 3 * src);
-    new_copy2(b.seg_spx + 2 * r, b.k_seg_spx + 2 * src); new_copy2(b.seg_epx + 2 * r, b.k_seg_epx + 2 * src);
-    seed_mut(s.seg_a)[r] = 10.0f; seed_mut(s.seg_b)[r] = 10.0f; seed_mut(s.seg_mu_s)[r] = J.mu; seed_mut(s.seg_mu_e)[r] = J.mu;
-    seed_mut(s.seg_z_range_s)[r] = J.z_range; seed_mut(s.seg_z_range_e)[r] = J.z_range; seed_mut(s.seg_sigma2_s)[r] = J.sigma2; seed_mut(s.seg_sigma2_e)[r] = J.sigma2;
-  }
+  seed_append_segments(b, S, lane, n_ss, J.n_seg, J.seg_at, J.new_kf, counter, J.mu, J.z_range, J.sigma2);
   if (lane == 0) { S.n_pt = n_sp + J.n_pt; S.n_seg = n_ss + J.n_seg; S.batch_counter = counter; }
 }
+
+// ---- a keyframe's point seeds from its FAST corners: DepthFilter::initializeSeeds' first half (:151-191) ----
+//   seeds_occupancy_kernel   the detector's grid of every active stream: the caller's bytes, FastDetector::setExistingFeatures of the
+//                            features the last selection wrote (:161), setGridOccpuancy of the last update's matches (:327-331); and
+//                            the detection's slot table entry, from the stream's resident frame_slot row
+//   seeds_start_kernel       removeKeyframe, then one PointSeed per cell key the detection left (src/feature_detection.cpp:95-101 and
+//                            PointFeat's constructor, src/depth_filter.cpp:184-186), then the uploaded line seeds; re-arms the keys
+// One wave per ACTIVE stream in both.  The occupancy rows are zeroed by a memset ahead of the launch: the kernel only ever stores a 1,
+// so lanes that mark the same cell store the same byte and no order among them matters.
+
+// the cell of a level-0 position, plsvo_detect_cell's rule; -1 for a position that is not finite, negative or outside the image (pin)
+__device__ __forceinline__ int seed_cell_of(const SeedStartBatchDev& b, double px, double py) {
+  if (!(px >= 0.0 && px < (double)b.width && py >= 0.0 && py < (double)b.height)) return -1;   // (a NaN fails every comparison)
+  return (int)(py / (double)b.cell) * b.cols + (int)(px / (double)b.cell);
+}
+
+__global__ __launch_bounds__(64 * kSeedWaves) void seeds_occupancy_kernel(const SeedStartBatchDev b) {
+  const int lane = threadIdx.x & 63;
+  const int pos = blockIdx.x * kSeedWaves + (int)(threadIdx.x >> 6);
+  if (pos >= b.n_act) return;
+  const SeedStartJobDev J = b.jobs[pos];
+  const SeedStreamDev& S = b.l.streams[J.stream];
+  const CandMapDev& M = b.l.m.c.maps[J.stream];
+  uint8_t* const occ = b.occ + (size_t)pos * (size_t)b.n_cells;
+  if (J.d_occ)
+    for (int i = lane; i < b.n_cells; i += 64) if (J.d_occ[i]) occ[i] = 1;
+  if (J.occ_sources & PLSVO_SEED_OCC_SELECTED) {
+    const int n = b.scalars[3 * J.stream];
+    for (int i = lane; i < n; i += 64) {
+      const long long o = M.opt_off + i;
+      const int k = seed_cell_of(b, b.f_pt_px[2 * o], b.f_pt_px[2 * o + 1]);
+      if (k >= 0) occ[k] = 1;
+    }
+  }
+  if (J.occ_sources & PLSVO_SEED_OCC_UPDATED)
+    for (int i = lane; i < J.n_upd_rows; i += 64) {
+      const long long r = S.pt_off + i;
+      const int st = b.l.s.o_pt_status[r];
+      if (st != PLSVO_SEED_UPDATED && st != PLSVO_SEED_CONVERGED && st != PLSVO_SEED_NAN) continue;
+      const int k = seed_cell_of(b, b.l.s.o_pt_px[2 * r], b.l.s.o_pt_px[2 * r + 1]);
+      if (k >= 0) occ[k] = 1;
+    }
+  if (lane == 0) b.slots[pos] = b.l.m.c.frame_slot[M.f_off + J.new_kf];
+}
+
+__global__ __launch_bounds__(64 * kSeedWaves) void seeds_start_kernel(const SeedStartBatchDev b) {
+  const int lane = threadIdx.x & 63;
+  const int pos = blockIdx.x * kSeedWaves + (int)(threadIdx.x >> 6);
+  if (pos >= b.n_act) return;
+  const SeedStartJobDev J = b.jobs[pos];
+  const SeedListBatchDev& l = b.l;
+  const SeedsBatchDev& s = l.s;
+  SeedStreamDev& S = l.streams[J.stream];
+  int n_sp = S.n_pt, n_ss = S.n_seg;
+  const int counter = S.batch_counter + (J.new_batch ? 1 : 0);
+
+  // -- 1. removeKeyframe
+  if (J.removed_kf >= 0) seed_remove_keyframe(l, S, J.removed_kf, lane, n_sp, n_ss);
+
+  // -- 2. the cells that hold a corner (and, for the report, the cells that were occupied)
+  unsigned long long* const keys = b.keys + (size_t)pos * (size_t)b.n_cells;
+  const uint8_t* const occ = b.occ + (size_t)pos * (size_t)b.n_cells;
+  int n_new = 0, n_occ = 0;
+  for (int base = 0; base < b.n_cells; base += 64) {
+    const int i = base + lane;
+    const bool in = i < b.n_cells;
+    n_new += __popcll(__ballot(in && keys[i] != 0ull));
+    n_occ += __popcll(__ballot(in && occ[i] != 0));
+  }
+
+  // -- 3. room for all of them or for none: the rows the stream was laid out with
+  const bool room = n_sp + n_new <= J.lim_pt;
+
+  // -- 4. one seed per key, in cell order, behind the live rows; every key that was read is armed again
+  int at = 0;
+  for (int base = 0; base < b.n_cells; base += 64) {
+    const int i = base + lane;
+    unsigned long long key = 0ull;
+    if (i < b.n_cells) { key = keys[i]; if (key) keys[i] = 0ull; }
+    const unsigned long long m = __ballot(key != 0ull);
+    if (key && room) {
+      const uint32_t p = ~(uint32_t)key;
+      const int L = (int)(p >> 26), y = (int)((p >> 13) & 8191u), x = (int)(p & 8191u);
+      const long long r = S.pt_off + n_sp + at + seed_rank(m, lane);
+      const double px[2] = { (double)(x << L), (double)(y << L) };
+      // cam2world of the seed tables' camera: sel_bearing's expressions (select_device.hpp), uncontracted
+      const double bx = (px[0] - s.cx) / s.fx, by = (px[1] - s.cy) / s.fy;
+      const double bn = sqrt((bx * bx + by * by) + 1.0);
+      const double f[3] = { bx / bn, by / bn, 1.0 / bn };
+      const double grad[2] = { 1.0, 0.0 };
+      seed_mut(s.pt_ref_frame)[r] = J.new_kf; l.pt_batch_id[r] = counter; seed_mut(s.pt_level)[r] = L; seed_mut(s.pt_type)[r] = PLSVO_FTR_CORNER;
+      seed_st2(seed_mut(s.pt_px) + 2 * r, px); new_copy3(seed_mut(s.pt_f) + 3 * r, f); seed_st2(seed_mut(s.pt_grad) + 2 * r, grad);
+      seed_mut(s.pt_a)[r] = 10.0f; seed_mut(s.pt_b)[r] = 10.0f; seed_mut(s.pt_mu)[r] = J.mu; seed_mut(s.pt_z_range)[r] = J.z_range; seed_mut(s.pt_sigma2)[r] = J.sigma2;
+    }
+    at += __popcll(m);
+  }
+
+  // -- 5. the uploaded line seeds
+  if (room) seed_append_segments(l, S, lane, n_ss, J.n_seg, J.seg_at, J.new_kf, counter, J.mu, J.z_range, J.sigma2);
+
+  // -- 6. the counts and the report, last
+  if (lane == 0) {
+    SeedStartReportDev R;
+    R.n_new_pt = room ? n_new : 0; R.n_new_seg = room ? J.n_seg : 0;
+    R.n_pt_seeds = n_sp + R.n_new_pt; R.n_seg_seeds = n_ss + R.n_new_seg; R.batch_counter = counter; R.no_room = room ? 0 : 1; R.n_occupied = n_occ; R.reserved0 = 0;
+    S.n_pt = R.n_pt_seeds; S.n_seg = R.n_seg_seeds; S.batch_counter = counter;
+    b.report[J.stream] = R;
+  }
+}
+
 
 }  // namespace plsvo_hip

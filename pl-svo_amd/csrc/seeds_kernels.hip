@@ -9,7 +9,8 @@
 //   DepthFilter::computeTau / updatePointSeed / updateLineSeed   src/depth_filter.cpp:568-584, :489-512, :514-566
 //   [ext] vk::patch_score::ZMSSD<4>, boost::math::pdf(normal_distribution<float>), warp::*, align2D (match_device.hpp)
 // plsvo_update_seeds maps seed state to seed state for lists kept on the host; plsvo_seeds_* keep the lists, their age test and the
-// converged-seed callbacks on the device (seedlist_device.hpp).  The detector's grid occupancy stays on the host.
+// converged-seed callbacks on the device (seedlist_device.hpp), and start a keyframe's point seeds there from the detector's cell keys,
+// the detector's grid occupancy included (plsvo_seeds_keyframe_detect).
 //
 // A seed is an independent problem: project its inverse-depth interval into the new frame, walk the epipolar segment
 // in 0.7-pixel steps scoring an 8x8 warped reference patch by zero-mean SSD (integer), refine the best position with
@@ -461,6 +462,17 @@ hipError_t launch_seeds_commit(const SeedListBatchDev& b, hipStream_t stream) {
 hipError_t launch_seeds_keyframe(const SeedListBatchDev& b, hipStream_t stream) {
   if (b.n_jobs <= 0) return hipSuccess;
   hipLaunchKernelGGL(seeds_keyframe_kernel, dim3((b.n_jobs + kSeedWaves - 1) / kSeedWaves), dim3(64 * kSeedWaves), 0, stream, b);
+  return hipGetLastError();
+}
+// a keyframe's point seeds from its corners: one wave per ACTIVE stream in both (the detection runs between them)
+hipError_t launch_seeds_occupancy(const SeedStartBatchDev& b, hipStream_t stream) {
+  if (b.n_act <= 0) return hipSuccess;
+  hipLaunchKernelGGL(seeds_occupancy_kernel, dim3((b.n_act + kSeedWaves - 1) / kSeedWaves), dim3(64 * kSeedWaves), 0, stream, b);
+  return hipGetLastError();
+}
+hipError_t launch_seeds_start(const SeedStartBatchDev& b, hipStream_t stream) {
+  if (b.n_act <= 0) return hipSuccess;
+  hipLaunchKernelGGL(seeds_start_kernel, dim3((b.n_act + kSeedWaves - 1) / kSeedWaves), dim3(64 * kSeedWaves), 0, stream, b);
   return hipGetLastError();
 }
 // keyframe stage (keyframe_device.hpp): one wave per stream, four streams per workgroup

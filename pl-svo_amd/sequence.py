@@ -182,13 +182,24 @@ class HipBackend:
         new seeds' arrays"""
         self.ctx.seeds_keyframe([event])
 
+    def seeds_keyframe_detect(self, cell_size=25, n_levels=3, detection_threshold=20.0, fast_threshold=20, **event):
+        """a keyframe event whose point seeds start on the device from the corners of the keyframe's own pyramid slot
+        (plsvo_seeds_keyframe_detect): removed_kf, new_batch, new_kf, depth_mean, depth_min, occ_sources (default: the
+        last selection's features and the last update's matches), d_occupancy and the line seeds' arrays.  Enqueue only.
+        -> nothing; seeds_keyframe_fetch() has the report"""
+        self.ctx.seeds_keyframe_detect([event], cell_size, n_levels, fast_threshold, detection_threshold)
+
+    def seeds_keyframe_fetch(self):
+        """what the last seeds_keyframe_detect did (plsvo_seeds_keyframe_fetch): capi.Context.seeds_keyframe_fetch's record"""
+        return self.ctx.seeds_keyframe_fetch()[0]
+
     def seeds_fetch_lists(self):
         """the resident seed lists as they stand (plsvo_seeds_fetch_lists)"""
         return self.ctx.seeds_fetch_lists()[0]
 
-    def detect_corners(self, slot, occupancy=None, cell_size=25, n_levels=3, detection_threshold=20.0):
+    def detect_corners(self, slot, occupancy=None, cell_size=25, n_levels=3, detection_threshold=20.0, fast_threshold=20):
         """FastDetector::detect on the frame in `slot` (plsvo_hip_detect_fast): abi.CORNER_DTYPE records in cell order"""
-        return self.ctx.detect_fast(slot, 1, cell_size, n_levels, 20, detection_threshold, None if occupancy is None else occupancy[None])[0]
+        return self.ctx.detect_fast(slot, 1, cell_size, n_levels, fast_threshold, detection_threshold, None if occupancy is None else occupancy[None])[0]
 
 
 class HipChainBackend(HipBackend):
@@ -296,7 +307,7 @@ def candidate_map_tables(t):
 def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_thresh=2.0, mapping=False, known_frac=0.6,
                  pos_noise=0.005, map_seed=0, kf_every=5, detect=False, detect_cell_size=25, kf_select=False, kfselect_mindist_t=0.06,
                  kfselect_mindist_r=3.0, max_n_kfs=10, map_candidates=False, record_candidates=False, cell_select=False, select_params=None, kf_insert=False,
-                 seed_candidates=False, seeds_resident=False):
+                 seed_candidates=False, seeds_resident=False, image_seeds=None, image_seed_params=None):
     """-> list of per-frame dicts (pose T_f_w, cov, counts).  Frame 0 is the keyframe with the true pose.
     mapping=True: only `known_frac` of the point landmarks start in the map (positions off by `pos_noise` x depth along
     their viewing ray), the others are depth-filter seeds; the seed update runs every frame; every `kf_every`-th frame
@@ -335,8 +346,21 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
     no record comes back, only the report and the update's rows, from which the harness keeps its own tables exactly as it does from an
     add's report.  A removal at an insertion is passed on (plsvo_seeds_keyframe); when it takes frame 0's keyframe out, the seeds that
     are left leave the device with it -- their keyframe is no longer in the table -- and the harness goes on following them on the host,
-    outside the map, as it does without this flag.  With the flag off every record is what it is without it."""
+    outside the map, as it does without this flag.  With the flag off every record is what it is without it.
+    image_seeds="host" | "device" (with seeds_resident; default None: nothing changes): at a keyframe whose seed tables are on the device
+    the image's corners become point seeds of the RESIDENT lists (DepthFilter::initializeSeeds' creating half), behind the
+    insertion, with the cells of the frame's selected features and of the last update's matches occupied.  "device" is
+    plsvo_seeds_keyframe_detect with both occupancy sources; "host" does the same with the calls there were before -- detect_corners on
+    an occupancy built from the fetched selection and the fetched rows by the same rule, seeds_from_corners, seeds_keyframe(pt_..) --
+    so the two differ in transport alone and agree in every record and in the lists.  These seeds have no landmark of the synthetic
+    map: the harness keeps, per resident row, the landmark of a map seed or -1, follows removals and erasures through the rows and the
+    reports, and gives a converged image seed a table row of its own without a landmark (such rows are selected, optimised and inserted
+    on the device like any other; the harness's own alignment and structure optimisation leave them out).  The records gain
+    n_image_seeds / n_image_seeds_converged / n_image_seeds_started.  image_seed_params: fast_threshold, detection_threshold (20, 20.0).
+    When frame 0's keyframe leaves the table the resident lists are given up as without this flag, image seeds included."""
     params = dict(locals())                            # (first statement: exactly the arguments)
+    if image_seeds not in (None, "host", "device") or (image_seeds and not (seeds_resident and hasattr(backend, "seeds_keyframe_detect" if image_seeds == "device" else "detect_corners"))):
+        raise ValueError("image_seeds is None, 'host' or 'device', needs seeds_resident and a backend with detect_corners() / seeds_keyframe_detect()")
     if seeds_resident and not (seed_candidates and hasattr(backend, "seeds_stage")):
         raise ValueError("seeds_resident needs seed_candidates and a backend with seeds_stage()")
     if seed_candidates and not (kf_insert and hasattr(backend, "map_add_candidates")):
@@ -359,8 +383,13 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
 
 
 def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thresh, mapping, known_frac, pos_noise, map_seed, kf_every, detect, detect_cell_size, kf_select,
-                  kfselect_mindist_t, kfselect_mindist_r, max_n_kfs, map_candidates, record_candidates, cell_select, select_params, kf_insert, seed_candidates, seeds_resident):
+                  kfselect_mindist_t, kfselect_mindist_r, max_n_kfs, map_candidates, record_candidates, cell_select, select_params, kf_insert, seed_candidates, seeds_resident,
+                  image_seeds=None, image_seed_params=None):
     cam = seq["cam"]
+    img_kw = dict(fast_threshold=20, detection_threshold=20.0)
+    img_kw.update(image_seed_params or {})
+    res_lm, res_kf, res_ftr, last_rows, img_conv = [], [], [], None, 0   # image_seeds: per resident point row its landmark (-1: from the image), its keyframe row, its feature
+    sel_mask = None
     seeds_on_device = False                            # seeds_resident: the seed lists are staged and their keyframe is still in the table
     if cell_select and not (map_candidates and hasattr(backend, "map_select")):
         raise ValueError("cell_select needs map_candidates and a backend with map_select()")
@@ -492,8 +521,10 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                         backend.seeds_stage(dict(batch_counter=0, pt_ref_kf=np.full(len(si_), seed_kf, np.int32), pt_batch_id=np.zeros(len(si_), np.int32), pt_px=seq["pt_px0"][si_],
                                                  pt_f=seq["pt_f0"][si_], pt_level=np.zeros(len(si_), np.int32), pt_type=np.zeros(len(si_), np.uint8),
                                                  pt_grad=np.zeros((len(si_), 2)), pt_a=seeds["a"], pt_b=seeds["b"], pt_mu=seeds["mu"], pt_z_range=seeds["z_range"],
-                                                 pt_sigma2=seeds["sigma2"]), cam, max_n_kfs=1 << 30, n_pyr_levels=n_pyr_levels)
+                                                 pt_sigma2=seeds["sigma2"]), cam, max_n_kfs=1 << 30, n_pyr_levels=n_pyr_levels,
+                                            **(dict(room=dict(extra_pt=len(seq["images"]) * (-(-w_img // detect_cell_size)) * (-(-h_img // detect_cell_size)))) if image_seeds else {}))
                         seeds_on_device = True
+                        res_lm, res_kf, res_ftr = [int(i) for i in si_], [seed_kf] * len(si_), [None] * len(si_)
                 else:
                     cr, mr = backend.map_candidates(map_job, abi.CandidateFrameJob(T_k, overlap, cur_slot=k), cam, n_pyr_levels)
                 npf, nsf = cr["n_filed_pt"], cr["n_filed_seg"]
@@ -501,9 +532,10 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                 px_new = np.zeros((len(pos_all), 2))
                 level = np.zeros(len(pos_all), np.int32)
                 at = np.concatenate([np.asarray(row_lm, np.int64)[cr["pt_lm"]], n_pts + cr["seg_lm"], n_pts + n_seg + cr["seg_lm"]]).astype(np.int64)
-                found[at] = mr["found"].astype(bool)
-                px_new[at] = mr["px"]
-                level[at] = np.maximum(mr["search_level"], 0)
+                own = at >= 0                          # (image_seeds: a row without a landmark of the harness's map is the device's alone)
+                found[at[own]] = mr["found"].astype(bool)[own]
+                px_new[at[own]] = mr["px"][own]
+                level[at[own]] = np.maximum(mr["search_level"], 0)[own]
                 hist = np.zeros(len(cm["kf_T"]), np.int64)
                 for lm, o in zip(cr["pt_lm"], cr["pt_obs"]):
                     if o >= 0:
@@ -555,6 +587,8 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
             if cell_select:
                 # ---- 4. on the device: the selected features in selection order, the resident pose optimiser's result ----
                 pt_i, seg_i = np.asarray(row_lm, np.int64)[sel["pt_lm"]], sel["seg_lm"].astype(np.int64)
+                sel_mask = pt_i >= 0
+                pt_i = pt_i[sel_mask]
                 pt_ok = np.zeros(n_pts, bool); pt_ok[pt_i] = True
                 seg_ok = np.zeros(n_seg, bool); seg_ok[seg_i] = True
                 pr = pr_sel
@@ -576,6 +610,8 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
         T_last = T_prev
         T_k = pr.T.copy()
         pt_keep, seg_keep = pr.pt_keep.astype(bool), pr.seg_keep.astype(bool)
+        if cell_select and sel_mask is not None:
+            pt_keep = pt_keep[sel_mask]
         prev = dict(pt_idx=pt_i[pt_keep], pt_px=px_new[pt_i[pt_keep]], seg_idx=seg_i[seg_keep],
                     seg_spx=px_new[n_pts + seg_i[seg_keep]], seg_epx=px_new[n_pts + n_seg + seg_i[seg_keep]])
         T_prev = T_k
@@ -613,10 +649,43 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                             seed_kf = None if remove == seed_kf else seed_kf - (remove < seed_kf)
                     before = (copy.deepcopy(cm), quality) if record_candidates else None
                     tables, quality, ins = backend.map_insert(remove, k)
-                    if seeds_on_device and remove >= 0:                # removeKeyframe: the seeds' keyframe moves down a row, or leaves with its seeds
+                    cm = candidate_map_tables(tables)
+                    if seeds_on_device and image_seeds and seed_kf is not None:
+                        # initializeSeeds on the resident lists: the removal, then the corners of the frame's free cells
+                        new_kf = len(cm["kf_T"]) - 1
+                        assert ins.get("new_kf", new_kf) == new_kf and cm["kf_slot"][new_kf] == k
+                        ev = dict(removed_kf=remove, new_batch=True, new_kf=new_kf, depth_mean=seed_depth[0], depth_min=seed_depth[1])
+                        if image_seeds == "device":
+                            backend.seeds_keyframe_detect(detect_cell_size, n_pyr_levels, img_kw["detection_threshold"], fast_threshold=img_kw["fast_threshold"],
+                                                          occ_sources=abi.SEED_OCC_SELECTED | (abi.SEED_OCC_UPDATED if last_rows is not None else 0), **ev)
+                            kf_rep = backend.seeds_keyframe_fetch()
+                            assert not kf_rep["no_room"]
+                            n_started = kf_rep["n_new_pt"]
+                        else:
+                            marking = np.zeros((0, 2))
+                            if last_rows is not None:
+                                stl = last_rows["pt_status"]
+                                marking = last_rows["pt_px_cur"][(stl == abi.SEED_UPDATED) | (stl == abi.SEED_CONVERGED) | (stl == abi.SEED_NAN)]
+                            occ = _occupancy(np.concatenate([sel["pt_px"].reshape(-1, 2), marking]), w_img, h_img, detect_cell_size)
+                            corners = backend.detect_corners(k, occ, detect_cell_size, n_pyr_levels, img_kw["detection_threshold"], fast_threshold=img_kw["fast_threshold"])
+                            sdn = seeds_from_corners(corners, cam, *seed_depth)
+                            backend.seeds_keyframe(pt_px=sdn["px"], pt_f=sdn["f"], pt_level=sdn["level"], pt_type=sdn["type"], pt_grad=sdn["grad"], **ev)
+                            n_started = len(corners)
+                        if remove >= 0:
+                            stay = [j for j, r in enumerate(res_kf) if r != remove]
+                            res_lm, res_ftr = [res_lm[j] for j in stay], [res_ftr[j] for j in stay]
+                            res_kf = [res_kf[j] - (res_kf[j] > remove) for j in stay]
+                        if n_started:                                  # the new rows' features, for the landmark a converged one becomes (both transports: from the lists)
+                            ls = backend.seeds_fetch_lists()
+                            assert len(ls["pt_ref_kf"]) == len(res_lm) + n_started
+                            for j in range(len(res_lm), len(res_lm) + n_started):
+                                res_ftr.append(dict(px=[float(x) for x in ls["pt_px"][j]], f=[float(x) for x in ls["pt_f"][j]], level=int(ls["pt_level"][j])))
+                            res_lm += [-1] * n_started; res_kf += [new_kf] * n_started
+                        rec["n_image_seeds_started"] = int(n_started)
+                    elif seeds_on_device and remove >= 0:              # removeKeyframe: the seeds' keyframe moves down a row, or leaves with its seeds
                         backend.seeds_keyframe(removed_kf=remove)
                         seeds_on_device = seed_kf is not None
-                    cm = candidate_map_tables(tables)
+                        res_lm, res_kf, res_ftr = [], [], []
                     rec.update(n_joined=ins["n_joined_pt"] + ins["n_joined_seg"], n_deleted_kf=ins["n_deleted_pt"] + ins["n_deleted_seg"], remove_kf=remove)
                     if record_candidates:
                         rec["insert"] = dict(stream=before[0], quality_before=before[1], select=sel, pt_keep=pr.pt_keep.copy(), seg_keep=pr.seg_keep.copy(), T=[float(v) for v in T_k],
@@ -661,20 +730,47 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                     cm_dirty = True
             # ---- 6. depth-filter update of the seeds with this frame (DepthFilter::updateSeeds) ----
             ns = len(seeds["idx"])
-            if ns:
+            img_dev = bool(image_seeds) and seeds_on_device    # the resident rows hold seeds from the image beside the map's
+            if ns or (img_dev and res_lm):
                 si_ = seeds["idx"]
                 ptd = dict(ref_frame=np.zeros(ns, np.int32), cur_frame=np.ones(ns, np.int32), px=seq["pt_px0"][si_], f=seq["pt_f0"][si_], level=np.zeros(ns, np.int32),
                            a=seeds["a"], b=seeds["b"], mu=seeds["mu"], z_range=seeds["z_range"], sigma2=seeds["sigma2"])
                 if seeds_on_device:                               # on the resident lists: the report and the rows come back, no record travels
                     seed_report, sr, seed_quality = backend.seeds_update(k, T_k)
-                    assert len(sr["pt_status"]) == ns and seed_report["no_room"] == 0
+                    assert len(sr["pt_status"]) == (len(res_lm) if img_dev else ns) and seed_report["no_room"] == 0
+                    if img_dev:                                   # the map's seeds are the rows with a landmark, in the order of seeds["idx"]
+                        all_rows, is_map = sr, np.asarray(res_lm, np.int64) >= 0
+                        last_rows = dict(pt_status=sr["pt_status"].copy(), pt_px_cur=sr["pt_px_cur"].copy())
+                        assert np.array_equal(np.asarray(res_lm, np.int64)[is_map], si_)
+                        sr = {f: v[is_map] for f, v in sr.items() if f.startswith("pt_")}
                 else:
                     sr = backend.update_seeds(abi.SeedsJob(cam, np.stack([kf_T, T_k]), np.array([0, k], np.int32), ptd, None, n_pyr_levels=n_pyr_levels))
                 stt = sr["pt_status"]
                 conv = stt == abi.SEED_CONVERGED
                 P3[si_[conv]] = sr["pt_xyz_world"][conv]
                 known[si_[conv]] = True
-                if seed_candidates and conv.any() and seed_kf is not None:
+                if img_dev:
+                    # every converged row, from the map or from the image, is a new landmark row of the resident tables, in list order
+                    st_all = all_rows["pt_status"]
+                    for j, r in enumerate(np.nonzero(st_all == abi.SEED_CONVERGED)[0]):
+                        row, lm = len(cm["pt_pos"]), res_lm[r]
+                        assert row == seed_report["first_pt"] + j
+                        if lm >= 0:
+                            ftr = dict(px=[float(x) for x in seq["pt_px0"][lm]], f=[float(x) for x in seq["pt_f0"][lm]], level=0, grad=[0.0, 0.0])
+                            lm_row[lm] = row
+                        else:
+                            ftr = dict(res_ftr[r], grad=[1.0, 0.0])
+                            img_conv += 1
+                        cm["pt_pos"].append([float(x) for x in all_rows["pt_xyz_world"][r]])
+                        cm["pt_type"].append(abi.LM_CANDIDATE)
+                        cm["pt_obs"].append([dict(kf=res_kf[r], px=ftr["px"], f=ftr["f"], level=ftr["level"], type=abi.FTR_CORNER, grad=ftr["grad"])])
+                        cm["pt_cand"].append(row)
+                        row_lm.append(lm)
+                        quality = seed_quality
+                    stay = [r for r in range(len(res_lm)) if st_all[r] not in (abi.SEED_CONVERGED, abi.SEED_NAN, abi.SEED_AGED)]
+                    res_lm, res_kf, res_ftr = [res_lm[r] for r in stay], [res_kf[r] for r in stay], [res_ftr[r] for r in stay]
+                    rec.update(n_image_seeds=sum(1 for v in res_lm if v < 0), n_image_seeds_converged=img_conv)
+                elif seed_candidates and conv.any() and seed_kf is not None:
                     # the converged seeds join the RESIDENT tables on the device as new landmark rows (newCandidatePoint); the harness
                     # appends the same rows to its own
                     ci = [int(i) for i in si_[conv]]

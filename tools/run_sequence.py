@@ -11,7 +11,7 @@ With --kf-select (off by default; needs mapping) the keyframe stage runs on the 
 frame plays the keyframe when FrameHandlerMono::needNewKf says so instead of every fifth, and the JSON line lists the keyframe frames.
 With --map-candidates (off by default) reprojection and matching take their candidates from the map-candidate stage (plsvo_candidates_*):
 the overlap keyframes' features, one visit per landmark, the closest-view observation as the reference patch.
-usage: python tools/run_sequence.py [--distortion k1,k2,p1,p2[,k3]] [--detect] [--kf-select] [--map-candidates] [--cell-select] [--kf-insert] [--seed-candidates] [--seeds-resident] [out.txt] [n_frames] [seed] [mapping 0|1]"""
+usage: python tools/run_sequence.py [--distortion k1,k2,p1,p2[,k3]] [--detect] [--kf-select] [--map-candidates] [--cell-select] [--kf-insert] [--seed-candidates] [--seeds-resident] [--image-seeds host|device] [out.txt] [n_frames] [seed] [mapping 0|1]"""
 import importlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -48,6 +48,11 @@ if seed_candidates:
 seeds_resident = "--seeds-resident" in argv        # with --seed-candidates: the seed lists are staged once and updated, erased and handed over on the device (plsvo_seeds_*)
 if seeds_resident:
     argv.remove("--seeds-resident")
+image_seeds = None                                 # with --seeds-resident: a keyframe's corners become point seeds of the resident lists, on the device or through the host
+if "--image-seeds" in argv:
+    i = argv.index("--image-seeds")
+    image_seeds = argv[i + 1]
+    del argv[i:i + 2]
 sys.argv = sys.argv[:1] + argv
 
 out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "gpurun_out", "trajectory.txt")
@@ -63,7 +68,8 @@ if distortion is not None:
     seq = dict(seq, images=[P.synth.distort_image(img, dict(fx=fx, fy=fy, cx=cx, cy=cy, d=distortion)) for img in seq["images"]])
     rectify = P.abi.pinhole_radtan(w, h, fx, fy, cx, cy, distortion)
 res = seqm.run_sequence(seqm.HipBackend(ctx, rectify=rectify), seq, mapping=mapping, detect=detect, kf_select=kf_select, map_candidates=map_candidates, cell_select=cell_select, kf_insert=kf_insert,
-                        seed_candidates=seed_candidates, seeds_resident=seeds_resident)
+                        seed_candidates=seed_candidates, seeds_resident=seeds_resident, image_seeds=image_seeds,
+                        image_seed_params=dict(fast_threshold=7, detection_threshold=2.0) if image_seeds else None)
 n = P.trajectory.write_trajectory(out, ["%.6f" % (0.05 * k) for k in range(n_frames)], [r["T"] for r in res], [r["cov"] for r in res])
 err = seqm.pose_errors(res, seq)
 print(json.dumps({"frames": n_frames, "lines_written": n, "trajectory": out, "max_rot_err_rad": max(e[0] for e in err),

@@ -472,7 +472,13 @@ typedef struct plsvo_structopt_out {   /* caller buffers; any of them may be NUL
   int32_t* seg_iters;               /* n_seg */
 } plsvo_structopt_out;
 
+/* pt_obs_off / seg_obs_off must start at 0 and never decrease: anything else is PLSVO_E_INVALID before anything is uploaded. */
 int plsvo_structure_optimize(plsvo_ctx* ctx, const plsvo_structopt_in* in, plsvo_structopt_out* out);
+
+/* Diagnostic view of the optimiser's 3x3 solve (tests; like plsvo_match_warp_patches for the matcher): x = A.ldlt().solve(b) for n
+ * independent systems, one lane each, through the device function plsvo_structure_optimize's kernel calls (Eigen 3.2's zero-pivot
+ * rule, flavour 320 only).  A: 9*n, row-major 3x3 per system, the lower triangle is read; b, x: 3*n.  NaN/Inf propagate into x. */
+int plsvo_structure_solve3(plsvo_ctx* ctx, int32_t n, const double* A, const double* b, double* x);
 
 /* ------------------------------------------------------------------------------------------ */
 /* direct feature matching (hot-path contract row (f) "next" #2)                               */

@@ -72,6 +72,7 @@ def lib():
             ("plsvo_oracle_se3_exp", [d, d], None), ("plsvo_oracle_se3_mul", [d, d, d], None),
             ("plsvo_oracle_se3_inv", [d, d], None), ("plsvo_oracle_se3_act", [d, d, d], None),
             ("plsvo_oracle_se3_matrix", [d, d, d], None), ("plsvo_oracle_ldlt_solve6", [d, d, d], C.c_int),
+            ("plsvo_oracle_ldlt_solve3", [d, d, d], C.c_int),
             ("plsvo_oracle_set_ldlt_flavour", [C.c_int], None), ("plsvo_oracle_get_ldlt_flavour", [], C.c_int),
             ("plsvo_oracle_inv6", [d, d], None), ("plsvo_oracle_jacobian_xyz2uv", [d, d], None),
             ("plsvo_oracle_setup_sampling", [d, d, C.c_double, C.c_uint64, d], C.c_uint64),
@@ -315,6 +316,15 @@ def ldlt_solve6(H, b):
     b = np.ascontiguousarray(b, dtype=np.float64)
     x = np.empty(6)
     lib().plsvo_oracle_ldlt_solve6(_dp(H), _dp(b), _dp(x))
+    return x
+
+
+def ldlt_solve3(A, b):
+    """A.ldlt().solve(b) of Point::optimize / LineSeg::optimize: ldlt_solve_n at N = 3, in the current flavour"""
+    A = np.ascontiguousarray(A, dtype=np.float64).reshape(9)
+    b = np.ascontiguousarray(b, dtype=np.float64).reshape(3)
+    x = np.empty(3)
+    lib().plsvo_oracle_ldlt_solve3(_dp(A), _dp(b), _dp(x))
     return x
 
 

@@ -912,6 +912,8 @@ done:
 
 /* [ext] Eigen::LDLT<Matrix3d>::compute + solve, the 3x3 instance of the algorithm restated above */
 static void ldlt_solve3(const double A[9], const double b[3], double x[3]) { ldlt_solve_n(3, A, b, x); }
+/* the same, exported for the directed solver tests (tests/test_structopt_paths.py); returns 0 always */
+int plsvo_oracle_ldlt_solve3(const double A[9], const double b[3], double x[3]) { ldlt_solve_n(3, A, b, x); return 0; }
 
 /* one observation's contribution: Point::jacobian_xyz2uv (include/plsvo/feature3D.h:126-140),
  * e = project2d(f) - project2d(p_in_f), A += J^T J, b -= J^T e, chi2 += |e|^2  (feature3D_impl.cpp:49-58) */

@@ -25,7 +25,7 @@ SYMBOLS = [
     "plsvo_align_set_trace", "plsvo_align_fetch_trace", "plsvo_align_poses_dev", "plsvo_align_copy_poses", "plsvo_align_work", "plsvo_align_work_points", "plsvo_align_chi2_ties", "plsvo_align_launch_order", "plsvo_align_tail_frames",
     "plsvo_pose_optimize", "plsvo_pose_optimize_batch", "plsvo_poseopt_stage", "plsvo_poseopt_run", "plsvo_poseopt_fetch",
     "plsvo_poseopt_set_trace", "plsvo_poseopt_fetch_trace", "plsvo_poseopt_poses_dev", "plsvo_poseopt_copy_poses", "plsvo_poseopt_work", "plsvo_poseopt_refill_frames", "plsvo_poseopt_row_select",
-    "plsvo_structure_optimize", "plsvo_match_direct", "plsvo_match_warp_patches", "plsvo_reproject", "plsvo_trajectory_record", "plsvo_update_seeds",
+    "plsvo_structure_optimize", "plsvo_structure_solve3", "plsvo_match_direct", "plsvo_match_warp_patches", "plsvo_reproject", "plsvo_trajectory_record", "plsvo_update_seeds",
     "plsvo_close_keyframes", "plsvo_keyframe_decide",
     "plsvo_candidates_stage", "plsvo_candidates_run", "plsvo_candidates_fetch", "plsvo_candidates_match", "plsvo_candidates_match_fetch", "plsvo_candidates_dev",
     "plsvo_candidates_set_quality", "plsvo_candidates_fetch_quality", "plsvo_candidates_select", "plsvo_candidates_select_fetch", "plsvo_candidates_pose_optimize",
@@ -143,6 +143,7 @@ def lib():
         "plsvo_poseopt_poses_dev": (vp, [ctxp]),
         "plsvo_poseopt_work": (C.c_int, [ctxp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "plsvo_structure_optimize": (C.c_int, [ctxp, C.POINTER(abi.StructOptIn), C.POINTER(abi.StructOptOut)]),
+        "plsvo_structure_solve3": (C.c_int, [ctxp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "plsvo_match_direct": (C.c_int, [ctxp, C.POINTER(abi.MatchIn), C.POINTER(abi.MatchOut)]),
         "plsvo_match_warp_patches": (C.c_int, [ctxp, C.POINTER(abi.MatchIn), C.POINTER(abi.MatchWarpOut)]),
         "plsvo_reproject": (C.c_int, [ctxp, C.POINTER(abi.ReprojectIn), C.POINTER(abi.ReprojectOut)]),
@@ -1162,6 +1163,17 @@ class Context:
         out, bufs = job.make_out()
         self._chk(self.L.plsvo_structure_optimize(self.h, C.byref(job.c), C.byref(out)))
         return job.trim(bufs)
+
+    def structure_solve3(self, A, b):
+        """plsvo_structure_solve3 (diagnostic): the kernel's own 3x3 A.ldlt().solve(b), one lane per system.  A [n, 3, 3], b [n, 3] -> x [n, 3]"""
+        A = np.ascontiguousarray(A, dtype=np.float64).reshape(-1, 3, 3)
+        b = np.ascontiguousarray(b, dtype=np.float64).reshape(-1, 3)
+        if A.shape[0] != b.shape[0]:
+            raise ValueError("structure_solve3: A and b disagree on the number of systems")
+        x = np.zeros((max(A.shape[0], 1), 3))
+        dp = C.POINTER(C.c_double)
+        self._chk(self.L.plsvo_structure_solve3(self.h, A.shape[0], A.ctypes.data_as(dp), b.ctypes.data_as(dp), x.ctypes.data_as(dp)))
+        return x[:A.shape[0]].copy()
 
     # ---- direct feature matching ----
     def match_direct(self, job):

@@ -21,6 +21,7 @@ hipError_t launch_align_levels(const AlignBatchDev& b, int cap, int scap, int le
                                hipStream_t stream);
 hipError_t launch_pose_opt(const PoseBatchDev& b, double* d_poses, int threads, int select, hipStream_t stream);
 hipError_t launch_structopt(const StructBatchDev& s, hipStream_t stream);
+hipError_t launch_structopt_solve3(const double* A, const double* b, double* x, int n, hipStream_t stream);
 hipError_t launch_match_direct(const MatchBatchDev& b, hipStream_t stream);
 hipError_t launch_match_warp_patches(const MatchBatchDev& b, hipStream_t stream);
 hipError_t launch_reproject(const ReprojBatchDev& b, hipStream_t stream);

@@ -1583,6 +1583,16 @@ extern "C" int plsvo_structure_optimize(plsvo_ctx* c, const plsvo_structopt_in* 
   if ((in->n_pts > 0 && (!in->pt_pos || !in->pt_obs_off)) || (in->n_seg > 0 && (!in->seg_spos || !in->seg_epos || !in->seg_obs_off)))
     return fail(c, PLSVO_E_INVALID, "structure_optimize: null landmark array");
   if (in->n_pts + in->n_seg == 0) return PLSVO_OK;
+  // the kernel reads observations [off[i], off[i+1]) of every landmark: a table must start at 0 and never decrease (so no entry is
+  // negative and none exceeds the last, which sizes the upload) -- checked here, before anything is uploaded or launched
+  auto bad_offsets = [](const int32_t* off, int n) {
+    if (n <= 0) return false;
+    if (off[0] != 0) return true;
+    for (int i = 0; i < n; ++i) if (off[i + 1] < off[i]) return true;
+    return false;
+  };
+  if (bad_offsets(in->pt_obs_off, in->n_pts) || bad_offsets(in->seg_obs_off, in->n_seg))
+    return fail(c, PLSVO_E_INVALID, "structure_optimize: observation offsets must start at 0 and not decrease");
   HIP_TRY(c, hipSetDevice(c->device));
   const int np = in->n_pts, ns = in->n_seg;
   const int npo = np > 0 ? in->pt_obs_off[np] : 0, nso = ns > 0 ? in->seg_obs_off[ns] : 0;
@@ -1633,6 +1643,24 @@ extern "C" int plsvo_structure_optimize(plsvo_ctx* c, const plsvo_structopt_in* 
   if (out->seg_epos && ns) memcpy(out->seg_epos, hd.data() + (size_t)(np + ns) * 3, (size_t)ns * 3 * sizeof(double));
   if (out->pt_iters && np) memcpy(out->pt_iters, hi.data(), (size_t)np * sizeof(int));
   if (out->seg_iters && ns) memcpy(out->seg_iters, hi.data() + np, (size_t)ns * sizeof(int));
+  return PLSVO_OK;
+}
+
+// diagnostic view of the 3x3 solve inside structopt_kernel (tests): n systems, one lane each
+extern "C" int plsvo_structure_solve3(plsvo_ctx* c, int32_t n, const double* A, const double* b, double* x) {
+  CTX_CHECK(c);
+  if (n < 0 || (n > 0 && (!A || !b || !x))) return fail(c, PLSVO_E_INVALID, "structure_solve3: bad arguments");
+  if (n == 0) return PLSVO_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t na = (size_t)n * 9, nb = (size_t)n * 3;
+  HIP_TRY(c, c->s_d_in.ensure((na + nb) * sizeof(double)));
+  HIP_TRY(c, c->s_d_out.ensure(nb * sizeof(double)));
+  double* dA = c->s_d_in.as<double>();
+  HIP_TRY(c, hipMemcpyAsync(dA, A, na * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(dA + na, b, nb * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, launch_structopt_solve3(dA, dA + na, c->s_d_out.as<double>(), n, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(x, c->s_d_out.as<double>(), nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   return PLSVO_OK;
 }
 

@@ -162,4 +162,22 @@ hipError_t launch_structopt(const StructBatchDev& s, hipStream_t stream) {
   return hipGetLastError();
 }
 
+// Diagnostic view of the solve (plsvo_structure_solve3; tests): one lane per system through the very ldlt_solve3 above, in this
+// translation unit and therefore under its flags.  A is row-major 3x3 (the lower triangle is read), n systems back to back.
+__global__ __launch_bounds__(64) void structopt_solve3_kernel(const double* A, const double* b, double* x, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double a[9], r[3], o[3];
+  for (int k = 0; k < 9; ++k) a[k] = A[9 * (size_t)i + k];
+  for (int k = 0; k < 3; ++k) r[k] = b[3 * (size_t)i + k];
+  ldlt_solve3(a, r, o);
+  for (int k = 0; k < 3; ++k) x[3 * (size_t)i + k] = o[k];
+}
+
+hipError_t launch_structopt_solve3(const double* A, const double* b, double* x, int n, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(structopt_solve3_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, A, b, x, n);
+  return hipGetLastError();
+}
+
 }  // namespace plsvo_hip

@@ -950,6 +950,18 @@ def test_every_entry_point_rejects_malformed_arguments(P, gpu_ctx):
     rejected(L.plsvo_structure_optimize(h, C.byref(so), C.byref(A.StructOptOut())), "structure_optimize")
     so = A.StructOptIn(); so.n_pts = 3                       # landmarks without their arrays
     rejected(L.plsvo_structure_optimize(h, C.byref(so), C.byref(A.StructOptOut())), "structure_optimize")
+    # offset tables that do not start at 0, hold a negative entry or decrease (their last entry, which sizes the upload, is valid):
+    # rejected by the argument check, before anything is uploaded or launched
+    sb = P.synth.make_structure_batch(31, n_pts=6, n_seg=6)
+    for key in ("pt_obs_off", "seg_obs_off"):
+        for i, v in ((0, 1), (0, -1), (2, -3), (2, int(sb[key][-1]) + 4), (5, int(sb[key][4]) - 1)):
+            bad = dict(sb)
+            bad[key] = sb[key].copy()
+            bad[key][i] = v
+            sj = P.structopt_job_from_batch(bad)
+            so_out, _ = sj.make_out()
+            rejected(L.plsvo_structure_optimize(h, C.byref(sj.c), C.byref(so_out)), "structure_optimize: observation offsets")
+    rejected(L.plsvo_structure_solve3(h, -1, None, None, None), "structure_solve3")
     mi = A.MatchIn()                                         # n_pyr_levels = 0
     rejected(L.plsvo_match_direct(h, C.byref(mi), C.byref(A.MatchOut())), "match_direct")
     mi = A.MatchIn(); mi.n = 4; mi.n_frames = 1; mi.n_pyr_levels = 3

@@ -4,66 +4,44 @@ GPU: the HIP kernel is compiled without fma contraction and must reproduce the o
 import numpy as np
 import pytest
 
-import np_restatement as npr
-
-
-def _np_point_optimize(frame_T, pos, obs_frame, obs_f, n_iter):
-    """NumPy restatement of Point::optimize (independent of oracle/plsvo_oracle.c)"""
-    pos = np.array(pos, float)
-    old = pos.copy()
-    chi2, iters = 0.0, 0
-    for it in range(n_iter):
-        A, b, new_chi2 = np.zeros((3, 3)), np.zeros(3), 0.0
-        iters += 1
-        for fr, f in zip(obs_frame, obs_f):
-            T = frame_T[fr]
-            p = npr.se3_act(T, pos)
-            x, y, z, w = T[:4]
-            R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
-                          [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
-                          [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
-            zi = 1.0 / p[2]
-            P = np.array([[zi, 0, -p[0] * zi * zi], [0, zi, -p[1] * zi * zi]])
-            J = (-P) @ R
-            e = f[:2] / f[2] - p[:2] / p[2]
-            new_chi2 += float(e @ e)
-            A += J.T @ J
-            b -= J.T @ e
-        dp = np.linalg.solve(A, b) if abs(np.linalg.det(A)) > 0 else np.zeros(3)
-        if (it > 0 and new_chi2 > chi2) or np.isnan(dp[0]):
-            pos = old.copy()
-            break
-        old = pos.copy()
-        pos = pos + dp
-        chi2 = new_chi2
-        if np.max(np.abs(dp)) <= 1e-10:
-            break
-    return pos, iters
+import np_structopt as nso
 
 
 def test_oracle_points_match_numpy_restatement(P, ob):
+    """the oracle against tests/np_structopt.py (term by term in the reference's order, its own pivoted LDLT -- singular systems
+    included): bit for bit"""
     d = P.synth.make_structure_batch(1, n_pts=12, n_seg=0)
     res = ob.structure_optimize(P.structopt_job_from_batch(d))
     for i in range(12):
         o0, o1 = d["pt_obs_off"][i], d["pt_obs_off"][i + 1]
-        pos, iters = _np_point_optimize(d["frame_T"], d["pt_pos"][i], d["pt_obs_frame"][o0:o1], d["pt_obs_f"][o0:o1], 5)
+        pos, iters, _ = nso.point_optimize(d["frame_T"], d["pt_pos"][i], d["pt_obs_frame"][o0:o1], d["pt_obs_f"][o0:o1], 5)
         assert iters == res["pt_iters"][i]
-        assert np.allclose(pos, res["pt_pos"][i], rtol=0, atol=1e-11)
+        assert np.array_equal(pos, res["pt_pos"][i])
+    # one observation each: singular (rank-2) normal equations
+    d["pt_obs_off"] = np.arange(13, dtype=np.int32)
+    res = ob.structure_optimize(P.structopt_job_from_batch(d))
+    for i in range(12):
+        pos, iters, rec = nso.point_optimize(d["frame_T"], d["pt_pos"][i], d["pt_obs_frame"][i:i + 1], d["pt_obs_f"][i:i + 1], 5)
+        assert any(rec.solves[0].zeroed) and iters == res["pt_iters"][i] and np.array_equal(pos, res["pt_pos"][i])
 
 
 def test_oracle_segments_are_two_coupled_point_problems(P, ob):
-    """LineSeg::optimize runs the point update on both end points but breaks / rolls back jointly (:139-146, :169)"""
+    """LineSeg::optimize runs the point update on both end points but breaks / rolls back jointly (:139-146, :169): the oracle equals
+    the restatement of the joint loop bit for bit on every segment, and the joint exits are not those of the two ends alone"""
     d = P.synth.make_structure_batch(2, n_pts=0, n_seg=10)
     res = ob.structure_optimize(P.structopt_job_from_batch(d))
+    coupled = 0
     for i in range(10):
         o0, o1 = d["seg_obs_off"][i], d["seg_obs_off"][i + 1]
-        n = int(res["seg_iters"][i])
-        ps, its = _np_point_optimize(d["frame_T"], d["seg_spos"][i], d["seg_obs_frame"][o0:o1], d["seg_obs_sf"][o0:o1], n)
-        pe, ite = _np_point_optimize(d["frame_T"], d["seg_epos"][i], d["seg_obs_frame"][o0:o1], d["seg_obs_ef"][o0:o1], n)
-        if its == n and ite == n and n < 5:      # both end points ran the same number of steps without a private early stop
-            continue
-        if its == n and ite == n:
-            assert np.allclose(ps, res["seg_spos"][i], atol=1e-10) and np.allclose(pe, res["seg_epos"][i], atol=1e-10)
+        fr, sf, ef = d["seg_obs_frame"][o0:o1], d["seg_obs_sf"][o0:o1], d["seg_obs_ef"][o0:o1]
+        sp, ep, iters, rec = nso.segment_optimize(d["frame_T"], d["seg_spos"][i], d["seg_epos"][i], fr, sf, ef, 5)
+        assert iters == res["seg_iters"][i], rec
+        assert np.array_equal(sp, res["seg_spos"][i]) and np.array_equal(ep, res["seg_epos"][i]), rec
+        ps, its, _ = nso.point_optimize(d["frame_T"], d["seg_spos"][i], fr, sf, 5)
+        pe, ite, _ = nso.point_optimize(d["frame_T"], d["seg_epos"][i], fr, ef, 5)
+        assert iters == min(its, ite)                    # whichever end stops or fails first ends both
+        coupled += int(not (np.array_equal(ps, sp) and np.array_equal(pe, ep)))
+    assert coupled >= 3                                  # ... so a segment is not two independent point problems
 
 
 def test_known_answer_triangulation(P, ob):

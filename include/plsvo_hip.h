@@ -314,6 +314,15 @@ int plsvo_align_set_trace(plsvo_ctx* ctx, int max_records_per_job);
 int plsvo_align_fetch_trace(plsvo_ctx* ctx, int job, plsvo_align_iterlog* out, int max_records,
                             int* n_records);
 
+/* Diagnostic view of the per-level set-up (tests; like plsvo_structure_solve3 for the structure optimiser): after plsvo_align_run,
+ * the first n_slots patch slots of one job as the LAST level the run executed left them -- records: 64 bytes per slot (seven rows
+ * of the 8 reference-image bytes [vi-3+k][ui-3 .. ui+4], then the two sub-pixel fractions as floats), uvref: the slot's reference
+ * pixel position (u, v) at that level.  Slots no live feature owns at the level (holes) hold whatever was there.  Run ONE level
+ * (max_level == min_level) to look at that level.  PLSVO_E_STATE before a run or after a run in a latency shape (256 threads per
+ * frame and more keep float rows, not records); PLSVO_E_INVALID for n_slots beyond the job's allocation (the largest level's
+ * slot count, rounded up to 4).  Costs the hot path nothing: two copies out of the buffers the kernel works in. */
+int plsvo_align_fetch_records(plsvo_ctx* ctx, int job, int n_slots, unsigned char* records, float* uvref);
+
 /* device pointer to the staged batch's result poses, n*7 doubles (for a device-side gather) */
 const double* plsvo_align_poses_dev(plsvo_ctx* ctx);
 /* enqueue a device-to-device copy of those n*7 doubles into caller-owned HBM (e.g. a torch tensor) */

@@ -22,7 +22,7 @@ SYMBOLS = [
     "plsvo_rectify_map", "plsvo_hip_config_rectify", "plsvo_hip_rectify_build_pyramid", "plsvo_hip_rectify_build_pyramids_dev",
     "plsvo_detect_grid", "plsvo_detect_cell", "plsvo_hip_detect_fast", "plsvo_hip_detect_fast_dev", "plsvo_hip_detect_stages",
     "plsvo_sparse_align", "plsvo_sparse_align_batch", "plsvo_align_stage", "plsvo_align_run", "plsvo_align_fetch",
-    "plsvo_align_set_trace", "plsvo_align_fetch_trace", "plsvo_align_poses_dev", "plsvo_align_copy_poses", "plsvo_align_work", "plsvo_align_work_points", "plsvo_align_chi2_ties", "plsvo_align_launch_order", "plsvo_align_tail_frames",
+    "plsvo_align_set_trace", "plsvo_align_fetch_trace", "plsvo_align_fetch_records", "plsvo_align_poses_dev", "plsvo_align_copy_poses", "plsvo_align_work", "plsvo_align_work_points", "plsvo_align_chi2_ties", "plsvo_align_launch_order", "plsvo_align_tail_frames",
     "plsvo_pose_optimize", "plsvo_pose_optimize_batch", "plsvo_poseopt_stage", "plsvo_poseopt_run", "plsvo_poseopt_fetch",
     "plsvo_poseopt_set_trace", "plsvo_poseopt_fetch_trace", "plsvo_poseopt_poses_dev", "plsvo_poseopt_copy_poses", "plsvo_poseopt_work", "plsvo_poseopt_refill_frames", "plsvo_poseopt_row_select",
     "plsvo_structure_optimize", "plsvo_structure_solve3", "plsvo_match_direct", "plsvo_match_warp_patches", "plsvo_reproject", "plsvo_trajectory_record", "plsvo_update_seeds",
@@ -123,6 +123,7 @@ def lib():
         "plsvo_align_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.AlignOut)]),
         "plsvo_align_set_trace": (C.c_int, [ctxp, C.c_int]),
         "plsvo_align_fetch_trace": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.AlignIterLog), C.c_int, C.POINTER(C.c_int)]),
+        "plsvo_align_fetch_records": (C.c_int, [ctxp, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
         "plsvo_align_poses_dev": (vp, [ctxp]),
         "plsvo_align_copy_poses": (C.c_int, [ctxp, vp]),
         "plsvo_poseopt_copy_poses": (C.c_int, [ctxp, vp]),
@@ -425,6 +426,14 @@ class Context:
         n = C.c_int(0)
         self._chk(self.L.plsvo_align_fetch_trace(self.h, job, log, cap, C.byref(n)))
         return abi.align_log_to_dicts(log, n.value)
+
+    def align_fetch_records(self, job, n_slots):
+        """plsvo_align_fetch_records (diagnostic): the first n_slots patch slots of one job of the staged batch as the last level of the
+        last align_run left them -> (records uint8 [n_slots, 64], uvref float32 [n_slots, 2])"""
+        rec = np.zeros((max(n_slots, 1), 64), dtype=np.uint8)
+        uv = np.zeros((max(n_slots, 1), 2), dtype=np.float32)
+        self._chk(self.L.plsvo_align_fetch_records(self.h, int(job), int(n_slots), rec.ctypes.data, uv.ctypes.data))
+        return rec[:n_slots], uv[:n_slots]
 
     def sparse_align_batch(self, jobs):
         self.align_stage(jobs)

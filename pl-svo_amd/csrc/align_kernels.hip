@@ -70,25 +70,27 @@ __device__ __forceinline__ float robust_weight(float a) { return robust_weight_f
 // very operations of the reference's precompute (:236-264, :348-375) -- bit-identical values (tests/test_refpatch_host.py) -- for 64 B
 // streamed per patch-iteration instead of the 192 B of three float arrays (rounds 1-3) and ~340 more float operations per slot.
 // Measured on MI355X (round 4, one lane per slot): 15.14 -> 13.91 ms per 32768-frame launch.
-// bytes [x, x+8) of row y of a u8 pyramid level: aligned dword reads + v_alignbyte
+// bytes [x, x+8) of row y of a u8 pyramid level as the three aligned dwords requested and the byte shift (returned) that v_alignbyte puts
+// them into place with: the set-up of the throughput shapes keeps a window in flight from one trip of its record loop to the next and
+// shifts when it stores.  The offsets are unsigned -- a window inside the level has none below zero -- so every request is the level's
+// base plus a 32-bit offset.
 template <bool TILED>
-__device__ __forceinline__ uint2 load_row8_raw(const uint8_t* img, int pitch, int x, int y) {
-  uint32_t d0, d1, d2, sh;
+__device__ __forceinline__ uint32_t load_row8_dwords(const uint8_t* img, int pitch, int x, int y, uint32_t* d) {
   if constexpr (TILED) {
     const int a = x & ~3;
-    sh = (uint32_t)(x & 3);
     const int row = tiled_row_offset(pitch, y);
-    d0 = *reinterpret_cast<const uint32_t*>(img + (row + tiled_col_offset(a)));
-    d1 = *reinterpret_cast<const uint32_t*>(img + (row + tiled_col_offset(a + 4)));
-    d2 = *reinterpret_cast<const uint32_t*>(img + (row + tiled_col_offset(a + 8)));
+    d[0] = *reinterpret_cast<const uint32_t*>(img + (unsigned)(row + tiled_col_offset(a)));
+    d[1] = *reinterpret_cast<const uint32_t*>(img + (unsigned)(row + tiled_col_offset(a + 4)));
+    d[2] = *reinterpret_cast<const uint32_t*>(img + (unsigned)(row + tiled_col_offset(a + 8)));
+    return (uint32_t)(x & 3);
   } else {
-    const int off = y * pitch + x, a = off & ~3;
-    sh = (uint32_t)(off & 3);
-    d0 = *reinterpret_cast<const uint32_t*>(img + a);
-    d1 = *reinterpret_cast<const uint32_t*>(img + a + 4);
-    d2 = *reinterpret_cast<const uint32_t*>(img + a + 8);
+    const int off = y * pitch + x;
+    const unsigned a = (unsigned)(off & ~3);
+    d[0] = *reinterpret_cast<const uint32_t*>(img + a);
+    d[1] = *reinterpret_cast<const uint32_t*>(img + a + 4);
+    d[2] = *reinterpret_cast<const uint32_t*>(img + a + 8);
+    return (uint32_t)(off & 3);
   }
-  return make_uint2(__builtin_amdgcn_alignbyte(d1, d0, sh), __builtin_amdgcn_alignbyte(d2, d1, sh));
 }
 // optional per-phase timing (compile with -DPLSVO_TIMING): thread 0 accumulates s_memtime deltas
 #ifdef PLSVO_TIMING
@@ -367,7 +369,6 @@ __global__ __launch_bounds__(T, kMinWavesPerSimd) void align_fused_kernel(AlignB
   const AlignJobDev job = b.jobs[job_id];
   AlignStateDev* st = b.state + job_id;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int grp = tid >> 2, row = tid & 3;     // reference-patch precompute: four lanes per slot, one patch row each
   constexpr int ROWS = T / 16;                 // DPP rows of the workgroup (row partials of the reduction)
 
   extern __shared__ __align__(16) unsigned char smem[];
@@ -513,16 +514,19 @@ __global__ __launch_bounds__(T, kMinWavesPerSimd) void align_fused_kernel(AlignB
         }
         const float u = (float)(b.pt_px[2 * i] * scale), v = (float)(b.pt_px[2 * i + 1] * scale);
         if constexpr (kQuad) { s_uvr[2 * f] = u; s_uvr[2 * f + 1] = v; }
-        if (u >= 3.0f && v >= 3.0f && u < (float)(W - 3) && v < (float)(Hh - 3)) {
-          s_meta[f] = make_int2(f, f | (1 << 20));
-          if constexpr (kQuad) {
-          } else {
+        else {
+          // (throughput shapes: position and 3-D point are ONE round trip too -- a point owns slot f whether or not it is live at this
+          //  level, so its entries are written before the border test; a hole's are never read)
+          //  (all three coordinates are read before the first store: a store to patch_xyz may, for all the compiler knows, change pt_xyz)
+          const double x0 = b.pt_xyz[3 * i], x1 = b.pt_xyz[3 * i + 1], x2 = b.pt_xyz[3 * i + 2];
           b.patch_uvref[2 * (pbase + f)] = u;
           b.patch_uvref[2 * (pbase + f) + 1] = v;
-          pxyz[3 * f] = b.pt_xyz[3 * i];
-          pxyz[3 * f + 1] = b.pt_xyz[3 * i + 1];
-          pxyz[3 * f + 2] = b.pt_xyz[3 * i + 2];
-          }
+          pxyz[3 * f] = x0;
+          pxyz[3 * f + 1] = x1;
+          pxyz[3 * f + 2] = x2;
+        }
+        if (u >= 3.0f && v >= 3.0f && u < (float)(W - 3) && v < (float)(Hh - 3)) {
+          s_meta[f] = make_int2(f, f | (1 << 20));
           ++my_patches;
         }
       } else {
@@ -539,17 +543,31 @@ __global__ __launch_bounds__(T, kMinWavesPerSimd) void align_fused_kernel(AlignB
           for (int c = 0; c < 3; ++c) { g_p[c] = b.seg_p[3 * s + c]; g_q[c] = b.seg_q[3 * s + c]; }
         }
         const int code = b.seg_slot[(size_t)(level - b.slot_level0) * b.slot_stride + s];
-        if (code >= 0 && seg_flags()[s]) {
+        bool seg_live;
+        if constexpr (kQuad) seg_live = code >= 0 && seg_flags()[s];
+        else {
+          // throughput shapes: slot code, flag and the ten doubles are ONE round trip as well (a dead segment's are requested and dropped)
+          const uint8_t flag = seg_flags()[s];
+          g_s[0] = b.seg_spx[2 * s]; g_s[1] = b.seg_spx[2 * s + 1]; g_e[0] = b.seg_epx[2 * s]; g_e[1] = b.seg_epx[2 * s + 1];
+#pragma unroll
+          for (int c = 0; c < 3; ++c) { g_p[c] = b.seg_p[3 * s + c]; g_q[c] = b.seg_q[3 * s + c]; }
+#ifndef PLSVO_WAVE_EMU
+          // (an empty use of the ten before the test: left to itself the compiler moves their requests behind it, into the only branch that reads them)
+          asm volatile("" :: "v"(g_s[0]), "v"(g_s[1]), "v"(g_e[0]), "v"(g_e[1]), "v"(g_p[0]), "v"(g_p[1]), "v"(g_p[2]), "v"(g_q[0]), "v"(g_q[1]), "v"(g_q[2]));
+#endif
+          seg_live = code >= 0 && flag;
+        }
+        if (seg_live) {
           const int p0 = code & 0xfffff, N = code >> 20;
           // :316-332: 2-D step on the level image, 3-D step between the end points, both accumulated
-          const double sx = kQuad ? g_s[0] : b.seg_spx[2 * s], sy = kQuad ? g_s[1] : b.seg_spx[2 * s + 1];
-          double inc2x = ((kQuad ? g_e[0] : b.seg_epx[2 * s]) - sx) * scale / (double)(N - 1);
-          double inc2y = ((kQuad ? g_e[1] : b.seg_epx[2 * s + 1]) - sy) * scale / (double)(N - 1);
+          const double sx = g_s[0], sy = g_s[1];
+          double inc2x = (g_e[0] - sx) * scale / (double)(N - 1);
+          double inc2y = (g_e[1] - sy) * scale / (double)(N - 1);
           double px = sx * scale, py = sy * scale;
           double xr[3], inc3[3];
           for (int c = 0; c < 3; ++c) {
-            const double pr = kQuad ? g_p[c] : b.seg_p[3 * s + c];
-            inc3[c] = ((kQuad ? g_q[c] : b.seg_q[3 * s + c]) - pr) / (double)(N - 1);
+            const double pr = g_p[c];
+            inc3[c] = (g_q[c] - pr) / (double)(N - 1);
             xr[c] = pr;
           }
           for (int n = 0; n < N; ++n) {
@@ -627,18 +645,66 @@ __global__ __launch_bounds__(T, kMinWavesPerSimd) void align_fused_kernel(AlignB
         }
       }
     } else {
-    // throughput shapes: the byte record the iterations rebuild intensity and gradient from
-    for (int pb = 0; pb < n_slots; pb += T / 4) {
-      const int p = pb + grp;
-      if (p < n_slots && s_meta[p].x != SLOT_HOLE) {
-        const float u = b.patch_uvref[2 * (pbase + p)], v = b.patch_uvref[2 * (pbase + p) + 1];
-        const PatchW pw = patch_weights(u, v);
-        // lane `row` of the slot's four writes record rows `row` and `row + 4` (image rows vi-3+.., columns ui-3 .. ui+3); lane 3 the fractions
-        unsigned char* const rec = reinterpret_cast<unsigned char*>(b.cache_ref) + ((pbase + p) << 6);
-        const int cx = pw.ui - 3, ry = pw.vi - 3 + row;
-        *reinterpret_cast<uint2*>(rec + 8 * row) = load_row8_raw<kTiled>(ref_img, pitch, cx, ry);
-        if (row < 3) *reinterpret_cast<uint2*>(rec + 8 * (row + 4)) = load_row8_raw<kTiled>(ref_img, pitch, cx, ry + 4);
-        else *reinterpret_cast<float2*>(rec + 56) = make_float2(u - floorf(u), v - floorf(v));
+    // throughput shapes: the byte record the iterations rebuild intensity and gradient from.  ONE LANE PER SLOT, T slots per trip: the
+    // lane requests the seven window rows (image rows vi-3 .. vi+3, columns ui-3 .. ui+4) together, assembles the record in registers
+    // as the latency shapes do above and stores it as four 16-byte pieces.  The trips are pipelined by hand: a trip's position is
+    // requested two trips ahead and its window one trip ahead, so nothing a trip waits for was requested in that trip.  (Four lanes
+    // per slot, a quarter of the slots per trip and three dependent steps in every trip -- table entry, position, window -- was the
+    // first form of this loop: 20-32 trips of two global round trips each, nothing of the next trip in flight.)
+    // A lane without a live slot requests the window at the level's origin (position (3, 3)) and stores nothing: every trip is one
+    // straight run of instructions, which is what lets the requests of two trips overlap.
+    if (n_slots > 0) {
+      struct RecPos { bool on; float2 uv; };                        // as requested: nothing here waits for the position
+      struct RecFrac { bool on; float fu, fv; };                    // what the store needs of a position once its window is requested
+      // (the window travels from trip to trip as the dwords that were requested: shifted into place where the request was made, the
+      //  first shift would wait for the window in the trip that asked for it)
+      struct RecWin { uint32_t d[7][3]; uint32_t sh[7]; };
+      auto rec_pos = [&](int pb_) -> RecPos {
+        const int pc = min(pb_ + tid, n_slots - 1);   // (clamped: in the table and in the job's allocation)
+        RecPos r;
+        r.uv = *reinterpret_cast<const float2*>(b.patch_uvref + 2 * (pbase + pc));
+        r.on = pb_ + tid < n_slots && s_meta[pc].x != SLOT_HOLE;
+        return r;
+      };
+      auto rec_win = [&](const RecPos& in, RecFrac& fr) -> RecWin {
+        const float u = in.on ? in.uv.x : 3.0f, v = in.on ? in.uv.y : 3.0f;   // (a hole's position was never written)
+        const float fu = floorf(u), fv = floorf(v);
+        const int cx = (int)fu - 3, ry = (int)fv - 3;                         // patch_weights' ui, vi
+        fr.on = in.on; fr.fu = u - fu; fr.fv = v - fv;
+        RecWin w;
+#pragma unroll
+        for (int k = 0; k < 7; ++k) w.sh[k] = load_row8_dwords<kTiled>(ref_img, pitch, cx, ry + k, w.d[k]);
+        return w;
+      };
+      auto rec_row = [](const RecWin& w, int k) -> uint2 {
+        return make_uint2(__builtin_amdgcn_alignbyte(w.d[k][1], w.d[k][0], w.sh[k]), __builtin_amdgcn_alignbyte(w.d[k][2], w.d[k][1], w.sh[k]));
+      };
+      auto rec_store = [&](int pb_, const RecFrac& fr, const RecWin& win) {
+        if (fr.on) {
+          // the record's layout: q[k] = record rows 2k, 2k+1 (8 bytes each); q[3].zw = the two sub-pixel fractions
+          uint4* const rec = reinterpret_cast<uint4*>(b.cache_ref) + (pbase + pb_ + tid) * 4;
+          uint2 r[7];
+#pragma unroll
+          for (int k = 0; k < 7; ++k) r[k] = rec_row(win, k);
+          rec[0] = make_uint4(r[0].x, r[0].y, r[1].x, r[1].y);
+          rec[1] = make_uint4(r[2].x, r[2].y, r[3].x, r[3].y);
+          rec[2] = make_uint4(r[4].x, r[4].y, r[5].x, r[5].y);
+          rec[3] = make_uint4(r[6].x, r[6].y, __float_as_uint(fr.fu), __float_as_uint(fr.fv));
+        }
+      };
+      // (two trips per turn of the loop, each with a position and a window of its own, requested again in place once used: ONE of
+      //  either handed from turn to turn is copied register by register at the loop's end, and the copies wait for the requests just made)
+      RecFrac fr_a, fr_b;
+      RecPos pos_a = rec_pos(0), pos_b = rec_pos(T);
+      RecWin win_a = rec_win(pos_a, fr_a);
+      pos_a = rec_pos(2 * T);
+      for (int pb = 0; pb < n_slots; pb += 2 * T) {
+        const RecWin win_b = rec_win(pos_b, fr_b);
+        pos_b = rec_pos(pb + 3 * T);
+        rec_store(pb, fr_a, win_a);
+        win_a = rec_win(pos_a, fr_a);
+        pos_a = rec_pos(pb + 4 * T);
+        rec_store(pb + T, fr_b, win_b);
       }
     }
     }
@@ -921,11 +987,16 @@ __global__ __launch_bounds__(T, kMinWavesPerSimd) void align_fused_kernel(AlignB
           SlotB g;
           // warp the 3-D point, project (:422-431, :583-594); the pose is re-read from LDS every round (twelve doubles that would
           // otherwise stay in registers across the whole pass)
-          const PLSVO_LDS double* const pq = (const PLSVO_LDS double*)pose_rt;
+          const PLSVO_LDS double* pq = (const PLSVO_LDS double*)pose_rt;
+#ifndef PLSVO_WAVE_EMU
+          // (the base in ONE vector register the compiler cannot see through: the twelve reads become offsets from it and merge in pairs,
+          //  where a known scalar base gave twelve scalar addresses, each moved to a vector register of its own)
+          asm("" : "+v"(pq));
+#endif
           const double x_cam = pq[0] * a_.X + pq[1] * a_.Y + pq[2] * a_.Z + pq[9];
           const double y_cam = pq[3] * a_.X + pq[4] * a_.Y + pq[5] * a_.Z + pq[10];
           const double z_cam = pq[6] * a_.X + pq[7] * a_.Y + pq[8] * a_.Z + pq[11];
-          g.u = (float)((job.fx * (x_cam / z_cam) + job.cx) * scale);
+          g.u =(float)((job.fx * (x_cam / z_cam) + job.cx) * scale);
           g.v = (float)((job.fy * (y_cam / z_cam) + job.cy) * scale);
           // Patch::isInFrame(halfsize=2) on floorf(u), floorf(v); NaN -> out of frame
           g.live = a_.cand && (g.u >= 2.0f) && (g.v >= 2.0f) && (g.u < colmax) && (g.v < rowmax);
@@ -941,7 +1012,8 @@ __global__ __launch_bounds__(T, kMinWavesPerSimd) void align_fused_kernel(AlignB
               for (int r = 0; r < 5; ++r) {
                 const int q = tiled_row_offset(pitch, y0 + r);
                 g.wsh[r] = x0 & 3;
-                g.wlo[r] = *reinterpret_cast<const uint32_t*>(cur_img + (q + ca)); g.whi[r] = *reinterpret_cast<const uint32_t*>(cur_img + (q + cb));
+                // (unsigned: a live window's offsets are never negative, and a signed one is sign-extended and added in 64 bits per load)
+                g.wlo[r] = *reinterpret_cast<const uint32_t*>(cur_img + (unsigned)(q + ca)); g.whi[r] = *reinterpret_cast<const uint32_t*>(cur_img + (unsigned)(q + cb));
               }
             } else {
 #pragma unroll

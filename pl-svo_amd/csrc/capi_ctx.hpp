@@ -160,6 +160,7 @@ struct plsvo_ctx {
   int a_trace_cap = 0;
   DevBuf a_d_state, a_d_alive;   // (inputs: a_d_blob)
   DevBuf a_d_pxyz, a_d_puv, a_d_cref, a_d_chi, a_d_log, a_d_poses;
+  int a_run_threads = 0;                    // threads per frame of the last plsvo_align_run (plsvo_align_fetch_records)
   size_t a_patch_total = 0;                 // patch slots of the staged batch (all jobs, all levels' maximum)
   int a_seg_align = 32;                     // the staged layout's segment alignment (64: two workgroups per frame are possible)
   DevBuf a_d_workkey;                       // per job: the patch-iterations its last launch evaluated

@@ -1110,7 +1110,7 @@ extern "C" int plsvo_align_run(plsvo_ctx* c) {
       prof_end(c, PLSVO_K_ALIGN_LEVEL, &ep);
     }
   }
-  c->a_run_seq = ++c->run_seq;
+  c->a_run_seq = ++c->run_seq; c->a_run_threads = threads;
   return PLSVO_OK;
 }
 
@@ -1197,6 +1197,24 @@ extern "C" int plsvo_align_fetch_trace(plsvo_ctx* c, int job, plsvo_align_iterlo
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   *n_records = nrec;
+  return PLSVO_OK;
+}
+
+// Diagnostic view of a level's set-up (tests): what the last plsvo_align_run left in the job's patch slots -- the 64-byte records and the
+// reference pixel positions of the LAST level it ran (every level's set-up writes the same slots).  Two plain copies behind the stream.
+extern "C" int plsvo_align_fetch_records(plsvo_ctx* c, int job, int n_slots, unsigned char* records, float* uvref) {
+  CTX_CHECK(c);
+  if (!c->a_staged || c->a_run_seq == 0) return fail(c, PLSVO_E_STATE, "fetch_records: the staged batch has not run");
+  if (c->a_run_threads >= kQuadMinThreads) return fail(c, PLSVO_E_STATE, "fetch_records: the last run used a latency shape, which keeps float rows instead of records");
+  if (job < 0 || job >= c->a_n || n_slots < 0 || n_slots > c->a_jobs[(size_t)job].patch_cap || !records || !uvref)
+    return fail(c, PLSVO_E_INVALID, "fetch_records: bad arguments (n_slots is bounded by the job's slot allocation)");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t p0 = (size_t)c->a_jobs[(size_t)job].patch_off;
+  if (n_slots > 0) {
+    HIP_TRY(c, hipMemcpyAsync(records, c->a_d_cref.as<unsigned char>() + p0 * 64, (size_t)n_slots * 64, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(uvref, c->a_d_puv.as<float>() + p0 * 2, (size_t)n_slots * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   return PLSVO_OK;
 }
 

@@ -251,15 +251,11 @@ extern "C" int plsvo_candidates_run(plsvo_ctx* c, int n, const plsvo_cand_frame*
   CandBatchDev b = c->cd_b;
   const char* dr = reinterpret_cast<const char*>(c->cd_d_run.p);
   b.jobs = reinterpret_cast<const CandJobDev*>(dr + b_jobs); b.overlap_idx = reinterpret_cast<const int*>(dr + b_ov); b.kf_count = c->cd_d_kfcount.as<int>();
-  {
-    EventPair ep{}; prof_begin(c, PLSVO_K_CANDIDATES, &ep);
-    // the first-visit words are all ones ahead of EVERY launch: a run must not see the visits of the one before
-    hipError_t rearm_then_launch = hipSuccess;
-    if (c->cd_vis_bytes) rearm_then_launch = hipMemsetAsync(reinterpret_cast<char*>(c->cd_d_work.p) + c->cd_vis_off, 0xff, c->cd_vis_bytes, c->stream);
-    if (rearm_then_launch == hipSuccess) rearm_then_launch = launch_map_candidates(b, c->stream);
-    prof_end(c, PLSVO_K_CANDIDATES, &ep);            // ahead of the error return: the event pair goes back to the pool either way
-    HIP_TRY(c, rearm_then_launch);
-  }
+  const auto rearm_then_launch = [&]() -> hipError_t {   // the first-visit words are all ones ahead of EVERY launch: a run must not see the visits of the one before
+    const hipError_t e = c->cd_vis_bytes ? hipMemsetAsync(c->cd_d_work.as<char>() + c->cd_vis_off, 0xff, c->cd_vis_bytes, c->stream) : hipSuccess;
+    return e != hipSuccess ? e : launch_map_candidates(b, c->stream);
+  };
+  HIP_TRY_TIMED(c, PLSVO_K_CANDIDATES, rearm_then_launch());
   c->cd_ran = true;
   return PLSVO_OK;
 }
@@ -269,15 +265,13 @@ extern "C" int plsvo_candidates_fetch(plsvo_ctx* c, int n, plsvo_cand_out* out) 
   if (!c->cd_staged || !c->cd_ran) return fail(c, PLSVO_E_STATE, "candidates_fetch: no run to fetch");
   if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_fetch: n does not match the staged batch");
   if (n == 0) return PLSVO_OK;
-  std::vector<char> h(c->cd_fetch_bytes);
-  const size_t t_ov = (size_t)c->cd_ov_off[(size_t)n];
-  std::vector<int> kfc(std::max(t_ov, (size_t)1));
-  HIP_TRY(c, hipMemcpyAsync(h.data(), c->cd_d_work.p, h.size(), hipMemcpyDeviceToHost, c->stream));
-  if (t_ov) HIP_TRY(c, hipMemcpyAsync(kfc.data(), c->cd_d_kfcount.p, t_ov * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  Readback rb;   // (the fetched arrays are the first sections of the work allocation: one range)
+  const int r_work = rb.add(c->cd_d_work.p, c->cd_fetch_bytes), r_kfc = rb.add(c->cd_d_kfcount.p, (size_t)c->cd_ov_off[(size_t)n] * sizeof(int));
+  if (const int rc = rb.wait(c)) return rc;
+  const char* const h = rb.at<char>(r_work); const int* const kfc = rb.at<int>(r_kfc);
   const CandFetchSections& F = c->cd_off;
-  const int* cnt = reinterpret_cast<const int*>(h.data() + F.counts);
-  auto cp = [&](void* dst, size_t sec, size_t at, size_t count, size_t elem) { if (dst && count) memcpy(dst, h.data() + sec + at * elem, count * elem); };
+  const int* cnt = reinterpret_cast<const int*>(h + F.counts);
+  auto cp = [&](void* dst, size_t sec, size_t at, size_t count, size_t elem) { if (dst && count) memcpy(dst, h + sec + at * elem, count * elem); };
   for (int s = 0; s < n; ++s) {
     const CandMapDev& M = c->cd_maps[(size_t)s]; const CandStreamHost& H = c->cd_host[(size_t)s];
     plsvo_cand_out& O = out[s];
@@ -289,7 +283,7 @@ extern "C" int plsvo_candidates_fetch(plsvo_ctx* c, int n, plsvo_cand_out* out) 
     cp(O.seg_obs, F.seg_obs, so, ns, sizeof(int)); cp(O.seg_has_view, F.seg_view, so, ns, 1); cp(O.seg_active, F.seg_active, so, ns, 1);
     cp(O.pt_cand_failed, F.pt_cand_failed, (size_t)M.ptc_off, (size_t)H.fetch_pt_cand, 1); cp(O.seg_cand_failed, F.seg_cand_failed, (size_t)M.segc_off, (size_t)H.fetch_seg_cand, 1);
     const size_t a = (size_t)c->cd_ov_off[(size_t)s], e = (size_t)c->cd_ov_off[(size_t)s + 1];
-    if (O.kf_count && e > a) memcpy(O.kf_count, kfc.data() + a, (e - a) * sizeof(int));
+    if (O.kf_count && e > a) memcpy(O.kf_count, kfc + a, (e - a) * sizeof(int));
   }
   return PLSVO_OK;
 }
@@ -310,12 +304,7 @@ extern "C" int plsvo_candidates_match(plsvo_ctx* c) {
   HIP_TRY(c, hipSetDevice(c->device));
   MatchBatchDev mb = c->cd_match;
   mb.pyr_base = c->pyr.base; mb.slot_bytes = c->pyr.slot_bytes; mb.width = c->pyr.w[0]; mb.height = c->pyr.h[0];
-  {
-    EventPair ep{}; prof_begin(c, PLSVO_K_MATCH, &ep);
-    const hipError_t launched = launch_match_direct(mb, c->stream);
-    prof_end(c, PLSVO_K_MATCH, &ep);                 // ahead of the error return, as in plsvo_candidates_run
-    HIP_TRY(c, launched);
-  }
+  HIP_TRY_TIMED(c, PLSVO_K_MATCH, launch_match_direct(mb, c->stream));
   c->cd_matched = true;
   return PLSVO_OK;
 }
@@ -326,21 +315,18 @@ extern "C" int plsvo_candidates_match_fetch(plsvo_ctx* c, int n, plsvo_cand_matc
   if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_match_fetch: n does not match the staged batch");
   if (n == 0 || c->cd_total_m == 0) return PLSVO_OK;
   const size_t NM = c->cd_total_m;
-  std::vector<int> cnt((size_t)n * 2), lev(NM);
-  std::vector<double> px(NM * 2);
-  std::vector<uint8_t> found(NM);
   const MatchBatchDev& mb = c->cd_match;
-  HIP_TRY(c, hipMemcpyAsync(cnt.data(), c->cd_b.counts, cnt.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(px.data(), mb.px_out, NM * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(lev.data(), mb.search_level, NM * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(found.data(), mb.found, NM, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  Readback rb;
+  const int r_cnt = rb.add(c->cd_b.counts, (size_t)n * 2 * sizeof(int)), r_px = rb.add(mb.px_out, NM * 2 * sizeof(double)), r_lev = rb.add(mb.search_level, NM * sizeof(int)),
+            r_found = rb.add(mb.found, NM);
+  if (const int rc = rb.wait(c)) return rc;
+  const int* cnt = rb.at<int>(r_cnt); const double* px = rb.at<double>(r_px); const int* lev = rb.at<int>(r_lev); const uint8_t* found = rb.at<uint8_t>(r_found);
   for (int s = 0; s < n; ++s) {
     const size_t at = (size_t)c->cd_maps[(size_t)s].m_off, k = (size_t)cnt[2 * s] + 2 * (size_t)cnt[2 * s + 1];
     if (!k) continue;
-    if (out[s].found) memcpy(out[s].found, found.data() + at, k);
-    if (out[s].px) memcpy(out[s].px, px.data() + 2 * at, k * 2 * sizeof(double));
-    if (out[s].search_level) memcpy(out[s].search_level, lev.data() + at, k * sizeof(int));
+    if (out[s].found) memcpy(out[s].found, found + at, k);
+    if (out[s].px) memcpy(out[s].px, px + 2 * at, k * 2 * sizeof(double));
+    if (out[s].search_level) memcpy(out[s].search_level, lev + at, k * sizeof(int));
   }
   return PLSVO_OK;
 }
@@ -413,31 +399,26 @@ extern "C" int plsvo_candidates_fetch_quality(plsvo_ctx* c, int n, plsvo_cand_qu
   HIP_TRY(c, hipSetDevice(c->device));
   const QualitySections q = quality_sections(c);
   const CandBatchDev& b = c->cd_b;
-  std::vector<char> hq(q.end);
-  std::vector<CandMapDev> maps((size_t)n);
-  std::vector<int> ptype(std::max(c->cd_t_pt, (size_t)1)), stype(std::max(c->cd_t_seg, (size_t)1)), ptc(std::max(c->cd_t_ptc, (size_t)1)), segc(std::max(c->cd_t_segc, (size_t)1));
-  HIP_TRY(c, hipMemcpyAsync(hq.data(), c->cs_d_q.p, q.end, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(maps.data(), b.maps, (size_t)n * sizeof(CandMapDev), hipMemcpyDeviceToHost, c->stream));
-  if (c->cd_t_pt) HIP_TRY(c, hipMemcpyAsync(ptype.data(), b.pt_type, c->cd_t_pt * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (c->cd_t_seg) HIP_TRY(c, hipMemcpyAsync(stype.data(), b.seg_type, c->cd_t_seg * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (c->cd_t_ptc) HIP_TRY(c, hipMemcpyAsync(ptc.data(), b.pt_cand, c->cd_t_ptc * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (c->cd_t_segc) HIP_TRY(c, hipMemcpyAsync(segc.data(), b.seg_cand, c->cd_t_segc * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  Readback rb;
+  const int r_q = rb.add(c->cs_d_q.p, q.end), r_maps = rb.add(b.maps, (size_t)n * sizeof(CandMapDev)), r_pty = rb.add(b.pt_type, c->cd_t_pt * sizeof(int)),
+            r_sty = rb.add(b.seg_type, c->cd_t_seg * sizeof(int)), r_ptc = rb.add(b.pt_cand, c->cd_t_ptc * sizeof(int)), r_segc = rb.add(b.seg_cand, c->cd_t_segc * sizeof(int));
+  if (const int rc = rb.wait(c)) return rc;
+  const char* const hq = rb.at<char>(r_q); const CandMapDev* const maps = rb.at<CandMapDev>(r_maps);
   auto cp = [&](void* dst, const void* src, size_t at, size_t count, size_t elem) { if (dst && count) memcpy(dst, reinterpret_cast<const char*>(src) + at * elem, count * elem); };
   for (int s = 0; s < n; ++s) {
-    const CandMapDev& M = maps[(size_t)s];
+    const CandMapDev& M = maps[s];
     plsvo_cand_quality_out& O = out[s];
     const size_t np = (size_t)M.n_pt, ns = (size_t)M.n_seg, po = (size_t)M.pt_off, so = (size_t)M.seg_off;
     O.n_pt_cand = M.n_pt_cand; O.n_seg_cand = M.n_seg_cand;
-    cp(O.pt_n_failed, hq.data() + q.pt_nf, po, np, sizeof(int)); cp(O.pt_n_succeeded, hq.data() + q.pt_ns, po, np, sizeof(int));
-    cp(O.seg_n_failed, hq.data() + q.seg_nf, so, ns, sizeof(int)); cp(O.seg_n_succeeded, hq.data() + q.seg_ns, so, ns, sizeof(int));
-    cp(O.pt_type, ptype.data(), po, np, sizeof(int)); cp(O.seg_type, stype.data(), so, ns, sizeof(int));
+    cp(O.pt_n_failed, hq + q.pt_nf, po, np, sizeof(int)); cp(O.pt_n_succeeded, hq + q.pt_ns, po, np, sizeof(int));
+    cp(O.seg_n_failed, hq + q.seg_nf, so, ns, sizeof(int)); cp(O.seg_n_succeeded, hq + q.seg_ns, so, ns, sizeof(int));
+    cp(O.pt_type, rb.at<int>(r_pty), po, np, sizeof(int)); cp(O.seg_type, rb.at<int>(r_sty), so, ns, sizeof(int));
     // (the insertion's bit sits above the selection's internal ones)
     auto public_event = [](char ev) { return (uint8_t)((ev & (PLSVO_LM_EVENT_PROMOTED | PLSVO_LM_EVENT_DELETED)) | ((ev & kInsJoinedBit) ? PLSVO_LM_EVENT_JOINED : 0) |
                                                     ((ev & kNewCandBit) ? PLSVO_LM_EVENT_NEW : 0)); };
     if (O.pt_event) for (size_t k = 0; k < np; ++k) O.pt_event[k] = public_event(hq[q.pt_ev + po + k]);
     if (O.seg_event) for (size_t k = 0; k < ns; ++k) O.seg_event[k] = public_event(hq[q.seg_ev + so + k]);
-    cp(O.pt_cand, ptc.data(), (size_t)M.ptc_off, (size_t)M.n_pt_cand, sizeof(int)); cp(O.seg_cand, segc.data(), (size_t)M.segc_off, (size_t)M.n_seg_cand, sizeof(int));
+    cp(O.pt_cand, rb.at<int>(r_ptc), (size_t)M.ptc_off, (size_t)M.n_pt_cand, sizeof(int)); cp(O.seg_cand, rb.at<int>(r_segc), (size_t)M.segc_off, (size_t)M.n_seg_cand, sizeof(int));
   }
   return PLSVO_OK;
 }
@@ -451,9 +432,10 @@ extern "C" int plsvo_candidates_set_match(plsvo_ctx* c, int n, const plsvo_cand_
   for (int s = 0; s < n; ++s) if (!in[s].found || !in[s].px || !in[s].search_level) return fail(c, PLSVO_E_INVALID, "candidates_set_match: null array");
   if (n == 0 || c->cd_total_m == 0) { c->cd_matched = true; return PLSVO_OK; }
   HIP_TRY(c, hipSetDevice(c->device));
-  std::vector<int> cnt((size_t)n * 2);
-  HIP_TRY(c, hipMemcpyAsync(cnt.data(), c->cd_b.counts, cnt.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  Readback rb;
+  rb.add(c->cd_b.counts, (size_t)n * 2 * sizeof(int));
+  if (const int rc = rb.wait(c)) return rc;
+  const int* cnt = rb.at<int>(0);
   const MatchBatchDev& mb = c->cd_match;
   for (int s = 0; s < n; ++s) {
     const size_t at = (size_t)c->cd_maps[(size_t)s].m_off, k = (size_t)cnt[2 * s] + 2 * (size_t)cnt[2 * s + 1];
@@ -519,15 +501,12 @@ extern "C" int plsvo_candidates_select(plsvo_ctx* c, const plsvo_cand_select_par
   b.seg_line = WD(w_line); b.seg_spos = WD(w_spos); b.seg_epos = WD(w_epos); b.seg_level = WI(w_seglev);
   b.reproj_thresh = sp->reproj_thresh; b.po_n_iter = sp->poseopt_n_iter; b.ldlt_flavour = c->ldlt_flavour;
   c->cs_b = b;
-  {
-    EventPair ep{}; prof_begin(c, PLSVO_K_SELECT, &ep);
-    // ahead of EVERY launch: the event bytes are zero, the cells' winner words all ones
-    hipError_t rearm_then_launch = hipMemsetAsync(dq + q.pt_ev, 0, q.end - q.pt_ev, c->stream);
-    if (rearm_then_launch == hipSuccess) rearm_then_launch = hipMemsetAsync(b.cell_win, 0xff, N * (size_t)n_cells * sizeof(unsigned int), c->stream);
-    if (rearm_then_launch == hipSuccess) rearm_then_launch = launch_map_select(b, c->stream);
-    prof_end(c, PLSVO_K_SELECT, &ep);                // ahead of the error return, as in plsvo_candidates_run
-    HIP_TRY(c, rearm_then_launch);
-  }
+  const auto rearm_then_launch = [&]() -> hipError_t {   // ahead of EVERY launch: the event bytes are zero, the cells' winner words all ones
+    hipError_t e = hipMemsetAsync(dq + q.pt_ev, 0, q.end - q.pt_ev, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(b.cell_win, 0xff, N * (size_t)n_cells * sizeof(unsigned int), c->stream);
+    return e != hipSuccess ? e : launch_map_select(b, c->stream);
+  };
+  HIP_TRY_TIMED(c, PLSVO_K_SELECT, rearm_then_launch());
   c->cs_selected = true;
   return PLSVO_OK;
 }
@@ -541,10 +520,10 @@ extern "C" int plsvo_candidates_select_fetch(plsvo_ctx* c, int n, plsvo_cand_sel
   const SelectBatchDev& b = c->cs_b;
   // the features lie between the scalars and the pose optimiser's jobs: one copy
   const char* lo = reinterpret_cast<const char*>(b.scalars); const char* hi = reinterpret_cast<const char*>(b.po_jobs);
-  std::vector<char> h((size_t)(hi - lo));
-  HIP_TRY(c, hipMemcpyAsync(h.data(), lo, h.size(), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  auto H = [&](const void* dev) { return h.data() + (reinterpret_cast<const char*>(dev) - lo); };
+  Readback rb;
+  rb.add(lo, (size_t)(hi - lo));
+  if (const int rc = rb.wait(c)) return rc;
+  auto H = [&](const void* dev) { return rb.at<char>(0) + (reinterpret_cast<const char*>(dev) - lo); };
   auto cp = [&](void* dst, const void* dev, size_t at, size_t count, size_t elem) { if (dst && count) memcpy(dst, H(dev) + at * elem, count * elem); };
   const int* sc = reinterpret_cast<const int*>(H(b.scalars));
   for (int s = 0; s < n; ++s) {
@@ -573,10 +552,7 @@ extern "C" int plsvo_candidates_pose_optimize(plsvo_ctx* c) {
   c->cs_w.bind_resident(c->cs_pose, c->cs_b, n);
   const int threads = pose_opt_threads(c, n, (long)nft);   // (selected features <= filed landmarks)
   c->p_refill_frames = 0;                           // (jobs written on the device, as in plsvo_chain_run)
-  EventPair ep{}; prof_begin(c, PLSVO_K_POSEOPT, &ep);
-  const hipError_t launched = launch_pose_opt(c->cs_pose, c->cs_w.poses.as<double>(), threads, c->opt_poseopt_select ? 1 : 0, c->stream);
-  prof_end(c, PLSVO_K_POSEOPT, &ep);
-  HIP_TRY(c, launched);
+  HIP_TRY_TIMED(c, PLSVO_K_POSEOPT, launch_pose_opt(c->cs_pose, c->cs_w.poses.as<double>(), threads, c->opt_poseopt_select ? 1 : 0, c->stream));
   c->cs_posed = true;
   return PLSVO_OK;
 }
@@ -590,20 +566,16 @@ extern "C" int plsvo_candidates_pose_fetch(plsvo_ctx* c, int n, plsvo_poseopt_ou
   if (n == 0) return PLSVO_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t NP = std::max(c->cd_t_opt, (size_t)1), NS = std::max(2 * c->cd_t_oseg, (size_t)1);
-  std::vector<PoseStateDev> st((size_t)n);
-  std::vector<PoseJobDev> jobs((size_t)n);
-  std::vector<uint8_t> pk(NP), sk(NS);
-  HIP_TRY(c, hipMemcpyAsync(st.data(), c->cs_w.state.p, (size_t)n * sizeof(PoseStateDev), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(jobs.data(), c->cs_b.po_jobs, (size_t)n * sizeof(PoseJobDev), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(pk.data(), c->cs_w.ptkeep.p, NP, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(sk.data(), c->cs_w.segkeep.p, NS, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  Readback rb;
+  const int r_st = rb.add(c->cs_w.state.p, (size_t)n * sizeof(PoseStateDev)), r_jobs = rb.add(c->cs_b.po_jobs, (size_t)n * sizeof(PoseJobDev)),
+            r_pk = rb.add(c->cs_w.ptkeep.p, NP), r_sk = rb.add(c->cs_w.segkeep.p, NS);
+  if (const int rc = rb.wait(c)) return rc;
   for (int j = 0; j < n; ++j) {
-    const PoseStateDev& s = st[(size_t)j]; const PoseJobDev& J = jobs[(size_t)j];
+    const PoseJobDev& J = rb.at<PoseJobDev>(r_jobs)[j];
     plsvo_poseopt_out& o = out[j];
-    pose_state_to_out(s, o);
-    if (o.pt_keep && J.n_pts > 0) memcpy(o.pt_keep, pk.data() + J.pt_off, (size_t)J.n_pts);
-    if (o.seg_keep && J.n_seg > 0) memcpy(o.seg_keep, sk.data() + J.seg_off, (size_t)J.n_seg);
+    pose_state_to_out(rb.at<PoseStateDev>(r_st)[j], o);
+    if (o.pt_keep && J.n_pts > 0) memcpy(o.pt_keep, rb.at<uint8_t>(r_pk) + J.pt_off, (size_t)J.n_pts);
+    if (o.seg_keep && J.n_seg > 0) memcpy(o.seg_keep, rb.at<uint8_t>(r_sk) + J.seg_off, (size_t)J.n_seg);
   }
   return PLSVO_OK;
 }
@@ -649,11 +621,10 @@ extern "C" int plsvo_candidates_insert_keyframe(plsvo_ctx* c, int n, const plsvo
   if (!any) { c->ci_have_out = true; return PLSVO_OK; }
   HIP_TRY(c, hipSetDevice(c->device));
   // -- the records and the caller's masks, laid out like the resident masks (feature rows from opt_off / 2 * oseg_off)
-  std::vector<int> sc(N * 3);
-  if (host_masks) {
-    HIP_TRY(c, hipMemcpyAsync(sc.data(), c->cs_b.scalars, sc.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
+  Readback rb_sc;   // (consumed into the blob below, ahead of the plan's fetch)
+  if (host_masks) rb_sc.add(c->cs_b.scalars, N * 3 * sizeof(int));
+  if (const int rc = host_masks ? rb_sc.wait(c) : PLSVO_OK) return rc;
+  const int* const sc = host_masks ? rb_sc.at<int>(0) : nullptr;
   Blob blob;
   const size_t b_jobs = blob.reserve<InsertJobDev>(N);
   const size_t b_pk = host_masks ? blob.reserve<uint8_t>(c->cd_t_opt) : 0, b_sk = host_masks ? blob.reserve<uint8_t>(2 * c->cd_t_oseg) : 0;
@@ -702,21 +673,17 @@ extern "C" int plsvo_candidates_insert_keyframe(plsvo_ctx* c, int n, const plsvo
   b.jobs = reinterpret_cast<const InsertJobDev*>(din + b_jobs); b.plan = c->ci_d_plan.as<InsertPlanDev>();
   // -- the plan: decisions and counts in scratch; capacity is decided before anything is changed
   HIP_TRY(c, launch_map_insert_plan(b, c->stream));
-  std::vector<InsertPlanDev> plan(N);
-  HIP_TRY(c, hipMemcpyAsync(plan.data(), b.plan, N * sizeof(InsertPlanDev), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  Readback rb;
+  rb.add(b.plan, N * sizeof(InsertPlanDev));
+  if ((rc = rb.wait(c))) return rc;
+  const InsertPlanDev* const plan = rb.at<InsertPlanDev>(0);
   for (int s = 0; s < n; ++s) {
     if (!in[s].is_kf) continue;
     const InsertPlanDev& P = plan[(size_t)s]; const CandStreamHost& H = c->cd_host[(size_t)s];
     if (P.n_kf > H.cap_kf || P.n_kf_pt > H.cap_kf_pt || P.n_kf_seg > H.cap_kf_seg || P.n_pt_obs > H.cap_pt_obs || P.n_seg_obs > H.cap_seg_obs)
       return fail(c, PLSVO_E_CAPACITY, "candidates_insert_keyframe: a stream's new sizes exceed its room (plsvo_candidates_reserve); nothing was changed");
   }
-  {
-    EventPair ep{}; prof_begin(c, PLSVO_K_INSERT, &ep);
-    const hipError_t launched = launch_map_insert(b, c->stream);
-    prof_end(c, PLSVO_K_INSERT, &ep);                // ahead of the error return, as in plsvo_candidates_run
-    HIP_TRY(c, launched);
-  }
+  HIP_TRY_TIMED(c, PLSVO_K_INSERT, launch_map_insert(b, c->stream));
   // -- the host mirrors describe the new tables
   for (int s = 0; s < n; ++s) {
     if (!in[s].is_kf) { c->ci_last[(size_t)s] = plan[(size_t)s]; continue; }
@@ -767,12 +734,12 @@ extern "C" int plsvo_candidates_fetch_map(plsvo_ctx* c, int n, plsvo_cand_map_ou
   if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_fetch_map: n does not match the staged batch");
   if (n == 0) return PLSVO_OK;
   HIP_TRY(c, hipSetDevice(c->device));
-  std::vector<char> h(c->cd_blob_bytes);           // the tables are one allocation: one copy
-  HIP_TRY(c, hipMemcpyAsync(h.data(), c->cd_d_blob.p, h.size(), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  Readback rb;                                     // the tables are one allocation: one range
+  rb.add(c->cd_d_blob.p, c->cd_blob_bytes);
+  if (const int rc = rb.wait(c)) return rc;
   const CandBatchDev& b = c->cd_b;
   const char* base = reinterpret_cast<const char*>(c->cd_d_blob.p);
-  auto H = [&](const void* dev) { return h.data() + (reinterpret_cast<const char*>(dev) - base); };
+  auto H = [&](const void* dev) { return rb.at<char>(0) + (reinterpret_cast<const char*>(dev) - base); };
   auto cp = [&](void* dst, const void* dev, size_t at, size_t count, size_t elem) { if (dst && count) memcpy(dst, H(dev) + at * elem, count * elem); };
   const CandMapDev* maps = reinterpret_cast<const CandMapDev*>(H(b.maps));
   for (int s = 0; s < n; ++s) {
@@ -943,12 +910,7 @@ extern "C" int plsvo_candidates_add(plsvo_ctx* c, int n, const plsvo_cand_new* i
   b.pt_obs_type = reinterpret_cast<const uint8_t*>(d + b_pty); b.pt_obs_grad = D(b_pgr);
   b.seg_spos = D(b_ss); b.seg_epos = D(b_se); b.seg_obs_kf = Iv(b_skf); b.seg_obs_spx = D(b_sspx); b.seg_obs_epx = D(b_sepx); b.seg_obs_sf = D(b_ssf);
   b.seg_obs_ef = D(b_sef); b.seg_obs_level = Iv(b_slv);
-  {
-    EventPair ep{}; prof_begin(c, PLSVO_K_NEWCAND, &ep);
-    const hipError_t launched = launch_map_add_candidates(b, c->stream);
-    prof_end(c, PLSVO_K_NEWCAND, &ep);               // ahead of the error return, as in plsvo_candidates_run
-    HIP_TRY(c, launched);
-  }
+  HIP_TRY_TIMED(c, PLSVO_K_NEWCAND, launch_map_add_candidates(b, c->stream));
   // -- the host mirrors describe the new tables (the candidate counts are upper bounds: the selection shortens the lists on the device)
   for (int s = 0; s < n; ++s) {
     CandMapDev& M = c->cd_maps[(size_t)s]; CandStreamHost& H = c->cd_host[(size_t)s];
@@ -966,11 +928,11 @@ extern "C" int plsvo_candidates_add_fetch(plsvo_ctx* c, int n, plsvo_cand_add_ou
   if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_add_fetch: n does not match the staged batch");
   if (n == 0) return PLSVO_OK;
   HIP_TRY(c, hipSetDevice(c->device));
-  std::vector<CandMapDev> maps((size_t)n);         // the candidate counts as they stand are the device's
-  HIP_TRY(c, hipMemcpyAsync(maps.data(), c->cd_b.maps, (size_t)n * sizeof(CandMapDev), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  Readback rb;                                     // the candidate counts as they stand are the device's
+  rb.add(c->cd_b.maps, (size_t)n * sizeof(CandMapDev));
+  if (const int rc = rb.wait(c)) return rc;
   for (int s = 0; s < n; ++s) {
-    const CandMapDev& M = maps[(size_t)s]; const CandStreamHost& H = c->cd_host[(size_t)s];
+    const CandMapDev& M = rb.at<CandMapDev>(0)[s]; const CandStreamHost& H = c->cd_host[(size_t)s];
     out[s] = c->cn_last[(size_t)s];
     out[s].n_pt = M.n_pt; out[s].n_seg = M.n_seg; out[s].n_pt_cand = M.n_pt_cand; out[s].n_seg_cand = M.n_seg_cand; out[s].n_pt_obs = H.n_pt_obs; out[s].n_seg_obs = H.n_seg_obs;
   }
@@ -1006,18 +968,8 @@ static int seeds_enqueue(plsvo_ctx* c, int n, const std::vector<SeedFrameDev>& f
   SeedListBatchDev b = c->sd_b;
   b.frames = c->sd_d_in.as<SeedFrameDev>();
   b.s.pyr_base = c->pyr.base; b.s.slot_bytes = c->pyr.slot_bytes; b.s.width = c->pyr.w[0]; b.s.height = c->pyr.h[0];
-  if (launch_update) {
-    EventPair ep{}; prof_begin(c, PLSVO_K_SEEDS, &ep);
-    const hipError_t launched = launch_update_seeds_resident(b, c->stream);
-    prof_end(c, PLSVO_K_SEEDS, &ep);                 // ahead of the error return, as in plsvo_candidates_run
-    HIP_TRY(c, launched);
-  }
-  {
-    EventPair ep{}; prof_begin(c, PLSVO_K_NEWCAND, &ep);
-    const hipError_t launched = launch_seeds_commit(b, c->stream);
-    prof_end(c, PLSVO_K_NEWCAND, &ep);
-    HIP_TRY(c, launched);
-  }
+  if (launch_update) HIP_TRY_TIMED(c, PLSVO_K_SEEDS, launch_update_seeds_resident(b, c->stream));
+  HIP_TRY_TIMED(c, PLSVO_K_NEWCAND, launch_seeds_commit(b, c->stream));
   c->cd_max_level = std::max(c->cd_max_level, c->sd_max_level);   // a new landmark's observation has its seed's level
   c->cn_closed = true;                              // the open run is over, as behind plsvo_candidates_add
   c->sd_pending = true; c->sd_have_report = false;
@@ -1229,9 +1181,10 @@ extern "C" int plsvo_seeds_update_fetch(plsvo_ctx* c, int n, plsvo_seed_report* 
   static_assert(sizeof(SeedReportDev) == sizeof(plsvo_seed_report), "the device's report is the public one");
   if (c->sd_pending) {
     HIP_TRY(c, hipSetDevice(c->device));
-    c->sd_last.resize((size_t)n);
-    if (n > 0) HIP_TRY(c, hipMemcpyAsync(c->sd_last.data(), c->sd_b.report, (size_t)n * sizeof(SeedReportDev), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    Readback rb;
+    rb.add(c->sd_b.report, (size_t)n * sizeof(SeedReportDev));
+    if (const int rc = rb.wait(c)) return rc;
+    c->sd_last.assign(rb.at<SeedReportDev>(0), rb.at<SeedReportDev>(0) + n);
     for (int s = 0; s < n; ++s) {                   // the host mirrors describe the tables as they stand
       const SeedReportDev& R = c->sd_last[(size_t)s];
       CandMapDev& M = c->cd_maps[(size_t)s]; CandStreamHost& H = c->cd_host[(size_t)s]; SeedStreamDev& S = c->sd_host[(size_t)s];
@@ -1309,12 +1262,7 @@ extern "C" int plsvo_seeds_keyframe(plsvo_ctx* c, int n, const plsvo_seed_kf* in
   b.kf_jobs = reinterpret_cast<const SeedKfJobDev*>(d + b_jobs);
   b.k_pt_px = D(p_px); b.k_pt_f = D(p_f); b.k_pt_level = reinterpret_cast<const int*>(d + p_lv); b.k_pt_type = reinterpret_cast<const uint8_t*>(d + p_ty); b.k_pt_grad = D(p_gr);
   b.k_seg_px = D(s_px); b.k_seg_f = D(s_f); b.k_seg_sf = D(s_sf); b.k_seg_ef = D(s_ef); b.k_seg_spx = D(s_spx); b.k_seg_epx = D(s_epx); b.k_seg_level = reinterpret_cast<const int*>(d + s_lv);
-  {
-    EventPair ep{}; prof_begin(c, PLSVO_K_NEWCAND, &ep);
-    const hipError_t launched = launch_seeds_keyframe(b, c->stream);
-    prof_end(c, PLSVO_K_NEWCAND, &ep);
-    HIP_TRY(c, launched);
-  }
+  HIP_TRY_TIMED(c, PLSVO_K_NEWCAND, launch_seeds_keyframe(b, c->stream));
   for (int s = 0; s < n; ++s) {                     // (with a removal the lengths are upper bounds until the next update fetch)
     SeedStreamDev& S = c->sd_host[(size_t)s];
     S.n_pt += in[s].n_pt; S.n_seg += in[s].n_seg; S.batch_counter += in[s].new_batch ? 1 : 0;
@@ -1436,13 +1384,14 @@ extern "C" int plsvo_seeds_keyframe_fetch(plsvo_ctx* c, int n, plsvo_seed_kf_rep
   static_assert(sizeof(SeedStartReportDev) == sizeof(plsvo_seed_kf_report) && sizeof(plsvo_seed_kf_report) == 32, "the device's report is the public one");
   if (n == 0) return PLSVO_OK;
   HIP_TRY(c, hipSetDevice(c->device));
-  std::vector<SeedStreamDev> streams((size_t)n);
-  HIP_TRY(c, hipMemcpyAsync(out, c->sk_d_report.p, (size_t)n * sizeof(plsvo_seed_kf_report), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(streams.data(), c->sd_b.streams, (size_t)n * sizeof(SeedStreamDev), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpyAsync(out, c->sk_d_report.p, (size_t)n * sizeof(plsvo_seed_kf_report), hipMemcpyDeviceToHost, c->stream));   // (the caller's own buffer: a plain copy, landed by the wait below)
+  Readback rb;
+  rb.add(c->sd_b.streams, (size_t)n * sizeof(SeedStreamDev));
+  if (const int rc = rb.wait(c)) return rc;
+  const SeedStreamDev* const streams = rb.at<SeedStreamDev>(0);
   for (int s = 0; s < n; ++s) {                     // the mirrors are exact again, as behind plsvo_seeds_fetch_lists
     SeedStreamDev& S = c->sd_host[(size_t)s];
-    S.n_pt = streams[(size_t)s].n_pt; S.n_seg = streams[(size_t)s].n_seg; S.batch_counter = streams[(size_t)s].batch_counter;
+    S.n_pt = streams[s].n_pt; S.n_seg = streams[s].n_seg; S.batch_counter = streams[s].batch_counter;
   }
   return PLSVO_OK;
 }
@@ -1452,13 +1401,14 @@ extern "C" int plsvo_seeds_fetch_lists(plsvo_ctx* c, int n, plsvo_seed_list* out
   if (const int rc = seeds_ready(c, n, out, "seeds_fetch_lists")) return rc;
   if (n == 0) return PLSVO_OK;
   HIP_TRY(c, hipSetDevice(c->device));
-  std::vector<char> h(c->sd_tab_bytes);            // the tables are one allocation: one copy
-  HIP_TRY(c, hipMemcpyAsync(h.data(), c->sd_d_tab.p, h.size(), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  Readback rb;                                     // the tables are one allocation: one range
+  rb.add(c->sd_d_tab.p, c->sd_tab_bytes);
+  if (const int rc = rb.wait(c)) return rc;
+  const char* const h = rb.at<char>(0);
   const SeedListBatchDev& b = c->sd_b; const SeedsBatchDev& q = b.s;
   const char* base = reinterpret_cast<const char*>(c->sd_d_tab.p);
-  auto cp = [&](void* dst, const void* dev, size_t at, size_t count, size_t elem) { if (dst && count) memcpy(dst, h.data() + (reinterpret_cast<const char*>(dev) - base) + at * elem, count * elem); };
-  const SeedStreamDev* streams = reinterpret_cast<const SeedStreamDev*>(h.data() + (reinterpret_cast<const char*>(b.streams) - base));
+  auto cp = [&](void* dst, const void* dev, size_t at, size_t count, size_t elem) { if (dst && count) memcpy(dst, h + (reinterpret_cast<const char*>(dev) - base) + at * elem, count * elem); };
+  const SeedStreamDev* streams = reinterpret_cast<const SeedStreamDev*>(h + (reinterpret_cast<const char*>(b.streams) - base));
   for (int s = 0; s < n; ++s) {
     const SeedStreamDev& S = streams[s]; plsvo_seed_list& O = out[s];
     const size_t np = (size_t)S.n_pt, ns = (size_t)S.n_seg, po = (size_t)S.pt_off, so = (size_t)S.seg_off;
@@ -1482,10 +1432,10 @@ extern "C" int plsvo_seeds_fetch_rows(plsvo_ctx* c, int n, plsvo_seed_rows* out)
   if (n == 0) return PLSVO_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   const SeedWorkSections W = seed_work_sections((size_t)n, c->sd_t_pt, c->sd_t_seg);
-  std::vector<char> h(W.end);
-  HIP_TRY(c, hipMemcpyAsync(h.data(), c->sd_d_work.p, h.size(), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  auto cp = [&](void* dst, size_t sec, size_t at, size_t count, size_t elem) { if (dst && count) memcpy(dst, h.data() + sec + at * elem, count * elem); };
+  Readback rb;
+  rb.add(c->sd_d_work.p, W.end);
+  if (const int rc = rb.wait(c)) return rc;
+  auto cp = [&](void* dst, size_t sec, size_t at, size_t count, size_t elem) { if (dst && count) memcpy(dst, rb.at<char>(0) + sec + at * elem, count * elem); };
   for (int s = 0; s < n; ++s) {
     const SeedReportDev& R = c->sd_last[(size_t)s]; const SeedStreamDev& S = c->sd_host[(size_t)s]; plsvo_seed_rows& O = out[s];
     size_t np = 0, ns = 0;

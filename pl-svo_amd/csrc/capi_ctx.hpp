@@ -1,5 +1,5 @@
 // capi_ctx.hpp -- what the translation units of the C ABI (plsvo_capi.hip, capi_candidates.hip) share: the kernels' launch functions, the
-// device buffer / staging helpers, the context, the error macros.  Internal: no part of include/plsvo_hip.h, hidden from the dynamic symbol table.
+// device buffers, the context, the error and timing macros, the launch order; staging and readback: capi_transfer.hpp.  Internal: no part of include/plsvo_hip.h, hidden from the dynamic symbol table.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -74,29 +74,16 @@ struct PLSVO_LOCAL DevBuf {
 
 struct PLSVO_LOCAL EventPair { hipEvent_t a, b; };
 
-// All input arrays of a staged batch travel as ONE host-to-device copy: sections of a single blob, each 256-byte aligned.
-// (A single-frame call used to pay a dozen small pageable copies; small blobs go through a pinned staging buffer.)
-struct PLSVO_LOCAL Blob {
-  std::vector<uint8_t> host;
-  template <typename T> size_t add(const std::vector<T>& v) {
-    const size_t off = (host.size() + 255) & ~(size_t)255;
-    host.resize(off + std::max(v.size() * sizeof(T), (size_t)16));
-    if (!v.empty()) memcpy(host.data() + off, v.data(), v.size() * sizeof(T));
-    return off;
-  }
-  // a section of n elements to be filled in place: take the pointers (at<T>) only after the LAST reserve / add, which may move the blob
-  template <typename T> size_t reserve(size_t n) {
-    const size_t off = (host.size() + 255) & ~(size_t)255;
-    host.resize(off + std::max(n * sizeof(T), (size_t)16));
-    return off;
-  }
-  template <typename T> T* at(size_t off) { return reinterpret_cast<T*>(host.data() + off); }
-};
-
-// carve typed arrays out of one device allocation (256-byte aligned sections)
-struct PLSVO_LOCAL Carver {
-  size_t off = 0;
-  template <typename T> size_t take(size_t n) { const size_t o = (off + 255) & ~(size_t)255; off = o + std::max(n, (size_t)1) * sizeof(T); return o; }
+// Launch order of a RE-RUN resident batch (alignment, pose optimiser): a launch records per job the work it evaluated (key), one small kernel
+// behind it (align_kernels.hip::align_reorder_kernel) sorts the jobs most-work-first into the OTHER of two order buffers -- the running
+// launch's is never written -- for the next launch.  WHETHER a launch reorders, and what its order is when it does not, is the run functions' decision.
+struct plsvo_ctx;
+struct PLSVO_LOCAL LaunchOrder {
+  DevBuf key, order[2];
+  int next = 0;                                        // the order buffer the next sort writes
+  int* arm(plsvo_ctx* c, int n);                       // the key of n jobs; a fresh buffer starts at zero work (jobs that leave the kernel early never write theirs).  nullptr: failed, c->err says why
+  const int* sort(plsvo_ctx* c, int n, int shift);     // behind the launch that wrote the key: the next launch's order (nullptr: failed)
+  void release() { key.release(); order[0].release(); order[1].release(); }
 };
 
 struct PLSVO_LOCAL CandStreamHost {      // map candidates: one stream's host mirror of the resident tables' sizes
@@ -163,9 +150,7 @@ struct plsvo_ctx {
   int a_run_threads = 0;                    // threads per frame of the last plsvo_align_run (plsvo_align_fetch_records)
   size_t a_patch_total = 0;                 // patch slots of the staged batch (all jobs, all levels' maximum)
   int a_seg_align = 32;                     // the staged layout's segment alignment (64: two workgroups per frame are possible)
-  DevBuf a_d_workkey;                       // per job: the patch-iterations its last launch evaluated
-  DevBuf a_d_order[2];                      // launch order of a RE-RUN resident batch: sorted on the device by the last launch's measured work
-  int a_order_next = 0;                     //   (align_kernels.hip::align_reorder_kernel); the buffer the next reorder writes
+  LaunchOrder a_order;                      // launch order of a RE-RUN resident batch, from the patch-iterations its last launch evaluated
   bool env_align_no_reorder = false;
   const int* a_stage_order = nullptr;          // the staged batch's own order (most patches first), inside a_d_blob
   bool a_one_shot = false, p_one_shot = false;   // set around the run of a one-shot batch call: its launch order is never consumed
@@ -191,8 +176,8 @@ struct plsvo_ctx {
   PoseWork p_w;                             // (inputs: p_d_blob)
   DevBuf p_d_log;
   PoseBatchDev p_b{};
-  DevBuf p_d_workkey, p_d_order[2];         // as a_d_workkey / a_d_order: the launch order of a re-run staged batch, from its last launch's feature-iterations
-  int p_order_next = 0, p_key_shift = 0;
+  LaunchOrder p_order;                      // as a_order, from its last launch's feature-iterations
+  int p_key_shift = 0;
   bool env_poseopt_no_reorder = false;
   int env_poseopt_reorder_min = 0;          //   PLSVO_POSEOPT_REORDER_MIN (tests)
   // row refill of the row shape's Gauss-Newton loop (poseopt_kernels.hip: three launches): PLSVO_OPT_POSEOPT_REFILL, and for tests and
@@ -310,20 +295,50 @@ struct plsvo_ctx {
 };
 
 #define CTX_CHECK(ctx) do { if (!(ctx)) return PLSVO_E_INVALID; } while (0)
-#define HIP_TRY(ctx, expr)                                                                      \
+#define HIP_FAIL_IF(ctx, e, what)                                                               \
   do {                                                                                          \
-    hipError_t e__ = (expr);                                                                    \
-    if (e__ != hipSuccess) {                                                                    \
-      (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e__);                          \
+    if ((e) != hipSuccess) {                                                                    \
+      (ctx)->err = std::string(what) + ": " + hipGetErrorString(e);                             \
       return PLSVO_E_HIP;                                                                       \
     }                                                                                           \
   } while (0)
+#define HIP_TRY(ctx, expr) do { const hipError_t e__ = (expr); HIP_FAIL_IF(ctx, e__, #expr); } while (0)
 static inline int fail(plsvo_ctx* ctx, int code, const std::string& msg) { ctx->err = msg; return code; }
 
 PLSVO_LOCAL void prof_begin(plsvo_ctx* c, int k, EventPair* ep);   // helpers both units use, defined in plsvo_capi.hip
 PLSVO_LOCAL void prof_end(plsvo_ctx* c, int k, EventPair* ep);
-PLSVO_LOCAL int download_ranges(plsvo_ctx* c, int n_ranges, const void* const* src, const size_t* bytes, std::vector<uint8_t>& fallback, const uint8_t** h);
-PLSVO_LOCAL int upload_blob(plsvo_ctx* c, DevBuf& buf, const Blob& blob);
+// HIP_TRY of a launch expression between the two events of kernel family k: the event pair goes back to the pool whether the launch failed or not
+#define HIP_TRY_TIMED(ctx, k, expr)                                                             \
+  do {                                                                                          \
+    EventPair ep__{};                                                                           \
+    prof_begin((ctx), (k), &ep__);                                                              \
+    const hipError_t e__ = (expr);                                                              \
+    prof_end((ctx), (k), &ep__);                                                                \
+    HIP_FAIL_IF(ctx, e__, #expr);                                                               \
+  } while (0)
+
+#include "capi_transfer.hpp"
+
+inline int* LaunchOrder::arm(plsvo_ctx* c, int n) {
+  const auto grow = [&]() -> int {
+    HIP_TRY(c, key.ensure((size_t)n * sizeof(int)));
+    HIP_TRY(c, hipMemsetAsync(key.p, 0, key.cap, c->stream));
+    return PLSVO_OK;
+  };
+  return (key.cap >= (size_t)n * sizeof(int) || grow() == PLSVO_OK) ? key.as<int>() : nullptr;
+}
+inline const int* LaunchOrder::sort(plsvo_ctx* c, int n, int shift) {
+  DevBuf& ob = order[next];
+  const auto enqueue = [&]() -> int {
+    HIP_TRY(c, ob.ensure((size_t)n * sizeof(int)));
+    HIP_TRY(c, launch_align_reorder(key.as<int>(), n, ob.as<int>(), shift, c->stream));
+    return PLSVO_OK;
+  };
+  if (enqueue() != PLSVO_OK) return nullptr;
+  next ^= 1;
+  return ob.as<int>();
+}
+
 PLSVO_LOCAL int pose_opt_threads(const plsvo_ctx* c, int n, long feats);
 // corner detection, shared by plsvo_hip_detect_fast(_dev) and plsvo_seeds_keyframe_detect (defined in plsvo_capi.hip).  detect_check_params:
 // everything the detect entry points refuse in their params, for n launch positions; the pyramids are configured and p is not NULL.

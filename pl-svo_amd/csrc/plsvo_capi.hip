@@ -111,7 +111,7 @@ extern "C" void plsvo_hip_destroy(plsvo_ctx* c) {
   (void)hipStreamSynchronize(c->stream);
   prof_collect(c);
   for (auto& ep : c->ev_pool) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
-  c->a_d_tailflag.release(); c->a_d_alive_tail.release(); c->a_d_xbuf.release(); c->a_d_order[0].release(); c->a_d_order[1].release(); c->a_d_workkey.release(); c->p_d_workkey.release(); c->p_d_order[0].release(); c->p_d_order[1].release();
+  c->a_d_tailflag.release(); c->a_d_alive_tail.release(); c->a_d_xbuf.release(); c->a_order.release(); c->p_order.release();
   c->p_d_carry.release(); c->p_d_refill_next.release();
   for (DevBuf* b : { &c->cd_d_blob, &c->cd_d_work, &c->cd_d_run, &c->cd_d_kfcount, &c->ci_d_work, &c->ci_d_in, &c->ci_d_plan, &c->ci_d_pos, &c->cn_d_in, &c->sd_d_tab, &c->sd_d_work, &c->sd_d_in, &c->cs_d_q,
                      &c->cs_d_work, &c->cs_d_order, &c->pyr_slab, &c->pyr_tiled, &c->pyr_upload, &c->a_d_blob, &c->a_d_state, &c->a_d_alive, &c->a_d_pxyz, &c->a_d_puv,
@@ -310,12 +310,9 @@ extern "C" int plsvo_hip_upload_pyramid(plsvo_ctx* c, int slot, int n_levels, co
 
 static int build_levels(plsvo_ctx* c, int first_slot, int n, int rounding) {
   uint8_t* base = c->pyr_slab.as<uint8_t>() + (size_t)first_slot * c->pyr.slot_bytes;
-  for (int l = 1; l < c->pyr.n_levels; ++l) {
-    EventPair ep{}; prof_begin(c, PLSVO_K_HALFSAMPLE, &ep);
-    HIP_TRY(c, launch_halfsample(base + c->pyr.off[l - 1], c->pyr.slot_bytes, c->pyr.w[l - 1], c->pyr.h[l - 1], c->pyr.w[l - 1],
-                                 base + c->pyr.off[l], c->pyr.slot_bytes, n, rounding, c->stream));
-    prof_end(c, PLSVO_K_HALFSAMPLE, &ep);
-  }
+  for (int l = 1; l < c->pyr.n_levels; ++l)
+    HIP_TRY_TIMED(c, PLSVO_K_HALFSAMPLE, launch_halfsample(base + c->pyr.off[l - 1], c->pyr.slot_bytes, c->pyr.w[l - 1], c->pyr.h[l - 1], c->pyr.w[l - 1],
+                                                          base + c->pyr.off[l], c->pyr.slot_bytes, n, rounding, c->stream));
   // (the slots count as fresh only once their tile launches are enqueued: a failed launch leaves them stale and the next launch that
   //  reads the mirror tries again -- ADVICE r05)
   const int rc_t = retile(c, first_slot, n, c->pyr.n_levels);
@@ -641,17 +638,18 @@ extern "C" int plsvo_hip_detect_fast(plsvo_ctx* c, int first_slot, int n, const 
                       c->det_counts.as<int32_t>());
   if (rc) return rc;
   // the records come back through a host copy of the device buffer: only the valid ones of every slot reach the caller's array
-  std::vector<int32_t> cnt((size_t)n);
-  HIP_TRY(c, hipMemcpyAsync(cnt.data(), c->det_counts.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  Readback rb;
+  rb.add(c->det_counts.p, (size_t)n * sizeof(int32_t));
+  if ((rc = rb.wait(c))) return rc;
+  const int32_t* const cnt = rb.at<int32_t>(0);
   for (int i = 0; i < n; ++i) {
-    if (cnt[(size_t)i] < 0 || cnt[(size_t)i] > cells) return fail(c, PLSVO_E_HIP, "detect_fast: corrupt count");
-    if (cnt[(size_t)i] > 0)
-      HIP_TRY(c, hipMemcpyAsync(corners + (size_t)i * cells, c->det_corners.as<plsvo_corner>() + (size_t)i * cells, (size_t)cnt[(size_t)i] * sizeof(plsvo_corner),
+    if (cnt[i] < 0 || cnt[i] > cells) return fail(c, PLSVO_E_HIP, "detect_fast: corrupt count");
+    if (cnt[i] > 0)
+      HIP_TRY(c, hipMemcpyAsync(corners + (size_t)i * cells, c->det_corners.as<plsvo_corner>() + (size_t)i * cells, (size_t)cnt[i] * sizeof(plsvo_corner),
                                 hipMemcpyDeviceToHost, c->stream));
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  memcpy(counts, cnt.data(), (size_t)n * sizeof(int32_t));
+  memcpy(counts, cnt, (size_t)n * sizeof(int32_t));
   return PLSVO_OK;
 }
 
@@ -678,13 +676,6 @@ extern "C" int plsvo_hip_detect_stages(plsvo_ctx* c, int slot, int level, int fa
 }
 
 // ---- alignment -----------------------------------------------------------------------------------
-template <typename T>
-static int upload(plsvo_ctx* c, DevBuf& buf, const std::vector<T>& v) {
-  HIP_TRY(c, buf.ensure(std::max(v.size(), (size_t)1) * sizeof(T)));
-  if (!v.empty()) HIP_TRY(c, hipMemcpyAsync(buf.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
-  return PLSVO_OK;
-}
-
 // Static patch-slot layout of one job at one level (align_kernels.hip header).  Points own slots [0, n_pts).  The kernel works through the
 // slots in WAVE-ROUNDS of 64 (slots [64 r, 64 r + 64) go to the 64 lanes of one wave) and weights a line from the residual sums its samples
 // left in LDS behind a wave-level fence, so all samples of a segment with N <= 64 must sit inside ONE round; longer segments make the
@@ -753,66 +744,6 @@ static int slot_layout(const plsvo_align_in* in, int level, int seg_align, int32
 extern "C" int plsvo_align_slot_layout(const plsvo_align_in* in, int level, int32_t* seg_code, int32_t* n_slots, int32_t* long_lines,
                                        long long* n_patches) {
   return slot_layout(in, level, 32, seg_code, n_slots, long_lines, n_patches);
-}
-
-// Up to three device ranges to the host with ONE wait: through the context's pinned download buffer when they fit (a per-frame caller's
-// results: a few hundred bytes of state + the flags), straight into the caller's (pageable) buffers otherwise.  On return h[k] points at
-// range k's bytes: inside the pinned buffer (valid until the next fetch) or inside `fallback`.
-// (`fallback` is sized HERE whenever the pinned path is not taken -- too large, or no pinned memory to be had -- so the decision and the
-//  storage can never disagree: ADVICE r05)
-int download_ranges(plsvo_ctx* c, int n_ranges, const void* const* src, const size_t* bytes, std::vector<uint8_t>& fallback, const uint8_t** h) {
-  size_t total = 0, off[3] = { 0, 0, 0 };
-  for (int k = 0; k < n_ranges; ++k) { off[k] = total; total += (bytes[k] + 63) & ~(size_t)63; }
-  bool pinned = total <= ((size_t)4 << 20);
-  if (pinned && c->dl_pinned_cap < total) {
-    if (c->dl_pinned) (void)hipHostFree(c->dl_pinned);
-    c->dl_pinned = nullptr; c->dl_pinned_cap = 0;
-    const size_t want = std::max(total * 2, (size_t)64 << 10);
-    if (hipHostMalloc(&c->dl_pinned, want, hipHostMallocDefault) == hipSuccess) c->dl_pinned_cap = want; else { c->dl_pinned = nullptr; pinned = false; }
-  }
-  if (!pinned) fallback.resize(std::max(total, (size_t)64));
-  uint8_t* const base = pinned ? static_cast<uint8_t*>(c->dl_pinned) : fallback.data();
-  for (int k = 0; k < n_ranges; ++k) {
-    void* to = static_cast<void*>(base + off[k]);
-    h[k] = static_cast<const uint8_t*>(to);
-    if (bytes[k]) HIP_TRY(c, hipMemcpyAsync(to, src[k], bytes[k], hipMemcpyDeviceToHost, c->stream));
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return PLSVO_OK;
-}
-
-static const size_t kPinnedMax = (size_t)8 << 20;   // blobs up to 8 MB (hundreds of frames) bounce through pinned memory
-int upload_blob(plsvo_ctx* c, DevBuf& buf, const Blob& blob) {
-  const size_t bytes = std::max(blob.host.size(), (size_t)256);
-  HIP_TRY(c, buf.ensure(bytes));
-  if (blob.host.empty()) return PLSVO_OK;
-  // Small blobs (a frame, a few hundred frames) bounce through one of two pinned buffers: the DMA of a stage call is awaited only when
-  // ITS buffer comes up for reuse two stage calls later (an event recorded behind the copy), so a per-frame caller's stage -> run -> fetch
-  // makes ONE synchronisation, the fetch's.  (Round 3 waited for the stream inside every stage call.)
-  if (blob.host.size() <= kPinnedMax) {
-    const int k = c->pinned_next;
-    if (!c->pinned_done[k] && hipEventCreate(&c->pinned_done[k]) != hipSuccess) c->pinned_done[k] = nullptr;
-    if (c->pinned_done[k]) {
-      HIP_TRY(c, hipEventSynchronize(c->pinned_done[k]));        // the copy that last read this buffer has landed (no-op when never recorded)
-      if (c->pinned_cap[k] < blob.host.size()) {
-        if (c->pinned[k]) (void)hipHostFree(c->pinned[k]);
-        c->pinned[k] = nullptr; c->pinned_cap[k] = 0;
-        const size_t want = std::max(blob.host.size() * 2, (size_t)1 << 20);
-        if (hipHostMalloc(&c->pinned[k], want, hipHostMallocDefault) == hipSuccess) c->pinned_cap[k] = want; else c->pinned[k] = nullptr;
-      }
-      if (c->pinned[k]) {
-        memcpy(c->pinned[k], blob.host.data(), blob.host.size());
-        HIP_TRY(c, hipMemcpyAsync(buf.p, c->pinned[k], blob.host.size(), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipEventRecord(c->pinned_done[k], c->stream));
-        c->pinned_next = k ^ 1;
-        return PLSVO_OK;
-      }
-    }
-  }
-  // large blobs (or no pinned memory): straight from the caller's Blob, which must not be touched while the DMA is in flight -- wait here
-  HIP_TRY(c, hipMemcpyAsync(buf.p, blob.host.data(), blob.host.size(), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return PLSVO_OK;
 }
 
 extern "C" int plsvo_align_stage(plsvo_ctx* c, int n, const plsvo_align_in* in) {
@@ -1062,13 +993,7 @@ extern "C" int plsvo_align_run(plsvo_ctx* c) {
   const bool reorder = have_levels && !per_level && c->a_n > (c->env_align_reorder_min > 0 ? c->env_align_reorder_min - 1 : cus_run * 512 / threads) &&   // more frames than resident workgroups (eight waves per CU)
                        !c->env_align_no_reorder && !c->env_align_no_lpt && !c->a_one_shot;
   c->a_b.work_key = nullptr;
-  if (reorder) {
-    if (c->a_d_workkey.cap < (size_t)c->a_n * sizeof(int)) {   // a fresh key buffer starts at zero work: jobs that leave the kernel early never write theirs
-      HIP_TRY(c, c->a_d_workkey.ensure((size_t)c->a_n * sizeof(int)));
-      HIP_TRY(c, hipMemsetAsync(c->a_d_workkey.p, 0, c->a_d_workkey.cap, c->stream));
-    }
-    c->a_b.work_key = c->a_d_workkey.as<int>();
-  }
+  if (reorder && !(c->a_b.work_key = c->a_order.arm(c, c->a_n))) return PLSVO_E_HIP;
   // TAIL SPLIT: a launch of many rounds of resident workgroups ends on whichever long frames started last (~5 % of it: nothing known
   // before a frame runs predicts its cost).  The frames at the end of the launch order -- two rounds' worth -- therefore run as two
   // workgroups of the same launch, their coarse levels first and their finest level last (align_kernels.hip), so that the launch ends on
@@ -1091,24 +1016,17 @@ extern "C" int plsvo_align_run(plsvo_ctx* c) {
     }
   }
   if (!per_level || !have_levels) {
-    EventPair ep{}; prof_begin(c, PLSVO_K_ALIGN_LEVEL, &ep);
-    HIP_TRY(c, launch_align_levels(c->a_b, cap, scap, have_levels ? c->a_gmax : 0, have_levels ? c->a_gmin : 0, 1, threads, lds, c->stream));
-    prof_end(c, PLSVO_K_ALIGN_LEVEL, &ep);
+    HIP_TRY_TIMED(c, PLSVO_K_ALIGN_LEVEL, launch_align_levels(c->a_b, cap, scap, have_levels ? c->a_gmax : 0, have_levels ? c->a_gmin : 0, 1, threads, lds, c->stream));
     // a batch with more frames than resident slots: the NEXT launch of this staged batch starts its frames longest-first by what they cost in
-    // this one (one small kernel behind the launch; the order buffers alternate, the running launch's is never written)
+    // this one (LaunchOrder); a launch that does not reorder keeps the order it has
     if (reorder) {
-      DevBuf& ob = c->a_d_order[c->a_order_next];
-      HIP_TRY(c, ob.ensure((size_t)c->a_n * sizeof(int)));
-      HIP_TRY(c, launch_align_reorder(c->a_b.work_key, c->a_n, ob.as<int>(), 7, c->stream));
-      c->a_b.order = ob.as<int>();
-      c->a_order_next ^= 1;
+      const int* const next_order = c->a_order.sort(c, c->a_n, 7);
+      if (!next_order) return PLSVO_E_HIP;
+      c->a_b.order = next_order;
     }
   } else {
-    for (int level = c->a_gmax; level >= c->a_gmin; --level) {   // debug: one launch per level, state carried in HBM
-      EventPair ep{}; prof_begin(c, PLSVO_K_ALIGN_LEVEL, &ep);
-      HIP_TRY(c, launch_align_levels(c->a_b, cap, scap, level, level, level == c->a_gmax ? 1 : 0, threads, lds, c->stream));
-      prof_end(c, PLSVO_K_ALIGN_LEVEL, &ep);
-    }
+    for (int level = c->a_gmax; level >= c->a_gmin; --level)   // debug: one launch per level, state carried in HBM
+      HIP_TRY_TIMED(c, PLSVO_K_ALIGN_LEVEL, launch_align_levels(c->a_b, cap, scap, level, level, level == c->a_gmax ? 1 : 0, threads, lds, c->stream));
   }
   c->a_run_seq = ++c->run_seq; c->a_run_threads = threads;
   return PLSVO_OK;
@@ -1119,13 +1037,11 @@ extern "C" int plsvo_align_fetch(plsvo_ctx* c, int n, plsvo_align_out* out) {
   if (!c->a_staged) return fail(c, PLSVO_E_STATE, "align_fetch: no staged batch");
   if (n != c->a_n || !out) return fail(c, PLSVO_E_INVALID, "align_fetch: n does not match the staged batch");
   HIP_TRY(c, hipSetDevice(c->device));
-  std::vector<uint8_t> big;   // (large batches, or no pinned memory: download_ranges sizes it)
-  const size_t rb[2] = { (size_t)n * sizeof(AlignStateDev), (size_t)std::max(c->a_total_seg, 0) };
-  const void* const rs[2] = { c->a_d_state.p, c->a_d_alive.p };
-  const uint8_t* rh[2] = { nullptr, nullptr };
-  { const int rc_d = download_ranges(c, 2, rs, rb, big, rh); if (rc_d) return rc_d; }
-  const AlignStateDev* const st = reinterpret_cast<const AlignStateDev*>(rh[0]);
-  const uint8_t* const alive = rh[1];
+  Readback rb;
+  const int r_st = rb.add(c->a_d_state.p, (size_t)n * sizeof(AlignStateDev)), r_alive = rb.add(c->a_d_alive.p, (size_t)std::max(c->a_total_seg, 0));
+  if (const int rc = rb.wait(c)) return rc;
+  const AlignStateDev* const st = rb.at<AlignStateDev>(r_st);
+  const uint8_t* const alive = rb.at<uint8_t>(r_alive);
   int dev_err = 0;
   for (int j = 0; j < n; ++j) {
     const AlignStateDev& s = st[(size_t)j];
@@ -1220,25 +1136,30 @@ extern "C" int plsvo_align_fetch_records(plsvo_ctx* c, int job, int n_slots, uns
 
 extern "C" const double* plsvo_align_poses_dev(plsvo_ctx* c) { return (c && c->a_staged) ? c->a_d_poses.as<double>() : nullptr; }
 
+// the diagnostics below sum fields over a staged batch's state array (AlignStateDev / PoseStateDev): fetch its n states, visit each
+template <typename S, typename F>
+static int for_each_state(plsvo_ctx* c, const DevBuf& states, int n, F visit) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  Readback rb;
+  rb.add(states.p, (size_t)n * sizeof(S));
+  if (const int rc = rb.wait(c)) return rc;
+  for (int j = 0; j < n; ++j) visit(rb.at<S>(0)[j]);
+  return PLSVO_OK;
+}
+
 // debug: per-phase s_memtime ticks summed over the batch (all zero unless built with -DPLSVO_TIMING); not in the public header
 extern "C" int plsvo_align_phase_ticks(plsvo_ctx* c, unsigned long long* out8) {
   CTX_CHECK(c);
   if (!c->a_staged || !out8) return fail(c, PLSVO_E_STATE, "phase_ticks: no staged batch");
-  std::vector<AlignStateDev> st((size_t)c->a_n);
-  HIP_TRY(c, hipMemcpyAsync(st.data(), c->a_d_state.p, (size_t)c->a_n * sizeof(AlignStateDev), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (int k = 0; k < 8; ++k) { out8[k] = 0; for (auto& s : st) out8[k] += s.phase_ticks[k]; }
-  return PLSVO_OK;
+  std::fill(out8, out8 + 8, 0ull);
+  return for_each_state<AlignStateDev>(c, c->a_d_state, c->a_n, [&](const AlignStateDev& s) { for (int k = 0; k < 8; ++k) out8[k] += s.phase_ticks[k]; });
 }
 
 extern "C" int plsvo_poseopt_phase_ticks(plsvo_ctx* c, unsigned long long* out8) {
   CTX_CHECK(c);
   if (!c->p_staged || !out8) return fail(c, PLSVO_E_STATE, "phase_ticks: no staged batch");
-  std::vector<PoseStateDev> st((size_t)c->p_n);
-  HIP_TRY(c, hipMemcpyAsync(st.data(), c->p_w.state.p, (size_t)c->p_n * sizeof(PoseStateDev), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (int k = 0; k < 8; ++k) { out8[k] = 0; for (auto& s : st) out8[k] += s.phase_ticks[k]; }
-  return PLSVO_OK;
+  std::fill(out8, out8 + 8, 0ull);
+  return for_each_state<PoseStateDev>(c, c->p_w.state, c->p_n, [&](const PoseStateDev& s) { for (int k = 0; k < 8; ++k) out8[k] += s.phase_ticks[k]; });
 }
 
 extern "C" int plsvo_align_copy_poses(plsvo_ctx* c, double* d_dst) {
@@ -1252,12 +1173,8 @@ extern "C" int plsvo_align_copy_poses(plsvo_ctx* c, double* d_dst) {
 extern "C" int plsvo_align_work(plsvo_ctx* c, uint64_t* patch_levels, uint64_t* patch_iters) {
   CTX_CHECK(c);
   if (!c->a_staged) return fail(c, PLSVO_E_STATE, "align_work: no staged batch");
-  HIP_TRY(c, hipSetDevice(c->device));
-  std::vector<AlignStateDev> st((size_t)c->a_n);
-  HIP_TRY(c, hipMemcpyAsync(st.data(), c->a_d_state.p, (size_t)c->a_n * sizeof(AlignStateDev), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
   uint64_t pl = 0, pi = 0;
-  for (auto& s : st) { pl += s.patch_levels; pi += s.patch_iters; }
+  if (const int rc = for_each_state<AlignStateDev>(c, c->a_d_state, c->a_n, [&](const AlignStateDev& s) { pl += s.patch_levels; pi += s.patch_iters; })) return rc;
   if (patch_levels) *patch_levels = pl;
   if (patch_iters) *patch_iters = pi;
   return PLSVO_OK;
@@ -1266,12 +1183,8 @@ extern "C" int plsvo_align_work(plsvo_ctx* c, uint64_t* patch_levels, uint64_t* 
 extern "C" int plsvo_align_work_points(plsvo_ctx* c, uint64_t* point_patch_iters) {
   CTX_CHECK(c);
   if (!c->a_staged) return fail(c, PLSVO_E_STATE, "align_work_points: no staged batch");
-  HIP_TRY(c, hipSetDevice(c->device));
-  std::vector<AlignStateDev> st((size_t)c->a_n);
-  HIP_TRY(c, hipMemcpyAsync(st.data(), c->a_d_state.p, (size_t)c->a_n * sizeof(AlignStateDev), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
   uint64_t n = 0;
-  for (auto& s : st) n += s.patch_iters_pt;
+  if (const int rc = for_each_state<AlignStateDev>(c, c->a_d_state, c->a_n, [&](const AlignStateDev& s) { n += s.patch_iters_pt; })) return rc;
   if (point_patch_iters) *point_patch_iters = n;
   return PLSVO_OK;
 }
@@ -1298,12 +1211,9 @@ extern "C" int plsvo_align_tail_frames(plsvo_ctx* c, int* tail_frames) {
 extern "C" int plsvo_align_chi2_ties(plsvo_ctx* c, uint64_t* iterations, uint64_t* ties, uint64_t* near_ties_without_terms) {
   CTX_CHECK(c);
   if (!c->a_staged) return fail(c, PLSVO_E_STATE, "align_chi2_ties: no staged batch");
-  HIP_TRY(c, hipSetDevice(c->device));
-  std::vector<AlignStateDev> st((size_t)c->a_n);
-  HIP_TRY(c, hipMemcpyAsync(st.data(), c->a_d_state.p, (size_t)c->a_n * sizeof(AlignStateDev), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
   uint64_t it = 0, t = 0, un = 0;
-  for (auto& s : st) { t += (uint64_t)s.chi2_ties; un += (uint64_t)s.chi2_unarmed; for (int l = 0; l < PLSVO_MAX_LEVELS; ++l) it += (uint64_t)s.iters[l]; }
+  if (const int rc = for_each_state<AlignStateDev>(c, c->a_d_state, c->a_n, [&](const AlignStateDev& s) {
+        t += (uint64_t)s.chi2_ties; un += (uint64_t)s.chi2_unarmed; for (int l = 0; l < PLSVO_MAX_LEVELS; ++l) it += (uint64_t)s.iters[l]; })) return rc;
   if (iterations) *iterations = it;
   if (ties) *ties = t;
   if (near_ties_without_terms) *near_ties_without_terms = un;
@@ -1413,13 +1323,8 @@ extern "C" int plsvo_poseopt_run(plsvo_ctx* c) {
   const bool reorder = threads != 256 && !c->env_poseopt_no_reorder && !c->p_one_shot &&
                        c->p_n > (c->env_poseopt_reorder_min > 0 ? c->env_poseopt_reorder_min - 1 : (threads == 16 ? 4 : 8) * cus);   // (rows: the grouping pays before the launch has a tail)
   c->p_b.work_key = nullptr;
-  if (reorder) {
-    if (c->p_d_workkey.cap < (size_t)c->p_n * sizeof(int)) {
-      HIP_TRY(c, c->p_d_workkey.ensure((size_t)c->p_n * sizeof(int)));
-      HIP_TRY(c, hipMemsetAsync(c->p_d_workkey.p, 0, c->p_d_workkey.cap, c->stream));
-    }
-    c->p_b.work_key = c->p_d_workkey.as<int>();
-  } else c->p_b.order = nullptr;
+  if (!reorder) c->p_b.order = nullptr;
+  else if (!(c->p_b.work_key = c->p_order.arm(c, c->p_n))) return PLSVO_E_HIP;
   // ROW REFILL: the four frames of a row-shape wave iterate until the last of them stops, and iteration counts are bimodal -- in the
   // stage order almost every wave runs all ten.  With more than two frames per resident row the launch is cut at the Gauss-Newton
   // loop's borders and the rows of a persistent kernel take their next frame from a queue (poseopt_kernels.hip).  Scheduling only: every
@@ -1431,27 +1336,26 @@ extern "C" int plsvo_poseopt_run(plsvo_ctx* c) {
   const int refill_min = c->env_poseopt_refill_min > 0 ? c->env_poseopt_refill_min : 2 * 4 * resident_wgs + 1;
   const bool refill = c->opt_poseopt_refill && threads == 16 && !c->p_b.log && !c->p_any_ref && pose_opt_refill_built() && c->p_n >= refill_min;
   c->p_refill_frames = 0;
-  EventPair ep{}; prof_begin(c, PLSVO_K_POSEOPT, &ep);
   if (refill) {
     const int wgs = (c->p_n + 3) / 4;
     const int gn_grid = std::max(1, std::min(wgs, c->env_poseopt_refill_waves > 0 ? c->env_poseopt_refill_waves : resident_wgs));
     HIP_TRY(c, c->p_d_carry.ensure((size_t)c->p_n * sizeof(PoseRefillCarry)));
     HIP_TRY(c, c->p_d_refill_next.ensure(16));
-    HIP_TRY(c, hipMemsetAsync(c->p_d_refill_next.p, 0, 16, c->stream));   // the queue is re-armed ahead of every launch
     const PoseRefillDev q{ c->p_d_carry.as<PoseRefillCarry>(), c->p_d_refill_next.as<int>() };
-    HIP_TRY(c, launch_pose_opt_refill(c->p_b, q, c->p_w.poses.as<double>(), gn_grid, c->opt_poseopt_select ? 1 : 0, c->stream));
+    const auto rearm_then_launch = [&]() -> hipError_t {   // the queue is re-armed ahead of every launch
+      const hipError_t e = hipMemsetAsync(c->p_d_refill_next.p, 0, 16, c->stream);
+      return e != hipSuccess ? e : launch_pose_opt_refill(c->p_b, q, c->p_w.poses.as<double>(), gn_grid, c->opt_poseopt_select ? 1 : 0, c->stream);
+    };
+    HIP_TRY_TIMED(c, PLSVO_K_POSEOPT, rearm_then_launch());
     c->p_refill_frames = c->p_n;
   } else {
-    HIP_TRY(c, launch_pose_opt(c->p_b, c->p_w.poses.as<double>(), threads, c->opt_poseopt_select ? 1 : 0, c->stream));
+    HIP_TRY_TIMED(c, PLSVO_K_POSEOPT, launch_pose_opt(c->p_b, c->p_w.poses.as<double>(), threads, c->opt_poseopt_select ? 1 : 0, c->stream));
   }
-  c->p_run_seq = ++c->run_seq;
-  prof_end(c, PLSVO_K_POSEOPT, &ep);
+  c->p_run_seq = ++c->run_seq;   // (a launch that failed has returned above: the sequence counts launches that were enqueued)
   if (reorder) {
-    DevBuf& ob = c->p_d_order[c->p_order_next];
-    HIP_TRY(c, ob.ensure((size_t)c->p_n * sizeof(int)));
-    HIP_TRY(c, launch_align_reorder(c->p_b.work_key, c->p_n, ob.as<int>(), c->p_key_shift, c->stream));
-    c->p_b.order = ob.as<int>();
-    c->p_order_next ^= 1;
+    const int* const next_order = c->p_order.sort(c, c->p_n, c->p_key_shift);
+    if (!next_order) return PLSVO_E_HIP;
+    c->p_b.order = next_order;
   }
   return PLSVO_OK;
 }
@@ -1461,13 +1365,12 @@ extern "C" int plsvo_poseopt_fetch(plsvo_ctx* c, int n, plsvo_poseopt_out* out) 
   if (!c->p_staged) return fail(c, PLSVO_E_STATE, "poseopt_fetch: no staged batch");
   if (n != c->p_n || !out) return fail(c, PLSVO_E_INVALID, "poseopt_fetch: n does not match the staged batch");
   HIP_TRY(c, hipSetDevice(c->device));
-  std::vector<uint8_t> big;   // (large batches, or no pinned memory: download_ranges sizes it)
-  const size_t rb[3] = { (size_t)n * sizeof(PoseStateDev), (size_t)std::max(c->p_total_pt, 0), (size_t)std::max(c->p_total_seg, 0) };
-  const void* const rs[3] = { c->p_w.state.p, c->p_w.ptkeep.p, c->p_w.segkeep.p };
-  const uint8_t* rh[3] = { nullptr, nullptr, nullptr };
-  { const int rc_d = download_ranges(c, 3, rs, rb, big, rh); if (rc_d) return rc_d; }
-  const PoseStateDev* const st = reinterpret_cast<const PoseStateDev*>(rh[0]);
-  const uint8_t* const pk = rh[1]; const uint8_t* const sk = rh[2];
+  Readback rb;
+  const int r_st = rb.add(c->p_w.state.p, (size_t)n * sizeof(PoseStateDev)), r_pk = rb.add(c->p_w.ptkeep.p, (size_t)std::max(c->p_total_pt, 0)),
+            r_sk = rb.add(c->p_w.segkeep.p, (size_t)std::max(c->p_total_seg, 0));
+  if (const int rc = rb.wait(c)) return rc;
+  const PoseStateDev* const st = rb.at<PoseStateDev>(r_st);
+  const uint8_t* const pk = rb.at<uint8_t>(r_pk); const uint8_t* const sk = rb.at<uint8_t>(r_sk);
   for (int j = 0; j < n; ++j) {
     const PoseStateDev& s = st[(size_t)j];
     const PoseJobDev& J = c->p_jobs[(size_t)j];
@@ -1501,33 +1404,26 @@ extern "C" int plsvo_poseopt_row_select(plsvo_ctx* c, const plsvo_row_select_in*
     if (in->row_active[r] && n > 0 && (in->row_k[r] < 0 || in->row_k[r] >= n)) return fail(c, PLSVO_E_INVALID, "poseopt_row_select: k outside [0, n)");
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  const size_t width = (size_t)in->bits / 8;
-  auto up16 = [](size_t v) { return (v + 15) / 16 * 16; };
-  const size_t o_off = up16((size_t)in->n_patterns * width), o_n = o_off + up16((size_t)nr * sizeof(long long)), o_k = o_n + up16((size_t)nr * sizeof(int));
-  const size_t o_act = o_k + up16((size_t)nr * sizeof(int)), in_bytes = o_act + up16((size_t)nr);
-  std::vector<uint8_t> h(in_bytes, 0);
-  if (in->n_patterns > 0) memcpy(h.data(), in->patterns, (size_t)in->n_patterns * width);
-  memcpy(h.data() + o_off, in->row_off, (size_t)nr * sizeof(long long));
-  memcpy(h.data() + o_n, in->row_n, (size_t)nr * sizeof(int));
-  memcpy(h.data() + o_k, in->row_k, (size_t)nr * sizeof(int));
-  memcpy(h.data() + o_act, in->row_active, (size_t)nr);
-  const size_t o_path = up16((size_t)nr * width), out_bytes = o_path + (size_t)nr * sizeof(int);
-  HIP_TRY(c, c->s_d_in.ensure(in_bytes + 16));
-  HIP_TRY(c, c->s_d_out.ensure(out_bytes + 16));
-  char* din = reinterpret_cast<char*>(c->s_d_in.p); char* dout = reinterpret_cast<char*>(c->s_d_out.p);
-  HIP_TRY(c, hipMemcpyAsync(din, h.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemsetAsync(dout, 0, out_bytes, c->stream));
+  const size_t width = (size_t)in->bits / 8, NR = (size_t)nr;
+  Blob blob;
+  const size_t b_pat = blob.add(static_cast<const uint8_t*>(in->patterns), (size_t)in->n_patterns * width), b_off = blob.add(in->row_off, NR),
+               b_n = blob.add(in->row_n, NR), b_k = blob.add(in->row_k, NR), b_act = blob.add(in->row_active, NR);
+  if (const int rc = upload_blob(c, c->s_d_in, blob)) return rc;
+  Carver cv;
+  const size_t o_sel = cv.take<uint8_t>(NR * width), o_path = cv.take<int>(NR);
+  HIP_TRY(c, c->s_d_out.ensure(cv.off + 256));
+  HIP_TRY(c, hipMemsetAsync(c->s_d_out.p, 0, cv.off, c->stream));
   RowSelectDev t{};
-  t.patterns = din; t.row_off = reinterpret_cast<const long long*>(din + o_off); t.row_n = reinterpret_cast<const int*>(din + o_n);
-  t.row_k = reinterpret_cast<const int*>(din + o_k); t.row_active = reinterpret_cast<const uint8_t*>(din + o_act);
-  t.selected = dout; t.path = reinterpret_cast<int*>(dout + o_path);
+  t.patterns = Blob::dev<uint8_t>(c->s_d_in, b_pat); t.row_off = Blob::dev<long long>(c->s_d_in, b_off); t.row_n = Blob::dev<int>(c->s_d_in, b_n);
+  t.row_k = Blob::dev<int>(c->s_d_in, b_k); t.row_active = Blob::dev<uint8_t>(c->s_d_in, b_act);
+  t.selected = Carver::dev<uint8_t>(c->s_d_out, o_sel); t.path = Carver::dev<int>(c->s_d_out, o_path);
   t.n_rows = nr; t.bits = in->bits; t.select = c->opt_poseopt_select ? 1 : 0;
   HIP_TRY(c, launch_pose_row_select(t, c->stream));
-  std::vector<uint8_t> ho(out_bytes);
-  HIP_TRY(c, hipMemcpyAsync(ho.data(), dout, out_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  memcpy(selected, ho.data(), (size_t)nr * width);
-  memcpy(path, ho.data() + o_path, (size_t)nr * sizeof(int));
+  Readback rb;
+  const int r_sel = rb.add(t.selected, NR * width), r_path = rb.add(t.path, NR * sizeof(int));
+  if (const int rc = rb.wait(c)) return rc;
+  memcpy(selected, rb.at<uint8_t>(r_sel), NR * width);
+  memcpy(path, rb.at<int>(r_path), NR * sizeof(int));
   return PLSVO_OK;
 }
 
@@ -1582,12 +1478,8 @@ extern "C" int plsvo_poseopt_copy_poses(plsvo_ctx* c, double* d_dst) {
 extern "C" int plsvo_poseopt_work(plsvo_ctx* c, uint64_t* pt_iters, uint64_t* seg_iters) {
   CTX_CHECK(c);
   if (!c->p_staged) return fail(c, PLSVO_E_STATE, "poseopt_work: no staged batch");
-  HIP_TRY(c, hipSetDevice(c->device));
-  std::vector<PoseStateDev> st((size_t)c->p_n);
-  HIP_TRY(c, hipMemcpyAsync(st.data(), c->p_w.state.p, (size_t)c->p_n * sizeof(PoseStateDev), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
   uint64_t a = 0, b2 = 0;
-  for (auto& s : st) { a += s.pt_iters; b2 += s.seg_iters; }
+  if (const int rc = for_each_state<PoseStateDev>(c, c->p_w.state, c->p_n, [&](const PoseStateDev& s) { a += s.pt_iters; b2 += s.seg_iters; })) return rc;
   if (pt_iters) *pt_iters = a;
   if (seg_iters) *seg_iters = b2;
   return PLSVO_OK;
@@ -1619,48 +1511,35 @@ extern "C" int plsvo_structure_optimize(plsvo_ctx* c, const plsvo_structopt_in* 
     return fail(c, PLSVO_E_INVALID, "structure_optimize: bad observation tables");
   for (int i = 0; i < npo; ++i) if (in->pt_obs_frame[i] < 0 || in->pt_obs_frame[i] >= in->n_frames) return fail(c, PLSVO_E_INVALID, "structure_optimize: frame index out of range");
   for (int i = 0; i < nso; ++i) if (in->seg_obs_frame[i] < 0 || in->seg_obs_frame[i] >= in->n_frames) return fail(c, PLSVO_E_INVALID, "structure_optimize: frame index out of range");
-  // one packed upload: doubles first, then ints
-  std::vector<double> d;
-  auto putd = [&](const double* p, size_t n) { const size_t o = d.size(); if (n) d.insert(d.end(), p, p + n); return o; };
-  const size_t o_T = putd(in->frame_T, (size_t)in->n_frames * 7), o_pp = putd(in->pt_pos, (size_t)np * 3), o_pf = putd(in->pt_obs_f, (size_t)npo * 3);
-  const size_t o_ss = putd(in->seg_spos, (size_t)ns * 3), o_se = putd(in->seg_epos, (size_t)ns * 3);
-  const size_t o_sf = putd(in->seg_obs_sf, (size_t)nso * 3), o_ef = putd(in->seg_obs_ef, (size_t)nso * 3);
-  std::vector<int> iv;
-  auto puti = [&](const int32_t* p, size_t n) { const size_t o = iv.size(); if (n) iv.insert(iv.end(), p, p + n); return o; };
-  const size_t o_po = puti(in->pt_obs_off, np > 0 ? (size_t)np + 1 : 0), o_pfr = puti(in->pt_obs_frame, (size_t)npo);
-  const size_t o_so = puti(in->seg_obs_off, ns > 0 ? (size_t)ns + 1 : 0), o_sfr = puti(in->seg_obs_frame, (size_t)nso);
-  const size_t dbytes = (d.size() + 1) * sizeof(double), ibytes = (iv.size() + 1) * sizeof(int);
-  HIP_TRY(c, c->s_d_in.ensure(dbytes + ibytes));
-  HIP_TRY(c, hipMemcpyAsync(c->s_d_in.p, d.data(), d.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  if (!iv.empty()) HIP_TRY(c, hipMemcpyAsync(reinterpret_cast<char*>(c->s_d_in.p) + dbytes, iv.data(), iv.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  const size_t out_d = (size_t)(np + 2 * ns) * 3, out_i = (size_t)(np + ns);
-  HIP_TRY(c, c->s_d_out.ensure((out_d + 1) * sizeof(double) + (out_i + 1) * sizeof(int)));
-  const double* dd = c->s_d_in.as<double>();
-  const int* di = reinterpret_cast<const int*>(reinterpret_cast<const char*>(c->s_d_in.p) + dbytes);
-  double* od = c->s_d_out.as<double>();
-  int* oi = reinterpret_cast<int*>(reinterpret_cast<char*>(c->s_d_out.p) + (out_d + 1) * sizeof(double));
+  const size_t NP = (size_t)np, NS = (size_t)ns;
+  Blob blob;
+  const size_t b_T = blob.add(in->frame_T, (size_t)in->n_frames * 7), b_pp = blob.add(in->pt_pos, NP * 3), b_pf = blob.add(in->pt_obs_f, (size_t)npo * 3),
+               b_ss = blob.add(in->seg_spos, NS * 3), b_se = blob.add(in->seg_epos, NS * 3), b_sf = blob.add(in->seg_obs_sf, (size_t)nso * 3),
+               b_ef = blob.add(in->seg_obs_ef, (size_t)nso * 3), b_po = blob.add(in->pt_obs_off, np > 0 ? NP + 1 : 0), b_pfr = blob.add(in->pt_obs_frame, (size_t)npo),
+               b_so = blob.add(in->seg_obs_off, ns > 0 ? NS + 1 : 0), b_sfr = blob.add(in->seg_obs_frame, (size_t)nso);
+  if (const int rc = upload_blob(c, c->s_d_in, blob)) return rc;
+  Carver cv;
+  const size_t o_pp = cv.take<double>(NP * 3), o_ss = cv.take<double>(NS * 3), o_se = cv.take<double>(NS * 3), o_pi = cv.take<int>(NP), o_si = cv.take<int>(NS);
+  HIP_TRY(c, c->s_d_out.ensure(cv.off + 256));
+  const DevBuf& din = c->s_d_in; const DevBuf& dout = c->s_d_out;
   StructBatchDev s{};
-  s.frame_T = dd + o_T; s.pt_pos = dd + o_pp; s.pt_obs_f = dd + o_pf; s.seg_spos = dd + o_ss; s.seg_epos = dd + o_se;
-  s.seg_obs_sf = dd + o_sf; s.seg_obs_ef = dd + o_ef;
-  s.pt_obs_off = di + o_po; s.pt_obs_frame = di + o_pfr; s.seg_obs_off = di + o_so; s.seg_obs_frame = di + o_sfr;
-  s.pt_pos_out = od; s.seg_spos_out = od + (size_t)np * 3; s.seg_epos_out = od + (size_t)(np + ns) * 3;
-  s.pt_iters = oi; s.seg_iters = oi + np;
+  s.frame_T = Blob::dev<double>(din, b_T); s.pt_pos = Blob::dev<double>(din, b_pp); s.pt_obs_f = Blob::dev<double>(din, b_pf);
+  s.seg_spos = Blob::dev<double>(din, b_ss); s.seg_epos = Blob::dev<double>(din, b_se);
+  s.seg_obs_sf = Blob::dev<double>(din, b_sf); s.seg_obs_ef = Blob::dev<double>(din, b_ef);
+  s.pt_obs_off = Blob::dev<int>(din, b_po); s.pt_obs_frame = Blob::dev<int>(din, b_pfr); s.seg_obs_off = Blob::dev<int>(din, b_so); s.seg_obs_frame = Blob::dev<int>(din, b_sfr);
+  s.pt_pos_out = Carver::dev<double>(dout, o_pp); s.seg_spos_out = Carver::dev<double>(dout, o_ss); s.seg_epos_out = Carver::dev<double>(dout, o_se);
+  s.pt_iters = Carver::dev<int>(dout, o_pi); s.seg_iters = Carver::dev<int>(dout, o_si);
   s.n_pts = np; s.n_seg = ns; s.n_iter_pts = in->n_iter_pts; s.n_iter_segs = in->n_iter_segs;
-  {
-    EventPair ep{}; prof_begin(c, PLSVO_K_STRUCTOPT, &ep);
-    HIP_TRY(c, launch_structopt(s, c->stream));
-    prof_end(c, PLSVO_K_STRUCTOPT, &ep);
-  }
-  std::vector<double> hd(out_d + 1);
-  std::vector<int> hi(out_i + 1);
-  HIP_TRY(c, hipMemcpyAsync(hd.data(), od, out_d * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(hi.data(), oi, out_i * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (out->pt_pos && np) memcpy(out->pt_pos, hd.data(), (size_t)np * 3 * sizeof(double));
-  if (out->seg_spos && ns) memcpy(out->seg_spos, hd.data() + (size_t)np * 3, (size_t)ns * 3 * sizeof(double));
-  if (out->seg_epos && ns) memcpy(out->seg_epos, hd.data() + (size_t)(np + ns) * 3, (size_t)ns * 3 * sizeof(double));
-  if (out->pt_iters && np) memcpy(out->pt_iters, hi.data(), (size_t)np * sizeof(int));
-  if (out->seg_iters && ns) memcpy(out->seg_iters, hi.data() + np, (size_t)ns * sizeof(int));
+  HIP_TRY_TIMED(c, PLSVO_K_STRUCTOPT, launch_structopt(s, c->stream));
+  Readback rb;
+  const int r_pp = rb.add(s.pt_pos_out, NP * 3 * sizeof(double)), r_ss = rb.add(s.seg_spos_out, NS * 3 * sizeof(double)), r_se = rb.add(s.seg_epos_out, NS * 3 * sizeof(double)),
+            r_pi = rb.add(s.pt_iters, NP * sizeof(int)), r_si = rb.add(s.seg_iters, NS * sizeof(int));
+  if (const int rc = rb.wait(c)) return rc;
+  if (out->pt_pos && np) memcpy(out->pt_pos, rb.at<double>(r_pp), NP * 3 * sizeof(double));
+  if (out->seg_spos && ns) memcpy(out->seg_spos, rb.at<double>(r_ss), NS * 3 * sizeof(double));
+  if (out->seg_epos && ns) memcpy(out->seg_epos, rb.at<double>(r_se), NS * 3 * sizeof(double));
+  if (out->pt_iters && np) memcpy(out->pt_iters, rb.at<int>(r_pi), NP * sizeof(int));
+  if (out->seg_iters && ns) memcpy(out->seg_iters, rb.at<int>(r_si), NS * sizeof(int));
   return PLSVO_OK;
 }
 
@@ -1671,13 +1550,12 @@ extern "C" int plsvo_structure_solve3(plsvo_ctx* c, int32_t n, const double* A, 
   if (n == 0) return PLSVO_OK;
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t na = (size_t)n * 9, nb = (size_t)n * 3;
-  HIP_TRY(c, c->s_d_in.ensure((na + nb) * sizeof(double)));
+  Blob blob;
+  const size_t b_A = blob.add(A, na), b_b = blob.add(b, nb);
+  if (const int rc = upload_blob(c, c->s_d_in, blob)) return rc;
   HIP_TRY(c, c->s_d_out.ensure(nb * sizeof(double)));
-  double* dA = c->s_d_in.as<double>();
-  HIP_TRY(c, hipMemcpyAsync(dA, A, na * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(dA + na, b, nb * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, launch_structopt_solve3(dA, dA + na, c->s_d_out.as<double>(), n, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(x, c->s_d_out.as<double>(), nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, launch_structopt_solve3(Blob::dev<double>(c->s_d_in, b_A), Blob::dev<double>(c->s_d_in, b_b), c->s_d_out.as<double>(), n, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(x, c->s_d_out.p, nb * sizeof(double), hipMemcpyDeviceToHost, c->stream));   // (one whole range into the caller's own buffer: a plain copy)
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return PLSVO_OK;
 }
@@ -1707,65 +1585,50 @@ static int match_run(plsvo_ctx* c, const plsvo_match_in* in, plsvo_match_out* ou
   }
   if (any_edgelet && !in->ref_grad) return fail(c, PLSVO_E_INVALID, "match_direct: edgelets without ref_grad");
   HIP_TRY(c, hipSetDevice(c->device));
-  // one packed upload: doubles, then ints, then bytes
-  std::vector<double> d;
-  auto putd = [&](const double* p, size_t k) { const size_t o = d.size(); if (p) d.insert(d.end(), p, p + k); else d.resize(d.size() + k, 0.0); return o; };
-  const size_t o_T = putd(in->frame_T, (size_t)nf * 7), o_px = putd(in->ref_px, (size_t)n * 2), o_f = putd(in->ref_f, (size_t)n * 3);
-  const size_t o_g = putd(in->ref_grad, (size_t)n * 2), o_pos = putd(in->pos, (size_t)n * 3), o_pc = putd(in->px_cur, (size_t)n * 2);
-  std::vector<int> iv;
-  auto puti = [&](const int32_t* p, size_t k) { const size_t o = iv.size(); iv.insert(iv.end(), p, p + k); return o; };
-  const size_t o_slot = puti(in->frame_slot, (size_t)nf), o_cf = puti(in->cur_frame, (size_t)n), o_rf = puti(in->ref_frame, (size_t)n), o_lv = puti(in->ref_level, (size_t)n);
-  const size_t dbytes = d.size() * sizeof(double), ibytes = ((iv.size() * sizeof(int) + 15) / 16) * 16, bbytes = (size_t)n;
-  HIP_TRY(c, c->s_d_in.ensure(dbytes + ibytes + bbytes + 16));
-  char* din = reinterpret_cast<char*>(c->s_d_in.p);
-  HIP_TRY(c, hipMemcpyAsync(din, d.data(), dbytes, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(din + dbytes, iv.data(), iv.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(din + dbytes + ibytes, in->ref_type, bbytes, hipMemcpyHostToDevice, c->stream));
-  const size_t out_d = (size_t)n * 2 * sizeof(double), out_i = (size_t)n * 2 * sizeof(int), out_b = (size_t)n;
+  const size_t N = (size_t)n;
+  Blob blob;
+  const size_t b_T = blob.add(in->frame_T, (size_t)nf * 7), b_px = blob.add(in->ref_px, N * 2), b_f = blob.add(in->ref_f, N * 3), b_g = blob.add(in->ref_grad, N * 2),   // (no ref_grad: zeros)
+               b_pos = blob.add(in->pos, N * 3), b_pc = blob.add(in->px_cur, N * 2), b_slot = blob.add(in->frame_slot, (size_t)nf), b_cf = blob.add(in->cur_frame, N),
+               b_rf = blob.add(in->ref_frame, N), b_lv = blob.add(in->ref_level, N), b_ty = blob.add(in->ref_type, N);
+  if (const int rc = upload_blob(c, c->s_d_in, blob)) return rc;
+  Carver cv;
+  const size_t o_px = cv.take<double>(N * 2), o_lv = cv.take<int>(N), o_it = cv.take<int>(N), o_found = cv.take<uint8_t>(N);
   // the diagnostic view appends: A (4 doubles), then warped, staged, patch (100 bytes) per candidate
-  const size_t o_dA = (out_d + out_i + out_b + 15) / 16 * 16, diag_A = (size_t)n * 4 * sizeof(double), diag_b = (size_t)n * (2 + kWarpPatchBytes);
-  HIP_TRY(c, c->s_d_out.ensure((wout ? o_dA + diag_A + diag_b : out_d + out_i + out_b) + 16));
-  char* dout = reinterpret_cast<char*>(c->s_d_out.p);
-  const double* dd = reinterpret_cast<const double*>(din);
-  const int* di = reinterpret_cast<const int*>(din + dbytes);
+  const size_t o_A = wout ? cv.take<double>(N * 4) : 0, o_wp = wout ? cv.take<uint8_t>(N) : 0, o_st = wout ? cv.take<uint8_t>(N) : 0, o_pa = wout ? cv.take<uint8_t>(N * kWarpPatchBytes) : 0;
+  HIP_TRY(c, c->s_d_out.ensure(cv.off + 256));
+  const DevBuf& din = c->s_d_in; const DevBuf& dout = c->s_d_out;
   MatchBatchDev b{};
   b.pyr_base = c->pyr.base; b.slot_bytes = c->pyr.slot_bytes; b.width = c->pyr.w[0]; b.height = c->pyr.h[0];
   b.fx = in->cam.fx; b.fy = in->cam.fy; b.cx = in->cam.cx; b.cy = in->cam.cy; b.cam_width = in->cam.width; b.cam_height = in->cam.height;
   b.n = n; b.n_pyr_levels = in->n_pyr_levels; b.align_max_iter = in->align_max_iter;
-  b.frame_T = dd + o_T; b.ref_px = dd + o_px; b.ref_f = dd + o_f; b.ref_grad = dd + o_g; b.pos = dd + o_pos; b.px_cur = dd + o_pc;
-  b.frame_slot = di + o_slot; b.cur_frame = di + o_cf; b.ref_frame = di + o_rf; b.ref_level = di + o_lv;
-  b.ref_type = reinterpret_cast<const uint8_t*>(din + dbytes + ibytes);
-  b.px_out = reinterpret_cast<double*>(dout);
-  b.search_level = reinterpret_cast<int*>(dout + out_d); b.n_iter = b.search_level + n;
-  b.found = reinterpret_cast<uint8_t*>(dout + out_d + out_i);
+  b.frame_T = Blob::dev<double>(din, b_T); b.ref_px = Blob::dev<double>(din, b_px); b.ref_f = Blob::dev<double>(din, b_f); b.ref_grad = Blob::dev<double>(din, b_g);
+  b.pos = Blob::dev<double>(din, b_pos); b.px_cur = Blob::dev<double>(din, b_pc);
+  b.frame_slot = Blob::dev<int>(din, b_slot); b.cur_frame = Blob::dev<int>(din, b_cf); b.ref_frame = Blob::dev<int>(din, b_rf); b.ref_level = Blob::dev<int>(din, b_lv);
+  b.ref_type = Blob::dev<uint8_t>(din, b_ty);
+  b.px_out = Carver::dev<double>(dout, o_px); b.search_level = Carver::dev<int>(dout, o_lv); b.n_iter = Carver::dev<int>(dout, o_it); b.found = Carver::dev<uint8_t>(dout, o_found);
+  Readback rb;
   if (wout) {
-    HIP_TRY(c, hipMemsetAsync(dout + o_dA, 0, diag_A + diag_b, c->stream));
-    b.diag_A = reinterpret_cast<double*>(dout + o_dA);
-    b.diag_warped = reinterpret_cast<uint8_t*>(dout + o_dA + diag_A); b.diag_staged = b.diag_warped + n; b.diag_patch = b.diag_staged + n;
+    HIP_TRY(c, hipMemsetAsync(Carver::dev<uint8_t>(dout, o_A), 0, cv.off - o_A, c->stream));
+    b.diag_A = Carver::dev<double>(dout, o_A);
+    b.diag_warped = Carver::dev<uint8_t>(dout, o_wp); b.diag_staged = Carver::dev<uint8_t>(dout, o_st); b.diag_patch = Carver::dev<uint8_t>(dout, o_pa);
     HIP_TRY(c, launch_match_warp_patches(b, c->stream));
-    std::vector<char> h(o_dA + diag_A + diag_b);
-    HIP_TRY(c, hipMemcpyAsync(h.data(), dout, h.size(), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const char* hb = h.data() + o_dA + diag_A;
-    if (wout->A) memcpy(wout->A, h.data() + o_dA, diag_A);
-    if (wout->search_level) memcpy(wout->search_level, h.data() + out_d, (size_t)n * sizeof(int));
-    if (wout->warped) memcpy(wout->warped, hb, (size_t)n);
-    if (wout->staged) memcpy(wout->staged, hb + n, (size_t)n);
-    if (wout->patch) memcpy(wout->patch, hb + 2 * (size_t)n, (size_t)n * kWarpPatchBytes);
+    const int r_A = rb.add(b.diag_A, N * 4 * sizeof(double)), r_lv = rb.add(b.search_level, N * sizeof(int)), r_wp = rb.add(b.diag_warped, N), r_st = rb.add(b.diag_staged, N),
+              r_pa = rb.add(b.diag_patch, N * kWarpPatchBytes);
+    if (const int rc = rb.wait(c)) return rc;
+    if (wout->A) memcpy(wout->A, rb.at<double>(r_A), N * 4 * sizeof(double));
+    if (wout->search_level) memcpy(wout->search_level, rb.at<int>(r_lv), N * sizeof(int));
+    if (wout->warped) memcpy(wout->warped, rb.at<uint8_t>(r_wp), N);
+    if (wout->staged) memcpy(wout->staged, rb.at<uint8_t>(r_st), N);
+    if (wout->patch) memcpy(wout->patch, rb.at<uint8_t>(r_pa), N * kWarpPatchBytes);
     return PLSVO_OK;
   }
-  {
-    EventPair ep{}; prof_begin(c, PLSVO_K_MATCH, &ep);
-    HIP_TRY(c, launch_match_direct(b, c->stream));
-    prof_end(c, PLSVO_K_MATCH, &ep);
-  }
-  std::vector<char> h(out_d + out_i + out_b);
-  HIP_TRY(c, hipMemcpyAsync(h.data(), dout, h.size(), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (out->px_cur) memcpy(out->px_cur, h.data(), out_d);
-  if (out->search_level) memcpy(out->search_level, h.data() + out_d, (size_t)n * sizeof(int));
-  if (out->n_iter) memcpy(out->n_iter, h.data() + out_d + (size_t)n * sizeof(int), (size_t)n * sizeof(int));
-  if (out->found) memcpy(out->found, h.data() + out_d + out_i, out_b);
+  HIP_TRY_TIMED(c, PLSVO_K_MATCH, launch_match_direct(b, c->stream));
+  const int r_px = rb.add(b.px_out, N * 2 * sizeof(double)), r_lv = rb.add(b.search_level, N * sizeof(int)), r_it = rb.add(b.n_iter, N * sizeof(int)), r_found = rb.add(b.found, N);
+  if (const int rc = rb.wait(c)) return rc;
+  if (out->px_cur) memcpy(out->px_cur, rb.at<double>(r_px), N * 2 * sizeof(double));
+  if (out->search_level) memcpy(out->search_level, rb.at<int>(r_lv), N * sizeof(int));
+  if (out->n_iter) memcpy(out->n_iter, rb.at<int>(r_it), N * sizeof(int));
+  if (out->found) memcpy(out->found, rb.at<uint8_t>(r_found), N);
   return PLSVO_OK;
 }
 
@@ -1791,31 +1654,24 @@ extern "C" int plsvo_reproject(plsvo_ctx* c, const plsvo_reproject_in* in, plsvo
   if (nf <= 0 || !in->frame_T || !in->frame || !in->pos) return fail(c, PLSVO_E_INVALID, "reproject: null input array");
   for (int i = 0; i < n; ++i) if (in->frame[i] < 0 || in->frame[i] >= nf) return fail(c, PLSVO_E_INVALID, "reproject: frame index out of range");
   HIP_TRY(c, hipSetDevice(c->device));
-  const size_t dT = (size_t)nf * 7, dP = (size_t)n * 3;
-  const size_t dbytes = (dT + dP) * sizeof(double), ibytes = (size_t)n * sizeof(int);
-  HIP_TRY(c, c->s_d_in.ensure(dbytes + ibytes + 16));
-  char* din = reinterpret_cast<char*>(c->s_d_in.p);
-  HIP_TRY(c, hipMemcpyAsync(din, in->frame_T, dT * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(din + dT * sizeof(double), in->pos, dP * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(din + dbytes, in->frame, ibytes, hipMemcpyHostToDevice, c->stream));
-  const size_t out_d = (size_t)n * 2 * sizeof(double), out_i = (size_t)n * sizeof(int);
-  HIP_TRY(c, c->s_d_out.ensure(out_d + out_i + 16));
-  char* dout = reinterpret_cast<char*>(c->s_d_out.p);
+  const size_t N = (size_t)n;
+  Blob blob;
+  const size_t b_T = blob.add(in->frame_T, (size_t)nf * 7), b_pos = blob.add(in->pos, N * 3), b_fr = blob.add(in->frame, N);
+  if (const int rc = upload_blob(c, c->s_d_in, blob)) return rc;
+  Carver cv;
+  const size_t o_px = cv.take<double>(N * 2), o_cell = cv.take<int>(N);
+  HIP_TRY(c, c->s_d_out.ensure(cv.off + 256));
   ReprojBatchDev b{};
   b.fx = in->cam.fx; b.fy = in->cam.fy; b.cx = in->cam.cx; b.cy = in->cam.cy; b.cam_width = in->cam.width; b.cam_height = in->cam.height;
   b.n = n; b.cell_size = in->cell_size; b.grid_n_cols = in->grid_n_cols; b.boundary = in->boundary;
-  b.frame_T = reinterpret_cast<const double*>(din); b.pos = b.frame_T + dT; b.frame = reinterpret_cast<const int*>(din + dbytes);
-  b.px = reinterpret_cast<double*>(dout); b.cell = reinterpret_cast<int*>(dout + out_d);
-  {
-    EventPair ep{}; prof_begin(c, PLSVO_K_MATCH, &ep);
-    HIP_TRY(c, launch_reproject(b, c->stream));
-    prof_end(c, PLSVO_K_MATCH, &ep);
-  }
-  std::vector<char> h(out_d + out_i);
-  HIP_TRY(c, hipMemcpyAsync(h.data(), dout, h.size(), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (out->px) memcpy(out->px, h.data(), out_d);
-  if (out->cell) memcpy(out->cell, h.data() + out_d, out_i);
+  b.frame_T = Blob::dev<double>(c->s_d_in, b_T); b.pos = Blob::dev<double>(c->s_d_in, b_pos); b.frame = Blob::dev<int>(c->s_d_in, b_fr);
+  b.px = Carver::dev<double>(c->s_d_out, o_px); b.cell = Carver::dev<int>(c->s_d_out, o_cell);
+  HIP_TRY_TIMED(c, PLSVO_K_MATCH, launch_reproject(b, c->stream));
+  Readback rb;
+  const int r_px = rb.add(b.px, N * 2 * sizeof(double)), r_cell = rb.add(b.cell, N * sizeof(int));
+  if (const int rc = rb.wait(c)) return rc;
+  if (out->px) memcpy(out->px, rb.at<double>(r_px), N * 2 * sizeof(double));
+  if (out->cell) memcpy(out->cell, rb.at<int>(r_cell), N * sizeof(int));
   return PLSVO_OK;
 }
 
@@ -1859,23 +1715,17 @@ extern "C" int plsvo_close_keyframes(plsvo_ctx* c, int n, const plsvo_close_kf_i
   Carver cv;
   const size_t o_tmp = cv.take<double>(total), o_idx = cv.take<int>(total), o_dist = cv.take<double>(total), o_cnt = cv.take<int>((size_t)n * 2);
   HIP_TRY(c, c->s_d_out.ensure(cv.off + 256));
-  char* din = reinterpret_cast<char*>(c->s_d_in.p); char* dout = reinterpret_cast<char*>(c->s_d_out.p);
+  const DevBuf& din = c->s_d_in; const DevBuf& dout = c->s_d_out;
   CloseKfBatchDev b{};
-  b.jobs = reinterpret_cast<const CloseKfJobDev*>(din + o_jobs); b.n_jobs = n;
-  b.kf_T = reinterpret_cast<const double*>(din + o_T); b.keypt_pos = reinterpret_cast<const double*>(din + o_kp);
-  b.keypt_valid = reinterpret_cast<const uint8_t*>(din + o_kv);
-  b.tmp_dist = reinterpret_cast<double*>(dout + o_tmp); b.close_idx = reinterpret_cast<int*>(dout + o_idx);
-  b.close_dist = reinterpret_cast<double*>(dout + o_dist); b.counts = reinterpret_cast<int*>(dout + o_cnt);
-  {
-    EventPair ep{}; prof_begin(c, PLSVO_K_KEYFRAME, &ep);
-    HIP_TRY(c, launch_close_keyframes(b, c->stream));
-    prof_end(c, PLSVO_K_KEYFRAME, &ep);
-  }
-  std::vector<char> h(cv.off);
-  HIP_TRY(c, hipMemcpyAsync(h.data(), dout, h.size(), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const int* h_idx = reinterpret_cast<const int*>(h.data() + o_idx); const double* h_dist = reinterpret_cast<const double*>(h.data() + o_dist);
-  const int* h_cnt = reinterpret_cast<const int*>(h.data() + o_cnt);
+  b.jobs = Blob::dev<CloseKfJobDev>(din, o_jobs); b.n_jobs = n;
+  b.kf_T = Blob::dev<double>(din, o_T); b.keypt_pos = Blob::dev<double>(din, o_kp); b.keypt_valid = Blob::dev<uint8_t>(din, o_kv);
+  b.tmp_dist = Carver::dev<double>(dout, o_tmp); b.close_idx = Carver::dev<int>(dout, o_idx);
+  b.close_dist = Carver::dev<double>(dout, o_dist); b.counts = Carver::dev<int>(dout, o_cnt);
+  HIP_TRY_TIMED(c, PLSVO_K_KEYFRAME, launch_close_keyframes(b, c->stream));
+  Readback rb;   // (the scratch row tmp_dist stays on the device)
+  const int r_idx = rb.add(b.close_idx, total * sizeof(int)), r_dist = rb.add(b.close_dist, total * sizeof(double)), r_cnt = rb.add(b.counts, (size_t)n * 2 * sizeof(int));
+  if ((rc = rb.wait(c))) return rc;
+  const int* h_idx = rb.at<int>(r_idx); const double* h_dist = rb.at<double>(r_dist); const int* h_cnt = rb.at<int>(r_cnt);
   for (int i = 0; i < n; ++i) {
     const size_t at = (size_t)blob.at<CloseKfJobDev>(o_jobs)[(size_t)i].kf_off;
     const int nc = h_cnt[2 * i];
@@ -1943,31 +1793,24 @@ extern "C" int plsvo_keyframe_decide(plsvo_ctx* c, int n, const plsvo_kf_decide_
   }
   int rc;
   if ((rc = upload_blob(c, c->s_d_in, blob))) return rc;
-  Carver cv;   // results first (what travels back), the depth rows behind them
+  Carver cv;
   const size_t r_out = cv.take<KfDecideOutDev>((size_t)n), r_dt = cv.take<double>(t_ov), r_dr = cv.take<double>(t_ov);
-  const size_t fetch_bytes = cv.off;
   const size_t r_keys = cv.take<unsigned long long>(o_depth);
   HIP_TRY(c, c->s_d_out.ensure(cv.off + 256));
-  char* din = reinterpret_cast<char*>(c->s_d_in.p); char* dout = reinterpret_cast<char*>(c->s_d_out.p);
+  const DevBuf& din = c->s_d_in; const DevBuf& dout = c->s_d_out;
   KfDecideBatchDev b{};
-  b.jobs = reinterpret_cast<const KfDecideJobDev*>(din + b_jobs); b.out = reinterpret_cast<KfDecideOutDev*>(dout + r_out); b.n_jobs = n;
-  b.pt_px = reinterpret_cast<const double*>(din + b_px); b.pt_pos = reinterpret_cast<const double*>(din + b_pos);
-  b.pt_alive = reinterpret_cast<const uint8_t*>(din + b_pa);
-  b.seg_spos = reinterpret_cast<const double*>(din + b_sp); b.seg_epos = reinterpret_cast<const double*>(din + b_ep);
-  b.seg_alive = reinterpret_cast<const uint8_t*>(din + b_sa);
-  b.kf_T = reinterpret_cast<const double*>(din + b_kf); b.overlap_idx = reinterpret_cast<const int*>(din + b_ov);
-  b.depth_keys = reinterpret_cast<unsigned long long*>(dout + r_keys);
-  b.delta_t = reinterpret_cast<double*>(dout + r_dt); b.delta_r = reinterpret_cast<double*>(dout + r_dr);
-  {
-    EventPair ep{}; prof_begin(c, PLSVO_K_KEYFRAME, &ep);
-    HIP_TRY(c, launch_keyframe_decide(b, c->stream));
-    prof_end(c, PLSVO_K_KEYFRAME, &ep);
-  }
-  std::vector<char> h(fetch_bytes);
-  HIP_TRY(c, hipMemcpyAsync(h.data(), dout, h.size(), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const KfDecideOutDev* ho = reinterpret_cast<const KfDecideOutDev*>(h.data() + r_out);
-  const double* h_dt = reinterpret_cast<const double*>(h.data() + r_dt); const double* h_dr = reinterpret_cast<const double*>(h.data() + r_dr);
+  b.jobs = Blob::dev<KfDecideJobDev>(din, b_jobs); b.out = Carver::dev<KfDecideOutDev>(dout, r_out); b.n_jobs = n;
+  b.pt_px = Blob::dev<double>(din, b_px); b.pt_pos = Blob::dev<double>(din, b_pos); b.pt_alive = Blob::dev<uint8_t>(din, b_pa);
+  b.seg_spos = Blob::dev<double>(din, b_sp); b.seg_epos = Blob::dev<double>(din, b_ep); b.seg_alive = Blob::dev<uint8_t>(din, b_sa);
+  b.kf_T = Blob::dev<double>(din, b_kf); b.overlap_idx = Blob::dev<int>(din, b_ov);
+  b.depth_keys = Carver::dev<unsigned long long>(dout, r_keys);
+  b.delta_t = Carver::dev<double>(dout, r_dt); b.delta_r = Carver::dev<double>(dout, r_dr);
+  HIP_TRY_TIMED(c, PLSVO_K_KEYFRAME, launch_keyframe_decide(b, c->stream));
+  Readback rb;   // (the depth rows stay on the device)
+  const int h_out = rb.add(b.out, (size_t)n * sizeof(KfDecideOutDev)), h_t = rb.add(b.delta_t, t_ov * sizeof(double)), h_r = rb.add(b.delta_r, t_ov * sizeof(double));
+  if ((rc = rb.wait(c))) return rc;
+  const KfDecideOutDev* ho = rb.at<KfDecideOutDev>(h_out);
+  const double* h_dt = rb.at<double>(h_t); const double* h_dr = rb.at<double>(h_r);
   for (int i = 0; i < n; ++i) {
     const KfDecideOutDev& o = ho[i];
     plsvo_kf_decide_out& O = out[i];
@@ -2114,17 +1957,16 @@ extern "C" int plsvo_chain_run(plsvo_ctx* c) {
   if (!c->ch_staged || !c->a_staged || c->a_n != c->ch_n) return fail(c, PLSVO_E_STATE, "chain_run: no staged frame step (or the alignment batch was re-staged since)");
   int rc = plsvo_align_run(c); if (rc) return rc;
   HIP_TRY(c, launch_chain_pose(c->ch_b, c->stream));
-  { EventPair ep{}; prof_begin(c, PLSVO_K_MATCH, &ep);
-    HIP_TRY(c, launch_reproject(c->ch_reproj, c->stream));
-    HIP_TRY(c, launch_chain_active(c->ch_b, c->stream));
-    HIP_TRY(c, launch_match_direct(c->ch_match, c->stream));
-    HIP_TRY(c, launch_chain_select(c->ch_b, c->stream));
-    prof_end(c, PLSVO_K_MATCH, &ep); }
+  const auto reproject_match_select = [&]() -> hipError_t {   // four launches timed as one: the first failure ends them
+    hipError_t e = launch_reproject(c->ch_reproj, c->stream);
+    if (e == hipSuccess) e = launch_chain_active(c->ch_b, c->stream);
+    if (e == hipSuccess) e = launch_match_direct(c->ch_match, c->stream);
+    return e != hipSuccess ? e : launch_chain_select(c->ch_b, c->stream);
+  };
+  HIP_TRY_TIMED(c, PLSVO_K_MATCH, reproject_match_select());
   const int threads = pose_opt_threads(c, c->ch_n, (long)c->ch_b.n_cand);   // (selected features <= candidates)
   c->p_refill_frames = 0;   // (the chain's jobs are written on the device: the host cannot see whether one has a refinement loop -- pose_opt_rows_kernel)
-  EventPair ep{}; prof_begin(c, PLSVO_K_POSEOPT, &ep);
-  HIP_TRY(c, launch_pose_opt(c->ch_pose, c->ch_w.poses.as<double>(), threads, c->opt_poseopt_select ? 1 : 0, c->stream));
-  prof_end(c, PLSVO_K_POSEOPT, &ep);
+  HIP_TRY_TIMED(c, PLSVO_K_POSEOPT, launch_pose_opt(c->ch_pose, c->ch_w.poses.as<double>(), threads, c->opt_poseopt_select ? 1 : 0, c->stream));
   c->ch_run_seq = ++c->run_seq;
   return PLSVO_OK;
 }
@@ -2140,42 +1982,27 @@ extern "C" int plsvo_chain_fetch(plsvo_ctx* c, int n, plsvo_chain_out* out) {
   for (int j = 0; j < n; ++j) ao[(size_t)j].seg_alive_out = out[j].align.seg_alive_out;
   int rc = plsvo_align_fetch(c, n, ao.data()); if (rc) return rc;
   const size_t NC = (size_t)c->ch_ncand, NP = (size_t)c->ch_npt_cap, NS = (size_t)c->ch_nseg_cap;
-  std::vector<PoseStateDev> st((size_t)n);
-  std::vector<uint8_t> found(std::max(NC, (size_t)1)), pk(std::max(NP, (size_t)1)), sk(std::max(NS, (size_t)1));
-  std::vector<double> mpx(std::max(NC * 2, (size_t)1));
-  std::vector<int> slev(std::max(NC, (size_t)1)), selp(std::max(NP, (size_t)1)), sels(std::max(NS, (size_t)1)), nsel((size_t)n * 2);
   const ChainBatchDev& b = c->ch_b;
-  HIP_TRY(c, hipMemcpyAsync(st.data(), c->ch_w.state.p, (size_t)n * sizeof(PoseStateDev), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(nsel.data(), b.n_sel, (size_t)n * 2 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  if (NC) {
-    HIP_TRY(c, hipMemcpyAsync(found.data(), b.found, NC, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(mpx.data(), b.m_px, NC * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(slev.data(), b.search_level, NC * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  }
-  if (NP) {
-    HIP_TRY(c, hipMemcpyAsync(pk.data(), c->ch_w.ptkeep.p, NP, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(selp.data(), b.sel_pt, NP * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  }
-  if (NS) {
-    HIP_TRY(c, hipMemcpyAsync(sk.data(), c->ch_w.segkeep.p, NS, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(sels.data(), b.sel_seg, NS * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  Readback rb;   // (behind the alignment's fetch, whose views have been consumed into ao)
+  const int r_st = rb.add(c->ch_w.state.p, (size_t)n * sizeof(PoseStateDev)), r_nsel = rb.add(b.n_sel, (size_t)n * 2 * sizeof(int)), r_found = rb.add(b.found, NC),
+            r_mpx = rb.add(b.m_px, NC * 2 * sizeof(double)), r_slev = rb.add(b.search_level, NC * sizeof(int)), r_pk = rb.add(c->ch_w.ptkeep.p, NP),
+            r_selp = rb.add(b.sel_pt, NP * sizeof(int)), r_sk = rb.add(c->ch_w.segkeep.p, NS), r_sels = rb.add(b.sel_seg, NS * sizeof(int));
+  if ((rc = rb.wait(c))) return rc;
+  const PoseStateDev* st = rb.at<PoseStateDev>(r_st); const int* nsel = rb.at<int>(r_nsel);
   for (int j = 0; j < n; ++j) {
     const ChainJobDev& J = c->ch_jobs[(size_t)j];
-    const PoseStateDev& s = st[(size_t)j];
     plsvo_chain_out& o = out[j];
     o.align = ao[(size_t)j];
-    pose_state_to_out(s, o.pose);
+    pose_state_to_out(st[j], o.pose);
     o.n_sel_pt = nsel[(size_t)j * 2]; o.n_sel_seg = nsel[(size_t)j * 2 + 1];
     const int nc = J.n_pt + 2 * J.n_seg;
-    if (o.pose.pt_keep && o.n_sel_pt > 0) memcpy(o.pose.pt_keep, pk.data() + J.po_pt_off, (size_t)o.n_sel_pt);
-    if (o.pose.seg_keep && o.n_sel_seg > 0) memcpy(o.pose.seg_keep, sk.data() + J.po_seg_off, (size_t)o.n_sel_seg);
-    if (o.found && nc) memcpy(o.found, found.data() + J.cand_off, (size_t)nc);
-    if (o.px && nc) memcpy(o.px, mpx.data() + 2 * (size_t)J.cand_off, (size_t)nc * 2 * sizeof(double));
-    if (o.search_level && nc) memcpy(o.search_level, slev.data() + J.cand_off, (size_t)nc * sizeof(int));
-    if (o.sel_pt && o.n_sel_pt > 0) memcpy(o.sel_pt, selp.data() + J.po_pt_off, (size_t)o.n_sel_pt * sizeof(int));
-    if (o.sel_seg && o.n_sel_seg > 0) memcpy(o.sel_seg, sels.data() + J.po_seg_off, (size_t)o.n_sel_seg * sizeof(int));
+    if (o.pose.pt_keep && o.n_sel_pt > 0) memcpy(o.pose.pt_keep, rb.at<uint8_t>(r_pk) + J.po_pt_off, (size_t)o.n_sel_pt);
+    if (o.pose.seg_keep && o.n_sel_seg > 0) memcpy(o.pose.seg_keep, rb.at<uint8_t>(r_sk) + J.po_seg_off, (size_t)o.n_sel_seg);
+    if (o.found && nc) memcpy(o.found, rb.at<uint8_t>(r_found) + J.cand_off, (size_t)nc);
+    if (o.px && nc) memcpy(o.px, rb.at<double>(r_mpx) + 2 * (size_t)J.cand_off, (size_t)nc * 2 * sizeof(double));
+    if (o.search_level && nc) memcpy(o.search_level, rb.at<int>(r_slev) + J.cand_off, (size_t)nc * sizeof(int));
+    if (o.sel_pt && o.n_sel_pt > 0) memcpy(o.sel_pt, rb.at<int>(r_selp) + J.po_pt_off, (size_t)o.n_sel_pt * sizeof(int));
+    if (o.sel_seg && o.n_sel_seg > 0) memcpy(o.sel_seg, rb.at<int>(r_sels) + J.po_seg_off, (size_t)o.n_sel_seg * sizeof(int));
   }
   return PLSVO_OK;
 }
@@ -2226,38 +2053,26 @@ extern "C" int plsvo_update_seeds(plsvo_ctx* c, const plsvo_seeds_in* in, plsvo_
     if (in->seg_level[i] < 0 || in->seg_level[i] >= c->pyr.n_levels) return fail(c, PLSVO_E_INVALID, "update_seeds: feature level outside the configured pyramid");
   }
   HIP_TRY(c, hipSetDevice(c->device));
-  // one packed upload per element type
-  std::vector<double> d; std::vector<int> iv; std::vector<float> fv;
-  auto putd = [&](const double* p, size_t k) { const size_t o = d.size(); if (p) d.insert(d.end(), p, p + k); else d.resize(d.size() + k, 0.0); return o; };
-  auto puti = [&](const int32_t* p, size_t k) { const size_t o = iv.size(); iv.insert(iv.end(), p, p + k); return o; };
-  auto putf = [&](const float* p, size_t k) { const size_t o = fv.size(); fv.insert(fv.end(), p, p + k); return o; };
   const size_t NP = (size_t)np, NS = (size_t)ns;
-  const size_t o_T = putd(in->frame_T, (size_t)nf * 7), o_ppx = putd(in->pt_px, NP * 2), o_pf = putd(in->pt_f, NP * 3), o_pg = putd(in->pt_grad, NP * 2);
-  const size_t o_spx = putd(in->seg_px, NS * 2), o_sf0 = putd(in->seg_f, NS * 3), o_ssf = putd(in->seg_sf, NS * 3), o_sef = putd(in->seg_ef, NS * 3);
-  const size_t o_slot = puti(in->frame_slot, (size_t)nf), o_prf = puti(in->pt_ref_frame, NP), o_pcf = puti(in->pt_cur_frame, NP), o_plv = puti(in->pt_level, NP);
-  const size_t o_srf = puti(in->seg_ref_frame, NS), o_scf = puti(in->seg_cur_frame, NS), o_slv = puti(in->seg_level, NS);
-  const size_t o_pa = putf(in->pt_a, NP), o_pb = putf(in->pt_b, NP), o_pmu = putf(in->pt_mu, NP), o_pzr = putf(in->pt_z_range, NP), o_ps2 = putf(in->pt_sigma2, NP);
-  const size_t o_sa = putf(in->seg_a, NS), o_sb = putf(in->seg_b, NS), o_smus = putf(in->seg_mu_s, NS), o_smue = putf(in->seg_mu_e, NS);
-  const size_t o_szrs = putf(in->seg_z_range_s, NS), o_szre = putf(in->seg_z_range_e, NS), o_ss2s = putf(in->seg_sigma2_s, NS), o_ss2e = putf(in->seg_sigma2_e, NS);
-  auto pad16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-  const size_t dbytes = pad16(d.size() * sizeof(double)), ibytes = pad16(iv.size() * sizeof(int)), fbytes = pad16(fv.size() * sizeof(float)), bbytes = pad16(NP);
-  HIP_TRY(c, c->s_d_in.ensure(dbytes + ibytes + fbytes + bbytes + 16));
-  char* din = reinterpret_cast<char*>(c->s_d_in.p);
-  HIP_TRY(c, hipMemcpyAsync(din, d.data(), d.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(din + dbytes, iv.data(), iv.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  if (!fv.empty()) HIP_TRY(c, hipMemcpyAsync(din + dbytes + ibytes, fv.data(), fv.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  if (np > 0) HIP_TRY(c, hipMemcpyAsync(din + dbytes + ibytes + fbytes, in->pt_type, NP, hipMemcpyHostToDevice, c->stream));
-  // outputs: doubles, then floats, then ints
+  Blob blob;
+  const size_t b_T = blob.add(in->frame_T, (size_t)nf * 7), b_ppx = blob.add(in->pt_px, NP * 2), b_pf = blob.add(in->pt_f, NP * 3), b_pg = blob.add(in->pt_grad, NP * 2),
+               b_spx = blob.add(in->seg_px, NS * 2), b_sf0 = blob.add(in->seg_f, NS * 3), b_ssf = blob.add(in->seg_sf, NS * 3), b_sef = blob.add(in->seg_ef, NS * 3),
+               b_slot = blob.add(in->frame_slot, (size_t)nf), b_prf = blob.add(in->pt_ref_frame, NP), b_pcf = blob.add(in->pt_cur_frame, NP), b_plv = blob.add(in->pt_level, NP),
+               b_srf = blob.add(in->seg_ref_frame, NS), b_scf = blob.add(in->seg_cur_frame, NS), b_slv = blob.add(in->seg_level, NS),
+               b_pa = blob.add(in->pt_a, NP), b_pb = blob.add(in->pt_b, NP), b_pmu = blob.add(in->pt_mu, NP), b_pzr = blob.add(in->pt_z_range, NP), b_ps2 = blob.add(in->pt_sigma2, NP),
+               b_sa = blob.add(in->seg_a, NS), b_sb = blob.add(in->seg_b, NS), b_smus = blob.add(in->seg_mu_s, NS), b_smue = blob.add(in->seg_mu_e, NS),
+               b_szrs = blob.add(in->seg_z_range_s, NS), b_szre = blob.add(in->seg_z_range_e, NS), b_ss2s = blob.add(in->seg_sigma2_s, NS), b_ss2e = blob.add(in->seg_sigma2_e, NS),
+               b_pty = blob.add(in->pt_type, NP);
+  if (const int rc = upload_blob(c, c->s_d_in, blob)) return rc;
+  // outputs: doubles, floats, ints -- one section per element type, the arrays of a type one behind the other
   const size_t od_n = NP * 6 + NS * 8, of_n = NP * 4 + NS * 6, oi_n = NP + NS;
-  const size_t od_b = pad16(od_n * sizeof(double)), of_b = pad16(of_n * sizeof(float)), oi_b = pad16(oi_n * sizeof(int));
-  HIP_TRY(c, c->s_d_out.ensure(od_b + of_b + oi_b + 16));
-  char* dout = reinterpret_cast<char*>(c->s_d_out.p);
-  const double* dd = reinterpret_cast<const double*>(din);
-  const int* di = reinterpret_cast<const int*>(din + dbytes);
-  const float* df = reinterpret_cast<const float*>(din + dbytes + ibytes);
-  double* od = reinterpret_cast<double*>(dout);
-  float* of = reinterpret_cast<float*>(dout + od_b);
-  int* oi = reinterpret_cast<int*>(dout + od_b + of_b);
+  Carver cv;
+  const size_t o_d = cv.take<double>(od_n), o_f = cv.take<float>(of_n), o_i = cv.take<int>(oi_n);
+  HIP_TRY(c, c->s_d_out.ensure(cv.off + 256));
+  const DevBuf& din = c->s_d_in;
+  double* od = Carver::dev<double>(c->s_d_out, o_d);
+  float* of = Carver::dev<float>(c->s_d_out, o_f);
+  int* oi = Carver::dev<int>(c->s_d_out, o_i);
   SeedsBatchDev b{};
   b.pyr_base = c->pyr.base; b.slot_bytes = c->pyr.slot_bytes; b.width = c->pyr.w[0]; b.height = c->pyr.h[0];
   b.fx = in->cam.fx; b.fy = in->cam.fy; b.cx = in->cam.cx; b.cy = in->cam.cy; b.cam_width = in->cam.width; b.cam_height = in->cam.height;
@@ -2266,14 +2081,17 @@ extern "C" int plsvo_update_seeds(plsvo_ctx* c, const plsvo_seeds_in* in, plsvo_
   b.px_error_angle = std::atan(in->px_noise / (2.0 * std::fabs(in->cam.fx))) * 2.0;   // depth_filter.cpp:279-280 (host libm, like the reference)
   b.convergence_sigma2_thresh = in->convergence_sigma2_thresh;
   b.n_pt = np; b.n_seg = ns;
-  b.frame_T = dd + o_T; b.frame_slot = di + o_slot;
-  b.pt_ref_frame = di + o_prf; b.pt_cur_frame = di + o_pcf; b.pt_level = di + o_plv; b.pt_px = dd + o_ppx; b.pt_f = dd + o_pf;
-  b.pt_grad = in->pt_grad ? dd + o_pg : nullptr; b.pt_type = reinterpret_cast<const uint8_t*>(din + dbytes + ibytes + fbytes);
-  b.pt_a = df + o_pa; b.pt_b = df + o_pb; b.pt_mu = df + o_pmu; b.pt_z_range = df + o_pzr; b.pt_sigma2 = df + o_ps2;
-  b.seg_ref_frame = di + o_srf; b.seg_cur_frame = di + o_scf; b.seg_level = di + o_slv;
-  b.seg_px = dd + o_spx; b.seg_f = dd + o_sf0; b.seg_sf = dd + o_ssf; b.seg_ef = dd + o_sef;
-  b.seg_a = df + o_sa; b.seg_b = df + o_sb; b.seg_mu_s = df + o_smus; b.seg_mu_e = df + o_smue; b.seg_z_range_s = df + o_szrs;
-  b.seg_z_range_e = df + o_szre; b.seg_sigma2_s = df + o_ss2s; b.seg_sigma2_e = df + o_ss2e;
+  const auto D = [&](size_t o) { return Blob::dev<double>(din, o); };
+  const auto I = [&](size_t o) { return Blob::dev<int>(din, o); };
+  const auto F = [&](size_t o) { return Blob::dev<float>(din, o); };
+  b.frame_T = D(b_T); b.frame_slot = I(b_slot);
+  b.pt_ref_frame = I(b_prf); b.pt_cur_frame = I(b_pcf); b.pt_level = I(b_plv); b.pt_px = D(b_ppx); b.pt_f = D(b_pf);
+  b.pt_grad = in->pt_grad ? D(b_pg) : nullptr; b.pt_type = Blob::dev<uint8_t>(din, b_pty);
+  b.pt_a = F(b_pa); b.pt_b = F(b_pb); b.pt_mu = F(b_pmu); b.pt_z_range = F(b_pzr); b.pt_sigma2 = F(b_ps2);
+  b.seg_ref_frame = I(b_srf); b.seg_cur_frame = I(b_scf); b.seg_level = I(b_slv);
+  b.seg_px = D(b_spx); b.seg_f = D(b_sf0); b.seg_sf = D(b_ssf); b.seg_ef = D(b_sef);
+  b.seg_a = F(b_sa); b.seg_b = F(b_sb); b.seg_mu_s = F(b_smus); b.seg_mu_e = F(b_smue); b.seg_z_range_s = F(b_szrs);
+  b.seg_z_range_e = F(b_szre); b.seg_sigma2_s = F(b_ss2s); b.seg_sigma2_e = F(b_ss2e);
   b.o_pt_xyz = od; b.o_pt_px = od + NP * 3; b.o_pt_depth = od + NP * 5;
   double* ods = od + NP * 6;
   b.o_seg_xyz_s = ods; b.o_seg_xyz_e = ods + NS * 3; b.o_seg_depth_s = ods + NS * 6; b.o_seg_depth_e = ods + NS * 7;
@@ -2281,17 +2099,13 @@ extern "C" int plsvo_update_seeds(plsvo_ctx* c, const plsvo_seeds_in* in, plsvo_
   float* ofs = of + NP * 4;
   b.o_seg_a = ofs; b.o_seg_b = ofs + NS; b.o_seg_mu_s = ofs + NS * 2; b.o_seg_mu_e = ofs + NS * 3; b.o_seg_sigma2_s = ofs + NS * 4; b.o_seg_sigma2_e = ofs + NS * 5;
   b.o_pt_status = oi; b.o_seg_status = oi + NP;
-  {
-    EventPair ep{}; prof_begin(c, PLSVO_K_SEEDS, &ep);
-    HIP_TRY(c, launch_update_seeds(b, c->stream));
-    prof_end(c, PLSVO_K_SEEDS, &ep);
-  }
-  std::vector<char> h(od_b + of_b + oi_b);
-  HIP_TRY(c, hipMemcpyAsync(h.data(), dout, h.size(), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const double* hd = reinterpret_cast<const double*>(h.data());
-  const float* hf = reinterpret_cast<const float*>(h.data() + od_b);
-  const int* hi = reinterpret_cast<const int*>(h.data() + od_b + of_b);
+  HIP_TRY_TIMED(c, PLSVO_K_SEEDS, launch_update_seeds(b, c->stream));
+  Readback rb;
+  const int r_d = rb.add(od, od_n * sizeof(double)), r_f = rb.add(of, of_n * sizeof(float)), r_i = rb.add(oi, oi_n * sizeof(int));
+  if (const int rc = rb.wait(c)) return rc;
+  const double* hd = rb.at<double>(r_d);
+  const float* hf = rb.at<float>(r_f);
+  const int* hi = rb.at<int>(r_i);
   auto cpd = [&](double* dst, const double* src, size_t k) { if (dst && k) memcpy(dst, src, k * sizeof(double)); };
   auto cpf = [&](float* dst, const float* src, size_t k) { if (dst && k) memcpy(dst, src, k * sizeof(float)); };
   cpd(out->pt_xyz_world, hd, NP * 3); cpd(out->pt_px_cur, hd + NP * 3, NP * 2); cpd(out->pt_depth, hd + NP * 5, NP);

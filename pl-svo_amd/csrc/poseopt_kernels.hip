@@ -261,34 +261,146 @@ __device__ __forceinline__ double popt_cull_feature(const PoseBatchDev& b, const
   return e0 * e0 + e1 * e1;
 }
 
+// ---- what every launch shape does once per frame or per iteration, written once ------------------------------------------------------
+// A frame's pose block is 32 doubles of LDS (s_pose of the block shape, PoseRowLds::pose of the row shape): 0..8 R, 9..11 t, 12..18
+// model, 19..25 T_old, 26 chi2, 27 point-iterations, 28 line-iterations.
+
+// quat_to_matrix (plsvo_math.hpp) with its contractions WRITTEN OUT, for the row shape.  Every entry of R is a sum of two products, and
+// which of the two hipcc fuses into the fma depends on the code around the call (the use counts of the products when the sum is
+// visited): inside the single-launch row kernel it was the first one in all three places, inside a kernel that holds the Gauss-Newton
+// loop alone it came out as the second for five of the nine entries -- R a last bit off, and with it every later iteration.  The three
+// refill kernels must match pose_opt_rows_kernel bit for bit (tests/test_gpu_poseopt_refill.py holds the two together), so no row-shape
+// code leaves the choice open.  The block shape (pose_opt_kernel) keeps quat_to_matrix.
+#ifdef PLSVO_WAVE_EMU   // (the host emulation build contracts nothing anywhere)
+__device__ __forceinline__ void quat_to_matrix_rows(const Quat& q, double* R) { quat_to_matrix(q, R); }
+#else
+__device__ __forceinline__ void quat_to_matrix_rows(const Quat& q, double* R) {
+#pragma clang fp contract(off)
+  const double tx = 2.0 * q.x, ty = 2.0 * q.y, tz = 2.0 * q.z;
+  const double twx = tx * q.w, twy = ty * q.w, twz = tz * q.w;
+  const double tyy = ty * q.y, tzz = tz * q.z;
+  R[0] = 1.0 - fma(q.y, ty, tzz); R[1] = fma(q.x, ty, -twz);      R[2] = fma(q.x, tz, twy);
+  R[3] = fma(q.x, ty, twz);       R[4] = 1.0 - fma(q.x, tx, tzz); R[5] = fma(q.y, tz, -twx);
+  R[6] = fma(q.x, tz, -twy);      R[7] = fma(q.y, tz, twx);       R[8] = 1.0 - fma(q.x, tx, tyy);
+}
+#endif
+
+// one frame of a launch as its lanes hold it
+struct PoseFrame {
+  PoseJobDev job;
+  PoseStateDev* st;
+  int job_id;
+  bool valid;                  // row shape: the row's launch slot lies inside the batch
+  // scratch: floats [0,np) point errors, [np, np+ns) line errors; doubles [0,nf) init (first loop), [nf,2nf) init (refinement),
+  // [2nf,3nf) final, [3nf, 3nf + 2 np) the points' normalised observations
+  float* errs;
+  double* vec;
+  double scale_pt, scale_ls;   // the MAD scales, once the scale pass has run
+  int n_del_pt, n_del_ls;      // what the cull deleted, once it has run
+};
+__device__ __forceinline__ PoseFrame popt_frame(const PoseBatchDev& b, int job_id) {
+  PoseFrame F;
+  F.job = b.jobs[job_id]; F.st = b.state + job_id; F.job_id = job_id; F.valid = true;
+  const size_t fbase = (size_t)F.job.pt_off + (size_t)F.job.seg_off;
+  F.errs = b.scratch_f32 + fbase; F.vec = b.scratch_f64 + 5 * fbase;
+  F.scale_pt = 1.0; F.scale_ls = 1.0; F.n_del_pt = 0; F.n_del_ls = 0;
+  return F;
+}
+
+// R | t of `model` into pose[0..11]; ROWS: the pinned rotation rows.  (A template parameter, not an argument: with both calls in one
+// function body the optimiser merges their common products ahead of inlining, and the merged ones have lost the right to contract.)
+template <bool ROWS>
+__device__ __forceinline__ void popt_store_Rt(const SE3d& model, double* pose) {
+  if constexpr (ROWS) quat_to_matrix_rows(model.q, pose); else quat_to_matrix(model.q, pose);
+  pose[9] = model.t[0]; pose[10] = model.t[1]; pose[11] = model.t[2];
+}
+
+// the block shape at one wave per frame, three waves per SIMD: the pose is re-read from LDS for every feature round -- twelve broadcast
+// reads against ~250 f64 instructions -- instead of living in 24 registers across the loop; the laundered offset keeps the compiler from
+// hoisting the reads
+__device__ __forceinline__ void popt_pose_per_round(const double* s_pose, double (&P)[12]) {
+  int off = 0;
+#ifndef PLSVO_WAVE_EMU
+  asm volatile("" : "+v"(off));
+#endif
+#pragma unroll
+  for (int k = 0; k < 12; ++k) P[k] = s_pose[off + k];
+}
+
+// one lane, after the solve of iteration `iter` (:173-195): a step whose chi2 rose, or a NaN solve, rolls the model back to T_old and
+// stops the loop; otherwise the left update, which stops the loop below EPS.  Writes the pose block.
+struct PoseUpdate { SE3d model; int accepted, brk; };
+template <bool ROWS>
+__device__ __forceinline__ PoseUpdate popt_update_model(double* pose, const double (&dT)[6], double new_chi2, int iter) {
+  SE3d model = se3_load(pose + 12);
+  int accepted = 1, brk = 0;
+  if ((iter > 0 && new_chi2 > pose[26]) || isnan(dT[0])) {            // :173-180
+    model = se3_load(pose + 19); accepted = 0; brk = 1;
+  } else {
+    const SE3d Tn = se3_mul_dev(se3_exp_dev(dT), model);               // :183 left update
+    se3_store(model, pose + 19);
+    model = Tn; pose[26] = new_chi2;
+    if (norm_max6(dT) <= 0.0000000001) brk = 1;                        // EPS, global.h:99
+  }
+  se3_store(model, pose + 12);
+  popt_store_Rt<ROWS>(model, pose);
+  return { model, accepted, brk };
+}
+
+// a frame's PoseStateDev at the start of a launch (one lane); phase_ticks are the caller's
+__device__ __forceinline__ void popt_reset_state(const PoseJobDev& job, PoseStateDev* st) {
+  st->log_count = 0; st->status = 0; st->iters = 0; st->iters_ref = 0; st->pt_iters = 0; st->seg_iters = 0;
+  st->num_obs_pt = 0; st->num_obs_ls = 0; st->estimated_scale = 0; st->error_init = 0; st->error_final = 0;
+  for (int k = 0; k < 36; ++k) st->cov[k] = 0.0;
+  for (int k = 0; k < 7; ++k) st->T[k] = job.T0[k];
+}
+
+// a frame's results at the end of a launch (one lane).  mi, mf: the patterns of the two f64 medians (:244-249), mi read only where
+// has_init; iters: the iteration counts of the two loops
+__device__ __forceinline__ void popt_write_result(const PoseBatchDev& b, const PoseFrame& F, double* poses, const double* pose, bool has_init,
+                                                  unsigned long long mi, unsigned long long mf, const int* iters) {
+  const PoseJobDev& job = F.job;
+  PoseStateDev* st = F.st;
+  for (int k = 0; k < 7; ++k) st->T[k] = pose[12 + k];
+  if (poses) for (int k = 0; k < 7; ++k) poses[7 * F.job_id + k] = pose[12 + k];
+  st->error_init = has_init ? sqrt(__longlong_as_double((long long)mi)) * job.fx : 0.0;
+  st->error_final = sqrt(__longlong_as_double((long long)mf)) * job.fx;
+  st->estimated_scale = F.scale_pt * job.fx;
+  st->num_obs_pt = (unsigned long long)(job.n_pts - F.n_del_pt);
+  st->num_obs_ls = (unsigned long long)(job.n_seg - F.n_del_ls);
+  st->iters = iters[0]; st->iters_ref = iters[1];
+  st->pt_iters = (unsigned long long)(pose[27] + 0.5); st->seg_iters = (unsigned long long)(pose[28] + 0.5);
+  if (b.work_key) b.work_key[F.job_id] = (int)fmin(pose[27] + pose[28] + 0.5, 2147483647.0);   // what this frame cost: the next launch's sort key
+}
+
+// ---- the block shape: one workgroup per frame ------------------------------------------------------------------------------------------
+// LDS roles: s_red 32*(PO_T/16) doubles (row partials); s_pose the pose block; s_tot the totals of the last iteration; s_ctl 0 break
+// flag, 1 / 2 iterations of the two loops
+
+// one GN loop (src/pose_optimizer.cpp:103-195 and the identical text at :469-563); phase 0 the first loop, 1 the refinement
 template <int PO_T>
-__device__ void popt_gn_loop(const PoseBatchDev& b, const PoseJobDev& job, PoseStateDev* st, int job_id, double* s_red,
-                             double* s_pose, int* s_ctl, int n_iter, int phase, double scale_pt, double scale_ls,
-                             double* init_vec, const double* obs, double* s_tot) {
+__device__ void popt_gn_loop(const PoseBatchDev& b, const PoseFrame& F, double* s_red, double* s_pose, double* s_tot, int* s_ctl, int n_iter, int phase) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int np = job.n_pts, ns = job.n_seg, nf = np + ns;
+  const PoseJobDev& job = F.job;
+  PoseStateDev* st = F.st;
+  const int nf = job.n_pts + job.n_seg;
+  double* init_vec = F.vec + phase * nf;
+  const double* obs = F.vec + 3 * nf;
   for (int iter = 0; iter < n_iter; ++iter) {
     double acc[32];   // 0..20 A (upper, row-major), 21..26 b, 27 chi2, 28 #points, 29 #segments, 30..31 unused
 #pragma unroll
     for (int k = 0; k < 32; ++k) acc[k] = 0.0;
     if constexpr (PO_T == 64) {
-      // (wave per frame, three waves per SIMD: the pose is re-read from LDS for every feature round -- twelve broadcast reads against ~250
-      //  f64 instructions -- instead of living in 24 registers across the loop; the laundered offset keeps the compiler from hoisting them)
       for (int f = tid; f < nf; f += PO_T) {
-        int off = 0;
-#ifndef PLSVO_WAVE_EMU
-        asm volatile("" : "+v"(off));
-#endif
         double P[12];
-#pragma unroll
-        for (int k = 0; k < 12; ++k) P[k] = s_pose[off + k];
-        popt_accumulate_feature(b, job, f, P, scale_pt, scale_ls, iter == 0, init_vec, obs, acc);
+        popt_pose_per_round(s_pose, P);
+        popt_accumulate_feature(b, job, f, P, F.scale_pt, F.scale_ls, iter == 0, init_vec, obs, acc);
       }
     } else {
-    double P[12];
+      double P[12];
 #pragma unroll
-    for (int k = 0; k < 12; ++k) P[k] = s_pose[k];
-    for (int f = tid; f < nf; f += PO_T) popt_accumulate_feature(b, job, f, P, scale_pt, scale_ls, iter == 0, init_vec, obs, acc);
+      for (int k = 0; k < 12; ++k) P[k] = s_pose[k];
+      for (int f = tid; f < nf; f += PO_T) popt_accumulate_feature(b, job, f, P, F.scale_pt, F.scale_ls, iter == 0, init_vec, obs, acc);
     }
     {
       double out2[2];
@@ -305,26 +417,15 @@ __device__ void popt_gn_loop(const PoseBatchDev& b, const PoseJobDev& job, PoseS
       if (lane == 0) {
         s_pose[27] += npt; s_pose[28] += nls;
         s_ctl[1 + phase] += 1;
-        SE3d model = se3_load(s_pose + 12);
-        int accepted = 1, brk = 0;
-        if ((iter > 0 && new_chi2 > s_pose[26]) || isnan(dT[0])) {          // :173-180
-          model = se3_load(s_pose + 19); accepted = 0; brk = 1;
-        } else {
-          const SE3d Tn = se3_mul_dev(se3_exp_dev(dT), model);               // :183 left update
-          se3_store(model, s_pose + 19);
-          model = Tn; s_pose[26] = new_chi2;
-          if (norm_max6(dT) <= 0.0000000001) brk = 1;                        // EPS, global.h:99
-        }
-        se3_store(model, s_pose + 12);
-        quat_to_matrix(model.q, s_pose); s_pose[9] = model.t[0]; s_pose[10] = model.t[1]; s_pose[11] = model.t[2];
-        s_ctl[0] = brk;
+        const PoseUpdate u = popt_update_model<false>(s_pose, dT, new_chi2, iter);
+        s_ctl[0] = u.brk;
         if (b.log) {
           const int lc = st->log_count;
           if (lc < b.log_cap) {
-            plsvo_poseopt_iterlog* r = b.log + (size_t)job_id * b.log_cap + lc;
-            r->phase = phase; r->iter = iter; r->accepted = accepted; r->reserved0 = 0; r->new_chi2 = new_chi2;
+            plsvo_poseopt_iterlog* r = b.log + (size_t)F.job_id * b.log_cap + lc;
+            r->phase = phase; r->iter = iter; r->accepted = u.accepted; r->reserved0 = 0; r->new_chi2 = new_chi2;
             for (int k = 0; k < 6; ++k) r->dT[k] = dT[k];
-            se3_store(model, r->T_after);
+            se3_store(u.model, r->T_after);
           }
           st->log_count = lc + 1;
         }
@@ -334,7 +435,7 @@ __device__ void popt_gn_loop(const PoseBatchDev& b, const PoseJobDev& job, PoseS
     if (b.log && tid == 0) {   // A and b of the trace come from s_tot (written by lanes 0..26 of wave 0 above)
       const int lc = st->log_count - 1;
       if (lc >= 0 && lc < b.log_cap) {
-        plsvo_poseopt_iterlog* r = b.log + (size_t)job_id * b.log_cap + lc;
+        plsvo_poseopt_iterlog* r = b.log + (size_t)F.job_id * b.log_cap + lc;
         for (int i = 0; i < 6; ++i) for (int jj = 0; jj < 6; ++jj) r->A[i * 6 + jj] = s_tot[sym6_index(i, jj)];
         for (int k = 0; k < 6; ++k) r->b[k] = s_tot[21 + k];
       }
@@ -345,27 +446,23 @@ __device__ void popt_gn_loop(const PoseBatchDev& b, const PoseJobDev& job, PoseS
 
 template <int PO_T>
 __global__ __launch_bounds__(PO_T) PLSVO_PO_OCC(PO_T) void pose_opt_kernel(PoseBatchDev b, double* poses) {
-  const int job_id = b.order ? b.order[blockIdx.x] : (int)blockIdx.x;
-  const PoseJobDev job = b.jobs[job_id];
-  PoseStateDev* st = b.state + job_id;
+  PoseFrame F = popt_frame(b, b.order ? b.order[blockIdx.x] : (int)blockIdx.x);
+  const PoseJobDev& job = F.job;
+  PoseStateDev* st = F.st;
   const int tid = threadIdx.x;
-  if (tid == 0 && b.work_key) b.work_key[job_id] = 0;
+  if (tid == 0 && b.work_key) b.work_key[F.job_id] = 0;
   const int np = job.n_pts, ns = job.n_seg, nf = np + ns;
+  float* errs = F.errs;
+  double* vec = F.vec;
 
   __shared__ __align__(16) double s_red[32 * (PO_T / 16)];
   __shared__ double s_lu[36];     // covariance: the LU factors live in LDS (dynamic pivot indexing would put them in scratch)
   __shared__ int s_perm[8];
-  __shared__ double s_pose[32];   // 27: point-iterations, 28: line-iterations
+  __shared__ double s_pose[32];
   __shared__ double s_tot[32];
   __shared__ int s_ctl[32];
   __shared__ int s_hist[PO_BINS];                           // 8 KB: radix histogram, or staging for the rank select
   __shared__ int s_sel[16];
-
-  // scratch: floats [0,np) point errors, [np, np+ns) line errors; doubles [0,nf) init (first loop),
-  // [nf,2nf) init (refinement), [2nf,3nf) final, [3nf, 3nf + 2 np) the points' normalised observations
-  const size_t fbase = (size_t)job.pt_off + (size_t)job.seg_off;
-  float* errs = b.scratch_f32 + fbase;
-  double* vec = b.scratch_f64 + 5 * fbase;
 
 #ifdef PLSVO_TIMING
   __shared__ unsigned long long s_time[8];
@@ -376,31 +473,23 @@ __global__ __launch_bounds__(PO_T) PLSVO_PO_OCC(PO_T) void pose_opt_kernel(PoseB
     SE3d m = se3_load(job.T0);
     se3_store(m, s_pose + 12); se3_store(m, s_pose + 19); s_pose[26] = 0.0; s_pose[27] = 0.0; s_pose[28] = 0.0;
     for (int k = 0; k < 32; ++k) s_tot[k] = 0.0;
-    quat_to_matrix(m.q, s_pose); s_pose[9] = m.t[0]; s_pose[10] = m.t[1]; s_pose[11] = m.t[2];
+    popt_store_Rt<false>(m, s_pose);
     s_ctl[0] = 0; s_ctl[1] = 0; s_ctl[2] = 0;
-    st->log_count = 0; st->status = 0; st->iters = 0; st->iters_ref = 0; st->pt_iters = 0; st->seg_iters = 0;
-    st->num_obs_pt = 0; st->num_obs_ls = 0; st->estimated_scale = 0; st->error_init = 0; st->error_final = 0;
-    for (int k = 0; k < 36; ++k) st->cov[k] = 0.0;
-    for (int k = 0; k < 7; ++k) st->T[k] = job.T0[k];
+    popt_reset_state(job, st);
   }
   for (int i = tid; i < np; i += PO_T) b.pt_keep[job.pt_off + i] = 1;
   for (int s = tid; s < ns; s += PO_T) b.seg_keep[job.seg_off + s] = 1;
   __syncthreads();
   if (nf == 0) {                                                              // errors.empty() :88-89
-    if (tid == 0) { st->status = 1; if (poses) for (int k = 0; k < 7; ++k) poses[7 * job_id + k] = job.T0[k]; }
+    if (tid == 0) { st->status = 1; if (poses) for (int k = 0; k < 7; ++k) poses[7 * F.job_id + k] = job.T0[k]; }
     return;
   }
 
   // ---- scale pass :57-95 ----
-  if constexpr (PO_T == 64) {   // (the pose from LDS per feature round: see popt_gn_loop)
+  if constexpr (PO_T == 64) {
     for (int f = tid; f < nf; f += PO_T) {
-      int off = 0;
-#ifndef PLSVO_WAVE_EMU
-      asm volatile("" : "+v"(off));
-#endif
       double P[12];
-#pragma unroll
-      for (int k = 0; k < 12; ++k) P[k] = s_pose[off + k];
+      popt_pose_per_round(s_pose, P);
       errs[f] = popt_scale_error(b, job, f, P, vec + 3 * nf);
     }
   } else {
@@ -412,17 +501,16 @@ __global__ __launch_bounds__(PO_T) PLSVO_PO_OCC(PO_T) void pose_opt_kernel(PoseB
   __syncthreads();
   PTICK(0);
   // MAD scale = 1.48f * median (float).  Zero points: the reference is undefined (:70); we define 1.0.
-  double scale_pt = 1.0, scale_ls = 1.0;
   auto median_f32 = [&](const float* v, int n) -> float {
     return __uint_as_float(block_radix_select<PO_T, 32, uint32_t>([&](int i) { return (uint32_t)__float_as_uint(v[i]); }, n, n / 2, s_hist, s_sel));
   };
-  if (np > 0) scale_pt = (double)__fmul_rn(1.48f, median_f32(errs, np));
-  if (ns > 0) scale_ls = (double)__fmul_rn(1.48f, median_f32(errs + np, ns));
+  if (np > 0) F.scale_pt = (double)__fmul_rn(1.48f, median_f32(errs, np));
+  if (ns > 0) F.scale_ls = (double)__fmul_rn(1.48f, median_f32(errs + np, ns));
 
   PTICK(1);
   // ---- first GN loop ----
   if (job.n_iter <= 0) for (int f = tid; f < nf; f += PO_T) vec[f] = __longlong_as_double(0x7ff0000000000000LL);
-  popt_gn_loop<PO_T>(b, job, st, job_id, s_red, s_pose, s_ctl, job.n_iter, 0, scale_pt, scale_ls, vec, vec + 3 * nf, s_tot);
+  popt_gn_loop<PO_T>(b, F, s_red, s_pose, s_tot, s_ctl, job.n_iter, 0);
 
   PTICK(2);
   // ---- covariance :197-199 (from the last assembled A, even if that iteration was rolled back) ----
@@ -437,21 +525,14 @@ __global__ __launch_bounds__(PO_T) PLSVO_PO_OCC(PO_T) void pose_opt_kernel(PoseB
 
   // ---- cull :201-242 ----
   const double thr_pt = job.reproj_thresh / job.fx;
-  const double thr_ls = thr_pt * scale_ls / scale_pt;
+  const double thr_ls = thr_pt * F.scale_ls / F.scale_pt;
   int del_pt = 0, del_ls = 0;
   {
     double P[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) P[k] = s_pose[k];
     for (int f = tid; f < nf; f += PO_T) {
-      if constexpr (PO_T == 64) {   // (the pose from LDS per feature round: see popt_gn_loop)
-        int off = 0;
-#ifndef PLSVO_WAVE_EMU
-        asm volatile("" : "+v"(off));
-#endif
-#pragma unroll
-        for (int k = 0; k < 12; ++k) P[k] = s_pose[off + k];
-      }
+      if constexpr (PO_T == 64) popt_pose_per_round(s_pose, P);
       int deleted;
       vec[2 * nf + f] = popt_cull_feature(b, job, f, P, thr_pt, thr_ls, vec + 3 * nf, deleted);
       del_pt += deleted == 1; del_ls += deleted == 2;
@@ -466,15 +547,14 @@ __global__ __launch_bounds__(PO_T) PLSVO_PO_OCC(PO_T) void pose_opt_kernel(PoseB
     if (lane == 63) { s_red[PO_RED * wave] = a; s_red[PO_RED * wave + 1] = c; }
     __syncthreads();
   }
-  int n_del_pt = 0, n_del_ls = 0;
-  for (int w = 0; w < PO_T / 64; ++w) { n_del_pt += (int)(s_red[PO_RED * w] + 0.5); n_del_ls += (int)(s_red[PO_RED * w + 1] + 0.5); }
+  for (int w = 0; w < PO_T / 64; ++w) { F.n_del_pt += (int)(s_red[PO_RED * w] + 0.5); F.n_del_ls += (int)(s_red[PO_RED * w + 1] + 0.5); }
   __syncthreads();
 
   // ---- refinement with inliers :469-563 (10-argument overload) ----
   int n_init = job.n_iter > 0 ? nf : 0;
   if (job.n_iter_ref >= 0) {
-    popt_gn_loop<PO_T>(b, job, st, job_id, s_red, s_pose, s_ctl, job.n_iter_ref, 1, scale_pt, scale_ls, vec + nf, vec + 3 * nf, s_tot);
-    if (job.n_iter_ref > 0) n_init += nf - n_del_pt - n_del_ls;
+    popt_gn_loop<PO_T>(b, F, s_red, s_pose, s_tot, s_ctl, job.n_iter_ref, 1);
+    if (job.n_iter_ref > 0) n_init += nf - F.n_del_pt - F.n_del_ls;
   }
   __syncthreads();
 
@@ -487,16 +567,7 @@ __global__ __launch_bounds__(PO_T) PLSVO_PO_OCC(PO_T) void pose_opt_kernel(PoseB
   if (n_init > 0) mi = kth_f64(vec, (job.n_iter_ref > 0) ? 2 * nf : nf, n_init / 2);   // unwritten refinement entries hold +inf and sort last
   const unsigned long long mf = kth_f64(vec + 2 * nf, nf, nf / 2);
   if (tid == 0) {
-    for (int k = 0; k < 7; ++k) st->T[k] = s_pose[12 + k];
-    if (poses) for (int k = 0; k < 7; ++k) poses[7 * job_id + k] = s_pose[12 + k];
-    st->error_init = sqrt(__longlong_as_double((long long)mi)) * job.fx;
-    st->error_final = sqrt(__longlong_as_double((long long)mf)) * job.fx;
-    st->estimated_scale = scale_pt * job.fx;
-    st->num_obs_pt = (unsigned long long)(np - n_del_pt);
-    st->num_obs_ls = (unsigned long long)(ns - n_del_ls);
-    st->iters = s_ctl[1]; st->iters_ref = s_ctl[2];
-    st->pt_iters = (unsigned long long)(s_pose[27] + 0.5); st->seg_iters = (unsigned long long)(s_pose[28] + 0.5);
-    if (b.work_key) b.work_key[job_id] = (int)fmin(s_pose[27] + s_pose[28] + 0.5, 2147483647.0);   // what this frame cost: the next launch's sort key
+    popt_write_result(b, F, poses, s_pose, true, mi, mf, s_ctl + 1);
 #ifdef PLSVO_TIMING
     { const unsigned long long t__ = __builtin_amdgcn_s_memtime(); s_time[4] += t__ - s_tlast; }
     for (int k = 0; k < 8; ++k) st->phase_ticks[k] = s_time[k];
@@ -799,105 +870,48 @@ __device__ __forceinline__ void lane_solve6(const double* tot, double* xs, doubl
   for (int c = 0; c < 6; ++c) x[c] = xs[c];
 }
 
-// one GN loop (:103-195 / :469-563) for the four frames of the wave
-__device__ __forceinline__ void rows_gn_loop(const PoseBatchDev& b, const PoseJobDev& job, PoseStateDev* st, int job_id, PoseRowLds& L, bool row_on,
-                                             int n_iter, int phase, double scale_pt, double scale_ls, double* init_vec, const double* obs) {
-  const int lane = threadIdx.x & 63, rl = lane & 15;
-  const int nf = job.n_pts + job.n_seg;
-  bool running = row_on && n_iter > 0;
-  for (int iter = 0; __any(running); ++iter) {
-    double acc[32];
-#pragma unroll
-    for (int k = 0; k < 32; ++k) acc[k] = 0.0;
-    if (running) {
-      double P[12];
-#pragma unroll
-      for (int k = 0; k < 12; ++k) P[k] = L.pose[k];
-      for (int f = rl; f < nf; f += 16) popt_accumulate_feature(b, job, f, P, scale_pt, scale_ls, iter == 0, init_vec, obs, acc);
-    }
-    double out2[2];
-    row_reduce_scatter32(acc, out2);     // every lane of the wave takes part (DPP); the row's totals are the frame's
-    if (running) *reinterpret_cast<double2*>(L.tot + row_reduce_scatter32_index(lane)) = make_double2(out2[0], out2[1]);
-    wave_lds_fence();
-    if (running && rl == 0) {
-      double dT[6];
-      lane_solve6(L.tot, L.x, dT, job.ldlt_flavour);                          // A.ldlt().solve(b) :170
-      const double new_chi2 = L.tot[27];
-      L.pose[27] += L.tot[28]; L.pose[28] += L.tot[29];
-      L.ctl[1 + phase] += 1;
-      SE3d model = se3_load(L.pose + 12);
-      int accepted = 1, brk = 0;
-      if ((iter > 0 && new_chi2 > L.pose[26]) || isnan(dT[0])) {              // :173-180
-        model = se3_load(L.pose + 19); accepted = 0; brk = 1;
-      } else {
-        const SE3d Tn = se3_mul_dev(se3_exp_dev(dT), model);                   // :183 left update
-        se3_store(model, L.pose + 19);
-        model = Tn; L.pose[26] = new_chi2;
-        if (norm_max6(dT) <= 0.0000000001) brk = 1;                            // EPS, global.h:99
-      }
-      if (iter + 1 >= n_iter) brk = 1;
-      se3_store(model, L.pose + 12);
-      quat_to_matrix(model.q, L.pose); L.pose[9] = model.t[0]; L.pose[10] = model.t[1]; L.pose[11] = model.t[2];
-      L.ctl[0] = brk;
-      if (b.log) {
-        const int lc = st->log_count;
-        if (lc < b.log_cap) {
-          plsvo_poseopt_iterlog* r = b.log + (size_t)job_id * b.log_cap + lc;
-          r->phase = phase; r->iter = iter; r->accepted = accepted; r->reserved0 = 0; r->new_chi2 = new_chi2;
-          for (int k = 0; k < 6; ++k) r->dT[k] = dT[k];
-          se3_store(model, r->T_after);
-          for (int i = 0; i < 6; ++i) for (int jj = 0; jj < 6; ++jj) r->A[i * 6 + jj] = L.tot[sym6_index(i, jj)];
-          for (int k = 0; k < 6; ++k) r->b[k] = L.tot[21 + k];
-        }
-        st->log_count = lc + 1;
-      }
-    }
-    wave_lds_fence();
-    if (running && L.ctl[0]) running = false;
-  }
+// ---- the phases of a row's frame: begin, Gauss-Newton step, finish.  pose_opt_rows_kernel and the three refill kernels below are
+// compositions of them; what differs between the kernels is an argument here, never a second copy. ---------------------------------------
+
+// the frame of this lane's row: launch slot 4 * workgroup + row, taken through b.order where `ordered`; a row past the batch holds the
+// batch's last frame with `valid` false
+__device__ __forceinline__ PoseFrame rows_frame(const PoseBatchDev& b, bool ordered) {
+  const int slot = blockIdx.x * 4 + ((threadIdx.x & 63) >> 4);
+  const bool valid = slot < b.n_jobs;
+  PoseFrame F = popt_frame(b, valid ? ((ordered && b.order) ? b.order[slot] : slot) : b.n_jobs - 1);
+  F.valid = valid;
+  return F;
 }
 
-__global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_opt_rows_kernel(PoseBatchDev b, double* poses, int select) {
-  __shared__ __align__(16) PoseRowLds s_rows[4];
-  const int lane = threadIdx.x & 63, row = lane >> 4, rl = lane & 15;
-  const int job_raw = blockIdx.x * 4 + row;
-  const bool row_valid = job_raw < b.n_jobs;
-  // a re-run staged batch comes sorted by the feature-iterations of its last launch (plsvo_capi.hip::plsvo_poseopt_run): the four frames of a
-  // wave run in lock step until the LAST of them stops, and the iteration counts are bimodal (4-6, or all 10) -- in an arbitrary order three
-  // waves of four hold a ten-iteration frame and run ten; sorted, the rows of a wave stop together
-  const int job_id = row_valid ? (b.order ? b.order[job_raw] : job_raw) : b.n_jobs - 1;
-  const PoseJobDev job = b.jobs[job_id];
-  PoseStateDev* st = b.state + job_id;
-  PoseRowLds& L = s_rows[row];
+// begin: state reset, the empty-frame result, keep flags, scale pass :57-95, the two MAD scales, the +inf fill of a frame without
+// iterations.  to_carry: the row's pose block goes to a PoseRefillCarry next, which is copied whole (words 29..31 are cleared) and gets
+// a zero tot of its own; otherwise the Gauss-Newton loop follows in this launch (L.tot and L.ctl are cleared)
+__device__ __forceinline__ void rows_begin(const PoseBatchDev& b, PoseFrame& F, PoseRowLds& L, double* poses, int select, bool to_carry) {
+  const int rl = threadIdx.x & 15;
+  const PoseJobDev& job = F.job;
+  PoseStateDev* st = F.st;
   const int np = job.n_pts, ns = job.n_seg, nf = np + ns;
-
-  // scratch: floats [0,np) point errors, [np, np+ns) line errors; doubles [0,nf) init (first loop), [nf,2nf) init (refinement), [2nf,3nf) final, [3nf, 3nf + 2 np) the points' normalised observations
-  const size_t fbase = (size_t)job.pt_off + (size_t)job.seg_off;
-  float* errs = b.scratch_f32 + fbase;
-  double* vec = b.scratch_f64 + 5 * fbase;
-
-  if (row_valid && rl == 0) {
+  float* errs = F.errs;
+  double* vec = F.vec;
+  if (F.valid && rl == 0) {
     SE3d m = se3_load(job.T0);
     se3_store(m, L.pose + 12); se3_store(m, L.pose + 19); L.pose[26] = 0.0; L.pose[27] = 0.0; L.pose[28] = 0.0;
-    for (int k = 0; k < 32; ++k) L.tot[k] = 0.0;
-    quat_to_matrix(m.q, L.pose); L.pose[9] = m.t[0]; L.pose[10] = m.t[1]; L.pose[11] = m.t[2];
-    L.ctl[0] = 0; L.ctl[1] = 0; L.ctl[2] = 0;
-    st->log_count = 0; st->status = 0; st->iters = 0; st->iters_ref = 0; st->pt_iters = 0; st->seg_iters = 0;
-    st->num_obs_pt = 0; st->num_obs_ls = 0; st->estimated_scale = 0; st->error_init = 0; st->error_final = 0;
-    for (int k = 0; k < 36; ++k) st->cov[k] = 0.0;
-    for (int k = 0; k < 7; ++k) st->T[k] = job.T0[k];
+    if (to_carry) { L.pose[29] = 0.0; L.pose[30] = 0.0; L.pose[31] = 0.0; }
+    else for (int k = 0; k < 32; ++k) L.tot[k] = 0.0;
+    popt_store_Rt<true>(m, L.pose);
+    if (!to_carry) { L.ctl[0] = 0; L.ctl[1] = 0; L.ctl[2] = 0; }
+    popt_reset_state(job, st);
     for (int k = 0; k < 8; ++k) st->phase_ticks[k] = 0;
-    if (nf == 0) { st->status = 1; if (poses) for (int k = 0; k < 7; ++k) poses[7 * job_id + k] = job.T0[k]; }   // errors.empty() :88-89
-    if (b.work_key) b.work_key[job_id] = 0;
+    if (nf == 0) { st->status = 1; if (poses) for (int k = 0; k < 7; ++k) poses[7 * F.job_id + k] = job.T0[k]; }   // errors.empty() :88-89
+    if (b.work_key) b.work_key[F.job_id] = 0;
   }
-  const bool row_on = row_valid && nf > 0;
+  const bool row_on = F.valid && nf > 0;
   if (row_on) {
     for (int i = rl; i < np; i += 16) b.pt_keep[job.pt_off + i] = 1;
     for (int s = rl; s < ns; s += 16) b.seg_keep[job.seg_off + s] = 1;
   }
   wave_lds_fence();
 
-  // ---- scale pass :57-95 ----
   if (row_on) {
     double P[12];
 #pragma unroll
@@ -906,20 +920,78 @@ __global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_opt_rows_kernel(Pos
   }
   wave_lds_fence();   // (global scratch written and read by lanes of this wave only)
   // MAD scale = 1.48f * median (float).  Zero points: the reference is undefined (:70); we define 1.0.
-  double scale_pt = 1.0, scale_ls = 1.0;
   {
     int path;
     const uint32_t m_pt = row_select<32, uint32_t>(errs, np, np / 2, row_on && np > 0, select != 0, L.hist, L.sel, path);
     const uint32_t m_ls = row_select<32, uint32_t>(errs + np, ns, ns / 2, row_on && ns > 0, select != 0, L.hist, L.sel, path);
-    if (np > 0) scale_pt = (double)__fmul_rn(1.48f, __uint_as_float(m_pt));
-    if (ns > 0) scale_ls = (double)__fmul_rn(1.48f, __uint_as_float(m_ls));
+    if (np > 0) F.scale_pt = (double)__fmul_rn(1.48f, __uint_as_float(m_pt));
+    if (ns > 0) F.scale_ls = (double)__fmul_rn(1.48f, __uint_as_float(m_ls));
   }
-
-  // ---- first GN loop ----
   if (row_on && job.n_iter <= 0) for (int f = rl; f < nf; f += 16) vec[f] = __longlong_as_double(0x7ff0000000000000LL);
-  rows_gn_loop(b, job, st, job_id, L, row_on, job.n_iter, 0, scale_pt, scale_ls, vec, vec + 3 * nf);
+}
 
-  // ---- covariance :197-199 (from the last assembled A, even if that iteration was rolled back) ----
+// one Gauss-Newton iteration (:103-195 / :469-563) of the rows that are `running`: iteration `iter` of `n_iter` of the row's own frame,
+// phase 0 the first loop, 1 the refinement.  Afterwards L.ctl[0] says whether the row's loop has stopped.  TRACE: the iteration trace
+// (b.log) is compiled in
+template <bool TRACE>
+__device__ __forceinline__ void rows_gn_step(const PoseBatchDev& b, const PoseFrame& F, PoseRowLds& L, bool running, int iter, int n_iter, int phase) {
+  const int lane = threadIdx.x & 63, rl = lane & 15;
+  const PoseJobDev& job = F.job;
+  const int nf = job.n_pts + job.n_seg;
+  double acc[32];
+#pragma unroll
+  for (int k = 0; k < 32; ++k) acc[k] = 0.0;
+  if (running) {
+    double P[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) P[k] = L.pose[k];
+    for (int f = rl; f < nf; f += 16) popt_accumulate_feature(b, job, f, P, F.scale_pt, F.scale_ls, iter == 0, F.vec + phase * nf, F.vec + 3 * nf, acc);
+  }
+  double out2[2];
+  row_reduce_scatter32(acc, out2);     // every lane of the wave takes part (DPP); the row's totals are the frame's
+  if (running) *reinterpret_cast<double2*>(L.tot + row_reduce_scatter32_index(lane)) = make_double2(out2[0], out2[1]);
+  wave_lds_fence();
+  if (running && rl == 0) {
+    double dT[6];
+    lane_solve6(L.tot, L.x, dT, job.ldlt_flavour);                          // A.ldlt().solve(b) :170
+    const double new_chi2 = L.tot[27];
+    L.pose[27] += L.tot[28]; L.pose[28] += L.tot[29];
+    L.ctl[1 + phase] += 1;
+    const PoseUpdate u = popt_update_model<true>(L.pose, dT, new_chi2, iter);
+    L.ctl[0] = iter + 1 >= n_iter ? 1 : u.brk;
+    if constexpr (TRACE) if (b.log) {
+      PoseStateDev* st = F.st;
+      const int lc = st->log_count;
+      if (lc < b.log_cap) {
+        plsvo_poseopt_iterlog* r = b.log + (size_t)F.job_id * b.log_cap + lc;
+        r->phase = phase; r->iter = iter; r->accepted = u.accepted; r->reserved0 = 0; r->new_chi2 = new_chi2;
+        for (int k = 0; k < 6; ++k) r->dT[k] = dT[k];
+        se3_store(u.model, r->T_after);
+        for (int i = 0; i < 6; ++i) for (int jj = 0; jj < 6; ++jj) r->A[i * 6 + jj] = L.tot[sym6_index(i, jj)];
+        for (int k = 0; k < 6; ++k) r->b[k] = L.tot[21 + k];
+      }
+      st->log_count = lc + 1;
+    }
+  }
+  wave_lds_fence();
+}
+
+// one GN loop for the four frames of the wave, in lock step until the last of them stops
+__device__ __forceinline__ void rows_gn_loop(const PoseBatchDev& b, const PoseFrame& F, PoseRowLds& L, bool row_on, int n_iter, int phase) {
+  bool running = row_on && n_iter > 0;
+  for (int iter = 0; __any(running); ++iter) {
+    rows_gn_step<true>(b, F, L, running, iter, n_iter, phase);
+    if (running && L.ctl[0]) running = false;
+  }
+}
+
+// finish, first part: covariance :197-199 (from the last assembled A, even if that iteration was rolled back) and cull :201-242
+__device__ __forceinline__ void rows_finish_cull(const PoseBatchDev& b, PoseFrame& F, PoseRowLds& L) {
+  const int rl = threadIdx.x & 15;
+  const PoseJobDev& job = F.job;
+  const int nf = job.n_pts + job.n_seg;
+  double* vec = F.vec;
+  const bool row_on = F.valid && nf > 0;
   if (row_on) {
     const double f2 = job.fx * job.fx;
     for (int t = rl; t < 36; t += 16) L.lu[t] = L.tot[sym6_index(t / 6, t % 6)] * f2;
@@ -927,11 +999,10 @@ __global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_opt_rows_kernel(Pos
   wave_lds_fence();
   if (row_on && rl == 0) lu6_lds(L.lu, L.perm);
   wave_lds_fence();
-  if (row_on && rl < 6) inv6_column_lds(L.lu, L.perm, rl, st->cov);
+  if (row_on && rl < 6) inv6_column_lds(L.lu, L.perm, rl, F.st->cov);
 
-  // ---- cull :201-242 ----
   const double thr_pt = job.reproj_thresh / job.fx;
-  const double thr_ls = thr_pt * scale_ls / scale_pt;
+  const double thr_ls = thr_pt * F.scale_ls / F.scale_pt;
   int del_pt = 0, del_ls = 0;
   if (row_on) {
     double P[12];
@@ -944,31 +1015,46 @@ __global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_opt_rows_kernel(Pos
       vec[nf + f] = __longlong_as_double(0x7ff0000000000000LL);  // +inf sentinel for the refinement's init entries
     }
   }
-  const int n_del_pt = row_sum_i32(del_pt), n_del_ls = row_sum_i32(del_ls);
+  F.n_del_pt = row_sum_i32(del_pt); F.n_del_ls = row_sum_i32(del_ls);
   wave_lds_fence();   // keep flags and vec visible to the row
+}
 
-  // ---- refinement with inliers :469-563 (10-argument overload) ----
-  int n_init = job.n_iter > 0 ? nf : 0;
-  rows_gn_loop(b, job, st, job_id, L, row_on && job.n_iter_ref >= 0, job.n_iter_ref, 1, scale_pt, scale_ls, vec + nf, vec + 3 * nf);
-  if (job.n_iter_ref > 0) n_init += nf - n_del_pt - n_del_ls;
-  wave_lds_fence();
-
-  // ---- medians :244-249 ----
+// finish, second part: the two f64 medians :244-249 and the final write.  n_iter_ref: the refinement loop's bound where one ran in this
+// launch -- its init entries then join the first median -- and 0 where none can have (the refill).  iters: see popt_write_result
+__device__ __forceinline__ void rows_finish_write(const PoseBatchDev& b, const PoseFrame& F, PoseRowLds& L, double* poses, int select, int n_iter_ref, const int* iters) {
+  const int rl = threadIdx.x & 15;
+  const int nf = F.job.n_pts + F.job.n_seg;
+  double* vec = F.vec;
+  const bool row_on = F.valid && nf > 0;
+  int n_init = F.job.n_iter > 0 ? nf : 0;
+  if (n_iter_ref > 0) n_init += nf - F.n_del_pt - F.n_del_ls;
   int path;
-  const unsigned long long mi = row_select<64, unsigned long long>(vec, (job.n_iter_ref > 0) ? 2 * nf : nf, n_init / 2, row_on && n_init > 0, select != 0, L.hist, L.sel, path);   // unwritten refinement entries hold +inf and sort last
+  const unsigned long long mi = row_select<64, unsigned long long>(vec, (n_iter_ref > 0) ? 2 * nf : nf, n_init / 2, row_on && n_init > 0, select != 0, L.hist, L.sel, path);   // unwritten refinement entries hold +inf and sort last
   const unsigned long long mf = row_select<64, unsigned long long>(vec + 2 * nf, nf, nf / 2, row_on, select != 0, L.hist, L.sel, path);
-  if (row_on && rl == 0) {
-    for (int k = 0; k < 7; ++k) st->T[k] = L.pose[12 + k];
-    if (poses) for (int k = 0; k < 7; ++k) poses[7 * job_id + k] = L.pose[12 + k];
-    st->error_init = n_init > 0 ? sqrt(__longlong_as_double((long long)mi)) * job.fx : 0.0;
-    st->error_final = sqrt(__longlong_as_double((long long)mf)) * job.fx;
-    st->estimated_scale = scale_pt * job.fx;
-    st->num_obs_pt = (unsigned long long)(np - n_del_pt);
-    st->num_obs_ls = (unsigned long long)(ns - n_del_ls);
-    st->iters = L.ctl[1]; st->iters_ref = L.ctl[2];
-    st->pt_iters = (unsigned long long)(L.pose[27] + 0.5); st->seg_iters = (unsigned long long)(L.pose[28] + 0.5);
-    if (b.work_key) b.work_key[job_id] = (int)fmin(L.pose[27] + L.pose[28] + 0.5, 2147483647.0);
-  }
+  if (row_on && rl == 0) popt_write_result(b, F, poses, L.pose, n_init > 0, mi, mf, iters);
+}
+
+__device__ __forceinline__ void rows_finish(const PoseBatchDev& b, PoseFrame& F, PoseRowLds& L, double* poses, int select, int n_iter_ref, const int* iters) {
+  rows_finish_cull(b, F, L);
+  rows_finish_write(b, F, L, poses, select, n_iter_ref, iters);
+}
+
+// a re-run staged batch comes sorted by the feature-iterations of its last launch (plsvo_capi.hip::plsvo_poseopt_run): the four frames of a
+// wave run in lock step until the LAST of them stops, and the iteration counts are bimodal (4-6, or all 10) -- in an arbitrary order three
+// waves of four hold a ten-iteration frame and run ten; sorted, the rows of a wave stop together
+__global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_opt_rows_kernel(PoseBatchDev b, double* poses, int select) {
+  __shared__ __align__(16) PoseRowLds s_rows[4];
+  PoseRowLds& L = s_rows[(threadIdx.x & 63) >> 4];
+  PoseFrame F = rows_frame(b, true);
+  const int nf = F.job.n_pts + F.job.n_seg;
+  const bool row_on = F.valid && nf > 0;
+  rows_begin(b, F, L, poses, select, false);
+  rows_gn_loop(b, F, L, row_on, F.job.n_iter, 0);
+  rows_finish_cull(b, F, L);
+  // refinement with inliers :469-563 (10-argument overload)
+  rows_gn_loop(b, F, L, row_on && F.job.n_iter_ref >= 0, F.job.n_iter_ref, 1);
+  wave_lds_fence();
+  rows_finish_write(b, F, L, poses, select, F.job.n_iter_ref, L.ctl + 1);
 }
 
 // ================================================================================================================================
@@ -977,103 +1063,39 @@ __global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_opt_rows_kernel(Pos
 // The four frames of a pose_opt_rows_kernel wave iterate until the LAST of them stops, and iteration counts are bimodal (4-6, or all
 // ten): in an arbitrary launch order almost every wave runs ten.  Rows share a program counter, so a row cannot start its next frame's
 // scale pass while its neighbours iterate -- the kernel is therefore cut at the loop's borders:
-//   * pose_refill_prologue_kernel: everything up to the two MAD scales, four frames per wave in lock step (uniform work);
+//   * pose_refill_prologue_kernel: rows_begin, four frames per wave in lock step (uniform work, so in index order), then the carry;
 //   * pose_refill_gn_kernel: persistent.  A row without a running frame takes the next launch slot from one device counter, loads that
-//     frame's carry (PoseRefillCarry) into its PoseRowLds and joins the loop at ITS iteration 0; when the frame stops the row writes the
-//     carry back.  A row either gets a slot or is done: nothing polls, nothing waits for another workgroup;
-//   * pose_refill_epilogue_kernel: covariance, cull, medians and the final writes, four frames per wave in lock step.
-// Per frame the arithmetic, the sums and their order are pose_opt_rows_kernel's: every output is bit-identical.  Batches with a
-// refinement loop (n_iter_ref > 0), an iteration trace or a -DPLSVO_TIMING build keep pose_opt_rows_kernel (plsvo_capi.hip decides).
+//     frame's carry (PoseRefillCarry) into its PoseRowLds and joins rows_gn_step at ITS iteration 0; when the frame stops the row
+//     writes the carry back.  A row either gets a slot or is done: nothing polls, nothing waits for another workgroup;
+//   * pose_refill_epilogue_kernel: the carry, then rows_finish, four frames per wave in lock step.
+// The phases are the functions pose_opt_rows_kernel is made of, so per frame the arithmetic, the sums and their order are the same
+// and every output is bit-identical.  Batches with a refinement loop (n_iter_ref > 0), an iteration trace or a -DPLSVO_TIMING build
+// keep pose_opt_rows_kernel (plsvo_capi.hip decides).
 // ================================================================================================================================
-// quat_to_matrix (plsvo_math.hpp) with its contractions WRITTEN OUT.  Every entry of R is a sum of two products, and which of the two
-// hipcc fuses into the fma depends on the code around the call (the use counts of the products when the sum is visited): inside
-// pose_opt_rows_kernel it is the first one in all three places, inside a kernel that holds the Gauss-Newton loop alone it came out
-// as the second for five of the nine entries -- R a last bit off, and with it every later iteration.  The refill kernels must match
-// pose_opt_rows_kernel bit for bit (tests/test_gpu_poseopt_refill.py holds the two together), so they do not leave the choice open.
-#ifdef PLSVO_WAVE_EMU   // (the host emulation build contracts nothing anywhere)
-__device__ __forceinline__ void quat_to_matrix_rows(const Quat& q, double* R) { quat_to_matrix(q, R); }
-#else
-__device__ __forceinline__ void quat_to_matrix_rows(const Quat& q, double* R) {
-#pragma clang fp contract(off)
-  const double tx = 2.0 * q.x, ty = 2.0 * q.y, tz = 2.0 * q.z;
-  const double twx = tx * q.w, twy = ty * q.w, twz = tz * q.w;
-  const double tyy = ty * q.y, tzz = tz * q.z;
-  R[0] = 1.0 - fma(q.y, ty, tzz); R[1] = fma(q.x, ty, -twz);      R[2] = fma(q.x, tz, twy);
-  R[3] = fma(q.x, ty, twz);       R[4] = 1.0 - fma(q.x, tx, tzz); R[5] = fma(q.y, tz, -twx);
-  R[6] = fma(q.x, tz, -twy);      R[7] = fma(q.y, tz, twx);       R[8] = 1.0 - fma(q.x, tx, tyy);
-}
-#endif
-
 __global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_refill_prologue_kernel(PoseBatchDev b, PoseRefillDev q, double* poses, int select) {
   __shared__ __align__(16) PoseRowLds s_rows[4];
-  const int lane = threadIdx.x & 63, row = lane >> 4, rl = lane & 15;
-  const int job_raw = blockIdx.x * 4 + row;
-  const bool row_valid = job_raw < b.n_jobs;
-  const int job_id = row_valid ? job_raw : b.n_jobs - 1;   // (index order: the work of a frame is uniform here)
-  const PoseJobDev job = b.jobs[job_id];
-  PoseStateDev* st = b.state + job_id;
-  PoseRowLds& L = s_rows[row];
-  const int np = job.n_pts, ns = job.n_seg, nf = np + ns;
-  const size_t fbase = (size_t)job.pt_off + (size_t)job.seg_off;   // scratch layout: see pose_opt_rows_kernel
-  float* errs = b.scratch_f32 + fbase;
-  double* vec = b.scratch_f64 + 5 * fbase;
-
-  if (row_valid && rl == 0) {
-    SE3d m = se3_load(job.T0);
-    se3_store(m, L.pose + 12); se3_store(m, L.pose + 19); L.pose[26] = 0.0; L.pose[27] = 0.0; L.pose[28] = 0.0;
-    L.pose[29] = 0.0; L.pose[30] = 0.0; L.pose[31] = 0.0;
-    quat_to_matrix_rows(m.q, L.pose); L.pose[9] = m.t[0]; L.pose[10] = m.t[1]; L.pose[11] = m.t[2];
-    st->log_count = 0; st->status = 0; st->iters = 0; st->iters_ref = 0; st->pt_iters = 0; st->seg_iters = 0;
-    st->num_obs_pt = 0; st->num_obs_ls = 0; st->estimated_scale = 0; st->error_init = 0; st->error_final = 0;
-    for (int k = 0; k < 36; ++k) st->cov[k] = 0.0;
-    for (int k = 0; k < 7; ++k) st->T[k] = job.T0[k];
-    for (int k = 0; k < 8; ++k) st->phase_ticks[k] = 0;
-    if (nf == 0) { st->status = 1; if (poses) for (int k = 0; k < 7; ++k) poses[7 * job_id + k] = job.T0[k]; }   // errors.empty() :88-89
-    if (b.work_key) b.work_key[job_id] = 0;
-  }
-  const bool row_on = row_valid && nf > 0;
-  if (row_on) {
-    for (int i = rl; i < np; i += 16) b.pt_keep[job.pt_off + i] = 1;
-    for (int s = rl; s < ns; s += 16) b.seg_keep[job.seg_off + s] = 1;
-  }
-  wave_lds_fence();
-
-  // ---- scale pass :57-95 ----
-  if (row_on) {
-    double P[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) P[k] = L.pose[k];
-    for (int f = rl; f < nf; f += 16) errs[f] = popt_scale_error(b, job, f, P, vec + 3 * nf);
-  }
-  wave_lds_fence();
-  double scale_pt = 1.0, scale_ls = 1.0;
-  {
-    int path;
-    const uint32_t m_pt = row_select<32, uint32_t>(errs, np, np / 2, row_on && np > 0, select != 0, L.hist, L.sel, path);
-    const uint32_t m_ls = row_select<32, uint32_t>(errs + np, ns, ns / 2, row_on && ns > 0, select != 0, L.hist, L.sel, path);
-    if (np > 0) scale_pt = (double)__fmul_rn(1.48f, __uint_as_float(m_pt));
-    if (ns > 0) scale_ls = (double)__fmul_rn(1.48f, __uint_as_float(m_ls));
-  }
-  if (row_on && job.n_iter <= 0) for (int f = rl; f < nf; f += 16) vec[f] = __longlong_as_double(0x7ff0000000000000LL);
-
-  if (row_valid) {
-    PoseRefillCarry& c = q.carry[job_id];
+  const int rl = threadIdx.x & 15;
+  PoseRowLds& L = s_rows[(threadIdx.x & 63) >> 4];
+  PoseFrame F = rows_frame(b, false);
+  rows_begin(b, F, L, poses, select, true);
+  if (F.valid) {
+    PoseRefillCarry& c = q.carry[F.job_id];
     *reinterpret_cast<double2*>(c.pose + 2 * rl) = *reinterpret_cast<const double2*>(L.pose + 2 * rl);
     *reinterpret_cast<double2*>(c.tot + 2 * rl) = make_double2(0.0, 0.0);
-    if (rl == 0) { c.scale_pt = scale_pt; c.scale_ls = scale_ls; c.iters = 0; }
+    if (rl == 0) { c.scale_pt = F.scale_pt; c.scale_ls = F.scale_ls; c.iters = 0; }
   }
 }
 
 __global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_refill_gn_kernel(PoseBatchDev b, PoseRefillDev q) {
   __shared__ __align__(16) PoseRowLds s_rows[4];
-  const int lane = threadIdx.x & 63, row = lane >> 4, rl = lane & 15;
-  PoseRowLds& L = s_rows[row];
-  // per row, in plain lane registers: the frame, its iteration index, what of its job the feature pass reads
-  PoseJobDev job;
+  const int rl = threadIdx.x & 15;
+  PoseRowLds& L = s_rows[(threadIdx.x & 63) >> 4];
+  // per row, in plain lane registers: the frame (what of its job the feature pass reads) and its iteration index
+  PoseFrame F;
+  PoseJobDev& job = F.job;
   job.n_pts = 0; job.n_seg = 0; job.pt_off = 0; job.seg_off = 0; job.n_iter = 0; job.ldlt_flavour = 320;
-  int job_id = 0, nf = 0, iter = 0;
-  double scale_pt = 1.0, scale_ls = 1.0;
-  double* vec = b.scratch_f64;
+  F.job_id = 0; F.scale_pt = 1.0; F.scale_ls = 1.0; F.vec = b.scratch_f64;
+  int iter = 0;
   bool running = false, want = true;
   for (;;) {
     // ---- refill: a row without a frame takes the next launch slot; frames without iterations to run are passed over ----
@@ -1085,16 +1107,15 @@ __global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_refill_gn_kernel(Po
         if (slot >= b.n_jobs) {
           want = false;
         } else {
-          job_id = b.order ? b.order[slot] : slot;
-          const PoseJobDev* J = b.jobs + job_id;
+          F.job_id = b.order ? b.order[slot] : slot;
+          const PoseJobDev* J = b.jobs + F.job_id;
           job.n_pts = J->n_pts; job.n_seg = J->n_seg; job.pt_off = J->pt_off; job.seg_off = J->seg_off; job.n_iter = J->n_iter; job.ldlt_flavour = J->ldlt_flavour;
-          nf = job.n_pts + job.n_seg;
-          if (nf > 0 && job.n_iter > 0) {
-            const PoseRefillCarry& c = q.carry[job_id];
+          if (job.n_pts + job.n_seg > 0 && job.n_iter > 0) {
+            const PoseRefillCarry& c = q.carry[F.job_id];
             *reinterpret_cast<double2*>(L.pose + 2 * rl) = *reinterpret_cast<const double2*>(c.pose + 2 * rl);
             if (rl == 0) { L.ctl[0] = 0; L.ctl[1] = 0; }
-            scale_pt = c.scale_pt; scale_ls = c.scale_ls;
-            vec = b.scratch_f64 + 5 * ((size_t)job.pt_off + (size_t)job.seg_off);
+            F.scale_pt = c.scale_pt; F.scale_ls = c.scale_ls;
+            F.vec = b.scratch_f64 + 5 * ((size_t)job.pt_off + (size_t)job.seg_off);
             iter = 0; running = true; want = false;
           }
         }
@@ -1103,46 +1124,11 @@ __global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_refill_gn_kernel(Po
     }
     if (!__any(running)) break;
 
-    // ---- one Gauss-Newton iteration of every running row (rows_gn_loop's body with the iteration index per row) ----
-    double acc[32];
-#pragma unroll
-    for (int k = 0; k < 32; ++k) acc[k] = 0.0;
-    if (running) {
-      double P[12];
-#pragma unroll
-      for (int k = 0; k < 12; ++k) P[k] = L.pose[k];
-      for (int f = rl; f < nf; f += 16) popt_accumulate_feature(b, job, f, P, scale_pt, scale_ls, iter == 0, vec, vec + 3 * nf, acc);
-    }
-    double out2[2];
-    row_reduce_scatter32(acc, out2);
-    if (running) *reinterpret_cast<double2*>(L.tot + row_reduce_scatter32_index(lane)) = make_double2(out2[0], out2[1]);
-    wave_lds_fence();
-    if (running && rl == 0) {
-      double dT[6];
-      lane_solve6(L.tot, L.x, dT, job.ldlt_flavour);                          // A.ldlt().solve(b) :170
-      const double new_chi2 = L.tot[27];
-      L.pose[27] += L.tot[28]; L.pose[28] += L.tot[29];
-      L.ctl[1] += 1;
-      SE3d model = se3_load(L.pose + 12);
-      int brk = 0;
-      if ((iter > 0 && new_chi2 > L.pose[26]) || isnan(dT[0])) {              // :173-180
-        model = se3_load(L.pose + 19); brk = 1;
-      } else {
-        const SE3d Tn = se3_mul_dev(se3_exp_dev(dT), model);                   // :183 left update
-        se3_store(model, L.pose + 19);
-        model = Tn; L.pose[26] = new_chi2;
-        if (norm_max6(dT) <= 0.0000000001) brk = 1;                            // EPS, global.h:99
-      }
-      if (iter + 1 >= job.n_iter) brk = 1;
-      se3_store(model, L.pose + 12);
-      quat_to_matrix_rows(model.q, L.pose); L.pose[9] = model.t[0]; L.pose[10] = model.t[1]; L.pose[11] = model.t[2];
-      L.ctl[0] = brk;
-    }
-    wave_lds_fence();
+    rows_gn_step<false>(b, F, L, running, iter, job.n_iter, 0);
     if (running) {
       ++iter;
       if (L.ctl[0]) {   // the frame has stopped: its carry goes back, the row is free
-        PoseRefillCarry& c = q.carry[job_id];
+        PoseRefillCarry& c = q.carry[F.job_id];
         *reinterpret_cast<double2*>(c.pose + 2 * rl) = *reinterpret_cast<const double2*>(L.pose + 2 * rl);
         *reinterpret_cast<double2*>(c.tot + 2 * rl) = *reinterpret_cast<const double2*>(L.tot + 2 * rl);
         if (rl == 0) c.iters = L.ctl[1];
@@ -1154,69 +1140,16 @@ __global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_refill_gn_kernel(Po
 
 __global__ __launch_bounds__(64) PLSVO_PO_ROWS_OCC void pose_refill_epilogue_kernel(PoseBatchDev b, PoseRefillDev q, double* poses, int select) {
   __shared__ __align__(16) PoseRowLds s_rows[4];
-  const int lane = threadIdx.x & 63, row = lane >> 4, rl = lane & 15;
-  const int job_raw = blockIdx.x * 4 + row;
-  const bool row_valid = job_raw < b.n_jobs;
-  const int job_id = row_valid ? job_raw : b.n_jobs - 1;
-  const PoseJobDev job = b.jobs[job_id];
-  PoseStateDev* st = b.state + job_id;
-  PoseRowLds& L = s_rows[row];
-  const int np = job.n_pts, ns = job.n_seg, nf = np + ns;
-  const size_t fbase = (size_t)job.pt_off + (size_t)job.seg_off;
-  double* vec = b.scratch_f64 + 5 * fbase;
-  const bool row_on = row_valid && nf > 0;
-  const PoseRefillCarry& c = q.carry[job_id];
+  const int rl = threadIdx.x & 15;
+  PoseRowLds& L = s_rows[(threadIdx.x & 63) >> 4];
+  PoseFrame F = rows_frame(b, false);
+  const PoseRefillCarry& c = q.carry[F.job_id];
   *reinterpret_cast<double2*>(L.pose + 2 * rl) = *reinterpret_cast<const double2*>(c.pose + 2 * rl);
   *reinterpret_cast<double2*>(L.tot + 2 * rl) = *reinterpret_cast<const double2*>(c.tot + 2 * rl);
-  const double scale_pt = c.scale_pt, scale_ls = c.scale_ls;
-  const int iters = c.iters;
+  F.scale_pt = c.scale_pt; F.scale_ls = c.scale_ls;
+  const int iters[2] = { c.iters, 0 };   // (no batch with a refinement loop comes here)
   wave_lds_fence();
-
-  // ---- covariance :197-199 (from the last assembled A, even if that iteration was rolled back) ----
-  if (row_on) {
-    const double f2 = job.fx * job.fx;
-    for (int t = rl; t < 36; t += 16) L.lu[t] = L.tot[sym6_index(t / 6, t % 6)] * f2;
-  }
-  wave_lds_fence();
-  if (row_on && rl == 0) lu6_lds(L.lu, L.perm);
-  wave_lds_fence();
-  if (row_on && rl < 6) inv6_column_lds(L.lu, L.perm, rl, st->cov);
-
-  // ---- cull :201-242 ----
-  const double thr_pt = job.reproj_thresh / job.fx;
-  const double thr_ls = thr_pt * scale_ls / scale_pt;
-  int del_pt = 0, del_ls = 0;
-  if (row_on) {
-    double P[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) P[k] = L.pose[k];
-    for (int f = rl; f < nf; f += 16) {
-      int deleted;
-      vec[2 * nf + f] = popt_cull_feature(b, job, f, P, thr_pt, thr_ls, vec + 3 * nf, deleted);
-      del_pt += deleted == 1; del_ls += deleted == 2;
-      vec[nf + f] = __longlong_as_double(0x7ff0000000000000LL);  // (the refinement's init entries: no batch with a refinement loop comes here)
-    }
-  }
-  const int n_del_pt = row_sum_i32(del_pt), n_del_ls = row_sum_i32(del_ls);
-  wave_lds_fence();   // keep flags and vec visible to the row
-
-  // ---- medians :244-249 ----
-  const int n_init = job.n_iter > 0 ? nf : 0;
-  int path;
-  const unsigned long long mi = row_select<64, unsigned long long>(vec, nf, n_init / 2, row_on && n_init > 0, select != 0, L.hist, L.sel, path);
-  const unsigned long long mf = row_select<64, unsigned long long>(vec + 2 * nf, nf, nf / 2, row_on, select != 0, L.hist, L.sel, path);
-  if (row_on && rl == 0) {
-    for (int k = 0; k < 7; ++k) st->T[k] = L.pose[12 + k];
-    if (poses) for (int k = 0; k < 7; ++k) poses[7 * job_id + k] = L.pose[12 + k];
-    st->error_init = n_init > 0 ? sqrt(__longlong_as_double((long long)mi)) * job.fx : 0.0;
-    st->error_final = sqrt(__longlong_as_double((long long)mf)) * job.fx;
-    st->estimated_scale = scale_pt * job.fx;
-    st->num_obs_pt = (unsigned long long)(np - n_del_pt);
-    st->num_obs_ls = (unsigned long long)(ns - n_del_ls);
-    st->iters = iters; st->iters_ref = 0;
-    st->pt_iters = (unsigned long long)(L.pose[27] + 0.5); st->seg_iters = (unsigned long long)(L.pose[28] + 0.5);
-    if (b.work_key) b.work_key[job_id] = (int)fmin(L.pose[27] + L.pose[28] + 0.5, 2147483647.0);
-  }
+  rows_finish(b, F, L, poses, select, 0, iters);
 }
 
 bool pose_opt_refill_built() {

@@ -1,5 +1,6 @@
-// poseopt_refill.hpp -- the row shape of the pose optimiser as three launches (poseopt_kernels.hip: prologue, persistent Gauss-Newton
-// kernel whose rows take their next frame from a queue, epilogue): what a frame carries through HBM between them, and the queue.
+// poseopt_refill.hpp -- the row shape of the pose optimiser as three launches (poseopt_kernels.hip: prologue = rows_begin, persistent
+// Gauss-Newton kernel whose rows take their next frame from a queue and run rows_gn_step, epilogue = rows_finish -- the phase functions
+// pose_opt_rows_kernel is made of): what a frame carries through HBM between them, and the queue.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1096,6 +1096,76 @@ int plsvo_candidates_fetch_map(plsvo_ctx* ctx, int n, plsvo_cand_map_out* out);
 int plsvo_candidates_set_positions(plsvo_ctx* ctx, int n, const plsvo_cand_positions* in);
 
 /* ------------------------------------------------------------------------------------------ */
+/* structure optimisation on the resident tables: FrameHandlerBase::optimizeStructure           */
+/* (src/frame_handler_base.cpp:192-237, called at src/frame_handler_mono.cpp:340 on every        */
+/* tracked frame), in place (one wave per stream).  Among the features of the    */
+/* last selection whose keep byte is set (feat3D != NULL behind the pose optimiser's cull) the   */
+/* min(max_n, count) landmarks with the smallest last_structure_optim_ are refined by            */
+/* Point::optimize / LineSeg::optimize (plsvo_structure_optimize's arithmetic, bit for bit) on   */
+/* the resident keyframe poses and observation lists; their positions are written in place and   */
+/* their last_structure_optim_ becomes frame_id, also when the optimiser rolled back (:221).     */
+/* The new frame is no keyframe yet and is in no observation list.  A segment that won both of   */
+/* its cells is a feature twice, is in the reference's deque twice and, selected twice, is       */
+/* optimised twice in sequence.                                                                  */
+/* Pinned where the reference leaves the result open: std::nth_element does not say which of     */
+/* several equal keys at the cut are taken -- ties go to the EARLIER feature (signed 32-bit      */
+/* keys; with count <= max_n every entry is taken).  The selected entries are reported in        */
+/* feature order.                                                                                */
+/* last_structure_optim_ is one int32 per landmark row, zero after plsvo_candidates_stage and    */
+/* for every row first used later (plsvo_candidates_add, a converged seed), as the reference's   */
+/* constructors set it; a keyframe insertion leaves it alone.                                    */
+/* Preconditions (unchecked): a feature's landmark is never TYPE_DELETED here (a landmark        */
+/* receives a feature only when its refine succeeded in that selection); point features are      */
+/* distinct landmarks.                                                                           */
+/* ------------------------------------------------------------------------------------------ */
+
+typedef struct plsvo_cand_structopt_params {   /* one set for the batch; the reference's 20 / 5 / 20 / 5 (src/config.cpp:105-108) */
+  int32_t max_n_pts;                /* structureoptim_max_pts */
+  int32_t n_iter_pts;               /* structureoptim_num_iter */
+  int32_t max_n_segs;               /* structureoptim_max_segs */
+  int32_t n_iter_segs;              /* structureoptim_num_iter_segs */
+} plsvo_cand_structopt_params;
+
+typedef struct plsvo_cand_structopt {   /* one stream */
+  int32_t active;                   /* 0: this stream is left alone (the reference skips the stage on a frame that failed earlier) */
+  int32_t frame_id;                 /* Frame::id_ */
+  const uint8_t* pt_keep;           /* HOST keep masks in selection order (n_matches / n_ls_matches entries), or NULL: the resident */
+  const uint8_t* seg_keep;          /* masks of plsvo_candidates_pose_optimize */
+} plsvo_cand_structopt;
+
+/* What the last call did to one stream.  Caller buffers (3 doubles per position), any may be NULL; cap_pt / cap_seg are INPUTS: the
+ * entries each non-NULL point / segment buffer holds.  max_n_pts / max_n_segs of the call always suffice. */
+typedef struct plsvo_cand_structopt_out {
+  int32_t n_sel_pt, n_sel_seg;      /* selected entries (0 for an inactive stream) */
+  int32_t cap_pt, cap_seg;          /* in: capacity of the caller's point / segment buffers, in entries */
+  int32_t* pt_lm;                   /* landmark index, in feature order */
+  int32_t* pt_iters;                /* residual evaluations executed (plsvo_structopt_out's pt_iters) */
+  double* pt_pos;                   /* the position behind the entry's run */
+  int32_t* seg_lm; int32_t* seg_iters; double* seg_spos; double* seg_epos;   /* a segment listed twice: the second entry holds the final position */
+} plsvo_cand_structopt_out;
+
+/* last_structure_optim_ per landmark of one stream (n_pt / n_seg entries).  A NULL array is skipped. */
+typedef struct plsvo_cand_last_optim_in { const int32_t* pt_last_optim; const int32_t* seg_last_optim; } plsvo_cand_last_optim_in;
+typedef struct plsvo_cand_last_optim_out { int32_t* pt_last_optim; int32_t* seg_last_optim; } plsvo_cand_last_optim_out;
+
+/* optimize_structure: enqueue only, apart from the copy of the records and of host masks (which waits for the selection's counts); timed
+ * under PLSVO_K_STRUCTOPT.  Its place in a run: after plsvo_candidates_pose_optimize, before plsvo_candidates_insert_keyframe; the next
+ * plsvo_candidates_run projects with the moved positions.  PLSVO_E_STATE: no selection on the last run; NULL masks of an active stream
+ * without a resident pose optimisation; a second call on the same run (the keys have moved on); the run closed by an insertion or an add;
+ * an unfetched seed update pending.  PLSVO_E_INVALID (nothing written): another n than staged, NULL arguments with n > 0, NULL params, a
+ * negative cap or iteration count.
+ * structure_fetch: synchronises; PLSVO_E_STATE before the first optimize_structure since the tables were staged; PLSVO_E_INVALID, no
+ * buffer of any stream written, when a stream selected more entries than the capacity it gives for a non-NULL buffer (the counts of
+ * every stream are reported all the same, so the caller can size the buffers and fetch again).  A caller that follows the map needs
+ * these few hundred bytes and no table fetch.
+ * set_last_optim / fetch_last_optim: synchronous, valid from plsvo_candidates_stage on (PLSVO_E_STATE with an unfetched seed update
+ * pending): they let a caller that restages carry the keys over. */
+int plsvo_candidates_optimize_structure(plsvo_ctx* ctx, int n, const plsvo_cand_structopt* in, const plsvo_cand_structopt_params* params);
+int plsvo_candidates_structure_fetch(plsvo_ctx* ctx, int n, plsvo_cand_structopt_out* out);
+int plsvo_candidates_set_last_optim(plsvo_ctx* ctx, int n, const plsvo_cand_last_optim_in* in);
+int plsvo_candidates_fetch_last_optim(plsvo_ctx* ctx, int n, plsvo_cand_last_optim_out* out);
+
+/* ------------------------------------------------------------------------------------------ */
 /* new map candidates: a depth-filter seed that converged becomes a landmark of the resident    */
 /* tables, in place (one wave per stream).  It replaces what                    */
 /* DepthFilter::updatePointSeeds / updateLineSeeds do with a converged seed                     */

@@ -283,6 +283,32 @@ class CandPositions(C.Structure):
                 ("seg_epos", c_double_p)]
 
 
+class CandStructOptParams(C.Structure):
+    """plsvo_cand_structopt_params"""
+    _fields_ = [("max_n_pts", C.c_int32), ("n_iter_pts", C.c_int32), ("max_n_segs", C.c_int32), ("n_iter_segs", C.c_int32)]
+
+
+class CandStructOpt(C.Structure):
+    """plsvo_cand_structopt"""
+    _fields_ = [("active", C.c_int32), ("frame_id", C.c_int32), ("pt_keep", c_u8_p), ("seg_keep", c_u8_p)]
+
+
+class CandStructOptOut(C.Structure):
+    """plsvo_cand_structopt_out"""
+    _fields_ = [("n_sel_pt", C.c_int32), ("n_sel_seg", C.c_int32), ("cap_pt", C.c_int32), ("cap_seg", C.c_int32), ("pt_lm", c_i32_p), ("pt_iters", c_i32_p), ("pt_pos", c_double_p), ("seg_lm", c_i32_p),
+                ("seg_iters", c_i32_p), ("seg_spos", c_double_p), ("seg_epos", c_double_p)]
+
+
+class CandLastOptimIn(C.Structure):
+    """plsvo_cand_last_optim_in"""
+    _fields_ = [("pt_last_optim", c_i32_p), ("seg_last_optim", c_i32_p)]
+
+
+class CandLastOptimOut(C.Structure):
+    """plsvo_cand_last_optim_out"""
+    _fields_ = [("pt_last_optim", c_i32_p), ("seg_last_optim", c_i32_p)]
+
+
 LM_EVENT_NEW = 8
 
 

@@ -31,6 +31,7 @@ SYMBOLS = [
     "plsvo_candidates_set_quality", "plsvo_candidates_fetch_quality", "plsvo_candidates_select", "plsvo_candidates_select_fetch", "plsvo_candidates_pose_optimize",
     "plsvo_candidates_pose_fetch", "plsvo_candidates_poses_dev", "plsvo_candidates_set_match",
     "plsvo_candidates_reserve", "plsvo_candidates_capacity", "plsvo_candidates_insert_keyframe", "plsvo_candidates_insert_fetch", "plsvo_candidates_fetch_map", "plsvo_candidates_set_positions",
+    "plsvo_candidates_optimize_structure", "plsvo_candidates_structure_fetch", "plsvo_candidates_set_last_optim", "plsvo_candidates_fetch_last_optim",
     "plsvo_candidates_reserve_landmarks", "plsvo_candidates_lm_capacity", "plsvo_candidates_add", "plsvo_candidates_add_fetch",
     "plsvo_seeds_reserve", "plsvo_seeds_capacity", "plsvo_seeds_stage", "plsvo_seeds_update", "plsvo_seeds_update_fetch", "plsvo_seeds_keyframe", "plsvo_seeds_fetch_lists",
     "plsvo_seeds_fetch_rows", "plsvo_seeds_commit_rows", "plsvo_seeds_keyframe_detect", "plsvo_seeds_keyframe_fetch",
@@ -170,6 +171,10 @@ def lib():
         "plsvo_candidates_insert_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandInsertOut)]),
         "plsvo_candidates_fetch_map": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandMapOut)]),
         "plsvo_candidates_set_positions": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandPositions)]),
+        "plsvo_candidates_optimize_structure": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandStructOpt), C.POINTER(abi.CandStructOptParams)]),
+        "plsvo_candidates_structure_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandStructOptOut)]),
+        "plsvo_candidates_set_last_optim": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandLastOptimIn)]),
+        "plsvo_candidates_fetch_last_optim": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandLastOptimOut)]),
         "plsvo_candidates_reserve_landmarks": (C.c_int, [ctxp, C.POINTER(abi.CandLmReserve)]),
         "plsvo_candidates_lm_capacity": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandLmReserve)]),
         "plsvo_candidates_add": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandNew)]),
@@ -1002,6 +1007,75 @@ class Context:
                     keep.append(v)
                     setattr(a, f, v.ctypes.data_as(abi.c_double_p))
         self._chk(self.L.plsvo_candidates_set_positions(self.h, n, arr))
+
+    # ---- structure optimisation on the resident map tables ----
+    def candidates_optimize_structure(self, jobs, max_n_pts=20, n_iter_pts=5, max_n_segs=20, n_iter_segs=5):
+        """plsvo_candidates_optimize_structure (enqueue only after the copy of host masks): per staged stream None (left alone) or a dict of
+        frame_id and optionally pt_keep / seg_keep (host masks in selection order; missing: the resident pose optimiser's)"""
+        n = len(jobs)
+        arr = (abi.CandStructOpt * max(n, 1))()
+        keep = []
+        for a, j in zip(arr, jobs):
+            if j is None:
+                continue
+            a.active, a.frame_id = 1, int(j.get("frame_id", 0))
+            for f in ("pt_keep", "seg_keep"):
+                if j.get(f) is not None:
+                    v = np.ascontiguousarray(j[f], dtype=np.uint8).reshape(-1)
+                    v = v if v.size else np.zeros(1, np.uint8)
+                    keep.append(v)
+                    setattr(a, f, v.ctypes.data_as(abi.c_u8_p))
+        pr = abi.CandStructOptParams(int(max_n_pts), int(n_iter_pts), int(max_n_segs), int(n_iter_segs))
+        self._chk(self.L.plsvo_candidates_optimize_structure(self.h, n, arr, C.byref(pr)))
+
+    def candidates_structure_fetch(self):
+        """plsvo_candidates_structure_fetch (synchronises): per stream a dict of n_sel_pt, n_sel_seg and the selected entries in feature
+        order (pt_lm, pt_iters, pt_pos [k, 3], seg_lm, seg_iters, seg_spos [k, 3], seg_epos [k, 3])"""
+        n = len(self._cand_maps)
+        outs = (abi.CandStructOptOut * max(n, 1))()
+        bufs = []
+        for o, m in zip(outs, self._cand_cap):
+            cp, cs = max(m["filed_pt"], 1), max(2 * m["filed_seg"], 1)      # what a stream can select at most, whatever the call's caps were
+            o.cap_pt, o.cap_seg = cp, cs
+            b = dict(pt_lm=np.full(cp, -9, np.int32), pt_iters=np.full(cp, -9, np.int32), pt_pos=np.zeros((cp, 3)), seg_lm=np.full(cs, -9, np.int32),
+                     seg_iters=np.full(cs, -9, np.int32), seg_spos=np.zeros((cs, 3)), seg_epos=np.zeros((cs, 3)))
+            for k, v in b.items():
+                setattr(o, k, self._ptr(v))
+            bufs.append(b)
+        self._chk(self.L.plsvo_candidates_structure_fetch(self.h, n, outs))
+        res = []
+        for o, b in zip(outs[:n], bufs):
+            r = dict(n_sel_pt=int(o.n_sel_pt), n_sel_seg=int(o.n_sel_seg))
+            r.update({k: v[:(o.n_sel_pt if k.startswith("pt_") else o.n_sel_seg)].copy() for k, v in b.items()})
+            res.append(r)
+        return res
+
+    def candidates_set_last_optim(self, keys):
+        """plsvo_candidates_set_last_optim: per staged stream None or a dict with any of pt_last_optim, seg_last_optim (a missing one leaves
+        those keys as they are)"""
+        n = len(keys)
+        arr = (abi.CandLastOptimIn * max(n, 1))()
+        keep = []
+        for a, q in zip(arr, keys):
+            for f in ("pt_last_optim", "seg_last_optim"):
+                if q and q.get(f) is not None:
+                    v = np.ascontiguousarray(q[f], dtype=np.int32)
+                    keep.append(v)
+                    setattr(a, f, v.ctypes.data_as(abi.c_i32_p))
+        self._chk(self.L.plsvo_candidates_set_last_optim(self.h, n, arr))
+
+    def candidates_fetch_last_optim(self):
+        """plsvo_candidates_fetch_last_optim: per stream a dict of pt_last_optim / seg_last_optim as they now stand"""
+        n = len(self._cand_maps)
+        outs = (abi.CandLastOptimOut * max(n, 1))()
+        bufs = []
+        for o, m in zip(outs, self._cand_cap):
+            b = dict(pt_last_optim=np.full(max(m["pt"], 1), -9, np.int32), seg_last_optim=np.full(max(m["seg"], 1), -9, np.int32))
+            for k, v in b.items():
+                setattr(o, k, self._ptr(v))
+            bufs.append(b)
+        self._chk(self.L.plsvo_candidates_fetch_last_optim(self.h, n, outs))
+        return [{k: v[:(m["pt"] if k.startswith("pt_") else m["seg"])].copy() for k, v in b.items()} for m, b in zip(self._cand_now, bufs)]
 
     # ---- depth-filter seed lists resident beside the map tables ----
     @staticmethod

@@ -23,8 +23,8 @@ static QualitySections quality_sections(const plsvo_ctx* c) {
   s.pt_ev = q.take<uint8_t>(c->cd_t_pt); s.seg_ev = q.take<uint8_t>(c->cd_t_seg); s.end = q.off;
   return s;
 }
-static void cand_reset_run(plsvo_ctx* c) { c->cd_ran = c->cd_matched = c->cs_selected = c->cs_posed = c->ci_inserted = c->cn_closed = false; }   // the steps taken on the last run's results
-static void cand_reset_stage(plsvo_ctx* c) { cand_reset_run(c); c->cd_staged = c->ci_have_out = c->cn_have_out = c->sd_staged = c->sd_pending = c->sd_have_report = c->sk_have_report = false; }   // those, the tables, the last insertion's and add's reports
+static void cand_reset_run(plsvo_ctx* c) { c->cd_ran = c->cd_matched = c->cs_selected = c->cs_posed = c->ci_inserted = c->cn_closed = c->co_done = false; }   // the steps taken on the last run's results
+static void cand_reset_stage(plsvo_ctx* c) { cand_reset_run(c); c->cd_staged = c->ci_have_out = c->cn_have_out = c->co_have_out = c->sd_staged = c->sd_pending = c->sd_have_report = c->sk_have_report = false; }   // those, the tables, the last insertion's and add's reports
 // PLSVO_OK while the last run's candidates still describe the tables; once an insertion or an add came behind it, the refusal of entry point `who`
 static int cand_run_open(plsvo_ctx* c, const char* who) {
   const char* why = c->ci_inserted ? "this run's frame was inserted" : c->cn_closed ? "landmarks were added behind this run" : nullptr;
@@ -211,6 +211,9 @@ extern "C" int plsvo_candidates_stage(plsvo_ctx* c, int n, const plsvo_cand_map*
   const size_t q_bytes = quality_sections(c).end;   // the landmark quality starts at zero
   HIP_TRY(c, c->cs_d_q.ensure(q_bytes + 256));
   HIP_TRY(c, hipMemsetAsync(c->cs_d_q.p, 0, q_bytes, c->stream));
+  const size_t key_bytes = (t.pt + t.seg) * sizeof(int);   // last_structure_optim_ of every landmark row of capacity starts at zero, as the reference's constructors set it
+  HIP_TRY(c, c->co_d_key.ensure(key_bytes + 256));
+  HIP_TRY(c, hipMemsetAsync(c->co_d_key.p, 0, key_bytes, c->stream));
   c->cd_staged = true;
   return PLSVO_OK;
 }
@@ -807,6 +810,140 @@ extern "C" int plsvo_candidates_set_positions(plsvo_ctx* c, int n, const plsvo_c
   p.seg_at = reinterpret_cast<const long long*>(d + b_si); p.seg_ssrc = reinterpret_cast<const double*>(d + b_ss); p.seg_esrc = reinterpret_cast<const double*>(d + b_se);
   p.pt_pos = const_cast<double*>(c->cd_b.pt_pos); p.seg_spos = const_cast<double*>(c->cd_b.seg_spos); p.seg_epos = const_cast<double*>(c->cd_b.seg_epos);
   HIP_TRY(c, launch_map_set_positions(p, c->stream));
+  return PLSVO_OK;
+}
+
+// ---- structure optimisation on the resident map tables (structsel_device.hpp) ---------------------------------------------
+extern "C" int plsvo_candidates_optimize_structure(plsvo_ctx* c, int n, const plsvo_cand_structopt* in, const plsvo_cand_structopt_params* pr) {
+  CTX_CHECK(c);
+  if (!c->cd_staged || !c->cd_ran || !c->cs_selected) return fail(c, PLSVO_E_STATE, "candidates_optimize_structure: no selection on the last run");
+  if (const int rc = cand_seeds_pending(c, "candidates_optimize_structure")) return rc;
+  if (c->co_done) return fail(c, PLSVO_E_STATE, "candidates_optimize_structure: this run's structure was optimised already (the keys have moved on)");
+  if (const int rc = cand_run_open(c, "candidates_optimize_structure")) return rc;
+  if (!pr || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_optimize_structure: bad arguments");
+  if (n != c->cd_n) return fail(c, PLSVO_E_INVALID, "candidates_optimize_structure: n does not match the staged batch");
+  if (pr->max_n_pts < 0 || pr->n_iter_pts < 0 || pr->max_n_segs < 0 || pr->n_iter_segs < 0) return fail(c, PLSVO_E_INVALID, "candidates_optimize_structure: negative cap or iteration count");
+  bool host_masks = false;
+  for (int s = 0; s < n; ++s) {
+    if (!in[s].active) continue;
+    if ((!in[s].pt_keep || !in[s].seg_keep) && !c->cs_posed) return fail(c, PLSVO_E_STATE, "candidates_optimize_structure: no resident pose optimisation for the masks");
+    if (in[s].pt_keep || in[s].seg_keep) host_masks = true;
+  }
+  if (n == 0) { c->co_done = c->co_have_out = true; c->co_b = StructSelBatchDev{}; return PLSVO_OK; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t N = (size_t)n;
+  // -- the report's rows per stream: the caps, no more than a stream can select
+  int cap_pt = 0, cap_seg = 0;
+  for (const CandMapDev& M : c->cd_maps) { cap_pt = std::max(cap_pt, M.cap_pt); cap_seg = std::max(cap_seg, (int)std::min<long long>(2ll * M.cap_seg, INT32_MAX)); }
+  const int max_pts = std::min(pr->max_n_pts, cap_pt), max_segs = std::min(pr->max_n_segs, cap_seg);
+  // -- the records and the caller's masks, laid out like the resident masks (feature rows from opt_off / 2 * oseg_off)
+  Readback rb_sc;
+  if (host_masks) rb_sc.add(c->cs_b.scalars, N * 3 * sizeof(int));
+  if (const int rc = host_masks ? rb_sc.wait(c) : PLSVO_OK) return rc;
+  const int* const sc = host_masks ? rb_sc.at<int>(0) : nullptr;
+  Blob blob;
+  const size_t b_jobs = blob.reserve<StructSelJobDev>(N);
+  const size_t b_pk = host_masks ? blob.reserve<uint8_t>(c->cd_t_opt) : 0, b_sk = host_masks ? blob.reserve<uint8_t>(2 * c->cd_t_oseg) : 0;
+  HIP_TRY(c, c->co_d_in.ensure(std::max(blob.host.size(), (size_t)256)));
+  const uint8_t* din = c->co_d_in.as<uint8_t>();
+  StructSelJobDev* jobs = blob.at<StructSelJobDev>(b_jobs);
+  for (int s = 0; s < n; ++s) {
+    const plsvo_cand_structopt& I = in[s]; const CandMapDev& M = c->cd_maps[(size_t)s];
+    StructSelJobDev& J = jobs[s];
+    memset(&J, 0, sizeof(J));
+    J.active = I.active ? 1 : 0; J.frame_id = I.frame_id;
+    if (!J.active) continue;
+    J.pt_keep = c->cs_w.ptkeep.as<uint8_t>(); J.seg_keep = c->cs_w.segkeep.as<uint8_t>();
+    if (I.pt_keep) { J.pt_keep = din + b_pk; if (sc[3 * (size_t)s] > 0) memcpy(blob.at<uint8_t>(b_pk) + M.opt_off, I.pt_keep, (size_t)sc[3 * (size_t)s]); }
+    if (I.seg_keep) { J.seg_keep = din + b_sk; if (sc[3 * (size_t)s + 1] > 0) memcpy(blob.at<uint8_t>(b_sk) + 2 * M.oseg_off, I.seg_keep, (size_t)sc[3 * (size_t)s + 1]); }
+  }
+  int rc;
+  if ((rc = upload_blob(c, c->co_d_in, blob))) return rc;
+  Carver w;
+  const size_t w_cnt = w.take<int>(N * 2), w_plm = w.take<int>(N * (size_t)max_pts), w_pit = w.take<int>(N * (size_t)max_pts), w_ppos = w.take<double>(N * (size_t)max_pts * 3),
+               w_slm = w.take<int>(N * (size_t)max_segs), w_sit = w.take<int>(N * (size_t)max_segs), w_ss = w.take<double>(N * (size_t)max_segs * 3),
+               w_se = w.take<double>(N * (size_t)max_segs * 3);
+  HIP_TRY(c, c->co_d_rep.ensure(w.off + 256));
+  StructSelBatchDev b{};
+  b.s = c->cs_b;
+  b.jobs = reinterpret_cast<const StructSelJobDev*>(din + b_jobs);
+  b.pt_last_optim = c->co_d_key.as<int>(); b.seg_last_optim = c->co_d_key.as<int>() + c->cd_t_pt;
+  b.max_n_pts = max_pts; b.n_iter_pts = pr->n_iter_pts; b.max_n_segs = max_segs; b.n_iter_segs = pr->n_iter_segs;
+  b.r_counts = Carver::dev<int>(c->co_d_rep, w_cnt); b.r_pt_lm = Carver::dev<int>(c->co_d_rep, w_plm); b.r_pt_iters = Carver::dev<int>(c->co_d_rep, w_pit);
+  b.r_pt_pos = Carver::dev<double>(c->co_d_rep, w_ppos); b.r_seg_lm = Carver::dev<int>(c->co_d_rep, w_slm); b.r_seg_iters = Carver::dev<int>(c->co_d_rep, w_sit);
+  b.r_seg_spos = Carver::dev<double>(c->co_d_rep, w_ss); b.r_seg_epos = Carver::dev<double>(c->co_d_rep, w_se);
+  HIP_TRY_TIMED(c, PLSVO_K_STRUCTOPT, launch_map_optimize_structure(b, c->stream));
+  c->co_b = b; c->co_rep_bytes = w.off;
+  c->co_done = c->co_have_out = true;
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_structure_fetch(plsvo_ctx* c, int n, plsvo_cand_structopt_out* out) {
+  CTX_CHECK(c);
+  if (!c->cd_staged || !c->co_have_out) return fail(c, PLSVO_E_STATE, "candidates_structure_fetch: no structure optimisation since the tables were staged");
+  if (n > 0 && !out) return fail(c, PLSVO_E_INVALID, "candidates_structure_fetch: bad arguments");
+  if (n != c->cd_n) return fail(c, PLSVO_E_INVALID, "candidates_structure_fetch: n does not match the staged batch");
+  if (n == 0) return PLSVO_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const StructSelBatchDev& b = c->co_b;
+  Readback rb;                                     // the report is one allocation: one range
+  rb.add(c->co_d_rep.p, c->co_rep_bytes);
+  if (const int rc = rb.wait(c)) return rc;
+  const char* base = reinterpret_cast<const char*>(c->co_d_rep.p);
+  auto H = [&](const void* dev) { return rb.at<char>(0) + (reinterpret_cast<const char*>(dev) - base); };
+  auto cp = [&](void* dst, const void* dev, size_t at, size_t count, size_t elem) { if (dst && count) memcpy(dst, H(dev) + at * elem, count * elem); };
+  const int* cnt = reinterpret_cast<const int*>(H(b.r_counts));
+  bool fits = true;                                // the counts first, for every stream: no buffer is written unless all of them hold their entries
+  for (int s = 0; s < n; ++s) {
+    plsvo_cand_structopt_out& O = out[s];
+    O.n_sel_pt = cnt[2 * s]; O.n_sel_seg = cnt[2 * s + 1];
+    if ((O.pt_lm || O.pt_iters || O.pt_pos) && O.n_sel_pt > O.cap_pt) fits = false;
+    if ((O.seg_lm || O.seg_iters || O.seg_spos || O.seg_epos) && O.n_sel_seg > O.cap_seg) fits = false;
+  }
+  if (!fits) return fail(c, PLSVO_E_INVALID, "candidates_structure_fetch: a stream selected more entries than its buffers' cap_pt / cap_seg hold; nothing was copied");
+  for (int s = 0; s < n; ++s) {
+    plsvo_cand_structopt_out& O = out[s];
+    const size_t np = (size_t)O.n_sel_pt, ns = (size_t)O.n_sel_seg, po = (size_t)s * (size_t)b.max_n_pts, so = (size_t)s * (size_t)b.max_n_segs;
+    cp(O.pt_lm, b.r_pt_lm, po, np, sizeof(int)); cp(O.pt_iters, b.r_pt_iters, po, np, sizeof(int)); cp(O.pt_pos, b.r_pt_pos, po * 3, np * 3, sizeof(double));
+    cp(O.seg_lm, b.r_seg_lm, so, ns, sizeof(int)); cp(O.seg_iters, b.r_seg_iters, so, ns, sizeof(int));
+    cp(O.seg_spos, b.r_seg_spos, so * 3, ns * 3, sizeof(double)); cp(O.seg_epos, b.r_seg_epos, so * 3, ns * 3, sizeof(double));
+  }
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_set_last_optim(plsvo_ctx* c, int n, const plsvo_cand_last_optim_in* in) {
+  CTX_CHECK(c);
+  if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_set_last_optim: no staged map tables");
+  if (const int rc = cand_seeds_pending(c, "candidates_set_last_optim")) return rc;
+  if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_set_last_optim: n does not match the staged batch");
+  if (n == 0) return PLSVO_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  int* d = c->co_d_key.as<int>();
+  for (int s = 0; s < n; ++s) {
+    const CandMapDev& M = c->cd_maps[(size_t)s];
+    if (in[s].pt_last_optim && M.n_pt) HIP_TRY(c, hipMemcpyAsync(d + M.pt_off, in[s].pt_last_optim, (size_t)M.n_pt * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if (in[s].seg_last_optim && M.n_seg) HIP_TRY(c, hipMemcpyAsync(d + c->cd_t_pt + M.seg_off, in[s].seg_last_optim, (size_t)M.n_seg * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));      // the caller's arrays are free again
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_fetch_last_optim(plsvo_ctx* c, int n, plsvo_cand_last_optim_out* out) {
+  CTX_CHECK(c);
+  if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_fetch_last_optim: no staged map tables");
+  if (const int rc = cand_seeds_pending(c, "candidates_fetch_last_optim")) return rc;
+  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_fetch_last_optim: n does not match the staged batch");
+  if (n == 0) return PLSVO_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  Readback rb;
+  rb.add(c->co_d_key.p, (c->cd_t_pt + c->cd_t_seg) * sizeof(int));
+  if (const int rc = rb.wait(c)) return rc;
+  const int* h = rb.at<int>(0);
+  for (int s = 0; s < n; ++s) {
+    const CandMapDev& M = c->cd_maps[(size_t)s];
+    if (out[s].pt_last_optim && M.n_pt) memcpy(out[s].pt_last_optim, h + M.pt_off, (size_t)M.n_pt * sizeof(int));
+    if (out[s].seg_last_optim && M.n_seg) memcpy(out[s].seg_last_optim, h + c->cd_t_pt + M.seg_off, (size_t)M.n_seg * sizeof(int));
+  }
   return PLSVO_OK;
 }
 

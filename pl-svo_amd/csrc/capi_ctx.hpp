@@ -33,6 +33,7 @@ hipError_t launch_map_select(const SelectBatchDev& b, hipStream_t stream);      
 hipError_t launch_map_insert_plan(const InsertBatchDev& b, hipStream_t stream);       // insert_device.hpp, in seeds_kernels.hip
 hipError_t launch_map_insert(const InsertBatchDev& b, hipStream_t stream);
 hipError_t launch_map_set_positions(const PositionsBatchDev& b, hipStream_t stream);
+hipError_t launch_map_optimize_structure(const StructSelBatchDev& b, hipStream_t stream);   // structsel_device.hpp, in seeds_kernels.hip
 hipError_t launch_map_add_candidates(const NewCandBatchDev& b, hipStream_t stream);   // newcand_device.hpp, in seeds_kernels.hip
 hipError_t launch_update_seeds_resident(const SeedListBatchDev& b, hipStream_t stream);   // seedlist_device.hpp, in seeds_kernels.hip
 hipError_t launch_seeds_commit(const SeedListBatchDev& b, hipStream_t stream);
@@ -235,6 +236,13 @@ struct plsvo_ctx {
   bool ci_inserted = false, ci_have_out = false;
   std::vector<InsertPlanDev> ci_last;
   DevBuf ci_d_work, ci_d_in, ci_d_plan, ci_d_pos;
+  // structure optimisation on the resident tables (plsvo_candidates_optimize_structure ..): last_structure_optim_ per landmark row of
+  // capacity, an allocation of its own zeroed at stage time (co_d_key: points, then segments); a call's records and host masks (co_d_in);
+  // the report (co_d_rep) and the launch that wrote it (co_b); whether this run was optimised, whether there is a report since the stage
+  bool co_done = false, co_have_out = false;
+  DevBuf co_d_key, co_d_in, co_d_rep;
+  size_t co_rep_bytes = 0;
+  StructSelBatchDev co_b{};
   // new candidate landmarks (plsvo_candidates_add ..): the landmark room plsvo_candidates_reserve_landmarks asks for (cn_reserve: the next
   // stage's), per stream the rows its layout was made with and the candidate counts a run's fetch reports (cd_host), whether an add
   // closed the open run, the last report

@@ -420,6 +420,20 @@ struct PositionsBatchDev {          // plsvo_candidates_set_positions: moved lan
   const long long* pt_at; const double* pt_src; const long long* seg_at; const double* seg_ssrc; const double* seg_esrc;
   double* pt_pos; double* seg_spos; double* seg_epos;
 };
+// structure optimisation on the resident map tables (structsel_device.hpp, include/plsvo_hip.h plsvo_candidates_optimize_structure): one
+// wave per stream chooses the least recently refined landmarks among the selection's kept features and refines them in place.
+struct StructSelJobDev {            // one stream's record
+  const uint8_t* pt_keep; const uint8_t* seg_keep;   // keep masks in selection order (device), whole-batch arrays: rows from opt_off / 2 * oseg_off
+  int active, frame_id;
+};
+struct StructSelBatchDev {
+  SelectBatchDev s;
+  const StructSelJobDev* jobs;
+  int* pt_last_optim; int* seg_last_optim;           // last_structure_optim_ per landmark row of capacity (pt_off / seg_off)
+  int max_n_pts, n_iter_pts, max_n_segs, n_iter_segs;   // the caps are also the report's rows per stream
+  // the report: 2 counts per stream; per selected entry its landmark, residual evaluations and position(s) behind its run
+  int* r_counts; int* r_pt_lm; int* r_pt_iters; double* r_pt_pos; int* r_seg_lm; int* r_seg_iters; double* r_seg_spos; double* r_seg_epos;
+};
 
 // corner detection (detect_device.hpp, include/plsvo_hip.h plsvo_hip_detect_fast): tile geometry and the launch record
 constexpr int kDetTileW = 64, kDetTileH = 32;          // pixels of a tile that one workgroup decides

@@ -29,6 +29,7 @@
 #include "insert_device.hpp"     // and the keyframe insertion into the resident tables
 #include "newcand_device.hpp"    // and the new candidate landmarks appended to them
 #include "seedlist_device.hpp"   // and the seed lists kept resident beside them
+#include "structsel_device.hpp"  // and the structure optimisation of their least recently refined landmarks
 
 namespace plsvo_hip {
 
@@ -512,6 +513,12 @@ hipError_t launch_map_set_positions(const PositionsBatchDev& b, hipStream_t stre
 hipError_t launch_map_insert(const InsertBatchDev& b, hipStream_t stream) {
   if (b.s.c.n_jobs <= 0) return hipSuccess;
   hipLaunchKernelGGL(map_insert_kernel, dim3((b.s.c.n_jobs + kInsWaves - 1) / kInsWaves), dim3(64 * kInsWaves), 0, stream, b);
+  return hipGetLastError();
+}
+// structure optimisation on the resident tables (structsel_device.hpp): the same shape
+hipError_t launch_map_optimize_structure(const StructSelBatchDev& b, hipStream_t stream) {
+  if (b.s.c.n_jobs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_optimize_structure_kernel, dim3((b.s.c.n_jobs + kStsWaves - 1) / kStsWaves), dim3(64 * kStsWaves), 0, stream, b);
   return hipGetLastError();
 }
 // new candidate landmarks (newcand_device.hpp): the same shape

@@ -47,7 +47,10 @@ map_set_positions, and only a seed that converges into a NEW candidate stages ag
 backend with map_add_candidates) that last restage goes too: the converged seed is appended to the resident tables on the device
 (plsvo_candidates_add) as a new landmark row with one observation and an entry at the back of the candidate list, and the
 stage is called once, at the first frame.  The
-features reach the pose optimiser in selection order; a segment that won both of its cells is a feature twice.
+features reach the pose optimiser in selection order; a segment that won both of its cells is a feature twice.  With
+structopt_resident=True (cell_select, a backend with map_optimize_structure) the structure optimisation runs on the resident tables too
+(plsvo_candidates_optimize_structure): one call on every tracked frame, points and segments, ahead of an insertion; the
+harness takes the moved positions and the keys from the call's report.
 
 `backend` is duck-typed: load_frames(list of level-0 images; HipBackend also takes raw frames with rectify=), sparse_align(job), reproject(job), match_direct(job),
 pose_optimize(job), for mapping structure_optimize(job), update_seeds(job), and for kf_select close_keyframes(job), keyframe_decide(job).  The product backend is HipBackend (C ABI on the GPU, no fallback); tests pass an oracle-backed one
@@ -152,6 +155,17 @@ class HipBackend:
     def map_set_positions(self, pt_idx, pt_pos):
         """moved point landmarks into the resident tables (plsvo_candidates_set_positions)"""
         self.ctx.candidates_set_positions([dict(pt_idx=pt_idx, pt_pos=pt_pos)])
+
+    def map_optimize_structure(self, frame_id, **params):
+        """FrameHandlerBase::optimizeStructure on the resident tables (plsvo_candidates_optimize_structure, DESIGN.md 3.17) behind the last
+        map_select, with the keep masks the resident pose optimiser left on the device; params: max_n_pts, n_iter_pts, max_n_segs,
+        n_iter_segs (20 / 5 / 20 / 5).  -> what was refined: capi.Context.candidates_structure_fetch's record"""
+        self.ctx.candidates_optimize_structure([dict(frame_id=frame_id)], **params)
+        return self.ctx.candidates_structure_fetch()[0]
+
+    def map_set_last_optim(self, pt_last_optim, seg_last_optim):
+        """the landmarks' last_structure_optim_ carried over a restage (plsvo_candidates_set_last_optim)"""
+        self.ctx.candidates_set_last_optim([dict(pt_last_optim=pt_last_optim, seg_last_optim=seg_last_optim)])
 
     def map_reserve_landmarks(self, **room):
         """landmark rows per stream for the candidates to come (plsvo_candidates_reserve_landmarks; no arguments: today's layout again)"""
@@ -307,7 +321,7 @@ def candidate_map_tables(t):
 def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_thresh=2.0, mapping=False, known_frac=0.6,
                  pos_noise=0.005, map_seed=0, kf_every=5, detect=False, detect_cell_size=25, kf_select=False, kfselect_mindist_t=0.06,
                  kfselect_mindist_r=3.0, max_n_kfs=10, map_candidates=False, record_candidates=False, cell_select=False, select_params=None, kf_insert=False,
-                 seed_candidates=False, seeds_resident=False, image_seeds=None, image_seed_params=None):
+                 seed_candidates=False, seeds_resident=False, image_seeds=None, image_seed_params=None, structopt_resident=False):
     """-> list of per-frame dicts (pose T_f_w, cov, counts).  Frame 0 is the keyframe with the true pose.
     mapping=True: only `known_frac` of the point landmarks start in the map (positions off by `pos_noise` x depth along
     their viewing ray), the others are depth-filter seeds; the seed update runs every frame; every `kf_every`-th frame
@@ -357,8 +371,17 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
     reports, and gives a converged image seed a table row of its own without a landmark (such rows are selected, optimised and inserted
     on the device like any other; the harness's own alignment and structure optimisation leave them out).  The records gain
     n_image_seeds / n_image_seeds_converged / n_image_seeds_started.  image_seed_params: fast_threshold, detection_threshold (20, 20.0).
-    When frame 0's keyframe leaves the table the resident lists are given up as without this flag, image seeds included."""
+    When frame 0's keyframe leaves the table the resident lists are given up as without this flag, image seeds included.
+    structopt_resident=True (with mapping and cell_select, a backend with map_optimize_structure): step 5 runs on the resident tables
+    (plsvo_candidates_optimize_structure) in place of the gather / structure_optimize / map_set_positions of the harness:
+    one call on EVERY tracked frame, behind the pose optimiser and ahead of an insertion as in processFrame (:340), points and segments,
+    with the resident keep masks and frame_id = k.  The harness takes the moved positions for its own tables from the call's report and
+    follows the keys from it, to carry them over a restage (map_set_last_optim).  The records gain n_structopt_pt / n_structopt_seg, and
+    with record_candidates rec["structopt"]: the tables and the keys before, the selection, the masks, the report, and both after.
+    With the flag off every record is what it is without it."""
     params = dict(locals())                            # (first statement: exactly the arguments)
+    if structopt_resident and not (mapping and cell_select and hasattr(backend, "map_optimize_structure")):
+        raise ValueError("structopt_resident needs mapping, cell_select and a backend with map_optimize_structure()")
     if image_seeds not in (None, "host", "device") or (image_seeds and not (seeds_resident and hasattr(backend, "seeds_keyframe_detect" if image_seeds == "device" else "detect_corners"))):
         raise ValueError("image_seeds is None, 'host' or 'device', needs seeds_resident and a backend with detect_corners() / seeds_keyframe_detect()")
     if seeds_resident and not (seed_candidates and hasattr(backend, "seeds_stage")):
@@ -384,7 +407,7 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
 
 def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thresh, mapping, known_frac, pos_noise, map_seed, kf_every, detect, detect_cell_size, kf_select,
                   kfselect_mindist_t, kfselect_mindist_r, max_n_kfs, map_candidates, record_candidates, cell_select, select_params, kf_insert, seed_candidates, seeds_resident,
-                  image_seeds=None, image_seed_params=None):
+                  image_seeds=None, image_seed_params=None, structopt_resident=False):
     cam = seq["cam"]
     img_kw = dict(fast_threshold=20, detection_threshold=20.0)
     img_kw.update(image_seed_params or {})
@@ -468,6 +491,7 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
         row_lm = list(range(n_pts))
         lm_row = np.arange(n_pts, dtype=np.int64)
         quality = None                                 # cell_select: the quality state after the last frame (None: nothing staged yet)
+        so_keys = dict(pt=[], seg=[])                  # structopt_resident: last_structure_optim_ per table row, followed from the reports (0: never refined)
         select_kw = dict(max_fts=120, max_fts_segs=100, cell_order=None, seg_cell_order=None, reproj_thresh=reproj_thresh)
         select_kw.update(select_params or {})
     for k in range(1, len(seq["images"])):
@@ -514,6 +538,9 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                     cm_before = copy.deepcopy(cm) if record_candidates else None
                     cr, mr, sel, pr_sel, q_after = backend.map_select(map_job, abi.CandidateFrameJob(T_k, overlap, cur_slot=k), cam, n_pyr_levels, select_kw,
                                                                       carry=quality if map_job is not None else None)
+                    if structopt_resident and map_job is not None and (any(so_keys["pt"]) or any(so_keys["seg"])):
+                        # the keys do not survive a stage: carried over like the quality counters (rows appended since read 0)
+                        backend.map_set_last_optim(so_keys["pt"] + [0] * (len(cm["pt_pos"]) - len(so_keys["pt"])), so_keys["seg"] + [0] * (len(cm["seg_spos"]) - len(so_keys["seg"])))
                     if seeds_resident and map_job is not None and mapping and seed_kf is not None:
                         # the seed lists join the tables that were just staged: every seed was started in frame 0's keyframe, in one batch
                         # that never ages (the harness keeps its seeds until they converge)
@@ -635,6 +662,24 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                     add_keyframe(T_k, dec["key_pts"], P3[kept])
                     if dec["has_depth"]:
                         seed_depth = (dec["depth_mean"] * 2.0, 0.1 * dec["depth_min"])
+            if structopt_resident:
+                # ---- 5. structure optimisation on the resident tables, ahead of the insertion as in processFrame (:340 before :358) ----
+                for name, rows in (("pt", len(cm["pt_pos"])), ("seg", len(cm["seg_spos"]))):
+                    so_keys[name] += [0] * (rows - len(so_keys[name]))
+                before = (copy.deepcopy(cm), copy.deepcopy(so_keys)) if record_candidates else None
+                so = backend.map_optimize_structure(k)
+                for row, p in zip(so["pt_lm"], so["pt_pos"]):
+                    cm["pt_pos"][int(row)] = [float(x) for x in p]
+                    so_keys["pt"][int(row)] = k
+                    if row_lm[int(row)] >= 0:
+                        P3[row_lm[int(row)]] = p
+                for row, a, b in zip(so["seg_lm"], so["seg_spos"], so["seg_epos"]):
+                    cm["seg_spos"][int(row)], cm["seg_epos"][int(row)] = [float(x) for x in a], [float(x) for x in b]
+                    so_keys["seg"][int(row)] = k
+                rec.update(n_structopt_pt=int(so["n_sel_pt"]), n_structopt_seg=int(so["n_sel_seg"]))
+                if record_candidates:
+                    rec["structopt"] = dict(stream=before[0], keys_before=before[1], select=sel, pt_keep=pr.pt_keep.copy(), seg_keep=pr.seg_keep.copy(), frame_id=k, report=so,
+                                            tables=copy.deepcopy(cm), keys=copy.deepcopy(so_keys))
             if is_kf:
                 for i, brg in zip(kept, _bearing(cam, px_new[kept])):
                     obs[int(i)].append((k, brg))
@@ -710,7 +755,7 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                     cm_dirty = True
             # ---- 5. structure optimisation (FrameHandlerBase::optimizeStructure: the 20 least recently refined, :202-237) ----
             cand = np.array([i for i in kept if len(obs[int(i)]) >= 2], np.int64)
-            if len(cand) and is_kf:
+            if len(cand) and is_kf and not structopt_resident:
                 sel = cand[np.argsort(last_optim[cand], kind="stable")[:20]]
                 off, ofr, of_ = [0], [], []
                 for i in sel:

@@ -173,7 +173,7 @@ __global__ void __launch_bounds__(256) chain_select_kernel(const ChainBatchDev b
     double l[3] = { sf[1] * ef[2] - sf[2] * ef[1], sf[2] * ef[0] - sf[0] * ef[2], sf[0] * ef[1] - sf[1] * ef[0] };
     const double n = sqrt(l[0] * l[0] + l[1] * l[1]);
     for (int d = 0; d < 3; ++d) { b.seg_line[3 * o + d] = l[d] / n; b.seg_spos[3 * o + d] = b.pos[3 * cs + d]; b.seg_epos[3 * o + d] = b.pos[3 * ce + d]; }
-    b.seg_level[o] = max(b.search_level[cs], 0);
+    b.seg_level[o] = max(b.search_level[ce], 0);   // Matcher::search_level_ as the END point's match left it (src/matcher.cpp:264, src/reprojector.cpp:373)
   }
   if (tid == 0) {
     PoseJobDev& P = b.po_jobs[j];

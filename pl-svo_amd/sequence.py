@@ -626,7 +626,7 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
             line = np.cross(sf, ef)
             line = line / np.sqrt(line[:, 0:1] ** 2 + line[:, 1:2] ** 2) if len(seg_i) else np.zeros((0, 3))    # feature.cpp:103-104
             pj = abi.PoseOptJob(T_k, abs(cam[0]), reproj_thresh, 10, _bearing(cam, px_new[pt_i]), P3[pt_i], level[pt_i], line,
-                                seq["seg_spos"][seg_i], seq["seg_epos"][seg_i], level[n_pts + seg_i])
+                                seq["seg_spos"][seg_i], seq["seg_epos"][seg_i], level[n_pts + n_seg + seg_i])       # a LineFeat's level: the END point's (matcher.cpp:264)
             pr = backend.pose_optimize(pj)
         n_ties = backend.align_ties() if hasattr(backend, "align_ties") else None
         if kf_select and not map_candidates:

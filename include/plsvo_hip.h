@@ -1181,8 +1181,7 @@ int plsvo_candidates_fetch_last_optim(plsvo_ctx* ctx, int n, plsvo_cand_last_opt
 /* segments are separate landmark spaces.  The callbacks' depth_sigma2 arguments are unused by  */
 /* the reference and are not part of this interface.  The landmark's position is an INPUT: the  */
 /* pt_xyz_world / seg_xyz_world_s / _e plsvo_update_seeds reports, passed through unchanged.    */
-/* Landmark rows are never reclaimed: a landmark deleted later keeps its row, and a restage     */
-/* (plsvo_candidates_stage) is the only compaction.                                             */
+/* A landmark deleted later keeps its row until plsvo_candidates_compact (below) reclaims it.    */
 /* ------------------------------------------------------------------------------------------ */
 
 #define PLSVO_LM_EVENT_NEW      8   /* a landmark appended by plsvo_candidates_add since the last selection */
@@ -1243,6 +1242,59 @@ int plsvo_candidates_reserve_landmarks(plsvo_ctx* ctx, const plsvo_cand_lm_reser
 int plsvo_candidates_lm_capacity(plsvo_ctx* ctx, int n, plsvo_cand_lm_reserve* out);
 int plsvo_candidates_add(plsvo_ctx* ctx, int n, const plsvo_cand_new* in);
 int plsvo_candidates_add_fetch(plsvo_ctx* ctx, int n, plsvo_cand_add_out* out);
+
+/* ------------------------------------------------------------------------------------------ */
+/* compaction of the resident map tables: the landmark rows whose type is PLSVO_LM_DELETED      */
+/* leave, in place (one wave per stream).  It is what Map::emptyTrash           */
+/* (src/map.cpp:259-275) does for the reference's heap: list surgery, no arithmetic.  Per kind  */
+/* (points and segments are separate landmark spaces) the live rows close up in a stable way -- */
+/* remap[old] = number of live rows below old, -1 for a deleted row -- and everything of a row  */
+/* moves with it bit for bit: position(s), type, n_failed_reproj_, n_succeeded_reproj_, the     */
+/* event byte, the last_structure_optim_ key, the observation list.  The observation arrays     */
+/* hold the live rows' lists in row order (a deleted row's list, emptied or left over, is       */
+/* dropped), the keyframes' feature lists and the candidate lists are rewritten through the     */
+/* remap.  Pinned where a precondition of the tables could be broken: a keyframe feature that   */
+/* points at a deleted row becomes -1 (safeDelete*'s ftr->feat3D = NULL), a candidate entry     */
+/* that does is erased by a stable compaction of its list (deleteCandidate*); both are counted. */
+/* A freed row reads as one that was never used (its last_structure_optim_ key is 0).  Keyframe */
+/* rows, feature-list lengths and order, -1 features and the seed tables do not change.  Order  */
+/* is kept everywhere, so no result of any later frame changes.                                 */
+/* ------------------------------------------------------------------------------------------ */
+
+#define PLSVO_COMPACT_STANDBY  0    /* the stream is untouched, byte for byte */
+#define PLSVO_COMPACT_ALWAYS   1
+#define PLSVO_COMPACT_ROOM     2    /* a kind is compacted only where rows - n_landmarks < min_room: decided on the device, per kind */
+
+typedef struct plsvo_cand_compact {
+  int32_t mode;                     /* PLSVO_COMPACT_* */
+  int32_t min_room_pt, min_room_seg;
+  int32_t reserved0;
+} plsvo_cand_compact;
+
+/* What the last plsvo_candidates_compact did to one stream. */
+typedef struct plsvo_cand_compact_out {
+  int32_t ran_pt, ran_seg;          /* 1: the kind was compacted (also when no row of it was deleted) */
+  int32_t n_pt_before, n_pt_after, n_seg_before, n_seg_after;
+  int32_t n_pt_obs_before, n_pt_obs_after, n_seg_obs_before, n_seg_obs_after;
+  int32_t n_pt_cand_before, n_pt_cand_after, n_seg_cand_before, n_seg_cand_after;
+  int32_t n_repointed_pt, n_repointed_seg;       /* keyframe features that pointed at a deleted row */
+  int32_t n_erased_pt_cand, n_erased_seg_cand;   /* candidate entries that did */
+  int32_t* pt_remap;                /* n_pt_before entries, may be NULL; the identity where the kind did not run */
+  int32_t* seg_remap;               /* n_seg_before entries, may be NULL */
+} plsvo_cand_compact_out;
+
+/* compact: one launch (timed under PLSVO_K_INSERT) and one synchronisation, like the insertion; the host's mirrors (landmark counts,
+ * used observation entries, candidate counts) describe the new tables afterwards, so the capacity checks of plsvo_candidates_add, the
+ * insertion, _fetch_map, _fetch_quality, _set_quality and plsvo_seeds_keyframe see the new sizes, and a repeated plsvo_seeds_update
+ * finds the room on the device.  Every check runs before anything is written: PLSVO_E_INVALID for another n than staged, NULL in with
+ * n > 0, an unknown mode, a negative threshold; PLSVO_E_STATE before a stage and between plsvo_seeds_update and its fetch.  A compaction
+ * ends the open run as an add and an insertion do (plsvo_candidates_match / _set_match / _select / _pose_optimize / _dev /
+ * _optimize_structure / _insert_keyframe return PLSVO_E_STATE until the next plsvo_candidates_run); the closed run's fetches keep
+ * returning its results, in the OLD row numbers.  It is legal behind an insertion and behind adds.
+ * compact_fetch: host only unless a remap is asked for; valid until the next call that moves the tables (a stage, an insertion, an add,
+ * a seed update, another compaction), PLSVO_E_STATE afterwards and before the first compaction. */
+int plsvo_candidates_compact(plsvo_ctx* ctx, int n, const plsvo_cand_compact* in);
+int plsvo_candidates_compact_fetch(plsvo_ctx* ctx, int n, plsvo_cand_compact_out* out);
 
 /* TUM-style trajectory record of a frame (app/run_pipeline.cpp:425-451): the camera pose in the world,
  * T_f_w^-1, as tx ty tz qx qy qz qw.  Returns 1 and fills out7 when the reference would write the line, 0 when

@@ -342,6 +342,22 @@ class CandAddOut(C.Structure):
     _fields_ = [(f, C.c_int32) for f in ("first_pt", "first_seg", "n_added_pt", "n_added_seg", "n_pt", "n_seg", "n_pt_cand", "n_seg_cand", "n_pt_obs", "n_seg_obs")]
 
 
+COMPACT_STANDBY, COMPACT_ALWAYS, COMPACT_ROOM = 0, 1, 2
+_CAND_COMPACT_COUNTS = ("ran_pt", "ran_seg", "n_pt_before", "n_pt_after", "n_seg_before", "n_seg_after", "n_pt_obs_before", "n_pt_obs_after", "n_seg_obs_before",
+                        "n_seg_obs_after", "n_pt_cand_before", "n_pt_cand_after", "n_seg_cand_before", "n_seg_cand_after", "n_repointed_pt", "n_repointed_seg",
+                        "n_erased_pt_cand", "n_erased_seg_cand")
+
+
+class CandCompact(C.Structure):
+    """plsvo_cand_compact"""
+    _fields_ = [("mode", C.c_int32), ("min_room_pt", C.c_int32), ("min_room_seg", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class CandCompactOut(C.Structure):
+    """plsvo_cand_compact_out"""
+    _fields_ = [(f, C.c_int32) for f in _CAND_COMPACT_COUNTS] + [("pt_remap", c_i32_p), ("seg_remap", c_i32_p)]
+
+
 SEED_NOT_VISIBLE, SEED_NO_MATCH, SEED_UPDATED, SEED_CONVERGED, SEED_NAN, SEED_AGED = 0, 1, 2, 3, 4, 5
 SEEDS_NO_ROOM = 1
 _c_float_p = C.POINTER(C.c_float)

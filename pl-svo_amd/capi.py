@@ -33,6 +33,7 @@ SYMBOLS = [
     "plsvo_candidates_reserve", "plsvo_candidates_capacity", "plsvo_candidates_insert_keyframe", "plsvo_candidates_insert_fetch", "plsvo_candidates_fetch_map", "plsvo_candidates_set_positions",
     "plsvo_candidates_optimize_structure", "plsvo_candidates_structure_fetch", "plsvo_candidates_set_last_optim", "plsvo_candidates_fetch_last_optim",
     "plsvo_candidates_reserve_landmarks", "plsvo_candidates_lm_capacity", "plsvo_candidates_add", "plsvo_candidates_add_fetch",
+    "plsvo_candidates_compact", "plsvo_candidates_compact_fetch",
     "plsvo_seeds_reserve", "plsvo_seeds_capacity", "plsvo_seeds_stage", "plsvo_seeds_update", "plsvo_seeds_update_fetch", "plsvo_seeds_keyframe", "plsvo_seeds_fetch_lists",
     "plsvo_seeds_fetch_rows", "plsvo_seeds_commit_rows", "plsvo_seeds_keyframe_detect", "plsvo_seeds_keyframe_fetch",
     "plsvo_chain_stage", "plsvo_chain_run", "plsvo_chain_fetch", "plsvo_frame_step_batch", "plsvo_chain_poses_dev",
@@ -179,6 +180,8 @@ def lib():
         "plsvo_candidates_lm_capacity": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandLmReserve)]),
         "plsvo_candidates_add": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandNew)]),
         "plsvo_candidates_add_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandAddOut)]),
+        "plsvo_candidates_compact": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandCompact)]),
+        "plsvo_candidates_compact_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandCompactOut)]),
         "plsvo_seeds_reserve": (C.c_int, [ctxp, C.POINTER(abi.SeedReserve)]),
         "plsvo_seeds_capacity": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.SeedReserve)]),
         "plsvo_seeds_stage": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.SeedParams), C.POINTER(abi.SeedList)]),
@@ -985,6 +988,47 @@ class Context:
         outs = (abi.CandAddOut * max(n, 1))()
         self._chk(self.L.plsvo_candidates_add_fetch(self.h, n, outs))
         return [{f: int(getattr(o, f)) for f, _ in abi.CandAddOut._fields_} for o in outs[:n]]
+
+    # ---- compaction of the resident map tables over their deleted landmark rows ----
+    def candidates_compact(self, modes):
+        """plsvo_candidates_compact (one launch, one synchronisation): per staged stream None / 0 (stands by), "always" / 1, or
+        "room" / 2 -- as a plain mode, a (mode, min_room_pt, min_room_seg) tuple or a dict of those names.  The landmark and candidate
+        counts this object keeps follow the report"""
+        names = dict(standby=abi.COMPACT_STANDBY, always=abi.COMPACT_ALWAYS, room=abi.COMPACT_ROOM)
+        n = len(modes)
+        arr = (abi.CandCompact * max(n, 1))()
+        for a, m in zip(arr, modes):
+            if m is None:
+                continue
+            if isinstance(m, dict):
+                m = (m.get("mode", abi.COMPACT_ALWAYS), m.get("min_room_pt", 0), m.get("min_room_seg", 0))
+            elif not isinstance(m, (tuple, list)):
+                m = (m, 0, 0)
+            a.mode, a.min_room_pt, a.min_room_seg = int(names.get(m[0], m[0])), int(m[1]), int(m[2])
+        self._chk(self.L.plsvo_candidates_compact(self.h, n, arr))
+        outs = (abi.CandCompactOut * max(n, 1))()
+        self._chk(self.L.plsvo_candidates_compact_fetch(self.h, n, outs))
+        for now, o in zip(self._cand_now, outs[:n]):
+            now["pt"], now["seg"], now["pt_cand"], now["seg_cand"] = o.n_pt_after, o.n_seg_after, o.n_pt_cand_after, o.n_seg_cand_after
+
+    def candidates_compact_fetch(self, remap=True):
+        """plsvo_candidates_compact_fetch: per stream a dict of abi.CandCompactOut's counts and, with remap, pt_remap / seg_remap over the
+        old rows (-1: the row was deleted; the identity where the kind did not run)"""
+        n = len(self._cand_maps)
+        outs = (abi.CandCompactOut * max(n, 1))()
+        bufs = []
+        for o, m in zip(outs, self._cand_cap):
+            b = dict(pt_remap=np.full(max(m["pt"], 1), -9, np.int32), seg_remap=np.full(max(m["seg"], 1), -9, np.int32)) if remap else {}
+            for k, v in b.items():
+                setattr(o, k, self._ptr(v))
+            bufs.append(b)
+        self._chk(self.L.plsvo_candidates_compact_fetch(self.h, n, outs))
+        res = []
+        for o, b in zip(outs[:n], bufs):
+            r = {f: int(getattr(o, f)) for f in abi._CAND_COMPACT_COUNTS}
+            r.update({k: v[:(o.n_pt_before if k == "pt_remap" else o.n_seg_before)].copy() for k, v in b.items()})
+            res.append(r)
+        return res
 
     def candidates_set_positions(self, moved):
         """plsvo_candidates_set_positions (enqueue only after the copy): per staged stream None or a dict of pt_idx / pt_pos [k, 3] and

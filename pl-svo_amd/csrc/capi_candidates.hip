@@ -23,11 +23,11 @@ static QualitySections quality_sections(const plsvo_ctx* c) {
   s.pt_ev = q.take<uint8_t>(c->cd_t_pt); s.seg_ev = q.take<uint8_t>(c->cd_t_seg); s.end = q.off;
   return s;
 }
-static void cand_reset_run(plsvo_ctx* c) { c->cd_ran = c->cd_matched = c->cs_selected = c->cs_posed = c->ci_inserted = c->cn_closed = c->co_done = false; }   // the steps taken on the last run's results
-static void cand_reset_stage(plsvo_ctx* c) { cand_reset_run(c); c->cd_staged = c->ci_have_out = c->cn_have_out = c->co_have_out = c->sd_staged = c->sd_pending = c->sd_have_report = c->sk_have_report = false; }   // those, the tables, the last insertion's and add's reports
+static void cand_reset_run(plsvo_ctx* c) { c->cd_ran = c->cd_matched = c->cs_selected = c->cs_posed = c->ci_inserted = c->cn_closed = c->cc_closed = c->co_done = false; }   // the steps taken on the last run's results
+static void cand_reset_stage(plsvo_ctx* c) { cand_reset_run(c); c->cd_staged = c->ci_have_out = c->cn_have_out = c->cc_have_out = c->co_have_out = c->sd_staged = c->sd_pending = c->sd_have_report = c->sk_have_report = false; }   // those, the tables, the last insertion's and add's reports
 // PLSVO_OK while the last run's candidates still describe the tables; once an insertion or an add came behind it, the refusal of entry point `who`
 static int cand_run_open(plsvo_ctx* c, const char* who) {
-  const char* why = c->ci_inserted ? "this run's frame was inserted" : c->cn_closed ? "landmarks were added behind this run" : nullptr;
+  const char* why = c->ci_inserted ? "this run's frame was inserted" : c->cn_closed ? "landmarks were added behind this run" : c->cc_closed ? "the tables were compacted behind this run" : nullptr;
   return why ? fail(c, PLSVO_E_STATE, std::string(who) + ": " + why + " (the tables have moved on); run again") : PLSVO_OK;
 }
 // between plsvo_seeds_update and plsvo_seeds_update_fetch the tables' sizes are known to the device alone: the refusal of entry point `who`
@@ -337,7 +337,7 @@ extern "C" int plsvo_candidates_match_fetch(plsvo_ctx* c, int n, plsvo_cand_matc
 extern "C" int plsvo_candidates_dev(plsvo_ctx* c, plsvo_cand_dev* o) {
   CTX_CHECK(c);
   if (!o) return fail(c, PLSVO_E_INVALID, "candidates_dev: bad arguments");
-  if (!c->cd_staged || !c->cd_ran || c->cd_n == 0 || c->ci_inserted || c->cn_closed) return fail(c, PLSVO_E_STATE, "candidates_dev: no candidates on the device");
+  if (!c->cd_staged || !c->cd_ran || c->cd_n == 0 || c->ci_inserted || c->cn_closed || c->cc_closed) return fail(c, PLSVO_E_STATE, "candidates_dev: no candidates on the device");
   if (const int rc = cand_seeds_pending(c, "candidates_dev")) return rc;
   const CandBatchDev& b = c->cd_b; const MatchBatchDev& mb = c->cd_match;
   o->n_entries = (int64_t)c->cd_total_m; o->n_frames = (int64_t)c->cd_total_f;
@@ -702,7 +702,7 @@ extern "C" int plsvo_candidates_insert_keyframe(plsvo_ctx* c, int n, const plsvo
     c->ci_last[(size_t)s] = P;
   }
   c->cd_max_level = std::max(c->cd_max_level, c->cd_params.n_pyr_levels - 1);   // the new observations' levels are the matcher's search levels
-  c->ci_inserted = true; c->ci_have_out = true;
+  c->ci_inserted = true; c->ci_have_out = true; c->cc_have_out = false;   // (a compaction's report describes the tables before this)
   return PLSVO_OK;
 }
 
@@ -993,6 +993,9 @@ extern "C" int plsvo_candidates_add(plsvo_ctx* c, int n, const plsvo_cand_new* i
     const CandStreamHost& H = c->cd_host[(size_t)s];
     if ((long long)M.n_pt + I.n_pt > H.rows_pt || (long long)M.n_seg + I.n_seg > H.rows_seg)
       return fail(c, PLSVO_E_CAPACITY, "candidates_add: a stream lacks landmark rows (plsvo_candidates_reserve_landmarks); nothing was changed");
+    // (implied by the landmark rows until a compaction frees rows of landmarks that had left the candidate list)
+    if ((long long)M.n_pt_cand + I.n_pt > H.rows_pt_cand || (long long)M.n_seg_cand + I.n_seg > H.rows_seg_cand)
+      return fail(c, PLSVO_E_CAPACITY, "candidates_add: a stream lacks candidate-list rows (plsvo_candidates_reserve_landmarks); nothing was changed");
     if ((long long)H.n_pt_obs + I.n_pt > H.cap_pt_obs || (long long)H.n_seg_obs + I.n_seg > H.cap_seg_obs)
       return fail(c, PLSVO_E_CAPACITY, "candidates_add: a stream lacks observation entries (plsvo_candidates_reserve); nothing was changed");
   }
@@ -1003,6 +1006,7 @@ extern "C" int plsvo_candidates_add(plsvo_ctx* c, int n, const plsvo_cand_new* i
     plsvo_cand_add_out& O = c->cn_last[(size_t)s];
     O.first_pt = I.n_pt ? M.n_pt : -1; O.first_seg = I.n_seg ? M.n_seg : -1; O.n_added_pt = I.n_pt; O.n_added_seg = I.n_seg;
   }
+  c->cc_have_out = false;
   c->cn_closed = true; c->cn_have_out = true;       // (an add of nothing ends the run too: the rule does not depend on the counts)
   if (t_pt + t_seg == 0) return PLSVO_OK;
   if (t_pt > (size_t)INT32_MAX || t_seg > (size_t)INT32_MAX) return fail(c, PLSVO_E_CAPACITY, "candidates_add: batch too large");
@@ -1076,6 +1080,86 @@ extern "C" int plsvo_candidates_add_fetch(plsvo_ctx* c, int n, plsvo_cand_add_ou
   return PLSVO_OK;
 }
 
+// ---- compaction of the resident map tables over their deleted landmark rows (compact_device.hpp) ------------------------------
+extern "C" int plsvo_candidates_compact(plsvo_ctx* c, int n, const plsvo_cand_compact* in) {
+  CTX_CHECK(c);
+  if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_compact: no staged map tables");
+  if (const int rc = cand_seeds_pending(c, "candidates_compact")) return rc;
+  if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_compact: n does not match the staged batch");
+  for (int s = 0; s < n; ++s) {
+    if (in[s].mode < PLSVO_COMPACT_STANDBY || in[s].mode > PLSVO_COMPACT_ROOM) return fail(c, PLSVO_E_INVALID, "candidates_compact: unknown mode");
+    if (in[s].min_room_pt < 0 || in[s].min_room_seg < 0) return fail(c, PLSVO_E_INVALID, "candidates_compact: negative threshold");
+  }
+  const size_t N = (size_t)n;
+  c->cc_closed = true; c->cc_have_out = false;      // (a compaction of nothing ends the run too: the rule does not depend on the modes)
+  c->cc_last.assign(N, CompactReportDev{});
+  if (n == 0) { c->cc_have_out = true; return PLSVO_OK; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  Blob blob;
+  const size_t b_jobs = blob.reserve<CompactJobDev>(N);
+  for (int s = 0; s < n; ++s) {
+    CompactJobDev& J = blob.at<CompactJobDev>(b_jobs)[s]; const CandStreamHost& H = c->cd_host[(size_t)s];
+    J.mode = in[s].mode; J.min_room_pt = in[s].min_room_pt; J.min_room_seg = in[s].min_room_seg; J.rows_pt = H.rows_pt; J.rows_seg = H.rows_seg; J.reserved0 = 0;
+  }
+  int rc;
+  if ((rc = upload_blob(c, c->cc_d_in, blob))) return rc;
+  Carver w;
+  const size_t w_rep = w.take<CompactReportDev>(N), w_pt = w.take<int>(c->cd_t_pt), w_seg = w.take<int>(c->cd_t_seg);
+  HIP_TRY(c, c->cc_d_work.ensure(w.off + 256));
+  c->cc_remap_off = w_pt; c->cc_remap_seg = w_seg; c->cc_work_end = w.off;
+  const QualitySections q = quality_sections(c);
+  char* dq = reinterpret_cast<char*>(c->cs_d_q.p);
+  CompactBatchDev b{};
+  b.c = c->cd_b;
+  b.pt_nfail = reinterpret_cast<int*>(dq + q.pt_nf); b.pt_nsucc = reinterpret_cast<int*>(dq + q.pt_ns);
+  b.seg_nfail = reinterpret_cast<int*>(dq + q.seg_nf); b.seg_nsucc = reinterpret_cast<int*>(dq + q.seg_ns);
+  b.pt_event = reinterpret_cast<uint8_t*>(dq + q.pt_ev); b.seg_event = reinterpret_cast<uint8_t*>(dq + q.seg_ev);
+  b.pt_key = c->co_d_key.as<int>(); b.seg_key = c->co_d_key.as<int>() + c->cd_t_pt;
+  b.jobs = Blob::dev<CompactJobDev>(c->cc_d_in, b_jobs); b.report = Carver::dev<CompactReportDev>(c->cc_d_work, w_rep);
+  b.pt_remap = Carver::dev<int>(c->cc_d_work, w_pt); b.seg_remap = Carver::dev<int>(c->cc_d_work, w_seg);
+  HIP_TRY_TIMED(c, PLSVO_K_INSERT, launch_map_compact(b, c->stream));
+  Readback rb;
+  rb.add(b.report, N * sizeof(CompactReportDev));
+  if ((rc = rb.wait(c))) return rc;
+  c->cc_last.assign(rb.at<CompactReportDev>(0), rb.at<CompactReportDev>(0) + n);
+  // -- the host mirrors describe the new tables
+  for (int s = 0; s < n; ++s) {
+    const CompactReportDev& R = c->cc_last[(size_t)s];
+    CandMapDev& M = c->cd_maps[(size_t)s]; CandStreamHost& H = c->cd_host[(size_t)s];
+    M.n_pt = R.n_pt_after; M.n_seg = R.n_seg_after; M.n_pt_cand = R.n_pt_cand_after; M.n_seg_cand = R.n_seg_cand_after;
+    H.n_pt_obs = R.n_pt_obs_after; H.n_seg_obs = R.n_seg_obs_after;
+  }
+  c->cc_have_out = true;
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_compact_fetch(plsvo_ctx* c, int n, plsvo_cand_compact_out* out) {
+  CTX_CHECK(c);
+  if (!c->cd_staged || !c->cc_have_out) return fail(c, PLSVO_E_STATE, "candidates_compact_fetch: no compaction, or the tables have moved since the last one");
+  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_compact_fetch: n does not match the staged batch");
+  bool remaps = false;
+  for (int s = 0; s < n; ++s) {
+    const CompactReportDev& R = c->cc_last[(size_t)s]; plsvo_cand_compact_out& O = out[s];
+    static_assert(sizeof(CompactReportDev) == 18 * sizeof(int32_t) && offsetof(plsvo_cand_compact_out, pt_remap) >= sizeof(CompactReportDev), "the device's report is the head of the public one");
+    memcpy(&O, &R, sizeof(R));
+    if ((O.pt_remap && R.ran_pt) || (O.seg_remap && R.ran_seg)) remaps = true;
+  }
+  Readback rb;
+  if (remaps) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    rb.add(Carver::dev<char>(c->cc_d_work, c->cc_remap_off), c->cc_work_end - c->cc_remap_off);   // both remaps are one range
+    if (const int rc = rb.wait(c)) return rc;
+  }
+  for (int s = 0; s < n; ++s) {
+    const CompactReportDev& R = c->cc_last[(size_t)s]; plsvo_cand_compact_out& O = out[s]; const CandMapDev& M = c->cd_maps[(size_t)s];
+    const int* const hp = remaps ? rb.at<int>(0) + M.pt_off : nullptr;
+    const int* const hs = remaps ? reinterpret_cast<const int*>(rb.at<char>(0) + (c->cc_remap_seg - c->cc_remap_off)) + M.seg_off : nullptr;
+    if (O.pt_remap) for (int k = 0; k < R.n_pt_before; ++k) O.pt_remap[k] = R.ran_pt ? hp[k] : k;
+    if (O.seg_remap) for (int k = 0; k < R.n_seg_before; ++k) O.seg_remap[k] = R.ran_seg ? hs[k] : k;
+  }
+  return PLSVO_OK;
+}
+
 // ---- depth-filter seed lists resident beside the map tables (seedlist_device.hpp) -------------------------------------------
 namespace {
 // the sections of sd_d_work: reports, then the shadow rows (SeedsBatchDev's outputs, one per capacity row)
@@ -1108,7 +1192,7 @@ static int seeds_enqueue(plsvo_ctx* c, int n, const std::vector<SeedFrameDev>& f
   if (launch_update) HIP_TRY_TIMED(c, PLSVO_K_SEEDS, launch_update_seeds_resident(b, c->stream));
   HIP_TRY_TIMED(c, PLSVO_K_NEWCAND, launch_seeds_commit(b, c->stream));
   c->cd_max_level = std::max(c->cd_max_level, c->sd_max_level);   // a new landmark's observation has its seed's level
-  c->cn_closed = true;                              // the open run is over, as behind plsvo_candidates_add
+  c->cn_closed = true; c->cc_have_out = false;      // the open run is over, as behind plsvo_candidates_add
   c->sd_pending = true; c->sd_have_report = false;
   (void)n;
   return PLSVO_OK;

@@ -35,6 +35,7 @@ hipError_t launch_map_insert(const InsertBatchDev& b, hipStream_t stream);
 hipError_t launch_map_set_positions(const PositionsBatchDev& b, hipStream_t stream);
 hipError_t launch_map_optimize_structure(const StructSelBatchDev& b, hipStream_t stream);   // structsel_device.hpp, in seeds_kernels.hip
 hipError_t launch_map_add_candidates(const NewCandBatchDev& b, hipStream_t stream);   // newcand_device.hpp, in seeds_kernels.hip
+hipError_t launch_map_compact(const CompactBatchDev& b, hipStream_t stream);           // compact_device.hpp, in seeds_kernels.hip
 hipError_t launch_update_seeds_resident(const SeedListBatchDev& b, hipStream_t stream);   // seedlist_device.hpp, in seeds_kernels.hip
 hipError_t launch_seeds_commit(const SeedListBatchDev& b, hipStream_t stream);
 hipError_t launch_seeds_keyframe(const SeedListBatchDev& b, hipStream_t stream);
@@ -250,6 +251,12 @@ struct plsvo_ctx {
   bool cn_closed = false, cn_have_out = false;
   std::vector<plsvo_cand_add_out> cn_last;
   DevBuf cn_d_in;
+  // compaction over the deleted landmark rows (plsvo_candidates_compact ..): whether one closed the open run, the last report (valid until
+  // the tables move again), a call's records (cc_d_in), the reports and the per-landmark remap scratch (cc_d_work: points, then segments)
+  bool cc_closed = false, cc_have_out = false;
+  std::vector<CompactReportDev> cc_last;
+  DevBuf cc_d_in, cc_d_work;
+  size_t cc_remap_off = 0, cc_remap_seg = 0, cc_work_end = 0;   // sections of cc_d_work: the two remaps, the end
   // resident seed lists (plsvo_seeds_*): the room plsvo_seeds_reserve asks for (the next stage's), per stream the host mirror of its
   // record (sd_host: list lengths, upper bounds between a keyframe event and the next update fetch) and the rows it may fill (sd_lim);
   // the tables (sd_d_tab: records, workgroup map, rows), shadow rows and reports (sd_d_work), a call's upload (sd_d_in).  A candidate

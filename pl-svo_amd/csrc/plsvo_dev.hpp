@@ -435,6 +435,24 @@ struct StructSelBatchDev {
   int* r_counts; int* r_pt_lm; int* r_pt_iters; double* r_pt_pos; int* r_seg_lm; int* r_seg_iters; double* r_seg_spos; double* r_seg_epos;
 };
 
+// compaction of the resident map tables (compact_device.hpp, include/plsvo_hip.h plsvo_candidates_compact): one wave per stream closes
+// the stream's rows up over its deleted landmarks, in place.
+struct CompactJobDev {              // one stream's record
+  int mode, min_room_pt, min_room_seg;               // 0 = stand by, 1 = compact, 2 = a kind only where rows - n_lm < min_room
+  int rows_pt, rows_seg, reserved0;                  // the landmark rows the stream was laid out with (CandStreamHost)
+};
+struct CompactReportDev {           // plsvo_cand_compact_out's counts, field for field
+  int ran_pt, ran_seg, n_pt_before, n_pt_after, n_seg_before, n_seg_after, n_pt_obs_before, n_pt_obs_after, n_seg_obs_before, n_seg_obs_after;
+  int n_pt_cand_before, n_pt_cand_after, n_seg_cand_before, n_seg_cand_after, n_repointed_pt, n_repointed_seg, n_erased_pt_cand, n_erased_seg_cand;
+};
+struct CompactBatchDev {
+  CandBatchDev c;
+  int* pt_nfail; int* pt_nsucc; int* seg_nfail; int* seg_nsucc; uint8_t* pt_event; uint8_t* seg_event;   // the resident landmark quality
+  int* pt_key; int* seg_key;                         // last_structure_optim_ per landmark row (StructSelBatchDev)
+  const CompactJobDev* jobs; CompactReportDev* report;
+  int* pt_remap; int* seg_remap;                     // per landmark row (pt_off / seg_off): its new row, -1 = deleted; written where the kind ran
+};
+
 // corner detection (detect_device.hpp, include/plsvo_hip.h plsvo_hip_detect_fast): tile geometry and the launch record
 constexpr int kDetTileW = 64, kDetTileH = 32;          // pixels of a tile that one workgroup decides
 constexpr int kDetImgX0 = 8, kDetImgY0 = 5;            // LDS image origin = tile origin - (8, 5): a halo of 5 (Shi-Tomasi: x - 5 .. x + 4), 8 keeps rows dword-aligned

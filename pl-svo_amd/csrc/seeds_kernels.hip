@@ -27,6 +27,7 @@
 #include "candidates_device.hpp" // and the map candidates' kernel
 #include "select_device.hpp"     // and their cell selection
 #include "insert_device.hpp"     // and the keyframe insertion into the resident tables
+#include "compact_device.hpp"    // and their compaction over the deleted landmark rows
 #include "newcand_device.hpp"    // and the new candidate landmarks appended to them
 #include "seedlist_device.hpp"   // and the seed lists kept resident beside them
 #include "structsel_device.hpp"  // and the structure optimisation of their least recently refined landmarks
@@ -525,6 +526,12 @@ hipError_t launch_map_optimize_structure(const StructSelBatchDev& b, hipStream_t
 hipError_t launch_map_add_candidates(const NewCandBatchDev& b, hipStream_t stream) {
   if (b.c.n_jobs <= 0) return hipSuccess;
   hipLaunchKernelGGL(map_add_candidates_kernel, dim3((b.c.n_jobs + kNewWaves - 1) / kNewWaves), dim3(64 * kNewWaves), 0, stream, b);
+  return hipGetLastError();
+}
+// compaction over the deleted landmark rows (compact_device.hpp): the same shape
+hipError_t launch_map_compact(const CompactBatchDev& b, hipStream_t stream) {
+  if (b.c.n_jobs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_compact_kernel, dim3((b.c.n_jobs + kCmpWaves - 1) / kCmpWaves), dim3(64 * kCmpWaves), 0, stream, b);
   return hipGetLastError();
 }
 

@@ -177,6 +177,13 @@ class HipBackend:
         self.ctx.candidates_add([new])
         return self.ctx.candidates_add_fetch()[0], self.ctx.candidates_fetch_quality()[0]
 
+    def map_compact(self, mode="always", min_room_pt=0, min_room_seg=0):
+        """the resident tables close up over their deleted landmark rows (plsvo_candidates_compact); mode: "always", or
+        "room" -- a kind only where fewer than min_room rows of it are free.  -> (the tables as they now stand, the quality state, what the
+        compaction did with pt_remap / seg_remap over the old rows: capi.Context.candidates_compact_fetch's record)"""
+        self.ctx.candidates_compact([(mode, min_room_pt, min_room_seg)])
+        return self.ctx.candidates_fetch_map()[0], self.ctx.candidates_fetch_quality()[0], self.ctx.candidates_compact_fetch()[0]
+
     def seeds_stage(self, lists, cam, room=None, **params):
         """the stream's seed lists become a resident table beside the staged map tables (plsvo_seeds_stage); lists: the
         arrays of plsvo_seed_list and batch_counter as capi.Context.seeds_stage takes them; room: extra_pt / extra_seg rows for the seeds
@@ -321,7 +328,7 @@ def candidate_map_tables(t):
 def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_thresh=2.0, mapping=False, known_frac=0.6,
                  pos_noise=0.005, map_seed=0, kf_every=5, detect=False, detect_cell_size=25, kf_select=False, kfselect_mindist_t=0.06,
                  kfselect_mindist_r=3.0, max_n_kfs=10, map_candidates=False, record_candidates=False, cell_select=False, select_params=None, kf_insert=False,
-                 seed_candidates=False, seeds_resident=False, image_seeds=None, image_seed_params=None, structopt_resident=False):
+                 seed_candidates=False, seeds_resident=False, image_seeds=None, image_seed_params=None, structopt_resident=False, compact=None, lm_room=None):
     """-> list of per-frame dicts (pose T_f_w, cov, counts).  Frame 0 is the keyframe with the true pose.
     mapping=True: only `known_frac` of the point landmarks start in the map (positions off by `pos_noise` x depth along
     their viewing ray), the others are depth-filter seeds; the seed update runs every frame; every `kf_every`-th frame
@@ -378,8 +385,17 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
     with the resident keep masks and frame_id = k.  The harness takes the moved positions for its own tables from the call's report and
     follows the keys from it, to carry them over a restage (map_set_last_optim).  The records gain n_structopt_pt / n_structopt_seg, and
     with record_candidates rec["structopt"]: the tables and the keys before, the selection, the masks, the report, and both after.
-    With the flag off every record is what it is without it."""
+    With the flag off every record is what it is without it.
+    compact="room" | "always" (with seed_candidates, a backend with map_compact; default None: nothing changes): behind every keyframe's
+    insertion the resident tables close up over their deleted POINT rows on the device (plsvo_candidates_compact) --
+    "always" at every keyframe, "room" only when fewer rows are free than seeds are alive, decided on the device.  The harness takes the
+    tables from the backend's fetch and applies the remap to its row <-> landmark maps and to the keys it follows.  The segments have no
+    reserve here (no segment seed exists) and are never compacted.  lm_room: landmark rows reserved per kind instead of one per seed of
+    the sequence; without compaction a sequence whose converged seeds outnumber it ends in PLSVO_E_CAPACITY.  Stable order is kept, so
+    every pose, covariance and count equals those of the run with the full reserve; the keyframe records gain n_compacted_pt."""
     params = dict(locals())                            # (first statement: exactly the arguments)
+    if compact not in (None, "room", "always") or (compact and not (seed_candidates and hasattr(backend, "map_compact"))):
+        raise ValueError("compact is None, 'room' or 'always' and needs seed_candidates and a backend with map_compact()")
     if structopt_resident and not (mapping and cell_select and hasattr(backend, "map_optimize_structure")):
         raise ValueError("structopt_resident needs mapping, cell_select and a backend with map_optimize_structure()")
     if image_seeds not in (None, "host", "device") or (image_seeds and not (seeds_resident and hasattr(backend, "seeds_keyframe_detect" if image_seeds == "device" else "detect_corners"))):
@@ -396,7 +412,7 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
     n_fr, n_lm = len(seq["images"]), len(seq["pt_pos"]) + 2 * len(seq["seg_spos"])
     backend.map_reserve(extra_kf=n_fr, extra_kf_pt=n_fr * n_lm, extra_kf_seg=n_fr * n_lm, extra_pt_obs=n_fr * n_lm, extra_seg_obs=n_fr * n_lm)
     if seed_candidates:                                # a landmark row per seed that can converge (its observation fits the room above)
-        backend.map_reserve_landmarks(extra_pt=len(seq["pt_pos"]), extra_seg=0)
+        backend.map_reserve_landmarks(extra_pt=len(seq["pt_pos"]) if lm_room is None else int(lm_room), extra_seg=0 if lm_room is None else int(lm_room))
     try:
         return _run_sequence(**params)
     finally:
@@ -407,7 +423,7 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
 
 def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thresh, mapping, known_frac, pos_noise, map_seed, kf_every, detect, detect_cell_size, kf_select,
                   kfselect_mindist_t, kfselect_mindist_r, max_n_kfs, map_candidates, record_candidates, cell_select, select_params, kf_insert, seed_candidates, seeds_resident,
-                  image_seeds=None, image_seed_params=None, structopt_resident=False):
+                  image_seeds=None, image_seed_params=None, structopt_resident=False, compact=None, lm_room=None):
     cam = seq["cam"]
     img_kw = dict(fast_threshold=20, detection_threshold=20.0)
     img_kw.update(image_seed_params or {})
@@ -732,6 +748,21 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                         seeds_on_device = seed_kf is not None
                         res_lm, res_kf, res_ftr = [], [], []
                     rec.update(n_joined=ins["n_joined_pt"] + ins["n_joined_seg"], n_deleted_kf=ins["n_deleted_pt"] + ins["n_deleted_seg"], remove_kf=remove)
+                    if compact:
+                        # Map::emptyTrash on the resident tables: the deleted point rows leave, the rows behind them move down; the
+                        # harness's rows follow the remap ("room": only when every live seed could no longer get a row)
+                        alive = len(seeds["idx"]) + sum(1 for v in res_lm if v < 0)
+                        tables, quality, cp = backend.map_compact("room", (1 << 30) if compact == "always" else alive, 0)
+                        if cp["ran_pt"]:
+                            cm = candidate_map_tables(tables)
+                            remap = cp["pt_remap"]
+                            lm_row[[lm for row, lm in enumerate(row_lm) if lm >= 0 and remap[row] < 0]] = -1
+                            row_lm = [lm for row, lm in enumerate(row_lm) if remap[row] >= 0]
+                            for row, lm in enumerate(row_lm):
+                                if lm >= 0:
+                                    lm_row[lm] = row
+                            so_keys["pt"] = [v for row, v in enumerate(so_keys["pt"]) if row >= len(remap) or remap[row] >= 0]
+                        rec["n_compacted_pt"] = int(cp["n_pt_before"] - cp["n_pt_after"])
                     if record_candidates:
                         rec["insert"] = dict(stream=before[0], quality_before=before[1], select=sel, pt_keep=pr.pt_keep.copy(), seg_keep=pr.seg_keep.copy(), T=[float(v) for v in T_k],
                                              slot=k, remove_kf=remove, tables=tables, quality=quality, report=ins)

@@ -11,7 +11,7 @@ With --kf-select (off by default; needs mapping) the keyframe stage runs on the 
 frame plays the keyframe when FrameHandlerMono::needNewKf says so instead of every fifth, and the JSON line lists the keyframe frames.
 With --map-candidates (off by default) reprojection and matching take their candidates from the map-candidate stage (plsvo_candidates_*):
 the overlap keyframes' features, one visit per landmark, the closest-view observation as the reference patch.
-usage: python tools/run_sequence.py [--distortion k1,k2,p1,p2[,k3]] [--detect] [--kf-select] [--map-candidates] [--cell-select] [--kf-insert] [--seed-candidates] [--seeds-resident] [--image-seeds host|device] [--structopt-resident] [out.txt] [n_frames] [seed] [mapping 0|1]"""
+usage: python tools/run_sequence.py [--distortion k1,k2,p1,p2[,k3]] [--detect] [--kf-select] [--map-candidates] [--cell-select] [--kf-insert] [--seed-candidates] [--seeds-resident] [--image-seeds host|device] [--structopt-resident] [--compact room|always] [--lm-room N] [out.txt] [n_frames] [seed] [mapping 0|1]"""
 import importlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -56,6 +56,15 @@ if "--image-seeds" in argv:
 structopt_resident = "--structopt-resident" in argv   # with --cell-select and mapping: the structure optimisation runs on the resident tables every tracked frame
 if structopt_resident:
     argv.remove("--structopt-resident")
+compact, lm_room = None, None                      # with --seed-candidates: the resident tables close up over their deleted point rows behind every keyframe
+if "--compact" in argv:
+    i = argv.index("--compact")
+    compact = argv[i + 1]
+    del argv[i:i + 2]
+if "--lm-room" in argv:                            # landmark rows reserved per kind instead of one per seed of the sequence
+    i = argv.index("--lm-room")
+    lm_room = int(argv[i + 1])
+    del argv[i:i + 2]
 sys.argv = sys.argv[:1] + argv
 
 out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "gpurun_out", "trajectory.txt")
@@ -71,7 +80,7 @@ if distortion is not None:
     seq = dict(seq, images=[P.synth.distort_image(img, dict(fx=fx, fy=fy, cx=cx, cy=cy, d=distortion)) for img in seq["images"]])
     rectify = P.abi.pinhole_radtan(w, h, fx, fy, cx, cy, distortion)
 res = seqm.run_sequence(seqm.HipBackend(ctx, rectify=rectify), seq, mapping=mapping, detect=detect, kf_select=kf_select, map_candidates=map_candidates, cell_select=cell_select, kf_insert=kf_insert,
-                        seed_candidates=seed_candidates, seeds_resident=seeds_resident, image_seeds=image_seeds, structopt_resident=structopt_resident,
+                        seed_candidates=seed_candidates, seeds_resident=seeds_resident, image_seeds=image_seeds, structopt_resident=structopt_resident, compact=compact, lm_room=lm_room,
                         image_seed_params=dict(fast_threshold=7, detection_threshold=2.0) if image_seeds else None)
 n = P.trajectory.write_trajectory(out, ["%.6f" % (0.05 * k) for k in range(n_frames)], [r["T"] for r in res], [r["cov"] for r in res])
 err = seqm.pose_errors(res, seq)
@@ -83,5 +92,6 @@ print(json.dumps({"frames": n_frames, "lines_written": n, "trajectory": out, "ma
                   **({"keyframes": [k for k, r in enumerate(res) if r.get("is_kf")], "overlap_last": res[-1].get("n_overlap"),
                       "depth_mean_last": res[-1].get("depth_mean")} if kf_select else {}),
                   **({"seed_candidates_per_frame": [r.get("n_seed_candidates", 0) for r in res[1:]],
-                      "seed_candidates_mean": sum(r.get("n_seed_candidates", 0) for r in res[1:]) / max(len(res) - 1, 1)} if seed_candidates else {})}))
+                      "seed_candidates_mean": sum(r.get("n_seed_candidates", 0) for r in res[1:]) / max(len(res) - 1, 1)} if seed_candidates else {}),
+                  **({"compacted_rows_per_keyframe": [r["n_compacted_pt"] for r in res if "n_compacted_pt" in r]} if compact else {})}))
 ctx.close()

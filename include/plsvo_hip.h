@@ -993,8 +993,11 @@ int plsvo_candidates_set_match(plsvo_ctx* ctx, int n, const plsvo_cand_match_out
 /*  - segment candidates of the removed keyframe are deleted and erased like point candidates;   */
 /*    the reference (src/map.cpp:73) calls removeFrameCandidates for points only and leaves a    */
 /*    segment candidate that observes a freed frame;                                             */
-/*  - Frame::key_pts_ (removeKeyPoint) are not in these tables: the deleted landmarks are        */
-/*    reported as events and the removed keyframe is the caller's own argument;                  */
+/*  - Frame::key_pts_ (removeKeyPoint) are not in THESE tables: the deleted landmarks are        */
+/*    reported as events and the removed keyframe is the caller's own argument.  They are a      */
+/*    table of their own beside them once plsvo_candidates_set_keypts has made it live (below,   */
+/*    "keyframe stage on the resident tables"): then the insertion keeps it up in a launch of    */
+/*    its own behind map_insert_kernel, which itself is what it was;                             */
 /*  - the observation list of a landmark deleted HERE is emptied (the reference clears it); a    */
 /*    landmark deleted earlier keeps its list, less the observations in the removed keyframe.    */
 /* Preconditions (unchecked) as for the selection, and: a landmark in a candidate list has       */
@@ -1295,6 +1298,100 @@ typedef struct plsvo_cand_compact_out {
  * a seed update, another compaction), PLSVO_E_STATE afterwards and before the first compaction. */
 int plsvo_candidates_compact(plsvo_ctx* ctx, int n, const plsvo_cand_compact* in);
 int plsvo_candidates_compact_fetch(plsvo_ctx* ctx, int n, plsvo_cand_compact_out* out);
+
+/* ------------------------------------------------------------------------------------------ */
+/* keyframe stage on the resident tables: Frame::key_pts_ as a resident table, and              */
+/* Map::getCloseKeyframes with the sort and the cut of Reprojector::reprojectMap                */
+/* (src/map.cpp:158-179, src/reprojector.cpp:147-163) on it, feeding the candidate stage        */
+/* without the host (one wave per stream).  The key-point table holds five      */
+/* int32 per keyframe row of capacity: the POSITION of key_pts_[k] in that keyframe's           */
+/* point-feature list (kf_pt_lm's CSR), -1 = NULL.  A feature's px is the observation of its    */
+/* landmark whose pt_obs_kf is the keyframe (the insertion's precondition: it exists).          */
+/* While the table is live, each entry point that changes the keyframes' feature lists keeps    */
+/* it up in a small launch of its own behind its kernel:                                        */
+/*  - plsvo_candidates_select: for every keyframe one of whose holders has lost its landmark     */
+/*    (Map::safeDeletePoint -> Frame::removeKeyPoint, src/map.cpp:116-123, src/frame.cpp:143-154) */
+/*    the NULL holders are dropped and Frame::setKeyPoints (:87-141) runs over the features that  */
+/*    hold a landmark, in list order, the surviving holders staying unless a feature is strictly  */
+/*    better (slots 3 and 4 compare x with cv, as the reference does);                           */
+/*  - plsvo_candidates_insert_keyframe: the rows close up over remove_kf, the keyframes that     */
+/*    lost a holder during the removal are rebuilt in the same way, and the new keyframe's row   */
+/*    is the key points of this run's plsvo_candidates_keyframe_decide (positions in selection   */
+/*    order), or, without one, setKeyPoints from five NULLs over its features that hold a        */
+/*    landmark after the insertion.  Features that joined a keyframe are ordinary features       */
+/*    from then on: only a rebuild picks them up;                                                */
+/*  - plsvo_candidates_compact moves landmark rows, not feature positions: nothing to do;         */
+/*  - plsvo_candidates_stage drops the table: call plsvo_candidates_set_keypts again.             */
+/* Pinned where the device's form differs from the reference's:                                 */
+/*  - the device sees a launch's deletions at once, the reference one by one.  A keyframe is     */
+/*    rebuilt if and only if one of the deleted features was a holder when the launch began;     */
+/*    afterwards every slot holds the best of the surviving features, a surviving holder winning  */
+/*    ties, the lowest position among equal features.  The event-by-event form can differ only   */
+/*    when two distinct features tie EXACTLY in a slot's value after an intermediate promotion    */
+/*    (a feature G that is strictly better than a slot's surviving holder H takes the slot in    */
+/*    the rebuild after the first deletion and is deleted itself later in the same launch; the   */
+/*    reference's next rebuild fills the empty slot with the FIRST feature of H's value, which   */
+/*    is another feature E when E ties with H exactly and stands before it; here H stays);       */
+/*  - a holder position outside its keyframe's feature list counts as NULL.                      */
+/* ------------------------------------------------------------------------------------------ */
+
+/* One stream's key points: 5 * n_kf positions (-1 = NULL), or NULL: computed on the device by Frame::setKeyPoints from five NULLs over
+ * each keyframe's features that hold a landmark -- what Frame::setKeyframe does to a fresh frame. */
+typedef struct plsvo_cand_keypts {
+  const int32_t* key_pts;
+} plsvo_cand_keypts;
+
+/* Caller buffer of 5 * keyframe CAPACITY entries (plsvo_candidates_capacity), or NULL: the first 5 * n_kf are the table, the rest -1. */
+typedef struct plsvo_cand_keypts_out {
+  int32_t* key_pts;
+} plsvo_cand_keypts_out;
+
+/* set_keypts: the staged keyframes get their key_pts_ and the table is LIVE from here to the next plsvo_candidates_stage; until it is
+ * called every other entry point enqueues exactly what it enqueues without this section.  in == NULL: every stream as with a NULL
+ * array.  Enqueue only: the caller's arrays are copied before it returns.
+ * fetch_keypts: synchronous.
+ * run_close: enqueue only.  plsvo_candidates_run with the overlap list decided on the device: `frames` are its records with
+ * n_overlap == 0 and overlap_idx == NULL (the pose from T_f_w or d_T_f_w).  One launch per batch does getCloseKeyframes on the resident
+ * kf_T, the live key-point table and the LIVE pt_pos of each key point's landmark, the stable sort by distance and the cut to
+ * max_n_kfs, and writes the stream's overlap list and count where the candidate kernel reads them; the unchanged candidate launch
+ * follows in the same enqueue.  plsvo_candidates_fetch's kf_count then needs n_kf entries per stream (those behind n_overlap are 0),
+ * and every later stage of the run works with the device-decided list.
+ * close_fetch: plsvo_close_kf_out per stream of the last run_close (close_idx / close_dist: buffers of n_kf entries or NULL); synchronises.
+ * PLSVO_E_STATE: set_keypts without staged tables; fetch_keypts / run_close without a live table; close_fetch without a run_close as
+ * the last run; any of them between plsvo_seeds_update and its fetch.  PLSVO_E_INVALID (nothing written): another n than staged, NULL
+ * frames / out with n > 0, a key point below -1, a negative slot or max_n_kfs, a non-zero n_overlap or a non-NULL overlap_idx. */
+int plsvo_candidates_set_keypts(plsvo_ctx* ctx, int n, const plsvo_cand_keypts* in);
+int plsvo_candidates_fetch_keypts(plsvo_ctx* ctx, int n, plsvo_cand_keypts_out* out);
+int plsvo_candidates_run_close(plsvo_ctx* ctx, int n, const plsvo_cand_frame* frames, int max_n_kfs);
+int plsvo_candidates_close_fetch(plsvo_ctx* ctx, int n, plsvo_close_kf_out* out);
+
+/* The keyframe decision on the resident selection: what plsvo_keyframe_decide computes with key_pts_prev all -1 -- getSceneDepth,
+ * needNewKf, setKeyPoints, getFurthestKeyframe -- with every input read where it already lies on the device: the optimised pose
+ * (plsvo_candidates_poses_dev), the new frame's features (the selection's f_pt_lm / f_pt_px / f_seg_lm) with the resident keep masks
+ * as alive, the landmark positions FROM THE TABLES, not from the copy the selection gathered for the pose optimiser
+ * (FrameHandlerBase::optimizeStructure, src/frame_handler_mono.cpp:340, runs before setKeyPoints / getSceneDepth, :351-352: a
+ * plsvo_candidates_optimize_structure or _set_positions behind the selection is seen), kf_T and the run's resident overlap list (the
+ * caller's of plsvo_candidates_run or the device's of plsvo_candidates_run_close).  Per stream only this record travels: */
+typedef struct plsvo_cand_kf_decide {
+  double T_last_w[7];               /* last_frame_->T_f_w_, which needNewKf measures from */
+  const double* d_T_last_w;         /* NULL, or a DEVICE pointer to 7 doubles read instead */
+  double kfselect_mindist_t;        /* Config::kfSelectMinDistT() */
+  double kfselect_mindist_r;        /* Config::kfSelectMinDistR() */
+  int32_t active;                   /* 0: the stream sits this call out; its record is what an earlier call of this run left (zeros before the first) */
+  int32_t reserved0;
+} plsvo_cand_kf_decide;
+
+/* keyframe_decide: enqueue only, valid after plsvo_candidates_pose_optimize of a run, any number of times.  The decision records (56
+ * bytes per stream) stay on the device: an insertion behind it, with a live key-point table, gives the new keyframe's row the decision's
+ * key points (indices in selection order = positions in the new keyframe's feature list) instead of building it from five NULLs; a
+ * key point whose feature the insertion leaves without a landmark is dropped and the row rebuilt, as for every other keyframe.
+ * decide_fetch: synchronises; plsvo_kf_decide_out per stream, key_pts in selection order.  delta_t / delta_r are optional buffers of
+ * n_overlap entries (after plsvo_candidates_run_close: of n_kf entries, the first n_overlap written); asking for them also brings the
+ * deltas and the device-decided counts over the bus.
+ * PLSVO_E_STATE: keyframe_decide before the pose optimisation of the last run or after an insertion, an add or a compaction closed it;
+ * decide_fetch without a decision on the last run.  PLSVO_E_INVALID (nothing written): another n than staged, NULL in / out with n > 0. */
+int plsvo_candidates_keyframe_decide(plsvo_ctx* ctx, int n, const plsvo_cand_kf_decide* in);
+int plsvo_candidates_decide_fetch(plsvo_ctx* ctx, int n, plsvo_kf_decide_out* out);
 
 /* TUM-style trajectory record of a frame (app/run_pipeline.cpp:425-451): the camera pose in the world,
  * T_f_w^-1, as tx ty tz qx qy qz qw.  Returns 1 and fills out7 when the reference would write the line, 0 when

@@ -213,6 +213,17 @@ class CandFrame(C.Structure):
     _fields_ = [("T_f_w", C.c_double * 7), ("d_T_f_w", C.c_void_p), ("cur_slot", C.c_int32), ("n_overlap", C.c_int32), ("overlap_idx", c_i32_p)]
 
 
+class CandKeyPts(C.Structure):
+    """plsvo_cand_keypts / plsvo_cand_keypts_out"""
+    _fields_ = [("key_pts", c_i32_p)]
+
+
+class CandKfDecide(C.Structure):
+    """plsvo_cand_kf_decide"""
+    _fields_ = [("T_last_w", C.c_double * 7), ("d_T_last_w", C.c_void_p), ("kfselect_mindist_t", C.c_double), ("kfselect_mindist_r", C.c_double),
+                ("active", C.c_int32), ("reserved0", C.c_int32)]
+
+
 class CandOut(C.Structure):
     """plsvo_cand_out"""
     _fields_ = [("n_filed_pt", C.c_int32), ("n_filed_seg", C.c_int32), ("pt_lm", c_i32_p), ("pt_px", c_double_p), ("pt_cell", c_i32_p), ("pt_obs", c_i32_p),

@@ -27,7 +27,7 @@ SYMBOLS = [
     "plsvo_poseopt_set_trace", "plsvo_poseopt_fetch_trace", "plsvo_poseopt_poses_dev", "plsvo_poseopt_copy_poses", "plsvo_poseopt_work", "plsvo_poseopt_refill_frames", "plsvo_poseopt_row_select",
     "plsvo_structure_optimize", "plsvo_structure_solve3", "plsvo_match_direct", "plsvo_match_warp_patches", "plsvo_reproject", "plsvo_trajectory_record", "plsvo_update_seeds",
     "plsvo_close_keyframes", "plsvo_keyframe_decide",
-    "plsvo_candidates_stage", "plsvo_candidates_run", "plsvo_candidates_fetch", "plsvo_candidates_match", "plsvo_candidates_match_fetch", "plsvo_candidates_dev",
+    "plsvo_candidates_stage", "plsvo_candidates_run", "plsvo_candidates_set_keypts", "plsvo_candidates_fetch_keypts", "plsvo_candidates_run_close", "plsvo_candidates_close_fetch", "plsvo_candidates_keyframe_decide", "plsvo_candidates_decide_fetch", "plsvo_candidates_fetch", "plsvo_candidates_match", "plsvo_candidates_match_fetch", "plsvo_candidates_dev",
     "plsvo_candidates_set_quality", "plsvo_candidates_fetch_quality", "plsvo_candidates_select", "plsvo_candidates_select_fetch", "plsvo_candidates_pose_optimize",
     "plsvo_candidates_pose_fetch", "plsvo_candidates_poses_dev", "plsvo_candidates_set_match",
     "plsvo_candidates_reserve", "plsvo_candidates_capacity", "plsvo_candidates_insert_keyframe", "plsvo_candidates_insert_fetch", "plsvo_candidates_fetch_map", "plsvo_candidates_set_positions",
@@ -154,6 +154,12 @@ def lib():
         "plsvo_keyframe_decide": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.KfDecideIn), C.POINTER(abi.KfDecideOut)]),
         "plsvo_candidates_stage": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandMap), C.POINTER(abi.CandParams)]),
         "plsvo_candidates_run": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandFrame)]),
+        "plsvo_candidates_set_keypts": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandKeyPts)]),
+        "plsvo_candidates_fetch_keypts": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandKeyPts)]),
+        "plsvo_candidates_run_close": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandFrame), C.c_int]),
+        "plsvo_candidates_close_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CloseKfOut)]),
+        "plsvo_candidates_keyframe_decide": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandKfDecide)]),
+        "plsvo_candidates_decide_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.KfDecideOut)]),
         "plsvo_candidates_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandOut)]),
         "plsvo_candidates_match": (C.c_int, [ctxp]),
         "plsvo_candidates_match_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandMatchOut)]),
@@ -679,6 +685,95 @@ class Context:
         self._chk(self.L.plsvo_candidates_run(self.h, n, arr))
         self._cand_frames = list(frames)
         self._cand_at_run = [dict(c) for c in self._cand_now]
+        self._cand_closed = False
+
+    # ---- keyframe stage on the resident tables ----
+    def candidates_set_keypts(self, key_pts=None):
+        """plsvo_candidates_set_keypts (enqueue only): per staged stream None (Frame::setKeyPoints from five NULLs, on the device) or
+        [n_kf, 5] positions in the keyframes' point-feature lists (-1 = NULL); key_pts=None: every stream None.  The table is live
+        until the next candidates_stage"""
+        n = len(self._cand_maps)
+        arr, keep = None, []
+        if key_pts is not None:
+            arr = (abi.CandKeyPts * max(n, 1))()
+            for a, k in zip(arr, key_pts):
+                if k is not None:
+                    v = np.ascontiguousarray(k, dtype=np.int32).reshape(-1)
+                    keep.append(v if v.size else np.full(5, -1, np.int32))
+                    a.key_pts = keep[-1].ctypes.data_as(abi.c_i32_p)
+        self._chk(self.L.plsvo_candidates_set_keypts(self.h, n, arr))
+
+    def candidates_fetch_keypts(self):
+        """plsvo_candidates_fetch_keypts: per stream the key-point table [keyframe capacity, 5]; the rows behind n_kf are -1"""
+        n = len(self._cand_maps)
+        outs = (abi.CandKeyPts * max(n, 1))()
+        bufs = [np.full((max(c["kf"], 1), 5), -9, np.int32) for c in self.candidates_capacity()]
+        for o, b in zip(outs, bufs):
+            o.key_pts = b.ctypes.data_as(abi.c_i32_p)
+        self._chk(self.L.plsvo_candidates_fetch_keypts(self.h, n, outs))
+        return [b[:c["kf"]] for b, c in zip(bufs, self.candidates_capacity())]
+
+    def candidates_run_close(self, frames, max_n_kfs=10, poses_dev=None):
+        """plsvo_candidates_run_close (enqueue only): candidates_run with the overlap lists decided on the device from the live
+        key-point table; frames: abi.CandidateFrameJob without an overlap list"""
+        n = len(frames)
+        arr = (abi.CandFrame * max(n, 1))(*[f.c for f in frames])
+        if poses_dev is not None:
+            for i in range(n):
+                arr[i].d_T_f_w = int(poses_dev[i]) if isinstance(poses_dev, (list, tuple)) else int(poses_dev) + 56 * i
+        self._chk(self.L.plsvo_candidates_run_close(self.h, n, arr, int(max_n_kfs)))
+        self._cand_frames = list(frames)
+        self._cand_at_run = [dict(c) for c in self._cand_now]
+        self._cand_closed = True
+
+    def candidates_close_fetch(self):
+        """plsvo_candidates_close_fetch: per stream what close_keyframes() reports, from the last candidates_run_close"""
+        n = len(self._cand_maps)
+        outs = (abi.CloseKfOut * max(n, 1))()
+        bufs = [(np.full(max(c["kf"], 1), -1, np.int32), np.zeros(max(c["kf"], 1))) for c in self.candidates_capacity()]
+        for o, (bi, bd) in zip(outs, bufs):
+            o.close_idx, o.close_dist = bi.ctypes.data_as(abi.c_i32_p), bd.ctypes.data_as(abi.c_double_p)
+        self._chk(self.L.plsvo_candidates_close_fetch(self.h, n, outs))
+        return [dict(n_close=int(o.n_close), n_overlap=int(o.n_overlap), close_idx=bi[:o.n_close].copy(), close_dist=bd[:o.n_close].copy())
+                for o, (bi, bd) in zip(outs[:n], bufs)]
+
+    def candidates_keyframe_decide(self, decides):
+        """plsvo_candidates_keyframe_decide (enqueue only, behind candidates_pose_optimize): per staged stream None (sits the call out) or
+        a dict of T_last_w (7 doubles) or d_T_last_w (a device pointer), and optionally kfselect_mindist_t (0.06) / kfselect_mindist_r (3.0)"""
+        n = len(decides)
+        arr = (abi.CandKfDecide * max(n, 1))()
+        for a, d in zip(arr, decides):
+            if d is None:
+                continue
+            a.active = 1
+            if d.get("T_last_w") is not None:
+                a.T_last_w = (C.c_double * 7)(*[float(v) for v in d["T_last_w"]])
+            if d.get("d_T_last_w") is not None:
+                a.d_T_last_w = int(d["d_T_last_w"])
+            a.kfselect_mindist_t, a.kfselect_mindist_r = float(d.get("kfselect_mindist_t", 0.06)), float(d.get("kfselect_mindist_r", 3.0))
+        self._chk(self.L.plsvo_candidates_keyframe_decide(self.h, n, arr))
+
+    def candidates_decide_fetch(self, deltas=True):
+        """plsvo_candidates_decide_fetch: per stream the dict keyframe_decide() returns, key_pts in selection order; deltas=False leaves
+        delta_t / delta_r on the device (the record alone crosses the bus)"""
+        n = len(self._cand_maps)
+        n_ov = room = [f.n_overlap for f in getattr(self, "_cand_frames", ())] or [0] * n   # (no run yet: the library refuses below)
+        if deltas and getattr(self, "_cand_closed", False):
+            n_ov, room = [c["n_overlap"] for c in self.candidates_close_fetch()], [c["kf"] for c in self.candidates_capacity()]
+        outs = (abi.KfDecideOut * max(n, 1))()
+        bufs = [(np.zeros(max(r, 1)), np.zeros(max(r, 1))) for r in room]
+        if deltas:
+            for o, (bt, br) in zip(outs, bufs):
+                o.delta_t, o.delta_r = bt.ctypes.data_as(abi.c_double_p), br.ctypes.data_as(abi.c_double_p)
+        self._chk(self.L.plsvo_candidates_decide_fetch(self.h, n, outs))
+        res = []
+        for o, k, (bt, br) in zip(outs[:n], n_ov, bufs):
+            r = dict(has_depth=int(o.has_depth), n_depth=int(o.n_depth), depth_mean=float(o.depth_mean), depth_min=float(o.depth_min), need_new_kf=int(o.need_new_kf),
+                     blocking=int(o.blocking), key_pts=np.array(list(o.key_pts), np.int32), furthest_kf=int(o.furthest_kf))
+            if deltas:
+                r.update(delta_t=bt[:k].copy(), delta_r=br[:k].copy())
+            res.append(r)
+        return res
 
     def candidates_fetch(self):
         """plsvo_candidates_fetch: per stream a dict of n_filed_pt / n_filed_seg, the filed points (pt_lm, pt_px [n, 2], pt_cell, pt_obs,
@@ -686,27 +781,31 @@ class Context:
         flags of the map's candidates"""
         maps, frames = self._cand_maps, self._cand_frames
         n = len(maps)
+        n_ov = [f.n_overlap for f in frames]
+        room = list(n_ov)
+        if getattr(self, "_cand_closed", False):        # the device decided the lists: a row of the keyframe table's size comes back
+            n_ov, room = [c["n_overlap"] for c in self.candidates_close_fetch()], [c["kf"] for c in self.candidates_capacity()]
         outs = (abi.CandOut * max(n, 1))()
         bufs = []
-        for o, m, f, cap in zip(outs, maps, frames, self._cand_cap):
+        for o, m, f, cap, kfc_room in zip(outs, maps, frames, self._cand_cap, room):
             cp, cs = max(cap["filed_pt"], 1), max(cap["filed_seg"], 1)
             b = dict(pt_lm=np.full(cp, -9, np.int32), pt_px=np.zeros((cp, 2)), pt_cell=np.full(cp, -9, np.int32), pt_obs=np.full(cp, -9, np.int32),
                      pt_has_view=np.full(cp, 9, np.uint8), pt_active=np.full(cp, 9, np.uint8),
                      seg_lm=np.full(cs, -9, np.int32), seg_px=np.zeros((cs, 4)), seg_cell=np.full((cs, 2), -9, np.int32), seg_obs=np.full(cs, -9, np.int32),
                      seg_has_view=np.full(cs, 9, np.uint8), seg_active=np.full(cs, 9, np.uint8),
-                     kf_count=np.full(max(f.n_overlap, 1), -9, np.int32), pt_cand_failed=np.full(max(cap["pt_cand"], 1), 9, np.uint8),
+                     kf_count=np.full(max(kfc_room, 1), -9, np.int32), pt_cand_failed=np.full(max(cap["pt_cand"], 1), 9, np.uint8),
                      seg_cand_failed=np.full(max(cap["seg_cand"], 1), 9, np.uint8))
             for k, v in b.items():
                 setattr(o, k, v.ctypes.data_as(abi.c_double_p if v.dtype == np.float64 else abi.c_u8_p if v.dtype == np.uint8 else abi.c_i32_p))
             bufs.append(b)
         self._chk(self.L.plsvo_candidates_fetch(self.h, n, outs))
         res = []
-        for o, m, f, b in zip(outs[:n], self._cand_at_run, frames, bufs):   # (the candidate lists as long as the run can have seen them)
+        for o, m, f_ov, b in zip(outs[:n], self._cand_at_run, n_ov, bufs):   # (the candidate lists as long as the run can have seen them)
             r = dict(n_filed_pt=int(o.n_filed_pt), n_filed_seg=int(o.n_filed_seg))
             for k, v in b.items():
                 cut = o.n_filed_pt if k.startswith("pt_") else o.n_filed_seg
                 if k == "kf_count":
-                    cut = f.n_overlap
+                    cut = f_ov
                 elif k == "pt_cand_failed":
                     cut = m["pt_cand"]
                 elif k == "seg_cand_failed":

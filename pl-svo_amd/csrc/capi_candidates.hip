@@ -23,8 +23,8 @@ static QualitySections quality_sections(const plsvo_ctx* c) {
   s.pt_ev = q.take<uint8_t>(c->cd_t_pt); s.seg_ev = q.take<uint8_t>(c->cd_t_seg); s.end = q.off;
   return s;
 }
-static void cand_reset_run(plsvo_ctx* c) { c->cd_ran = c->cd_matched = c->cs_selected = c->cs_posed = c->ci_inserted = c->cn_closed = c->cc_closed = c->co_done = false; }   // the steps taken on the last run's results
-static void cand_reset_stage(plsvo_ctx* c) { cand_reset_run(c); c->cd_staged = c->ci_have_out = c->cn_have_out = c->cc_have_out = c->co_have_out = c->sd_staged = c->sd_pending = c->sd_have_report = c->sk_have_report = false; }   // those, the tables, the last insertion's and add's reports
+static void cand_reset_run(plsvo_ctx* c) { c->cd_ran = c->cd_matched = c->cs_selected = c->cs_posed = c->ci_inserted = c->cn_closed = c->cc_closed = c->co_done = c->ck_have_close = c->ck_decided = false; }   // the steps taken on the last run's results
+static void cand_reset_stage(plsvo_ctx* c) { cand_reset_run(c); c->cd_staged = c->ci_have_out = c->cn_have_out = c->cc_have_out = c->co_have_out = c->sd_staged = c->sd_pending = c->sd_have_report = c->sk_have_report = c->ck_live = false; }   // those, the tables, the key-point table, the last insertion's and add's reports
 // PLSVO_OK while the last run's candidates still describe the tables; once an insertion or an add came behind it, the refusal of entry point `who`
 static int cand_run_open(plsvo_ctx* c, const char* who) {
   const char* why = c->ci_inserted ? "this run's frame was inserted" : c->cn_closed ? "landmarks were added behind this run" : c->cc_closed ? "the tables were compacted behind this run" : nullptr;
@@ -33,6 +33,13 @@ static int cand_run_open(plsvo_ctx* c, const char* who) {
 // between plsvo_seeds_update and plsvo_seeds_update_fetch the tables' sizes are known to the device alone: the refusal of entry point `who`
 static int cand_seeds_pending(plsvo_ctx* c, const char* who) {
   return c->sd_pending ? fail(c, PLSVO_E_STATE, std::string(who) + ": a seed update is not fetched yet (plsvo_seeds_update_fetch refreshes the tables' sizes)") : PLSVO_OK;
+}
+// the key-point table's upkeep behind a launch that changed the keyframes' feature lists (keystage_device.hpp); d_jobs: one record per stream, on the device
+static int keypts_enqueue(plsvo_ctx* c, const KeyPtsJobDev* d_jobs) {
+  KeyStageBatchDev b = c->ck_b;
+  b.c = c->cd_b; b.keypts = c->ck_d_keypts.as<int>(); b.kp_jobs = d_jobs; b.decided = c->ck_decided ? c->ck_dec_b.out : nullptr;
+  HIP_TRY_TIMED(c, PLSVO_K_KEYFRAME, launch_map_keypts(b, c->stream));
+  return PLSVO_OK;
 }
 }  // namespace
 
@@ -218,25 +225,19 @@ extern "C" int plsvo_candidates_stage(plsvo_ctx* c, int n, const plsvo_cand_map*
   return PLSVO_OK;
 }
 
-extern "C" int plsvo_candidates_run(plsvo_ctx* c, int n, const plsvo_cand_frame* fr) {
-  CTX_CHECK(c);
-  if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_run: no staged map tables");
-  if (const int rc = cand_seeds_pending(c, "candidates_run")) return rc;
-  if (n != c->cd_n || (n > 0 && !fr)) return fail(c, PLSVO_E_INVALID, "candidates_run: n does not match the staged batch");
+// plsvo_candidates_run (max_n_kfs < 0: the caller's overlap lists) and plsvo_candidates_run_close (the lists decided on the device by one
+// launch ahead of the candidate launch; a stream's overlap row then has room for every keyframe of its table)
+static int cand_run(plsvo_ctx* c, int n, const plsvo_cand_frame* fr, int max_n_kfs) {
+  const bool close = max_n_kfs >= 0;
   size_t t_ov = 0;
-  for (int s = 0; s < n; ++s) {
-    if (fr[s].n_overlap < 0 || fr[s].cur_slot < 0) return fail(c, PLSVO_E_INVALID, "candidates_run: negative count or slot");
-    if (fr[s].n_overlap > 0 && !fr[s].overlap_idx) return fail(c, PLSVO_E_INVALID, "candidates_run: null overlap list");
-    if (!cand_idx_ok(fr[s].overlap_idx, (size_t)fr[s].n_overlap, 0, c->cd_maps[(size_t)s].n_kf)) return fail(c, PLSVO_E_INVALID, "candidates_run: overlap index outside the keyframe table");
-    t_ov += (size_t)fr[s].n_overlap;
-  }
+  for (int s = 0; s < n; ++s) t_ov += close ? (size_t)c->cd_maps[(size_t)s].n_kf : (size_t)fr[s].n_overlap;
   cand_reset_run(c);
   for (int s = 0; s < n; ++s) { c->cd_host[(size_t)s].fetch_pt_cand = c->cd_maps[(size_t)s].n_pt_cand; c->cd_host[(size_t)s].fetch_seg_cand = c->cd_maps[(size_t)s].n_seg_cand; }
   c->cd_ov_off.assign((size_t)n + 1, 0);
   if (n == 0) { c->cd_ran = true; return PLSVO_OK; }
   HIP_TRY(c, hipSetDevice(c->device));
   Blob blob;
-  const size_t b_jobs = blob.reserve<CandJobDev>((size_t)n), b_ov = blob.reserve<int>(t_ov);
+  const size_t b_jobs = blob.reserve<CandJobDev>((size_t)n), b_ov = blob.reserve<int>(t_ov), b_room = close ? blob.reserve<int>((size_t)n) : 0;
   CandJobDev* jobs = blob.at<CandJobDev>(b_jobs); int* ov = blob.at<int>(b_ov);
   c->cd_cur_slot.resize((size_t)n);
   size_t o = 0;
@@ -245,7 +246,8 @@ extern "C" int plsvo_candidates_run(plsvo_ctx* c, int n, const plsvo_cand_frame*
     memcpy(J.T, fr[s].T_f_w, sizeof(J.T)); J.d_T = fr[s].d_T_f_w; J.cur_slot = fr[s].cur_slot; J.n_ov = fr[s].n_overlap; J.ov_off = (long long)o;
     if (J.n_ov) memcpy(ov + o, fr[s].overlap_idx, (size_t)J.n_ov * sizeof(int));
     c->cd_cur_slot[(size_t)s] = fr[s].cur_slot; c->cd_ov_off[(size_t)s] = (long long)o;
-    o += (size_t)J.n_ov;
+    if (close) blob.at<int>(b_room)[s] = c->cd_maps[(size_t)s].n_kf;
+    o += close ? (size_t)c->cd_maps[(size_t)s].n_kf : (size_t)J.n_ov;
   }
   c->cd_ov_off[(size_t)n] = (long long)o;
   int rc;
@@ -254,12 +256,127 @@ extern "C" int plsvo_candidates_run(plsvo_ctx* c, int n, const plsvo_cand_frame*
   CandBatchDev b = c->cd_b;
   const char* dr = reinterpret_cast<const char*>(c->cd_d_run.p);
   b.jobs = reinterpret_cast<const CandJobDev*>(dr + b_jobs); b.overlap_idx = reinterpret_cast<const int*>(dr + b_ov); b.kf_count = c->cd_d_kfcount.as<int>();
+  c->cd_run_jobs = b.jobs; c->cd_run_ov = b.overlap_idx;
   const auto rearm_then_launch = [&]() -> hipError_t {   // the first-visit words are all ones ahead of EVERY launch: a run must not see the visits of the one before
     const hipError_t e = c->cd_vis_bytes ? hipMemsetAsync(c->cd_d_work.as<char>() + c->cd_vis_off, 0xff, c->cd_vis_bytes, c->stream) : hipSuccess;
     return e != hipSuccess ? e : launch_map_candidates(b, c->stream);
   };
+  if (close) {                                      // results first (what plsvo_candidates_close_fetch brings back), then scratch
+    Carver w;
+    const size_t w_cnt = w.take<int>((size_t)n * 2), w_idx = w.take<int>(c->ci_t_kf), w_dist = w.take<double>(c->ci_t_kf);
+    c->ck_fetch_bytes = w.off;
+    const size_t w_tmp = w.take<double>(c->ci_t_kf);
+    HIP_TRY(c, c->ck_d_work.ensure(w.off + 256));
+    KeyStageBatchDev kb{};
+    kb.c = b; kb.keypts = c->ck_d_keypts.as<int>(); kb.ov_room = reinterpret_cast<const int*>(dr + b_room); kb.max_n_kfs = max_n_kfs;
+    kb.close_counts = Carver::dev<int>(c->ck_d_work, w_cnt); kb.close_idx = Carver::dev<int>(c->ck_d_work, w_idx); kb.close_dist = Carver::dev<double>(c->ck_d_work, w_dist);
+    kb.tmp_dist = Carver::dev<double>(c->ck_d_work, w_tmp);
+    HIP_TRY_TIMED(c, PLSVO_K_KEYFRAME, launch_map_close(kb, c->stream));
+    c->ck_b = kb;
+  }
   HIP_TRY_TIMED(c, PLSVO_K_CANDIDATES, rearm_then_launch());
-  c->cd_ran = true;
+  c->cd_ran = true; c->ck_have_close = close;
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_run(plsvo_ctx* c, int n, const plsvo_cand_frame* fr) {
+  CTX_CHECK(c);
+  if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_run: no staged map tables");
+  if (const int rc = cand_seeds_pending(c, "candidates_run")) return rc;
+  if (n != c->cd_n || (n > 0 && !fr)) return fail(c, PLSVO_E_INVALID, "candidates_run: n does not match the staged batch");
+  for (int s = 0; s < n; ++s) {
+    if (fr[s].n_overlap < 0 || fr[s].cur_slot < 0) return fail(c, PLSVO_E_INVALID, "candidates_run: negative count or slot");
+    if (fr[s].n_overlap > 0 && !fr[s].overlap_idx) return fail(c, PLSVO_E_INVALID, "candidates_run: null overlap list");
+    if (!cand_idx_ok(fr[s].overlap_idx, (size_t)fr[s].n_overlap, 0, c->cd_maps[(size_t)s].n_kf)) return fail(c, PLSVO_E_INVALID, "candidates_run: overlap index outside the keyframe table");
+  }
+  return cand_run(c, n, fr, -1);
+}
+
+// ---- keyframe stage on the resident tables: the key-point table, close keyframes ahead of the candidate launch (keystage_device.hpp) ---------
+extern "C" int plsvo_candidates_set_keypts(plsvo_ctx* c, int n, const plsvo_cand_keypts* in) {
+  CTX_CHECK(c);
+  if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_set_keypts: no staged map tables");
+  if (const int rc = cand_seeds_pending(c, "candidates_set_keypts")) return rc;
+  if (n != c->cd_n) return fail(c, PLSVO_E_INVALID, "candidates_set_keypts: n does not match the staged batch");
+  for (int s = 0; in && s < n; ++s)
+    if (in[s].key_pts && !cand_idx_ok(in[s].key_pts, 5 * (size_t)c->cd_maps[(size_t)s].n_kf, -1, INT32_MAX)) return fail(c, PLSVO_E_INVALID, "candidates_set_keypts: a key point below -1");
+  if (n == 0) { c->ck_live = true; return PLSVO_OK; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t N = (size_t)n, rows = 5 * c->ci_t_kf;
+  Blob blob;
+  const size_t b_up = blob.reserve<KeyPtsJobDev>(N), b_jobs = blob.reserve<KeyPtsJobDev>(N), b_tab = blob.reserve<int>(rows);
+  bool any_fresh = false;
+  for (size_t k = 0; k < rows; ++k) blob.at<int>(b_tab)[k] = -1;
+  for (int s = 0; s < n; ++s) {
+    const int32_t* kp = in ? in[s].key_pts : nullptr; const CandMapDev& M = c->cd_maps[(size_t)s];
+    blob.at<KeyPtsJobDev>(b_up)[s] = KeyPtsJobDev{ kKeyPtsUpkeep, -1, 0, 0 };
+    blob.at<KeyPtsJobDev>(b_jobs)[s] = KeyPtsJobDev{ kp ? kKeyPtsStandBy : kKeyPtsFresh, -1, 0, 0 };
+    if (kp) { if (M.n_kf) memcpy(blob.at<int>(b_tab) + 5 * M.kf_off, kp, 5 * (size_t)M.n_kf * sizeof(int)); } else any_fresh = true;
+  }
+  int rc;
+  if ((rc = upload_blob(c, c->ck_d_in, blob))) return rc;
+  HIP_TRY(c, c->ck_d_upkeep.ensure(N * sizeof(KeyPtsJobDev)));
+  HIP_TRY(c, c->ck_d_keypts.ensure(std::max(rows, (size_t)1) * sizeof(int)));
+  const char* din = reinterpret_cast<const char*>(c->ck_d_in.p);
+  HIP_TRY(c, hipMemcpyAsync(c->ck_d_upkeep.p, din + b_up, N * sizeof(KeyPtsJobDev), hipMemcpyDeviceToDevice, c->stream));
+  if (rows) HIP_TRY(c, hipMemcpyAsync(c->ck_d_keypts.p, din + b_tab, rows * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+  if (any_fresh && (rc = keypts_enqueue(c, reinterpret_cast<const KeyPtsJobDev*>(din + b_jobs)))) return rc;
+  c->ck_live = true;
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_fetch_keypts(plsvo_ctx* c, int n, plsvo_cand_keypts_out* out) {
+  CTX_CHECK(c);
+  if (!c->cd_staged || !c->ck_live) return fail(c, PLSVO_E_STATE, "candidates_fetch_keypts: no live key-point table (plsvo_candidates_set_keypts)");
+  if (const int rc = cand_seeds_pending(c, "candidates_fetch_keypts")) return rc;
+  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_fetch_keypts: n does not match the staged batch");
+  if (n == 0) return PLSVO_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  Readback rb;
+  rb.add(c->ck_d_keypts.p, 5 * c->ci_t_kf * sizeof(int));
+  if (const int rc = rb.wait(c)) return rc;
+  for (int s = 0; s < n; ++s) {
+    if (!out[s].key_pts) continue;
+    const CandMapDev& M = c->cd_maps[(size_t)s]; const size_t used = 5 * (size_t)M.n_kf, cap = 5 * (size_t)c->cd_host[(size_t)s].cap_kf;
+    if (used) memcpy(out[s].key_pts, rb.at<int>(0) + 5 * M.kf_off, used * sizeof(int));
+    for (size_t k = used; k < cap; ++k) out[s].key_pts[k] = -1;
+  }
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_run_close(plsvo_ctx* c, int n, const plsvo_cand_frame* fr, int max_n_kfs) {
+  CTX_CHECK(c);
+  if (!c->cd_staged || !c->ck_live) return fail(c, PLSVO_E_STATE, "candidates_run_close: no live key-point table (plsvo_candidates_set_keypts)");
+  if (const int rc = cand_seeds_pending(c, "candidates_run_close")) return rc;
+  if (n != c->cd_n || (n > 0 && !fr)) return fail(c, PLSVO_E_INVALID, "candidates_run_close: n does not match the staged batch");
+  if (max_n_kfs < 0) return fail(c, PLSVO_E_INVALID, "candidates_run_close: negative max_n_kfs");
+  for (int s = 0; s < n; ++s) {
+    if (fr[s].cur_slot < 0) return fail(c, PLSVO_E_INVALID, "candidates_run_close: negative slot");
+    if (fr[s].n_overlap != 0 || fr[s].overlap_idx) return fail(c, PLSVO_E_INVALID, "candidates_run_close: the overlap list is decided on the device (n_overlap 0, overlap_idx NULL)");
+  }
+  return cand_run(c, n, fr, max_n_kfs);
+}
+
+extern "C" int plsvo_candidates_close_fetch(plsvo_ctx* c, int n, plsvo_close_kf_out* out) {
+  CTX_CHECK(c);
+  if (!c->cd_staged || !c->cd_ran || !c->ck_have_close) return fail(c, PLSVO_E_STATE, "candidates_close_fetch: the last run was no plsvo_candidates_run_close");
+  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_close_fetch: n does not match the staged batch");
+  if (n == 0) return PLSVO_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  Readback rb;
+  rb.add(c->ck_d_work.p, c->ck_fetch_bytes);
+  if (const int rc = rb.wait(c)) return rc;
+  const char* const h = rb.at<char>(0); const char* const base = reinterpret_cast<const char*>(c->ck_d_work.p);
+  const KeyStageBatchDev& b = c->ck_b;
+  const int* cnt = reinterpret_cast<const int*>(h + (reinterpret_cast<const char*>(b.close_counts) - base));
+  const int* idx = reinterpret_cast<const int*>(h + (reinterpret_cast<const char*>(b.close_idx) - base));
+  const double* dist = reinterpret_cast<const double*>(h + (reinterpret_cast<const char*>(b.close_dist) - base));
+  for (int s = 0; s < n; ++s) {
+    const size_t at = (size_t)c->cd_maps[(size_t)s].kf_off, nc = (size_t)cnt[2 * s];
+    out[s].n_close = cnt[2 * s]; out[s].n_overlap = cnt[2 * s + 1];
+    if (out[s].close_idx && nc) memcpy(out[s].close_idx, idx + at, nc * sizeof(int));
+    if (out[s].close_dist && nc) memcpy(out[s].close_dist, dist + at, nc * sizeof(double));
+  }
   return PLSVO_OK;
 }
 
@@ -346,6 +463,73 @@ extern "C" int plsvo_candidates_dev(plsvo_ctx* c, plsvo_cand_dev* o) {
   o->d_ref_px = b.m_ref_px; o->d_ref_f = b.m_ref_f; o->d_ref_level = b.m_ref_level; o->d_ref_type = b.m_ref_type; o->d_ref_grad = b.m_ref_grad;
   o->d_pos = b.m_pos; o->d_px_cur = b.m_px_cur; o->d_active = b.m_active;
   o->d_found = mb.found; o->d_px_out = mb.px_out; o->d_search_level = mb.search_level;
+  return PLSVO_OK;
+}
+
+// ---- the keyframe decision on the resident selection (keystage_device.hpp) ---------------------------------------------
+extern "C" int plsvo_candidates_keyframe_decide(plsvo_ctx* c, int n, const plsvo_cand_kf_decide* in) {
+  CTX_CHECK(c);
+  if (!c->cd_staged || !c->cd_ran || !c->cs_selected || !c->cs_posed) return fail(c, PLSVO_E_STATE, "candidates_keyframe_decide: no resident pose optimisation on the last run");
+  if (const int rc = cand_seeds_pending(c, "candidates_keyframe_decide")) return rc;
+  if (const int rc = cand_run_open(c, "candidates_keyframe_decide")) return rc;
+  if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_keyframe_decide: n does not match the staged batch");
+  if (n == 0) { c->ck_decided = true; return PLSVO_OK; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t N = (size_t)n, t_ov = (size_t)c->cd_ov_off[N];
+  Blob blob;
+  const size_t b_jobs = blob.reserve<KeyDecideJobDev>(N);
+  if (!c->ck_decided) c->ck_dec_active.assign(N, 0);
+  for (int s = 0; s < n; ++s) {
+    KeyDecideJobDev& J = blob.at<KeyDecideJobDev>(b_jobs)[s];
+    memset(&J, 0, sizeof(J));
+    memcpy(J.T_last, in[s].T_last_w, sizeof(J.T_last)); J.d_T_last = in[s].d_T_last_w;
+    J.min_t = in[s].kfselect_mindist_t; J.min_r = in[s].kfselect_mindist_r; J.active = in[s].active ? 1 : 0;
+    if (J.active) c->ck_dec_active[(size_t)s] = 1;
+  }
+  int rc;
+  if ((rc = upload_blob(c, c->ck_d_dec_in, blob))) return rc;
+  Carver w;   // the records and the deltas come back with a fetch; the depth keys stay
+  const size_t w_out = w.take<KfDecideOutDev>(N), w_dt = w.take<double>(t_ov), w_dr = w.take<double>(t_ov), w_keys = w.take<unsigned long long>(c->cd_t_opt + 4 * c->cd_t_oseg);   // per stream n_matches + 2 * n_ls_matches keys: a segment can be a feature twice
+  HIP_TRY(c, c->ck_d_dec.ensure(w.off + 256));
+  if (!c->ck_decided) HIP_TRY(c, hipMemsetAsync(c->ck_d_dec.as<char>() + w_out, 0, N * sizeof(KfDecideOutDev), c->stream));   // the run's first decision: a stream that sits it out reads as zeros, not as the run before
+  KeyDecideBatchDev b{};
+  b.s = c->cs_b; b.s.c.jobs = c->cd_run_jobs; b.s.c.overlap_idx = c->cd_run_ov;
+  b.jobs = Blob::dev<KeyDecideJobDev>(c->ck_d_dec_in, b_jobs); b.out = Carver::dev<KfDecideOutDev>(c->ck_d_dec, w_out);
+  b.poses = c->cs_w.poses.as<double>(); b.pt_keep = c->cs_w.ptkeep.as<uint8_t>(); b.seg_keep = c->cs_w.segkeep.as<uint8_t>();
+  b.depth_keys = Carver::dev<unsigned long long>(c->ck_d_dec, w_keys); b.delta_t = Carver::dev<double>(c->ck_d_dec, w_dt); b.delta_r = Carver::dev<double>(c->ck_d_dec, w_dr);
+  HIP_TRY_TIMED(c, PLSVO_K_KEYFRAME, launch_map_keyframe_decide(b, c->stream));
+  c->ck_dec_b = b; c->ck_decided = true;
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_decide_fetch(plsvo_ctx* c, int n, plsvo_kf_decide_out* out) {
+  CTX_CHECK(c);
+  if (!c->cd_staged || !c->ck_decided) return fail(c, PLSVO_E_STATE, "candidates_decide_fetch: no decision on the last run");
+  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_decide_fetch: n does not match the staged batch");
+  if (n == 0) return PLSVO_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const KeyDecideBatchDev& b = c->ck_dec_b;
+  const size_t N = (size_t)n, t_ov = (size_t)c->cd_ov_off[N];
+  bool deltas = false;
+  for (int s = 0; s < n; ++s) deltas = deltas || out[s].delta_t || out[s].delta_r;
+  Readback rb;   // the records: at most 64 bytes per stream; the deltas and the device-decided counts only when they are asked for
+  const int r_out = rb.add(b.out, N * sizeof(KfDecideOutDev));
+  const int r_dt = deltas ? rb.add(b.delta_t, t_ov * sizeof(double)) : -1, r_dr = deltas ? rb.add(b.delta_r, t_ov * sizeof(double)) : -1;
+  const int r_cnt = (deltas && c->ck_have_close) ? rb.add(c->ck_b.close_counts, N * 2 * sizeof(int)) : -1;
+  if (const int rc = rb.wait(c)) return rc;
+  const KfDecideOutDev* ho = rb.at<KfDecideOutDev>(r_out);
+  for (int s = 0; s < n; ++s) {
+    const KfDecideOutDev& o = ho[s];
+    plsvo_kf_decide_out& O = out[s];
+    O.depth_mean = o.depth_mean; O.depth_min = o.depth_min; O.has_depth = o.has_depth; O.n_depth = o.n_depth;
+    O.need_new_kf = o.need_new_kf; O.blocking = o.blocking; O.furthest_kf = o.furthest_kf;
+    for (int k = 0; k < 5; ++k) O.key_pts[k] = o.key_pts[k];
+    if (!deltas || !c->ck_dec_active[(size_t)s]) continue;
+    const size_t at = (size_t)c->cd_ov_off[(size_t)s];
+    const size_t no = r_cnt >= 0 ? (size_t)rb.at<int>(r_cnt)[2 * s + 1] : (size_t)(c->cd_ov_off[(size_t)s + 1] - c->cd_ov_off[(size_t)s]);
+    if (O.delta_t && no) memcpy(O.delta_t, rb.at<double>(r_dt) + at, no * sizeof(double));
+    if (O.delta_r && no) memcpy(O.delta_r, rb.at<double>(r_dr) + at, no * sizeof(double));
+  }
   return PLSVO_OK;
 }
 
@@ -511,6 +695,7 @@ extern "C" int plsvo_candidates_select(plsvo_ctx* c, const plsvo_cand_select_par
   };
   HIP_TRY_TIMED(c, PLSVO_K_SELECT, rearm_then_launch());
   c->cs_selected = true;
+  if (c->ck_live) return keypts_enqueue(c, c->ck_d_upkeep.as<KeyPtsJobDev>());   // removeKeyPoint of the landmarks the selection deleted
   return PLSVO_OK;
 }
 
@@ -687,6 +872,13 @@ extern "C" int plsvo_candidates_insert_keyframe(plsvo_ctx* c, int n, const plsvo
       return fail(c, PLSVO_E_CAPACITY, "candidates_insert_keyframe: a stream's new sizes exceed its room (plsvo_candidates_reserve); nothing was changed");
   }
   HIP_TRY_TIMED(c, PLSVO_K_INSERT, launch_map_insert(b, c->stream));
+  if (c->ck_live) {                                 // the key-point table follows: rows close up, removeKeyPoint, the new keyframe's row
+    Blob kb;
+    const size_t b_kp = kb.reserve<KeyPtsJobDev>(N);
+    for (int s = 0; s < n; ++s) kb.at<KeyPtsJobDev>(b_kp)[s] = in[s].is_kf ? KeyPtsJobDev{ kKeyPtsUpkeep, in[s].remove_kf, (c->ck_decided && c->ck_dec_active[(size_t)s]) ? kKeyPtsRowDecided : kKeyPtsRowFresh, 0 } : KeyPtsJobDev{ kKeyPtsStandBy, -1, kKeyPtsRowOld, 0 };
+    if ((rc = upload_blob(c, c->ck_d_in, kb))) return rc;
+    if ((rc = keypts_enqueue(c, Blob::dev<KeyPtsJobDev>(c->ck_d_in, b_kp)))) return rc;
+  }
   // -- the host mirrors describe the new tables
   for (int s = 0; s < n; ++s) {
     if (!in[s].is_kf) { c->ci_last[(size_t)s] = plan[(size_t)s]; continue; }

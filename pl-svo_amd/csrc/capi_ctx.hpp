@@ -36,6 +36,9 @@ hipError_t launch_map_set_positions(const PositionsBatchDev& b, hipStream_t stre
 hipError_t launch_map_optimize_structure(const StructSelBatchDev& b, hipStream_t stream);   // structsel_device.hpp, in seeds_kernels.hip
 hipError_t launch_map_add_candidates(const NewCandBatchDev& b, hipStream_t stream);   // newcand_device.hpp, in seeds_kernels.hip
 hipError_t launch_map_compact(const CompactBatchDev& b, hipStream_t stream);           // compact_device.hpp, in seeds_kernels.hip
+hipError_t launch_map_keypts(const KeyStageBatchDev& b, hipStream_t stream);          // keystage_device.hpp, in seeds_kernels.hip
+hipError_t launch_map_close(const KeyStageBatchDev& b, hipStream_t stream);
+hipError_t launch_map_keyframe_decide(const KeyDecideBatchDev& b, hipStream_t stream);
 hipError_t launch_update_seeds_resident(const SeedListBatchDev& b, hipStream_t stream);   // seedlist_device.hpp, in seeds_kernels.hip
 hipError_t launch_seeds_commit(const SeedListBatchDev& b, hipStream_t stream);
 hipError_t launch_seeds_keyframe(const SeedListBatchDev& b, hipStream_t stream);
@@ -257,6 +260,21 @@ struct plsvo_ctx {
   std::vector<CompactReportDev> cc_last;
   DevBuf cc_d_in, cc_d_work;
   size_t cc_remap_off = 0, cc_remap_seg = 0, cc_work_end = 0;   // sections of cc_d_work: the two remaps, the end
+  // keyframe stage on the resident tables (plsvo_candidates_set_keypts ..): the key-point table, 5 per keyframe row of capacity, and
+  // whether it is live (ck_d_keypts, ck_live); a call's upload and the standing "upkeep" records of every stream (ck_d_in, ck_d_upkeep);
+  // the close launch's results, then its scratch (ck_d_work), whether the last run was a run_close, the launch that describes both
+  bool ck_live = false, ck_have_close = false;
+  DevBuf ck_d_keypts, ck_d_in, ck_d_upkeep, ck_d_work;
+  size_t ck_fetch_bytes = 0;
+  KeyStageBatchDev ck_b{};
+  // the keyframe decision on the resident selection (plsvo_candidates_keyframe_decide): the last run's job records and overlap rows on
+  // the device (inside cd_d_run), a call's records (ck_d_dec_in), the decision records / deltas / depth keys (ck_d_dec: zeroed when it
+  // grows, a stream that sits a call out keeps its record), whether this run has a decision
+  const CandJobDev* cd_run_jobs = nullptr; const int* cd_run_ov = nullptr;
+  bool ck_decided = false;
+  std::vector<uint8_t> ck_dec_active;        // per stream: a decision of this run was active for it
+  DevBuf ck_d_dec_in, ck_d_dec;
+  KeyDecideBatchDev ck_dec_b{};
   // resident seed lists (plsvo_seeds_*): the room plsvo_seeds_reserve asks for (the next stage's), per stream the host mirror of its
   // record (sd_host: list lengths, upper bounds between a keyframe event and the next update fetch) and the rows it may fill (sd_lim);
   // the tables (sd_d_tab: records, workgroup map, rows), shadow rows and reports (sd_d_work), a call's upload (sd_d_in).  A candidate

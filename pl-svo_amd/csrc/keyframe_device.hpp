@@ -130,6 +130,33 @@ __device__ __forceinline__ kf_u64 kf_wave_select(const kf_u64* keys, int n, int 
 }
 
 // ---- close keyframes ---------------------------------------------------------------------------------------------------------------------
+// The arithmetic of Map::getCloseKeyframes, shared by close_keyframes_kernel (host arrays) and keystage_device.hpp's map_close_kernel
+// (the resident tables).  Frame::isVisible for one world position:
+__device__ __forceinline__ bool kf_visible(const SE3d& T, const CamDev& cam, const double* xyz_w) {
+  double c[3], px[2];
+  se3_act(T, xyz_w, c);
+  if (c[2] < 0.0) return false;                     // behind the camera
+  world2cam(cam, c, px);
+  return px[0] >= 0.0 && px[1] >= 0.0 && px[0] < cam.width && px[1] < cam.height;
+}
+// (frame->T_f_w_.translation() - kf->T_f_w_.translation()).norm(), Eigen's norm()
+__device__ __forceinline__ double kf_translation_dist(const SE3d& T, const double* kf_T) {
+  const double dx = T.t[0] - kf_T[4], dy = T.t[1] - kf_T[5], dz = T.t[2] - kf_T[6];
+  return sqrt((dx * dx + dy * dy) + dz * dz);
+}
+// the place of a close keyframe = close keyframes with a smaller (distance, index), over ALL rounds; scatter.  tmp: per keyframe its
+// distance, -1 = not close, complete and fenced
+__device__ __forceinline__ void kf_rank_scatter(const double* tmp, int n_kf, int* oidx, double* odist) {
+  const int lane = threadIdx.x & 63;
+  for (int i = lane; i < n_kf; i += 64) {
+    const double d = tmp[i];
+    if (d < 0.0) continue;
+    int rank = 0;
+    for (int j = 0; j < n_kf; ++j) { const double o = tmp[j]; rank += (o >= 0.0 && (o < d || (o == d && j < i))) ? 1 : 0; }
+    oidx[rank] = i; odist[rank] = d;
+  }
+}
+
 __global__ __launch_bounds__(64 * kKfWaves) void close_keyframes_kernel(const CloseKfBatchDev b) {
   const int lane = threadIdx.x & 63;
   const int job = blockIdx.x * kKfWaves + (int)(threadIdx.x >> 6);
@@ -150,31 +177,14 @@ __global__ __launch_bounds__(64 * kKfWaves) void close_keyframes_kernel(const Cl
     if (i < n_kf) {
       for (int k = 0; k < 5 && !close; ++k) {
         if (!kv[5 * i + k]) continue;
-        double c[3], px[2];
-        se3_act(T, kp + 15 * i + 3 * k, c);
-        if (c[2] < 0.0) continue;                   // behind the camera
-        world2cam(cam, c, px);
-        close = px[0] >= 0.0 && px[1] >= 0.0 && px[0] < cam.width && px[1] < cam.height;
+        close = kf_visible(T, cam, kp + 15 * i + 3 * k);
       }
-      double d = -1.0;
-      if (close) {
-        const double dx = T.t[0] - kf_T[7 * i + 4], dy = T.t[1] - kf_T[7 * i + 5], dz = T.t[2] - kf_T[7 * i + 6];
-        d = sqrt((dx * dx + dy * dy) + dz * dz);    // Eigen's norm()
-      }
-      tmp[i] = d;
+      tmp[i] = close ? kf_translation_dist(T, kf_T + 7 * i) : -1.0;
     }
     n_close += __popcll(__ballot(close));
   }
   wave_lds_fence();                                 // the wave's own stores to tmp, read back by all of its lanes
-  // pass 2: the place of a close keyframe = close keyframes with a smaller (distance, index), over ALL rounds; scatter
-  int* oidx = b.close_idx + J.kf_off; double* odist = b.close_dist + J.kf_off;
-  for (int i = lane; i < n_kf; i += 64) {
-    const double d = tmp[i];
-    if (d < 0.0) continue;
-    int rank = 0;
-    for (int j = 0; j < n_kf; ++j) { const double o = tmp[j]; rank += (o >= 0.0 && (o < d || (o == d && j < i))) ? 1 : 0; }
-    oidx[rank] = i; odist[rank] = d;
-  }
+  kf_rank_scatter(tmp, n_kf, b.close_idx + J.kf_off, b.close_dist + J.kf_off);   // pass 2
   if (lane == 0) { b.counts[2 * job] = n_close; b.counts[2 * job + 1] = n_close < J.max_n_kfs ? n_close : J.max_n_kfs; }
 }
 
@@ -222,66 +232,79 @@ __device__ __forceinline__ void kf_point_values(double x, double y, int cu, int 
   pass[4] = x < cv && y >= cv;
 }
 
-__global__ __launch_bounds__(64 * kKfWaves) void keyframe_decide_kernel(const KfDecideBatchDev b) {
-  __shared__ int s_hist[kKfWaves][256];
-  __shared__ kf_u64 s_cand[kKfWaves][64];
-  __shared__ int s_ctr[kKfWaves];
-  const int lane = threadIdx.x & 63, wave = (int)(threadIdx.x >> 6);
-  const int job = blockIdx.x * kKfWaves + wave;
-  if (job >= b.n_jobs) return;                      // whole waves leave: nothing below synchronises across waves
-  const KfDecideJobDev& J = b.jobs[job];
-  const SE3d Tn = se3_load(J.d_T_new ? J.d_T_new : J.T_new);
-  const int n_pt = J.n_pt, n_seg = J.n_seg, n_kf = J.n_kf, n_ov = J.n_ov;
-  const double* pt_px = b.pt_px + 2 * J.pt_off;
-  const double* pt_pos = b.pt_pos + 3 * J.pt_off;
-  const uint8_t* pt_alive = b.pt_alive + J.pt_off;
-  const double* kf_T = b.kf_T + 7 * J.kf_off;
+// the five slots' candidates of all lanes, reduced: every lane ends with the wave's winner per slot
+__device__ __forceinline__ void kf_slots_reduce(double* val, int* rank) {
+#pragma unroll
+  for (int s = 0; s < 5; ++s) {
+#pragma unroll
+    for (int mk = 1; mk < 64; mk <<= 1) {
+      const double ov = __shfl_xor(val[s], mk, 64); const int orank = __shfl_xor(rank[s], mk, 64);
+      kf_slot_offer(val[s], rank[s], ov, orank);
+    }
+  }
+}
 
-  // -- getSceneDepth: the keys of all depths into the stream's row, minimum and maximum on the way
-  kf_u64* keys = b.depth_keys + J.depth_off;
+// The four parts of the decision, shared by keyframe_decide_kernel (host arrays) and keystage_device.hpp's map_keyframe_decide_kernel (the
+// resident selection).  A position source maps a feature index to three doubles: the arrays of a call, or the landmark tables through
+// the selection's landmark indices.
+struct KfPosDirect {
+  const double* p;
+  __device__ __forceinline__ const double* operator()(int i) const { return p + 3 * i; }
+};
+struct KfPosIndexed {
+  const double* p; const int* lm;
+  __device__ __forceinline__ const double* operator()(int i) const { return p + 3 * lm[i]; }
+};
+
+// getSceneDepth: the keys of all depths into the stream's row (n_pt points, then two per segment), minimum and maximum on the way; the
+// median is the element of rank m / 2.  Returns m, the depths that count.  hist / cand / ctr: this wave's LDS (kf_wave_select).
+template <typename PtPos, typename SegPos>
+__device__ __forceinline__ int kf_scene_depth(const SE3d& Tn, int n_pt, const uint8_t* pt_alive, const PtPos pt_pos, int n_seg, const uint8_t* seg_alive,
+                                              const SegPos seg_spos, const SegPos seg_epos, kf_u64* keys, int* hist, kf_u64* cand, int* ctr,
+                                              double* depth_mean, double* depth_min) {
+  const int lane = threadIdx.x & 63;
   kf_u64 mn = kKfOnes, mx = 0;
   int m = 0;
   for (int i = lane; i < n_pt; i += 64) {
     kf_u64 key = kKfOnes;
     if (pt_alive[i]) {
       double c[3];
-      se3_act(Tn, pt_pos + 3 * i, c);
+      se3_act(Tn, pt_pos(i), c);
       key = kf_key(c[2]); mn = key < mn ? key : mn; mx = key > mx ? key : mx; ++m;
     }
     keys[i] = key;
   }
-  {
-    const double* sp = b.seg_spos + 3 * J.seg_off; const double* ep = b.seg_epos + 3 * J.seg_off;
-    const uint8_t* sa = b.seg_alive + J.seg_off;
-    for (int s = lane; s < n_seg; s += 64) {
-      kf_u64 ks = kKfOnes, ke = kKfOnes;
-      if (sa[s]) {
-        double c[3];
-        se3_act(Tn, sp + 3 * s, c); ks = kf_key(c[2]);
-        se3_act(Tn, ep + 3 * s, c); ke = kf_key(c[2]);
-        const kf_u64 lo = ks < ke ? ks : ke, hi = ks < ke ? ke : ks;
-        mn = lo < mn ? lo : mn; mx = hi > mx ? hi : mx; m += 2;
-      }
-      keys[n_pt + 2 * s] = ks; keys[n_pt + 2 * s + 1] = ke;
+  for (int s = lane; s < n_seg; s += 64) {
+    kf_u64 ks = kKfOnes, ke = kKfOnes;
+    if (seg_alive[s]) {
+      double c[3];
+      se3_act(Tn, seg_spos(s), c); ks = kf_key(c[2]);
+      se3_act(Tn, seg_epos(s), c); ke = kf_key(c[2]);
+      const kf_u64 lo = ks < ke ? ks : ke, hi = ks < ke ? ke : ks;
+      mn = lo < mn ? lo : mn; mx = hi > mx ? hi : mx; m += 2;
     }
+    keys[n_pt + 2 * s] = ks; keys[n_pt + 2 * s + 1] = ke;
   }
   m = kf_wave_sum(m); mn = kf_wave_min(mn); mx = kf_wave_max(mx);
   wave_lds_fence();                                 // the wave's own stores to keys, read back by all of its lanes
-  double depth_mean = 0.0, depth_min = DBL_MAX;
+  *depth_mean = 0.0; *depth_min = DBL_MAX;
   if (m > 0) {
-    depth_mean = kf_unkey(kf_wave_select(keys, n_pt + 2 * n_seg, m / 2, mn, mx, s_hist[wave], s_cand[wave], &s_ctr[wave]));
-    depth_min = kf_unkey(mn);
+    *depth_mean = kf_unkey(kf_wave_select(keys, n_pt + 2 * n_seg, m / 2, mn, mx, hist, cand, ctr));
+    *depth_min = kf_unkey(mn);
   }
+  return m;
+}
 
-  // -- setKeyPoints: five arg-max reductions over (value, rank); a surviving holder has rank -1
-  const int cu = J.width / 2, cv = J.height / 2;
+// setKeyPoints over the alive points of a frame: five arg-max reductions over (value, rank); a surviving holder has rank -1
+__device__ __forceinline__ void kf_set_key_points(const double* pt_px, const uint8_t* pt_alive, int n_pt, int cu, int cv, const int* key_prev, int* key_out) {
+  const int lane = threadIdx.x & 63;
   double val[5]; int rank[5];
 #pragma unroll
   for (int s = 0; s < 5; ++s) { val[s] = 0.0; rank[s] = kKfNone; }
   if (lane == 0) {
 #pragma unroll
     for (int s = 0; s < 5; ++s) {
-      const int h = J.key_prev[s];
+      const int h = key_prev[s];
       if (h >= 0 && pt_alive[h]) {                  // (a holder is not tested against its slot's quadrant again)
         double v[5]; bool pass[5];
         kf_point_values(pt_px[2 * h], pt_px[2 * h + 1], cu, cv, v, pass);
@@ -296,18 +319,16 @@ __global__ __launch_bounds__(64 * kKfWaves) void keyframe_decide_kernel(const Kf
 #pragma unroll
     for (int s = 0; s < 5; ++s) if (pass[s]) kf_slot_offer(val[s], rank[s], v[s], i);
   }
+  kf_slots_reduce(val, rank);
 #pragma unroll
-  for (int s = 0; s < 5; ++s) {
-#pragma unroll
-    for (int mk = 1; mk < 64; mk <<= 1) {
-      const double ov = __shfl_xor(val[s], mk, 64); const int orank = __shfl_xor(rank[s], mk, 64);
-      kf_slot_offer(val[s], rank[s], ov, orank);
-    }
-  }
+  for (int s = 0; s < 5; ++s) key_out[s] = rank[s] == kKfNone ? -1 : (rank[s] < 0 ? key_prev[s] : rank[s]);
+}
 
-  // -- needNewKf: one lane per overlap keyframe, in rounds of 64; the first blocking keyframe decides, every delta is written
-  const SE3d T_last_inv = se3_inv(se3_load(J.T_last));
-  const int* ov = b.overlap_idx + J.ov_off;
+// needNewKf: one lane per overlap keyframe, in rounds of 64; the first blocking keyframe decides (its place in the list, -1 = none),
+// every delta is written
+__device__ __forceinline__ int kf_need_new_kf(const SE3d& T_last, const double* kf_T, const int* ov, int n_ov, double min_t, double min_r, double* out_t, double* out_r) {
+  const int lane = threadIdx.x & 63;
+  const SE3d T_last_inv = se3_inv(T_last);
   int blocking = -1;
   for (int base = 0; base < n_ov; base += 64) {
     const int j = base + lane;
@@ -318,14 +339,18 @@ __global__ __launch_bounds__(64 * kKfWaves) void keyframe_decide_kernel(const Kf
       se3_log_dev(delta_T, xi);
       const double delta_t = sqrt((xi[0] * xi[0] + xi[1] * xi[1]) + xi[2] * xi[2]);
       const double delta_r = sqrt((xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5]) * 180.0 / 3.1416;
-      b.delta_t[J.ov_off + j] = delta_t; b.delta_r[J.ov_off + j] = delta_r;
-      blocks = delta_t < J.min_t && delta_r < J.min_r;
+      out_t[j] = delta_t; out_r[j] = delta_r;
+      blocks = delta_t < min_t && delta_r < min_r;
     }
     const kf_u64 mask = __ballot(blocks);
     if (blocking < 0 && mask) blocking = base + __builtin_ctzll(mask);
   }
+  return blocking;
+}
 
-  // -- getFurthestKeyframe(new_frame->pos()): arg-max of the camera-centre distance, strict > from 0.0, the lowest index among equals
+// getFurthestKeyframe(new_frame->pos()): arg-max of the camera-centre distance, strict > from 0.0, the lowest index among equals
+__device__ __forceinline__ int kf_furthest_keyframe(const SE3d& Tn, const double* kf_T, int n_kf) {
+  const int lane = threadIdx.x & 63;
   const SE3d Tn_inv = se3_inv(Tn);
   double far_d = 0.0; int far_i = -1;
   for (int i = lane; i < n_kf; i += 64) {
@@ -339,14 +364,35 @@ __global__ __launch_bounds__(64 * kKfWaves) void keyframe_decide_kernel(const Kf
     const double od = __shfl_xor(far_d, mk, 64); const int oi = __shfl_xor(far_i, mk, 64);
     if (oi >= 0 && (od > far_d || (od == far_d && (far_i < 0 || oi < far_i)))) { far_d = od; far_i = oi; }
   }
+  return far_i;
+}
 
+__global__ __launch_bounds__(64 * kKfWaves) void keyframe_decide_kernel(const KfDecideBatchDev b) {
+  __shared__ int s_hist[kKfWaves][256];
+  __shared__ kf_u64 s_cand[kKfWaves][64];
+  __shared__ int s_ctr[kKfWaves];
+  const int lane = threadIdx.x & 63, wave = (int)(threadIdx.x >> 6);
+  const int job = blockIdx.x * kKfWaves + wave;
+  if (job >= b.n_jobs) return;                      // whole waves leave: nothing below synchronises across waves
+  const KfDecideJobDev& J = b.jobs[job];
+  const SE3d Tn = se3_load(J.d_T_new ? J.d_T_new : J.T_new);
+  const double* kf_T = b.kf_T + 7 * J.kf_off;
+  const uint8_t* pt_alive = b.pt_alive + J.pt_off;
+  double depth_mean, depth_min;
+  const KfPosDirect pp = { b.pt_pos + 3 * J.pt_off }, sp = { b.seg_spos + 3 * J.seg_off }, ep = { b.seg_epos + 3 * J.seg_off };
+  const int m = kf_scene_depth(Tn, J.n_pt, pt_alive, pp, J.n_seg, b.seg_alive + J.seg_off, sp, ep, b.depth_keys + J.depth_off, s_hist[wave], s_cand[wave], &s_ctr[wave],
+                               &depth_mean, &depth_min);
+  int key[5];
+  kf_set_key_points(b.pt_px + 2 * J.pt_off, pt_alive, J.n_pt, J.width / 2, J.height / 2, J.key_prev, key);
+  const int blocking = kf_need_new_kf(se3_load(J.T_last), kf_T, b.overlap_idx + J.ov_off, J.n_ov, J.min_t, J.min_r, b.delta_t + J.ov_off, b.delta_r + J.ov_off);
+  const int far_i = kf_furthest_keyframe(Tn, kf_T, J.n_kf);
   if (lane == 0) {
     KfDecideOutDev& o = b.out[job];
     o.depth_mean = depth_mean; o.depth_min = depth_min;
     o.has_depth = m > 0 ? 1 : 0; o.n_depth = m;
     o.need_new_kf = blocking < 0 ? 1 : 0; o.blocking = blocking;
 #pragma unroll
-    for (int s = 0; s < 5; ++s) o.key_pts[s] = rank[s] == kKfNone ? -1 : (rank[s] < 0 ? J.key_prev[s] : rank[s]);
+    for (int s = 0; s < 5; ++s) o.key_pts[s] = key[s];
     o.furthest_kf = far_i;
   }
 }

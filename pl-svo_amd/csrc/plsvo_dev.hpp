@@ -453,6 +453,45 @@ struct CompactBatchDev {
   int* pt_remap; int* seg_remap;                     // per landmark row (pt_off / seg_off): its new row, -1 = deleted; written where the kind ran
 };
 
+// keyframe stage on the resident map tables (keystage_device.hpp, include/plsvo_hip.h plsvo_candidates_set_keypts / _run_close): one wave
+// per stream.  The key-point table holds five entries per keyframe row of CAPACITY (from 5 * kf_off): the position of the key point in
+// the keyframe's point-feature list, -1 = NULL.
+constexpr int kKeyPtsStandBy = 0, kKeyPtsFresh = 1, kKeyPtsUpkeep = 2;   // KeyPtsJobDev::mode
+struct KeyPtsJobDev {               // one stream's record of map_keypts_kernel
+  int mode;                         // stand by; every row from five NULLs; the rows one of whose holders has lost its landmark
+  int remove_kf;                    // -1, or the row an insertion took out of the keyframe table: the rows above it close up first
+  int new_row;                      // kKeyPtsRow*: the LAST row is a new keyframe's, built from five NULLs or from the run's decision record
+  int reserved0;
+};
+constexpr int kKeyPtsRowOld = 0, kKeyPtsRowFresh = 1, kKeyPtsRowDecided = 2;
+struct KeyStageBatchDev {
+  CandBatchDev c;                   // the resident tables; c.jobs / c.overlap_idx / c.kf_count are the run's rows, which map_close_kernel WRITES
+  int* keypts;
+  const KfDecideOutDev* decided;    // the run's decision records (kKeyPtsRowDecided), or null
+  const KeyPtsJobDev* kp_jobs;      // map_keypts_kernel
+  const int* ov_room;               // map_close_kernel: per stream the entries of its overlap row (the keyframe count the host laid it out for)
+  int max_n_kfs;
+  double* tmp_dist;                 // per keyframe row (kf_off): its distance, -1 = not close
+  int* close_idx; double* close_dist;   // per keyframe row (kf_off)
+  int* close_counts;                // 2 per stream: n_close, n_overlap
+};
+
+// the keyframe decision on the resident selection (keystage_device.hpp's map_keyframe_decide_kernel, plsvo_candidates_keyframe_decide)
+struct KeyDecideJobDev {            // one stream's record: 88 bytes
+  double T_last[7];
+  const double* d_T_last;           // device pointer read instead of T_last, or null
+  double min_t, min_r;
+  int active, reserved0;            // 0: the stream's record of an earlier decision is left as it is
+};
+struct KeyDecideBatchDev {
+  SelectBatchDev s;                 // the selection's features (f_pt_lm / f_pt_px / f_seg_lm, scalars) and, in s.c, the tables and the run's overlap rows
+  const KeyDecideJobDev* jobs; KfDecideOutDev* out;
+  const double* poses;              // 7 per stream: the optimised T_f_w (plsvo_candidates_poses_dev)
+  const uint8_t* pt_keep; const uint8_t* seg_keep;   // the pose optimiser's keep masks, feature rows from opt_off / 2 * oseg_off
+  unsigned long long* depth_keys;   // per stream from opt_off + 4 * oseg_off: n_matches + 2 * n_ls_matches keys (a segment that won both its cells is a feature twice)
+  double* delta_t; double* delta_r; // per overlap entry, laid out like the run's overlap rows
+};
+
 // corner detection (detect_device.hpp, include/plsvo_hip.h plsvo_hip_detect_fast): tile geometry and the launch record
 constexpr int kDetTileW = 64, kDetTileH = 32;          // pixels of a tile that one workgroup decides
 constexpr int kDetImgX0 = 8, kDetImgY0 = 5;            // LDS image origin = tile origin - (8, 5): a halo of 5 (Shi-Tomasi: x - 5 .. x + 4), 8 keeps rows dword-aligned

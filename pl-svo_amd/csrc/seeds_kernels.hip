@@ -25,6 +25,7 @@
 #include "match_device.hpp"
 #include "keyframe_device.hpp"   // the keyframe stage's kernels live in this translation unit for its -ffp-contract=off
 #include "candidates_device.hpp" // and the map candidates' kernel
+#include "keystage_device.hpp"   // and the keyframe stage on the resident tables: key points, close keyframes
 #include "select_device.hpp"     // and their cell selection
 #include "insert_device.hpp"     // and the keyframe insertion into the resident tables
 #include "compact_device.hpp"    // and their compaction over the deleted landmark rows
@@ -532,6 +533,22 @@ hipError_t launch_map_add_candidates(const NewCandBatchDev& b, hipStream_t strea
 hipError_t launch_map_compact(const CompactBatchDev& b, hipStream_t stream) {
   if (b.c.n_jobs <= 0) return hipSuccess;
   hipLaunchKernelGGL(map_compact_kernel, dim3((b.c.n_jobs + kCmpWaves - 1) / kCmpWaves), dim3(64 * kCmpWaves), 0, stream, b);
+  return hipGetLastError();
+}
+// the keyframe stage on the resident tables (keystage_device.hpp): the same shape
+hipError_t launch_map_keypts(const KeyStageBatchDev& b, hipStream_t stream) {
+  if (b.c.n_jobs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_keypts_kernel, dim3((b.c.n_jobs + kKsWaves - 1) / kKsWaves), dim3(64 * kKsWaves), 0, stream, b);
+  return hipGetLastError();
+}
+hipError_t launch_map_close(const KeyStageBatchDev& b, hipStream_t stream) {
+  if (b.c.n_jobs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_close_kernel, dim3((b.c.n_jobs + kKsWaves - 1) / kKsWaves), dim3(64 * kKsWaves), 0, stream, b);
+  return hipGetLastError();
+}
+hipError_t launch_map_keyframe_decide(const KeyDecideBatchDev& b, hipStream_t stream) {
+  if (b.s.c.n_jobs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_keyframe_decide_kernel, dim3((b.s.c.n_jobs + kKsWaves - 1) / kKsWaves), dim3(64 * kKsWaves), 0, stream, b);
   return hipGetLastError();
 }
 

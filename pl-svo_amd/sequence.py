@@ -121,17 +121,26 @@ class HipBackend:
         self.ctx.candidates_match()
         return r, self.ctx.candidates_match_fetch([(r["n_filed_pt"], r["n_filed_seg"])])[0]
 
-    def map_select(self, map_job, frame_job, cam, n_pyr_levels, select, carry=None, cell_size=30, seg_cell_size=30):
+    def map_select(self, map_job, frame_job, cam, n_pyr_levels, select, carry=None, cell_size=30, seg_cell_size=30, close=None, key_pts=False):
         """the map part of a frame as one enqueue sequence on the resident tables: candidates, match, cell selection, pose optimisation
         (plsvo_candidates_run .. plsvo_candidates_pose_optimize).  map_job as in map_candidates; carry: the counters to put back after a
         restage (a candidates_fetch_quality() record), select: the keyword arguments of capi.Context.candidates_select.
+        close = max_n_kfs: the overlap list is decided on the device from the resident key-point table (plsvo_candidates_run_close; what
+        close_keyframes() reports is left in self.last_close), which a (re)stage gives its rows first: key_pts [n_kf, 5], or None for
+        setKeyPoints from five NULLs on the device (False: the table is not touched).
         -> (the stage's result, the matcher's, the selection, the pose optimiser's result, the quality state after the frame)"""
         if map_job is not None:
             self.ctx.candidates_stage([map_job], cam, cell_size, seg_cell_size, 8, n_pyr_levels, 10)
             if carry is not None:
                 self.ctx.candidates_set_quality([dict(pt_n_failed=carry["pt_n_failed"], pt_n_succeeded=carry["pt_n_succeeded"],
                                                       seg_n_failed=carry["seg_n_failed"], seg_n_succeeded=carry["seg_n_succeeded"])])
-        self.ctx.candidates_run([frame_job])
+        if map_job is not None and key_pts is not False:
+            self.ctx.candidates_set_keypts(None if key_pts is None else [key_pts])
+        if close is None:
+            self.ctx.candidates_run([frame_job])
+        else:
+            self.ctx.candidates_run_close([frame_job], close)
+            self.last_close = self.ctx.candidates_close_fetch()[0]
         self.ctx.candidates_match()
         self.ctx.candidates_select(**select)
         self.ctx.candidates_pose_optimize()
@@ -140,6 +149,29 @@ class HipBackend:
         sel = self.ctx.candidates_select_fetch()[0]
         pr = self.ctx.candidates_pose_fetch([(sel["n_matches"], sel["n_ls_matches"])])[0]
         return r, mr, sel, pr, self.ctx.candidates_fetch_quality()[0]
+
+    def map_set_keypts(self, key_pts=None):
+        """Frame::key_pts_ of the staged keyframes as a resident table (plsvo_candidates_set_keypts, DESIGN.md 3.19): [n_kf, 5] positions in
+        the keyframes' point-feature lists, or None: setKeyPoints from five NULLs on the device.  Live until the next stage; the selection
+        and the insertion keep it up.  -> the table as it stands"""
+        self.ctx.candidates_set_keypts(None if key_pts is None else [key_pts])
+        return self.map_fetch_keypts()
+
+    def map_fetch_keypts(self):
+        return self.ctx.candidates_fetch_keypts()[0]
+
+    def map_candidates_close(self, frame_job, max_n_kfs=10):
+        """plsvo_candidates_run_close on the staged tables: getCloseKeyframes from the live key-point table and the landmarks' positions as
+        they lie now, sorted and cut, feeding the candidate launch in the same enqueue (frame_job: no overlap list).
+        -> (what close_keyframes() reports, the candidate stage's result)"""
+        self.ctx.candidates_run_close([frame_job], max_n_kfs)
+        return self.ctx.candidates_close_fetch()[0], self.ctx.candidates_fetch()[0]
+
+    def map_keyframe_decide(self, T_last_w, kfselect_mindist_t=0.06, kfselect_mindist_r=3.0):
+        """the keyframe decision behind the last map_select, on the resident selection (plsvo_candidates_keyframe_decide): nothing but
+        T_last_w travels, one record comes back.  -> what keyframe_decide() reports, key_pts in selection order"""
+        self.ctx.candidates_keyframe_decide([dict(T_last_w=T_last_w, kfselect_mindist_t=kfselect_mindist_t, kfselect_mindist_r=kfselect_mindist_r)])
+        return self.ctx.candidates_decide_fetch()[0]
 
     def map_reserve(self, **room):
         """room per stream for the insertions to come (plsvo_candidates_reserve; no arguments: the tight layout again)"""
@@ -325,10 +357,47 @@ def candidate_map_tables(t):
                 seg_type=[int(v) for v in t["seg_type"]], seg_obs=seg_obs, pt_cand=[int(v) for v in t["pt_cand"]], seg_cand=[int(v) for v in t["seg_cand"]])
 
 
+def _set_key_points(cam, px, alive, prev):
+    """Frame::setKeyPoints / checkKeyPoints (src/frame.cpp:87-141) on indices, -1 = NULL: holders without a landmark are dropped, then every
+    feature that holds one challenges the five slots in list order (slots 3 and 4 compare x with cv, as written there)"""
+    key = [int(h) if h >= 0 and alive[h] else -1 for h in prev]
+    cu, cv = int(cam[4]) // 2, int(cam[5]) // 2
+    prod = lambda i: (float(px[i][0]) - cu) * (float(px[i][1]) - cv)
+    centre = lambda i: max(abs(float(px[i][0]) - cu), abs(float(px[i][1]) - cv))
+    for f in range(len(px)):
+        if not alive[f]:
+            continue
+        x, y = float(px[f][0]), float(px[f][1])
+        if key[0] < 0 or centre(f) < centre(key[0]):
+            key[0] = f
+        for s, ok in enumerate((x >= cu and y >= cv, x >= cu and y < cv, x < cv and y < cv, x < cv and y >= cv)):
+            if ok and (key[s + 1] < 0 or prod(f) > prod(key[s + 1])):
+                key[s + 1] = f
+    return key
+
+
+def _key_point_upkeep(cm, tab, cam, fresh=()):
+    """the key-point table on the tables as they now stand: a keyframe one of whose holders has lost its landmark (and every row of `fresh`,
+    from five NULLs) runs setKeyPoints over its features; a feature's px is its landmark's observation in that keyframe.
+    -> (the table, the rows rebuilt)"""
+    out, rebuilt = [], 0
+    for k, (fts, row) in enumerate(zip(cm["kf_pt"], tab)):
+        row = [-1] * 5 if k in fresh else [int(h) if h < len(fts) else -1 for h in row]
+        if k in fresh or any(h >= 0 and fts[h] < 0 for h in row):
+            px, alive = [], []
+            for lm in fts:
+                o = next((o for o in cm["pt_obs"][lm] if o["kf"] == k), None) if lm >= 0 else None
+                px.append(o["px"] if o else (0.0, 0.0)); alive.append(o is not None)
+            row = _set_key_points(cam, px, alive, row)
+            rebuilt += k not in fresh
+        out.append(row)
+    return out, rebuilt
+
+
 def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_thresh=2.0, mapping=False, known_frac=0.6,
                  pos_noise=0.005, map_seed=0, kf_every=5, detect=False, detect_cell_size=25, kf_select=False, kfselect_mindist_t=0.06,
                  kfselect_mindist_r=3.0, max_n_kfs=10, map_candidates=False, record_candidates=False, cell_select=False, select_params=None, kf_insert=False,
-                 seed_candidates=False, seeds_resident=False, image_seeds=None, image_seed_params=None, structopt_resident=False, compact=None, lm_room=None):
+                 seed_candidates=False, seeds_resident=False, image_seeds=None, image_seed_params=None, structopt_resident=False, compact=None, lm_room=None, keystage=None):
     """-> list of per-frame dicts (pose T_f_w, cov, counts).  Frame 0 is the keyframe with the true pose.
     mapping=True: only `known_frac` of the point landmarks start in the map (positions off by `pos_noise` x depth along
     their viewing ray), the others are depth-filter seeds; the seed update runs every frame; every `kf_every`-th frame
@@ -392,8 +461,21 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
     tables from the backend's fetch and applies the remap to its row <-> landmark maps and to the keys it follows.  The segments have no
     reserve here (no segment seed exists) and are never compacted.  lm_room: landmark rows reserved per kind instead of one per seed of
     the sequence; without compaction a sequence whose converged seeds outnumber it ends in PLSVO_E_CAPACITY.  Stable order is kept, so
-    every pose, covariance and count equals those of the run with the full reserve; the keyframe records gain n_compacted_pt."""
+    every pose, covariance and count equals those of the run with the full reserve; the keyframe records gain n_compacted_pt.
+    keystage="host" | "device" (with kf_select, cell_select and kf_insert; default None: every record is what it is without it): the
+    keyframe stage follows the reference instead of snapshotting a key point's position when its keyframe is inserted -- Frame::key_pts_
+    are positions in the keyframes' feature lists, a key point's position is its landmark's position in the tables NOW
+    (Map::getCloseKeyframes, src/map.cpp:165-169), a key point whose landmark is deleted is replaced (Map::safeDeletePoint ->
+    Frame::removeKeyPoint, :116-123), and the decision runs behind the structure optimisation (src/frame_handler_mono.cpp:340 before
+    :351) on the selection with the keep masks as alive.  "device" does it on the resident tables (plsvo_candidates_set_keypts,
+    _run_close, _keyframe_decide; DESIGN.md 3.19: a backend with map_set_keypts / map_keyframe_decide); "host" does the same with the
+    calls there were before: the key-point table kept here from the tables the harness follows, then the synchronous
+    close_keyframes / keyframe_decide on gathered arrays.  The two differ in transport alone and agree in every record; the last record
+    gains key_pts, the table at the end, every record overlap, the list itself, a keyframe's record key_pts_new, the decision's key points, and in "host" the keyframe records count the rows
+    rebuilt (n_kp_rebuilt)."""
     params = dict(locals())                            # (first statement: exactly the arguments)
+    if keystage not in (None, "host", "device") or (keystage and not (kf_select and cell_select and kf_insert and hasattr(backend, "map_keyframe_decide" if keystage == "device" else "keyframe_decide"))):
+        raise ValueError("keystage is None, 'host' or 'device' and needs kf_select, cell_select, kf_insert and a backend with keyframe_decide() / map_keyframe_decide()")
     if compact not in (None, "room", "always") or (compact and not (seed_candidates and hasattr(backend, "map_compact"))):
         raise ValueError("compact is None, 'room' or 'always' and needs seed_candidates and a backend with map_compact()")
     if structopt_resident and not (mapping and cell_select and hasattr(backend, "map_optimize_structure")):
@@ -423,8 +505,9 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
 
 def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thresh, mapping, known_frac, pos_noise, map_seed, kf_every, detect, detect_cell_size, kf_select,
                   kfselect_mindist_t, kfselect_mindist_r, max_n_kfs, map_candidates, record_candidates, cell_select, select_params, kf_insert, seed_candidates, seeds_resident,
-                  image_seeds=None, image_seed_params=None, structopt_resident=False, compact=None, lm_room=None):
+                  image_seeds=None, image_seed_params=None, structopt_resident=False, compact=None, lm_room=None, keystage=None):
     cam = seq["cam"]
+    kp_tab, kp_live = None, False                      # keystage: Frame::key_pts_ per keyframe row of cm ("host": kept here; "device": fetched when a restage needs it)
     img_kw = dict(fast_threshold=20, detection_threshold=20.0)
     img_kw.update(image_seed_params or {})
     res_lm, res_kf, res_ftr, last_rows, img_conv = [], [], [], None, 0   # image_seeds: per resident point row its landmark (-1: from the image), its keyframe row, its feature
@@ -540,20 +623,44 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
             if map_candidates:
                 # ---- 2 + 3 from the map-candidate stage: overlap keyframes' features, first visit wins, closest-view observation,
                 #      quality order, matched on the device (reprojectMap :157-183, getCloseViewObs, findMatchDirect) ----
-                if kf_select:
-                    close = backend.close_keyframes(abi.CloseKeyframesJob(cam, T_k, np.stack(kfs["T"]), np.stack(kfs["pos"]), np.stack(kfs["valid"]), max_n_kfs))
-                    overlap = [int(v) for v in close["close_idx"][:close["n_overlap"]]]
-                else:
-                    overlap = list(range(len(cm["kf_T"])))
                 map_job = None
                 if cm_dirty:
                     cm["pt_pos"] = [[float(x) for x in P3[i]] for i in row_lm]
                     map_job = candidate_map_job(cm)
                     cm_dirty = False
+                kp_frame = 0
+                if keystage:
+                    n_kf_now = len(cm["kf_T"])
+                    if map_job is not None and keystage == "device" and kp_live:
+                        kp_tab = [[int(h) for h in r] for r in backend.map_fetch_keypts()[:n_kf_now]]      # a restage drops the resident table: it travels with the tables
+                    if kp_tab is None and keystage == "host":
+                        kp_tab, _ = _key_point_upkeep(cm, [[-1] * 5] * n_kf_now, cam, fresh=range(n_kf_now))   # Frame::setKeyframe: from five NULLs
+                    kp_live = True
+                    if keystage == "host":
+                        # getCloseKeyframes reads key_pts_[k]->feat3D->pos_ as it is NOW
+                        kpos, kval = np.zeros((n_kf_now, 5, 3)), np.zeros((n_kf_now, 5), np.uint8)
+                        for j, row in enumerate(kp_tab):
+                            for s_, h in enumerate(row):
+                                lm = cm["kf_pt"][j][h] if h >= 0 else -1
+                                if lm >= 0:
+                                    kpos[j, s_], kval[j, s_] = cm["pt_pos"][lm], 1
+                        close = backend.close_keyframes(abi.CloseKeyframesJob(cam, T_k, np.array(cm["kf_T"], float).reshape(-1, 7), kpos, kval, max_n_kfs))
+                        overlap = [int(v) for v in close["close_idx"][:close["n_overlap"]]]
+                    else:
+                        overlap = []                   # decided on the device, from the resident table
+                elif kf_select:
+                    close = backend.close_keyframes(abi.CloseKeyframesJob(cam, T_k, np.stack(kfs["T"]), np.stack(kfs["pos"]), np.stack(kfs["valid"]), max_n_kfs))
+                    overlap = [int(v) for v in close["close_idx"][:close["n_overlap"]]]
+                else:
+                    overlap = list(range(len(cm["kf_T"])))
                 if cell_select:
                     cm_before = copy.deepcopy(cm) if record_candidates else None
                     cr, mr, sel, pr_sel, q_after = backend.map_select(map_job, abi.CandidateFrameJob(T_k, overlap, cur_slot=k), cam, n_pyr_levels, select_kw,
-                                                                      carry=quality if map_job is not None else None)
+                                                                      carry=quality if map_job is not None else None,
+                                                                      **(dict(close=max_n_kfs, key_pts=kp_tab) if keystage == "device" else {}))
+                    if keystage == "device":
+                        close = backend.last_close
+                        overlap = [int(v) for v in close["close_idx"][:close["n_overlap"]]]
                     if structopt_resident and map_job is not None and (any(so_keys["pt"]) or any(so_keys["seg"])):
                         # the keys do not survive a stage: carried over like the quality counters (rows appended since read 0)
                         backend.map_set_last_optim(so_keys["pt"] + [0] * (len(cm["pt_pos"]) - len(so_keys["pt"])), so_keys["seg"] + [0] * (len(cm["seg_spos"]) - len(so_keys["seg"])))
@@ -603,6 +710,8 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                     if record_candidates:
                         cand_rec["candidates"].update(select=sel, quality_before=quality, quality=q_after, select_params=dict(select_kw))
                     quality = q_after
+                    if keystage == "host":             # removeKeyPoint of the landmarks the selection deleted
+                        kp_tab, kp_frame = _key_point_upkeep(cm, kp_tab, cam)
             else:
                 # ---- 2. reprojection of the whole map (Reprojector::reprojectMap) ----
                 rp = backend.reproject(abi.ReprojectJob(cam, np.stack([kf_T, T_k]), np.ones(len(pos_all), np.int32), pos_all, cell_size=30))
@@ -668,7 +777,7 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
             poses_est.append(T_k.copy())
             kept = pt_i[pt_keep]
             is_kf = (k % kf_every) == 0
-            if kf_select:
+            if kf_select and not keystage:
                 # ---- scene depth, needNewKf against the overlap keyframes from the previous frame's pose, the frame's key points ----
                 skept = seg_i[seg_keep]
                 dec = decide(T_k, T_last, px_new[kept], P3[kept], seq["seg_spos"][skept], seq["seg_epos"][skept], close["close_idx"][:close["n_overlap"]])
@@ -696,6 +805,22 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                 if record_candidates:
                     rec["structopt"] = dict(stream=before[0], keys_before=before[1], select=sel, pt_keep=pr.pt_keep.copy(), seg_keep=pr.seg_keep.copy(), frame_id=k, report=so,
                                             tables=copy.deepcopy(cm), keys=copy.deepcopy(so_keys))
+            if keystage:
+                # ---- the keyframe decision behind the structure optimisation (:340 before :351), on the selection with the keep masks as
+                #      alive and the landmark positions as the tables hold them now; key_pts are indices in selection order ----
+                if keystage == "device":
+                    dec = backend.map_keyframe_decide(T_last, kfselect_mindist_t, kfselect_mindist_r)
+                else:
+                    at = lambda name, rows: np.array([cm[name][int(r)] for r in rows], float).reshape(-1, 3)
+                    dec = backend.keyframe_decide(abi.KeyframeDecideJob(cam, T_k, T_last, sel["pt_px"], at("pt_pos", sel["pt_lm"]), pr.pt_keep, at("seg_spos", sel["seg_lm"]),
+                                                                        at("seg_epos", sel["seg_lm"]), pr.seg_keep, np.array(cm["kf_T"], float).reshape(-1, 7),
+                                                                        close["close_idx"][:close["n_overlap"]], (-1,) * 5, kfselect_mindist_t, kfselect_mindist_r))
+                is_kf = bool(dec["need_new_kf"])
+                rec.update(is_kf=is_kf, n_overlap=close["n_overlap"], depth_mean=dec["depth_mean"], overlap=[int(v) for v in close["close_idx"][:close["n_overlap"]]])
+                if is_kf:
+                    rec["key_pts_new"] = [int(h) for h in dec["key_pts"]]      # the frame's key_pts_ as it becomes a keyframe, in selection order
+                if is_kf and dec["has_depth"]:
+                    seed_depth = (dec["depth_mean"] * 2.0, 0.1 * dec["depth_min"])
             if is_kf:
                 for i, brg in zip(kept, _bearing(cam, px_new[kept])):
                     obs[int(i)].append((k, brg))
@@ -704,13 +829,16 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                     remove = -1
                     if kf_select and len(cm["kf_T"]) >= max_n_kfs:
                         remove = max(int(dec["furthest_kf"]), 0)
-                        for key in kfs:
+                        for key in ([] if keystage else kfs):
                             del kfs[key][remove]
                         if seed_kf is not None:                       # the table closes up: frame 0's row moves, or is gone
                             seed_kf = None if remove == seed_kf else seed_kf - (remove < seed_kf)
                     before = (copy.deepcopy(cm), quality) if record_candidates else None
                     tables, quality, ins = backend.map_insert(remove, k)
                     cm = candidate_map_tables(tables)
+                    if keystage == "host":             # the rows close up, the new keyframe's row is the decision's, holders lost to the removal are replaced
+                        kp_tab, n_ = _key_point_upkeep(cm, [r for j, r in enumerate(kp_tab) if j != remove] + [[int(h) for h in dec["key_pts"]]], cam)
+                        kp_frame += n_
                     if seeds_on_device and image_seeds and seed_kf is not None:
                         # initializeSeeds on the resident lists: the removal, then the corners of the frame's free cells
                         new_kf = len(cm["kf_T"]) - 1
@@ -748,6 +876,8 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                         seeds_on_device = seed_kf is not None
                         res_lm, res_kf, res_ftr = [], [], []
                     rec.update(n_joined=ins["n_joined_pt"] + ins["n_joined_seg"], n_deleted_kf=ins["n_deleted_pt"] + ins["n_deleted_seg"], remove_kf=remove)
+                    if keystage == "host":
+                        rec["n_kp_rebuilt"] = int(kp_frame)
                     if compact:
                         # Map::emptyTrash on the resident tables: the deleted point rows leave, the rows behind them move down; the
                         # harness's rows follow the remap ("room": only when every live seed could no longer get a row)
@@ -905,6 +1035,8 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
             rec.update(n_known=int(known.sum()), n_seeds=len(seeds["idx"]),
                        landmark_err=float(np.median(np.linalg.norm(P3[known] - seq["pt_pos"][known], axis=1))))
         out.append(rec)
+    if keystage and kp_live:                           # Frame::key_pts_ of every keyframe at the end
+        out[-1]["key_pts"] = np.array(kp_tab if keystage == "host" else backend.map_fetch_keypts()[:len(cm["kf_T"])], np.int32).reshape(-1, 5)
     return out
 
 

@@ -310,6 +310,9 @@ int plsvo_align_fetch(plsvo_ctx* ctx, int n, plsvo_align_out* out);
 int plsvo_align_slot_layout(const plsvo_align_in* in, int level, int32_t* seg_code, int32_t* n_slots, int32_t* long_lines,
                             long long* n_patches);
 
+/* Diagnostic (measurements): the threads per frame and the LDS bytes per workgroup plsvo_align_run would launch the staged batch with. */
+int plsvo_align_launch_shape(plsvo_ctx* ctx, int32_t* threads, uint64_t* lds_bytes);
+
 int plsvo_align_set_trace(plsvo_ctx* ctx, int max_records_per_job);
 int plsvo_align_fetch_trace(plsvo_ctx* ctx, int job, plsvo_align_iterlog* out, int max_records,
                             int* n_records);
@@ -1392,6 +1395,107 @@ typedef struct plsvo_cand_kf_decide {
  * decide_fetch without a decision on the last run.  PLSVO_E_INVALID (nothing written): another n than staged, NULL in / out with n > 0. */
 int plsvo_candidates_keyframe_decide(plsvo_ctx* ctx, int n, const plsvo_cand_kf_decide* in);
 int plsvo_candidates_decide_fetch(plsvo_ctx* ctx, int n, plsvo_kf_decide_out* out);
+
+/* ------------------------------------------------------------------------------------------ */
+/* the next frame's alignment job from the resident selection, built on the device              */
+/* replaces, per tracked frame, what the caller gathered on the host for                        */
+/* SparseImgAlign::run(last_frame_, new_frame_) (src/frame_handler_mono.cpp:266-274): the       */
+/* reference frame's features that still hold a landmark, f * ||pos_ - ref_frame->pos()||       */
+/* (src/sparse_img_align.cpp:229-230, :327-330), LineFeat::length (src/feature.cpp:90), the      */
+/* initial model (:80), and the patch-slot layout plsvo_align_stage computes on one host thread  */
+/* (one wave per stream).  The reference frame is the frame the last run         */
+/* tracked: its features are the last selection's, in selection order; a feature holds its       */
+/* landmark when its keep byte is non-zero.                                                      */
+/* PINNED: a feature whose landmark row is PLSVO_LM_DELETED at build time counts as              */
+/* feat3D == NULL (Map::safeDeleteFrame, src/map.cpp:82-127, cuts such landmarks loose from the  */
+/* new keyframe's features).  LEFT OUT: a keyframe of the tables as the reference frame (the     */
+/* first frame, relocalizeFrame :408-436); the tracking-quality gates (:315-321, :335); writing  */
+/* the alignment's cull back into a keyframe's own segment features                              */
+/* (src/sparse_img_align.cpp:687-688); the C++ adapter.                                          */
+/* ------------------------------------------------------------------------------------------ */
+
+/* The resident alignment batch: per-stream CAPACITIES, by which its rows are laid out (stream s owns point rows from s * cap_pts,
+ * segment rows from s * cap_seg, patch slots from s * slot_cap rounded up to 4), and SparseImgAlign's constructor arguments. */
+typedef struct plsvo_cand_align_cfg {
+  int32_t max_level, min_level;     /* src/sparse_img_align.cpp:40-52; levels of the configured pyramid */
+  int32_t n_iter;                   /* 30 at the call sites */
+  int32_t cap_pts, cap_seg;         /* kept point features / segment features (all of them, kept or not) of one stream */
+  int32_t slot_cap;                 /* patch slots of one stream's largest level (plsvo_align_slot_layout's n_slots); at most 8064 */
+  double eps;                       /* 1e-6 */
+} plsvo_cand_align_cfg;
+
+/* One stream's record of a build.  pose_source: PLSVO_INSERT_POSE_* -- where the reference frame's T_f_w is read (RESIDENT: the
+ * optimised pose of plsvo_candidates_pose_optimize).  pt_keep / seg_keep: host masks in selection order (n_matches / n_ls_matches
+ * bytes), or NULL for the pose optimiser's resident ones. */
+typedef struct plsvo_cand_align_job {
+  int32_t active;                   /* 0: the stream sits this build out; its job, poses and report are what an earlier build left (an empty job after the reserve) */
+  int32_t ref_slot, cur_slot;       /* pyramid slots of the reference frame and of the frame to be aligned */
+  int32_t pose_source;
+  double T_f_w[7];
+  const double* d_T_f_w;            /* a DEVICE pointer to 7 doubles (PLSVO_INSERT_POSE_DEV) */
+  const uint8_t* pt_keep;
+  const uint8_t* seg_keep;
+} plsvo_cand_align_job;
+
+#define PLSVO_ALIGN_JOB_OK      0
+#define PLSVO_ALIGN_JOB_NO_ROOM 1   /* kept points > cap_pts, segments > cap_seg, a level's slots > slot_cap, or a segment of more than 2047 samples:
+                                       the stream was dropped whole -- its job has no features and skip set, its composed pose is its reference pose */
+typedef struct plsvo_cand_align_report {   /* 32 bytes per stream */
+  int32_t n_pts, n_seg;             /* kept point features; segment features */
+  int32_t n_seg_alive;              /* of those, the ones that hold a landmark */
+  int32_t n_slots;                  /* patch slots of the finest level; 0 when the layout was not reached (cap_pts / cap_seg exceeded) or could not be made */
+  int32_t long_mask;                /* bit l: level l has a segment of more than 64 samples */
+  int32_t status;                   /* PLSVO_ALIGN_JOB_* */
+  int32_t reserved0, reserved1;
+} plsvo_cand_align_report;
+
+/* Diagnostic view of one stream's built job (tests, like plsvo_align_fetch_records).  Every array is a caller buffer of the
+ * CAPACITY'S size or NULL: pt_* cap_pts entries (2 / 3 doubles each), seg_* cap_seg, seg_code (max_level - min_level + 1) * cap_seg
+ * int32, level-major from min_level (first slot | N << 20, or -1); the first n_pts / n_seg entries are written. */
+typedef struct plsvo_cand_align_job_out {
+  int32_t n_pts, n_seg, skip, long_mask;
+  int32_t n_slots[PLSVO_MAX_LEVELS];
+  int32_t ref_slot, cur_slot;
+  int32_t n_patches;                /* the launch-order key of the stream's last build: points + samples summed over the levels */
+  int32_t reserved0;
+  double T0[7];                     /* the initial model T_cur_from_ref = T_ref * T_ref^-1 */
+  double T_ref[7];                  /* the reference frame's T_f_w as the build read it */
+  double T_f_w[7];                  /* the composed pose of the last plsvo_candidates_align_compose (the identity before the first) */
+  double* pt_px; double* pt_xyz_ref;
+  double* seg_spx; double* seg_epx; double* seg_len; double* seg_p_ref; double* seg_q_ref;
+  uint8_t* seg_alive_in;
+  int32_t* seg_code;
+} plsvo_cand_align_job_out;
+
+/* align_reserve: allocates the resident alignment batch for the staged streams (synchronous; every stream starts with an empty job).
+ *   PLSVO_E_STATE without plsvo_candidates_stage or configured pyramids; PLSVO_E_INVALID for levels outside the configured pyramid,
+ *   n_iter < 0, non-positive capacities, a camera other than the pyramids' level 0; PLSVO_E_CAPACITY for slot_cap > 8064 or slot tables beyond a
+ *   workgroup's LDS in the shape a batch of the staged stream count launches with (few streams get many threads and more LDS per slot) or a batch beyond 2^31 rows.  A later plsvo_candidates_stage of another stream count drops it.
+ * align_build: ENQUEUE ONLY with resident masks -- only the records travel (host masks cost one wait for the selection's counts).
+ *   Its place is behind plsvo_candidates_pose_optimize, and behind _optimize_structure and _insert_keyframe (and _add) when the frame
+ *   has them: it reads the landmark positions and types as they are then.  It must be ahead of plsvo_candidates_compact, which
+ *   renumbers the rows the selection points at.  A successful build makes the built batch the context's STAGED ALIGNMENT BATCH,
+ *   exactly as plsvo_align_stage would on the same inputs: it replaces a previously staged batch and invalidates a staged frame
+ *   step; plsvo_align_run, _fetch, _poses_dev, _set_trace, _fetch_trace, _fetch_records, _chi2_ties, _work, _launch_order serve it
+ *   unchanged.  The host's view of the batch holds the capacities: plsvo_align_fetch's seg_alive_out needs cap_seg bytes per stream
+ *   (the first n_seg are the stream's), plsvo_align_fetch_records is bounded by slot_cap.  The first launch's order is most patches first
+ *   (a stream that sat the build out counts with the patches of its last one); it is the order PLSVO_OPT_ALIGN_REORDER = 0 goes back to.
+ *   PLSVO_E_STATE: no reserve (or one for another stream count); no selection on the last run; NULL masks or
+ *   PLSVO_INSERT_POSE_RESIDENT without a resident pose optimisation; behind the run's compaction; between plsvo_seeds_update and its
+ *   fetch.  PLSVO_E_INVALID (nothing enqueued): another n than staged, NULL jobs, an unknown pose source, PLSVO_INSERT_POSE_DEV
+ *   without a pointer, a slot outside the pyramids.
+ * align_compose: enqueue only, behind plsvo_align_run of the built batch: T_f_w(new) = T_cur_from_ref * T_ref per stream
+ *   (src/sparse_img_align.cpp:92) into n * 7 doubles on the device.  PLSVO_E_STATE unless the staged alignment batch is the built one and has run.
+ * align_poses_dev: that buffer (NULL before the first compose): what plsvo_cand_frame::d_T_f_w, plsvo_seed_frame::d_T_f_w and
+ *   plsvo_cand_kf_decide::d_T_last_w take -- stream s at + 7 * s.
+ * align_fetch: synchronises; the reports of the last build (a stream that sat it out: of its last one).
+ * align_fetch_job: synchronises; PLSVO_E_INVALID for a stream outside the batch. */
+int plsvo_candidates_align_reserve(plsvo_ctx* ctx, const plsvo_cand_align_cfg* cfg);
+int plsvo_candidates_align_build(plsvo_ctx* ctx, int n, const plsvo_cand_align_job* jobs);
+int plsvo_candidates_align_compose(plsvo_ctx* ctx);
+const double* plsvo_candidates_align_poses_dev(plsvo_ctx* ctx);
+int plsvo_candidates_align_fetch(plsvo_ctx* ctx, int n, plsvo_cand_align_report* out);
+int plsvo_candidates_align_fetch_job(plsvo_ctx* ctx, int stream, plsvo_cand_align_job_out* out);
 
 /* TUM-style trajectory record of a frame (app/run_pipeline.cpp:425-451): the camera pose in the world,
  * T_f_w^-1, as tx ty tz qx qy qz qw.  Returns 1 and fills out7 when the reference would write the line, 0 when

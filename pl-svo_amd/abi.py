@@ -320,6 +320,41 @@ class CandLastOptimOut(C.Structure):
     _fields_ = [("pt_last_optim", c_i32_p), ("seg_last_optim", c_i32_p)]
 
 
+ALIGN_JOB_OK, ALIGN_JOB_NO_ROOM = 0, 1
+
+
+class CandAlignCfg(C.Structure):
+    """plsvo_cand_align_cfg"""
+    _fields_ = [("max_level", C.c_int32), ("min_level", C.c_int32), ("n_iter", C.c_int32), ("cap_pts", C.c_int32), ("cap_seg", C.c_int32), ("slot_cap", C.c_int32),
+                ("eps", C.c_double)]
+
+
+class CandAlignJob(C.Structure):
+    """plsvo_cand_align_job"""
+    _fields_ = [("active", C.c_int32), ("ref_slot", C.c_int32), ("cur_slot", C.c_int32), ("pose_source", C.c_int32), ("T_f_w", C.c_double * 7), ("d_T_f_w", C.c_void_p),
+                ("pt_keep", c_u8_p), ("seg_keep", c_u8_p)]
+
+
+class BuiltAlignJob:
+    """what capi.Context.align_fetch() needs to know of a job built on the device: the segment flags come back cap_seg bytes per stream"""
+
+    def __init__(self, cap_seg):
+        self.n_seg = int(cap_seg)
+
+
+class CandAlignReport(C.Structure):
+    """plsvo_cand_align_report"""
+    _fields_ = [(f, C.c_int32) for f in ("n_pts", "n_seg", "n_seg_alive", "n_slots", "long_mask", "status", "reserved0", "reserved1")]
+
+
+class CandAlignJobOut(C.Structure):
+    """plsvo_cand_align_job_out"""
+    _fields_ = [("n_pts", C.c_int32), ("n_seg", C.c_int32), ("skip", C.c_int32), ("long_mask", C.c_int32), ("n_slots", C.c_int32 * MAX_LEVELS), ("ref_slot", C.c_int32),
+                ("cur_slot", C.c_int32), ("n_patches", C.c_int32), ("reserved0", C.c_int32), ("T0", C.c_double * 7), ("T_ref", C.c_double * 7), ("T_f_w", C.c_double * 7),
+                ("pt_px", c_double_p), ("pt_xyz_ref", c_double_p), ("seg_spx", c_double_p), ("seg_epx", c_double_p), ("seg_len", c_double_p), ("seg_p_ref", c_double_p),
+                ("seg_q_ref", c_double_p), ("seg_alive_in", c_u8_p), ("seg_code", c_i32_p)]
+
+
 LM_EVENT_NEW = 8
 
 

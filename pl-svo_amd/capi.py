@@ -22,7 +22,7 @@ SYMBOLS = [
     "plsvo_rectify_map", "plsvo_hip_config_rectify", "plsvo_hip_rectify_build_pyramid", "plsvo_hip_rectify_build_pyramids_dev",
     "plsvo_detect_grid", "plsvo_detect_cell", "plsvo_hip_detect_fast", "plsvo_hip_detect_fast_dev", "plsvo_hip_detect_stages",
     "plsvo_sparse_align", "plsvo_sparse_align_batch", "plsvo_align_stage", "plsvo_align_run", "plsvo_align_fetch",
-    "plsvo_align_set_trace", "plsvo_align_fetch_trace", "plsvo_align_fetch_records", "plsvo_align_poses_dev", "plsvo_align_copy_poses", "plsvo_align_work", "plsvo_align_work_points", "plsvo_align_chi2_ties", "plsvo_align_launch_order", "plsvo_align_tail_frames",
+    "plsvo_align_set_trace", "plsvo_align_fetch_trace", "plsvo_align_fetch_records", "plsvo_align_poses_dev", "plsvo_align_copy_poses", "plsvo_align_work", "plsvo_align_work_points", "plsvo_align_chi2_ties", "plsvo_align_launch_order", "plsvo_align_tail_frames", "plsvo_align_launch_shape",
     "plsvo_pose_optimize", "plsvo_pose_optimize_batch", "plsvo_poseopt_stage", "plsvo_poseopt_run", "plsvo_poseopt_fetch",
     "plsvo_poseopt_set_trace", "plsvo_poseopt_fetch_trace", "plsvo_poseopt_poses_dev", "plsvo_poseopt_copy_poses", "plsvo_poseopt_work", "plsvo_poseopt_refill_frames", "plsvo_poseopt_row_select",
     "plsvo_structure_optimize", "plsvo_structure_solve3", "plsvo_match_direct", "plsvo_match_warp_patches", "plsvo_reproject", "plsvo_trajectory_record", "plsvo_update_seeds",
@@ -34,6 +34,8 @@ SYMBOLS = [
     "plsvo_candidates_optimize_structure", "plsvo_candidates_structure_fetch", "plsvo_candidates_set_last_optim", "plsvo_candidates_fetch_last_optim",
     "plsvo_candidates_reserve_landmarks", "plsvo_candidates_lm_capacity", "plsvo_candidates_add", "plsvo_candidates_add_fetch",
     "plsvo_candidates_compact", "plsvo_candidates_compact_fetch",
+    "plsvo_candidates_align_reserve", "plsvo_candidates_align_build", "plsvo_candidates_align_compose", "plsvo_candidates_align_poses_dev", "plsvo_candidates_align_fetch",
+    "plsvo_candidates_align_fetch_job",
     "plsvo_seeds_reserve", "plsvo_seeds_capacity", "plsvo_seeds_stage", "plsvo_seeds_update", "plsvo_seeds_update_fetch", "plsvo_seeds_keyframe", "plsvo_seeds_fetch_lists",
     "plsvo_seeds_fetch_rows", "plsvo_seeds_commit_rows", "plsvo_seeds_keyframe_detect", "plsvo_seeds_keyframe_fetch",
     "plsvo_chain_stage", "plsvo_chain_run", "plsvo_chain_fetch", "plsvo_frame_step_batch", "plsvo_chain_poses_dev",
@@ -188,6 +190,13 @@ def lib():
         "plsvo_candidates_add_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandAddOut)]),
         "plsvo_candidates_compact": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandCompact)]),
         "plsvo_candidates_compact_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandCompactOut)]),
+        "plsvo_align_launch_shape": (C.c_int, [ctxp, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
+        "plsvo_candidates_align_reserve": (C.c_int, [ctxp, C.POINTER(abi.CandAlignCfg)]),
+        "plsvo_candidates_align_build": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandAlignJob)]),
+        "plsvo_candidates_align_compose": (C.c_int, [ctxp]),
+        "plsvo_candidates_align_poses_dev": (C.c_void_p, [ctxp]),
+        "plsvo_candidates_align_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandAlignReport)]),
+        "plsvo_candidates_align_fetch_job": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandAlignJobOut)]),
         "plsvo_seeds_reserve": (C.c_int, [ctxp, C.POINTER(abi.SeedReserve)]),
         "plsvo_seeds_capacity": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.SeedReserve)]),
         "plsvo_seeds_stage": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.SeedParams), C.POINTER(abi.SeedList)]),
@@ -497,6 +506,12 @@ class Context:
         n = C.c_int(0)
         self._chk(self.L.plsvo_poseopt_refill_frames(self.h, C.byref(n)))
         return n.value
+
+    def align_launch_shape(self):
+        """plsvo_align_launch_shape (diagnostic): (threads per frame, LDS bytes per workgroup) align_run() would launch the staged batch with"""
+        t, lds = C.c_int32(0), C.c_uint64(0)
+        self._chk(self.L.plsvo_align_launch_shape(self.h, C.byref(t), C.byref(lds)))
+        return t.value, lds.value
 
     def align_tail_frames(self):
         """plsvo_align_tail_frames: frames of the last align_run that ran as a coarse and a fine workgroup (0 = launch not split)"""
@@ -1150,6 +1165,70 @@ class Context:
                     keep.append(v)
                     setattr(a, f, v.ctypes.data_as(abi.c_double_p))
         self._chk(self.L.plsvo_candidates_set_positions(self.h, n, arr))
+
+    # ---- the next frame's alignment job built on the device from the resident selection ----
+    def candidates_align_reserve(self, max_level, min_level, cap_pts, cap_seg, slot_cap, n_iter=30, eps=1e-6):
+        """plsvo_candidates_align_reserve: the resident alignment batch of the staged streams, laid out by the per-stream capacities"""
+        g = abi.CandAlignCfg(int(max_level), int(min_level), int(n_iter), int(cap_pts), int(cap_seg), int(slot_cap), float(eps))
+        self._chk(self.L.plsvo_candidates_align_reserve(self.h, C.byref(g)))
+        self._align_cfg = dict(max_level=int(max_level), min_level=int(min_level), cap_pts=int(cap_pts), cap_seg=int(cap_seg), slot_cap=int(slot_cap))
+
+    def candidates_align_build(self, jobs):
+        """plsvo_candidates_align_build (enqueue only with resident masks): per staged stream None (sits the build out) or a dict of
+        ref_slot, cur_slot, the reference frame's pose as T_f_w (7 doubles), or poses_dev (a device pointer), or neither (the resident
+        optimised pose), and optionally pt_keep / seg_keep (host masks in selection order; missing: the resident pose optimiser's).
+        The built batch is the staged alignment batch afterwards: align_run() / align_fetch() serve it (seg_alive of cap_seg bytes)."""
+        n = len(jobs)
+        arr = (abi.CandAlignJob * max(n, 1))()
+        keep = []
+        for a, j in zip(arr, jobs):
+            if j is None:
+                continue
+            a.active, a.ref_slot, a.cur_slot = 1, int(j.get("ref_slot", 0)), int(j.get("cur_slot", 0))
+            if j.get("T_f_w") is not None:
+                a.pose_source, a.T_f_w = abi.INSERT_POSE_HOST, (C.c_double * 7)(*[float(v) for v in j["T_f_w"]])
+            elif j.get("poses_dev") is not None:
+                a.pose_source, a.d_T_f_w = abi.INSERT_POSE_DEV, int(j["poses_dev"])
+            else:
+                a.pose_source = abi.INSERT_POSE_RESIDENT
+            for f in ("pt_keep", "seg_keep"):
+                if j.get(f) is not None:
+                    v = np.ascontiguousarray(j[f], dtype=np.uint8).reshape(-1)
+                    v = v if v.size else np.zeros(1, np.uint8)
+                    keep.append(v)
+                    setattr(a, f, v.ctypes.data_as(abi.c_u8_p))
+        self._chk(self.L.plsvo_candidates_align_build(self.h, n, arr))
+        self._align_jobs = [abi.BuiltAlignJob(self._align_cfg["cap_seg"]) for _ in range(n)]      # what align_fetch() sizes its buffers by
+
+    def candidates_align_compose(self):
+        """plsvo_candidates_align_compose (enqueue only, behind align_run of the built batch)"""
+        self._chk(self.L.plsvo_candidates_align_compose(self.h))
+
+    def candidates_align_poses_dev(self):
+        return self.L.plsvo_candidates_align_poses_dev(self.h)
+
+    def candidates_align_fetch(self):
+        """plsvo_candidates_align_fetch (synchronises): per stream a dict of abi.CandAlignReport's fields"""
+        n = len(self._cand_maps)
+        outs = (abi.CandAlignReport * max(n, 1))()
+        self._chk(self.L.plsvo_candidates_align_fetch(self.h, n, outs))
+        return [{f: int(getattr(o, f)) for f, _ in abi.CandAlignReport._fields_ if not f.startswith("reserved")} for o in outs[:n]]
+
+    def candidates_align_fetch_job(self, stream):
+        """plsvo_candidates_align_fetch_job (diagnostic, synchronises): one stream's built job as a dict -- the counts, n_slots (8), T0,
+        T_ref, T_f_w (the composed pose), the feature arrays cut to n_pts / n_seg, seg_code [levels, n_seg] from min_level up"""
+        g = self._align_cfg
+        cp, cs, nl = g["cap_pts"], g["cap_seg"], g["max_level"] - g["min_level"] + 1
+        b = dict(pt_px=np.zeros((cp, 2)), pt_xyz_ref=np.zeros((cp, 3)), seg_spx=np.zeros((cs, 2)), seg_epx=np.zeros((cs, 2)), seg_len=np.zeros(cs), seg_p_ref=np.zeros((cs, 3)),
+                 seg_q_ref=np.zeros((cs, 3)), seg_alive_in=np.zeros(cs, np.uint8), seg_code=np.full((nl, cs), -9, np.int32))
+        o = abi.CandAlignJobOut()
+        for k, v in b.items():
+            setattr(o, k, self._ptr(v))
+        self._chk(self.L.plsvo_candidates_align_fetch_job(self.h, int(stream), C.byref(o)))
+        r = dict(n_pts=int(o.n_pts), n_seg=int(o.n_seg), skip=int(o.skip), long_mask=int(o.long_mask), n_slots=np.array(o.n_slots[:], np.int32), ref_slot=int(o.ref_slot),
+                 cur_slot=int(o.cur_slot), n_patches=int(o.n_patches), T0=np.array(o.T0[:]), T_ref=np.array(o.T_ref[:]), T_f_w=np.array(o.T_f_w[:]))
+        r.update({k: (v[:, :o.n_seg] if k == "seg_code" else v[:(o.n_pts if k.startswith("pt_") else o.n_seg)]).copy() for k, v in b.items()})
+        return r
 
     # ---- structure optimisation on the resident map tables ----
     def candidates_optimize_structure(self, jobs, max_n_pts=20, n_iter_pts=5, max_n_segs=20, n_iter_segs=5):

@@ -1352,6 +1352,267 @@ extern "C" int plsvo_candidates_compact_fetch(plsvo_ctx* c, int n, plsvo_cand_co
   return PLSVO_OK;
 }
 
+// ---- the next frame's alignment job from the resident selection (alignjob_device.hpp) ------------------------------------------
+namespace {
+// the sections of aj_d_batch (the resident alignment batch, rows by capacity) and of aj_d_out (reports, reference poses, composed poses)
+struct AlignJobSections { size_t jobs, T0, pt_px, pt_xyz, spx, epx, len, sp, sq, alive, slot, rank, end, o_report, o_tref, o_poses, o_key, o_end; };
+static AlignJobSections align_job_sections(size_t n, const plsvo_cand_align_cfg& g) {
+  const size_t np = n * (size_t)g.cap_pts, ns = n * (size_t)g.cap_seg, nl = (size_t)(g.max_level - g.min_level + 1);
+  Carver w; AlignJobSections o;
+  o.jobs = w.take<AlignJobDev>(n); o.T0 = w.take<double>(n * 7); o.pt_px = w.take<double>(np * 2); o.pt_xyz = w.take<double>(np * 3);
+  o.spx = w.take<double>(ns * 2); o.epx = w.take<double>(ns * 2); o.len = w.take<double>(ns); o.sp = w.take<double>(ns * 3); o.sq = w.take<double>(ns * 3);
+  o.alive = w.take<uint8_t>(ns); o.slot = w.take<int>(nl * ns); o.rank = w.take<int>(ns); o.end = w.off;
+  Carver v;
+  o.o_report = v.take<AlignBuildReportDev>(n); o.o_tref = v.take<double>(n * 7); o.o_poses = v.take<double>(n * 7); o.o_key = v.take<int>(n); o.o_end = v.off;   // (o_key: the patch count of every stream's last build, the launch-order key)
+  return o;
+}
+static int align_patch_cap(const plsvo_cand_align_cfg& g) { return (g.slot_cap + 3) & ~3; }
+// the work buffers of the alignment launch for a batch of n streams of the reserved capacities (plsvo_align_stage sizes the same ones: none shrinks)
+static int align_job_work(plsvo_ctx* c, size_t n, const plsvo_cand_align_cfg& g) {
+  const size_t pt = std::max(n * (size_t)align_patch_cap(g), (size_t)4), npt_total = n * (size_t)g.cap_pts + 32;
+  HIP_TRY(c, c->a_d_alive.ensure(std::max(n * (size_t)g.cap_seg, (size_t)1)));
+  HIP_TRY(c, c->a_d_state.ensure(n * sizeof(AlignStateDev)));
+  HIP_TRY(c, c->a_d_poses.ensure(n * 7 * sizeof(double)));
+  HIP_TRY(c, c->a_d_pxyz.ensure(pt * 3 * sizeof(double)));
+  HIP_TRY(c, c->a_d_puv.ensure(pt * 2 * sizeof(float)));
+  HIP_TRY(c, c->a_d_cref.ensure(pt * 64));
+  HIP_TRY(c, c->a_d_chi.ensure(2 * npt_total * 16 * sizeof(float)));
+  if (c->a_trace_cap > 0) HIP_TRY(c, c->a_d_log.ensure(n * (size_t)c->a_trace_cap * sizeof(plsvo_align_iterlog)));
+  return PLSVO_OK;
+}
+}  // namespace
+
+extern "C" int plsvo_candidates_align_reserve(plsvo_ctx* c, const plsvo_cand_align_cfg* g) {
+  CTX_CHECK(c);
+  if (!g) return fail(c, PLSVO_E_INVALID, "candidates_align_reserve: bad arguments");
+  if (!c->cd_staged) return fail(c, PLSVO_E_STATE, "candidates_align_reserve: no staged map tables");
+  if (!c->pyr.base) return fail(c, PLSVO_E_STATE, "candidates_align_reserve: pyramids not configured");
+  if (g->max_level < g->min_level || g->min_level < 0 || g->max_level >= c->pyr.n_levels || g->n_iter < 0)
+    return fail(c, PLSVO_E_INVALID, "candidates_align_reserve: bad parameters (levels must exist in the configured pyramid)");
+  if (g->cap_pts <= 0 || g->cap_seg <= 0 || g->slot_cap <= 0) return fail(c, PLSVO_E_INVALID, "candidates_align_reserve: non-positive capacity");
+  if (c->cd_b.cam_width != c->pyr.w[0] || c->cd_b.cam_height != c->pyr.h[0])
+    return fail(c, PLSVO_E_INVALID, "candidates_align_reserve: the staged camera's size does not match the configured pyramid");
+  const int n = c->cd_n, patch_cap = align_patch_cap(*g), scap = (std::max(g->cap_seg, 4) + 3) & ~3;
+  // the shape plsvo_align_run launches a batch of this many streams with: few streams get many threads, and more LDS per slot
+  int run_threads = 64, run_chi = 0; size_t run_lds = 0;
+  pick_align_config(c, std::max(n, 1), std::max(patch_cap, 4), scap, g->cap_pts, &run_threads, &run_lds, &run_chi);
+  if (g->slot_cap > kAlignJobMaxSlotCap || g->cap_seg >= (1 << 20) || run_lds > c->lds_per_block)
+    return fail(c, PLSVO_E_CAPACITY, "candidates_align_reserve: slot tables of these capacities do not fit a workgroup's LDS at " + std::to_string(run_threads) + " threads per frame");
+  const long long rows = std::max<long long>(std::max(g->cap_pts, g->cap_seg), patch_cap);
+  if ((long long)std::max(n, 1) * rows * (g->max_level - g->min_level + 1) > (long long)0x7fffffff / 16)
+    return fail(c, PLSVO_E_CAPACITY, "candidates_align_reserve: batch too large (row index overflow)");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (c->aj_built) c->a_staged = false;             // the built batch's rows are laid out anew
+  c->aj_reserved = c->aj_built = c->aj_composed = false;
+  const size_t N = (size_t)n;
+  const AlignJobSections o = align_job_sections(N, *g);
+  HIP_TRY(c, c->aj_d_batch.ensure(o.end + 256));
+  HIP_TRY(c, c->aj_d_out.ensure(o.o_end + 256));
+  if (const int rc = align_job_work(c, N, *g)) return rc;
+  // every stream starts with an empty job (skip) at the identity; codes -1, reports zero
+  std::vector<AlignJobDev> jobs(N);
+  std::vector<double> ident(N * 7, 0.0);
+  for (int j = 0; j < n; ++j) {
+    AlignJobDev& J = jobs[(size_t)j];
+    memset(&J, 0, sizeof(J));
+    J.fx = c->cd_b.fx; J.fy = c->cd_b.fy; J.cx = c->cd_b.cx; J.cy = c->cd_b.cy; J.width = c->cd_b.cam_width; J.height = c->cd_b.cam_height;
+    J.max_level = g->max_level; J.min_level = g->min_level; J.n_iter = g->n_iter; J.skip = 1; J.eps = g->eps;
+    J.pt_off = j * g->cap_pts; J.seg_off = j * g->cap_seg; J.patch_off = j * patch_cap; J.patch_cap = patch_cap; J.ldlt_flavour = c->ldlt_flavour;
+    ident[(size_t)j * 7 + 3] = 1.0;
+  }
+  char* db = c->aj_d_batch.as<char>(); char* dout = c->aj_d_out.as<char>();
+  HIP_TRY(c, hipMemsetAsync(db, 0, o.end, c->stream));
+  HIP_TRY(c, hipMemsetAsync(db + o.slot, 0xff, o.rank - o.slot, c->stream));
+  HIP_TRY(c, hipMemsetAsync(dout, 0, o.o_end, c->stream));
+  HIP_TRY(c, hipMemsetAsync(c->a_d_alive.p, 0, c->a_d_alive.cap, c->stream));
+  if (n > 0) {
+    HIP_TRY(c, hipMemcpyAsync(db + o.jobs, jobs.data(), N * sizeof(AlignJobDev), hipMemcpyHostToDevice, c->stream));
+    for (char* dst : { db + o.T0, dout + o.o_tref, dout + o.o_poses })
+      HIP_TRY(c, hipMemcpyAsync(dst, ident.data(), N * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));      // (the host vectors above are read by the copies)
+  AlignBuildBatchDev& b = c->aj_b;
+  b = AlignBuildBatchDev{};
+  b.report = reinterpret_cast<AlignBuildReportDev*>(dout + o.o_report);
+  b.a_jobs = reinterpret_cast<AlignJobDev*>(db + o.jobs); b.T0 = reinterpret_cast<double*>(db + o.T0); b.T_ref = reinterpret_cast<double*>(dout + o.o_tref);
+  b.pt_px = reinterpret_cast<double*>(db + o.pt_px); b.pt_xyz = reinterpret_cast<double*>(db + o.pt_xyz);
+  b.seg_spx = reinterpret_cast<double*>(db + o.spx); b.seg_epx = reinterpret_cast<double*>(db + o.epx); b.seg_len = reinterpret_cast<double*>(db + o.len);
+  b.seg_p = reinterpret_cast<double*>(db + o.sp); b.seg_q = reinterpret_cast<double*>(db + o.sq); b.seg_alive_in = reinterpret_cast<uint8_t*>(db + o.alive);
+  b.seg_slot = reinterpret_cast<int*>(db + o.slot); b.seg_rank = reinterpret_cast<int*>(db + o.rank);
+  b.work_key = reinterpret_cast<int*>(dout + o.o_key);
+  b.cap_pts = g->cap_pts; b.cap_seg = g->cap_seg; b.slot_cap = g->slot_cap; b.patch_cap = patch_cap;
+  b.max_level = g->max_level; b.min_level = g->min_level; b.n_iter = g->n_iter; b.eps = g->eps;
+  c->aj_pose = AlignPoseBatchDev{ nullptr, b.T_ref, reinterpret_cast<double*>(dout + o.o_poses), n };
+  c->aj_cfg = *g; c->aj_n = n; c->aj_slots.assign(2 * N, 0);
+  c->aj_reserved = true;
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_align_build(plsvo_ctx* c, int n, const plsvo_cand_align_job* in) {
+  CTX_CHECK(c);
+  if (!c->cd_staged || !c->aj_reserved || c->aj_n != c->cd_n) return fail(c, PLSVO_E_STATE, "candidates_align_build: no alignment batch reserved for the staged streams (plsvo_candidates_align_reserve)");
+  if (!c->cd_ran || !c->cs_selected) return fail(c, PLSVO_E_STATE, "candidates_align_build: no selection on the last run");
+  if (const int rc = cand_seeds_pending(c, "candidates_align_build")) return rc;
+  if (c->cc_closed) return fail(c, PLSVO_E_STATE, "candidates_align_build: the tables were compacted behind this run (the selection's rows have been renumbered); build ahead of the compaction");
+  if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_align_build: n does not match the staged batch");
+  const plsvo_cand_align_cfg& g = c->aj_cfg;
+  if (!c->pyr.base || g.max_level >= c->pyr.n_levels || c->cd_b.cam_width != c->pyr.w[0] || c->cd_b.cam_height != c->pyr.h[0])
+    return fail(c, PLSVO_E_STATE, "candidates_align_build: the pyramids or the camera changed since the reserve");
+  bool host_masks = false;
+  for (int s = 0; s < n; ++s) {
+    const plsvo_cand_align_job& I = in[s];
+    if (!I.active) continue;
+    if (I.ref_slot < 0 || I.ref_slot >= c->pyr.n_slots || I.cur_slot < 0 || I.cur_slot >= c->pyr.n_slots) return fail(c, PLSVO_E_INVALID, "candidates_align_build: pyramid slot out of range");
+    if (I.pose_source < PLSVO_INSERT_POSE_HOST || I.pose_source > PLSVO_INSERT_POSE_RESIDENT || (I.pose_source == PLSVO_INSERT_POSE_DEV && !I.d_T_f_w))
+      return fail(c, PLSVO_E_INVALID, "candidates_align_build: bad pose source");
+    if (I.pt_keep || I.seg_keep) host_masks = true;
+  }
+  for (int s = 0; s < n; ++s)
+    if (in[s].active && (!in[s].pt_keep || !in[s].seg_keep || in[s].pose_source == PLSVO_INSERT_POSE_RESIDENT) && !c->cs_posed)
+      return fail(c, PLSVO_E_STATE, "candidates_align_build: no resident pose optimisation for the masks or the pose");
+  if (n == 0) return PLSVO_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t N = (size_t)n;
+  // -- the records and the caller's masks, laid out like the resident masks (feature rows from opt_off / 2 * oseg_off)
+  Readback rb_sc;
+  if (host_masks) rb_sc.add(c->cs_b.scalars, N * 3 * sizeof(int));
+  if (const int rc = host_masks ? rb_sc.wait(c) : PLSVO_OK) return rc;
+  const int* const sc = host_masks ? rb_sc.at<int>(0) : nullptr;
+  Blob blob;
+  const size_t b_jobs = blob.reserve<AlignBuildJobDev>(N);
+  const size_t b_pk = host_masks ? blob.reserve<uint8_t>(c->cd_t_opt) : 0, b_sk = host_masks ? blob.reserve<uint8_t>(2 * c->cd_t_oseg) : 0;
+  HIP_TRY(c, c->aj_d_in.ensure(std::max(blob.host.size(), (size_t)256)));
+  const uint8_t* din = c->aj_d_in.as<uint8_t>();
+  AlignBuildJobDev* jobs = blob.at<AlignBuildJobDev>(b_jobs);
+  for (int s = 0; s < n; ++s) {
+    const plsvo_cand_align_job& I = in[s]; const CandMapDev& M = c->cd_maps[(size_t)s];
+    AlignBuildJobDev& J = jobs[s];
+    memset(&J, 0, sizeof(J));
+    J.active = I.active ? 1 : 0;
+    if (!J.active) continue;
+    J.ref_slot = I.ref_slot; J.cur_slot = I.cur_slot;
+    memcpy(J.T, I.T_f_w, sizeof(J.T));
+    J.d_T = I.pose_source == PLSVO_INSERT_POSE_DEV ? I.d_T_f_w : I.pose_source == PLSVO_INSERT_POSE_RESIDENT ? c->cs_w.poses.as<double>() + 7 * (size_t)s : nullptr;
+    J.pt_keep = c->cs_w.ptkeep.as<uint8_t>(); J.seg_keep = c->cs_w.segkeep.as<uint8_t>();
+    if (I.pt_keep) { J.pt_keep = din + b_pk; if (sc[3 * (size_t)s] > 0) memcpy(blob.at<uint8_t>(b_pk) + M.opt_off, I.pt_keep, (size_t)sc[3 * (size_t)s]); }
+    if (I.seg_keep) { J.seg_keep = din + b_sk; if (sc[3 * (size_t)s + 1] > 0) memcpy(blob.at<uint8_t>(b_sk) + 2 * M.oseg_off, I.seg_keep, (size_t)sc[3 * (size_t)s + 1]); }
+  }
+  int rc;
+  if ((rc = align_job_work(c, N, g))) return rc;
+  HIP_TRY(c, c->aj_d_order.ensure(N * sizeof(int)));
+  if ((rc = upload_blob(c, c->aj_d_in, blob))) return rc;
+  // small batches may run two workgroups per frame (plsvo_align_run decides from the launch shape): their segments start at a multiple of 64 slots
+  const int cus = c->cu_count > 0 ? c->cu_count : 256;
+  const int seg_align = (2 * n <= cus) ? 64 : 32;
+  AlignBuildBatchDev b = c->aj_b;
+  b.s = c->cs_b;
+  b.jobs = Blob::dev<AlignBuildJobDev>(c->aj_d_in, b_jobs);
+  b.seg_align = seg_align; b.ldlt_flavour = c->ldlt_flavour;
+  c->a_staged = false; c->aj_built = false;
+  c->ch_staged = false;                             // a resident frame step is built on the staged alignment batch: building another one invalidates it
+  HIP_TRY_TIMED(c, PLSVO_K_ALIGN_INIT, launch_map_align_job(b, c->stream));
+  // launch order: most patches (summed over the levels) first, by the counting sort that re-orders a re-run batch (bins of four patches),
+  // on the build's own key -- a stream that sat the build out keeps its last count -- into a buffer no later launch's re-ordering writes
+  const int* order = nullptr;
+  if (!c->env_align_no_lpt) {
+    HIP_TRY(c, launch_align_reorder(b.work_key, n, c->aj_d_order.as<int>(), 2, c->stream));
+    order = c->aj_d_order.as<int>();
+  }
+  // -- the built batch is the context's staged alignment batch; the host's view of it holds the capacities
+  for (int s = 0; s < n; ++s) if (in[s].active) { c->aj_slots[2 * (size_t)s] = in[s].ref_slot; c->aj_slots[2 * (size_t)s + 1] = in[s].cur_slot; }
+  const int patch_cap = b.patch_cap;
+  c->a_jobs.assign(N, AlignJobDev{});
+  for (int j = 0; j < n; ++j) {
+    AlignJobDev& J = c->a_jobs[(size_t)j];
+    J.ref_slot = c->aj_slots[2 * (size_t)j]; J.cur_slot = c->aj_slots[2 * (size_t)j + 1];
+    J.max_level = g.max_level; J.min_level = g.min_level; J.n_iter = g.n_iter; J.eps = g.eps;
+    J.pt_off = j * g.cap_pts; J.n_pts = g.cap_pts; J.seg_off = j * g.cap_seg; J.n_seg = g.cap_seg; J.patch_off = j * patch_cap; J.patch_cap = patch_cap;
+  }
+  AlignBatchDev& a = c->a_b;
+  a.jobs = b.a_jobs; a.state = c->a_d_state.as<AlignStateDev>(); a.T0 = b.T0;
+  a.pt_px = b.pt_px; a.pt_xyz = b.pt_xyz; a.seg_spx = b.seg_spx; a.seg_epx = b.seg_epx; a.seg_len = b.seg_len; a.seg_p = b.seg_p; a.seg_q = b.seg_q;
+  a.seg_alive_in = b.seg_alive_in; a.seg_alive = c->a_d_alive.as<uint8_t>();
+  a.patch_xyz = c->a_d_pxyz.as<double>(); a.patch_uvref = c->a_d_puv.as<float>(); a.cache_ref = c->a_d_cref.as<float>();
+  a.chi_terms = c->a_d_chi.as<float>(); a.chi_plane = (unsigned long long)(N * (size_t)g.cap_pts + 32) * 16;
+  a.seg_slot = b.seg_slot; a.slot_level0 = g.min_level; a.slot_stride = n * g.cap_seg;
+  a.poses = c->a_d_poses.as<double>();
+  a.pyr = c->pyr;
+  a.log = c->a_trace_cap > 0 ? c->a_d_log.as<plsvo_align_iterlog>() : nullptr;
+  a.log_cap = c->a_trace_cap;
+  a.n_jobs = n;
+  a.pair = 0; a.xseq0 = 0; a.xbuf = nullptr; a.work_key = nullptr; a.tail_n = 0; a.static_solve = 1; a.tail_flag = nullptr; a.seg_alive_tail = nullptr;   // (plsvo_align_run decides)
+  a.order = order;
+  c->a_stage_order = order;
+  c->a_patch_total = std::max(N * (size_t)patch_cap, (size_t)4);
+  c->a_n = n; c->a_total_seg = n * g.cap_seg; c->a_gmax = g.max_level; c->a_gmin = g.min_level;
+  for (int l = 0; l < PLSVO_MAX_LEVELS; ++l) c->a_cap[l] = (l >= g.min_level && l <= g.max_level) ? patch_cap : 0;
+  c->a_scap = std::max(4, g.cap_seg);
+  c->a_seg_align = seg_align;
+  c->a_staged = true; c->a_run_seq = 0;
+  c->aj_built = true; c->aj_composed = false;
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_align_compose(plsvo_ctx* c) {
+  CTX_CHECK(c);
+  if (!c->aj_reserved || !c->aj_built || !c->a_staged || c->a_run_seq == 0) return fail(c, PLSVO_E_STATE, "candidates_align_compose: the built alignment batch has not run");
+  HIP_TRY(c, hipSetDevice(c->device));
+  AlignPoseBatchDev b = c->aj_pose;
+  b.align_poses = c->a_d_poses.as<double>(); b.n_jobs = c->a_n;
+  HIP_TRY_TIMED(c, PLSVO_K_ALIGN_INIT, launch_map_align_pose(b, c->stream));
+  c->aj_composed = true;
+  return PLSVO_OK;
+}
+
+extern "C" const double* plsvo_candidates_align_poses_dev(plsvo_ctx* c) { return (c && c->aj_reserved && c->aj_composed) ? c->aj_pose.out : nullptr; }
+
+extern "C" int plsvo_candidates_align_fetch(plsvo_ctx* c, int n, plsvo_cand_align_report* out) {
+  CTX_CHECK(c);
+  if (!c->aj_reserved) return fail(c, PLSVO_E_STATE, "candidates_align_fetch: no alignment batch reserved");
+  if (n != c->aj_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_align_fetch: n does not match the reserved batch");
+  if (n == 0) return PLSVO_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  static_assert(sizeof(AlignBuildReportDev) == sizeof(plsvo_cand_align_report) && sizeof(plsvo_cand_align_report) == 32, "the device's report is the public one");
+  Readback rb;
+  rb.add(c->aj_b.report, (size_t)n * sizeof(AlignBuildReportDev));
+  if (const int rc = rb.wait(c)) return rc;
+  memcpy(out, rb.at<AlignBuildReportDev>(0), (size_t)n * sizeof(AlignBuildReportDev));
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_align_fetch_job(plsvo_ctx* c, int stream, plsvo_cand_align_job_out* O) {
+  CTX_CHECK(c);
+  if (!c->aj_reserved) return fail(c, PLSVO_E_STATE, "candidates_align_fetch_job: no alignment batch reserved");
+  if (stream < 0 || stream >= c->aj_n || !O) return fail(c, PLSVO_E_INVALID, "candidates_align_fetch_job: bad arguments");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const AlignBuildBatchDev& b = c->aj_b; const plsvo_cand_align_cfg& g = c->aj_cfg;
+  const size_t s = (size_t)stream, np = (size_t)g.cap_pts, ns = (size_t)g.cap_seg, nl = (size_t)(g.max_level - g.min_level + 1), stride = (size_t)c->aj_n * ns;
+  Readback rb;
+  const int r_job = rb.add(b.a_jobs + s, sizeof(AlignJobDev)), r_T0 = rb.add(b.T0 + 7 * s, 7 * sizeof(double)), r_Tr = rb.add(b.T_ref + 7 * s, 7 * sizeof(double));
+  const int r_Tc = rb.add(c->aj_pose.out + 7 * s, 7 * sizeof(double));
+  const int r_key = rb.add(b.work_key + s, sizeof(int));
+  const int r_ppx = rb.add(b.pt_px + 2 * s * np, 2 * np * sizeof(double)), r_pxyz = rb.add(b.pt_xyz + 3 * s * np, 3 * np * sizeof(double));
+  const int r_spx = rb.add(b.seg_spx + 2 * s * ns, 2 * ns * sizeof(double)), r_epx = rb.add(b.seg_epx + 2 * s * ns, 2 * ns * sizeof(double));
+  const int r_len = rb.add(b.seg_len + s * ns, ns * sizeof(double)), r_sp = rb.add(b.seg_p + 3 * s * ns, 3 * ns * sizeof(double)), r_sq = rb.add(b.seg_q + 3 * s * ns, 3 * ns * sizeof(double));
+  const int r_al = rb.add(b.seg_alive_in + s * ns, ns);
+  std::vector<int> r_code(nl);
+  for (size_t l = 0; l < nl; ++l) r_code[l] = rb.add(b.seg_slot + l * stride + s * ns, ns * sizeof(int));
+  if (const int rc = rb.wait(c)) return rc;
+  const AlignJobDev& J = *rb.at<AlignJobDev>(r_job);
+  if (J.n_pts < 0 || J.n_pts > g.cap_pts || J.n_seg < 0 || J.n_seg > g.cap_seg) return fail(c, PLSVO_E_HIP, "candidates_align_fetch_job: corrupt job");
+  O->n_pts = J.n_pts; O->n_seg = J.n_seg; O->skip = J.skip; O->long_mask = J.long_mask;
+  for (int l = 0; l < PLSVO_MAX_LEVELS; ++l) O->n_slots[l] = J.n_slots[l];
+  O->ref_slot = J.ref_slot; O->cur_slot = J.cur_slot; O->n_patches = *rb.at<int>(r_key); O->reserved0 = 0;
+  memcpy(O->T0, rb.at<double>(r_T0), sizeof(O->T0)); memcpy(O->T_ref, rb.at<double>(r_Tr), sizeof(O->T_ref)); memcpy(O->T_f_w, rb.at<double>(r_Tc), sizeof(O->T_f_w));
+  auto cp = [&](void* dst, int r, size_t count, size_t elem) { if (dst && count) memcpy(dst, rb.at<char>(r), count * elem); };
+  const size_t kp = (size_t)J.n_pts, ks = (size_t)J.n_seg;
+  cp(O->pt_px, r_ppx, 2 * kp, sizeof(double)); cp(O->pt_xyz_ref, r_pxyz, 3 * kp, sizeof(double));
+  cp(O->seg_spx, r_spx, 2 * ks, sizeof(double)); cp(O->seg_epx, r_epx, 2 * ks, sizeof(double)); cp(O->seg_len, r_len, ks, sizeof(double));
+  cp(O->seg_p_ref, r_sp, 3 * ks, sizeof(double)); cp(O->seg_q_ref, r_sq, 3 * ks, sizeof(double)); cp(O->seg_alive_in, r_al, ks, 1);
+  if (O->seg_code) for (size_t l = 0; l < nl; ++l) cp(O->seg_code + l * ns, r_code[l], ks, sizeof(int));
+  return PLSVO_OK;
+}
+
 // ---- depth-filter seed lists resident beside the map tables (seedlist_device.hpp) -------------------------------------------
 namespace {
 // the sections of sd_d_work: reports, then the shadow rows (SeedsBatchDev's outputs, one per capacity row)

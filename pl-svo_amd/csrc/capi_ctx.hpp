@@ -39,6 +39,8 @@ hipError_t launch_map_compact(const CompactBatchDev& b, hipStream_t stream);    
 hipError_t launch_map_keypts(const KeyStageBatchDev& b, hipStream_t stream);          // keystage_device.hpp, in seeds_kernels.hip
 hipError_t launch_map_close(const KeyStageBatchDev& b, hipStream_t stream);
 hipError_t launch_map_keyframe_decide(const KeyDecideBatchDev& b, hipStream_t stream);
+hipError_t launch_map_align_job(const AlignBuildBatchDev& b, hipStream_t stream);      // alignjob_device.hpp, in seeds_kernels.hip
+hipError_t launch_map_align_pose(const AlignPoseBatchDev& b, hipStream_t stream);
 hipError_t launch_update_seeds_resident(const SeedListBatchDev& b, hipStream_t stream);   // seedlist_device.hpp, in seeds_kernels.hip
 hipError_t launch_seeds_commit(const SeedListBatchDev& b, hipStream_t stream);
 hipError_t launch_seeds_keyframe(const SeedListBatchDev& b, hipStream_t stream);
@@ -275,6 +277,17 @@ struct plsvo_ctx {
   std::vector<uint8_t> ck_dec_active;        // per stream: a decision of this run was active for it
   DevBuf ck_d_dec_in, ck_d_dec;
   KeyDecideBatchDev ck_dec_b{};
+  // the next frame's alignment job built from the selection (plsvo_candidates_align_*): the reserve's configuration and stream count, the
+  // resident alignment batch laid out by capacity (aj_d_batch: what a_b points at while aj_built), a call's records and host masks
+  // (aj_d_in), the reports / the reference poses / the composed poses (aj_d_out), per stream the pyramid slots of its last build (the
+  // host's a_jobs mirror needs them), whether the staged alignment batch is the built one, whether its poses were composed
+  bool aj_reserved = false, aj_built = false, aj_composed = false;
+  int aj_n = 0;
+  plsvo_cand_align_cfg aj_cfg{};
+  std::vector<int> aj_slots;
+  DevBuf aj_d_batch, aj_d_in, aj_d_out, aj_d_order;   // (aj_d_order: the build's own launch order, which no later launch's re-ordering writes)
+  AlignBuildBatchDev aj_b{};              // the batch's sections (the selection, the records and the key are bound per call)
+  AlignPoseBatchDev aj_pose{};
   // resident seed lists (plsvo_seeds_*): the room plsvo_seeds_reserve asks for (the next stage's), per stream the host mirror of its
   // record (sd_host: list lengths, upper bounds between a keyframe event and the next update fetch) and the rows it may fill (sd_lim);
   // the tables (sd_d_tab: records, workgroup map, rows), shadow rows and reports (sd_d_work), a call's upload (sd_d_in).  A candidate
@@ -373,6 +386,8 @@ inline const int* LaunchOrder::sort(plsvo_ctx* c, int n, int shift) {
 }
 
 PLSVO_LOCAL int pose_opt_threads(const plsvo_ctx* c, int n, long feats);
+// launch configuration of the fused alignment kernel for n_jobs frames of at most `cap` slots, `scap` segments, `max_pts` points (defined in plsvo_capi.hip)
+PLSVO_LOCAL void pick_align_config(const plsvo_ctx* c, int n_jobs, int cap, int scap, int max_pts, int* threads, size_t* lds, int* chi_lds_pts);
 // corner detection, shared by plsvo_hip_detect_fast(_dev) and plsvo_seeds_keyframe_detect (defined in plsvo_capi.hip).  detect_check_params:
 // everything the detect entry points refuse in their params, for n launch positions; the pyramids are configured and p is not NULL.
 // detect_enqueue_keys: the detection launch alone -- position i reads slot first_slot + i, or d_slot_table[i] when a table is given --

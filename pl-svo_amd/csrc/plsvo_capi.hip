@@ -113,6 +113,7 @@ extern "C" void plsvo_hip_destroy(plsvo_ctx* c) {
   for (auto& ep : c->ev_pool) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
   c->a_d_tailflag.release(); c->a_d_alive_tail.release(); c->a_d_xbuf.release(); c->a_order.release(); c->p_order.release();
   c->p_d_carry.release(); c->p_d_refill_next.release();
+  c->aj_d_batch.release(); c->aj_d_in.release(); c->aj_d_out.release(); c->aj_d_order.release();
   for (DevBuf* b : { &c->cd_d_blob, &c->cd_d_work, &c->cd_d_run, &c->cd_d_kfcount, &c->ck_d_keypts, &c->ck_d_in, &c->ck_d_upkeep, &c->ck_d_work, &c->ck_d_dec_in, &c->ck_d_dec,&c->ci_d_work, &c->ci_d_in, &c->ci_d_plan, &c->ci_d_pos, &c->co_d_key, &c->co_d_in, &c->co_d_rep, &c->cn_d_in, &c->cc_d_in, &c->cc_d_work, &c->sd_d_tab, &c->sd_d_work, &c->sd_d_in, &c->cs_d_q,
                      &c->cs_d_work, &c->cs_d_order, &c->pyr_slab, &c->pyr_tiled, &c->pyr_upload, &c->a_d_blob, &c->a_d_state, &c->a_d_alive, &c->a_d_pxyz, &c->a_d_puv,
                      &c->a_d_cref, &c->a_d_chi, &c->a_d_log, &c->a_d_poses, &c->p_d_blob, &c->p_d_log, &c->s_d_in, &c->s_d_out, &c->ch_d_blob, &c->ch_d_work,
@@ -752,6 +753,7 @@ extern "C" int plsvo_align_stage(plsvo_ctx* c, int n, const plsvo_align_in* in) 
   if (!c->pyr.base) return fail(c, PLSVO_E_STATE, "align_stage: pyramids not configured");
   HIP_TRY(c, hipSetDevice(c->device));
   c->a_staged = false;
+  c->aj_built = false;    // (a batch built on the device, plsvo_candidates_align_build, is replaced like any other)
   c->ch_staged = false;   // a resident frame step is built on the staged alignment batch: staging another one invalidates it
   std::vector<AlignJobDev> jobs((size_t)n);
   std::vector<double> T0((size_t)n * 7), ptpx, ptxyz, spx, epx, len, sp, sq;
@@ -894,7 +896,7 @@ int pose_opt_threads(const plsvo_ctx* c, int n, long feats) {
   return c->env_poseopt_threads ? c->env_poseopt_threads : threads;
 }
 
-static void pick_align_config(const plsvo_ctx* c, int n_jobs, int cap, int scap, int max_pts, int* threads, size_t* lds, int* chi_lds_pts) {
+void pick_align_config(const plsvo_ctx* c, int n_jobs, int cap, int scap, int max_pts, int* threads, size_t* lds, int* chi_lds_pts) {
   const int cus = c->cu_count > 0 ? c->cu_count : 256;
   int t = 64;                            // >= 64 frames per CU: one wave per frame, no workgroup barrier at all
   if (n_jobs <= cus) t = 512;
@@ -932,6 +934,26 @@ struct RoctxRange {
 };
 }  // namespace
 
+// the launch configuration of the staged batch: the slot capacities the host mirrors hold, and pick_align_config on them
+static void staged_align_config(const plsvo_ctx* c, int* cap, int* scap, int* threads, size_t* lds, int* chi_lds_pts) {
+  *cap = 4;
+  if (c->a_gmax >= c->a_gmin && c->a_gmax >= 0) for (int l = c->a_gmin; l <= c->a_gmax; ++l) *cap = std::max(*cap, c->a_cap[l]);
+  *scap = (c->a_scap + 3) & ~3;
+  int max_pts = 0;
+  for (const AlignJobDev& J : c->a_jobs) max_pts = std::max(max_pts, J.n_pts);
+  pick_align_config(c, c->a_n, *cap, *scap, max_pts, threads, lds, chi_lds_pts);
+}
+// diagnostic (measurements): what plsvo_align_run would launch the staged batch with
+extern "C" int plsvo_align_launch_shape(plsvo_ctx* c, int32_t* threads, uint64_t* lds_bytes) {
+  CTX_CHECK(c);
+  if (!c->a_staged) return fail(c, PLSVO_E_STATE, "align_launch_shape: no staged batch");
+  if (!threads || !lds_bytes) return fail(c, PLSVO_E_INVALID, "align_launch_shape: NULL output");
+  int cap, scap, t, chi; size_t lds;
+  staged_align_config(c, &cap, &scap, &t, &lds, &chi);
+  *threads = t; *lds_bytes = (uint64_t)lds;
+  return PLSVO_OK;
+}
+
 constexpr int kAlignTailRounds = 2;   // tail set of the split, in rounds of resident workgroups (measured: DESIGN.md 3.1)
 extern "C" int plsvo_align_run(plsvo_ctx* c) {
   CTX_CHECK(c);
@@ -940,14 +962,9 @@ extern "C" int plsvo_align_run(plsvo_ctx* c) {
   HIP_TRY(c, hipSetDevice(c->device));
   // one launch: the workgroup of a job resets its solver state, runs its levels and writes its pose
   // (jobs without features, src/sparse_img_align.cpp:58-62, only do the first and the last)
-  int cap = 4;
   const bool have_levels = c->a_gmax >= c->a_gmin && c->a_gmax >= 0;
-  if (have_levels) for (int l = c->a_gmin; l <= c->a_gmax; ++l) cap = std::max(cap, c->a_cap[l]);
-  int threads; size_t lds;
-  const int scap = (c->a_scap + 3) & ~3;
-  int max_pts = 0, chi_lds_pts = 0;
-  for (const AlignJobDev& J : c->a_jobs) max_pts = std::max(max_pts, J.n_pts);
-  pick_align_config(c, c->a_n, cap, scap, max_pts, &threads, &lds, &chi_lds_pts);
+  int cap, scap, threads, chi_lds_pts; size_t lds;
+  staged_align_config(c, &cap, &scap, &threads, &lds, &chi_lds_pts);
   c->a_b.chi_lds_pts = chi_lds_pts;
   if (lds > c->lds_per_block) return fail(c, PLSVO_E_CAPACITY, "align_run: slot tables do not fit in LDS (too many features in one job)");
   if (threads <= 64 && c->tiled_stale_count > 0) {   // the one-wave-per-frame shape reads the tiled mirror: bring the uploaded slots' tiles up to date first

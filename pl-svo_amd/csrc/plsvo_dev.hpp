@@ -492,6 +492,38 @@ struct KeyDecideBatchDev {
   double* delta_t; double* delta_r; // per overlap entry, laid out like the run's overlap rows
 };
 
+// the next frame's alignment job from the resident selection (alignjob_device.hpp, include/plsvo_hip.h plsvo_candidates_align_build):
+// one wave per stream writes the stream's rows of an alignment batch laid out by CAPACITY -- point rows from job * cap_pts, segment rows
+// and slot codes from job * cap_seg, patch slots from job * patch_cap -- so no prefix sum is needed and the rows never move
+constexpr int kAlignJobOk = 0, kAlignJobNoRoom = 1;   // AlignBuildReportDev::status (PLSVO_ALIGN_JOB_*)
+constexpr int kAlignJobBinGroups = 2, kAlignJobBins = 64 * kAlignJobBinGroups;   // wave-rounds the short segments of one level may open, in groups of 64
+constexpr int kAlignJobMaxSlotCap = 64 * (kAlignJobBins - 2);                    // a level of at most this many slots never runs out of them (8064: more than a workgroup's LDS tables hold)
+struct AlignBuildJobDev {           // one stream's record
+  double T[7];                      // the reference frame's T_f_w
+  const double* d_T;                // device pointer read instead of T, or null
+  const uint8_t* pt_keep; const uint8_t* seg_keep;   // keep masks in selection order (device), whole-batch arrays: rows from opt_off / 2 * oseg_off
+  int active, ref_slot, cur_slot, reserved0;
+};
+struct AlignBuildReportDev {        // plsvo_cand_align_report, field for field: 32 bytes
+  int n_pts, n_seg, n_seg_alive, n_slots, long_mask, status, reserved0, reserved1;
+};
+struct AlignBuildBatchDev {
+  SelectBatchDev s;                 // the selection's features (f_pt_lm / f_pt_px / f_seg_lm / f_seg_px, scalars) and, in s.c, the tables
+  const AlignBuildJobDev* jobs; AlignBuildReportDev* report;
+  // the resident alignment batch (what AlignBatchDev reads)
+  AlignJobDev* a_jobs; double* T0; double* T_ref;
+  double* pt_px; double* pt_xyz; double* seg_spx; double* seg_epx; double* seg_len; double* seg_p; double* seg_q; uint8_t* seg_alive_in;
+  int* seg_slot;                    // [(level - min_level) * n_jobs * cap_seg + job * cap_seg + segment]
+  int* seg_rank;                    // scratch, cap_seg per stream: the short segments of a level in packing order, N << 20 | segment
+  int* work_key;                    // per stream: the patches summed over the levels, the key of the build's launch order (kept for a stream that sits a build out)
+  int cap_pts, cap_seg, slot_cap, patch_cap;   // per stream; patch_cap = slot_cap rounded up to 4
+  int max_level, min_level, n_iter, seg_align, ldlt_flavour, reserved0;
+  double eps;
+};
+struct AlignPoseBatchDev {          // map_align_pose_kernel: T_f_w(new) = T_cur_from_ref * T_ref
+  const double* align_poses; const double* T_ref; double* out; int n_jobs;
+};
+
 // corner detection (detect_device.hpp, include/plsvo_hip.h plsvo_hip_detect_fast): tile geometry and the launch record
 constexpr int kDetTileW = 64, kDetTileH = 32;          // pixels of a tile that one workgroup decides
 constexpr int kDetImgX0 = 8, kDetImgY0 = 5;            // LDS image origin = tile origin - (8, 5): a halo of 5 (Shi-Tomasi: x - 5 .. x + 4), 8 keeps rows dword-aligned

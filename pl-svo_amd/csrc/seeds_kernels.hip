@@ -32,6 +32,7 @@
 #include "newcand_device.hpp"    // and the new candidate landmarks appended to them
 #include "seedlist_device.hpp"   // and the seed lists kept resident beside them
 #include "structsel_device.hpp"  // and the structure optimisation of their least recently refined landmarks
+#include "alignjob_device.hpp"   // and the next frame's alignment job built from the selection
 
 namespace plsvo_hip {
 
@@ -549,6 +550,17 @@ hipError_t launch_map_close(const KeyStageBatchDev& b, hipStream_t stream) {
 hipError_t launch_map_keyframe_decide(const KeyDecideBatchDev& b, hipStream_t stream) {
   if (b.s.c.n_jobs <= 0) return hipSuccess;
   hipLaunchKernelGGL(map_keyframe_decide_kernel, dim3((b.s.c.n_jobs + kKsWaves - 1) / kKsWaves), dim3(64 * kKsWaves), 0, stream, b);
+  return hipGetLastError();
+}
+// the next frame's alignment job from the resident selection (alignjob_device.hpp): the same shape; the composed poses: a lane per stream
+hipError_t launch_map_align_job(const AlignBuildBatchDev& b, hipStream_t stream) {
+  if (b.s.c.n_jobs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_align_job_kernel, dim3((b.s.c.n_jobs + kAjWaves - 1) / kAjWaves), dim3(64 * kAjWaves), 0, stream, b);
+  return hipGetLastError();
+}
+hipError_t launch_map_align_pose(const AlignPoseBatchDev& b, hipStream_t stream) {
+  if (b.n_jobs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_align_pose_kernel, dim3((b.n_jobs + 63) / 64), dim3(64), 0, stream, b);
   return hipGetLastError();
 }
 

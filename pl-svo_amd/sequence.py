@@ -52,10 +52,18 @@ structopt_resident=True (cell_select, a backend with map_optimize_structure) the
 (plsvo_candidates_optimize_structure): one call on every tracked frame, points and segments, ahead of an insertion; the
 harness takes the moved positions and the keys from the call's report.
 
+With align="host" | "device" (map_candidates and cell_select) step 1 of every frame but the first is fed by the frame before it: the features of the
+alignment job are the previous frame's SELECTION with the pose optimiser's keep masks, the landmarks' positions and types as the tables
+hold them when that frame is done -- behind the structure optimisation and an insertion, ahead of a compaction --, the reference pose the
+optimised one; the first frame, and a frame behind one whose tables wait for a restage, are staged by the host as without it.  "device" builds that job on the device (plsvo_candidates_align_build .. _compose, DESIGN.md 3.20: no selection fetch, no
+pose fetch, no host arithmetic ahead of the alignment) and hands the composed pose on by device pointer; "host" restates the same job here
+in scalar float64 and stages it through plsvo_align_stage, so the two differ in transport alone and agree in every record.
+
 `backend` is duck-typed: load_frames(list of level-0 images; HipBackend also takes raw frames with rectify=), sparse_align(job), reproject(job), match_direct(job),
 pose_optimize(job), for mapping structure_optimize(job), update_seeds(job), and for kf_select close_keyframes(job), keyframe_decide(job).  The product backend is HipBackend (C ABI on the GPU, no fallback); tests pass an oracle-backed one
 to check the whole chain end to end."""
 import copy
+import math
 
 import numpy as np
 
@@ -121,25 +129,27 @@ class HipBackend:
         self.ctx.candidates_match()
         return r, self.ctx.candidates_match_fetch([(r["n_filed_pt"], r["n_filed_seg"])])[0]
 
-    def map_select(self, map_job, frame_job, cam, n_pyr_levels, select, carry=None, cell_size=30, seg_cell_size=30, close=None, key_pts=False):
+    def map_select(self, map_job, frame_job, cam, n_pyr_levels, select, carry=None, cell_size=30, seg_cell_size=30, close=None, key_pts=False, poses_dev=None):
         """the map part of a frame as one enqueue sequence on the resident tables: candidates, match, cell selection, pose optimisation
         (plsvo_candidates_run .. plsvo_candidates_pose_optimize).  map_job as in map_candidates; carry: the counters to put back after a
         restage (a candidates_fetch_quality() record), select: the keyword arguments of capi.Context.candidates_select.
         close = max_n_kfs: the overlap list is decided on the device from the resident key-point table (plsvo_candidates_run_close; what
         close_keyframes() reports is left in self.last_close), which a (re)stage gives its rows first: key_pts [n_kf, 5], or None for
         setKeyPoints from five NULLs on the device (False: the table is not touched).
+        poses_dev: a device pointer to the frame's pose, read instead of frame_job's (plsvo_candidates_align_poses_dev).
         -> (the stage's result, the matcher's, the selection, the pose optimiser's result, the quality state after the frame)"""
         if map_job is not None:
             self.ctx.candidates_stage([map_job], cam, cell_size, seg_cell_size, 8, n_pyr_levels, 10)
+            self._align_reserved = False
             if carry is not None:
                 self.ctx.candidates_set_quality([dict(pt_n_failed=carry["pt_n_failed"], pt_n_succeeded=carry["pt_n_succeeded"],
                                                       seg_n_failed=carry["seg_n_failed"], seg_n_succeeded=carry["seg_n_succeeded"])])
         if map_job is not None and key_pts is not False:
             self.ctx.candidates_set_keypts(None if key_pts is None else [key_pts])
         if close is None:
-            self.ctx.candidates_run([frame_job])
+            self.ctx.candidates_run([frame_job], poses_dev=poses_dev)
         else:
-            self.ctx.candidates_run_close([frame_job], close)
+            self.ctx.candidates_run_close([frame_job], close, poses_dev=poses_dev)
             self.last_close = self.ctx.candidates_close_fetch()[0]
         self.ctx.candidates_match()
         self.ctx.candidates_select(**select)
@@ -149,6 +159,25 @@ class HipBackend:
         sel = self.ctx.candidates_select_fetch()[0]
         pr = self.ctx.candidates_pose_fetch([(sel["n_matches"], sel["n_ls_matches"])])[0]
         return r, mr, sel, pr, self.ctx.candidates_fetch_quality()[0]
+
+    def align_build(self, ref_slot, cur_slot, max_level, min_level, cap_pts, cap_seg, slot_cap=2048):
+        """the next frame's alignment job from the selection of the last map_select, on the device (plsvo_candidates_align_build, DESIGN.md
+        3.20), with the keep masks and the optimised pose the resident pose optimiser left there; the capacities are reserved when the
+        tables were staged since the last build.  Enqueue only"""
+        if not getattr(self, "_align_reserved", False):
+            self.ctx.candidates_align_reserve(max_level, min_level, cap_pts, cap_seg, slot_cap)
+            self._align_reserved = True
+        self.ctx.candidates_align_build([dict(ref_slot=ref_slot, cur_slot=cur_slot)])
+
+    def align_built(self):
+        """the built job run and its pose composed (plsvo_align_run, plsvo_candidates_align_compose).
+        -> (the alignment's result, the composed T_f_w as a host copy for the records, the device pointer the next stage reads it from)"""
+        self.ctx.align_run()
+        self.ctx.candidates_align_compose()
+        ar = self.ctx.align_fetch()[0]
+        if self.ctx.candidates_align_fetch()[0]["status"] != abi.ALIGN_JOB_OK:
+            raise RuntimeError("align_built: the stream did not fit the reserved alignment batch (plsvo_candidates_align_reserve)")
+        return ar, self.ctx.candidates_align_fetch_job(0)["T_f_w"], self.ctx.candidates_align_poses_dev()
 
     def map_set_keypts(self, key_pts=None):
         """Frame::key_pts_ of the staged keyframes as a resident table (plsvo_candidates_set_keypts, DESIGN.md 3.19): [n_kf, 5] positions in
@@ -297,6 +326,67 @@ def _bearing(cam, px):
     return r / np.linalg.norm(r, axis=1, keepdims=True)
 
 
+def _q_rot(q, v):
+    """Eigen::Quaternion::_transformVector on Python floats, in the device's operation order (plsvo_math.hpp::quat_rotate)"""
+    qx, qy, qz, qw = q
+    ux, uy, uz = qy * v[2] - qz * v[1], qz * v[0] - qx * v[2], qx * v[1] - qy * v[0]
+    ux += ux; uy += uy; uz += uz
+    return [v[0] + qw * ux + (qy * uz - qz * uy), v[1] + qw * uy + (qz * ux - qx * uz), v[2] + qw * uz + (qx * uy - qy * ux)]
+
+
+def _se3_inv_s(T):
+    T = [float(v) for v in T]
+    qc = [-T[0], -T[1], -T[2], T[3]]
+    return qc + _q_rot(qc, [-T[4], -T[5], -T[6]])
+
+
+def _se3_mul_s(A, B):
+    """Sophus::SE3::operator* on Python floats (plsvo_math.hpp::se3_mul): what the device's compose kernel computes, bit for bit"""
+    A, B = [float(v) for v in A], [float(v) for v in B]
+    ax, ay, az, aw = A[:4]
+    bx, by, bz, bw = B[:4]
+    w = aw * bw - ax * bx - ay * by - az * bz
+    x = aw * bx + ax * bw + ay * bz - az * by
+    y = aw * by + ay * bw + az * bx - ax * bz
+    z = aw * bz + az * bw + ax * by - ay * bx
+    n = math.sqrt(x * x + y * y + z * z + w * w)
+    rt = _q_rot(A[:4], B[4:])
+    return [x / n, y / n, z / n, w / n, A[4] + rt[0], A[5] + rt[1], A[6] + rt[2]]
+
+
+def align_job_host(cam, max_level, min_level, sel, pt_keep, seg_keep, pt_type, seg_type, pt_pos, seg_spos, seg_epos, T_ref, ref_slot, cur_slot):
+    """The alignment job plsvo_candidates_align_build writes on the device, restated on the host in scalar float64 with the device's
+    operation order (the slot layout is plsvo_align_stage's): the selection's point features whose keep byte is set and
+    whose landmark row is not TYPE_DELETED, closed up; ALL its segment features, those without a landmark flagged and zeroed;
+    f * ||pos - ref_pos|| with the three squares added in order; T0 = T_ref * T_ref^-1.  -> abi.AlignJob"""
+    T_ref = [float(v) for v in T_ref]
+    T_inv = _se3_inv_s(T_ref)
+    ref = T_inv[4:]
+
+    def scaled(px, pos):
+        x, y = (px[0] - cam[2]) / cam[0], (px[1] - cam[3]) / cam[1]
+        n = math.sqrt((x * x + y * y) + 1.0)
+        dx, dy, dz = pos[0] - ref[0], pos[1] - ref[1], pos[2] - ref[2]
+        d = math.sqrt(dx * dx + dy * dy + dz * dz)
+        return [x / n * d, y / n * d, 1.0 / n * d]
+    px, xyz = [], []
+    for i, lm in enumerate(sel["pt_lm"]):
+        if pt_keep[i] and pt_type[int(lm)] != abi.LM_DELETED:
+            p = [float(v) for v in sel["pt_px"][i]]
+            px.append(p); xyz.append(scaled(p, [float(v) for v in pt_pos[int(lm)]]))
+    spx, epx, length, p_ref, q_ref, alive = [], [], [], [], [], []
+    for i, lm in enumerate(sel["seg_lm"]):
+        s4 = [float(v) for v in sel["seg_px"][i]]
+        a = bool(seg_keep[i]) and seg_type[int(lm)] != abi.LM_DELETED
+        dx, dy = s4[2] - s4[0], s4[3] - s4[1]
+        spx.append(s4[:2]); epx.append(s4[2:]); length.append(math.sqrt(dx * dx + dy * dy)); alive.append(int(a))
+        p_ref.append(scaled(s4[:2], [float(v) for v in seg_spos[int(lm)]]) if a else [0.0] * 3)
+        q_ref.append(scaled(s4[2:], [float(v) for v in seg_epos[int(lm)]]) if a else [0.0] * 3)
+    arr = lambda v, cols: np.array(v, float).reshape(-1, cols)
+    return abi.AlignJob(cam, max_level, min_level, 30, 1e-6, _se3_mul_s(T_ref, T_inv), arr(px, 2), arr(xyz, 3), arr(spx, 2), arr(epx, 2), np.array(length, float),
+                        arr(p_ref, 3), arr(q_ref, 3), np.array(alive, np.uint8), ref_slot=ref_slot, cur_slot=cur_slot)
+
+
 def seeds_from_corners(corners, cam, depth_mean, depth_min):
     """Point seeds for detected corners (abi.CORNER_DTYPE records), as DepthFilter::initializeSeeds creates them
     (src/depth_filter.cpp:161-172): a feature `new PointFeat(frame, px, level)` -- f = cam2world(px), type CORNER, grad (1, 0) -- in a
@@ -397,7 +487,7 @@ def _key_point_upkeep(cm, tab, cam, fresh=()):
 def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_thresh=2.0, mapping=False, known_frac=0.6,
                  pos_noise=0.005, map_seed=0, kf_every=5, detect=False, detect_cell_size=25, kf_select=False, kfselect_mindist_t=0.06,
                  kfselect_mindist_r=3.0, max_n_kfs=10, map_candidates=False, record_candidates=False, cell_select=False, select_params=None, kf_insert=False,
-                 seed_candidates=False, seeds_resident=False, image_seeds=None, image_seed_params=None, structopt_resident=False, compact=None, lm_room=None, keystage=None):
+                 seed_candidates=False, seeds_resident=False, image_seeds=None, image_seed_params=None, structopt_resident=False, compact=None, lm_room=None, keystage=None, align=None):
     """-> list of per-frame dicts (pose T_f_w, cov, counts).  Frame 0 is the keyframe with the true pose.
     mapping=True: only `known_frac` of the point landmarks start in the map (positions off by `pos_noise` x depth along
     their viewing ray), the others are depth-filter seeds; the seed update runs every frame; every `kf_every`-th frame
@@ -472,8 +562,17 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
     calls there were before: the key-point table kept here from the tables the harness follows, then the synchronous
     close_keyframes / keyframe_decide on gathered arrays.  The two differ in transport alone and agree in every record; the last record
     gains key_pts, the table at the end, every record overlap, the list itself, a keyframe's record key_pts_new, the decision's key points, and in "host" the keyframe records count the rows
-    rebuilt (n_kp_rebuilt)."""
+    rebuilt (n_kp_rebuilt).
+    align="host" | "device" (with map_candidates and cell_select; default None: every record is what it is without it): from the second
+    frame on the alignment job is the previous frame's selection as the device holds it when that frame is done (module docstring,
+    DESIGN.md 3.20).  "device" builds it there (a backend with align_build / align_built), runs it and passes the composed pose by device
+    pointer into the candidate stage; "host" restates the same job (align_job_host) and stages it as before.  The first frame's job
+    is gathered from keyframe 0 as without the flag, and so is the job of a frame behind one that left the tables waiting for a restage
+    (a keyframe without kf_insert, a converged seed without seed_candidates): the resident tables are then behind the harness's own.
+    The two agree in every record."""
     params = dict(locals())                            # (first statement: exactly the arguments)
+    if align not in (None, "host", "device") or (align and not (map_candidates and cell_select and (align == "host" or hasattr(backend, "align_build")))):
+        raise ValueError("align is None, 'host' or 'device' and needs map_candidates, cell_select and, for 'device', a backend with align_build() / align_built()")
     if keystage not in (None, "host", "device") or (keystage and not (kf_select and cell_select and kf_insert and hasattr(backend, "map_keyframe_decide" if keystage == "device" else "keyframe_decide"))):
         raise ValueError("keystage is None, 'host' or 'device' and needs kf_select, cell_select, kf_insert and a backend with keyframe_decide() / map_keyframe_decide()")
     if compact not in (None, "room", "always") or (compact and not (seed_candidates and hasattr(backend, "map_compact"))):
@@ -505,8 +604,9 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
 
 def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thresh, mapping, known_frac, pos_noise, map_seed, kf_every, detect, detect_cell_size, kf_select,
                   kfselect_mindist_t, kfselect_mindist_r, max_n_kfs, map_candidates, record_candidates, cell_select, select_params, kf_insert, seed_candidates, seeds_resident,
-                  image_seeds=None, image_seed_params=None, structopt_resident=False, compact=None, lm_room=None, keystage=None):
+                  image_seeds=None, image_seed_params=None, structopt_resident=False, compact=None, lm_room=None, keystage=None, align=None):
     cam = seq["cam"]
+    next_align = None                                  # align: the job of the frame to come -- an abi.AlignJob ("host") or True: built on the device
     kp_tab, kp_live = None, False                      # keystage: Frame::key_pts_ per keyframe row of cm ("host": kept here; "device": fetched when a restage needs it)
     img_kw = dict(fast_threshold=20, detection_threshold=20.0)
     img_kw.update(image_seed_params or {})
@@ -593,17 +693,26 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
         so_keys = dict(pt=[], seg=[])                  # structopt_resident: last_structure_optim_ per table row, followed from the reports (0: never refined)
         select_kw = dict(max_fts=120, max_fts_segs=100, cell_order=None, seg_cell_order=None, reproj_thresh=reproj_thresh)
         select_kw.update(select_params or {})
+    def align_job_of(k, sel, pr):
+        """frame k + 1's alignment job from frame k's selection and the tables as they stand at this point of frame k"""
+        if align == "device":
+            backend.align_build(k, k + 1, max_level, min_level, max(select_kw["max_fts"] + 2, 8), max(select_kw["max_fts_segs"] + 2, 8))
+            return True
+        return align_job_host(cam, max_level, min_level, sel, pr.pt_keep, pr.seg_keep, cm["pt_type"], cm["seg_type"], cm["pt_pos"], cm["seg_spos"], cm["seg_epos"], pr.T, k, k + 1)
+
     for k in range(1, len(seq["images"])):
         # ---- 1. sparse image alignment, previous frame -> frame k (processFrame :266-274) ----
-        ref_pos = synth.se3_inv(T_prev)[4:]
+        job = None
+        if next_align is None:                         # (align: otherwise the job was made behind the frame before this one)
+            ref_pos = synth.se3_inv(T_prev)[4:]
 
-        def scaled(px, pos):
-            return _bearing(cam, px) * np.linalg.norm(pos - ref_pos, axis=1)[:, None]        # f * |pos - ref_pos| (:229-230)
-        pi, si = prev["pt_idx"], prev["seg_idx"]
-        job = abi.AlignJob(cam, max_level, min_level, 30, 1e-6, synth.se3_mul(T_prev, synth.se3_inv(T_prev)), prev["pt_px"],
-                           scaled(prev["pt_px"], P3[pi]), prev["seg_spx"], prev["seg_epx"],
-                           np.linalg.norm(prev["seg_epx"] - prev["seg_spx"], axis=1), scaled(prev["seg_spx"], seq["seg_spos"][si]),
-                           scaled(prev["seg_epx"], seq["seg_epos"][si]), ref_slot=k - 1, cur_slot=k)
+            def scaled(px, pos):
+                return _bearing(cam, px) * np.linalg.norm(pos - ref_pos, axis=1)[:, None]    # f * |pos - ref_pos| (:229-230)
+            pi, si = prev["pt_idx"], prev["seg_idx"]
+            job = abi.AlignJob(cam, max_level, min_level, 30, 1e-6, synth.se3_mul(T_prev, synth.se3_inv(T_prev)), prev["pt_px"],
+                               scaled(prev["pt_px"], P3[pi]), prev["seg_spx"], prev["seg_epx"],
+                               np.linalg.norm(prev["seg_epx"] - prev["seg_spx"], axis=1), scaled(prev["seg_spx"], seq["seg_spos"][si]),
+                               scaled(prev["seg_epx"], seq["seg_epos"][si]), ref_slot=k - 1, cur_slot=k)
         pos_all = np.concatenate([P3, seq["seg_spos"], seq["seg_epos"]])
         if hasattr(backend, "frame_step"):
             # ---- 1-4 as one resident call: nothing but the final results comes back ----
@@ -617,8 +726,16 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
             pt_ok = np.zeros(n_pts, bool); pt_ok[pt_i] = True
             seg_ok = np.zeros(n_seg, bool); seg_ok[seg_i] = True
         else:
-            ar = backend.sparse_align(job)
-            T_k = synth.se3_mul(ar.T, T_prev)                                                    # :92
+            poses_dev = None
+            if next_align is None:
+                ar = backend.sparse_align(job)
+                T_k = synth.se3_mul(ar.T, T_prev)                                                # :92
+            elif align == "device":                    # the job was built behind the previous frame: run, compose, the pose stays on the device
+                ar, T_k, poses_dev = backend.align_built()
+            else:
+                ar = backend.sparse_align(next_align)
+                T_k = np.array(_se3_mul_s(ar.T, T_prev))
+            next_align = None
             close = None
             if map_candidates:
                 # ---- 2 + 3 from the map-candidate stage: overlap keyframes' features, first visit wins, closest-view observation,
@@ -657,7 +774,8 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                     cm_before = copy.deepcopy(cm) if record_candidates else None
                     cr, mr, sel, pr_sel, q_after = backend.map_select(map_job, abi.CandidateFrameJob(T_k, overlap, cur_slot=k), cam, n_pyr_levels, select_kw,
                                                                       carry=quality if map_job is not None else None,
-                                                                      **(dict(close=max_n_kfs, key_pts=kp_tab) if keystage == "device" else {}))
+                                                                      **(dict(close=max_n_kfs, key_pts=kp_tab) if keystage == "device" else {}),
+                                                                      **(dict(poses_dev=poses_dev) if poses_dev else {}))
                     if keystage == "device":
                         close = backend.last_close
                         overlap = [int(v) for v in close["close_idx"][:close["n_overlap"]]]
@@ -738,6 +856,7 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
             seg_ok = found[n_pts:n_pts + n_seg] & found[n_pts + n_seg:]
             if cell_select:
                 # ---- 4. on the device: the selected features in selection order, the resident pose optimiser's result ----
+                frame_sel = sel                        # (align: the selection under a name of its own -- step 5 has a `sel` too)
                 pt_i, seg_i = np.asarray(row_lm, np.int64)[sel["pt_lm"]], sel["seg_lm"].astype(np.int64)
                 sel_mask = pt_i >= 0
                 pt_i = pt_i[sel_mask]
@@ -878,6 +997,8 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                     rec.update(n_joined=ins["n_joined_pt"] + ins["n_joined_seg"], n_deleted_kf=ins["n_deleted_pt"] + ins["n_deleted_seg"], remove_kf=remove)
                     if keystage == "host":
                         rec["n_kp_rebuilt"] = int(kp_frame)
+                    if align and compact and k + 1 < len(seq["images"]):
+                        next_align = align_job_of(k, frame_sel, pr)    # ahead of the compaction, which renumbers the rows the selection points at
                     if compact:
                         # Map::emptyTrash on the resident tables: the deleted point rows leave, the rows behind them move down; the
                         # harness's rows follow the remap ("room": only when every live seed could no longer get a row)
@@ -1034,6 +1155,10 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                 rec.update(n_image_seeds=len(img_seeds["px"]), n_image_seeds_converged=img_converged)
             rec.update(n_known=int(known.sum()), n_seeds=len(seeds["idx"]),
                        landmark_err=float(np.median(np.linalg.norm(P3[known] - seq["pt_pos"][known], axis=1))))
+        if align and next_align is None and k + 1 < len(seq["images"]) and not cm_dirty:
+            # behind everything that moves a landmark in this frame.  Tables that wait for a restage no longer say what the harness's own do:
+            # the frame behind them is staged by the host as without the flag
+            next_align = align_job_of(k, frame_sel, pr)
         out.append(rec)
     if keystage and kp_live:                           # Frame::key_pts_ of every keyframe at the end
         out[-1]["key_pts"] = np.array(kp_tab if keystage == "host" else backend.map_fetch_keypts()[:len(cm["kf_T"])], np.int32).reshape(-1, 5)

@@ -11,7 +11,7 @@ With --kf-select (off by default; needs mapping) the keyframe stage runs on the 
 frame plays the keyframe when FrameHandlerMono::needNewKf says so instead of every fifth, and the JSON line lists the keyframe frames.
 With --map-candidates (off by default) reprojection and matching take their candidates from the map-candidate stage (plsvo_candidates_*):
 the overlap keyframes' features, one visit per landmark, the closest-view observation as the reference patch.
-usage: python tools/run_sequence.py [--distortion k1,k2,p1,p2[,k3]] [--detect] [--kf-select] [--map-candidates] [--cell-select] [--kf-insert] [--seed-candidates] [--seeds-resident] [--image-seeds host|device] [--structopt-resident] [--compact room|always] [--keystage host|device] [--lm-room N] [out.txt] [n_frames] [seed] [mapping 0|1]"""
+usage: python tools/run_sequence.py [--distortion k1,k2,p1,p2[,k3]] [--detect] [--kf-select] [--map-candidates] [--cell-select] [--kf-insert] [--seed-candidates] [--seeds-resident] [--image-seeds host|device] [--structopt-resident] [--compact room|always] [--keystage host|device] [--align host|device] [--lm-room N] [out.txt] [n_frames] [seed] [mapping 0|1]"""
 import importlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -61,6 +61,11 @@ if "--compact" in argv:
     i = argv.index("--compact")
     compact = argv[i + 1]
     del argv[i:i + 2]
+align = None
+if "--align" in argv:                              # host | device: the alignment job from the previous frame's selection (needs --map-candidates --cell-select)
+    i = argv.index("--align")
+    align = argv[i + 1]
+    del argv[i:i + 2]
 keystage = None
 if "--keystage" in argv:                           # host | device: the keyframe stage with live key points (needs --kf-select --cell-select --kf-insert)
     i = argv.index("--keystage")
@@ -85,7 +90,7 @@ if distortion is not None:
     seq = dict(seq, images=[P.synth.distort_image(img, dict(fx=fx, fy=fy, cx=cx, cy=cy, d=distortion)) for img in seq["images"]])
     rectify = P.abi.pinhole_radtan(w, h, fx, fy, cx, cy, distortion)
 res = seqm.run_sequence(seqm.HipBackend(ctx, rectify=rectify), seq, mapping=mapping, detect=detect, kf_select=kf_select, map_candidates=map_candidates, cell_select=cell_select, kf_insert=kf_insert,
-                        seed_candidates=seed_candidates, seeds_resident=seeds_resident, image_seeds=image_seeds, structopt_resident=structopt_resident, compact=compact, lm_room=lm_room, keystage=keystage,
+                        seed_candidates=seed_candidates, seeds_resident=seeds_resident, image_seeds=image_seeds, structopt_resident=structopt_resident, compact=compact, lm_room=lm_room, keystage=keystage, align=align,
                         image_seed_params=dict(fast_threshold=7, detection_threshold=2.0) if image_seeds else None)
 n = P.trajectory.write_trajectory(out, ["%.6f" % (0.05 * k) for k in range(n_frames)], [r["T"] for r in res], [r["cov"] for r in res])
 err = seqm.pose_errors(res, seq)

@@ -1408,10 +1408,10 @@ int plsvo_candidates_decide_fetch(plsvo_ctx* ctx, int n, plsvo_kf_decide_out* ou
 /* landmark when its keep byte is non-zero.                                                      */
 /* PINNED: a feature whose landmark row is PLSVO_LM_DELETED at build time counts as              */
 /* feat3D == NULL (Map::safeDeleteFrame, src/map.cpp:82-127, cuts such landmarks loose from the  */
-/* new keyframe's features).  LEFT OUT: a keyframe of the tables as the reference frame (the     */
-/* first frame, relocalizeFrame :408-436); the tracking-quality gates (:315-321, :335); writing  */
-/* the alignment's cull back into a keyframe's own segment features                              */
-/* (src/sparse_img_align.cpp:687-688); the C++ adapter.                                          */
+/* new keyframe's features).  LEFT OUT: writing the alignment's cull back into a keyframe's own   */
+/* segment features (src/sparse_img_align.cpp:687-688); the C++ adapter.  (A keyframe of the      */
+/* tables as the reference frame is plsvo_candidates_align_build_kf below, the tracking-quality   */
+/* gates, :315-321 and :335, plsvo_candidates_track_gate.)                                        */
 /* ------------------------------------------------------------------------------------------ */
 
 /* The resident alignment batch: per-stream CAPACITIES, by which its rows are laid out (stream s owns point rows from s * cap_pts,
@@ -1496,6 +1496,137 @@ int plsvo_candidates_align_compose(plsvo_ctx* ctx);
 const double* plsvo_candidates_align_poses_dev(plsvo_ctx* ctx);
 int plsvo_candidates_align_fetch(plsvo_ctx* ctx, int n, plsvo_cand_align_report* out);
 int plsvo_candidates_align_fetch_job(plsvo_ctx* ctx, int stream, plsvo_cand_align_job_out* out);
+
+/* ------------------------------------------------------------------------------------------ */
+/* the alignment job from a RESIDENT KEYFRAME as the reference frame           */
+/* SparseImgAlign::run(ref_keyframe, new_frame_) of FrameHandlerMono::relocalizeFrame            */
+/* (src/frame_handler_mono.cpp:408-436), its second alignment (last_frame_ = ref_keyframe;       */
+/* processFrame(), :266-274) and the first frame of a sequence, with Map::getClosestKeyframe      */
+/* (src/map.cpp:181-199) picking the row on request: one wave per stream writes the stream's     */
+/* rows of the SAME resident alignment batch plsvo_candidates_align_reserve laid out, in the     */
+/* same layout.  The keyframe's features are its lists in the tables (kf_pt_lm / kf_seg_lm); a    */
+/* feature's px, f, sf, ef are those of the FIRST observation of its landmark whose obs_kf is     */
+/* the keyframe (the pairing of the keyframe stage, also when a landmark is a feature of the      */
+/* keyframe twice).  A point feature is kept when it has a landmark (>= 0) whose row is not       */
+/* PLSVO_LM_DELETED (the pin of plsvo_candidates_align_build) and such an observation;            */
+/* PLSVO_LM_CANDIDATE landmarks are kept (feat3D != NULL).  pt_xyz_ref is the STORED bearing      */
+/* times ||pos - ref_pos|| ((*it)->f, src/sparse_img_align.cpp:229-230).  All segment features    */
+/* are written, in order; PINNED: a dead one (the same three conditions) has no pixels in the     */
+/* tables and gets zeros for pixels, length and the two vectors, seg_alive_in 0.                  */
+/* relocalizeFrame ignores its T_cur_ref argument; that is restated as it is.                     */
+/* LEFT OUT: writing the alignment's cull back into the keyframe's own segment features           */
+/* (src/sparse_img_align.cpp:687-688); relocalizeFrameAtPose; processFirstFrame /                 */
+/* processSecondFrame; the C++ adapter.                                                           */
+/* ------------------------------------------------------------------------------------------ */
+#define PLSVO_ALIGN_REF_CLOSEST (-1)  /* ref_kf: Map::getClosestKeyframe picks the row on the device */
+#define PLSVO_ALIGN_INIT_HOST     0   /* T_init of the record (relocalizeFrame's first run(): new_frame_'s default-constructed T_f_w_, the identity) */
+#define PLSVO_ALIGN_INIT_DEV      1   /* d_T_init */
+#define PLSVO_ALIGN_INIT_KEYFRAME 2   /* the reference keyframe's own pose (:266 with last_frame_ = ref_keyframe): T0 = T_kf * T_kf^-1, not the literal
+                                         identity; without a keyframe (PLSVO_ALIGN_JOB_NO_KEYFRAME) T_init of the record */
+#define PLSVO_ALIGN_JOB_NO_KEYFRAME 2 /* plsvo_cand_align_report::status: PLSVO_ALIGN_REF_CLOSEST found no close keyframe (relocalizeFrame's
+                                         "No reference keyframe", :413-417): an empty job with skip set whose reference pose, and so whose
+                                         composed pose, is T_init */
+
+/* One stream's record of a keyframe build.  T_last / d_T_last / last_source (PLSVO_INSERT_POSE_HOST or _DEV) and self_kf are read
+ * for PLSVO_ALIGN_REF_CLOSEST only: last_frame_->T_f_w_, the pose getCloseKeyframes looks from, and the row of last_frame_ when it is
+ * a keyframe of the table (else -1): the closest keyframe is the minimum by (distance, row) over the close keyframes other than
+ * self_kf.  PINNED: with self_kf the only close keyframe the reference calls front() on an empty list; here that is "none". */
+typedef struct plsvo_cand_align_kf_job {
+  int32_t active;                   /* 0: the stream sits this build out, as in plsvo_cand_align_job */
+  int32_t ref_kf;                   /* a keyframe row of the stream's table, or PLSVO_ALIGN_REF_CLOSEST */
+  int32_t self_kf;
+  int32_t cur_slot;                 /* pyramid slot of the frame to be aligned (the reference's is the keyframe's own) */
+  int32_t init_source;              /* PLSVO_ALIGN_INIT_* */
+  int32_t last_source;
+  double T_init[7];
+  double T_last[7];
+  const double* d_T_init;           /* DEVICE pointers to 7 doubles */
+  const double* d_T_last;
+} plsvo_cand_align_kf_job;
+
+/* align_build_kf: ENQUEUE ONLY; only the records travel.  It needs staged tables and the reserve -- no run, no selection, no pose
+ *   optimisation -- and reads only the tables, so it is valid BEHIND plsvo_candidates_compact as well.  Like plsvo_candidates_align_build
+ *   it makes the built batch the context's staged alignment batch, and the two compose on one batch: a stream active in one call sits
+ *   the other out and keeps its rows, so tracking and relocalising streams run in ONE plsvo_align_run; plsvo_align_run, _fetch,
+ *   plsvo_candidates_align_compose, _align_poses_dev, _align_fetch, _align_fetch_job serve the batch unchanged.  The report's
+ *   reserved0 carries ref_kf + 1 (the row the job was built from; 0 for a build from the selection and for NO_KEYFRAME); NO_ROOM as in
+ *   plsvo_candidates_align_build (a keyframe of more segment features than cap_seg is dropped before any scratch is used).
+ *   PLSVO_E_STATE: no reserve (or one for another stream count); between plsvo_seeds_update and its fetch; PLSVO_ALIGN_REF_CLOSEST
+ *   without a live key-point table (plsvo_candidates_set_keypts); the pyramids or the camera changed since the reserve.
+ *   PLSVO_E_INVALID (nothing enqueued): another n than staged, NULL jobs, a row outside the stream's keyframes by the host's mirror (self_kf
+ *   too), an unknown source, a source that needs a device pointer without one, cur_slot or the keyframe's slot outside the pyramids. */
+int plsvo_candidates_align_build_kf(plsvo_ctx* ctx, int n, const plsvo_cand_align_kf_job* jobs);
+
+/* ------------------------------------------------------------------------------------------ */
+/* the tracking gates of a tracked frame, decided on the device                */
+/* replaces, per tracked frame, the comparisons a caller made on fetched counts for             */
+/* FrameHandlerMono::processFrame: "not enough matched features"                                */
+/* (src/frame_handler_mono.cpp:315-321), fewer than 10 edges behind the pose optimisation        */
+/* (:335), FrameHandlerBase::setTrackingQuality (src/frame_handler_base.cpp:173-190) and the     */
+/* pose the frame carries forward (:318, :336; relocalizeFrame :432).  A lane per stream reads   */
+/* the selection's n_matches / n_ls_matches and the pose optimiser's num_obs_pt / num_obs_ls     */
+/* where they lie.  setTrackingQuality is restated literally: the segments' drop is computed and */
+/* reported and decides nothing; :346-350 (TRACKING_INSUFFICIENT behind setTrackingQuality)      */
+/* cannot be reached in the reference and is not built.                                          */
+/* LEFT OUT: device-side masks that would let the later stages of a frame skip a failed stream   */
+/* without the host (the caller fetches the 32-byte records ahead of the structure optimisation  */
+/* and leaves such a stream out of the later calls); relocalizeFrameAtPose; processFirstFrame /  */
+/* processSecondFrame; the C++ adapter.                                                          */
+/* ------------------------------------------------------------------------------------------ */
+#define PLSVO_GATE_TRACK 0            /* processFrame from STAGE_DEFAULT_FRAME */
+#define PLSVO_GATE_RELOC 1            /* processFrame inside relocalizeFrame: every failure resets the pose (:432) */
+#define PLSVO_GATE_OK           0
+#define PLSVO_GATE_FAIL_MATCHES 1     /* n_matches + n_ls_matches < quality_min_fts (:315-321) */
+#define PLSVO_GATE_FAIL_EDGES   2     /* num_obs_pt + num_obs_ls < 10 (:335) */
+#define PLSVO_TRACKING_INSUFFICIENT 0 /* FrameHandlerBase::TrackingQuality, in its order */
+#define PLSVO_TRACKING_BAD          1
+#define PLSVO_TRACKING_GOOD         2
+#define PLSVO_GATE_LAST_HOST     0    /* num_obs_last_pt / _ls of the record */
+#define PLSVO_GATE_LAST_RESIDENT 1    /* the stream's counts of its last active gate since plsvo_candidates_stage */
+
+/* One stream's record of a gate.  T_reset: last_frame_->T_f_w_ under PLSVO_GATE_TRACK, the last well localised pose under
+ * PLSVO_GATE_RELOC; reset_source: PLSVO_INSERT_POSE_HOST (T_reset) or PLSVO_INSERT_POSE_DEV (d_T_reset). */
+typedef struct plsvo_cand_gate {
+  int32_t active;                   /* 0: the stream sits the call out; its record, carried pose and resident counts stay */
+  int32_t mode;                     /* PLSVO_GATE_TRACK / _RELOC */
+  int32_t quality_min_fts;          /* Config::qualityMinFts() (20) */
+  int32_t quality_max_drop_fts;     /* int(Config::qualityMaxFtsDrop()) (50) */
+  int32_t max_fts, max_fts_segs;    /* Config::maxFts(), Config::maxFtsSegs(): the clamps of the two drops */
+  int32_t last_source;              /* PLSVO_GATE_LAST_* */
+  int32_t num_obs_last_pt, num_obs_last_ls;   /* FrameHandlerBase::num_obs_last_pt / _ls (PLSVO_GATE_LAST_HOST) */
+  int32_t reset_source;
+  double T_reset[7];
+  const double* d_T_reset;          /* a DEVICE pointer to 7 doubles */
+} plsvo_cand_gate;
+
+typedef struct plsvo_cand_gate_out {   /* 32 bytes per stream */
+  int32_t result;                   /* PLSVO_GATE_* */
+  int32_t tracking_quality;         /* PLSVO_TRACKING_*: INSUFFICIENT on either failure (finishFrameProcessingCommon), else setTrackingQuality's */
+  int32_t n_matched;                /* n_matches + n_ls_matches */
+  int32_t n_edges;                  /* num_obs_pt + num_obs_ls */
+  int32_t drop_pt, drop_ls;         /* min(num_obs_last, max_fts) - num_obs, per kind */
+  int32_t num_obs_last_pt, num_obs_last_ls;   /* the counts the drops were taken against */
+} plsvo_cand_gate_out;
+
+/* track_gate: ENQUEUE ONLY, behind plsvo_candidates_pose_optimize of a run, any number of times; only the records travel.  Per active
+ *   stream it writes the 32-byte record, the pose carried forward (PLSVO_GATE_TRACK: FAIL_MATCHES gives T_reset, FAIL_EDGES and OK the
+ *   optimised pose; PLSVO_GATE_RELOC: every failure gives T_reset) and the stream's resident num_obs_last_pt / _ls, which become this
+ *   frame's n_matches / n_ls_matches whatever the result (Frame::nObs() is the size of the feature list).
+ *   PLSVO_E_STATE: no resident pose optimisation on the last run; between plsvo_seeds_update and its fetch; PLSVO_GATE_LAST_RESIDENT
+ *   before the first gate since plsvo_candidates_stage.  PLSVO_E_INVALID (nothing enqueued): another n than staged, NULL jobs, an
+ *   unknown mode or source, PLSVO_INSERT_POSE_DEV without a pointer, a negative threshold, clamp or count.
+ * gate_fetch: synchronises; the records (a stream that sat every call since the stage out reads as zeros) and, when poses is not NULL,
+ *   the carried poses into n * 7 doubles.
+ *   PLSVO_E_STATE without a gate since the stage; PLSVO_E_INVALID for another n or NULL out.
+ * gate_poses_dev: the carried poses, n * 7 doubles on the device, stream s at + 7 * s (NULL before the first gate since the stage): what
+ *   plsvo_cand_frame::d_T_f_w, plsvo_cand_align_job::d_T_f_w, plsvo_seed_frame::d_T_f_w, plsvo_cand_kf_decide::d_T_last_w and
+ *   plsvo_cand_gate::d_T_reset take.  A stream that was never active holds zeros.  As d_T_reset of a gate it may alias only the
+ *   stream's OWN row (+ 7 * s: each element is read and written by the same lane); another stream's row is written by that stream's
+ *   lane in the same launch.  The buffer is laid out anew by the first gate behind a plsvo_candidates_stage: a pointer taken before
+ *   the stage must not be used after it. */
+int plsvo_candidates_track_gate(plsvo_ctx* ctx, int n, const plsvo_cand_gate* jobs);
+int plsvo_candidates_gate_fetch(plsvo_ctx* ctx, int n, plsvo_cand_gate_out* out, double* poses);
+const double* plsvo_candidates_gate_poses_dev(plsvo_ctx* ctx);
 
 /* TUM-style trajectory record of a frame (app/run_pipeline.cpp:425-451): the camera pose in the world,
  * T_f_w^-1, as tx ty tz qx qy qz qw.  Returns 1 and fills out7 when the reference would write the line, 0 when

@@ -355,6 +355,34 @@ class CandAlignJobOut(C.Structure):
                 ("seg_q_ref", c_double_p), ("seg_alive_in", c_u8_p), ("seg_code", c_i32_p)]
 
 
+ALIGN_JOB_NO_KEYFRAME = 2
+ALIGN_REF_CLOSEST = -1
+ALIGN_INIT_HOST, ALIGN_INIT_DEV, ALIGN_INIT_KEYFRAME = 0, 1, 2
+
+
+class CandAlignKfJob(C.Structure):
+    """plsvo_cand_align_kf_job"""
+    _fields_ = [(f, C.c_int32) for f in ("active", "ref_kf", "self_kf", "cur_slot", "init_source", "last_source")] + \
+               [("T_init", C.c_double * 7), ("T_last", C.c_double * 7), ("d_T_init", C.c_void_p), ("d_T_last", C.c_void_p)]
+
+
+GATE_TRACK, GATE_RELOC = 0, 1
+GATE_OK, GATE_FAIL_MATCHES, GATE_FAIL_EDGES = 0, 1, 2
+TRACKING_INSUFFICIENT, TRACKING_BAD, TRACKING_GOOD = 0, 1, 2
+GATE_LAST_HOST, GATE_LAST_RESIDENT = 0, 1
+
+
+class CandGate(C.Structure):
+    """plsvo_cand_gate"""
+    _fields_ = [(f, C.c_int32) for f in ("active", "mode", "quality_min_fts", "quality_max_drop_fts", "max_fts", "max_fts_segs", "last_source", "num_obs_last_pt",
+                                         "num_obs_last_ls", "reset_source")] + [("T_reset", C.c_double * 7), ("d_T_reset", C.c_void_p)]
+
+
+class CandGateOut(C.Structure):
+    """plsvo_cand_gate_out"""
+    _fields_ = [(f, C.c_int32) for f in ("result", "tracking_quality", "n_matched", "n_edges", "drop_pt", "drop_ls", "num_obs_last_pt", "num_obs_last_ls")]
+
+
 LM_EVENT_NEW = 8
 
 

@@ -36,6 +36,7 @@ SYMBOLS = [
     "plsvo_candidates_compact", "plsvo_candidates_compact_fetch",
     "plsvo_candidates_align_reserve", "plsvo_candidates_align_build", "plsvo_candidates_align_compose", "plsvo_candidates_align_poses_dev", "plsvo_candidates_align_fetch",
     "plsvo_candidates_align_fetch_job",
+    "plsvo_candidates_align_build_kf", "plsvo_candidates_track_gate", "plsvo_candidates_gate_fetch", "plsvo_candidates_gate_poses_dev",
     "plsvo_seeds_reserve", "plsvo_seeds_capacity", "plsvo_seeds_stage", "plsvo_seeds_update", "plsvo_seeds_update_fetch", "plsvo_seeds_keyframe", "plsvo_seeds_fetch_lists",
     "plsvo_seeds_fetch_rows", "plsvo_seeds_commit_rows", "plsvo_seeds_keyframe_detect", "plsvo_seeds_keyframe_fetch",
     "plsvo_chain_stage", "plsvo_chain_run", "plsvo_chain_fetch", "plsvo_frame_step_batch", "plsvo_chain_poses_dev",
@@ -196,6 +197,10 @@ def lib():
         "plsvo_candidates_align_compose": (C.c_int, [ctxp]),
         "plsvo_candidates_align_poses_dev": (C.c_void_p, [ctxp]),
         "plsvo_candidates_align_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandAlignReport)]),
+        "plsvo_candidates_align_build_kf": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandAlignKfJob)]),
+        "plsvo_candidates_track_gate": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandGate)]),
+        "plsvo_candidates_gate_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandGateOut), abi.c_double_p]),
+        "plsvo_candidates_gate_poses_dev": (C.c_void_p, [ctxp]),
         "plsvo_candidates_align_fetch_job": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.CandAlignJobOut)]),
         "plsvo_seeds_reserve": (C.c_int, [ctxp, C.POINTER(abi.SeedReserve)]),
         "plsvo_seeds_capacity": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.SeedReserve)]),
@@ -1200,6 +1205,37 @@ class Context:
         self._chk(self.L.plsvo_candidates_align_build(self.h, n, arr))
         self._align_jobs = [abi.BuiltAlignJob(self._align_cfg["cap_seg"]) for _ in range(n)]      # what align_fetch() sizes its buffers by
 
+    def candidates_align_build_kf(self, jobs):
+        """plsvo_candidates_align_build_kf (enqueue only): per staged stream None (sits the build out) or a dict of cur_slot, ref_kf (a
+        keyframe row; missing or None: the closest keyframe, picked on the device from T_last (7 doubles) or last_dev (a device pointer)
+        with self_kf, the row of the last frame when it is a keyframe, default -1) and the frame's initial pose: T_init (7 doubles),
+        init_dev (a device pointer) or neither (the reference keyframe's own pose).  The built batch is the staged alignment batch
+        afterwards, as after candidates_align_build; the two compose on one batch."""
+        n = len(jobs)
+        arr = (abi.CandAlignKfJob * max(n, 1))()
+        for a, j in zip(arr, jobs):
+            if j is None:
+                continue
+            a.active, a.cur_slot, a.self_kf = 1, int(j.get("cur_slot", 0)), int(j.get("self_kf", -1))
+            a.ref_kf = abi.ALIGN_REF_CLOSEST if j.get("ref_kf") is None else int(j["ref_kf"])
+            if j.get("init_dev") is not None:
+                a.init_source, a.d_T_init = abi.ALIGN_INIT_DEV, int(j["init_dev"])
+            elif j.get("T_init") is not None and not j.get("init_keyframe"):
+                a.init_source = abi.ALIGN_INIT_HOST
+            else:
+                a.init_source = abi.ALIGN_INIT_KEYFRAME
+            if j.get("T_init") is not None:
+                a.T_init = (C.c_double * 7)(*[float(v) for v in j["T_init"]])
+            if j.get("last_dev") is not None:
+                a.last_source, a.d_T_last = abi.INSERT_POSE_DEV, int(j["last_dev"])
+            elif j.get("T_last") is not None:
+                a.last_source, a.T_last = abi.INSERT_POSE_HOST, (C.c_double * 7)(*[float(v) for v in j["T_last"]])
+            if "raw" in j:                                            # (tests of the argument checks: fields set as given)
+                for f, v in j["raw"].items():
+                    setattr(a, f, v)
+        self._chk(self.L.plsvo_candidates_align_build_kf(self.h, n, arr))
+        self._align_jobs = [abi.BuiltAlignJob(self._align_cfg["cap_seg"]) for _ in range(n)]      # what align_fetch() sizes its buffers by
+
     def candidates_align_compose(self):
         """plsvo_candidates_align_compose (enqueue only, behind align_run of the built batch)"""
         self._chk(self.L.plsvo_candidates_align_compose(self.h))
@@ -1212,7 +1248,7 @@ class Context:
         n = len(self._cand_maps)
         outs = (abi.CandAlignReport * max(n, 1))()
         self._chk(self.L.plsvo_candidates_align_fetch(self.h, n, outs))
-        return [{f: int(getattr(o, f)) for f, _ in abi.CandAlignReport._fields_ if not f.startswith("reserved")} for o in outs[:n]]
+        return [dict({f: int(getattr(o, f)) for f, _ in abi.CandAlignReport._fields_ if not f.startswith("reserved")}, ref_kf=int(o.reserved0) - 1) for o in outs[:n]]
 
     def candidates_align_fetch_job(self, stream):
         """plsvo_candidates_align_fetch_job (diagnostic, synchronises): one stream's built job as a dict -- the counts, n_slots (8), T0,
@@ -1229,6 +1265,43 @@ class Context:
                  cur_slot=int(o.cur_slot), n_patches=int(o.n_patches), T0=np.array(o.T0[:]), T_ref=np.array(o.T_ref[:]), T_f_w=np.array(o.T_f_w[:]))
         r.update({k: (v[:, :o.n_seg] if k == "seg_code" else v[:(o.n_pts if k.startswith("pt_") else o.n_seg)]).copy() for k, v in b.items()})
         return r
+
+    # ---- the tracking gates of a tracked frame, decided on the device ----
+    def candidates_track_gate(self, jobs):
+        """plsvo_candidates_track_gate (enqueue only, behind candidates_pose_optimize): per staged stream None (sits the call out) or a
+        dict of mode (abi.GATE_TRACK / GATE_RELOC), quality_min_fts, quality_max_drop_fts, max_fts, max_fts_segs, the pose a failure
+        resets to as T_reset (7 doubles) or reset_dev (a device pointer), and num_obs_last=(pt, ls) -- missing: the resident counts of
+        the stream's last active gate"""
+        n = len(jobs)
+        arr = (abi.CandGate * max(n, 1))()
+        for a, j in zip(arr, jobs):
+            if j is None:
+                continue
+            a.active, a.mode = 1, int(j.get("mode", abi.GATE_TRACK))
+            a.quality_min_fts, a.quality_max_drop_fts = int(j.get("quality_min_fts", 20)), int(j.get("quality_max_drop_fts", 50))
+            a.max_fts, a.max_fts_segs = int(j.get("max_fts", 100)), int(j.get("max_fts_segs", 100))
+            if j.get("num_obs_last") is not None:
+                a.last_source, a.num_obs_last_pt, a.num_obs_last_ls = abi.GATE_LAST_HOST, int(j["num_obs_last"][0]), int(j["num_obs_last"][1])
+            else:
+                a.last_source = abi.GATE_LAST_RESIDENT
+            if j.get("reset_dev") is not None:
+                a.reset_source, a.d_T_reset = abi.INSERT_POSE_DEV, int(j["reset_dev"])
+            else:
+                a.reset_source, a.T_reset = abi.INSERT_POSE_HOST, (C.c_double * 7)(*[float(v) for v in j["T_reset"]])
+        self._chk(self.L.plsvo_candidates_track_gate(self.h, n, arr))
+
+    def candidates_gate_fetch(self, poses=False):
+        """plsvo_candidates_gate_fetch (synchronises): per stream a dict of abi.CandGateOut's fields; poses=True: (those, the carried
+        poses [n, 7])"""
+        n = len(self._cand_maps)
+        outs = (abi.CandGateOut * max(n, 1))()
+        T = np.zeros((max(n, 1), 7))
+        self._chk(self.L.plsvo_candidates_gate_fetch(self.h, n, outs, self._ptr(T) if poses else None))
+        recs = [{f: int(getattr(o, f)) for f, _ in abi.CandGateOut._fields_} for o in outs[:n]]
+        return (recs, T[:n]) if poses else recs
+
+    def candidates_gate_poses_dev(self):
+        return self.L.plsvo_candidates_gate_poses_dev(self.h)
 
     # ---- structure optimisation on the resident map tables ----
     def candidates_optimize_structure(self, jobs, max_n_pts=20, n_iter_pts=5, max_n_segs=20, n_iter_segs=5):

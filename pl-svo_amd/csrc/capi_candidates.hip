@@ -24,7 +24,7 @@ static QualitySections quality_sections(const plsvo_ctx* c) {
   return s;
 }
 static void cand_reset_run(plsvo_ctx* c) { c->cd_ran = c->cd_matched = c->cs_selected = c->cs_posed = c->ci_inserted = c->cn_closed = c->cc_closed = c->co_done = c->ck_have_close = c->ck_decided = false; }   // the steps taken on the last run's results
-static void cand_reset_stage(plsvo_ctx* c) { cand_reset_run(c); c->cd_staged = c->ci_have_out = c->cn_have_out = c->cc_have_out = c->co_have_out = c->sd_staged = c->sd_pending = c->sd_have_report = c->sk_have_report = c->ck_live = false; }   // those, the tables, the key-point table, the last insertion's and add's reports
+static void cand_reset_stage(plsvo_ctx* c) { cand_reset_run(c); c->cd_staged = c->ci_have_out = c->cn_have_out = c->cc_have_out = c->co_have_out = c->sd_staged = c->sd_pending = c->sd_have_report = c->sk_have_report = c->ck_live = c->tg_have = false; }   // those, the tables, the key-point table, the last insertion's and add's reports
 // PLSVO_OK while the last run's candidates still describe the tables; once an insertion or an add came behind it, the refusal of entry point `who`
 static int cand_run_open(plsvo_ctx* c, const char* who) {
   const char* why = c->ci_inserted ? "this run's frame was inserted" : c->cn_closed ? "landmarks were added behind this run" : c->cc_closed ? "the tables were compacted behind this run" : nullptr;
@@ -1355,13 +1355,13 @@ extern "C" int plsvo_candidates_compact_fetch(plsvo_ctx* c, int n, plsvo_cand_co
 // ---- the next frame's alignment job from the resident selection (alignjob_device.hpp) ------------------------------------------
 namespace {
 // the sections of aj_d_batch (the resident alignment batch, rows by capacity) and of aj_d_out (reports, reference poses, composed poses)
-struct AlignJobSections { size_t jobs, T0, pt_px, pt_xyz, spx, epx, len, sp, sq, alive, slot, rank, end, o_report, o_tref, o_poses, o_key, o_end; };
+struct AlignJobSections { size_t jobs, T0, pt_px, pt_xyz, spx, epx, len, sp, sq, alive, slot, rank, obs, end, o_report, o_tref, o_poses, o_key, o_end; };
 static AlignJobSections align_job_sections(size_t n, const plsvo_cand_align_cfg& g) {
   const size_t np = n * (size_t)g.cap_pts, ns = n * (size_t)g.cap_seg, nl = (size_t)(g.max_level - g.min_level + 1);
   Carver w; AlignJobSections o;
   o.jobs = w.take<AlignJobDev>(n); o.T0 = w.take<double>(n * 7); o.pt_px = w.take<double>(np * 2); o.pt_xyz = w.take<double>(np * 3);
   o.spx = w.take<double>(ns * 2); o.epx = w.take<double>(ns * 2); o.len = w.take<double>(ns); o.sp = w.take<double>(ns * 3); o.sq = w.take<double>(ns * 3);
-  o.alive = w.take<uint8_t>(ns); o.slot = w.take<int>(nl * ns); o.rank = w.take<int>(ns); o.end = w.off;
+  o.alive = w.take<uint8_t>(ns); o.slot = w.take<int>(nl * ns); o.rank = w.take<int>(ns); o.obs = w.take<int>(ns); o.end = w.off;   // (obs: a keyframe build's scratch, behind the codes' 0xff fill)
   Carver v;
   o.o_report = v.take<AlignBuildReportDev>(n); o.o_tref = v.take<double>(n * 7); o.o_poses = v.take<double>(n * 7); o.o_key = v.take<int>(n); o.o_end = v.off;   // (o_key: the patch count of every stream's last build, the launch-order key)
   return o;
@@ -1378,6 +1378,51 @@ static int align_job_work(plsvo_ctx* c, size_t n, const plsvo_cand_align_cfg& g)
   HIP_TRY(c, c->a_d_cref.ensure(pt * 64));
   HIP_TRY(c, c->a_d_chi.ensure(2 * npt_total * 16 * sizeof(float)));
   if (c->a_trace_cap > 0) HIP_TRY(c, c->a_d_log.ensure(n * (size_t)c->a_trace_cap * sizeof(plsvo_align_iterlog)));
+  return PLSVO_OK;
+}
+// behind a build's launch: its launch order, and the built batch becomes the context's staged alignment batch (the host's view of it
+// holds the capacities; aj_slots: per stream the pyramid slots of its last build)
+static int align_job_adopt(plsvo_ctx* c, const AlignBuildBatchDev& b, int n, int seg_align) {
+  const plsvo_cand_align_cfg& g = c->aj_cfg;
+  const size_t N = (size_t)n;
+  // launch order: most patches (summed over the levels) first, by the counting sort that re-orders a re-run batch (bins of four patches),
+  // on the build's own key -- a stream that sat the build out keeps its last count -- into a buffer no later launch's re-ordering writes
+  const int* order = nullptr;
+  if (!c->env_align_no_lpt) {
+    HIP_TRY(c, launch_align_reorder(b.work_key, n, c->aj_d_order.as<int>(), 2, c->stream));
+    order = c->aj_d_order.as<int>();
+  }
+  // -- the built batch is the context's staged alignment batch; the host's view of it holds the capacities
+  const int patch_cap = b.patch_cap;
+  c->a_jobs.assign(N, AlignJobDev{});
+  for (int j = 0; j < n; ++j) {
+    AlignJobDev& J = c->a_jobs[(size_t)j];
+    J.ref_slot = c->aj_slots[2 * (size_t)j]; J.cur_slot = c->aj_slots[2 * (size_t)j + 1];
+    J.max_level = g.max_level; J.min_level = g.min_level; J.n_iter = g.n_iter; J.eps = g.eps;
+    J.pt_off = j * g.cap_pts; J.n_pts = g.cap_pts; J.seg_off = j * g.cap_seg; J.n_seg = g.cap_seg; J.patch_off = j * patch_cap; J.patch_cap = patch_cap;
+  }
+  AlignBatchDev& a = c->a_b;
+  a.jobs = b.a_jobs; a.state = c->a_d_state.as<AlignStateDev>(); a.T0 = b.T0;
+  a.pt_px = b.pt_px; a.pt_xyz = b.pt_xyz; a.seg_spx = b.seg_spx; a.seg_epx = b.seg_epx; a.seg_len = b.seg_len; a.seg_p = b.seg_p; a.seg_q = b.seg_q;
+  a.seg_alive_in = b.seg_alive_in; a.seg_alive = c->a_d_alive.as<uint8_t>();
+  a.patch_xyz = c->a_d_pxyz.as<double>(); a.patch_uvref = c->a_d_puv.as<float>(); a.cache_ref = c->a_d_cref.as<float>();
+  a.chi_terms = c->a_d_chi.as<float>(); a.chi_plane = (unsigned long long)(N * (size_t)g.cap_pts + 32) * 16;
+  a.seg_slot = b.seg_slot; a.slot_level0 = g.min_level; a.slot_stride = n * g.cap_seg;
+  a.poses = c->a_d_poses.as<double>();
+  a.pyr = c->pyr;
+  a.log = c->a_trace_cap > 0 ? c->a_d_log.as<plsvo_align_iterlog>() : nullptr;
+  a.log_cap = c->a_trace_cap;
+  a.n_jobs = n;
+  a.pair = 0; a.xseq0 = 0; a.xbuf = nullptr; a.work_key = nullptr; a.tail_n = 0; a.static_solve = 1; a.tail_flag = nullptr; a.seg_alive_tail = nullptr;   // (plsvo_align_run decides)
+  a.order = order;
+  c->a_stage_order = order;
+  c->a_patch_total = std::max(N * (size_t)patch_cap, (size_t)4);
+  c->a_n = n; c->a_total_seg = n * g.cap_seg; c->a_gmax = g.max_level; c->a_gmin = g.min_level;
+  for (int l = 0; l < PLSVO_MAX_LEVELS; ++l) c->a_cap[l] = (l >= g.min_level && l <= g.max_level) ? patch_cap : 0;
+  c->a_scap = std::max(4, g.cap_seg);
+  c->a_seg_align = seg_align;
+  c->a_staged = true; c->a_run_seq = 0;
+  c->aj_built = true; c->aj_composed = false;
   return PLSVO_OK;
 }
 }  // namespace
@@ -1443,7 +1488,8 @@ extern "C" int plsvo_candidates_align_reserve(plsvo_ctx* c, const plsvo_cand_ali
   b.cap_pts = g->cap_pts; b.cap_seg = g->cap_seg; b.slot_cap = g->slot_cap; b.patch_cap = patch_cap;
   b.max_level = g->max_level; b.min_level = g->min_level; b.n_iter = g->n_iter; b.eps = g->eps;
   c->aj_pose = AlignPoseBatchDev{ nullptr, b.T_ref, reinterpret_cast<double*>(dout + o.o_poses), n };
-  c->aj_cfg = *g; c->aj_n = n; c->aj_slots.assign(2 * N, 0);
+  c->aj_seg_obs = reinterpret_cast<int*>(db + o.obs);
+  c->aj_cfg = *g; c->aj_n = n; c->aj_slots.assign(2 * N, 0); c->aj_kf_slots.assign(N, std::vector<int>());
   c->aj_reserved = true;
   return PLSVO_OK;
 }
@@ -1511,46 +1557,81 @@ extern "C" int plsvo_candidates_align_build(plsvo_ctx* c, int n, const plsvo_can
   c->a_staged = false; c->aj_built = false;
   c->ch_staged = false;                             // a resident frame step is built on the staged alignment batch: building another one invalidates it
   HIP_TRY_TIMED(c, PLSVO_K_ALIGN_INIT, launch_map_align_job(b, c->stream));
-  // launch order: most patches (summed over the levels) first, by the counting sort that re-orders a re-run batch (bins of four patches),
-  // on the build's own key -- a stream that sat the build out keeps its last count -- into a buffer no later launch's re-ordering writes
-  const int* order = nullptr;
-  if (!c->env_align_no_lpt) {
-    HIP_TRY(c, launch_align_reorder(b.work_key, n, c->aj_d_order.as<int>(), 2, c->stream));
-    order = c->aj_d_order.as<int>();
+  for (int s = 0; s < n; ++s) if (in[s].active) { c->aj_slots[2 * (size_t)s] = in[s].ref_slot; c->aj_slots[2 * (size_t)s + 1] = in[s].cur_slot; c->aj_kf_slots[(size_t)s].clear(); }
+  return align_job_adopt(c, b, n, seg_align);
+}
+
+// relocalizeFrame's and the first frame's job: a keyframe row of the resident tables as the reference frame (map_align_kf_job_kernel)
+extern "C" int plsvo_candidates_align_build_kf(plsvo_ctx* c, int n, const plsvo_cand_align_kf_job* in) {
+  CTX_CHECK(c);
+  if (!c->cd_staged || !c->aj_reserved || c->aj_n != c->cd_n) return fail(c, PLSVO_E_STATE, "candidates_align_build_kf: no alignment batch reserved for the staged streams (plsvo_candidates_align_reserve)");
+  if (const int rc = cand_seeds_pending(c, "candidates_align_build_kf")) return rc;
+  if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_align_build_kf: n does not match the staged batch");
+  const plsvo_cand_align_cfg& g = c->aj_cfg;
+  if (!c->pyr.base || g.max_level >= c->pyr.n_levels || c->cd_b.cam_width != c->pyr.w[0] || c->cd_b.cam_height != c->pyr.h[0])
+    return fail(c, PLSVO_E_STATE, "candidates_align_build_kf: the pyramids or the camera changed since the reserve");
+  bool closest = false;
+  for (int s = 0; s < n; ++s) {
+    const plsvo_cand_align_kf_job& I = in[s];
+    if (!I.active) continue;
+    const CandMapDev& M = c->cd_maps[(size_t)s];
+    if (I.ref_kf != PLSVO_ALIGN_REF_CLOSEST && (I.ref_kf < 0 || I.ref_kf >= M.n_kf)) return fail(c, PLSVO_E_INVALID, "candidates_align_build_kf: no such keyframe row");
+    if (I.cur_slot < 0 || I.cur_slot >= c->pyr.n_slots) return fail(c, PLSVO_E_INVALID, "candidates_align_build_kf: pyramid slot out of range");
+    for (int k = 0; k < M.n_kf; ++k)
+      if ((I.ref_kf == PLSVO_ALIGN_REF_CLOSEST || I.ref_kf == k) && (c->cd_kf_slot[(size_t)M.kf_off + (size_t)k] < 0 || c->cd_kf_slot[(size_t)M.kf_off + (size_t)k] >= c->pyr.n_slots))
+        return fail(c, PLSVO_E_INVALID, "candidates_align_build_kf: a keyframe's pyramid slot is out of range");
+    if (I.init_source < PLSVO_ALIGN_INIT_HOST || I.init_source > PLSVO_ALIGN_INIT_KEYFRAME || (I.init_source == PLSVO_ALIGN_INIT_DEV && !I.d_T_init))
+      return fail(c, PLSVO_E_INVALID, "candidates_align_build_kf: bad source of the initial pose");
+    if (I.ref_kf == PLSVO_ALIGN_REF_CLOSEST) {
+      if ((I.last_source != PLSVO_INSERT_POSE_HOST && I.last_source != PLSVO_INSERT_POSE_DEV) || (I.last_source == PLSVO_INSERT_POSE_DEV && !I.d_T_last))
+        return fail(c, PLSVO_E_INVALID, "candidates_align_build_kf: bad source of the last frame's pose");
+      if (I.self_kf < -1 || I.self_kf >= M.n_kf) return fail(c, PLSVO_E_INVALID, "candidates_align_build_kf: self_kf is no keyframe row");
+      closest = true;
+    }
   }
-  // -- the built batch is the context's staged alignment batch; the host's view of it holds the capacities
-  for (int s = 0; s < n; ++s) if (in[s].active) { c->aj_slots[2 * (size_t)s] = in[s].ref_slot; c->aj_slots[2 * (size_t)s + 1] = in[s].cur_slot; }
-  const int patch_cap = b.patch_cap;
-  c->a_jobs.assign(N, AlignJobDev{});
-  for (int j = 0; j < n; ++j) {
-    AlignJobDev& J = c->a_jobs[(size_t)j];
-    J.ref_slot = c->aj_slots[2 * (size_t)j]; J.cur_slot = c->aj_slots[2 * (size_t)j + 1];
-    J.max_level = g.max_level; J.min_level = g.min_level; J.n_iter = g.n_iter; J.eps = g.eps;
-    J.pt_off = j * g.cap_pts; J.n_pts = g.cap_pts; J.seg_off = j * g.cap_seg; J.n_seg = g.cap_seg; J.patch_off = j * patch_cap; J.patch_cap = patch_cap;
+  if (closest && !c->ck_live) return fail(c, PLSVO_E_STATE, "candidates_align_build_kf: the closest keyframe needs a live key-point table (plsvo_candidates_set_keypts)");
+  if (n == 0) return PLSVO_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t N = (size_t)n;
+  Blob blob;
+  const size_t b_jobs = blob.reserve<AlignKfJobDev>(N);
+  for (int s = 0; s < n; ++s) {
+    const plsvo_cand_align_kf_job& I = in[s];
+    AlignKfJobDev& J = blob.at<AlignKfJobDev>(b_jobs)[s];
+    memset(&J, 0, sizeof(J));
+    J.active = I.active ? 1 : 0;
+    if (!J.active) continue;
+    J.ref_kf = I.ref_kf; J.self_kf = I.ref_kf == PLSVO_ALIGN_REF_CLOSEST ? I.self_kf : -1; J.init_source = I.init_source; J.cur_slot = I.cur_slot;
+    memcpy(J.T_init, I.T_init, sizeof(J.T_init)); J.d_T_init = I.init_source == PLSVO_ALIGN_INIT_DEV ? I.d_T_init : nullptr;
+    if (I.ref_kf == PLSVO_ALIGN_REF_CLOSEST) { memcpy(J.T_last, I.T_last, sizeof(J.T_last)); J.d_T_last = I.last_source == PLSVO_INSERT_POSE_DEV ? I.d_T_last : nullptr; }
   }
-  AlignBatchDev& a = c->a_b;
-  a.jobs = b.a_jobs; a.state = c->a_d_state.as<AlignStateDev>(); a.T0 = b.T0;
-  a.pt_px = b.pt_px; a.pt_xyz = b.pt_xyz; a.seg_spx = b.seg_spx; a.seg_epx = b.seg_epx; a.seg_len = b.seg_len; a.seg_p = b.seg_p; a.seg_q = b.seg_q;
-  a.seg_alive_in = b.seg_alive_in; a.seg_alive = c->a_d_alive.as<uint8_t>();
-  a.patch_xyz = c->a_d_pxyz.as<double>(); a.patch_uvref = c->a_d_puv.as<float>(); a.cache_ref = c->a_d_cref.as<float>();
-  a.chi_terms = c->a_d_chi.as<float>(); a.chi_plane = (unsigned long long)(N * (size_t)g.cap_pts + 32) * 16;
-  a.seg_slot = b.seg_slot; a.slot_level0 = g.min_level; a.slot_stride = n * g.cap_seg;
-  a.poses = c->a_d_poses.as<double>();
-  a.pyr = c->pyr;
-  a.log = c->a_trace_cap > 0 ? c->a_d_log.as<plsvo_align_iterlog>() : nullptr;
-  a.log_cap = c->a_trace_cap;
-  a.n_jobs = n;
-  a.pair = 0; a.xseq0 = 0; a.xbuf = nullptr; a.work_key = nullptr; a.tail_n = 0; a.static_solve = 1; a.tail_flag = nullptr; a.seg_alive_tail = nullptr;   // (plsvo_align_run decides)
-  a.order = order;
-  c->a_stage_order = order;
-  c->a_patch_total = std::max(N * (size_t)patch_cap, (size_t)4);
-  c->a_n = n; c->a_total_seg = n * g.cap_seg; c->a_gmax = g.max_level; c->a_gmin = g.min_level;
-  for (int l = 0; l < PLSVO_MAX_LEVELS; ++l) c->a_cap[l] = (l >= g.min_level && l <= g.max_level) ? patch_cap : 0;
-  c->a_scap = std::max(4, g.cap_seg);
-  c->a_seg_align = seg_align;
-  c->a_staged = true; c->a_run_seq = 0;
-  c->aj_built = true; c->aj_composed = false;
-  return PLSVO_OK;
+  int rc;
+  if ((rc = align_job_work(c, N, g))) return rc;
+  HIP_TRY(c, c->aj_d_order.ensure(N * sizeof(int)));
+  if ((rc = upload_blob(c, c->aj_d_kf_in, blob))) return rc;
+  const int cus = c->cu_count > 0 ? c->cu_count : 256;
+  const int seg_align = (2 * n <= cus) ? 64 : 32;   // as plsvo_candidates_align_build lays out: the two compose on one batch
+  AlignKfBatchDev k{};
+  k.a = c->aj_b;
+  k.a.s = SelectBatchDev{}; k.a.s.c = c->cd_b;      // the tables alone: no selection is read
+  k.a.seg_align = seg_align; k.a.ldlt_flavour = c->ldlt_flavour;
+  k.jobs = Blob::dev<AlignKfJobDev>(c->aj_d_kf_in, b_jobs);
+  k.keypts = c->ck_live ? c->ck_d_keypts.as<int>() : nullptr;
+  k.seg_obs = c->aj_seg_obs;
+  c->a_staged = false; c->aj_built = false;
+  c->ch_staged = false;                             // (as plsvo_candidates_align_build)
+  HIP_TRY_TIMED(c, PLSVO_K_ALIGN_INIT, launch_map_align_kf_job(k, c->stream));
+  for (int s = 0; s < n; ++s) {
+    const plsvo_cand_align_kf_job& I = in[s];
+    if (!I.active) continue;
+    const CandMapDev& M = c->cd_maps[(size_t)s];
+    const int* slot = c->cd_kf_slot.data() + M.kf_off;
+    std::vector<int>& may = c->aj_kf_slots[(size_t)s];
+    may.clear();
+    if (I.ref_kf == PLSVO_ALIGN_REF_CLOSEST) may.assign(slot, slot + M.n_kf);   // the device picks the row: the launch may read any of them
+    c->aj_slots[2 * (size_t)s] = I.ref_kf == PLSVO_ALIGN_REF_CLOSEST ? I.cur_slot : slot[I.ref_kf]; c->aj_slots[2 * (size_t)s + 1] = I.cur_slot;
+  }
+  return align_job_adopt(c, k.a, n, seg_align);
 }
 
 extern "C" int plsvo_candidates_align_compose(plsvo_ctx* c) {
@@ -1612,6 +1693,87 @@ extern "C" int plsvo_candidates_align_fetch_job(plsvo_ctx* c, int stream, plsvo_
   if (O->seg_code) for (size_t l = 0; l < nl; ++l) cp(O->seg_code + l * ns, r_code[l], ks, sizeof(int));
   return PLSVO_OK;
 }
+
+// ---- the tracking gates behind the pose optimisation (alignjob_device.hpp map_track_gate_kernel) ------------------------------
+namespace {
+// the sections of tg_d_out: the records, the carried poses, num_obs_last_pt / _ls
+struct GateSections { size_t out, carried, last, end; };
+static GateSections gate_sections(size_t n) {
+  Carver w; GateSections o;
+  o.out = w.take<TrackGateOutDev>(n); o.carried = w.take<double>(n * 7); o.last = w.take<int>(n * 2); o.end = w.off;
+  return o;
+}
+}  // namespace
+
+extern "C" int plsvo_candidates_track_gate(plsvo_ctx* c, int n, const plsvo_cand_gate* in) {
+  CTX_CHECK(c);
+  if (!c->cd_staged || !c->cd_ran || !c->cs_selected || !c->cs_posed) return fail(c, PLSVO_E_STATE, "candidates_track_gate: no resident pose optimisation on the last run");
+  if (const int rc = cand_seeds_pending(c, "candidates_track_gate")) return rc;
+  if (n != c->cd_n || (n > 0 && !in)) return fail(c, PLSVO_E_INVALID, "candidates_track_gate: n does not match the staged batch");
+  const bool have = c->tg_have && c->tg_n == n;   // (tg_have is cleared by every stage and n is the staged count: `have` means a gate since THIS stage)
+  bool resident = false;
+  for (int s = 0; s < n; ++s) {
+    const plsvo_cand_gate& I = in[s];
+    if (!I.active) continue;
+    if (I.mode != PLSVO_GATE_TRACK && I.mode != PLSVO_GATE_RELOC) return fail(c, PLSVO_E_INVALID, "candidates_track_gate: unknown mode");
+    if (I.last_source != PLSVO_GATE_LAST_HOST && I.last_source != PLSVO_GATE_LAST_RESIDENT) return fail(c, PLSVO_E_INVALID, "candidates_track_gate: unknown source of num_obs_last");
+    if ((I.reset_source != PLSVO_INSERT_POSE_HOST && I.reset_source != PLSVO_INSERT_POSE_DEV) || (I.reset_source == PLSVO_INSERT_POSE_DEV && !I.d_T_reset))
+      return fail(c, PLSVO_E_INVALID, "candidates_track_gate: bad pose source");
+    if (I.quality_min_fts < 0 || I.quality_max_drop_fts < 0 || I.max_fts < 0 || I.max_fts_segs < 0 ||
+        (I.last_source == PLSVO_GATE_LAST_HOST && (I.num_obs_last_pt < 0 || I.num_obs_last_ls < 0)))
+      return fail(c, PLSVO_E_INVALID, "candidates_track_gate: negative threshold, clamp or count");
+    resident = resident || I.last_source == PLSVO_GATE_LAST_RESIDENT;
+  }
+  if (resident && !have) return fail(c, PLSVO_E_STATE, "candidates_track_gate: no resident num_obs_last (no gate since the stage)");
+  if (n == 0) { c->tg_have = true; c->tg_n = 0; return PLSVO_OK; }
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t N = (size_t)n;
+  Blob blob;
+  const size_t b_jobs = blob.reserve<TrackGateJobDev>(N);
+  for (int s = 0; s < n; ++s) {
+    const plsvo_cand_gate& I = in[s];
+    TrackGateJobDev& J = blob.at<TrackGateJobDev>(b_jobs)[s];
+    memset(&J, 0, sizeof(J));
+    J.active = I.active ? 1 : 0;
+    if (!J.active) continue;
+    memcpy(J.T_reset, I.T_reset, sizeof(J.T_reset)); J.d_T_reset = I.reset_source == PLSVO_INSERT_POSE_DEV ? I.d_T_reset : nullptr;
+    J.mode = I.mode; J.quality_min_fts = I.quality_min_fts; J.quality_max_drop_fts = I.quality_max_drop_fts; J.max_fts = I.max_fts; J.max_fts_segs = I.max_fts_segs;
+    J.last_resident = I.last_source == PLSVO_GATE_LAST_RESIDENT ? 1 : 0; J.num_obs_last_pt = I.num_obs_last_pt; J.num_obs_last_ls = I.num_obs_last_ls;
+  }
+  int rc;
+  if ((rc = upload_blob(c, c->tg_d_in, blob))) return rc;
+  const GateSections o = gate_sections(N);
+  if (!have) {                                      // the first gate behind a stage: a stream that sits it out reads as zeros
+    c->tg_have = false;
+    HIP_TRY(c, c->tg_d_out.ensure(o.end + 256));
+    HIP_TRY(c, hipMemsetAsync(c->tg_d_out.p, 0, o.end, c->stream));
+  }
+  TrackGateBatchDev b{};
+  b.jobs = Blob::dev<TrackGateJobDev>(c->tg_d_in, b_jobs); b.out = Carver::dev<TrackGateOutDev>(c->tg_d_out, o.out);
+  b.scalars = c->cs_b.scalars; b.state = c->cs_w.state.as<PoseStateDev>(); b.poses = c->cs_w.poses.as<double>();
+  b.carried = Carver::dev<double>(c->tg_d_out, o.carried); b.obs_last = Carver::dev<int>(c->tg_d_out, o.last); b.n_jobs = n;
+  HIP_TRY_TIMED(c, PLSVO_K_KEYFRAME, launch_map_track_gate(b, c->stream));
+  c->tg_b = b; c->tg_have = true; c->tg_n = n;
+  return PLSVO_OK;
+}
+
+extern "C" int plsvo_candidates_gate_fetch(plsvo_ctx* c, int n, plsvo_cand_gate_out* out, double* poses) {
+  CTX_CHECK(c);
+  if (!c->cd_staged || !c->tg_have || c->tg_n != c->cd_n) return fail(c, PLSVO_E_STATE, "candidates_gate_fetch: no gate since the stage");
+  if (n != c->cd_n || (n > 0 && !out)) return fail(c, PLSVO_E_INVALID, "candidates_gate_fetch: n does not match the staged batch");
+  if (n == 0) return PLSVO_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  static_assert(sizeof(TrackGateOutDev) == sizeof(plsvo_cand_gate_out) && sizeof(plsvo_cand_gate_out) == 32, "the device's record is the public one");
+  Readback rb;
+  const int r_out = rb.add(c->tg_b.out, (size_t)n * sizeof(TrackGateOutDev));
+  const int r_T = poses ? rb.add(c->tg_b.carried, (size_t)n * 7 * sizeof(double)) : -1;
+  if (const int rc = rb.wait(c)) return rc;
+  memcpy(out, rb.at<TrackGateOutDev>(r_out), (size_t)n * sizeof(TrackGateOutDev));
+  if (poses) memcpy(poses, rb.at<double>(r_T), (size_t)n * 7 * sizeof(double));
+  return PLSVO_OK;
+}
+
+extern "C" const double* plsvo_candidates_gate_poses_dev(plsvo_ctx* c) { return (c && c->cd_staged && c->tg_have && c->tg_n == c->cd_n && c->tg_n > 0) ? c->tg_b.carried : nullptr; }
 
 // ---- depth-filter seed lists resident beside the map tables (seedlist_device.hpp) -------------------------------------------
 namespace {

@@ -41,6 +41,8 @@ hipError_t launch_map_close(const KeyStageBatchDev& b, hipStream_t stream);
 hipError_t launch_map_keyframe_decide(const KeyDecideBatchDev& b, hipStream_t stream);
 hipError_t launch_map_align_job(const AlignBuildBatchDev& b, hipStream_t stream);      // alignjob_device.hpp, in seeds_kernels.hip
 hipError_t launch_map_align_pose(const AlignPoseBatchDev& b, hipStream_t stream);
+hipError_t launch_map_align_kf_job(const AlignKfBatchDev& b, hipStream_t stream);
+hipError_t launch_map_track_gate(const TrackGateBatchDev& b, hipStream_t stream);
 hipError_t launch_update_seeds_resident(const SeedListBatchDev& b, hipStream_t stream);   // seedlist_device.hpp, in seeds_kernels.hip
 hipError_t launch_seeds_commit(const SeedListBatchDev& b, hipStream_t stream);
 hipError_t launch_seeds_keyframe(const SeedListBatchDev& b, hipStream_t stream);
@@ -288,6 +290,16 @@ struct plsvo_ctx {
   DevBuf aj_d_batch, aj_d_in, aj_d_out, aj_d_order;   // (aj_d_order: the build's own launch order, which no later launch's re-ordering writes)
   AlignBuildBatchDev aj_b{};              // the batch's sections (the selection, the records and the key are bound per call)
   AlignPoseBatchDev aj_pose{};
+  int* aj_seg_obs = nullptr;              // a keyframe build's scratch inside aj_d_batch: cap_seg observation indices per stream
+  std::vector<std::vector<int>> aj_kf_slots;   // per stream built against its CLOSEST keyframe: every keyframe slot it may have picked (the tiled mirror's upkeep)
+  DevBuf aj_d_kf_in;                      // a keyframe build's records
+  // the tracking gates behind the pose optimisation (plsvo_candidates_track_gate ..): a call's records (tg_d_in); the gate records, the
+  // carried poses and num_obs_last_pt / _ls per stream (tg_d_out: zeroed at the first gate behind a stage, a stream that sits a call
+  // out keeps its rows), the stream count they were laid out for, whether there is a gate since the stage
+  bool tg_have = false;
+  int tg_n = 0;
+  DevBuf tg_d_in, tg_d_out;
+  TrackGateBatchDev tg_b{};
   // resident seed lists (plsvo_seeds_*): the room plsvo_seeds_reserve asks for (the next stage's), per stream the host mirror of its
   // record (sd_host: list lengths, upper bounds between a keyframe event and the next update fetch) and the rows it may fill (sd_lim);
   // the tables (sd_d_tab: records, workgroup map, rows), shadow rows and reports (sd_d_work), a call's upload (sd_d_in).  A candidate

@@ -125,6 +125,22 @@ __global__ __launch_bounds__(64 * kKsWaves) void map_keypts_kernel(const KeyStag
   }
 }
 
+// Map::getCloseKeyframes (src/map.cpp:158-179), one keyframe row of the stream: is one of its key points' landmarks visible at its
+// position NOW from the frame at T, and then the distance between the two (map_close_kernel; the closest keyframe of alignjob_device.hpp)
+__device__ __forceinline__ bool ks_close(const KsView& V, const int* kp, const double* kf_T, const SE3d& T, const CamDev& cam, int i, double* dist) {
+  const int f0 = V.kf_off[i], n_ftr = V.kf_off[i + 1] - f0;
+  bool close = false;
+  for (int k = 0; k < 5 && !close; ++k) {
+    const int h = kp[5 * i + k];
+    if (h < 0 || h >= n_ftr) continue;
+    const int lm = V.kf_lm[f0 + h];
+    if (lm < 0) continue;                           // (the upkeep leaves no such holder)
+    close = kf_visible(T, cam, V.pt_pos + 3 * lm);
+  }
+  *dist = close ? kf_translation_dist(T, kf_T + 7 * i) : -1.0;
+  return close;
+}
+
 __global__ __launch_bounds__(64 * kKsWaves) void map_close_kernel(const KeyStageBatchDev b) {
   const int lane = threadIdx.x & 63;
   const int job = blockIdx.x * kKsWaves + (int)(threadIdx.x >> 6);
@@ -145,15 +161,9 @@ __global__ __launch_bounds__(64 * kKsWaves) void map_close_kernel(const KeyStage
     const int i = base + lane;
     bool close = false;
     if (i < n_kf) {
-      const int f0 = V.kf_off[i], n_ftr = V.kf_off[i + 1] - f0;
-      for (int k = 0; k < 5 && !close; ++k) {
-        const int h = kp[5 * i + k];
-        if (h < 0 || h >= n_ftr) continue;
-        const int lm = V.kf_lm[f0 + h];
-        if (lm < 0) continue;                       // (the upkeep leaves no such holder)
-        close = kf_visible(T, cam, V.pt_pos + 3 * lm);
-      }
-      tmp[i] = close ? kf_translation_dist(T, kf_T + 7 * i) : -1.0;
+      double d;
+      close = ks_close(V, kp, kf_T, T, cam, i, &d);
+      tmp[i] = d;
     }
     n_close += __popcll(__ballot(close));
   }

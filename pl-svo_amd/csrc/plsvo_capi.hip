@@ -113,7 +113,7 @@ extern "C" void plsvo_hip_destroy(plsvo_ctx* c) {
   for (auto& ep : c->ev_pool) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
   c->a_d_tailflag.release(); c->a_d_alive_tail.release(); c->a_d_xbuf.release(); c->a_order.release(); c->p_order.release();
   c->p_d_carry.release(); c->p_d_refill_next.release();
-  c->aj_d_batch.release(); c->aj_d_in.release(); c->aj_d_out.release(); c->aj_d_order.release();
+  c->aj_d_batch.release(); c->aj_d_in.release(); c->aj_d_out.release(); c->aj_d_order.release(); c->tg_d_in.release(); c->tg_d_out.release(); c->aj_d_kf_in.release();
   for (DevBuf* b : { &c->cd_d_blob, &c->cd_d_work, &c->cd_d_run, &c->cd_d_kfcount, &c->ck_d_keypts, &c->ck_d_in, &c->ck_d_upkeep, &c->ck_d_work, &c->ck_d_dec_in, &c->ck_d_dec,&c->ci_d_work, &c->ci_d_in, &c->ci_d_plan, &c->ci_d_pos, &c->co_d_key, &c->co_d_in, &c->co_d_rep, &c->cn_d_in, &c->cc_d_in, &c->cc_d_work, &c->sd_d_tab, &c->sd_d_work, &c->sd_d_in, &c->cs_d_q,
                      &c->cs_d_work, &c->cs_d_order, &c->pyr_slab, &c->pyr_tiled, &c->pyr_upload, &c->a_d_blob, &c->a_d_state, &c->a_d_alive, &c->a_d_pxyz, &c->a_d_puv,
                      &c->a_d_cref, &c->a_d_chi, &c->a_d_log, &c->a_d_poses, &c->p_d_blob, &c->p_d_log, &c->s_d_in, &c->s_d_out, &c->ch_d_blob, &c->ch_d_work,
@@ -971,6 +971,7 @@ extern "C" int plsvo_align_run(plsvo_ctx* c) {
     std::vector<int> slots;
     slots.reserve(2 * c->a_jobs.size());
     for (const AlignJobDev& J : c->a_jobs) { slots.push_back(J.ref_slot); slots.push_back(J.cur_slot); }
+    if (c->aj_built) for (const std::vector<int>& v : c->aj_kf_slots) slots.insert(slots.end(), v.begin(), v.end());   // (a reference keyframe picked on the device)
     const int rc_t = retile_stale(c, slots); if (rc_t) return rc_t;
   }
   // TWO WORKGROUPS PER FRAME: a frame that has a CU to itself is bound by that CU's instruction issue (two 64-slot wave-rounds per SIMD per

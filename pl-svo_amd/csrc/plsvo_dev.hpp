@@ -524,6 +524,52 @@ struct AlignPoseBatchDev {          // map_align_pose_kernel: T_f_w(new) = T_cur
   const double* align_poses; const double* T_ref; double* out; int n_jobs;
 };
 
+// the alignment job from a RESIDENT KEYFRAME as the reference frame (alignjob_device.hpp map_align_kf_job_kernel, include/plsvo_hip.h
+// plsvo_candidates_align_build_kf): the same resident alignment batch, one stream's rows per wave
+constexpr int kAlignJobNoKeyframe = 2;                // AlignBuildReportDev::status (PLSVO_ALIGN_JOB_NO_KEYFRAME)
+constexpr int kAlignRefClosest = -1;                  // AlignKfJobDev::ref_kf (PLSVO_ALIGN_REF_CLOSEST)
+constexpr int kAlignInitHost = 0, kAlignInitDev = 1, kAlignInitKeyframe = 2;   // AlignKfJobDev::init_source (PLSVO_ALIGN_INIT_*)
+struct AlignKfJobDev {              // one stream's record: 152 bytes
+  double T_init[7];                 // the frame's initial T_f_w (kAlignInitHost; kAlignInitKeyframe without a keyframe)
+  double T_last[7];                 // last_frame_->T_f_w_, the frame Map::getClosestKeyframe looks from (kAlignRefClosest)
+  const double* d_T_init;           // device pointers read instead (kAlignInitDev; T_last: whenever non-null)
+  const double* d_T_last;
+  int active, ref_kf, self_kf, init_source, cur_slot, reserved0;
+};
+struct AlignKfBatchDev {
+  AlignBuildBatchDev a;             // the tables (a.s.c) and the resident alignment batch; the selection's rows are not read
+  const AlignKfJobDev* jobs;
+  const int* keypts;                // the live key-point table, 5 per keyframe row of capacity (kAlignRefClosest), or null
+  int* seg_obs;                     // scratch, cap_seg per stream: per segment feature of the keyframe its observation's index, -1 dead
+};
+
+// the tracking gates of FrameHandlerMono::processFrame on the resident selection and pose optimisation (alignjob_device.hpp
+// map_track_gate_kernel, include/plsvo_hip.h plsvo_candidates_track_gate): a lane per stream
+constexpr int kGateTrack = 0, kGateReloc = 1;                       // TrackGateJobDev::mode (PLSVO_GATE_TRACK / _RELOC)
+constexpr int kGateOk = 0, kGateFailMatches = 1, kGateFailEdges = 2;   // TrackGateOutDev::result (PLSVO_GATE_*)
+constexpr int kTrackInsufficient = 0, kTrackBad = 1, kTrackGood = 2;   // TrackGateOutDev::quality: FrameHandlerBase::TrackingQuality, in its order
+struct TrackGateJobDev {            // one stream's record: 104 bytes
+  double T_reset[7];                // last_frame_->T_f_w_ (the last well localised pose under kGateReloc)
+  const double* d_T_reset;          // device pointer read instead of T_reset, or null
+  int active, mode;                 // 0: the stream's record, carried pose and counts are left as they are
+  int quality_min_fts, quality_max_drop_fts, max_fts, max_fts_segs;
+  int last_resident;                // non-zero: num_obs_last_pt / _ls are the resident ones (this stream's last active call)
+  int num_obs_last_pt, num_obs_last_ls, reserved0;
+};
+struct TrackGateOutDev {            // plsvo_cand_gate_out, field for field: 32 bytes
+  int result, quality, n_matched, n_edges, drop_pt, drop_ls;
+  int num_obs_last_pt, num_obs_last_ls;   // the counts the drops were taken against
+};
+struct TrackGateBatchDev {
+  const TrackGateJobDev* jobs; TrackGateOutDev* out;
+  const int* scalars;               // the selection's, 3 per stream: n_matches, n_ls_matches, n_trials
+  const PoseStateDev* state;        // the pose optimiser's record per stream (num_obs_pt, num_obs_ls)
+  const double* poses;              // 7 per stream: the optimised T_f_w
+  double* carried;                  // 7 per stream: the pose carried forward
+  int* obs_last;                    // 2 per stream: num_obs_last_pt, num_obs_last_ls
+  int n_jobs, reserved0;
+};
+
 // corner detection (detect_device.hpp, include/plsvo_hip.h plsvo_hip_detect_fast): tile geometry and the launch record
 constexpr int kDetTileW = 64, kDetTileH = 32;          // pixels of a tile that one workgroup decides
 constexpr int kDetImgX0 = 8, kDetImgY0 = 5;            // LDS image origin = tile origin - (8, 5): a halo of 5 (Shi-Tomasi: x - 5 .. x + 4), 8 keeps rows dword-aligned

@@ -563,5 +563,16 @@ hipError_t launch_map_align_pose(const AlignPoseBatchDev& b, hipStream_t stream)
   hipLaunchKernelGGL(map_align_pose_kernel, dim3((b.n_jobs + 63) / 64), dim3(64), 0, stream, b);
   return hipGetLastError();
 }
+hipError_t launch_map_align_kf_job(const AlignKfBatchDev& b, hipStream_t stream) {
+  if (b.a.s.c.n_jobs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_align_kf_job_kernel, dim3((b.a.s.c.n_jobs + kAjWaves - 1) / kAjWaves), dim3(64 * kAjWaves), 0, stream, b);
+  return hipGetLastError();
+}
+// the tracking gates behind the pose optimisation (alignjob_device.hpp): a lane per stream
+hipError_t launch_map_track_gate(const TrackGateBatchDev& b, hipStream_t stream) {
+  if (b.n_jobs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(map_track_gate_kernel, dim3((b.n_jobs + 63) / 64), dim3(64), 0, stream, b);
+  return hipGetLastError();
+}
 
 }  // namespace plsvo_hip

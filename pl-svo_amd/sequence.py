@@ -59,6 +59,10 @@ optimised one; the first frame, and a frame behind one whose tables wait for a r
 pose fetch, no host arithmetic ahead of the alignment) and hands the composed pose on by device pointer; "host" restates the same job here
 in scalar float64 and stages it through plsvo_align_stage, so the two differ in transport alone and agree in every record.
 
+With relocalize="host" | "device" (align and keystage) the harness plays the reference's stage machine: the gates of
+processFrame stand behind every frame's pose optimisation, a frame that fails them is carried forward with the pose the gate gives and
+the next frame relocalises against the closest keyframe of the resident tables (relocalizeFrame) until a frame passes the gates again.
+
 `backend` is duck-typed: load_frames(list of level-0 images; HipBackend also takes raw frames with rectify=), sparse_align(job), reproject(job), match_direct(job),
 pose_optimize(job), for mapping structure_optimize(job), update_seeds(job), and for kf_select close_keyframes(job), keyframe_decide(job).  The product backend is HipBackend (C ABI on the GPU, no fallback); tests pass an oracle-backed one
 to check the whole chain end to end."""
@@ -178,6 +182,39 @@ class HipBackend:
         if self.ctx.candidates_align_fetch()[0]["status"] != abi.ALIGN_JOB_OK:
             raise RuntimeError("align_built: the stream did not fit the reserved alignment batch (plsvo_candidates_align_reserve)")
         return ar, self.ctx.candidates_align_fetch_job(0)["T_f_w"], self.ctx.candidates_align_poses_dev()
+
+    def align_kf(self, ref_kf, cur_slot, T_init, max_level, min_level, cap_pts, cap_seg, slot_cap=2048, T_last=None, last_dev=None):
+        """the alignment against keyframe row ref_kf of the resident tables (plsvo_candidates_align_build_kf), run and
+        composed.  ref_kf None: the closest keyframe, picked on the device from T_last (or the device pointer last_dev) on the live
+        key-point table; T_init None: the keyframe's own pose.
+        -> (the alignment's result or None without a keyframe, the row, the composed T_f_w as a host copy, its device pointer)"""
+        if not getattr(self, "_align_reserved", False):
+            self.ctx.candidates_align_reserve(max_level, min_level, cap_pts, cap_seg, slot_cap)
+            self._align_reserved = True
+        j = dict(ref_kf=ref_kf, cur_slot=cur_slot, T_init=T_init)
+        if ref_kf is None:
+            j.update(last_dev=last_dev) if last_dev else j.update(T_last=T_last)
+        self.ctx.candidates_align_build_kf([j])
+        self.ctx.align_run()
+        self.ctx.candidates_align_compose()
+        ar = self.ctx.align_fetch()[0]
+        rep = self.ctx.candidates_align_fetch()[0]
+        if rep["status"] == abi.ALIGN_JOB_NO_KEYFRAME:
+            return None, -1, None, None
+        if rep["status"] != abi.ALIGN_JOB_OK:
+            raise RuntimeError("align_kf: the keyframe did not fit the reserved alignment batch (plsvo_candidates_align_reserve)")
+        return ar, rep["ref_kf"], self.ctx.candidates_align_fetch_job(0)["T_f_w"], self.ctx.candidates_align_poses_dev()
+
+    def track_gate(self, **job):
+        """the gates of processFrame behind the last map_select, on the device (plsvo_candidates_track_gate).
+        -> (the 32-byte record, the pose carried forward as a host copy, its device pointer)"""
+        self.ctx.candidates_track_gate([job])
+        recs, T = self.ctx.candidates_gate_fetch(poses=True)
+        return recs[0], T[0].copy(), self.ctx.candidates_gate_poses_dev()
+
+    def map_fetch(self):
+        """the resident tables as they stand (plsvo_candidates_fetch_map)"""
+        return self.ctx.candidates_fetch_map()[0]
 
     def map_set_keypts(self, key_pts=None):
         """Frame::key_pts_ of the staged keyframes as a resident table (plsvo_candidates_set_keypts, DESIGN.md 3.19): [n_kf, 5] positions in
@@ -387,6 +424,65 @@ def align_job_host(cam, max_level, min_level, sel, pt_keep, seg_keep, pt_type, s
                         arr(p_ref, 3), arr(q_ref, 3), np.array(alive, np.uint8), ref_slot=ref_slot, cur_slot=cur_slot)
 
 
+def align_kf_job_host(cam, max_level, min_level, t, ref_kf, T_init, cur_slot):
+    """The alignment job plsvo_candidates_align_build_kf writes on the device from keyframe row ref_kf, assembled on the host from one
+    stream's fetched tables (capi.Context.candidates_fetch_map) in scalar float64 with the device's operation order (the
+    slot layout is plsvo_align_stage's): the keyframe's point features that hold a landmark which is not TYPE_DELETED and has an
+    observation in this keyframe -- the first one: its px and its STORED bearing -- closed up; ALL its segment features, a dead one
+    zeroed; T0 = T_init * T_kf^-1 (T_init None: the keyframe's own pose).  The path the device build replaces.  -> abi.AlignJob"""
+    T_ref = [float(v) for v in np.asarray(t["kf_T"], float).reshape(-1, 7)[ref_kf]]
+    T_inv = _se3_inv_s(T_ref)
+    ref = T_inv[4:]
+
+    def first_obs(kind, lm, types):
+        if lm < 0 or int(types[lm]) == abi.LM_DELETED:
+            return -1
+        off, kf = t[kind + "_obs_off"], t[kind + "_obs_kf"]
+        return next((o for o in range(int(off[lm]), int(off[lm + 1])) if int(kf[o]) == ref_kf), -1)
+
+    def scaled(f, pos):
+        dx, dy, dz = float(pos[0]) - ref[0], float(pos[1]) - ref[1], float(pos[2]) - ref[2]
+        d = math.sqrt(dx * dx + dy * dy + dz * dz)
+        return [float(f[0]) * d, float(f[1]) * d, float(f[2]) * d]
+    rows = lambda f, w: np.asarray(t[f], float).reshape(-1, w)
+    pt_pos, obs_px, obs_f = rows("pt_pos", 3), rows("pt_obs_px", 2), rows("pt_obs_f", 3)
+    px, xyz = [], []
+    for i in range(int(t["kf_pt_off"][ref_kf]), int(t["kf_pt_off"][ref_kf + 1])):
+        lm = int(t["kf_pt_lm"][i])
+        o = first_obs("pt", lm, t["pt_type"])
+        if o >= 0:
+            px.append([float(v) for v in obs_px[o]]); xyz.append(scaled(obs_f[o], pt_pos[lm]))
+    s_spx, s_epx, s_sf, s_ef, spos, epos = rows("seg_obs_spx", 2), rows("seg_obs_epx", 2), rows("seg_obs_sf", 3), rows("seg_obs_ef", 3), rows("seg_spos", 3), rows("seg_epos", 3)
+    spx, epx, length, p_ref, q_ref, alive = [], [], [], [], [], []
+    for i in range(int(t["kf_seg_off"][ref_kf]), int(t["kf_seg_off"][ref_kf + 1])):
+        lm = int(t["kf_seg_lm"][i])
+        o = first_obs("seg", lm, t["seg_type"])
+        alive.append(int(o >= 0))
+        if o < 0:                                      # no pixels in the tables for a feature without a landmark: zeros
+            spx.append([0.0] * 2); epx.append([0.0] * 2); length.append(0.0); p_ref.append([0.0] * 3); q_ref.append([0.0] * 3)
+            continue
+        a, b = [float(v) for v in s_spx[o]], [float(v) for v in s_epx[o]]
+        dx, dy = b[0] - a[0], b[1] - a[1]
+        spx.append(a); epx.append(b); length.append(math.sqrt(dx * dx + dy * dy))
+        p_ref.append(scaled(s_sf[o], spos[lm])); q_ref.append(scaled(s_ef[o], epos[lm]))
+    arr = lambda v, cols: np.array(v, float).reshape(-1, cols)
+    return abi.AlignJob(cam, max_level, min_level, 30, 1e-6, _se3_mul_s(T_ref if T_init is None else T_init, T_inv), arr(px, 2), arr(xyz, 3), arr(spx, 2), arr(epx, 2),
+                        np.array(length, float), arr(p_ref, 3), arr(q_ref, 3), np.array(alive, np.uint8), ref_slot=int(t["kf_slot"][ref_kf]), cur_slot=cur_slot)
+
+
+def track_gate_host(n_matches, n_ls_matches, num_obs_pt, num_obs_ls, num_obs_last_pt, num_obs_last_ls, relocalizing=False, quality_min_fts=20, quality_max_drop_fts=50,
+                    max_fts=100, max_fts_segs=100):
+    """The comparisons plsvo_candidates_track_gate makes on the device, on fetched counts (the selection's n_matches / n_ls_matches, the
+    pose optimisation's num_obs): src/frame_handler_mono.cpp:315-321, :335, FrameHandlerBase::setTrackingQuality.  -> (result
+    abi.GATE_*, tracking quality abi.TRACKING_*, whether the frame's pose is reset to the last one)"""
+    if n_matches + n_ls_matches < quality_min_fts:
+        return abi.GATE_FAIL_MATCHES, abi.TRACKING_INSUFFICIENT, True
+    if num_obs_pt + num_obs_ls < 10:
+        return abi.GATE_FAIL_EDGES, abi.TRACKING_INSUFFICIENT, bool(relocalizing)
+    bad = num_obs_pt + num_obs_ls < quality_min_fts or min(num_obs_last_pt, max_fts) - num_obs_pt > quality_max_drop_fts
+    return abi.GATE_OK, abi.TRACKING_BAD if bad else abi.TRACKING_GOOD, False
+
+
 def seeds_from_corners(corners, cam, depth_mean, depth_min):
     """Point seeds for detected corners (abi.CORNER_DTYPE records), as DepthFilter::initializeSeeds creates them
     (src/depth_filter.cpp:161-172): a feature `new PointFeat(frame, px, level)` -- f = cam2world(px), type CORNER, grad (1, 0) -- in a
@@ -487,7 +583,8 @@ def _key_point_upkeep(cm, tab, cam, fresh=()):
 def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_thresh=2.0, mapping=False, known_frac=0.6,
                  pos_noise=0.005, map_seed=0, kf_every=5, detect=False, detect_cell_size=25, kf_select=False, kfselect_mindist_t=0.06,
                  kfselect_mindist_r=3.0, max_n_kfs=10, map_candidates=False, record_candidates=False, cell_select=False, select_params=None, kf_insert=False,
-                 seed_candidates=False, seeds_resident=False, image_seeds=None, image_seed_params=None, structopt_resident=False, compact=None, lm_room=None, keystage=None, align=None):
+                 seed_candidates=False, seeds_resident=False, image_seeds=None, image_seed_params=None, structopt_resident=False, compact=None, lm_room=None, keystage=None, align=None,
+                 relocalize=None, reloc_params=None):
     """-> list of per-frame dicts (pose T_f_w, cov, counts).  Frame 0 is the keyframe with the true pose.
     mapping=True: only `known_frac` of the point landmarks start in the map (positions off by `pos_noise` x depth along
     their viewing ray), the others are depth-filter seeds; the seed update runs every frame; every `kf_every`-th frame
@@ -569,8 +666,24 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
     pointer into the candidate stage; "host" restates the same job (align_job_host) and stages it as before.  The first frame's job
     is gathered from keyframe 0 as without the flag, and so is the job of a frame behind one that left the tables waiting for a restage
     (a keyframe without kf_insert, a converged seed without seed_candidates): the resident tables are then behind the harness's own.
-    The two agree in every record."""
+    The two agree in every record.
+    relocalize="host" | "device" (with align and keystage; default None: every record is what it is without it): the harness plays the
+    reference's stage machine, STAGE_DEFAULT_FRAME <-> STAGE_RELOCALIZING (finishFrameProcessingCommon).  Behind the pose optimisation of
+    every frame stand the gates of processFrame (src/frame_handler_mono.cpp:315-321, :335, setTrackingQuality): a frame that fails is not
+    structure-optimised, decided, inserted or fed to the depth filter, its pose is the one the gate carries, and the next frame
+    relocalises (relocalizeFrame :408-436): Map::getClosestKeyframe from the last frame's pose, a gating alignment against that keyframe
+    from the identity that must track more than 30, a second alignment from the keyframe's own pose, and the rest of processFrame, whose
+    every failure carries the last frame's pose; a success returns to STAGE_DEFAULT_FRAME.  TRACKING_BAD keeps a frame from becoming a
+    keyframe.  "device" uses plsvo_candidates_align_build_kf and plsvo_candidates_track_gate (a backend with align_kf /
+    track_gate); "host" does the same with the calls there were before -- fetched tables, close_keyframes, align_kf_job_host staged
+    through plsvo_align_stage, track_gate_host on the fetched counts.  The two differ in transport alone and agree in every record.  The
+    two host waits of "device": the gate's record ahead of the structure optimisation, and n_tracked behind the gating alignment.
+    reloc_params: quality_min_fts (20), quality_max_drop_fts (50); the clamps are the selection's max_fts / max_fts_segs.  The records
+    gain stage (the stage the frame was processed in), gate, tracking_quality and, in a relocalising frame, reloc_kf / reloc_tracked.
+    The tables must not wait for a restage while a stream relocalises (kf_insert with seed_candidates keeps them resident)."""
     params = dict(locals())                            # (first statement: exactly the arguments)
+    if relocalize not in (None, "host", "device") or (relocalize and not (align and keystage and (relocalize == "host" or (keystage == "device" and hasattr(backend, "align_kf"))))):
+        raise ValueError("relocalize is None, 'host' or 'device' and needs align, keystage and, for 'device', keystage='device' (the live key-point table) and a backend with align_kf() / track_gate()")
     if align not in (None, "host", "device") or (align and not (map_candidates and cell_select and (align == "host" or hasattr(backend, "align_build")))):
         raise ValueError("align is None, 'host' or 'device' and needs map_candidates, cell_select and, for 'device', a backend with align_build() / align_built()")
     if keystage not in (None, "host", "device") or (keystage and not (kf_select and cell_select and kf_insert and hasattr(backend, "map_keyframe_decide" if keystage == "device" else "keyframe_decide"))):
@@ -604,8 +717,12 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
 
 def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thresh, mapping, known_frac, pos_noise, map_seed, kf_every, detect, detect_cell_size, kf_select,
                   kfselect_mindist_t, kfselect_mindist_r, max_n_kfs, map_candidates, record_candidates, cell_select, select_params, kf_insert, seed_candidates, seeds_resident,
-                  image_seeds=None, image_seed_params=None, structopt_resident=False, compact=None, lm_room=None, keystage=None, align=None):
+                  image_seeds=None, image_seed_params=None, structopt_resident=False, compact=None, lm_room=None, keystage=None, align=None, relocalize=None, reloc_params=None):
     cam = seq["cam"]
+    stage, gate_dev, obs_last, obs_resident = "default", None, None, False   # relocalize: the stage, the gate's carried poses on the device, num_obs_last_pt / _ls and whether the device holds them
+    gate_kw = dict(quality_min_fts=20, quality_max_drop_fts=50)
+    gate_kw.update(reloc_params or {})
+    IDENT = [0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0]
     next_align = None                                  # align: the job of the frame to come -- an abi.AlignJob ("host") or True: built on the device
     kp_tab, kp_live = None, False                      # keystage: Frame::key_pts_ per keyframe row of cm ("host": kept here; "device": fetched when a restage needs it)
     img_kw = dict(fast_threshold=20, detection_threshold=20.0)
@@ -701,9 +818,54 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
         return align_job_host(cam, max_level, min_level, sel, pr.pt_keep, pr.seg_keep, cm["pt_type"], cm["seg_type"], cm["pt_pos"], cm["seg_spos"], cm["seg_epos"], pr.T, k, k + 1)
 
     for k in range(1, len(seq["images"])):
+        reloc_try, T_reset = bool(relocalize) and stage == "reloc", None
+        if reloc_try:
+            # ---- relocalizeFrame (:408-436): the closest keyframe from the last frame's pose, the gating alignment from the identity,
+            #      then processFrame with last_frame_ = ref_keyframe.  (last_frame_ is never a keyframe of the table here: self_kf -1)
+            if cm_dirty:
+                raise ValueError("relocalize: the resident tables wait for a restage")
+            caps = (max(select_kw["max_fts"] + 2, 8, max(len(l) for l in cm["kf_pt"])), max(select_kw["max_fts_segs"] + 2, 8, max(len(l) for l in cm["kf_seg"])))
+            fail = None
+            if relocalize == "device":
+                ar, ref_kf, T_gate, _ = backend.align_kf(None, k, IDENT, max_level, min_level, *caps, T_last=T_prev, last_dev=gate_dev)
+            else:
+                tabs = backend.map_fetch()
+                kp_now = kp_tab if keystage == "host" else backend.map_fetch_keypts()[:len(cm["kf_T"])]
+                n_kf_now = len(cm["kf_T"])
+                kpos, kval = np.zeros((n_kf_now, 5, 3)), np.zeros((n_kf_now, 5), np.uint8)
+                for j, row in enumerate(kp_now):
+                    for s_, h in enumerate(row):
+                        lm = int(tabs["kf_pt_lm"][int(tabs["kf_pt_off"][j]) + int(h)]) if 0 <= h < int(tabs["kf_pt_off"][j + 1]) - int(tabs["kf_pt_off"][j]) else -1
+                        if lm >= 0:
+                            kpos[j, s_], kval[j, s_] = tabs["pt_pos"][lm], 1
+                cl = backend.close_keyframes(abi.CloseKeyframesJob(cam, T_prev, np.asarray(tabs["kf_T"], float).reshape(-1, 7), kpos, kval, max_n_kfs))
+                ar, ref_kf, T_gate = None, -1, None
+                if cl["n_close"] > 0:                  # Map::getClosestKeyframe: the front of the sorted list
+                    ref_kf = int(cl["close_idx"][0])
+                    ar = backend.sparse_align(align_kf_job_host(cam, max_level, min_level, tabs, ref_kf, IDENT, k))
+                    T_gate = np.array(_se3_mul_s(ar.T, tabs["kf_T"][ref_kf]))
+            if ar is None:
+                fail, T_fail, n_tr = "no_keyframe", np.array(IDENT), 0           # "No reference keyframe": new_frame_ keeps its default pose
+            elif ar.n_tracked <= 30:
+                fail, T_fail, n_tr = "gating", np.asarray(T_gate, float).copy(), int(ar.n_tracked)   # (:421; the pose the alignment wrote stays)
+            if fail:
+                out.append(dict(T=T_fail, cov=np.full((6, 6), 1e-9), n_align=n_tr, n_matched_pt=0, n_matched_seg=0, n_kept_pt=0, n_kept_seg=0, stage="reloc",
+                                gate=fail, tracking_quality=abi.TRACKING_INSUFFICIENT, reloc_kf=ref_kf, reloc_tracked=n_tr))
+                if mapping:
+                    poses_est.append(T_fail.copy())
+                T_prev, gate_dev, obs_last, obs_resident, next_align = T_fail, None, (0, 0), False, None   # Frame::nObs() of a frame without features
+                continue
+            T_reset, reloc_kf, reloc_tracked = T_prev, ref_kf, int(ar.n_tracked)     # T_f_w_last
+            T_ref_kf = np.array(cm["kf_T"][ref_kf], float)
+            if relocalize == "device":                 # the second alignment: new_frame_->T_f_w_ = ref_keyframe->T_f_w_ (:266)
+                ar, _, T_k, reloc_dev = backend.align_kf(ref_kf, k, None, max_level, min_level, *caps)
+            else:
+                ar = backend.sparse_align(align_kf_job_host(cam, max_level, min_level, tabs, ref_kf, None, k))
+                T_k, reloc_dev = np.array(_se3_mul_s(ar.T, tabs["kf_T"][ref_kf])), None
+            next_align = None
         # ---- 1. sparse image alignment, previous frame -> frame k (processFrame :266-274) ----
         job = None
-        if next_align is None:                         # (align: otherwise the job was made behind the frame before this one)
+        if next_align is None and not reloc_try:       # (align: otherwise the job was made behind the frame before this one)
             ref_pos = synth.se3_inv(T_prev)[4:]
 
             def scaled(px, pos):
@@ -727,7 +889,9 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
             seg_ok = np.zeros(n_seg, bool); seg_ok[seg_i] = True
         else:
             poses_dev = None
-            if next_align is None:
+            if reloc_try:                              # aligned against the keyframe above
+                poses_dev = reloc_dev
+            elif next_align is None:
                 ar = backend.sparse_align(job)
                 T_k = synth.se3_mul(ar.T, T_prev)                                                # :92
             elif align == "device":                    # the job was built behind the previous frame: run, compose, the pose stays on the device
@@ -878,7 +1042,35 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
             #      map_candidates takes its candidates from keyframe 0 either way, so the call's place here does not matter) ----
             close = backend.close_keyframes(abi.CloseKeyframesJob(cam, synth.se3_mul(ar.T, T_prev), np.stack(kfs["T"]), np.stack(kfs["pos"]),
                                                                   np.stack(kfs["valid"]), max_n_kfs))
-        T_last = T_prev
+        T_last = T_ref_kf if reloc_try else T_prev       # last_frame_ of this processFrame
+        bad_quality = False
+        if relocalize:
+            # ---- the gates of processFrame (:315-321, :335) and setTrackingQuality, ahead of the structure optimisation ----
+            if obs_last is None:
+                obs_last = (out[0]["n_matched_pt"], out[0]["n_matched_seg"])
+            T_rs = T_reset if reloc_try else T_prev
+            gk = dict(gate_kw, max_fts=select_kw["max_fts"], max_fts_segs=select_kw["max_fts_segs"])
+            if relocalize == "device":
+                grec, T_carried, gate_dev = backend.track_gate(mode=abi.GATE_RELOC if reloc_try else abi.GATE_TRACK, T_reset=T_rs,
+                                                               **({} if obs_resident and map_job is None else dict(num_obs_last=obs_last)), **gk)
+                g_result, g_quality = grec["result"], grec["tracking_quality"]
+            else:
+                g_result, g_quality, reset = track_gate_host(frame_sel["n_matches"], frame_sel["n_ls_matches"], pr.num_obs_pt, pr.num_obs_ls, *obs_last, relocalizing=reloc_try, **gk)
+                T_carried = np.array(T_rs, float) if reset else pr.T.copy()
+            obs_last, obs_resident = (int(frame_sel["n_matches"]), int(frame_sel["n_ls_matches"])), True
+            if g_result != abi.GATE_OK:                # RESULT_FAILURE: nothing behind the gate runs; the next frame relocalises
+                frec = dict(T=np.asarray(T_carried, float).copy(), cov=pr.cov.copy(), n_align=ar.n_tracked, n_matched_pt=int(pt_ok.sum()), n_matched_seg=int(seg_ok.sum()),
+                            n_kept_pt=int(pr.pt_keep.sum()), n_kept_seg=int(pr.seg_keep.sum()), stage=stage, gate=int(g_result), tracking_quality=int(g_quality))
+                if reloc_try:
+                    frec.update(reloc_kf=reloc_kf, reloc_tracked=reloc_tracked)
+                if map_candidates:
+                    frec.update(cand_rec)
+                if mapping:
+                    poses_est.append(frec["T"].copy())
+                out.append(frec)
+                T_prev, stage, next_align = frec["T"].copy(), "reloc", None
+                continue
+            bad_quality = g_quality == abi.TRACKING_BAD
         T_k = pr.T.copy()
         pt_keep, seg_keep = pr.pt_keep.astype(bool), pr.seg_keep.astype(bool)
         if cell_select and sel_mask is not None:
@@ -890,6 +1082,11 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                    n_kept_pt=int(pt_keep.sum()), n_kept_seg=int(seg_keep.sum()))
         if n_ties is not None:
             rec["align_ties"] = n_ties
+        if relocalize:
+            rec.update(stage=stage, gate=int(g_result), tracking_quality=int(g_quality))
+            if reloc_try:
+                rec.update(reloc_kf=reloc_kf, reloc_tracked=reloc_tracked)
+            stage = "default"                          # "Relocalization successful."
         if map_candidates:
             rec.update(cand_rec)
         if mapping:
@@ -934,7 +1131,7 @@ def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thres
                     dec = backend.keyframe_decide(abi.KeyframeDecideJob(cam, T_k, T_last, sel["pt_px"], at("pt_pos", sel["pt_lm"]), pr.pt_keep, at("seg_spos", sel["seg_lm"]),
                                                                         at("seg_epos", sel["seg_lm"]), pr.seg_keep, np.array(cm["kf_T"], float).reshape(-1, 7),
                                                                         close["close_idx"][:close["n_overlap"]], (-1,) * 5, kfselect_mindist_t, kfselect_mindist_r))
-                is_kf = bool(dec["need_new_kf"])
+                is_kf = bool(dec["need_new_kf"]) and not bad_quality       # (!needNewKf || TRACKING_BAD: no keyframe, :352)
                 rec.update(is_kf=is_kf, n_overlap=close["n_overlap"], depth_mean=dec["depth_mean"], overlap=[int(v) for v in close["close_idx"][:close["n_overlap"]]])
                 if is_kf:
                     rec["key_pts_new"] = [int(h) for h in dec["key_pts"]]      # the frame's key_pts_ as it becomes a keyframe, in selection order

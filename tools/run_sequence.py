@@ -11,7 +11,7 @@ With --kf-select (off by default; needs mapping) the keyframe stage runs on the 
 frame plays the keyframe when FrameHandlerMono::needNewKf says so instead of every fifth, and the JSON line lists the keyframe frames.
 With --map-candidates (off by default) reprojection and matching take their candidates from the map-candidate stage (plsvo_candidates_*):
 the overlap keyframes' features, one visit per landmark, the closest-view observation as the reference patch.
-usage: python tools/run_sequence.py [--distortion k1,k2,p1,p2[,k3]] [--detect] [--kf-select] [--map-candidates] [--cell-select] [--kf-insert] [--seed-candidates] [--seeds-resident] [--image-seeds host|device] [--structopt-resident] [--compact room|always] [--keystage host|device] [--align host|device] [--lm-room N] [out.txt] [n_frames] [seed] [mapping 0|1]"""
+usage: python tools/run_sequence.py [--distortion k1,k2,p1,p2[,k3]] [--detect] [--kf-select] [--map-candidates] [--cell-select] [--kf-insert] [--seed-candidates] [--seeds-resident] [--image-seeds host|device] [--structopt-resident] [--compact room|always] [--keystage host|device] [--align host|device] [--relocalize host|device] [--lm-room N] [out.txt] [n_frames] [seed] [mapping 0|1]"""
 import importlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -71,6 +71,11 @@ if "--keystage" in argv:                           # host | device: the keyframe
     i = argv.index("--keystage")
     keystage = argv[i + 1]
     del argv[i:i + 2]
+relocalize = None
+if "--relocalize" in argv:                         # host | device: the tracking gates and relocalizeFrame (needs --align and --keystage of the same transport)
+    i = argv.index("--relocalize")
+    relocalize = argv[i + 1]
+    del argv[i:i + 2]
 if "--lm-room" in argv:                            # landmark rows reserved per kind instead of one per seed of the sequence
     i = argv.index("--lm-room")
     lm_room = int(argv[i + 1])
@@ -90,7 +95,7 @@ if distortion is not None:
     seq = dict(seq, images=[P.synth.distort_image(img, dict(fx=fx, fy=fy, cx=cx, cy=cy, d=distortion)) for img in seq["images"]])
     rectify = P.abi.pinhole_radtan(w, h, fx, fy, cx, cy, distortion)
 res = seqm.run_sequence(seqm.HipBackend(ctx, rectify=rectify), seq, mapping=mapping, detect=detect, kf_select=kf_select, map_candidates=map_candidates, cell_select=cell_select, kf_insert=kf_insert,
-                        seed_candidates=seed_candidates, seeds_resident=seeds_resident, image_seeds=image_seeds, structopt_resident=structopt_resident, compact=compact, lm_room=lm_room, keystage=keystage, align=align,
+                        seed_candidates=seed_candidates, seeds_resident=seeds_resident, image_seeds=image_seeds, structopt_resident=structopt_resident, compact=compact, lm_room=lm_room, keystage=keystage, align=align, relocalize=relocalize,
                         image_seed_params=dict(fast_threshold=7, detection_threshold=2.0) if image_seeds else None)
 n = P.trajectory.write_trajectory(out, ["%.6f" % (0.05 * k) for k in range(n_frames)], [r["T"] for r in res], [r["cov"] for r in res])
 err = seqm.pose_errors(res, seq)
@@ -103,6 +108,7 @@ print(json.dumps({"frames": n_frames, "lines_written": n, "trajectory": out, "ma
                       "depth_mean_last": res[-1].get("depth_mean")} if kf_select else {}),
                   **({"seed_candidates_per_frame": [r.get("n_seed_candidates", 0) for r in res[1:]],
                       "seed_candidates_mean": sum(r.get("n_seed_candidates", 0) for r in res[1:]) / max(len(res) - 1, 1)} if seed_candidates else {}),
+                  **({"relocalize": relocalize, "stages": [r["stage"] for r in res[1:]], "gates": [r["gate"] for r in res[1:]]} if relocalize else {}),
                   **({"keystage": keystage, "key_pts_last": res[-1]["key_pts"].tolist()} if keystage else {}),
                   **({"compacted_rows_per_keyframe": [r["n_compacted_pt"] for r in res if "n_compacted_pt" in r]} if compact else {})}))
 ctx.close()

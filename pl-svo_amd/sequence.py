@@ -1,73 +1,38 @@
-"""A minimal frame-to-frame harness over the widened hot path, in the order FrameHandlerMono::processFrame runs it
-(src/frame_handler_mono.cpp:266-340):
+"""The sequence harness: the one place where the resident stages are chained the way FrameHandlerMono::processFrame chains them
+(src/frame_handler_mono.cpp:266-340), frame after frame on a synthetic sequence -- a textured plane carrying point and line-segment
+landmarks, observed in keyframe 0, frame 0 the keyframe with the true pose (make_sequence).  Tests check the stages end to end through
+it, tools/run_sequence.py runs it on the card, and it emits trajectory files in the reference harness's format.
 
-    sparse image alignment (previous frame -> new frame)        plsvo_sparse_align
-    reprojection of the map into the new frame                  plsvo_reproject
-    direct feature matching against the keyframe observations   plsvo_match_direct
-    motion-only pose optimisation on the matches                plsvo_pose_optimize
-    trajectory record (TUM line of T_f_w^-1)                    plsvo_trajectory_record
+run_sequence() checks its flags against one table (_PREREQUISITES) and hands them to a run object, _Run, whose process_frame() reads as
+the step list of processFrame; each step is a method that carries the rules of the reference and the contract with the backend it
+implements.  In call order:
 
-on a synthetic sequence with a known map (a textured plane carrying point and line-segment landmarks, observed in
-keyframe 0).  It exists to exercise the entry points chained the way the reference chains them and to emit trajectory
-files in the reference harness's format; it is not a VO system: the map is given, and its maintenance (candidate
-lists, keyframe removal) is not part of it.
+    relocalize_frame      relocalizeFrame: closest keyframe, gating alignment, alignment from the keyframe        (relocalize)
+    align                 1. sparse image alignment, previous frame -> new frame                                   plsvo_sparse_align
+    track_map_*           2. reprojection of the map, 3. direct matching against the reference observations        plsvo_reproject, plsvo_match_direct
+                          -- keyframe 0's; the map-candidate stage, with the cell selection; or 1-4 as one call    plsvo_candidates_*, plsvo_frame_step_batch
+    pose_optimize_host    4. motion-only pose optimisation on the matches                                          plsvo_pose_optimize
+    gate                  the gates of processFrame and setTrackingQuality                                         (relocalize)
+    decide_keyframe*      scene depth, new-keyframe test, the frame's five key points                              plsvo_keyframe_decide
+    structure_resident    5. structure optimisation on the resident tables, every frame                            plsvo_candidates_optimize_structure
+    insert_keyframe       the frame joins the resident tables; image seeds; compaction (join_keyframe_host: the restaging path)
+    structure_host        5. structure optimisation of the 20 least recently refined landmarks, at a keyframe       plsvo_structure_optimize   (:340)
+    update_seeds          6. depth-filter update of the seeds with the new frame                                   plsvo_update_seeds         (depth_filter.cpp:262)
+    image_seeds_host      7. the seeds from the image's own corners                                                (detect)
+    queue_next_align      the next frame's alignment job from this frame's selection                               (align)
 
-With mapping=True two more steps run per frame, again as processFrame / the depth-filter thread order them:
+and the trajectory record (TUM line of T_f_w^-1, plsvo_trajectory_record) is written from the result by the caller.  What lives from
+frame to frame is held by small state classes: _MapTables (the map tables the harness follows beside the device's, and the row <->
+landmark maps), _SeedRows (the resident seed rows), _Keyframes (the keyframe table without keystage), _RelocState (the stage machine);
+what one step hands to a later one travels in the frame's _Frame.  It is not a VO system: the map is synthetic and its truth is known.
 
-    structure optimisation of the 20 least recently refined landmarks   plsvo_structure_optimize   (:340)
-    depth-filter update of the seeds with the new frame                  plsvo_update_seeds         (depth_filter.cpp:262)
-
-starting from a map that knows only part of the landmarks (with noisy positions) and holds the rest as seeds that turn
-into landmarks when they converge.
-
-With kf_select=True (and mapping) the keyframe stage of processFrame runs on the device too (:351-358, :396):
-
-    keyframes that overlap the aligned frame, before matching           plsvo_close_keyframes      (reprojector.cpp:147-163)
-    scene depth, new-keyframe test, the frame's five key points          plsvo_keyframe_decide
-
-A frame then plays the keyframe when needNewKf says so -- measured, like the reference, from the PREVIOUS frame's pose -- instead of
-every kf_every-th; the keyframe table (pose and the landmark positions of the five key points) grows with it, and the seeds of a
-keyframe's corners start from depth_mean * 2.0 and 0.1 * depth_min of that call (:391).
-
-With map_candidates=True (a per-call backend with map_candidates) steps 2 and 3 take their candidates and reference observations from the
-map-candidate stage (plsvo_candidates_*) instead of keyframe 0: the harness keeps the map tables the stage needs -- the
-keyframes' feature lists, every landmark's observation list with px / f / level, newest first -- restages them when they change (a frame
-becomes a keyframe, a seed converges into the map's candidate list), and hands each frame its pose and its overlap list: the one of
-plsvo_close_keyframes with kf_select, otherwise every keyframe in table order.  The matches reach the pose optimiser in landmark-index
-order, as without it.
-
-With cell_select=True on top of it (a backend with map_select) the second half of Reprojector::reprojectMap runs on the device as well
-(plsvo_candidates_select): one candidate per grid cell in place of every found match, the landmark quality
-(n_failed_reproj_ / n_succeeded_reproj_, promotions, deletions) kept resident from frame to frame, and the pose optimiser fed on the
-device.  The harness follows the types, the candidate lists and the deletions in its own tables from fetch_quality, restages only when
-the map changes at a keyframe (or a seed converges), and carries the counters over a restage with fetch_quality / set_quality.  With
-kf_insert=True on top of that (a backend with map_insert) a keyframe no longer restages: the frame joins the resident tables on the device
-(plsvo_candidates_insert_keyframe), the harness takes its own tables from the backend's fetch, moved landmarks go through
-map_set_positions, and only a seed that converges into a NEW candidate stages again.  With seed_candidates=True on top of that (a
-backend with map_add_candidates) that last restage goes too: the converged seed is appended to the resident tables on the device
-(plsvo_candidates_add) as a new landmark row with one observation and an entry at the back of the candidate list, and the
-stage is called once, at the first frame.  The
-features reach the pose optimiser in selection order; a segment that won both of its cells is a feature twice.  With
-structopt_resident=True (cell_select, a backend with map_optimize_structure) the structure optimisation runs on the resident tables too
-(plsvo_candidates_optimize_structure): one call on every tracked frame, points and segments, ahead of an insertion; the
-harness takes the moved positions and the keys from the call's report.
-
-With align="host" | "device" (map_candidates and cell_select) step 1 of every frame but the first is fed by the frame before it: the features of the
-alignment job are the previous frame's SELECTION with the pose optimiser's keep masks, the landmarks' positions and types as the tables
-hold them when that frame is done -- behind the structure optimisation and an insertion, ahead of a compaction --, the reference pose the
-optimised one; the first frame, and a frame behind one whose tables wait for a restage, are staged by the host as without it.  "device" builds that job on the device (plsvo_candidates_align_build .. _compose, DESIGN.md 3.20: no selection fetch, no
-pose fetch, no host arithmetic ahead of the alignment) and hands the composed pose on by device pointer; "host" restates the same job here
-in scalar float64 and stages it through plsvo_align_stage, so the two differ in transport alone and agree in every record.
-
-With relocalize="host" | "device" (align and keystage) the harness plays the reference's stage machine: the gates of
-processFrame stand behind every frame's pose optimisation, a frame that fails them is carried forward with the pose the gate gives and
-the next frame relocalises against the closest keyframe of the resident tables (relocalizeFrame) until a frame passes the gates again.
-
-`backend` is duck-typed: load_frames(list of level-0 images; HipBackend also takes raw frames with rectify=), sparse_align(job), reproject(job), match_direct(job),
-pose_optimize(job), for mapping structure_optimize(job), update_seeds(job), and for kf_select close_keyframes(job), keyframe_decide(job).  The product backend is HipBackend (C ABI on the GPU, no fallback); tests pass an oracle-backed one
-to check the whole chain end to end."""
+`backend` is duck-typed: load_frames(list of level-0 images; HipBackend also takes raw frames with rectify=), sparse_align(job),
+reproject(job), match_direct(job), pose_optimize(job), and per flag the methods run_sequence's table names.  The product backend is
+HipBackend (C ABI on the GPU, no fallback), HipChainBackend with steps 1-4 as one resident call; tests pass an oracle-backed one to check
+the whole chain end to end."""
 import copy
 import math
+import types
 
 import numpy as np
 
@@ -585,781 +550,1037 @@ def run_sequence(backend, seq, max_level=3, min_level=1, n_pyr_levels=3, reproj_
                  kfselect_mindist_r=3.0, max_n_kfs=10, map_candidates=False, record_candidates=False, cell_select=False, select_params=None, kf_insert=False,
                  seed_candidates=False, seeds_resident=False, image_seeds=None, image_seed_params=None, structopt_resident=False, compact=None, lm_room=None, keystage=None, align=None,
                  relocalize=None, reloc_params=None):
-    """-> list of per-frame dicts (pose T_f_w, cov, counts).  Frame 0 is the keyframe with the true pose.
-    mapping=True: only `known_frac` of the point landmarks start in the map (positions off by `pos_noise` x depth along
-    their viewing ray), the others are depth-filter seeds; the seed update runs every frame; every `kf_every`-th frame
-    plays the keyframe: its matches become observations of their landmarks (Feature3D::obs_ grows at keyframes only, as
-    in the reference) and the 20 least recently refined landmarks with >= 2 observations are structure-optimised.
-    detect=True (with mapping, a backend with detect_corners): every keyframe, frame 0 included, also runs the corner detector on its
-    own pyramid slot with the cells of the features it tracks marked occupied (DepthFilter::initializeSeeds), and the corners become
-    point seeds (seeds_from_corners) that the following frames update next to the map's own; the records gain n_image_seeds /
-    n_image_seeds_converged.  These seeds come from the image alone and are not added to the map, whose landmarks carry the truth.
-    kf_select=True (with mapping, a backend with close_keyframes / keyframe_decide): the keyframe stage decides which frames play the
-    keyframe (module docstring); the records gain is_kf, n_overlap, depth_mean.
-    map_candidates=True (a backend with map_candidates, not the resident chain): candidates and reference observations come from the
-    map-candidate stage (module docstring); the records gain n_filed_pt / n_filed_seg and ref_kf_hist, how many of the filed landmarks
-    took their reference observation from each keyframe of the table.  record_candidates=True also keeps each frame's stage inputs and
-    result in rec["candidates"] (tests).
-    cell_select=True (with map_candidates, a backend with map_select): the cell selection and the resident pose optimiser take the place
-    of "every found match" and the per-call pose optimiser (module docstring); select_params: keyword arguments of
-    capi.Context.candidates_select (default: max_fts 120, max_fts_segs 100, cells in index order).  The records gain n_trials and
-    n_promoted / n_deleted; rec["candidates"] gains the selection and the quality state before and after the frame.
-    kf_insert=True (with cell_select, a backend with map_insert): a keyframe is inserted into the resident tables on the device
-    (plsvo_candidates_insert_keyframe) with the resident pose and keep masks; when the table holds max_n_kfs keyframes the
-    one keyframe_decide names as the furthest is removed in the same call (kf_select; the first row when it names none).  The harness
-    brings its own tables up to date from the backend's fetch, sends structure-optimised positions with map_set_positions, and stages
-    only at the start and when a seed converges into a NEW candidate -- observed in frame 0's keyframe, whose row the harness follows through
-    the removals; a seed that converges after that keyframe was removed stays outside the map's tables (n_seed_candidates counts the
-    others).  The keyframe records gain n_joined / n_deleted_kf / remove_kf, and
-    with record_candidates rec["insert"]: the tables and the quality before, the selection, the masks, the pose, and all three after.
-    seed_candidates=True (with kf_insert, a backend with map_add_candidates): a converged seed whose keyframe is still in the table is
-    appended to the resident tables on the device (plsvo_candidates_add) instead of marking the tables for a restage; the
-    harness appends the same row to its own tables.  The seed's table row is then a NEW one behind the staged rows, no longer its landmark
-    index: the harness keeps the row of every landmark and the landmark of every row, and translates wherever the backend speaks in rows
-    (filed and selected landmarks, moved positions).  With record_candidates rec["add"] holds the tables and the quality before, the new
-    records, the tables and the quality after, and the backend's report.
-    seeds_resident=True (with seed_candidates, a backend with seeds_stage): the map's seeds are staged ONCE, beside the map tables, and are
-    updated, erased and handed over to the resident tables on the device (plsvo_seeds_update): no seed travels per frame and
-    no record comes back, only the report and the update's rows, from which the harness keeps its own tables exactly as it does from an
-    add's report.  A removal at an insertion is passed on (plsvo_seeds_keyframe); when it takes frame 0's keyframe out, the seeds that
-    are left leave the device with it -- their keyframe is no longer in the table -- and the harness goes on following them on the host,
-    outside the map, as it does without this flag.  With the flag off every record is what it is without it.
-    image_seeds="host" | "device" (with seeds_resident; default None: nothing changes): at a keyframe whose seed tables are on the device
-    the image's corners become point seeds of the RESIDENT lists (DepthFilter::initializeSeeds' creating half), behind the
-    insertion, with the cells of the frame's selected features and of the last update's matches occupied.  "device" is
-    plsvo_seeds_keyframe_detect with both occupancy sources; "host" does the same with the calls there were before -- detect_corners on
-    an occupancy built from the fetched selection and the fetched rows by the same rule, seeds_from_corners, seeds_keyframe(pt_..) --
-    so the two differ in transport alone and agree in every record and in the lists.  These seeds have no landmark of the synthetic
-    map: the harness keeps, per resident row, the landmark of a map seed or -1, follows removals and erasures through the rows and the
-    reports, and gives a converged image seed a table row of its own without a landmark (such rows are selected, optimised and inserted
-    on the device like any other; the harness's own alignment and structure optimisation leave them out).  The records gain
-    n_image_seeds / n_image_seeds_converged / n_image_seeds_started.  image_seed_params: fast_threshold, detection_threshold (20, 20.0).
-    When frame 0's keyframe leaves the table the resident lists are given up as without this flag, image seeds included.
-    structopt_resident=True (with mapping and cell_select, a backend with map_optimize_structure): step 5 runs on the resident tables
-    (plsvo_candidates_optimize_structure) in place of the gather / structure_optimize / map_set_positions of the harness:
-    one call on EVERY tracked frame, behind the pose optimiser and ahead of an insertion as in processFrame (:340), points and segments,
-    with the resident keep masks and frame_id = k.  The harness takes the moved positions for its own tables from the call's report and
-    follows the keys from it, to carry them over a restage (map_set_last_optim).  The records gain n_structopt_pt / n_structopt_seg, and
-    with record_candidates rec["structopt"]: the tables and the keys before, the selection, the masks, the report, and both after.
-    With the flag off every record is what it is without it.
-    compact="room" | "always" (with seed_candidates, a backend with map_compact; default None: nothing changes): behind every keyframe's
-    insertion the resident tables close up over their deleted POINT rows on the device (plsvo_candidates_compact) --
-    "always" at every keyframe, "room" only when fewer rows are free than seeds are alive, decided on the device.  The harness takes the
-    tables from the backend's fetch and applies the remap to its row <-> landmark maps and to the keys it follows.  The segments have no
-    reserve here (no segment seed exists) and are never compacted.  lm_room: landmark rows reserved per kind instead of one per seed of
-    the sequence; without compaction a sequence whose converged seeds outnumber it ends in PLSVO_E_CAPACITY.  Stable order is kept, so
-    every pose, covariance and count equals those of the run with the full reserve; the keyframe records gain n_compacted_pt.
-    keystage="host" | "device" (with kf_select, cell_select and kf_insert; default None: every record is what it is without it): the
-    keyframe stage follows the reference instead of snapshotting a key point's position when its keyframe is inserted -- Frame::key_pts_
-    are positions in the keyframes' feature lists, a key point's position is its landmark's position in the tables NOW
-    (Map::getCloseKeyframes, src/map.cpp:165-169), a key point whose landmark is deleted is replaced (Map::safeDeletePoint ->
-    Frame::removeKeyPoint, :116-123), and the decision runs behind the structure optimisation (src/frame_handler_mono.cpp:340 before
-    :351) on the selection with the keep masks as alive.  "device" does it on the resident tables (plsvo_candidates_set_keypts,
-    _run_close, _keyframe_decide; DESIGN.md 3.19: a backend with map_set_keypts / map_keyframe_decide); "host" does the same with the
-    calls there were before: the key-point table kept here from the tables the harness follows, then the synchronous
-    close_keyframes / keyframe_decide on gathered arrays.  The two differ in transport alone and agree in every record; the last record
-    gains key_pts, the table at the end, every record overlap, the list itself, a keyframe's record key_pts_new, the decision's key points, and in "host" the keyframe records count the rows
-    rebuilt (n_kp_rebuilt).
-    align="host" | "device" (with map_candidates and cell_select; default None: every record is what it is without it): from the second
-    frame on the alignment job is the previous frame's selection as the device holds it when that frame is done (module docstring,
-    DESIGN.md 3.20).  "device" builds it there (a backend with align_build / align_built), runs it and passes the composed pose by device
-    pointer into the candidate stage; "host" restates the same job (align_job_host) and stages it as before.  The first frame's job
-    is gathered from keyframe 0 as without the flag, and so is the job of a frame behind one that left the tables waiting for a restage
-    (a keyframe without kf_insert, a converged seed without seed_candidates): the resident tables are then behind the harness's own.
-    The two agree in every record.
-    relocalize="host" | "device" (with align and keystage; default None: every record is what it is without it): the harness plays the
-    reference's stage machine, STAGE_DEFAULT_FRAME <-> STAGE_RELOCALIZING (finishFrameProcessingCommon).  Behind the pose optimisation of
-    every frame stand the gates of processFrame (src/frame_handler_mono.cpp:315-321, :335, setTrackingQuality): a frame that fails is not
-    structure-optimised, decided, inserted or fed to the depth filter, its pose is the one the gate carries, and the next frame
-    relocalises (relocalizeFrame :408-436): Map::getClosestKeyframe from the last frame's pose, a gating alignment against that keyframe
-    from the identity that must track more than 30, a second alignment from the keyframe's own pose, and the rest of processFrame, whose
-    every failure carries the last frame's pose; a success returns to STAGE_DEFAULT_FRAME.  TRACKING_BAD keeps a frame from becoming a
-    keyframe.  "device" uses plsvo_candidates_align_build_kf and plsvo_candidates_track_gate (a backend with align_kf /
-    track_gate); "host" does the same with the calls there were before -- fetched tables, close_keyframes, align_kf_job_host staged
-    through plsvo_align_stage, track_gate_host on the fetched counts.  The two differ in transport alone and agree in every record.  The
-    two host waits of "device": the gate's record ahead of the structure optimisation, and n_tracked behind the gating alignment.
-    reloc_params: quality_min_fts (20), quality_max_drop_fts (50); the clamps are the selection's max_fts / max_fts_segs.  The records
-    gain stage (the stage the frame was processed in), gate, tracking_quality and, in a relocalising frame, reloc_kf / reloc_tracked.
-    The tables must not wait for a restage while a stream relocalises (kf_insert with seed_candidates keeps them resident)."""
-    params = dict(locals())                            # (first statement: exactly the arguments)
-    if relocalize not in (None, "host", "device") or (relocalize and not (align and keystage and (relocalize == "host" or (keystage == "device" and hasattr(backend, "align_kf"))))):
-        raise ValueError("relocalize is None, 'host' or 'device' and needs align, keystage and, for 'device', keystage='device' (the live key-point table) and a backend with align_kf() / track_gate()")
-    if align not in (None, "host", "device") or (align and not (map_candidates and cell_select and (align == "host" or hasattr(backend, "align_build")))):
-        raise ValueError("align is None, 'host' or 'device' and needs map_candidates, cell_select and, for 'device', a backend with align_build() / align_built()")
-    if keystage not in (None, "host", "device") or (keystage and not (kf_select and cell_select and kf_insert and hasattr(backend, "map_keyframe_decide" if keystage == "device" else "keyframe_decide"))):
-        raise ValueError("keystage is None, 'host' or 'device' and needs kf_select, cell_select, kf_insert and a backend with keyframe_decide() / map_keyframe_decide()")
-    if compact not in (None, "room", "always") or (compact and not (seed_candidates and hasattr(backend, "map_compact"))):
-        raise ValueError("compact is None, 'room' or 'always' and needs seed_candidates and a backend with map_compact()")
-    if structopt_resident and not (mapping and cell_select and hasattr(backend, "map_optimize_structure")):
-        raise ValueError("structopt_resident needs mapping, cell_select and a backend with map_optimize_structure()")
-    if image_seeds not in (None, "host", "device") or (image_seeds and not (seeds_resident and hasattr(backend, "seeds_keyframe_detect" if image_seeds == "device" else "detect_corners"))):
-        raise ValueError("image_seeds is None, 'host' or 'device', needs seeds_resident and a backend with detect_corners() / seeds_keyframe_detect()")
-    if seeds_resident and not (seed_candidates and hasattr(backend, "seeds_stage")):
-        raise ValueError("seeds_resident needs seed_candidates and a backend with seeds_stage()")
-    if seed_candidates and not (kf_insert and hasattr(backend, "map_add_candidates")):
-        raise ValueError("seed_candidates needs kf_insert and a backend with map_add_candidates()")
-    if kf_insert and not (cell_select and mapping and hasattr(backend, "map_insert")):
-        raise ValueError("kf_insert needs mapping, cell_select and a backend with map_insert()")
+    """-> list of per-frame dicts (pose T_f_w, cov, counts).  Frame 0 is the keyframe with the true pose.  One line per flag; what a flag
+    does, and its contract with the backend, is written at the step of _Run named in the last column.  With a flag off (False / None)
+    every record is what it is without it.
+
+    flag                values              needs: flags; backend method                                   the records gain                                          step
+    mapping             bool                structure_optimize, update_seeds                               n_seed_converged, n_known, n_seeds, landmark_err          _Run.init_mapping
+    detect              bool                mapping; detect_corners (ignored without)                      n_image_seeds, n_image_seeds_converged                    image_seeds_host
+    kf_select           bool                mapping; close_keyframes, keyframe_decide (ignored without)    is_kf, n_overlap, depth_mean                              decide_keyframe_host
+    map_candidates      bool                map_candidates, no frame_step                                  n_filed_pt, n_filed_seg, ref_kf_hist                      track_map_candidates
+    record_candidates   bool                map_candidates                                                 candidates; insert, add, structopt (tests)                the steps that record
+    cell_select         bool                map_candidates; map_select                                     n_trials, n_promoted, n_deleted                           select_cells
+    kf_insert           bool                mapping, cell_select; map_insert, map_reserve                  n_joined, n_deleted_kf, remove_kf, n_seed_candidates      insert_keyframe
+    seed_candidates     bool                kf_insert; map_add_candidates, map_reserve_landmarks           (rec["add"])                                              converged_seeds_join
+    seeds_resident      bool                seed_candidates; seeds_stage                                   --                                                        stage_seeds
+    image_seeds         "host" | "device"   seeds_resident; detect_corners | seeds_keyframe_detect         n_image_seeds, _converged, _started                       start_image_seeds
+    structopt_resident  bool                mapping, cell_select; map_optimize_structure                   n_structopt_pt, n_structopt_seg                           structure_resident
+    compact             "room" | "always"   seed_candidates; map_compact                                   n_compacted_pt                                            compact_tables
+    keystage            "host" | "device"   kf_select, cell_select, kf_insert; keyframe_decide |           is_kf, n_overlap, depth_mean, overlap, key_pts_new,       decide_keyframe
+                                            map_keyframe_decide                                            n_kp_rebuilt ("host"), key_pts (last record)
+    align               "host" | "device"   map_candidates, cell_select; "device": align_build             --                                                        queue_next_align
+    relocalize          "host" | "device"   align, keystage; "device": keystage="device", align_kf         stage, gate, tracking_quality, reloc_kf, reloc_tracked    relocalize_frame, gate
+
+    known_frac, pos_noise, map_seed, kf_every: the map mapping=True starts from and the keyframe cadence without kf_select (_Run.init_mapping).
+    kfselect_mindist_t / _r, max_n_kfs: the keyframe stage's options.  detect_cell_size: the detector's grid, detect and image_seeds.
+    select_params: keyword arguments of capi.Context.candidates_select (default: max_fts 120, max_fts_segs 100, cells in index order).
+    image_seed_params: fast_threshold, detection_threshold (20, 20.0).  reloc_params: quality_min_fts (20), quality_max_drop_fts (50); the
+    clamps are the selection's max_fts / max_fts_segs.  lm_room: landmark rows reserved per kind instead of one per seed of the sequence;
+    without compaction a sequence whose converged seeds outnumber it ends in PLSVO_E_CAPACITY."""
+    o = types.SimpleNamespace(**locals())              # (first statement: exactly the arguments)
+    o.map_stage = "cell_select" if cell_select else "map_candidates" if map_candidates else None
+    _check_options(o)
     if not kf_insert:
-        return _run_sequence(**params)
+        return _Run(o).run()
     # room for every keyframe the sequence can add (a joined candidate adds a feature, every feature an observation)
     n_fr, n_lm = len(seq["images"]), len(seq["pt_pos"]) + 2 * len(seq["seg_spos"])
     backend.map_reserve(extra_kf=n_fr, extra_kf_pt=n_fr * n_lm, extra_kf_seg=n_fr * n_lm, extra_pt_obs=n_fr * n_lm, extra_seg_obs=n_fr * n_lm)
     if seed_candidates:                                # a landmark row per seed that can converge (its observation fits the room above)
         backend.map_reserve_landmarks(extra_pt=len(seq["pt_pos"]) if lm_room is None else int(lm_room), extra_seg=0 if lm_room is None else int(lm_room))
     try:
-        return _run_sequence(**params)
+        return _Run(o).run()
     finally:
         backend.map_reserve()                          # the tight layout again for whoever stages next on this backend
         if seed_candidates:
             backend.map_reserve_landmarks()
 
 
-def _run_sequence(backend, seq, max_level, min_level, n_pyr_levels, reproj_thresh, mapping, known_frac, pos_noise, map_seed, kf_every, detect, detect_cell_size, kf_select,
-                  kfselect_mindist_t, kfselect_mindist_r, max_n_kfs, map_candidates, record_candidates, cell_select, select_params, kf_insert, seed_candidates, seeds_resident,
-                  image_seeds=None, image_seed_params=None, structopt_resident=False, compact=None, lm_room=None, keystage=None, align=None, relocalize=None, reloc_params=None):
-    cam = seq["cam"]
-    stage, gate_dev, obs_last, obs_resident = "default", None, None, False   # relocalize: the stage, the gate's carried poses on the device, num_obs_last_pt / _ls and whether the device holds them
-    gate_kw = dict(quality_min_fts=20, quality_max_drop_fts=50)
-    gate_kw.update(reloc_params or {})
-    IDENT = [0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0]
-    next_align = None                                  # align: the job of the frame to come -- an abi.AlignJob ("host") or True: built on the device
-    kp_tab, kp_live = None, False                      # keystage: Frame::key_pts_ per keyframe row of cm ("host": kept here; "device": fetched when a restage needs it)
-    img_kw = dict(fast_threshold=20, detection_threshold=20.0)
-    img_kw.update(image_seed_params or {})
-    res_lm, res_kf, res_ftr, last_rows, img_conv = [], [], [], None, 0   # image_seeds: per resident point row its landmark (-1: from the image), its keyframe row, its feature
-    sel_mask = None
-    seeds_on_device = False                            # seeds_resident: the seed lists are staged and their keyframe is still in the table
-    if cell_select and not (map_candidates and hasattr(backend, "map_select")):
-        raise ValueError("cell_select needs map_candidates and a backend with map_select()")
-    if map_candidates and (hasattr(backend, "frame_step") or not hasattr(backend, "map_select" if cell_select else "map_candidates")):
-        raise ValueError("cell_select needs a per-call backend with map_select()" if cell_select else "map_candidates needs a per-call backend with map_candidates()")
-    backend.load_frames(seq["images"])
-    n_pts, n_seg = len(seq["pt_pos"]), len(seq["seg_spos"])
-    T_prev = seq["poses_true"][0].copy()
-    kf_T = seq["poses_true"][0]
-    P3 = seq["pt_pos"].copy()                      # the map's point positions (seq["pt_pos"] stays the truth)
-    known = np.ones(n_pts, bool)
-    if mapping:
-        rng = np.random.default_rng(map_seed + 77)
-        known = rng.uniform(size=n_pts) < known_frac
+_MODES = (None, "host", "device")
+# flag, its values (None: a switch), the flags it needs, per value what else: a backend method, "!method" (the backend must not have it) or (flag, value); the refusal
+_PREREQUISITES = (
+    ("relocalize", _MODES, ("align", "keystage"), {"device": (("keystage", "device"), "align_kf")}, "relocalize is None, 'host' or 'device' and needs align, keystage and, for 'device', keystage='device' (the live key-point table) and a backend with align_kf() / track_gate()"),
+    ("align", _MODES, ("map_candidates", "cell_select"), {"device": ("align_build",)}, "align is None, 'host' or 'device' and needs map_candidates, cell_select and, for 'device', a backend with align_build() / align_built()"),
+    ("keystage", _MODES, ("kf_select", "cell_select", "kf_insert"), {"device": ("map_keyframe_decide",), "host": ("keyframe_decide",)}, "keystage is None, 'host' or 'device' and needs kf_select, cell_select, kf_insert and a backend with keyframe_decide() / map_keyframe_decide()"),
+    ("compact", (None, "room", "always"), ("seed_candidates",), {"room": ("map_compact",), "always": ("map_compact",)}, "compact is None, 'room' or 'always' and needs seed_candidates and a backend with map_compact()"),
+    ("structopt_resident", None, ("mapping", "cell_select"), {True: ("map_optimize_structure",)}, "structopt_resident needs mapping, cell_select and a backend with map_optimize_structure()"),
+    ("image_seeds", _MODES, ("seeds_resident",), {"device": ("seeds_keyframe_detect",), "host": ("detect_corners",)}, "image_seeds is None, 'host' or 'device', needs seeds_resident and a backend with detect_corners() / seeds_keyframe_detect()"),
+    ("seeds_resident", None, ("seed_candidates",), {True: ("seeds_stage",)}, "seeds_resident needs seed_candidates and a backend with seeds_stage()"),
+    ("seed_candidates", None, ("kf_insert",), {True: ("map_add_candidates",)}, "seed_candidates needs kf_insert and a backend with map_add_candidates()"),
+    ("kf_insert", None, ("cell_select", "mapping"), {True: ("map_insert",)}, "kf_insert needs mapping, cell_select and a backend with map_insert()"),
+    ("cell_select", None, ("map_candidates",), {True: ("map_select",)}, "cell_select needs map_candidates and a backend with map_select()"),
+    ("map_stage", (None, "map_candidates", "cell_select"), (), {"map_candidates": ("!frame_step", "map_candidates"), "cell_select": ("!frame_step", "map_select")}, {"map_candidates": "map_candidates needs a per-call backend with map_candidates()", "cell_select": "cell_select needs a per-call backend with map_select()"}))
+
+
+def _check_options(o):
+    """the refusals of run_sequence: a value outside a flag's list, a flag without the flags it stands on, a backend without the
+    method -- in the table's order.  (map_stage: steps 2 and 3 by name, the flag the two backend-shape refusals speak of)"""
+    met = lambda need: getattr(o, need[0]) == need[1] if isinstance(need, tuple) else hasattr(o.backend, need.lstrip("!")) != need.startswith("!")
+    for flag, values, flags, per_value, refusal in _PREREQUISITES:
+        v = getattr(o, flag)
+        if values is not None and v not in values or v and not (all(getattr(o, f) for f in flags) and all(met(n) for n in per_value.get(v if values else True, ()))):
+            raise ValueError(refusal[v] if isinstance(refusal, dict) else refusal)
+
+
+def _f3(v):
+    return [float(x) for x in v]                       # plain floats for the map tables
+
+
+def _rows_of(table, rows):
+    return np.array([table[int(r)] for r in rows], float).reshape(-1, 3)
+
+
+def _overlap_of(close):
+    """the overlap list of a close_keyframes report"""
+    return [int(v) for v in close["close_idx"][:close["n_overlap"]]]
+
+
+class _MapTables:
+    """map_candidates: the map tables the harness follows beside the device's.  cm: the tables as lists (tests/np_candidates.py reads
+    them so): the keyframes' feature lists, every landmark's observation list with px / f / level, newest first.  They are restaged
+    when they change without the device (dirty: a frame becomes a keyframe, a seed converges into the candidate list) and, where the
+    device changes them, taken from its fetch (adopt) or kept in step from its reports.
+    Point rows of the tables <-> landmarks (indices of P3 / px_new): the identity until seed_candidates appends a converged seed as a NEW
+    row (its own row stays behind, empty and in no list), or image_seeds a row without a landmark (-1); segment rows are segment indices
+    throughout.  The harness translates wherever the backend speaks in rows (filed and selected landmarks, moved positions)."""
+
+    def __init__(self, seq, known):
+        n_pts, n_seg = len(seq["pt_pos"]), len(seq["seg_spos"])
+        # keyframe 0 with the features of the landmarks it starts with, one observation each
+        self.cm = dict(kf_T=[_f3(seq["poses_true"][0])], kf_slot=[0], kf_pt=[[int(i) for i in np.nonzero(known)[0]]], kf_seg=[list(range(n_seg))],
+                       pt_pos=None, pt_type=[abi.LM_UNKNOWN] * n_pts,
+                       pt_obs=[[dict(kf=0, px=_f3(seq["pt_px0"][i]), f=_f3(seq["pt_f0"][i]), level=0, type=abi.FTR_CORNER, grad=[0.0, 0.0])] if known[i] else [] for i in range(n_pts)],
+                       seg_spos=[_f3(v) for v in seq["seg_spos"]], seg_epos=[_f3(v) for v in seq["seg_epos"]], seg_type=[abi.LM_UNKNOWN] * n_seg,
+                       seg_obs=[[dict(kf=0, spx=_f3(seq["seg_spx0"][i]), epx=_f3(seq["seg_epx0"][i]), sf=_f3(seq["seg_sf0"][i]), ef=_f3(seq["seg_ef0"][i]), level=0)]
+                                for i in range(n_seg)], pt_cand=[], seg_cand=[])
+        self.dirty = True                              # the device's tables are behind cm: the next frame stages
+        self.seed_kf = 0                               # the row of frame 0, where every seed was started (None once kf_insert removed it)
+        self.row_lm, self.lm_row = list(range(n_pts)), np.arange(n_pts, dtype=np.int64)
+        self.quality = None                            # cell_select: the quality state after the last frame (None: nothing staged yet), carried over a restage
+        self.so_keys = dict(pt=[], seg=[])             # structopt_resident: last_structure_optim_ per table row, followed from the reports (0: never refined)
+
+    def stage_job(self, P3):
+        """-> the abi.CandidateMapJob to (re)stage, the point rows at their landmarks' positions now; None: the device's tables are current"""
+        if not self.dirty:
+            return None
+        self.cm["pt_pos"] = [[float(x) for x in P3[i]] for i in self.row_lm]
+        self.dirty = False
+        return candidate_map_job(self.cm)
+
+    def adopt(self, tables):
+        """behind an insertion or a compaction the harness's tables are the backend's fetch"""
+        self.cm = candidate_map_tables(tables)
+
+    def lm_of_rows(self, rows):
+        return np.asarray(self.row_lm, np.int64)[rows]
+
+    def row_of_lm(self, lms):
+        return self.lm_row[lms]
+
+    def append_candidate(self, pos, kf, px, f, level, grad, lm, own_row=False):
+        """a converged seed becomes a candidate of the map (map_.point_candidates_, newCandidatePoint) with its one observation, in keyframe
+        row kf: a NEW row behind the others, as plsvo_candidates_add / the seed commit append it on the device (lm -1: a seed from the
+        image, no landmark of the harness's map) -- or, own_row, the landmark's staged row, empty until now, for the restage that follows
+        (which takes the position from P3).  A seed is observed in the keyframe it was started in (frame 0); once that keyframe has left
+        the table the seed's only observation is gone with it, as removeFrameCandidates would delete it, and the callers leave the
+        landmark outside the map's tables.  -> the row"""
+        cm, obs = self.cm, [dict(kf=kf, px=_f3(px), f=_f3(f), level=level, type=abi.FTR_CORNER, grad=grad)]
+        if own_row:
+            row = int(self.lm_row[lm])
+            cm["pt_obs"][row], cm["pt_type"][row], self.dirty = obs, abi.LM_CANDIDATE, True
+        else:
+            row = len(cm["pt_pos"])
+            cm["pt_pos"].append(_f3(pos)); cm["pt_type"].append(abi.LM_CANDIDATE); cm["pt_obs"].append(obs)
+            self.row_lm.append(lm)
+            if lm >= 0:
+                self.lm_row[lm] = row
+        cm["pt_cand"].append(row)
+        return row
+
+    def apply_pt_remap(self, remap):
+        """a compaction's effect on the rows the harness follows: remap[old row] = the new row, or < 0 for a deleted one"""
+        self.lm_row[[lm for row, lm in enumerate(self.row_lm) if lm >= 0 and remap[row] < 0]] = -1
+        self.row_lm = [lm for row, lm in enumerate(self.row_lm) if remap[row] >= 0]
+        for row, lm in enumerate(self.row_lm):
+            if lm >= 0:
+                self.lm_row[lm] = row
+        self.so_keys["pt"] = [v for row, v in enumerate(self.so_keys["pt"]) if row >= len(remap) or remap[row] >= 0]
+
+    def keyframe_removed(self, row):
+        """the keyframe table closes up: frame 0's row moves, or is gone"""
+        if self.seed_kf is not None:
+            self.seed_kf = None if row == self.seed_kf else self.seed_kf - (row < self.seed_kf)
+
+    def key_point_positions(self, kp_tab, tables=None):
+        """getCloseKeyframes reads key_pts_[k]->feat3D->pos_ as it is NOW: kp_tab [n_kf, 5], positions in the keyframes' point-feature lists
+        (-1 or out of range: none) -> ([n_kf, 5, 3] landmark positions, [n_kf, 5] validity).  Read from the harness's own tables, or from
+        `tables`, a fetched record of the device's (capi.Context.candidates_fetch_map)"""
+        n_kf = len(self.cm["kf_T"])
+        fts, pos = self.cm["kf_pt"], self.cm["pt_pos"]
+        if tables is not None:
+            off, pos = tables["kf_pt_off"], tables["pt_pos"]
+            fts = [tables["kf_pt_lm"][int(off[j]):int(off[j + 1])] for j in range(n_kf)]
+        kpos, kval = np.zeros((n_kf, 5, 3)), np.zeros((n_kf, 5), np.uint8)
+        for j, row in enumerate(kp_tab):
+            for s, h in enumerate(row):
+                lm = int(fts[j][int(h)]) if 0 <= h < len(fts[j]) else -1
+                if lm >= 0:
+                    kpos[j, s], kval[j, s] = pos[lm], 1
+        return kpos, kval
+
+    def follow_selection(self, q_after):
+        """the tables follow the device behind a selection: types, candidate lists, and the keyframe features of the landmarks safeDelete* cut loose"""
+        cm = self.cm
+        for name in ("pt", "seg"):
+            for lm in np.nonzero(q_after[name + "_event"] & abi.LM_EVENT_DELETED)[0]:
+                if cm[name + "_type"][int(lm)] == abi.LM_UNKNOWN:
+                    cm["kf_" + name] = [[-1 if v == lm else v for v in fts] for fts in cm["kf_" + name]]
+            cm[name + "_type"] = [int(v) for v in q_after[name + "_type"]]
+            cm[name + "_cand"] = [int(v) for v in q_after[name + "_cand"]]
+
+
+class _SeedRows:
+    """seeds_resident: the resident seed rows as the harness follows them, one (landmark, or -1: a seed from the image; keyframe row;
+    feature: px / f / level of an image seed) per point row of the device's lists, through removals, starts and erasures"""
+
+    def __init__(self):
+        self.rows, self.n_image_converged = [], 0
+        self.on_device = False                         # the seed lists are staged and their keyframe is still in the table
+        self.last_rows = None                          # image_seeds: pt_status / pt_px_cur of the last update (the occupancy of the next keyframe)
+
+    def lms(self):
+        return np.array([r[0] for r in self.rows], np.int64)
+
+    def n_image(self):
+        return sum(1 for lm, _, _ in self.rows if lm < 0)
+
+    def remove_keyframe(self, row):
+        """removeKeyframe: the seeds of keyframe `row` leave, the rows behind it move down"""
+        self.rows = [(lm, kf - (kf > row), ftr) for lm, kf, ftr in self.rows if kf != row]
+
+    def started(self, n, new_kf, lists):
+        """n image seeds started in keyframe row new_kf, at the back; their features from the fetched lists (both transports), for the
+        landmark a converged one becomes"""
+        first = len(self.rows)
+        assert len(lists["pt_ref_kf"]) == first + n
+        self.rows += [(-1, new_kf, dict(px=_f3(lists["pt_px"][j]), f=_f3(lists["pt_f"][j]), level=int(lists["pt_level"][j]))) for j in range(first, first + n)]
+
+    def drop(self, status):
+        """an update's erasures: converged, NaN and aged rows leave"""
+        self.rows = [r for r, st in zip(self.rows, status) if st not in (abi.SEED_CONVERGED, abi.SEED_NAN, abi.SEED_AGED)]
+
+
+class _Keyframes:
+    """kf_select without keystage: the keyframe table of the synchronous keyframe stage -- per row the pose and the landmark positions of
+    the five key points, snapshotted when the keyframe is added -- and seed_depth, the (depth_mean * 2.0, 0.1 * depth_min) a keyframe's
+    corner seeds start from (:391), which keystage keeps here too"""
+
+    def __init__(self, backend, o, seed_depth):
+        self.backend, self.o, self.seed_depth = backend, o, seed_depth
+        self.T, self.pos, self.valid = [], [], []
+
+    def decide(self, T_new, T_last, px, pos, sp, ep, overlap):
+        kf_T = np.stack(self.T) if self.T else np.zeros((0, 7))
+        return self.backend.keyframe_decide(abi.KeyframeDecideJob(self.o.seq["cam"], T_new, T_last, px, pos, None, sp, ep, None, kf_T, overlap,
+                                                                  (-1,) * 5, self.o.kfselect_mindist_t, self.o.kfselect_mindist_r))
+
+    def add_keyframe(self, T, key_pts, pos):
+        """the keyframe table row: the pose and the landmark positions of the five key points (key_pts index `pos`, -1 = none)"""
+        self.T.append(np.asarray(T, float).copy())
+        self.pos.append(np.array([pos[i] if i >= 0 else np.zeros(3) for i in key_pts]))
+        self.valid.append(np.array([i >= 0 for i in key_pts], np.uint8))
+
+    def remove(self, row):
+        del self.T[row], self.pos[row], self.valid[row]
+
+    def close_job(self, T, max_n_kfs):
+        return abi.CloseKeyframesJob(self.o.seq["cam"], T, np.stack(self.T), np.stack(self.pos), np.stack(self.valid), max_n_kfs)
+
+    def depth_from(self, dec):
+        if dec["has_depth"]:
+            self.seed_depth = (dec["depth_mean"] * 2.0, 0.1 * dec["depth_min"])
+
+
+class _RelocState:
+    """relocalize: the reference's stage machine, and align's hand-over to the next frame"""
+
+    def __init__(self):
+        self.stage, self.gate_dev = "default", None    # "default" | "reloc": STAGE_DEFAULT_FRAME / STAGE_RELOCALIZING; the gate's carried poses on the device
+        self.obs_last, self.obs_resident = None, False  # num_obs_last_pt / _ls, and whether the device holds them
+        self.next_align = None                         # align: the job of the frame to come -- an abi.AlignJob ("host") or True: built on the device
+
+
+class _Frame:
+    """what the steps of one frame hand to one another"""
+
+    def __init__(self, reloc):
+        self.reloc = reloc                             # the frame is a relocalisation attempt
+        self.reloc_kf = self.reloc_tracked = self.T_reset = self.T_ref_kf = None   # its keyframe, n_tracked of the gating alignment, T_f_w_last, the keyframe's pose
+        self.job = self.ar = self.T_k = self.poses_dev = None   # 1: the gathered job, the alignment's result, the aligned pose (host copy, device pointer)
+        self.map_job = self.close = self.cand_rec = None        # 2-3: the stage job if the tables were staged, the close_keyframes report, the candidate stage's record fields
+        self.px_new = self.level = self.pt_ok = self.seg_ok = None   # per landmark (points, segment starts, segment ends): matched px and level; found, per point / segment
+        self.frame_sel = self.sel_mask = None          # cell_select: the frame's selection, and which selected points have a landmark of the harness
+        self.pr = self.pt_i = self.seg_i = self.n_ties = self.gate = None   # 4: the pose optimiser's result, the landmarks of its features, align_ties; the gates' (result, tracking quality)
+        self.T = self.T_last = self.pt_keep = self.seg_keep = self.kept = None   # the optimised pose, last_frame_'s, the keep masks over pt_i / seg_i, pt_i[pt_keep]
+        self.rec = self.dec = self.is_kf = None        # the record, the keyframe decision
+        self.bad_quality, self.kp_frame = False, 0     # TRACKING_BAD; keystage "host": key-point rows rebuilt in this frame
+
+
+_IDENT = [0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0]
+
+
+class _Run:
+    """One run_sequence call: the state that lives from frame to frame, and the steps of FrameHandlerMono::processFrame as methods, in
+    the order process_frame calls them.  A step reads and writes the run's state and the frame's _Frame, nothing else."""
+
+    def __init__(self, o):
+        self.o, self.backend, self.seq, self.cam = o, o.backend, o.seq, o.seq["cam"]
+        seq = o.seq
+        self.chain = hasattr(o.backend, "frame_step")  # steps 1-4 are one resident call
+        self.rs, self.rows = _RelocState(), _SeedRows()
+        self.gate_kw = dict(dict(quality_min_fts=20, quality_max_drop_fts=50), **(o.reloc_params or {}))
+        self.img_kw = dict(dict(fast_threshold=20, detection_threshold=20.0), **(o.image_seed_params or {}))
+        self.kp_tab, self.kp_live = None, False        # keystage: Frame::key_pts_ per keyframe row of cm ("host": kept here; "device": fetched when a restage needs it)
+        o.backend.load_frames(seq["images"])
+        self.n_frames, self.n_pts, self.n_seg = len(seq["images"]), len(seq["pt_pos"]), len(seq["seg_spos"])
+        self.kf_T, self.T_prev = seq["poses_true"][0], seq["poses_true"][0].copy()
+        self.P3 = seq["pt_pos"].copy()                 # the map's point positions (seq["pt_pos"] stays the truth)
+        self.known = np.ones(self.n_pts, bool)
+        self.kf_select = self.detect = False           # the flags where the backend can serve them
+        if o.mapping:
+            self.init_mapping()
+        k0 = np.nonzero(self.known)[0]                 # prev: features of the previous frame that still carry a landmark: index into the map + pixel position
+        self.prev = dict(pt_idx=k0, pt_px=seq["pt_px0"][k0].copy(), seg_idx=np.arange(self.n_seg), seg_spx=seq["seg_spx0"].copy(), seg_epx=seq["seg_epx0"].copy())
+        self.out = [dict(T=self.T_prev.copy(), cov=np.full((6, 6), 1e-9), n_align=0, n_matched_pt=int(self.known.sum()), n_matched_seg=self.n_seg)]
+        if o.map_candidates:
+            self.mt = _MapTables(seq, self.known)
+            self.select_kw = dict(dict(max_fts=120, max_fts_segs=100, cell_order=None, seg_cell_order=None, reproj_thresh=o.reproj_thresh), **(o.select_params or {}))
+            self.align_caps = (max(self.select_kw["max_fts"] + 2, 8), max(self.select_kw["max_fts_segs"] + 2, 8))   # align: the alignment batch's capacities
+
+    def init_mapping(self):
+        """mapping=True: only `known_frac` of the point landmarks start in the map (positions off by `pos_noise` x depth along their viewing
+        ray), the others are depth-filter seeds that turn into landmarks when they converge; the seed update runs every frame; every
+        `kf_every`-th frame plays the keyframe: its matches become observations of their landmarks (Feature3D::obs_ grows at keyframes
+        only, as in the reference) and the 20 least recently refined landmarks with >= 2 observations are structure-optimised.
+        detect and kf_select hold where the backend has detect_corners / keyframe_decide.  With kf_select frame 0 is a keyframe whose key
+        points come from the same call as every other's (no overlap keyframes: nothing else is looked at)."""
+        o, seq, kf_T, P3, n_pts = self.o, self.seq, self.kf_T, self.P3, self.n_pts
+        rng = np.random.default_rng(o.map_seed + 77)
+        known = self.known = rng.uniform(size=n_pts) < o.known_frac
         kf_pos = synth.se3_inv(kf_T)[4:]
         ray = P3 - kf_pos
-        P3[known] = (kf_pos + ray * (1.0 + rng.uniform(-pos_noise, pos_noise, n_pts))[:, None])[known]
+        P3[known] = (kf_pos + ray * (1.0 + rng.uniform(-o.pos_noise, o.pos_noise, n_pts))[:, None])[known]
         depth0 = np.linalg.norm(ray, axis=1)
         dmean, dmin = float(depth0[known].mean()), 0.7 * float(depth0[known].min())
         nsd = int((~known).sum())
-        seeds = dict(idx=np.nonzero(~known)[0], a=np.full(nsd, 10.0, np.float32), b=np.full(nsd, 10.0, np.float32), mu=np.full(nsd, 1.0 / dmean, np.float32),
-                     z_range=np.full(nsd, 1.0 / dmin, np.float32), sigma2=np.full(nsd, (1.0 / dmin) ** 2 / 36.0, np.float32))
-        obs = {int(i): [(0, seq["pt_f0"][i])] for i in range(n_pts)}     # Feature3D::obs_: (frame, unit bearing)
-        last_optim = np.zeros(n_pts, np.int64)
-        poses_est = [kf_T.copy()]
-        detect = detect and hasattr(backend, "detect_corners")
-        img_seeds, img_converged = None, 0
-        w_img, h_img = int(cam[4]), int(cam[5])
+        self.seeds = dict(idx=np.nonzero(~known)[0], a=np.full(nsd, 10.0, np.float32), b=np.full(nsd, 10.0, np.float32), mu=np.full(nsd, 1.0 / dmean, np.float32),
+                          z_range=np.full(nsd, 1.0 / dmin, np.float32), sigma2=np.full(nsd, (1.0 / dmin) ** 2 / 36.0, np.float32))
+        self.obs = {int(i): [(0, seq["pt_f0"][i])] for i in range(n_pts)}     # Feature3D::obs_: (frame, unit bearing)
+        self.last_optim = np.zeros(n_pts, np.int64)
+        self.poses_est = [kf_T.copy()]
+        self.detect = o.detect and hasattr(self.backend, "detect_corners")
+        self.img_seeds, self.img_converged = None, 0
+        self.w_img, self.h_img = int(self.cam[4]), int(self.cam[5])
+        self.kf_select = o.kf_select and hasattr(self.backend, "keyframe_decide")
+        self.kfs = _Keyframes(self.backend, o, (dmean, dmin))
+        if self.kf_select:
+            z3 = np.zeros((0, 3))
+            self.kfs.add_keyframe(kf_T, self.kfs.decide(kf_T, kf_T, seq["pt_px0"][known], P3[known], z3, z3, ())["key_pts"], P3[known])
+        if self.detect:
+            self.img_seeds = self.new_image_seeds(0, seq["pt_px0"][known])
 
-        kf_select = kf_select and hasattr(backend, "keyframe_decide")
-        z3 = np.zeros((0, 3))
+    def run(self):
+        for k in range(1, self.n_frames):
+            self.out.append(self.process_frame(k))
+        if self.o.keystage and self.kp_live:           # Frame::key_pts_ of every keyframe at the end
+            kp = self.kp_tab if self.o.keystage == "host" else self.backend.map_fetch_keypts()[:len(self.mt.cm["kf_T"])]
+            self.out[-1]["key_pts"] = np.array(kp, np.int32).reshape(-1, 5)
+        return self.out
 
-        def decide(T_new, T_last, px, pos, sp, ep, overlap):
-            return backend.keyframe_decide(abi.KeyframeDecideJob(cam, T_new, T_last, px, pos, None, sp, ep, None, np.stack(kfs["T"]), overlap,
-                                                                 (-1,) * 5, kfselect_mindist_t, kfselect_mindist_r))
-
-        def add_keyframe(T, key_pts, pos):
-            """the keyframe table row: the pose and the landmark positions of the five key points (key_pts index `pos`, -1 = none)"""
-            kfs["T"].append(np.asarray(T, float).copy())
-            kfs["pos"].append(np.array([pos[i] if i >= 0 else np.zeros(3) for i in key_pts]))
-            kfs["valid"].append(np.array([i >= 0 for i in key_pts], np.uint8))
-        kfs = dict(T=[kf_T.copy()], pos=[], valid=[])
-        seed_depth = (dmean, dmin)
-        if kf_select:      # frame 0 is a keyframe: its key points come from the same call (no overlap keyframes: nothing else is looked at)
-            kfs["T"] = []
-            d0_ = backend.keyframe_decide(abi.KeyframeDecideJob(cam, kf_T, kf_T, seq["pt_px0"][known], P3[known], None, z3, z3, None, np.zeros((0, 7)), (),
-                                                                (-1,) * 5, kfselect_mindist_t, kfselect_mindist_r))
-            add_keyframe(kf_T, d0_["key_pts"], P3[known])
-
-        def new_image_seeds(frame, feature_px):
-            corners = backend.detect_corners(frame, _occupancy(feature_px, w_img, h_img, detect_cell_size), detect_cell_size, n_pyr_levels)
-            sd = seeds_from_corners(corners, cam, *seed_depth)
-            sd["ref_frame"] = np.full(len(corners), frame, np.int32)
-            return sd
-        if detect:
-            img_seeds = new_image_seeds(0, seq["pt_px0"][known])
-    # features of the previous frame that still carry a landmark: index into the map + pixel position
-    k0 = np.nonzero(known)[0]
-    prev = dict(pt_idx=k0, pt_px=seq["pt_px0"][k0].copy(), seg_idx=np.arange(n_seg), seg_spx=seq["seg_spx0"].copy(),
-                seg_epx=seq["seg_epx0"].copy())
-    out = [dict(T=T_prev.copy(), cov=np.full((6, 6), 1e-9), n_align=0, n_matched_pt=int(known.sum()), n_matched_seg=n_seg)]
-    kf_select = mapping and kf_select
-    f3 = lambda v: [float(x) for x in v]             # plain floats for the map tables below and in the keyframe branch of the loop
-    if map_candidates:
-        # the map tables of the stage: keyframe 0 with the features of the landmarks it starts with, one observation each (newest first later)
-        cm = dict(kf_T=[f3(kf_T)], kf_slot=[0], kf_pt=[[int(i) for i in k0]], kf_seg=[list(range(n_seg))],
-                  pt_pos=None, pt_type=[abi.LM_UNKNOWN] * n_pts,
-                  pt_obs=[[dict(kf=0, px=f3(seq["pt_px0"][i]), f=f3(seq["pt_f0"][i]), level=0, type=abi.FTR_CORNER, grad=[0.0, 0.0])] if known[i] else [] for i in range(n_pts)],
-                  seg_spos=[f3(v) for v in seq["seg_spos"]], seg_epos=[f3(v) for v in seq["seg_epos"]], seg_type=[abi.LM_UNKNOWN] * n_seg,
-                  seg_obs=[[dict(kf=0, spx=f3(seq["seg_spx0"][i]), epx=f3(seq["seg_epx0"][i]), sf=f3(seq["seg_sf0"][i]), ef=f3(seq["seg_ef0"][i]), level=0)]
-                           for i in range(n_seg)], pt_cand=[], seg_cand=[])
-        cm_dirty = True
-        seed_kf = 0                                    # the row of frame 0, where every seed was started (None once kf_insert removed it)
-        # point rows of the tables <-> landmarks (indices of P3 / px_new): the identity until seed_candidates appends a converged seed as a
-        # NEW row (its own row stays behind, empty and in no list); segment rows are segment indices throughout
-        row_lm = list(range(n_pts))
-        lm_row = np.arange(n_pts, dtype=np.int64)
-        quality = None                                 # cell_select: the quality state after the last frame (None: nothing staged yet)
-        so_keys = dict(pt=[], seg=[])                  # structopt_resident: last_structure_optim_ per table row, followed from the reports (0: never refined)
-        select_kw = dict(max_fts=120, max_fts_segs=100, cell_order=None, seg_cell_order=None, reproj_thresh=reproj_thresh)
-        select_kw.update(select_params or {})
-    def align_job_of(k, sel, pr):
-        """frame k + 1's alignment job from frame k's selection and the tables as they stand at this point of frame k"""
-        if align == "device":
-            backend.align_build(k, k + 1, max_level, min_level, max(select_kw["max_fts"] + 2, 8), max(select_kw["max_fts_segs"] + 2, 8))
-            return True
-        return align_job_host(cam, max_level, min_level, sel, pr.pt_keep, pr.seg_keep, cm["pt_type"], cm["seg_type"], cm["pt_pos"], cm["seg_spos"], cm["seg_epos"], pr.T, k, k + 1)
-
-    for k in range(1, len(seq["images"])):
-        reloc_try, T_reset = bool(relocalize) and stage == "reloc", None
-        if reloc_try:
-            # ---- relocalizeFrame (:408-436): the closest keyframe from the last frame's pose, the gating alignment from the identity,
-            #      then processFrame with last_frame_ = ref_keyframe.  (last_frame_ is never a keyframe of the table here: self_kf -1)
-            if cm_dirty:
-                raise ValueError("relocalize: the resident tables wait for a restage")
-            caps = (max(select_kw["max_fts"] + 2, 8, max(len(l) for l in cm["kf_pt"])), max(select_kw["max_fts_segs"] + 2, 8, max(len(l) for l in cm["kf_seg"])))
-            fail = None
-            if relocalize == "device":
-                ar, ref_kf, T_gate, _ = backend.align_kf(None, k, IDENT, max_level, min_level, *caps, T_last=T_prev, last_dev=gate_dev)
-            else:
-                tabs = backend.map_fetch()
-                kp_now = kp_tab if keystage == "host" else backend.map_fetch_keypts()[:len(cm["kf_T"])]
-                n_kf_now = len(cm["kf_T"])
-                kpos, kval = np.zeros((n_kf_now, 5, 3)), np.zeros((n_kf_now, 5), np.uint8)
-                for j, row in enumerate(kp_now):
-                    for s_, h in enumerate(row):
-                        lm = int(tabs["kf_pt_lm"][int(tabs["kf_pt_off"][j]) + int(h)]) if 0 <= h < int(tabs["kf_pt_off"][j + 1]) - int(tabs["kf_pt_off"][j]) else -1
-                        if lm >= 0:
-                            kpos[j, s_], kval[j, s_] = tabs["pt_pos"][lm], 1
-                cl = backend.close_keyframes(abi.CloseKeyframesJob(cam, T_prev, np.asarray(tabs["kf_T"], float).reshape(-1, 7), kpos, kval, max_n_kfs))
-                ar, ref_kf, T_gate = None, -1, None
-                if cl["n_close"] > 0:                  # Map::getClosestKeyframe: the front of the sorted list
-                    ref_kf = int(cl["close_idx"][0])
-                    ar = backend.sparse_align(align_kf_job_host(cam, max_level, min_level, tabs, ref_kf, IDENT, k))
-                    T_gate = np.array(_se3_mul_s(ar.T, tabs["kf_T"][ref_kf]))
-            if ar is None:
-                fail, T_fail, n_tr = "no_keyframe", np.array(IDENT), 0           # "No reference keyframe": new_frame_ keeps its default pose
-            elif ar.n_tracked <= 30:
-                fail, T_fail, n_tr = "gating", np.asarray(T_gate, float).copy(), int(ar.n_tracked)   # (:421; the pose the alignment wrote stays)
-            if fail:
-                out.append(dict(T=T_fail, cov=np.full((6, 6), 1e-9), n_align=n_tr, n_matched_pt=0, n_matched_seg=0, n_kept_pt=0, n_kept_seg=0, stage="reloc",
-                                gate=fail, tracking_quality=abi.TRACKING_INSUFFICIENT, reloc_kf=ref_kf, reloc_tracked=n_tr))
-                if mapping:
-                    poses_est.append(T_fail.copy())
-                T_prev, gate_dev, obs_last, obs_resident, next_align = T_fail, None, (0, 0), False, None   # Frame::nObs() of a frame without features
-                continue
-            T_reset, reloc_kf, reloc_tracked = T_prev, ref_kf, int(ar.n_tracked)     # T_f_w_last
-            T_ref_kf = np.array(cm["kf_T"][ref_kf], float)
-            if relocalize == "device":                 # the second alignment: new_frame_->T_f_w_ = ref_keyframe->T_f_w_ (:266)
-                ar, _, T_k, reloc_dev = backend.align_kf(ref_kf, k, None, max_level, min_level, *caps)
-            else:
-                ar = backend.sparse_align(align_kf_job_host(cam, max_level, min_level, tabs, ref_kf, None, k))
-                T_k, reloc_dev = np.array(_se3_mul_s(ar.T, tabs["kf_T"][ref_kf])), None
-            next_align = None
-        # ---- 1. sparse image alignment, previous frame -> frame k (processFrame :266-274) ----
-        job = None
-        if next_align is None and not reloc_try:       # (align: otherwise the job was made behind the frame before this one)
-            ref_pos = synth.se3_inv(T_prev)[4:]
-
-            def scaled(px, pos):
-                return _bearing(cam, px) * np.linalg.norm(pos - ref_pos, axis=1)[:, None]    # f * |pos - ref_pos| (:229-230)
-            pi, si = prev["pt_idx"], prev["seg_idx"]
-            job = abi.AlignJob(cam, max_level, min_level, 30, 1e-6, synth.se3_mul(T_prev, synth.se3_inv(T_prev)), prev["pt_px"],
-                               scaled(prev["pt_px"], P3[pi]), prev["seg_spx"], prev["seg_epx"],
-                               np.linalg.norm(prev["seg_epx"] - prev["seg_spx"], axis=1), scaled(prev["seg_spx"], seq["seg_spos"][si]),
-                               scaled(prev["seg_epx"], seq["seg_epos"][si]), ref_slot=k - 1, cur_slot=k)
-        pos_all = np.concatenate([P3, seq["seg_spos"], seq["seg_epos"]])
-        if hasattr(backend, "frame_step"):
-            # ---- 1-4 as one resident call: nothing but the final results comes back ----
-            act = np.concatenate([known, np.ones(2 * n_seg, bool)]).astype(np.uint8)
-            ref_px_all = np.concatenate([seq["pt_px0"], seq["seg_spx0"], seq["seg_epx0"]])
-            ref_f_all = np.concatenate([seq["pt_f0"], seq["seg_sf0"], seq["seg_ef0"]])
-            cr = backend.frame_step(job, T_prev, kf_T, 0, n_pts, n_seg, pos_all, ref_px_all, ref_f_all, act, cam, n_pyr_levels, reproj_thresh)
-            ar, pr = cr.align, cr.pose
-            px_new = cr.px
-            pt_i, seg_i = cr.sel_pt.astype(np.int64), cr.sel_seg.astype(np.int64)
-            pt_ok = np.zeros(n_pts, bool); pt_ok[pt_i] = True
-            seg_ok = np.zeros(n_seg, bool); seg_ok[seg_i] = True
+    def process_frame(self, k):
+        """frame k through FrameHandlerMono::processFrame (src/frame_handler_mono.cpp:266-340) and, with mapping, what stands behind it
+        there and in the depth-filter thread.  -> the frame's record"""
+        o = self.o
+        fr = _Frame(bool(o.relocalize) and self.rs.stage == "reloc")
+        failed = self.relocalize_frame(k, fr) if fr.reloc else None
+        if failed:
+            return failed
+        self.align(k, fr)
+        if self.chain:
+            self.track_map_chain(k, fr)
+        elif o.map_candidates:
+            self.track_map_candidates(k, fr)
         else:
-            poses_dev = None
-            if reloc_try:                              # aligned against the keyframe above
-                poses_dev = reloc_dev
-            elif next_align is None:
-                ar = backend.sparse_align(job)
-                T_k = synth.se3_mul(ar.T, T_prev)                                                # :92
-            elif align == "device":                    # the job was built behind the previous frame: run, compose, the pose stays on the device
-                ar, T_k, poses_dev = backend.align_built()
-            else:
-                ar = backend.sparse_align(next_align)
-                T_k = np.array(_se3_mul_s(ar.T, T_prev))
-            next_align = None
-            close = None
-            if map_candidates:
-                # ---- 2 + 3 from the map-candidate stage: overlap keyframes' features, first visit wins, closest-view observation,
-                #      quality order, matched on the device (reprojectMap :157-183, getCloseViewObs, findMatchDirect) ----
-                map_job = None
-                if cm_dirty:
-                    cm["pt_pos"] = [[float(x) for x in P3[i]] for i in row_lm]
-                    map_job = candidate_map_job(cm)
-                    cm_dirty = False
-                kp_frame = 0
-                if keystage:
-                    n_kf_now = len(cm["kf_T"])
-                    if map_job is not None and keystage == "device" and kp_live:
-                        kp_tab = [[int(h) for h in r] for r in backend.map_fetch_keypts()[:n_kf_now]]      # a restage drops the resident table: it travels with the tables
-                    if kp_tab is None and keystage == "host":
-                        kp_tab, _ = _key_point_upkeep(cm, [[-1] * 5] * n_kf_now, cam, fresh=range(n_kf_now))   # Frame::setKeyframe: from five NULLs
-                    kp_live = True
-                    if keystage == "host":
-                        # getCloseKeyframes reads key_pts_[k]->feat3D->pos_ as it is NOW
-                        kpos, kval = np.zeros((n_kf_now, 5, 3)), np.zeros((n_kf_now, 5), np.uint8)
-                        for j, row in enumerate(kp_tab):
-                            for s_, h in enumerate(row):
-                                lm = cm["kf_pt"][j][h] if h >= 0 else -1
-                                if lm >= 0:
-                                    kpos[j, s_], kval[j, s_] = cm["pt_pos"][lm], 1
-                        close = backend.close_keyframes(abi.CloseKeyframesJob(cam, T_k, np.array(cm["kf_T"], float).reshape(-1, 7), kpos, kval, max_n_kfs))
-                        overlap = [int(v) for v in close["close_idx"][:close["n_overlap"]]]
-                    else:
-                        overlap = []                   # decided on the device, from the resident table
-                elif kf_select:
-                    close = backend.close_keyframes(abi.CloseKeyframesJob(cam, T_k, np.stack(kfs["T"]), np.stack(kfs["pos"]), np.stack(kfs["valid"]), max_n_kfs))
-                    overlap = [int(v) for v in close["close_idx"][:close["n_overlap"]]]
-                else:
-                    overlap = list(range(len(cm["kf_T"])))
-                if cell_select:
-                    cm_before = copy.deepcopy(cm) if record_candidates else None
-                    cr, mr, sel, pr_sel, q_after = backend.map_select(map_job, abi.CandidateFrameJob(T_k, overlap, cur_slot=k), cam, n_pyr_levels, select_kw,
-                                                                      carry=quality if map_job is not None else None,
-                                                                      **(dict(close=max_n_kfs, key_pts=kp_tab) if keystage == "device" else {}),
-                                                                      **(dict(poses_dev=poses_dev) if poses_dev else {}))
-                    if keystage == "device":
-                        close = backend.last_close
-                        overlap = [int(v) for v in close["close_idx"][:close["n_overlap"]]]
-                    if structopt_resident and map_job is not None and (any(so_keys["pt"]) or any(so_keys["seg"])):
-                        # the keys do not survive a stage: carried over like the quality counters (rows appended since read 0)
-                        backend.map_set_last_optim(so_keys["pt"] + [0] * (len(cm["pt_pos"]) - len(so_keys["pt"])), so_keys["seg"] + [0] * (len(cm["seg_spos"]) - len(so_keys["seg"])))
-                    if seeds_resident and map_job is not None and mapping and seed_kf is not None:
-                        # the seed lists join the tables that were just staged: every seed was started in frame 0's keyframe, in one batch
-                        # that never ages (the harness keeps its seeds until they converge)
-                        si_ = seeds["idx"]
-                        backend.seeds_stage(dict(batch_counter=0, pt_ref_kf=np.full(len(si_), seed_kf, np.int32), pt_batch_id=np.zeros(len(si_), np.int32), pt_px=seq["pt_px0"][si_],
-                                                 pt_f=seq["pt_f0"][si_], pt_level=np.zeros(len(si_), np.int32), pt_type=np.zeros(len(si_), np.uint8),
-                                                 pt_grad=np.zeros((len(si_), 2)), pt_a=seeds["a"], pt_b=seeds["b"], pt_mu=seeds["mu"], pt_z_range=seeds["z_range"],
-                                                 pt_sigma2=seeds["sigma2"]), cam, max_n_kfs=1 << 30, n_pyr_levels=n_pyr_levels,
-                                            **(dict(room=dict(extra_pt=len(seq["images"]) * (-(-w_img // detect_cell_size)) * (-(-h_img // detect_cell_size)))) if image_seeds else {}))
-                        seeds_on_device = True
-                        res_lm, res_kf, res_ftr = [int(i) for i in si_], [seed_kf] * len(si_), [None] * len(si_)
-                else:
-                    cr, mr = backend.map_candidates(map_job, abi.CandidateFrameJob(T_k, overlap, cur_slot=k), cam, n_pyr_levels)
-                npf, nsf = cr["n_filed_pt"], cr["n_filed_seg"]
-                found = np.zeros(len(pos_all), bool)
-                px_new = np.zeros((len(pos_all), 2))
-                level = np.zeros(len(pos_all), np.int32)
-                at = np.concatenate([np.asarray(row_lm, np.int64)[cr["pt_lm"]], n_pts + cr["seg_lm"], n_pts + n_seg + cr["seg_lm"]]).astype(np.int64)
-                own = at >= 0                          # (image_seeds: a row without a landmark of the harness's map is the device's alone)
-                found[at[own]] = mr["found"].astype(bool)[own]
-                px_new[at[own]] = mr["px"][own]
-                level[at[own]] = np.maximum(mr["search_level"], 0)[own]
-                hist = np.zeros(len(cm["kf_T"]), np.int64)
-                for lm, o in zip(cr["pt_lm"], cr["pt_obs"]):
-                    if o >= 0:
-                        hist[cm["pt_obs"][lm][o]["kf"]] += 1
-                for lm, o in zip(cr["seg_lm"], cr["seg_obs"]):
-                    if o >= 0:
-                        hist[cm["seg_obs"][lm][o]["kf"]] += 1
-                cand_rec = dict(n_filed_pt=npf, n_filed_seg=nsf, ref_kf_hist=[int(v) for v in hist])
-                if record_candidates:
-                    cand_rec["candidates"] = dict(stream=cm_before if cell_select else copy.deepcopy(cm), T=[float(v) for v in T_k], overlap=list(overlap), out=cr, match=mr)
-                if cell_select:
-                    # the tables follow the device: types, candidate lists, and the keyframe features of the landmarks safeDelete* cut loose
-                    for name in ("pt", "seg"):
-                        for lm in np.nonzero(q_after[name + "_event"] & abi.LM_EVENT_DELETED)[0]:
-                            if cm[name + "_type"][int(lm)] == abi.LM_UNKNOWN:
-                                cm["kf_" + name] = [[-1 if v == lm else v for v in fts] for fts in cm["kf_" + name]]
-                        cm[name + "_type"] = [int(v) for v in q_after[name + "_type"]]
-                        cm[name + "_cand"] = [int(v) for v in q_after[name + "_cand"]]
-                    ev = np.concatenate([q_after["pt_event"], q_after["seg_event"]])
-                    cand_rec.update(n_trials=sel["n_trials"], n_promoted=int((ev & abi.LM_EVENT_PROMOTED).astype(bool).sum()),
-                                    n_deleted=int((ev & abi.LM_EVENT_DELETED).astype(bool).sum()))
-                    if record_candidates:
-                        cand_rec["candidates"].update(select=sel, quality_before=quality, quality=q_after, select_params=dict(select_kw))
-                    quality = q_after
-                    if keystage == "host":             # removeKeyPoint of the landmarks the selection deleted
-                        kp_tab, kp_frame = _key_point_upkeep(cm, kp_tab, cam)
-            else:
-                # ---- 2. reprojection of the whole map (Reprojector::reprojectMap) ----
-                rp = backend.reproject(abi.ReprojectJob(cam, np.stack([kf_T, T_k]), np.ones(len(pos_all), np.int32), pos_all, cell_size=30))
-                vis = rp["cell"] >= 0
-                vis[:n_pts] &= known                     # seeds are not in the map yet
-                seg_vis = vis[n_pts:n_pts + n_seg] & vis[n_pts + n_seg:]
-                vis[n_pts:n_pts + n_seg] = seg_vis
-                vis[n_pts + n_seg:] = seg_vis
-                idx = np.nonzero(vis)[0]
-                # ---- 3. direct matching against the keyframe-0 observations (Matcher::findMatchDirect) ----
-                ref_px = np.concatenate([seq["pt_px0"], seq["seg_spx0"], seq["seg_epx0"]])[idx]
-                ref_f = np.concatenate([seq["pt_f0"], seq["seg_sf0"], seq["seg_ef0"]])[idx]
-                m = len(idx)
-                mj = abi.MatchJob(cam, np.stack([kf_T, T_k]), np.array([0, k], np.int32), np.ones(m, np.int32), np.zeros(m, np.int32), ref_px, ref_f,
-                                  np.zeros(m, np.int32), np.zeros(m, np.uint8), np.zeros((m, 2)), pos_all[idx], rp["px"][idx], n_pyr_levels, 10)
-                mr = backend.match_direct(mj)
-                found = np.zeros(len(pos_all), bool)
-                found[idx] = mr["found"].astype(bool)
-                px_new = rp["px"].copy()
-                px_new[idx] = mr["px_cur"]
-                level = np.zeros(len(pos_all), np.int32)
-                level[idx] = np.maximum(mr["search_level"], 0)
-            pt_ok = found[:n_pts]
-            seg_ok = found[n_pts:n_pts + n_seg] & found[n_pts + n_seg:]
-            if cell_select:
-                # ---- 4. on the device: the selected features in selection order, the resident pose optimiser's result ----
-                frame_sel = sel                        # (align: the selection under a name of its own -- step 5 has a `sel` too)
-                pt_i, seg_i = np.asarray(row_lm, np.int64)[sel["pt_lm"]], sel["seg_lm"].astype(np.int64)
-                sel_mask = pt_i >= 0
-                pt_i = pt_i[sel_mask]
-                pt_ok = np.zeros(n_pts, bool); pt_ok[pt_i] = True
-                seg_ok = np.zeros(n_seg, bool); seg_ok[seg_i] = True
-                pr = pr_sel
-        if not hasattr(backend, "frame_step") and not cell_select:
-            # ---- 4. motion-only pose optimisation on the matches (processFrame :327-329) ----
-            pt_i, seg_i = np.nonzero(pt_ok)[0], np.nonzero(seg_ok)[0]
-            sf, ef = _bearing(cam, px_new[n_pts + seg_i]), _bearing(cam, px_new[n_pts + n_seg + seg_i])
-            line = np.cross(sf, ef)
-            line = line / np.sqrt(line[:, 0:1] ** 2 + line[:, 1:2] ** 2) if len(seg_i) else np.zeros((0, 3))    # feature.cpp:103-104
-            pj = abi.PoseOptJob(T_k, abs(cam[0]), reproj_thresh, 10, _bearing(cam, px_new[pt_i]), P3[pt_i], level[pt_i], line,
-                                seq["seg_spos"][seg_i], seq["seg_epos"][seg_i], level[n_pts + n_seg + seg_i])       # a LineFeat's level: the END point's (matcher.cpp:264)
-            pr = backend.pose_optimize(pj)
-        n_ties = backend.align_ties() if hasattr(backend, "align_ties") else None
-        if kf_select and not map_candidates:
-            # ---- the keyframes that overlap the aligned frame (the head of reprojectMap: it runs before the matching, which without
-            #      map_candidates takes its candidates from keyframe 0 either way, so the call's place here does not matter) ----
-            close = backend.close_keyframes(abi.CloseKeyframesJob(cam, synth.se3_mul(ar.T, T_prev), np.stack(kfs["T"]), np.stack(kfs["pos"]),
-                                                                  np.stack(kfs["valid"]), max_n_kfs))
-        T_last = T_ref_kf if reloc_try else T_prev       # last_frame_ of this processFrame
-        bad_quality = False
-        if relocalize:
-            # ---- the gates of processFrame (:315-321, :335) and setTrackingQuality, ahead of the structure optimisation ----
-            if obs_last is None:
-                obs_last = (out[0]["n_matched_pt"], out[0]["n_matched_seg"])
-            T_rs = T_reset if reloc_try else T_prev
-            gk = dict(gate_kw, max_fts=select_kw["max_fts"], max_fts_segs=select_kw["max_fts_segs"])
-            if relocalize == "device":
-                grec, T_carried, gate_dev = backend.track_gate(mode=abi.GATE_RELOC if reloc_try else abi.GATE_TRACK, T_reset=T_rs,
-                                                               **({} if obs_resident and map_job is None else dict(num_obs_last=obs_last)), **gk)
-                g_result, g_quality = grec["result"], grec["tracking_quality"]
-            else:
-                g_result, g_quality, reset = track_gate_host(frame_sel["n_matches"], frame_sel["n_ls_matches"], pr.num_obs_pt, pr.num_obs_ls, *obs_last, relocalizing=reloc_try, **gk)
-                T_carried = np.array(T_rs, float) if reset else pr.T.copy()
-            obs_last, obs_resident = (int(frame_sel["n_matches"]), int(frame_sel["n_ls_matches"])), True
-            if g_result != abi.GATE_OK:                # RESULT_FAILURE: nothing behind the gate runs; the next frame relocalises
-                frec = dict(T=np.asarray(T_carried, float).copy(), cov=pr.cov.copy(), n_align=ar.n_tracked, n_matched_pt=int(pt_ok.sum()), n_matched_seg=int(seg_ok.sum()),
-                            n_kept_pt=int(pr.pt_keep.sum()), n_kept_seg=int(pr.seg_keep.sum()), stage=stage, gate=int(g_result), tracking_quality=int(g_quality))
-                if reloc_try:
-                    frec.update(reloc_kf=reloc_kf, reloc_tracked=reloc_tracked)
-                if map_candidates:
-                    frec.update(cand_rec)
-                if mapping:
-                    poses_est.append(frec["T"].copy())
-                out.append(frec)
-                T_prev, stage, next_align = frec["T"].copy(), "reloc", None
-                continue
-            bad_quality = g_quality == abi.TRACKING_BAD
-        T_k = pr.T.copy()
-        pt_keep, seg_keep = pr.pt_keep.astype(bool), pr.seg_keep.astype(bool)
-        if cell_select and sel_mask is not None:
-            pt_keep = pt_keep[sel_mask]
-        prev = dict(pt_idx=pt_i[pt_keep], pt_px=px_new[pt_i[pt_keep]], seg_idx=seg_i[seg_keep],
-                    seg_spx=px_new[n_pts + seg_i[seg_keep]], seg_epx=px_new[n_pts + n_seg + seg_i[seg_keep]])
-        T_prev = T_k
-        rec = dict(T=T_k.copy(), cov=pr.cov.copy(), n_align=ar.n_tracked, n_matched_pt=int(pt_ok.sum()), n_matched_seg=int(seg_ok.sum()),
-                   n_kept_pt=int(pt_keep.sum()), n_kept_seg=int(seg_keep.sum()))
+            self.track_map_keyframe0(k, fr)
+        if not self.chain and not o.cell_select:
+            self.pose_optimize_host(k, fr)
+        fr.n_ties = self.backend.align_ties() if hasattr(self.backend, "align_ties") else None
+        fr.T_last = fr.T_ref_kf if fr.reloc else self.T_prev     # last_frame_ of this processFrame
+        failed = self.gate(k, fr) if o.relocalize else None
+        if failed:
+            return failed
+        rec = fr.rec = self.tracked(k, fr)
+        if o.mapping:
+            fr.is_kf = (k % o.kf_every) == 0
+            if self.kf_select and not o.keystage:
+                self.decide_keyframe_host(k, fr)
+            if o.structopt_resident:
+                self.structure_resident(k, fr)
+            if o.keystage:
+                self.decide_keyframe(k, fr)
+            if fr.is_kf:
+                for i, brg in zip(fr.kept, _bearing(self.cam, fr.px_new[fr.kept])):
+                    self.obs[int(i)].append((k, brg))
+                if o.kf_insert:
+                    self.insert_keyframe(k, fr)
+                elif o.map_candidates:
+                    self.join_keyframe_host(k, fr)
+            self.structure_host(k, fr)
+            self.update_seeds(k, fr)
+            if self.detect:
+                self.image_seeds_host(k, fr)
+            rec.update(n_known=int(self.known.sum()), n_seeds=len(self.seeds["idx"]),
+                       landmark_err=float(np.median(np.linalg.norm(self.P3[self.known] - self.seq["pt_pos"][self.known], axis=1))))
+        self.queue_next_align(k, fr)
+        return rec
+
+    def record(self, fr, T, cov, n_align, n_matched, n_kept, gate=None, n_ties=None):
+        """the per-frame record of a tracked frame, a failed gate and a failed relocalisation; gate: (result, tracking quality)"""
+        rec = dict(T=T, cov=cov, n_align=n_align, n_matched_pt=n_matched[0], n_matched_seg=n_matched[1], n_kept_pt=n_kept[0], n_kept_seg=n_kept[1])
         if n_ties is not None:
             rec["align_ties"] = n_ties
-        if relocalize:
-            rec.update(stage=stage, gate=int(g_result), tracking_quality=int(g_quality))
-            if reloc_try:
-                rec.update(reloc_kf=reloc_kf, reloc_tracked=reloc_tracked)
-            stage = "default"                          # "Relocalization successful."
-        if map_candidates:
-            rec.update(cand_rec)
-        if mapping:
-            poses_est.append(T_k.copy())
-            kept = pt_i[pt_keep]
-            is_kf = (k % kf_every) == 0
-            if kf_select and not keystage:
-                # ---- scene depth, needNewKf against the overlap keyframes from the previous frame's pose, the frame's key points ----
-                skept = seg_i[seg_keep]
-                dec = decide(T_k, T_last, px_new[kept], P3[kept], seq["seg_spos"][skept], seq["seg_epos"][skept], close["close_idx"][:close["n_overlap"]])
-                is_kf = bool(dec["need_new_kf"])
-                rec.update(is_kf=is_kf, n_overlap=close["n_overlap"], depth_mean=dec["depth_mean"])
-                if is_kf:
-                    add_keyframe(T_k, dec["key_pts"], P3[kept])
-                    if dec["has_depth"]:
-                        seed_depth = (dec["depth_mean"] * 2.0, 0.1 * dec["depth_min"])
-            if structopt_resident:
-                # ---- 5. structure optimisation on the resident tables, ahead of the insertion as in processFrame (:340 before :358) ----
-                for name, rows in (("pt", len(cm["pt_pos"])), ("seg", len(cm["seg_spos"]))):
-                    so_keys[name] += [0] * (rows - len(so_keys[name]))
-                before = (copy.deepcopy(cm), copy.deepcopy(so_keys)) if record_candidates else None
-                so = backend.map_optimize_structure(k)
-                for row, p in zip(so["pt_lm"], so["pt_pos"]):
-                    cm["pt_pos"][int(row)] = [float(x) for x in p]
-                    so_keys["pt"][int(row)] = k
-                    if row_lm[int(row)] >= 0:
-                        P3[row_lm[int(row)]] = p
-                for row, a, b in zip(so["seg_lm"], so["seg_spos"], so["seg_epos"]):
-                    cm["seg_spos"][int(row)], cm["seg_epos"][int(row)] = [float(x) for x in a], [float(x) for x in b]
-                    so_keys["seg"][int(row)] = k
-                rec.update(n_structopt_pt=int(so["n_sel_pt"]), n_structopt_seg=int(so["n_sel_seg"]))
-                if record_candidates:
-                    rec["structopt"] = dict(stream=before[0], keys_before=before[1], select=sel, pt_keep=pr.pt_keep.copy(), seg_keep=pr.seg_keep.copy(), frame_id=k, report=so,
-                                            tables=copy.deepcopy(cm), keys=copy.deepcopy(so_keys))
-            if keystage:
-                # ---- the keyframe decision behind the structure optimisation (:340 before :351), on the selection with the keep masks as
-                #      alive and the landmark positions as the tables hold them now; key_pts are indices in selection order ----
-                if keystage == "device":
-                    dec = backend.map_keyframe_decide(T_last, kfselect_mindist_t, kfselect_mindist_r)
-                else:
-                    at = lambda name, rows: np.array([cm[name][int(r)] for r in rows], float).reshape(-1, 3)
-                    dec = backend.keyframe_decide(abi.KeyframeDecideJob(cam, T_k, T_last, sel["pt_px"], at("pt_pos", sel["pt_lm"]), pr.pt_keep, at("seg_spos", sel["seg_lm"]),
-                                                                        at("seg_epos", sel["seg_lm"]), pr.seg_keep, np.array(cm["kf_T"], float).reshape(-1, 7),
-                                                                        close["close_idx"][:close["n_overlap"]], (-1,) * 5, kfselect_mindist_t, kfselect_mindist_r))
-                is_kf = bool(dec["need_new_kf"]) and not bad_quality       # (!needNewKf || TRACKING_BAD: no keyframe, :352)
-                rec.update(is_kf=is_kf, n_overlap=close["n_overlap"], depth_mean=dec["depth_mean"], overlap=[int(v) for v in close["close_idx"][:close["n_overlap"]]])
-                if is_kf:
-                    rec["key_pts_new"] = [int(h) for h in dec["key_pts"]]      # the frame's key_pts_ as it becomes a keyframe, in selection order
-                if is_kf and dec["has_depth"]:
-                    seed_depth = (dec["depth_mean"] * 2.0, 0.1 * dec["depth_min"])
-            if is_kf:
-                for i, brg in zip(kept, _bearing(cam, px_new[kept])):
-                    obs[int(i)].append((k, brg))
-                if kf_insert:
-                    # the frame joins the RESIDENT tables on the device; the harness's own follow the backend's fetch
-                    remove = -1
-                    if kf_select and len(cm["kf_T"]) >= max_n_kfs:
-                        remove = max(int(dec["furthest_kf"]), 0)
-                        for key in ([] if keystage else kfs):
-                            del kfs[key][remove]
-                        if seed_kf is not None:                       # the table closes up: frame 0's row moves, or is gone
-                            seed_kf = None if remove == seed_kf else seed_kf - (remove < seed_kf)
-                    before = (copy.deepcopy(cm), quality) if record_candidates else None
-                    tables, quality, ins = backend.map_insert(remove, k)
-                    cm = candidate_map_tables(tables)
-                    if keystage == "host":             # the rows close up, the new keyframe's row is the decision's, holders lost to the removal are replaced
-                        kp_tab, n_ = _key_point_upkeep(cm, [r for j, r in enumerate(kp_tab) if j != remove] + [[int(h) for h in dec["key_pts"]]], cam)
-                        kp_frame += n_
-                    if seeds_on_device and image_seeds and seed_kf is not None:
-                        # initializeSeeds on the resident lists: the removal, then the corners of the frame's free cells (DESIGN.md 3.16)
-                        new_kf = len(cm["kf_T"]) - 1
-                        assert ins.get("new_kf", new_kf) == new_kf and cm["kf_slot"][new_kf] == k
-                        ev = dict(removed_kf=remove, new_batch=True, new_kf=new_kf, depth_mean=seed_depth[0], depth_min=seed_depth[1])
-                        if image_seeds == "device":
-                            backend.seeds_keyframe_detect(detect_cell_size, n_pyr_levels, img_kw["detection_threshold"], fast_threshold=img_kw["fast_threshold"],
-                                                          occ_sources=abi.SEED_OCC_SELECTED | (abi.SEED_OCC_UPDATED if last_rows is not None else 0), **ev)
-                            kf_rep = backend.seeds_keyframe_fetch()
-                            assert not kf_rep["no_room"]
-                            n_started = kf_rep["n_new_pt"]
-                        else:
-                            marking = np.zeros((0, 2))
-                            if last_rows is not None:
-                                stl = last_rows["pt_status"]
-                                marking = last_rows["pt_px_cur"][(stl == abi.SEED_UPDATED) | (stl == abi.SEED_CONVERGED) | (stl == abi.SEED_NAN)]
-                            occ = _occupancy(np.concatenate([sel["pt_px"].reshape(-1, 2), marking]), w_img, h_img, detect_cell_size)
-                            corners = backend.detect_corners(k, occ, detect_cell_size, n_pyr_levels, img_kw["detection_threshold"], fast_threshold=img_kw["fast_threshold"])
-                            sdn = seeds_from_corners(corners, cam, *seed_depth)
-                            backend.seeds_keyframe(pt_px=sdn["px"], pt_f=sdn["f"], pt_level=sdn["level"], pt_type=sdn["type"], pt_grad=sdn["grad"], **ev)
-                            n_started = len(corners)
-                        if remove >= 0:
-                            stay = [j for j, r in enumerate(res_kf) if r != remove]
-                            res_lm, res_ftr = [res_lm[j] for j in stay], [res_ftr[j] for j in stay]
-                            res_kf = [res_kf[j] - (res_kf[j] > remove) for j in stay]
-                        if n_started:                                  # the new rows' features, for the landmark a converged one becomes (both transports: from the lists)
-                            ls = backend.seeds_fetch_lists()
-                            assert len(ls["pt_ref_kf"]) == len(res_lm) + n_started
-                            for j in range(len(res_lm), len(res_lm) + n_started):
-                                res_ftr.append(dict(px=[float(x) for x in ls["pt_px"][j]], f=[float(x) for x in ls["pt_f"][j]], level=int(ls["pt_level"][j])))
-                            res_lm += [-1] * n_started; res_kf += [new_kf] * n_started
-                        rec["n_image_seeds_started"] = int(n_started)
-                    elif seeds_on_device and remove >= 0:              # removeKeyframe: the seeds' keyframe moves down a row, or leaves with its seeds
-                        backend.seeds_keyframe(removed_kf=remove)
-                        seeds_on_device = seed_kf is not None
-                        res_lm, res_kf, res_ftr = [], [], []
-                    rec.update(n_joined=ins["n_joined_pt"] + ins["n_joined_seg"], n_deleted_kf=ins["n_deleted_pt"] + ins["n_deleted_seg"], remove_kf=remove)
-                    if keystage == "host":
-                        rec["n_kp_rebuilt"] = int(kp_frame)
-                    if align and compact and k + 1 < len(seq["images"]):
-                        next_align = align_job_of(k, frame_sel, pr)    # ahead of the compaction, which renumbers the rows the selection points at
-                    if compact:
-                        # Map::emptyTrash on the resident tables: the deleted point rows leave, the rows behind them move down; the
-                        # harness's rows follow the remap ("room": only when every live seed could no longer get a row)
-                        alive = len(seeds["idx"]) + sum(1 for v in res_lm if v < 0)
-                        tables, quality, cp = backend.map_compact("room", (1 << 30) if compact == "always" else alive, 0)
-                        if cp["ran_pt"]:
-                            cm = candidate_map_tables(tables)
-                            remap = cp["pt_remap"]
-                            lm_row[[lm for row, lm in enumerate(row_lm) if lm >= 0 and remap[row] < 0]] = -1
-                            row_lm = [lm for row, lm in enumerate(row_lm) if remap[row] >= 0]
-                            for row, lm in enumerate(row_lm):
-                                if lm >= 0:
-                                    lm_row[lm] = row
-                            so_keys["pt"] = [v for row, v in enumerate(so_keys["pt"]) if row >= len(remap) or remap[row] >= 0]
-                        rec["n_compacted_pt"] = int(cp["n_pt_before"] - cp["n_pt_after"])
-                    if record_candidates:
-                        rec["insert"] = dict(stream=before[0], quality_before=before[1], select=sel, pt_keep=pr.pt_keep.copy(), seg_keep=pr.seg_keep.copy(), T=[float(v) for v in T_k],
-                                             slot=k, remove_kf=remove, tables=tables, quality=quality, report=ins)
-                elif map_candidates:
-                    # the frame joins the keyframe table: its features, and an observation at the FRONT of every landmark's list
-                    # (Feature3D::addFrameRef pushes at the front, include/plsvo/feature3D.h:204); a candidate it matched leaves the
-                    # map's candidate list for the keyframe's features
-                    skept_ = seg_i[seg_keep]
-                    kf_id = len(cm["kf_T"])
-                    cm["kf_T"].append(f3(T_k)); cm["kf_slot"].append(k)
-                    cm["kf_pt"].append([int(i) for i in kept]); cm["kf_seg"].append([int(i) for i in skept_])
-                    for i, brg in zip(kept, _bearing(cam, px_new[kept])):
-                        cm["pt_obs"][int(i)].insert(0, dict(kf=kf_id, px=f3(px_new[i]), f=f3(brg), level=int(level[i]), type=abi.FTR_CORNER, grad=[0.0, 0.0]))
-                        if not cell_select or cm["pt_type"][int(i)] == abi.LM_CANDIDATE:      # (a candidate that joins a keyframe: TYPE_UNKNOWN)
-                            cm["pt_type"][int(i)] = abi.LM_UNKNOWN
-                    for i, sb, eb in zip(skept_, _bearing(cam, px_new[n_pts + skept_]), _bearing(cam, px_new[n_pts + n_seg + skept_])):
-                        cm["seg_obs"][int(i)].insert(0, dict(kf=kf_id, spx=f3(px_new[n_pts + i]), epx=f3(px_new[n_pts + n_seg + i]), sf=f3(sb), ef=f3(eb),
-                                                             level=int(level[n_pts + i])))
-                    matched = set(int(v) for v in kept)
-                    cm["pt_cand"] = [i for i in cm["pt_cand"] if i not in matched]
-                    cm_dirty = True
-            # ---- 5. structure optimisation (FrameHandlerBase::optimizeStructure: the 20 least recently refined, :202-237) ----
-            cand = np.array([i for i in kept if len(obs[int(i)]) >= 2], np.int64)
-            if len(cand) and is_kf and not structopt_resident:
-                sel = cand[np.argsort(last_optim[cand], kind="stable")[:20]]
-                off, ofr, of_ = [0], [], []
-                for i in sel:
-                    for fr_, brg in obs[int(i)]:
-                        ofr.append(fr_)
-                        of_.append(brg)
-                    off.append(len(ofr))
-                z3, zi = np.zeros((0, 3)), np.zeros(0, np.int32)
-                so = backend.structure_optimize(abi.StructOptJob(np.stack(poses_est), P3[sel], off, ofr, np.array(of_), z3, z3, np.zeros(1, np.int32), zi, z3, z3, 5, 5))
-                P3[sel] = so["pt_pos"]
-                last_optim[sel] = k
-                if kf_insert:
-                    backend.map_set_positions(lm_row[sel].astype(np.int32), P3[sel])
-                    for i in sel:
-                        cm["pt_pos"][int(lm_row[i])] = [float(x) for x in P3[i]]
-                elif map_candidates:
-                    cm_dirty = True
-            # ---- 6. depth-filter update of the seeds with this frame (DepthFilter::updateSeeds) ----
-            ns = len(seeds["idx"])
-            img_dev = bool(image_seeds) and seeds_on_device    # the resident rows hold seeds from the image beside the map's
-            if ns or (img_dev and res_lm):
-                si_ = seeds["idx"]
-                ptd = dict(ref_frame=np.zeros(ns, np.int32), cur_frame=np.ones(ns, np.int32), px=seq["pt_px0"][si_], f=seq["pt_f0"][si_], level=np.zeros(ns, np.int32),
-                           a=seeds["a"], b=seeds["b"], mu=seeds["mu"], z_range=seeds["z_range"], sigma2=seeds["sigma2"])
-                if seeds_on_device:                               # on the resident lists: the report and the rows come back, no record travels
-                    seed_report, sr, seed_quality = backend.seeds_update(k, T_k)
-                    assert len(sr["pt_status"]) == (len(res_lm) if img_dev else ns) and seed_report["no_room"] == 0
-                    if img_dev:                                   # the map's seeds are the rows with a landmark, in the order of seeds["idx"]
-                        all_rows, is_map = sr, np.asarray(res_lm, np.int64) >= 0
-                        last_rows = dict(pt_status=sr["pt_status"].copy(), pt_px_cur=sr["pt_px_cur"].copy())
-                        assert np.array_equal(np.asarray(res_lm, np.int64)[is_map], si_)
-                        sr = {f: v[is_map] for f, v in sr.items() if f.startswith("pt_")}
-                else:
-                    sr = backend.update_seeds(abi.SeedsJob(cam, np.stack([kf_T, T_k]), np.array([0, k], np.int32), ptd, None, n_pyr_levels=n_pyr_levels))
-                stt = sr["pt_status"]
-                conv = stt == abi.SEED_CONVERGED
-                P3[si_[conv]] = sr["pt_xyz_world"][conv]
-                known[si_[conv]] = True
-                if img_dev:
-                    # every converged row, from the map or from the image, is a new landmark row of the resident tables, in list order
-                    st_all = all_rows["pt_status"]
-                    for j, r in enumerate(np.nonzero(st_all == abi.SEED_CONVERGED)[0]):
-                        row, lm = len(cm["pt_pos"]), res_lm[r]
-                        assert row == seed_report["first_pt"] + j
-                        if lm >= 0:
-                            ftr = dict(px=[float(x) for x in seq["pt_px0"][lm]], f=[float(x) for x in seq["pt_f0"][lm]], level=0, grad=[0.0, 0.0])
-                            lm_row[lm] = row
-                        else:
-                            ftr = dict(res_ftr[r], grad=[1.0, 0.0])
-                            img_conv += 1
-                        cm["pt_pos"].append([float(x) for x in all_rows["pt_xyz_world"][r]])
-                        cm["pt_type"].append(abi.LM_CANDIDATE)
-                        cm["pt_obs"].append([dict(kf=res_kf[r], px=ftr["px"], f=ftr["f"], level=ftr["level"], type=abi.FTR_CORNER, grad=ftr["grad"])])
-                        cm["pt_cand"].append(row)
-                        row_lm.append(lm)
-                        quality = seed_quality
-                    stay = [r for r in range(len(res_lm)) if st_all[r] not in (abi.SEED_CONVERGED, abi.SEED_NAN, abi.SEED_AGED)]
-                    res_lm, res_kf, res_ftr = [res_lm[r] for r in stay], [res_kf[r] for r in stay], [res_ftr[r] for r in stay]
-                    rec.update(n_image_seeds=sum(1 for v in res_lm if v < 0), n_image_seeds_converged=img_conv)
-                elif seed_candidates and conv.any() and seed_kf is not None:
-                    # the converged seeds join the RESIDENT tables on the device as new landmark rows (newCandidatePoint); the harness
-                    # appends the same rows to its own
-                    ci = [int(i) for i in si_[conv]]
-                    new = dict(pt_pos=sr["pt_xyz_world"][conv], pt_obs_kf=np.full(len(ci), seed_kf, np.int32), pt_obs_px=seq["pt_px0"][ci], pt_obs_f=seq["pt_f0"][ci],
-                               pt_obs_level=np.zeros(len(ci), np.int32), pt_obs_type=np.full(len(ci), abi.FTR_CORNER, np.uint8), pt_obs_grad=np.zeros((len(ci), 2)))
-                    before = (copy.deepcopy(cm), quality) if record_candidates else None
-                    if seeds_on_device:                           # the commit has appended them already: its report stands in for the add's
-                        report = dict(first_pt=seed_report["first_pt"], first_seg=-1, n_added_pt=len(ci), n_added_seg=0, n_pt=seed_report["n_pt"], n_seg=seed_report["n_seg"],
-                                      n_pt_cand=seed_report["n_pt_cand"], n_seg_cand=seed_report["n_seg_cand"], n_pt_obs=seed_report["n_pt_obs"], n_seg_obs=seed_report["n_seg_obs"])
-                        quality = seed_quality
-                    else:
-                        report, quality = backend.map_add_candidates(new)
-                    for j, i in enumerate(ci):
-                        row = len(cm["pt_pos"])
-                        assert row == report["first_pt"] + j
-                        cm["pt_pos"].append([float(x) for x in P3[i]])
-                        cm["pt_type"].append(abi.LM_CANDIDATE)
-                        cm["pt_obs"].append([dict(kf=seed_kf, px=[float(x) for x in seq["pt_px0"][i]], f=[float(x) for x in seq["pt_f0"][i]], level=0,
-                                                  type=abi.FTR_CORNER, grad=[0.0, 0.0])])
-                        cm["pt_cand"].append(row)
-                        row_lm.append(i); lm_row[i] = row
-                    if record_candidates:
-                        rec["add"] = dict(stream=before[0], quality_before=before[1], new=new, tables=copy.deepcopy(cm), quality=quality, report=report)
-                elif map_candidates and conv.any() and seed_kf is not None:
-                    # a converged seed becomes a candidate of the map (map_.point_candidates_), observed in the keyframe it was started in
-                    # (frame 0; once that keyframe has left the table the seed's only observation is gone with it, as
-                    # removeFrameCandidates would delete it: the landmark stays outside the map's tables)
-                    for i in si_[conv]:
-                        cm["pt_obs"][int(i)] = [dict(kf=seed_kf, px=[float(x) for x in seq["pt_px0"][i]], f=[float(x) for x in seq["pt_f0"][i]], level=0,
-                                                     type=abi.FTR_CORNER, grad=[0.0, 0.0])]
-                        cm["pt_type"][int(i)] = abi.LM_CANDIDATE
-                        cm["pt_cand"].append(int(i))
-                    cm_dirty = True
-                keep_s = ~(conv | (stt == abi.SEED_NAN))
-                seeds = dict(idx=si_[keep_s], a=sr["pt_a"][keep_s], b=sr["pt_b"][keep_s], mu=sr["pt_mu"][keep_s], z_range=seeds["z_range"][keep_s],
-                             sigma2=sr["pt_sigma2"][keep_s])
-                rec["n_seed_converged"] = int(conv.sum())
-                if kf_insert:
-                    rec["n_seed_candidates"] = int(conv.sum()) if seed_kf is not None else 0
-            if detect:
-                # ---- 7. the seeds that came from the image: updated with this frame; a keyframe adds those of its own free cells ----
-                ni = len(img_seeds["px"])
-                if ni:
-                    sr = backend.update_seeds(abi.SeedsJob(cam, np.stack(poses_est), np.arange(len(poses_est), dtype=np.int32),
-                                                           dict(img_seeds, cur_frame=np.full(ni, k, np.int32)), None, n_pyr_levels=n_pyr_levels))
-                    stt = sr["pt_status"]
-                    img_converged += int((stt == abi.SEED_CONVERGED).sum())
-                    keep_s = ~((stt == abi.SEED_CONVERGED) | (stt == abi.SEED_NAN))
-                    img_seeds = {key: v[keep_s] for key, v in img_seeds.items()}
-                    for key in ("a", "b", "mu", "sigma2"):
-                        img_seeds[key] = sr["pt_" + key][keep_s]
-                if is_kf:
-                    fresh = new_image_seeds(k, px_new[kept])
-                    img_seeds = {key: np.concatenate([img_seeds[key], fresh[key]]) for key in img_seeds}
-                rec.update(n_image_seeds=len(img_seeds["px"]), n_image_seeds_converged=img_converged)
-            rec.update(n_known=int(known.sum()), n_seeds=len(seeds["idx"]),
-                       landmark_err=float(np.median(np.linalg.norm(P3[known] - seq["pt_pos"][known], axis=1))))
-        if align and next_align is None and k + 1 < len(seq["images"]) and not cm_dirty:
-            # behind everything that moves a landmark in this frame.  Tables that wait for a restage no longer say what the harness's own do:
-            # the frame behind them is staged by the host as without the flag
-            next_align = align_job_of(k, frame_sel, pr)
-        out.append(rec)
-    if keystage and kp_live:                           # Frame::key_pts_ of every keyframe at the end
-        out[-1]["key_pts"] = np.array(kp_tab if keystage == "host" else backend.map_fetch_keypts()[:len(cm["kf_T"])], np.int32).reshape(-1, 5)
-    return out
+        if gate is not None:
+            rec.update(stage=self.rs.stage, gate=gate[0], tracking_quality=gate[1])
+            if fr.reloc:
+                rec.update(reloc_kf=fr.reloc_kf, reloc_tracked=fr.reloc_tracked)
+        if fr.cand_rec is not None:
+            rec.update(fr.cand_rec)
+        if self.o.mapping:
+            self.poses_est.append(T.copy())
+        return rec
+
+    def pos_all(self):
+        return np.concatenate([self.P3, self.seq["seg_spos"], self.seq["seg_epos"]])
+
+    def relocalize_frame(self, k, fr):
+        """relocalize="host" | "device": the harness plays the reference's stage machine, STAGE_DEFAULT_FRAME <-> STAGE_RELOCALIZING
+        (finishFrameProcessingCommon).  A frame that fails the gates (gate) is carried forward with the pose the gate
+        gives and the next frame relocalises against the closest keyframe of the resident tables until a frame passes the gates again:
+        relocalizeFrame (:408-436) is Map::getClosestKeyframe from the last frame's pose, a gating alignment against that keyframe from the
+        identity that must track more than 30, a second alignment from the keyframe's own pose (new_frame_->T_f_w_ =
+        ref_keyframe->T_f_w_, :266), and the rest of processFrame with last_frame_ = ref_keyframe, whose every failure carries the last
+        frame's pose; a success returns to STAGE_DEFAULT_FRAME.  (last_frame_ is never a keyframe of the table here: self_kf -1.)
+        "device" uses plsvo_candidates_align_build_kf (a backend with align_kf / track_gate); "host" does the same with the calls there
+        were before -- fetched tables, close_keyframes, align_kf_job_host staged through plsvo_align_stage.  The two differ in transport
+        alone and agree in every record.  One of the two host waits of "device" is here: n_tracked behind the gating alignment.
+        The tables must not wait for a restage while a stream relocalises (kf_insert with seed_candidates keeps them resident).
+        -> the failure's record, or None: fr holds the alignment against the keyframe (ar, T_k, poses_dev)"""
+        o, backend, mt, rs = self.o, self.backend, self.mt, self.rs
+        if mt.dirty:
+            raise ValueError("relocalize: the resident tables wait for a restage")
+        caps = (max(self.align_caps[0], max(len(l) for l in mt.cm["kf_pt"])), max(self.align_caps[1], max(len(l) for l in mt.cm["kf_seg"])))
+        if o.relocalize == "device":
+            ar, fr.reloc_kf, T_gate, _ = backend.align_kf(None, k, _IDENT, o.max_level, o.min_level, *caps, T_last=self.T_prev, last_dev=rs.gate_dev)
+        else:
+            tabs = backend.map_fetch()
+            kp_now = self.kp_tab if o.keystage == "host" else backend.map_fetch_keypts()[:len(mt.cm["kf_T"])]
+            kpos, kval = mt.key_point_positions(kp_now, tabs)
+            cl = backend.close_keyframes(abi.CloseKeyframesJob(self.cam, self.T_prev, np.asarray(tabs["kf_T"], float).reshape(-1, 7), kpos, kval, o.max_n_kfs))
+            ar, fr.reloc_kf, T_gate = None, -1, None
+            if cl["n_close"] > 0:                      # Map::getClosestKeyframe: the front of the sorted list
+                fr.reloc_kf = int(cl["close_idx"][0])
+                ar = backend.sparse_align(align_kf_job_host(self.cam, o.max_level, o.min_level, tabs, fr.reloc_kf, _IDENT, k))
+                T_gate = np.array(_se3_mul_s(ar.T, tabs["kf_T"][fr.reloc_kf]))
+        fr.reloc_tracked = 0 if ar is None else int(ar.n_tracked)
+        if ar is None or ar.n_tracked <= 30:
+            # "No reference keyframe": new_frame_ keeps its default pose; the gating alignment (:421): the pose it wrote stays
+            fail, T_fail = ("no_keyframe", np.array(_IDENT)) if ar is None else ("gating", np.asarray(T_gate, float).copy())
+            rec = self.record(fr, T_fail, np.full((6, 6), 1e-9), fr.reloc_tracked, (0, 0), (0, 0), gate=(fail, abi.TRACKING_INSUFFICIENT))
+            self.T_prev, rs.gate_dev, rs.obs_last, rs.obs_resident, rs.next_align = T_fail, None, (0, 0), False, None   # Frame::nObs() of a frame without features
+            return rec
+        fr.T_reset = self.T_prev                       # T_f_w_last
+        fr.T_ref_kf = np.array(mt.cm["kf_T"][fr.reloc_kf], float)
+        if o.relocalize == "device":
+            fr.ar, _, fr.T_k, fr.poses_dev = backend.align_kf(fr.reloc_kf, k, None, o.max_level, o.min_level, *caps)
+        else:
+            fr.ar = backend.sparse_align(align_kf_job_host(self.cam, o.max_level, o.min_level, tabs, fr.reloc_kf, None, k))
+            fr.T_k = np.array(_se3_mul_s(fr.ar.T, tabs["kf_T"][fr.reloc_kf]))
+        rs.next_align = None
+        return None
+
+    def align(self, k, fr):
+        """1. sparse image alignment, previous frame -> frame k (processFrame :266-274; T_k = T_cur_from_ref * T_prev, :92).  The job:
+          - gathered here from the previous frame's kept features (f * |pos - ref_pos|, :229-230) -- every frame without align, and
+            with it the first frame and a frame behind one that left the tables waiting for a restage (a keyframe without kf_insert, a
+            converged seed without seed_candidates): the resident tables are then behind the harness's own; the resident chain runs
+            it inside frame_step;
+          - align="host": the abi.AlignJob queue_next_align left, staged through plsvo_align_stage;
+          - align="device": built on the device behind the previous frame: run, compose, the pose stays on the device and reaches the
+            candidate stage by device pointer (poses_dev);
+          - a relocalising frame is aligned against its keyframe already (relocalize_frame)."""
+        rs, backend = self.rs, self.backend
+        if rs.next_align is None and not fr.reloc:
+            prev, seq, scaled = self.prev, self.seq, self.scaled_bearing
+            fr.job = abi.AlignJob(self.cam, self.o.max_level, self.o.min_level, 30, 1e-6, synth.se3_mul(self.T_prev, synth.se3_inv(self.T_prev)), prev["pt_px"],
+                                  scaled(prev["pt_px"], self.P3[prev["pt_idx"]]), prev["seg_spx"], prev["seg_epx"],
+                                  np.linalg.norm(prev["seg_epx"] - prev["seg_spx"], axis=1), scaled(prev["seg_spx"], seq["seg_spos"][prev["seg_idx"]]),
+                                  scaled(prev["seg_epx"], seq["seg_epos"][prev["seg_idx"]]), ref_slot=k - 1, cur_slot=k)
+        if self.chain or fr.reloc:
+            return
+        if rs.next_align is None:
+            fr.ar = backend.sparse_align(fr.job)
+            fr.T_k = synth.se3_mul(fr.ar.T, self.T_prev)
+        elif self.o.align == "device":
+            fr.ar, fr.T_k, fr.poses_dev = backend.align_built()
+        else:
+            fr.ar = backend.sparse_align(rs.next_align)
+            fr.T_k = np.array(_se3_mul_s(fr.ar.T, self.T_prev))
+        rs.next_align = None
+
+    def scaled_bearing(self, px, pos):
+        """f * |pos - ref_pos| of a feature of the previous frame (:229-230)"""
+        return _bearing(self.cam, px) * np.linalg.norm(pos - synth.se3_inv(self.T_prev)[4:], axis=1)[:, None]
+
+    def track_map_chain(self, k, fr):
+        """1-4 as one resident call (HipChainBackend.frame_step): nothing but the final results comes back"""
+        seq, n_pts, n_seg = self.seq, self.n_pts, self.n_seg
+        act = np.concatenate([self.known, np.ones(2 * n_seg, bool)]).astype(np.uint8)
+        ref_px_all = np.concatenate([seq["pt_px0"], seq["seg_spx0"], seq["seg_epx0"]])
+        ref_f_all = np.concatenate([seq["pt_f0"], seq["seg_sf0"], seq["seg_ef0"]])
+        cr = self.backend.frame_step(fr.job, self.T_prev, self.kf_T, 0, n_pts, n_seg, self.pos_all(), ref_px_all, ref_f_all, act, self.cam, self.o.n_pyr_levels, self.o.reproj_thresh)
+        fr.ar, fr.pr, fr.px_new, fr.T_k = cr.align, cr.pose, cr.px, synth.se3_mul(cr.align.T, self.T_prev)
+        fr.pt_i, fr.seg_i = cr.sel_pt.astype(np.int64), cr.sel_seg.astype(np.int64)
+        fr.pt_ok = np.zeros(n_pts, bool); fr.pt_ok[fr.pt_i] = True
+        fr.seg_ok = np.zeros(n_seg, bool); fr.seg_ok[fr.seg_i] = True
+
+    def track_map_keyframe0(self, k, fr):
+        """2. reprojection of the whole map (Reprojector::reprojectMap) and 3. direct matching against the keyframe-0 observations
+        (Matcher::findMatchDirect); seeds are not in the map yet"""
+        seq, n_pts, n_seg, pos_all = self.seq, self.n_pts, self.n_seg, self.pos_all()
+        frame_T = np.stack([self.kf_T, fr.T_k])
+        rp = self.backend.reproject(abi.ReprojectJob(self.cam, frame_T, np.ones(len(pos_all), np.int32), pos_all, cell_size=30))
+        vis = rp["cell"] >= 0
+        vis[:n_pts] &= self.known
+        seg_vis = vis[n_pts:n_pts + n_seg] & vis[n_pts + n_seg:]
+        vis[n_pts:n_pts + n_seg] = vis[n_pts + n_seg:] = seg_vis
+        idx = np.nonzero(vis)[0]
+        ref_px = np.concatenate([seq["pt_px0"], seq["seg_spx0"], seq["seg_epx0"]])[idx]
+        ref_f = np.concatenate([seq["pt_f0"], seq["seg_sf0"], seq["seg_ef0"]])[idx]
+        m = len(idx)
+        mr = self.backend.match_direct(abi.MatchJob(self.cam, frame_T, np.array([0, k], np.int32), np.ones(m, np.int32), np.zeros(m, np.int32), ref_px, ref_f,
+                                                    np.zeros(m, np.int32), np.zeros(m, np.uint8), np.zeros((m, 2)), pos_all[idx], rp["px"][idx], self.o.n_pyr_levels, 10))
+        found = np.zeros(len(pos_all), bool)
+        found[idx] = mr["found"].astype(bool)
+        fr.px_new = rp["px"].copy()
+        fr.px_new[idx] = mr["px_cur"]
+        fr.level = np.zeros(len(pos_all), np.int32)
+        fr.level[idx] = np.maximum(mr["search_level"], 0)
+        fr.pt_ok, fr.seg_ok = found[:n_pts], found[n_pts:n_pts + n_seg] & found[n_pts + n_seg:]
+
+    def overlap_keyframes(self, k, fr):
+        """the frame's overlap list for the candidate stage: the one of plsvo_close_keyframes with kf_select, otherwise every keyframe in
+        table order.
+        keystage="host" | "device": the keyframe stage follows the reference instead of snapshotting a key point's position when its
+        keyframe is inserted -- Frame::key_pts_ are positions in the keyframes' feature lists, a key point's position is its landmark's
+        position in the tables NOW (Map::getCloseKeyframes, src/map.cpp:165-169), a key point whose landmark is deleted is replaced
+        (Map::safeDeletePoint -> Frame::removeKeyPoint, :116-123).  "device" does it on the resident tables (plsvo_candidates_set_keypts,
+        _run_close; DESIGN.md 3.19: a backend with map_set_keypts / map_keyframe_decide) and the list is decided there, inside map_select
+        (-> []); "host" does the same with the calls there were before: the key-point table kept here from the tables the harness
+        follows (Frame::setKeyframe: from five NULLs), then the synchronous close_keyframes on gathered arrays.  A restage drops the
+        resident table: it travels with the tables."""
+        o, mt = self.o, self.mt
+        if o.keystage:
+            n_kf = len(mt.cm["kf_T"])
+            if fr.map_job is not None and o.keystage == "device" and self.kp_live:
+                self.kp_tab = [[int(h) for h in r] for r in self.backend.map_fetch_keypts()[:n_kf]]
+            if self.kp_tab is None and o.keystage == "host":
+                self.kp_tab, _ = _key_point_upkeep(mt.cm, [[-1] * 5] * n_kf, self.cam, fresh=range(n_kf))
+            self.kp_live = True
+            if o.keystage == "device":
+                return []
+            kpos, kval = mt.key_point_positions(self.kp_tab)
+            fr.close = self.backend.close_keyframes(abi.CloseKeyframesJob(self.cam, fr.T_k, np.array(mt.cm["kf_T"], float).reshape(-1, 7), kpos, kval, o.max_n_kfs))
+        elif self.kf_select:
+            fr.close = self.backend.close_keyframes(self.kfs.close_job(fr.T_k, o.max_n_kfs))
+        else:
+            return list(range(len(mt.cm["kf_T"])))
+        return _overlap_of(fr.close)
+
+    def track_map_candidates(self, k, fr):
+        """2 + 3 from the map-candidate stage (plsvo_candidates_*) instead of keyframe 0: overlap keyframes' features,
+        first visit wins, closest-view observation, quality order, matched on the device (reprojectMap :157-183, getCloseViewObs,
+        findMatchDirect).  The harness keeps the map tables the stage needs (_MapTables), restages them when they change, and hands each
+        frame its pose and its overlap list.  Without cell_select the matches reach the pose optimiser in landmark-index order, as
+        without the stage.  ref_kf_hist: how many of the filed landmarks took their reference observation from each keyframe of the
+        table.  record_candidates keeps the frame's stage inputs and result in rec["candidates"]; with cell_select also the selection
+        and the quality state before and after the frame."""
+        o, mt, n_pts, n_seg = self.o, self.mt, self.n_pts, self.n_seg
+        fr.map_job = mt.stage_job(self.P3)
+        overlap = self.overlap_keyframes(k, fr)
+        frame_job = abi.CandidateFrameJob(fr.T_k, overlap, cur_slot=k)
+        cm_before = copy.deepcopy(mt.cm) if o.record_candidates else None
+        if o.cell_select:
+            cr, mr, q_after = self.select_cells(k, fr, frame_job)
+            overlap = _overlap_of(fr.close) if o.keystage == "device" else overlap
+        else:
+            cr, mr = self.backend.map_candidates(fr.map_job, frame_job, self.cam, o.n_pyr_levels)
+        n_all = n_pts + 2 * n_seg
+        found, fr.px_new, fr.level = np.zeros(n_all, bool), np.zeros((n_all, 2)), np.zeros(n_all, np.int32)
+        lm_at = np.concatenate([mt.lm_of_rows(cr["pt_lm"]), n_pts + cr["seg_lm"], n_pts + n_seg + cr["seg_lm"]]).astype(np.int64)
+        own = lm_at >= 0                               # (image_seeds: a row without a landmark of the harness's map is the device's alone)
+        found[lm_at[own]] = mr["found"].astype(bool)[own]
+        fr.px_new[lm_at[own]] = mr["px"][own]
+        fr.level[lm_at[own]] = np.maximum(mr["search_level"], 0)[own]
+        fr.pt_ok, fr.seg_ok = found[:n_pts], found[n_pts:n_pts + n_seg] & found[n_pts + n_seg:]
+        hist = np.zeros(len(mt.cm["kf_T"]), np.int64)
+        for name in ("pt", "seg"):
+            for lm, ob in zip(cr[name + "_lm"], cr[name + "_obs"]):
+                if ob >= 0:
+                    hist[mt.cm[name + "_obs"][lm][ob]["kf"]] += 1
+        fr.cand_rec = dict(n_filed_pt=cr["n_filed_pt"], n_filed_seg=cr["n_filed_seg"], ref_kf_hist=[int(v) for v in hist])
+        if o.record_candidates:
+            fr.cand_rec["candidates"] = dict(stream=cm_before, T=[float(v) for v in fr.T_k], overlap=list(overlap), out=cr, match=mr)
+        if o.cell_select:
+            self.follow_selection(fr, q_after)
+
+    def select_cells(self, k, fr, frame_job):
+        """cell_select: the second half of Reprojector::reprojectMap on the device as well (plsvo_candidates_select; DESIGN.md 3.12): one
+        candidate per grid cell in place of every found match, the landmark quality (n_failed_reproj_ / n_succeeded_reproj_, promotions,
+        deletions) kept resident from frame to frame, and the pose optimiser fed on the device in place of the per-call one.  The
+        features reach the pose optimiser in selection order; a segment that won both of its cells is a feature twice.  The harness
+        restages only when the map changes at a keyframe (or a seed converges), and carries the counters over a restage with
+        fetch_quality / set_quality (carry=); the structure optimiser's keys do not survive a stage either and are carried like them
+        (map_set_last_optim; rows appended since read 0).
+        -> (the stage's result, the matcher's, the quality state after the frame); fr: the selection, the pose optimiser's result"""
+        o, mt, backend = self.o, self.mt, self.backend
+        staged = fr.map_job is not None
+        cr, mr, fr.frame_sel, fr.pr, q_after = backend.map_select(fr.map_job, frame_job, self.cam, o.n_pyr_levels, self.select_kw, carry=mt.quality if staged else None,
+                                                                 **(dict(close=o.max_n_kfs, key_pts=self.kp_tab) if o.keystage == "device" else {}),
+                                                                 **(dict(poses_dev=fr.poses_dev) if fr.poses_dev else {}))
+        if o.keystage == "device":
+            fr.close = backend.last_close
+        if o.structopt_resident and staged and (any(mt.so_keys["pt"]) or any(mt.so_keys["seg"])):
+            backend.map_set_last_optim(mt.so_keys["pt"] + [0] * (len(mt.cm["pt_pos"]) - len(mt.so_keys["pt"])), mt.so_keys["seg"] + [0] * (len(mt.cm["seg_spos"]) - len(mt.so_keys["seg"])))
+        if o.seeds_resident and staged and o.mapping and mt.seed_kf is not None:
+            self.stage_seeds()
+        return cr, mr, q_after
+
+    def stage_seeds(self):
+        """seeds_resident: the map's seeds are staged ONCE, beside the map tables that were just staged, and are updated, erased and
+        handed over to the resident tables on the device (plsvo_seeds_update): no seed travels per frame and no record
+        comes back, only the report and the update's rows (update_seeds).  Every seed was started in frame 0's keyframe, in one batch
+        that never ages (the harness keeps its seeds until they converge).  image_seeds: room for the seeds the keyframes start."""
+        o, seq, seeds = self.o, self.seq, self.seeds
+        si_ = seeds["idx"]
+        cells = (-(-self.w_img // o.detect_cell_size)) * (-(-self.h_img // o.detect_cell_size))
+        self.backend.seeds_stage(dict(batch_counter=0, pt_ref_kf=np.full(len(si_), self.mt.seed_kf, np.int32), pt_batch_id=np.zeros(len(si_), np.int32), pt_px=seq["pt_px0"][si_],
+                                      pt_f=seq["pt_f0"][si_], pt_level=np.zeros(len(si_), np.int32), pt_type=np.zeros(len(si_), np.uint8),
+                                      pt_grad=np.zeros((len(si_), 2)), pt_a=seeds["a"], pt_b=seeds["b"], pt_mu=seeds["mu"], pt_z_range=seeds["z_range"],
+                                      pt_sigma2=seeds["sigma2"]), self.cam, max_n_kfs=1 << 30, n_pyr_levels=o.n_pyr_levels,
+                                 **(dict(room=dict(extra_pt=self.n_frames * cells)) if o.image_seeds else {}))
+        self.rows.rows, self.rows.on_device = [(int(i), self.mt.seed_kf, None) for i in si_], True
+
+    def follow_selection(self, fr, q_after):
+        """behind map_select: the harness follows the types, the candidate lists and the deletions in its own tables from fetch_quality,
+        keystage "host" replaces the key points of the landmarks the selection deleted (removeKeyPoint), and 4. on the device: the
+        selected features in selection order with the resident pose optimiser's result, as landmarks of the harness"""
+        o, mt = self.o, self.mt
+        mt.follow_selection(q_after)
+        ev = np.concatenate([q_after["pt_event"], q_after["seg_event"]])
+        fr.cand_rec.update(n_trials=fr.frame_sel["n_trials"], n_promoted=int((ev & abi.LM_EVENT_PROMOTED).astype(bool).sum()),
+                           n_deleted=int((ev & abi.LM_EVENT_DELETED).astype(bool).sum()))
+        if o.record_candidates:
+            fr.cand_rec["candidates"].update(select=fr.frame_sel, quality_before=mt.quality, quality=q_after, select_params=dict(self.select_kw))
+        mt.quality = q_after
+        if o.keystage == "host":
+            self.kp_tab, fr.kp_frame = _key_point_upkeep(mt.cm, self.kp_tab, self.cam)
+        pt_i, fr.seg_i = mt.lm_of_rows(fr.frame_sel["pt_lm"]), fr.frame_sel["seg_lm"].astype(np.int64)
+        fr.sel_mask = pt_i >= 0
+        fr.pt_i = pt_i[fr.sel_mask]
+        fr.pt_ok = np.zeros(self.n_pts, bool); fr.pt_ok[fr.pt_i] = True
+        fr.seg_ok = np.zeros(self.n_seg, bool); fr.seg_ok[fr.seg_i] = True
+
+    def pose_optimize_host(self, k, fr):
+        """4. motion-only pose optimisation on the matches (processFrame :327-329); a LineFeat's level is the END point's (matcher.cpp:264)"""
+        seq, cam, px_new, n_pts, n_seg = self.seq, self.cam, fr.px_new, self.n_pts, self.n_seg
+        pt_i, seg_i = fr.pt_i, fr.seg_i = np.nonzero(fr.pt_ok)[0], np.nonzero(fr.seg_ok)[0]
+        sf, ef = _bearing(cam, px_new[n_pts + seg_i]), _bearing(cam, px_new[n_pts + n_seg + seg_i])
+        line = np.cross(sf, ef)
+        line = line / np.sqrt(line[:, 0:1] ** 2 + line[:, 1:2] ** 2) if len(seg_i) else np.zeros((0, 3))    # feature.cpp:103-104
+        fr.pr = self.backend.pose_optimize(abi.PoseOptJob(fr.T_k, abs(cam[0]), self.o.reproj_thresh, 10, _bearing(cam, px_new[pt_i]), self.P3[pt_i], fr.level[pt_i], line,
+                                                          seq["seg_spos"][seg_i], seq["seg_epos"][seg_i], fr.level[n_pts + n_seg + seg_i]))
+
+    def gate(self, k, fr):
+        """relocalize: the gates of processFrame (:315-321, :335) and setTrackingQuality stand behind every frame's pose optimisation, ahead
+        of the structure optimisation: a frame that fails is not structure-optimised, decided, inserted or fed to the depth filter
+        (RESULT_FAILURE: nothing behind the gate runs), its pose is the one the gate carries, and the next frame relocalises.
+        TRACKING_BAD keeps a frame from becoming a keyframe.  "device": plsvo_candidates_track_gate (its record is the other host wait);
+        "host": track_gate_host on the fetched counts.  -> the failure's record, or None"""
+        o, rs, pr, frame_sel = self.o, self.rs, fr.pr, fr.frame_sel
+        if rs.obs_last is None:
+            rs.obs_last = (self.out[0]["n_matched_pt"], self.out[0]["n_matched_seg"])
+        T_reset = fr.T_reset if fr.reloc else self.T_prev
+        gk = dict(self.gate_kw, max_fts=self.select_kw["max_fts"], max_fts_segs=self.select_kw["max_fts_segs"])
+        if o.relocalize == "device":
+            grec, T_carried, rs.gate_dev = self.backend.track_gate(mode=abi.GATE_RELOC if fr.reloc else abi.GATE_TRACK, T_reset=T_reset,
+                                                                   **({} if rs.obs_resident and fr.map_job is None else dict(num_obs_last=rs.obs_last)), **gk)
+            fr.gate = (int(grec["result"]), int(grec["tracking_quality"]))
+        else:
+            g_result, g_quality, reset = track_gate_host(frame_sel["n_matches"], frame_sel["n_ls_matches"], pr.num_obs_pt, pr.num_obs_ls, *rs.obs_last,
+                                                        relocalizing=fr.reloc, **gk)
+            fr.gate, T_carried = (int(g_result), int(g_quality)), np.array(T_reset, float) if reset else pr.T.copy()
+        rs.obs_last, rs.obs_resident = (int(frame_sel["n_matches"]), int(frame_sel["n_ls_matches"])), True
+        fr.bad_quality = fr.gate[1] == abi.TRACKING_BAD
+        if fr.gate[0] == abi.GATE_OK:
+            return None
+        rec = self.record(fr, np.asarray(T_carried, float).copy(), pr.cov.copy(), fr.ar.n_tracked, (int(fr.pt_ok.sum()), int(fr.seg_ok.sum())),
+                          (int(pr.pt_keep.sum()), int(pr.seg_keep.sum())), gate=fr.gate)
+        self.T_prev, rs.stage, rs.next_align = rec["T"].copy(), "reloc", None      # the next frame relocalises
+        return rec
+
+    def tracked(self, k, fr):
+        """the frame is tracked: its pose and keep masks, the features the next frame is aligned from, its record"""
+        pr, px_new, n_pts, n_seg = fr.pr, fr.px_new, self.n_pts, self.n_seg
+        fr.T = pr.T.copy()
+        fr.pt_keep, fr.seg_keep = pr.pt_keep.astype(bool), pr.seg_keep.astype(bool)
+        if fr.sel_mask is not None:
+            fr.pt_keep = fr.pt_keep[fr.sel_mask]
+        fr.kept, skept = fr.pt_i[fr.pt_keep], fr.seg_i[fr.seg_keep]
+        self.prev = dict(pt_idx=fr.kept, pt_px=px_new[fr.kept], seg_idx=skept, seg_spx=px_new[n_pts + skept], seg_epx=px_new[n_pts + n_seg + skept])
+        self.T_prev = fr.T
+        rec = self.record(fr, fr.T.copy(), pr.cov.copy(), fr.ar.n_tracked, (int(fr.pt_ok.sum()), int(fr.seg_ok.sum())), (int(fr.pt_keep.sum()), int(fr.seg_keep.sum())), gate=fr.gate, n_ties=fr.n_ties)
+        self.rs.stage = "default"                      # "Relocalization successful."
+        return rec
+
+    def decide_keyframe_host(self, k, fr):
+        """kf_select without keystage: scene depth, needNewKf against the overlap keyframes -- measured, like the reference, from the
+        PREVIOUS frame's pose --, the frame's five key points (plsvo_keyframe_decide, :351-358, :396).  A frame plays the
+        keyframe when needNewKf says so instead of every kf_every-th; the keyframe table (_Keyframes) grows with it.
+        Without map_candidates the keyframes that overlap the aligned frame are found here (the head of reprojectMap: it runs before the
+        matching, which then takes its candidates from keyframe 0 either way, so the call's place does not matter)."""
+        if not self.o.map_candidates:
+            fr.close = self.backend.close_keyframes(self.kfs.close_job(fr.T_k, self.o.max_n_kfs))
+        skept = fr.seg_i[fr.seg_keep]
+        dec = fr.dec = self.kfs.decide(fr.T, fr.T_last, fr.px_new[fr.kept], self.P3[fr.kept], self.seq["seg_spos"][skept], self.seq["seg_epos"][skept],
+                                       fr.close["close_idx"][:fr.close["n_overlap"]])
+        fr.is_kf = bool(dec["need_new_kf"])
+        fr.rec.update(is_kf=fr.is_kf, n_overlap=fr.close["n_overlap"], depth_mean=dec["depth_mean"])
+        if fr.is_kf:
+            self.kfs.add_keyframe(fr.T, dec["key_pts"], self.P3[fr.kept])
+            self.kfs.depth_from(dec)
+
+    def structure_resident(self, k, fr):
+        """structopt_resident: step 5 runs on the resident tables (plsvo_candidates_optimize_structure) in place of the
+        gather / structure_optimize / map_set_positions of structure_host: one call on EVERY tracked frame, behind the pose optimiser
+        and ahead of an insertion as in processFrame (:340 before :358), points and segments, with the resident keep masks and
+        frame_id = k.  The harness takes the moved positions for its own tables from the call's report and follows the keys from it, to
+        carry them over a restage.  record_candidates: rec["structopt"] holds the tables and the keys before, the selection, the masks,
+        the report, and both after."""
+        mt, rec = self.mt, fr.rec
+        cm, so_keys = mt.cm, mt.so_keys
+        for name, n_rows in (("pt", len(cm["pt_pos"])), ("seg", len(cm["seg_spos"]))):
+            so_keys[name] += [0] * (n_rows - len(so_keys[name]))
+        before = (copy.deepcopy(cm), copy.deepcopy(so_keys)) if self.o.record_candidates else None
+        so = self.backend.map_optimize_structure(k)
+        for row, p in zip(so["pt_lm"], so["pt_pos"]):
+            cm["pt_pos"][int(row)] = [float(x) for x in p]
+            so_keys["pt"][int(row)] = k
+            if mt.row_lm[int(row)] >= 0:
+                self.P3[mt.row_lm[int(row)]] = p
+        for row, a, b in zip(so["seg_lm"], so["seg_spos"], so["seg_epos"]):
+            cm["seg_spos"][int(row)], cm["seg_epos"][int(row)] = [float(x) for x in a], [float(x) for x in b]
+            so_keys["seg"][int(row)] = k
+        rec.update(n_structopt_pt=int(so["n_sel_pt"]), n_structopt_seg=int(so["n_sel_seg"]))
+        if self.o.record_candidates:
+            rec["structopt"] = dict(stream=before[0], keys_before=before[1], select=fr.frame_sel, pt_keep=fr.pr.pt_keep.copy(), seg_keep=fr.pr.seg_keep.copy(), frame_id=k, report=so,
+                                    tables=copy.deepcopy(cm), keys=copy.deepcopy(so_keys))
+
+    def decide_keyframe(self, k, fr):
+        """keystage: the keyframe decision behind the structure optimisation (src/frame_handler_mono.cpp:340 before :351), on the
+        selection with the keep masks as alive and the landmark positions as the tables hold them now; key_pts are indices in selection
+        order.  "device": on the resident selection (plsvo_candidates_keyframe_decide); "host": the synchronous keyframe_decide on
+        gathered arrays.  The two differ in transport alone and agree in every record.  The records gain overlap, the list itself, and a
+        keyframe's record key_pts_new, the frame's key_pts_ as it becomes a keyframe.  (!needNewKf || TRACKING_BAD: no keyframe, :352)"""
+        o, cm, frame_sel, close = self.o, self.mt.cm, fr.frame_sel, fr.close
+        if o.keystage == "device":
+            dec = self.backend.map_keyframe_decide(fr.T_last, o.kfselect_mindist_t, o.kfselect_mindist_r)
+        else:
+            dec = self.backend.keyframe_decide(abi.KeyframeDecideJob(self.cam, fr.T, fr.T_last, frame_sel["pt_px"], _rows_of(cm["pt_pos"], frame_sel["pt_lm"]), fr.pr.pt_keep,
+                                                                     _rows_of(cm["seg_spos"], frame_sel["seg_lm"]), _rows_of(cm["seg_epos"], frame_sel["seg_lm"]), fr.pr.seg_keep,
+                                                                     np.array(cm["kf_T"], float).reshape(-1, 7), close["close_idx"][:close["n_overlap"]], (-1,) * 5,
+                                                                     o.kfselect_mindist_t, o.kfselect_mindist_r))
+        fr.dec, fr.is_kf = dec, bool(dec["need_new_kf"]) and not fr.bad_quality
+        fr.rec.update(is_kf=fr.is_kf, n_overlap=close["n_overlap"], depth_mean=dec["depth_mean"], overlap=_overlap_of(close))
+        if fr.is_kf:
+            fr.rec["key_pts_new"] = [int(h) for h in dec["key_pts"]]
+            self.kfs.depth_from(dec)
+
+    def insert_keyframe(self, k, fr):
+        """kf_insert: a keyframe no longer restages: the frame joins the RESIDENT tables on the device (plsvo_candidates_insert_keyframe,
+        DESIGN.md 3.13) with the resident pose and keep masks; when the table holds max_n_kfs keyframes the one keyframe_decide names as
+        the furthest is removed in the same call (kf_select; the first row when it names none).  The harness brings its own tables up to
+        date from the backend's fetch, sends structure-optimised positions with map_set_positions (structure_host), and stages only at
+        the start and when a seed converges into a NEW candidate.  keystage "host": the key-point rows close up, the new keyframe's row
+        is the decision's, holders lost to the removal are replaced (n_kp_rebuilt counts the rows rebuilt in the frame).  A removal is
+        passed on to the resident seed lists (plsvo_seeds_keyframe); when it takes frame 0's keyframe out, the seeds that are left leave
+        the device with it -- their keyframe is no longer in the table, image seeds included -- and the harness goes on following them
+        on the host, outside the map.  record_candidates: rec["insert"] holds the tables and the quality before, the selection, the
+        masks, the pose, and all three after."""
+        o, mt, rows, rec, backend = self.o, self.mt, self.rows, fr.rec, self.backend
+        remove = -1
+        if self.kf_select and len(mt.cm["kf_T"]) >= o.max_n_kfs:
+            remove = max(int(fr.dec["furthest_kf"]), 0)
+            if not o.keystage:
+                self.kfs.remove(remove)
+            mt.keyframe_removed(remove)
+        before = (copy.deepcopy(mt.cm), mt.quality) if o.record_candidates else None
+        tables, mt.quality, ins = backend.map_insert(remove, k)
+        mt.adopt(tables)
+        if o.keystage == "host":
+            self.kp_tab, n_rebuilt = _key_point_upkeep(mt.cm, [r for j, r in enumerate(self.kp_tab) if j != remove] + [[int(h) for h in fr.dec["key_pts"]]], self.cam)
+            fr.kp_frame += n_rebuilt
+        if rows.on_device and o.image_seeds and mt.seed_kf is not None:
+            rec["n_image_seeds_started"] = self.start_image_seeds(k, fr, remove, ins)
+        elif rows.on_device and remove >= 0:
+            backend.seeds_keyframe(removed_kf=remove)
+            rows.rows, rows.on_device = [], mt.seed_kf is not None
+        rec.update(n_joined=ins["n_joined_pt"] + ins["n_joined_seg"], n_deleted_kf=ins["n_deleted_pt"] + ins["n_deleted_seg"], remove_kf=remove)
+        if o.keystage == "host":
+            rec["n_kp_rebuilt"] = int(fr.kp_frame)
+        if o.align and o.compact and k + 1 < self.n_frames:
+            self.rs.next_align = self.align_job_of(k, fr)    # ahead of the compaction, which renumbers the rows the selection points at
+        if o.compact:
+            tables = self.compact_tables(k, fr)
+        if o.record_candidates:
+            rec["insert"] = dict(stream=before[0], quality_before=before[1], select=fr.frame_sel, pt_keep=fr.pr.pt_keep.copy(), seg_keep=fr.pr.seg_keep.copy(), T=[float(v) for v in fr.T],
+                                 slot=k, remove_kf=remove, tables=tables, quality=mt.quality, report=ins)
+
+    def start_image_seeds(self, k, fr, remove, ins):
+        """image_seeds="host" | "device": at a keyframe whose seed tables are on the device the image's corners become point seeds of the
+        RESIDENT lists (DepthFilter::initializeSeeds' creating half, DESIGN.md 3.16), behind the insertion: the removal, then the corners
+        of the frame's free cells, with the cells of the frame's selected features and of the last update's matches occupied.  "device"
+        is plsvo_seeds_keyframe_detect with both occupancy sources; "host" does the same with the calls there were before --
+        detect_corners on an occupancy built from the fetched selection and the fetched rows by the same rule, seeds_from_corners,
+        seeds_keyframe(pt_..) -- so the two differ in transport alone and agree in every record and in the lists.  These seeds have no
+        landmark of the synthetic map: the harness keeps, per resident row, the landmark of a map seed or -1 (_SeedRows) and follows
+        removals and erasures through the rows and the reports.  -> the seeds started"""
+        o, backend, rows, img_kw = self.o, self.backend, self.rows, self.img_kw
+        new_kf = len(self.mt.cm["kf_T"]) - 1
+        assert ins.get("new_kf", new_kf) == new_kf and self.mt.cm["kf_slot"][new_kf] == k
+        ev = dict(removed_kf=remove, new_batch=True, new_kf=new_kf, depth_mean=self.kfs.seed_depth[0], depth_min=self.kfs.seed_depth[1])
+        if o.image_seeds == "device":
+            backend.seeds_keyframe_detect(o.detect_cell_size, o.n_pyr_levels, img_kw["detection_threshold"], fast_threshold=img_kw["fast_threshold"],
+                                          occ_sources=abi.SEED_OCC_SELECTED | (abi.SEED_OCC_UPDATED if rows.last_rows is not None else 0), **ev)
+            kf_rep = backend.seeds_keyframe_fetch()
+            assert not kf_rep["no_room"]
+            n_started = kf_rep["n_new_pt"]
+        else:
+            marking = np.zeros((0, 2))
+            if rows.last_rows is not None:
+                stl = rows.last_rows["pt_status"]
+                marking = rows.last_rows["pt_px_cur"][(stl == abi.SEED_UPDATED) | (stl == abi.SEED_CONVERGED) | (stl == abi.SEED_NAN)]
+            occ = _occupancy(np.concatenate([fr.frame_sel["pt_px"].reshape(-1, 2), marking]), self.w_img, self.h_img, o.detect_cell_size)
+            corners = backend.detect_corners(k, occ, o.detect_cell_size, o.n_pyr_levels, img_kw["detection_threshold"], fast_threshold=img_kw["fast_threshold"])
+            sdn = seeds_from_corners(corners, self.cam, *self.kfs.seed_depth)
+            backend.seeds_keyframe(pt_px=sdn["px"], pt_f=sdn["f"], pt_level=sdn["level"], pt_type=sdn["type"], pt_grad=sdn["grad"], **ev)
+            n_started = len(corners)
+        if remove >= 0:
+            rows.remove_keyframe(remove)
+        if n_started:
+            rows.started(n_started, new_kf, backend.seeds_fetch_lists())
+        return int(n_started)
+
+    def compact_tables(self, k, fr):
+        """compact="room" | "always": behind every keyframe's insertion the resident tables close up over their deleted POINT rows on the
+        device (plsvo_candidates_compact, DESIGN.md 3.18; Map::emptyTrash: the deleted rows leave, the rows behind them move down) --
+        "always" at every keyframe, "room" only when fewer rows are free than seeds are alive, decided on the device.  The harness takes
+        the tables from the backend's fetch and applies the remap to its row <-> landmark maps and to the keys it follows.  The segments
+        have no reserve here (no segment seed exists) and are never compacted.  Stable order is kept, so every pose, covariance and
+        count equals those of the run with the full reserve.  -> the fetched tables"""
+        alive = len(self.seeds["idx"]) + self.rows.n_image()
+        tables, self.mt.quality, cp = self.backend.map_compact("room", (1 << 30) if self.o.compact == "always" else alive, 0)
+        if cp["ran_pt"]:
+            self.mt.adopt(tables)
+            self.mt.apply_pt_remap(cp["pt_remap"])
+        fr.rec["n_compacted_pt"] = int(cp["n_pt_before"] - cp["n_pt_after"])
+        return tables
+
+    def join_keyframe_host(self, k, fr):
+        """map_candidates without kf_insert: the frame joins the keyframe table of the harness's own tables, which are restaged: its
+        features, and an observation at the FRONT of every landmark's list (Feature3D::addFrameRef pushes at the front,
+        include/plsvo/feature3D.h:204); a candidate it matched leaves the map's candidate list for the keyframe's features (a candidate
+        that joins a keyframe: TYPE_UNKNOWN)"""
+        cm, cam, px_new, level, n_pts, n_seg, kept = self.mt.cm, self.cam, fr.px_new, fr.level, self.n_pts, self.n_seg, fr.kept
+        skept = fr.seg_i[fr.seg_keep]
+        kf_id = len(cm["kf_T"])
+        cm["kf_T"].append(_f3(fr.T)); cm["kf_slot"].append(k)
+        cm["kf_pt"].append([int(i) for i in kept]); cm["kf_seg"].append([int(i) for i in skept])
+        for i, brg in zip(kept, _bearing(cam, px_new[kept])):
+            cm["pt_obs"][int(i)].insert(0, dict(kf=kf_id, px=_f3(px_new[i]), f=_f3(brg), level=int(level[i]), type=abi.FTR_CORNER, grad=[0.0, 0.0]))
+            if not self.o.cell_select or cm["pt_type"][int(i)] == abi.LM_CANDIDATE:
+                cm["pt_type"][int(i)] = abi.LM_UNKNOWN
+        for i, sb, eb in zip(skept, _bearing(cam, px_new[n_pts + skept]), _bearing(cam, px_new[n_pts + n_seg + skept])):
+            cm["seg_obs"][int(i)].insert(0, dict(kf=kf_id, spx=_f3(px_new[n_pts + i]), epx=_f3(px_new[n_pts + n_seg + i]), sf=_f3(sb), ef=_f3(eb), level=int(level[n_pts + i])))
+        matched = set(int(v) for v in kept)
+        cm["pt_cand"] = [i for i in cm["pt_cand"] if i not in matched]
+        self.mt.dirty = True
+
+    def structure_host(self, k, fr):
+        """5. structure optimisation at a keyframe (FrameHandlerBase::optimizeStructure: the 20 least recently refined, :202-237) of the
+        kept point landmarks with >= 2 observations; the moved positions go to the resident tables (kf_insert: map_set_positions, in
+        rows) or wait for the restage"""
+        o, P3 = self.o, self.P3
+        cand = np.array([i for i in fr.kept if len(self.obs[int(i)]) >= 2], np.int64)
+        if not (len(cand) and fr.is_kf and not o.structopt_resident):
+            return
+        refine = cand[np.argsort(self.last_optim[cand], kind="stable")[:20]]
+        off, ofr, of_ = [0], [], []
+        for i in refine:
+            for fr_, brg in self.obs[int(i)]:
+                ofr.append(fr_)
+                of_.append(brg)
+            off.append(len(ofr))
+        z3, zi = np.zeros((0, 3)), np.zeros(0, np.int32)
+        so = self.backend.structure_optimize(abi.StructOptJob(np.stack(self.poses_est), P3[refine], off, ofr, np.array(of_), z3, z3, np.zeros(1, np.int32), zi, z3, z3, 5, 5))
+        P3[refine] = so["pt_pos"]
+        self.last_optim[refine] = k
+        if o.kf_insert:
+            self.backend.map_set_positions(self.mt.row_of_lm(refine).astype(np.int32), P3[refine])
+            for i in refine:
+                self.mt.cm["pt_pos"][int(self.mt.lm_row[i])] = [float(x) for x in P3[i]]
+        elif o.map_candidates:
+            self.mt.dirty = True
+
+    def update_seeds(self, k, fr):
+        """6. depth-filter update of the seeds with this frame (DepthFilter::updateSeeds, depth_filter.cpp:262); a converged seed turns
+        into a landmark.  On the resident lists (seeds_resident) the report and the update's rows come back, no record travels; with
+        image_seeds they hold seeds from the image beside the map's, which are the rows with a landmark, in the order of seeds["idx"].
+        n_seed_candidates counts the converged seeds whose keyframe, frame 0's, is still in the table."""
+        o, seq, rows, seeds, rec = self.o, self.seq, self.rows, self.seeds, fr.rec
+        ns, si_ = len(seeds["idx"]), seeds["idx"]
+        img_dev = bool(o.image_seeds) and rows.on_device
+        if not (ns or (img_dev and rows.rows)):
+            return
+        all_rows = report = quality = None
+        if rows.on_device:
+            report, sr, quality = self.backend.seeds_update(k, fr.T)
+            assert len(sr["pt_status"]) == (len(rows.rows) if img_dev else ns) and report["no_room"] == 0
+            if img_dev:
+                all_rows, is_map = sr, rows.lms() >= 0
+                rows.last_rows = dict(pt_status=sr["pt_status"].copy(), pt_px_cur=sr["pt_px_cur"].copy())
+                assert np.array_equal(rows.lms()[is_map], si_)
+                sr = {f: v[is_map] for f, v in sr.items() if f.startswith("pt_")}
+        else:
+            ptd = dict(ref_frame=np.zeros(ns, np.int32), cur_frame=np.ones(ns, np.int32), px=seq["pt_px0"][si_], f=seq["pt_f0"][si_], level=np.zeros(ns, np.int32),
+                       a=seeds["a"], b=seeds["b"], mu=seeds["mu"], z_range=seeds["z_range"], sigma2=seeds["sigma2"])
+            sr = self.backend.update_seeds(abi.SeedsJob(self.cam, np.stack([self.kf_T, fr.T]), np.array([0, k], np.int32), ptd, None, n_pyr_levels=o.n_pyr_levels))
+        stt = sr["pt_status"]
+        conv = stt == abi.SEED_CONVERGED
+        self.P3[si_[conv]] = sr["pt_xyz_world"][conv]
+        self.known[si_[conv]] = True
+        in_table = conv.any() and o.map_candidates and self.mt.seed_kf is not None
+        if img_dev:
+            self.converged_rows_join(fr, all_rows, report, quality)
+        elif o.seed_candidates and in_table:
+            self.converged_seeds_join(fr, [int(i) for i in si_[conv]], sr["pt_xyz_world"][conv], report, quality)
+        elif in_table:
+            for i in si_[conv]:
+                self.mt.append_candidate(None, self.mt.seed_kf, seq["pt_px0"][i], seq["pt_f0"][i], 0, [0.0, 0.0], int(i), own_row=True)
+        keep_s = ~(conv | (stt == abi.SEED_NAN))
+        self.seeds = dict(idx=si_[keep_s], a=sr["pt_a"][keep_s], b=sr["pt_b"][keep_s], mu=sr["pt_mu"][keep_s], z_range=seeds["z_range"][keep_s], sigma2=sr["pt_sigma2"][keep_s])
+        rec["n_seed_converged"] = int(conv.sum())
+        if o.kf_insert:
+            rec["n_seed_candidates"] = int(conv.sum()) if self.mt.seed_kf is not None else 0
+
+    def converged_rows_join(self, fr, all_rows, report, quality):
+        """image_seeds: every converged row of the resident lists, from the map or from the image, is a new landmark row of the resident
+        tables, in list order; a converged image seed gets a table row of its own without a landmark (such rows are selected, optimised
+        and inserted on the device like any other; the harness's own alignment and structure optimisation leave them out)"""
+        seq, rows, mt = self.seq, self.rows, self.mt
+        status = all_rows["pt_status"]
+        for j, r in enumerate(np.nonzero(status == abi.SEED_CONVERGED)[0]):
+            lm, kf, ftr = rows.rows[r]
+            if lm >= 0:
+                ftr = dict(px=seq["pt_px0"][lm], f=seq["pt_f0"][lm], level=0)
+            else:
+                rows.n_image_converged += 1
+            row = mt.append_candidate(all_rows["pt_xyz_world"][r], kf, ftr["px"], ftr["f"], ftr["level"], [0.0, 0.0] if lm >= 0 else [1.0, 0.0], lm)
+            assert row == report["first_pt"] + j
+            mt.quality = quality
+        rows.drop(status)
+        fr.rec.update(n_image_seeds=rows.n_image(), n_image_seeds_converged=rows.n_image_converged)
+
+    def converged_seeds_join(self, fr, lms, pos, seed_report, seed_quality):
+        """seed_candidates: a converged seed whose keyframe is still in the table joins the RESIDENT tables on the device as a new landmark
+        row with one observation and an entry at the back of the candidate list (newCandidatePoint; plsvo_candidates_add, DESIGN.md
+        3.14) instead of marking the tables for a restage, so the stage is called once, at the first frame; the harness appends the same
+        row to its own tables.  With seeds_resident the update's commit has appended them already: its report stands in for the add's,
+        from which the harness keeps its own tables exactly as it does from an add's.  A seed that converges after frame 0's keyframe
+        was removed stays outside the map's tables.  record_candidates: rec["add"] holds the tables and the quality before, the new
+        records, the tables and the quality after, and the backend's report."""
+        seq, mt, n = self.seq, self.mt, len(lms)
+        new = dict(pt_pos=pos, pt_obs_kf=np.full(n, mt.seed_kf, np.int32), pt_obs_px=seq["pt_px0"][lms], pt_obs_f=seq["pt_f0"][lms],
+                   pt_obs_level=np.zeros(n, np.int32), pt_obs_type=np.full(n, abi.FTR_CORNER, np.uint8), pt_obs_grad=np.zeros((n, 2)))
+        before = (copy.deepcopy(mt.cm), mt.quality) if self.o.record_candidates else None
+        if self.rows.on_device:
+            report = dict(first_pt=seed_report["first_pt"], first_seg=-1, n_added_pt=n, n_added_seg=0, n_pt=seed_report["n_pt"], n_seg=seed_report["n_seg"],
+                          n_pt_cand=seed_report["n_pt_cand"], n_seg_cand=seed_report["n_seg_cand"], n_pt_obs=seed_report["n_pt_obs"], n_seg_obs=seed_report["n_seg_obs"])
+            mt.quality = seed_quality
+        else:
+            report, mt.quality = self.backend.map_add_candidates(new)
+        for j, i in enumerate(lms):
+            assert mt.append_candidate(self.P3[i], mt.seed_kf, seq["pt_px0"][i], seq["pt_f0"][i], 0, [0.0, 0.0], i) == report["first_pt"] + j
+        if self.o.record_candidates:
+            fr.rec["add"] = dict(stream=before[0], quality_before=before[1], new=new, tables=copy.deepcopy(mt.cm), quality=mt.quality, report=report)
+
+    def new_image_seeds(self, frame, feature_px):
+        """detect: the corner detector on the frame's own pyramid slot with the cells of the features it tracks marked occupied
+        (DepthFilter::initializeSeeds); the corners become point seeds (seeds_from_corners)"""
+        o = self.o
+        corners = self.backend.detect_corners(frame, _occupancy(feature_px, self.w_img, self.h_img, o.detect_cell_size), o.detect_cell_size, o.n_pyr_levels)
+        sd = seeds_from_corners(corners, self.cam, *self.kfs.seed_depth)
+        sd["ref_frame"] = np.full(len(corners), frame, np.int32)
+        return sd
+
+    def image_seeds_host(self, k, fr):
+        """7. detect=True: the seeds that came from the image are updated with this frame next to the map's own; every keyframe, frame 0
+        included, adds those of its own free cells (new_image_seeds).  These seeds come from the image alone and are not added to the
+        map, whose landmarks carry the truth."""
+        ni = len(self.img_seeds["px"])
+        if ni:
+            sr = self.backend.update_seeds(abi.SeedsJob(self.cam, np.stack(self.poses_est), np.arange(len(self.poses_est), dtype=np.int32),
+                                                        dict(self.img_seeds, cur_frame=np.full(ni, k, np.int32)), None, n_pyr_levels=self.o.n_pyr_levels))
+            stt = sr["pt_status"]
+            self.img_converged += int((stt == abi.SEED_CONVERGED).sum())
+            keep_s = ~((stt == abi.SEED_CONVERGED) | (stt == abi.SEED_NAN))
+            self.img_seeds = {key: v[keep_s] for key, v in self.img_seeds.items()}
+            for key in ("a", "b", "mu", "sigma2"):
+                self.img_seeds[key] = sr["pt_" + key][keep_s]
+        if fr.is_kf:
+            fresh = self.new_image_seeds(k, fr.px_new[fr.kept])
+            self.img_seeds = {key: np.concatenate([v, fresh[key]]) for key, v in self.img_seeds.items()}
+        fr.rec.update(n_image_seeds=len(self.img_seeds["px"]), n_image_seeds_converged=self.img_converged)
+
+    def align_job_of(self, k, fr):
+        """frame k + 1's alignment job from frame k's selection and the tables as they stand at this point of frame k.  "device" builds
+        it there (plsvo_candidates_align_build .. _compose, DESIGN.md 3.20: no selection fetch, no pose fetch, no host arithmetic ahead
+        of the alignment; -> True); "host" restates the same job here in scalar float64 (align_job_host), so the two differ in
+        transport alone and agree in every record"""
+        o, cm, pr = self.o, self.mt.cm, fr.pr
+        if o.align == "device":
+            self.backend.align_build(k, k + 1, o.max_level, o.min_level, *self.align_caps)
+            return True
+        return align_job_host(self.cam, o.max_level, o.min_level, fr.frame_sel, pr.pt_keep, pr.seg_keep, cm["pt_type"], cm["seg_type"], cm["pt_pos"], cm["seg_spos"], cm["seg_epos"],
+                              pr.T, k, k + 1)
+
+    def queue_next_align(self, k, fr):
+        """align="host" | "device": step 1 of every frame but the first is fed by the frame before it: the features of the alignment job
+        are the previous frame's SELECTION with the pose optimiser's keep masks, the landmarks' positions and types as the tables hold
+        them when that frame is done -- behind the structure optimisation and an insertion, behind everything that moves a landmark in
+        the frame, ahead of a compaction (insert_keyframe queues it there) --, the reference pose the optimised one.  Tables that wait
+        for a restage no longer say what the harness's own do: the frame behind them is staged by the host as without the flag."""
+        if self.o.align and self.rs.next_align is None and k + 1 < self.n_frames and not self.mt.dirty:
+            self.rs.next_align = self.align_job_of(k, fr)
 
 
 def pose_errors(result, seq):

@@ -1899,6 +1899,119 @@ int plsvo_seeds_keyframe_detect(plsvo_ctx* ctx, int n, const plsvo_detect_params
 int plsvo_seeds_keyframe_fetch(plsvo_ctx* ctx, int n, plsvo_seed_kf_report* out);
 
 /* ------------------------------------------------------------------------------------------ */
+/* bootstrap: pyramidal KLT track of the first keyframe's corners.  Replaces  */
+/* KltHomographyInit::addFirstFrame (src/initialization.cpp:40-54), ::addSecondFrame up to the */
+/* disparity gate (:56-69), the list building of detectFeatures (:147-167) and trackKlt        */
+/* (:170-215) with [ext] cv::calcOpticalFlowPyrLK, cv::buildOpticalFlowPyramid / pyrDown /     */
+/* Scharr restated from upstream (tests/np_klt.py).  Stops in front of computeHomography       */
+/* (:71-116).  Not covered: line detection, the error output's values, the C++ adapter.        */
+/* ------------------------------------------------------------------------------------------ */
+#define PLSVO_KLT_FAILURE     0   /* first frame: fewer than PLSVO_KLT_MIN_FIRST points (:44), nothing kept; second frame: n_tracked < init_min_tracked (:62) */
+#define PLSVO_KLT_NO_KEYFRAME 1   /* median disparity < init_min_disparity (:68) */
+#define PLSVO_KLT_TRACKED     2   /* both gates passed: the lists are ready for computeHomography */
+#define PLSVO_KLT_INACTIVE    3   /* no first frame holds for the stream (never given, failed or dropped): nothing was done */
+#define PLSVO_KLT_DROPPED     4   /* first frame: more points than cap_pts, nothing kept */
+#define PLSVO_KLT_FIRST       5   /* addFirstFrame's SUCCESS: px_ref = px_cur = the points, nothing tracked yet */
+#define PLSVO_KLT_MIN_FIRST   100
+#define PLSVO_KLT_MAX_LEVEL   4   /* trackKlt's maxLevel (:190): at most five levels */
+/* exit taken by calcOpticalFlowPyrLK at one level of one point (plsvo_klt_track_points) */
+#define PLSVO_KLT_EXIT_NONE      0   /* the level does not exist (above the top level) */
+#define PLSVO_KLT_EXIT_PREV_OOR  1   /* the window of prev lies outside the level */
+#define PLSVO_KLT_EXIT_FLAT      2   /* minEig < min_eig or D < FLT_EPSILON */
+#define PLSVO_KLT_EXIT_ITER_OOR  3   /* the window of next left the level in the iteration `iters` (0-based) */
+#define PLSVO_KLT_EXIT_EPS       4   /* |delta|^2 <= eps^2 after `iters` iterations */
+#define PLSVO_KLT_EXIT_OSC       5   /* delta + previous delta below 0.01 in both coordinates: half a step back */
+#define PLSVO_KLT_EXIT_MAX_ITER  6   /* max_iter iterations */
+
+typedef struct plsvo_klt_cfg {
+  int32_t streams, cap_pts;          /* resident streams; points a stream's lists may hold */
+  int32_t win;                       /* 30 (klt_win_size, :179); anything else is refused */
+  int32_t max_level;                 /* 4 (:190), 0 .. PLSVO_KLT_MAX_LEVEL */
+  int32_t max_iter;                  /* 30 (:180), 1 .. 255 */
+  int32_t reserved0;
+  double  eps;                       /* 0.001 (:181): the iteration stops at |delta|^2 <= eps * eps */
+  double  min_eig;                   /* 1e-4, calcOpticalFlowPyrLK's default minEigThreshold */
+} plsvo_klt_cfg;
+
+/* One stream's first frame.  The list is the corners -- px = ((float)x, (float)y), f = cam2world(px) -- followed by the extra points
+ * with the bearings given: the endpoint / midpoint / endpoint triples of :159-167 for segments the host detected (the midpoint's
+ * bearing is (sf + ef) / 2, no cam2world result). */
+typedef struct plsvo_klt_first {
+  int32_t active;                    /* 0: the stream is not touched at all */
+  int32_t slot;                      /* the pyramid slot of the reference frame; the caller leaves its level 0 as it is until the bootstrap ends */
+  plsvo_pinhole cam;
+  const plsvo_corner* d_corners;     /* DEVICE, the stream's records as plsvo_hip_detect_fast_dev left them (cell order), or NULL */
+  const int32_t* d_count;            /* DEVICE, their count (required with d_corners) */
+  int32_t n_host, n_extra;
+  const float* host_px;              /* n_host x 2, read when d_corners is NULL */
+  const float* extra_px;             /* n_extra x 2 */
+  const double* extra_f;             /* n_extra x 3 */
+} plsvo_klt_first;
+
+typedef struct plsvo_klt_second { int32_t active, cur_slot; } plsvo_klt_second;
+typedef struct plsvo_klt_params {
+  int32_t init_min_tracked;          /* Config::initMinTracked(), 40 */
+  int32_t reserved0;
+  double  init_min_disparity;        /* Config::initMinDisparity(), 40.0 */
+} plsvo_klt_params;
+
+/* What the last call that touched a stream did; PLSVO_KLT_INACTIVE and zeros after plsvo_klt_reserve. */
+typedef struct plsvo_klt_report {
+  int32_t result;                    /* PLSVO_KLT_* */
+  int32_t n_before, n_after;         /* list length in front of and behind the call (first frame: points offered, points kept) */
+  int32_t levels;                    /* pyramid levels the tracker used (top level + 1) */
+  double  median_disparity;          /* vk::getMedian(disparities_): the element of rank n_after / 2; 0 with an empty list and on a first frame */
+  int32_t n_calls;                   /* second-frame calls since the first frame */
+  int32_t reserved0;
+} plsvo_klt_report;
+
+/* A stream's lists in host memory (plsvo_klt_fetch_tracks; every pointer may be NULL) or on the device (plsvo_klt_tracks_dev: the
+ * arrays of ALL streams, stream s from element s * cap_pts, valid for the first count[s] entries once the launches in flight have run). */
+typedef struct plsvo_klt_tracks {
+  int32_t n, cap_pts;
+  float* px_ref; float* px_cur;      /* x 2 */
+  double* f_ref; double* f_cur;      /* x 3; f_cur and disparity are valid behind a second frame */
+  double* disparity;
+  int32_t* count;                    /* tracks_dev only: per stream */
+} plsvo_klt_tracks;
+
+/* reserve: lays out the lists and the KLT pyramid store (levels 1 .. L of two frames per stream, OpenCV's pyrDown of level 0 -- not the
+ *   slots' half-sampled levels) for the configured pyramids' level-0 size; every stream starts PLSVO_KLT_INACTIVE.  PLSVO_E_STATE
+ *   without configured pyramids; PLSVO_E_INVALID for NULL cfg, streams or cap_pts below 1, win other than 30, max_level outside
+ *   0 .. PLSVO_KLT_MAX_LEVEL, max_iter outside 1 .. 255, eps or min_eig negative or not finite.
+ * first_frame: ENQUEUE ONLY after the copy of the host lists: the lists of the active streams and the KLT pyramid of their slots.
+ *   Fewer than PLSVO_KLT_MIN_FIRST points: PLSVO_KLT_FAILURE; more than cap_pts: PLSVO_KLT_DROPPED; nothing is kept in both cases.
+ * second_frame: ENQUEUE ONLY, for any subset of the batch: the KLT pyramid of cur_slot, the track of every list entry from its px_cur
+ *   (OPTFLOW_USE_INITIAL_FLOW), then per stream the stable compaction of px_ref / px_cur / f_ref over status == 0, f_cur, the
+ *   disparities, their median and the gates.  The lists are left compacted whatever the result, so the next call starts from the kept px_cur.
+ * Both: PLSVO_E_STATE without a reserve or when the pyramids were reconfigured since; PLSVO_E_INVALID (nothing written or enqueued)
+ *   for another n than reserved, NULL in / params with n > 0 and, for an active stream, a slot outside the pyramids, a camera that is
+ *   not the pyramids' level-0 size or has a non-finite or zero focal length, d_corners without d_count, a negative count, a NULL
+ *   array with a non-zero count, a negative init_min_tracked or a non-finite init_min_disparity.
+ * fetch: synchronises; every stream's report.  PLSVO_E_STATE without a reserve, PLSVO_E_INVALID for another n or NULL out.
+ * fetch_tracks: synchronises; out->n and the arrays that are not NULL (room for cap_pts entries).  PLSVO_E_INVALID for a stream
+ *   outside the batch or NULL out.  tracks_dev: no synchronisation.
+ * The pyramid launches are timed under PLSVO_K_HALFSAMPLE, the track under PLSVO_K_MATCH, the list launches under PLSVO_K_NEWCAND. */
+int plsvo_klt_reserve(plsvo_ctx* ctx, const plsvo_klt_cfg* cfg);
+int plsvo_klt_first_frame(plsvo_ctx* ctx, int n, const plsvo_klt_first* in);
+int plsvo_klt_second_frame(plsvo_ctx* ctx, int n, const plsvo_klt_second* in, const plsvo_klt_params* params);
+int plsvo_klt_fetch(plsvo_ctx* ctx, int n, plsvo_klt_report* report);
+int plsvo_klt_fetch_tracks(plsvo_ctx* ctx, int stream, plsvo_klt_tracks* out);
+int plsvo_klt_tracks_dev(plsvo_ctx* ctx, plsvo_klt_tracks* out);
+/* Host only, no ctx: the top level L of calcOpticalFlowPyrLK's pyramid for a level-0 size (the first level whose next size has
+ * w <= win or h <= win, at most max_level) and the sizes of levels 0 .. L (w, h: room for PLSVO_KLT_MAX_LEVEL + 1, may be NULL).
+ * Returns L, or PLSVO_E_INVALID for a size or win below 1 or max_level outside 0 .. PLSVO_KLT_MAX_LEVEL. */
+int plsvo_klt_levels(int width, int height, int win, int max_level, int32_t* w, int32_t* h);
+/* Diagnostics (tests; like plsvo_hip_detect_stages for the detector).  download_level: level 1 .. L of a stream's KLT pyramid,
+ * which = 0 the reference frame's, 1 the last current frame's; synchronises; PLSVO_E_INVALID for a level the store does not hold.
+ * track_points: STATELESS -- builds the KLT pyramids of two slots in a scratch store and runs the production track kernel on n
+ * arbitrary prev / next points (x 2 floats each) under cfg (streams and cap_pts are not read); next_out: n x 2, status: n bytes,
+ * exit_code / iters: n x (PLSVO_KLT_MAX_LEVEL + 1) bytes indexed by level.  Needs no reserve and leaves the resident lists alone. */
+int plsvo_klt_download_level(plsvo_ctx* ctx, int stream, int which, int level, uint8_t* out);
+int plsvo_klt_track_points(plsvo_ctx* ctx, const plsvo_klt_cfg* cfg, int ref_slot, int cur_slot, int n, const float* prev, const float* next_in,
+                           float* next_out, uint8_t* status, uint8_t* exit_code, uint8_t* iters);
+
+/* ------------------------------------------------------------------------------------------ */
 /* multi-GPU: gather of per-stream pose records (new; the reference is single-process)         */
 /* ------------------------------------------------------------------------------------------ */
 

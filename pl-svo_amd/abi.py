@@ -57,6 +57,46 @@ def detect_params(cell_size=25, n_levels=3, fast_threshold=20, detection_thresho
     return DetectParams(int(cell_size), int(n_levels), int(fast_threshold), 0, float(detection_threshold))
 
 
+# bootstrap KLT (plsvo_klt_*): result codes, the exits plsvo_klt_track_points reports per level
+KLT_FAILURE, KLT_NO_KEYFRAME, KLT_TRACKED, KLT_INACTIVE, KLT_DROPPED, KLT_FIRST = 0, 1, 2, 3, 4, 5
+KLT_MIN_FIRST, KLT_MAX_LEVEL = 100, 4
+KLT_EXIT_NONE, KLT_EXIT_PREV_OOR, KLT_EXIT_FLAT, KLT_EXIT_ITER_OOR, KLT_EXIT_EPS, KLT_EXIT_OSC, KLT_EXIT_MAX_ITER = 0, 1, 2, 3, 4, 5, 6
+c_float_p = C.POINTER(C.c_float)
+
+
+class KltCfg(C.Structure):
+    """plsvo_klt_cfg (defaults: trackKlt's constants, src/initialization.cpp:179-190)"""
+    _fields_ = [("streams", C.c_int32), ("cap_pts", C.c_int32), ("win", C.c_int32), ("max_level", C.c_int32), ("max_iter", C.c_int32),
+                ("reserved0", C.c_int32), ("eps", C.c_double), ("min_eig", C.c_double)]
+
+
+def klt_cfg(streams=1, cap_pts=1, win=30, max_level=4, max_iter=30, eps=0.001, min_eig=1e-4):
+    return KltCfg(int(streams), int(cap_pts), int(win), int(max_level), int(max_iter), 0, float(eps), float(min_eig))
+
+
+class KltFirst(C.Structure):
+    _fields_ = [("active", C.c_int32), ("slot", C.c_int32), ("cam", Pinhole), ("d_corners", C.c_void_p), ("d_count", C.c_void_p),
+                ("n_host", C.c_int32), ("n_extra", C.c_int32), ("host_px", c_float_p), ("extra_px", c_float_p), ("extra_f", c_double_p)]
+
+
+class KltSecond(C.Structure):
+    _fields_ = [("active", C.c_int32), ("cur_slot", C.c_int32)]
+
+
+class KltParams(C.Structure):
+    _fields_ = [("init_min_tracked", C.c_int32), ("reserved0", C.c_int32), ("init_min_disparity", C.c_double)]
+
+
+class KltReport(C.Structure):
+    _fields_ = [("result", C.c_int32), ("n_before", C.c_int32), ("n_after", C.c_int32), ("levels", C.c_int32), ("median_disparity", C.c_double),
+                ("n_calls", C.c_int32), ("reserved0", C.c_int32)]
+
+
+class KltTracks(C.Structure):
+    _fields_ = [("n", C.c_int32), ("cap_pts", C.c_int32), ("px_ref", c_float_p), ("px_cur", c_float_p), ("f_ref", c_double_p), ("f_cur", c_double_p),
+                ("disparity", c_double_p), ("count", c_i32_p)]
+
+
 class AlignIn(C.Structure):
     _fields_ = [("ref_slot", C.c_int32), ("cur_slot", C.c_int32), ("cam", Pinhole),
                 ("max_level", C.c_int32), ("min_level", C.c_int32), ("n_iter", C.c_int32),

@@ -39,6 +39,8 @@ SYMBOLS = [
     "plsvo_candidates_align_build_kf", "plsvo_candidates_track_gate", "plsvo_candidates_gate_fetch", "plsvo_candidates_gate_poses_dev",
     "plsvo_seeds_reserve", "plsvo_seeds_capacity", "plsvo_seeds_stage", "plsvo_seeds_update", "plsvo_seeds_update_fetch", "plsvo_seeds_keyframe", "plsvo_seeds_fetch_lists",
     "plsvo_seeds_fetch_rows", "plsvo_seeds_commit_rows", "plsvo_seeds_keyframe_detect", "plsvo_seeds_keyframe_fetch",
+    "plsvo_klt_reserve", "plsvo_klt_first_frame", "plsvo_klt_second_frame", "plsvo_klt_fetch", "plsvo_klt_fetch_tracks", "plsvo_klt_tracks_dev",
+    "plsvo_klt_levels", "plsvo_klt_download_level", "plsvo_klt_track_points",
     "plsvo_chain_stage", "plsvo_chain_run", "plsvo_chain_fetch", "plsvo_frame_step_batch", "plsvo_chain_poses_dev",
     "plsvo_pack_pose_records", "plsvo_fetch_pose_records", "plsvo_gather_poses",
     "plsvo_hip_set_profiling", "plsvo_hip_kernel_time", "plsvo_hip_reset_profiling",
@@ -72,6 +74,16 @@ def detect_cell(cols, cell_size, px_x, px_y):
     if k < 0:
         raise PlsvoError(k, "detect_cell: cols and cell_size must be >= 1, the pixel finite and not negative")
     return k
+
+
+def klt_levels(width, height, win=30, max_level=4):
+    """plsvo_klt_levels (host only): the sizes [(w, h)] of levels 0 .. L of calcOpticalFlowPyrLK's pyramid"""
+    w = (C.c_int32 * (abi.KLT_MAX_LEVEL + 1))()
+    h = (C.c_int32 * (abi.KLT_MAX_LEVEL + 1))()
+    L = lib().plsvo_klt_levels(int(width), int(height), int(win), int(max_level), w, h)
+    if L < 0:
+        raise PlsvoError(L, "klt_levels: width, height and win must be >= 1, max_level 0 .. 4")
+    return [(w[l], h[l]) for l in range(L + 1)]
 
 
 class PlsvoError(RuntimeError):
@@ -213,6 +225,16 @@ def lib():
         "plsvo_seeds_commit_rows": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.SeedRows)]),
         "plsvo_seeds_keyframe_detect": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.DetectParams), C.POINTER(abi.SeedKfDetect)]),
         "plsvo_seeds_keyframe_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.SeedKfReport)]),
+        "plsvo_klt_reserve": (C.c_int, [ctxp, C.POINTER(abi.KltCfg)]),
+        "plsvo_klt_first_frame": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.KltFirst)]),
+        "plsvo_klt_second_frame": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.KltSecond), C.POINTER(abi.KltParams)]),
+        "plsvo_klt_fetch": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.KltReport)]),
+        "plsvo_klt_fetch_tracks": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.KltTracks)]),
+        "plsvo_klt_tracks_dev": (C.c_int, [ctxp, C.POINTER(abi.KltTracks)]),
+        "plsvo_klt_levels": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, abi.c_i32_p, abi.c_i32_p]),
+        "plsvo_klt_download_level": (C.c_int, [ctxp, C.c_int, C.c_int, C.c_int, abi.c_u8_p]),
+        "plsvo_klt_track_points": (C.c_int, [ctxp, C.POINTER(abi.KltCfg), C.c_int, C.c_int, C.c_int, abi.c_float_p, abi.c_float_p, abi.c_float_p, abi.c_u8_p,
+                                             abi.c_u8_p, abi.c_u8_p]),
         "plsvo_update_seeds": (C.c_int, [ctxp, C.POINTER(abi.SeedsIn), C.POINTER(abi.SeedsOut)]),
         "plsvo_trajectory_record": (C.c_int, [abi.c_double_p, abi.c_double_p, abi.c_double_p]),
         "plsvo_chain_stage": (C.c_int, [ctxp, C.c_int, C.POINTER(abi.ChainIn), C.POINTER(abi.ChainParams)]),
@@ -424,6 +446,102 @@ class Context:
         self._chk(self.L.plsvo_hip_detect_stages(self.h, int(slot), int(level), int(fast_threshold), score.ctypes.data_as(abi.c_u8_p),
                                                  surv.ctypes.data_as(abi.c_u8_p)))
         return score, surv
+
+    # ---- bootstrap: KLT track of the first keyframe's corners ----
+    def klt_reserve(self, streams, cap_pts, win=30, max_level=4, max_iter=30, eps=0.001, min_eig=1e-4):
+        """plsvo_klt_reserve: lists and KLT pyramid store for `streams` streams of the configured pyramids"""
+        cfg = abi.klt_cfg(streams, cap_pts, win, max_level, max_iter, eps, min_eig)
+        self._chk(self.L.plsvo_klt_reserve(self.h, C.byref(cfg)))
+        self._klt_n, self._klt_cap = int(streams), int(cap_pts)
+        self._klt_sizes = klt_levels(self.width, self.height, win, max_level)
+
+    def klt_first_frame(self, frames):
+        """plsvo_klt_first_frame (enqueue only): per reserved stream None (not touched) or a dict of slot, cam (abi.Pinhole) and either
+        d_corners + d_count (device pointers to the stream's plsvo_corner records and their count) or px (n x 2 float32), plus optional
+        extra_px (m x 2 float32) and extra_f (m x 3 float64) appended behind them"""
+        n = len(frames)
+        arr = (abi.KltFirst * max(n, 1))()
+        keep = []
+        for a, f in zip(arr, frames):
+            if f is None:
+                continue
+            a.active, a.slot, a.cam = 1, int(f["slot"]), f["cam"]
+            if f.get("d_corners") is not None:
+                a.d_corners, a.d_count = f["d_corners"], f.get("d_count")
+            else:
+                px = np.ascontiguousarray(f.get("px", np.zeros((0, 2))), dtype=np.float32).reshape(-1, 2)
+                a.n_host, a.host_px = len(px), px.ctypes.data_as(abi.c_float_p)
+                keep.append(px)
+            if f.get("extra_px") is not None:
+                epx = np.ascontiguousarray(f["extra_px"], dtype=np.float32).reshape(-1, 2)
+                ef = np.ascontiguousarray(f["extra_f"], dtype=np.float64).reshape(-1, 3)
+                assert len(epx) == len(ef)
+                a.n_extra, a.extra_px, a.extra_f = len(epx), epx.ctypes.data_as(abi.c_float_p), ef.ctypes.data_as(abi.c_double_p)
+                keep += [epx, ef]
+        self._chk(self.L.plsvo_klt_first_frame(self.h, n, arr))
+
+    def klt_second_frame(self, cur_slots, init_min_tracked=40, init_min_disparity=40.0):
+        """plsvo_klt_second_frame (enqueue only): per reserved stream None (sits the call out) or the slot of its current frame"""
+        n = len(cur_slots)
+        arr = (abi.KltSecond * max(n, 1))()
+        for a, sl in zip(arr, cur_slots):
+            if sl is not None:
+                a.active, a.cur_slot = 1, int(sl)
+        pr = abi.KltParams(int(init_min_tracked), 0, float(init_min_disparity))
+        self._chk(self.L.plsvo_klt_second_frame(self.h, n, arr, C.byref(pr)))
+
+    def klt_fetch(self):
+        """plsvo_klt_fetch (synchronises): per stream a dict of abi.KltReport's fields"""
+        n = self._klt_n
+        outs = (abi.KltReport * max(n, 1))()
+        self._chk(self.L.plsvo_klt_fetch(self.h, n, outs))
+        return [{f: getattr(o, f) for f, _ in abi.KltReport._fields_ if f != "reserved0"} for o in outs[:n]]
+
+    def klt_fetch_tracks(self, stream):
+        """plsvo_klt_fetch_tracks (synchronises): the stream's lists as a dict of px_ref, px_cur (n x 2 float32), f_ref, f_cur (n x 3) and
+        disparity (n) -- f_cur and disparity are valid behind a second frame"""
+        cap = self._klt_cap
+        a = dict(px_ref=np.zeros((cap, 2), np.float32), px_cur=np.zeros((cap, 2), np.float32), f_ref=np.zeros((cap, 3)), f_cur=np.zeros((cap, 3)),
+                 disparity=np.zeros(cap))
+        t = abi.KltTracks()
+        t.px_ref, t.px_cur = a["px_ref"].ctypes.data_as(abi.c_float_p), a["px_cur"].ctypes.data_as(abi.c_float_p)
+        t.f_ref, t.f_cur = a["f_ref"].ctypes.data_as(abi.c_double_p), a["f_cur"].ctypes.data_as(abi.c_double_p)
+        t.disparity = a["disparity"].ctypes.data_as(abi.c_double_p)
+        self._chk(self.L.plsvo_klt_fetch_tracks(self.h, int(stream), C.byref(t)))
+        return {k: v[:t.n].copy() for k, v in a.items()}
+
+    def klt_tracks_dev(self):
+        """plsvo_klt_tracks_dev: the device addresses of every stream's lists (stream s from element s * cap_pts) and of the counts"""
+        t = abi.KltTracks()
+        self._chk(self.L.plsvo_klt_tracks_dev(self.h, C.byref(t)))
+        out = {f: C.cast(getattr(t, f), C.c_void_p).value for f in ("px_ref", "px_cur", "f_ref", "f_cur", "disparity", "count")}
+        out["streams"], out["cap_pts"] = t.n, t.cap_pts
+        return out
+
+    def klt_download_level(self, stream, which, level):
+        """plsvo_klt_download_level: level 1 .. L of a stream's KLT pyramid (which: 0 = reference frame, 1 = last current frame)"""
+        sizes = self._klt_sizes
+        w, h = sizes[level] if 0 <= level < len(sizes) else (1, 1)
+        out = np.zeros((h, w), dtype=np.uint8)
+        self._chk(self.L.plsvo_klt_download_level(self.h, int(stream), int(which), int(level), out.ctypes.data_as(abi.c_u8_p)))
+        return out
+
+    def klt_track_points(self, ref_slot, cur_slot, prev, nxt, win=30, max_level=4, max_iter=30, eps=0.001, min_eig=1e-4):
+        """plsvo_klt_track_points (stateless diagnostic): the production track kernel on arbitrary prev / next points (n x 2 float32) of two
+        slots -> dict of next (n x 2), status (n), exit and iters (n x 5, indexed by level)"""
+        prev = np.ascontiguousarray(prev, dtype=np.float32).reshape(-1, 2)
+        nxt = np.ascontiguousarray(nxt, dtype=np.float32).reshape(-1, 2)
+        n = len(prev)
+        assert len(nxt) == n
+        nv = abi.KLT_MAX_LEVEL + 1
+        out = dict(next=np.zeros((max(n, 1), 2), np.float32), status=np.zeros(max(n, 1), np.uint8), exit=np.zeros((max(n, 1), nv), np.uint8),
+                   iters=np.zeros((max(n, 1), nv), np.uint8))
+        cfg = abi.klt_cfg(1, 1, win, max_level, max_iter, eps, min_eig)
+        self._chk(self.L.plsvo_klt_track_points(self.h, C.byref(cfg), int(ref_slot), int(cur_slot), n, prev.ctypes.data_as(abi.c_float_p),
+                                                nxt.ctypes.data_as(abi.c_float_p), out["next"].ctypes.data_as(abi.c_float_p),
+                                                out["status"].ctypes.data_as(abi.c_u8_p), out["exit"].ctypes.data_as(abi.c_u8_p),
+                                                out["iters"].ctypes.data_as(abi.c_u8_p)))
+        return {k: v[:n] for k, v in out.items()}
 
     # ---- sparse image alignment ----
     def align_set_trace(self, max_records):

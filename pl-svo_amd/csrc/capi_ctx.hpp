@@ -62,6 +62,10 @@ hipError_t launch_rectify(const uint8_t* raw, size_t raw_pitch, int stride, int 
 hipError_t launch_detect_fast(const DetectLaunch& a, int n_slots, hipStream_t stream);
 hipError_t launch_detect_stages(const DetectLaunch& a, hipStream_t stream);
 hipError_t launch_detect_compact(unsigned long long* keys, int n_cells, plsvo_corner* corners, int32_t* counts, int n_slots, hipStream_t stream);
+hipError_t launch_klt_pyrdown(const KltBatchDev& b, int level, int which, hipStream_t stream);   // klt_device.hpp, in seeds_kernels.hip
+hipError_t launch_klt_first(const KltBatchDev& b, int n_jobs, hipStream_t stream);
+hipError_t launch_klt_track(const KltBatchDev& b, int max_pts, hipStream_t stream);
+hipError_t launch_klt_commit(const KltBatchDev& b, hipStream_t stream);
 }  // namespace plsvo_hip
 
 using namespace plsvo_hip;
@@ -318,6 +322,15 @@ struct plsvo_ctx {
   // (sk_d_occ, sk_d_slots: per position of the launch), the reports (sk_d_report: per stream, zeroed at plsvo_seeds_stage)
   bool sk_have_report = false;
   DevBuf sk_d_occ, sk_d_slots, sk_d_report;
+  // bootstrap KLT (plsvo_klt_*, capi_klt.hpp): the reserve's configuration, the level-0 size and slab it was laid out for, per stream the
+  // reference slot of its first frame; the KLT pyramid store (kl_d_store), the lists / results / records (kl_d_lists), a call's rows and
+  // host lists (kl_d_in), the diagnostic's store and arrays (kl_d_diag)
+  bool kl_reserved = false;
+  plsvo_klt_cfg kl_cfg{};
+  const uint8_t* kl_pyr_base = nullptr;
+  std::vector<int> kl_ref_slot;
+  DevBuf kl_d_store, kl_d_lists, kl_d_in, kl_d_diag;
+  KltBatchDev kl_b{};
   unsigned long long run_seq = 0, a_run_seq = 0, p_run_seq = 0, ch_run_seq = 0;   // which resident batch ran last, 0 = not since it was staged (plsvo_pack_pose_records)
   unsigned long long ch_stage_seq = 0;      // when the frame step was staged, on the same count: a pose-optimisation batch that ran later describes the streams now
 

@@ -121,6 +121,7 @@ extern "C" void plsvo_hip_destroy(plsvo_ctx* c) {
   c->p_w.release(); c->ch_w.release(); c->cs_w.release();
   for (auto& r : c->rect) r.map.release();
   c->det_keys.release(); c->det_occ.release(); c->det_corners.release(); c->det_counts.release(); c->det_stage.release(); c->sk_d_occ.release(); c->sk_d_slots.release(); c->sk_d_report.release();
+  c->kl_d_store.release(); c->kl_d_lists.release(); c->kl_d_in.release(); c->kl_d_diag.release();
   for (int k = 0; k < 2; ++k) { if (c->pinned[k]) (void)hipHostFree(c->pinned[k]); if (c->pinned_done[k]) (void)hipEventDestroy(c->pinned_done[k]); }
   for (int k = 0; k < 2; ++k) { if (c->pyr_pinned[k]) (void)hipHostFree(c->pyr_pinned[k]); if (c->pyr_pinned_done[k]) (void)hipEventDestroy(c->pyr_pinned_done[k]); }
   if (c->dl_pinned) (void)hipHostFree(c->dl_pinned);
@@ -2218,3 +2219,6 @@ extern "C" int plsvo_hip_reset_profiling(plsvo_ctx* c) {
   for (int k = 0; k < PLSVO_K_COUNT; ++k) { c->ev_ms[k] = 0.0; c->ev_launches[k] = 0; }
   return PLSVO_OK;
 }
+
+// ---- bootstrap KLT (plsvo_klt_*) ----
+#include "capi_klt.hpp"

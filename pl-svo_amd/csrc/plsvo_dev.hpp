@@ -659,6 +659,39 @@ struct SeedStartBatchDev {
   SeedStartReportDev* report;       // per STREAM
 };
 
+// bootstrap KLT (klt_device.hpp, include/plsvo_hip.h plsvo_klt_*).  The KLT pyramids are OpenCV's pyrDown of a slot's level 0, kept in a
+// store of their own: pyramid k at store + k * pyr_bytes, level l >= 1 at + off[l] (256-byte aligned, rows tight); stream s owns
+// pyramid 2 s (reference frame) and 2 s + 1 (current frame).  Lists are stream-major with cap_pts entries per stream.
+constexpr int kKltWin = 30, kKltLevels = PLSVO_KLT_MAX_LEVEL + 1, kKltWaves = 4;
+struct KltLevelsDev {
+  int n_lv;                          // top level + 1
+  int w[kKltLevels], h[kKltLevels];
+  unsigned int off[kKltLevels];      // off[0]: level 0 inside a pyramid SLOT
+  unsigned long long pyr_bytes;
+};
+struct KltRowDev { int stream, ref_slot, cur_slot, reserved0; };   // one launch row: an active stream
+struct KltStreamDev { double fx, fy, cx, cy; int started, n_calls; };
+struct KltFirstDev {
+  int stream, n_host, n_extra, reserved0;
+  double fx, fy, cx, cy;
+  const plsvo_corner* d_corners; const int32_t* d_count;
+  long long host_at, extra_at;       // the stream's entries in the uploaded arrays
+};
+struct KltBatchDev {
+  const uint8_t* pyr; unsigned long long slot_bytes;
+  uint8_t* store;
+  KltLevelsDev lv;
+  const KltRowDev* rows; int n_rows;
+  int cap_pts, max_iter, min_tracked;
+  double eps2, min_eig, min_disparity;
+  float* px_ref; float* px_cur; double* f_ref; double* f_cur; double* disparity;
+  float* next; uint8_t* status;      // the track launch's results, per list entry
+  int* count; KltStreamDev* st; unsigned long long* keys; plsvo_klt_report* report;
+  uint8_t* diag_exit; uint8_t* diag_iters;   // plsvo_klt_track_points only: kKltLevels per point
+  // a first frame's upload
+  const KltFirstDev* first; const float* host_px; const float* extra_px; const double* extra_f;
+};
+
 inline int detect_tiles(int w, int h, int* tiles_x) {
   *tiles_x = (w + kDetTileW - 1) / kDetTileW;
   return *tiles_x * ((h + kDetTileH - 1) / kDetTileH);

@@ -33,6 +33,7 @@
 #include "seedlist_device.hpp"   // and the seed lists kept resident beside them
 #include "structsel_device.hpp"  // and the structure optimisation of their least recently refined landmarks
 #include "alignjob_device.hpp"   // and the next frame's alignment job built from the selection
+#include "klt_device.hpp"        // and the bootstrap's KLT tracker, whose median is the keyframe stage's wave select
 
 namespace plsvo_hip {
 
@@ -572,6 +573,32 @@ hipError_t launch_map_align_kf_job(const AlignKfBatchDev& b, hipStream_t stream)
 hipError_t launch_map_track_gate(const TrackGateBatchDev& b, hipStream_t stream) {
   if (b.n_jobs <= 0) return hipSuccess;
   hipLaunchKernelGGL(map_track_gate_kernel, dim3((b.n_jobs + 63) / 64), dim3(64), 0, stream, b);
+  return hipGetLastError();
+}
+
+// ---- bootstrap KLT (klt_device.hpp) ----
+hipError_t launch_klt_pyrdown(const KltBatchDev& b, int level, int which, hipStream_t stream) {
+  const int work = ((b.lv.w[level] + 3) >> 2) * b.lv.h[level];
+  if (work <= 0 || b.n_rows <= 0) return hipSuccess;
+  hipLaunchKernelGGL(klt_pyrdown_kernel, dim3((work + 255) / 256, b.n_rows), dim3(256), 0, stream, b, level, which);
+  return hipGetLastError();
+}
+
+hipError_t launch_klt_first(const KltBatchDev& b, int n_jobs, hipStream_t stream) {
+  if (n_jobs <= 0) return hipSuccess;
+  hipLaunchKernelGGL(klt_first_kernel, dim3(n_jobs), dim3(256), 0, stream, b);
+  return hipGetLastError();
+}
+
+hipError_t launch_klt_track(const KltBatchDev& b, int max_pts, hipStream_t stream) {
+  if (max_pts <= 0 || b.n_rows <= 0) return hipSuccess;
+  hipLaunchKernelGGL(klt_track_kernel, dim3((max_pts + kKltWaves - 1) / kKltWaves, b.n_rows), dim3(kKltWaves * 64), 0, stream, b);
+  return hipGetLastError();
+}
+
+hipError_t launch_klt_commit(const KltBatchDev& b, hipStream_t stream) {
+  if (b.n_rows <= 0) return hipSuccess;
+  hipLaunchKernelGGL(klt_commit_kernel, dim3((b.n_rows + kKltWaves - 1) / kKltWaves), dim3(kKltWaves * 64), 0, stream, b);
   return hipGetLastError();
 }
 

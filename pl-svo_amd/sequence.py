@@ -285,6 +285,23 @@ class HipBackend:
         """FastDetector::detect on the frame in `slot` (plsvo_hip_detect_fast): abi.CORNER_DTYPE records in cell order"""
         return self.ctx.detect_fast(slot, 1, cell_size, n_levels, fast_threshold, detection_threshold, None if occupancy is None else occupancy[None])[0]
 
+    # ---- bootstrap: KLT track of the first keyframe's corners (plsvo_klt_*; one stream) ----
+    def klt_first_frame(self, slot, cam, px, extra_px=None, extra_f=None, cap_pts=None, max_level=4):
+        """addFirstFrame on the frame in `slot`: the lists from a host list of pixels (and extra points with their bearings)"""
+        n = len(px) + (0 if extra_px is None else len(extra_px))
+        self.ctx.klt_reserve(1, max(int(cap_pts or n), 1), max_level=max_level)
+        fx, fy, cx, cy, w, h = cam
+        self.ctx.klt_first_frame([dict(slot=slot, cam=abi.Pinhole(fx, fy, cx, cy, int(w), int(h)), px=px, extra_px=extra_px, extra_f=extra_f)])
+        return self.ctx.klt_fetch()[0]
+
+    def klt_second_frame(self, slot, init_min_tracked=40, init_min_disparity=40.0):
+        """addSecondFrame up to the disparity gate on the frame in `slot`: the report"""
+        self.ctx.klt_second_frame([slot], init_min_tracked, init_min_disparity)
+        return self.ctx.klt_fetch()[0]
+
+    def klt_tracks(self):
+        return self.ctx.klt_fetch_tracks(0)
+
 
 class HipChainBackend(HipBackend):
     """The same product backend with steps 1-4 of a frame -- alignment, reprojection, matching, pose optimisation -- as ONE resident
@@ -320,6 +337,24 @@ def make_sequence(seed, n_frames=6, W=320, H=240, n_pts=120, n_seg=30, step_scal
     return dict(images=images, cam=st.cam, poses_true=np.stack(poses), stream=st,
                 pt_pos=st.pt_pos_w, pt_px0=st.pt_px, pt_f0=st.pt_f,
                 seg_spos=st.seg_spos_w, seg_epos=st.seg_epos_w, seg_spx0=st.seg_spx, seg_epx0=st.seg_epx, seg_sf0=st.seg_sf, seg_ef0=st.seg_ef)
+
+
+def klt_bootstrap(backend, images, cam, init_min_tracked=40, init_min_disparity=40.0, detect=None, extra_px=None, extra_f=None, cap_pts=None, max_level=4):
+    """KltHomographyInit up to computeHomography (src/initialization.cpp:40-69): the first image's corners (FastDetector::detect on its
+    pyramid slot, `detect` = keyword arguments of backend.detect_corners) and the caller's extra points become the lists, then every
+    following image is a second frame until the result is TRACKED (ready for the homography) or FAILURE.  Returns (reports, tracks):
+    one report per frame played -- abi.KltReport's fields -- and the final lists (px_ref, px_cur, f_ref, f_cur, disparity).
+    backend: load_frames, detect_corners, klt_first_frame, klt_second_frame, klt_tracks."""
+    backend.load_frames(images)
+    corners = backend.detect_corners(0, **(detect or {}))
+    px = np.stack([corners["x"], corners["y"]], axis=1).astype(np.float32)
+    reports = [backend.klt_first_frame(0, cam, px, extra_px, extra_f, cap_pts, max_level)]
+    if reports[0]["result"] == abi.KLT_FIRST:
+        for k in range(1, len(images)):
+            reports.append(backend.klt_second_frame(k, init_min_tracked, init_min_disparity))
+            if reports[-1]["result"] in (abi.KLT_TRACKED, abi.KLT_FAILURE):
+                break
+    return reports, backend.klt_tracks()
 
 
 def _bearing(cam, px):

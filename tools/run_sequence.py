@@ -11,7 +11,9 @@ With --kf-select (off by default; needs mapping) the keyframe stage runs on the 
 frame plays the keyframe when FrameHandlerMono::needNewKf says so instead of every fifth, and the JSON line lists the keyframe frames.
 With --map-candidates (off by default) reprojection and matching take their candidates from the map-candidate stage (plsvo_candidates_*):
 the overlap keyframes' features, one visit per landmark, the closest-view observation as the reference patch.
-usage: python tools/run_sequence.py [--distortion k1,k2,p1,p2[,k3]] [--detect] [--kf-select] [--map-candidates] [--cell-select] [--kf-insert] [--seed-candidates] [--seeds-resident] [--image-seeds host|device] [--structopt-resident] [--compact room|always] [--keystage host|device] [--align host|device] [--relocalize host|device] [--lm-room N] [out.txt] [n_frames] [seed] [mapping 0|1]"""
+With --bootstrap-klt nothing of the above runs: the sequence's first frames play KltHomographyInit up to the homography on the device
+(sequence.klt_bootstrap: corners of frame 0, a KLT second frame per image until the disparity gate passes) and the reports are printed.
+usage: python tools/run_sequence.py [--bootstrap-klt] [--distortion k1,k2,p1,p2[,k3]] [--detect] [--kf-select] [--map-candidates] [--cell-select] [--kf-insert] [--seed-candidates] [--seeds-resident] [--image-seeds host|device] [--structopt-resident] [--compact room|always] [--keystage host|device] [--align host|device] [--relocalize host|device] [--lm-room N] [out.txt] [n_frames] [seed] [mapping 0|1]"""
 import importlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -80,6 +82,9 @@ if "--lm-room" in argv:                            # landmark rows reserved per 
     i = argv.index("--lm-room")
     lm_room = int(argv[i + 1])
     del argv[i:i + 2]
+bootstrap_klt = "--bootstrap-klt" in argv
+if bootstrap_klt:
+    argv.remove("--bootstrap-klt")
 sys.argv = sys.argv[:1] + argv
 
 out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "gpurun_out", "trajectory.txt")
@@ -89,6 +94,13 @@ mapping = bool(int(sys.argv[4])) if len(sys.argv) > 4 else True
 os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
 seq = seqm.make_sequence(seed, n_frames, 640, 480, 200, 80, total=0.35)      # 35 % of the scene depth + 0.09 rad over the whole run
 ctx = P.capi.Context(0)
+if bootstrap_klt:
+    # the synthetic plane is smooth between its landmarks: a FAST threshold of 7 finds the corners the default of 20 does not (as --image-seeds)
+    reports, tracks = seqm.klt_bootstrap(seqm.HipBackend(ctx), seq["images"], seq["cam"], detect=dict(fast_threshold=7, detection_threshold=2.0))
+    print(json.dumps({"bootstrap_klt": reports, "frames_played": len(reports), "tracks": len(tracks["px_ref"]),
+                      "disparity_min_max": [float(tracks["disparity"].min()), float(tracks["disparity"].max())] if len(tracks["disparity"]) else None}))
+    ctx.close()
+    sys.exit(0)
 rectify = None
 if distortion is not None:
     fx, fy, cx, cy, w, h = seq["cam"]
